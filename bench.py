@@ -8,14 +8,22 @@ reference) + ``Model.inference`` (DIGAT.inference, fp32) + dot-product logits.  
 before the timed region.  The corpus has the real scale of the data set the workload names (MIND-small: 65 238 news,
 MIND-large: 161 013) and no batch is visited twice inside the timed region.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload: N=1 -> BASELINE.json configs[1] (MIND-small default); N>1 -> configs[3]'s shape (MIND-large default), rows
 sharded over the ranks, the final all_gather of the scores inside the timed region.  ``--mode train`` times the
 DDP training step instead (trainer.py:71-105; RCCL gradient all-reduce).
 
-Rank 0 prints ONE JSON line (contract in the task statement) with these extra objects:
+A plain run does what the headline needs and no more: setup, pre-warm, warm-up, the K timed steps, the result line.  Its
+warm-up and timed steps take the same batches of the same seeded corpus every run, and ``--dump-outputs DIR`` writes what
+the last timed step returned (rank 0's scores of that batch) to DIR/scores.npy (float32), so that two builds can be compared
+output for output.  The AUC matches are not run (the metric says so); ``--full`` runs them.
+
+``--full`` adds everything else: the per-kernel profile of the timed region and the untimed profiling passes behind the
+rooflines, the oracle / reference checks, the extra workloads, precisions and batch sizes, the training step, the end-to-end
+run, the one-GPU reference of a multi-GPU run and the full result document (bench_detail.json).  Rank 0 prints ONE JSON line
+(metric, value, unit, ms_per_step, ...); with ``--full`` it carries these extra objects:
   roofline         the dominant kernel of the step, timed live with HIP events over the timed region
   roofline_xattn   the fused Eq. 8 kernel of the user graph against the HBM roofline (what north_star asks for)
   cpu_baseline     the oracle (unfused reference algorithm, torch-CPU) on a bounded sample, N=1 only
@@ -81,9 +89,9 @@ def parse_args():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--mode", default="infer", choices=["infer", "train", "e2e"],
                     help="infer: dev scoring (the metric); train: the DDP training step (trainer.py:71-105); e2e: only the end-to-end "
-                         "dev run (title tokens -> rank file), which infer also appends at N = 1")
+                         "dev run (title tokens -> rank file), which infer --full also appends at N = 1")
     ap.add_argument("--e2e-impressions", type=int, default=MIND_SMALL_DEV_IMPRESSIONS,
-                    help="impressions of the end-to-end dev run (MIND-small dev: 73 152; 0 = skip it)")
+                    help="impressions of the end-to-end dev run of --mode e2e and --full (MIND-small dev: 73 152; 0 = skip it)")
     ap.add_argument("--batch", type=int, default=4096,
                     help="rows per step = rows per launch set (util.LAUNCH_ROWS; the reference's dev batch is batch_size*16 = 1024 rows, "
                          "main.py:42: sized for a 24 GB card, rows are independent)")
@@ -91,9 +99,9 @@ def parse_args():
                     help="auto: mind-small-default on one GPU (BASELINE configs[1]), mind-large-default on several (configs[3])")
     ap.add_argument("--impressions", type=int, default=40000, help="synthetic impressions per rank (~37 rows each)")
     ap.add_argument("--news", type=int, default=0, help="synthetic news corpus size (0 = the data set's real size)")
-    ap.add_argument("--cpu-rows", type=int, default=1536, help="max rows of the CPU-baseline sample (0 = skip)")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="time bound of the CPU-baseline sample")
-    ap.add_argument("--extra-steps", type=int, default=12, help="timed steps of each extra workload at N=1 (0 = skip)")
+    ap.add_argument("--cpu-rows", type=int, default=1536, help="--full: max rows of the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="--full: time bound of the CPU-baseline sample")
+    ap.add_argument("--extra-steps", type=int, default=12, help="--full: timed steps of each extra workload at N=1 (0 = skip)")
     ap.add_argument("--train-precision", default="fp32", choices=["fp32", "bf16"],
                     help="--mode train: bf16 = bf16 matrix-core operands for the large training GEMMs (BASELINE configs[4])")
     ap.add_argument("--per-row-users", action="store_true",
@@ -107,6 +115,11 @@ def parse_args():
     ap.add_argument("--projection", default="auto", choices=["auto", "bf16x6", "bf16x6-pq3", "fp32", "pq-bf16", "pq-bf16-x1", "pq-fp8", "fp16x3"],
                     help="node projections: split-bf16 (fp32-equivalent) on the bf16 matrix cores, or fp32 MFMA; pq-bf16 = BASELINE "
                          "configs[4]: P', Q of the user graph's Eq. 8 stored in bf16 (three bf16 products; -x1: one); pq-fp8: stored as block-scaled e4m3")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: per-kernel profile and rooflines, CPU baseline and AUC matches, extra workloads and "
+                         "precisions, training step, end-to-end run, one-GPU reference at N > 1, the full result document")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="--mode infer: write the scores of the last timed step (rank 0) to DIR/scores.npy, float32")
     return ap.parse_args()
 
 
@@ -296,7 +309,7 @@ class Scorer:
         self.lanes = util.batch_streams(D.dev, int(getattr(args, "lanes", 0) or os.environ.get("DIGAT_BENCH_LANES", "3")))
         self.nlanes = len(self.lanes)
         self.lane_scores = [torch.empty(self.B, dtype=torch.float32, device=D.dev) for _ in self.lanes]
-        self.k, self.base, self.pipe, self.order = 0, 0, None, None
+        self.k, self.base, self.pipe, self.order, self.last = 0, 0, None, None, None
         self.kept = [] if keep_scores else None
         enc = W.model.graph_encoder
         util.apply_corpus_hint(enc, W.dc)            # this corpus's sparse / dense choice (several workloads share the process)
@@ -313,21 +326,35 @@ class Scorer:
     def revisited(self):
         return self.k > self.nbatches
 
+    def _start_chunk(self, k):
+        util, W, B = self.util, self.W, self.B
+        self.base = k
+        self.order = [(((k + j) % self.nbatches) * B, min(((k + j) % self.nbatches) * B + B, W.dc.rows)) for j in range(self.CHUNK)]
+        if self.pipe is not None:             # the old pipeline's buffers return to the allocator: every lane must be done with them
+            self.join()
+            with torch.cuda.stream(self.lanes[0]):
+                self.pipe.drain()
+        enc = W.model.graph_encoder
+        self.pipe = None if self.per_row else util.GroupedBatchPipeline(
+            W.dc, self.order, self.imp_host, nsets=len(self.lanes),
+            news_sparse=(enc.resolved_xattn_mode("news") == "sparse") if hasattr(enc, "resolved_xattn_mode") else None)
+        for extra in self.lanes[1:]:
+            extra.wait_stream(self.lanes[0])
+
+    def restart(self):
+        """Back to batch 0 with a fresh pipeline, built here rather than inside the next step."""
+        self.k = 0
+        self._start_chunk(0)
+
+    def last_scores(self):
+        """What the caller of the last step received: the scores of that step's batch (host copy, after a fence)."""
+        lane, n, kept = self.last
+        return (kept if kept is not None else self.lane_scores[lane][:n]).float().cpu().numpy()
+
     def step(self):
-        util, W, B, k = self.util, self.W, self.B, self.k
+        util, W, k = self.util, self.W, self.k
         if self.pipe is None and self.order is None or k - self.base >= self.CHUNK:
-            self.base = k
-            self.order = [(((k + j) % self.nbatches) * B, min(((k + j) % self.nbatches) * B + B, W.dc.rows)) for j in range(self.CHUNK)]
-            if self.pipe is not None:             # the old pipeline's buffers return to the allocator: every lane must be done with them
-                self.join()
-                with torch.cuda.stream(self.lanes[0]):
-                    self.pipe.drain()
-            enc = W.model.graph_encoder
-            self.pipe = None if self.per_row else util.GroupedBatchPipeline(
-                W.dc, self.order, self.imp_host, nsets=len(self.lanes),
-                news_sparse=(enc.resolved_xattn_mode("news") == "sparse") if hasattr(enc, "resolved_xattn_mode") else None)
-            for extra in self.lanes[1:]:
-                extra.wait_stream(self.lanes[0])
+            self._start_chunk(k)
         s, e = self.order[k - self.base]
         lane = k % self.nlanes
         with torch.no_grad(), torch.cuda.stream(self.lanes[lane]):
@@ -342,6 +369,7 @@ class Scorer:
                 self.lane_scores[lane][:e - s] = out
             if self.pipe is not None:
                 self.pipe.scored(k - self.base)
+        self.last = (lane, e - s, out if self.kept is not None else None)
         self.k = k + 1
         return e - s
 
@@ -350,8 +378,9 @@ class Scorer:
             self.lanes[0].wait_stream(extra)
 
 
-def run_inference(W, args, D: Dist, steps, warmup, with_profile=True, gather_scores=False):
-    """Pre-warm, W warm-up steps, exactly K timed steps between fences -> timing + the library's per-kernel events."""
+def run_inference(W, args, D: Dist, steps, warmup, with_profile=True, gather_scores=False, keep_last=False):
+    """Pre-warm, W warm-up steps, exactly K timed steps between fences -> timing + the library's per-kernel events
+    (with_profile) + the scores of the last timed step (keep_last)."""
     from digat_amd import _lib, util
     sc = Scorer(W, args, D, keep_scores=False)
     L = W.L
@@ -376,6 +405,9 @@ def run_inference(W, args, D: Dist, steps, warmup, with_profile=True, gather_sco
         for _ in range(8):
             sc.step()
         torch.cuda.synchronize()
+    # the pre-warm took as many batches as the clock allowed: from here on (a fixed number of tuning steps, the warm-up, the
+    # timed steps) the batches are the same every run, and so are the scores of the last timed step
+    sc.restart()
     # Setup, untimed: how many batches to keep in flight (util.batch_streams: 3 is best at the default shapes, 2 at the stress
     # shape and with bf16 P', Q — the optimum moves with the kernels' lengths, so it is measured, 2 x 30 steps per candidate)
     t_tune = time.perf_counter()
@@ -430,7 +462,8 @@ def run_inference(W, args, D: Dist, steps, warmup, with_profile=True, gather_sco
     out = types.SimpleNamespace(elapsed=elapsed, rows_done=rows_done, profiled_steps=profiled_steps, revisited=sc.revisited,
                                 batches_in_flight=sc.nlanes, untimed_s=untimed_s, all_gather_ms=gather_ms,
                                 prof=None, prof_iso=None, live_fraction=None, iso_steps=0,
-                                gathered_rows=None if gathered is None else int(gathered.numel()))
+                                gathered_rows=None if gathered is None else int(gathered.numel()),
+                                last_scores=sc.last_scores() if keep_last and steps > 0 else None)
     out.prof_all, out.all_steps = None, 0
     if with_profile:
         out.prof = _lib.profile_stop()
@@ -1052,12 +1085,14 @@ def compact_line(out):
 
 def emit(out, args):
     """Write the full document to bench_detail.json (next to bench.py, and under gpurun_out/ when that directory exists) and print
-    the compact line as the ONLY line on stdout."""
+    the compact line as the ONLY line on stdout.  Without --full the document is written only where --detail says."""
     paths = [os.path.join(REPO, "bench_detail.json")]
     if os.path.isdir(os.path.join(REPO, "gpurun_out")):
         paths.append(os.path.join(REPO, "gpurun_out", "bench_detail.json"))
     if getattr(args, "detail", None):
         paths = [args.detail]
+    elif not args.full:
+        paths = []
     written = None
     for path in paths:
         try:
@@ -1078,6 +1113,8 @@ def emit(out, args):
 
 def main():
     args = parse_args()
+    if args.dump_outputs and args.mode != "infer":
+        raise SystemExit("--dump-outputs: --mode infer only")
     D = Dist(args)
     name = args.workload if args.workload != "auto" else ("mind-small-default" if D.world == 1 else "mind-large-default")
 
@@ -1122,7 +1159,11 @@ def main():
     W = build_workload(name, args, D, args.impressions)
     from digat_amd import util as _util
     _util.freeze_host_heap()      # the synthetic corpus's host structures out of the garbage collector's walks (util.compute_scores does the same)
-    run = run_inference(W, args, D, args.steps, args.warmup, with_profile=True, gather_scores=D.world > 1)
+    run = run_inference(W, args, D, args.steps, args.warmup, with_profile=args.full, gather_scores=D.world > 1,
+                        keep_last=bool(args.dump_outputs) and D.rank == 0)
+    if run.last_scores is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "scores.npy"), run.last_scores)
     range_overflow = bool(W.model.graph_encoder.range_overflowed())
     elapsed = D.reduce([run.elapsed], "max")[0]
     rows_total, rows_all, imps_all = D.reduce([run.rows_done, W.corpus.rows, W.spec.impressions])
@@ -1138,7 +1179,7 @@ def main():
     # the other is not a scaling efficiency.  So the N > 1 line carries its OWN one-GPU reference: after the timed region rank 0
     # scores the same workload, same steps, alone (the other ranks wait at the fence below, their GPUs idle).
     n1_same = None
-    if D.world > 1:
+    if D.world > 1 and args.full:
         D.fence()
         if D.rank == 0:
             rs = run_inference(W, args, SoloView(D), args.steps, args.warmup, with_profile=False, gather_scores=False)
@@ -1150,19 +1191,21 @@ def main():
         D.close()
         return
 
-    roof_dom, roof_x, kernel_ms, kernel_iso = rooflines(W, run, args)
+    roof_dom = roof_x = kernel_ms = kernel_iso = None
+    if args.full:
+        roof_dom, roof_x, kernel_ms, kernel_iso = rooflines(W, run, args)
     cpu_baseline = auc_match = cpu_sample = None
-    if args.cpu_rows > 0:
+    if args.full and args.cpu_rows > 0:
         # N = 1: the reported CPU baseline (~20 s) and the AUC match on its rows; N > 1: a short AUC match only
         rows = args.cpu_rows if D.world == 1 else min(args.cpu_rows, 384)
         secs = args.cpu_seconds if D.world == 1 else min(args.cpu_seconds, 6.0)
         cpu_baseline, auc_match, cpu_sample = cpu_baseline_and_auc(W, args, rows, secs, report_baseline=D.world == 1)
-    trained = auc_match_trained(args, D) if args.cpu_rows > 0 else None
+    trained = auc_match_trained(args, D) if args.full and args.cpu_rows > 0 else None
     matched = (auc_match is not None and auc_match["max_abs_metric_diff"] <= auc_match["tolerance"]
                and (trained is None or trained["max_abs_metric_diff"] <= trained["tolerance"]) and not range_overflow)
 
     extra = None
-    if D.world == 1 and args.extra_steps > 0 and args.workload == "auto":
+    if args.full and D.world == 1 and args.extra_steps > 0 and args.workload == "auto":
         # BASELINE configs[2] and the configs[3] shape, a few steps each, in the same invocation (same method, fewer steps)
         extra = {}
         if args.batch != REFERENCE_BATCH:
@@ -1304,7 +1347,7 @@ def main():
             extra["mind-small-default/train-step"] = {"error": repr(exc)}
 
     e2e = None
-    if D.world == 1 and args.e2e_impressions > 0 and args.workload == "auto" and args.extra_steps > 0:
+    if args.full and D.world == 1 and args.e2e_impressions > 0 and args.workload == "auto" and args.extra_steps > 0:
         del W.dc.news_hpq0, W.dc.SA_news_representations           # 4 GB of the headline workload's tables: the e2e run builds its own
         W.dc.news_hpq0 = W.dc.SA_news_representations = None
         torch.cuda.empty_cache()
@@ -1367,7 +1410,7 @@ def main():
         "roofline": roof_dom,
         "roofline_xattn": roof_x,
         # the whole step against the chip: executed matrix-core flops and compulsory HBM bytes, each / peak, vs ms_per_step
-        "roofline_step": roofline_step(W, run, elapsed / args.steps * 1e3),
+        "roofline_step": roofline_step(W, run, elapsed / args.steps * 1e3) if args.full else None,
         "kernel_ms_per_step": kernel_ms,
         "kernel_ms_per_step_single_stream": kernel_iso,
         # rows projected / rows nominal over the row-list launches (user-graph layers >= 1 and featureAffine): the encoder

@@ -29,7 +29,7 @@ def _detail(path):
 
 def test_bench_single_gpu_prints_the_contract_line(tmp_path):
     detail = str(tmp_path / "detail.json")
-    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "6", "--warmup", "2", "--impressions", "600", "--news", "2048",
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "6", "--warmup", "2", "--impressions", "600", "--news", "2048", "--full",
            "--cpu-rows", "256", "--cpu-seconds", "5", "--extra-steps", "2", "--e2e-impressions", "1500", "--detail", detail]
     res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
@@ -126,10 +126,36 @@ def test_bench_single_gpu_prints_the_contract_line(tmp_path):
         assert 0 < ex[k]["roofline"]["frac"] < 1 and 0 < ex[k]["roofline_xattn"]["frac"] < 1 and ex[k]["kernel_ms_per_step_single_stream"]
 
 
+def test_bench_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full: the headline alone (no profile, no oracle, no extras, no document), and --dump-outputs writes the scores of
+    the last timed step — the same batch, so the same scores, in every run with the same arguments."""
+    import numpy as np
+    scores = []
+    for tag in ("a", "b"):
+        out = tmp_path / tag
+        cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2", "--impressions", "600", "--news", "2048",
+               "--dump-outputs", str(out)]
+        res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
+        assert res.returncode == 0, res.stderr[-2000:]
+        line = _last_json_line(res.stdout)
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(line)
+        assert line["steps"] == 5 and line["warmup"] == 2 and line["value"] > 0 and line["ms_per_step"] > 0
+        assert line["unit"] == "impressions/s" and line["higher_is_better"] is True and line["dtype"] == "f32" and line["valid"] is True
+        assert line["metric"].startswith("MIND dev impressions scored/sec")
+        assert line.get("roofline") is None and line["cpu_baseline"] is None and line["auc_match"] is None
+        assert "extra_workloads" not in line and line["detail"] is None
+        assert sorted(os.listdir(out)) == ["scores.npy"]
+        s = np.load(out / "scores.npy")
+        assert s.dtype == np.float32 and s.shape == (4096,) and np.isfinite(s).all() and s.std() > 0
+        scores.append(s)
+    np.testing.assert_allclose(scores[0], scores[1], rtol=1e-5, atol=1e-5)
+
+
 def test_bench_two_ranks_sum_their_rows():
     env = dict(os.environ, DIGAT_BENCH_TEST_SHARED_GPU="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29731", "bench.py", "--gpus", "2", "--steps", "4", "--warmup", "2", "--impressions", "600", "--news", "2048"]
+           "--master-port", "29731", "bench.py", "--gpus", "2", "--steps", "4", "--warmup", "2", "--impressions", "600", "--news", "2048",
+           "--full"]
     res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=420, env=env)
     assert res.returncode == 0, res.stderr[-2000:]
     line = _last_json_line(res.stdout)
@@ -152,7 +178,7 @@ def test_bench_two_gpus_starts_its_own_launcher():
     torch.distributed.run as a child before touching the GPU and relays its JSON line and exit code."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.update(DIGAT_BENCH_TEST_SHARED_GPU="1")
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "4", "--warmup", "2", "--impressions", "600", "--news", "2048"]
+    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "4", "--warmup", "2", "--impressions", "600", "--news", "2048", "--full"]
     res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=420, env=env)
     assert res.returncode == 0, res.stderr[-2000:]
     line = _last_json_line(res.stdout)
@@ -160,6 +186,22 @@ def test_bench_two_gpus_starts_its_own_launcher():
     assert line["n_gpus"] == 2 and line["value"] > 0 and line["config"]["ranks_in_process_group"] == 2
     assert line["config"]["backend"] == "gloo"            # the one-GPU test hook; "nccl" (RCCL) on a multi-GPU node
     assert line["auc_match"]["max_abs_metric_diff"] <= 1e-4
+
+
+def test_bench_two_ranks_plain_run_dumps_rank0_scores(tmp_path):
+    """Without --full at N = 2: no one-GPU reference run, no oracle; rank 0 dumps the scores of its last timed step."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    env.update(DIGAT_BENCH_TEST_SHARED_GPU="1")
+    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "4", "--warmup", "2", "--impressions", "600", "--news", "2048",
+           "--dump-outputs", str(tmp_path)]
+    res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=420, env=env)
+    assert res.returncode == 0, res.stderr[-2000:]
+    line = _last_json_line(res.stdout)
+    assert line["n_gpus"] == 2 and line["steps"] == 4 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert len(line["per_rank_impressions_per_s"]) == 2 and line["auc_match"] is None and "n1_same_workload" not in line
+    s = np.load(tmp_path / "scores.npy")
+    assert s.dtype == np.float32 and s.shape == (4096,) and np.isfinite(s).all() and s.std() > 0
 
 
 def test_bench_train_mode_two_ranks_ddp():
@@ -186,7 +228,7 @@ def test_bench_eight_ranks_dress_rehearsal_on_one_gpu():
     real 8-GPU lease.  Eight ranks, eight shards, every rank's rows in the sum."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.update(DIGAT_BENCH_TEST_SHARED_GPU="1")
-    cmd = [sys.executable, "bench.py", "--gpus", "8", "--steps", "3", "--warmup", "1", "--impressions", "300", "--news", "2048"]
+    cmd = [sys.executable, "bench.py", "--gpus", "8", "--steps", "3", "--warmup", "1", "--impressions", "300", "--news", "2048", "--full"]
     res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert res.returncode == 0, res.stderr[-2000:]
     line = _last_json_line(res.stdout)

@@ -9,8 +9,8 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp
-python3 $ROOT/bench.py --detail $OUT/bench_detail.json > $OUT/bench.json 2> $OUT/bench.err
-B="python3 $ROOT/bench.py --extra-steps 0 --cpu-rows 0 --steps 30 --e2e-impressions 0 --impressions 12000"
+python3 $ROOT/bench.py --full --detail $OUT/bench_detail.json > $OUT/bench.json 2> $OUT/bench.err
+B="python3 $ROOT/bench.py --full --extra-steps 0 --cpu-rows 0 --steps 30 --e2e-impressions 0 --impressions 12000"
 # the traced run records its event pairs on EVERY step of the timed region, so that the library's averages and the trace's
 # (tools/trace_region.py, below) are over the same launches
 DIGAT_BENCH_PROFILE_EVERY=1 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o t -- $B --detail $OUT/bench_traced_detail.json > $OUT/bench_traced.json 2> $OUT/trace.err

@@ -31,7 +31,7 @@ def main():
     for r in range(runs):
         for name, env in configs:
             with tempfile.NamedTemporaryFile(suffix=".json") as f:
-                cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "60", "--warmup", "10", "--cpu-rows", "0", "--extra-steps", "0",
+                cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "60", "--warmup", "10", "--cpu-rows", "0", "--extra-steps", "0",
                        "--e2e-impressions", "0", "--detail", f.name] + extra
                 res = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, **env), capture_output=True, text=True)
                 if res.returncode != 0:

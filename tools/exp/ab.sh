@@ -4,7 +4,7 @@ VAR=DIGAT_BENCH_LANES
 for rep in 1 2; do
 for v in 2 3; do
   echo "== $VAR=$v"
-  env $VAR=$v python bench.py --steps 120 --warmup 10 --extra-steps 0 --cpu-rows 0 2>/dev/null | tail -n 1 | python -c "
+  env $VAR=$v python bench.py --full --steps 120 --warmup 10 --extra-steps 0 --cpu-rows 0 2>/dev/null | tail -n 1 | python -c "
 import sys, json
 j = json.loads(sys.stdin.readlines()[-1])
 iso = j['kernel_ms_per_step_single_stream']

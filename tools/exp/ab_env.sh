@@ -3,7 +3,7 @@
 VAR=$1; A=$2; B=$3; RUNS=${4:-2}; shift 4
 for r in $(seq 1 $RUNS); do
   for v in $A $B; do
-    env $VAR=$v python bench.py --steps 200 --warmup 20 --cpu-rows 0 --extra-steps 0 "$@" 2>/dev/null | python -c "
+    env $VAR=$v python bench.py --full --steps 200 --warmup 20 --cpu-rows 0 --extra-steps 0 "$@" 2>/dev/null | python -c "
 import sys, json
 l = json.loads(sys.stdin.read().strip().splitlines()[-1])
 k = l['kernel_ms_per_step']; i = l['kernel_ms_per_step_single_stream']
