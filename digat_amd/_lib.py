@@ -183,7 +183,6 @@ _SIGNATURES = {
     "digat_split_ctx_fused_bytes": (C.c_size_t, [C.c_int]),
     "digat_split_ctx_fused_weights": (C.c_int, [_f, C.c_int, _f, _f]),
 }
-_LAB_SIGNATURES = {"digat_set_staged_xattn": (C.c_int, [C.c_int])}
 KERNEL_KINDS = ("proj", "linear", "xattn", "pool", "topic", "glue", "agg")
 XATTN_PARTS = ("twin", "l0", "news", "other")      # digat_profile_xattn_parts: the Eq. 8 launches by kernel
 EXPORTED = tuple(_SIGNATURES)
@@ -209,10 +208,6 @@ def lib() -> C.CDLL:
         for name, (res, args) in _SIGNATURES.items():
             fn = getattr(handle, name)
             fn.restype, fn.argtypes = res, args
-        for name, (res, args) in _LAB_SIGNATURES.items():          # LAB builds only (-DDIGAT_LAB through DIGAT_HIP_LIB)
-            if hasattr(handle, name):
-                fn = getattr(handle, name)
-                fn.restype, fn.argtypes = res, args
         _lib = handle
     return _lib
 

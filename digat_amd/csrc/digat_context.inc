@@ -149,9 +149,8 @@ static int launch_pool(const float* feat, long ld_b, const float* kq, const uint
     if (B == 0) return DIGAT_OK;
     PoolArgs g{feat, ld_b, kq, mask, addend, out, B, n, d, sqrtf((float)d), nullptr};
     ProfScope prof(DIGAT_KERNEL_POOL, (double)B * ((double)n * d * 4 + 2.0 * d * 4 + n), st);
-    static const int resident = LAB_ENV("DIGAT_POOL_RESIDENT", 1);
     const int d4 = d / 4;
-    if (resident && d4 <= 128 && n <= 68) {              // every node read once (registers); inference and training alike
+    if (d4 <= 128 && n <= 68) {              // every node read once (registers); inference and training alike
         if (d4 <= 64) {
             if (n <= 12) hipLaunchKernelGGL((attn_pool_resident_kernel<3, 1>), dim3(B), dim3(256), 0, st, g);
             else if (n <= 20) hipLaunchKernelGGL((attn_pool_resident_kernel<5, 1>), dim3(B), dim3(256), 0, st, g);
@@ -180,7 +179,7 @@ struct TopicArgs {
     const float* Xu; long ld_b; const float* kq; const int64_t* idx; float* out;
     int B, H, C1, d; float sqrt_d;
     float* alpha_out;                    // optional [B,H]: the segment-softmax weights (training)
-    int skip;                            // ablation only (env DIGAT_TOPIC_SKIP, 0 in production)
+    int skip;                            // always 0 (a removed timing ablation's switch: bits 1, 2, 4 skip kernel phases)
     const int* group;                    // optional [B]: row b's nodes live at Xu + group[b] * ld_b (rows of one impression share them)
     const uint8_t* live; int live_ld;    // optional [B, live_ld] bytes: history rows t with live[b * live_ld + t] == 0 hold nothing
                                          // (dead nodes are never written by the encoder's layers): they are taken as 0 — by a
@@ -451,147 +450,7 @@ __global__ void __launch_bounds__(TOPIC_RES_STEPS > 13 ? 512 : 1024) topic_pool_
         if (cslot[c] < 0 && ch_ok) *reinterpret_cast<float4*>(Ob + (long)c * g.d + ch) = f4_zero();
 }
 
-// The same, as FOUR waves per row (256 threads, d <= 512): a lane holds two channel quads of every history row (piece p of wave w
-// and lane lr is float4 number p * 64 + w * 16 + lr of the row: every wave owns a full first piece, the second pieces cover the
-// channels from 256 up), so a workgroup is one wave per SIMD at ~200 registers — it fits into the slot ONE finished workgroup of the
-// projection GEMM (four 216-register waves, one per SIMD) leaves behind.  The seven-wave form above needs 2 x 128 registers on three
-// SIMDs at once, i.e. a CU the GEMM has left altogether: inside the overlapped region of a scoring run it waited 3.7x its own run
-// time for one (round 3: 361 us in-region against 97 us alone, 21 % of all in-region kernel time).  Scores: partial dot products
-// over the wave's channels, summed over the four waves in wave order — the seven-wave kernel's sum in a different grouping.
-// MEASURED (round 4, alternating runs, three launch sets in flight): alone 102 vs 100 us per launch; in-region 420-447 vs 452-459 us;
-// step 3.38-3.39 vs 3.35-3.36 ms.  The in-region time is what an HBM-bound kernel takes while two other launch sets share the
-// chip's bandwidth with it, not a wait for registers: the hypothesis was wrong, the seven-wave form stays the default and this one
-// is a LAB-build switch (DIGAT_TOPIC_4W=1).
-template <int TOPIC_RES_STEPS>
-__global__ void __launch_bounds__(256, 2) topic_pool_resident4_kernel(const TopicArgs g) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int nw = 4;
-    const int H = g.H, hs = H | 1;
-    const int ct = (g.C1 + 15) >> 4;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    float* M = reinterpret_cast<float*>(smem);               // [ct*16][hs]
-    float* part = M + ct * 16 * hs;                          // [nw][64] partial scores
-    float* sa = part + nw * 64;                              // [64]
-    int* sidx = reinterpret_cast<int*>(sa + 64);             // [64]
-    int* slive = sidx + 64;                                  // [64] live flags of the history rows (1 without a list)
-    const int b = blockIdx.x;
-    const float* Xb = g.Xu + (long)(g.group ? g.group[b] : b) * g.ld_b;
-    const int lr = lane & 15, lq = lane >> 4;
-    const int d4 = g.d >> 2;
-    const int q4[2] = {wave * 16 + lr, 64 + wave * 16 + lr};          // this lane's two float4 pieces of a row
-    const bool ok[2] = {q4[0] < d4, q4[1] < d4};
-    const bool any1 = 64 + wave * 16 < d4;                            // wave-uniform: the wave has a second piece at all
-    const int nsteps = (H + 3) >> 2;
-    const int nl = (g.live && g.hlast) ? min(g.hlast[b], H) : H;     // rows past the last live history slot are not requested
-
-    float4 xq[TOPIC_RES_STEPS][2];
-#pragma unroll
-    for (int s = 0; s < TOPIC_RES_STEPS; ++s) {
-        const int j = s * 4 + lq;
-        const int jr = min(j, nl > 0 ? nl - 1 : 0);                  // redirected, not predicated (see the seven-wave kernel)
-        const float4* row = reinterpret_cast<const float4*>(Xb + (long)jr * g.d);
-#pragma unroll
-        for (int p = 0; p < 2; ++p)
-            xq[s][p] = (s < nsteps && j < H && ok[p] && (p == 0 || any1)) ? row[q4[p]] : f4_zero();
-    }
-    float4 k4[2];
-#pragma unroll
-    for (int p = 0; p < 2; ++p) k4[p] = ok[p] ? reinterpret_cast<const float4*>(g.kq + (long)b * g.d)[q4[p]] : f4_zero();
-    if (tid < 64) {
-        long v = -1;
-        if (tid < H) v = g.idx[(long)b * H + tid];
-        sidx[tid] = (v >= 0 && v < g.C1) ? (int)v : -1;
-        slive[tid] = (g.live && tid < H) ? (int)g.live[(long)b * g.live_ld + tid] : 1;
-    }
-    for (int i = tid; i < ct * 16 * hs; i += 256) M[i] = 0.f;
-    if (g.live) {
-        __syncthreads();                       // dead rows are dropped by a select, never a multiply
-#pragma unroll
-        for (int s = 0; s < TOPIC_RES_STEPS; ++s) {
-            const bool lv = slive[min(s * 4 + lq, 63)] != 0;
-            xq[s][0] = lv ? xq[s][0] : f4_zero();
-            xq[s][1] = lv ? xq[s][1] : f4_zero();
-        }
-    }
-    // partial scores of this wave's channels
-#pragma unroll
-    for (int s = 0; s < TOPIC_RES_STEPS; ++s) {
-        float pp = fmaf(xq[s][0].w, k4[0].w, fmaf(xq[s][0].z, k4[0].z, fmaf(xq[s][0].y, k4[0].y, xq[s][0].x * k4[0].x)));
-        pp = fmaf(xq[s][1].w, k4[1].w, fmaf(xq[s][1].z, k4[1].z, fmaf(xq[s][1].y, k4[1].y, fmaf(xq[s][1].x, k4[1].x, pp))));
-        pp += dpp_mov<0xB1>(pp); pp += dpp_mov<0x4E>(pp); pp += dpp_mov<0x141>(pp); pp += dpp_mov<0x140>(pp);
-        if (lr == 0) part[wave * 64 + s * 4 + lq] = pp;
-    }
-    __syncthreads();
-    if (tid < 64) sa[tid] = (((part[tid] + part[64 + tid]) + part[128 + tid]) + part[192 + tid]) / g.sqrt_d;
-    __syncthreads();
-    // segment softmax: wave w takes the categories c = w, w + 4, ...; lane t is history row t
-    {
-        const int my = lane < H ? sidx[lane] : -2;
-        const float v = lane < H ? sa[lane] : 0.f;
-        for (int c = wave; c < g.C1; c += nw) {
-            const bool in = my == c;
-            const float m = wave_max(in ? v : -INFINITY);
-            const float e = in ? expf(v - m) : 0.f;
-            const float den = wave_sum(e);
-            if (in) {
-                const float al = e / den;
-                M[c * hs + lane] = al;
-                if (g.alpha_out) g.alpha_out[(long)b * H + lane] = al;
-            }
-        }
-        if (wave == 0 && g.alpha_out && lane < H && my < 0) g.alpha_out[(long)b * H + lane] = 0.f;
-    }
-    __syncthreads();
-
-    v4f acc[TOPIC_MAX_CT][2][4];
-#pragma unroll
-    for (int it = 0; it < TOPIC_MAX_CT; ++it)
-#pragma unroll
-        for (int p = 0; p < 2; ++p)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) acc[it][p][c] = (v4f){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int s = 0; s < TOPIC_RES_STEPS; ++s) {
-        if (s * 4 < nl) {                    // wave-uniform; the steps past the last live row hold zeros only
-            const int j = s * 4 + lq;
-#pragma unroll
-            for (int it = 0; it < TOPIC_MAX_CT; ++it) {
-                if (it < ct) {
-                    const float av = j < H ? M[(it * 16 + lr) * hs + j] : 0.f;
-#pragma unroll
-                    for (int p = 0; p < 2; ++p) {
-                        if (p == 0 || any1) {
-                            const float4 xc = xq[s][p];
-                            acc[it][p][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, xc.x, acc[it][p][0], 0, 0, 0);
-                            acc[it][p][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, xc.y, acc[it][p][1], 0, 0, 0);
-                            acc[it][p][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, xc.z, acc[it][p][2], 0, 0, 0);
-                            acc[it][p][3] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, xc.w, acc[it][p][3], 0, 0, 0);
-                        }
-                    }
-                }
-            }
-        }
-    }
-    float* Ob = g.out + (long)b * g.C1 * g.d;
-#pragma unroll
-    for (int it = 0; it < TOPIC_MAX_CT; ++it) {
-        if (it < ct) {
-#pragma unroll
-            for (int p = 0; p < 2; ++p)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int c = it * 16 + 4 * lq + r;
-                    if (c < g.C1 && ok[p])
-                        reinterpret_cast<float4*>(Ob + (long)c * g.d)[q4[p]] =
-                            make_float4(acc[it][p][0][r], acc[it][p][1][r], acc[it][p][2][r], acc[it][p][3][r]);
-                }
-        }
-    }
-}
-
 static int launch_topic_args(TopicArgs g, hipStream_t st) {
-    static const int skip = LAB_ENV("DIGAT_TOPIC_SKIP", 0);       // LAB builds: timing ablations (wrong results)
-    g.skip = skip;
     const int groups = (g.d + 63) / 64;
     const int ct = (g.C1 + 15) / 16;
     if (g.H > TOPIC_MAX_H || g.d % 4 || groups > 16 || ct > TOPIC_MAX_CT) return DIGAT_ERR_SHAPE;
@@ -604,12 +463,7 @@ static int launch_topic_args(TopicArgs g, hipStream_t st) {
             raised = 1;
         }
     }
-    static const int four_waves = LAB_ENV("DIGAT_TOPIC_4W", 0);
-    if (g.H <= 52 && !(g.skip & 64) && groups <= 8 && four_waves && ct <= 2) {      // d <= 512, C + 1 <= 32: four fat waves per row
-        // (H = 53 .. 64 would need 16 steps x 2 pieces in registers: 22 spills at the 256 a wave may use — those take the form below)
-        const size_t ldsr = ((size_t)ct * 16 * (g.H | 1) + 4 * 64 + 192) * 4;
-        hipLaunchKernelGGL(topic_pool_resident4_kernel<13>, dim3(g.B), dim3(256), ldsr, st, g);
-    } else if (g.H <= 64 && !(g.skip & 64) && (g.H <= 52 || groups <= 8)) {
+    if (g.H <= 64 && (g.H <= 52 || groups <= 8)) {
         const size_t ldsr = ((size_t)ct * 16 * (g.H | 1) + (size_t)groups * 64 + 192 + 64 + 68) * 4;
         if (g.H <= 52) hipLaunchKernelGGL(topic_pool_resident_kernel<13>, dim3(g.B), dim3(64 * groups), ldsr, st, g);
         else hipLaunchKernelGGL(topic_pool_resident_kernel<16>, dim3(g.B), dim3(64 * groups), ldsr, st, g);

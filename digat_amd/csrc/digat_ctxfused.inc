@@ -27,7 +27,7 @@ struct CtxFusedArgs {
     const float* kq_topic; const float* kq_user; const int64_t* idx; const uint8_t* cat_mask; const float* addend; float* out;
     const uint4* wimg; const float* bFa; unsigned* range_flag;
     int B, H, C1, d; float sqrt_d;
-    int dbg;                              // LAB builds only (DIGAT_CF_DBG): timing ablations, wrong results
+    int dbg;                              // unused, always 0 (a removed timing ablation's switch)
 };
 constexpr int CF_R = 4;                  // rows per workgroup
 constexpr int CF_STEPS = 13;             // 4-row steps of a history held in registers: H <= 52
@@ -202,9 +202,6 @@ __global__ void __launch_bounds__(448) user_ctx_fused_kernel(const CtxFusedArgs 
         for (int s = 0; s < 4; ++s) acc[s] = (v4f){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int s = 0; s < STEPS; ++s) {
-#ifdef DIGAT_LAB
-            if (g.dbg & 2) break;
-#endif
             if (s * 4 < nl) {                    // wave-uniform
                 const float2 as = aslot[r * 64 + min(s * 4 + lq, 63)];
                 const float av = as.y == (float)lr ? as.x : 0.f;
@@ -349,11 +346,7 @@ __global__ void __launch_bounds__(448) user_ctx_fused_kernel(const CtxFusedArgs 
                 for (int r = 0; r < R; ++r) acc[r][q] = mma(ah[r], bh[q], acc[r][q]);     // x hi . w hi
             }
         };
-#ifdef DIGAT_LAB
-        const int KTX = (g.dbg & 1) ? 1 : KT;
-#else
         const int KTX = KT;
-#endif
         uint4 bh0[2], bl0[2], bh1[2], bl1[2], bh2[2], bl2[2];
         load_b2(0, bh0, bl0);
         if (1 < KTX) load_b2(1, bh1, bl1);

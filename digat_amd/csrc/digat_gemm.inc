@@ -9,9 +9,9 @@ enum { EPI_NONE = 0, EPI_RELU_RES = 1, EPI_GATE = 2, EPI_ACCUM = 3,     // ACCUM
 
 struct GemmArgs {
     const float* a0; long lda0; int k0;      // columns [0,k0) of A come from a0 ...
-    const void* a_split;                     // strip-mined fp16x3 kernel only, optional: the rows of a0 ALREADY SPLIT by their producer (same
-                                             // row stride, 32 bytes per 8 columns: [8 fp16 hi | 8 fp16 lo], the pieces split_mt makes; see
-                                             // split_store4 in digat_xattn.inc): the kernel then reads its A fragments as they are
+    const void* a_split;                     // strip-mined fp16x3 kernel, PRE only: the rows of a0 ALREADY SPLIT by their producer (same
+                                             // row stride, 32 bytes per 8 columns: [8 fp16 hi | 8 fp16 lo], the pieces split_mt makes).
+                                             // No launch sets it (docs/REJECTED.md row 4q)
     const float* a1; long lda1;              // ... columns [k0,K) from a1 (gate: [local ; global])
     const float* w[3]; const float* bias[3]; float* y[3]; long ldy;
     int nseg, nsegs, M, K, transW;           // transW: w_s stored [K, nseg] (y = A @ w)
@@ -37,10 +37,6 @@ struct GemmArgs {
     const uint8_t* dmask; long lddm; float dscale; // bf16x6 kernel, optional: y = (result [+ e0]) x (dmask[row][col] ? dscale : 0) — the backward
     int dmask_cols;                                // of the dropout in front of the layer (training: dX through the keep bytes [M, lddm]);
                                                    // dmask_cols > 0: the mask has that many columns, output columns beyond them are left as computed
-#ifdef DIGAT_LAB
-    int diag;                                      // LAB builds (env DIGAT_GEMM_DIAG): timing ablations of the strip-mined kernel, WRONG results:
-                                                   // 1 = strip images fetched for the first K tile only, 2 = A tile fetched once, 4 = no MFMA
-#endif
 };
 
 // LDS image: float4 tile[k4][row ^ k4]  (k4 = 4-float column group of the 32-deep K tile).
@@ -507,16 +503,6 @@ __global__ void __launch_bounds__(256, MT == 1 ? 3 : (MT == 2 ? 2 : 1)) gemm_bf1
     const int kg = lane >> 4, lr = lane & 15;
     const int m0 = mtile * TROWS;
     const int strip0 = ntile * NSUB;
-#ifdef DIGAT_LAB
-    // experiment (round 6, DIGAT_GEMM_DIAG >= 16): the workgroups of the FIRST round start up to 15 x (diag >> 4) x 1024 cycles apart, so that
-    // the rounds of a launch — every workgroup storing its 123 KB tile at the same moment: the epilogue is a fifth of the kernel and
-    // HBM-write-bound — fall out of step
-    if ((g.diag >> 4) && blockIdx.x < 512) {
-        const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-        const unsigned long long want = (unsigned long long)(((blockIdx.x * 2654435761u) >> 28) & 15u) * (unsigned long long)(g.diag >> 4) * 1024ull;
-        while (__builtin_amdgcn_s_memtime() - t0 < want) __builtin_amdgcn_s_sleep(32);
-    }
-#endif
 #ifdef DIGAT_GEMM_TIMERS
     const unsigned long long gt_enter = GT_NOW();
     unsigned long long gt_wait = 0, gt_bar = 0, gt_body = 0, gt_steps = 0, gt_last = 0;
@@ -629,9 +615,6 @@ __global__ void __launch_bounds__(256, MT == 1 ? 3 : (MT == 2 ? 2 : 1)) gemm_bf1
         }
     };
     auto mma = [&](const bf16x8 w, const bf16x8 a, const v4f c) -> v4f {      // fragments are typed bf16x8 for storage only
-#ifdef DIGAT_LAB
-        if (g.diag & 4) return c;
-#endif
         if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, w), __builtin_bit_cast(half8, a), c, 0, 0, 0);
         else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, a, c, 0, 0, 0);
     };
@@ -701,19 +684,14 @@ __global__ void __launch_bounds__(256, MT == 1 ? 3 : (MT == 2 ? 2 : 1)) gemm_bf1
             gt_last = GT_NOW();
             gt_wait += gt1 - gt0; gt_bar += gt_last - gt1; ++gt_steps;
 #endif
-#ifdef DIGAT_LAB
-            const bool lab_a = !(g.diag & 2), lab_b = !(g.diag & 1);
-#else
-            constexpr bool lab_a = true, lab_b = true;
-#endif
             // SPREAD (experiment, off: see DIGAT_GEMM_SPREAD): the step's DMA pieces — this wave's four of the next A tile at strip 0,
             // its three of the strip image two steps ahead — one or two per 16-column block behind that block's six MFMAs instead of
             // in one burst in front of the step's first MFMA; the queue order (A pieces, then the image's) and every vmcnt count stay
             constexpr bool SPREAD = DIGAT_GEMM_SPREAD && NSUB > 1 && MT == 2 && !PRE;
-            const bool do_a = NSUB > 1 && s == 0 && more && lab_a, do_b = NSUB > 1 && step + 2 < nsteps && lab_b;
+            const bool do_a = NSUB > 1 && s == 0 && more, do_b = NSUB > 1 && step + 2 < nsteps;
             if (NSUB == 1) {
-                if (kt + ABUF < KT && lab_a) issue_a(kt + ABUF, kt % ABUF);  // the buffer of A(kt): split during step kt - 1
-                if (step + RING - 1 < nsteps && lab_b) issue_b(step + RING - 1);
+                if (kt + ABUF < KT) issue_a(kt + ABUF, kt % ABUF);  // the buffer of A(kt): split during step kt - 1
+                if (step + RING - 1 < nsteps) issue_b(step + RING - 1);
             } else if (!SPREAD) {
                 if (do_a) issue_a(kt + 1, 0);            // read at strip 1, after the next barrier
                 if (do_b) issue_b(step + 2);
@@ -934,324 +912,6 @@ __global__ void __launch_bounds__(256, MT == 1 ? 3 : (MT == 2 ? 2 : 1)) gemm_bf1
     }
 #endif
 }
-
-#ifdef DIGAT_LAB
-// 1b''. LAB builds only (DIGAT_GEMM_PERSIST=1; measured: -3.6 % alone, nothing with three passes in flight — docs/REJECTED.md row 31):
-// PERSISTENT form of gemm_bf16x6s_kernel<3, true, 2, false, true> (round 6).  The phase timers of the one-tile-per-workgroup kernel
-// (-DDIGAT_GEMM_TIMERS) put 8 % of a wave's life into the prologue (address set-up, the first A tile and two strip images requested and
-// WAITED for before the first MFMA) and 23 % into the epilogue (row index / bias / K3 loads, 30 stores, the drain before the slot is handed
-// to the next workgroup): a third of a tile's time with the matrix pipe idle for that wave.  Here a workgroup walks the tiles of its XCD's
-// chunk (grid = 2 workgroups per CU): the strip images of the NEXT tile's first two steps and its first two A tiles are requested during
-// the last K tile of the current one (the image ring and the A buffer simply run on across the tile boundary: the step counter is
-// global), so a tile after the first has NO prologue; its epilogue's stores are issued and the next tile's MFMAs start behind them
-// without waiting for their completion (steps 0 and 1 of a tile read operands that landed before the stores were issued: one
-// "s_waitcnt vmcnt(0)" in front of the stores; from step 2 on the in-order queue has the stores ahead of the DMA pieces it waits
-// for, which by then have had two steps to drain).  The A tile of K tile kt + 2 is requested at strip 2 of kt (the buffer is free
-// once strip 1 has split kt + 1), one strip earlier than in the one-tile kernel, so that the request for the tile after next sits
-// in front of the stores.  Per output element the products, their order and the epilogue are those of the one-tile kernel: same bits.
-__global__ void __launch_bounds__(256, 2) gemm_f16x3_persist_kernel(const GemmArgs g) {
-    constexpr int NSUB = 3, MT = 2, NT = 5, WROWS = 32, TROWS = 128, APW = 4, RING = 3, WS_SLOTS = 640, PIECES = 10, IMG_I = 3;
-    __shared__ uint4 Bs[RING][WS_SLOTS];
-    __shared__ uint4 As[TROWS * 8];
-    const int Mv = g.nrows_dev ? __builtin_amdgcn_readfirstlane(*g.nrows_dev) : g.M;
-    if (g.exec_rows && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(g.exec_rows, (unsigned long long)Mv);
-    const int total = ((Mv + TROWS - 1) / TROWS) * g.ntiles;
-    const int chunk = (total + 7) >> 3;
-    const int xcd = (int)(blockIdx.x & 7), slot = (int)(blockIdx.x >> 3), nslot = (int)(gridDim.x >> 3);
-    const int chunk_len = min(chunk, total - xcd * chunk);          // tiles of this XCD's chunk (the same tile -> XCD map as the one-tile kernel)
-    if (slot >= chunk_len) return;
-    const int tid = threadIdx.x, lane = tid & 63, wm = tid >> 6;
-    const int kg = lane >> 4, lr = lane & 15;
-    const int KT = (g.K + 31) >> 5;
-    const int nsteps = KT * NSUB;
-    const unsigned ldsB = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)&Bs[0][0];
-    const unsigned ldsA = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)&As[0];
-    const char* const wimg = reinterpret_cast<const char*>(g.wsplit);
-    const unsigned wlane = (unsigned)lane * 16u;
-    const int wu = __builtin_amdgcn_readfirstlane(wm);
-
-    struct Tile { int m0, strip0; long arow0; unsigned aoff[APW]; };
-    int ac4[APW];
-#pragma unroll
-    for (int k = 0; k < APW; ++k) { const int sl = (wm + 4 * k) * 64 + lane; const int r = sl >> 3; ac4[k] = ((sl & 7) ^ ((r >> 1) & 7)) * 4; }
-    // the rows of a tile's A pieces: index loads (row-list launches) are requested a tile ahead and turned into offsets where they are first used
-    auto tile_rows = [&](int tile, int (&gm)[APW], Tile& t) {
-        const int mtile = tile / g.ntiles, ntile = tile - mtile * g.ntiles;
-        t.m0 = mtile * TROWS; t.strip0 = ntile * NSUB;
-        t.arow0 = g.rowidx ? 0 : (long)(t.m0 < Mv ? t.m0 : Mv - 1);
-#pragma unroll
-        for (int k = 0; k < APW; ++k) {
-            const int sl = (wm + 4 * k) * 64 + lane;
-            int r = t.m0 + (sl >> 3);
-            r = r < Mv ? r : Mv - 1;
-            gm[k] = g.rowidx ? g.rowidx[r] : r;
-        }
-    };
-    auto tile_offsets = [&](const int (&gm)[APW], Tile& t) {
-#pragma unroll
-        for (int k = 0; k < APW; ++k) t.aoff[k] = (unsigned)((((long)gm[k] - t.arow0) * g.lda0 + ac4[k]) * 4);
-    };
-    auto issue_b = [&](const Tile& t, int step, int gstep) {     // strip image of the tile's step -> Bs[gstep % RING]
-        const int kt = step / NSUB, s = step - kt * NSUB;
-        const int buf = gstep % RING;
-        const char* src = wimg + ((long)(t.strip0 + s) * KT + kt) * (WS_SLOTS * 16);
-#pragma unroll
-        for (int k = 0; k < IMG_I; ++k) {
-            int q = wu + 4 * k;
-            q = q < PIECES ? q : PIECES - 1;
-            lds_dma16_s(src + q * 1024, wlane, ldsB + (unsigned)((buf * WS_SLOTS + q * 64) * 16));
-        }
-    };
-    auto issue_a = [&](const Tile& t, int kt) {
-        const char* const abase = reinterpret_cast<const char*>(g.a0 + t.arow0 * g.lda0);
-#pragma unroll
-        for (int k = 0; k < APW; ++k) {
-            unsigned vo = t.aoff[k];
-            long sk = (long)kt * 128;
-            if (kt * 32 + 32 > g.K) { vo += kt * 32 + ac4[k] < g.K ? (unsigned)kt * 128u : 0u; sk = 0; }
-            lds_dma16_s(abase + sk, vo, ldsA + (unsigned)(((wu + 4 * k) * 64) * 16));
-        }
-    };
-    float amax = 0.f;
-    auto split_mt = [&](int mt, bf16x8 (&dst)[3][MT]) {
-        const int r = wm * WROWS + mt * 16 + lr;
-        const int sw = (r >> 1) & 7;
-        const float4 v0 = __builtin_bit_cast(float4, As[r * 8 + ((kg * 2) ^ sw)]);
-        const float4 v1 = __builtin_bit_cast(float4, As[r * 8 + ((kg * 2 + 1) ^ sw)]);
-        constexpr float xs = F16_ACT_SCALE;
-        const float raw[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-        const float v[8] = {v0.x * xs, v0.y * xs, v0.z * xs, v0.w * xs, v1.x * xs, v1.y * xs, v1.z * xs, v1.w * xs};
-        amax = fmaxf(fmaxf(amax, fabsf(v[0])), fabsf(v[1])); amax = fmaxf(fmaxf(amax, fabsf(v[2])), fabsf(v[3]));
-        amax = fmaxf(fmaxf(amax, fabsf(v[4])), fabsf(v[5])); amax = fmaxf(fmaxf(amax, fabsf(v[6])), fabsf(v[7]));
-        unsigned hi[4], lo[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            hi[e] = pack_half_rtz(v[2 * e], v[2 * e + 1]);
-            const fp16x2 h = __builtin_bit_cast(fp16x2, hi[e]);
-            const _Float16 l0 = (_Float16)__builtin_fmaf(raw[2 * e], xs, -(float)h[0]), l1 = (_Float16)__builtin_fmaf(raw[2 * e + 1], xs, -(float)h[1]);
-            lo[e] = (unsigned)__builtin_bit_cast(unsigned short, l0) | ((unsigned)__builtin_bit_cast(unsigned short, l1) << 16);
-        }
-        dst[0][mt] = __builtin_bit_cast(bf16x8, make_uint4(hi[0], hi[1], hi[2], hi[3]));
-        dst[1][mt] = __builtin_bit_cast(bf16x8, make_uint4(lo[0], lo[1], lo[2], lo[3]));
-    };
-    auto mma = [&](const bf16x8 w, const bf16x8 a, const v4f c) -> v4f {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, w), __builtin_bit_cast(half8, a), c, 0, 0, 0);
-    };
-
-    Tile cur, nxt;
-    int gm_cur[APW], gm_nxt[APW];
-    int j = 0;                                // this workgroup's tile counter
-    int tile = xcd * chunk + slot;
-    tile_rows(tile, gm_cur, cur);
-    tile_offsets(gm_cur, cur);
-    int gstep = 0;
-    // prologue of the FIRST tile only
-    issue_a(cur, 0);
-    issue_b(cur, 0, 0);
-    if (nsteps > 1) issue_b(cur, 1, 1);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    bf16x8 af[3][MT], afn[3][MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) split_mt(mt, af);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();             // every wave has read the A tile: the buffer may take K tile 1
-    if (KT > 1) issue_a(cur, 1);
-
-    for (;;) {
-        const int next_tile = xcd * chunk + slot + (j + 1) * nslot;
-        const bool has_next = slot + (j + 1) * nslot < chunk_len;
-        if (has_next) tile_rows(next_tile, gm_nxt, nxt);       // index loads in flight under this tile's K loop
-        // the output rows of THIS tile (row-list launches: an index load per row block), requested now, used in the epilogue
-        int gmv[MT];
-        bool rok[MT];
-        {
-            const int* const ri = (g.rowidx && !g.gather_only) ? g.rowidx : nullptr;
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) {
-                const int gv = cur.m0 + wm * WROWS + mt * 16 + lr;
-                rok[mt] = gv < Mv;
-                const int gvc = rok[mt] ? gv : Mv - 1;
-                gmv[mt] = ri ? ri[gvc] : gvc;
-            }
-        }
-        v4f acc[NSUB][MT][NT];
-#pragma unroll
-        for (int s = 0; s < NSUB; ++s)
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) acc[s][mt][nt] = (v4f){0.f, 0.f, 0.f, 0.f};
-        bool nxt_ready = false;               // nxt.aoff computed (first needed at strip 2 of K tile KT - 2)
-
-        for (int kt = 0; kt < KT; ++kt) {
-#pragma unroll
-            for (int s = 0; s < NSUB; ++s) {
-                const int step = kt * NSUB + s;
-                // needed now: image(step) (requested two steps ago) and, at strip 1, the A tile of kt + 1 (requested two steps ago, in
-                // front of that image).  Younger: what the previous step requested — an image (3 pieces), behind an A tile (4) when the
-                // previous step was a strip 2.  Steps 0 and 1 of a later tile: everything they read landed before the previous tile's
-                // stores were issued (vmcnt(0) there).  The last tile's tail requests nothing: count down to 0.
-                if (j > 0 && step < 2) {
-                } else if (!has_next && step + 1 >= nsteps) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                else if (!has_next && kt + 2 >= KT && s == 0 && kt + 1 >= KT) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-                else if (s == 0 && (has_next || kt + 1 < KT) && !(j == 0 && kt == 0)) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-                if (s == 2) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // strip 1's reads of the A tile are done before it is overwritten
-                __builtin_amdgcn_s_barrier();
-                // requests of this step: at strip 2 the A tile of kt + 2 (this tile's, or the next tile's kt + 2 - KT), then the image of step + 2
-                if (s == 2) {
-                    if (kt + 2 < KT) issue_a(cur, kt + 2);
-                    else if (has_next) {
-                        if (!nxt_ready) { tile_offsets(gm_nxt, nxt); nxt_ready = true; }
-                        issue_a(nxt, kt + 2 - KT);
-                    }
-                }
-                if (step + 2 < nsteps) issue_b(cur, step + 2, gstep + 2);
-                else if (has_next) issue_b(nxt, step + 2 - nsteps, gstep + 2);
-                const uint4* Bi = Bs[gstep % RING];
-                const int lslot = kg * 80 + lr;
-                bf16x8 bq[2][2];
-#pragma unroll
-                for (int p = 0; p < 2; ++p) bq[0][p] = __builtin_bit_cast(bf16x8, Bi[p * 320 + lslot]);
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    if (nt + 1 < NT) {
-#pragma unroll
-                        for (int p = 0; p < 2; ++p) bq[(nt + 1) & 1][p] = __builtin_bit_cast(bf16x8, Bi[p * 320 + lslot + (nt + 1) * 16]);
-                    }
-                    const bf16x8 b1 = bq[nt & 1][0], b2 = bq[nt & 1][1];
-                    v4f c[MT];
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) c[mt] = acc[s][mt][nt];
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) c[mt] = mma(b1, af[1][mt], c[mt]);   // x lo . w hi
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) c[mt] = mma(b2, af[0][mt], c[mt]);   // x hi . w lo
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) c[mt] = mma(b1, af[0][mt], c[mt]);   // x hi . w hi
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) acc[s][mt][nt] = c[mt];
-                    // the A tile of K tile kt + 1 (the next tile's K tile 0 behind the last one) landed at this step's wait
-                    if (s == 1 && nt == 0) split_mt(0, afn);
-                    if (s == 1 && nt == 2) split_mt(1, afn);
-                }
-                if (s == 1) {
-#pragma unroll
-                    for (int i = 0; i < 56; ++i) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-                    }
-                }
-                ++gstep;
-            }
-#pragma unroll
-            for (int p = 0; p < 2; ++p)
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) af[p][mt] = afn[p][mt];
-        }
-
-        // ---- epilogue of the tile (gemm_bf16x6s_kernel's, verbatim): the next tile's first operands must have landed before its stores
-        if (has_next) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const bool has_e0 = g.epi == EPI_RELU_RES || g.epi == EPI_ADD_E0;
-#pragma unroll
-        for (int s = 0; s < NSUB; ++s) {
-            const int ncol0 = (cur.strip0 + s) * 80;
-            const int seg = ncol0 / g.nseg;
-            const int nbase = ncol0 - seg * g.nseg + kg * 4;
-            const float* const bp = g.bias[seg];
-            const bool radd_here = g.radd && seg == g.radd_seg;
-            const bool y16 = (g.bf16_segs >> seg) & 1;
-            const bool y8 = (g.fp8_segs >> seg) & 1;
-            float4 bv[NT];
-            if (bp) {
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) bv[nt] = *reinterpret_cast<const float4*>(bp + nbase + nt * 16);
-            }
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) {
-                const int gm = gmv[mt];
-                float* const yrow = g.y[seg] + (long)gm * g.ldy;
-                float4 rv[NT], ev[NT];
-                if (radd_here) {
-                    const float* rrow = g.radd + (long)(gm / g.rows_per_b) * g.nseg + nbase;
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) rv[nt] = *reinterpret_cast<const float4*>(rrow + nt * 16);
-                }
-                if (y8) {
-                    float4 vv[NT];
-                    float amx = 0.f;
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) {
-                        const v4f a = acc[s][mt][nt];
-                        constexpr float u = 1.f / (F16_WEIGHT_SCALE * F16_ACT_SCALE);
-                        float4 v = make_float4(a[0] * u, a[1] * u, a[2] * u, a[3] * u);
-                        if (bp) v = f4_add(v, bv[nt]);
-                        if (radd_here) v = f4_add(rv[nt], v);
-                        vv[nt] = v;
-                        amx = fmaxf(fmaxf(amx, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-                    }
-                    amx = fmaxf(amx, __shfl_xor(amx, 16, 64));
-                    amx = fmaxf(amx, __shfl_xor(amx, 32, 64));
-                    const float scale = amx > 0.f ? amx * (1.f / 448.f) : 1.f;
-                    const float inv = 1.f / scale;
-                    unsigned char* const row8 = reinterpret_cast<unsigned char*>(g.y[seg]) + (long)gm * g.ldy8;
-                    if (rok[mt]) {
-#pragma unroll
-                        for (int nt = 0; nt < NT; ++nt) {
-                            int w = 0;
-                            w = __builtin_amdgcn_cvt_pk_fp8_f32(vv[nt].x * inv, vv[nt].y * inv, w, false);
-                            w = __builtin_amdgcn_cvt_pk_fp8_f32(vv[nt].z * inv, vv[nt].w * inv, w, true);
-                            *reinterpret_cast<int*>(row8 + nbase + nt * 16) = w;
-                        }
-                        if (kg == 0) *reinterpret_cast<float*>(row8 + g.nseg + 4 * ((ncol0 - seg * g.nseg) / 80)) = scale;
-                    }
-                    continue;
-                }
-                if (has_e0) {
-                    const float* erow = g.e0 + (long)gm * g.lde0 + nbase;
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) ev[nt] = *reinterpret_cast<const float4*>(erow + nt * 16);
-                } else if (g.epi == EPI_ACCUM) {
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) ev[nt] = *reinterpret_cast<const float4*>(yrow + nbase + nt * 16);
-                }
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    const int nn = nbase + nt * 16;
-                    const v4f a = acc[s][mt][nt];
-                    constexpr float u = 1.f / (F16_WEIGHT_SCALE * F16_ACT_SCALE);
-                    float4 v = make_float4(a[0] * u, a[1] * u, a[2] * u, a[3] * u);
-                    if (bp) v = f4_add(v, bv[nt]);
-                    if (radd_here) v = f4_add(rv[nt], v);
-                    if (y16) {
-                        if (rok[mt])
-                            *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(g.y[seg]) + (long)gm * g.ldy + nn) =
-                                make_uint2(pack_bf16_rne(v.x, v.y), pack_bf16_rne(v.z, v.w));
-                        continue;
-                    }
-                    if (g.epi == EPI_RELU_RES) {
-                        const float4 x = ev[nt];
-                        v = make_float4(fmaxf(v.x, 0.f) + x.x, fmaxf(v.y, 0.f) + x.y, fmaxf(v.z, 0.f) + x.z, fmaxf(v.w, 0.f) + x.w);
-                    }
-                    if (g.epi == EPI_ACCUM || g.epi == EPI_ADD_E0) v = f4_add(ev[nt], v);
-                    if (rok[mt]) *reinterpret_cast<float4*>(yrow + nn) = v;
-                }
-            }
-        }
-        if (!has_next) break;
-        cur = nxt;
-        ++j;
-    }
-    if (g.range_flag && __builtin_amdgcn_ballot_w64(!(amax < 65504.f)) != 0 && lane == 0) atomicOr(g.range_flag, 1u);
-}
-#endif
-
-// 1b'. LAB builds only: the ping-pong variant of the kernel above (round 4; measured and not shipped, docs/REJECTED.md) lives in
-// digat_gemm_lab.inc so that the product translation unit carries only what it launches.
-#ifdef DIGAT_LAB
-#include "digat_gemm_lab.inc"
-#endif
 
 // 1c. skinny linear for the [B,d] projections (M < 2048): a latency chain, not a throughput problem
 // =================================================================================================
@@ -1597,10 +1257,6 @@ static double gemm_row_bytes(const GemmArgs& g) {
 
 static int launch_gemm(GemmArgs g, hipStream_t st, int kind = DIGAT_KERNEL_LINEAR) {
     if (g.M <= 0) return DIGAT_OK;
-#ifdef DIGAT_LAB
-    static const int diag = LAB_ENV("DIGAT_GEMM_DIAG", 0);
-    g.diag = diag;
-#endif
     if (g.rowidx && !gemm_is_bf16x6(g)) return DIGAT_ERR_ARG;
     const int Ntot = g.nseg * g.nsegs;
     const int Md = g.m_dispatch > 0 ? g.m_dispatch : g.M;
@@ -1619,11 +1275,10 @@ static int launch_gemm(GemmArgs g, hipStream_t st, int kind = DIGAT_KERNEL_LINEA
         DIGAT_CHECK_LAUNCH();
         return DIGAT_OK;
     }
-    static const int skinny_split_on = LAB_ENV("DIGAT_SKINNY_SPLIT", 1);
     // up to 2 048 rows (the encoder's [B,d] linears say which kernel they want through m_dispatch: 1 = this one at every row count —
     // the gate's two-operand launch always does: the tiled split-operand kernel does not take [c_n | pooled], and at 4 096 rows it
     // fell to the fp32 kernel on 160 workgroups, 88 us against 33 us here)
-    if (Md < 2048 && g.wsplit && skinny_split_on && g.nseg % 80 == 0 && !g.transW && g.K % 8 == 0 && g.k0 % 8 == 0 && !g.radd && !g.rowidx &&
+    if (Md < 2048 && g.wsplit && g.nseg % 80 == 0 && !g.transW && g.K % 8 == 0 && g.k0 % 8 == 0 && !g.radd && !g.rowidx &&
         g.ldy % 4 == 0 && g.lda0 % 4 == 0 && (!g.a1 || g.lda1 % 4 == 0) && g.lde0 % 4 == 0 && g.lde1 % 4 == 0 && g.lde2 % 4 == 0 &&
         (g.epi == EPI_NONE || g.epi == EPI_RELU_RES || g.epi == EPI_GATE || g.epi == EPI_ACCUM)) {
         // the [B,d] linears of the inference path on the weights' split images (gemm_skinny_split_kernel)
@@ -1701,43 +1356,10 @@ static int launch_gemm(GemmArgs g, hipStream_t st, int kind = DIGAT_KERNEL_LINEA
         const int made_as = wsplit_format_of(g.wsplit);
         if (made_as >= 0 && made_as != g.format) return DIGAT_ERR_ARG;       // the image was split for the other kernel
         const bool f16 = g.format == 1;
-#ifdef DIGAT_LAB
-        // experiments, measured slower (see the kernels): the ping-pong form (same bits) and 64-row "fat" wave tiles
-        static const int pp_rows = LAB_ENV("DIGAT_GEMM_PP", 0);           // from this many rows up (0 = never)
-        if (strips % 3 == 0 && f16 && pp_rows > 0 && Md >= pp_rows && g.epi == EPI_NONE && !g.x1_segs) {
-            g.ntiles = strips / 3;
-            g.mtiles = (g.M + 255) / 256;
-            const dim3 grid((unsigned)(((g.mtiles * g.ntiles + 7) / 8) * 8));
-            if (g.a_split) hipLaunchKernelGGL(gemm_f16x3_pp_kernel<true>, grid, dim3(512), 0, st, g);
-            else hipLaunchKernelGGL(gemm_f16x3_pp_kernel<false>, grid, dim3(512), 0, st, g);
-            DIGAT_CHECK_LAUNCH();
-            return DIGAT_OK;
-        }
-        static const int thin = LAB_ENV("DIGAT_GEMM_THIN", 0);
-        if (strips % 3 == 0 && f16 && thin && g.M >= thin && !g.a_split) {      // 16-row wave tiles, 64-row workgroups, four per CU
-            g.ntiles = strips / 3;
-            g.mtiles = (g.M + 63) / 64;
-            const dim3 grid((unsigned)(((g.mtiles * g.ntiles + 7) / 8) * 8));
-            hipLaunchKernelGGL((gemm_bf16x6s_kernel<3, true, 1>), grid, dim3(256), 0, st, g);
-            DIGAT_CHECK_LAUNCH();
-            return DIGAT_OK;
-        }
-        static const int fat = LAB_ENV("DIGAT_GEMM_FAT", 0);
-        if (strips % 3 == 0 && f16 && fat && g.M >= fat) {      // 64-row wave tiles, one wave per SIMD: 963 vs 522 us (hipcc shuffles
-                                                                // the 240 AGPR accumulators through the loop's back edge: ~700 moves per K tile)
-            g.ntiles = strips / 3;
-            g.mtiles = (g.M + 255) / 256;
-            const dim3 grid((unsigned)(((g.mtiles * g.ntiles + 7) / 8) * 8));
-            hipLaunchKernelGGL((gemm_bf16x6s_kernel<3, true, 4>), grid, dim3(256), 0, st, g);
-            DIGAT_CHECK_LAUNCH();
-            return DIGAT_OK;
-        }
-#endif
         // Launches that leave the chip under-filled at 128-row tiles (a 4 096-row pass's [B,d] linears and news-side projections: 160
-        // workgroups for 256 CUs, each a 13-step latency chain) take 64-row tiles: twice the workgroups, the same chain.  LAB: DIGAT_GEMM_SMALL_MT=0 keeps 128.
-        static const int small_mt = LAB_ENV("DIGAT_GEMM_SMALL_MT", 1);
+        // workgroups for 256 CUs, each a 13-step latency chain) take 64-row tiles: twice the workgroups, the same chain.
         const int wg128 = g.mtiles * (strips % 3 == 0 ? strips / 3 : strips);
-        if (small_mt && f16 && wg128 < 400 && !g.a_split) {
+        if (f16 && wg128 < 400) {
             g.ntiles = strips % 3 == 0 ? strips / 3 : strips;
             g.mtiles = (g.M + 63) / 64;
             const dim3 grid((unsigned)(((g.mtiles * g.ntiles + 7) / 8) * 8));
@@ -1747,7 +1369,7 @@ static int launch_gemm(GemmArgs g, hipStream_t st, int kind = DIGAT_KERNEL_LINEA
             return DIGAT_OK;
         }
         // the same for the bf16x6 launches of a training step's news graph (3 200 rows: 125 workgroups at 128-row tiles; round 6)
-        if (small_mt && !f16 && wg128 < 400 && !g.rowidx) {
+        if (!f16 && wg128 < 400 && !g.rowidx) {
             g.ntiles = strips % 3 == 0 ? strips / 3 : strips;
             g.mtiles = (g.M + 63) / 64;
             const dim3 grid((unsigned)(((g.mtiles * g.ntiles + 7) / 8) * 8));
@@ -1759,24 +1381,8 @@ static int launch_gemm(GemmArgs g, hipStream_t st, int kind = DIGAT_KERNEL_LINEA
         if (strips % 3 == 0) {           // 240-column tiles: the operand split is paid once per three strips
             g.ntiles = strips / 3;
             const dim3 grid((unsigned)(((g.mtiles * g.ntiles + 7) / 8) * 8));
-            // LAB: DIGAT_GEMM_LDSPAD=<KB> of unused dynamic LDS per workgroup (80: ONE workgroup per CU, one wave per SIMD — does a
-            // co-running latency-bound kernel of another launch set gain more from the freed registers than this one loses?)
-            static const int ldspad = LAB_ENV("DIGAT_GEMM_LDSPAD", 0);
-#ifdef DIGAT_LAB
-            static const int persist = LAB_ENV("DIGAT_GEMM_PERSIST", 0);
-#endif
-#ifdef DIGAT_LAB
-            if (f16 && g.a_split) hipLaunchKernelGGL((gemm_bf16x6s_kernel<3, true, 2, true>), grid, dim3(256), 0, st, g);     // pre-split A rows: LAB
-            else
-#endif
-#ifdef DIGAT_LAB
-            if (f16 && !g.x1_segs && !g.x3_segs && DIGAT_GEMM_FULL && persist && g.K > 32 && !g.a1) {
-                // persistent form: two workgroups per CU walk the tiles (no prologue after the first tile, stores not waited for)
-                hipLaunchKernelGGL(gemm_f16x3_persist_kernel, dim3(512), dim3(256), 0, st, g);
-            } else
-#endif
-            if (f16 && !g.x1_segs && !g.x3_segs && DIGAT_GEMM_FULL) hipLaunchKernelGGL((gemm_bf16x6s_kernel<3, true, 2, false, true>), grid, dim3(256), (size_t)ldspad * 1024, st, g);
-            else if (f16) hipLaunchKernelGGL((gemm_bf16x6s_kernel<3, true>), grid, dim3(256), (size_t)ldspad * 1024, st, g);
+            if (f16 && !g.x1_segs && !g.x3_segs && DIGAT_GEMM_FULL) hipLaunchKernelGGL((gemm_bf16x6s_kernel<3, true, 2, false, true>), grid, dim3(256), 0, st, g);
+            else if (f16) hipLaunchKernelGGL((gemm_bf16x6s_kernel<3, true>), grid, dim3(256), 0, st, g);
             else hipLaunchKernelGGL((gemm_bf16x6s_kernel<3, false>), grid, dim3(256), 0, st, g);
         } else {
             g.ntiles = strips;

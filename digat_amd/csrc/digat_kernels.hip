@@ -35,17 +35,6 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-// Development knobs read from the environment — A/B switches between two kernels that give the same results, timing ablations
-// that give WRONG results (DIGAT_*_SKIP), phase timers — exist in LAB builds only (-DDIGAT_LAB: tools/exp/build_variant.sh).  In
-// the product library LAB_ENV is its default and the variable's name is not even in the binary: no environment variable can
-// change what a scoring run computes (tests/test_abi_cpu.py looks for the names).
-#ifdef DIGAT_LAB
-static int lab_env_value(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-#define LAB_ENV(name, dflt) lab_env_value(name, dflt)
-#else
-#define LAB_ENV(name, dflt) (dflt)
-#endif
-
 // ---- optional per-kernel event timing (bench.py's roofline leg) ---------------------------------
 // Between digat_profile_start and digat_profile_stop every launch is bracketed by two hipEvents
 // recorded on the stream the kernel is launched on; stop() synchronises once and sums elapsed time
@@ -203,17 +192,6 @@ constexpr int TWIN_R = DIGAT_TWIN_R;   // centres with equal adjacency rows serv
 #include "digat_context.inc"
 #include "digat_ctxfused.inc"
 #include "digat_glue.inc"
-#ifdef DIGAT_LAB
-#include "digat_staged.inc"       // Eq. 8 of the user graph from LDS-staged rows: five variants, all measured slower (docs/REJECTED.md, row 7)
-#else
-// the product library carries the evidence (profiles/), not the code path
-struct PlanBuffers {};
-static size_t plan_bytes(int, int) { return 0; }
-static bool staged_ok(int, int) { return false; }
-static PlanBuffers plan_carve(void*, int, int) { return PlanBuffers{}; }
-static int launch_staged(const SparseArgs&, const PlanBuffers&, int, int, hipStream_t) { return DIGAT_ERR_ARG; }
-static int launch_plan(const uint8_t*, const uint8_t*, const int64_t*, const int*, int, int, int, int, int, int, bool, const PlanBuffers&, hipStream_t) { return DIGAT_ERR_ARG; }
-#endif
 
 // =================================================================================================
 // C ABI
@@ -255,9 +233,6 @@ int digat_xattn_pairwise_fwd(const float* Pr, const float* Q, const float* h, co
 }
 
 struct TwinLists { const unsigned* word; const int* list; const int* count; };     // user_live_flags_kernel's twins (see there)
-// pre-split node rows between two Eq. 8 layers (fp16x3 format): `in` = the rows of X as the previous layer's Eq. 8 kernel stored
-// them for this layer's projection GEMM (GemmArgs.a_split), `out` = where this layer's Eq. 8 kernel stores its output rows for the next
-struct SplitIO { const void* in; unsigned char* out; unsigned* range; };
 
 // Eq. 8 layer with K3 (r = ctx F3^T + b3) already computed; `r_given` may live anywhere
 static int xattn_core(const float* X, const uint8_t* A, const float* r_given,
@@ -265,9 +240,8 @@ static int xattn_core(const float* X, const uint8_t* A, const float* r_given,
                       float* out, float* alpha_out, int B, int n, int d, void* workspace, hipStream_t st,
                       const void* wsplit = nullptr, const int* rowidx = nullptr, const int* nrows_dev = nullptr,
                       const uint8_t* live = nullptr, int sparse_mode = DIGAT_XATTN_DENSE, const int* sparse_flag = nullptr,
-                      int pq_x3 = 0, const PlanBuffers* plan = nullptr, int plan_slot = 0, int pq_mode = 0, int centre_limit = 0,
-                      int gemm_format = 0, unsigned* range_flag = nullptr, const TwinLists* tw = nullptr, const SplitIO* sio = nullptr,
-                      int prof_part = 0) {
+                      int pq_x3 = 0, int pq_mode = 0, int centre_limit = 0, int gemm_format = 0, unsigned* range_flag = nullptr,
+                      const TwinLists* tw = nullptr, int prof_part = 0) {
     const size_t nd = (size_t)B * n * d;
     float* h = (float*)workspace;
     float* P = h + nd;
@@ -284,30 +258,27 @@ static int xattn_core(const float* X, const uint8_t* A, const float* r_given,
     g.radd = r_given; g.radd_seg = 1; g.rows_per_b = n; // P' = K3 + K1: the reference's left-to-right order
     g.x3_segs = pq_x3 ? 6 : 0;                          // DIGAT_PROJ_PQ_X3: P and Q (segments 1, 2) with three products
     // DIGAT_PQ_BF16 (pq_mode & 1): P' and Q stored in bf16, read by the wave-per-centre sparse kernel; & 2: one product for them
-    const bool pq16 = (pq_mode & 1) && gemm_is_bf16x6(g) && sparse_mode == DIGAT_XATTN_SPARSE && !alpha_out && !plan && n > 16 &&
+    const bool pq16 = (pq_mode & 1) && gemm_is_bf16x6(g) && sparse_mode == DIGAT_XATTN_SPARSE && !alpha_out && n > 16 &&
                       d / 4 <= 256 && d % 8 == 0 && (long)B * n >= 2048;
     // DIGAT_PQ_FP8 (pq_mode & 4): P' and Q stored as block-scaled e4m3 rows (one fp32 scale per 80-channel strip), same reader
-    const bool pq8 = (pq_mode & 4) && !(pq_mode & 1) && gemm_is_bf16x6(g) && sparse_mode == DIGAT_XATTN_SPARSE && !alpha_out && !plan && n > 16 &&
+    const bool pq8 = (pq_mode & 4) && !(pq_mode & 1) && gemm_is_bf16x6(g) && sparse_mode == DIGAT_XATTN_SPARSE && !alpha_out && n > 16 &&
                      d / 4 <= 256 && d % 80 == 0 && (long)B * n >= 2048;
     const long ld8 = (long)align_up((size_t)d + 4 * (size_t)(d / 80), 64);      // [d codes | d / 80 scales | pad]: whole 64-byte lines
     if (pq16) { g.bf16_segs = 6; if (pq_mode & 2) g.x1_segs = 6; }
     if (pq8) { g.fp8_segs = 6; g.ldy8 = ld8; if (pq_mode & 2) g.x1_segs = 6; }
     const bool listed = rowidx && gemm_is_bf16x6(g);
     if (listed) { g.rowidx = rowidx; g.nrows_dev = nrows_dev; }                         // live rows only (see user_live_flags_kernel)
-    if (sio && sio->in && listed && gemm_format == 1 && d % 8 == 0) g.a_split = sio->in;    // the rows arrive split: no operand split in the GEMM
     const int rc = launch_gemm(g, st, DIGAT_KERNEL_PROJ);
     if (rc) return rc;
     const int* skip_if = nullptr;
     if (sparse_mode != DIGAT_XATTN_DENSE && !alpha_out && n > 16 && d / 4 <= 256) {      // see xattn_sparse_kernel
         SparseArgs sg{P, Q, h, X, a, A, out, nullptr, nullptr, listed ? live : nullptr,
                       sparse_mode == DIGAT_XATTN_AUTO ? sparse_flag : nullptr, B, n, d / 4, 0, nullptr, nullptr,
-                      listed && live ? rowidx : nullptr, listed && live ? nrows_dev : nullptr, 0, nullptr, pq8 ? 2 : (pq16 ? 1 : 0), plan ? 0 : centre_limit};
+                      listed && live ? rowidx : nullptr, listed && live ? nrows_dev : nullptr, 0, nullptr, pq8 ? 2 : (pq16 ? 1 : 0), centre_limit};
         sg.ld8 = pq8 ? ld8 : 0;
         sg.prof_part = prof_part;
-        if (tw && listed && live && !plan) { sg.twin = tw->word; sg.twlist = tw->list; sg.twcount = tw->count; }
-        if (sio && sio->out && listed && live && !plan && sparse_mode == DIGAT_XATTN_SPARSE) { sg.xsplit = sio->out; sg.xsplit_range = sio->range; }
-        // with a plan of the batch (encoder entry points): the LDS-staged kernel, each needed row read once (digat_staged.inc)
-        const int rcs = plan ? launch_staged(sg, *plan, listed && live ? 1 : 0, plan_slot, st) : launch_sparse(sg, st);
+        if (tw && listed && live) { sg.twin = tw->word; sg.twlist = tw->list; sg.twcount = tw->count; }
+        const int rcs = launch_sparse(sg, st);
         if (rcs || sparse_mode == DIGAT_XATTN_SPARSE) return rcs;
         skip_if = sparse_flag;
     }
@@ -366,7 +337,7 @@ int digat_xattn_fwd_lowprec(const float* X, const uint8_t* A, const float* ctx,
     const int rc = launch_gemm(gemm_plain(ctx, d, F3, b3, r, d, B, d, d, 0), st);
     if (rc) return rc;
     return xattn_core(X, A, r, W, bW, F1, F2, a, out, nullptr, B, n, d, workspace, st, wsplit, nullptr, nullptr, nullptr, DIGAT_XATTN_SPARSE,
-                      nullptr, 0, nullptr, 0, pq == 1 ? 1 : (pq == 2 ? 4 : 0), 0, format, nullptr);
+                      nullptr, 0, pq == 1 ? 1 : (pq == 2 ? 4 : 0), 0, format, nullptr);
 }
 
 // ---- bf16x6 weight preparation + a directly callable linear (tests, micro-benchmarks) --------------
@@ -386,11 +357,7 @@ struct PremadeImage {
 static int launch_split(const float* w0, const float* w1, const float* w2, int nseg, int nsegs, int K, void* wsplit, hipStream_t st,
                         int transposed = 0, int format = 0) {
     if (format != 0 && format != 1) return DIGAT_ERR_ARG;
-#ifdef DIGAT_LAB
-    if (wsplit && wsplit == tl_premade_image && format == 0) return DIGAT_OK;      // (LAB, DIGAT_TRAIN_F16: an fp16x3 image is split over the ready-made one)
-#else
     if (wsplit && wsplit == tl_premade_image) return format == 0 ? DIGAT_OK : DIGAT_ERR_ARG;
-#endif
     const long total = (long)nseg * nsegs * K;
     int blocks = (int)((total + 255) / 256);
     if (blocks > 2048) blocks = 2048;
@@ -658,8 +625,7 @@ static size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
 // the queries derived from the new c_n — is independent of the user graph's Eq. 8 until the user context is
 // pooled.  The news kernels are small (N = 10 nodes, [B,d] linears: tens of workgroups, latency chains) and run
 // on a side stream under the user graph's projection / score / aggregation, which fill the chip; fork and join
-// are two events per layer (a pattern hipGraph capture accepts).  DIGAT_SINGLE_STREAM=1 keeps everything on the
-// caller's stream.
+// are two events per layer (a pattern hipGraph capture accepts).
 static size_t l0_chunk_bytes(int B, int U);      // the extra lists of the folded path (defined with the workspace sizes below)
 // group-level outputs of user_live_flags_kernel (grouped entries: at most B / 4 groups), expanded to rows by live_expand_kernel
 static size_t live_group_bytes(int B, int U, int C1) {
@@ -674,21 +640,9 @@ struct SideStream { hipStream_t s; hipEvent_t fork, join, early; int ok; };
 // Nothing below is mutable: live-row lists and the side stream are chosen PER CALL through digat_params.flags
 // (DIGAT_PARAMS_NO_LIVE_ROWS, DIGAT_PARAMS_SIDE_STREAM_OFF / _ON), so two host threads with different settings cannot flip each
 // other's (round 3 had process-wide setters for them).
-static const int g_sparse_per_node = LAB_ENV("DIGAT_SPARSE_PER_NODE", 20);
-// 0 = never, 1 = always, 2 = by pass size (default): below 2 048 rows — there the news kernels are a few waves of workgroups each;
-// from 2 048 rows up every kernel fills the chip by itself and the second stream only makes launches share it (4 096 rows,
-// three passes in flight: 3.21 vs 3.28 ms per pass; stress 16.4 vs 16.8, MIND-large shape 4.52 vs 4.65).  DIGAT_SINGLE_STREAM=1 / 0
-// forces never / always.
-static const int g_side_stream_lab = LAB_ENV("DIGAT_SINGLE_STREAM", -1);       // LAB builds: 1 / 0 force never / always
-// layer 0 of the user graph on the live nodes only (A/B switch for measurements; DIGAT_L0_LIVE=0: every node at layer 0)
-static const int g_l0_live_on = LAB_ENV("DIGAT_L0_LIVE", 1);
-// 0 (default): the wave-per-centre sparse kernel; 1: the LDS-staged kernels of digat_staged.inc (compulsory HBM traffic, measured
-// slower in round 2: DESIGN.md section 4)
-#ifdef DIGAT_LAB
-static int g_staged_on = LAB_ENV("DIGAT_XATTN_STAGED", 0);
-#else
-static constexpr int g_staged_on = 0;
-#endif
+// Eq. 8 of a batch goes to the sparse kernel when its adjacency holds at most this many entries per node on average
+// (sparse_decide_kernel, train_sparse_decide_kernel)
+constexpr int SPARSE_PER_NODE = 20;
 // One side stream (and its three events) per CALLER stream: consecutive batches issued on alternating caller streams
 // (util.batch_streams) then overlap their side work too, and two host threads driving two streams never touch the same
 // events.  A caller stream is expected to be driven by one thread at a time (include/digat_hip.h, threading contract); the
@@ -707,12 +661,7 @@ static SideStream* side_stream(hipStream_t caller) {
     Entry& e = tab[used++];
     e.dev = dev; e.caller = caller;
     SideStream& x = e.side;
-    // LAB builds: DIGAT_SIDE_PRIO=1 makes the side stream a high-priority queue (its small news-side kernels are dispatched ahead of the
-    // caller stream's long-running Eq. 8 / GEMM workgroups whenever a slot frees up)
-    static const int side_prio = LAB_ENV("DIGAT_SIDE_PRIO", 0);
-    int prio_lo = 0, prio_hi = 0;
-    if (side_prio) (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    const bool ok = (side_prio ? hipStreamCreateWithPriority(&x.s, hipStreamNonBlocking, prio_hi) : hipStreamCreateWithFlags(&x.s, hipStreamNonBlocking)) == hipSuccess &&
+    const bool ok = hipStreamCreateWithFlags(&x.s, hipStreamNonBlocking) == hipSuccess &&
                     hipEventCreateWithFlags(&x.fork, hipEventDisableTiming) == hipSuccess &&
                     hipEventCreateWithFlags(&x.join, hipEventDisableTiming) == hipSuccess &&
                     hipEventCreateWithFlags(&x.early, hipEventDisableTiming) == hipSuccess;
@@ -725,8 +674,8 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
                               float* c_n, float* c_u, int B, int N, int H, float* const Xu[2], float* const Xn[2],
                               void* xws, void* xws_news, void* cws, float* kq_t, float* kq_u, float* const r_user2[2],
                               float* r_news, int* live_ws, hipStream_t st, const int* row_group, int G, const float* ue_groups,
-                              const float* Xg0, const float* news_hpq0, const float* hist_hpq0, const float* topic_hpq0, void* plan_ws,
-                              void* chunk_ws, unsigned char* xsplit_ws, const uint8_t* Au_g, const uint8_t* cm_g, const int64_t* ci_g, const float* ctxq0,
+                              const float* Xg0, const float* news_hpq0, const float* hist_hpq0, const float* topic_hpq0,
+                              void* chunk_ws, const uint8_t* Au_g, const uint8_t* cm_g, const int64_t* ci_g, const float* ctxq0,
                               const int64_t* news_index, int64_t news_rows, const float* c_n_src, void* live_g_ws = nullptr,
                               const uint8_t* run_leader = nullptr, const uint8_t* run_lead = nullptr, void* news_live_ws = nullptr) {
     // SHARED-USER RUNS (digat_encoder_fwd_shared; round 5): the user tensors are given per ROW, as the reference's driver hands them
@@ -772,9 +721,9 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
                              const uint8_t* live = nullptr, const float* kq_topic = nullptr, const float* kq_user = nullptr) -> int {
         if (!kq_topic) { kq_topic = kq_t; kq_user = kq_u; }
         // ONE launch (digat_ctxfused.inc) when the weight version carries the fused image and the shape fits; T, T2 stay unused then
-        if (p->featureAffine_fsplit && fmt == 1 && ctxfused_ok(H, C1, d) && LAB_ENV("DIGAT_CTX_FUSED", 1) != 0) {
+        if (p->featureAffine_fsplit && fmt == 1 && ctxfused_ok(H, C1, d)) {
             const CtxFusedArgs fa{Xu_cur, (long)U * d, xgroup, live, U, live ? hist_last : nullptr, kq_topic, kq_user, cat_idx, cat_mask, addend, c_u,
-                                  (const uint4*)p->featureAffine_fsplit, p->featureAffine_b, rflag, B, H, C1, d, sqrtf((float)d), LAB_ENV("DIGAT_CF_DBG", 0)};
+                                  (const uint4*)p->featureAffine_fsplit, p->featureAffine_b, rflag, B, H, C1, d, sqrtf((float)d), 0};
             return launch_user_ctx_fused(fa, sq);
         }
         int e = launch_topic(Xu_cur, (long)U * d, kq_topic, cat_idx, T, B, H, C1, d, sq, xgroup, live, U, live ? hist_last : nullptr);
@@ -806,7 +755,7 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
         return launch_gemm(g, sq);
     };
 
-    const bool want_live = L > 0 && !(p->flags & DIGAT_PARAMS_NO_LIVE_ROWS) && LAB_ENV("DIGAT_NO_SKIP", 0) == 0 && live_ws;
+    const bool want_live = L > 0 && !(p->flags & DIGAT_PARAMS_NO_LIVE_ROWS) && live_ws;
     // Eq. 8 of the user graph: the sparse kernel, the dense pair, or both with the device choosing (p->flags; the choice
     // comes out of the adjacency pass of find_live_rows)
     int sparse_mode = p->flags & 3;
@@ -814,10 +763,7 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
     const int* sparse_flag = nullptr;
     const int pq_x3 = (p->flags & DIGAT_PROJ_PQ_X3) ? 1 : 0;
     const bool want_scan = want_live || sparse_mode == DIGAT_XATTN_AUTO;      // the adjacency pass: live lists and / or the decision
-    // sparse Eq. 8 of the user graph from LDS-staged rows (digat_staged.inc): needs the plan of the batch (units of centres)
-    const bool use_staged = L > 0 && g_staged_on && plan_ws && sparse_mode != DIGAT_XATTN_DENSE && U > 16 && staged_ok(U, d / 4);
-    const PlanBuffers plan = use_staged ? plan_carve(plan_ws, B, U) : PlanBuffers{};
-    // live rows of the user graph for the projections of layers >= 1 (DIGAT_NO_SKIP=1: every row)
+    // live rows of the user graph for the projections of layers >= 1
     const int* rowidx = nullptr;
     const int* nrows_dev = nullptr;
     uint8_t* live_flags = nullptr;
@@ -828,8 +774,7 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
     uint8_t* pend_flags = nullptr;
     // layer 0 of grouped rows on the chunk kernel (R rows of an impression per wave: xattn_sparse_l0_kernel): its list — the live
     // centres of the rows that lead a chunk — is made with the other two
-    static const int l0_chunks_on = LAB_ENV("DIGAT_L0_CHUNKS", 1);
-    const bool l0_chunked = l0_chunks_on && chunk_ws && row_group && (Xg0 || shared) && want_live && g_l0_live_on && !use_staged &&
+    const bool l0_chunked = chunk_ws && row_group && (Xg0 || shared) && want_live &&
                             sparse_mode == DIGAT_XATTN_SPARSE && d / 4 <= 128 && U <= 128;
     int* const l0_gs = (int*)chunk_ws;
     int* const l0_off = l0_gs + align_up((size_t)B + 64, 64);
@@ -837,8 +782,7 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
     const uint8_t* const l0_lead = shared ? run_lead : l0_lead_own;          // shared runs: the chunk sizes came with the runs
     int* const l0_idx = (int*)(l0_lead_own + align_up((size_t)B, 256));
     // twins: centres of a graph with equal adjacency rows, served together in layers >= 1 (xattn_sparse_twin_kernel)
-    static const int twins_on = LAB_ENV("DIGAT_SPARSE_TWINS", 1);
-    const bool twins = twins_on && chunk_ws && want_live && !use_staged && sparse_mode == DIGAT_XATTN_SPARSE && d / 4 <= 128 && U <= 128 && L > 1;
+    const bool twins = chunk_ws && want_live && sparse_mode == DIGAT_XATTN_SPARSE && d / 4 <= 128 && U <= 128 && L > 1;
     unsigned* const tw_word = (unsigned*)((char*)l0_idx + align_up((size_t)B * U * 4, 256));
     int* const tw_list = (int*)((char*)tw_word + align_up((size_t)B * U * 4, 256));
     uint8_t* const tw_flags = (uint8_t*)tw_list + align_up((size_t)B * U * 4, 256);
@@ -848,14 +792,6 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
     int* const gl_off = tw_off + align_up((size_t)B + 64, 64);
     int* const gl_idx = gl_off + align_up((size_t)B + 64, 64);
     TwinLists tw_pub{nullptr, nullptr, nullptr};
-    // Node rows between two layers also as ready-split fp16 pairs (fp16x3 format, sparse Eq. 8 on the live lists): the Eq. 8 kernel of
-    // layer i stores them, the projection GEMM of layer i + 1 reads its A fragments as they are (GemmArgs.a_split; same bits)
-    // MEASURED (round 4): the shipped GEMM loses 5-8 % of its time with it (its step is bound by the lockstep of its two workgroups,
-    // not by the split), the Eq. 8 kernels lose as much storing the second copy: LAB builds only, off by default.
-    static const int presplit_on = LAB_ENV("DIGAT_PRESPLIT", 0);
-    const bool presplit = presplit_on && xsplit_ws && fmt == 1 && want_live && !use_staged && sparse_mode == DIGAT_XATTN_SPARSE &&
-                          d % 8 == 0 && d / 4 <= 256 && U > 16 && (long)B * U >= 2048 && L > 1;
-    bool xs_ready = false;            // the split rows of the CURRENT user nodes exist (written by the previous layer's Eq. 8 kernel)
     auto find_live_rows = [&](hipStream_t sq) -> int {
         int* cnt = live_ws;
         int* off = cnt + align_up((size_t)B, 64);
@@ -913,7 +849,7 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
             DIGAT_CHECK_LAUNCH();
         }
         if (sparse_mode == DIGAT_XATTN_AUTO) {
-            hipLaunchKernelGGL(sparse_decide_kernel, dim3(1), dim3(1024), 0, sq, (const int*)entries, B, U, g_sparse_per_node, flag);
+            hipLaunchKernelGGL(sparse_decide_kernel, dim3(1), dim3(1024), 0, sq, (const int*)entries, B, U, SPARSE_PER_NODE, flag);
             DIGAT_CHECK_LAUNCH();
             sparse_flag = flag;
         }
@@ -946,21 +882,15 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
         pend_rowidx = idx; pend_nrows = off + B; pend_bidx = idx2; pend_nb = off2 + B; pend_flags = flags1; pend_hlast = hlast;
         return DIGAT_OK;
     };
-    // the plan follows the live flags on the same stream (its second list is the live centres)
-    // one plan per distinct user graph: per group when the caller gave the user side per group, else per row
-    auto make_plan = [&](hipStream_t sq) -> int {
-        const bool per_group = row_group && Au_g && cm_g && ci_g;
-        return launch_plan(per_group ? Au_g : Au, per_group ? cm_g : cat_mask, per_group ? ci_g : cat_idx, per_group ? row_group : nullptr,
-                           B, per_group ? G : B, U, H, C1, d / 4, want_live, plan, sq);
-    };
     auto publish_live_rows = [&]() {
         rowidx = pend_rowidx; nrows_dev = pend_nrows; bucket_idx = pend_bidx; nbuckets_dev = pend_nb; live_flags = pend_flags;
         hist_last = pend_hlast;
         if (twins) tw_pub = TwinLists{tw_word, tw_list, tw_off + B};
     };
-    // side stream: by pass size unless the caller says (flags): never / always
-    int side_mode = (p->flags & DIGAT_PARAMS_SIDE_STREAM_OFF) ? 0 : ((p->flags & DIGAT_PARAMS_SIDE_STREAM_ON) ? 1 : 2);
-    if (g_side_stream_lab >= 0) side_mode = g_side_stream_lab ? 0 : 1;
+    // side stream: 0 = never, 1 = always (the caller's flags), 2 = by pass size (default): below 2 048 rows — there the news kernels
+    // are a few waves of workgroups each; from 2 048 rows up every kernel fills the chip by itself and the second stream only makes
+    // launches share it (4 096 rows, three passes in flight: 3.21 vs 3.28 ms per pass; stress 16.4 vs 16.8, MIND-large shape 4.52 vs 4.65)
+    const int side_mode = (p->flags & DIGAT_PARAMS_SIDE_STREAM_OFF) ? 0 : ((p->flags & DIGAT_PARAMS_SIDE_STREAM_ON) ? 1 : 2);
     SideStream* side = (side_mode == 0 || (side_mode == 2 && B >= 2048)) ? nullptr : side_stream(st);
     // Small news graphs (the wave-per-centre score kernel adds K3 itself): the node projections of a layer depend only on
     // the news nodes, so they are issued on the side stream a phase early — layer 0's under the initial user context,
@@ -970,7 +900,7 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
     // (news_live_flags_kernel); the context pooling masks them and skips zero weights, nobody else reads them.  Larger graphs
     // (N > 16, sparse kernel): projection and Eq. 8 run on the live list.  Small graphs: the projections of layers >= 1 do; the
     // one-workgroup-per-graph Eq. 8 kernel still computes every centre (a live centre visits its adjacency entries only: live nodes).
-    const bool news_lists_on = L > 0 && news_live_ws && d / 4 <= 256 && !(p->flags & DIGAT_PARAMS_NO_LIVE_ROWS) && LAB_ENV("DIGAT_NEWS_LIVE", 1) != 0;
+    const bool news_lists_on = L > 0 && news_live_ws && d / 4 <= 256 && !(p->flags & DIGAT_PARAMS_NO_LIVE_ROWS);
     const bool news_lists = news_lists_on && ((!news_early && (p->flags & DIGAT_NEWS_XATTN_SPARSE) && N > 16) || (news_early && L > 1 && B >= 2048));
     // (small graphs below 2 048 rows: the three list launches sit on the news chain's critical path and cost what two smaller projections save)
     const int* news_rowidx = nullptr; const int* news_nrows = nullptr; const uint8_t* news_flags = nullptr;
@@ -1059,24 +989,15 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
         if (hipEventRecord(side->fork, st) != hipSuccess || hipStreamWaitEvent(side->s, side->fork, 0) != hipSuccess)
             return DIGAT_ERR_LAUNCH;
     }
-    const bool plan_early = side && use_staged;
-    if (side && plan_early && !(news_early || group_early || live_early)) {
-        if (hipEventRecord(side->fork, st) != hipSuccess || hipStreamWaitEvent(side->s, side->fork, 0) != hipSuccess)
-            return DIGAT_ERR_LAUNCH;
-    }
     if (live_early) {                  // first: layer 0 may need the sparse / dense decision
         rc = find_live_rows(side->s);
-        if (rc) return rc;
-    }
-    if (plan_early) {
-        rc = make_plan(side->s);
         if (rc) return rc;
     }
     if (group_early) {
         rc = group_project(side->s);
         if (rc) return rc;
     }
-    if (group_early || plan_early || live_early) {
+    if (group_early || live_early) {
         if (hipEventRecord(side->early, side->s) != hipSuccess) return DIGAT_ERR_LAUNCH;
     }
     if (news_early && !news_hpq0) {      // news_hpq0: the caller kept layer 0's news projections per news (digat_news_project0)
@@ -1113,11 +1034,7 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
             rc = find_live_rows(st);
             if (rc) return rc;
         }
-        if (i == 0 && use_staged && !plan_early) {
-            rc = make_plan(st);
-            if (rc) return rc;
-        }
-        if (i == 0 && side && (group_early || plan_early || live_early)) {
+        if (i == 0 && side && (group_early || live_early)) {
             if (hipStreamWaitEvent(st, side->early, 0) != hipSuccess) return DIGAT_ERR_LAUNCH;
         }
         // The live lists are in force from layer 0 on: a dead node (a history padding slot, the topic node of an unread category:
@@ -1140,19 +1057,17 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
             rc = DIGAT_OK;
             if (sparse_mode != DIGAT_XATTN_DENSE && d / 4 <= 256) {
                 // P' = K1 (the groups' P0) + K3 (this layer's r_user) is formed inside the kernel: nothing is expanded
-                // live centres only (the list of find_live_rows), P / Q / h / X read through the group index.  The staged kernels
-                // (opt-in) keep the older arrangement: every centre computed, and the dead rows of the other buffer filled with X_i
-                const bool l0_live = want_live && live_flags && !use_staged && g_l0_live_on;
+                // live centres only (the list of find_live_rows), P / Q / h / X read through the group index
+                const bool l0_live = want_live && live_flags;
                 SparseArgs sg{P0, Q0, h0, xu0_grouped ? Xg0 : Xu[0], lu.a, Au, Xu[1], r_user, row_group, l0_live ? live_flags : nullptr,
                                     sparse_mode == DIGAT_XATTN_AUTO ? sparse_flag : nullptr, B, U, d / 4, (xu0_grouped || xu0_shared) ? 1 : 0,
                                     (!l0_live && xu0_grouped && want_live) ? (const uint8_t*)pend_flags : nullptr, Xu[0],
                                     l0_live ? rowidx : nullptr, l0_live ? nrows_dev : nullptr, G, nullptr, 0, 0};
-                if (presplit && l0_live && L > 1) { sg.xsplit = xsplit_ws; sg.xsplit_range = rflag; xs_ready = true; }
                 if (l0_chunked && l0_live && sparse_l0_ok(sg)) {
                     // R rows of an impression per wave: every neighbour row fetched serves R rows (xattn_sparse_l0_kernel; same bits)
                     rc = launch_sparse_l0(sg, l0_lead, l0_idx, l0_off + B, shared ? (B + SPARSE_L0_ROWS - 1) / SPARSE_L0_ROWS : G, st);
                 } else
-                rc = use_staged ? launch_staged(sg, plan, 0, 0, st) : launch_sparse(sg, st);
+                rc = launch_sparse(sg, st);
             }
             if (!rc && !(sparse_mode == DIGAT_XATTN_SPARSE && d / 4 <= 256)) {
                 const int* skip_if = sparse_mode == DIGAT_XATTN_AUTO && d / 4 <= 256 ? sparse_flag : nullptr;
@@ -1171,18 +1086,13 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
             }
         } else {
             // every layer projects, scores and writes the live nodes only (layer 0 too: see publish_live_rows above)
-            const bool lv_on = i > 0 || (g_l0_live_on && !use_staged);
-            const bool xs_out = presplit && lv_on && rowidx && live_flags && i + 1 < L;
-            const SplitIO sio{xs_ready && lv_on && rowidx ? (const void*)xsplit_ws : nullptr, xs_out ? xsplit_ws : nullptr, rflag};
             rc = xattn_core(Xu[un], Au, r_user, lu.W, lu.bW, lu.F1, lu.F2, lu.a, Xu[un ^ 1], nullptr, B, U, d, xws, st, lu.wsplit,
-                            lv_on ? rowidx : nullptr, lv_on ? nrows_dev : nullptr, lv_on ? live_flags : nullptr, sparse_mode,
-                            sparse_flag, pq_x3, use_staged ? &plan : nullptr, i,
+                            rowidx, nrows_dev, live_flags, sparse_mode, sparse_flag, pq_x3,
                             i > 0 ? ((p->flags & DIGAT_PQ_BF16) ? 1 : 0) | ((p->flags & DIGAT_PQ_X1) ? 2 : 0) | ((p->flags & DIGAT_PQ_FP8) ? 4 : 0) : 0,
                             // after the last layer only the history rows are read (the user context's topic pooling, :124):
                             // the topic nodes' own Eq. 8 is not computed there (wave-per-centre sparse kernel)
                             (i > 0 && i == L - 1 && sparse_mode == DIGAT_XATTN_SPARSE) ? H : 0, fmt, rflag,
-                            (i > 0 && lv_on && tw_pub.word) ? &tw_pub : nullptr, &sio);
-            xs_ready = sio.out != nullptr;
+                            (i > 0 && tw_pub.word) ? &tw_pub : nullptr);
         }
         if (rc) return rc;
         if (side && hipEventRecord(side->fork, st) != hipSuccess) return DIGAT_ERR_LAUNCH;      // this layer's user nodes are written
@@ -1237,10 +1147,10 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
             // caller says so (flags bit 3); there is no device-side decision for this graph
             rc = xattn_core(xn_cur, An, r_news, ln.W, ln.bW, ln.F1, ln.F2, ln.a, Xn[nn], nullptr, B, N, d, xws_news, sn, ln.wsplit,
                             news_rowidx, news_nrows, news_flags, (p->flags & DIGAT_NEWS_XATTN_SPARSE) ? DIGAT_XATTN_SPARSE : DIGAT_XATTN_DENSE,
-                            nullptr, pq_x3, nullptr, 0,
+                            nullptr, pq_x3,
                             // the news graph's P' always carries K3 from the GEMM epilogue: bf16 storage applies at every layer
                             ((p->flags & DIGAT_PQ_BF16) ? 1 : 0) | ((p->flags & DIGAT_PQ_X1) ? 2 : 0) | ((p->flags & DIGAT_PQ_FP8) ? 4 : 0), 0, fmt, rflag,
-                            nullptr, nullptr, news_rowidx ? XPART_NEWS + 1 : 0);
+                            nullptr, news_rowidx ? XPART_NEWS + 1 : 0);
         }
         if (rc) return rc;
         xn_cur = Xn[nn]; nn ^= 1; un ^= 1;
@@ -1266,11 +1176,6 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
     return DIGAT_OK;
 }
 
-#ifdef DIGAT_LAB
-static size_t xsplit_bytes(int B, int U, int d) { return align_up((size_t)B * U * d * 4, 256); }
-#else
-static size_t xsplit_bytes(int, int, int) { return 0; }
-#endif
 // layer 0 of grouped rows (xattn_sparse_l0_kernel): group starts [B + 64] int, rows led by each row [B] bytes, offsets [B + 64] int
 // and list [B U] int of the live centres of the chunk-leading rows
 // + twins (xattn_sparse_twin_kernel): twin words [B U] u32, lead flags [B U] bytes, leads per row [B + 64] int, offsets [B + 64] int, list [B U] int
@@ -1299,9 +1204,7 @@ size_t digat_encoder_workspace_bytes(int B, int N, int H, int C, int d, int dept
     tot += align_up((4 * align_up((size_t)B, 64) + 2 * align_up((size_t)B + 1, 64) + align_up((size_t)B * U, 64)
                      + align_up((size_t)B * (C + 1), 64) + 64) * 4 + align_up((size_t)B * U, 256) + align_up((size_t)B * (C + 1), 256), 256);
     tot += news_live_bytes(B, N);                         // larger news graphs on the sparse kernel: live-node flags, counts, offsets, list
-    tot += xsplit_bytes(B, U, d);                         // LAB builds: the user nodes as split fp16 pairs between two layers (SplitIO)
     tot += l0_chunk_bytes(B, U);                          // layer 0 of grouped rows: group starts + rows led by each row (xattn_sparse_l0_kernel)
-    tot += plan_bytes(B, U);                             // the staged Eq. 8 kernel's plan of the batch (digat_staged.inc)
     return tot;
 }
 
@@ -1353,10 +1256,8 @@ static int encoder_fwd_impl(const digat_params* p, const float* Xn_in, const uin
     float* const r_user2[2] = {r_user, (float*)(ws + 4 * sb)};
     void* xws_news = ws + 5 * sb;
     int* live_ws = (int*)((char*)xws_news + digat_xattn_workspace_bytes(B, N, d));
-    void* plan_ws = (char*)workspace + digat_encoder_workspace_bytes(B, N, H, C, d, L) - plan_bytes(B, U);
-    void* chunk_ws = (char*)plan_ws - l0_chunk_bytes(B, U);
-    unsigned char* xsplit_ws = xsplit_bytes(B, U, d) ? (unsigned char*)chunk_ws - xsplit_bytes(B, U, d) : nullptr;
-    void* news_live_ws = (char*)chunk_ws - xsplit_bytes(B, U, d) - news_live_bytes(B, N);
+    void* chunk_ws = (char*)workspace + digat_encoder_workspace_bytes(B, N, H, C, d, L) - l0_chunk_bytes(B, U);
+    void* news_live_ws = (char*)chunk_ws - news_live_bytes(B, N);
 
     int rc;
     const bool folded = p->cand_fold_W && p->user_news_fold_W && p->userAtt_fold_W;
@@ -1396,7 +1297,7 @@ static int encoder_fwd_impl(const digat_params* p, const float* Xn_in, const uin
     }
     if (folded)
         return encoder_fwd_folded(p, Xn_in, An, Mn, Au, cat_mask, cat_idx, out_news, out_user, B, N, H, Xu, Xn, xws,
-                                  xws_news, cws, kq_t, kq_u, r_user2, r_news, live_ws, st, row_group, G, ue, Xg0, news_hpq0, hist_hpq0, topic_hpq0, plan_ws, chunk_ws, xsplit_ws, Au_g, cm_g, ci_g,
+                                  xws_news, cws, kq_t, kq_u, r_user2, r_news, live_ws, st, row_group, G, ue, Xg0, news_hpq0, hist_hpq0, topic_hpq0, chunk_ws, Au_g, cm_g, ci_g,
                                   c_n0 ? ctxq0 : nullptr, news_index, news_rows, c_n0_in_place ? c_n0 : out_news, live_g_ws,
                                   run_leader, run_lead, news_live_ws);
     // c_u (:192)
@@ -1416,12 +1317,12 @@ static int encoder_fwd_impl(const digat_params* p, const float* Xn_in, const uin
         const int fmt = (p->flags & DIGAT_PARAMS_GEMM_F16X3) ? 1 : 0;
         unsigned* const rflag = fmt ? (unsigned*)p->range_flag : nullptr;
         rc = xattn_core(xn_cur, An, r_news, ln.W, ln.bW, ln.F1, ln.F2, ln.a, Xn[nn], nullptr, B, N, d, xws, st, ln.wsplit,
-                        nullptr, nullptr, nullptr, DIGAT_XATTN_DENSE, nullptr, 0, nullptr, 0, 0, 0, fmt, rflag);
+                        nullptr, nullptr, nullptr, DIGAT_XATTN_DENSE, nullptr, 0, 0, 0, fmt, rflag);
         if (rc) return rc;
         rc = launch_gemm(gemm_plain(out_news, d, lu.F3, lu.b3, r_user, d, B, d, d, 0), st);
         if (rc) return rc;
         rc = xattn_core(Xu[un], Au, r_user, lu.W, lu.bW, lu.F1, lu.F2, lu.a, Xu[un ^ 1], nullptr, B, U, d, xws, st, lu.wsplit,
-                        nullptr, nullptr, nullptr, DIGAT_XATTN_DENSE, nullptr, 0, nullptr, 0, 0, 0, fmt, rflag);
+                        nullptr, nullptr, nullptr, DIGAT_XATTN_DENSE, nullptr, 0, 0, 0, fmt, rflag);
         if (rc) return rc;
         xn_cur = Xn[nn]; nn ^= 1; un ^= 1;
         // c_n += news context (:196); c_u += user context with the UPDATED c_n (:197)
@@ -1436,15 +1337,6 @@ static int encoder_fwd_impl(const digat_params* p, const float* Xn_in, const uin
     return DIGAT_OK;
 }
 
-#ifdef DIGAT_LAB
-int digat_set_staged_xattn(int mode) {        // LAB builds only: process-wide, one host thread
-    (void)staged_cfg();
-    const int prev = g_staged_on ? 1 + g_staged_cfg : 0;
-    g_staged_on = mode > 0 ? 1 : 0;
-    if (mode > 0 && mode <= 5) g_staged_cfg = mode - 1;
-    return prev;
-}
-#endif
 
 int digat_encoder_fwd(const digat_params* p, const float* Xn_in, const uint8_t* An, const uint8_t* Mn,
                       const float* ue, const uint8_t* Au, const uint8_t* cat_mask, const int64_t* cat_idx,
@@ -1576,9 +1468,6 @@ int digat_user_project0(const digat_params* p, const float* X, float* hpq, int M
     gg.wsplit = (const unsigned short*)lu.wsplit;
     gg.format = (p->flags & DIGAT_PARAMS_GEMM_F16X3) ? 1 : 0; gg.range_flag = gg.format ? (unsigned*)p->range_flag : nullptr;
     gg.m_dispatch = 1 << 30;                                               // the large-M kernel whatever M is (C topic rows)
-#ifdef DIGAT_LAB
-    if (LAB_ENV("DIGAT_LAB_FAKE_PRESPLIT", 0) && gg.format == 1) gg.a_split = X;     // timing only (tools/exp/gemm_lab.py): X read as if already split
-#endif
     return launch_gemm(gg, (hipStream_t)stream, DIGAT_KERNEL_PROJ);
 }
 

@@ -1317,8 +1317,7 @@ int digat_linear_bwd_input(const float* dy, int64_t lddy, const float* w, float*
 // ~512 workgroups when M allows — the [B,d] linears' weight gradients (M = 320 rows: 47 of a step's 56 TN launches) ran as 50
 // workgroups of five dependent 32-row steps each, 44 us apiece; as 10 slices x 25 tiles they are one step deep
 static bool tn_bf16x6_ok(int M, int vec) {
-    static const int on = LAB_ENV("DIGAT_TN_BF16X6", 1);   // LAB builds: 0 keeps every weight gradient on the fp32-MFMA kernel (A/B measurements)
-    return on && vec && M >= 2048;
+    return vec && M >= 2048;
 }
 static int tn_slices(int M, int No, int Ni) {
     if (M >= 2048 && tn_bf16x6_ok(M, 1)) {           // 160 x 160 tiles: about two rounds of 512 workgroup slots, K tiles of 32 rows
@@ -1620,15 +1619,14 @@ static int xattn_pairwise_fwd_train_flag(const float* Pr, const float* Q, const 
     const bool small = n <= 16 && d / 4 <= 256;
     if (p > 0.f) { pl.g.amask = amask; pl.g.adrop = small ? nullptr : alpha_drop; pl.g.drop_p = p; pl.g.drop_seed = seed; }
     if (small) { pl.g.agg_h = h; pl.g.agg_x = X; pl.g.agg_out = out; }
-    static const int train_sparse = LAB_ENV("DIGAT_TRAIN_SPARSE", 1);
-    const bool eligible = !small && train_sparse && d / 4 <= 256;
+    const bool eligible = !small && d / 4 <= 256;
     if (eligible && mode == 1)          // the caller knows the corpus is sparse: the entry-wise kernel alone
         return launch_sparse_train(Pr, Q, h, X, a, A, out, alpha, s_pre, amask, p, seed, B, n, d, nullptr, st);
     const bool guarded = eligible && sparse_flag && mode == 0;
     if (guarded) {
         // round 6: the user graph's forward on the sparse kernel (a wave per centre walks its ~9 adjacency entries: score, softmax,
         // dropout and aggregation from registers; the tile kernel + aggregation pair visits all n^2 pairs)
-        hipLaunchKernelGGL(train_sparse_decide_kernel, dim3(1), dim3(1024), 0, st, A, B, n, g_sparse_per_node, sparse_flag);
+        hipLaunchKernelGGL(train_sparse_decide_kernel, dim3(1), dim3(1024), 0, st, A, B, n, SPARSE_PER_NODE, sparse_flag);
         DIGAT_CHECK_LAUNCH();
         rc = launch_sparse_train(Pr, Q, h, X, a, A, out, alpha, s_pre, amask, p, seed, B, n, d, sparse_flag, st);
         if (rc) return rc;
@@ -1687,8 +1685,7 @@ static int xattn_pairwise_bwd_ld(const float* dOut, const float* out, const floa
     const uint8_t* am = p > 0.f ? amask : nullptr;
     // the forward's choice (a device int in its save buffer): the entry-wise pair below when the batch's adjacency is sparse, the three
     // all-pairs launches otherwise — the launches of the other side return at once
-    static const int train_sparse = LAB_ENV("DIGAT_TRAIN_SPARSE", 1);
-    const bool eligible = train_sparse && d / 4 <= 128 && dr;
+    const bool eligible = d / 4 <= 128 && dr;
     // graphs of at most 16 nodes (the news graph): a centre has at most 16 entries whatever the adjacency — always the entry-wise pair
     // (the all-pairs launches walk 13 channel chunks per row for a 10 x 10 product: 65 us per layer against 20)
     const bool only_sparse = eligible && (mode == 1 || n <= 16) && mode != 2;   // else the caller's choice (xattn_pairwise_fwd_train_flag): no guards
@@ -1778,19 +1775,13 @@ int digat_xattn_project_x3(const float* X, const float* r, const float* W, const
                            float* h, float* Pr, float* Q, int B, int n, int d, void* wsplit, void* stream) {
     if (!X || !r || !W || !F1 || !F2 || !h || !Pr || !Q || !wsplit) return DIGAT_ERR_ARG;
     if (d % 80 || (long)B * n < 2048) return DIGAT_ERR_SHAPE;
-#ifdef DIGAT_LAB
-    static const int lab_f16 = LAB_ENV("DIGAT_TRAIN_F16", 0);      // experiment: the forward projections in the fp16x3 format (no range fallback: timing only)
-#else
-    constexpr int lab_f16 = 0;
-#endif
-    int rc = launch_split(W, F1, F2, d, 3, d, wsplit, (hipStream_t)stream, 0, lab_f16 ? 1 : 0);
+    int rc = launch_split(W, F1, F2, d, 3, d, wsplit, (hipStream_t)stream, 0, 0);
     if (rc) return rc;
     GemmArgs g = gemm_plain(X, d, W, bW, h, d, B * n, d, d, 0);
     g.w[1] = F1; g.bias[1] = nullptr; g.y[1] = Pr;
     g.w[2] = F2; g.bias[2] = nullptr; g.y[2] = Q;
     g.nsegs = 3;
     g.wsplit = (const unsigned short*)wsplit;
-    g.format = lab_f16 ? 1 : 0;
     if (g_train_bf16) g.x1_segs = 7;           // digat_set_train_precision(1): one bf16 product
     g.radd = r; g.radd_seg = 1; g.rows_per_b = n;
     return launch_gemm(g, (hipStream_t)stream, DIGAT_KERNEL_PROJ);

@@ -49,8 +49,7 @@ struct ScoreArgs {
     int ld_off;        // byte offset of the per-node linear terms a.P'_j, a.Q_i (2 * RB * 4*NT floats)
     int pm_off;        // byte offset of the node permutation: keys [RB*n] ints, then node_of [RB*n] ints
     const int* skip_if;    // optional device int: the launch returns at once when *skip_if != 0 (the sparse kernel does this batch)
-    int skip;          // ablation only (env DIGAT_XATTN_SKIP, 0 in production): 1 no score loop,
-                       // 2 no aggregation launch, 8 no softmax, 16 no empty-tile skipping, 32 no score launch
+    int skip;          // always 0 (a removed timing ablation's switch): 1 no score loop, 8 no softmax, 16 no empty-tile skipping
     // training (round 6): the attention dropout is applied where alpha is produced (amask != NULL): keep bytes [B,n,n] by the
     // counter hash of (drop_seed, flat index), alpha itself stays undropped for the backward, adrop (tile kernel; the small-graph
     // kernel aggregates from registers) receives drop_p(alpha)
@@ -583,9 +582,8 @@ struct SparseArgs {
     long ld8;                                    // pq16 == 2: bytes between rows ([d codes | d / 80 fp32 scales | pad]: the GEMM's fp8 segments)
     const unsigned* twin; const int* twlist; const int* twcount;   // optional, with rowidx: centres with EQUAL adjacency rows served together
                                                  // (user_live_flags_kernel's twin words [B n], the list of the leading centres, their count)
-    unsigned char* xsplit;                       // optional [B n d] x 4 bytes: every output row is ALSO stored as the two scaled fp16 pieces the
-                                                 // next layer's projection GEMM would split it into (split_store4; GemmArgs.a_split)
-    unsigned* xsplit_range;                      // with xsplit: |= 1 when an output leaves the fp16x3 format's range (the GEMM's own check moves here)
+    unsigned char* xsplit;                       // unused, always NULL (the removed pre-split store of the output rows: docs/REJECTED.md row 4q)
+    unsigned* xsplit_range;                      // unused, always NULL
     unsigned exec_unit;                          // with exec_rows: algorithmic bytes per live centre of the list (0: a counting kernel prices the launch)
     int prof_part;                               // profiling: 0 = the part follows from the arguments (sparse_part), else XPART_* + 1 (the news graph's row-list launches)
     // training (xattn_sparse_kernel<., 0, false, true>; round 6): what the backward needs leaves the wave — the centre's alpha row
@@ -610,32 +608,6 @@ struct SparseArgs {
 #ifndef DIGAT_SPARSE_NBR
 #define DIGAT_SPARSE_NBR 4
 #endif
-// LAB builds only (DIGAT_PRESPLIT=1; measured: no gain, docs/REJECTED.md row 4q): the Eq. 8 kernels also store their output rows
-// as the split pieces the next layer's projection GEMM wants
-#ifdef DIGAT_LAB
-#define XSPLIT_STORE(bad_, o_, row_, c4_) do { if (g.xsplit) bad_ |= split_store4(o_, row_, c4_); } while (0)
-#define XSPLIT_FLAG(bad_) do { if (g.xsplit && g.xsplit_range && __ballot(bad_) != 0ull && lane == 0) atomicOr(g.xsplit_range, 1u); } while (0)
-#else
-#define XSPLIT_STORE(bad_, o_, row_, c4_) do { (void)(bad_); } while (0)
-#define XSPLIT_FLAG(bad_) do { (void)(bad_); } while (0)
-#endif
-// The two scaled fp16 pieces of four consecutive channels of an output row — exactly what gemm_bf16x6s_kernel<., true>::split_mt
-// makes of them (hi = x 2^4 truncated to fp16, lo = x 2^4 - hi rounded) — stored where the next layer's projection GEMM reads its
-// A fragments: 32 bytes per 8 channels, [8 hi | 8 lo], the row stride of the fp32 row.  Returns whether a value left the range.
-__device__ __forceinline__ bool split_store4(const float4 v, unsigned char* row, const int c4) {
-    constexpr float xs = F16_ACT_SCALE;
-    const float s0 = v.x * xs, s1 = v.y * xs, s2 = v.z * xs, s3 = v.w * xs;
-    const unsigned h01 = pack_half_rtz(s0, s1), h23 = pack_half_rtz(s2, s3);
-    const fp16x2 a = __builtin_bit_cast(fp16x2, h01), b = __builtin_bit_cast(fp16x2, h23);
-    const _Float16 l0 = (_Float16)__builtin_fmaf(v.x, xs, -(float)a[0]), l1 = (_Float16)__builtin_fmaf(v.y, xs, -(float)a[1]);
-    const _Float16 l2 = (_Float16)__builtin_fmaf(v.z, xs, -(float)b[0]), l3 = (_Float16)__builtin_fmaf(v.w, xs, -(float)b[1]);
-    const unsigned l01 = (unsigned)__builtin_bit_cast(unsigned short, l0) | ((unsigned)__builtin_bit_cast(unsigned short, l1) << 16);
-    const unsigned l23 = (unsigned)__builtin_bit_cast(unsigned short, l2) | ((unsigned)__builtin_bit_cast(unsigned short, l3) << 16);
-    unsigned char* p = row + (c4 >> 1) * 32 + (c4 & 1) * 8;
-    *reinterpret_cast<uint2*>(p) = make_uint2(h01, h23);
-    *reinterpret_cast<uint2*>(p + 16) = make_uint2(l01, l23);
-    return !(fmaxf(fmaxf(fabsf(s0), fabsf(s1)), fmaxf(fabsf(s2), fabsf(s3))) < 65504.f);
-}
 // a . relu(p + q) over the 8 channels of one 16-byte piece of bf16 rows (a in fp32: two float4), added to `part`
 __device__ __forceinline__ float score8_bf16(const uint4 p, const uint4 q, const float4 a0, const float4 a1, float part) {
     const unsigned pw[4] = {p.x, p.y, p.z, p.w}, qw[4] = {q.x, q.y, q.z, q.w};
@@ -906,7 +878,6 @@ __device__ __forceinline__ void xattn_sparse_centre(const SparseArgs& g, long rh
             if (lane + 64 * u < d4) Fi[lane + 64 * u] = xin[u];
     }
     float4* Oi = reinterpret_cast<float4*>(g.out) + rho * d4;
-    bool bad = false;
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const int c4 = lane + 64 * u;
@@ -915,10 +886,8 @@ __device__ __forceinline__ void xattn_sparse_centre(const SparseArgs& g, long rh
             const float4 o = make_float4(fmaxf(acc[u].x, 0.f) + x.x, fmaxf(acc[u].y, 0.f) + x.y,
                                          fmaxf(acc[u].z, 0.f) + x.z, fmaxf(acc[u].w, 0.f) + x.w);
             Oi[c4] = o;
-            XSPLIT_STORE(bad, o, g.xsplit + rho * d4 * 16, c4);
         }
     }
-    XSPLIT_FLAG(bad);
     SP_T(7);
 #ifdef DIGAT_SPARSE_TIMERS
     if (sp_on && lane == 0) atomicAdd(g.timers + 8, 1ull);
@@ -1205,7 +1174,6 @@ __device__ __forceinline__ void xattn_sparse_l0_chunk(const SparseL0Args& a, con
             }
         }
     }
-    bool bad = false;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         if (r < nr) {
@@ -1218,12 +1186,10 @@ __device__ __forceinline__ void xattn_sparse_l0_chunk(const SparseL0Args& a, con
                     const float4 o = make_float4(fmaxf(acc[r][u].x, 0.f) + x.x, fmaxf(acc[r][u].y, 0.f) + x.y,
                                                  fmaxf(acc[r][u].z, 0.f) + x.z, fmaxf(acc[r][u].w, 0.f) + x.w);
                     Oi[c4] = o;
-                    XSPLIT_STORE(bad, o, g.xsplit + (rho + (long)r * n) * d4 * 16, c4);
                 }
             }
         }
     }
-    XSPLIT_FLAG(bad);
 }
 
 // ---- twins: up to TWIN_R centres of one graph with equal adjacency rows per wave -------------------------------------------------------
@@ -1389,7 +1355,6 @@ __device__ __forceinline__ void xattn_sparse_twin_chunk(const SparseArgs& g, con
 #pragma unroll
             for (int u = 0; u < U; ++u) xin[r][u] = reinterpret_cast<const float4*>(g.X)[(b * n + mem[r]) * d4 + c4l[u]];
     }
-    bool bad = false;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         if (r < nr) {
@@ -1402,12 +1367,10 @@ __device__ __forceinline__ void xattn_sparse_twin_chunk(const SparseArgs& g, con
                     const float4 o = make_float4(fmaxf(acc[r][u].x, 0.f) + x.x, fmaxf(acc[r][u].y, 0.f) + x.y,
                                                  fmaxf(acc[r][u].z, 0.f) + x.z, fmaxf(acc[r][u].w, 0.f) + x.w);
                     Oi[c4] = o;
-                    XSPLIT_STORE(bad, o, g.xsplit + (b * n + mem[r]) * d4 * 16, c4);
                 }
             }
         }
     }
-    XSPLIT_FLAG(bad);
 }
 
 // the grid is capped (the number of leading centres is known on the device only): a wave strides over the list
@@ -1554,19 +1517,18 @@ static int launch_sparse(const SparseArgs& g_in, hipStream_t st) {
     if (g.run_if && blocks > 2048u) blocks = 2048u;        // guarded: a fixed grid striding over the centres (see the kernel)
     // 16: runs of 64 consecutive centres (about two user graphs) per XCD; measured 1.431 vs 1.442 ms per step against the
     // dispatcher's plain round-robin (0), 8: 1.434, 4: 1.436, 2: 1.443 (tools/exp/ab.sh, two alternating runs each)
-    static const int xcd_env = LAB_ENV("DIGAT_SPARSE_XCD", 16);
-    g.xcd_group = xcd_env;
+    constexpr int SPARSE_XCD_GROUP = 16;
+    g.xcd_group = SPARSE_XCD_GROUP;
 #ifdef DIGAT_SPARSE_TIMERS
     if (!g_sparse_timers && hipMalloc((void**)&g_sparse_timers, 16 * 8) == hipSuccess) (void)hipMemset(g_sparse_timers, 0, 16 * 8);
     g.timers = g.rowidx ? g_sparse_timers : nullptr;          // the user graph's row-list launches
 #endif
-    if (g.xcd_group > 0) blocks = (blocks + 8u * g.xcd_group - 1) / (8u * g.xcd_group) * (8u * g.xcd_group);   // whole windows
-    static const int twins_on = LAB_ENV("DIGAT_SPARSE_TWINS", 1);
-    if (twins_on && g.twin && g.twlist && g.twcount && g.rowidx && !g.pq16 && !g.radd && !g.group && !g.run_if && !g.fill_flags && g.d4 <= 128) {
+    blocks = (blocks + 8u * g.xcd_group - 1) / (8u * g.xcd_group) * (8u * g.xcd_group);   // whole windows
+    if (g.twin && g.twlist && g.twcount && g.rowidx && !g.pq16 && !g.radd && !g.group && !g.run_if && !g.fill_flags && g.d4 <= 128) {
         // centres with equal adjacency rows together (xattn_sparse_twin_kernel); how many lead is known on the device only: a capped
         // grid whose waves stride over the list
-        static const unsigned cap = (unsigned)LAB_ENV("DIGAT_TWIN_GRID", 8192);
-        if (blocks > cap) blocks = cap;
+        constexpr unsigned TWIN_GRID_CAP = 8192;
+        if (blocks > TWIN_GRID_CAP) blocks = TWIN_GRID_CAP;
         blocks = (blocks * 4 + DIGAT_TWIN_WPG - 1) / DIGAT_TWIN_WPG;
         if (g.d4 <= 64) hipLaunchKernelGGL((xattn_sparse_twin_kernel<1, TWIN_R>), dim3(blocks), dim3(64 * DIGAT_TWIN_WPG), 0, st, g);
         else hipLaunchKernelGGL((xattn_sparse_twin_kernel<2, TWIN_R>), dim3(blocks), dim3(64 * DIGAT_TWIN_WPG), 0, st, g);
@@ -1610,11 +1572,11 @@ static int launch_sparse_l0(const SparseArgs& g_in, const uint8_t* lead, const i
     SparseArgs& g = a.g;
     { const int rcp = sparse_prof_bytes(g, st); if (rcp) return rcp; }
     ProfScope prof(DIGAT_KERNEL_XATTN, sparse_bytes(g), st, 0.0, XPART_L0);
-    static const int xcd_env = LAB_ENV("DIGAT_L0_XCD", 16);
-    g.xcd_group = xcd_env;
+    constexpr int L0_XCD_GROUP = 16;       // runs of workgroups per XCD, as in launch_sparse
+    g.xcd_group = L0_XCD_GROUP;
     // at most ceil(rows of a group / R) chunks per group: B / R + G chunks, n centres each
     unsigned blocks = (unsigned)((((long)g.B / SPARSE_L0_ROWS + G) * g.n + 3) / 4);
-    if (g.xcd_group > 0) blocks = (blocks + 8u * g.xcd_group - 1) / (8u * g.xcd_group) * (8u * g.xcd_group);
+    blocks = (blocks + 8u * g.xcd_group - 1) / (8u * g.xcd_group) * (8u * g.xcd_group);
     if (g.d4 <= 64) hipLaunchKernelGGL((xattn_sparse_l0_kernel<1, SPARSE_L0_ROWS>), dim3(blocks), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((xattn_sparse_l0_kernel<2, SPARSE_L0_ROWS>), dim3(blocks), dim3(256), 0, st, a);
     DIGAT_CHECK_LAUNCH();
@@ -1792,8 +1754,7 @@ static int plan_xattn(int B, int n, int d, XattnPlan* pl) {
 static int launch_score(const XattnPlan& pl, hipStream_t st) {
     const ScoreArgs& g = pl.g;
     // small graphs in the fused form: the graph-in-LDS kernel when P' and h of a graph fit 64 KB (LDS-DMA addresses go through M0)
-    static const int lds_env = LAB_ENV("DIGAT_NEWS_LDS", 1);
-    if (g.n <= 16 && g.d4 <= 256 && !g.skip && lds_env && g.agg_out && !g.qgroup && !g.s_out) {
+    if (g.n <= 16 && g.d4 <= 256 && g.agg_out && !g.qgroup && !g.s_out) {
         const size_t lds = (size_t)2 * (((size_t)g.n * g.d4 + 63) / 64) * 1024;
         if (lds <= 64 * 1024) {
             if (g.d4 <= 64) hipLaunchKernelGGL(xattn_small_lds_kernel<1>, dim3(g.B), dim3(256), lds, st, g);
@@ -1803,7 +1764,7 @@ static int launch_score(const XattnPlan& pl, hipStream_t st) {
             return DIGAT_OK;
         }
     }
-    if (g.n <= 16 && g.d4 <= 256 && !g.skip) {
+    if (g.n <= 16 && g.d4 <= 256) {
         const unsigned blocks = (unsigned)(((long)g.B * g.n + 3) / 4);
         if (g.d4 <= 64) hipLaunchKernelGGL(xattn_score_small_kernel<1>, dim3(blocks), dim3(256), 0, st, g);
         else if (g.d4 <= 128) hipLaunchKernelGGL(xattn_score_small_kernel<2>, dim3(blocks), dim3(256), 0, st, g);
@@ -1843,10 +1804,6 @@ static int launch_xattn_pairwise(const float* Pr, const float* Q, const float* h
     const bool fused = !alpha_wanted && n <= 16 && pl.g.d4 <= 256 && !live && !group;
     if (fused) { pl.g.agg_h = h; pl.g.agg_x = X; pl.g.agg_out = out; }
     {
-        static const int skip = LAB_ENV("DIGAT_XATTN_SKIP", 0);       // LAB builds: timing ablations (wrong results)
-        pl.g.skip = skip;
-    }
-    if (!(pl.g.skip & 32)) {
         // algorithmic bytes of the score launch: P', Q in (2 n d floats), adjacency, alpha out, a (SURVEY 8d bytes_A);
         // the fused small-graph launch also aggregates: P', Q, h, X in, the nodes out, K3, adjacency (bytes_B)
         const double bytes = fused ? (double)B * (5.0 * n * d * 4 + (radd ? 4.0 * d : 0.0) + (double)n * n) + 4.0 * d
@@ -1855,7 +1812,7 @@ static int launch_xattn_pairwise(const float* Pr, const float* Q, const float* h
         const int rc2 = launch_score(pl, st);
         if (rc2) return rc2;
     }
-    if (!(pl.g.skip & 2) && !(fused && !pl.g.skip)) {
+    if (!fused) {
         AggArgs ag{alpha, h, X, out, B, n, d, (d + 63) / 64, n | 1, live, group, skip_if};
         if (ag.groups > 16) return DIGAT_ERR_SHAPE;        // d <= 1024
         // algorithmic bytes of the aggregation launch: h, X in + out (3 n d floats), alpha in;

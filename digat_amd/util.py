@@ -409,7 +409,7 @@ def batch_streams(device, count: int = 3):
     flight fill the phases where a batch has a single latency-bound kernel running (a kernel trace of the 2-stream run:
     no kernel 11 % of the time, one kernel 36 %).  The optimum depends on how the runtime maps the 2 x count + 1 streams to
     its 4 hardware queues: with 5 or more queues (GPU_MAX_HW_QUEUES) every count is slower (2.0-2.2 ms) — more kernels truly
-    concurrent contend for the chip; without the library's side streams (DIGAT_SINGLE_STREAM=1) two streams do as well as
+    concurrent contend for the chip; without the library's side streams (DIGAT_PARAMS_SIDE_STREAM_OFF) two streams do as well as
     three with them (1.37 ms), one is worse (1.63 vs 1.48)."""
     cur = torch.cuda.current_stream(device)
     extra = _batch_streams.setdefault((device, cur.cuda_stream), [])

@@ -23,9 +23,10 @@
  *     lists); the library keeps no mutable process-wide switch.  Per-caller-stream side streams live in a mutex-guarded table.
  *     Exceptions, both diagnostics: the launch profiler (digat_profile_*: one measuring thread) and digat_set_train_precision
  *     (set once per training run).
- *   - no environment variable changes what the product library computes or which kernels it runs: the development knobs of
- *     earlier rounds (A/B switches, the wrong-result timing ablations DIGAT_*_SKIP, phase timers, the LDS-staged Eq. 8 variants)
- *     exist only in LAB builds (-DDIGAT_LAB, tools/exp/build_variant.sh).
+ *   - no environment variable changes what the library computes or which kernels it runs.  The development knobs of earlier
+ *     rounds (A/B switches, the wrong-result timing ablations, the LDS-staged Eq. 8 variants) are gone from the sources: their
+ *     measurements are in docs/REJECTED.md, their code in git history.  Phase timers are compile-time options
+ *     (-DDIGAT_GEMM_TIMERS, -DDIGAT_SPARSE_TIMERS, -DDIGAT_CF_TIMERS through tools/exp/build_variant.sh).
  */
 #ifndef DIGAT_HIP_H
 #define DIGAT_HIP_H
@@ -273,13 +274,6 @@ int digat_encoder_fwd(const digat_params* params,
  * cannot reach an output — history padding slots, topic nodes of unread categories: only their self loop, pooled with weight 0 —
  * are found on the device and skipped (about half of a MIND user graph).  Outputs are bit-identical either way. */
 enum { DIGAT_PARAMS_SIDE_STREAM_OFF = 512, DIGAT_PARAMS_SIDE_STREAM_ON = 1024, DIGAT_PARAMS_NO_LIVE_ROWS = 2048 };
-
-#ifdef DIGAT_LAB
-/* LAB builds only (process-wide, one host thread): sparse Eq. 8 of the user graph from LDS-staged rows (digat_staged.inc; five
- * variants, mode 1-5; 0 = the wave-per-centre kernel).  Measured slower in round 2: the product
- * library does not carry the code path. */
-int digat_set_staged_xattn(int mode);
-#endif
 
 /* The same inference for rows that SHARE users: in dev/test scoring the ~37 candidate rows of one
  * impression carry identical user tensors (util.py:57-67 expands them per row).  Here the user side is

@@ -566,29 +566,36 @@ def fixture_msa_train():
         text, mask = synthetic.make_titles(T_, Lw, V, seed=seed + 1)
         text[2], mask[2] = 0, False                                                            # an empty (all-padding) title
         R = np.random.default_rng(seed + 2).standard_normal((T_, h * dk)).astype(np.float32)
-        mha = layers.MultiHeadAttention(h, dm, Lw, Lw, dk, dk)
-        attn = layers.Attention(h * dk, att)
-        mha.load_state_dict({k[len("multiheadSelfattention."):]: T(v) for k, v in state.items() if k.startswith("multiheadSelfattention.")})
-        attn.load_state_dict({k[len("attention."):]: T(v) for k, v in state.items() if k.startswith("attention.")})
-        emb = torch.nn.Embedding(V, dm)
-        emb.weight.data.copy_(T(state["word_embedding.weight"]))
-        mha.train(); attn.train()
-        w = emb(T(text))                                                                       # newsEncoders.py:76 (dropout 0)
-        hfeat = torch.relu(mha(w, w, w))                                                       # :78
-        out = attn(hfeat, mask=T(mask.astype(np.int64)))                                       # :80
-        loss = (out * T(R)).sum()
-        loss.backward()
-        named = [("word_embedding.weight", emb.weight)] + [("multiheadSelfattention." + k, v) for k, v in mha.named_parameters()] \
-            + [("attention." + k, v) for k, v in attn.named_parameters()]
-        grads = {}
-        for k, v in named:
-            if tag == "msa_train_tiny":
-                grads["g_" + k] = v.grad.numpy()
-            else:
-                grads.update(grad_digest(k, v.grad.numpy()))
+
+        def step(dtype):
+            mha = layers.MultiHeadAttention(h, dm, Lw, Lw, dk, dk)
+            attn = layers.Attention(h * dk, att)
+            mha.load_state_dict({k[len("multiheadSelfattention."):]: T(v) for k, v in state.items() if k.startswith("multiheadSelfattention.")})
+            attn.load_state_dict({k[len("attention."):]: T(v) for k, v in state.items() if k.startswith("attention.")})
+            emb = torch.nn.Embedding(V, dm)
+            emb.weight.data.copy_(T(state["word_embedding.weight"]))
+            mha.to(dtype).train(); attn.to(dtype).train(); emb.to(dtype)
+            w = emb(T(text))                                                                   # newsEncoders.py:76 (dropout 0)
+            hfeat = torch.relu(mha(w, w, w))                                                   # :78
+            out = attn(hfeat, mask=T(mask.astype(np.int64)))                                   # :80
+            loss = (out * T(R).to(dtype)).sum()
+            loss.backward()
+            named = [("word_embedding.weight", emb.weight)] + [("multiheadSelfattention." + k, v) for k, v in mha.named_parameters()] \
+                + [("attention." + k, v) for k, v in attn.named_parameters()]
+            res = {"out_news_representation": out.detach().numpy(), "out_loss": loss.detach().numpy()}
+            for k, v in named:
+                if tag == "msa_train_tiny":
+                    res["g_" + k] = v.grad.numpy()
+                else:
+                    res.update(grad_digest(k, v.grad.numpy()))
+            return res
+
+        # float32: what the HIP path is held to.  float64 ("f64_" keys): the same step without fp32 rounding, for the news
+        # oracle's own check — some gradients (attention.affine1.bias: a softmax backward that nearly cancels) move by 1e-4 of
+        # their norm in fp32 with the CPU's summation order, more than that check's tolerance
+        f64 = {"f64_" + k: v for k, v in step(torch.float64).items()}
         save(f"{tag}.npz", meta=np.array([T_, Lw, V, dm, h, dk, att]), seeds=np.array([seed, seed + 1, seed + 2]),
-             input_checksum=checksum({"t": text, "m": mask, "r": R}, state), out_news_representation=out.detach().numpy(),
-             out_loss=loss.detach().numpy(), **grads)
+             input_checksum=checksum({"t": text, "m": mask, "r": R}, state), **step(torch.float32), **f64)
 
 
 def fixture_sag():

@@ -1,10 +1,10 @@
 #!/bin/bash
-# single-stream kernel trace of the default workload, grouped by (kernel, grid): tools/exp/solo_trace.sh <outdir> [bench args]
+# kernel trace of the default workload on one bench lane, grouped by (kernel, grid): tools/exp/solo_trace.sh <outdir> [bench args]
 OUT=$(realpath -m $1); shift
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp
-DIGAT_SINGLE_STREAM=1 DIGAT_BENCH_LANES=1 rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -o t -- python3 $ROOT/bench.py --extra-steps 0 --cpu-rows 0 --steps 40 --warmup 5 "$@" > $OUT/bench.json 2> $OUT/trace.err
+DIGAT_BENCH_LANES=1 rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -o t -- python3 $ROOT/bench.py --extra-steps 0 --cpu-rows 0 --steps 40 --warmup 5 "$@" > $OUT/bench.json 2> $OUT/trace.err
 cd $ROOT
 python3 - $OUT <<'PY'
 import csv, glob, sys, collections

@@ -56,7 +56,7 @@ def bench_xattn(B=1024, n=67, d=400, density=None):
     med, best = timeit(run)
     bytes_b = B * (5.0 * n * d * 4 + d * 4 + n * n) + 4 * d
     lane_ops = 3.0 * B * n * n * d + 2.0 * B * n * n * d / 2
-    print(f"xattn B={B} n={n} d={d} skip={os.environ.get('DIGAT_XATTN_SKIP', '0')}: median {med*1e3:.1f} us  best {best*1e3:.1f} us  "
+    print(f"xattn B={B} n={n} d={d}: median {med*1e3:.1f} us  best {best*1e3:.1f} us  "
           f"{bytes_b/med/1e6:.0f} GB/s algorithmic  ({bytes_b/1e6:.0f} MB)")
 
 
@@ -136,7 +136,7 @@ def bench_topic(B=1024, H=50, C=17, d=400):
                                           _lib.stream_ptr()), "topic")
     med, best = timeit(run)
     by = B * (H * d * 4 + d * 4 + H * 8 + (C + 1) * d * 4)
-    print(f"topic B={B} H={H} C1={C+1} d={d} skip={os.environ.get('DIGAT_TOPIC_SKIP', '0')}: median {med*1e3:.1f} us best {best*1e3:.1f} us "
+    print(f"topic B={B} H={H} C1={C+1} d={d}: median {med*1e3:.1f} us best {best*1e3:.1f} us "
           f"{by/med/1e6:.0f} GB/s algorithmic ({by/1e6:.0f} MB)")
 
 
