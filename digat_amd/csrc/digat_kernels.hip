@@ -34,6 +34,26 @@ typedef float v4f __attribute__((ext_vector_type(4)));
     } while (0)
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// Bump allocator over a caller buffer in 256-byte-aligned regions; `ok` turns false on overflow.  Arena() only measures: no
+// buffer, no limit, take() hands out nullptr and `used` ends as the size of the carve (the *_workspace_bytes queries run the
+// carve of their entry this way, so a layout is written once).
+struct Arena {
+    char* base; size_t cap, used; bool ok;
+    Arena() : base(nullptr), cap(SIZE_MAX), used(0), ok(true) {}
+    Arena(void* p, size_t n) : base((char*)p), cap(n), used(0), ok(p != nullptr) {}
+    template <class T> T* take(size_t count) {
+        const size_t bytes = align_up(count * sizeof(T), 256);
+        if (!ok || used + bytes > cap) { ok = false; return nullptr; }
+        T* r = base ? (T*)(base + used) : nullptr;
+        used += bytes;
+        return r;
+    }
+    Arena sub(size_t bytes) {           // the next `bytes` as an arena of their own (a measuring arena hands out a measuring one)
+        Arena r;
+        r.base = take<char>(bytes); r.cap = bytes; r.ok = ok;
+        return r;
+    }
+};
 
 // ---- optional per-kernel event timing (bench.py's roofline leg) ---------------------------------
 // Between digat_profile_start and digat_profile_stop every launch is bracketed by two hipEvents
@@ -219,11 +239,18 @@ int digat_linear_f32(const float* x, int64_t ldx, const float* w, const float* b
 }
 
 // ---- a1 / a2 ------------------------------------------------------------------------------------
-size_t digat_xattn_workspace_bytes(int B, int n, int d) {
-    // h, P, Q [B,n,d] + r [B,d] + alpha [B,n,n]
-    return align_up((size_t)3 * B * n * d * 4, 256) + align_up((size_t)B * d * 4, 256)
-           + align_up((size_t)B * n * n * 4, 256);
+// Eq. 8 workspace: [h | P | Q] [B,n,d] back to back (one three-segment projection writes them), r [B,d] (K3), alpha [B,n,n]
+struct XattnWs { float *h, *P, *Q, *r, *alpha; };
+static XattnWs xattn_carve(Arena& a, int B, int n, int d) {
+    const size_t nd = (size_t)B * n * d;
+    XattnWs w{};
+    w.h = a.take<float>(3 * nd);
+    if (w.h) { w.P = w.h + nd; w.Q = w.P + nd; }
+    w.r = a.take<float>((size_t)B * d);
+    w.alpha = a.take<float>((size_t)B * n * n);
+    return w;
 }
+size_t digat_xattn_workspace_bytes(int B, int n, int d) { Arena a; xattn_carve(a, B, n, d); return a.used; }
 
 int digat_xattn_pairwise_fwd(const float* Pr, const float* Q, const float* h, const float* X,
                              const float* a, const uint8_t* A, float* out, float* alpha,
@@ -234,29 +261,36 @@ int digat_xattn_pairwise_fwd(const float* Pr, const float* Q, const float* h, co
 
 struct TwinLists { const unsigned* word; const int* list; const int* count; };     // user_live_flags_kernel's twins (see there)
 
-// Eq. 8 layer with K3 (r = ctx F3^T + b3) already computed; `r_given` may live anywhere
+// xattn_core's optional inputs; what a caller does not set stays off
+struct XattnOpts {
+    const void* wsplit = nullptr;                                                   // split weight image: bf16x6 / f16x3 projections
+    const int* rowidx = nullptr; const int* nrows_dev = nullptr; const uint8_t* live = nullptr;      // live-row lists
+    int sparse_mode = DIGAT_XATTN_DENSE; const int* sparse_flag = nullptr;
+    int pq_x3 = 0, pq_mode = 0, centre_limit = 0, gemm_format = 0, prof_part = 0;
+    unsigned* range_flag = nullptr; const TwinLists* tw = nullptr;
+};
+
+// Eq. 8 layer with K3 (r = ctx F3^T + b3) already computed; `r_given` may live anywhere.  The workspace is carved at this n
+// (the encoder's is sized for the larger of its two graphs).
 static int xattn_core(const float* X, const uint8_t* A, const float* r_given,
                       const float* W, const float* bW, const float* F1, const float* F2, const float* a,
-                      float* out, float* alpha_out, int B, int n, int d, void* workspace, hipStream_t st,
-                      const void* wsplit = nullptr, const int* rowidx = nullptr, const int* nrows_dev = nullptr,
-                      const uint8_t* live = nullptr, int sparse_mode = DIGAT_XATTN_DENSE, const int* sparse_flag = nullptr,
-                      int pq_x3 = 0, int pq_mode = 0, int centre_limit = 0, int gemm_format = 0, unsigned* range_flag = nullptr,
-                      const TwinLists* tw = nullptr, int prof_part = 0) {
-    const size_t nd = (size_t)B * n * d;
-    float* h = (float*)workspace;
-    float* P = h + nd;
-    float* Q = P + nd;
-    float* alpha = alpha_out ? alpha_out
-                             : (float*)((char*)workspace + align_up(3 * nd * 4, 256) + align_up((size_t)B * d * 4, 256));
+                      float* out, float* alpha_out, int B, int n, int d, void* workspace, size_t workspace_bytes, hipStream_t st,
+                      const XattnOpts& o = XattnOpts()) {
+    Arena ar(workspace, workspace_bytes);
+    const XattnWs w = xattn_carve(ar, B, n, d);
+    if (!ar.ok) return DIGAT_ERR_WORKSPACE;
+    const int* rowidx = o.rowidx; const int* nrows_dev = o.nrows_dev; const uint8_t* live = o.live;
+    const int sparse_mode = o.sparse_mode, pq_mode = o.pq_mode;
+    float *h = w.h, *P = w.P, *Q = w.Q, *alpha = alpha_out ? alpha_out : w.alpha;
     // [h | P | Q] = X [W | F1 | F2]^T (+ bW on h): one pass over X on the matrix cores
     GemmArgs g = gemm_plain(X, d, W, bW, h, d, B * n, d, d, 0);
     g.w[1] = F1; g.bias[1] = nullptr; g.y[1] = P;
     g.w[2] = F2; g.bias[2] = nullptr; g.y[2] = Q;
     g.nsegs = 3;
-    g.wsplit = (const unsigned short*)wsplit;          // non-NULL: split operands on the bf16 / fp16 matrix cores
-    g.format = gemm_format; g.range_flag = range_flag;
+    g.wsplit = (const unsigned short*)o.wsplit;        // non-NULL: split operands on the bf16 / fp16 matrix cores
+    g.format = o.gemm_format; g.range_flag = o.range_flag;
     g.radd = r_given; g.radd_seg = 1; g.rows_per_b = n; // P' = K3 + K1: the reference's left-to-right order
-    g.x3_segs = pq_x3 ? 6 : 0;                          // DIGAT_PROJ_PQ_X3: P and Q (segments 1, 2) with three products
+    g.x3_segs = o.pq_x3 ? 6 : 0;                        // DIGAT_PROJ_PQ_X3: P and Q (segments 1, 2) with three products
     // DIGAT_PQ_BF16 (pq_mode & 1): P' and Q stored in bf16, read by the wave-per-centre sparse kernel; & 2: one product for them
     const bool pq16 = (pq_mode & 1) && gemm_is_bf16x6(g) && sparse_mode == DIGAT_XATTN_SPARSE && !alpha_out && n > 16 &&
                       d / 4 <= 256 && d % 8 == 0 && (long)B * n >= 2048;
@@ -273,17 +307,31 @@ static int xattn_core(const float* X, const uint8_t* A, const float* r_given,
     const int* skip_if = nullptr;
     if (sparse_mode != DIGAT_XATTN_DENSE && !alpha_out && n > 16 && d / 4 <= 256) {      // see xattn_sparse_kernel
         SparseArgs sg{P, Q, h, X, a, A, out, nullptr, nullptr, listed ? live : nullptr,
-                      sparse_mode == DIGAT_XATTN_AUTO ? sparse_flag : nullptr, B, n, d / 4, 0, nullptr, nullptr,
-                      listed && live ? rowidx : nullptr, listed && live ? nrows_dev : nullptr, 0, nullptr, pq8 ? 2 : (pq16 ? 1 : 0), centre_limit};
+                      sparse_mode == DIGAT_XATTN_AUTO ? o.sparse_flag : nullptr, B, n, d / 4, 0, nullptr, nullptr,
+                      listed && live ? rowidx : nullptr, listed && live ? nrows_dev : nullptr, 0, nullptr, pq8 ? 2 : (pq16 ? 1 : 0), o.centre_limit};
         sg.ld8 = pq8 ? ld8 : 0;
-        sg.prof_part = prof_part;
-        if (tw && listed && live) { sg.twin = tw->word; sg.twlist = tw->list; sg.twcount = tw->count; }
+        sg.prof_part = o.prof_part;
+        if (o.tw && listed && live) { sg.twin = o.tw->word; sg.twlist = o.tw->list; sg.twcount = o.tw->count; }
         const int rcs = launch_sparse(sg, st);
         if (rcs || sparse_mode == DIGAT_XATTN_SPARSE) return rcs;
-        skip_if = sparse_flag;
+        skip_if = o.sparse_flag;
     }
     return launch_xattn_pairwise(P, Q, h, X, a, A, out, alpha, B, n, d, st, listed ? live : nullptr, nullptr, nullptr,
                                  alpha_out != nullptr, skip_if);
+}
+
+// the xattn entries: r = ctx F3^T + b3 (K3) into the workspace's r, then the layer
+static int xattn_fwd_k3(const float* X, const uint8_t* A, const float* ctx, const float* W, const float* bW, const float* F1,
+                        const float* F2, const float* F3, const float* b3, const float* a, float* out, float* alpha_out,
+                        int B, int n, int d, void* workspace, size_t workspace_bytes, void* stream, const XattnOpts& o = XattnOpts()) {
+    Arena ar(workspace, workspace_bytes);
+    const XattnWs w = xattn_carve(ar, B, n, d);
+    if (!ar.ok) return DIGAT_ERR_WORKSPACE;
+    if (B == 0) return DIGAT_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = launch_gemm(gemm_plain(ctx, d, F3, b3, w.r, d, B, d, d, 0), st);
+    if (rc) return rc;
+    return xattn_core(X, A, w.r, W, bW, F1, F2, a, out, alpha_out, B, n, d, workspace, workspace_bytes, st, o);
 }
 
 int digat_xattn_fwd(const float* X, const uint8_t* A, const float* ctx,
@@ -294,14 +342,7 @@ int digat_xattn_fwd(const float* X, const uint8_t* A, const float* ctx,
     if (!X || !A || !ctx || !W || !F1 || !F2 || !F3 || !a || !out || !workspace) return DIGAT_ERR_ARG;
     if (B < 0 || n <= 0 || d <= 0) return DIGAT_ERR_ARG;
     if (d % 4 || n > DIGAT_MAX_NODES) return DIGAT_ERR_SHAPE;
-    if (workspace_bytes < digat_xattn_workspace_bytes(B, n, d)) return DIGAT_ERR_WORKSPACE;
-    if (B == 0) return DIGAT_OK;
-    hipStream_t st = (hipStream_t)stream;
-    float* r = (float*)((char*)workspace + align_up((size_t)3 * B * n * d * 4, 256));
-    // r = ctx F3^T + b3   (K3)
-    const int rc = launch_gemm(gemm_plain(ctx, d, F3, b3, r, d, B, d, d, 0), st);
-    if (rc) return rc;
-    return xattn_core(X, A, r, W, bW, F1, F2, a, out, alpha_out, B, n, d, workspace, st);
+    return xattn_fwd_k3(X, A, ctx, W, bW, F1, F2, F3, b3, a, out, alpha_out, B, n, d, workspace, workspace_bytes, stream);
 }
 
 int digat_xattn_fwd_mode(const float* X, const uint8_t* A, const float* ctx,
@@ -313,13 +354,9 @@ int digat_xattn_fwd_mode(const float* X, const uint8_t* A, const float* ctx,
     if (!X || !A || !ctx || !W || !F1 || !F2 || !F3 || !a || !out || !workspace) return DIGAT_ERR_ARG;
     if (B < 0 || n <= 0 || d <= 0) return DIGAT_ERR_ARG;
     if (d % 4 || n > DIGAT_MAX_NODES) return DIGAT_ERR_SHAPE;
-    if (workspace_bytes < digat_xattn_workspace_bytes(B, n, d)) return DIGAT_ERR_WORKSPACE;
-    if (B == 0) return DIGAT_OK;
-    hipStream_t st = (hipStream_t)stream;
-    float* r = (float*)((char*)workspace + align_up((size_t)3 * B * n * d * 4, 256));
-    const int rc = launch_gemm(gemm_plain(ctx, d, F3, b3, r, d, B, d, d, 0), st);
-    if (rc) return rc;
-    return xattn_core(X, A, r, W, bW, F1, F2, a, out, nullptr, B, n, d, workspace, st, nullptr, nullptr, nullptr, nullptr, mode);
+    XattnOpts o;
+    o.sparse_mode = mode;
+    return xattn_fwd_k3(X, A, ctx, W, bW, F1, F2, F3, b3, a, out, nullptr, B, n, d, workspace, workspace_bytes, stream, o);
 }
 
 int digat_xattn_fwd_lowprec(const float* X, const uint8_t* A, const float* ctx,
@@ -331,13 +368,9 @@ int digat_xattn_fwd_lowprec(const float* X, const uint8_t* A, const float* ctx,
     if (!X || !A || !ctx || !W || !F1 || !F2 || !F3 || !a || !wsplit || !out || !workspace) return DIGAT_ERR_ARG;
     if (B < 0 || n <= 0 || d <= 0) return DIGAT_ERR_ARG;
     if (d % 80 || d > 1024 || n <= 16 || n > DIGAT_MAX_NODES || (long)B * n < 2048) return DIGAT_ERR_SHAPE;
-    if (workspace_bytes < digat_xattn_workspace_bytes(B, n, d)) return DIGAT_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    float* r = (float*)((char*)workspace + align_up((size_t)3 * B * n * d * 4, 256));
-    const int rc = launch_gemm(gemm_plain(ctx, d, F3, b3, r, d, B, d, d, 0), st);
-    if (rc) return rc;
-    return xattn_core(X, A, r, W, bW, F1, F2, a, out, nullptr, B, n, d, workspace, st, wsplit, nullptr, nullptr, nullptr, DIGAT_XATTN_SPARSE,
-                      nullptr, 0, pq == 1 ? 1 : (pq == 2 ? 4 : 0), 0, format, nullptr);
+    XattnOpts o;
+    o.wsplit = wsplit; o.sparse_mode = DIGAT_XATTN_SPARSE; o.pq_mode = pq == 1 ? 1 : (pq == 2 ? 4 : 0); o.gemm_format = format;
+    return xattn_fwd_k3(X, A, ctx, W, bW, F1, F2, F3, b3, a, out, nullptr, B, n, d, workspace, workspace_bytes, stream, o);
 }
 
 // ---- bf16x6 weight preparation + a directly callable linear (tests, micro-benchmarks) --------------
@@ -497,23 +530,25 @@ int digat_linear_f32x3(const float* x, int64_t ldx, const float* w, const float*
 }
 
 // ---- a3 -----------------------------------------------------------------------------------------
-size_t digat_news_ctx_workspace_bytes(int B, int N, int d) {
-    (void)N;
-    return 3 * align_up((size_t)B * d * 4, 256);
+// query, K^T query and the global context, [B,d] each
+struct NewsCtxWs { float *qv, *kq, *glob; };
+static NewsCtxWs news_ctx_carve(Arena& a, int B, int d) {
+    const size_t bd = (size_t)B * d;
+    return NewsCtxWs{a.take<float>(bd), a.take<float>(bd), a.take<float>(bd)};      // braces: taken left to right
 }
+size_t digat_news_ctx_workspace_bytes(int B, int N, int d) { (void)N; Arena a; news_ctx_carve(a, B, d); return a.used; }
 
 int digat_news_ctx_fwd(const float* X, const uint8_t* mask, const float* Kc, const float* Qc, const float* bQc,
                        const float* Wg, const float* bg, const float* addend, float* out, int B, int N, int d,
                        void* workspace, size_t workspace_bytes, void* stream) {
     if (!X || !mask || !Kc || !Qc || !Wg || !out || !workspace || B < 0 || N <= 0 || d <= 0) return DIGAT_ERR_ARG;
     if (d % 4 || N > DIGAT_MAX_NODES) return DIGAT_ERR_SHAPE;
-    if (workspace_bytes < digat_news_ctx_workspace_bytes(B, N, d)) return DIGAT_ERR_WORKSPACE;
+    Arena ar(workspace, workspace_bytes);
+    const NewsCtxWs w = news_ctx_carve(ar, B, d);
+    if (!ar.ok) return DIGAT_ERR_WORKSPACE;
     if (B == 0) return DIGAT_OK;
     hipStream_t st = (hipStream_t)stream;
-    const size_t slot = align_up((size_t)B * d * 4, 256);
-    float* qv = (float*)workspace;
-    float* kq = (float*)((char*)workspace + slot);
-    float* glob = (float*)((char*)workspace + 2 * slot);
+    float *qv = w.qv, *kq = w.kq, *glob = w.glob;
     const long ldx = (long)N * d;      // node 0 of every row: the local context (graphEncoders.py:110)
     int rc;
     rc = launch_gemm(gemm_plain(X, ldx, Qc, bQc, qv, d, B, d, d, 0), st);           // Q(query)
@@ -529,10 +564,13 @@ int digat_news_ctx_fwd(const float* X, const uint8_t* mask, const float* Kc, con
 }
 
 // ---- a4 -----------------------------------------------------------------------------------------
-size_t digat_user_ctx_workspace_bytes(int B, int U, int H, int C1, int d) {
-    (void)U; (void)H;
-    return 2 * align_up((size_t)B * d * 4, 256) + 2 * align_up((size_t)B * C1 * d * 4, 256);
+// query and K^T query [B,d], the pooled topics T and featureAffine's T2 [B,C1,d]
+struct UserCtxWs { float *qv, *kq, *T, *T2; };
+static UserCtxWs user_ctx_carve(Arena& a, int B, int C1, int d) {
+    const size_t bd = (size_t)B * d, bcd = (size_t)B * C1 * d;
+    return UserCtxWs{a.take<float>(bd), a.take<float>(bd), a.take<float>(bcd), a.take<float>(bcd)};
 }
+size_t digat_user_ctx_workspace_bytes(int B, int U, int H, int C1, int d) { (void)U; (void)H; Arena a; user_ctx_carve(a, B, C1, d); return a.used; }
 
 int digat_topic_pool_fwd(const float* Xu, const float* kq, const int64_t* cat_idx, float* out,
                          int B, int U, int H, int C1, int d, void* stream) {
@@ -548,14 +586,12 @@ int digat_user_ctx_fwd(const float* Xu, const uint8_t* cat_mask, const int64_t* 
         return DIGAT_ERR_ARG;
     if (B < 0 || H < 0 || U < H || C1 <= 0 || d <= 0) return DIGAT_ERR_ARG;
     if (d % 4 || C1 > DIGAT_MAX_NODES || H > TOPIC_MAX_H) return DIGAT_ERR_SHAPE;
-    if (workspace_bytes < digat_user_ctx_workspace_bytes(B, U, H, C1, d)) return DIGAT_ERR_WORKSPACE;
+    Arena ar(workspace, workspace_bytes);
+    const UserCtxWs w = user_ctx_carve(ar, B, C1, d);
+    if (!ar.ok) return DIGAT_ERR_WORKSPACE;
     if (B == 0) return DIGAT_OK;
     hipStream_t st = (hipStream_t)stream;
-    const size_t s1 = align_up((size_t)B * d * 4, 256), s2 = align_up((size_t)B * C1 * d * 4, 256);
-    float* qv = (float*)workspace;
-    float* kq = (float*)((char*)workspace + s1);
-    float* T = (float*)((char*)workspace + 2 * s1);
-    float* T2 = (float*)((char*)workspace + 2 * s1 + s2);
+    float *qv = w.qv, *kq = w.kq, *T = w.T, *T2 = w.T2;
     int rc;
     // topic-level attention (:126-130)
     rc = launch_gemm(gemm_plain(c_n, d, Qu, bQu, qv, d, B, d, d, 0), st);
@@ -626,16 +662,94 @@ static size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
 // pooled.  The news kernels are small (N = 10 nodes, [B,d] linears: tens of workgroups, latency chains) and run
 // on a side stream under the user graph's projection / score / aggregation, which fill the chip; fork and join
 // are two events per layer (a pattern hipGraph capture accepts).
-static size_t l0_chunk_bytes(int B, int U);      // the extra lists of the folded path (defined with the workspace sizes below)
-// group-level outputs of user_live_flags_kernel (grouped entries: at most B / 4 groups), expanded to rows by live_expand_kernel
-static size_t live_group_bytes(int B, int U, int C1) {
-    const size_t Gm = (size_t)B / 4 + 1;
-    return 2 * align_up(Gm * U, 256) + align_up(Gm * U * 4, 256) + align_up(Gm * C1, 256) + 5 * align_up(Gm * 4, 256);
+
+// The encoder's workspace, carved by encoder_carve alone (the entries carve it, the *_workspace_bytes queries measure it).  The
+// grouped and shared entries append their regions after the base layout, so every base region has one offset in all three.
+enum { ENC_PLAIN, ENC_GROUPED, ENC_SHARED };
+struct FoldCtxWs { float *T, *T2, *glob; };      // the folded path's [B,C1,d] pooled topics + featureAffine, [B,d] news context
+struct EncoderWs {
+    float *Xu[2], *Xn[2];                   // user nodes [B,U,d] and news nodes [B,N,d], ping-pong
+    char* xws; size_t xws_bytes;            // Eq. 8 of either graph: sized for max(N, U), carved by xattn_core at the graph's n
+    XattnWs xu;                             // ... carved at n = U: layer 0 of grouped / shared rows (group_project)
+    char* cws; size_t cws_bytes;            // max(news_ctx, user_ctx): the unfolded path's context entries carve it themselves,
+    FoldCtxWs fc;                           // ... the folded path lays T, T2, glob inside it
+    float *kq_t, *kq_u, *r_user[2], *r_news;  // folded path: topic / user queries from c_n; K3 of the user (ping-pong) and news graphs
+    char* xws_news; size_t xws_news_bytes;  // the news graph's own Eq. 8 (side stream)
+    XattnWs xn;                             // ... carved at n = N
+    // live nodes (cnt, off, idx, flags1) and live buckets (cnt2, off2, idx2, flags2) of the user graphs; adjacency entries per row
+    // and the sparse / dense decision (flag); 1 + the last live history slot of every row (hlast)
+    int *cnt, *off, *idx, *cnt2, *off2, *idx2, *entries, *flag, *hlast;
+    uint8_t *flags1, *flags2;
+    int *cnt_n, *off_n, *idx_n; uint8_t* flags_n;      // live nodes of the news graphs (news_live_flags_kernel)
+    // layer 0 of grouped rows (xattn_sparse_l0_kernel): group starts, rows led by each row, offsets and list of the live centres
+    // of the chunk-leading rows
+    int *l0_gs, *l0_off; uint8_t* l0_lead; int* l0_idx;
+    // twins (xattn_sparse_twin_kernel): twin words, lead flags, leads per row, offsets, list
+    unsigned* tw_word; int* tw_list; uint8_t* tw_flags; int *tw_cnt, *tw_off;
+    int *gl_off, *gl_idx;                   // shared runs: offsets and list of the live nodes of the run-leading rows
+    int* idx32;                             // the candidate ids as 32-bit indices (layer 0 of larger news graphs from the tables)
+    // ENC_GROUPED: the per-group adjacency / category arrays expanded to rows; user_live_flags_kernel's outputs per group (at
+    // most B / 4 + 1 groups), expanded to rows by live_expand_kernel
+    uint8_t *Au, *cm; int64_t* ci;
+    uint8_t *fg, *tfg; unsigned* twg; uint8_t* bfg; int *cg, *eg, *hg, *bcg, *tcg;
+    uint8_t *same, *is_leader, *lead; int* leader_of;      // ENC_SHARED: equal users, run leaders, layer-0 chunk sizes, run of every row
+};
+static bool encoder_carve(Arena& a, int B, int N, int H, int C, int d, int variant, EncoderWs& e) {
+    const int U = H + C, C1 = C + 1, nmax = N > U ? N : U;
+    const size_t b = (size_t)B, bd = b * d, bu = b * U;
+    e = EncoderWs();
+    for (float*& x : e.Xu) x = a.take<float>(bu * d);
+    for (float*& x : e.Xn) x = a.take<float>(b * N * d);
+    Arena xa = a.sub(digat_xattn_workspace_bytes(B, nmax, d));
+    e.xws = xa.base; e.xws_bytes = xa.cap;
+    e.xu = xattn_carve(xa, B, U, d);
+    Arena ca = a.sub(max_sz(digat_news_ctx_workspace_bytes(B, N, d), digat_user_ctx_workspace_bytes(B, U, H, C1, d)));
+    e.cws = ca.base; e.cws_bytes = ca.cap;
+    e.fc = FoldCtxWs{ca.take<float>(b * C1 * d), ca.take<float>(b * C1 * d), ca.take<float>(bd)};
+    e.kq_t = a.take<float>(bd); e.kq_u = a.take<float>(bd);
+    e.r_user[0] = a.take<float>(bd); e.r_news = a.take<float>(bd); e.r_user[1] = a.take<float>(bd);
+    Arena na = a.sub(digat_xattn_workspace_bytes(B, N, d));
+    e.xws_news = na.base; e.xws_news_bytes = na.cap;
+    e.xn = xattn_carve(na, B, N, d);
+    e.cnt = a.take<int>(b); e.off = a.take<int>(b + 1); e.idx = a.take<int>(bu);
+    e.cnt2 = a.take<int>(b); e.off2 = a.take<int>(b + 1); e.idx2 = a.take<int>(b * C1);
+    e.entries = a.take<int>(b); e.flag = a.take<int>(64); e.hlast = a.take<int>(b);
+    e.flags1 = a.take<uint8_t>(bu); e.flags2 = a.take<uint8_t>(b * C1);
+    e.cnt_n = a.take<int>(b); e.off_n = a.take<int>(b + 1); e.idx_n = a.take<int>(b * N); e.flags_n = a.take<uint8_t>(b * N);
+    e.l0_gs = a.take<int>(b + 64); e.l0_off = a.take<int>(b + 64); e.l0_lead = a.take<uint8_t>(b); e.l0_idx = a.take<int>(bu);
+    e.tw_word = a.take<unsigned>(bu); e.tw_list = a.take<int>(bu); e.tw_flags = a.take<uint8_t>(bu);
+    e.tw_cnt = a.take<int>(b + 64); e.tw_off = a.take<int>(b + 64);
+    e.gl_off = a.take<int>(b + 64); e.gl_idx = a.take<int>(bu);
+    e.idx32 = a.take<int>(b);
+    if (variant == ENC_GROUPED) {           // appended: the grouped regions
+        const size_t g = b / 4 + 1;
+        e.Au = a.take<uint8_t>(bu * U); e.cm = a.take<uint8_t>(b * C1); e.ci = a.take<int64_t>(b * H);
+        e.fg = a.take<uint8_t>(g * U); e.tfg = a.take<uint8_t>(g * U); e.twg = a.take<unsigned>(g * U); e.bfg = a.take<uint8_t>(g * C1);
+        for (int** x : {&e.cg, &e.eg, &e.hg, &e.bcg, &e.tcg}) *x = a.take<int>(g);
+    } else if (variant == ENC_SHARED) {     // appended: the shared regions
+        e.same = a.take<uint8_t>(b); e.is_leader = a.take<uint8_t>(b); e.lead = a.take<uint8_t>(b); e.leader_of = a.take<int>(b);
+    }
+    return a.ok && xa.ok && ca.ok && na.ok;
 }
-// live nodes of the news graphs (news_live_flags_kernel): cnt [B], off [B + 1], list [B N] (int) and flags [B N] (bytes)
-static size_t news_live_bytes(int B, int N) {
-    return (align_up((size_t)B, 64) + align_up((size_t)B + 1, 64) + align_up((size_t)B * N, 64)) * 4 + align_up((size_t)B * N, 256);
-}
+static size_t encoder_ws_bytes(int B, int N, int H, int C, int d, int variant) { Arena a; EncoderWs e; encoder_carve(a, B, N, H, C, d, variant, e); return a.used; }
+
+// One encoder call: what the public entry was given, and the workspace carved from it (encoder_fwd_impl).
+struct EncoderCall {
+    const digat_params* p;
+    const float* Xn_in; const uint8_t *An, *Mn;
+    const float* ue;                        // user embeddings per row (per group: ENC_GROUPED)
+    const uint8_t *Au, *cat_mask; const int64_t* cat_idx;       // per row (ENC_GROUPED: the expanded *_g arrays)
+    const float* c_n0; float *out_news, *out_user;
+    int B, N, H;
+    void* workspace; size_t workspace_bytes; hipStream_t st;
+    int variant;                            // ENC_PLAIN, ENC_GROUPED, ENC_SHARED
+    const int* row_group; int G;            // the group of every row (ENC_SHARED: the row that leads its run)
+    const uint8_t *Au_g, *cm_g; const int64_t* ci_g;            // ENC_GROUPED: the user side per group
+    // cached per-news / per-topic tables of layer 0 and the queries of c_n0 (digat_encoder_fwd_grouped_cached)
+    const float *news_hpq0, *hist_hpq0, *topic_hpq0, *ctxq0; const int64_t* news_index; int64_t news_rows;
+    const uint8_t *run_leader, *run_lead;   // ENC_SHARED: rows that lead a run, rows of the layer-0 chunk a row leads
+    EncoderWs ws;
+};
 struct SideStream { hipStream_t s; hipEvent_t fork, join, early; int ok; };
 // Nothing below is mutable: live-row lists and the side stream are chosen PER CALL through digat_params.flags
 // (DIGAT_PARAMS_NO_LIVE_ROWS, DIGAT_PARAMS_SIDE_STREAM_OFF / _ON), so two host threads with different settings cannot flip each
@@ -669,15 +783,17 @@ static SideStream* side_stream(hipStream_t caller) {
     return ok ? &x : nullptr;
 }
 
-static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const uint8_t* An, const uint8_t* Mn,
-                              const uint8_t* Au, const uint8_t* cat_mask, const int64_t* cat_idx,
-                              float* c_n, float* c_u, int B, int N, int H, float* const Xu[2], float* const Xn[2],
-                              void* xws, void* xws_news, void* cws, float* kq_t, float* kq_u, float* const r_user2[2],
-                              float* r_news, int* live_ws, hipStream_t st, const int* row_group, int G, const float* ue_groups,
-                              const float* Xg0, const float* news_hpq0, const float* hist_hpq0, const float* topic_hpq0,
-                              void* chunk_ws, const uint8_t* Au_g, const uint8_t* cm_g, const int64_t* ci_g, const float* ctxq0,
-                              const int64_t* news_index, int64_t news_rows, const float* c_n_src, void* live_g_ws = nullptr,
-                              const uint8_t* run_leader = nullptr, const uint8_t* run_lead = nullptr, void* news_live_ws = nullptr) {
+// Xg0: the layer-0 user nodes once per group (NULL: per row in w.Xu[0])
+static int encoder_fwd_folded(const EncoderCall& c, const float* Xg0) {
+    const digat_params* p = c.p;
+    const EncoderWs& w = c.ws;
+    const int B = c.B, N = c.N, H = c.H, G = c.G;
+    const uint8_t *An = c.An, *Mn = c.Mn, *Au = c.Au, *cat_mask = c.cat_mask, *run_leader = c.run_leader, *run_lead = c.run_lead;
+    const int64_t* cat_idx = c.cat_idx;
+    const int* row_group = c.row_group;
+    const float *news_hpq0 = c.news_hpq0, *ctxq0 = c.ctxq0;
+    float *c_n = c.out_news, *c_u = c.out_user;
+    hipStream_t st = c.st;
     // SHARED-USER RUNS (digat_encoder_fwd_shared; round 5): the user tensors are given per ROW, as the reference's driver hands them
     // over (util.py:57-67), and consecutive rows with identical users were found on the device: row_group[b] = the ROW that leads
     // row b's run, run_leader[b] = 1 for those rows, run_lead[b] = rows of the layer-0 chunk row b leads.  Layer 0's group-level
@@ -686,6 +802,7 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
     const bool shared = run_leader != nullptr && run_lead != nullptr && row_group != nullptr;
     // c_n_src: where the news context stands BEFORE layer 0 — c_n itself, or (depth >= 1, context given) the caller's c_n0, read
     // in place by the two consumers that precede the first update instead of being copied into c_n first
+    const float* c_n_src = c.c_n0 && p->depth > 0 ? c.c_n0 : c_n;
     const bool xu0_grouped = Xg0 != nullptr;       // layer-0 user nodes exist once per group, at Xg0 [G,U,d]
     const int d = p->d, C = p->category_num, L = p->depth, U = H + C, C1 = C + 1;
     const int fmt = (p->flags & DIGAT_PARAMS_GEMM_F16X3) ? 1 : 0;       // the format every wsplit image of `p` was split in
@@ -693,21 +810,18 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
     // the kernel of the [B,d] linears is named by the caller, not chosen from B: a row's bits must not depend on the batch it sits in
     // (nor on whether its context queries come from the per-news table)
     const int bd_disp = (p->flags & DIGAT_PARAMS_BD_TILED) ? (1 << 30) : 1;
-    const size_t s2 = align_up((size_t)B * C1 * d * 4, 256);
-    float* T = (float*)cws;                       // [B,C1,d] pooled topics
-    float* T2 = (float*)((char*)cws + s2);        // after featureAffine
-    float* glob = (float*)((char*)cws + 2 * s2);  // [B,d]; cws holds >= 2*s2 + 2*[B,d] (user-context layout)
+    float *T = w.fc.T, *T2 = w.fc.T2, *glob = w.fc.glob;
     const int* bucket_idx = nullptr;              // live topic buckets (set by find_live_rows during layer 0)
     const int* nbuckets_dev = nullptr;
     const int* hist_last = nullptr;               // [B]: 1 + the last live history slot of every row (published with the lists)
     int rc;
     // the user-side queries + (optionally) the next user-graph K3, all from c_n
     auto from_c_n = [&](int next_layer, hipStream_t sq) -> int {
-        GemmArgs g = gemm_plain(next_layer == 0 ? c_n_src : c_n, d, p->user_news_fold_W, p->user_news_fold_b, kq_t, d, B, d, d, 0);
-        g.w[1] = p->userAtt_fold_W; g.bias[1] = p->userAtt_fold_b; g.y[1] = kq_u;
+        GemmArgs g = gemm_plain(next_layer == 0 ? c_n_src : c_n, d, p->user_news_fold_W, p->user_news_fold_b, w.kq_t, d, B, d, d, 0);
+        g.w[1] = p->userAtt_fold_W; g.bias[1] = p->userAtt_fold_b; g.y[1] = w.kq_u;
         g.nsegs = 2;
         if (next_layer < L) {
-            g.w[2] = p->user[next_layer].F3; g.bias[2] = p->user[next_layer].b3; g.y[2] = r_user2[next_layer & 1];
+            g.w[2] = p->user[next_layer].F3; g.bias[2] = p->user[next_layer].b3; g.y[2] = w.r_user[next_layer & 1];
             g.nsegs = 3;
         }
         g.wsplit = (const unsigned short*)p->ctx_wsplit[next_layer]; g.format = fmt; g.range_flag = rflag;   // NULL: fp32 MFMA
@@ -719,7 +833,7 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
     // per-news table the caller gathered: ctxq0)
     auto user_ctx_tail = [&](const float* Xu_cur, const float* addend, hipStream_t sq, const int* xgroup = nullptr,
                              const uint8_t* live = nullptr, const float* kq_topic = nullptr, const float* kq_user = nullptr) -> int {
-        if (!kq_topic) { kq_topic = kq_t; kq_user = kq_u; }
+        if (!kq_topic) { kq_topic = w.kq_t; kq_user = w.kq_u; }
         // ONE launch (digat_ctxfused.inc) when the weight version carries the fused image and the shape fits; T, T2 stay unused then
         if (p->featureAffine_fsplit && fmt == 1 && ctxfused_ok(H, C1, d)) {
             const CtxFusedArgs fa{Xu_cur, (long)U * d, xgroup, live, U, live ? hist_last : nullptr, kq_topic, kq_user, cat_idx, cat_mask, addend, c_u,
@@ -739,7 +853,7 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
     };
     auto news_ctx = [&](const float* Xn_cur, hipStream_t sq, bool first) -> int {
         const long ldx = (long)N * d;
-        float* kq = kq_t;                          // free here: the previous user context has consumed it
+        float* kq = w.kq_t;                        // the news context's kq reuses kq_t: the previous user context has consumed it
         GemmArgs gq = gemm_plain(Xn_cur, ldx, p->cand_fold_W, p->cand_fold_b, kq, d, B, d, d, 0);
         gq.wsplit = (const unsigned short*)p->cand_fold_wsplit; gq.format = fmt; gq.range_flag = rflag;
         gq.m_dispatch = bd_disp;
@@ -755,13 +869,14 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
         return launch_gemm(g, sq);
     };
 
-    const bool want_live = L > 0 && !(p->flags & DIGAT_PARAMS_NO_LIVE_ROWS) && live_ws;
+    const bool want_live = L > 0 && !(p->flags & DIGAT_PARAMS_NO_LIVE_ROWS);
     // Eq. 8 of the user graph: the sparse kernel, the dense pair, or both with the device choosing (p->flags; the choice
     // comes out of the adjacency pass of find_live_rows)
     int sparse_mode = p->flags & 3;
-    if (sparse_mode == 3 || (sparse_mode == DIGAT_XATTN_AUTO && !(L > 0 && live_ws))) sparse_mode = DIGAT_XATTN_DENSE;
+    if (sparse_mode == 3 || (sparse_mode == DIGAT_XATTN_AUTO && L == 0)) sparse_mode = DIGAT_XATTN_DENSE;
     const int* sparse_flag = nullptr;
     const int pq_x3 = (p->flags & DIGAT_PROJ_PQ_X3) ? 1 : 0;
+    const int pq_mode = ((p->flags & DIGAT_PQ_BF16) ? 1 : 0) | ((p->flags & DIGAT_PQ_X1) ? 2 : 0) | ((p->flags & DIGAT_PQ_FP8) ? 4 : 0);
     const bool want_scan = want_live || sparse_mode == DIGAT_XATTN_AUTO;      // the adjacency pass: live lists and / or the decision
     // live rows of the user graph for the projections of layers >= 1
     const int* rowidx = nullptr;
@@ -774,39 +889,22 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
     uint8_t* pend_flags = nullptr;
     // layer 0 of grouped rows on the chunk kernel (R rows of an impression per wave: xattn_sparse_l0_kernel): its list — the live
     // centres of the rows that lead a chunk — is made with the other two
-    const bool l0_chunked = chunk_ws && row_group && (Xg0 || shared) && want_live &&
+    const bool l0_chunked = row_group && (Xg0 || shared) && want_live &&
                             sparse_mode == DIGAT_XATTN_SPARSE && d / 4 <= 128 && U <= 128;
-    int* const l0_gs = (int*)chunk_ws;
-    int* const l0_off = l0_gs + align_up((size_t)B + 64, 64);
-    uint8_t* const l0_lead_own = (uint8_t*)(l0_off + align_up((size_t)B + 64, 64));
-    const uint8_t* const l0_lead = shared ? run_lead : l0_lead_own;          // shared runs: the chunk sizes came with the runs
-    int* const l0_idx = (int*)(l0_lead_own + align_up((size_t)B, 256));
+    const uint8_t* const l0_lead = shared ? run_lead : w.l0_lead;           // shared runs: the chunk sizes came with the runs
     // twins: centres of a graph with equal adjacency rows, served together in layers >= 1 (xattn_sparse_twin_kernel)
-    const bool twins = chunk_ws && want_live && sparse_mode == DIGAT_XATTN_SPARSE && d / 4 <= 128 && U <= 128 && L > 1;
-    unsigned* const tw_word = (unsigned*)((char*)l0_idx + align_up((size_t)B * U * 4, 256));
-    int* const tw_list = (int*)((char*)tw_word + align_up((size_t)B * U * 4, 256));
-    uint8_t* const tw_flags = (uint8_t*)tw_list + align_up((size_t)B * U * 4, 256);
-    int* const tw_cnt = (int*)(tw_flags + align_up((size_t)B * U, 256));
-    int* const tw_off = tw_cnt + align_up((size_t)B + 64, 64);
-    // shared runs: the live nodes of the LEADING rows (the rows layer 0's group projection has to make), offsets [B + 64] + list [B U]
-    int* const gl_off = tw_off + align_up((size_t)B + 64, 64);
-    int* const gl_idx = gl_off + align_up((size_t)B + 64, 64);
+    const bool twins = want_live && sparse_mode == DIGAT_XATTN_SPARSE && d / 4 <= 128 && U <= 128 && L > 1;
+    unsigned* const tw_word = w.tw_word; uint8_t* const tw_flags = w.tw_flags;
+    int *const tw_list = w.tw_list, *const tw_cnt = w.tw_cnt, *const tw_off = w.tw_off;
+    // shared runs: the live nodes of the LEADING rows (the rows layer 0's group projection has to make)
+    int *const gl_off = w.gl_off, *const gl_idx = w.gl_idx, *const l0_gs = w.l0_gs, *const l0_off = w.l0_off, *const l0_idx = w.l0_idx;
     TwinLists tw_pub{nullptr, nullptr, nullptr};
     auto find_live_rows = [&](hipStream_t sq) -> int {
-        int* cnt = live_ws;
-        int* off = cnt + align_up((size_t)B, 64);
-        int* idx = off + align_up((size_t)B + 1, 64);
-        int* cnt2 = idx + align_up((size_t)B * U, 64);
-        int* off2 = cnt2 + align_up((size_t)B, 64);
-        int* idx2 = off2 + align_up((size_t)B + 1, 64);
-        int* entries = idx2 + align_up((size_t)B * C1, 64);
-        int* flag = entries + align_up((size_t)B, 64);
-        int* hlast = flag + 64;
-        uint8_t* flags1 = (uint8_t*)(hlast + align_up((size_t)B, 64));
-        uint8_t* flags2 = flags1 + align_up((size_t)B * U, 256);
+        int *cnt = w.cnt, *off = w.off, *idx = w.idx, *cnt2 = w.cnt2, *off2 = w.off2, *idx2 = w.idx2, *entries = w.entries, *flag = w.flag;
+        int* hlast = w.hlast; uint8_t *flags1 = w.flags1, *flags2 = w.flags2;
         ProfScope prof(DIGAT_KERNEL_GLUE, (double)B * ((double)U * U + 2.0 * C1 + H * 8.0) + (double)B * (U + C1) * 6, sq);
         if (l0_chunked && !shared) {
-            hipLaunchKernelGGL(sparse_l0_chunks_kernel, dim3(1), dim3(1024), 0, sq, row_group, B, G, SPARSE_L0_ROWS, l0_gs, l0_lead_own);
+            hipLaunchKernelGGL(sparse_l0_chunks_kernel, dim3(1), dim3(1024), 0, sq, row_group, B, G, SPARSE_L0_ROWS, l0_gs, w.l0_lead);
             DIGAT_CHECK_LAUNCH();
         }
         if (shared) {
@@ -822,18 +920,12 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
                                 cnt, want_entries ? entries : nullptr, hlast, cnt2, twins ? tw_cnt : nullptr};
             hipLaunchKernelGGL(live_expand_kernel, dim3((B + 3) / 4), dim3(256), 0, sq, le, row_group, B, U, C1);
             DIGAT_CHECK_LAUNCH();
-        } else if (live_g_ws && row_group && Au_g && cm_g && ci_g && 4 * (long)G <= B) {
+        } else if (c.variant == ENC_GROUPED) {
             // the user side is given per group: the adjacency pass once per GROUP, its results handed to the group's rows
-            const size_t Gm = (size_t)B / 4 + 1;
-            uint8_t* fg = (uint8_t*)live_g_ws;
-            uint8_t* tfg = fg + align_up(Gm * U, 256);
-            unsigned* twg = (unsigned*)(tfg + align_up(Gm * U, 256));
-            uint8_t* bfg = (uint8_t*)twg + align_up(Gm * U * 4, 256);
-            int* cg = (int*)(bfg + align_up(Gm * C1, 256));
-            const size_t gi = align_up(Gm * 4, 256) / 4;
-            int *eg = cg + gi, *hg = eg + gi, *bcg = hg + gi, *tcg = bcg + gi;
+            uint8_t *fg = w.fg, *tfg = w.tfg, *bfg = w.bfg; unsigned* twg = w.twg;
+            int *cg = w.cg, *eg = w.eg, *hg = w.hg, *bcg = w.bcg, *tcg = w.tcg;
             const bool want_entries = sparse_mode == DIGAT_XATTN_AUTO;
-            hipLaunchKernelGGL(user_live_flags_kernel, dim3((G + 3) / 4), dim3(256), (size_t)4 * ((U * U + 63) & ~63), sq, Au_g, cm_g, ci_g, G, U, H, C1,
+            hipLaunchKernelGGL(user_live_flags_kernel, dim3((G + 3) / 4), dim3(256), (size_t)4 * ((U * U + 63) & ~63), sq, c.Au_g, c.cm_g, c.ci_g, G, U, H, C1,
                                fg, cg, want_entries ? eg : (int*)nullptr, hg, bfg, bcg,
                                twins ? twg : (unsigned*)nullptr, twins ? tfg : (uint8_t*)nullptr, twins ? tcg : (int*)nullptr);
             DIGAT_CHECK_LAUNCH();
@@ -900,17 +992,15 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
     // (news_live_flags_kernel); the context pooling masks them and skips zero weights, nobody else reads them.  Larger graphs
     // (N > 16, sparse kernel): projection and Eq. 8 run on the live list.  Small graphs: the projections of layers >= 1 do; the
     // one-workgroup-per-graph Eq. 8 kernel still computes every centre (a live centre visits its adjacency entries only: live nodes).
-    const bool news_lists_on = L > 0 && news_live_ws && d / 4 <= 256 && !(p->flags & DIGAT_PARAMS_NO_LIVE_ROWS);
+    const bool news_lists_on = L > 0 && d / 4 <= 256 && !(p->flags & DIGAT_PARAMS_NO_LIVE_ROWS);
     const bool news_lists = news_lists_on && ((!news_early && (p->flags & DIGAT_NEWS_XATTN_SPARSE) && N > 16) || (news_early && L > 1 && B >= 2048));
     // (small graphs below 2 048 rows: the three list launches sit on the news chain's critical path and cost what two smaller projections save)
     const int* news_rowidx = nullptr; const int* news_nrows = nullptr; const uint8_t* news_flags = nullptr;
     auto news_project = [&](int layer, const float* Xn_cur, hipStream_t sq) -> int {
         const digat_layer_params& ln = p->news[layer];
-        const size_t ndn = (size_t)B * N * d;
-        float* hn = (float*)xws_news;
-        GemmArgs gp = gemm_plain(Xn_cur, d, ln.W, ln.bW, hn, d, B * N, d, d, 0);
-        gp.w[1] = ln.F1; gp.bias[1] = nullptr; gp.y[1] = hn + ndn;
-        gp.w[2] = ln.F2; gp.bias[2] = nullptr; gp.y[2] = hn + 2 * ndn;
+        GemmArgs gp = gemm_plain(Xn_cur, d, ln.W, ln.bW, w.xn.h, d, B * N, d, d, 0);
+        gp.w[1] = ln.F1; gp.bias[1] = nullptr; gp.y[1] = w.xn.P;
+        gp.w[2] = ln.F2; gp.bias[2] = nullptr; gp.y[2] = w.xn.Q;
         gp.nsegs = 3;
         gp.x3_segs = pq_x3 ? 6 : 0;
         gp.m_dispatch = 1 << 30;       // always the large-M kernel: a row's bits then do not depend on the batch it sits in
@@ -929,11 +1019,9 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
         if (shared) {
             // shared runs: [h|P|Q] of the LEADING rows' live nodes, in place in the full-size planes (the per-row launch of layer 0
             // restricted to the rows whose results anybody reads; K3 joins in the Eq. 8 kernel, as for the groups below)
-            const size_t ndf = (size_t)B * U * d;
-            float* hs = (float*)xws;
-            GemmArgs gs = gemm_plain(Xu[0], d, lu.W, lu.bW, hs, d, B * U, d, d, 0);
-            gs.w[1] = lu.F1; gs.bias[1] = nullptr; gs.y[1] = hs + ndf;
-            gs.w[2] = lu.F2; gs.bias[2] = nullptr; gs.y[2] = hs + 2 * ndf;
+            GemmArgs gs = gemm_plain(w.Xu[0], d, lu.W, lu.bW, w.xu.h, d, B * U, d, d, 0);
+            gs.w[1] = lu.F1; gs.bias[1] = nullptr; gs.y[1] = w.xu.P;
+            gs.w[2] = lu.F2; gs.bias[2] = nullptr; gs.y[2] = w.xu.Q;
             gs.nsegs = 3;
             gs.x3_segs = pq_x3 ? 6 : 0;
             gs.wsplit = (const unsigned short*)lu.wsplit;
@@ -943,28 +1031,27 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
             return launch_gemm(gs, sq, DIGAT_KERNEL_PROJ);
         }
         const size_t ndg = (size_t)G * U * d;
-        const size_t nd = (size_t)B * U * d;
-        float* Xg = xu0_grouped ? const_cast<float*>(Xg0) : Xu[1];     // group nodes: built by the caller, or here (Xu[1] is free until layer 0 writes it)
-        float* h0 = (float*)xws;
+        float* Xg = xu0_grouped ? const_cast<float*>(Xg0) : w.Xu[1];   // group nodes: built by the caller, or here (Xu[1] is free until layer 0 writes it)
+        float* h0 = w.xu.h;
         float* P0 = h0 + ndg;                               // behind the groups' h in the h slot (2 ndg <= nd)
-        float* Q0 = h0 + 2 * nd;
+        float* Q0 = w.xu.Q;                                 // the groups' Q at the start of the full-size Q plane
         const long total4 = (long)ndg / 4;
         int blocks = (int)((total4 + 255) / 256);
         if (blocks > 2048) blocks = 2048;
         if (!xu0_grouped) {
-            hipLaunchKernelGGL(build_user_nodes_kernel, dim3(blocks), dim3(256), 0, sq, (const float4*)ue_groups,
+            hipLaunchKernelGGL(build_user_nodes_kernel, dim3(blocks), dim3(256), 0, sq, (const float4*)c.ue,
                                (const float4*)p->topic_node_embedding, (float4*)Xg, (long)G, H, C, d / 4, (const int*)nullptr);
             DIGAT_CHECK_LAUNCH();
         }
-        if (hist_hpq0 && topic_hpq0 && (long)B * U >= 2048) {
+        if (c.hist_hpq0 && c.topic_hpq0 && (long)B * U >= 2048) {
             // [h|P|Q] of a history node depend on that news alone and those of a topic node on nothing: the caller keeps them
             // per news / per topic (digat_user_project0) and hands over the groups' history rows; the projection GEMM of the
             // groups becomes three assemblies [history rows | topic rows] (same kernel, same bits: rows are independent)
             float* dst[3] = {h0, P0, Q0};
             UserNodes3 un3;
             for (int t = 0; t < 3; ++t) {
-                un3.hist[t] = (const float4*)(hist_hpq0 + (size_t)t * G * H * d);
-                un3.topic[t] = (const float4*)(topic_hpq0 + (size_t)t * C * d);
+                un3.hist[t] = (const float4*)(c.hist_hpq0 + (size_t)t * G * H * d);
+                un3.topic[t] = (const float4*)(c.topic_hpq0 + (size_t)t * C * d);
                 un3.dst[t] = (float4*)dst[t];
             }
             hipLaunchKernelGGL(build_user_nodes3_kernel, dim3(blocks, 3), dim3(256), 0, sq, un3, (long)G, H, C, d / 4);
@@ -1001,7 +1088,7 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
         if (hipEventRecord(side->early, side->s) != hipSuccess) return DIGAT_ERR_LAUNCH;
     }
     if (news_early && !news_hpq0) {      // news_hpq0: the caller kept layer 0's news projections per news (digat_news_project0)
-        rc = news_project(0, Xn_in, side ? side->s : st);
+        rc = news_project(0, c.Xn_in, side ? side->s : st);
         if (rc) return rc;
     }
     // [kq_topic | kq_user | K3 of the user graph's layer 0] are functions of the candidate's cached c_n0: a caller that keeps them
@@ -1012,15 +1099,15 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
         if (rc) return rc;
     }
     const bool xu0_shared = shared && sparse_mode == DIGAT_XATTN_SPARSE;      // only the leading rows of Xu[0] were built: read through row_group
-    rc = user_ctx_tail(xu0_grouped ? Xg0 : Xu[0], nullptr, st, (xu0_grouped || xu0_shared) ? row_group : nullptr, nullptr,
+    rc = user_ctx_tail(xu0_grouped ? Xg0 : w.Xu[0], nullptr, st, (xu0_grouped || xu0_shared) ? row_group : nullptr, nullptr,
                        ctxq0 ? ctxq0 : nullptr, ctxq0 ? ctxq0 + bd : nullptr);        // c_u (:192)
     if (rc) return rc;
-    const float* xn_cur = Xn_in;
+    const float* xn_cur = c.Xn_in;
     int un = 0, nn = 0;
     for (int i = 0; i < L; ++i) {
         const digat_layer_params& ln = p->news[i];
         const digat_layer_params& lu = p->user[i];
-        const float* r_user = (i == 0 && ctxq0 && L > 0) ? ctxq0 + 2 * bd : r_user2[i & 1];     // K3 of the user graph, from the previous c_n
+        const float* r_user = (i == 0 && ctxq0 && L > 0) ? ctxq0 + 2 * bd : w.r_user[i & 1];     // K3 of the user graph, from the previous c_n
         hipStream_t sn = side ? side->s : st;
         if (side && i == 0) {                      // the news chain starts from the initial c_u (caller's stream)
             if (hipEventRecord(side->fork, st) != hipSuccess || hipStreamWaitEvent(sn, side->fork, 0) != hipSuccess)
@@ -1044,12 +1131,11 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
         // test_uninitialised_workspace_cannot_reach_the_outputs fills the scratch with NaN patterns).
         if (i == 0 && want_live) publish_live_rows();
         if (i == 0 && row_group) {
-            const size_t nd = (size_t)B * U * d;
-            const size_t ndg = shared ? nd : (size_t)G * U * d;      // shared runs: full-size planes, a group's rows sit in its leading row's slots
-            float* h0 = (float*)xws;
-            float* P0 = h0 + ndg;
-            float* P = h0 + nd;
-            float* Q0 = P + nd;
+            const size_t ndg = shared ? (size_t)B * U * d : (size_t)G * U * d;      // shared runs: full-size planes, a group's rows sit in its leading row's slots
+            float* h0 = w.xu.h;
+            float* P0 = h0 + ndg;                           // group_project's layout
+            float* P = w.xu.P;
+            float* Q0 = w.xu.Q;
             if (!group_early) {
                 rc = group_project(st);
                 if (rc) return rc;
@@ -1059,9 +1145,9 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
                 // P' = K1 (the groups' P0) + K3 (this layer's r_user) is formed inside the kernel: nothing is expanded
                 // live centres only (the list of find_live_rows), P / Q / h / X read through the group index
                 const bool l0_live = want_live && live_flags;
-                SparseArgs sg{P0, Q0, h0, xu0_grouped ? Xg0 : Xu[0], lu.a, Au, Xu[1], r_user, row_group, l0_live ? live_flags : nullptr,
+                SparseArgs sg{P0, Q0, h0, xu0_grouped ? Xg0 : w.Xu[0], lu.a, Au, w.Xu[1], r_user, row_group, l0_live ? live_flags : nullptr,
                                     sparse_mode == DIGAT_XATTN_AUTO ? sparse_flag : nullptr, B, U, d / 4, (xu0_grouped || xu0_shared) ? 1 : 0,
-                                    (!l0_live && xu0_grouped && want_live) ? (const uint8_t*)pend_flags : nullptr, Xu[0],
+                                    (!l0_live && xu0_grouped && want_live) ? (const uint8_t*)pend_flags : nullptr, w.Xu[0],
                                     l0_live ? rowidx : nullptr, l0_live ? nrows_dev : nullptr, G, nullptr, 0, 0};
                 if (l0_chunked && l0_live && sparse_l0_ok(sg)) {
                     // R rows of an impression per wave: every neighbour row fetched serves R rows (xattn_sparse_l0_kernel; same bits)
@@ -1071,7 +1157,8 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
             }
             if (!rc && !(sparse_mode == DIGAT_XATTN_SPARSE && d / 4 <= 256)) {
                 const int* skip_if = sparse_mode == DIGAT_XATTN_AUTO && d / 4 <= 256 ? sparse_flag : nullptr;
-                float* alpha = (float*)((char*)xws + align_up(3 * nd * 4, 256) + align_up((size_t)B * d * 4, 256));
+                const size_t nd = (size_t)B * U * d;
+                float* alpha = w.xu.alpha;
                 {
                     const long total4 = (long)nd / 4;
                     int blocks = (int)((total4 + 255) / 256);
@@ -1081,34 +1168,33 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
                                        row_group, (float4*)P, (long)B, U, d / 4, skip_if);
                     DIGAT_CHECK_LAUNCH();
                 }
-                rc = launch_xattn_pairwise(P, Q0, h0, Xu[0], lu.a, Au, Xu[1], alpha, B, U, d, st, nullptr, row_group, nullptr, true,
+                rc = launch_xattn_pairwise(P, Q0, h0, w.Xu[0], lu.a, Au, w.Xu[1], alpha, B, U, d, st, nullptr, row_group, nullptr, true,
                                            skip_if);
             }
         } else {
             // every layer projects, scores and writes the live nodes only (layer 0 too: see publish_live_rows above)
-            rc = xattn_core(Xu[un], Au, r_user, lu.W, lu.bW, lu.F1, lu.F2, lu.a, Xu[un ^ 1], nullptr, B, U, d, xws, st, lu.wsplit,
-                            rowidx, nrows_dev, live_flags, sparse_mode, sparse_flag, pq_x3,
-                            i > 0 ? ((p->flags & DIGAT_PQ_BF16) ? 1 : 0) | ((p->flags & DIGAT_PQ_X1) ? 2 : 0) | ((p->flags & DIGAT_PQ_FP8) ? 4 : 0) : 0,
-                            // after the last layer only the history rows are read (the user context's topic pooling, :124):
-                            // the topic nodes' own Eq. 8 is not computed there (wave-per-centre sparse kernel)
-                            (i > 0 && i == L - 1 && sparse_mode == DIGAT_XATTN_SPARSE) ? H : 0, fmt, rflag,
-                            (i > 0 && tw_pub.word) ? &tw_pub : nullptr);
+            XattnOpts o;
+            o.wsplit = lu.wsplit; o.rowidx = rowidx; o.nrows_dev = nrows_dev; o.live = live_flags;
+            o.sparse_mode = sparse_mode; o.sparse_flag = sparse_flag; o.pq_x3 = pq_x3; o.pq_mode = i > 0 ? pq_mode : 0;
+            // after the last layer only the history rows are read (the user context's topic pooling, :124):
+            // the topic nodes' own Eq. 8 is not computed there (wave-per-centre sparse kernel)
+            o.centre_limit = (i > 0 && i == L - 1 && sparse_mode == DIGAT_XATTN_SPARSE) ? H : 0;
+            o.gemm_format = fmt; o.range_flag = rflag;
+            o.tw = (i > 0 && tw_pub.word) ? &tw_pub : nullptr;
+            rc = xattn_core(w.Xu[un], Au, r_user, lu.W, lu.bW, lu.F1, lu.F2, lu.a, w.Xu[un ^ 1], nullptr, B, U, d, w.xws, w.xws_bytes, st, o);
         }
         if (rc) return rc;
         if (side && hipEventRecord(side->fork, st) != hipSuccess) return DIGAT_ERR_LAUNCH;      // this layer's user nodes are written
         // ---- news graph, Eq. 8 + context + the queries that follow from the new c_n (side stream)
         {
-            GemmArgs g3 = gemm_plain(c_u, d, ln.F3, ln.b3, r_news, d, B, d, d, 0);              // K3 of the news graph
+            GemmArgs g3 = gemm_plain(c_u, d, ln.F3, ln.b3, w.r_news, d, B, d, d, 0);              // K3 of the news graph
             g3.wsplit = (const unsigned short*)ln.f3_wsplit; g3.format = fmt; g3.range_flag = rflag;
             g3.m_dispatch = bd_disp;
             rc = launch_gemm(g3, sn);
         }
         if (rc) return rc;
         if (i == 0 && news_lists) {            // the live nodes of the news graphs, once per pass (the graphs do not change with the layers)
-            int* cnt_n = (int*)news_live_ws;
-            int* off_n = cnt_n + align_up((size_t)B, 64);
-            int* idx_n = off_n + align_up((size_t)B + 1, 64);
-            uint8_t* flags_n = (uint8_t*)(idx_n + align_up((size_t)B * N, 64));
+            int *cnt_n = w.cnt_n, *off_n = w.off_n, *idx_n = w.idx_n; uint8_t* flags_n = w.flags_n;
             ProfScope prof(DIGAT_KERNEL_GLUE, (double)B * ((double)N * N + 6.0 * N), sn);
             hipLaunchKernelGGL(news_live_flags_kernel, dim3((B + 3) / 4), dim3(256), (size_t)4 * ((N * N + 15) & ~15), sn, An, Mn, B, N, flags_n, cnt_n);
             DIGAT_CHECK_LAUNCH();
@@ -1122,38 +1208,38 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
         }
         if (news_early) {        // projections already done (news_project below): K3 joins in the score kernel
             const size_t ndn = (size_t)B * N * d;
-            const float* hn = (i == 0 && news_hpq0) ? news_hpq0 : (const float*)xws_news;
+            const float* hn = (i == 0 && news_hpq0) ? news_hpq0 : w.xn.h;
             // layer 0 with news_index: h | P | Q and the nodes themselves are the per-news TABLES, read in place through the index
-            const bool tab = i == 0 && news_hpq0 && news_index;
-            const size_t plane = tab ? (size_t)news_rows * N * d : ndn;
-            float* alpha_n = (float*)((char*)xws_news + align_up(3 * ndn * 4, 256) + align_up((size_t)B * d * 4, 256));
-            rc = launch_xattn_pairwise(hn + plane, hn + 2 * plane, hn, xn_cur, ln.a, An, Xn[nn], alpha_n, B, N, d, sn, nullptr, nullptr, r_news,
-                                       false, nullptr, tab ? news_index : nullptr);
-        } else if (i == 0 && news_hpq0 && news_index) {
+            const bool tab = i == 0 && news_hpq0 && c.news_index;
+            const size_t plane = tab ? (size_t)c.news_rows * N * d : ndn;
+            rc = launch_xattn_pairwise(hn + plane, hn + 2 * plane, hn, xn_cur, ln.a, An, w.Xn[nn], w.xn.alpha, B, N, d, sn, nullptr, nullptr,
+                                       w.r_news, false, nullptr, tab ? c.news_index : nullptr);
+        } else if (i == 0 && news_hpq0 && c.news_index) {
             // Larger news graphs, layer 0 from the per-news TABLES (round 4): [h | P | Q] of a news graph depend on the news alone, so
             // the projection GEMM of layer 0 (B N rows: at N = 26 the largest launch of a MIND-large step) is replaced by reading the
             // candidates' rows of the table IN PLACE — the sparse kernel's group indirection with the candidate id as the "group" —
             // and adding K3 in the kernel, in the GEMM epilogue's order (K3 + K1): the bits of the in-batch launch.
-            const size_t plane = (size_t)news_rows * N * d;
-            int* idx32 = (int*)((char*)chunk_ws + l0_chunk_bytes(B, U) - align_up((size_t)B * 4, 256));
-            hipLaunchKernelGGL(index_to_i32_kernel, dim3((B + 255) / 256), dim3(256), 0, sn, news_index, idx32, B);
+            const size_t plane = (size_t)c.news_rows * N * d;
+            hipLaunchKernelGGL(index_to_i32_kernel, dim3((B + 255) / 256), dim3(256), 0, sn, c.news_index, w.idx32, B);
             DIGAT_CHECK_LAUNCH();
-            SparseArgs sgn{news_hpq0 + plane, news_hpq0 + 2 * plane, news_hpq0, xn_cur, ln.a, An, Xn[nn], r_news, idx32, news_flags,
+            SparseArgs sgn{news_hpq0 + plane, news_hpq0 + 2 * plane, news_hpq0, xn_cur, ln.a, An, w.Xn[nn], w.r_news, w.idx32, news_flags,
                            nullptr, B, N, d / 4, 1, nullptr, nullptr, news_rowidx, news_nrows, B, nullptr, 0, 0};      // G (profiling: distinct rows behind the index): at most B candidates
             if (news_rowidx) sgn.prof_part = XPART_NEWS + 1;
             rc = launch_sparse(sgn, sn);
         } else {
             // larger news graphs (N = 26 / 65: the breadth-first SAG, a few entries per node) take the sparse kernel when the
             // caller says so (flags bit 3); there is no device-side decision for this graph
-            rc = xattn_core(xn_cur, An, r_news, ln.W, ln.bW, ln.F1, ln.F2, ln.a, Xn[nn], nullptr, B, N, d, xws_news, sn, ln.wsplit,
-                            news_rowidx, news_nrows, news_flags, (p->flags & DIGAT_NEWS_XATTN_SPARSE) ? DIGAT_XATTN_SPARSE : DIGAT_XATTN_DENSE,
-                            nullptr, pq_x3,
-                            // the news graph's P' always carries K3 from the GEMM epilogue: bf16 storage applies at every layer
-                            ((p->flags & DIGAT_PQ_BF16) ? 1 : 0) | ((p->flags & DIGAT_PQ_X1) ? 2 : 0) | ((p->flags & DIGAT_PQ_FP8) ? 4 : 0), 0, fmt, rflag,
-                            nullptr, news_rowidx ? XPART_NEWS + 1 : 0);
+            XattnOpts o;
+            o.wsplit = ln.wsplit; o.rowidx = news_rowidx; o.nrows_dev = news_nrows; o.live = news_flags;
+            o.sparse_mode = (p->flags & DIGAT_NEWS_XATTN_SPARSE) ? DIGAT_XATTN_SPARSE : DIGAT_XATTN_DENSE;
+            o.pq_x3 = pq_x3;
+            o.pq_mode = pq_mode;      // the news graph's P' always carries K3 from the GEMM epilogue: bf16 storage applies at every layer
+            o.gemm_format = fmt; o.range_flag = rflag;
+            o.prof_part = news_rowidx ? XPART_NEWS + 1 : 0;
+            rc = xattn_core(xn_cur, An, w.r_news, ln.W, ln.bW, ln.F1, ln.F2, ln.a, w.Xn[nn], nullptr, B, N, d, w.xws_news, w.xws_news_bytes, sn, o);
         }
         if (rc) return rc;
-        xn_cur = Xn[nn]; nn ^= 1; un ^= 1;
+        xn_cur = w.Xn[nn]; nn ^= 1; un ^= 1;
         rc = news_ctx(xn_cur, sn, i == 0);         // c_n += ... (:196)
         if (rc) return rc;
         rc = from_c_n(i + 1, sn);                  // queries (+ next K3, into the other r_user buffer) from the UPDATED c_n
@@ -1166,7 +1252,7 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
         // The user context of this layer feeds the next NEWS update and the result, not the next user-graph update: it runs
         // on the side stream once the caller's stream has written the user nodes, under the next layer's projection GEMM.
         if (side && hipStreamWaitEvent(sn, side->fork, 0) != hipSuccess) return DIGAT_ERR_LAUNCH;
-        rc = user_ctx_tail(Xu[un], c_u, sn, nullptr, live_flags);       // c_u += ... (:197)
+        rc = user_ctx_tail(w.Xu[un], c_u, sn, nullptr, live_flags);       // c_u += ... (:197)
         if (rc) return rc;
     }
     if (side && L > 0) {
@@ -1176,102 +1262,64 @@ static int encoder_fwd_folded(const digat_params* p, const float* Xn_in, const u
     return DIGAT_OK;
 }
 
-// layer 0 of grouped rows (xattn_sparse_l0_kernel): group starts [B + 64] int, rows led by each row [B] bytes, offsets [B + 64] int
-// and list [B U] int of the live centres of the chunk-leading rows
-// + twins (xattn_sparse_twin_kernel): twin words [B U] u32, lead flags [B U] bytes, leads per row [B + 64] int, offsets [B + 64] int, list [B U] int
-// + [B] int: the candidate ids as 32-bit indices (layer 0 of larger news graphs from the per-news tables)
-// + shared-user runs (digat_encoder_fwd_shared): offsets [B + 64] int and list [B U] int of the live nodes of the run-leading rows
-static size_t l0_chunk_bytes(int B, int U) {
-    return 2 * align_up((size_t)(B + 64) * 4, 256) + align_up((size_t)B, 256) + align_up((size_t)B * U * 4, 256)
-           + 2 * align_up((size_t)B * U * 4, 256) + align_up((size_t)B * U, 256) + 2 * align_up((size_t)(B + 64) * 4, 256)
-           + align_up((size_t)(B + 64) * 4, 256) + align_up((size_t)B * U * 4, 256)
-           + align_up((size_t)B * 4, 256);
-}
+size_t digat_encoder_workspace_bytes(int B, int N, int H, int C, int d, int depth) { (void)depth; return encoder_ws_bytes(B, N, H, C, d, ENC_PLAIN); }
 
-size_t digat_encoder_workspace_bytes(int B, int N, int H, int C, int d, int depth) {
-    (void)depth;
-    const int U = H + C;
-    const int nmax = N > U ? N : U;
-    size_t tot = 0;
-    tot += 2 * align_up((size_t)B * U * d * 4, 256);     // user nodes, ping-pong
-    tot += 2 * align_up((size_t)B * N * d * 4, 256);     // news nodes, ping-pong
-    tot += digat_xattn_workspace_bytes(B, nmax, d);
-    tot += max_sz(digat_news_ctx_workspace_bytes(B, N, d), digat_user_ctx_workspace_bytes(B, U, H, C + 1, d));
-    tot += 5 * align_up((size_t)B * d * 4, 256);         // folded path: kq_topic, kq_user, r_user x2, r_news
-    tot += digat_xattn_workspace_bytes(B, N, d);         // the news graph's own Eq. 8 workspace (side stream)
-    // live-node and live-bucket counts, offsets, lists (int) and flags (bytes)
-    // + adjacency entries per row and the sparse / dense decision (int)
-    tot += align_up((4 * align_up((size_t)B, 64) + 2 * align_up((size_t)B + 1, 64) + align_up((size_t)B * U, 64)
-                     + align_up((size_t)B * (C + 1), 64) + 64) * 4 + align_up((size_t)B * U, 256) + align_up((size_t)B * (C + 1), 256), 256);
-    tot += news_live_bytes(B, N);                         // larger news graphs on the sparse kernel: live-node flags, counts, offsets, list
-    tot += l0_chunk_bytes(B, U);                          // layer 0 of grouped rows: group starts + rows led by each row (xattn_sparse_l0_kernel)
-    return tot;
-}
-
-// row_group == NULL: user tensors are per row.  Otherwise they are per group (G of them) and row_group[b]
-// names the group of row b; the caller (digat_encoder_fwd_grouped) has expanded the small per-row byte /
-// index arrays, so Au / cat_mask / cat_idx are per row in both cases and only ue [G,H,d] is per group.
-static int encoder_fwd_impl(const digat_params* p, const float* Xn_in, const uint8_t* An, const uint8_t* Mn,
-                            const float* ue, const uint8_t* Au, const uint8_t* cat_mask, const int64_t* cat_idx,
-                            const float* c_n0, float* out_news, float* out_user, int B, int N, int H,
-                            void* workspace, size_t workspace_bytes, void* stream, const int* row_group, int G,
-                            const float* news_hpq0 = nullptr, const float* hist_hpq0 = nullptr, const float* topic_hpq0 = nullptr,
-                            const uint8_t* Au_g = nullptr, const uint8_t* cm_g = nullptr, const int64_t* ci_g = nullptr,
-                            const float* ctxq0 = nullptr, const int64_t* news_index = nullptr, int64_t news_rows = 0,
-                            void* live_g_ws = nullptr, const uint8_t* run_leader = nullptr, const uint8_t* run_lead = nullptr) {
-    if (!p || !Xn_in || !An || !Mn || !ue || !Au || !cat_mask || !cat_idx || !out_news || !out_user || !workspace)
-        return DIGAT_ERR_ARG;
+// Every entry: the checks, the carve and (grouped / shared entries) the per-row user arrays of the variant, then the unfolded
+// path or encoder_fwd_folded.  ENC_GROUPED: the user tensors are per group (G of them) and row_group[b] names the group of
+// row b; the small per-row byte / index arrays are expanded here, so Au / cat_mask / cat_idx are per row in every variant and
+// only ue [G,H,d] stays per group.
+static int encoder_fwd_impl(EncoderCall& c) {
+    const digat_params* p = c.p;
+    const bool grouped = c.variant == ENC_GROUPED;
+    if (!p || !c.Xn_in || !c.An || !c.Mn || !c.ue || !c.out_news || !c.out_user || !c.workspace) return DIGAT_ERR_ARG;
+    if (grouped ? (!c.Au_g || !c.cm_g || !c.ci_g || !c.row_group || c.G <= 0) : (!c.Au || !c.cat_mask || !c.cat_idx)) return DIGAT_ERR_ARG;
+    const int B = c.B, N = c.N, H = c.H;
     if (B < 0 || N <= 0 || H < 0) return DIGAT_ERR_ARG;
     const int d = p->d, C = p->category_num, L = p->depth, U = H + C;
+    const bool folded = p->cand_fold_W && p->user_news_fold_W && p->userAtt_fold_W;
+    if (grouped && !folded) return DIGAT_ERR_ARG;                              // grouped = folded path
     if (d <= 0 || d % 4 || L < 0 || L > DIGAT_MAX_DEPTH || N > DIGAT_MAX_NODES || U > DIGAT_MAX_NODES || C < 0)
         return DIGAT_ERR_SHAPE;
-    if (workspace_bytes < digat_encoder_workspace_bytes(B, N, H, C, d, L)) return DIGAT_ERR_WORKSPACE;
+    if (grouped && (size_t)4 * c.G > (size_t)B) return DIGAT_ERR_SHAPE;        // the group-level projections reuse one [B,U,d] buffer
+    Arena ar(c.workspace, c.workspace_bytes);
+    if (!encoder_carve(ar, B, N, H, C, d, c.variant, c.ws)) return DIGAT_ERR_WORKSPACE;
     if (B == 0) return DIGAT_OK;
     // per-news tables read in place: only where layer 0 of the news graph is the one reader of the node table (given c_n0,
     // cached projections, the small-graph kernel)
     // ... or, for larger news graphs (round 4), the sparse Eq. 8 kernel through the candidate ids (flags: DIGAT_NEWS_XATTN_SPARSE)
-    if (news_index && !(c_n0 && news_hpq0 && L > 0 && d / 4 <= 256 && news_rows > 0 && news_rows <= 0x7fffffffLL &&
-                        (N <= 16 || ((p->flags & DIGAT_NEWS_XATTN_SPARSE) && N <= DIGAT_MAX_NODES)) &&
-                        p->cand_fold_W && p->user_news_fold_W && p->userAtt_fold_W)) return DIGAT_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-
-    char* ws = (char*)workspace;
-    const size_t su = align_up((size_t)B * U * d * 4, 256), sn = align_up((size_t)B * N * d * 4, 256);
-    float* Xu[2] = {(float*)ws, (float*)(ws + su)};
-    ws += 2 * su;
-    float* Xn[2] = {(float*)ws, (float*)(ws + sn)};
-    ws += 2 * sn;
-    const int nmax = N > U ? N : U;
-    void* xws = ws;
-    const size_t xws_bytes = digat_xattn_workspace_bytes(B, nmax, d);
-    ws += xws_bytes;
-    void* cws = ws;
-    const size_t cws_bytes = max_sz(digat_news_ctx_workspace_bytes(B, N, d), digat_user_ctx_workspace_bytes(B, U, H, C + 1, d));
-    ws += cws_bytes;
-    const size_t sb = align_up((size_t)B * d * 4, 256);
-    float* kq_t = (float*)ws;
-    float* kq_u = (float*)(ws + sb);
-    float* r_user = (float*)(ws + 2 * sb);
-    float* r_news = (float*)(ws + 3 * sb);
-    float* const r_user2[2] = {r_user, (float*)(ws + 4 * sb)};
-    void* xws_news = ws + 5 * sb;
-    int* live_ws = (int*)((char*)xws_news + digat_xattn_workspace_bytes(B, N, d));
-    void* chunk_ws = (char*)workspace + digat_encoder_workspace_bytes(B, N, H, C, d, L) - l0_chunk_bytes(B, U);
-    void* news_live_ws = (char*)chunk_ws - news_live_bytes(B, N);
-
+    if (c.news_index && !(c.c_n0 && c.news_hpq0 && L > 0 && d / 4 <= 256 && c.news_rows > 0 && c.news_rows <= 0x7fffffffLL &&
+                          (N <= 16 || ((p->flags & DIGAT_NEWS_XATTN_SPARSE) && N <= DIGAT_MAX_NODES)) && folded)) return DIGAT_ERR_ARG;
+    hipStream_t st = c.st;
+    const EncoderWs& w = c.ws;
     int rc;
-    const bool folded = p->cand_fold_W && p->user_news_fold_W && p->userAtt_fold_W;
+    if (grouped) {
+        // expand the small per-user byte / index arrays to rows (4.6 MB for 1024 rows of 67x67 adjacency)
+        const GatherJobs jobs{{c.Au_g, c.cm_g, (const uint8_t*)c.ci_g}, {w.Au, w.cm, (uint8_t*)w.ci}, {(long)U * U, (long)(C + 1), (long)H * 8}};
+        hipLaunchKernelGGL(gather_rows_kernel, dim3(B), dim3(256), 0, st, jobs, c.row_group, (long)B);
+        DIGAT_CHECK_LAUNCH();
+        c.Au = w.Au; c.cat_mask = w.cm; c.cat_idx = w.ci;
+    } else if (c.variant == ENC_SHARED) {
+        // consecutive rows with identical users: runs found on the device (user_rows_same_kernel, shared_runs_kernel)
+        ProfScope prof(DIGAT_KERNEL_GLUE, (double)B * ((double)H * d * 4 + (double)U * U + (C + 1) + 8.0 * H), st);
+        hipLaunchKernelGGL(user_rows_same_kernel, dim3(B), dim3(256), 0, st, (const uint4*)c.ue, c.Au, c.cat_mask, c.cat_idx, B, (long)H * d / 4, U * U,
+                           C + 1, H, w.same);
+        DIGAT_CHECK_LAUNCH();
+        hipLaunchKernelGGL(shared_runs_kernel, dim3(1), dim3(1024), 0, st, (const uint8_t*)w.same, B, SPARSE_L0_ROWS, w.leader_of, w.is_leader, w.lead);
+        DIGAT_CHECK_LAUNCH();
+        c.row_group = w.leader_of; c.run_leader = w.is_leader; c.run_lead = w.lead;
+    }
     // Rows of one impression share the user nodes.  When every reader of the layer-0 nodes can go through the group index
     // (the sparse Eq. 8 kernel and the topic pooling can; the dense tile / aggregation kernels cannot) they are built once
     // per GROUP: 3 MB instead of a 110 MB expansion that the first two kernels would read back.
     // Shared-user runs (digat_encoder_fwd_shared): ue is per ROW, row_group[b] = the row that leads row b's run.  Taken when the
     // group-indexed kernels of layer 0 apply (sparse Eq. 8 on the live lists); otherwise the runs are ignored: the plain per-row path.
-    const bool shared = run_leader && run_lead && row_group && folded && L > 0 && (p->flags & 3) == DIGAT_XATTN_SPARSE &&
+    const bool shared = c.run_leader && c.run_lead && c.row_group && folded && L > 0 && (p->flags & 3) == DIGAT_XATTN_SPARSE &&
                         !(p->flags & DIGAT_PARAMS_NO_LIVE_ROWS) && d / 4 <= 128 && U <= 128 && U > 16;
-    if ((run_leader || run_lead) && !shared) { row_group = nullptr; G = 0; run_leader = run_lead = nullptr; }
-    const bool xu0_grouped = !shared && folded && row_group && L > 0 && (p->flags & 3) == DIGAT_XATTN_SPARSE && d / 4 <= 256 && U > 16 && 3 * (long)G <= B;
+    if ((c.run_leader || c.run_lead) && !shared) { c.row_group = nullptr; c.G = 0; c.run_leader = c.run_lead = nullptr; }
+    const int G = c.G;
+    const bool xu0_grouped = !shared && folded && c.row_group && L > 0 && (p->flags & 3) == DIGAT_XATTN_SPARSE && d / 4 <= 256 && U > 16 && 3 * (long)G <= B;
     // user graph nodes = [history | topic nodes]  (:191)
-    float* const Xg0 = xu0_grouped ? (float*)xws + 2 * (size_t)G * U * d : nullptr;      // behind the groups' h and P in the h slot (3 G <= B)
+    float* const Xg0 = xu0_grouped ? w.xu.h + 2 * (size_t)G * U * d : nullptr;      // behind the groups' h and P in the h slot (3 G <= B)
     {
         const long nrows = xu0_grouped ? G : B;
         const long total4 = nrows * U * (d / 4);
@@ -1279,114 +1327,83 @@ static int encoder_fwd_impl(const digat_params* p, const float* Xn_in, const uin
         if (blocks > 2048) blocks = 2048;
         ProfScope prof(DIGAT_KERNEL_GLUE, (double)nrows * ((double)H * d * 8 + (double)C * d * 4), st);
         // shared runs: ue is per row already, and only the run-leading rows are ever read (through row_group)
-        hipLaunchKernelGGL(build_user_nodes_kernel, dim3(blocks), dim3(256), 0, st, (const float4*)ue,
-                           (const float4*)p->topic_node_embedding, (float4*)(xu0_grouped ? Xg0 : Xu[0]), nrows, H, C, d / 4,
-                           (xu0_grouped || shared) ? (const int*)nullptr : row_group, shared ? run_leader : (const uint8_t*)nullptr);
+        hipLaunchKernelGGL(build_user_nodes_kernel, dim3(blocks), dim3(256), 0, st, (const float4*)c.ue,
+                           (const float4*)p->topic_node_embedding, (float4*)(xu0_grouped ? Xg0 : w.Xu[0]), nrows, H, C, d / 4,
+                           (xu0_grouped || shared) ? (const int*)nullptr : c.row_group, shared ? c.run_leader : (const uint8_t*)nullptr);
         DIGAT_CHECK_LAUNCH();
     }
     // c_n: given (inference, :189) or computed (forward, :180); it lives in out_news from here on
-    const bool c_n0_in_place = c_n0 && folded && L > 0;        // layer 0's news context update writes out_news from c_n0 directly
+    const bool c_n0_in_place = c.c_n0 && folded && L > 0;        // layer 0's news context update writes out_news from c_n0 directly
     if (c_n0_in_place) {
-    } else if (c_n0) {
-        if (hipMemcpyAsync(out_news, c_n0, (size_t)B * d * 4, hipMemcpyDeviceToDevice, st) != hipSuccess)
+    } else if (c.c_n0) {
+        if (hipMemcpyAsync(c.out_news, c.c_n0, (size_t)B * d * 4, hipMemcpyDeviceToDevice, st) != hipSuccess)
             return DIGAT_ERR_LAUNCH;
     } else {
-        rc = digat_news_ctx_fwd(Xn_in, Mn, p->cand_K, p->cand_Q, p->cand_bQ, p->news_graph_W, p->news_graph_b,
-                                nullptr, out_news, B, N, d, cws, cws_bytes, stream);
+        rc = digat_news_ctx_fwd(c.Xn_in, c.Mn, p->cand_K, p->cand_Q, p->cand_bQ, p->news_graph_W, p->news_graph_b,
+                                nullptr, c.out_news, B, N, d, w.cws, w.cws_bytes, st);
         if (rc) return rc;
     }
-    if (folded)
-        return encoder_fwd_folded(p, Xn_in, An, Mn, Au, cat_mask, cat_idx, out_news, out_user, B, N, H, Xu, Xn, xws,
-                                  xws_news, cws, kq_t, kq_u, r_user2, r_news, live_ws, st, row_group, G, ue, Xg0, news_hpq0, hist_hpq0, topic_hpq0, chunk_ws, Au_g, cm_g, ci_g,
-                                  c_n0 ? ctxq0 : nullptr, news_index, news_rows, c_n0_in_place ? c_n0 : out_news, live_g_ws,
-                                  run_leader, run_lead, news_live_ws);
+    if (folded) {
+        if (!c.c_n0) c.ctxq0 = nullptr;          // the queries belong to a given news context
+        return encoder_fwd_folded(c, Xg0);
+    }
     // c_u (:192)
-    rc = digat_user_ctx_fwd(Xu[0], cat_mask, cat_idx, out_news, p->user_news_K, p->user_news_Q, p->user_news_bQ,
+    rc = digat_user_ctx_fwd(w.Xu[0], c.cat_mask, c.cat_idx, c.out_news, p->user_news_K, p->user_news_Q, p->user_news_bQ,
                             p->featureAffine_W, p->featureAffine_b, p->userAtt_K, p->userAtt_Q, p->userAtt_bQ,
-                            nullptr, out_user, B, U, H, C + 1, d, cws, cws_bytes, stream);
+                            nullptr, c.out_user, B, U, H, C + 1, d, w.cws, w.cws_bytes, st);
     if (rc) return rc;
 
-    const float* xn_cur = Xn_in;
+    const float* xn_cur = c.Xn_in;
     int un = 0, nn = 0;
+    XattnOpts o;
+    o.gemm_format = (p->flags & DIGAT_PARAMS_GEMM_F16X3) ? 1 : 0;
+    o.range_flag = o.gemm_format ? (unsigned*)p->range_flag : nullptr;
     for (int i = 0; i < L; ++i) {
         const digat_layer_params& ln = p->news[i];
         const digat_layer_params& lu = p->user[i];
         // both graph updates read the PREVIOUS contexts (:194-195)
-        rc = launch_gemm(gemm_plain(out_user, d, ln.F3, ln.b3, r_news, d, B, d, d, 0), st);
+        rc = launch_gemm(gemm_plain(c.out_user, d, ln.F3, ln.b3, w.r_news, d, B, d, d, 0), st);
         if (rc) return rc;
-        const int fmt = (p->flags & DIGAT_PARAMS_GEMM_F16X3) ? 1 : 0;
-        unsigned* const rflag = fmt ? (unsigned*)p->range_flag : nullptr;
-        rc = xattn_core(xn_cur, An, r_news, ln.W, ln.bW, ln.F1, ln.F2, ln.a, Xn[nn], nullptr, B, N, d, xws, st, ln.wsplit,
-                        nullptr, nullptr, nullptr, DIGAT_XATTN_DENSE, nullptr, 0, 0, 0, fmt, rflag);
+        o.wsplit = ln.wsplit;
+        rc = xattn_core(xn_cur, c.An, w.r_news, ln.W, ln.bW, ln.F1, ln.F2, ln.a, w.Xn[nn], nullptr, B, N, d, w.xws, w.xws_bytes, st, o);
         if (rc) return rc;
-        rc = launch_gemm(gemm_plain(out_news, d, lu.F3, lu.b3, r_user, d, B, d, d, 0), st);
+        rc = launch_gemm(gemm_plain(c.out_news, d, lu.F3, lu.b3, w.r_user[0], d, B, d, d, 0), st);
         if (rc) return rc;
-        rc = xattn_core(Xu[un], Au, r_user, lu.W, lu.bW, lu.F1, lu.F2, lu.a, Xu[un ^ 1], nullptr, B, U, d, xws, st, lu.wsplit,
-                        nullptr, nullptr, nullptr, DIGAT_XATTN_DENSE, nullptr, 0, 0, 0, fmt, rflag);
+        o.wsplit = lu.wsplit;
+        rc = xattn_core(w.Xu[un], c.Au, w.r_user[0], lu.W, lu.bW, lu.F1, lu.F2, lu.a, w.Xu[un ^ 1], nullptr, B, U, d, w.xws, w.xws_bytes, st, o);
         if (rc) return rc;
-        xn_cur = Xn[nn]; nn ^= 1; un ^= 1;
+        xn_cur = w.Xn[nn]; nn ^= 1; un ^= 1;
         // c_n += news context (:196); c_u += user context with the UPDATED c_n (:197)
-        rc = digat_news_ctx_fwd(xn_cur, Mn, p->cand_K, p->cand_Q, p->cand_bQ, p->news_graph_W, p->news_graph_b,
-                                out_news, out_news, B, N, d, cws, cws_bytes, stream);
+        rc = digat_news_ctx_fwd(xn_cur, c.Mn, p->cand_K, p->cand_Q, p->cand_bQ, p->news_graph_W, p->news_graph_b,
+                                c.out_news, c.out_news, B, N, d, w.cws, w.cws_bytes, st);
         if (rc) return rc;
-        rc = digat_user_ctx_fwd(Xu[un], cat_mask, cat_idx, out_news, p->user_news_K, p->user_news_Q, p->user_news_bQ,
+        rc = digat_user_ctx_fwd(w.Xu[un], c.cat_mask, c.cat_idx, c.out_news, p->user_news_K, p->user_news_Q, p->user_news_bQ,
                                 p->featureAffine_W, p->featureAffine_b, p->userAtt_K, p->userAtt_Q, p->userAtt_bQ,
-                                out_user, out_user, B, U, H, C + 1, d, cws, cws_bytes, stream);
+                                c.out_user, c.out_user, B, U, H, C + 1, d, w.cws, w.cws_bytes, st);
         if (rc) return rc;
     }
     return DIGAT_OK;
 }
 
-
 int digat_encoder_fwd(const digat_params* p, const float* Xn_in, const uint8_t* An, const uint8_t* Mn,
                       const float* ue, const uint8_t* Au, const uint8_t* cat_mask, const int64_t* cat_idx,
                       const float* c_n0, float* out_news, float* out_user, int B, int N, int H,
                       void* workspace, size_t workspace_bytes, void* stream) {
-    return encoder_fwd_impl(p, Xn_in, An, Mn, ue, Au, cat_mask, cat_idx, c_n0, out_news, out_user, B, N, H, workspace,
-                            workspace_bytes, stream, nullptr, 0);
+    EncoderCall c{};
+    c.variant = ENC_PLAIN; c.p = p; c.Xn_in = Xn_in; c.An = An; c.Mn = Mn; c.ue = ue; c.Au = Au; c.cat_mask = cat_mask; c.cat_idx = cat_idx;
+    c.c_n0 = c_n0; c.out_news = out_news; c.out_user = out_user; c.B = B; c.N = N; c.H = H;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.st = (hipStream_t)stream;
+    return encoder_fwd_impl(c);
 }
 
-size_t digat_encoder_grouped_workspace_bytes(int B, int N, int H, int C, int d, int depth) {
-    const int U = H + C;
-    return digat_encoder_workspace_bytes(B, N, H, C, d, depth) + align_up((size_t)B * U * U, 256)
-           + align_up((size_t)B * (C + 1), 256) + align_up((size_t)B * H * 8, 256) + live_group_bytes(B, U, C + 1);
-}
-
-static int encoder_fwd_grouped_impl(const digat_params* p, const float* Xn_in, const uint8_t* An, const uint8_t* Mn,
-                                    const float* ue_g, const uint8_t* Au_g, const uint8_t* cat_mask_g, const int64_t* cat_idx_g,
-                                    const int32_t* row_group, const float* c_n0, float* out_news, float* out_user,
-                                    int B, int G, int N, int H, void* workspace, size_t workspace_bytes, void* stream,
-                                    const float* news_hpq0, const float* hist_hpq0 = nullptr, const float* topic_hpq0 = nullptr,
-                                    const float* ctxq0 = nullptr, const int64_t* news_index = nullptr, int64_t news_rows = 0) {
-    if (!p || !ue_g || !Au_g || !cat_mask_g || !cat_idx_g || !row_group || !workspace || G <= 0) return DIGAT_ERR_ARG;
-    const int d = p->d, C = p->category_num, U = H + C;
-    if (!p->cand_fold_W || !p->user_news_fold_W || !p->userAtt_fold_W) return DIGAT_ERR_ARG;   // grouped = folded path
-    if ((size_t)4 * G > (size_t)B) return DIGAT_ERR_SHAPE;       // the group-level projections reuse one [B,U,d] buffer
-    if (workspace_bytes < digat_encoder_grouped_workspace_bytes(B, N, H, C, d, p->depth)) return DIGAT_ERR_WORKSPACE;
-    if (B == 0) return DIGAT_OK;
-    hipStream_t st = (hipStream_t)stream;
-    // expand the small per-user byte / index arrays to rows (4.6 MB for 1024 rows of 67x67 adjacency)
-    const size_t base = digat_encoder_workspace_bytes(B, N, H, C, d, p->depth);
-    uint8_t* Au = (uint8_t*)workspace + base;
-    uint8_t* cm = Au + align_up((size_t)B * U * U, 256);
-    uint8_t* ci = cm + align_up((size_t)B * (C + 1), 256);
-    {
-        const GatherJobs jobs{{Au_g, cat_mask_g, (const uint8_t*)cat_idx_g}, {Au, cm, ci}, {(long)U * U, (long)(C + 1), (long)H * 8}};
-        hipLaunchKernelGGL(gather_rows_kernel, dim3(B), dim3(256), 0, st, jobs, row_group, (long)B);
-        DIGAT_CHECK_LAUNCH();
-    }
-    void* live_g_ws = ci + align_up((size_t)B * H * 8, 256);
-    return encoder_fwd_impl(p, Xn_in, An, Mn, ue_g, Au, cm, (const int64_t*)ci, c_n0, out_news, out_user, B, N, H, workspace,
-                            base, stream, row_group, G, news_hpq0, hist_hpq0, topic_hpq0, Au_g, cat_mask_g, cat_idx_g, ctxq0, news_index, news_rows,
-                            live_g_ws);
-}
+size_t digat_encoder_grouped_workspace_bytes(int B, int N, int H, int C, int d, int depth) { (void)depth; return encoder_ws_bytes(B, N, H, C, d, ENC_GROUPED); }
 
 int digat_encoder_fwd_grouped(const digat_params* p, const float* Xn_in, const uint8_t* An, const uint8_t* Mn,
                               const float* ue_g, const uint8_t* Au_g, const uint8_t* cat_mask_g, const int64_t* cat_idx_g,
                               const int32_t* row_group, const float* c_n0, float* out_news, float* out_user,
                               int B, int G, int N, int H, void* workspace, size_t workspace_bytes, void* stream) {
-    return encoder_fwd_grouped_impl(p, Xn_in, An, Mn, ue_g, Au_g, cat_mask_g, cat_idx_g, row_group, c_n0, out_news, out_user, B, G, N, H,
-                                    workspace, workspace_bytes, stream, nullptr);
+    return digat_encoder_fwd_grouped_cached(p, Xn_in, An, Mn, ue_g, Au_g, cat_mask_g, cat_idx_g, row_group, c_n0, nullptr, nullptr, nullptr,
+                                            nullptr, nullptr, 0, out_news, out_user, B, G, N, H, workspace, workspace_bytes, stream);
 }
 
 int digat_encoder_fwd_grouped_cached(const digat_params* p, const float* Xn_in, const uint8_t* An, const uint8_t* Mn,
@@ -1398,41 +1415,25 @@ int digat_encoder_fwd_grouped_cached(const digat_params* p, const float* Xn_in, 
                                      void* stream) {
     if ((hist_hpq0 == nullptr) != (topic_hpq0 == nullptr)) return DIGAT_ERR_ARG;
     if (ctxq0 && !c_n0) return DIGAT_ERR_ARG;           // the queries belong to a given news context
-    return encoder_fwd_grouped_impl(p, Xn_in, An, Mn, ue_g, Au_g, cat_mask_g, cat_idx_g, row_group, c_n0, out_news, out_user, B, G, N, H,
-                                    workspace, workspace_bytes, stream, news_hpq0, hist_hpq0, topic_hpq0, ctxq0, news_index, news_rows);
+    EncoderCall c{};
+    c.variant = ENC_GROUPED; c.p = p; c.Xn_in = Xn_in; c.An = An; c.Mn = Mn; c.ue = ue_g; c.Au_g = Au_g; c.cm_g = cat_mask_g; c.ci_g = cat_idx_g;
+    c.row_group = row_group; c.G = G; c.c_n0 = c_n0; c.out_news = out_news; c.out_user = out_user; c.B = B; c.N = N; c.H = H;
+    c.news_hpq0 = news_hpq0; c.hist_hpq0 = hist_hpq0; c.topic_hpq0 = topic_hpq0; c.ctxq0 = ctxq0; c.news_index = news_index; c.news_rows = news_rows;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.st = (hipStream_t)stream;
+    return encoder_fwd_impl(c);
 }
 
 // ---- shared-user runs: the per-row signature of digat_encoder_fwd, the grouped arithmetic of layer 0 --------------------------
-size_t digat_encoder_shared_workspace_bytes(int B, int N, int H, int C, int d, int depth) {
-    // + same[B] bytes, leader_of[B] int, is_leader[B] bytes, lead[B] bytes
-    return digat_encoder_workspace_bytes(B, N, H, C, d, depth) + 3 * align_up((size_t)B, 256) + align_up((size_t)B * 4, 256);
-}
+size_t digat_encoder_shared_workspace_bytes(int B, int N, int H, int C, int d, int depth) { (void)depth; return encoder_ws_bytes(B, N, H, C, d, ENC_SHARED); }
 
 int digat_encoder_fwd_shared(const digat_params* p, const float* Xn_in, const uint8_t* An, const uint8_t* Mn, const float* ue,
                              const uint8_t* Au, const uint8_t* cat_mask, const int64_t* cat_idx, const float* c_n0, float* out_news,
                              float* out_user, int B, int N, int H, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!p || !ue || !Au || !cat_mask || !cat_idx || !workspace) return DIGAT_ERR_ARG;
-    if (B < 0 || N <= 0 || H < 0) return DIGAT_ERR_ARG;
-    const int d = p->d, C = p->category_num, U = H + C;
-    if (d <= 0 || d % 4 || C < 0) return DIGAT_ERR_SHAPE;
-    if (workspace_bytes < digat_encoder_shared_workspace_bytes(B, N, H, C, d, p->depth)) return DIGAT_ERR_WORKSPACE;
-    if (B == 0) return DIGAT_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t base = digat_encoder_workspace_bytes(B, N, H, C, d, p->depth);
-    uint8_t* same = (uint8_t*)workspace + base;
-    uint8_t* is_leader = same + align_up((size_t)B, 256);
-    uint8_t* lead = is_leader + align_up((size_t)B, 256);
-    int* leader_of = (int*)(lead + align_up((size_t)B, 256));
-    {
-        ProfScope prof(DIGAT_KERNEL_GLUE, (double)B * ((double)H * d * 4 + (double)U * U + (C + 1) + 8.0 * H), st);
-        hipLaunchKernelGGL(user_rows_same_kernel, dim3(B), dim3(256), 0, st, (const uint4*)ue, Au, cat_mask, cat_idx, B, (long)H * d / 4, U * U,
-                           C + 1, H, same);
-        DIGAT_CHECK_LAUNCH();
-        hipLaunchKernelGGL(shared_runs_kernel, dim3(1), dim3(1024), 0, st, (const uint8_t*)same, B, SPARSE_L0_ROWS, leader_of, is_leader, lead);
-        DIGAT_CHECK_LAUNCH();
-    }
-    return encoder_fwd_impl(p, Xn_in, An, Mn, ue, Au, cat_mask, cat_idx, c_n0, out_news, out_user, B, N, H, workspace, base, stream,
-                            leader_of, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, is_leader, lead);
+    EncoderCall c{};
+    c.variant = ENC_SHARED; c.p = p; c.Xn_in = Xn_in; c.An = An; c.Mn = Mn; c.ue = ue; c.Au = Au; c.cat_mask = cat_mask; c.cat_idx = cat_idx;
+    c.c_n0 = c_n0; c.out_news = out_news; c.out_user = out_user; c.B = B; c.N = N; c.H = H;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.st = (hipStream_t)stream;
+    return encoder_fwd_impl(c);
 }
 
 int digat_news_context_queries(const digat_params* p, const float* c_n, float* out, int M, void* stream) {

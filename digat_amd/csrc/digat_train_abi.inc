@@ -9,18 +9,6 @@
 // layout is private to this file); scratch comes from `workspace`.  Dropout uses the library's counter-hash generator
 // (digat_dropout_fwd) with the caller's seeds; p = 0 disables it.  All reductions are ordered: gradients are bit-reproducible.
 
-struct Arena {              // bump allocator over a caller buffer; `ok` turns false on overflow
-    char* base; size_t cap, used; bool ok;
-    Arena(void* p, size_t n) : base((char*)p), cap(n), used(0), ok(p != nullptr) {}
-    template <class T> T* take(size_t count) {
-        const size_t bytes = align_up(count * sizeof(T), 256);
-        if (!ok || used + bytes > cap) { ok = false; return nullptr; }
-        T* r = (T*)(base + used);
-        used += bytes;
-        return r;
-    }
-};
-
 static bool x3_ok(long M, int n_out, int k_in) { return M >= 2048 && n_out % 80 == 0 && k_in % 8 == 0 && k_in >= 32; }
 static size_t wsplit_scratch(int d) { return digat_split_weights_bytes(3 * d, 2 * d); }     // covers every split made here
 

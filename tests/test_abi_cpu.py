@@ -58,6 +58,25 @@ def test_workspace_queries():
     e = L.digat_encoder_workspace_bytes(B, N, H, C, d, depth)
     assert e >= 2 * B * U * d * 4 + 2 * B * N * d * 4 + x
     assert e < 2 << 30          # far below the 288 GB of one MI355X
+    # The byte counts are ABI (Python and the torch extension size their buffers with them): pinned per shape as
+    # (encoder, encoder grouped, encoder shared, xattn at n = U, xattn at n = N, news context, user context), depth 3.
+    pinned = {
+        (1024, 10, 50, 17, 400): (725021952, 730161920, 725029120, 349343744, 51200000, 4915200, 62259200),
+        (4096, 10, 50, 17, 400): (2900080896, 2920633088, 2900109568, 1397374976, 204800000, 19660800, 249036800),
+        (1000, 10, 50, 17, 400): (708031232, 713049600, 708038400, 341156096, 50000128, 4800000, 60800000),
+        (1024, 26, 50, 17, 400): (858535168, 863675136, 858542336, 349343744, 132202496, 4915200, 62259200),
+        (1024, 65, 50, 17, 400): (1192759552, 1197899520, 1192766720, 349343744, 338432000, 4915200, 62259200),
+        (1024, 10, 50, 17, 64): (133231872, 138371840, 133239040, 71340032, 8536064, 786432, 9961472),
+        (1, 10, 50, 17, 400): (718848, 726784, 719872, 341760, 50432, 5376, 61440),
+        (256, 65, 30, 17, 80): (63025920, 63679744, 63027712, 13894656, 20382720, 245760, 3112960),      # N > U
+    }
+    for (B, N, H, C, d), want in pinned.items():
+        U = H + C
+        got = (L.digat_encoder_workspace_bytes(B, N, H, C, d, depth), L.digat_encoder_grouped_workspace_bytes(B, N, H, C, d, depth),
+               L.digat_encoder_shared_workspace_bytes(B, N, H, C, d, depth), L.digat_xattn_workspace_bytes(B, U, d),
+               L.digat_xattn_workspace_bytes(B, N, d), L.digat_news_ctx_workspace_bytes(B, N, d),
+               L.digat_user_ctx_workspace_bytes(B, U, H, C + 1, d))
+        assert got == want, (B, N, H, C, d)
 
 
 def test_struct_layout_matches_header():
