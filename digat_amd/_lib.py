@@ -18,11 +18,13 @@ LIB_PATH = os.environ.get("DIGAT_HIP_LIB") or os.path.join(_HERE, "lib", "libdig
 DIGAT_MAX_DEPTH = 16
 DIGAT_MAX_NODES = 128
 GEMM_BF16X6, GEMM_F16X3 = 0, 1          # operand format of a split weight image (include/digat_hip.h)
+GEMM_F16F8C = 2                         # ... fp16 leading product + MX-e4m3 corrections (layer projections only)
 PARAMS_GEMM_F16X3 = 64                  # digat_params.flags: the block's wsplit images are GEMM_F16X3
 PARAMS_BD_TILED = 128                   # digat_params.flags: the [B,d] linears run on the tiled kernel at every row count
 PARAMS_PQ_FP8 = 256                     # digat_params.flags: P', Q of Eq. 8 stored as block-scaled e4m3 (DIGAT_PQ_FP8)
 PARAMS_SIDE_STREAM_OFF, PARAMS_SIDE_STREAM_ON = 512, 1024      # digat_params.flags: never / always (neither: by pass size)
 PARAMS_NO_LIVE_ROWS = 2048              # digat_params.flags: project every user-graph node in every layer
+PARAMS_PROJ_F16F8C = 4096               # digat_params.flags: the layers' [W|ffn1|ffn2] images are GEMM_F16F8C
 
 _f = C.c_void_p  # every device pointer crosses as void*
 
@@ -123,6 +125,7 @@ _SIGNATURES = {
     "digat_user_project0": (C.c_int, [C.POINTER(Params), _f, _f, C.c_int, _f]),
     "digat_news_project0": (C.c_int, [C.POINTER(Params), _f, _f, C.c_int, C.c_int, _f]),
     "digat_split_weights_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "digat_split_weights_bytes_format": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "digat_forget_split_image": (C.c_int, [_f]),
     "digat_split_proj_weights": (C.c_int, [_f, _f, _f, C.c_int, _f, C.c_int, _f]),
     "digat_split_weights": (C.c_int, [_f, C.c_int, C.c_int, _f, C.c_int, _f]),

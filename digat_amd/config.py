@@ -46,6 +46,9 @@ class Config:
         p.add_argument('--synthetic_news', type=int, default=8192)
         p.add_argument('--synthetic_impressions', type=int, default=2048)
         p.add_argument('--max_steps', type=int, default=0, help='stop training after this many steps (0 = all epochs)')
+        p.add_argument('--inference_projection', default='auto',
+                       choices=['auto', 'bf16x6', 'bf16x6-pq3', 'fp32', 'fp16x3', 'fp16-fp8c', 'pq-bf16', 'pq-bf16-x1', 'pq-fp8'],
+                       help="the graph encoder's projection_mode for dev / test scoring (fp16-fp8c: fp16 + fp8 matrix-core corrections)")
         a = p.parse_args(argv)
         self.attribute_dict = dict(vars(a))
         for k, v in self.attribute_dict.items():

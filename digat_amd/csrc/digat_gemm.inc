@@ -1214,6 +1214,355 @@ __global__ void __launch_bounds__(256) gemm_skinny_split_kernel(const GemmArgs g
     }
 }
 
+// =================================================================================================
+// 1e. "fp16-fp8c": the Eq. 8 node projections with the two correction products on the fp8 matrix cores
+// =================================================================================================
+// fp16x3 (above) computes x.w as x_hi w_hi + x_hi w_lo + x_lo w_hi, all three on v_mfma_f32_16x16x32_f16.  The two corrections
+// are each ~2^-11 of the result, so they can carry e4m3's 2^-4 relative step and still land at ~2^-15 of it: here they run on
+// the block-scaled v_mfma_scale_f32_16x16x128_f8f6f4 as q(w_lo) q(x_hi) + q(w_hi) q(x_lo), q = OCP e4m3 with one E8M0 (power of
+// two) scale per 32 consecutive K values — the instruction's own MX block — chosen so that the block's largest magnitude maps to
+// at most 448 (no saturation).  x_hi w_hi stays on fp16, exactly as fp16x3 makes it (same 2^10 / 2^4 scaling, same pieces:
+// w_hi rounded to nearest, x_hi truncated; the corrections quantise the fp32 remainders w - w_hi, x - x_hi directly).
+//
+// Operand layout of the 16x16x128 form, measured on gfx950 with exact data (NOT one 32-deep block per lane): lane l (row /
+// column l & 15, group g = l >> 4) holds K 16 g .. 16 g + 15 in bytes 0-15 and K 64 + 16 g .. + 15 in bytes 16-31, and the scale
+// of MX block b (K 32 b .. 32 b + 31) is read from the scale VGPR of lane group b (byte chosen by op_sel).  A block's 32 values
+// therefore sit in two lanes (g, g ^ 1): a block scale costs one lane exchange (l ^ 16), and handing each lane group its
+// block's scale one more (l ^ 48: groups 1 and 2 supply the blocks of the other pair).
+// The fp16 product's four 32-deep k-steps are fed the same 32 K values per lane, in a PERMUTED k order — value v of a lane
+// (v < 16: K 16 g + v, else K 64 + 16 g + v - 16) is element v % 8 of k-step v / 8, for both operands, so the sum is unchanged —
+// so the activation split is lane-local but for the two exchanges of the scales.
+//
+// Image of one (80-column strip, 128-deep K tile), K zero-padded to a multiple of 128 (F8C_IMG_BYTES = 41 984 bytes, 41 DMA pieces):
+//   slots    0 .. 1279: w_hi fp16,       [s 4][k group 4][row 80] x 8 halves   (values 8 s .. 8 s + 7 of lane (group, row))
+//   slots 1280 .. 1919: q(w_hi) e4m3,    [half 2][k group 4][row 80] x 16 bytes (K 64 half + 16 group + j)
+//   slots 1920 .. 2559: q(w_lo) e4m3,    same
+//   bytes 40960 .. 41983: E8M0 scales,   [plane 2][block 4][row & 15][row >> 4, padded to 8] bytes
+// Every fragment read is a 16-byte slot on consecutive slots for consecutive lanes (the shipped kernel's conflict-free pattern),
+// and a lane's scales for the five 16-column blocks of a strip are one 8-byte read per plane (byte = block, picked by op_sel).
+constexpr int F8C_IMG_BYTES = 41984;
+constexpr int F8C_PIECES = F8C_IMG_BYTES / 1024;
+typedef int v8i __attribute__((ext_vector_type(8)));
+
+// E8M0 exponent (biased) of the block scale of a block whose largest magnitude is amax: the least power of two 2^(x - 127) with
+// amax / 2^(x - 127) <= 448 (e4m3's largest finite value: 1.75 x 2^8); amax = 0 gives x = 0 (any scale would do)
+__device__ __forceinline__ int f8c_e8m0(float amax) {
+    const unsigned u = __builtin_bit_cast(unsigned, amax);
+    int x = (int)(u >> 23) - 8 + ((u & 0x7fffffu) > 0x600000u ? 1 : 0);
+    return x < 0 ? 0 : (x > 253 ? 253 : x);
+}
+__device__ __forceinline__ float f8c_inv_scale(int x) { return __builtin_bit_cast(float, (unsigned)(254 - x) << 23); }   // 2^(127 - x)
+// 32 values (scaled by 2^(127 - x), |v| <= 448) -> 32 e4m3 codes, round to nearest even
+__device__ __forceinline__ v8i f8c_codes(const float (&v)[32], float inv) {
+    v8i o;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        int w = 0;
+        w = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * i] * inv, v[4 * i + 1] * inv, w, false);
+        w = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * i + 2] * inv, v[4 * i + 3] * inv, w, true);
+        o[i] = w;
+    }
+    return o;
+}
+
+// the scaled MFMA on e4m3 operands; byte `ba` of the A scale word and byte OB of the B scale word (op_sel: compile-time; `ba` is
+// one after unrolling)
+template <int OB>
+__device__ __forceinline__ v4f f8c_mma(int ba, const v8i a, const v8i b, const v4f c, int sa, int sb) {
+    switch (ba) {
+        case 0: return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 0, 0, sa, OB, sb);
+        case 1: return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 0, 1, sa, OB, sb);
+        case 2: return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 0, 2, sa, OB, sb);
+        default: return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 0, 3, sa, OB, sb);
+    }
+}
+
+// the same with values 0 .. 15 and 16 .. 31 under two scales (the two MX blocks a lane's operand touches)
+__device__ __forceinline__ v8i f8c_codes2(const float (&v)[32], float inv0, float inv1) {
+    v8i o;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const float inv = i < 4 ? inv0 : inv1;
+        int w = 0;
+        w = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * i] * inv, v[4 * i + 1] * inv, w, false);
+        w = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * i + 2] * inv, v[4 * i + 3] * inv, w, true);
+        o[i] = w;
+    }
+    return o;
+}
+
+// one thread per (strip, K tile, MX block, row): that row's 32 K values of the block -> its slots in the three planes (two lanes'
+// halves) + the block's two scale bytes
+__global__ void __launch_bounds__(256) split_weights_f8c_kernel(const float* w0, const float* w1, const float* w2, int nseg, int nsegs,
+                                                                int K, unsigned char* out) {
+    const int KT = (K + 127) >> 7;
+    const int Ntot = nseg * nsegs;
+    const int strips = (Ntot + 79) / 80;
+    const long total = (long)strips * KT * 320;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int r = (int)(i % 80), bk = (int)((i / 80) & 3);
+        const long img = i / 320;                       // strip * KT + kt
+        const int strip = (int)(img / KT), kt = (int)(img - (long)strip * KT);
+        const int n = strip * 80 + r, k0 = kt * 128 + bk * 32;
+        float hi[32], lo[32];
+        float ah = 0.f, al = 0.f;
+#pragma unroll
+        for (int e = 0; e < 32; ++e) {
+            float v = 0.f;
+            if (n < Ntot && k0 + e < K) {
+                const int seg = n / nseg;
+                v = (seg == 0 ? w0 : (seg == 1 ? w1 : w2))[(long)(n - seg * nseg) * K + k0 + e];
+            }
+            const float vs = v * F16_WEIGHT_SCALE;       // as fp16x3: w_hi = fp16(w 2^10), round to nearest
+            const float h = (float)(_Float16)vs;
+            hi[e] = h; lo[e] = vs - h;                   // exact in fp32
+            ah = fmaxf(ah, fabsf(h)); al = fmaxf(al, fabsf(lo[e]));
+        }
+        unsigned char* const base = out + img * F8C_IMG_BYTES;
+        uint4* const slots = reinterpret_cast<uint4*>(base);
+        // block bk = K 32 bk + [0, 32) is half (bk >> 1) of lane groups 2 (bk & 1) + e, e = 0, 1: their values 16 (bk >> 1) + [0, 16)
+        const int half = bk >> 1;
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int kgx = 2 * (bk & 1) + e;
+#pragma unroll
+            for (int ss = 0; ss < 2; ++ss) {             // k-step 2 half + ss takes values 8 ss .. 8 ss + 7 of this half
+                unsigned p[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const unsigned a = __builtin_bit_cast(unsigned short, (_Float16)hi[16 * e + 8 * ss + 2 * q]);
+                    const unsigned b = __builtin_bit_cast(unsigned short, (_Float16)hi[16 * e + 8 * ss + 2 * q + 1]);
+                    p[q] = a | (b << 16);
+                }
+                slots[((2 * half + ss) * 4 + kgx) * 80 + r] = make_uint4(p[0], p[1], p[2], p[3]);
+            }
+        }
+        const int xh = f8c_e8m0(ah), xl = f8c_e8m0(al);
+        const v8i ch = f8c_codes(hi, f8c_inv_scale(xh)), cl = f8c_codes(lo, f8c_inv_scale(xl));
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int kgx = 2 * (bk & 1) + e;
+            slots[1280 + (half * 4 + kgx) * 80 + r] = make_uint4(ch[4 * e], ch[4 * e + 1], ch[4 * e + 2], ch[4 * e + 3]);
+            slots[1920 + (half * 4 + kgx) * 80 + r] = make_uint4(cl[4 * e], cl[4 * e + 1], cl[4 * e + 2], cl[4 * e + 3]);
+        }
+        unsigned char* const sc = base + 40960;          // read by lane group bk: the group that supplies block bk's scale
+        sc[((0 * 4 + bk) * 16 + (r & 15)) * 8 + (r >> 4)] = (unsigned char)xh;
+        sc[((1 * 4 + bk) * 16 + (r & 15)) * 8 + (r >> 4)] = (unsigned char)xl;
+        if (r < 16) {                                    // the padding bytes 5 .. 7 of each 8-byte record: zero, deterministically
+#pragma unroll
+            for (int p = 0; p < 2; ++p)
+#pragma unroll
+                for (int b = 5; b < 8; ++b) sc[((p * 4 + bk) * 16 + r) * 8 + b] = 0;
+        }
+    }
+}
+
+// Strip-mined projection kernel on that image: gemm_bf16x6s_kernel<NSUB, true>'s structure (strip images go global -> LDS by
+// LDS-DMA into a ring, the activations are split in the kernel, float4 epilogue with bias, K3 addend and segments, row lists,
+// the range flag) with 128-deep K tiles.  Eight waves stacked along M (16 rows each: a 128 x 80 NSUB tile per workgroup) share a
+// ring of two 41 KB images (one workgroup per CU, two waves per SIMD).  The activations do not pass through LDS: a lane's 32
+// K values of its row are two 64-byte runs (the four k groups of a row: two 256-byte runs), loaded as eight float4 one K tile ahead.
+// Any M: rows past M (or past *nrows_dev) are clamped copies of the last row, computed and never stored.
+template <int NSUB>
+__global__ void __launch_bounds__(512, 1) gemm_f16f8c_kernel(const GemmArgs g) {
+    constexpr int NT = 5, WAVES = 8, TROWS = 16 * WAVES;
+    constexpr int IMG_I = (F8C_PIECES + WAVES - 1) / WAVES;   // DMA instructions per wave and image (the last piece repeats)
+    constexpr int SLOTS = F8C_IMG_BYTES / 16;
+    __shared__ uint4 Bs[2][SLOTS];
+
+    const int Mv = g.nrows_dev ? __builtin_amdgcn_readfirstlane(*g.nrows_dev) : g.M;
+    if (g.exec_rows && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(g.exec_rows, (unsigned long long)Mv);
+    const int total = ((Mv + TROWS - 1) / TROWS) * g.ntiles;
+    const int chunk = (total + 7) >> 3;
+    if ((int)(blockIdx.x >> 3) >= chunk) return;
+    const int tile = (int)(blockIdx.x & 7) * chunk + (int)(blockIdx.x >> 3);
+    if (tile >= total) return;
+    const int mtile = tile / g.ntiles, ntile = tile - mtile * g.ntiles;
+
+    const int tid = threadIdx.x, lane = tid & 63, wm = tid >> 6;
+    const int kg = lane >> 4, lr = lane & 15;
+    const int m0 = mtile * TROWS;
+    const int strip0 = ntile * NSUB;
+    const int KT = (g.K + 127) >> 7;
+    const int nsteps = KT * NSUB;
+    const unsigned ldsB = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)&Bs[0][0];
+    const char* const wimg = reinterpret_cast<const char*>(g.wsplit);
+    const unsigned wlane = (unsigned)lane * 16u;
+    const int wu = __builtin_amdgcn_readfirstlane(wm);
+
+    auto issue_b = [&](int step) {           // strip image of step (kt, s) -> Bs[step & 1]
+        const int kt = step / NSUB, s = step - kt * NSUB;
+        const char* src = wimg + ((long)(strip0 + s) * KT + kt) * F8C_IMG_BYTES;
+#pragma unroll
+        for (int k = 0; k < IMG_I; ++k) {
+            int q = wu + WAVES * k;
+            q = q < F8C_PIECES ? q : F8C_PIECES - 1;
+            lds_dma16_s(src + q * 1024, wlane, ldsB + (unsigned)((step & 1) * F8C_IMG_BYTES + q * 1024));
+        }
+    };
+    // this lane's activation row (clamped; through the row list when there is one)
+    int gma = m0 + wm * 16 + lr;
+    gma = gma < Mv ? gma : Mv - 1;
+    if (g.rowidx) gma = g.rowidx[gma];
+    const float* const arow = g.a0 + (long)gma * g.lda0 + kg * 16;
+    float4 xr[8];                            // values 4 i .. 4 i + 3: K 16 kg + 4 i (i < 4), K 64 + 16 kg + 4 (i - 4) (i >= 4)
+    auto load_x = [&](int kt) {              // K % 4 == 0: a float4 is wholly inside K or wholly past it (zero)
+        const float* p = arow + kt * 128;
+        if (kt * 128 + 128 <= g.K) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) xr[i] = *reinterpret_cast<const float4*>(p + 4 * i + (i >= 4 ? 48 : 0));
+        } else {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int ko = 4 * i + (i >= 4 ? 48 : 0);
+                xr[i] = kt * 128 + kg * 16 + ko < g.K ? *reinterpret_cast<const float4*>(p + ko) : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        }
+    };
+    float amax = 0.f;                        // largest |activation| x 2^4 this lane has split (range flag)
+    bf16x8 xh[4];                            // x_hi, fp16, k-step s (bf16x8: storage type only)
+    v8i xq1, xq2;                            // q(x_hi), q(x_lo)
+    int xsc = 0;                             // E8M0 of q(x_hi) in byte 0, of q(x_lo) in byte 1
+    auto split_x = [&]() {
+        constexpr float xs = F16_ACT_SCALE;
+        float hi[32], lo[32];
+        unsigned xhw[16];
+        float ah[2] = {0.f, 0.f}, al[2] = {0.f, 0.f};       // per half of the lane's values (= its share of one MX block each)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float v[4] = {xr[i].x * xs, xr[i].y * xs, xr[i].z * xs, xr[i].w * xs};
+            amax = fmaxf(fmaxf(amax, fabsf(v[0])), fabsf(v[1])); amax = fmaxf(fmaxf(amax, fabsf(v[2])), fabsf(v[3]));
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const unsigned hb = pack_half_rtz(v[2 * e], v[2 * e + 1]);      // x_hi: fp16, round toward zero (as fp16x3)
+                const fp16x2 h = __builtin_bit_cast(fp16x2, hb);
+                hi[4 * i + 2 * e] = (float)h[0]; hi[4 * i + 2 * e + 1] = (float)h[1];
+                xhw[(i >> 1) * 4 + (i & 1) * 2 + e] = hb;                       // k-step i >> 1, dword (i & 1) * 2 + e of it
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                lo[4 * i + e] = v[e] - hi[4 * i + e];                          // exact
+                ah[i >> 2] = fmaxf(ah[i >> 2], fabsf(hi[4 * i + e])); al[i >> 2] = fmaxf(al[i >> 2], fabsf(lo[4 * i + e]));
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) xh[k] = __builtin_bit_cast(bf16x8, make_uint4(xhw[4 * k], xhw[4 * k + 1], xhw[4 * k + 2], xhw[4 * k + 3]));
+        // a block's other 16 values are in lane l ^ 16
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            ah[h] = fmaxf(ah[h], __shfl_xor(ah[h], 16, 64));
+            al[h] = fmaxf(al[h], __shfl_xor(al[h], 16, 64));
+        }
+        const int eh0 = f8c_e8m0(ah[0]), eh1 = f8c_e8m0(ah[1]), el0 = f8c_e8m0(al[0]), el1 = f8c_e8m0(al[1]);
+        xq1 = f8c_codes2(hi, f8c_inv_scale(eh0), f8c_inv_scale(eh1));
+        xq2 = f8c_codes2(lo, f8c_inv_scale(el0), f8c_inv_scale(el1));
+        // lane group g supplies block g's scale: groups 0 / 3 hold it (their pair's low / high half), groups 1 / 2 take it from
+        // the other pair (l ^ 48)
+        const int mine = eh0 | (eh1 << 8) | (el0 << 16) | (el1 << 24);
+        const int other = __shfl_xor(mine, 48, 64);
+        const int w = (kg == 0 || kg == 3) ? mine : other;
+        const int sh = kg < 2 ? 0 : 8;                   // groups 0, 1: low halves; 2, 3: high halves
+        xsc = ((w >> sh) & 0xff) | (((w >> (16 + sh)) & 0xff) << 8);
+    };
+
+    v4f acc[NSUB][NT];
+#pragma unroll
+    for (int s = 0; s < NSUB; ++s)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) acc[s][nt] = (v4f){0.f, 0.f, 0.f, 0.f};
+
+    load_x(0);
+    issue_b(0);
+    for (int kt = 0; kt < KT; ++kt) {
+        const int krel = g.K - kt * 128;
+        const int nks = krel >= 32 ? 4 : (krel + 7) >> 3;        // fp16 k-steps that meet a K value below K (the tail skips the rest)
+#pragma unroll
+        for (int s = 0; s < NSUB; ++s) {
+            const int step = kt * NSUB + s;
+            // the queue holds image(step) and (s == 0) this K tile's activations: both needed now
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();                          // landed for every wave; image(step - 1)'s buffer is free
+            if (s == 0) split_x();
+            if (step + 1 < nsteps) issue_b(step + 1);
+            if (s == NSUB - 1 && kt + 1 < KT) load_x(kt + 1);       // in flight under this step's MFMAs
+            const uint4* Bi = Bs[step & 1];
+            const int lslot = kg * 80 + lr;
+            const uint2 sch = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned char*>(Bi) + 40960 + ((0 * 4 + kg) * 16 + lr) * 8);
+            const uint2 scl = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned char*>(Bi) + 40960 + ((1 * 4 + kg) * 16 + lr) * 8);
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                const int sl = lslot + nt * 16;
+                const uint4 q1a = Bi[1280 + sl], q1b = Bi[1280 + 320 + sl];
+                const uint4 q2a = Bi[1920 + sl], q2b = Bi[1920 + 320 + sl];
+                const v8i wq1 = (v8i){(int)q1a.x, (int)q1a.y, (int)q1a.z, (int)q1a.w, (int)q1b.x, (int)q1b.y, (int)q1b.z, (int)q1b.w};
+                const v8i wq2 = (v8i){(int)q2a.x, (int)q2a.y, (int)q2a.z, (int)q2a.w, (int)q2b.x, (int)q2b.y, (int)q2b.z, (int)q2b.w};
+                const int sh = (int)(nt < 4 ? sch.x : sch.y), sl8 = (int)(nt < 4 ? scl.x : scl.y);
+                v4f c = acc[s][nt];
+                // the corrections first (small terms), then the leading product; byte (nt & 3) of the weights' scale word
+                c = f8c_mma<0>(nt & 3, wq2, xq1, c, sl8, xsc);    // q(w_lo) q(x_hi)
+                c = f8c_mma<1>(nt & 3, wq1, xq2, c, sh, xsc);     // q(w_hi) q(x_lo)
+#pragma unroll
+                for (int ks = 0; ks < 4; ++ks) {
+                    if (ks < nks) {
+                        const bf16x8 wh = __builtin_bit_cast(bf16x8, Bi[ks * 320 + sl]);
+                        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, wh), __builtin_bit_cast(half8, xh[ks]), c, 0, 0, 0);
+                    }
+                }
+                acc[s][nt] = c;
+            }
+        }
+    }
+
+    if (g.range_flag && __builtin_amdgcn_ballot_w64(!(amax < 65504.f)) != 0 && lane == 0) atomicOr(g.range_flag, 1u);
+    // epilogue as gemm_bf16x6s_kernel's (fp32 outputs only): a lane holds four consecutive output columns of one row
+    const int gv = m0 + wm * 16 + lr;
+    const bool rok = gv < Mv;
+    const int gvc = rok ? gv : Mv - 1;
+    const int gm = (g.rowidx && !g.gather_only) ? g.rowidx[gvc] : gvc;
+    const bool has_e0 = g.epi == EPI_RELU_RES || g.epi == EPI_ADD_E0;
+    constexpr float u = 1.f / (F16_WEIGHT_SCALE * F16_ACT_SCALE);      // the operands carry 2^10 and 2^4
+#pragma unroll
+    for (int s = 0; s < NSUB; ++s) {
+        const int ncol0 = (strip0 + s) * 80;
+        const int seg = ncol0 / g.nseg;
+        const int nbase = ncol0 - seg * g.nseg + kg * 4;
+        const float* const bp = g.bias[seg];
+        const bool radd_here = g.radd && seg == g.radd_seg;
+        float* const yrow = g.y[seg] + (long)gm * g.ldy;
+        float4 bv[NT], rv[NT], ev[NT];
+        if (bp) {
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) bv[nt] = *reinterpret_cast<const float4*>(bp + nbase + nt * 16);
+        }
+        if (radd_here) {
+            const float* rrow = g.radd + (long)(gm / g.rows_per_b) * g.nseg + nbase;
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) rv[nt] = *reinterpret_cast<const float4*>(rrow + nt * 16);
+        }
+        if (has_e0) {
+            const float* erow = g.e0 + (long)gm * g.lde0 + nbase;
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) ev[nt] = *reinterpret_cast<const float4*>(erow + nt * 16);
+        } else if (g.epi == EPI_ACCUM) {
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) ev[nt] = *reinterpret_cast<const float4*>(yrow + nbase + nt * 16);
+        }
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const v4f a = acc[s][nt];
+            float4 v = make_float4(a[0] * u, a[1] * u, a[2] * u, a[3] * u);
+            if (bp) v = f4_add(v, bv[nt]);
+            if (radd_here) v = f4_add(rv[nt], v);
+            if (g.epi == EPI_RELU_RES) {
+                const float4 x = ev[nt];
+                v = make_float4(fmaxf(v.x, 0.f) + x.x, fmaxf(v.y, 0.f) + x.y, fmaxf(v.z, 0.f) + x.z, fmaxf(v.w, 0.f) + x.w);
+            }
+            if (g.epi == EPI_ACCUM || g.epi == EPI_ADD_E0) v = f4_add(ev[nt], v);
+            if (rok) *reinterpret_cast<float4*>(yrow + nbase + nt * 16) = v;
+        }
+    }
+}
+
 // The split format of the strip-mined kernel's operands — 0 = three bf16 pieces, six products (fp32-grade); 1 = two fp16 pieces,
 // three products (gemm_bf16x6s_kernel<., true>) — is a property of the split IMAGE: whoever splits the weights says which
 // (GemmArgs.format travels with GemmArgs.wsplit; digat_params.flags & DIGAT_PARAMS_GEMM_F16X3 for the encoder's images), there is no
@@ -1235,8 +1584,16 @@ static int wsplit_format_of(const void* image) {          // -1: not an image th
     const auto it = g_wsplit_format.find(image);
     return it == g_wsplit_format.end() ? -1 : it->second;
 }
-// the strip-mined bf16x6 kernel serves this launch (the only kernel that takes a row list)
+// the fp16-fp8c kernel takes this launch (what gemm_f16f8c_kernel implements; anything else is refused, never sent elsewhere)
+static bool gemm_f16f8c_ok(const GemmArgs& g) {
+    return g.nseg % 80 == 0 && g.K % 4 == 0 && g.k0 == g.K && !g.a1 && !g.transW && !g.a_split && g.lda0 % 4 == 0 &&
+           ((uintptr_t)g.a0 & 15) == 0 && g.ldy % 4 == 0 && g.lde0 % 4 == 0 &&
+           (g.epi == EPI_NONE || g.epi == EPI_RELU_RES || g.epi == EPI_ACCUM || g.epi == EPI_ADD_E0) &&
+           !g.x1_segs && !g.x3_segs && !g.bf16_segs && !g.fp8_segs && !g.dmask;
+}
+// the strip-mined bf16x6 kernel serves this launch (the only kernel that takes a row list; fp16-fp8c: its own kernel)
 static bool gemm_is_bf16x6(const GemmArgs& g) {
+    if (g.format == DIGAT_GEMM_F16F8C) return g.wsplit && gemm_f16f8c_ok(g);        // its own kernel at every row count
     const int Md = g.m_dispatch > 0 ? g.m_dispatch : g.M;
     return g.wsplit && Md >= 2048 && g.nseg % 80 == 0 && g.K % 4 == 0 && g.K >= 32 && g.ldy % 4 == 0 && g.lde0 % 4 == 0 &&
            (g.epi == EPI_NONE || g.epi == EPI_RELU_RES || g.epi == EPI_ACCUM || g.epi == EPI_ADD_E0) && g.k0 == g.K && !g.transW;
@@ -1255,8 +1612,34 @@ static double gemm_row_bytes(const GemmArgs& g) {
     return in + out;
 }
 
+// DIGAT_GEMM_F16F8C: gemm_f16f8c_kernel at every row count (no other kernel reads its images)
+static int launch_gemm_f16f8c(GemmArgs g, hipStream_t st, int kind) {
+    if (!g.wsplit || !gemm_f16f8c_ok(g)) return DIGAT_ERR_ARG;
+    const int made_as = wsplit_format_of(g.wsplit);
+    if (made_as >= 0 && made_as != DIGAT_GEMM_F16F8C) return DIGAT_ERR_ARG;       // an image of another format
+    const int Ntot = g.nseg * g.nsegs, strips = Ntot / 80;
+    const bool listed = g.rowidx != nullptr && !g.gather_only;
+    if (listed && g_prof.enabled) {
+        g.exec_rows = g_prof.rows_dev + kind;
+        g_prof.flops_per_row[kind] = 2.0 * (double)Ntot * g.K; g_prof.rows_nominal[kind] += g.M;
+        g_prof.bytes_per_row[kind] = gemm_row_bytes(g);
+    }
+    ProfScope prof(kind, listed ? 0.0 : 2.0 * g.M * (double)Ntot * g.K, st, listed ? 0.0 : (double)g.M * gemm_row_bytes(g));
+    g.mtiles = (g.M + 127) / 128;
+    g.ntiles = strips % 3 == 0 ? strips / 3 : strips;
+    const dim3 grid((unsigned)(((g.mtiles * g.ntiles + 7) / 8) * 8));
+    if (strips % 3 == 0) hipLaunchKernelGGL((gemm_f16f8c_kernel<3>), grid, dim3(512), 0, st, g);
+    else hipLaunchKernelGGL((gemm_f16f8c_kernel<1>), grid, dim3(512), 0, st, g);
+    DIGAT_CHECK_LAUNCH();
+    return DIGAT_OK;
+}
+
 static int launch_gemm(GemmArgs g, hipStream_t st, int kind = DIGAT_KERNEL_LINEAR) {
     if (g.M <= 0) return DIGAT_OK;
+    if (g.format == DIGAT_GEMM_F16F8C) {
+        if (g.wsplit) return launch_gemm_f16f8c(g, st, kind);
+        g.format = DIGAT_GEMM_F16X3;        // no image (d % 80 != 0: nothing was split): the launch runs fp32, as fp16x3's would
+    }
     if (g.rowidx && !gemm_is_bf16x6(g)) return DIGAT_ERR_ARG;
     const int Ntot = g.nseg * g.nsegs;
     const int Md = g.m_dispatch > 0 ? g.m_dispatch : g.M;

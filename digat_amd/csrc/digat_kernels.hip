@@ -364,7 +364,8 @@ int digat_xattn_fwd_lowprec(const float* X, const uint8_t* A, const float* ctx,
                             const float* F3, const float* b3, const float* a, const void* wsplit, int format,
                             float* out, int B, int n, int d, int pq,
                             void* workspace, size_t workspace_bytes, void* stream) {
-    if (pq < 0 || pq > 2 || (format != 0 && format != 1)) return DIGAT_ERR_ARG;
+    if (pq < 0 || pq > 2 || (format != 0 && format != 1 && format != DIGAT_GEMM_F16F8C) || (format == DIGAT_GEMM_F16F8C && pq != 0))
+        return DIGAT_ERR_ARG;
     if (!X || !A || !ctx || !W || !F1 || !F2 || !F3 || !a || !wsplit || !out || !workspace) return DIGAT_ERR_ARG;
     if (B < 0 || n <= 0 || d <= 0) return DIGAT_ERR_ARG;
     if (d % 80 || d > 1024 || n <= 16 || n > DIGAT_MAX_NODES || (long)B * n < 2048) return DIGAT_ERR_SHAPE;
@@ -377,6 +378,12 @@ int digat_xattn_fwd_lowprec(const float* X, const uint8_t* A, const float* ctx,
 size_t digat_split_weights_bytes(int rows, int K) {
     return (size_t)((rows + 79) / 80) * ((K + 31) / 32) * WS_SLOTS * 16;       // one 15 KB image per (80-row strip, K tile)
 }
+size_t digat_split_weights_bytes_format(int rows, int K, int format) {
+    if (rows <= 0 || K <= 0) return 0;
+    if (format == DIGAT_GEMM_BF16X6 || format == DIGAT_GEMM_F16X3) return digat_split_weights_bytes(rows, K);
+    if (format == DIGAT_GEMM_F16F8C) return (size_t)((rows + 79) / 80) * ((K + 127) / 128) * F8C_IMG_BYTES;   // 41 KB per (strip, 128-deep K tile)
+    return 0;
+}
 
 // A training entry that was handed a ready-made image of its weights (digat_split_jobs: every image of a step in one launch) passes
 // the image where its helpers expect their split destination and names it here: the split launch for exactly that pointer is skipped.
@@ -386,11 +393,22 @@ struct PremadeImage {
     explicit PremadeImage(const void* image) : prev(tl_premade_image) { tl_premade_image = image; }
     ~PremadeImage() { tl_premade_image = prev; }
 };
-// format: DIGAT_GEMM_BF16X6 (three bf16 pieces; what every training entry uses) or DIGAT_GEMM_F16X3 (two scaled fp16 pieces)
+// format: DIGAT_GEMM_BF16X6 (three bf16 pieces; what every training entry uses), DIGAT_GEMM_F16X3 (two scaled fp16 pieces) or
+// DIGAT_GEMM_F16F8C (w_hi in fp16 + MX-e4m3 q(w_hi), q(w_lo): digat_split_weights_bytes_format bytes; [N, K] weights only)
 static int launch_split(const float* w0, const float* w1, const float* w2, int nseg, int nsegs, int K, void* wsplit, hipStream_t st,
                         int transposed = 0, int format = 0) {
-    if (format != 0 && format != 1) return DIGAT_ERR_ARG;
+    if (format != 0 && format != 1 && format != DIGAT_GEMM_F16F8C) return DIGAT_ERR_ARG;
     if (wsplit && wsplit == tl_premade_image) return format == 0 ? DIGAT_OK : DIGAT_ERR_ARG;
+    if (format == DIGAT_GEMM_F16F8C) {
+        if (transposed) return DIGAT_ERR_ARG;
+        const long total = (long)((nseg * nsegs + 79) / 80) * ((K + 127) / 128) * 320;      // threads: one per (image, k group, row)
+        int blocks = (int)((total + 255) / 256);
+        if (blocks > 2048) blocks = 2048;
+        wsplit_note(wsplit, format);
+        hipLaunchKernelGGL(split_weights_f8c_kernel, dim3(blocks), dim3(256), 0, st, w0, w1, w2, nseg, nsegs, K, (unsigned char*)wsplit);
+        DIGAT_CHECK_LAUNCH();
+        return DIGAT_OK;
+    }
     const long total = (long)nseg * nsegs * K;
     int blocks = (int)((total + 255) / 256);
     if (blocks > 2048) blocks = 2048;
@@ -524,7 +542,7 @@ int digat_linear_f32x3(const float* x, int64_t ldx, const float* w, const float*
     if (rcs) return rcs;
     GemmArgs g = gemm_plain(x, ldx, w, b, y, ldy, M, N, K, 0);
     g.wsplit = (const unsigned short*)wsplit; g.format = format;
-    if (g_train_bf16) g.x1_segs = 7;
+    if (g_train_bf16 && format != DIGAT_GEMM_F16F8C) g.x1_segs = 7;
     // M >= 2048: the strip-mined kernel; below: the skinny kernel on the same split image (gemm_skinny_split_kernel)
     return launch_gemm(g, (hipStream_t)stream, DIGAT_KERNEL_PROJ);
 }
@@ -805,8 +823,9 @@ static int encoder_fwd_folded(const EncoderCall& c, const float* Xg0) {
     const float* c_n_src = c.c_n0 && p->depth > 0 ? c.c_n0 : c_n;
     const bool xu0_grouped = Xg0 != nullptr;       // layer-0 user nodes exist once per group, at Xg0 [G,U,d]
     const int d = p->d, C = p->category_num, L = p->depth, U = H + C, C1 = C + 1;
-    const int fmt = (p->flags & DIGAT_PARAMS_GEMM_F16X3) ? 1 : 0;       // the format every wsplit image of `p` was split in
+    const int fmt = (p->flags & DIGAT_PARAMS_GEMM_F16X3) ? 1 : 0;       // the format every wsplit image of `p` was split in ...
     unsigned* const rflag = fmt ? (unsigned*)p->range_flag : nullptr;
+    const int lfmt = (p->flags & DIGAT_PARAMS_PROJ_F16F8C) ? DIGAT_GEMM_F16F8C : fmt;   // ... but the layers' [W|ffn1|ffn2]
     // the kernel of the [B,d] linears is named by the caller, not chosen from B: a row's bits must not depend on the batch it sits in
     // (nor on whether its context queries come from the per-news table)
     const int bd_disp = (p->flags & DIGAT_PARAMS_BD_TILED) ? (1 << 30) : 1;
@@ -1006,7 +1025,7 @@ static int encoder_fwd_folded(const EncoderCall& c, const float* Xg0) {
         gp.m_dispatch = 1 << 30;       // always the large-M kernel: a row's bits then do not depend on the batch it sits in
                                        // (digat_news_project0 makes the same launch per news, once)
         gp.wsplit = (const unsigned short*)ln.wsplit;
-        gp.format = fmt; gp.range_flag = rflag;
+        gp.format = lfmt; gp.range_flag = rflag;
         if (news_rowidx && gemm_is_bf16x6(gp)) { gp.rowidx = news_rowidx; gp.nrows_dev = news_nrows; }      // live nodes only (layers >= 1)
         return launch_gemm(gp, sq, DIGAT_KERNEL_PROJ);
     };
@@ -1025,7 +1044,7 @@ static int encoder_fwd_folded(const EncoderCall& c, const float* Xg0) {
             gs.nsegs = 3;
             gs.x3_segs = pq_x3 ? 6 : 0;
             gs.wsplit = (const unsigned short*)lu.wsplit;
-            gs.format = fmt; gs.range_flag = rflag;
+            gs.format = lfmt; gs.range_flag = rflag;
             gs.m_dispatch = B * U;
             if (want_live && gemm_is_bf16x6(gs)) { gs.rowidx = gl_idx; gs.nrows_dev = gl_off + B; }
             return launch_gemm(gs, sq, DIGAT_KERNEL_PROJ);
@@ -1064,7 +1083,7 @@ static int encoder_fwd_folded(const EncoderCall& c, const float* Xg0) {
         gg.nsegs = 3;
         gg.x3_segs = pq_x3 ? 6 : 0;
         gg.wsplit = (const unsigned short*)lu.wsplit;
-        gg.format = fmt; gg.range_flag = rflag;
+        gg.format = lfmt; gg.range_flag = rflag;
         gg.m_dispatch = B * U;                              // the kernel the per-row path would pick: same bits
         return launch_gemm(gg, sq, DIGAT_KERNEL_PROJ);
     };
@@ -1179,7 +1198,7 @@ static int encoder_fwd_folded(const EncoderCall& c, const float* Xg0) {
             // after the last layer only the history rows are read (the user context's topic pooling, :124):
             // the topic nodes' own Eq. 8 is not computed there (wave-per-centre sparse kernel)
             o.centre_limit = (i > 0 && i == L - 1 && sparse_mode == DIGAT_XATTN_SPARSE) ? H : 0;
-            o.gemm_format = fmt; o.range_flag = rflag;
+            o.gemm_format = lfmt; o.range_flag = rflag;
             o.tw = (i > 0 && tw_pub.word) ? &tw_pub : nullptr;
             rc = xattn_core(w.Xu[un], Au, r_user, lu.W, lu.bW, lu.F1, lu.F2, lu.a, w.Xu[un ^ 1], nullptr, B, U, d, w.xws, w.xws_bytes, st, o);
         }
@@ -1234,7 +1253,7 @@ static int encoder_fwd_folded(const EncoderCall& c, const float* Xg0) {
             o.sparse_mode = (p->flags & DIGAT_NEWS_XATTN_SPARSE) ? DIGAT_XATTN_SPARSE : DIGAT_XATTN_DENSE;
             o.pq_x3 = pq_x3;
             o.pq_mode = pq_mode;      // the news graph's P' always carries K3 from the GEMM epilogue: bf16 storage applies at every layer
-            o.gemm_format = fmt; o.range_flag = rflag;
+            o.gemm_format = lfmt; o.range_flag = rflag;
             o.prof_part = news_rowidx ? XPART_NEWS + 1 : 0;
             rc = xattn_core(xn_cur, An, w.r_news, ln.W, ln.bW, ln.F1, ln.F2, ln.a, w.Xn[nn], nullptr, B, N, d, w.xws_news, w.xws_news_bytes, sn, o);
         }
@@ -1358,6 +1377,7 @@ static int encoder_fwd_impl(EncoderCall& c) {
     XattnOpts o;
     o.gemm_format = (p->flags & DIGAT_PARAMS_GEMM_F16X3) ? 1 : 0;
     o.range_flag = o.gemm_format ? (unsigned*)p->range_flag : nullptr;
+    if (p->flags & DIGAT_PARAMS_PROJ_F16F8C) o.gemm_format = DIGAT_GEMM_F16F8C;     // the layers' images (the only ones this loop reads)
     for (int i = 0; i < L; ++i) {
         const digat_layer_params& ln = p->news[i];
         const digat_layer_params& lu = p->user[i];
@@ -1468,6 +1488,7 @@ int digat_user_project0(const digat_params* p, const float* X, float* hpq, int M
     gg.x3_segs = (p->flags & DIGAT_PROJ_PQ_X3) ? 6 : 0;
     gg.wsplit = (const unsigned short*)lu.wsplit;
     gg.format = (p->flags & DIGAT_PARAMS_GEMM_F16X3) ? 1 : 0; gg.range_flag = gg.format ? (unsigned*)p->range_flag : nullptr;
+    if (p->flags & DIGAT_PARAMS_PROJ_F16F8C) gg.format = DIGAT_GEMM_F16F8C;
     gg.m_dispatch = 1 << 30;                                               // the large-M kernel whatever M is (C topic rows)
     return launch_gemm(gg, (hipStream_t)stream, DIGAT_KERNEL_PROJ);
 }
@@ -1487,6 +1508,7 @@ int digat_news_project0(const digat_params* p, const float* Xn, float* hpq, int 
     gp.x3_segs = (p->flags & DIGAT_PROJ_PQ_X3) ? 6 : 0;
     gp.wsplit = (const unsigned short*)ln.wsplit;
     gp.format = (p->flags & DIGAT_PARAMS_GEMM_F16X3) ? 1 : 0; gp.range_flag = gp.format ? (unsigned*)p->range_flag : nullptr;
+    if (p->flags & DIGAT_PARAMS_PROJ_F16F8C) gp.format = DIGAT_GEMM_F16F8C;
     gp.m_dispatch = 1 << 30;
     return launch_gemm(gp, (hipStream_t)stream, DIGAT_KERNEL_PROJ);
 }

@@ -84,6 +84,9 @@ class DIGAT(GraphEncoder):
         # 80-channel strip; the fp8 half of configs[4]);
         # "fp16x3" = every operand as two fp16 pieces, three products (digat_set_gemm_format(1): 0.7x the GEMM time, error at or
         # below an fp32 fma chain's against fp64 for |w| < 63, |x| < 4094 — fp16's range after the format's scaling);
+        # "fp16-fp8c" (opt-in) = fp16x3 everywhere except the Eq. 8 node projections [W | ffn1 | ffn2] of every layer, whose two
+        # correction products run on the block-scaled fp8 matrix cores (DIGAT_GEMM_F16F8C / DIGAT_PARAMS_PROJ_F16F8C: e4m3 with
+        # one power-of-two scale per 32 K values; ~2^-15 of the result); fp16x3's range limits and range flag apply;
         # "auto" (default) = "fp16x3" when every projected weight is below 32 in magnitude, else "bf16x6" (no range limit)
         self.projection_mode = "auto"
         self._resolved_pm = None
@@ -218,17 +221,19 @@ class DIGAT(GraphEncoder):
                 lp.a = getattr(self, f"{g}_graph_attention_a")[i].weight.data_ptr()
         # bf16x6 projections: split [W | ffn1 | ffn2] of every layer into three bf16 planes (once per weight version)
         P._splits = []
-        if pm in ("bf16x6", "bf16x6-pq3", "pq-bf16", "pq-bf16-x1", "pq-fp8", "fp16x3") and self.news_embedding_dim % 80 == 0:
+        if pm in ("bf16x6", "bf16x6-pq3", "pq-bf16", "pq-bf16-x1", "pq-fp8", "fp16x3", "fp16-fp8c") and self.news_embedding_dim % 80 == 0:
             L_ = _lib.lib()
             d = self.news_embedding_dim
-            nbytes = L_.digat_split_weights_bytes(3 * d, d)
+            # the layers' images: "fp16-fp8c" splits them in their own format (every other image of the block stays fp16x3)
+            lfmt = _lib.GEMM_F16F8C if pm == "fp16-fp8c" else fmt
+            nbytes = L_.digat_split_weights_bytes_format(3 * d, d, lfmt)
             for g, arr in (("news", P.news), ("user", P.user)):
                 for i in range(self.graph_depth):
                     buf = _lib.split_buffer(nbytes, self.topic_node_embedding.device)
                     _lib.check(L_.digat_split_proj_weights(
                         getattr(self, f"{g}_graph_attention_W")[i].weight.data_ptr(),
                         getattr(self, f"{g}_graph_attention_ffn1")[i].weight.data_ptr(),
-                        getattr(self, f"{g}_graph_attention_ffn2")[i].weight.data_ptr(), d, buf.data_ptr(), fmt,
+                        getattr(self, f"{g}_graph_attention_ffn2")[i].weight.data_ptr(), d, buf.data_ptr(), lfmt,
                         _lib.stream_ptr()), "digat_split_proj_weights")
                     arr[i].wsplit = buf.data_ptr()
                     P._splits.append(buf)
@@ -287,7 +292,7 @@ class DIGAT(GraphEncoder):
         """The operand format of this encoder's split weight images: fp16x3 when asked for, and under "auto" / "pq-bf16" whenever
         the range conditions of ``_auto_base`` hold; bf16x6 otherwise."""
         pm = self.projection_mode
-        if pm == "fp16x3" or (pm in ("auto", "pq-bf16", "pq-fp8") and self._auto_base() == "fp16x3"):
+        if pm in ("fp16x3", "fp16-fp8c") or (pm in ("auto", "pq-bf16", "pq-fp8") and self._auto_base() == "fp16x3"):
             return _lib.GEMM_F16X3
         return _lib.GEMM_BF16X6
 
@@ -342,6 +347,7 @@ class DIGAT(GraphEncoder):
                 | (32 if pm == "pq-bf16-x1" else 0)                      # DIGAT_PQ_X1: ... and computed with one bf16 product
                 | (256 if pm == "pq-fp8" else 0)                         # DIGAT_PQ_FP8: P', Q of Eq. 8 stored as block-scaled e4m3
                 | (_lib.PARAMS_GEMM_F16X3 if self.gemm_format() == _lib.GEMM_F16X3 else 0)
+                | (_lib.PARAMS_PROJ_F16F8C if pm == "fp16-fp8c" else 0)  # ... except the layers' images: fp16 + MX-e4m3 corrections
                 | (_lib.PARAMS_BD_TILED if self.pass_rows >= 2048 else 0)
                 | {"auto": 0, "off": _lib.PARAMS_SIDE_STREAM_OFF, "on": _lib.PARAMS_SIDE_STREAM_ON}[self._launch_option("side_stream")]
                 | (0 if self._launch_option("live_rows") else _lib.PARAMS_NO_LIVE_ROWS))

@@ -43,6 +43,8 @@ def main(argv=None):
     if config.local_rank in (-1, 0):
         start = time.time()
         dc.news_embedding = model.news_encoder.table.detach()
+        if hasattr(model.graph_encoder, 'projection_mode'):      # the public switch of the scoring run's projection format
+            model.graph_encoder.projection_mode = config.inference_projection
         scores, metrics = util.compute_scores(model, dc, config.batch_size * 16, labels=corpus.row_label)
         print('AUC : %.4f\nMRR : %.4f\nnDCG@5 : %.4f\nnDCG@10 : %.4f' % metrics)
         print('Inference time : %.1fs' % (time.time() - start))

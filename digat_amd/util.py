@@ -491,9 +491,10 @@ def _range_fallback(enc, dc, batch_size):
     """An fp16x3 GEMM met an activation at or beyond the format's range (|x| >= 4094: node features of a deep layer, say): its
     results are degraded or inf.  Under "auto" the encoder moves to the range-free bf16x6 format (and stays there) and the
     per-news tables are rebuilt; an explicit "fp16x3" is the caller's word against the data's — refuse to return such scores."""
-    if enc.projection_mode == "fp16x3":
+    if enc.projection_mode in ("fp16x3", "fp16-fp8c"):       # both explicit, both with fp16x3's range
         from ._lib import DigatHipError
-        raise DigatHipError("projection_mode='fp16x3': an activation left the format's range (|x| >= 4094); use 'bf16x6' or 'auto'")
+        raise DigatHipError(f"projection_mode='{enc.projection_mode}': an activation left the format's range (|x| >= 4094); "
+                            "use 'bf16x6' or 'auto'")
     import warnings
     warnings.warn("digat_amd: fp16x3 projections met activations beyond the format's range; re-scoring in bf16x6")
     enc.range_fallback = True

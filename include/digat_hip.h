@@ -274,6 +274,11 @@ int digat_encoder_fwd(const digat_params* params,
  * cannot reach an output — history padding slots, topic nodes of unread categories: only their self loop, pooled with weight 0 —
  * are found on the device and skipped (about half of a MIND user graph).  Outputs are bit-identical either way. */
 enum { DIGAT_PARAMS_SIDE_STREAM_OFF = 512, DIGAT_PARAMS_SIDE_STREAM_ON = 1024, DIGAT_PARAMS_NO_LIVE_ROWS = 2048 };
+/* Bit 12, DIGAT_PARAMS_PROJ_F16F8C (with bit 6 set: every other image of the block is fp16x3): the layers' `wsplit` images
+ * ([W|ffn1|ffn2] of both graphs) were split with format DIGAT_GEMM_F16F8C, and every launch that reads one — the grouped, shared
+ * and per-row layer-0 projections, every layer's projection GEMM, digat_news_project0 / digat_user_project0 — runs the fp8-
+ * correction kernel at any row count.  Not combined with DIGAT_PROJ_PQ_X3, DIGAT_PQ_BF16 or DIGAT_PQ_FP8 (DIGAT_ERR_ARG). */
+enum { DIGAT_PARAMS_PROJ_F16F8C = 4096 };
 
 /* The same inference for rows that SHARE users: in dev/test scoring the ~37 candidate rows of one
  * impression carry identical user tensors (util.py:57-67 expands them per row).  Here the user side is
@@ -403,6 +408,20 @@ int digat_set_train_precision(int bf16);
  * zero; bf16 pieces keep fp32's exponent range.  Two host threads on two streams may therefore run an fp16x3 evaluation and a
  * training step at the same time. */
 enum { DIGAT_GEMM_BF16X6 = 0, DIGAT_GEMM_F16X3 = 1 };
+/* DIGAT_GEMM_F16F8C ("fp16-fp8c", BASELINE configs[4] on the fp8 matrix cores; images of the Eq. 8 node projections
+ * [W|ffn1|ffn2] only): fp16x3's three products with the two corrections, x_hi w_lo and x_lo w_hi, on the block-scaled
+ * v_mfma_scale_f32_16x16x128_f8f6f4 — operands OCP e4m3 with one E8M0 (power-of-two) scale per 32 consecutive K values, the
+ * largest magnitude of a block mapped to at most 448 — and the leading x_hi w_hi on v_mfma_f32_16x16x32_f16 as in fp16x3 (same
+ * 2^10 / 2^4 scaling, same range limits, same range flag).  Each correction is ~2^-11 of the result and carries e4m3's 2^-4
+ * relative step, so the product's relative error is ~2^-15 of the row scale (fp16x3: below an fp32 fma chain's); outputs stay
+ * fp32.  Image: per (80-column strip, 128-deep K tile; K zero-padded to a multiple of 128) the fp16 w_hi plane, the e4m3 planes of
+ * q(w_hi) and q(w_lo) and their scale bytes, 41 984 bytes (csrc/digat_gemm.inc, section 1e):
+ * digat_split_weights_bytes_format(rows, K, DIGAT_GEMM_F16F8C) bytes, NOT digat_split_weights_bytes (which is too small for
+ * K <= 96).  Any M; row lists; no bf16 / e4m3 output segments (digat_xattn_fwd_lowprec: pq = 0 only). */
+enum { DIGAT_GEMM_F16F8C = 2 };
+/* bytes of a split image of a [rows, K] weight (or of a stack of them: rows = the stacked rows) in `format`; formats 0 and 1
+ * give exactly digat_split_weights_bytes(rows, K).  0 for an unknown format. */
+size_t digat_split_weights_bytes_format(int rows, int K, int format);
 
 /* The step's head and tail around the encoder (round 6): the backward of digat_row_logits (model.py:75: logits = sum_d user_ctx news_ctx)
  * and the loss of trainer.py:100 — mean over the B impressions of -log_softmax(logits [B,K])[:, 0] — with its gradient d loss / d logits

@@ -4,6 +4,8 @@
   python tools/kbench.py xattn  [B n d]      Eq. 8 pairwise kernel alone (digat_xattn_pairwise_fwd)
   python tools/kbench.py linear [M N K]      fp32 MFMA linear (digat_linear_f32)
   python tools/kbench.py encoder             whole DIGAT.inference, per-kernel-kind breakdown
+  python tools/kbench.py gemm [M N K]        Eq. 8 projection GEMM in fp16x3 and fp16-fp8c (137 k x 1 200 x 400: the bench's
+                                             live rows), alternated; then 4 096-row scoring passes (inference_grouped) in each mode
 Timing with torch events on the current stream, median of --iters launches.
 """
 import os
@@ -120,6 +122,81 @@ def bench_linear(M=68608, N=400, K=400):
     ref = torch.addmm(b, x, w.t())
     t_ref, _ = timeit(lambda: torch.addmm(b, x, w.t()))
     print(f"   (rocBLAS addmm for scale: {t_ref*1e3:.1f} us, max|diff| {float((ref - y).abs().max()):.2e})")
+
+
+def bench_gemm(M=137216, N=1200, K=400, rounds=3):
+    """fp16x3 against fp16-fp8c (DIGAT_GEMM_F16F8C) on the same data, alternated `rounds` times: the projection GEMM alone (split
+    images made once, outside the timing), then whole 4 096-row passes of util.score_rows (inference_grouped) on a MIND-small-shaped
+    synthetic corpus.  Executed TF/s counts the issued MFMA work (fp16x3: three f16 products over K padded to 32; fp16-fp8c: the
+    f16 product over the k-steps below K plus two e4m3 products over K padded to 128) against the fp32-equivalent 2 M N K."""
+    import time
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(0)
+    x = torch.randn(M, K, device=dev, generator=g)
+    w = torch.randn(N, K, device=dev, generator=g) / K ** 0.5
+    b = torch.randn(N, device=dev, generator=g)
+    L = _lib.lib()
+    fmts = {"fp16x3": _lib.GEMM_F16X3, "fp16-fp8c": _lib.GEMM_F16F8C}
+    ys, imgs = {}, {}
+    for name, f in fmts.items():
+        imgs[name] = torch.empty(L.digat_split_weights_bytes_format(N, K, f), dtype=torch.uint8, device=dev)
+        _lib.check(L.digat_split_weights(w.data_ptr(), N, K, imgs[name].data_ptr(), f, _lib.stream_ptr()), "split")
+        ys[name] = torch.empty(M, N, device=dev)
+    # the GEMM alone: digat_linear_f32x3 re-splits per call, so time the split by itself and subtract it
+    times = {n: [] for n in fmts}
+    for _ in range(rounds):
+        for name, f in fmts.items():
+            def run():
+                _lib.check(L.digat_linear_f32x3(x.data_ptr(), K, w.data_ptr(), b.data_ptr(), ys[name].data_ptr(), N, M, N, K,
+                                                imgs[name].data_ptr(), f, _lib.stream_ptr()), "linear")
+            def split():
+                _lib.check(L.digat_split_weights(w.data_ptr(), N, K, imgs[name].data_ptr(), f, _lib.stream_ptr()), "split")
+            t, _ = timeit(run)
+            ts, _ = timeit(split)
+            times[name].append((t - ts) * 1e3)
+    ref = x.double() @ w.double().t() + b.double()
+    kp32, kp128 = -(-K // 32) * 32, -(-K // 128) * 128
+    ks_f16 = sum(min(4, -(-(K - kt * 128) // 8)) for kt in range(kp128 // 128)) * 32
+    issued = {"fp16x3": 3 * 2.0 * M * N * kp32, "fp16-fp8c": 2.0 * M * N * (ks_f16 + 2 * kp128)}
+    for name in fmts:
+        us = float(np.median(times[name]))
+        err = float((ys[name].double() - ref).abs().max() / ref.abs().max())
+        print(f"gemm {name:9s} M={M} N={N} K={K}: {us:.1f} us (median of {rounds} alternations: "
+              f"{', '.join(f'{t:.1f}' for t in times[name])})  {2.0 * M * N * K / us / 1e6:.1f} fp32-equivalent TF/s  "
+              f"{issued[name] / us / 1e6:.1f} executed TF/s  max err / max|y| {err:.2e}")
+    # whole scoring passes
+    from digat_amd import synthetic, util
+    from digat_amd.model import Model, PrecomputedNewsEncoder
+    import types
+    spec = synthetic.SynthSpec(news_num=8192, impressions=1200, seed=3)
+    corpus = synthetic.make_corpus(spec)
+    state = synthetic.make_state_dict(spec.embedding_dim, spec.category_num, 3, seed=4, bias_std=0.05)
+    cfg = types.SimpleNamespace(news_encoder="MSA", graph_encoder="DIGAT", news_graph_size=spec.news_graph_size,
+                                max_history_num=spec.max_history_num, category_num=spec.category_num, graph_depth=3, dropout_rate=0.2)
+    model = Model(cfg, news_encoder=PrecomputedNewsEncoder(torch.from_numpy(corpus.news_embedding)))
+    model.graph_encoder.load_state_dict({k: torch.from_numpy(v) for k, v in state.items()})
+    model = model.to(dev).eval()
+    dc = util.DeviceCorpus.from_numpy(corpus, dev)
+    rows = dc.rows
+    npass = rows / 4096.0
+    imps = int(spec.impressions)
+    enc = model.graph_encoder
+    pass_ms = {n: [] for n in fmts}
+    for _ in range(rounds):
+        for name in fmts:
+            enc.projection_mode = name
+            util.prepare_news_side(enc, dc, 1024)
+            util.score_rows(model, dc, 0, rows, 1024, launch_rows=4096)          # warm
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            with torch.no_grad():
+                util.score_rows(model, dc, 0, rows, 1024, launch_rows=4096)
+            torch.cuda.synchronize()
+            pass_ms[name].append((time.perf_counter() - t0) * 1e3 / npass)
+    for name in fmts:
+        ms = float(np.median(pass_ms[name]))
+        print(f"pass {name:9s} 4 096-row passes ({npass:.1f} per run, {rows} rows, {imps} impressions): {ms:.3f} ms per pass "
+              f"({', '.join(f'{t:.3f}' for t in pass_ms[name])}), {imps / (ms * npass / 1e3):.0f} impressions/s")
 
 
 def bench_topic(B=1024, H=50, C=17, d=400):
@@ -255,3 +332,5 @@ if __name__ == "__main__":
         bench_topic(*nums)
     elif what == "linear":
         bench_linear(*nums)
+    elif what == "gemm":
+        bench_gemm(*nums)
