@@ -179,7 +179,6 @@ struct TopicArgs {
     const float* Xu; long ld_b; const float* kq; const int64_t* idx; float* out;
     int B, H, C1, d; float sqrt_d;
     float* alpha_out;                    // optional [B,H]: the segment-softmax weights (training)
-    int skip;                            // always 0 (a removed timing ablation's switch: bits 1, 2, 4 skip kernel phases)
     const int* group;                    // optional [B]: row b's nodes live at Xu + group[b] * ld_b (rows of one impression share them)
     const uint8_t* live; int live_ld;    // optional [B, live_ld] bytes: history rows t with live[b * live_ld + t] == 0 hold nothing
                                          // (dead nodes are never written by the encoder's layers): they are taken as 0 — by a
@@ -221,7 +220,7 @@ __global__ void __launch_bounds__(1024) topic_pool_kernel(const TopicArgs g) {
     }
     for (int i = tid; i < ct * 16 * hs; i += nthreads) M[i] = 0.f;
     __syncthreads();
-    for (int t0 = wave; t0 < ((g.skip & 1) ? 0 : H); t0 += 4 * nw) {
+    for (int t0 = wave; t0 < H; t0 += 4 * nw) {
         float part[4] = {0.f, 0.f, 0.f, 0.f};
         for (int c4 = lane; c4 < d4; c4 += 64) {
             const float4 k = K4[c4];
@@ -242,7 +241,7 @@ __global__ void __launch_bounds__(1024) topic_pool_kernel(const TopicArgs g) {
         }
     }
     __syncthreads();
-    for (int t = tid; t < ((g.skip & 2) ? 0 : H); t += nthreads) {
+    for (int t = tid; t < H; t += nthreads) {
         const int s = sidx[t];
         float m = -INFINITY;
         for (int u = 0; u < H; ++u) if (sidx[u] == s) m = fmaxf(m, sa[u]);
@@ -257,7 +256,7 @@ __global__ void __launch_bounds__(1024) topic_pool_kernel(const TopicArgs g) {
     const int lr = lane & 15, lq = lane >> 4;
     const int ch = wave * 64 + 4 * lr;
     const bool ch_ok = ch < g.d;             // no early exit: the MFMAs need every lane's operand rows
-    const int nsteps = (g.skip & 4) ? 0 : (H + 3) >> 2;
+    const int nsteps = (H + 3) >> 2;
     auto load_x = [&](int step) -> float4 {
         const int j = step * 4 + lq;
         return (j < H && ch_ok && slive[j]) ? *reinterpret_cast<const float4*>(Xb + (long)j * g.d + ch) : f4_zero();
@@ -478,7 +477,7 @@ static int launch_topic(const float* Xu, long ld_b, const float* kq, const int64
                         int B, int H, int C1, int d, hipStream_t st, const int* group = nullptr,
                         const uint8_t* live = nullptr, int live_ld = 0, const int* hlast = nullptr) {
     if (B == 0) return DIGAT_OK;
-    TopicArgs g{Xu, ld_b, kq, idx, out, B, H, C1, d, sqrtf((float)d), nullptr, 0, group, live, live_ld, hlast};
+    TopicArgs g{Xu, ld_b, kq, idx, out, B, H, C1, d, sqrtf((float)d), nullptr, group, live, live_ld, hlast};
     ProfScope prof(DIGAT_KERNEL_TOPIC, (double)B * ((double)H * d * 4 + d * 4.0 + H * 8.0 + (double)C1 * d * 4), st);
     return launch_topic_args(g, st);
 }

@@ -27,7 +27,6 @@ struct CtxFusedArgs {
     const float* kq_topic; const float* kq_user; const int64_t* idx; const uint8_t* cat_mask; const float* addend; float* out;
     const uint4* wimg; const float* bFa; unsigned* range_flag;
     int B, H, C1, d; float sqrt_d;
-    int dbg;                              // unused, always 0 (a removed timing ablation's switch)
 };
 constexpr int CF_R = 4;                  // rows per workgroup
 constexpr int CF_STEPS = 13;             // 4-row steps of a history held in registers: H <= 52
@@ -85,7 +84,7 @@ __device__ __forceinline__ float cf_row16_sum(float p) {      // sum over the 16
     p += dpp_mov<0xB1>(p); p += dpp_mov<0x4E>(p); p += dpp_mov<0x141>(p); p += dpp_mov<0x140>(p);
     return p;
 }
-// four consecutive channels -> their two scaled fp16 pieces (gemm_bf16x6s_kernel<., true>::split_mt's arithmetic), 8 bytes each
+// four consecutive channels -> their two scaled fp16 pieces (gemm_bf16x6s_kernel<., true, ., .>::split_mt's arithmetic), 8 bytes each
 __device__ __forceinline__ void cf_split4(const float a, const float b, const float c, const float d4, uint2& hi, uint2& lo, float& amax) {
     constexpr float xs = F16_ACT_SCALE;
     const float s0 = a * xs, s1 = b * xs, s2 = c * xs, s3 = d4 * xs;

@@ -1,44 +1,12 @@
-// digat_gemm.inc — the GEMMs of the path: fp32 MFMA, strip-mined bf16x6 (LDS-DMA), skinny [B,d] linears, and their dispatch
+// digat_gemm.inc — the GEMMs of the path: fp32 MFMA, strip-mined bf16x6 (LDS-DMA), skinny [B,d] linears, and launch_gemm, which runs
+// every GEMM the way gemm_plan (digat_gemm_plan.h) decides
 // Included by digat_kernels.hip (one translation unit: hipcc --offload-arch=gfx950).
+
+#include "digat_gemm_plan.h"         // GemmArgs, the EPI_* epilogues and gemm_plan: which kernel below runs a launch
 
 // =================================================================================================
 // 1. fp32 MFMA GEMM:  y_s[M, nseg] = A[M,K] @ w_s[nseg,K]^T (+ bias_s), s < nsegs, fused epilogue
 // =================================================================================================
-enum { EPI_NONE = 0, EPI_RELU_RES = 1, EPI_GATE = 2, EPI_ACCUM = 3,     // ACCUM: y += result (backward sums)
-       EPI_ADD_E0 = 4 };   // y = result + e0 (strip-mined kernel only: a residual gradient joins without a copy + read-modify-write)
-
-struct GemmArgs {
-    const float* a0; long lda0; int k0;      // columns [0,k0) of A come from a0 ...
-    const void* a_split;                     // strip-mined fp16x3 kernel, PRE only: the rows of a0 ALREADY SPLIT by their producer (same
-                                             // row stride, 32 bytes per 8 columns: [8 fp16 hi | 8 fp16 lo], the pieces split_mt makes).
-                                             // No launch sets it (docs/REJECTED.md row 4q)
-    const float* a1; long lda1;              // ... columns [k0,K) from a1 (gate: [local ; global])
-    const float* w[3]; const float* bias[3]; float* y[3]; long ldy;
-    int nseg, nsegs, M, K, transW;           // transW: w_s stored [K, nseg] (y = A @ w)
-    int epi;
-    const float* e0; long lde0; const float* e1; long lde1; const float* e2; long lde2;
-    int mtiles, ntiles;
-    const unsigned short* wsplit;            // bf16x6 path: [3 planes][nsegs*nseg][K] bf16 of the weights
-    const float* radd; int radd_seg, rows_per_b;   // segment radd_seg: y += radd[row / rows_per_b][col]  (K3 + K1 of Eq. 8)
-    unsigned long long* exec_rows;                 // profiling only: += rows processed by a row-list launch
-    const int* rowidx; const int* nrows_dev;       // bf16x6 kernel only: process rows rowidx[0 .. *nrows_dev) of A / y (live rows)
-    int gather_only;                               // with rowidx: only A is indexed (embedding lookup), y rows are 0 .. M-1
-    int m_dispatch;                                // != 0: choose the kernel as if M were this (bit-identical results across batchings)
-    int x3_segs;                                   // bf16x6 kernel: bit s set = segment s with the three leading products only
-                                                   // (hi*hi, mid*hi, hi*mid: relative error ~2^-16 instead of ~2^-24)
-    int x1_segs;                                   // ... bit s set = segment s with the leading product alone (hi*hi: ~2^-8)
-    int bf16_segs;                                 // ... bit s set = y[s] is a bf16 array (round to nearest even), ldy in elements
-    int fp8_segs; long ldy8;                       // ... bit s set = y[s] is an array of block-scaled e4m3 rows, ldy8 BYTES apart:
-                                                   // [nseg bytes of OCP e4m3 | nseg / 80 fp32 scales, one per 80-column strip | pad]
-                                                   // (value = e4m3 x scale; scale = the strip's absmax / 448: see the epilogue)
-    int format;                                    // operand format of the strip-mined kernel AND of the wsplit image: 0 = three bf16
-                                                   // pieces, six products ("bf16x6"); 1 = two scaled fp16 pieces, three products ("fp16x3")
-    unsigned* range_flag;                          // fp16x3 only, optional: |= 1 when an activation leaves the format's range (|x| >= 4094)
-    const uint8_t* dmask; long lddm; float dscale; // bf16x6 kernel, optional: y = (result [+ e0]) x (dmask[row][col] ? dscale : 0) — the backward
-    int dmask_cols;                                // of the dropout in front of the layer (training: dX through the keep bytes [M, lddm]);
-                                                   // dmask_cols > 0: the mask has that many columns, output columns beyond them are left as computed
-};
-
 // LDS image: float4 tile[k4][row ^ k4]  (k4 = 4-float column group of the 32-deep K tile).
 // A lane quarter q reads column group 4*kk+q with ds_read_b128 and feeds element s of it to the
 // s-th MFMA k-step (A and B use the same k assignment, so the sum over k is complete); the XOR of
@@ -321,7 +289,7 @@ constexpr int WS_SLOTS = 960;            // 16-byte slots of one strip image: 3 
 // transposed != 0 (one segment): the weight is stored [K, nseg] and used as its transpose (dX = dY @ W); 2: three such matrices of
 // K / 3 rows each, given separately, stacked along K (dX = [dh | dP | dQ] @ [W; F1; F2] without concatenating the weights)
 // planes = 3: the three bf16 pieces; planes = 2: two fp16 pieces (hi = v truncated to fp16, lo = the remainder truncated: 22
-// significant bits; "fp16x3", see gemm_bf16x6s_kernel<., true>), images of 2 x 320 slots
+// significant bits; "fp16x3", see gemm_bf16x6s_kernel<., true, ., .>), images of 2 x 320 slots
 __device__ __forceinline__ void split_weights_tiled_body(const float* w0, const float* w1, const float* w2,
                                                          int nseg, int nsegs, int K, unsigned short* out, int transposed, int planes) {
     const int KT = (K + 31) >> 5, Kp = KT * 32;
@@ -447,40 +415,25 @@ __device__ unsigned long long g_gemm_timers[8];
 #else
 #define GT_NOW() 0ull
 #endif
-// PRE (round 4, fp16x3 only): the A rows arrive already split into their two scaled fp16 pieces (GemmArgs.a_split: written by the
-// kernel that produced the rows).  A row's 32 k of a K tile are the same 128 bytes in both layouts, so the DMA is unchanged and the
-// operand "split" is two LDS reads — the ~50 vector instructions per K tile and wave that every one of a row's five 240-column tiles
-// used to repeat are gone from the loop.  Same pieces, same products, same order: bit-identical results.
-// Round 5 experiment, OFF (tools/exp/build_variant.sh x -DDIGAT_GEMM_SPREAD=1): the step's LDS-DMA pieces issued one or two per
-// 16-column block behind that block's MFMAs instead of in one burst at the top of the step.  Bit-identical; measured 1.27 against
-// 1.25 ms of projection time per 4 096-row step alone (2 % slower), the step 3.04-3.07 against 3.07-3.09 ms (noise): like DESIGN.md
-// docs/REJECTED.md rows 1-4q, where the burst sits is not what a step waits for.
-#ifndef DIGAT_GEMM_FULL
-#define DIGAT_GEMM_FULL 1
-#endif
-#ifndef DIGAT_GEMM_SPREAD
-#define DIGAT_GEMM_SPREAD 0
-#endif
-// FULL (round 5): every segment of the launch takes all its products (x1_segs == x3_segs == 0: what inference launches ask for) —
-// the per-strip product selector becomes a compile-time constant, the wave-uniform branch around each 16-column block's extra
-// products (five per strip) goes, and a strip's 30 MFMAs + 10 fragment reads are ONE basic block for the scheduler.
-template <int NSUB, bool F16, int MT = 2, bool PRE = false, bool FULL = false>      // MT: 16-row blocks per wave (wave tile 16 MT x 80 NSUB); 4 = "fat waves", one per SIMD
-__global__ void __launch_bounds__(256, MT == 1 ? 3 : (MT == 2 ? 2 : 1)) gemm_bf16x6s_kernel(const GemmArgs g) {
-    static_assert(!PRE || F16, "pre-split A rows are fp16x3 pieces");
+// The instantiations gemm_plan launches: NSUB = 3 (240-column tiles) or 1; F16 (fp16x3) or bf16x6; MT = 2 (128-row tiles) or 1
+// (64-row tiles for launches that would leave the chip under-filled); FULL (round 5, fp16x3 with 240-column tiles): every segment
+// of the launch takes all its products (x1_segs == x3_segs == 0: what inference launches ask for) — the per-strip product
+// selector becomes a compile-time constant, the wave-uniform branch around each 16-column block's extra products (five per strip)
+// goes, and a strip's 30 MFMAs + 10 fragment reads are ONE basic block for the scheduler.  The variants measured and rejected
+// (pre-split A rows, the spread DMA issue, 64-row "fat" wave tiles) are in docs/REJECTED.md.
+template <int NSUB, bool F16, int MT, bool FULL>      // MT: 16-row blocks per wave (wave tile 16 MT x 80 NSUB)
+__global__ void __launch_bounds__(256, MT == 1 ? 3 : 2) gemm_bf16x6s_kernel(const GemmArgs g) {
+    static_assert(MT == 1 || MT == 2, "wave tiles of 16 or 32 rows");
     constexpr int NT = 5;
     constexpr int WROWS = 16 * MT, TROWS = 4 * WROWS;      // rows of a wave tile / of the workgroup's tile (four waves stacked along M)
     constexpr int APW = 2 * MT;                             // 1 KB DMA pieces (8 rows x 32 k fp32) of the A tile per wave
-#ifndef DIGAT_G1_RING
-#define DIGAT_G1_RING 3
-#define DIGAT_G1_ABUF 2
-#endif
     // One-strip tiles (NSUB == 1: featureAffine, N not a multiple of 240): the A tile travels ABUF - 1 steps ahead, the strip
     // images RING - 1, and the operand split of step k + 1 runs in the shadow of step k's MFMAs (it used to open every step:
     // 16.0 -> 14.7 us on 7 000 x 400 x 400).  Deeper rings measured no better (3 / 3: 16.2 us; 5 / 4 at one workgroup per CU:
     // 24.8 us): the phase timers show these launches waiting 7 % of a step — what is left is launch, prologue and epilogue.
-    constexpr int RING = NSUB == 1 ? DIGAT_G1_RING : 3;   // strip images in LDS: RING - 1 in flight behind the one being read
-    constexpr int ABUF = NSUB == 1 ? (F16 ? DIGAT_G1_ABUF : 2) : 1;   // fp32 A tiles (128 rows x 32 k) in LDS (three 15 KB bf16
-                                                          // planes per image leave room for two: 77 KB, two workgroups per CU)
+    constexpr int RING = 3;                   // strip images in LDS: RING - 1 in flight behind the one being read
+    constexpr int ABUF = NSUB == 1 ? 2 : 1;   // fp32 A tiles (128 rows x 32 k) in LDS (three 15 KB bf16 planes per image leave
+                                              // room for two: 77 KB, two workgroups per CU)
     constexpr int PL = F16 ? 2 : 3;          // operand pieces
     constexpr int WS_SLOTS = PL * 320;       // 16-byte slots of one strip image (shadows the bf16 constant)
     constexpr int PIECES = WS_SLOTS / 64;    // 1 KB DMA pieces of an image: 15 / 10
@@ -532,7 +485,7 @@ __global__ void __launch_bounds__(256, MT == 1 ? 3 : (MT == 2 ? 2 : 1)) gemm_bf1
     // (contiguous rows: the offsets stay below 128 rows), or the operand's start for a row-list launch, whose rows then have to span
     // less than 4 GB (checked by the launcher; 439 MB for the 274 k x 400 user nodes of a 4 096-row pass)
     const long arow0 = g.rowidx ? 0 : (long)(m0 < Mv ? m0 : Mv - 1);
-    const char* const abase = reinterpret_cast<const char*>((PRE ? reinterpret_cast<const float*>(g.a_split) : g.a0) + arow0 * g.lda0);
+    const char* const abase = reinterpret_cast<const char*>(g.a0 + arow0 * g.lda0);
     unsigned aoff[APW];
     int ac4[APW];
 #pragma unroll
@@ -557,14 +510,6 @@ __global__ void __launch_bounds__(256, MT == 1 ? 3 : (MT == 2 ? 2 : 1)) gemm_bf1
 #pragma unroll
         for (int k = 0; k < APW; ++k) issue_a_piece(kt, abuf, k);
     };
-    auto issue_b_piece = [&](int step, int k) {             // piece k (0 .. IMG_I - 1) of this wave's share of the strip image of `step`
-        const int kt = step / NSUB, s = step - kt * NSUB;
-        const int buf = step % RING;
-        const char* src = wimg + ((long)(strip0 + s) * KT + kt) * (WS_SLOTS * 16);
-        int q = wu + 4 * k;
-        q = q < PIECES ? q : PIECES - 1;
-        lds_dma16_s(src + q * 1024, wlane, ldsB + (unsigned)((buf * WS_SLOTS + q * 64) * 16));
-    };
     auto split_half = [&](const float4& v, unsigned (&o)[3][2]) {
         const Split3f s0 = split3f(v.x), s1 = split3f(v.y), s2 = split3f(v.z), s3 = split3f(v.w);
         o[0][0] = pack_hi16(s0.a, s1.a); o[0][1] = pack_hi16(s2.a, s3.a);
@@ -575,11 +520,6 @@ __global__ void __launch_bounds__(256, MT == 1 ? 3 : (MT == 2 ? 2 : 1)) gemm_bf1
     auto split_mt = [&](int mt, int abuf, bf16x8 (&dst)[3][MT]) {     // this lane's 8 k of row (mt, lr): LDS -> 3 bf16 (2 fp16) fragments
         const int r = wm * WROWS + mt * 16 + lr;
         const int sw = (r >> 1) & 7;
-        if constexpr (PRE) {                 // [8 hi | 8 lo] of this lane's 8 k, as the producer stored them
-            dst[0][mt] = __builtin_bit_cast(bf16x8, As[abuf][r * 8 + ((kg * 2) ^ sw)]);
-            dst[1][mt] = __builtin_bit_cast(bf16x8, As[abuf][r * 8 + ((kg * 2 + 1) ^ sw)]);
-            return;
-        }
         const float4 v0 = __builtin_bit_cast(float4, As[abuf][r * 8 + ((kg * 2) ^ sw)]);
         const float4 v1 = __builtin_bit_cast(float4, As[abuf][r * 8 + ((kg * 2 + 1) ^ sw)]);
         if constexpr (F16) {
@@ -684,17 +624,12 @@ __global__ void __launch_bounds__(256, MT == 1 ? 3 : (MT == 2 ? 2 : 1)) gemm_bf1
             gt_last = GT_NOW();
             gt_wait += gt1 - gt0; gt_bar += gt_last - gt1; ++gt_steps;
 #endif
-            // SPREAD (experiment, off: see DIGAT_GEMM_SPREAD): the step's DMA pieces — this wave's four of the next A tile at strip 0,
-            // its three of the strip image two steps ahead — one or two per 16-column block behind that block's six MFMAs instead of
-            // in one burst in front of the step's first MFMA; the queue order (A pieces, then the image's) and every vmcnt count stay
-            constexpr bool SPREAD = DIGAT_GEMM_SPREAD && NSUB > 1 && MT == 2 && !PRE;
-            const bool do_a = NSUB > 1 && s == 0 && more, do_b = NSUB > 1 && step + 2 < nsteps;
             if (NSUB == 1) {
                 if (kt + ABUF < KT) issue_a(kt + ABUF, kt % ABUF);  // the buffer of A(kt): split during step kt - 1
                 if (step + RING - 1 < nsteps) issue_b(step + RING - 1);
-            } else if (!SPREAD) {
-                if (do_a) issue_a(kt + 1, 0);            // read at strip 1, after the next barrier
-                if (do_b) issue_b(step + 2);
+            } else {
+                if (s == 0 && more) issue_a(kt + 1, 0);   // read at strip 1, after the next barrier
+                if (step + 2 < nsteps) issue_b(step + 2);
             }
             const uint4* Bi = Bs[buf];
             const int lslot = kg * 80 + lr;
@@ -730,30 +665,16 @@ __global__ void __launch_bounds__(256, MT == 1 ? 3 : (MT == 2 ? 2 : 1)) gemm_bf1
                 for (int mt = 0; mt < MT; ++mt) c[mt] = mma(b1, af[0][mt], c[mt]);       // x1 w1
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt) acc[s][mt][nt] = c[mt];
-                if constexpr (SPREAD) {
-                    // A pieces 0,1 behind block 0 and 2,3 behind block 1 (strip 0 only), the image's pieces behind blocks 2, 3, 4
-                    if (nt == 0 && do_a) { issue_a_piece(kt + 1, 0, 0); issue_a_piece(kt + 1, 0, 1); }
-                    if (nt == 1 && do_a) { issue_a_piece(kt + 1, 0, 2); issue_a_piece(kt + 1, 0, 3); }
-                    if (nt >= 2 && nt < NT - 1 && do_b) issue_b_piece(step + 2, nt - 2);
-                    if (nt == NT - 1 && do_b) {
-#pragma unroll
-                        for (int k = NT - 3; k < IMG_I; ++k) issue_b_piece(step + 2, k);       // the last block takes what is left (bf16x6: two)
-                    }
-                }
                 if (NSUB > 1) {      // the next K tile's rows landed at this step's wait (requested at strip 0); after the last
                                      // K tile the split runs on the stale tile (unused) so that the strip stays one basic block
                     if (s == 1 && nt == 0) split_mt(0, 0, afn);
                     if constexpr (MT > 1) { if (s == 1 && nt == 2) split_mt(1, 0, afn); }
-                    if constexpr (MT > 2) {
-                        if (s == 2 && nt == 0) split_mt(2, 0, afn);
-                        if (s == 2 && nt == 2) split_mt(3, 0, afn);
-                    }
                 } else {             // one-strip tiles: A(kt + 1) landed at this step's wait (after the last K tile: a stale buffer, unused)
                     if (nt == 0) split_mt(0, (kt + 1) % ABUF, afn);
                     if constexpr (MT > 1) { if (nt == 2) split_mt(1, (kt + 1) % ABUF, afn); }
                 }
             }
-            if (NSUB == 1 || s == 1 || (MT > 2 && s == 2)) {
+            if (NSUB == 1 || s == 1) {
                 // the ~100 vector instructions of the operand split go two per MFMA (an MFMA holds the SIMD's vector issue for
                 // 8 of its 16 cycles: two 4-cycle instructions fit in the gap) instead of two bursts that stall the matrix pipe
 #pragma unroll
@@ -1357,7 +1278,7 @@ __global__ void __launch_bounds__(256) split_weights_f8c_kernel(const float* w0,
     }
 }
 
-// Strip-mined projection kernel on that image: gemm_bf16x6s_kernel<NSUB, true>'s structure (strip images go global -> LDS by
+// Strip-mined projection kernel on that image: gemm_bf16x6s_kernel<NSUB, true, ., .>'s structure (strip images go global -> LDS by
 // LDS-DMA into a ring, the activations are split in the kernel, float4 epilogue with bias, K3 addend and segments, row lists,
 // the range flag) with 128-deep K tiles.  Eight waves stacked along M (16 rows each: a 128 x 80 NSUB tile per workgroup) share a
 // ring of two 41 KB images (one workgroup per CU, two waves per SIMD).  The activations do not pass through LDS: a lane's 32
@@ -1564,7 +1485,7 @@ __global__ void __launch_bounds__(512, 1) gemm_f16f8c_kernel(const GemmArgs g) {
 }
 
 // The split format of the strip-mined kernel's operands — 0 = three bf16 pieces, six products (fp32-grade); 1 = two fp16 pieces,
-// three products (gemm_bf16x6s_kernel<., true>) — is a property of the split IMAGE: whoever splits the weights says which
+// three products (gemm_bf16x6s_kernel<., true, ., .>) — is a property of the split IMAGE: whoever splits the weights says which
 // (GemmArgs.format travels with GemmArgs.wsplit; digat_params.flags & DIGAT_PARAMS_GEMM_F16X3 for the encoder's images), there is no
 // process-wide setting.  Every split records its image's format here and every launch checks it, so an image can never be read
 // by the other format's kernel (DIGAT_ERR_ARG).  The training entries split their weights per call, always in format 0:
@@ -1584,21 +1505,6 @@ static int wsplit_format_of(const void* image) {          // -1: not an image th
     const auto it = g_wsplit_format.find(image);
     return it == g_wsplit_format.end() ? -1 : it->second;
 }
-// the fp16-fp8c kernel takes this launch (what gemm_f16f8c_kernel implements; anything else is refused, never sent elsewhere)
-static bool gemm_f16f8c_ok(const GemmArgs& g) {
-    return g.nseg % 80 == 0 && g.K % 4 == 0 && g.k0 == g.K && !g.a1 && !g.transW && !g.a_split && g.lda0 % 4 == 0 &&
-           ((uintptr_t)g.a0 & 15) == 0 && g.ldy % 4 == 0 && g.lde0 % 4 == 0 &&
-           (g.epi == EPI_NONE || g.epi == EPI_RELU_RES || g.epi == EPI_ACCUM || g.epi == EPI_ADD_E0) &&
-           !g.x1_segs && !g.x3_segs && !g.bf16_segs && !g.fp8_segs && !g.dmask;
-}
-// the strip-mined bf16x6 kernel serves this launch (the only kernel that takes a row list; fp16-fp8c: its own kernel)
-static bool gemm_is_bf16x6(const GemmArgs& g) {
-    if (g.format == DIGAT_GEMM_F16F8C) return g.wsplit && gemm_f16f8c_ok(g);        // its own kernel at every row count
-    const int Md = g.m_dispatch > 0 ? g.m_dispatch : g.M;
-    return g.wsplit && Md >= 2048 && g.nseg % 80 == 0 && g.K % 4 == 0 && g.K >= 32 && g.ldy % 4 == 0 && g.lde0 % 4 == 0 &&
-           (g.epi == EPI_NONE || g.epi == EPI_RELU_RES || g.epi == EPI_ACCUM || g.epi == EPI_ADD_E0) && g.k0 == g.K && !g.transW;
-}
-
 // compulsory HBM bytes of a launch per row of A: the row itself, its results (fp32, bf16 or block-scaled e4m3 per segment) and
 // the epilogue's row operands; the weights (a few hundred KB, L2-resident) are not counted
 static double gemm_row_bytes(const GemmArgs& g) {
@@ -1612,105 +1518,12 @@ static double gemm_row_bytes(const GemmArgs& g) {
     return in + out;
 }
 
-// DIGAT_GEMM_F16F8C: gemm_f16f8c_kernel at every row count (no other kernel reads its images)
-static int launch_gemm_f16f8c(GemmArgs g, hipStream_t st, int kind) {
-    if (!g.wsplit || !gemm_f16f8c_ok(g)) return DIGAT_ERR_ARG;
-    const int made_as = wsplit_format_of(g.wsplit);
-    if (made_as >= 0 && made_as != DIGAT_GEMM_F16F8C) return DIGAT_ERR_ARG;       // an image of another format
-    const int Ntot = g.nseg * g.nsegs, strips = Ntot / 80;
-    const bool listed = g.rowidx != nullptr && !g.gather_only;
-    if (listed && g_prof.enabled) {
-        g.exec_rows = g_prof.rows_dev + kind;
-        g_prof.flops_per_row[kind] = 2.0 * (double)Ntot * g.K; g_prof.rows_nominal[kind] += g.M;
-        g_prof.bytes_per_row[kind] = gemm_row_bytes(g);
-    }
-    ProfScope prof(kind, listed ? 0.0 : 2.0 * g.M * (double)Ntot * g.K, st, listed ? 0.0 : (double)g.M * gemm_row_bytes(g));
-    g.mtiles = (g.M + 127) / 128;
-    g.ntiles = strips % 3 == 0 ? strips / 3 : strips;
-    const dim3 grid((unsigned)(((g.mtiles * g.ntiles + 7) / 8) * 8));
-    if (strips % 3 == 0) hipLaunchKernelGGL((gemm_f16f8c_kernel<3>), grid, dim3(512), 0, st, g);
-    else hipLaunchKernelGGL((gemm_f16f8c_kernel<1>), grid, dim3(512), 0, st, g);
-    DIGAT_CHECK_LAUNCH();
-    return DIGAT_OK;
-}
-
+// Every GEMM launch: gemm_plan (digat_gemm_plan.h) decides the kernel, its tiles and grid, and what is refused
 static int launch_gemm(GemmArgs g, hipStream_t st, int kind = DIGAT_KERNEL_LINEAR) {
     if (g.M <= 0) return DIGAT_OK;
-    if (g.format == DIGAT_GEMM_F16F8C) {
-        if (g.wsplit) return launch_gemm_f16f8c(g, st, kind);
-        g.format = DIGAT_GEMM_F16X3;        // no image (d % 80 != 0: nothing was split): the launch runs fp32, as fp16x3's would
-    }
-    if (g.rowidx && !gemm_is_bf16x6(g)) return DIGAT_ERR_ARG;
-    const int Ntot = g.nseg * g.nsegs;
-    const int Md = g.m_dispatch > 0 ? g.m_dispatch : g.M;
-    if (Md < 2048 && g.nseg % 80 == 0 && g.transW && g.nsegs == 1 && g.K % 16 == 0 && g.k0 == g.K && !g.radd && !g.a1) {
-        // the input gradient of a [B,d] linear: the skinny kernel with the weight read as its transpose (16 us on the 32x64
-        // LDS-tiled kernel, 34 launches per training step)
-        ProfScope prof(kind, 2.0 * g.M * (double)Ntot * g.K, st, (double)g.M * gemm_row_bytes(g));
-        g.ntiles = Ntot / 80;
-        if (((g.M + 31) / 32) * g.ntiles >= 480 || g.K >= 800) {
-            g.mtiles = (g.M + 31) / 32;
-            hipLaunchKernelGGL((gemm_skinny_kernel<2, false, true>), dim3(g.mtiles * g.ntiles), dim3(256), 0, st, g);
-        } else {
-            g.mtiles = (g.M + 15) / 16;
-            hipLaunchKernelGGL((gemm_skinny_kernel<1, false, true>), dim3(g.mtiles * g.ntiles), dim3(256), 0, st, g);
-        }
-        DIGAT_CHECK_LAUNCH();
-        return DIGAT_OK;
-    }
-    // up to 2 048 rows (the encoder's [B,d] linears say which kernel they want through m_dispatch: 1 = this one at every row count —
-    // the gate's two-operand launch always does: the tiled split-operand kernel does not take [c_n | pooled], and at 4 096 rows it
-    // fell to the fp32 kernel on 160 workgroups, 88 us against 33 us here)
-    if (Md < 2048 && g.wsplit && g.nseg % 80 == 0 && !g.transW && g.K % 8 == 0 && g.k0 % 8 == 0 && !g.radd && !g.rowidx &&
-        g.ldy % 4 == 0 && g.lda0 % 4 == 0 && (!g.a1 || g.lda1 % 4 == 0) && g.lde0 % 4 == 0 && g.lde1 % 4 == 0 && g.lde2 % 4 == 0 &&
-        (g.epi == EPI_NONE || g.epi == EPI_RELU_RES || g.epi == EPI_GATE || g.epi == EPI_ACCUM)) {
-        // the [B,d] linears of the inference path on the weights' split images (gemm_skinny_split_kernel)
-        if (g.format != 0 && g.format != 1) return DIGAT_ERR_ARG;
-        const int made_as = wsplit_format_of(g.wsplit);
-        if (made_as >= 0 && made_as != g.format) return DIGAT_ERR_ARG;
-        ProfScope prof(kind, 2.0 * g.M * (double)Ntot * g.K, st, (double)g.M * gemm_row_bytes(g));
-        g.ntiles = Ntot / 80;
-        // 32-row tiles (half the weight traffic) once that leaves at least 320 workgroups; the gate's K = 800 launch is faster on
-        // 16-row tiles too (1.014 -> 1.010 ms per step): twice the workgroups for its long per-wave chain of K tiles
-        const bool mt2 = ((g.M + 31) / 32) * g.ntiles >= 320;
-        g.mtiles = mt2 ? (g.M + 31) / 32 : (g.M + 15) / 16;
-        const dim3 grid((unsigned)(g.mtiles * g.ntiles));
-        if (g.format == 1) {
-            if (mt2) hipLaunchKernelGGL((gemm_skinny_split_kernel<2, true>), grid, dim3(256), 0, st, g);
-            else hipLaunchKernelGGL((gemm_skinny_split_kernel<1, true>), grid, dim3(256), 0, st, g);
-        } else {
-            if (mt2) hipLaunchKernelGGL((gemm_skinny_split_kernel<2, false>), grid, dim3(256), 0, st, g);
-            else hipLaunchKernelGGL((gemm_skinny_split_kernel<1, false>), grid, dim3(256), 0, st, g);
-        }
-        DIGAT_CHECK_LAUNCH();
-        return DIGAT_OK;
-    }
-    if (Md < 2048 && g.nseg % 80 == 0 && !g.transW && g.K % 4 == 0 && g.k0 % 16 == 0 && !g.radd) {
-        ProfScope prof(kind, 2.0 * g.M * (double)Ntot * g.K, st, (double)g.M * gemm_row_bytes(g));
-        g.ntiles = Ntot / 80;
-        // 32-row tiles halve the weight traffic from L2 (what these launches wait for) and halve the workgroups: taken when
-        // that still leaves about two per CU, or when K is long (measured: 1024x1200x400 28.6 -> 26.0 us, 1024x400x800
-        // 28.8 -> 25.7 us, 1024x400x400 17.8 -> 18.4 us)
-        if (((g.M + 31) / 32) * g.ntiles >= 480 || g.K >= 800) {
-            g.mtiles = (g.M + 31) / 32;
-            if (g.K & 15) hipLaunchKernelGGL((gemm_skinny_kernel<2, true>), dim3(g.mtiles * g.ntiles), dim3(256), 0, st, g);
-            else hipLaunchKernelGGL((gemm_skinny_kernel<2, false>), dim3(g.mtiles * g.ntiles), dim3(256), 0, st, g);
-        } else {
-            g.mtiles = (g.M + 15) / 16;
-            if (g.K & 15) hipLaunchKernelGGL((gemm_skinny_kernel<1, true>), dim3(g.mtiles * g.ntiles), dim3(256), 0, st, g);
-            else hipLaunchKernelGGL((gemm_skinny_kernel<1, false>), dim3(g.mtiles * g.ntiles), dim3(256), 0, st, g);
-        }
-        DIGAT_CHECK_LAUNCH();
-        return DIGAT_OK;
-    }
-    // tile configuration: 128x80 for the big projections; below 2048 rows 32x64 (most workgroups), or
-    // 64x80 for multi-segment launches whose segments are multiples of 80 columns (d = 400); the small-M
-    // shapes keep two K tiles in flight
-    const int cfg = Md >= 2048 ? 0 : ((g.nsegs > 1 && g.nseg % 80 == 0) ? 1 : 2);
-    const int bn = cfg == 2 ? 64 : 80;
-    if (g.nsegs > 1 && g.nseg % bn != 0) {
-        // a tile must lie inside one weight segment; when the tile width does not divide the segment
-        // (only small test shapes), run the segments one launch each
+    const GemmPlan p = gemm_plan(g, kind);
+    if (p.status) return p.status;
+    if (p.kernel == GEMM_PER_SEGMENT) {
         for (int sgm = 0; sgm < g.nsegs; ++sgm) {
             GemmArgs one = g;
             one.w[0] = g.w[sgm]; one.bias[0] = g.bias[sgm]; one.y[0] = g.y[sgm]; one.nsegs = 1;
@@ -1720,8 +1533,13 @@ static int launch_gemm(GemmArgs g, hipStream_t st, int kind = DIGAT_KERNEL_LINEA
         }
         return DIGAT_OK;
     }
+    if (p.image_format >= 0) {
+        const int made_as = wsplit_format_of(g.wsplit);
+        if (made_as >= 0 && made_as != p.image_format) return DIGAT_ERR_ARG;       // the image was split for another kernel
+    }
     // a row-list launch does the work of its live rows only: the kernel adds that count to a device counter and
     // digat_profile_stop prices it; the launch itself is recorded with zero work
+    const int Ntot = g.nseg * g.nsegs;
     const bool listed = g.rowidx != nullptr && !g.gather_only;
     if (listed && g_prof.enabled) {
         g.exec_rows = g_prof.rows_dev + kind;
@@ -1729,61 +1547,13 @@ static int launch_gemm(GemmArgs g, hipStream_t st, int kind = DIGAT_KERNEL_LINEA
         g_prof.bytes_per_row[kind] = gemm_row_bytes(g);
     }
     ProfScope prof(kind, listed ? 0.0 : 2.0 * g.M * (double)Ntot * g.K, st, listed ? 0.0 : (double)g.M * gemm_row_bytes(g));
-    if (g.wsplit && cfg == 0 && g.nseg % 80 == 0 && g.K % 4 == 0 && g.K >= 32 && g.ldy % 4 == 0 && g.lde0 % 4 == 0 &&
-        (g.epi == EPI_NONE || g.epi == EPI_RELU_RES || g.epi == EPI_ACCUM || g.epi == EPI_ADD_E0) && g.k0 == g.K && !g.transW) {
-        const int strips = Ntot / 80;
-        g.mtiles = (g.M + 127) / 128;
-        if (g.format != 0 && g.format != 1) return DIGAT_ERR_ARG;
-        // a row-list launch addresses its rows as 32-bit byte offsets from the operand's start (the kernel's LDS-DMA pieces)
-        if (g.rowidx && (unsigned long long)g.M * (unsigned long long)g.lda0 * 4ull >= (1ull << 32)) return DIGAT_ERR_SHAPE;
-        const int made_as = wsplit_format_of(g.wsplit);
-        if (made_as >= 0 && made_as != g.format) return DIGAT_ERR_ARG;       // the image was split for the other kernel
-        const bool f16 = g.format == 1;
-        // Launches that leave the chip under-filled at 128-row tiles (a 4 096-row pass's [B,d] linears and news-side projections: 160
-        // workgroups for 256 CUs, each a 13-step latency chain) take 64-row tiles: twice the workgroups, the same chain.
-        const int wg128 = g.mtiles * (strips % 3 == 0 ? strips / 3 : strips);
-        if (f16 && wg128 < 400) {
-            g.ntiles = strips % 3 == 0 ? strips / 3 : strips;
-            g.mtiles = (g.M + 63) / 64;
-            const dim3 grid((unsigned)(((g.mtiles * g.ntiles + 7) / 8) * 8));
-            if (strips % 3 == 0) hipLaunchKernelGGL((gemm_bf16x6s_kernel<3, true, 1>), grid, dim3(256), 0, st, g);
-            else hipLaunchKernelGGL((gemm_bf16x6s_kernel<1, true, 1>), grid, dim3(256), 0, st, g);
-            DIGAT_CHECK_LAUNCH();
-            return DIGAT_OK;
-        }
-        // the same for the bf16x6 launches of a training step's news graph (3 200 rows: 125 workgroups at 128-row tiles; round 6)
-        if (!f16 && wg128 < 400 && !g.rowidx) {
-            g.ntiles = strips % 3 == 0 ? strips / 3 : strips;
-            g.mtiles = (g.M + 63) / 64;
-            const dim3 grid((unsigned)(((g.mtiles * g.ntiles + 7) / 8) * 8));
-            if (strips % 3 == 0) hipLaunchKernelGGL((gemm_bf16x6s_kernel<3, false, 1>), grid, dim3(256), 0, st, g);
-            else hipLaunchKernelGGL((gemm_bf16x6s_kernel<1, false, 1>), grid, dim3(256), 0, st, g);
-            DIGAT_CHECK_LAUNCH();
-            return DIGAT_OK;
-        }
-        if (strips % 3 == 0) {           // 240-column tiles: the operand split is paid once per three strips
-            g.ntiles = strips / 3;
-            const dim3 grid((unsigned)(((g.mtiles * g.ntiles + 7) / 8) * 8));
-            if (f16 && !g.x1_segs && !g.x3_segs && DIGAT_GEMM_FULL) hipLaunchKernelGGL((gemm_bf16x6s_kernel<3, true, 2, false, true>), grid, dim3(256), 0, st, g);
-            else if (f16) hipLaunchKernelGGL((gemm_bf16x6s_kernel<3, true>), grid, dim3(256), 0, st, g);
-            else hipLaunchKernelGGL((gemm_bf16x6s_kernel<3, false>), grid, dim3(256), 0, st, g);
-        } else {
-            g.ntiles = strips;
-            const dim3 grid((unsigned)(((g.mtiles * g.ntiles + 7) / 8) * 8));
-            if (f16) hipLaunchKernelGGL((gemm_bf16x6s_kernel<1, true>), grid, dim3(256), 0, st, g);
-            else hipLaunchKernelGGL((gemm_bf16x6s_kernel<1, false>), grid, dim3(256), 0, st, g);
-        }
-        DIGAT_CHECK_LAUNCH();
-        return DIGAT_OK;
+    g.mtiles = p.mtiles; g.ntiles = p.ntiles;
+    switch (p.kernel) {
+#define DIGAT_GEMM_LAUNCH(id, ...) case GEMM_##id: hipLaunchKernelGGL((__VA_ARGS__), dim3(p.grid), dim3(p.block), 0, st, g); break;
+        DIGAT_GEMM_KERNELS(DIGAT_GEMM_LAUNCH)
+#undef DIGAT_GEMM_LAUNCH
+        default: return DIGAT_ERR_ARG;
     }
-    const int bm = cfg == 0 ? 128 : (cfg == 1 ? 64 : 32);
-    g.mtiles = (g.M + bm - 1) / bm;
-    g.ntiles = (Ntot + bn - 1) / bn;
-    const dim3 grid((unsigned)(((g.mtiles * g.ntiles + 7) / 8) * 8));
-    if (cfg == 0 && kind == DIGAT_KERNEL_PROJ) hipLaunchKernelGGL((gemm_f32_kernel<128, 80, 4, 1, 1, 1>), grid, dim3(256), 0, st, g);
-    else if (cfg == 0) hipLaunchKernelGGL((gemm_f32_kernel<128, 80, 4, 1, 1, 0>), grid, dim3(256), 0, st, g);
-    else if (cfg == 1) hipLaunchKernelGGL((gemm_f32_kernel<64, 80, 4, 1, 2, 0>), grid, dim3(256), 0, st, g);
-    else hipLaunchKernelGGL((gemm_f32_kernel<32, 64, 1, 4, 2, 0>), grid, dim3(256), 0, st, g);
     DIGAT_CHECK_LAUNCH();
     return DIGAT_OK;
 }

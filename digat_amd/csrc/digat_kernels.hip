@@ -292,15 +292,15 @@ static int xattn_core(const float* X, const uint8_t* A, const float* r_given,
     g.radd = r_given; g.radd_seg = 1; g.rows_per_b = n; // P' = K3 + K1: the reference's left-to-right order
     g.x3_segs = o.pq_x3 ? 6 : 0;                        // DIGAT_PROJ_PQ_X3: P and Q (segments 1, 2) with three products
     // DIGAT_PQ_BF16 (pq_mode & 1): P' and Q stored in bf16, read by the wave-per-centre sparse kernel; & 2: one product for them
-    const bool pq16 = (pq_mode & 1) && gemm_is_bf16x6(g) && sparse_mode == DIGAT_XATTN_SPARSE && !alpha_out && n > 16 &&
+    const bool pq16 = (pq_mode & 1) && gemm_takes_row_list(g) && sparse_mode == DIGAT_XATTN_SPARSE && !alpha_out && n > 16 &&
                       d / 4 <= 256 && d % 8 == 0 && (long)B * n >= 2048;
     // DIGAT_PQ_FP8 (pq_mode & 4): P' and Q stored as block-scaled e4m3 rows (one fp32 scale per 80-channel strip), same reader
-    const bool pq8 = (pq_mode & 4) && !(pq_mode & 1) && gemm_is_bf16x6(g) && sparse_mode == DIGAT_XATTN_SPARSE && !alpha_out && n > 16 &&
+    const bool pq8 = (pq_mode & 4) && !(pq_mode & 1) && gemm_takes_row_list(g) && sparse_mode == DIGAT_XATTN_SPARSE && !alpha_out && n > 16 &&
                      d / 4 <= 256 && d % 80 == 0 && (long)B * n >= 2048;
     const long ld8 = (long)align_up((size_t)d + 4 * (size_t)(d / 80), 64);      // [d codes | d / 80 scales | pad]: whole 64-byte lines
     if (pq16) { g.bf16_segs = 6; if (pq_mode & 2) g.x1_segs = 6; }
     if (pq8) { g.fp8_segs = 6; g.ldy8 = ld8; if (pq_mode & 2) g.x1_segs = 6; }
-    const bool listed = rowidx && gemm_is_bf16x6(g);
+    const bool listed = rowidx && gemm_takes_row_list(g);
     if (listed) { g.rowidx = rowidx; g.nrows_dev = nrows_dev; }                         // live rows only (see user_live_flags_kernel)
     const int rc = launch_gemm(g, st, DIGAT_KERNEL_PROJ);
     if (rc) return rc;
@@ -856,7 +856,7 @@ static int encoder_fwd_folded(const EncoderCall& c, const float* Xg0) {
         // ONE launch (digat_ctxfused.inc) when the weight version carries the fused image and the shape fits; T, T2 stay unused then
         if (p->featureAffine_fsplit && fmt == 1 && ctxfused_ok(H, C1, d)) {
             const CtxFusedArgs fa{Xu_cur, (long)U * d, xgroup, live, U, live ? hist_last : nullptr, kq_topic, kq_user, cat_idx, cat_mask, addend, c_u,
-                                  (const uint4*)p->featureAffine_fsplit, p->featureAffine_b, rflag, B, H, C1, d, sqrtf((float)d), 0};
+                                  (const uint4*)p->featureAffine_fsplit, p->featureAffine_b, rflag, B, H, C1, d, sqrtf((float)d)};
             return launch_user_ctx_fused(fa, sq);
         }
         int e = launch_topic(Xu_cur, (long)U * d, kq_topic, cat_idx, T, B, H, C1, d, sq, xgroup, live, U, live ? hist_last : nullptr);
@@ -865,7 +865,7 @@ static int encoder_fwd_folded(const EncoderCall& c, const float* Xg0) {
         g.epi = EPI_RELU_RES; g.e0 = T; g.lde0 = d;
         g.wsplit = (const unsigned short*)p->featureAffine_wsplit;       // non-NULL: split operands on the matrix cores
         g.format = fmt; g.range_flag = rflag;
-        if (bucket_idx && gemm_is_bf16x6(g)) { g.rowidx = bucket_idx; g.nrows_dev = nbuckets_dev; }   // unmasked buckets only
+        if (bucket_idx && gemm_takes_row_list(g)) { g.rowidx = bucket_idx; g.nrows_dev = nbuckets_dev; }   // unmasked buckets only
         e = launch_gemm(g, sq);
         if (e) return e;
         return launch_pool(T2, (long)C1 * d, kq_user, cat_mask, addend, c_u, B, C1, d, sq);
@@ -1026,7 +1026,7 @@ static int encoder_fwd_folded(const EncoderCall& c, const float* Xg0) {
                                        // (digat_news_project0 makes the same launch per news, once)
         gp.wsplit = (const unsigned short*)ln.wsplit;
         gp.format = lfmt; gp.range_flag = rflag;
-        if (news_rowidx && gemm_is_bf16x6(gp)) { gp.rowidx = news_rowidx; gp.nrows_dev = news_nrows; }      // live nodes only (layers >= 1)
+        if (news_rowidx && gemm_takes_row_list(gp)) { gp.rowidx = news_rowidx; gp.nrows_dev = news_nrows; }      // live nodes only (layers >= 1)
         return launch_gemm(gp, sq, DIGAT_KERNEL_PROJ);
     };
     // layer 0 of grouped rows: every row of a group has the same user nodes, so the G groups are projected once
@@ -1046,7 +1046,7 @@ static int encoder_fwd_folded(const EncoderCall& c, const float* Xg0) {
             gs.wsplit = (const unsigned short*)lu.wsplit;
             gs.format = lfmt; gs.range_flag = rflag;
             gs.m_dispatch = B * U;
-            if (want_live && gemm_is_bf16x6(gs)) { gs.rowidx = gl_idx; gs.nrows_dev = gl_off + B; }
+            if (want_live && gemm_takes_row_list(gs)) { gs.rowidx = gl_idx; gs.nrows_dev = gl_off + B; }
             return launch_gemm(gs, sq, DIGAT_KERNEL_PROJ);
         }
         const size_t ndg = (size_t)G * U * d;

@@ -287,7 +287,7 @@ int digat_msa_fwd(const digat_msa_params* p, const int32_t* title_text, const ui
     g.wsplit = (const unsigned short*)p->qkv_wsplit;
     g.rowidx = title_text; g.gather_only = 1;
     int rc;
-    if (gemm_is_bf16x6(g)) {
+    if (gemm_takes_row_list(g)) {
         rc = launch_gemm(g, st, DIGAT_KERNEL_LINEAR);
     } else {                                       // small / odd shapes: materialise the embeddings, then the generic dispatch
         const long total = M * (dm / 4);
@@ -328,7 +328,7 @@ int digat_msa_fwd(const digat_msa_params* p, const int32_t* title_text, const ui
     if (p->a1_wsplit) {
         GemmArgs gx = ga;
         gx.nseg = attp; gx.wsplit = (const unsigned short*)p->a1_wsplit;
-        if (gemm_is_bf16x6(gx)) ga = gx;
+        if (gemm_takes_row_list(gx)) ga = gx;
     }
     rc = launch_gemm(ga, st, DIGAT_KERNEL_LINEAR);
     if (rc) return rc;

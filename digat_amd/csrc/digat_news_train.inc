@@ -604,7 +604,7 @@ int digat_msa_fwd_train(const digat_msa_params* p, const int32_t* title_text, co
         GemmArgs gx = ga;
         gx.nseg = attp; gx.wsplit = (const unsigned short*)a1_split;
         if (g_train_bf16) gx.x1_segs = 7;
-        if (gemm_is_bf16x6(gx)) ga = gx;
+        if (gemm_takes_row_list(gx)) ga = gx;
     }
     T_TRY(launch_gemm(ga, st, DIGAT_KERNEL_LINEAR));
     MsaPoolArgs pa{s.pre, attp, p->b1, p->a2, s.h, title_mask, out, T, Lw, att, hd, s.alpha};
@@ -691,7 +691,7 @@ int digat_msa_bwd(const digat_msa_params* p, const int32_t* title_text, const ui
         GemmArgs gx = gemm_plain(dqkv, 3 * hd, p->W_Q, nullptr, row_grad, ld_row_grad, (int)M, dm, 3 * hd, 0);
         gx.nseg = dmp; gx.wsplit = (const unsigned short*)wcat_split;
         if (g_train_bf16) gx.x1_segs = 7;
-        if (!gemm_is_bf16x6(gx)) return DIGAT_ERR_SHAPE;
+        if (!gemm_takes_row_list(gx)) return DIGAT_ERR_SHAPE;
         const bool mask_here = p_drop > 0.f && dm % 4 == 0;          // round 6: the embedding dropout's backward in this product's epilogue
         if (mask_here) { gx.dmask = s.dmask; gx.lddm = dm; gx.dscale = 1.f / (1.f - p_drop); gx.dmask_cols = dm; }
         T_TRY(launch_gemm(gx, st, DIGAT_KERNEL_LINEAR));

@@ -1560,7 +1560,7 @@ int digat_topic_pool_fwd_train(const float* Xu, const float* kq, const int64_t* 
                                int B, int U, int H, int C1, int d, void* stream) {
     if (!Xu || !kq || !cat_idx || !out || !alpha_out) return DIGAT_ERR_ARG;
     if (B == 0) return DIGAT_OK;
-    TopicArgs g{Xu, (long)U * d, kq, cat_idx, out, B, H, C1, d, sqrtf((float)d), alpha_out, 0};
+    TopicArgs g{Xu, (long)U * d, kq, cat_idx, out, B, H, C1, d, sqrtf((float)d), alpha_out};
     return launch_topic_args(g, (hipStream_t)stream);
 }
 // the same launch, also zero-filling the topic rows of dXu (digat_user_ctx_bwd: one 34 MB memset launch per call less)

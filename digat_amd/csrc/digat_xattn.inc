@@ -49,7 +49,6 @@ struct ScoreArgs {
     int ld_off;        // byte offset of the per-node linear terms a.P'_j, a.Q_i (2 * RB * 4*NT floats)
     int pm_off;        // byte offset of the node permutation: keys [RB*n] ints, then node_of [RB*n] ints
     const int* skip_if;    // optional device int: the launch returns at once when *skip_if != 0 (the sparse kernel does this batch)
-    int skip;          // always 0 (a removed timing ablation's switch): 1 no score loop, 8 no softmax, 16 no empty-tile skipping
     // training (round 6): the attention dropout is applied where alpha is produced (amask != NULL): keep bytes [B,n,n] by the
     // counter hash of (drop_seed, flat index), alpha itself stays undropped for the backward, adrop (tile kernel; the small-graph
     // kernel aggregates from registers) receives drop_p(alpha)
@@ -112,11 +111,9 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(5, 8)
     for (int e = tid; e < rows_here * n; e += nthreads) {
         const int rb = e / n, i = e - rb * n;
         int key = g.live ? n + i : i;        // rows without any bit (dead nodes, when a list is given) go last, together
-        if (!(g.skip & 16)) {
-            for (int w = 0; w < NW; ++w) {
-                const unsigned bits = Ab[e * NW + w];
-                if (bits) { key = w * 32 + __ffs(bits) - 1; break; }
-            }
+        for (int w = 0; w < NW; ++w) {
+            const unsigned bits = Ab[e * NW + w];
+            if (bits) { key = w * 32 + __ffs(bits) - 1; break; }
         }
         keys[e] = key;
     }
@@ -184,17 +181,13 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(5, 8)
         if (t < rows_here * tiles) {
             const int rb = t / tiles, tt = t - rb * tiles;
             const int ti = tt / NT, tj = tt - ti * NT;
-            if (g.skip & 16) {
-                flag = true;
-            } else {
 #pragma unroll
-                for (int ii = 0; ii < 4; ++ii) {
-                    const int si = 4 * ti + ii;
+            for (int ii = 0; ii < 4; ++ii) {
+                const int si = 4 * ti + ii;
 #pragma unroll
-                    for (int jj = 0; jj < 4; ++jj) {
-                        const int sj = 4 * tj + jj;
-                        if (si < n && sj < n && edge(rb, node_of[rb * n + si], node_of[rb * n + sj])) flag = true;
-                    }
+                for (int jj = 0; jj < 4; ++jj) {
+                    const int sj = 4 * tj + jj;
+                    if (si < n && sj < n && edge(rb, node_of[rb * n + si], node_of[rb * n + sj])) flag = true;
                 }
             }
         }
@@ -232,7 +225,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(5, 8)
         // ... and every wave has said so: the barrier publishes chunk ch and retires chunk ch-1's readers
         __builtin_amdgcn_s_barrier();
         if (ch + 2 < g.nchunks) issue(ch + 2, (ch + 2) % XA_RING);      // into the image read in iteration ch-1
-        if (active && !(g.skip & 1)) {
+        if (active) {
             const float4* Pb = ring + (ch % XA_RING) * g.ring_slots + rb_t * 4 * NT * CC4;
             const float4* Qb = Pb + g.img_slots;
             const float4* av = a_lds + ch * CC4;
@@ -295,7 +288,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(5, 8)
 
     // ---- phase 2b: softmax over the neighbours j, one wave per (row, centre i); a row without any
     // edge is all -1e9 and comes out uniform, as in the reference
-    for (int rho = wave; rho < ((g.skip & 8) ? 0 : rows_here * n); rho += nwaves) {
+    for (int rho = wave; rho < rows_here * n; rho += nwaves) {
         if (g.live && !g.live[(long)b0 * n + rho]) continue;           // dead centre: its alpha row keeps its (finite) old values
         const float* srow = Ss + (long)rho * SN;
         const float v0 = lane < n ? srow[lane] : -INFINITY;
@@ -582,8 +575,6 @@ struct SparseArgs {
     long ld8;                                    // pq16 == 2: bytes between rows ([d codes | d / 80 fp32 scales | pad]: the GEMM's fp8 segments)
     const unsigned* twin; const int* twlist; const int* twcount;   // optional, with rowidx: centres with EQUAL adjacency rows served together
                                                  // (user_live_flags_kernel's twin words [B n], the list of the leading centres, their count)
-    unsigned char* xsplit;                       // unused, always NULL (the removed pre-split store of the output rows: docs/REJECTED.md row 4q)
-    unsigned* xsplit_range;                      // unused, always NULL
     unsigned exec_unit;                          // with exec_rows: algorithmic bytes per live centre of the list (0: a counting kernel prices the launch)
     int prof_part;                               // profiling: 0 = the part follows from the arguments (sparse_part), else XPART_* + 1 (the news graph's row-list launches)
     // training (xattn_sparse_kernel<., 0, false, true>; round 6): what the backward needs leaves the wave — the centre's alpha row
