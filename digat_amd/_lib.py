@@ -40,6 +40,12 @@ class MsaParams(C.Structure):
                                              "qkv_wsplit", "a1_wsplit")])
 
 
+class CnnParams(C.Structure):
+    """digat_cnn_params (include/digat_hip.h)."""
+    _fields_ = ([(k, C.c_int32) for k in ("word_embedding_dim", "kernel_num", "taps", "attention_dim")]
+                + [(k, C.c_void_p) for k in ("word_embedding", "W", "b", "A1", "b1", "a2", "w_split", "a1_wsplit")])
+
+
 class SplitJob(C.Structure):
     """digat_split_job (include/digat_hip.h)."""
     _fields_ = [("w0", C.c_void_p), ("w1", C.c_void_p), ("w2", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32), ("layout", C.c_int32),
@@ -113,6 +119,17 @@ _SIGNATURES = {
     "digat_msa_bwd": (C.c_int, [C.POINTER(MsaParams), _f, _f, _f, C.c_float, _f, C.c_size_t, _f, C.c_int64] + [_f] * 8
                       + [C.c_int, C.c_int, _f, C.c_size_t, _f]),
     "digat_msa_row_grad_ld": (C.c_int64, [C.c_int] * 3),
+    "digat_cnn_split_bytes": (C.c_size_t, [C.c_int] * 3),
+    "digat_split_cnn_weights": (C.c_int, [_f] + [C.c_int] * 3 + [_f, _f]),
+    "digat_cnn_merge_group3": (C.c_int, [_f] * 6 + [C.c_int] * 2 + [_f] * 3),
+    "digat_cnn_workspace_bytes": (C.c_size_t, [C.c_int] * 6),
+    "digat_cnn_fwd": (C.c_int, [C.POINTER(CnnParams), _f, _f, _f, C.c_int, C.c_int, _f, C.c_size_t, _f]),
+    "digat_cnn_train_save_bytes": (C.c_size_t, [C.c_int] * 6),
+    "digat_cnn_train_workspace_bytes": (C.c_size_t, [C.c_int] * 6),
+    "digat_cnn_fwd_train": (C.c_int, [C.POINTER(CnnParams), _f, _f, _f, C.c_float, C.c_uint32, C.c_int, C.c_int, _f, C.c_size_t, _f,
+                                      C.c_size_t, _f]),
+    "digat_cnn_bwd": (C.c_int, [C.POINTER(CnnParams), _f, _f, _f, C.c_float, C.c_uint32, _f, C.c_size_t, _f, C.c_int64] + [_f] * 5
+                      + [C.c_int, C.c_int, _f, C.c_size_t, _f]),
     "digat_embedding_bwd_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "digat_embedding_bwd": (C.c_int, [_f, C.c_int64, _f, _f, C.c_int64, C.c_int, _f, _f, C.c_size_t, _f]),
     "digat_embedding_bwd_unsorted_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int64]),

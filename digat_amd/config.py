@@ -43,6 +43,14 @@ class Config:
         p.add_argument('--SAG_hops', type=int, default=2)
         p.add_argument('--SAG_neighbors', type=int, default=5)
         p.add_argument('--news_embedding_dim', type=int, default=400, help='MSA: 16 heads x 25')
+        p.add_argument('--word_embedding_dim', type=int, default=300)
+        p.add_argument('--cnn_method', default='naive', choices=['naive', 'group3', 'group4', 'group5'],
+                       help='naive and group3 run; the others are refused by the encoder as the reference itself fails on them')
+        p.add_argument('--cnn_kernel_num', type=int, default=400)
+        p.add_argument('--cnn_window_size', type=int, default=3)
+        p.add_argument('--attention_dim', type=int, default=256)
+        p.add_argument('--MSA_head_num', type=int, default=16)
+        p.add_argument('--MSA_head_dim', type=int, default=25)
         p.add_argument('--synthetic_news', type=int, default=8192)
         p.add_argument('--synthetic_impressions', type=int, default=2048)
         p.add_argument('--max_steps', type=int, default=0, help='stop training after this many steps (0 = all epochs)')

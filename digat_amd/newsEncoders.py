@@ -1,11 +1,12 @@
 """News encoders: UPSTREAM of the hot path.  ``MSA`` on the GPU runs on the HIP kernels: inference on
 ``digat_msa_fwd`` (``csrc/digat_news.inc``), training forward / backward on ``digat_msa_fwd_train`` / ``digat_msa_bwd``
-(``csrc/digat_news_train.inc``); on the CPU (tests without a GPU) and for ``CNN`` the stock PyTorch modules below.
+(``csrc/digat_news_train.inc``); ``CNN`` likewise on ``digat_cnn_fwd`` / ``digat_cnn_fwd_train`` / ``digat_cnn_bwd``
+(``csrc/digat_cnn.inc``); on the CPU (tests without a GPU) the stock PyTorch modules below.
 
 Their output ``[., news_embedding_dim]`` is the graph encoder's input.  They are restated here
 so that ``Model.forward`` (training) and the news-representation cache of ``compute_scores``
 have a producer with the reference's parameter names (``word_embedding``, ``multiheadSelfattention.
-W_{K,Q,V}``, ``attention.affine{1,2}``, ``conv.conv``) and the same semantics:
+W_{K,Q,V}``, ``attention.affine{1,2}``, ``conv.conv`` / ``conv.conv{1,2,3}``) and the same semantics:
 word embedding -> dropout -> MSA (16 heads x 25) + ReLU | Conv1d + ReLU -> additive tanh attention.
 GloVe initialisation needs the downloaded vectors; without them the table keeps its random init.
 """
@@ -61,16 +62,147 @@ class Attention(nn.Module):
         return (F.softmax(a, dim=1).unsqueeze(1) @ feature).squeeze(1)
 
 
-class _Conv(nn.Module):
-    def __init__(self, in_channels, kernels, window):
+class Conv1D(nn.Module):
+    """layers.py:7-47 with the reference's parameter names: ``naive`` (``conv``: one window, odd, 1..7) and ``group3``
+    (``conv1/2/3``: windows 1, 3, 5 on a third of the kernels each, concatenated along channels before the ReLU).  The reference's
+    ``group5`` raises inside its forward (layers.py:41-46: ``torch.cat(..., dim=1)`` of a length-1 tensor), ``group4`` fails its
+    constructor's assert (layers.py:10) and an even window yields Lw - 1 positions, which the attention's mask rejects: all three
+    raise here, at construction."""
+
+    def __init__(self, cnn_method: str, in_channels: int, cnn_kernel_num: int, cnn_window_size: int):
         super().__init__()
-        self.conv = nn.Conv1d(in_channels, kernels, kernel_size=window, padding=(window - 1) // 2)
+        if cnn_method not in ('naive', 'group3'):
+            raise ValueError(f"cnn_method {cnn_method!r} is not supported: the reference's group5 fails in its forward "
+                             "(layers.py:41-46) and anything else fails its constructor's assert (layers.py:10); use naive or group3")
+        self.cnn_method, self.in_channels, self.cnn_kernel_num = cnn_method, in_channels, cnn_kernel_num
+        if cnn_method == 'naive':
+            if cnn_window_size % 2 == 0 or not 1 <= cnn_window_size <= 7:
+                raise ValueError(f"cnn_window_size {cnn_window_size}: an even window gives Lw - 1 positions (layers.py:14: padding "
+                                 "(w - 1) // 2), which the attention's mask rejects; odd windows 1..7 are supported")
+            self.taps = cnn_window_size
+            self.conv = nn.Conv1d(in_channels, cnn_kernel_num, kernel_size=cnn_window_size, padding=(cnn_window_size - 1) // 2)
+        else:
+            if cnn_kernel_num % 3:
+                raise ValueError(f"group3 needs cnn_kernel_num % 3 == 0 (layers.py:16), got {cnn_kernel_num}")
+            self.taps = 5
+            self.conv1 = nn.Conv1d(in_channels, cnn_kernel_num // 3, kernel_size=1, padding=0)
+            self.conv2 = nn.Conv1d(in_channels, cnn_kernel_num // 3, kernel_size=3, padding=1)
+            self.conv3 = nn.Conv1d(in_channels, cnn_kernel_num // 3, kernel_size=5, padding=2)
 
     def initialize(self):
         pass
 
+    def branches(self):
+        return (self.conv,) if self.cnn_method == 'naive' else (self.conv1, self.conv2, self.conv3)
+
     def forward(self, x):
-        return F.relu(self.conv(x))
+        if self.cnn_method == 'naive':
+            return F.relu(self.conv(x))
+        return F.relu(torch.cat([self.conv1(x), self.conv2(x), self.conv3(x)], dim=1))
+
+
+def merge_group3(w1, w2, w3):
+    """The three branch weights [K3, dm, {1,3,5}] as one zero-filled 5-tap weight [3 K3, dm, 5] (same convolution: the extra
+    products are x * 0)."""
+    K3, dm = w1.shape[0], w1.shape[1]
+    W = w1.new_zeros((3 * K3, dm, 5))
+    W[:K3, :, 2:3] = w1
+    W[K3:2 * K3, :, 1:4] = w2
+    W[2 * K3:] = w3
+    return W
+
+
+class CnnFused(torch.autograd.Function):
+    """The CNN news encoder as one library call per direction (``digat_cnn_fwd_train`` / ``digat_cnn_bwd``, then
+    ``digat_embedding_bwd`` for the word-embedding rows).  ``conv`` is (W, b) for ``naive`` or (W1, b1, W2, b2, W3, b3) for ``group3``:
+    the latter run as the zero-filled 5-tap convolution and each branch's gradient is cut from its own taps."""
+
+    @staticmethod
+    def _merged(conv, dev):
+        """(W [Kc, dm, taps], b [Kc]) fp32 contiguous."""
+        from . import _lib
+        c = [w.detach().float().contiguous() for w in conv]
+        if len(c) == 2:
+            return c[0], c[1]
+        K3, dm = c[0].shape[0], c[0].shape[1]
+        W = torch.empty((3 * K3, dm, 5), dtype=torch.float32, device=dev)
+        b = torch.empty(3 * K3, dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib().digat_cnn_merge_group3(*(t.data_ptr() for t in c), dm, 3 * K3, W.data_ptr(), b.data_ptr(), _lib.stream_ptr()),
+                   "digat_cnn_merge_group3")
+        return W, b
+
+    @staticmethod
+    def _params(table, W, b, A1, b1, a2):
+        from . import _lib
+        P = _lib.CnnParams(word_embedding_dim=table.shape[1], kernel_num=W.shape[0], taps=W.shape[2], attention_dim=A1.shape[0])
+        for name, w in zip(("word_embedding", "W", "b", "A1", "b1", "a2"), (table, W, b, A1, b1, a2)):
+            setattr(P, name, w.data_ptr())
+        return P
+
+    @staticmethod
+    def forward(ctx, tokens, mask, table, A1, b1, a2, p_drop, *conv):
+        from . import _lib
+        L = _lib.lib()
+        table_, A1_, b1_, a2_ = (w.detach().float().contiguous() for w in (table, A1, b1, a2))
+        dev = _lib.require_device(tokens, mask, table_, A1_, b1_, a2_, *conv)
+        W, b = CnnFused._merged(conv, dev)
+        T, Lw = tokens.shape
+        dm, Kc, taps, att = table_.shape[1], W.shape[0], W.shape[2], A1_.shape[0]
+        P = CnnFused._params(table_, W, b, A1_, b1_, a2_)
+        out = torch.empty((T, Kc), dtype=torch.float32, device=dev)
+        nsave = L.digat_cnn_train_save_bytes(T, Lw, dm, Kc, taps, att)
+        nws = L.digat_cnn_train_workspace_bytes(T, Lw, dm, Kc, taps, att)
+        save = torch.empty(max(int(nsave), 256), dtype=torch.uint8, device=dev)
+        ws = _lib.workspace(nws, dev, "cnn_train")
+        p = float(p_drop)
+        seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if p > 0 else 0
+        if T:
+            _lib.check(L.digat_cnn_fwd_train(P, tokens.data_ptr(), mask.data_ptr(), out.data_ptr(), p, seed, T, Lw, save.data_ptr(), nsave,
+                                             ws.data_ptr(), nws, _lib.stream_ptr()), "digat_cnn_fwd_train")
+        ctx.save_for_backward(tokens, mask, save, table_, W, b, A1_, b1_, a2_)
+        ctx.p, ctx.seed, ctx.sizes, ctx.group3, ctx.a2_shape = p, seed, (nsave, nws), len(conv) == 6, a2.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from . import _lib
+        L = _lib.lib()
+        tokens, mask, save, table, W, b, A1, b1, a2 = ctx.saved_tensors
+        T, Lw = tokens.shape
+        dm, Kc, taps, att = table.shape[1], W.shape[0], W.shape[2], A1.shape[0]
+        dev = tokens.device
+        f = dict(dtype=torch.float32, device=dev)
+
+        def conv_grads(dW, db):
+            if not ctx.group3:
+                return dW, db
+            K3 = Kc // 3                              # each branch from its own taps only
+            return (dW[:K3, :, 2:3].contiguous(), db[:K3].contiguous(), dW[K3:2 * K3, :, 1:4].contiguous(), db[K3:2 * K3].contiguous(),
+                    dW[2 * K3:].contiguous(), db[2 * K3:].contiguous())
+        if T == 0:                                    # no title: every gradient is zero
+            return (None, None, torch.zeros_like(table) if ctx.needs_input_grad[2] else None, torch.zeros_like(A1), torch.zeros_like(b1),
+                    torch.zeros(ctx.a2_shape, **f), None, *conv_grads(torch.zeros_like(W), torch.zeros_like(b)))
+        dout = dout.float().contiguous()
+        P = CnnFused._params(table, W, b, A1, b1, a2)
+        nsave, nws = ctx.sizes
+        ws = _lib.workspace(nws, dev, "cnn_train")
+        row_grad = torch.empty((T * Lw, dm), **f)
+        dW, db = torch.empty_like(W), torch.empty_like(b)
+        dA1, db1, da2 = torch.empty((att, Kc), **f), torch.empty(att, **f), torch.empty(att, **f)
+        _lib.check(L.digat_cnn_bwd(P, tokens.data_ptr(), mask.data_ptr(), dout.data_ptr(), ctx.p, ctx.seed, save.data_ptr(), nsave,
+                                   row_grad.data_ptr(), dm, dW.data_ptr(), db.data_ptr(), dA1.data_ptr(), db1.data_ptr(), da2.data_ptr(),
+                                   T, Lw, ws.data_ptr(), nws, _lib.stream_ptr()), "digat_cnn_bwd")
+        dtable = None
+        if ctx.needs_input_grad[2]:
+            # index plumbing only: the rows in token order (stable); the sums run in the library, in that fixed order
+            stok, order = torch.sort(tokens.reshape(-1).to(torch.int64), stable=True)
+            stok, order = stok.to(torch.int32), order.to(torch.int32)
+            dtable = torch.zeros_like(table)
+            nb = L.digat_embedding_bwd_workspace_bytes(T * Lw, dm)
+            ews = _lib.workspace(nb, dev, "emb_bwd")
+            _lib.check(L.digat_embedding_bwd(row_grad.data_ptr(), dm, order.data_ptr(), stok.data_ptr(), T * Lw, dm, dtable.data_ptr(),
+                                             ews.data_ptr(), nb, _lib.stream_ptr()), "digat_embedding_bwd")
+        return (None, None, dtable, dA1, db1, da2.view(ctx.a2_shape), None, *conv_grads(dW, db))
 
 
 class MsaFused(torch.autograd.Function):
@@ -259,18 +391,95 @@ class MSA(NewsEncoder):
 
 
 class CNN(NewsEncoder):
-    """newsEncoders.py:30-54 with the 'naive' Conv1D (layers.py:13-14)."""
+    """newsEncoders.py:29-54 with layers.Conv1D (``naive`` or ``group3``)."""
 
     def __init__(self, config):
         super().__init__(config)
-        self.conv = _Conv(config.word_embedding_dim, config.cnn_kernel_num, config.cnn_window_size)
+        self.conv = Conv1D(getattr(config, 'cnn_method', 'naive'), config.word_embedding_dim, config.cnn_kernel_num, config.cnn_window_size)
         self.news_embedding_dim = config.cnn_kernel_num
         self.attention = Attention(self.news_embedding_dim, config.attention_dim)
 
     def initialize(self):
+        self.conv.initialize()
         self.attention.initialize()
 
+    def _hip_shape_ok(self, training: bool) -> bool:
+        """What the library takes (include/digat_hip.h): float4 rows everywhere; group3 additionally whole float4 rows per branch."""
+        ok = self.word_embedding_dim % 4 == 0 and self.news_embedding_dim % (12 if self.conv.cnn_method == 'group3' else 4) == 0
+        return ok and (not training or self.attention.affine1.out_features % 4 == 0)
+
     def forward(self, title_text, title_mask):
+        if title_text.is_cuda and not torch.is_grad_enabled() and self._hip_shape_ok(False) and title_text.shape[-1] <= 64:
+            if not self.training or self.dropout.p == 0:
+                return self.encode_hip(title_text, title_mask)  # inference: the HIP kernels (digat_cnn_fwd)
+        if title_text.is_cuda and torch.is_grad_enabled() and title_text.shape[-1] <= 32 and self._hip_shape_ok(True):
+            return self.train_hip(title_text, title_mask)       # training: digat_cnn_fwd_train / digat_cnn_bwd
+        return self.forward_stock(title_text, title_mask)       # CPU (tests without a GPU)
+
+    def forward_stock(self, title_text, title_mask):
+        """The same function on stock PyTorch modules (CPU runs; the yardstick of tools/kbench.py cnn / cnn-train)."""
         w, B, n = self._words(title_text)
         h = self.dropout(self.conv(w.permute(0, 2, 1)).permute(0, 2, 1))
         return self.attention(h, mask=title_mask.view(B * n, -1)).view(B, n, self.news_embedding_dim)
+
+    def _conv_tensors(self):
+        out = []
+        for c in self.conv.branches():
+            out += [c.weight, c.bias]
+        return out
+
+    def train_hip(self, title_text, title_mask):
+        """Forward with autograd through the HIP pair (both dropouts of newsEncoders.py:46-48 live in train mode)."""
+        shape = title_text.shape
+        Lw = shape[-1]
+        att = self.attention
+        out = CnnFused.apply(title_text.reshape(-1, Lw).to(torch.int32).contiguous(),
+                             (title_mask.reshape(-1, Lw) != 0).to(torch.uint8).contiguous(),
+                             self.word_embedding.weight, att.affine1.weight, att.affine1.bias, att.affine2.weight,
+                             float(self.dropout.p) if self.training else 0.0, *self._conv_tensors())
+        return out.view(*shape[:-1], self.news_embedding_dim)
+
+    # ---- inference on the HIP kernels (digat_cnn.inc)
+    def _hip_params(self):
+        from . import _lib
+        att = self.attention
+        ws = [self.word_embedding.weight, att.affine1.weight, att.affine1.bias, att.affine2.weight] + self._conv_tensors()
+        key = tuple((w.data_ptr(), w._version) for w in ws)
+        cached = getattr(self, "_hip_cache", None)
+        if cached is not None and cached[0] == key:
+            return cached[1]
+        L = _lib.lib()
+        dev = ws[0].device
+        table, A1, b1, a2 = (w.detach().float().contiguous() for w in ws[:4])
+        W, b = CnnFused._merged(ws[4:], dev)
+        P = CnnFused._params(table, W, b, A1, b1, a2)
+        keep = [table, A1, b1, a2, W, b]
+        dm, Kc, taps, natt = table.shape[1], W.shape[0], W.shape[2], A1.shape[0]
+        if dm % 4 == 0 and dm >= 32 and Kc % 4 == 0:            # the bf16x6 matrix-core path (fp32-grade)
+            img = torch.empty(int(L.digat_cnn_split_bytes(dm, Kc, taps)), dtype=torch.uint8, device=dev)
+            _lib.check(L.digat_split_cnn_weights(W.data_ptr(), dm, Kc, taps, img.data_ptr(), _lib.stream_ptr()), "digat_split_cnn_weights")
+            a1 = _lib.split_buffer(L.digat_split_weights_bytes(natt, Kc), dev)
+            _lib.check(L.digat_split_weights(A1.data_ptr(), natt, Kc, a1.data_ptr(), _lib.GEMM_BF16X6, _lib.stream_ptr()), "digat_split_weights")
+            P.w_split, P.a1_wsplit = img.data_ptr(), a1.data_ptr()
+            keep += [img, a1]
+        self._hip_cache = (key, (P, keep))
+        return P, keep
+
+    def encode_hip(self, title_text, title_mask):
+        """title_text / title_mask [B, n, Lw] (or [T, Lw]) on the GPU -> [B, n, news_embedding_dim] ([T, ...])."""
+        from . import _lib
+        shape = title_text.shape
+        Lw = shape[-1]
+        tok = title_text.reshape(-1, Lw).to(torch.int32).contiguous()
+        msk = (title_mask.reshape(-1, Lw) != 0).to(torch.uint8).contiguous()
+        dev = _lib.require_device(tok, msk)
+        T = tok.shape[0]
+        P, _keep = self._hip_params()
+        out = torch.empty((T, self.news_embedding_dim), dtype=torch.float32, device=dev)
+        if T:
+            L = _lib.lib()
+            nbytes = L.digat_cnn_workspace_bytes(T, Lw, P.word_embedding_dim, P.kernel_num, P.taps, P.attention_dim)
+            ws = _lib.workspace(nbytes, dev, "cnn")
+            _lib.check(L.digat_cnn_fwd(P, tok.data_ptr(), msk.data_ptr(), out.data_ptr(), T, Lw, ws.data_ptr(), nbytes, _lib.stream_ptr()),
+                       "digat_cnn_fwd")
+        return out.view(*shape[:-1], self.news_embedding_dim)

@@ -629,6 +629,44 @@ int digat_embedding_bwd_unsorted(const int64_t* ids0, const float* g0, int64_t l
                                  int64_t ld1, int64_t M1, int dm, int64_t V, float* table_grad, void* workspace, size_t workspace_bytes,
                                  void* stream);
 
+/* ---- CNN news encoder (newsEncoders.py:29-54, layers.Conv1D :7-47, layers.Attention :91-115) ---------------------------------
+ * out[t] = attention_pool(dropout_2(relu(conv1d(dropout_1(word_embedding[title_text[t]])) + b))): the convolution zero-pads
+ * (taps - 1) / 2 positions at both ends of each title; padding tokens are looked up like any other.  taps odd, 1..7; `group3`
+ * (windows 1, 3, 5 on a third of the kernels each) is the 5-tap convolution whose weights are zero where a branch has no tap:
+ * digat_cnn_merge_group3 builds W [Kc][dm][5] and b [Kc] from the three branches.  word_embedding_dim % 4 == 0, kernel_num % 4 == 0,
+ * Lw <= 64 (inference), <= 32 and attention_dim % 4 == 0 (training).
+ * w_split: digat_split_cnn_weights output (digat_cnn_split_bytes bytes) — the matrix-core kernel's bf16x6 weight image; NULL, fewer
+ * than 2 048 token rows or Lw < 16: a plain fp32 kernel of the same semantics.  a1_wsplit as in digat_msa_params. */
+typedef struct digat_cnn_params {
+    int32_t word_embedding_dim, kernel_num, taps, attention_dim;
+    const float *word_embedding;                 /* word_embedding.weight [V, word_embedding_dim]            */
+    const float *W, *b;                          /* conv weight [kernel_num][word_embedding_dim][taps] (torch's Conv1d layout), bias */
+    const float *A1, *b1, *a2;                   /* attention.affine1.{weight,bias}, attention.affine2.weight */
+    const void  *w_split;                        /* digat_split_cnn_weights output, or NULL                   */
+    const void  *a1_wsplit;                      /* digat_split_weights(affine1.weight, attention_dim, kernel_num) output, or NULL */
+} digat_cnn_params;
+size_t digat_cnn_split_bytes(int word_embedding_dim, int kernel_num, int taps);
+int digat_split_cnn_weights(const float* W, int word_embedding_dim, int kernel_num, int taps, void* w_split, void* stream);
+int digat_cnn_merge_group3(const float* W1, const float* b1, const float* W2, const float* b2, const float* W3, const float* b3,
+                           int word_embedding_dim, int kernel_num, float* W, float* b, void* stream);
+size_t digat_cnn_workspace_bytes(int T, int Lw, int word_embedding_dim, int kernel_num, int taps, int attention_dim);
+int digat_cnn_fwd(const digat_cnn_params* params, const int32_t* title_text, const uint8_t* title_mask, float* out, int T, int Lw,
+                  void* workspace, size_t workspace_bytes, void* stream);
+/* Training, one call per direction.  p_drop is the rate of both dropouts; their keep bits come from the library's counter hash: site 1
+ * (embedded tokens) of `seed` over the [T*Lw, word_embedding_dim] elements, site 2 (after the ReLU) of `seed + 1` over the
+ * [T*Lw, kernel_num] elements.  `save` carries h (after site 2), the affine1 product and the pooling weights; the backward regenerates
+ * site 1's bits.  The *_split fields of params are ignored (the weights are split inside, into the workspace).
+ * digat_cnn_bwd writes (does not accumulate) row_grad [T*Lw, word_embedding_dim], rows ld_row_grad floats apart (>= word_embedding_dim,
+ * a multiple of 4) — feed it to digat_embedding_bwd — and dW [kernel_num][word_embedding_dim][taps], db [kernel_num],
+ * dA1 [attention_dim, kernel_num], db1 da2 [attention_dim]. */
+size_t digat_cnn_train_save_bytes(int T, int Lw, int word_embedding_dim, int kernel_num, int taps, int attention_dim);
+size_t digat_cnn_train_workspace_bytes(int T, int Lw, int word_embedding_dim, int kernel_num, int taps, int attention_dim);
+int digat_cnn_fwd_train(const digat_cnn_params* params, const int32_t* title_text, const uint8_t* title_mask, float* out, float p_drop,
+                        uint32_t seed, int T, int Lw, void* save, size_t save_bytes, void* workspace, size_t workspace_bytes, void* stream);
+int digat_cnn_bwd(const digat_cnn_params* params, const int32_t* title_text, const uint8_t* title_mask, const float* dout, float p_drop,
+                  uint32_t seed, const void* save, size_t save_bytes, float* row_grad, int64_t ld_row_grad, float* dW, float* db, float* dA1,
+                  float* db1, float* da2, int T, int Lw, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- runs of identical consecutive user rows (drop-in path) -------------------------------------------------------------------
  * The reference's driver hands Model.inference the user tensors EXPANDED per row — an impression's history embeddings, user graph,
  * category mask and indices repeated once per candidate (util.py:57-67, model.py:87-90) — so consecutive rows are bit-identical

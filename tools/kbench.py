@@ -6,6 +6,9 @@
   python tools/kbench.py encoder             whole DIGAT.inference, per-kernel-kind breakdown
   python tools/kbench.py gemm [M N K]        Eq. 8 projection GEMM in fp16x3 and fp16-fp8c (137 k x 1 200 x 400: the bench's
                                              live rows), alternated; then 4 096-row scoring passes (inference_grouped) in each mode
+  python tools/kbench.py cnn [T Lw V dm Kc att window]        CNN news encoder, inference: HIP vs forward_stock on the same device,
+                                             alternated, the spread of the rounds' medians reported (default T = 8 192 and 65 238)
+  python tools/kbench.py cnn-train [T ...]   one CNN training step (forward + backward, dropout 0.2), the same way (T = 6 400)
 Timing with torch events on the current stream, median of --iters launches.
 """
 import os
@@ -283,6 +286,70 @@ def bench_msa_train(T=6400, Lw=32, V=30000, dm=300, h=16, dk=25, att=256):
     print("   library kernel ms by kind (proj, linear, xattn, pool, topic, glue, agg):", [round(v, 3) for v in ms], list(cn))
 
 
+def alternate(fa, fb, rounds=5, iters=5):
+    """Medians of ``rounds`` timing rounds of fa and fb, taken in turn (ABAB...): ((median, min, max) of fa's rounds, the same of fb's)."""
+    ma, mb = [], []
+    for _ in range(rounds):
+        ma.append(timeit(fa, iters=iters, warm=1)[0])
+        mb.append(timeit(fb, iters=iters, warm=1)[0])
+    stat = lambda v: (sorted(v)[len(v) // 2], min(v), max(v))
+    return stat(ma), stat(mb)
+
+
+def _cnn_encoder(T, Lw, V, dm, Kc, att, window):
+    import types
+    from digat_amd import newsEncoders, synthetic
+    dev = torch.device("cuda:0")
+    state = synthetic.make_cnn_state(V, dm, Kc, att, "naive", window, seed=1)
+    text, mask = synthetic.make_titles(T, Lw, V, seed=2)
+    cfg = types.SimpleNamespace(vocabulary_size=V, word_embedding_dim=dm, max_title_length=Lw, dropout_rate=0.2, cnn_method="naive",
+                                cnn_kernel_num=Kc, cnn_window_size=window, attention_dim=att)
+    enc = newsEncoders.CNN(cfg)
+    enc.load_state_dict({k_: torch.from_numpy(v) for k_, v in state.items()})
+    return enc.to(dev), torch.from_numpy(text).to(dev).unsqueeze(0), torch.from_numpy(mask).to(dev).unsqueeze(0)
+
+
+def bench_cnn(T=0, Lw=32, V=30000, dm=300, Kc=400, att=256, window=3):
+    """CNN news encoder, inference (digat_cnn_fwd) against forward_stock on the same device in the same process.  T = 65 238 is
+    MIND-small's news count (the news-representation cache of a dev run), V x dm = 36 MB: the table sits in the Infinity Cache."""
+    for T_ in ([T] if T else [8192, 65238]):
+        enc, tt, tm = _cnn_encoder(T_, Lw, V, dm, Kc, att, window)
+        enc.eval()
+
+        def hip():
+            with torch.no_grad():
+                return enc(tt, tm)
+
+        def stock():
+            with torch.no_grad():
+                return enc.forward_stock(tt, tm)
+        diff = float((hip() - stock()).abs().max())
+        (m1, lo1, hi1), (m2, lo2, hi2) = alternate(hip, stock)
+        flops = 2.0 * T_ * Lw * (window * dm * Kc + Kc * att)
+        print(f"CNN news encoder T={T_} titles x {Lw} tokens, window {window}: HIP {m1:.2f} ms [{lo1:.2f}, {hi1:.2f}] ({T_/m1/1e3:.2f} M titles/s, "
+              f"{flops/m1/1e9:.1f} TFLOP/s fp32-eq)   stock torch {m2:.2f} ms [{lo2:.2f}, {hi2:.2f}]   max|diff| {diff:.2e}")
+        del enc, tt, tm
+        torch.cuda.empty_cache()
+
+
+def bench_cnn_train(T=6400, Lw=32, V=30000, dm=300, Kc=400, att=256, window=3):
+    """One training step of the CNN news encoder (forward + backward, both dropouts at 0.2): digat_cnn_fwd_train / digat_cnn_bwd /
+    digat_embedding_bwd against the stock PyTorch modules, alternated.  T = 6 400 titles is the reference's step."""
+    enc, tt, tm = _cnn_encoder(T, Lw, V, dm, Kc, att, window)
+    enc.train()
+    R = torch.randn(1, T, Kc, device=tt.device)
+
+    def step(fn):
+        def run():
+            enc.zero_grad(set_to_none=True)
+            (fn(tt, tm) * R).sum().backward()
+        return run
+    (m1, lo1, hi1), (m2, lo2, hi2) = alternate(step(enc), step(enc.forward_stock))
+    flops = 3 * 2.0 * T * Lw * (window * dm * Kc + Kc * att)
+    print(f"CNN training step T={T} titles x {Lw} tokens, window {window}: HIP {m1:.2f} ms [{lo1:.2f}, {hi1:.2f}] ({flops/m1/1e9:.1f} TFLOP/s fp32-eq)"
+          f"   stock torch {m2:.2f} ms [{lo2:.2f}, {hi2:.2f}]")
+
+
 def bench_sag(n=30000, m=30000, dim=768, top_M=5, news_num=65238, hop=2, cpu_rows=32):
     """SAG construction: cosine top-k of one category of n news against an m-news corpus, and the walk over
     news_num similarity lists; the reference's per-news loop (oracle restatement) timed on cpu_rows rows beside it."""
@@ -326,6 +393,10 @@ if __name__ == "__main__":
         bench_msa(*nums)
     elif what == "msa-train":
         bench_msa_train(*nums)
+    elif what == "cnn":
+        bench_cnn(*nums)
+    elif what == "cnn-train":
+        bench_cnn_train(*nums)
     elif what == "sag":
         bench_sag(*nums)
     elif what == "topic":
