@@ -1,8 +1,8 @@
 // digat_cnn.inc — CNN news encoder, inference and training (reference: newsEncoders.py:29-54, layers.py:7-47 Conv1D,
-// layers.py:91-115 Attention).  Three stages, the last one shared with the MSA encoder (digat_news.inc, digat_news_train.inc):
+// layers.py:91-115 Attention).  Three stages, the last one owned by the MSA encoder's files and called from here:
 //   A. x = dropout_1(embedding[tokens])                                           [T, Lw, dm]     (never stored)
 //   B. h = dropout_2(relu(conv1d(x) + b)), zero padding of p = (taps-1)/2 positions at both ends OF EACH TITLE    [T, Lw, Kc]
-//   C. additive attention pooling: the affine1 product, msa_pool_kernel / msa_pool_bwd_kernel.
+//   C. additive attention pooling: news_pool_fwd (digat_news.inc) / news_pool_bwd (digat_news_train.inc).
 // The convolution is a GEMM with M = T Lw rows, N = Kc columns and K = taps x dm whose A operand is never materialised: row (t, j),
 // tap s is x[t, j+s-p] inside the title and zero outside.  cnn_conv_tiled_kernel stages, per 32-deep slice of dm, the rows of a
 // tile's titles ONCE in LDS with p zero halo rows around each title, already split into the three bf16 pieces of the bf16x6 format
@@ -371,70 +371,67 @@ static int cnn_shape_ok(const digat_cnn_params* p, int Lw, int max_Lw) {
     const int dm = p->word_embedding_dim, Kc = p->kernel_num, taps = p->taps, att = p->attention_dim;
     return dm > 0 && dm % 4 == 0 && Kc > 0 && Kc % 4 == 0 && taps >= 1 && taps <= 7 && (taps & 1) && att > 0 && Lw <= max_Lw;
 }
+static bool cnn_params_set(const digat_cnn_params* p) { return p->word_embedding && p->W && p->b && p->A1 && p->b1 && p->a2; }
+
+struct CnnFwdWs { float *h, *pre; };
+static size_t cnn_fwd_carve(Arena& w, int T, int Lw, int Kc, int att, CnnFwdWs* o) {
+    const size_t M = (size_t)T * Lw;
+    o->h = w.take<float>(M * Kc); o->pre = w.take<float>(M * msa_attp(att));
+    return w.used;
+}
 size_t digat_cnn_workspace_bytes(int T, int Lw, int word_embedding_dim, int kernel_num, int taps, int attention_dim) {
     (void)word_embedding_dim; (void)taps;
     if (T <= 0 || Lw <= 0 || kernel_num <= 0 || attention_dim <= 0) return 0;
-    const size_t M = (size_t)T * Lw;
-    return align_up(M * kernel_num * 4, 256) + align_up(M * msa_attp(attention_dim) * 4, 256);
-}
-
-static int cnn_pool_fwd(const float* A1, const void* a1_wsplit, const float* b1, const float* a2, const float* h, float* pre, const uint8_t* mask,
-                        float* out, float* alpha, int T, int Lw, int Kc, int att, hipStream_t st) {
-    const long M = (long)T * Lw;
-    const int attp = (int)msa_attp(att);
-    GemmArgs ga = gemm_plain(h, Kc, A1, nullptr, pre, attp, (int)M, att, Kc, 0);
-    if (a1_wsplit) {
-        GemmArgs gx = ga;
-        gx.nseg = attp; gx.wsplit = (const unsigned short*)a1_wsplit;
-        if (gemm_takes_row_list(gx)) ga = gx;
-    }
-    T_TRY(launch_gemm(ga, st, DIGAT_KERNEL_LINEAR));
-    MsaPoolArgs pa{pre, attp, b1, a2, h, mask, out, T, Lw, att, Kc, alpha};
-    hipLaunchKernelGGL(msa_pool_kernel, dim3(T), dim3(256), 0, st, pa);
-    DIGAT_CHECK_LAUNCH();
-    return DIGAT_OK;
+    Arena measure;
+    CnnFwdWs o;
+    return cnn_fwd_carve(measure, T, Lw, kernel_num, attention_dim, &o);
 }
 
 int digat_cnn_fwd(const digat_cnn_params* p, const int32_t* title_text, const uint8_t* title_mask, float* out, int T, int Lw,
                   void* workspace, size_t workspace_bytes, void* stream) {
     if (!p || !title_text || !title_mask || !out || !workspace || T < 0 || Lw <= 0) return DIGAT_ERR_ARG;
-    if (!p->word_embedding || !p->W || !p->b || !p->A1 || !p->b1 || !p->a2) return DIGAT_ERR_ARG;
+    if (!cnn_params_set(p)) return DIGAT_ERR_ARG;
     if (!cnn_shape_ok(p, Lw, 64)) return DIGAT_ERR_SHAPE;
     const int dm = p->word_embedding_dim, Kc = p->kernel_num, taps = p->taps, att = p->attention_dim;
-    if (workspace_bytes < digat_cnn_workspace_bytes(T, Lw, dm, Kc, taps, att)) return DIGAT_ERR_WORKSPACE;
+    Arena w(workspace, workspace_bytes);
+    CnnFwdWs o;
+    cnn_fwd_carve(w, T, Lw, Kc, att, &o);
+    if (!w.ok) return DIGAT_ERR_WORKSPACE;
     if (T == 0) return DIGAT_OK;
     hipStream_t st = (hipStream_t)stream;
-    Arena w(workspace, workspace_bytes);
-    const size_t M = (size_t)T * Lw;
-    float* h = w.take<float>(M * Kc);
-    float* pre = w.take<float>(M * msa_attp(att));
-    if (!w.ok) return DIGAT_ERR_WORKSPACE;
     CnnConvArgs c{};
     c.src = p->word_embedding; c.lds = dm; c.tokens = title_text; c.wimg = (const unsigned short*)p->w_split;
-    c.w = p->W; c.sn = (long)dm * taps; c.sk = taps; c.flip = 0; c.bias = p->b; c.out = h; c.ldo = Kc;
+    c.w = p->W; c.sn = (long)dm * taps; c.sk = taps; c.flip = 0; c.bias = p->b; c.out = o.h; c.ldo = Kc;
     c.T = T; c.Lw = Lw; c.K = dm; c.N = Kc; c.taps = taps; c.relu = 1;
     T_TRY(cnn_launch_conv(c, st));
-    return cnn_pool_fwd(p->A1, p->a1_wsplit, p->b1, p->a2, h, pre, title_mask, out, nullptr, T, Lw, Kc, att, st);
+    return news_pool_fwd(o.h, Kc, p->A1, p->a1_wsplit, p->b1, p->a2, o.pre, title_mask, out, nullptr, T, Lw, att, false, st);
 }
 
 // ---- the training pair ------------------------------------------------------------------------------------------------------
+struct CnnSave { float *h, *pre, *alpha; };
+static size_t cnn_save_carve(Arena& a, int T, int Lw, int Kc, int att, CnnSave* s) {
+    const size_t M = (size_t)T * Lw;
+    s->h = a.take<float>(M * Kc); s->pre = a.take<float>(M * msa_attp(att)); s->alpha = a.take<float>(M);
+    return a.used;
+}
 size_t digat_cnn_train_save_bytes(int T, int Lw, int word_embedding_dim, int kernel_num, int taps, int attention_dim) {
     (void)word_embedding_dim; (void)taps;
     if (T <= 0 || Lw <= 0 || kernel_num <= 0 || attention_dim <= 0) return 0;
-    const size_t M = (size_t)T * Lw;
-    return align_up(M * kernel_num * 4, 256) + align_up(M * msa_attp(attention_dim) * 4, 256) + align_up(M * 4, 256);      // h, pre, alpha
+    Arena measure;
+    CnnSave s;
+    return cnn_save_carve(measure, T, Lw, kernel_num, attention_dim, &s);
 }
-struct CnnTrainWs { void *w_img, *a1_img, *a1t_img, *wt_img; float *dh, *dpre, *da2p, *da2g, *dzpad, *xpad, *dwt; void* wg; size_t wgb; };
+struct CnnTrainWs { void *w_img, *a1_img, *wt_img; PoolBwdWs pool; float *dzpad, *xpad, *dwt; void* wg; size_t wgb; };
 static size_t cnn_train_carve(Arena& w, int T, int Lw, int dm, int Kc, int taps, int att, CnnTrainWs* o) {
     const size_t M = (size_t)T * Lw, Mp = (size_t)T * (Lw + taps - 1), attp = msa_attp(att);
     o->w_img = w.take<char>(cnn_image_bytes(dm, Kc, taps));
     o->a1_img = w.take<char>(digat_split_weights_bytes(att, Kc));
-    o->a1t_img = w.take<char>(digat_split_weights_bytes(Kc, att));
+    o->pool.a1t_img = w.take<char>(digat_split_weights_bytes(Kc, att));
     o->wt_img = w.take<char>(cnn_image_bytes(Kc, dm, taps));
-    o->dh = w.take<float>(M * Kc);
-    o->dpre = w.take<float>(M * attp);
-    o->da2p = w.take<float>((size_t)T * att);
-    o->da2g = w.take<float>((size_t)((T + 63) / 64) * att);
+    o->pool.dh = w.take<float>(M * Kc);
+    o->pool.dpre = w.take<float>(M * attp);
+    o->pool.da2p = w.take<float>((size_t)T * att);
+    o->pool.da2g = w.take<float>((size_t)((T + 63) / 64) * att);
     o->dzpad = w.take<float>(Mp * Kc);
     o->xpad = w.take<float>(Mp * dm);
     o->dwt = w.take<float>((size_t)taps * Kc * dm);
@@ -454,13 +451,6 @@ size_t digat_cnn_train_workspace_bytes(int T, int Lw, int word_embedding_dim, in
     CnnTrainWs o;
     return cnn_train_carve(measure, T, Lw, word_embedding_dim, kernel_num, taps, attention_dim, &o);
 }
-struct CnnSave { float *h, *pre, *alpha; };
-static bool cnn_save_carve(void* save, size_t bytes, int T, int Lw, int Kc, int att, CnnSave* s) {
-    Arena a(save, bytes);
-    const size_t M = (size_t)T * Lw;
-    s->h = a.take<float>(M * Kc); s->pre = a.take<float>(M * msa_attp(att)); s->alpha = a.take<float>(M);
-    return a.ok;
-}
 
 // out [T, Kc].  p_drop: both dropouts of newsEncoders.py:46-48 — site 1 on the embedded tokens (keep bits: the counter hash of `seed`
 // over the [T Lw, dm] elements), site 2 on relu(conv) (`seed + 1` over the [T Lw, Kc] elements).  `save` carries h (after the second
@@ -470,18 +460,16 @@ int digat_cnn_fwd_train(const digat_cnn_params* p, const int32_t* title_text, co
                         uint32_t seed, int T, int Lw, void* save, size_t save_bytes, void* workspace, size_t workspace_bytes, void* stream) {
     if (!p || !title_text || !title_mask || !out || !save || !workspace || T < 0 || Lw <= 0 || p_drop < 0.f || p_drop >= 1.f)
         return DIGAT_ERR_ARG;
-    if (!p->word_embedding || !p->W || !p->b || !p->A1 || !p->b1 || !p->a2) return DIGAT_ERR_ARG;
+    if (!cnn_params_set(p)) return DIGAT_ERR_ARG;
     if (!cnn_shape_ok(p, Lw, 32) || p->attention_dim % 4) return DIGAT_ERR_SHAPE;
     const int dm = p->word_embedding_dim, Kc = p->kernel_num, taps = p->taps, att = p->attention_dim;
     if (T == 0) return DIGAT_OK;
+    Arena sa(save, save_bytes), w(workspace, workspace_bytes);
     CnnSave s;
-    if (save_bytes < digat_cnn_train_save_bytes(T, Lw, dm, Kc, taps, att) || !cnn_save_carve(save, save_bytes, T, Lw, Kc, att, &s))
-        return DIGAT_ERR_WORKSPACE;
-    if (workspace_bytes < digat_cnn_train_workspace_bytes(T, Lw, dm, Kc, taps, att)) return DIGAT_ERR_WORKSPACE;
-    Arena w(workspace, workspace_bytes);
     CnnTrainWs o;
+    cnn_save_carve(sa, T, Lw, Kc, att, &s);
     cnn_train_carve(w, T, Lw, dm, Kc, taps, att, &o);
-    if (!w.ok) return DIGAT_ERR_WORKSPACE;
+    if (!sa.ok || !w.ok) return DIGAT_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const long M = (long)T * Lw;
     CnnConvArgs c{};
@@ -502,7 +490,8 @@ int digat_cnn_fwd_train(const digat_cnn_params* p, const int32_t* title_text, co
         T_TRY(launch_split(p->A1, p->A1, p->A1, att, 1, Kc, o.a1_img, st));
         a1_img = o.a1_img;
     }
-    return cnn_pool_fwd(p->A1, a1_img, p->b1, p->a2, s.h, s.pre, title_mask, out, s.alpha, T, Lw, Kc, att, st);
+    // bf16_ok = false: affine1 stays fp32-grade under digat_set_train_precision(1) (digat_msa_fwd_train's follows it)
+    return news_pool_fwd(s.h, Kc, p->A1, a1_img, p->b1, p->a2, s.pre, title_mask, out, s.alpha, T, Lw, att, false, st);
 }
 
 // dout [T, Kc].  Written (not accumulated): row_grad [T*Lw, dm], rows ld_row_grad >= dm floats apart (a multiple of 4) — the gradient
@@ -513,46 +502,27 @@ int digat_cnn_bwd(const digat_cnn_params* p, const int32_t* title_text, const ui
                   float* db1, float* da2, int T, int Lw, void* workspace, size_t workspace_bytes, void* stream) {
     if (!p || !title_text || !title_mask || !dout || !save || !row_grad || !dW || !db || !dA1 || !db1 || !da2 || !workspace || T < 0 ||
         Lw <= 0 || p_drop < 0.f || p_drop >= 1.f) return DIGAT_ERR_ARG;
-    if (!p->word_embedding || !p->W || !p->b || !p->A1 || !p->b1 || !p->a2) return DIGAT_ERR_ARG;
+    if (!cnn_params_set(p)) return DIGAT_ERR_ARG;
     if (!cnn_shape_ok(p, Lw, 32) || p->attention_dim % 4) return DIGAT_ERR_SHAPE;
     const int dm = p->word_embedding_dim, Kc = p->kernel_num, taps = p->taps, att = p->attention_dim;
-    const int attp = (int)msa_attp(att), pad = (taps - 1) / 2;
+    const int pad = (taps - 1) / 2;
     if (ld_row_grad < dm || ld_row_grad % 4) return DIGAT_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    if (T == 0) {
-        if (hipMemsetAsync(dW, 0, (size_t)Kc * dm * taps * 4, st) != hipSuccess || hipMemsetAsync(db, 0, (size_t)Kc * 4, st) != hipSuccess ||
-            hipMemsetAsync(dA1, 0, (size_t)att * Kc * 4, st) != hipSuccess || hipMemsetAsync(db1, 0, (size_t)att * 4, st) != hipSuccess ||
-            hipMemsetAsync(da2, 0, (size_t)att * 4, st) != hipSuccess) return DIGAT_ERR_LAUNCH;
-        return DIGAT_OK;
-    }
+    const size_t kn = Kc, an = att;
+    if (T == 0) return zero_floats(st, {{dW, kn * dm * taps}, {db, kn}, {dA1, an * kn}, {db1, an}, {da2, an}});
+    Arena sa(const_cast<void*>(save), save_bytes), w(workspace, workspace_bytes);
     CnnSave s;
-    if (save_bytes < digat_cnn_train_save_bytes(T, Lw, dm, Kc, taps, att) ||
-        !cnn_save_carve(const_cast<void*>(save), save_bytes, T, Lw, Kc, att, &s)) return DIGAT_ERR_WORKSPACE;
-    if (workspace_bytes < digat_cnn_train_workspace_bytes(T, Lw, dm, Kc, taps, att)) return DIGAT_ERR_WORKSPACE;
-    Arena w(workspace, workspace_bytes);
     CnnTrainWs o;
+    cnn_save_carve(sa, T, Lw, Kc, att, &s);
     cnn_train_carve(w, T, Lw, dm, Kc, taps, att, &o);
-    if (!w.ok) return DIGAT_ERR_WORKSPACE;
+    if (!sa.ok || !w.ok) return DIGAT_ERR_WORKSPACE;
     const long M = (long)T * Lw, Mp = (long)T * (Lw + 2 * pad);
-    // pooling
-    MsaPoolBwdArgs pb{dout, s.h, s.pre, attp, p->b1, p->a2, s.alpha, title_mask, o.dh, o.dpre, o.da2p, T, Lw, att, Kc};
-    hipLaunchKernelGGL(msa_pool_bwd_kernel, dim3(T), dim3(256), 0, st, pb);
-    DIGAT_CHECK_LAUNCH();
-    {
-        const int per = 64, G = (T + per - 1) / per;
-        hipLaunchKernelGGL(colsum_groups_kernel, dim3((att + 63) / 64, G), dim3(256), 0, st, (const float*)o.da2p, (long)att, o.da2g, T, att, per, (const int*)nullptr, 0);
-        DIGAT_CHECK_LAUNCH();
-        hipLaunchKernelGGL(colsum_kernel, dim3((att + 63) / 64), dim3(256), 0, st, (const float*)o.da2g, (long)att, da2, G, att, 0, (const int*)nullptr, 0);
-        DIGAT_CHECK_LAUNCH();
-    }
-    // affine1: dh += dpre A1; dA1 = dpre^T h; db1 = colsum(dpre)
-    if (x3_ok(M, Kc, att)) T_TRY(digat_linear_bwd_input_x3(o.dpre, attp, p->A1, o.dh, Kc, (int)M, att, Kc, 1, o.a1t_img, st));
-    else T_TRY(digat_linear_bwd_input(o.dpre, attp, p->A1, o.dh, Kc, (int)M, att, Kc, 1, st));
-    T_TRY(digat_linear_bwd_weight(o.dpre, attp, s.h, Kc, dA1, db1, (int)M, att, Kc, 0, o.wg, o.wgb, st));
+    T_TRY(news_pool_bwd(dout, s.h, Kc, s.pre, s.alpha, title_mask, p->A1, p->b1, p->a2, o.pool, o.wg, o.wgb, dA1, db1, da2, T, Lw, att, st));
+    float* const dh = o.pool.dh;
     // second dropout + ReLU (dh becomes dz), and the halo-padded copies for the weight gradient
     {
         const float sc = p_drop > 0.f ? 1.f / (1.f - p_drop) : 1.f;
-        CnnPadArgs a{s.h, o.dh, o.dzpad, p->word_embedding, title_text, o.xpad, T, Lw, pad, Kc, dm, sc,
+        CnnPadArgs a{s.h, dh, o.dzpad, p->word_embedding, title_text, o.xpad, T, Lw, pad, Kc, dm, sc,
                      p_drop > 0.f ? drop_threshold(p_drop) : 0u, seed, sc};
         hipLaunchKernelGGL(cnn_pad_kernel, dim3(grid_for(Mp * ((Kc + dm) / 4))), dim3(256), 0, st, a);
         DIGAT_CHECK_LAUNCH();
@@ -560,7 +530,7 @@ int digat_cnn_bwd(const digat_cnn_params* p, const int32_t* title_text, const ui
     // input gradient: the same convolution of dz with W flipped in s and transposed in (c, i); site 1's backward in its epilogue
     {
         CnnConvArgs c{};
-        c.src = o.dh; c.lds = Kc; c.tokens = nullptr;
+        c.src = dh; c.lds = Kc; c.tokens = nullptr;
         c.w = p->W; c.sn = taps; c.sk = (long)dm * taps; c.flip = 1; c.bias = nullptr; c.out = row_grad; c.ldo = ld_row_grad;
         c.T = T; c.Lw = Lw; c.K = Kc; c.N = dm; c.taps = taps; c.relu = 0;
         if (p_drop > 0.f) { c.out_thr = drop_threshold(p_drop); c.out_seed = seed; c.out_scale = 1.f / (1.f - p_drop); }

@@ -21,8 +21,10 @@
 #include <string.h>
 #include <stdlib.h>
 #include <atomic>
+#include <initializer_list>
 #include <mutex>
 #include <unordered_map>
+#include <utility>
 
 #include "../../include/digat_hip.h"
 

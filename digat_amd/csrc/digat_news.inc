@@ -5,7 +5,8 @@
 //   B. per title and head: softmax(Q K^T / sqrt(d_k)) V, no padding mask (layers.py:84-87), ReLU (newsEncoders.py:78);
 //   C. additive attention pooling: a_t = affine2 . tanh(affine1 h_t + b), -1e9 on padding, softmax over the title,
 //      sum_t alpha_t h_t (layers.py:108-114); the affine1 product is one more bf16x6 GEMM (its rows zero-padded to a
-//      multiple of 80), the rest one small kernel per title.
+//      multiple of 80), the rest one small kernel per title.  This stage is the CNN encoder's too (digat_cnn.inc): news_pool_fwd
+//      below is the one place it is launched from, for both encoders, inference and training.
 // Included at the end of digat_kernels.hip.
 
 // embeddings of the listed tokens as a dense matrix (fallback when the GEMM cannot take the row list)
@@ -247,6 +248,73 @@ __global__ void __launch_bounds__(256) msa_pool_kernel(const MsaPoolArgs g) {
     }
 }
 
+// ---- host side -------------------------------------------------------------------------------------------------------------
+// attention_dim (or any column count) rounded up to the 80-column strips of the bf16x6 GEMM
+static size_t msa_attp(int att) { return ((size_t)att + 79) / 80 * 80; }
+
+// out [M, dm] = table[tokens]
+static int launch_gather_embedding(const float* table, const int32_t* tokens, float* out, long M, int dm, hipStream_t st) {
+    hipLaunchKernelGGL(gather_embedding_kernel, dim3(grid_for(M * (dm / 4))), dim3(256), 0, st, (const float4*)table, tokens, (float4*)out, M,
+                       dm / 4);
+    DIGAT_CHECK_LAUNCH();
+    return DIGAT_OK;
+}
+
+// Stage B: the matrix-core kernel up to 32 words a title, the LDS-broadcast one above
+static int launch_msa_attention(const float* qkv, float* h, int T, int Lw, int heads, int dk, hipStream_t st) {
+    MsaAttnArgs a{qkv, h, T, Lw, heads, dk};
+    if (Lw <= 32) {
+        const int ks = (dk + 3) / 4, kp = ks * 4;
+        const size_t lds = (size_t)4 * (2 * 32 * kp + 32 * 33) * 4;
+        switch (ks) {
+            case 1: hipLaunchKernelGGL(msa_attention_mfma_kernel<1>, dim3(T), dim3(256), lds, st, a); break;
+            case 2: hipLaunchKernelGGL(msa_attention_mfma_kernel<2>, dim3(T), dim3(256), lds, st, a); break;
+            case 3: hipLaunchKernelGGL(msa_attention_mfma_kernel<3>, dim3(T), dim3(256), lds, st, a); break;
+            case 4: hipLaunchKernelGGL(msa_attention_mfma_kernel<4>, dim3(T), dim3(256), lds, st, a); break;
+            case 5: hipLaunchKernelGGL(msa_attention_mfma_kernel<5>, dim3(T), dim3(256), lds, st, a); break;
+            case 6: hipLaunchKernelGGL(msa_attention_mfma_kernel<6>, dim3(T), dim3(256), lds, st, a); break;
+            case 7: hipLaunchKernelGGL(msa_attention_mfma_kernel<7>, dim3(T), dim3(256), lds, st, a); break;
+            default: hipLaunchKernelGGL(msa_attention_mfma_kernel<8>, dim3(T), dim3(256), lds, st, a); break;
+        }
+    } else {
+        const size_t lds = (size_t)4 * (2 * Lw * dk + Lw * (Lw + 1)) * 4;
+        hipLaunchKernelGGL(msa_attention_kernel, dim3(T), dim3(256), lds, st, a);
+    }
+    DIGAT_CHECK_LAUNCH();
+    return DIGAT_OK;
+}
+
+// Stage C of BOTH news encoders, inference and training (h [T Lw, hd]: hd = heads * d_k, or the CNN's kernel_num): pre = h A1^T
+// without the bias (the pooling kernel adds it), then msa_pool_kernel; `alpha` (optional [T, Lw]) keeps the pooling weights for the
+// backward.  `a1_image`: a ready split image of A1, or NULL — whether one exists is the caller's decision; with it the product runs
+// over attp = att rounded up to 80 columns (the image holds zero rows there; those columns of `pre` are never read).  `bf16_ok`:
+// under digat_set_train_precision(1) the image's product may run on the bf16 single-product segments.
+static int news_pool_fwd(const float* h, int hd, const float* A1, const void* a1_image, const float* b1, const float* a2, float* pre,
+                         const uint8_t* mask, float* out, float* alpha, int T, int Lw, int att, bool bf16_ok, hipStream_t st) {
+    const long M = (long)T * Lw;
+    const int attp = (int)msa_attp(att);
+    GemmArgs ga = gemm_plain(h, hd, A1, nullptr, pre, attp, (int)M, att, hd, 0);
+    if (a1_image) {
+        GemmArgs gx = ga;
+        gx.nseg = attp; gx.wsplit = (const unsigned short*)a1_image;
+        if (bf16_ok && g_train_bf16) gx.x1_segs = 7;
+        if (gemm_takes_row_list(gx)) ga = gx;
+    }
+    T_TRY(launch_gemm(ga, st, DIGAT_KERNEL_LINEAR));
+    MsaPoolArgs pa{pre, attp, b1, a2, h, mask, out, T, Lw, att, hd, alpha};
+    hipLaunchKernelGGL(msa_pool_kernel, dim3(T), dim3(256), 0, st, pa);
+    DIGAT_CHECK_LAUNCH();
+    return DIGAT_OK;
+}
+
+// the inference workspace: qkv, h, the affine1 product, and the embedded tokens for shapes whose GEMM cannot take the row list
+struct MsaFwdWs { float *qkv, *h, *pre, *emb; };
+static size_t msa_fwd_carve(Arena& w, int T, int Lw, int dm, int hd, int att, MsaFwdWs* o) {
+    const size_t M = (size_t)T * Lw;
+    o->qkv = w.take<float>(M * 3 * hd); o->h = w.take<float>(M * hd); o->pre = w.take<float>(M * msa_attp(att)); o->emb = w.take<float>(M * dm);
+    return w.used;
+}
+
 extern "C" {
 
 size_t digat_msa_split_bytes(int word_embedding_dim, int head_num, int head_dim) {
@@ -259,83 +327,41 @@ int digat_split_msa_weights(const float* W_Q, const float* W_K, const float* W_V
 }
 
 size_t digat_msa_workspace_bytes(int T, int Lw, int dm, int heads, int dk, int att) {
-    const size_t M = (size_t)T * Lw, hd = (size_t)heads * dk, attp = ((size_t)att + 79) / 80 * 80;
-    return align_up(M * 3 * hd * 4, 256) + align_up(M * hd * 4, 256) + align_up(M * attp * 4, 256) + align_up(M * dm * 4, 256);
+    Arena measure;
+    MsaFwdWs o;
+    return msa_fwd_carve(measure, T, Lw, dm, heads * dk, att, &o);
 }
 
 int digat_msa_fwd(const digat_msa_params* p, const int32_t* title_text, const uint8_t* title_mask, float* out,
                   int T, int Lw, void* workspace, size_t workspace_bytes, void* stream) {
     if (!p || !title_text || !title_mask || !out || !workspace || T < 0 || Lw <= 0) return DIGAT_ERR_ARG;
     const int dm = p->word_embedding_dim, heads = p->head_num, dk = p->head_dim, att = p->attention_dim;
-    const int hd = heads * dk, attp = (att + 79) / 80 * 80;
+    const int hd = heads * dk;
     if (dm <= 0 || dm % 4 || heads <= 0 || dk <= 0 || dk > MSA_MAX_DK || att <= 0 || hd % 4 || Lw > 64) return DIGAT_ERR_SHAPE;
-    if (workspace_bytes < digat_msa_workspace_bytes(T, Lw, dm, heads, dk, att)) return DIGAT_ERR_WORKSPACE;
+    Arena w(workspace, workspace_bytes);
+    MsaFwdWs o;
+    msa_fwd_carve(w, T, Lw, dm, hd, att, &o);
+    if (!w.ok) return DIGAT_ERR_WORKSPACE;
     if (T == 0) return DIGAT_OK;
     hipStream_t st = (hipStream_t)stream;
     const long M = (long)T * Lw;
-    char* ws = (char*)workspace;
-    float* qkv = (float*)ws;  ws += align_up((size_t)M * 3 * hd * 4, 256);
-    float* h = (float*)ws;    ws += align_up((size_t)M * hd * 4, 256);
-    float* pre = (float*)ws;  ws += align_up((size_t)M * attp * 4, 256);
-    float* emb = (float*)ws;
 
     // A. [Q|K|V]
-    GemmArgs g = gemm_plain(p->word_embedding, dm, p->W_Q, p->b_Q, qkv, 3 * hd, (int)M, hd, dm, 0);
-    g.w[1] = p->W_K; g.bias[1] = nullptr; g.y[1] = qkv + hd;
-    g.w[2] = p->W_V; g.bias[2] = p->b_V; g.y[2] = qkv + 2 * hd;
+    GemmArgs g = gemm_plain(p->word_embedding, dm, p->W_Q, p->b_Q, o.qkv, 3 * hd, (int)M, hd, dm, 0);
+    g.w[1] = p->W_K; g.bias[1] = nullptr; g.y[1] = o.qkv + hd;
+    g.w[2] = p->W_V; g.bias[2] = p->b_V; g.y[2] = o.qkv + 2 * hd;
     g.nsegs = 3;
     g.wsplit = (const unsigned short*)p->qkv_wsplit;
     g.rowidx = title_text; g.gather_only = 1;
-    int rc;
-    if (gemm_takes_row_list(g)) {
-        rc = launch_gemm(g, st, DIGAT_KERNEL_LINEAR);
-    } else {                                       // small / odd shapes: materialise the embeddings, then the generic dispatch
-        const long total = M * (dm / 4);
-        int blocks = (int)((total + 255) / 256);
-        if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL(gather_embedding_kernel, dim3(blocks), dim3(256), 0, st, (const float4*)p->word_embedding, title_text,
-                           (float4*)emb, M, dm / 4);
-        DIGAT_CHECK_LAUNCH();
-        g.a0 = emb; g.rowidx = nullptr; g.gather_only = 0; g.wsplit = nullptr;
-        rc = launch_gemm(g, st, DIGAT_KERNEL_LINEAR);
+    if (!gemm_takes_row_list(g)) {                 // small / odd shapes: materialise the embeddings, then the generic dispatch
+        T_TRY(launch_gather_embedding(p->word_embedding, title_text, o.emb, M, dm, st));
+        g.a0 = o.emb; g.rowidx = nullptr; g.gather_only = 0; g.wsplit = nullptr;
     }
-    if (rc) return rc;
+    T_TRY(launch_gemm(g, st, DIGAT_KERNEL_LINEAR));
     // B. attention + ReLU
-    {
-        MsaAttnArgs a{qkv, h, T, Lw, heads, dk};
-        if (Lw <= 32) {
-            const int ks = (dk + 3) / 4, kp = ks * 4;
-            const size_t lds = (size_t)4 * (2 * 32 * kp + 32 * 33) * 4;
-            switch (ks) {
-                case 1: hipLaunchKernelGGL(msa_attention_mfma_kernel<1>, dim3(T), dim3(256), lds, st, a); break;
-                case 2: hipLaunchKernelGGL(msa_attention_mfma_kernel<2>, dim3(T), dim3(256), lds, st, a); break;
-                case 3: hipLaunchKernelGGL(msa_attention_mfma_kernel<3>, dim3(T), dim3(256), lds, st, a); break;
-                case 4: hipLaunchKernelGGL(msa_attention_mfma_kernel<4>, dim3(T), dim3(256), lds, st, a); break;
-                case 5: hipLaunchKernelGGL(msa_attention_mfma_kernel<5>, dim3(T), dim3(256), lds, st, a); break;
-                case 6: hipLaunchKernelGGL(msa_attention_mfma_kernel<6>, dim3(T), dim3(256), lds, st, a); break;
-                case 7: hipLaunchKernelGGL(msa_attention_mfma_kernel<7>, dim3(T), dim3(256), lds, st, a); break;
-                default: hipLaunchKernelGGL(msa_attention_mfma_kernel<8>, dim3(T), dim3(256), lds, st, a); break;
-            }
-        } else {
-            const size_t lds = (size_t)4 * (2 * Lw * dk + Lw * (Lw + 1)) * 4;
-            hipLaunchKernelGGL(msa_attention_kernel, dim3(T), dim3(256), lds, st, a);
-        }
-        DIGAT_CHECK_LAUNCH();
-    }
-    // C. affine1 without its bias (the pooling kernel adds it).  With split weights the product runs over attp = att
-    // rounded up to 80 columns (the split image holds zero rows there; those columns of `pre` are never read).
-    GemmArgs ga = gemm_plain(h, hd, p->A1, nullptr, pre, attp, (int)M, att, hd, 0);
-    if (p->a1_wsplit) {
-        GemmArgs gx = ga;
-        gx.nseg = attp; gx.wsplit = (const unsigned short*)p->a1_wsplit;
-        if (gemm_takes_row_list(gx)) ga = gx;
-    }
-    rc = launch_gemm(ga, st, DIGAT_KERNEL_LINEAR);
-    if (rc) return rc;
-    MsaPoolArgs pa{pre, attp, p->b1, p->a2, h, title_mask, out, T, Lw, att, hd};
-    hipLaunchKernelGGL(msa_pool_kernel, dim3(T), dim3(256), 0, st, pa);
-    DIGAT_CHECK_LAUNCH();
-    return DIGAT_OK;
+    T_TRY(launch_msa_attention(o.qkv, o.h, T, Lw, heads, dk, st));
+    // C. pooling (inference: fp32-grade whatever the training precision)
+    return news_pool_fwd(o.h, hd, p->A1, p->a1_wsplit, p->b1, p->a2, o.pre, title_mask, out, nullptr, T, Lw, att, false, st);
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 //   backward: the pooling (alpha, tanh), affine1 (two GEMMs), ReLU, the attention (S and alpha RECOMPUTED from Q, K: nothing
 //             of size Lw^2 is saved), the three projections (input and weight gradients), dropout, and the embedding rows
 //             summed per token in a fixed order (bit-reproducible, no atomics).
+// The pooling stage's backward (news_pool_bwd) also serves the CNN encoder (digat_cnn.inc).
 // Included by digat_kernels.hip after digat_news.inc.
 
 // ---- embedding rows of the listed tokens (float4) ---------------------------------------------------------------
@@ -426,6 +427,13 @@ __global__ void __launch_bounds__(256) msa_row_dropout_bwd_kernel(const MsaRowDr
     }
 }
 
+// {pointer, floats} pairs zero-filled on the stream: the gradients of a call without titles
+static int zero_floats(hipStream_t st, std::initializer_list<std::pair<float*, size_t>> bufs) {
+    for (const auto& b : bufs)
+        if (hipMemsetAsync(b.first, 0, b.second * 4, st) != hipSuccess) return DIGAT_ERR_LAUNCH;
+    return DIGAT_OK;
+}
+
 extern "C" {
 
 // table_grad [V, dm] must be zero-filled by the caller (rows of tokens that do not occur stay zero).
@@ -500,46 +508,79 @@ int digat_embedding_bwd_unsorted(const int64_t* ids0, const float* g0, int64_t l
     return DIGAT_OK;
 }
 
+// ---- the pooling stage's backward, shared with the CNN encoder (digat_cnn.inc) ---------------------------------------------
+// the regions it works in; each encoder's training carve places them in its own layout
+struct PoolBwdWs { void* a1t_img; float *dh, *dpre, *da2p, *da2g; };
+// h [T Lw, hd], pre, alpha: what news_pool_fwd left in `save`.  Written: w.dh = alpha_j dout + dpre A1 (the gradient at h), dA1 [att, hd],
+// db1, da2 [att].  wg / wgb: the encoder's weight-gradient scratch, at least digat_linear_bwd_weight_workspace(T Lw, att, hd) bytes.
+static int news_pool_bwd(const float* dout, const float* h, int hd, const float* pre, const float* alpha, const uint8_t* mask, const float* A1,
+                         const float* b1, const float* a2, const PoolBwdWs& w, void* wg, size_t wgb, float* dA1, float* db1, float* da2, int T, int Lw,
+                         int att, hipStream_t st) {
+    const long M = (long)T * Lw;
+    const int attp = (int)msa_attp(att);
+    MsaPoolBwdArgs pb{dout, h, pre, attp, b1, a2, alpha, mask, w.dh, w.dpre, w.da2p, T, Lw, att, hd};
+    hipLaunchKernelGGL(msa_pool_bwd_kernel, dim3(T), dim3(256), 0, st, pb);
+    DIGAT_CHECK_LAUNCH();
+    const int per = 64, G = (T + per - 1) / per;       // da2 = the column sums of the per-title partials, in two levels
+    hipLaunchKernelGGL(colsum_groups_kernel, dim3((att + 63) / 64, G), dim3(256), 0, st, (const float*)w.da2p, (long)att, w.da2g, T, att, per, (const int*)nullptr, 0);
+    DIGAT_CHECK_LAUNCH();
+    hipLaunchKernelGGL(colsum_kernel, dim3((att + 63) / 64), dim3(256), 0, st, (const float*)w.da2g, (long)att, da2, G, att, 0, (const int*)nullptr, 0);
+    DIGAT_CHECK_LAUNCH();
+    // affine1: dh += dpre A1; dA1 = dpre^T h; db1 = colsum(dpre)
+    if (x3_ok(M, hd, att)) T_TRY(digat_linear_bwd_input_x3(w.dpre, attp, A1, w.dh, hd, (int)M, att, hd, 1, w.a1t_img, st));
+    else T_TRY(digat_linear_bwd_input(w.dpre, attp, A1, w.dh, hd, (int)M, att, hd, 1, st));
+    return digat_linear_bwd_weight(w.dpre, attp, h, hd, dA1, db1, (int)M, att, hd, 0, wg, wgb, st);
+}
+
 // ---- the pair ------------------------------------------------------------------------------------------------------
-static size_t msa_attp(int att) { return ((size_t)att + 79) / 80 * 80; }
+struct MsaSave { float* Ed; uint8_t* dmask; float *qkv, *h, *pre, *alpha; };
+static size_t msa_save_carve(Arena& a, int T, int Lw, int dm, int hd, int att, MsaSave* s) {
+    const size_t M = (size_t)T * Lw;
+    s->Ed = a.take<float>(M * dm); s->dmask = a.take<uint8_t>(M * dm); s->qkv = a.take<float>(M * 3 * hd); s->h = a.take<float>(M * hd);
+    s->pre = a.take<float>(M * msa_attp(att)); s->alpha = a.take<float>(M);
+    return a.used;
+}
+// One layout for both directions.  Forward: the split images of [W_Q; W_K; W_V] and A1 (the weights change every optimiser step).
+// Backward: A1^T's image and the pooling regions, dqkv, the image of the stacked weights' transpose (dm rounded up to 80 rows), the
+// weight-gradient scratch (the larger of the two products), and the stacked dW / db for callers whose three dW are not one buffer.
+struct MsaTrainWs { void *qkv_img, *a1_img; PoolBwdWs pool; float* dqkv; void *wcat_img, *wg; size_t wgb; float *wg3, *db3g; };
+static size_t msa_train_carve(Arena& w, int T, int Lw, int dm, int hd, int att, MsaTrainWs* o) {
+    const size_t M = (size_t)T * Lw;
+    o->qkv_img = w.take<char>(digat_split_weights_bytes(3 * hd, dm));
+    o->a1_img = w.take<char>(digat_split_weights_bytes(att, hd));
+    o->pool.a1t_img = w.take<char>(digat_split_weights_bytes(hd, att));
+    o->pool.dh = w.take<float>(M * hd);
+    o->pool.dpre = w.take<float>(M * msa_attp(att));
+    o->dqkv = w.take<float>(M * 3 * hd);
+    o->pool.da2p = w.take<float>((size_t)T * att);
+    o->pool.da2g = w.take<float>((size_t)((T + 63) / 64) * att);
+    o->wcat_img = w.take<char>(digat_split_weights_bytes((int)msa_attp(dm), 3 * hd));
+    o->wgb = digat_linear_bwd_weight_workspace((int)M, 3 * hd, dm);
+    const size_t wgb2 = digat_linear_bwd_weight_workspace((int)M, att, hd);
+    if (wgb2 > o->wgb) o->wgb = wgb2;
+    o->wg = w.take<char>(o->wgb);
+    o->wg3 = w.take<float>(3 * (size_t)hd * dm);
+    o->db3g = w.take<float>(3 * (size_t)hd);
+    return w.used;
+}
+static int msa_shape_ok(const digat_msa_params* p, int Lw) {
+    const int dm = p->word_embedding_dim, heads = p->head_num, dk = p->head_dim, att = p->attention_dim;
+    return dm > 0 && dm % 4 == 0 && heads > 0 && dk > 0 && dk <= MSA_MAX_DK && att > 0 && att % 4 == 0 && (heads * dk) % 4 == 0 && Lw <= 32;
+}
+
 // the leading dimension of row_grad that lets digat_msa_bwd compute it as one matrix-core product
 int64_t digat_msa_row_grad_ld(int T, int Lw, int word_embedding_dim) {
     return (long)T * Lw >= 2048 ? (int64_t)msa_attp(word_embedding_dim) : word_embedding_dim;
 }
 size_t digat_msa_train_save_bytes(int T, int Lw, int dm, int heads, int dk, int att) {
-    const size_t M = (size_t)T * Lw, hd = (size_t)heads * dk;
-    // Ed, dropout mask, qkv, h, pre, alpha
-    return align_up(M * dm * 4, 256) + align_up(M * dm, 256) + align_up(M * 3 * hd * 4, 256) + align_up(M * hd * 4, 256)
-           + align_up(M * msa_attp(att) * 4, 256) + align_up(M * 4, 256);
+    Arena measure;
+    MsaSave s;
+    return msa_save_carve(measure, T, Lw, dm, heads * dk, att, &s);
 }
 size_t digat_msa_train_workspace_bytes(int T, int Lw, int dm, int heads, int dk, int att) {
-    const size_t M = (size_t)T * Lw, hd = (size_t)heads * dk, attp = msa_attp(att);
-    const size_t splits = align_up(digat_split_weights_bytes((int)(3 * hd), dm), 256) + align_up(digat_split_weights_bytes(att, (int)hd), 256)
-                          + align_up(digat_split_weights_bytes((int)hd, att), 256);
-    // backward: dh, dpre, dqkv, da2 partials, weight-gradient scratch (the largest of the four products)
-    size_t wg = digat_linear_bwd_weight_workspace((int)M, (int)(3 * hd), dm);
-    const size_t wg2 = digat_linear_bwd_weight_workspace((int)M, att, (int)hd);
-    if (wg2 > wg) wg = wg2;
-    wg = align_up(wg, 256) + align_up(3 * hd * (size_t)dm * 4, 256) + align_up(3 * hd * 4, 256);
-    const size_t dmp = msa_attp(dm);
-    const size_t bwd = align_up(M * hd * 4, 256) + align_up(M * attp * 4, 256) + align_up(M * 3 * hd * 4, 256)
-                       + align_up((size_t)T * att * 4, 256) + align_up((size_t)((T + 63) / 64) * att * 4, 256)
-                       + align_up(3 * hd * (size_t)dm * 4, 256) + align_up(digat_split_weights_bytes((int)dmp, (int)(3 * hd)), 256)
-                       + align_up(wg, 256);
-    return splits + bwd;
-}
-
-struct MsaSave { float* Ed; uint8_t* dmask; float *qkv, *h, *pre, *alpha; };
-static bool msa_save_carve(void* save, size_t bytes, int T, int Lw, int dm, int heads, int dk, int att, MsaSave* s) {
-    Arena a(save, bytes);
-    const size_t M = (size_t)T * Lw, hd = (size_t)heads * dk;
-    s->Ed = a.take<float>(M * dm); s->dmask = a.take<uint8_t>(M * dm); s->qkv = a.take<float>(M * 3 * hd); s->h = a.take<float>(M * hd);
-    s->pre = a.take<float>(M * msa_attp(att)); s->alpha = a.take<float>(M);
-    return a.ok;
-}
-static int msa_shape_ok(const digat_msa_params* p, int Lw) {
-    const int dm = p->word_embedding_dim, heads = p->head_num, dk = p->head_dim, att = p->attention_dim;
-    return dm > 0 && dm % 4 == 0 && heads > 0 && dk > 0 && dk <= MSA_MAX_DK && att > 0 && att % 4 == 0 && (heads * dk) % 4 == 0 && Lw <= 32;
+    Arena measure;
+    MsaTrainWs o;
+    return msa_train_carve(measure, T, Lw, dm, heads * dk, att, &o);
 }
 
 // out [T, heads*dk].  p_drop: dropout on the embedded tokens (newsEncoders.py:77); params' *_wsplit fields are not used (the
@@ -551,66 +592,37 @@ int digat_msa_fwd_train(const digat_msa_params* p, const int32_t* title_text, co
         return DIGAT_ERR_ARG;
     if (!msa_shape_ok(p, Lw)) return DIGAT_ERR_SHAPE;
     const int dm = p->word_embedding_dim, heads = p->head_num, dk = p->head_dim, att = p->attention_dim;
-    const int hd = heads * dk, attp = (int)msa_attp(att);
+    const int hd = heads * dk;
     if (T == 0) return DIGAT_OK;
+    Arena sa(save, save_bytes), w(workspace, workspace_bytes);
     MsaSave s;
-    if (save_bytes < digat_msa_train_save_bytes(T, Lw, dm, heads, dk, att) || !msa_save_carve(save, save_bytes, T, Lw, dm, heads, dk, att, &s))
-        return DIGAT_ERR_WORKSPACE;
-    if (workspace_bytes < digat_msa_train_workspace_bytes(T, Lw, dm, heads, dk, att)) return DIGAT_ERR_WORKSPACE;
-    Arena w(workspace, workspace_bytes);
-    void* qkv_split = w.take<char>(digat_split_weights_bytes(3 * hd, dm));
-    void* a1_split = w.take<char>(digat_split_weights_bytes(att, hd));
-    if (!w.ok) return DIGAT_ERR_WORKSPACE;
+    MsaTrainWs o;
+    msa_save_carve(sa, T, Lw, dm, hd, att, &s);
+    msa_train_carve(w, T, Lw, dm, hd, att, &o);
+    if (!sa.ok || !w.ok) return DIGAT_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const long M = (long)T * Lw;
-    {   // Ed = dropout(embedding[tokens])
-        const long total = M * (dm / 4);
-        int blocks = (int)((total + 255) / 256);
-        if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL(gather_embedding_kernel, dim3(blocks), dim3(256), 0, st, (const float4*)p->word_embedding, title_text,
-                           (float4*)s.Ed, M, dm / 4);
-        DIGAT_CHECK_LAUNCH();
-        if (p_drop > 0.f) T_TRY(digat_dropout_fwd(s.Ed, s.Ed, s.dmask, M * dm, p_drop, seed, stream));
-    }
+    // Ed = dropout(embedding[tokens])
+    T_TRY(launch_gather_embedding(p->word_embedding, title_text, s.Ed, M, dm, st));
+    if (p_drop > 0.f) T_TRY(digat_dropout_fwd(s.Ed, s.Ed, s.dmask, M * dm, p_drop, seed, stream));
     GemmArgs g = gemm_plain(s.Ed, dm, p->W_Q, p->b_Q, s.qkv, 3 * hd, (int)M, hd, dm, 0);
     g.w[1] = p->W_K; g.bias[1] = nullptr; g.y[1] = s.qkv + hd;
     g.w[2] = p->W_V; g.bias[2] = p->b_V; g.y[2] = s.qkv + 2 * hd;
     g.nsegs = 3;
     if (hd % 80 == 0 && dm >= 32 && M >= 2048) {
-        T_TRY(launch_split(p->W_Q, p->W_K, p->W_V, hd, 3, dm, qkv_split, st));
-        g.wsplit = (const unsigned short*)qkv_split;
+        T_TRY(launch_split(p->W_Q, p->W_K, p->W_V, hd, 3, dm, o.qkv_img, st));
+        g.wsplit = (const unsigned short*)o.qkv_img;
         if (g_train_bf16) g.x1_segs = 7;
     }
     T_TRY(launch_gemm(g, st, DIGAT_KERNEL_LINEAR));
-    {
-        MsaAttnArgs a{s.qkv, s.h, T, Lw, heads, dk};
-        const int ks = (dk + 3) / 4, kp = ks * 4;
-        const size_t lds = (size_t)4 * (2 * 32 * kp + 32 * 33) * 4;
-        switch (ks) {
-            case 1: hipLaunchKernelGGL(msa_attention_mfma_kernel<1>, dim3(T), dim3(256), lds, st, a); break;
-            case 2: hipLaunchKernelGGL(msa_attention_mfma_kernel<2>, dim3(T), dim3(256), lds, st, a); break;
-            case 3: hipLaunchKernelGGL(msa_attention_mfma_kernel<3>, dim3(T), dim3(256), lds, st, a); break;
-            case 4: hipLaunchKernelGGL(msa_attention_mfma_kernel<4>, dim3(T), dim3(256), lds, st, a); break;
-            case 5: hipLaunchKernelGGL(msa_attention_mfma_kernel<5>, dim3(T), dim3(256), lds, st, a); break;
-            case 6: hipLaunchKernelGGL(msa_attention_mfma_kernel<6>, dim3(T), dim3(256), lds, st, a); break;
-            case 7: hipLaunchKernelGGL(msa_attention_mfma_kernel<7>, dim3(T), dim3(256), lds, st, a); break;
-            default: hipLaunchKernelGGL(msa_attention_mfma_kernel<8>, dim3(T), dim3(256), lds, st, a); break;
-        }
-        DIGAT_CHECK_LAUNCH();
-    }
-    GemmArgs ga = gemm_plain(s.h, hd, p->A1, nullptr, s.pre, attp, (int)M, att, hd, 0);
+    T_TRY(launch_msa_attention(s.qkv, s.h, T, Lw, heads, dk, st));          // msa_shape_ok: Lw <= 32, the matrix-core kernel
+    const void* a1_img = nullptr;
     if (M >= 2048 && hd >= 32) {
-        T_TRY(launch_split(p->A1, p->A1, p->A1, att, 1, hd, a1_split, st));
-        GemmArgs gx = ga;
-        gx.nseg = attp; gx.wsplit = (const unsigned short*)a1_split;
-        if (g_train_bf16) gx.x1_segs = 7;
-        if (gemm_takes_row_list(gx)) ga = gx;
+        T_TRY(launch_split(p->A1, p->A1, p->A1, att, 1, hd, o.a1_img, st));
+        a1_img = o.a1_img;
     }
-    T_TRY(launch_gemm(ga, st, DIGAT_KERNEL_LINEAR));
-    MsaPoolArgs pa{s.pre, attp, p->b1, p->a2, s.h, title_mask, out, T, Lw, att, hd, s.alpha};
-    hipLaunchKernelGGL(msa_pool_kernel, dim3(T), dim3(256), 0, st, pa);
-    DIGAT_CHECK_LAUNCH();
-    return DIGAT_OK;
+    // bf16_ok = true: as the projections above, affine1 follows digat_set_train_precision (digat_cnn_fwd_train's does not)
+    return news_pool_fwd(s.h, hd, p->A1, a1_img, p->b1, p->a2, s.pre, title_mask, out, s.alpha, T, Lw, att, true, st);
 }
 
 // dout [T, heads*dk].  Written (not accumulated): row_grad [T*Lw, dm] with rows ld_row_grad floats apart — dm, or dm rounded up
@@ -624,94 +636,55 @@ int digat_msa_bwd(const digat_msa_params* p, const int32_t* title_text, const ui
         !da2 || !workspace || T < 0 || Lw <= 0) return DIGAT_ERR_ARG;
     if (!msa_shape_ok(p, Lw)) return DIGAT_ERR_SHAPE;
     const int dm = p->word_embedding_dim, heads = p->head_num, dk = p->head_dim, att = p->attention_dim;
-    const int hd = heads * dk, attp = (int)msa_attp(att), dmp = (int)msa_attp(dm);
+    const int hd = heads * dk, dmp = (int)msa_attp(dm);
     if (ld_row_grad != dm && ld_row_grad != dmp) return DIGAT_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    if (T == 0) {
-        const size_t wb = (size_t)hd * dm * 4;
-        if (hipMemsetAsync(dW_Q, 0, wb, st) != hipSuccess || hipMemsetAsync(dW_K, 0, wb, st) != hipSuccess ||
-            hipMemsetAsync(dW_V, 0, wb, st) != hipSuccess || hipMemsetAsync(db_Q, 0, (size_t)hd * 4, st) != hipSuccess ||
-            hipMemsetAsync(db_V, 0, (size_t)hd * 4, st) != hipSuccess || hipMemsetAsync(dA1, 0, (size_t)att * hd * 4, st) != hipSuccess ||
-            hipMemsetAsync(db1, 0, (size_t)att * 4, st) != hipSuccess || hipMemsetAsync(da2, 0, (size_t)att * 4, st) != hipSuccess)
-            return DIGAT_ERR_LAUNCH;
-        return DIGAT_OK;
-    }
+    const size_t wn = (size_t)hd * dm, hn = hd, an = att;          // floats of one projection's weight, of a bias, of an attention vector
+    if (T == 0) return zero_floats(st, {{dW_Q, wn}, {dW_K, wn}, {dW_V, wn}, {db_Q, hn}, {db_V, hn}, {dA1, an * hn}, {db1, an}, {da2, an}});
+    Arena sa(const_cast<void*>(save), save_bytes), w(workspace, workspace_bytes);
     MsaSave s;
-    if (save_bytes < digat_msa_train_save_bytes(T, Lw, dm, heads, dk, att) ||
-        !msa_save_carve(const_cast<void*>(save), save_bytes, T, Lw, dm, heads, dk, att, &s)) return DIGAT_ERR_WORKSPACE;
-    if (workspace_bytes < digat_msa_train_workspace_bytes(T, Lw, dm, heads, dk, att)) return DIGAT_ERR_WORKSPACE;
-    Arena w(workspace, workspace_bytes);
-    (void)w.take<char>(digat_split_weights_bytes(3 * hd, dm));
-    (void)w.take<char>(digat_split_weights_bytes(att, hd));
-    void* a1t_split = w.take<char>(digat_split_weights_bytes(hd, att));
+    MsaTrainWs o;
+    msa_save_carve(sa, T, Lw, dm, hd, att, &s);
+    msa_train_carve(w, T, Lw, dm, hd, att, &o);
+    if (!sa.ok || !w.ok) return DIGAT_ERR_WORKSPACE;
     const long M = (long)T * Lw;
-    float* dh = w.take<float>((size_t)M * hd);
-    float* dpre = w.take<float>((size_t)M * attp);
-    float* dqkv = w.take<float>((size_t)M * 3 * hd);
-    float* da2p = w.take<float>((size_t)T * att);
-    float* da2g = w.take<float>((size_t)((T + 63) / 64) * att);
-    float* wcat = w.take<float>((size_t)3 * hd * dm);
-    void* wcat_split = w.take<char>(digat_split_weights_bytes(dmp, 3 * hd));
-    size_t wgb = digat_linear_bwd_weight_workspace((int)M, 3 * hd, dm);
-    const size_t wgb2 = digat_linear_bwd_weight_workspace((int)M, att, hd);
-    if (wgb2 > wgb) wgb = wgb2;
-    void* wg = w.take<char>(wgb);
-    float* wg3 = w.take<float>(3 * (size_t)hd * dm);
-    float* db3g = w.take<float>(3 * (size_t)hd);
-    if (!w.ok) return DIGAT_ERR_WORKSPACE;
-    // pooling
-    MsaPoolBwdArgs pb{dout, s.h, s.pre, attp, p->b1, p->a2, s.alpha, title_mask, dh, dpre, da2p, T, Lw, att, hd};
-    hipLaunchKernelGGL(msa_pool_bwd_kernel, dim3(T), dim3(256), 0, st, pb);
-    DIGAT_CHECK_LAUNCH();
-    {
-        const int per = 64, G = (T + per - 1) / per;
-        hipLaunchKernelGGL(colsum_groups_kernel, dim3((att + 63) / 64, G), dim3(256), 0, st, (const float*)da2p, (long)att, da2g, T, att, per, (const int*)nullptr, 0);
-        DIGAT_CHECK_LAUNCH();
-        hipLaunchKernelGGL(colsum_kernel, dim3((att + 63) / 64), dim3(256), 0, st, (const float*)da2g, (long)att, da2, G, att, 0, (const int*)nullptr, 0);
-        DIGAT_CHECK_LAUNCH();
-    }
-    // affine1: dh += dpre A1; dA1 = dpre^T h; db1 = colsum(dpre)
-    if (x3_ok(M, hd, att)) T_TRY(digat_linear_bwd_input_x3(dpre, attp, p->A1, dh, hd, (int)M, att, hd, 1, a1t_split, st));
-    else T_TRY(digat_linear_bwd_input(dpre, attp, p->A1, dh, hd, (int)M, att, hd, 1, st));
-    T_TRY(digat_linear_bwd_weight(dpre, attp, s.h, hd, dA1, db1, (int)M, att, hd, 0, wg, wgb, st));
+    T_TRY(news_pool_bwd(dout, s.h, hd, s.pre, s.alpha, title_mask, p->A1, p->b1, p->a2, o.pool, o.wg, o.wgb, dA1, db1, da2, T, Lw, att, st));
     // ReLU + attention
     {
-        MsaAttnBwdArgs a{s.qkv, s.h, dh, dqkv, T, Lw, heads, dk};
+        MsaAttnBwdArgs a{s.qkv, s.h, o.pool.dh, o.dqkv, T, Lw, heads, dk};
         const size_t lds = (size_t)2 * 5 * MSA_BWD_IMG * 4;
         hipLaunchKernelGGL(msa_attention_bwd_kernel, dim3(T), dim3(128), lds, st, a);
         DIGAT_CHECK_LAUNCH();
     }
     // projections: dEd = dQ W_Q + dK W_K + dV W_V; dW_* = d*^T Ed; db_Q, db_V = column sums
     if (M >= 2048 && (3 * hd) % 8 == 0 && ld_row_grad == dmp) {
-        // one bf16x6 product over the stacked weights [W_Q; W_K; W_V] ([3 hd, dm], used as its transpose); the output's 80-column
-        // strips run over dm rounded up (zero weight rows): row_grad's rows are ld_row_grad = dmp floats apart
-        // (the stack is split from its three homes — round 6: three device copies into a concatenated scratch per call before)
-        (void)wcat;
-        T_TRY(launch_split(p->W_Q, p->W_K, p->W_V, dm, 1, 3 * hd, wcat_split, st, 2));
-        GemmArgs gx = gemm_plain(dqkv, 3 * hd, p->W_Q, nullptr, row_grad, ld_row_grad, (int)M, dm, 3 * hd, 0);
-        gx.nseg = dmp; gx.wsplit = (const unsigned short*)wcat_split;
+        // one bf16x6 product over the stacked weights [W_Q; W_K; W_V] ([3 hd, dm], used as its transpose), split from their three
+        // homes; the output's 80-column strips run over dm rounded up (zero weight rows): row_grad's rows are ld_row_grad = dmp
+        // floats apart
+        T_TRY(launch_split(p->W_Q, p->W_K, p->W_V, dm, 1, 3 * hd, o.wcat_img, st, 2));
+        GemmArgs gx = gemm_plain(o.dqkv, 3 * hd, p->W_Q, nullptr, row_grad, ld_row_grad, (int)M, dm, 3 * hd, 0);
+        gx.nseg = dmp; gx.wsplit = (const unsigned short*)o.wcat_img;
         if (g_train_bf16) gx.x1_segs = 7;
         if (!gemm_takes_row_list(gx)) return DIGAT_ERR_SHAPE;
-        const bool mask_here = p_drop > 0.f && dm % 4 == 0;          // round 6: the embedding dropout's backward in this product's epilogue
+        const bool mask_here = p_drop > 0.f && dm % 4 == 0;          // the embedding dropout's backward in this product's epilogue
         if (mask_here) { gx.dmask = s.dmask; gx.lddm = dm; gx.dscale = 1.f / (1.f - p_drop); gx.dmask_cols = dm; }
         T_TRY(launch_gemm(gx, st, DIGAT_KERNEL_LINEAR));
         if (mask_here) p_drop = 0.f;                                  // (the launch below is not needed)
     } else {
-        T_TRY(digat_linear_bwd_input(dqkv, 3 * hd, p->W_Q, row_grad, ld_row_grad, (int)M, hd, dm, 0, st));
-        T_TRY(digat_linear_bwd_input(dqkv + hd, 3 * hd, p->W_K, row_grad, ld_row_grad, (int)M, hd, dm, 1, st));
-        T_TRY(digat_linear_bwd_input(dqkv + 2 * hd, 3 * hd, p->W_V, row_grad, ld_row_grad, (int)M, hd, dm, 1, st));
+        T_TRY(digat_linear_bwd_input(o.dqkv, 3 * hd, p->W_Q, row_grad, ld_row_grad, (int)M, hd, dm, 0, st));
+        T_TRY(digat_linear_bwd_input(o.dqkv + hd, 3 * hd, p->W_K, row_grad, ld_row_grad, (int)M, hd, dm, 1, st));
+        T_TRY(digat_linear_bwd_input(o.dqkv + 2 * hd, 3 * hd, p->W_V, row_grad, ld_row_grad, (int)M, hd, dm, 1, st));
     }
     {   // the three weight gradients as one product dQKV^T Ed ([3 hd, dm]); db_Q / db_V are the column sums of its outer blocks
         // a caller that hands over dW_Q, dW_K, dW_V as the three blocks of ONE [3 hd, dm] buffer (newsEncoders.MsaFused does) gets the
-        // product written in place (round 6: three device copies per call less)
-        const bool stacked = dW_K == dW_Q + (size_t)hd * dm && dW_V == dW_Q + 2 * (size_t)hd * dm;
-        T_TRY(digat_linear_bwd_weight(dqkv, 3 * hd, s.Ed, dm, stacked ? dW_Q : wg3, db3g, (int)M, 3 * hd, dm, 0, wg, wgb, st));
-        const size_t wbytes = (size_t)hd * dm * 4;
-        if (!stacked && (hipMemcpyAsync(dW_Q, wg3, wbytes, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-                         hipMemcpyAsync(dW_K, wg3 + (size_t)hd * dm, wbytes, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-                         hipMemcpyAsync(dW_V, wg3 + 2 * (size_t)hd * dm, wbytes, hipMemcpyDeviceToDevice, st) != hipSuccess)) return DIGAT_ERR_LAUNCH;
-        if (hipMemcpyAsync(db_Q, db3g, (size_t)hd * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-            hipMemcpyAsync(db_V, db3g + 2 * hd, (size_t)hd * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return DIGAT_ERR_LAUNCH;
+        // product written in place
+        const bool stacked = dW_K == dW_Q + wn && dW_V == dW_Q + 2 * wn;
+        T_TRY(digat_linear_bwd_weight(o.dqkv, 3 * hd, s.Ed, dm, stacked ? dW_Q : o.wg3, o.db3g, (int)M, 3 * hd, dm, 0, o.wg, o.wgb, st));
+        if (!stacked && (hipMemcpyAsync(dW_Q, o.wg3, wn * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+                         hipMemcpyAsync(dW_K, o.wg3 + wn, wn * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+                         hipMemcpyAsync(dW_V, o.wg3 + 2 * wn, wn * 4, hipMemcpyDeviceToDevice, st) != hipSuccess)) return DIGAT_ERR_LAUNCH;
+        if (hipMemcpyAsync(db_Q, o.db3g, hn * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+            hipMemcpyAsync(db_V, o.db3g + 2 * hd, hn * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return DIGAT_ERR_LAUNCH;
     }
     if (p_drop > 0.f) {
         MsaRowDropArgs a{row_grad, ld_row_grad, s.dmask, M, dm, 1.f / (1.f - p_drop)};

@@ -18,6 +18,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import _lib
+from .training import _save_buffer, _seed
+
 
 class MultiHeadAttention(nn.Module):
     """layers.py:50-88 (no output projection, K without bias)."""
@@ -112,6 +115,21 @@ def merge_group3(w1, w2, w3):
     return W
 
 
+def _embedding_grad(tokens, row_grad, ld, table):
+    """The word-embedding gradient: the rows of ``row_grad`` ([T Lw, ld]) summed per token.  Index plumbing only here — the rows in
+    token order (stable); the sums run in the library (``digat_embedding_bwd``), in that fixed order."""
+    L = _lib.lib()
+    M, dm = tokens.numel(), table.shape[1]
+    stok, order = torch.sort(tokens.reshape(-1).to(torch.int64), stable=True)
+    stok, order = stok.to(torch.int32), order.to(torch.int32)
+    dtable = torch.zeros_like(table)
+    nb = L.digat_embedding_bwd_workspace_bytes(M, dm)
+    ews = _lib.workspace(nb, tokens.device, "emb_bwd")
+    _lib.check(L.digat_embedding_bwd(row_grad.data_ptr(), ld, order.data_ptr(), stok.data_ptr(), M, dm, dtable.data_ptr(),
+                                     ews.data_ptr(), nb, _lib.stream_ptr()), "digat_embedding_bwd")
+    return dtable
+
+
 class CnnFused(torch.autograd.Function):
     """The CNN news encoder as one library call per direction (``digat_cnn_fwd_train`` / ``digat_cnn_bwd``, then
     ``digat_embedding_bwd`` for the word-embedding rows).  ``conv`` is (W, b) for ``naive`` or (W1, b1, W2, b2, W3, b3) for ``group3``:
@@ -120,7 +138,6 @@ class CnnFused(torch.autograd.Function):
     @staticmethod
     def _merged(conv, dev):
         """(W [Kc, dm, taps], b [Kc]) fp32 contiguous."""
-        from . import _lib
         c = [w.detach().float().contiguous() for w in conv]
         if len(c) == 2:
             return c[0], c[1]
@@ -133,7 +150,6 @@ class CnnFused(torch.autograd.Function):
 
     @staticmethod
     def _params(table, W, b, A1, b1, a2):
-        from . import _lib
         P = _lib.CnnParams(word_embedding_dim=table.shape[1], kernel_num=W.shape[0], taps=W.shape[2], attention_dim=A1.shape[0])
         for name, w in zip(("word_embedding", "W", "b", "A1", "b1", "a2"), (table, W, b, A1, b1, a2)):
             setattr(P, name, w.data_ptr())
@@ -141,21 +157,18 @@ class CnnFused(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, tokens, mask, table, A1, b1, a2, p_drop, *conv):
-        from . import _lib
         L = _lib.lib()
         table_, A1_, b1_, a2_ = (w.detach().float().contiguous() for w in (table, A1, b1, a2))
         dev = _lib.require_device(tokens, mask, table_, A1_, b1_, a2_, *conv)
         W, b = CnnFused._merged(conv, dev)
         T, Lw = tokens.shape
-        dm, Kc, taps, att = table_.shape[1], W.shape[0], W.shape[2], A1_.shape[0]
+        dims = (T, Lw, table_.shape[1], W.shape[0], W.shape[2], A1_.shape[0])
         P = CnnFused._params(table_, W, b, A1_, b1_, a2_)
-        out = torch.empty((T, Kc), dtype=torch.float32, device=dev)
-        nsave = L.digat_cnn_train_save_bytes(T, Lw, dm, Kc, taps, att)
-        nws = L.digat_cnn_train_workspace_bytes(T, Lw, dm, Kc, taps, att)
-        save = torch.empty(max(int(nsave), 256), dtype=torch.uint8, device=dev)
-        ws = _lib.workspace(nws, dev, "cnn_train")
+        out = torch.empty((T, W.shape[0]), dtype=torch.float32, device=dev)
+        nsave, nws = L.digat_cnn_train_save_bytes(*dims), L.digat_cnn_train_workspace_bytes(*dims)
+        save, ws = _save_buffer(nsave, dev), _lib.workspace(nws, dev, "cnn_train")
         p = float(p_drop)
-        seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if p > 0 else 0
+        seed = _seed() if p > 0 else 0
         if T:
             _lib.check(L.digat_cnn_fwd_train(P, tokens.data_ptr(), mask.data_ptr(), out.data_ptr(), p, seed, T, Lw, save.data_ptr(), nsave,
                                              ws.data_ptr(), nws, _lib.stream_ptr()), "digat_cnn_fwd_train")
@@ -165,11 +178,10 @@ class CnnFused(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        from . import _lib
         L = _lib.lib()
         tokens, mask, save, table, W, b, A1, b1, a2 = ctx.saved_tensors
         T, Lw = tokens.shape
-        dm, Kc, taps, att = table.shape[1], W.shape[0], W.shape[2], A1.shape[0]
+        dm, Kc, att = table.shape[1], W.shape[0], A1.shape[0]
         dev = tokens.device
         f = dict(dtype=torch.float32, device=dev)
 
@@ -192,16 +204,7 @@ class CnnFused(torch.autograd.Function):
         _lib.check(L.digat_cnn_bwd(P, tokens.data_ptr(), mask.data_ptr(), dout.data_ptr(), ctx.p, ctx.seed, save.data_ptr(), nsave,
                                    row_grad.data_ptr(), dm, dW.data_ptr(), db.data_ptr(), dA1.data_ptr(), db1.data_ptr(), da2.data_ptr(),
                                    T, Lw, ws.data_ptr(), nws, _lib.stream_ptr()), "digat_cnn_bwd")
-        dtable = None
-        if ctx.needs_input_grad[2]:
-            # index plumbing only: the rows in token order (stable); the sums run in the library, in that fixed order
-            stok, order = torch.sort(tokens.reshape(-1).to(torch.int64), stable=True)
-            stok, order = stok.to(torch.int32), order.to(torch.int32)
-            dtable = torch.zeros_like(table)
-            nb = L.digat_embedding_bwd_workspace_bytes(T * Lw, dm)
-            ews = _lib.workspace(nb, dev, "emb_bwd")
-            _lib.check(L.digat_embedding_bwd(row_grad.data_ptr(), dm, order.data_ptr(), stok.data_ptr(), T * Lw, dm, dtable.data_ptr(),
-                                             ews.data_ptr(), nb, _lib.stream_ptr()), "digat_embedding_bwd")
+        dtable = _embedding_grad(tokens, row_grad, dm, table) if ctx.needs_input_grad[2] else None
         return (None, None, dtable, dA1, db1, da2.view(ctx.a2_shape), None, *conv_grads(dW, db))
 
 
@@ -211,7 +214,6 @@ class MsaFused(torch.autograd.Function):
 
     @staticmethod
     def _params(table, WQ, bQ, WK, WV, bV, A1, b1, a2, heads, dk):
-        from . import _lib
         P = _lib.MsaParams(word_embedding_dim=table.shape[1], head_num=heads, head_dim=dk, attention_dim=A1.shape[0])
         for name, w in zip(("word_embedding", "W_Q", "b_Q", "W_K", "W_V", "b_V", "A1", "b1", "a2"), (table, WQ, bQ, WK, WV, bV, A1, b1, a2)):
             setattr(P, name, w.data_ptr())
@@ -219,20 +221,17 @@ class MsaFused(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, tokens, mask, table, WQ, bQ, WK, WV, bV, A1, b1, a2, heads, dk, p_drop):
-        from . import _lib
         L = _lib.lib()
         ws_ = [w.detach().float().contiguous() for w in (table, WQ, bQ, WK, WV, bV, A1, b1, a2)]
         dev = _lib.require_device(tokens, mask, *ws_)
         T, Lw = tokens.shape
-        dm, att = ws_[0].shape[1], ws_[6].shape[0]
+        dims = (T, Lw, ws_[0].shape[1], heads, dk, ws_[6].shape[0])
         P = MsaFused._params(*ws_, heads, dk)
         out = torch.empty((T, heads * dk), dtype=torch.float32, device=dev)
-        nsave = L.digat_msa_train_save_bytes(T, Lw, dm, heads, dk, att)
-        nws = L.digat_msa_train_workspace_bytes(T, Lw, dm, heads, dk, att)
-        save = torch.empty(max(int(nsave), 256), dtype=torch.uint8, device=dev)
-        ws = _lib.workspace(nws, dev, "msa_train")
+        nsave, nws = L.digat_msa_train_save_bytes(*dims), L.digat_msa_train_workspace_bytes(*dims)
+        save, ws = _save_buffer(nsave, dev), _lib.workspace(nws, dev, "msa_train")
         p = float(p_drop)
-        seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if p > 0 else 0
+        seed = _seed() if p > 0 else 0
         if T:
             _lib.check(L.digat_msa_fwd_train(P, tokens.data_ptr(), mask.data_ptr(), out.data_ptr(), p, seed, T, Lw, save.data_ptr(),
                                              nsave, ws.data_ptr(), nws, _lib.stream_ptr()), "digat_msa_fwd_train")
@@ -242,7 +241,6 @@ class MsaFused(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        from . import _lib
         L = _lib.lib()
         tokens, mask, save, *ws_ = ctx.saved_tensors
         table, WQ, bQ, WK, WV, bV, A1, b1, a2 = ws_
@@ -268,20 +266,14 @@ class MsaFused(torch.autograd.Function):
                                    row_grad.data_ptr(), ld, dWQ.data_ptr(), dbQ.data_ptr(), dWK.data_ptr(), dWV.data_ptr(), dbV.data_ptr(),
                                    dA1.data_ptr(), db1.data_ptr(), da2.data_ptr(), T, Lw, ws.data_ptr(), nws, _lib.stream_ptr()),
                    "digat_msa_bwd")
-        dtable = None
-        if ctx.needs_input_grad[2]:
-            # index plumbing only: the rows in token order (stable); the sums run in the library, in that fixed order
-            stok, order = torch.sort(tokens.reshape(-1).to(torch.int64), stable=True)
-            stok, order = stok.to(torch.int32), order.to(torch.int32)
-            dtable = torch.zeros_like(table)
-            nb = L.digat_embedding_bwd_workspace_bytes(T * Lw, dm)
-            ews = _lib.workspace(nb, dev, "emb_bwd")
-            _lib.check(L.digat_embedding_bwd(row_grad.data_ptr(), ld, order.data_ptr(), stok.data_ptr(), T * Lw, dm, dtable.data_ptr(),
-                                             ews.data_ptr(), nb, _lib.stream_ptr()), "digat_embedding_bwd")
+        dtable = _embedding_grad(tokens, row_grad, ld, table) if ctx.needs_input_grad[2] else None
         return None, None, dtable, dWQ, dbQ, dWK, dWV, dbV, dA1, db1, da2.view_as(a2), None, None, None
 
 
 class NewsEncoder(nn.Module):
+    """What both encoders share: the word embedding and its dropout, and the call path of the HIP kernels.  A subclass names its
+    library entry (``_hip_entry``) and builds its parameter block (``_hip_tensors`` / ``_build_hip_params``)."""
+
     def __init__(self, config):
         super().__init__()
         self.word_embedding_dim = config.word_embedding_dim
@@ -296,6 +288,37 @@ class NewsEncoder(nn.Module):
         B, n = title_text.shape[:2]
         w = self.dropout(self.word_embedding(title_text.long()))
         return w.view(B * n, self.max_sentence_length, self.word_embedding_dim), B, n
+
+    @staticmethod
+    def _flat(title_text, title_mask):
+        """[..., Lw] -> tokens int32 [T, Lw], mask uint8 [T, Lw], contiguous: what the library reads."""
+        Lw = title_text.shape[-1]
+        return title_text.reshape(-1, Lw).to(torch.int32).contiguous(), (title_mask.reshape(-1, Lw) != 0).to(torch.uint8).contiguous()
+
+    def _hip_params(self):
+        """(parameter block, the tensors it points into) for inference, rebuilt when a parameter has moved or been written."""
+        ws = self._hip_tensors()
+        key = tuple((w.data_ptr(), w._version) for w in ws)
+        cached = getattr(self, "_hip_cache", None)
+        if cached is None or cached[0] != key:
+            cached = self._hip_cache = (key, self._build_hip_params(ws))
+        return cached[1]
+
+    def encode_hip(self, title_text, title_mask):
+        """title_text / title_mask [B, n, Lw] (or [T, Lw]) on the GPU -> [B, n, news_embedding_dim] ([T, ...])."""
+        tok, msk = self._flat(title_text, title_mask)
+        dev = _lib.require_device(tok, msk)
+        T, Lw = tok.shape
+        P, _keep = self._hip_params()
+        out = torch.empty((T, self.news_embedding_dim), dtype=torch.float32, device=dev)
+        if T:
+            L = _lib.lib()
+            name, dims = self._hip_entry(P)
+            nbytes = getattr(L, f"digat_{name}_workspace_bytes")(T, Lw, *dims)
+            ws = _lib.workspace(nbytes, dev, name)
+            _lib.check(getattr(L, f"digat_{name}_fwd")(P, tok.data_ptr(), msk.data_ptr(), out.data_ptr(), T, Lw, ws.data_ptr(), nbytes,
+                                                      _lib.stream_ptr()), f"digat_{name}_fwd")
+        return out.view(*title_text.shape[:-1], self.news_embedding_dim)
 
 
 class MSA(NewsEncoder):
@@ -326,37 +349,29 @@ class MSA(NewsEncoder):
         h = F.relu(self.multiheadSelfattention(w))
         return self.attention(h, mask=title_mask.view(B * n, -1)).view(B, n, self.news_embedding_dim)
 
+    def _hip_tensors(self):
+        mha, att = self.multiheadSelfattention, self.attention
+        return [self.word_embedding.weight, mha.W_Q.weight, mha.W_Q.bias, mha.W_K.weight, mha.W_V.weight, mha.W_V.bias,
+                att.affine1.weight, att.affine1.bias, att.affine2.weight]
+
     def train_hip(self, title_text, title_mask):
         """Forward with autograd through the HIP pair (newsEncoders.py:70-82; dropout on the embedded tokens in train mode)."""
-        shape = title_text.shape
-        Lw = shape[-1]
-        mha, att = self.multiheadSelfattention, self.attention
-        out = MsaFused.apply(title_text.reshape(-1, Lw).to(torch.int32).contiguous(),
-                             (title_mask.reshape(-1, Lw) != 0).to(torch.uint8).contiguous(),
-                             self.word_embedding.weight, mha.W_Q.weight, mha.W_Q.bias, mha.W_K.weight, mha.W_V.weight, mha.W_V.bias,
-                             att.affine1.weight, att.affine1.bias, att.affine2.weight, mha.h, mha.d_k,
+        mha = self.multiheadSelfattention
+        out = MsaFused.apply(*self._flat(title_text, title_mask), *self._hip_tensors(), mha.h, mha.d_k,
                              float(self.dropout.p) if self.training else 0.0)
-        return out.view(*shape[:-1], self.news_embedding_dim)
+        return out.view(*title_text.shape[:-1], self.news_embedding_dim)
 
     # ---- inference on the HIP kernels (digat_news.inc)
-    def _hip_params(self):
-        from . import _lib
-        ws = [self.word_embedding.weight, self.multiheadSelfattention.W_Q.weight, self.multiheadSelfattention.W_Q.bias,
-              self.multiheadSelfattention.W_K.weight, self.multiheadSelfattention.W_V.weight,
-              self.multiheadSelfattention.W_V.bias, self.attention.affine1.weight, self.attention.affine1.bias,
-              self.attention.affine2.weight]
-        key = tuple((w.data_ptr(), w._version) for w in ws)
-        cached = getattr(self, "_hip_cache", None)
-        if cached is not None and cached[0] == key:
-            return cached[1]
+    def _hip_entry(self, P):
+        return "msa", (P.word_embedding_dim, P.head_num, P.head_dim, P.attention_dim)
+
+    def _build_hip_params(self, ws):
         L = _lib.lib()
         mha = self.multiheadSelfattention
         dm, hd, att = self.word_embedding_dim, mha.h * mha.d_k, self.attention.affine1.out_features
         dev = ws[0].device
         keep = [w.detach().float().contiguous() for w in ws]
-        P = _lib.MsaParams(word_embedding_dim=dm, head_num=mha.h, head_dim=mha.d_k, attention_dim=att)
-        for name, w in zip(("word_embedding", "W_Q", "b_Q", "W_K", "W_V", "b_V", "A1", "b1", "a2"), keep):
-            setattr(P, name, w.data_ptr())
+        P = MsaFused._params(*keep, mha.h, mha.d_k)
         if hd % 80 == 0 and dm % 4 == 0 and dm >= 32:          # the bf16x6 matrix-core path (fp32-grade)
             qkv = _lib.split_buffer(L.digat_msa_split_bytes(dm, mha.h, mha.d_k), dev)
             _lib.check(L.digat_split_msa_weights(keep[1].data_ptr(), keep[3].data_ptr(), keep[4].data_ptr(), dm, hd,
@@ -366,28 +381,7 @@ class MSA(NewsEncoder):
             _lib.check(L.digat_split_weights(keep[6].data_ptr(), att, hd, a1.data_ptr(), _lib.GEMM_BF16X6, _lib.stream_ptr()), "digat_split_weights")
             P.qkv_wsplit, P.a1_wsplit = qkv.data_ptr(), a1.data_ptr()
             keep += [qkv, a1]
-        self._hip_cache = (key, (P, keep))
         return P, keep
-
-    def encode_hip(self, title_text, title_mask):
-        """title_text / title_mask [B, n, Lw] (or [T, Lw]) on the GPU -> [B, n, news_embedding_dim] ([T, ...])."""
-        from . import _lib
-        shape = title_text.shape
-        Lw = shape[-1]
-        tok = title_text.reshape(-1, Lw).to(torch.int32).contiguous()
-        msk = (title_mask.reshape(-1, Lw) != 0).to(torch.uint8).contiguous()
-        dev = _lib.require_device(tok, msk)
-        T = tok.shape[0]
-        P, _keep = self._hip_params()
-        out = torch.empty((T, self.news_embedding_dim), dtype=torch.float32, device=dev)
-        if T:
-            L = _lib.lib()
-            mha = self.multiheadSelfattention
-            nbytes = L.digat_msa_workspace_bytes(T, Lw, self.word_embedding_dim, mha.h, mha.d_k, self.attention.affine1.out_features)
-            ws = _lib.workspace(nbytes, dev, "msa")
-            _lib.check(L.digat_msa_fwd(P, tok.data_ptr(), msk.data_ptr(), out.data_ptr(), T, Lw, ws.data_ptr(), nbytes,
-                                       _lib.stream_ptr()), "digat_msa_fwd")
-        return out.view(*shape[:-1], self.news_embedding_dim)
 
 
 class CNN(NewsEncoder):
@@ -422,32 +416,25 @@ class CNN(NewsEncoder):
         h = self.dropout(self.conv(w.permute(0, 2, 1)).permute(0, 2, 1))
         return self.attention(h, mask=title_mask.view(B * n, -1)).view(B, n, self.news_embedding_dim)
 
-    def _conv_tensors(self):
-        out = []
+    def _hip_tensors(self):
+        """table, A1, b1, a2, then (weight, bias) of every convolution branch."""
+        att = self.attention
+        out = [self.word_embedding.weight, att.affine1.weight, att.affine1.bias, att.affine2.weight]
         for c in self.conv.branches():
             out += [c.weight, c.bias]
         return out
 
     def train_hip(self, title_text, title_mask):
         """Forward with autograd through the HIP pair (both dropouts of newsEncoders.py:46-48 live in train mode)."""
-        shape = title_text.shape
-        Lw = shape[-1]
-        att = self.attention
-        out = CnnFused.apply(title_text.reshape(-1, Lw).to(torch.int32).contiguous(),
-                             (title_mask.reshape(-1, Lw) != 0).to(torch.uint8).contiguous(),
-                             self.word_embedding.weight, att.affine1.weight, att.affine1.bias, att.affine2.weight,
-                             float(self.dropout.p) if self.training else 0.0, *self._conv_tensors())
-        return out.view(*shape[:-1], self.news_embedding_dim)
+        ws = self._hip_tensors()
+        out = CnnFused.apply(*self._flat(title_text, title_mask), *ws[:4], float(self.dropout.p) if self.training else 0.0, *ws[4:])
+        return out.view(*title_text.shape[:-1], self.news_embedding_dim)
 
     # ---- inference on the HIP kernels (digat_cnn.inc)
-    def _hip_params(self):
-        from . import _lib
-        att = self.attention
-        ws = [self.word_embedding.weight, att.affine1.weight, att.affine1.bias, att.affine2.weight] + self._conv_tensors()
-        key = tuple((w.data_ptr(), w._version) for w in ws)
-        cached = getattr(self, "_hip_cache", None)
-        if cached is not None and cached[0] == key:
-            return cached[1]
+    def _hip_entry(self, P):
+        return "cnn", (P.word_embedding_dim, P.kernel_num, P.taps, P.attention_dim)
+
+    def _build_hip_params(self, ws):
         L = _lib.lib()
         dev = ws[0].device
         table, A1, b1, a2 = (w.detach().float().contiguous() for w in ws[:4])
@@ -462,24 +449,4 @@ class CNN(NewsEncoder):
             _lib.check(L.digat_split_weights(A1.data_ptr(), natt, Kc, a1.data_ptr(), _lib.GEMM_BF16X6, _lib.stream_ptr()), "digat_split_weights")
             P.w_split, P.a1_wsplit = img.data_ptr(), a1.data_ptr()
             keep += [img, a1]
-        self._hip_cache = (key, (P, keep))
         return P, keep
-
-    def encode_hip(self, title_text, title_mask):
-        """title_text / title_mask [B, n, Lw] (or [T, Lw]) on the GPU -> [B, n, news_embedding_dim] ([T, ...])."""
-        from . import _lib
-        shape = title_text.shape
-        Lw = shape[-1]
-        tok = title_text.reshape(-1, Lw).to(torch.int32).contiguous()
-        msk = (title_mask.reshape(-1, Lw) != 0).to(torch.uint8).contiguous()
-        dev = _lib.require_device(tok, msk)
-        T = tok.shape[0]
-        P, _keep = self._hip_params()
-        out = torch.empty((T, self.news_embedding_dim), dtype=torch.float32, device=dev)
-        if T:
-            L = _lib.lib()
-            nbytes = L.digat_cnn_workspace_bytes(T, Lw, P.word_embedding_dim, P.kernel_num, P.taps, P.attention_dim)
-            ws = _lib.workspace(nbytes, dev, "cnn")
-            _lib.check(L.digat_cnn_fwd(P, tok.data_ptr(), msk.data_ptr(), out.data_ptr(), T, Lw, ws.data_ptr(), nbytes, _lib.stream_ptr()),
-                       "digat_cnn_fwd")
-        return out.view(*shape[:-1], self.news_embedding_dim)

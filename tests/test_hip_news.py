@@ -256,3 +256,24 @@ def test_msa_training_shapes_against_the_oracle_autograd(T_, Lw, V, dm, h, dk, a
     for k, v in enc.named_parameters():
         assert v.grad is not None, k
         _close(v.grad, p[k].grad.numpy(), "grad " + k)
+
+
+def test_msa_bwd_without_titles_returns_ok_and_zero_gradients():
+    """digat_msa_bwd at T = 0 (the status the CPU suite cannot take: tests/test_news_abi_cpu.py): 0, nothing read, every gradient
+    buffer zero-filled, whatever the save / workspace sizes."""
+    from digat_amd import _lib
+    dev = _dev()
+    dm, h, dk, att, Lw = 32, 2, 8, 12, 16
+    hd = h * dk
+    a = torch.empty(256, dtype=torch.uint8, device=dev)            # stands in for every buffer that is not touched
+    P = _lib.MsaParams(word_embedding_dim=dm, head_num=h, head_dim=dk, attention_dim=att)
+    for k in ("word_embedding", "W_Q", "b_Q", "W_K", "W_V", "b_V", "A1", "b1", "a2"):
+        setattr(P, k, a.data_ptr())
+    g = {k: torch.full(shape, 7.0, device=dev) for k, shape in (("dW_Q", (hd, dm)), ("db_Q", (hd,)), ("dW_K", (hd, dm)), ("dW_V", (hd, dm)),
+                                                                ("db_V", (hd,)), ("dA1", (att, hd)), ("db1", (att,)), ("da2", (att,)))}
+    rc = _lib.lib().digat_msa_bwd(P, a.data_ptr(), a.data_ptr(), a.data_ptr(), 0.2, a.data_ptr(), 0, a.data_ptr(), dm,
+                                  *(t.data_ptr() for t in g.values()), 0, Lw, a.data_ptr(), 0, _lib.stream_ptr())
+    torch.cuda.synchronize()
+    assert rc == 0
+    for k, t in g.items():
+        assert float(t.abs().max()) == 0.0, k
