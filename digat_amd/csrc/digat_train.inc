@@ -471,6 +471,7 @@ struct PoolBwdArgs {
 __global__ void __launch_bounds__(256) attn_pool_bwd_kernel(const PoolBwdArgs g) {
     __shared__ float sd[DIGAT_MAX_NODES];
     __shared__ float sda[DIGAT_MAX_NODES];
+    __shared__ float sal[DIGAT_MAX_NODES];      // alpha of the row: the last loop reads it between its stores (no reload from memory)
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int d4 = g.d >> 2, n = g.n;
     const float4* F4 = reinterpret_cast<const float4*>(g.feat + (long)b * g.ld_b);
@@ -485,7 +486,10 @@ __global__ void __launch_bounds__(256) attn_pool_bwd_kernel(const PoolBwdArgs g)
             part = fmaf(x.w, q.w, fmaf(x.z, q.z, fmaf(x.y, q.y, fmaf(x.x, q.x, part))));
         }
         part = wave_sum(part);
-        if (lane == 0) sd[j] = part;
+        // a weight of exactly zero (a masked node of a row that has live ones) takes no part: its row may never have been written
+        // (dead nodes of a larger news graph) and 0 x NaN would poison dot, dkq and with them the whole row — the forward's rule.
+        // Its dalpha is dropped here, so its da is 0 and dx_j = 0 x kq + 0 x dout = 0; below its x_j is zeroed before it meets dkq.
+        if (lane == 0) sd[j] = al[j] != 0.f ? part : 0.f;
     }
     __syncthreads();
     if (tid < n) {
@@ -493,14 +497,16 @@ __global__ void __launch_bounds__(256) attn_pool_bwd_kernel(const PoolBwdArgs g)
         for (int k = 0; k < n; ++k) dot += al[k] * sd[k];
         const bool masked = g.mask[(long)b * n + tid] == 0;
         sda[tid] = masked ? 0.f : al[tid] * (sd[tid] - dot) / g.sqrt_d;
+        sal[tid] = al[tid];
     }
     __syncthreads();
     for (int c4 = tid; c4 < d4; c4 += 256) {
         const float4 q = D4[c4], k = K4[c4];
         float4 dk = f4_zero();
         for (int j = 0; j < n; ++j) {
-            const float a = al[j], da = sda[j];
-            const float4 x = F4[(long)j * d4 + c4];
+            const float a = sal[j], da = sda[j];
+            const float4 xl = F4[(long)j * d4 + c4];
+            const float4 x = a != 0.f ? xl : f4_zero();        // (a select after the load, not a branch: the loads stay in flight together)
             float4 dx = make_float4(fmaf(da, k.x, a * q.x), fmaf(da, k.y, a * q.y), fmaf(da, k.z, a * q.z), fmaf(da, k.w, a * q.w));
             if (g.accumulate_dfeat) dx = f4_add(DF4[(long)j * d4 + c4], dx);
             DF4[(long)j * d4 + c4] = dx;

@@ -13,7 +13,8 @@ set of ``torch.autograd.Function``s whose forward AND backward are calls into ``
 
 One library call per function and direction: a training step is ~45 calls from the host; the
 finer-grained Functions below (Linear, MatmulW, AttnPool, TopicPool, GateMix, ReluRes, XattnLayer) wrap the primitives
-those calls are composed of and are kept for tests and for callers that build other encoders from them.
+those calls are composed of and are kept for tests (tests/test_hip_train_primitives.py holds each to float64 autograd) and for callers
+that build other encoders from them.
 
 PyTorch does what it does for the reference too: owns the tensors, records the graph, and runs the
 few pure data-movement ops (``cat``, ``select``, ``expand``, ``+`` of two contexts).  There is no
