@@ -239,7 +239,7 @@ _ext = None
 
 def ext():
     """The thin torch extension over the same C ABI (csrc/digat_torch_ext.cpp: tensors in, raw pointers + the current HIP stream
-    out), or None when it has not been built or is switched off — the ctypes table above then binds the same entry points.  A
+    out), or None when it has not been built or is switched off — ``binding()`` then hands out its ctypes twin.  A
     different library build named by DIGAT_HIP_LIB is only reachable through ctypes (the extension is linked to lib/libdigat_hip.so)."""
     global _ext
     if not USE_TORCH_EXT or os.environ.get("DIGAT_HIP_LIB"):
@@ -257,6 +257,16 @@ def ext():
                 raise DigatHipError("digat_torch_ext.so and libdigat_hip.so disagree about the ABI version: rebuild (python -m digat_amd.build)")
             _ext = mod
     return _ext or None
+
+
+def binding():
+    """The call surface of the hot entry points: the torch extension when ``ext()`` has one, else its ctypes twin
+    (_ctypes_binding.py: the same functions, arguments and returns).  The one place where the choice between the two is made."""
+    X = ext()
+    if X is not None:
+        return X
+    from . import _ctypes_binding
+    return _ctypes_binding
 
 
 def check(code: int, what: str) -> None:
@@ -331,6 +341,11 @@ def split_buffer(nbytes: int, device: torch.device) -> torch.Tensor:
     if device.type == "cuda":
         weakref.finalize(buf, lib().digat_forget_split_image, C.c_void_p(buf.data_ptr())).atexit = False
     return buf
+
+
+def save_buffer(nbytes: int, device: torch.device) -> torch.Tensor:
+    """Device bytes a training forward leaves for its backward (digat_*_train_save_bytes): owned by the autograd graph, never reused."""
+    return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
 
 
 _workspaces = {}

@@ -5,8 +5,9 @@
 // model.py:73,88), checks what the C ABI assumes about them — same CUDA device, dtype, contiguity, shapes — takes PyTorch's CURRENT
 // HIP stream, and forwards raw device pointers to libdigat_hip.so.  The parameter block (digat_params: pointers into the module's
 // own nn.Parameters and the split weight images) is built once per weight version on the Python side and arrives as an address.
-// digat_amd/_lib.py loads this module when it has been built (digat_amd/build.py) and binds the same entry points through ctypes
-// otherwise: both roads end in the same shared object, there is no CPU path on either.
+// digat_amd/_lib.py hands this module to the call sites when it has been built (digat_amd/build.py), and digat_amd/_ctypes_binding.py —
+// the same functions, argument for argument, over ctypes — otherwise: both roads end in the same shared object, there is no CPU
+// path on either.  A function added or changed here is added or changed there (tests/test_abi_cpu.py compares the two).
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 #include <c10/core/DeviceGuard.h>
@@ -174,6 +175,12 @@ const void* image_of(const c10::optional<at::Tensor>& image, const at::Tensor& l
          (size_t)image->numel() >= bytes, "image: a contiguous uint8 tensor on the inputs' device holding the whole split image");
     return image->data_ptr();
 }
+// the uint8 buffer a *_fwd_train call returned, handed back to its backward: on the inputs' device, at least `bytes` long
+const void* save_of(const at::Tensor& save, const at::Tensor& like, size_t bytes) {
+    need(save.is_cuda() && save.device() == like.device() && save.scalar_type() == at::kByte && save.is_contiguous() && (size_t)save.numel() >= bytes,
+         "save: the uint8 buffer the forward call returned (same device, same shapes)");
+    return save.data_ptr();
+}
 
 std::tuple<at::Tensor, at::Tensor> xattn_fwd_train(const at::Tensor& Xd, const at::Tensor& A, const at::Tensor& cvec, const at::Tensor& W,
                                                    const at::Tensor& bW, const at::Tensor& F1, const at::Tensor& F2, const at::Tensor& F3,
@@ -205,15 +212,14 @@ std::vector<at::Tensor> xattn_bwd(const at::Tensor& dOut, const at::Tensor& out,
     shape(dOut, {B, n, d}, "dOut"); shape(out, {B, n, d}, "out"); shape(A, {B, n, n}, "A"); shape(cvec, {B, d}, "ctx");
     shape(W, {d, d}, "W"); shape(F1, {d, d}, "F1"); shape(F2, {d, d}, "F2"); shape(F3, {d, d}, "F3"); need(a.numel() == d, "a [1,d] expected");
     const size_t nsave = digat_xattn_train_save_bytes(B, n, d), nws = digat_xattn_train_workspace_bytes(B, n, d);
-    need(save.is_cuda() && save.device() == Xd.device() && save.scalar_type() == at::kByte && save.is_contiguous() && (size_t)save.numel() >= nsave,
-         "save: the uint8 buffer the forward call returned (same device, same shapes)");
+    const void* saved = save_of(save, Xd, nsave);
     at::Tensor ws = scratch(Xd, nws);
     at::Tensor dX = at::empty_like(Xd), dc = at::empty_like(cvec), dW3 = at::empty({3, W.size(0), W.size(1)}, W.options()), dF3 = at::empty_like(W);
     at::Tensor dbW = at::empty({d}, W.options()), db3 = at::empty({d}, W.options()), da = at::empty({d}, W.options());
     float* w3 = out_f32(dW3);
     const size_t dd = (size_t)W.size(0) * W.size(1);
     check(digat_xattn_bwd(f32(dOut, Xd, "dOut"), f32(out, Xd, "out"), f32(Xd, Xd, "Xd"), bytes(A, Xd, "A"), f32(cvec, Xd, "ctx"), f32(W, Xd, "W"),
-                          f32(F1, Xd, "F1"), f32(F2, Xd, "F2"), f32(F3, Xd, "F3"), f32(a, Xd, "a"), (float)p, (float)p_in, save.data_ptr(), nsave, out_f32(dX),
+                          f32(F1, Xd, "F1"), f32(F2, Xd, "F2"), f32(F3, Xd, "F3"), f32(a, Xd, "a"), (float)p, (float)p_in, saved, nsave, out_f32(dX),
                           out_f32(dc), w3, out_f32(dbW), w3 + dd, w3 + 2 * dd, out_f32(dF3), out_f32(db3), out_f32(da), B, n, d, ws.data_ptr(), nws,
                           image_of(image, Xd, digat_split_job_bytes(d, d, 1, 3)), (int)xattn_mode, stream_of(Xd)), "digat_xattn_bwd");
     return {dX, dc, dW3, dbW, dF3, db3, da};
@@ -245,12 +251,11 @@ at::Tensor news_ctx_bwd(const at::Tensor& dout, const at::Tensor& X, const at::T
     shape(dout, {B, d}, "dout"); shape(mask, {B, N}, "mask"); shape(Kc, {d, d}, "Kc"); shape(Qc, {d, d}, "Qc"); shape(Wg, {d, 2 * d}, "Wg");
     shape(grads[0], {d, d}, "dKc"); shape(grads[1], {d, d}, "dQc"); shape(grads[2], {d}, "dbQc"); shape(grads[3], {d, 2 * d}, "dWg"); shape(grads[4], {d}, "dbg");
     const size_t nsave = digat_news_ctx_train_save_bytes(B, N, d), nws = digat_news_ctx_train_workspace_bytes(B, N, d);
-    need(save.is_cuda() && save.device() == X.device() && save.scalar_type() == at::kByte && save.is_contiguous() && (size_t)save.numel() >= nsave,
-         "save: the uint8 buffer the forward call returned (same device, same shapes)");
+    const void* saved = save_of(save, X, nsave);
     at::Tensor ws = scratch(X, nws), dX = at::empty_like(X);
     for (auto& g : grads) f32(g, X, "parameter gradient");
     check(digat_news_ctx_bwd(f32(dout, X, "dout"), f32(X, X, "X"), bytes(mask, X, "mask"), f32(Kc, X, "Kc"), f32(Qc, X, "Qc"), f32(Wg, X, "Wg"), (float)p,
-                             save.data_ptr(), nsave, out_f32(dX), out_f32(grads[0]), out_f32(grads[1]), out_f32(grads[2]), out_f32(grads[3]),
+                             saved, nsave, out_f32(dX), out_f32(grads[0]), out_f32(grads[1]), out_f32(grads[2]), out_f32(grads[3]),
                              out_f32(grads[4]), B, N, d, accumulate ? 1 : 0, ws.data_ptr(), nws, stream_of(X)), "digat_news_ctx_bwd");
     return dX;
 }
@@ -294,12 +299,11 @@ std::tuple<at::Tensor, at::Tensor> user_ctx_bwd(const at::Tensor& dout, const at
     for (int k = 0; k < 5; ++k) shape(grads[k], {d, d}, "weight gradient");
     for (int k = 5; k < 8; ++k) shape(grads[k], {d}, "bias gradient");
     const size_t nsave = digat_user_ctx_train_save_bytes(B, U, (int)H, (int)C1, d), nws = digat_user_ctx_train_workspace_bytes(B, U, (int)H, (int)C1, d);
-    need(save.is_cuda() && save.device() == Xu.device() && save.scalar_type() == at::kByte && save.is_contiguous() && (size_t)save.numel() >= nsave,
-         "save: the uint8 buffer the forward call returned (same device, same shapes)");
+    const void* saved = save_of(save, Xu, nsave);
     at::Tensor ws = scratch(Xu, nws), dXu = at::empty_like(Xu), dc = at::empty_like(c_n);
     for (auto& g : grads) f32(g, Xu, "parameter gradient");
     check(digat_user_ctx_bwd(f32(dout, Xu, "dout"), f32(Xu, Xu, "Xu"), bytes(cat_mask, Xu, "cat_mask"), i64(cat_idx, Xu, "cat_idx"), f32(c_n, Xu, "c_n"),
-                             f32(Ku, Xu, "Ku"), f32(Qu, Xu, "Qu"), f32(Fa, Xu, "Fa"), f32(Kua, Xu, "Kua"), f32(Qua, Xu, "Qua"), (float)p, save.data_ptr(), nsave,
+                             f32(Ku, Xu, "Ku"), f32(Qu, Xu, "Qu"), f32(Fa, Xu, "Fa"), f32(Kua, Xu, "Kua"), f32(Qua, Xu, "Qua"), (float)p, saved, nsave,
                              out_f32(dXu), out_f32(dc), out_f32(grads[0]), out_f32(grads[1]), out_f32(grads[5]), out_f32(grads[2]), out_f32(grads[6]),
                              out_f32(grads[3]), out_f32(grads[4]), out_f32(grads[7]), B, U, (int)H, (int)C1, d, accumulate ? 1 : 0, ws.data_ptr(), nws,
                              image_of(image, Xu, digat_split_job_bytes(d, d, 1, 1)), stream_of(Xu)), "digat_user_ctx_bwd");

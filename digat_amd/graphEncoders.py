@@ -497,14 +497,7 @@ class DIGAT(GraphEncoder):
         nbytes = (L.digat_encoder_shared_workspace_bytes if shared else L.digat_encoder_workspace_bytes)(B, N, H, C, d, self.graph_depth)
         ws = _lib.workspace(nbytes, dev, "encoder")
         P = self._params()
-        X = _lib.ext()
-        if X is not None:         # the thin torch extension: tensors in, the same C entry point behind it
-            X.encoder_fwd(_lib.addressof(P), bool(shared), Xn, An, Mn, ue, Au, cm, ci, c0, out_n, out_u, ws)
-            return out_n, out_u
-        fn, what = (L.digat_encoder_fwd_shared, "digat_encoder_fwd_shared") if shared else (L.digat_encoder_fwd, "digat_encoder_fwd")
-        _lib.check(fn(P, Xn.data_ptr(), An.data_ptr(), Mn.data_ptr(), ue.data_ptr(), Au.data_ptr(),
-                      cm.data_ptr(), ci.data_ptr(), _lib.ptr(c0), out_n.data_ptr(), out_u.data_ptr(),
-                      B, N, H, ws.data_ptr(), nbytes, _lib.stream_ptr()), what)
+        _lib.binding().encoder_fwd(_lib.addressof(P), bool(shared), Xn, An, Mn, ue, Au, cm, ci, c0, out_n, out_u, ws)
         return out_n, out_u
 
     def project_news_layer0(self, news_graph_embeddings):
@@ -581,47 +574,29 @@ class DIGAT(GraphEncoder):
         L = _lib.lib()
         nbytes = L.digat_encoder_grouped_workspace_bytes(B, N, H, C, d, self.graph_depth)
         ws = _lib.workspace(nbytes, dev, "encoder")
-        P = self._params()
-        X = _lib.ext()
         hpq = hh = th = cq = ni = None
-        if news_hpq0 is not None or hist_hpq0 is not None or ctxq0 is not None or news_index is not None:
-            M = 0
-            if news_index is not None:
-                if news_hpq0 is None or news_graph_context is None:
-                    raise ValueError("news_index needs news_hpq0 (the per-news table) and news_graph_context")
-                ni = news_index.to(torch.int64).contiguous()
-                M = Xn.shape[0]
-                if ni.shape[0] != B or tuple(news_hpq0.shape) != (3, M, N, d):
-                    raise ValueError("with news_index: news_graph_embeddings [M, N, d], news_hpq0 [3, M, N, d], news_index [B]")
-            if ctxq0 is not None:
-                cq = _lib.f32(ctxq0)
-                if tuple(cq.shape) != (3, B, d):
-                    raise ValueError("ctxq0 must be [3, B, d] (news_context_queries of the batch's news contexts)")
-            if news_hpq0 is not None:
-                hpq = _lib.f32(news_hpq0)
-                if ni is None and tuple(hpq.shape) != (3, B, N, d):
-                    raise ValueError("news_hpq0 must be [3, B, N, d] (project_news_layer0 of the batch's candidates)")
-            if hist_hpq0 is not None:
-                hh, th = _lib.f32(hist_hpq0), _lib.f32(topic_hpq0)
-                if tuple(hh.shape) != (3, G, H, d) or tuple(th.shape) != (3, C, d):
-                    raise ValueError("hist_hpq0 must be [3, G, H, d] and topic_hpq0 [3, C, d] (project_user_layer0)")
-            if X is not None:
-                X.encoder_fwd_grouped(_lib.addressof(P), Xn, An, Mn, ue, Au, cm, ci, rg, c0, hpq, hh, th, cq, ni, out_n, out_u, ws)
-                return out_n, out_u
-            _lib.check(L.digat_encoder_fwd_grouped_cached(P, Xn.data_ptr(), An.data_ptr(), Mn.data_ptr(), ue.data_ptr(),
-                                                          Au.data_ptr(), cm.data_ptr(), ci.data_ptr(), rg.data_ptr(), c0.data_ptr(),
-                                                          _lib.ptr(hpq), _lib.ptr(hh), _lib.ptr(th), _lib.ptr(cq), _lib.ptr(ni), M,
-                                                          out_n.data_ptr(),
-                                                          out_u.data_ptr(), B, G, N, H, ws.data_ptr(), nbytes, _lib.stream_ptr()),
-                       "digat_encoder_fwd_grouped_cached")
-            return out_n, out_u
-        if X is not None:
-            X.encoder_fwd_grouped(_lib.addressof(P), Xn, An, Mn, ue, Au, cm, ci, rg, c0, None, None, None, None, None, out_n, out_u, ws)
-            return out_n, out_u
-        _lib.check(L.digat_encoder_fwd_grouped(P, Xn.data_ptr(), An.data_ptr(), Mn.data_ptr(), ue.data_ptr(), Au.data_ptr(),
-                                               cm.data_ptr(), ci.data_ptr(), rg.data_ptr(), c0.data_ptr(), out_n.data_ptr(),
-                                               out_u.data_ptr(), B, G, N, H, ws.data_ptr(), nbytes, _lib.stream_ptr()),
-                   "digat_encoder_fwd_grouped")
+        if news_index is not None:
+            if news_hpq0 is None or news_graph_context is None:
+                raise ValueError("news_index needs news_hpq0 (the per-news table) and news_graph_context")
+            ni = news_index.to(torch.int64).contiguous()
+            M = Xn.shape[0]
+            if ni.shape[0] != B or tuple(news_hpq0.shape) != (3, M, N, d):
+                raise ValueError("with news_index: news_graph_embeddings [M, N, d], news_hpq0 [3, M, N, d], news_index [B]")
+        if ctxq0 is not None:
+            cq = _lib.f32(ctxq0)
+            if tuple(cq.shape) != (3, B, d):
+                raise ValueError("ctxq0 must be [3, B, d] (news_context_queries of the batch's news contexts)")
+        if news_hpq0 is not None:
+            hpq = _lib.f32(news_hpq0)
+            if ni is None and tuple(hpq.shape) != (3, B, N, d):
+                raise ValueError("news_hpq0 must be [3, B, N, d] (project_news_layer0 of the batch's candidates)")
+        if hist_hpq0 is not None:
+            hh, th = _lib.f32(hist_hpq0), _lib.f32(topic_hpq0)
+            if tuple(hh.shape) != (3, G, H, d) or tuple(th.shape) != (3, C, d):
+                raise ValueError("hist_hpq0 must be [3, G, H, d] and topic_hpq0 [3, C, d] (project_user_layer0)")
+        # the per-news tables are optional, any subset: the binding takes the plain grouped entry when none is given
+        P = self._params()
+        _lib.binding().encoder_fwd_grouped(_lib.addressof(P), Xn, An, Mn, ue, Au, cm, ci, rg, c0, hpq, hh, th, cq, ni, out_n, out_u, ws)
         return out_n, out_u
 
     def forward(self, news_graph_embeddings, news_graph, news_graph_mask, user_news_embedding, user_graph,
@@ -677,13 +652,7 @@ class DIGAT(GraphEncoder):
         leaders = torch.empty(B, dtype=torch.int64, device=dev)
         count = torch.empty(1, dtype=torch.int32, device=dev)
         ws = _lib.workspace(B, dev, "runs")
-        X = _lib.ext()
-        if X is not None:
-            X.user_row_runs(ue_c, Au_b, cm_b, ci_c, row_group, leaders, count, ws)
-        else:
-            _lib.check(_lib.lib().digat_user_row_runs(ue_c.data_ptr(), Au_b.data_ptr(), cm_b.data_ptr(), ci_c.data_ptr(), B, H, U, C1, d,
-                                                      row_group.data_ptr(), leaders.data_ptr(), count.data_ptr(), ws.data_ptr(), B,
-                                                      _lib.stream_ptr()), "digat_user_row_runs")
+        _lib.binding().user_row_runs(ue_c, Au_b, cm_b, ci_c, row_group, leaders, count, ws)
         G = int(count.item())              # the one host read of the drop-in path
         if 4 * G > B:
             return None

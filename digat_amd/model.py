@@ -15,13 +15,7 @@ from . import _lib, graphEncoders, newsEncoders
 
 def _row_logits(news_rep, user_rep, logits):
     """model.py:75,90: logits = sum_d(user_ctx * news_ctx), one wave per row (digat_row_logits)."""
-    X = _lib.ext()
-    if X is not None:
-        X.row_logits(news_rep, user_rep, logits)
-        return
-    B, d = news_rep.shape
-    _lib.check(_lib.lib().digat_row_logits(news_rep.data_ptr(), user_rep.data_ptr(), logits.data_ptr(), B, d, _lib.stream_ptr()),
-               "digat_row_logits")
+    _lib.binding().row_logits(news_rep, user_rep, logits)
 
 
 class Model(nn.Module):

@@ -19,7 +19,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from .training import _save_buffer, _seed
+from .training import _seed
 
 
 class MultiHeadAttention(nn.Module):
@@ -166,7 +166,7 @@ class CnnFused(torch.autograd.Function):
         P = CnnFused._params(table_, W, b, A1_, b1_, a2_)
         out = torch.empty((T, W.shape[0]), dtype=torch.float32, device=dev)
         nsave, nws = L.digat_cnn_train_save_bytes(*dims), L.digat_cnn_train_workspace_bytes(*dims)
-        save, ws = _save_buffer(nsave, dev), _lib.workspace(nws, dev, "cnn_train")
+        save, ws = _lib.save_buffer(nsave, dev), _lib.workspace(nws, dev, "cnn_train")
         p = float(p_drop)
         seed = _seed() if p > 0 else 0
         if T:
@@ -229,7 +229,7 @@ class MsaFused(torch.autograd.Function):
         P = MsaFused._params(*ws_, heads, dk)
         out = torch.empty((T, heads * dk), dtype=torch.float32, device=dev)
         nsave, nws = L.digat_msa_train_save_bytes(*dims), L.digat_msa_train_workspace_bytes(*dims)
-        save, ws = _save_buffer(nsave, dev), _lib.workspace(nws, dev, "msa_train")
+        save, ws = _lib.save_buffer(nsave, dev), _lib.workspace(nws, dev, "msa_train")
         p = float(p_drop)
         seed = _seed() if p > 0 else 0
         if T:

@@ -144,17 +144,7 @@ class MatmulW(Function):
 class Dropout(Function):
     @staticmethod
     def forward(ctx, x, p):
-        x = _f(x)
-        E = _lib.ext()
-        if E is not None:
-            y, mask = E.dropout_fwd(x, float(p), _seed())
-            ctx.save_for_backward(mask)
-            ctx.p = float(p)
-            return y
-        y = torch.empty_like(x)
-        mask = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
-        _lib.check(L().digat_dropout_fwd(x.data_ptr(), y.data_ptr(), mask.data_ptr(), x.numel(), float(p), _seed(), S()),
-                   "digat_dropout_fwd")
+        y, mask = _lib.binding().dropout_fwd(_f(x), float(p), _seed())
         ctx.save_for_backward(mask)
         ctx.p = float(p)
         return y
@@ -162,14 +152,7 @@ class Dropout(Function):
     @staticmethod
     def backward(ctx, dy):
         (mask,) = ctx.saved_tensors
-        dy = _f(dy)
-        E = _lib.ext()
-        if E is not None:
-            return E.dropout_bwd(dy, mask, ctx.p), None
-        dx = torch.empty_like(dy)
-        _lib.check(L().digat_dropout_bwd(dy.data_ptr(), mask.data_ptr(), dx.data_ptr(), dy.numel(), ctx.p, S()),
-                   "digat_dropout_bwd")
-        return dx, None
+        return _lib.binding().dropout_bwd(_f(dy), mask, ctx.p), None
 
 
 class RowLogits(Function):
@@ -414,10 +397,6 @@ class XattnLayer(Function):
 # --------------------------------------------------------------------------------------------------
 # the three functions of the path, one library call per direction (include/digat_hip.h: digat_*_fwd_train / digat_*_bwd)
 # --------------------------------------------------------------------------------------------------
-def _save_buffer(nbytes, dev):
-    return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
-
-
 class XattnFused(Function):
     """Eq. 8 layer on already-dropped-out inputs Xd (graphEncoders.py:143-154): K3, the projections, score / softmax /
     attention dropout / aggregation in ``digat_xattn_fwd_train``; the whole backward — pairwise (recomputing
@@ -431,54 +410,23 @@ class XattnFused(Function):
         ``xattn_mode``: 0 = the library decides per batch on the device between the entry-wise and the all-pairs Eq. 8 kernels (graphs of
         more than 16 nodes), 1 = entry-wise (sparse corpus), 2 = all-pairs — the same function, a choice of speed."""
         Xd, cvec = _f(Xd), _f(cvec)
-        B, n, d = Xd.shape
-        dev = Xd.device
         p, p_in = float(p_alpha), float(p_in)
         img_f, ctx.img_b = images if images is not None else (None, None)
         ctx.mode = int(xattn_mode)
         seed_in = _seed() if p_in > 0 else 0          # the input dropout's site comes first (graphEncoders.py:145 before :152)
         seed = _seed() if p > 0 else 0
-        E = _lib.ext()
-        if E is not None:          # the thin torch extension: tensors in, out / save allocated there (the same C entry)
-            out, save = E.xattn_fwd_train(Xd, A, cvec, W, bW, F1, F2, F3, b3, a, p, seed, p_in, seed_in, img_f, ctx.mode)
-            ctx.save_for_backward(Xd, A, cvec, W, F1, F2, F3, a, out, save)
-            ctx.p, ctx.p_in, ctx.sizes = p, p_in, None
-            return out
-        out = torch.empty_like(Xd)
-        nsave, nws = L().digat_xattn_train_save_bytes(B, n, d), L().digat_xattn_train_workspace_bytes(B, n, d)
-        save, ws = _save_buffer(nsave, dev), _lib.workspace(nws, dev, "train")
-        _lib.check(L().digat_xattn_fwd_train(Xd.data_ptr(), A.data_ptr(), cvec.data_ptr(), W.data_ptr(), bW.data_ptr(), F1.data_ptr(),
-                                             F2.data_ptr(), F3.data_ptr(), b3.data_ptr(), a.data_ptr(), out.data_ptr(), p,
-                                             seed, p_in, seed_in, B, n, d, save.data_ptr(), nsave, ws.data_ptr(), nws, _lib.ptr(img_f), ctx.mode, S()),
-                   "digat_xattn_fwd_train")
+        out, save = _lib.binding().xattn_fwd_train(Xd, A, cvec, W, bW, F1, F2, F3, b3, a, p, seed, p_in, seed_in, img_f, ctx.mode)
         ctx.save_for_backward(Xd, A, cvec, W, F1, F2, F3, a, out, save)
-        ctx.p, ctx.p_in, ctx.sizes = p, p_in, (nsave, nws)
+        ctx.p, ctx.p_in = p, p_in
         return out
 
     @staticmethod
     def backward(ctx, dOut):
         Xd, A, cvec, W, F1, F2, F3, a, out, save = ctx.saved_tensors
-        B, n, d = Xd.shape
-        dev = Xd.device
-        dOut = _f(dOut)
-        E = _lib.ext()
-        if E is not None and ctx.sizes is None:
-            dX, dc, dW3, dbW, dF3, db3, da = E.xattn_bwd(dOut, out, Xd, A, cvec, W, F1, F2, F3, a, ctx.p, ctx.p_in, save, ctx.img_b, ctx.mode)
-            return dX, None, dc, dW3[0], dbW, dW3[1], dW3[2], dF3, db3, da.view_as(a), None, None, None, None
-        nsave, nws = ctx.sizes
-        ws = _lib.workspace(nws, dev, "train")
-        dX, dc = torch.empty_like(Xd), torch.empty_like(cvec)
-        # dW, dF1, dF2 as the three blocks of one [3 d, d] buffer: the library writes its single [3 d, d] weight-gradient product in place
-        dW3 = torch.empty((3,) + tuple(W.shape), dtype=torch.float32, device=dev)
-        dW, dF1, dF2 = dW3[0], dW3[1], dW3[2]
-        dF3 = torch.empty_like(W)
-        dbW, db3, da = (torch.empty(d, dtype=torch.float32, device=dev) for _ in range(3))
-        _lib.check(L().digat_xattn_bwd(dOut.data_ptr(), out.data_ptr(), Xd.data_ptr(), A.data_ptr(), cvec.data_ptr(), W.data_ptr(),
-                                       F1.data_ptr(), F2.data_ptr(), F3.data_ptr(), a.data_ptr(), ctx.p, ctx.p_in, save.data_ptr(), nsave,
-                                       dX.data_ptr(), dc.data_ptr(), dW.data_ptr(), dbW.data_ptr(), dF1.data_ptr(), dF2.data_ptr(),
-                                       dF3.data_ptr(), db3.data_ptr(), da.data_ptr(), B, n, d, ws.data_ptr(), nws, _lib.ptr(ctx.img_b), ctx.mode, S()),
-                   "digat_xattn_bwd")
-        return dX, None, dc, dW, dbW, dF1, dF2, dF3, db3, da.view_as(a), None, None, None, None
+        # dW, dF1, dF2 arrive as the three blocks of one [3, d, d] buffer: the library writes its single weight-gradient product in place
+        dX, dc, dW3, dbW, dF3, db3, da = _lib.binding().xattn_bwd(_f(dOut), out, Xd, A, cvec, W, F1, F2, F3, a, ctx.p, ctx.p_in, save,
+                                                                  ctx.img_b, ctx.mode)
+        return dX, None, dc, dW3[0], dbW, dW3[1], dW3[2], dF3, db3, da.view_as(a), None, None, None, None
 
 
 class GatFused(Function):
@@ -492,13 +440,13 @@ class GatFused(Function):
         dev = Xd.device
         out = torch.empty_like(Xd)
         nsave, nws = L().digat_gat_train_save_bytes(B, n, d), L().digat_gat_train_workspace_bytes(B, n, d)
-        save, ws = _save_buffer(nsave, dev), _lib.workspace(nws, dev, "train")
+        save, ws = _lib.save_buffer(nsave, dev), _lib.workspace(nws, dev, "train")
         p = float(p_alpha)
         _lib.check(L().digat_gat_fwd_train(Xd.data_ptr(), A.data_ptr(), W.data_ptr(), bW.data_ptr(), a1.data_ptr(), a2.data_ptr(),
                                            out.data_ptr(), p, _seed() if p > 0 else 0, B, n, d, save.data_ptr(), nsave,
                                            ws.data_ptr(), nws, S()), "digat_gat_fwd_train")
         ctx.save_for_backward(Xd, A, W, a1, a2, out, save)
-        ctx.p, ctx.sizes = p, (nsave, nws)
+        ctx.p = p
         return out
 
     @staticmethod
@@ -507,7 +455,7 @@ class GatFused(Function):
         B, n, d = Xd.shape
         dev = Xd.device
         dOut = _f(dOut)
-        nsave, nws = ctx.sizes
+        nsave, nws = L().digat_gat_train_save_bytes(B, n, d), L().digat_gat_train_workspace_bytes(B, n, d)
         ws = _lib.workspace(nws, dev, "train")
         dX, dW = torch.empty_like(Xd), torch.empty_like(W)
         dbW, da1, da2 = (torch.empty(d, dtype=torch.float32, device=dev) for _ in range(3))
@@ -584,30 +532,16 @@ class NewsCtxFused(Function):
         ctx.sink, ctx.has_prev = sink, prev is not None
         if sink is not None:
             sink.enter("news_ctx")
-        B, N, d = X.shape
-        dev = X.device
-        E = _lib.ext()
-        if E is not None:
-            p = float(p_gate)
-            out, save = E.news_ctx_fwd_train(X, mask, Kc, Qc, bQc, Wg, bg, p, _seed() if p > 0 else 0, prev)
-            ctx.save_for_backward(X, mask, Kc, Qc, Wg, save)
-            ctx.p, ctx.sizes = p, None
-            return out
-        out = torch.empty((B, d), dtype=torch.float32, device=dev)
-        nsave, nws = L().digat_news_ctx_train_save_bytes(B, N, d), L().digat_news_ctx_train_workspace_bytes(B, N, d)
-        save, ws = _save_buffer(nsave, dev), _lib.workspace(nws, dev, "train")
         p = float(p_gate)
-        _lib.check(L().digat_news_ctx_fwd_train(X.data_ptr(), mask.data_ptr(), Kc.data_ptr(), Qc.data_ptr(), bQc.data_ptr(),
-                                                Wg.data_ptr(), bg.data_ptr(), out.data_ptr(), p, _seed() if p > 0 else 0, B, N, d,
-                                                save.data_ptr(), nsave, ws.data_ptr(), nws, _lib.ptr(prev), S()), "digat_news_ctx_fwd_train")
+        out, save = _lib.binding().news_ctx_fwd_train(X, mask, Kc, Qc, bQc, Wg, bg, p, _seed() if p > 0 else 0, prev)
         ctx.save_for_backward(X, mask, Kc, Qc, Wg, save)
-        ctx.p, ctx.sizes = p, (nsave, nws)
+        ctx.p = p
         return out
 
     @staticmethod
     def backward(ctx, dout):
         X, mask, Kc, Qc, Wg, save = ctx.saved_tensors
-        B, N, d = X.shape
+        d = X.shape[2]
         dev = X.device
         dout = _f(dout)
 
@@ -617,19 +551,7 @@ class NewsCtxFused(Function):
         sink = ctx.sink
         grads, acc = sink.begin("news_ctx", make) if sink is not None else (make(), 0)
         dKc, dQc, dbQc, dWg, dbg = grads
-        E = _lib.ext()
-        if E is not None and ctx.sizes is None:
-            dX = E.news_ctx_bwd(dout, X, mask, Kc, Qc, Wg, ctx.p, save, list(grads), bool(acc))
-            dprev = dout if ctx.has_prev else None
-            if sink is not None and not sink.end("news_ctx"):
-                return dX, None, None, None, None, None, None, None, None, dprev
-            return dX, None, dKc, dQc, dbQc, dWg, dbg, None, None, dprev
-        nsave, nws = ctx.sizes
-        ws = _lib.workspace(nws, dev, "train")
-        dX = torch.empty_like(X)
-        _lib.check(L().digat_news_ctx_bwd(dout.data_ptr(), X.data_ptr(), mask.data_ptr(), Kc.data_ptr(), Qc.data_ptr(), Wg.data_ptr(),
-                                          ctx.p, save.data_ptr(), nsave, dX.data_ptr(), dKc.data_ptr(), dQc.data_ptr(), dbQc.data_ptr(),
-                                          dWg.data_ptr(), dbg.data_ptr(), B, N, d, acc, ws.data_ptr(), nws, S()), "digat_news_ctx_bwd")
+        dX = _lib.binding().news_ctx_bwd(dout, X, mask, Kc, Qc, Wg, ctx.p, save, list(grads), bool(acc))
         dprev = dout if ctx.has_prev else None
         if sink is not None and not sink.end("news_ctx"):
             return dX, None, None, None, None, None, None, None, None, dprev
@@ -649,34 +571,17 @@ class UserCtxFused(Function):
         img_f, ctx.img_b = images if images is not None else (None, None)
         if sink is not None:
             sink.enter("user_ctx")
-        B, U, d = Xu.shape
-        dev = Xu.device
-        E = _lib.ext()
-        if E is not None:
-            p = float(p_topic)
-            out, save = E.user_ctx_fwd_train(Xu, cat_mask, cat_idx, c_n, Ku, Qu, bQu, Fa, bFa, Kua, Qua, bQua, int(H), int(C1), p,
-                                             _seed() if p > 0 else 0, img_f, prev)
-            ctx.save_for_backward(Xu, cat_mask, cat_idx, c_n, Ku, Qu, Fa, Kua, Qua, save)
-            ctx.p, ctx.sizes, ctx.dims = p, None, (H, C1)
-            return out
-        out = torch.empty((B, d), dtype=torch.float32, device=dev)
-        nsave = L().digat_user_ctx_train_save_bytes(B, U, H, C1, d)
-        nws = L().digat_user_ctx_train_workspace_bytes(B, U, H, C1, d)
-        save, ws = _save_buffer(nsave, dev), _lib.workspace(nws, dev, "train")
         p = float(p_topic)
-        _lib.check(L().digat_user_ctx_fwd_train(Xu.data_ptr(), cat_mask.data_ptr(), cat_idx.data_ptr(), c_n.data_ptr(), Ku.data_ptr(),
-                                                Qu.data_ptr(), bQu.data_ptr(), Fa.data_ptr(), bFa.data_ptr(), Kua.data_ptr(),
-                                                Qua.data_ptr(), bQua.data_ptr(), out.data_ptr(), p, _seed() if p > 0 else 0,
-                                                B, U, H, C1, d, save.data_ptr(), nsave, ws.data_ptr(), nws, _lib.ptr(img_f), _lib.ptr(prev), S()),
-                   "digat_user_ctx_fwd_train")
+        out, save = _lib.binding().user_ctx_fwd_train(Xu, cat_mask, cat_idx, c_n, Ku, Qu, bQu, Fa, bFa, Kua, Qua, bQua, int(H), int(C1), p,
+                                                      _seed() if p > 0 else 0, img_f, prev)
         ctx.save_for_backward(Xu, cat_mask, cat_idx, c_n, Ku, Qu, Fa, Kua, Qua, save)
-        ctx.p, ctx.sizes, ctx.dims = p, (nsave, nws), (H, C1)
+        ctx.p, ctx.dims = p, (H, C1)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         Xu, cat_mask, cat_idx, c_n, Ku, Qu, Fa, Kua, Qua, save = ctx.saved_tensors
-        B, U, d = Xu.shape
+        d = Xu.shape[2]
         H, C1 = ctx.dims
         dev = Xu.device
         dout = _f(dout)
@@ -686,22 +591,8 @@ class UserCtxFused(Function):
         sink = ctx.sink
         grads, acc = sink.begin("user_ctx", make) if sink is not None else (make(), 0)
         dKu, dQu, dFa, dKua, dQua, dbQu, dbFa, dbQua = grads
-        E = _lib.ext()
-        if E is not None and ctx.sizes is None:
-            dXu, dc = E.user_ctx_bwd(dout, Xu, cat_mask, cat_idx, c_n, Ku, Qu, Fa, Kua, Qua, ctx.p, save, list(grads), bool(acc), int(H), int(C1),
-                                     ctx.img_b)
-            dprev = dout if ctx.has_prev else None
-            if sink is not None and not sink.end("user_ctx"):
-                return (dXu, None, None, dc) + (None,) * 13 + (dprev,)
-            return dXu, None, None, dc, dKu, dQu, dbQu, dFa, dbFa, dKua, dQua, dbQua, None, None, None, None, None, dprev
-        nsave, nws = ctx.sizes
-        ws = _lib.workspace(nws, dev, "train")
-        dXu, dc = torch.empty_like(Xu), torch.empty_like(c_n)
-        _lib.check(L().digat_user_ctx_bwd(dout.data_ptr(), Xu.data_ptr(), cat_mask.data_ptr(), cat_idx.data_ptr(), c_n.data_ptr(),
-                                          Ku.data_ptr(), Qu.data_ptr(), Fa.data_ptr(), Kua.data_ptr(), Qua.data_ptr(), ctx.p,
-                                          save.data_ptr(), nsave, dXu.data_ptr(), dc.data_ptr(), dKu.data_ptr(), dQu.data_ptr(),
-                                          dbQu.data_ptr(), dFa.data_ptr(), dbFa.data_ptr(), dKua.data_ptr(), dQua.data_ptr(),
-                                          dbQua.data_ptr(), B, U, H, C1, d, acc, ws.data_ptr(), nws, _lib.ptr(ctx.img_b), S()), "digat_user_ctx_bwd")
+        dXu, dc = _lib.binding().user_ctx_bwd(dout, Xu, cat_mask, cat_idx, c_n, Ku, Qu, Fa, Kua, Qua, ctx.p, save, list(grads), bool(acc),
+                                              int(H), int(C1), ctx.img_b)
         dprev = dout if ctx.has_prev else None
         if sink is not None and not sink.end("user_ctx"):
             return (dXu, None, None, dc) + (None,) * 13 + (dprev,)

@@ -48,6 +48,28 @@ def test_torch_extension_is_built_and_binds_the_same_library():
     assert "libdigat_hip.so" in needed and "$ORIGIN" in needed
 
 
+def test_torch_extension_and_its_ctypes_twin_expose_one_surface():
+    """``_lib.binding()`` hands the call sites either the torch extension or its ctypes twin (digat_amd/_ctypes_binding.py): the
+    two must offer the same functions with the same number of parameters (pybind11 names them arg0, arg1, ... in the first line
+    of each docstring).  Their results are compared bit for bit on the GPU (test_hip_parity.py, test_hip_training.py)."""
+    import inspect
+    from digat_amd import _ctypes_binding as T, _lib, build
+    build.build(verbose=False)
+    X = _lib.ext()
+    assert X is not None and _lib.binding() is X
+    ext_names = {n for n in dir(X) if not n.startswith("_")} - {"abi_version"}
+    twin = {n: f for n, f in vars(T).items() if inspect.isfunction(f) and f.__module__ == T.__name__ and not n.startswith("_")}
+    assert ext_names == set(twin) and len(twin) == 12
+    for name, fn in twin.items():
+        first_line = getattr(X, name).__doc__.splitlines()[0]
+        assert len(re.findall(r"\barg\d+:", first_line)) == len(inspect.signature(fn).parameters), name
+    _lib.USE_TORCH_EXT = False
+    try:
+        assert _lib.ext() is None and _lib.binding() is T
+    finally:
+        _lib.USE_TORCH_EXT = True
+
+
 def test_workspace_queries():
     from digat_amd import _lib
     L = _lib.lib()

@@ -622,8 +622,8 @@ def test_twin_centres_and_row_chunks_are_bit_identical_to_the_wave_per_centre_ke
 
 def test_torch_extension_and_ctypes_bindings_agree():
     """The two bindings of the C ABI — the thin torch extension (digat_torch_ext.so, the default) and the ctypes table — reach the
-    same entry points with the same arguments: forward, inference, inference_grouped (plain and with per-news tables) and the logits
-    give the same bits, and the extension rejects what the ABI does not take (a non-contiguous tensor, a wrong dtype)."""
+    same entry points with the same arguments: forward, inference (per row and on runs of shared users), inference_grouped (plain
+    and with per-news tables), the search for the runs and the logits give the same bits, and the extension rejects what the ABI does not take (a non-contiguous tensor, a wrong dtype)."""
     from digat_amd import _lib, synthetic, util
     from digat_amd.model import Model, PrecomputedNewsEncoder
     assert _lib.ext() is not None, "digat_torch_ext.so has not been built (python -m digat_amd.build)"
@@ -643,11 +643,33 @@ def test_torch_extension_and_ctypes_bindings_agree():
     keys = ("news_graph_embeddings", "news_graph", "news_graph_mask", "user_news_embedding", "user_graph", "user_category_mask",
             "user_category_indices")
 
+    # 8 users x 16 consecutive rows = SHARED_USERS_MIN_ROWS rows: the least batch that takes the shared-user entries (4 G <= B)
+    G, per_user = 8, 16
+    B = G * per_user
+    assert B == enc.SHARED_USERS_MIN_ROWS
+    dims = (spec.news_graph_size, spec.max_history_num, spec.category_num, spec.embedding_dim)
+    users = to_dev(synthetic.make_encoder_batch(G, *dims, seed=94))
+    rows = to_dev(synthetic.make_encoder_batch(B, *dims, seed=95))
+    rg = torch.arange(G, device=_dev()).repeat_interleave(per_user)
+    exp = {k: users[k].index_select(0, rg).contiguous() for k in keys[3:]}
+    with torch.no_grad():
+        c0 = enc.compute_news_graph_context(rows["news_graph_embeddings"], rows["news_graph_mask"])
+
     def run():
         with torch.no_grad():
             out = list(enc(*(batch[k] for k in keys)))
             out.append(util.score_rows(model, dc, 0, dc.rows, 512))                      # grouped, per-news tables in place
             out.append(util.score_rows(model, dc, 0, dc.rows, 512, grouped=False))       # per-row entry
+            out += enc.inference_grouped(*(rows[k] for k in keys[:3]), *(users[k] for k in keys[3:]), rg, c0)    # plain grouped entry
+            hint = enc.corpus_xattn_hint
+            enc.corpus_xattn_hint = {"user": "sparse"}
+            try:
+                out += enc.inference(*(rows[k] for k in keys[:3]), *(exp[k] for k in keys[3:]), c0)              # shared=True entry
+                runs = enc._shared_user_runs(rows["news_graph_embeddings"], *(exp[k] for k in keys[3:]))
+            finally:
+                enc.corpus_xattn_hint = hint
+            assert runs is not None and torch.equal(runs[0], rg.int()) and runs[1].tolist() == list(range(0, B, per_user))
+            out += runs
         torch.cuda.synchronize()
         return out
     via_ext = run()
@@ -657,6 +679,7 @@ def test_torch_extension_and_ctypes_bindings_agree():
         via_ctypes = run()
     finally:
         _lib.USE_TORCH_EXT = True
+    assert len(via_ext) == len(via_ctypes) == 10
     for a, b in zip(via_ext, via_ctypes):
         assert torch.equal(a, b)
     X = _lib.ext()
