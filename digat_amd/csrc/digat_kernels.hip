@@ -13,7 +13,8 @@
 //   digat_glue.inc     user-node build, group expansion, live-row lists, row logits
 //   digat_train.inc    backward / training kernels;  digat_eval.inc  per-impression ranking + metrics
 //   digat_news.inc     MSA news encoder (inference);  digat_gat.inc  vanilla-GAT layer of the ablation encoders
-// This file: shared helpers, the per-kernel profiler, and the C ABI (encoder orchestration included).
+// This file: shared helpers, the per-kernel profiler, and the C ABI.  The encoder's orchestration is digat_encoder.inc (host
+// code only), and every decision of an encoder call is made in digat_encoder_plan.h (plain C++).
 //
 // gfx950 only: 64-wide wavefronts, 160 KiB LDS per CU, MFMA f32 16x16x4.  No CUDA shims.
 #include <hip/hip_runtime.h>
@@ -27,6 +28,7 @@
 #include <utility>
 
 #include "../../include/digat_hip.h"
+#include "digat_encoder_plan.h"
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 
@@ -272,6 +274,22 @@ struct XattnOpts {
     unsigned* range_flag = nullptr; const TwinLists* tw = nullptr;
 };
 
+// [h | P | Q] = X [W | F1 | F2]^T (+ bW on h): the three-segment node projection of an Eq. 8 layer, one pass over X on the matrix
+// cores.  wsplit non-NULL: split operands in `format` on the bf16 / fp16 / fp8 matrix cores; pq_x3 (DIGAT_PROJ_PQ_X3): P and Q
+// (segments 1, 2) with three products.  Every launch of this projection is built here; a caller adds only what differs
+// (m_dispatch, a row list, xattn_core its K3 addend and the bf16 / fp8 output segments).
+static GemmArgs proj3_args(const float* X, int M, int d, const float* W, const float* bW, const float* F1, const float* F2,
+                           float* h, float* P, float* Q, const void* wsplit, int pq_x3, int format, unsigned* range_flag) {
+    GemmArgs g = gemm_plain(X, d, W, bW, h, d, M, d, d, 0);
+    g.w[1] = F1; g.bias[1] = nullptr; g.y[1] = P;
+    g.w[2] = F2; g.bias[2] = nullptr; g.y[2] = Q;
+    g.nsegs = 3;
+    g.x3_segs = pq_x3 ? 6 : 0;
+    g.wsplit = (const unsigned short*)wsplit;
+    g.format = format; g.range_flag = range_flag;
+    return g;
+}
+
 // Eq. 8 layer with K3 (r = ctx F3^T + b3) already computed; `r_given` may live anywhere.  The workspace is carved at this n
 // (the encoder's is sized for the larger of its two graphs).
 static int xattn_core(const float* X, const uint8_t* A, const float* r_given,
@@ -284,21 +302,15 @@ static int xattn_core(const float* X, const uint8_t* A, const float* r_given,
     const int* rowidx = o.rowidx; const int* nrows_dev = o.nrows_dev; const uint8_t* live = o.live;
     const int sparse_mode = o.sparse_mode, pq_mode = o.pq_mode;
     float *h = w.h, *P = w.P, *Q = w.Q, *alpha = alpha_out ? alpha_out : w.alpha;
-    // [h | P | Q] = X [W | F1 | F2]^T (+ bW on h): one pass over X on the matrix cores
-    GemmArgs g = gemm_plain(X, d, W, bW, h, d, B * n, d, d, 0);
-    g.w[1] = F1; g.bias[1] = nullptr; g.y[1] = P;
-    g.w[2] = F2; g.bias[2] = nullptr; g.y[2] = Q;
-    g.nsegs = 3;
-    g.wsplit = (const unsigned short*)o.wsplit;        // non-NULL: split operands on the bf16 / fp16 matrix cores
-    g.format = o.gemm_format; g.range_flag = o.range_flag;
+    GemmArgs g = proj3_args(X, B * n, d, W, bW, F1, F2, h, P, Q, o.wsplit, o.pq_x3, o.gemm_format, o.range_flag);
     g.radd = r_given; g.radd_seg = 1; g.rows_per_b = n; // P' = K3 + K1: the reference's left-to-right order
-    g.x3_segs = o.pq_x3 ? 6 : 0;                        // DIGAT_PROJ_PQ_X3: P and Q (segments 1, 2) with three products
+    const bool sparse_fits = !alpha_out && eq8_sparse_graph(n) && eq8_row_fits_wave(d);      // see xattn_sparse_kernel
     // DIGAT_PQ_BF16 (pq_mode & 1): P' and Q stored in bf16, read by the wave-per-centre sparse kernel; & 2: one product for them
-    const bool pq16 = (pq_mode & 1) && gemm_takes_row_list(g) && sparse_mode == DIGAT_XATTN_SPARSE && !alpha_out && n > 16 &&
-                      d / 4 <= 256 && d % 8 == 0 && (long)B * n >= 2048;
+    const bool pq16 = (pq_mode & 1) && gemm_takes_row_list(g) && sparse_mode == DIGAT_XATTN_SPARSE && sparse_fits &&
+                      d % 8 == 0 && (long)B * n >= 2048;
     // DIGAT_PQ_FP8 (pq_mode & 4): P' and Q stored as block-scaled e4m3 rows (one fp32 scale per 80-channel strip), same reader
-    const bool pq8 = (pq_mode & 4) && !(pq_mode & 1) && gemm_takes_row_list(g) && sparse_mode == DIGAT_XATTN_SPARSE && !alpha_out && n > 16 &&
-                     d / 4 <= 256 && d % 80 == 0 && (long)B * n >= 2048;
+    const bool pq8 = (pq_mode & 4) && !(pq_mode & 1) && gemm_takes_row_list(g) && sparse_mode == DIGAT_XATTN_SPARSE && sparse_fits &&
+                     d % 80 == 0 && (long)B * n >= 2048;
     const long ld8 = (long)align_up((size_t)d + 4 * (size_t)(d / 80), 64);      // [d codes | d / 80 scales | pad]: whole 64-byte lines
     if (pq16) { g.bf16_segs = 6; if (pq_mode & 2) g.x1_segs = 6; }
     if (pq8) { g.fp8_segs = 6; g.ldy8 = ld8; if (pq_mode & 2) g.x1_segs = 6; }
@@ -307,7 +319,7 @@ static int xattn_core(const float* X, const uint8_t* A, const float* r_given,
     const int rc = launch_gemm(g, st, DIGAT_KERNEL_PROJ);
     if (rc) return rc;
     const int* skip_if = nullptr;
-    if (sparse_mode != DIGAT_XATTN_DENSE && !alpha_out && n > 16 && d / 4 <= 256) {      // see xattn_sparse_kernel
+    if (sparse_mode != DIGAT_XATTN_DENSE && sparse_fits) {
         SparseArgs sg{P, Q, h, X, a, A, out, nullptr, nullptr, listed ? live : nullptr,
                       sparse_mode == DIGAT_XATTN_AUTO ? o.sparse_flag : nullptr, B, n, d / 4, 0, nullptr, nullptr,
                       listed && live ? rowidx : nullptr, listed && live ? nrows_dev : nullptr, 0, nullptr, pq8 ? 2 : (pq16 ? 1 : 0), o.centre_limit};
@@ -671,849 +683,7 @@ int digat_fold_attention(const float* K, const float* Q, const float* bQ, float*
 }
 
 // ---- a5 -----------------------------------------------------------------------------------------
-static size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
-
-// Inference fast path with folded attention queries (digat_fold_attention): per layer the [B,d]
-// linears shrink from 9 launches to 4 — {topic query, user query, next layer's K3 of the user graph}
-// all read the same c_n and go out as ONE three-segment launch.
-// Within a layer the news-graph update and the user-graph update read only the PREVIOUS contexts
-// (graphEncoders.py:194-195), so the news chain — K3, projection, score, aggregation, context pooling, gate, and
-// the queries derived from the new c_n — is independent of the user graph's Eq. 8 until the user context is
-// pooled.  The news kernels are small (N = 10 nodes, [B,d] linears: tens of workgroups, latency chains) and run
-// on a side stream under the user graph's projection / score / aggregation, which fill the chip; fork and join
-// are two events per layer (a pattern hipGraph capture accepts).
-
-// The encoder's workspace, carved by encoder_carve alone (the entries carve it, the *_workspace_bytes queries measure it).  The
-// grouped and shared entries append their regions after the base layout, so every base region has one offset in all three.
-enum { ENC_PLAIN, ENC_GROUPED, ENC_SHARED };
-struct FoldCtxWs { float *T, *T2, *glob; };      // the folded path's [B,C1,d] pooled topics + featureAffine, [B,d] news context
-struct EncoderWs {
-    float *Xu[2], *Xn[2];                   // user nodes [B,U,d] and news nodes [B,N,d], ping-pong
-    char* xws; size_t xws_bytes;            // Eq. 8 of either graph: sized for max(N, U), carved by xattn_core at the graph's n
-    XattnWs xu;                             // ... carved at n = U: layer 0 of grouped / shared rows (group_project)
-    char* cws; size_t cws_bytes;            // max(news_ctx, user_ctx): the unfolded path's context entries carve it themselves,
-    FoldCtxWs fc;                           // ... the folded path lays T, T2, glob inside it
-    float *kq_t, *kq_u, *r_user[2], *r_news;  // folded path: topic / user queries from c_n; K3 of the user (ping-pong) and news graphs
-    char* xws_news; size_t xws_news_bytes;  // the news graph's own Eq. 8 (side stream)
-    XattnWs xn;                             // ... carved at n = N
-    // live nodes (cnt, off, idx, flags1) and live buckets (cnt2, off2, idx2, flags2) of the user graphs; adjacency entries per row
-    // and the sparse / dense decision (flag); 1 + the last live history slot of every row (hlast)
-    int *cnt, *off, *idx, *cnt2, *off2, *idx2, *entries, *flag, *hlast;
-    uint8_t *flags1, *flags2;
-    int *cnt_n, *off_n, *idx_n; uint8_t* flags_n;      // live nodes of the news graphs (news_live_flags_kernel)
-    // layer 0 of grouped rows (xattn_sparse_l0_kernel): group starts, rows led by each row, offsets and list of the live centres
-    // of the chunk-leading rows
-    int *l0_gs, *l0_off; uint8_t* l0_lead; int* l0_idx;
-    // twins (xattn_sparse_twin_kernel): twin words, lead flags, leads per row, offsets, list
-    unsigned* tw_word; int* tw_list; uint8_t* tw_flags; int *tw_cnt, *tw_off;
-    int *gl_off, *gl_idx;                   // shared runs: offsets and list of the live nodes of the run-leading rows
-    int* idx32;                             // the candidate ids as 32-bit indices (layer 0 of larger news graphs from the tables)
-    // ENC_GROUPED: the per-group adjacency / category arrays expanded to rows; user_live_flags_kernel's outputs per group (at
-    // most B / 4 + 1 groups), expanded to rows by live_expand_kernel
-    uint8_t *Au, *cm; int64_t* ci;
-    uint8_t *fg, *tfg; unsigned* twg; uint8_t* bfg; int *cg, *eg, *hg, *bcg, *tcg;
-    uint8_t *same, *is_leader, *lead; int* leader_of;      // ENC_SHARED: equal users, run leaders, layer-0 chunk sizes, run of every row
-};
-static bool encoder_carve(Arena& a, int B, int N, int H, int C, int d, int variant, EncoderWs& e) {
-    const int U = H + C, C1 = C + 1, nmax = N > U ? N : U;
-    const size_t b = (size_t)B, bd = b * d, bu = b * U;
-    e = EncoderWs();
-    for (float*& x : e.Xu) x = a.take<float>(bu * d);
-    for (float*& x : e.Xn) x = a.take<float>(b * N * d);
-    Arena xa = a.sub(digat_xattn_workspace_bytes(B, nmax, d));
-    e.xws = xa.base; e.xws_bytes = xa.cap;
-    e.xu = xattn_carve(xa, B, U, d);
-    Arena ca = a.sub(max_sz(digat_news_ctx_workspace_bytes(B, N, d), digat_user_ctx_workspace_bytes(B, U, H, C1, d)));
-    e.cws = ca.base; e.cws_bytes = ca.cap;
-    e.fc = FoldCtxWs{ca.take<float>(b * C1 * d), ca.take<float>(b * C1 * d), ca.take<float>(bd)};
-    e.kq_t = a.take<float>(bd); e.kq_u = a.take<float>(bd);
-    e.r_user[0] = a.take<float>(bd); e.r_news = a.take<float>(bd); e.r_user[1] = a.take<float>(bd);
-    Arena na = a.sub(digat_xattn_workspace_bytes(B, N, d));
-    e.xws_news = na.base; e.xws_news_bytes = na.cap;
-    e.xn = xattn_carve(na, B, N, d);
-    e.cnt = a.take<int>(b); e.off = a.take<int>(b + 1); e.idx = a.take<int>(bu);
-    e.cnt2 = a.take<int>(b); e.off2 = a.take<int>(b + 1); e.idx2 = a.take<int>(b * C1);
-    e.entries = a.take<int>(b); e.flag = a.take<int>(64); e.hlast = a.take<int>(b);
-    e.flags1 = a.take<uint8_t>(bu); e.flags2 = a.take<uint8_t>(b * C1);
-    e.cnt_n = a.take<int>(b); e.off_n = a.take<int>(b + 1); e.idx_n = a.take<int>(b * N); e.flags_n = a.take<uint8_t>(b * N);
-    e.l0_gs = a.take<int>(b + 64); e.l0_off = a.take<int>(b + 64); e.l0_lead = a.take<uint8_t>(b); e.l0_idx = a.take<int>(bu);
-    e.tw_word = a.take<unsigned>(bu); e.tw_list = a.take<int>(bu); e.tw_flags = a.take<uint8_t>(bu);
-    e.tw_cnt = a.take<int>(b + 64); e.tw_off = a.take<int>(b + 64);
-    e.gl_off = a.take<int>(b + 64); e.gl_idx = a.take<int>(bu);
-    e.idx32 = a.take<int>(b);
-    if (variant == ENC_GROUPED) {           // appended: the grouped regions
-        const size_t g = b / 4 + 1;
-        e.Au = a.take<uint8_t>(bu * U); e.cm = a.take<uint8_t>(b * C1); e.ci = a.take<int64_t>(b * H);
-        e.fg = a.take<uint8_t>(g * U); e.tfg = a.take<uint8_t>(g * U); e.twg = a.take<unsigned>(g * U); e.bfg = a.take<uint8_t>(g * C1);
-        for (int** x : {&e.cg, &e.eg, &e.hg, &e.bcg, &e.tcg}) *x = a.take<int>(g);
-    } else if (variant == ENC_SHARED) {     // appended: the shared regions
-        e.same = a.take<uint8_t>(b); e.is_leader = a.take<uint8_t>(b); e.lead = a.take<uint8_t>(b); e.leader_of = a.take<int>(b);
-    }
-    return a.ok && xa.ok && ca.ok && na.ok;
-}
-static size_t encoder_ws_bytes(int B, int N, int H, int C, int d, int variant) { Arena a; EncoderWs e; encoder_carve(a, B, N, H, C, d, variant, e); return a.used; }
-
-// One encoder call: what the public entry was given, and the workspace carved from it (encoder_fwd_impl).
-struct EncoderCall {
-    const digat_params* p;
-    const float* Xn_in; const uint8_t *An, *Mn;
-    const float* ue;                        // user embeddings per row (per group: ENC_GROUPED)
-    const uint8_t *Au, *cat_mask; const int64_t* cat_idx;       // per row (ENC_GROUPED: the expanded *_g arrays)
-    const float* c_n0; float *out_news, *out_user;
-    int B, N, H;
-    void* workspace; size_t workspace_bytes; hipStream_t st;
-    int variant;                            // ENC_PLAIN, ENC_GROUPED, ENC_SHARED
-    const int* row_group; int G;            // the group of every row (ENC_SHARED: the row that leads its run)
-    const uint8_t *Au_g, *cm_g; const int64_t* ci_g;            // ENC_GROUPED: the user side per group
-    // cached per-news / per-topic tables of layer 0 and the queries of c_n0 (digat_encoder_fwd_grouped_cached)
-    const float *news_hpq0, *hist_hpq0, *topic_hpq0, *ctxq0; const int64_t* news_index; int64_t news_rows;
-    const uint8_t *run_leader, *run_lead;   // ENC_SHARED: rows that lead a run, rows of the layer-0 chunk a row leads
-    EncoderWs ws;
-};
-struct SideStream { hipStream_t s; hipEvent_t fork, join, early; int ok; };
-// Nothing below is mutable: live-row lists and the side stream are chosen PER CALL through digat_params.flags
-// (DIGAT_PARAMS_NO_LIVE_ROWS, DIGAT_PARAMS_SIDE_STREAM_OFF / _ON), so two host threads with different settings cannot flip each
-// other's (round 3 had process-wide setters for them).
-// Eq. 8 of a batch goes to the sparse kernel when its adjacency holds at most this many entries per node on average
-// (sparse_decide_kernel, train_sparse_decide_kernel)
-constexpr int SPARSE_PER_NODE = 20;
-// One side stream (and its three events) per CALLER stream: consecutive batches issued on alternating caller streams
-// (util.batch_streams) then overlap their side work too, and two host threads driving two streams never touch the same
-// events.  A caller stream is expected to be driven by one thread at a time (include/digat_hip.h, threading contract); the
-// table itself is guarded by a mutex.  Entries live for the life of the process (streams are few and long-lived).
-static SideStream* side_stream(hipStream_t caller) {
-    struct Entry { int dev; hipStream_t caller; SideStream side; int state; };     // state: 1 = ready, -1 = unavailable
-    static Entry tab[64];
-    static int used = 0;
-    static std::mutex mu;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-    std::lock_guard<std::mutex> lock(mu);
-    for (int i = 0; i < used; ++i)
-        if (tab[i].dev == dev && tab[i].caller == caller) return tab[i].state == 1 ? &tab[i].side : nullptr;
-    if (used == 64) return nullptr;            // more caller streams than anyone has: those run single-stream
-    Entry& e = tab[used++];
-    e.dev = dev; e.caller = caller;
-    SideStream& x = e.side;
-    const bool ok = hipStreamCreateWithFlags(&x.s, hipStreamNonBlocking) == hipSuccess &&
-                    hipEventCreateWithFlags(&x.fork, hipEventDisableTiming) == hipSuccess &&
-                    hipEventCreateWithFlags(&x.join, hipEventDisableTiming) == hipSuccess &&
-                    hipEventCreateWithFlags(&x.early, hipEventDisableTiming) == hipSuccess;
-    e.state = ok ? 1 : -1;
-    return ok ? &x : nullptr;
-}
-
-// Xg0: the layer-0 user nodes once per group (NULL: per row in w.Xu[0])
-static int encoder_fwd_folded(const EncoderCall& c, const float* Xg0) {
-    const digat_params* p = c.p;
-    const EncoderWs& w = c.ws;
-    const int B = c.B, N = c.N, H = c.H, G = c.G;
-    const uint8_t *An = c.An, *Mn = c.Mn, *Au = c.Au, *cat_mask = c.cat_mask, *run_leader = c.run_leader, *run_lead = c.run_lead;
-    const int64_t* cat_idx = c.cat_idx;
-    const int* row_group = c.row_group;
-    const float *news_hpq0 = c.news_hpq0, *ctxq0 = c.ctxq0;
-    float *c_n = c.out_news, *c_u = c.out_user;
-    hipStream_t st = c.st;
-    // SHARED-USER RUNS (digat_encoder_fwd_shared; round 5): the user tensors are given per ROW, as the reference's driver hands them
-    // over (util.py:57-67), and consecutive rows with identical users were found on the device: row_group[b] = the ROW that leads
-    // row b's run, run_leader[b] = 1 for those rows, run_lead[b] = rows of the layer-0 chunk row b leads.  Layer 0's group-level
-    // data (user nodes, [h|P|Q], live flags) then lives in the LEADING ROW's slots of the full-size buffers, every count stays on
-    // the device (no host read of the number of runs), and the group-indexed kernels work as they are.  G is not used.
-    const bool shared = run_leader != nullptr && run_lead != nullptr && row_group != nullptr;
-    // c_n_src: where the news context stands BEFORE layer 0 — c_n itself, or (depth >= 1, context given) the caller's c_n0, read
-    // in place by the two consumers that precede the first update instead of being copied into c_n first
-    const float* c_n_src = c.c_n0 && p->depth > 0 ? c.c_n0 : c_n;
-    const bool xu0_grouped = Xg0 != nullptr;       // layer-0 user nodes exist once per group, at Xg0 [G,U,d]
-    const int d = p->d, C = p->category_num, L = p->depth, U = H + C, C1 = C + 1;
-    const int fmt = (p->flags & DIGAT_PARAMS_GEMM_F16X3) ? 1 : 0;       // the format every wsplit image of `p` was split in ...
-    unsigned* const rflag = fmt ? (unsigned*)p->range_flag : nullptr;
-    const int lfmt = (p->flags & DIGAT_PARAMS_PROJ_F16F8C) ? DIGAT_GEMM_F16F8C : fmt;   // ... but the layers' [W|ffn1|ffn2]
-    // the kernel of the [B,d] linears is named by the caller, not chosen from B: a row's bits must not depend on the batch it sits in
-    // (nor on whether its context queries come from the per-news table)
-    const int bd_disp = (p->flags & DIGAT_PARAMS_BD_TILED) ? (1 << 30) : 1;
-    float *T = w.fc.T, *T2 = w.fc.T2, *glob = w.fc.glob;
-    const int* bucket_idx = nullptr;              // live topic buckets (set by find_live_rows during layer 0)
-    const int* nbuckets_dev = nullptr;
-    const int* hist_last = nullptr;               // [B]: 1 + the last live history slot of every row (published with the lists)
-    int rc;
-    // the user-side queries + (optionally) the next user-graph K3, all from c_n
-    auto from_c_n = [&](int next_layer, hipStream_t sq) -> int {
-        GemmArgs g = gemm_plain(next_layer == 0 ? c_n_src : c_n, d, p->user_news_fold_W, p->user_news_fold_b, w.kq_t, d, B, d, d, 0);
-        g.w[1] = p->userAtt_fold_W; g.bias[1] = p->userAtt_fold_b; g.y[1] = w.kq_u;
-        g.nsegs = 2;
-        if (next_layer < L) {
-            g.w[2] = p->user[next_layer].F3; g.bias[2] = p->user[next_layer].b3; g.y[2] = w.r_user[next_layer & 1];
-            g.nsegs = 3;
-        }
-        g.wsplit = (const unsigned short*)p->ctx_wsplit[next_layer]; g.format = fmt; g.range_flag = rflag;   // NULL: fp32 MFMA
-        g.m_dispatch = bd_disp;
-        return launch_gemm(g, sq);
-    };
-    // `live` (layers' outputs): the rows of dead nodes were never written — the topic pooling takes them as zero
-    // kq_topic / kq_user: the two queries derived from the news context (the workspace ones, or — initial context — the rows of the
-    // per-news table the caller gathered: ctxq0)
-    auto user_ctx_tail = [&](const float* Xu_cur, const float* addend, hipStream_t sq, const int* xgroup = nullptr,
-                             const uint8_t* live = nullptr, const float* kq_topic = nullptr, const float* kq_user = nullptr) -> int {
-        if (!kq_topic) { kq_topic = w.kq_t; kq_user = w.kq_u; }
-        // ONE launch (digat_ctxfused.inc) when the weight version carries the fused image and the shape fits; T, T2 stay unused then
-        if (p->featureAffine_fsplit && fmt == 1 && ctxfused_ok(H, C1, d)) {
-            const CtxFusedArgs fa{Xu_cur, (long)U * d, xgroup, live, U, live ? hist_last : nullptr, kq_topic, kq_user, cat_idx, cat_mask, addend, c_u,
-                                  (const uint4*)p->featureAffine_fsplit, p->featureAffine_b, rflag, B, H, C1, d, sqrtf((float)d)};
-            return launch_user_ctx_fused(fa, sq);
-        }
-        int e = launch_topic(Xu_cur, (long)U * d, kq_topic, cat_idx, T, B, H, C1, d, sq, xgroup, live, U, live ? hist_last : nullptr);
-        if (e) return e;
-        GemmArgs g = gemm_plain(T, d, p->featureAffine_W, p->featureAffine_b, T2, d, B * C1, d, d, 0);
-        g.epi = EPI_RELU_RES; g.e0 = T; g.lde0 = d;
-        g.wsplit = (const unsigned short*)p->featureAffine_wsplit;       // non-NULL: split operands on the matrix cores
-        g.format = fmt; g.range_flag = rflag;
-        if (bucket_idx && gemm_takes_row_list(g)) { g.rowidx = bucket_idx; g.nrows_dev = nbuckets_dev; }   // unmasked buckets only
-        e = launch_gemm(g, sq);
-        if (e) return e;
-        return launch_pool(T2, (long)C1 * d, kq_user, cat_mask, addend, c_u, B, C1, d, sq);
-    };
-    auto news_ctx = [&](const float* Xn_cur, hipStream_t sq, bool first) -> int {
-        const long ldx = (long)N * d;
-        float* kq = w.kq_t;                        // the news context's kq reuses kq_t: the previous user context has consumed it
-        GemmArgs gq = gemm_plain(Xn_cur, ldx, p->cand_fold_W, p->cand_fold_b, kq, d, B, d, d, 0);
-        gq.wsplit = (const unsigned short*)p->cand_fold_wsplit; gq.format = fmt; gq.range_flag = rflag;
-        gq.m_dispatch = bd_disp;
-        int e = launch_gemm(gq, sq);
-        if (e) return e;
-        e = launch_pool(Xn_cur, ldx, kq, Mn, nullptr, glob, B, N, d, sq);
-        if (e) return e;
-        GemmArgs g = gemm_plain(Xn_cur, ldx, p->news_graph_W, p->news_graph_b, c_n, d, B, d, 2 * d, 0);
-        g.k0 = d; g.a1 = glob; g.lda1 = d;
-        g.epi = EPI_GATE; g.e0 = Xn_cur; g.lde0 = ldx; g.e1 = glob; g.lde1 = d; g.e2 = first ? c_n_src : c_n; g.lde2 = d;
-        g.wsplit = (const unsigned short*)p->gate_wsplit; g.format = fmt; g.range_flag = rflag;
-        g.m_dispatch = 1;          // two-operand input: the split-image [B,d] kernel at every row count (the tiled one does not take it)
-        return launch_gemm(g, sq);
-    };
-
-    const bool want_live = L > 0 && !(p->flags & DIGAT_PARAMS_NO_LIVE_ROWS);
-    // Eq. 8 of the user graph: the sparse kernel, the dense pair, or both with the device choosing (p->flags; the choice
-    // comes out of the adjacency pass of find_live_rows)
-    int sparse_mode = p->flags & 3;
-    if (sparse_mode == 3 || (sparse_mode == DIGAT_XATTN_AUTO && L == 0)) sparse_mode = DIGAT_XATTN_DENSE;
-    const int* sparse_flag = nullptr;
-    const int pq_x3 = (p->flags & DIGAT_PROJ_PQ_X3) ? 1 : 0;
-    const int pq_mode = ((p->flags & DIGAT_PQ_BF16) ? 1 : 0) | ((p->flags & DIGAT_PQ_X1) ? 2 : 0) | ((p->flags & DIGAT_PQ_FP8) ? 4 : 0);
-    const bool want_scan = want_live || sparse_mode == DIGAT_XATTN_AUTO;      // the adjacency pass: live lists and / or the decision
-    // live rows of the user graph for the projections of layers >= 1
-    const int* rowidx = nullptr;
-    const int* nrows_dev = nullptr;
-    uint8_t* live_flags = nullptr;
-    // launches the list kernels on `sq`; `publish` hands the lists to the code below (the initial user context, issued on
-    // the caller's stream at the same time, must not see them: only a join orders the caller's stream after the side stream)
-    const int *pend_rowidx = nullptr, *pend_nrows = nullptr, *pend_bidx = nullptr, *pend_nb = nullptr, *pend_hlast = nullptr;
-
-    uint8_t* pend_flags = nullptr;
-    // layer 0 of grouped rows on the chunk kernel (R rows of an impression per wave: xattn_sparse_l0_kernel): its list — the live
-    // centres of the rows that lead a chunk — is made with the other two
-    const bool l0_chunked = row_group && (Xg0 || shared) && want_live &&
-                            sparse_mode == DIGAT_XATTN_SPARSE && d / 4 <= 128 && U <= 128;
-    const uint8_t* const l0_lead = shared ? run_lead : w.l0_lead;           // shared runs: the chunk sizes came with the runs
-    // twins: centres of a graph with equal adjacency rows, served together in layers >= 1 (xattn_sparse_twin_kernel)
-    const bool twins = want_live && sparse_mode == DIGAT_XATTN_SPARSE && d / 4 <= 128 && U <= 128 && L > 1;
-    unsigned* const tw_word = w.tw_word; uint8_t* const tw_flags = w.tw_flags;
-    int *const tw_list = w.tw_list, *const tw_cnt = w.tw_cnt, *const tw_off = w.tw_off;
-    // shared runs: the live nodes of the LEADING rows (the rows layer 0's group projection has to make)
-    int *const gl_off = w.gl_off, *const gl_idx = w.gl_idx, *const l0_gs = w.l0_gs, *const l0_off = w.l0_off, *const l0_idx = w.l0_idx;
-    TwinLists tw_pub{nullptr, nullptr, nullptr};
-    auto find_live_rows = [&](hipStream_t sq) -> int {
-        int *cnt = w.cnt, *off = w.off, *idx = w.idx, *cnt2 = w.cnt2, *off2 = w.off2, *idx2 = w.idx2, *entries = w.entries, *flag = w.flag;
-        int* hlast = w.hlast; uint8_t *flags1 = w.flags1, *flags2 = w.flags2;
-        ProfScope prof(DIGAT_KERNEL_GLUE, (double)B * ((double)U * U + 2.0 * C1 + H * 8.0) + (double)B * (U + C1) * 6, sq);
-        if (l0_chunked && !shared) {
-            hipLaunchKernelGGL(sparse_l0_chunks_kernel, dim3(1), dim3(1024), 0, sq, row_group, B, G, SPARSE_L0_ROWS, l0_gs, w.l0_lead);
-            DIGAT_CHECK_LAUNCH();
-        }
-        if (shared) {
-            // the adjacency pass for the leading rows only; every other row takes its leader's results (in place)
-            const bool want_entries = sparse_mode == DIGAT_XATTN_AUTO;
-            hipLaunchKernelGGL(user_live_flags_kernel, dim3((B + 3) / 4), dim3(256), (size_t)4 * ((U * U + 63) & ~63), sq, Au, cat_mask, cat_idx, B, U, H, C1,
-                               flags1, cnt, want_entries ? entries : (int*)nullptr, hlast, flags2, cnt2,
-                               twins ? tw_word : (unsigned*)nullptr, twins ? tw_flags : (uint8_t*)nullptr, twins ? tw_cnt : (int*)nullptr,
-                               run_leader);
-            DIGAT_CHECK_LAUNCH();
-            const LiveExpand le{flags1, twins ? tw_word : nullptr, tw_flags, flags2, cnt, entries, hlast, cnt2, tw_cnt,
-                                flags1, twins ? tw_word : nullptr, tw_flags, flags2,
-                                cnt, want_entries ? entries : nullptr, hlast, cnt2, twins ? tw_cnt : nullptr};
-            hipLaunchKernelGGL(live_expand_kernel, dim3((B + 3) / 4), dim3(256), 0, sq, le, row_group, B, U, C1);
-            DIGAT_CHECK_LAUNCH();
-        } else if (c.variant == ENC_GROUPED) {
-            // the user side is given per group: the adjacency pass once per GROUP, its results handed to the group's rows
-            uint8_t *fg = w.fg, *tfg = w.tfg, *bfg = w.bfg; unsigned* twg = w.twg;
-            int *cg = w.cg, *eg = w.eg, *hg = w.hg, *bcg = w.bcg, *tcg = w.tcg;
-            const bool want_entries = sparse_mode == DIGAT_XATTN_AUTO;
-            hipLaunchKernelGGL(user_live_flags_kernel, dim3((G + 3) / 4), dim3(256), (size_t)4 * ((U * U + 63) & ~63), sq, c.Au_g, c.cm_g, c.ci_g, G, U, H, C1,
-                               fg, cg, want_entries ? eg : (int*)nullptr, hg, bfg, bcg,
-                               twins ? twg : (unsigned*)nullptr, twins ? tfg : (uint8_t*)nullptr, twins ? tcg : (int*)nullptr);
-            DIGAT_CHECK_LAUNCH();
-            const LiveExpand le{fg, twins ? twg : nullptr, tfg, bfg, cg, eg, hg, bcg, tcg,
-                                flags1, twins ? tw_word : nullptr, tw_flags, flags2,
-                                cnt, want_entries ? entries : nullptr, hlast, cnt2, twins ? tw_cnt : nullptr};
-            hipLaunchKernelGGL(live_expand_kernel, dim3((B + 3) / 4), dim3(256), 0, sq, le, row_group, B, U, C1);
-            DIGAT_CHECK_LAUNCH();
-        } else {
-            hipLaunchKernelGGL(user_live_flags_kernel, dim3((B + 3) / 4), dim3(256), (size_t)4 * ((U * U + 63) & ~63), sq, Au, cat_mask, cat_idx, B, U, H, C1,
-                               flags1, cnt, sparse_mode == DIGAT_XATTN_AUTO ? entries : (int*)nullptr, hlast, flags2, cnt2,
-                               twins ? tw_word : (unsigned*)nullptr, twins ? tw_flags : (uint8_t*)nullptr, twins ? tw_cnt : (int*)nullptr);
-            DIGAT_CHECK_LAUNCH();
-        }
-        if (sparse_mode == DIGAT_XATTN_AUTO) {
-            hipLaunchKernelGGL(sparse_decide_kernel, dim3(1), dim3(1024), 0, sq, (const int*)entries, B, U, SPARSE_PER_NODE, flag);
-            DIGAT_CHECK_LAUNCH();
-            sparse_flag = flag;
-        }
-        // node list and bucket list: both scans in one launch, both lists in one launch
-        // up to four lists in the two launches: live nodes, live buckets, [layer-0 chunk leads | twin leads] as wanted
-        ScanPair sp{{cnt, cnt2}, {off, off2}, {nullptr, nullptr}};
-        ListPair lp{{flags1, flags2}, {off, off2}, {U, C1, U, U, U, U}, {idx, idx2}, {nullptr, nullptr}};
-        int jobs = 2;
-        if (l0_chunked) {
-            sp.cnt[jobs] = cnt; sp.off[jobs] = l0_off; sp.rowmask[jobs] = l0_lead;
-            lp.flags[jobs] = flags1; lp.off[jobs] = l0_off; lp.out[jobs] = l0_idx; lp.rowmask[jobs] = l0_lead;
-            ++jobs;
-        }
-        if (twins) {
-            sp.cnt[jobs] = tw_cnt; sp.off[jobs] = tw_off;
-            lp.flags[jobs] = tw_flags; lp.off[jobs] = tw_off; lp.out[jobs] = tw_list;
-            lp.width[jobs] = U;
-            ++jobs;
-        }
-        if (shared) {            // the live nodes of the leading rows: what layer 0's group projection makes
-            sp.cnt[jobs] = cnt; sp.off[jobs] = gl_off; sp.rowmask[jobs] = run_leader;
-            lp.flags[jobs] = flags1; lp.off[jobs] = gl_off; lp.out[jobs] = gl_idx; lp.rowmask[jobs] = run_leader;
-            lp.width[jobs] = U;
-            ++jobs;
-        }
-        hipLaunchKernelGGL(exclusive_scan2_kernel, dim3(jobs), dim3(1024), 0, sq, sp, B);
-        DIGAT_CHECK_LAUNCH();
-        hipLaunchKernelGGL(live_list2_kernel, dim3((B + 3) / 4, jobs), dim3(256), 0, sq, lp, B);
-        DIGAT_CHECK_LAUNCH();
-        pend_rowidx = idx; pend_nrows = off + B; pend_bidx = idx2; pend_nb = off2 + B; pend_flags = flags1; pend_hlast = hlast;
-        return DIGAT_OK;
-    };
-    auto publish_live_rows = [&]() {
-        rowidx = pend_rowidx; nrows_dev = pend_nrows; bucket_idx = pend_bidx; nbuckets_dev = pend_nb; live_flags = pend_flags;
-        hist_last = pend_hlast;
-        if (twins) tw_pub = TwinLists{tw_word, tw_list, tw_off + B};
-    };
-    // side stream: 0 = never, 1 = always (the caller's flags), 2 = by pass size (default): below 2 048 rows — there the news kernels
-    // are a few waves of workgroups each; from 2 048 rows up every kernel fills the chip by itself and the second stream only makes
-    // launches share it (4 096 rows, three passes in flight: 3.21 vs 3.28 ms per pass; stress 16.4 vs 16.8, MIND-large shape 4.52 vs 4.65)
-    const int side_mode = (p->flags & DIGAT_PARAMS_SIDE_STREAM_OFF) ? 0 : ((p->flags & DIGAT_PARAMS_SIDE_STREAM_ON) ? 1 : 2);
-    SideStream* side = (side_mode == 0 || (side_mode == 2 && B >= 2048)) ? nullptr : side_stream(st);
-    // Small news graphs (the wave-per-centre score kernel adds K3 itself): the node projections of a layer depend only on
-    // the news nodes, so they are issued on the side stream a phase early — layer 0's under the initial user context,
-    // layer i+1's under the pooling of user context i — instead of waiting for c_u.
-    const bool news_early = L > 0 && N <= 16 && d / 4 <= 256;       // same arithmetic with and without the side stream
-    // The padding slots of a news graph are dead nodes — neither projected nor (on the sparse kernel) scored or written in any layer
-    // (news_live_flags_kernel); the context pooling masks them and skips zero weights, nobody else reads them.  Larger graphs
-    // (N > 16, sparse kernel): projection and Eq. 8 run on the live list.  Small graphs: the projections of layers >= 1 do; the
-    // one-workgroup-per-graph Eq. 8 kernel still computes every centre (a live centre visits its adjacency entries only: live nodes).
-    const bool news_lists_on = L > 0 && d / 4 <= 256 && !(p->flags & DIGAT_PARAMS_NO_LIVE_ROWS);
-    const bool news_lists = news_lists_on && ((!news_early && (p->flags & DIGAT_NEWS_XATTN_SPARSE) && N > 16) || (news_early && L > 1 && B >= 2048));
-    // (small graphs below 2 048 rows: the three list launches sit on the news chain's critical path and cost what two smaller projections save)
-    const int* news_rowidx = nullptr; const int* news_nrows = nullptr; const uint8_t* news_flags = nullptr;
-    auto news_project = [&](int layer, const float* Xn_cur, hipStream_t sq) -> int {
-        const digat_layer_params& ln = p->news[layer];
-        GemmArgs gp = gemm_plain(Xn_cur, d, ln.W, ln.bW, w.xn.h, d, B * N, d, d, 0);
-        gp.w[1] = ln.F1; gp.bias[1] = nullptr; gp.y[1] = w.xn.P;
-        gp.w[2] = ln.F2; gp.bias[2] = nullptr; gp.y[2] = w.xn.Q;
-        gp.nsegs = 3;
-        gp.x3_segs = pq_x3 ? 6 : 0;
-        gp.m_dispatch = 1 << 30;       // always the large-M kernel: a row's bits then do not depend on the batch it sits in
-                                       // (digat_news_project0 makes the same launch per news, once)
-        gp.wsplit = (const unsigned short*)ln.wsplit;
-        gp.format = lfmt; gp.range_flag = rflag;
-        if (news_rowidx && gemm_takes_row_list(gp)) { gp.rowidx = news_rowidx; gp.nrows_dev = news_nrows; }      // live nodes only (layers >= 1)
-        return launch_gemm(gp, sq, DIGAT_KERNEL_PROJ);
-    };
-    // layer 0 of grouped rows: every row of a group has the same user nodes, so the G groups are projected once
-    // ([G*U] rows instead of [B*U]).  h and Q of a group go straight to the h / Q slots of the Eq. 8 workspace and are
-    // read through the group index by the aggregation / score kernels (the 37 rows of an impression share them: they
-    // stay in L2); only P' = K3_b + P depends on the row and is expanded later.  Needs nothing but the inputs.
-    auto group_project = [&](hipStream_t sq) -> int {
-        const digat_layer_params& lu = p->user[0];
-        if (shared) {
-            // shared runs: [h|P|Q] of the LEADING rows' live nodes, in place in the full-size planes (the per-row launch of layer 0
-            // restricted to the rows whose results anybody reads; K3 joins in the Eq. 8 kernel, as for the groups below)
-            GemmArgs gs = gemm_plain(w.Xu[0], d, lu.W, lu.bW, w.xu.h, d, B * U, d, d, 0);
-            gs.w[1] = lu.F1; gs.bias[1] = nullptr; gs.y[1] = w.xu.P;
-            gs.w[2] = lu.F2; gs.bias[2] = nullptr; gs.y[2] = w.xu.Q;
-            gs.nsegs = 3;
-            gs.x3_segs = pq_x3 ? 6 : 0;
-            gs.wsplit = (const unsigned short*)lu.wsplit;
-            gs.format = lfmt; gs.range_flag = rflag;
-            gs.m_dispatch = B * U;
-            if (want_live && gemm_takes_row_list(gs)) { gs.rowidx = gl_idx; gs.nrows_dev = gl_off + B; }
-            return launch_gemm(gs, sq, DIGAT_KERNEL_PROJ);
-        }
-        const size_t ndg = (size_t)G * U * d;
-        float* Xg = xu0_grouped ? const_cast<float*>(Xg0) : w.Xu[1];   // group nodes: built by the caller, or here (Xu[1] is free until layer 0 writes it)
-        float* h0 = w.xu.h;
-        float* P0 = h0 + ndg;                               // behind the groups' h in the h slot (2 ndg <= nd)
-        float* Q0 = w.xu.Q;                                 // the groups' Q at the start of the full-size Q plane
-        const long total4 = (long)ndg / 4;
-        int blocks = (int)((total4 + 255) / 256);
-        if (blocks > 2048) blocks = 2048;
-        if (!xu0_grouped) {
-            hipLaunchKernelGGL(build_user_nodes_kernel, dim3(blocks), dim3(256), 0, sq, (const float4*)c.ue,
-                               (const float4*)p->topic_node_embedding, (float4*)Xg, (long)G, H, C, d / 4, (const int*)nullptr);
-            DIGAT_CHECK_LAUNCH();
-        }
-        if (c.hist_hpq0 && c.topic_hpq0 && (long)B * U >= 2048) {
-            // [h|P|Q] of a history node depend on that news alone and those of a topic node on nothing: the caller keeps them
-            // per news / per topic (digat_user_project0) and hands over the groups' history rows; the projection GEMM of the
-            // groups becomes three assemblies [history rows | topic rows] (same kernel, same bits: rows are independent)
-            float* dst[3] = {h0, P0, Q0};
-            UserNodes3 un3;
-            for (int t = 0; t < 3; ++t) {
-                un3.hist[t] = (const float4*)(c.hist_hpq0 + (size_t)t * G * H * d);
-                un3.topic[t] = (const float4*)(c.topic_hpq0 + (size_t)t * C * d);
-                un3.dst[t] = (float4*)dst[t];
-            }
-            hipLaunchKernelGGL(build_user_nodes3_kernel, dim3(blocks, 3), dim3(256), 0, sq, un3, (long)G, H, C, d / 4);
-            DIGAT_CHECK_LAUNCH();
-            return DIGAT_OK;
-        }
-        GemmArgs gg = gemm_plain(Xg, d, lu.W, lu.bW, h0, d, G * U, d, d, 0);
-        gg.w[1] = lu.F1; gg.bias[1] = nullptr; gg.y[1] = P0;
-        gg.w[2] = lu.F2; gg.bias[2] = nullptr; gg.y[2] = Q0;
-        gg.nsegs = 3;
-        gg.x3_segs = pq_x3 ? 6 : 0;
-        gg.wsplit = (const unsigned short*)lu.wsplit;
-        gg.format = lfmt; gg.range_flag = rflag;
-        gg.m_dispatch = B * U;                              // the kernel the per-row path would pick: same bits
-        return launch_gemm(gg, sq, DIGAT_KERNEL_PROJ);
-    };
-    // Work that depends on the inputs alone goes out on the side stream at once, under the initial user context:
-    // the group projections of layer 0 and (small news graphs) the news projections of layer 0.
-    const bool group_early = side && L > 0 && row_group;
-    const bool live_early = side && want_scan;
-    if (side && (news_early || group_early || live_early)) {
-        if (hipEventRecord(side->fork, st) != hipSuccess || hipStreamWaitEvent(side->s, side->fork, 0) != hipSuccess)
-            return DIGAT_ERR_LAUNCH;
-    }
-    if (live_early) {                  // first: layer 0 may need the sparse / dense decision
-        rc = find_live_rows(side->s);
-        if (rc) return rc;
-    }
-    if (group_early) {
-        rc = group_project(side->s);
-        if (rc) return rc;
-    }
-    if (group_early || live_early) {
-        if (hipEventRecord(side->early, side->s) != hipSuccess) return DIGAT_ERR_LAUNCH;
-    }
-    if (news_early && !news_hpq0) {      // news_hpq0: the caller kept layer 0's news projections per news (digat_news_project0)
-        rc = news_project(0, c.Xn_in, side ? side->s : st);
-        if (rc) return rc;
-    }
-    // [kq_topic | kq_user | K3 of the user graph's layer 0] are functions of the candidate's cached c_n0: a caller that keeps them
-    // per news (digat_news_context_queries, next to c_n0 itself) hands over the batch's rows and the first link of the chain goes
-    const size_t bd = (size_t)B * d;
-    if (!ctxq0) {
-        rc = from_c_n(0, st);
-        if (rc) return rc;
-    }
-    const bool xu0_shared = shared && sparse_mode == DIGAT_XATTN_SPARSE;      // only the leading rows of Xu[0] were built: read through row_group
-    rc = user_ctx_tail(xu0_grouped ? Xg0 : w.Xu[0], nullptr, st, (xu0_grouped || xu0_shared) ? row_group : nullptr, nullptr,
-                       ctxq0 ? ctxq0 : nullptr, ctxq0 ? ctxq0 + bd : nullptr);        // c_u (:192)
-    if (rc) return rc;
-    const float* xn_cur = c.Xn_in;
-    int un = 0, nn = 0;
-    for (int i = 0; i < L; ++i) {
-        const digat_layer_params& ln = p->news[i];
-        const digat_layer_params& lu = p->user[i];
-        const float* r_user = (i == 0 && ctxq0 && L > 0) ? ctxq0 + 2 * bd : w.r_user[i & 1];     // K3 of the user graph, from the previous c_n
-        hipStream_t sn = side ? side->s : st;
-        if (side && i == 0) {                      // the news chain starts from the initial c_u (caller's stream)
-            if (hipEventRecord(side->fork, st) != hipSuccess || hipStreamWaitEvent(sn, side->fork, 0) != hipSuccess)
-                return DIGAT_ERR_LAUNCH;
-        }
-        if (side && i > 0) {                       // K3 of this layer's user graph + the live lists come from the side stream
-            if (hipStreamWaitEvent(st, side->join, 0) != hipSuccess) return DIGAT_ERR_LAUNCH;
-        }
-        // ---- user graph, Eq. 8 (caller's stream)
-        if (i == 0 && want_scan && !live_early) {              // no side stream: the lists and the sparse / dense decision first
-            rc = find_live_rows(st);
-            if (rc) return rc;
-        }
-        if (i == 0 && side && (group_early || live_early)) {
-            if (hipStreamWaitEvent(st, side->early, 0) != hipSuccess) return DIGAT_ERR_LAUNCH;
-        }
-        // The live lists are in force from layer 0 on: a dead node (a history padding slot, the topic node of an unread category:
-        // only its self loop, pooled with weight 0) is never projected, scored or written, in ANY layer.  Its rows of the two
-        // node buffers therefore hold whatever the workspace held; the one reader that walks all history rows — the topic
-        // pooling — takes them as zero through the flags (a select: no bits of such a row can reach a result;
-        // test_uninitialised_workspace_cannot_reach_the_outputs fills the scratch with NaN patterns).
-        if (i == 0 && want_live) publish_live_rows();
-        if (i == 0 && row_group) {
-            const size_t ndg = shared ? (size_t)B * U * d : (size_t)G * U * d;      // shared runs: full-size planes, a group's rows sit in its leading row's slots
-            float* h0 = w.xu.h;
-            float* P0 = h0 + ndg;                           // group_project's layout
-            float* P = w.xu.P;
-            float* Q0 = w.xu.Q;
-            if (!group_early) {
-                rc = group_project(st);
-                if (rc) return rc;
-            }
-            rc = DIGAT_OK;
-            if (sparse_mode != DIGAT_XATTN_DENSE && d / 4 <= 256) {
-                // P' = K1 (the groups' P0) + K3 (this layer's r_user) is formed inside the kernel: nothing is expanded
-                // live centres only (the list of find_live_rows), P / Q / h / X read through the group index
-                const bool l0_live = want_live && live_flags;
-                SparseArgs sg{P0, Q0, h0, xu0_grouped ? Xg0 : w.Xu[0], lu.a, Au, w.Xu[1], r_user, row_group, l0_live ? live_flags : nullptr,
-                                    sparse_mode == DIGAT_XATTN_AUTO ? sparse_flag : nullptr, B, U, d / 4, (xu0_grouped || xu0_shared) ? 1 : 0,
-                                    (!l0_live && xu0_grouped && want_live) ? (const uint8_t*)pend_flags : nullptr, w.Xu[0],
-                                    l0_live ? rowidx : nullptr, l0_live ? nrows_dev : nullptr, G, nullptr, 0, 0};
-                if (l0_chunked && l0_live && sparse_l0_ok(sg)) {
-                    // R rows of an impression per wave: every neighbour row fetched serves R rows (xattn_sparse_l0_kernel; same bits)
-                    rc = launch_sparse_l0(sg, l0_lead, l0_idx, l0_off + B, shared ? (B + SPARSE_L0_ROWS - 1) / SPARSE_L0_ROWS : G, st);
-                } else
-                rc = launch_sparse(sg, st);
-            }
-            if (!rc && !(sparse_mode == DIGAT_XATTN_SPARSE && d / 4 <= 256)) {
-                const int* skip_if = sparse_mode == DIGAT_XATTN_AUTO && d / 4 <= 256 ? sparse_flag : nullptr;
-                const size_t nd = (size_t)B * U * d;
-                float* alpha = w.xu.alpha;
-                {
-                    const long total4 = (long)nd / 4;
-                    int blocks = (int)((total4 + 255) / 256);
-                    if (blocks > 4096) blocks = 4096;
-                    ProfScope prof(DIGAT_KERNEL_GLUE, skip_if ? 0.0 : (double)nd * 4, st);
-                    hipLaunchKernelGGL(expand_proj_kernel, dim3(blocks), dim3(256), 0, st, (const float4*)P0, (const float4*)r_user,
-                                       row_group, (float4*)P, (long)B, U, d / 4, skip_if);
-                    DIGAT_CHECK_LAUNCH();
-                }
-                rc = launch_xattn_pairwise(P, Q0, h0, w.Xu[0], lu.a, Au, w.Xu[1], alpha, B, U, d, st, nullptr, row_group, nullptr, true,
-                                           skip_if);
-            }
-        } else {
-            // every layer projects, scores and writes the live nodes only (layer 0 too: see publish_live_rows above)
-            XattnOpts o;
-            o.wsplit = lu.wsplit; o.rowidx = rowidx; o.nrows_dev = nrows_dev; o.live = live_flags;
-            o.sparse_mode = sparse_mode; o.sparse_flag = sparse_flag; o.pq_x3 = pq_x3; o.pq_mode = i > 0 ? pq_mode : 0;
-            // after the last layer only the history rows are read (the user context's topic pooling, :124):
-            // the topic nodes' own Eq. 8 is not computed there (wave-per-centre sparse kernel)
-            o.centre_limit = (i > 0 && i == L - 1 && sparse_mode == DIGAT_XATTN_SPARSE) ? H : 0;
-            o.gemm_format = lfmt; o.range_flag = rflag;
-            o.tw = (i > 0 && tw_pub.word) ? &tw_pub : nullptr;
-            rc = xattn_core(w.Xu[un], Au, r_user, lu.W, lu.bW, lu.F1, lu.F2, lu.a, w.Xu[un ^ 1], nullptr, B, U, d, w.xws, w.xws_bytes, st, o);
-        }
-        if (rc) return rc;
-        if (side && hipEventRecord(side->fork, st) != hipSuccess) return DIGAT_ERR_LAUNCH;      // this layer's user nodes are written
-        // ---- news graph, Eq. 8 + context + the queries that follow from the new c_n (side stream)
-        {
-            GemmArgs g3 = gemm_plain(c_u, d, ln.F3, ln.b3, w.r_news, d, B, d, d, 0);              // K3 of the news graph
-            g3.wsplit = (const unsigned short*)ln.f3_wsplit; g3.format = fmt; g3.range_flag = rflag;
-            g3.m_dispatch = bd_disp;
-            rc = launch_gemm(g3, sn);
-        }
-        if (rc) return rc;
-        if (i == 0 && news_lists) {            // the live nodes of the news graphs, once per pass (the graphs do not change with the layers)
-            int *cnt_n = w.cnt_n, *off_n = w.off_n, *idx_n = w.idx_n; uint8_t* flags_n = w.flags_n;
-            ProfScope prof(DIGAT_KERNEL_GLUE, (double)B * ((double)N * N + 6.0 * N), sn);
-            hipLaunchKernelGGL(news_live_flags_kernel, dim3((B + 3) / 4), dim3(256), (size_t)4 * ((N * N + 15) & ~15), sn, An, Mn, B, N, flags_n, cnt_n);
-            DIGAT_CHECK_LAUNCH();
-            ScanPair sp{{cnt_n}, {off_n}, {nullptr}};
-            ListPair lp{{flags_n}, {off_n}, {N, N, N, N, N, N}, {idx_n}, {nullptr}};
-            hipLaunchKernelGGL(exclusive_scan2_kernel, dim3(1), dim3(1024), 0, sn, sp, B);
-            DIGAT_CHECK_LAUNCH();
-            hipLaunchKernelGGL(live_list2_kernel, dim3((B + 3) / 4, 1), dim3(256), 0, sn, lp, B);
-            DIGAT_CHECK_LAUNCH();
-            news_rowidx = idx_n; news_nrows = off_n + B; news_flags = flags_n;
-        }
-        if (news_early) {        // projections already done (news_project below): K3 joins in the score kernel
-            const size_t ndn = (size_t)B * N * d;
-            const float* hn = (i == 0 && news_hpq0) ? news_hpq0 : w.xn.h;
-            // layer 0 with news_index: h | P | Q and the nodes themselves are the per-news TABLES, read in place through the index
-            const bool tab = i == 0 && news_hpq0 && c.news_index;
-            const size_t plane = tab ? (size_t)c.news_rows * N * d : ndn;
-            rc = launch_xattn_pairwise(hn + plane, hn + 2 * plane, hn, xn_cur, ln.a, An, w.Xn[nn], w.xn.alpha, B, N, d, sn, nullptr, nullptr,
-                                       w.r_news, false, nullptr, tab ? c.news_index : nullptr);
-        } else if (i == 0 && news_hpq0 && c.news_index) {
-            // Larger news graphs, layer 0 from the per-news TABLES (round 4): [h | P | Q] of a news graph depend on the news alone, so
-            // the projection GEMM of layer 0 (B N rows: at N = 26 the largest launch of a MIND-large step) is replaced by reading the
-            // candidates' rows of the table IN PLACE — the sparse kernel's group indirection with the candidate id as the "group" —
-            // and adding K3 in the kernel, in the GEMM epilogue's order (K3 + K1): the bits of the in-batch launch.
-            const size_t plane = (size_t)c.news_rows * N * d;
-            hipLaunchKernelGGL(index_to_i32_kernel, dim3((B + 255) / 256), dim3(256), 0, sn, c.news_index, w.idx32, B);
-            DIGAT_CHECK_LAUNCH();
-            SparseArgs sgn{news_hpq0 + plane, news_hpq0 + 2 * plane, news_hpq0, xn_cur, ln.a, An, w.Xn[nn], w.r_news, w.idx32, news_flags,
-                           nullptr, B, N, d / 4, 1, nullptr, nullptr, news_rowidx, news_nrows, B, nullptr, 0, 0};      // G (profiling: distinct rows behind the index): at most B candidates
-            if (news_rowidx) sgn.prof_part = XPART_NEWS + 1;
-            rc = launch_sparse(sgn, sn);
-        } else {
-            // larger news graphs (N = 26 / 65: the breadth-first SAG, a few entries per node) take the sparse kernel when the
-            // caller says so (flags bit 3); there is no device-side decision for this graph
-            XattnOpts o;
-            o.wsplit = ln.wsplit; o.rowidx = news_rowidx; o.nrows_dev = news_nrows; o.live = news_flags;
-            o.sparse_mode = (p->flags & DIGAT_NEWS_XATTN_SPARSE) ? DIGAT_XATTN_SPARSE : DIGAT_XATTN_DENSE;
-            o.pq_x3 = pq_x3;
-            o.pq_mode = pq_mode;      // the news graph's P' always carries K3 from the GEMM epilogue: bf16 storage applies at every layer
-            o.gemm_format = lfmt; o.range_flag = rflag;
-            o.prof_part = news_rowidx ? XPART_NEWS + 1 : 0;
-            rc = xattn_core(xn_cur, An, w.r_news, ln.W, ln.bW, ln.F1, ln.F2, ln.a, w.Xn[nn], nullptr, B, N, d, w.xws_news, w.xws_news_bytes, sn, o);
-        }
-        if (rc) return rc;
-        xn_cur = w.Xn[nn]; nn ^= 1; un ^= 1;
-        rc = news_ctx(xn_cur, sn, i == 0);         // c_n += ... (:196)
-        if (rc) return rc;
-        rc = from_c_n(i + 1, sn);                  // queries (+ next K3, into the other r_user buffer) from the UPDATED c_n
-        if (rc) return rc;
-        if (side && hipEventRecord(side->join, sn) != hipSuccess) return DIGAT_ERR_LAUNCH;      // the next user-graph update may start
-        if (news_early && i + 1 < L) {             // the next layer's news projections need only Xn
-            rc = news_project(i + 1, xn_cur, sn);
-            if (rc) return rc;
-        }
-        // The user context of this layer feeds the next NEWS update and the result, not the next user-graph update: it runs
-        // on the side stream once the caller's stream has written the user nodes, under the next layer's projection GEMM.
-        if (side && hipStreamWaitEvent(sn, side->fork, 0) != hipSuccess) return DIGAT_ERR_LAUNCH;
-        rc = user_ctx_tail(w.Xu[un], c_u, sn, nullptr, live_flags);       // c_u += ... (:197)
-        if (rc) return rc;
-    }
-    if (side && L > 0) {
-        if (hipEventRecord(side->join, side->s) != hipSuccess || hipStreamWaitEvent(st, side->join, 0) != hipSuccess)
-            return DIGAT_ERR_LAUNCH;
-    }
-    return DIGAT_OK;
-}
-
-size_t digat_encoder_workspace_bytes(int B, int N, int H, int C, int d, int depth) { (void)depth; return encoder_ws_bytes(B, N, H, C, d, ENC_PLAIN); }
-
-// Every entry: the checks, the carve and (grouped / shared entries) the per-row user arrays of the variant, then the unfolded
-// path or encoder_fwd_folded.  ENC_GROUPED: the user tensors are per group (G of them) and row_group[b] names the group of
-// row b; the small per-row byte / index arrays are expanded here, so Au / cat_mask / cat_idx are per row in every variant and
-// only ue [G,H,d] stays per group.
-static int encoder_fwd_impl(EncoderCall& c) {
-    const digat_params* p = c.p;
-    const bool grouped = c.variant == ENC_GROUPED;
-    if (!p || !c.Xn_in || !c.An || !c.Mn || !c.ue || !c.out_news || !c.out_user || !c.workspace) return DIGAT_ERR_ARG;
-    if (grouped ? (!c.Au_g || !c.cm_g || !c.ci_g || !c.row_group || c.G <= 0) : (!c.Au || !c.cat_mask || !c.cat_idx)) return DIGAT_ERR_ARG;
-    const int B = c.B, N = c.N, H = c.H;
-    if (B < 0 || N <= 0 || H < 0) return DIGAT_ERR_ARG;
-    const int d = p->d, C = p->category_num, L = p->depth, U = H + C;
-    const bool folded = p->cand_fold_W && p->user_news_fold_W && p->userAtt_fold_W;
-    if (grouped && !folded) return DIGAT_ERR_ARG;                              // grouped = folded path
-    if (d <= 0 || d % 4 || L < 0 || L > DIGAT_MAX_DEPTH || N > DIGAT_MAX_NODES || U > DIGAT_MAX_NODES || C < 0)
-        return DIGAT_ERR_SHAPE;
-    if (grouped && (size_t)4 * c.G > (size_t)B) return DIGAT_ERR_SHAPE;        // the group-level projections reuse one [B,U,d] buffer
-    Arena ar(c.workspace, c.workspace_bytes);
-    if (!encoder_carve(ar, B, N, H, C, d, c.variant, c.ws)) return DIGAT_ERR_WORKSPACE;
-    if (B == 0) return DIGAT_OK;
-    // per-news tables read in place: only where layer 0 of the news graph is the one reader of the node table (given c_n0,
-    // cached projections, the small-graph kernel)
-    // ... or, for larger news graphs (round 4), the sparse Eq. 8 kernel through the candidate ids (flags: DIGAT_NEWS_XATTN_SPARSE)
-    if (c.news_index && !(c.c_n0 && c.news_hpq0 && L > 0 && d / 4 <= 256 && c.news_rows > 0 && c.news_rows <= 0x7fffffffLL &&
-                          (N <= 16 || ((p->flags & DIGAT_NEWS_XATTN_SPARSE) && N <= DIGAT_MAX_NODES)) && folded)) return DIGAT_ERR_ARG;
-    hipStream_t st = c.st;
-    const EncoderWs& w = c.ws;
-    int rc;
-    if (grouped) {
-        // expand the small per-user byte / index arrays to rows (4.6 MB for 1024 rows of 67x67 adjacency)
-        const GatherJobs jobs{{c.Au_g, c.cm_g, (const uint8_t*)c.ci_g}, {w.Au, w.cm, (uint8_t*)w.ci}, {(long)U * U, (long)(C + 1), (long)H * 8}};
-        hipLaunchKernelGGL(gather_rows_kernel, dim3(B), dim3(256), 0, st, jobs, c.row_group, (long)B);
-        DIGAT_CHECK_LAUNCH();
-        c.Au = w.Au; c.cat_mask = w.cm; c.cat_idx = w.ci;
-    } else if (c.variant == ENC_SHARED) {
-        // consecutive rows with identical users: runs found on the device (user_rows_same_kernel, shared_runs_kernel)
-        ProfScope prof(DIGAT_KERNEL_GLUE, (double)B * ((double)H * d * 4 + (double)U * U + (C + 1) + 8.0 * H), st);
-        hipLaunchKernelGGL(user_rows_same_kernel, dim3(B), dim3(256), 0, st, (const uint4*)c.ue, c.Au, c.cat_mask, c.cat_idx, B, (long)H * d / 4, U * U,
-                           C + 1, H, w.same);
-        DIGAT_CHECK_LAUNCH();
-        hipLaunchKernelGGL(shared_runs_kernel, dim3(1), dim3(1024), 0, st, (const uint8_t*)w.same, B, SPARSE_L0_ROWS, w.leader_of, w.is_leader, w.lead);
-        DIGAT_CHECK_LAUNCH();
-        c.row_group = w.leader_of; c.run_leader = w.is_leader; c.run_lead = w.lead;
-    }
-    // Rows of one impression share the user nodes.  When every reader of the layer-0 nodes can go through the group index
-    // (the sparse Eq. 8 kernel and the topic pooling can; the dense tile / aggregation kernels cannot) they are built once
-    // per GROUP: 3 MB instead of a 110 MB expansion that the first two kernels would read back.
-    // Shared-user runs (digat_encoder_fwd_shared): ue is per ROW, row_group[b] = the row that leads row b's run.  Taken when the
-    // group-indexed kernels of layer 0 apply (sparse Eq. 8 on the live lists); otherwise the runs are ignored: the plain per-row path.
-    const bool shared = c.run_leader && c.run_lead && c.row_group && folded && L > 0 && (p->flags & 3) == DIGAT_XATTN_SPARSE &&
-                        !(p->flags & DIGAT_PARAMS_NO_LIVE_ROWS) && d / 4 <= 128 && U <= 128 && U > 16;
-    if ((c.run_leader || c.run_lead) && !shared) { c.row_group = nullptr; c.G = 0; c.run_leader = c.run_lead = nullptr; }
-    const int G = c.G;
-    const bool xu0_grouped = !shared && folded && c.row_group && L > 0 && (p->flags & 3) == DIGAT_XATTN_SPARSE && d / 4 <= 256 && U > 16 && 3 * (long)G <= B;
-    // user graph nodes = [history | topic nodes]  (:191)
-    float* const Xg0 = xu0_grouped ? w.xu.h + 2 * (size_t)G * U * d : nullptr;      // behind the groups' h and P in the h slot (3 G <= B)
-    {
-        const long nrows = xu0_grouped ? G : B;
-        const long total4 = nrows * U * (d / 4);
-        int blocks = (int)((total4 + 255) / 256);
-        if (blocks > 2048) blocks = 2048;
-        ProfScope prof(DIGAT_KERNEL_GLUE, (double)nrows * ((double)H * d * 8 + (double)C * d * 4), st);
-        // shared runs: ue is per row already, and only the run-leading rows are ever read (through row_group)
-        hipLaunchKernelGGL(build_user_nodes_kernel, dim3(blocks), dim3(256), 0, st, (const float4*)c.ue,
-                           (const float4*)p->topic_node_embedding, (float4*)(xu0_grouped ? Xg0 : w.Xu[0]), nrows, H, C, d / 4,
-                           (xu0_grouped || shared) ? (const int*)nullptr : c.row_group, shared ? c.run_leader : (const uint8_t*)nullptr);
-        DIGAT_CHECK_LAUNCH();
-    }
-    // c_n: given (inference, :189) or computed (forward, :180); it lives in out_news from here on
-    const bool c_n0_in_place = c.c_n0 && folded && L > 0;        // layer 0's news context update writes out_news from c_n0 directly
-    if (c_n0_in_place) {
-    } else if (c.c_n0) {
-        if (hipMemcpyAsync(c.out_news, c.c_n0, (size_t)B * d * 4, hipMemcpyDeviceToDevice, st) != hipSuccess)
-            return DIGAT_ERR_LAUNCH;
-    } else {
-        rc = digat_news_ctx_fwd(c.Xn_in, c.Mn, p->cand_K, p->cand_Q, p->cand_bQ, p->news_graph_W, p->news_graph_b,
-                                nullptr, c.out_news, B, N, d, w.cws, w.cws_bytes, st);
-        if (rc) return rc;
-    }
-    if (folded) {
-        if (!c.c_n0) c.ctxq0 = nullptr;          // the queries belong to a given news context
-        return encoder_fwd_folded(c, Xg0);
-    }
-    // c_u (:192)
-    rc = digat_user_ctx_fwd(w.Xu[0], c.cat_mask, c.cat_idx, c.out_news, p->user_news_K, p->user_news_Q, p->user_news_bQ,
-                            p->featureAffine_W, p->featureAffine_b, p->userAtt_K, p->userAtt_Q, p->userAtt_bQ,
-                            nullptr, c.out_user, B, U, H, C + 1, d, w.cws, w.cws_bytes, st);
-    if (rc) return rc;
-
-    const float* xn_cur = c.Xn_in;
-    int un = 0, nn = 0;
-    XattnOpts o;
-    o.gemm_format = (p->flags & DIGAT_PARAMS_GEMM_F16X3) ? 1 : 0;
-    o.range_flag = o.gemm_format ? (unsigned*)p->range_flag : nullptr;
-    if (p->flags & DIGAT_PARAMS_PROJ_F16F8C) o.gemm_format = DIGAT_GEMM_F16F8C;     // the layers' images (the only ones this loop reads)
-    for (int i = 0; i < L; ++i) {
-        const digat_layer_params& ln = p->news[i];
-        const digat_layer_params& lu = p->user[i];
-        // both graph updates read the PREVIOUS contexts (:194-195)
-        rc = launch_gemm(gemm_plain(c.out_user, d, ln.F3, ln.b3, w.r_news, d, B, d, d, 0), st);
-        if (rc) return rc;
-        o.wsplit = ln.wsplit;
-        rc = xattn_core(xn_cur, c.An, w.r_news, ln.W, ln.bW, ln.F1, ln.F2, ln.a, w.Xn[nn], nullptr, B, N, d, w.xws, w.xws_bytes, st, o);
-        if (rc) return rc;
-        rc = launch_gemm(gemm_plain(c.out_news, d, lu.F3, lu.b3, w.r_user[0], d, B, d, d, 0), st);
-        if (rc) return rc;
-        o.wsplit = lu.wsplit;
-        rc = xattn_core(w.Xu[un], c.Au, w.r_user[0], lu.W, lu.bW, lu.F1, lu.F2, lu.a, w.Xu[un ^ 1], nullptr, B, U, d, w.xws, w.xws_bytes, st, o);
-        if (rc) return rc;
-        xn_cur = w.Xn[nn]; nn ^= 1; un ^= 1;
-        // c_n += news context (:196); c_u += user context with the UPDATED c_n (:197)
-        rc = digat_news_ctx_fwd(xn_cur, c.Mn, p->cand_K, p->cand_Q, p->cand_bQ, p->news_graph_W, p->news_graph_b,
-                                c.out_news, c.out_news, B, N, d, w.cws, w.cws_bytes, st);
-        if (rc) return rc;
-        rc = digat_user_ctx_fwd(w.Xu[un], c.cat_mask, c.cat_idx, c.out_news, p->user_news_K, p->user_news_Q, p->user_news_bQ,
-                                p->featureAffine_W, p->featureAffine_b, p->userAtt_K, p->userAtt_Q, p->userAtt_bQ,
-                                c.out_user, c.out_user, B, U, H, C + 1, d, w.cws, w.cws_bytes, st);
-        if (rc) return rc;
-    }
-    return DIGAT_OK;
-}
-
-int digat_encoder_fwd(const digat_params* p, const float* Xn_in, const uint8_t* An, const uint8_t* Mn,
-                      const float* ue, const uint8_t* Au, const uint8_t* cat_mask, const int64_t* cat_idx,
-                      const float* c_n0, float* out_news, float* out_user, int B, int N, int H,
-                      void* workspace, size_t workspace_bytes, void* stream) {
-    EncoderCall c{};
-    c.variant = ENC_PLAIN; c.p = p; c.Xn_in = Xn_in; c.An = An; c.Mn = Mn; c.ue = ue; c.Au = Au; c.cat_mask = cat_mask; c.cat_idx = cat_idx;
-    c.c_n0 = c_n0; c.out_news = out_news; c.out_user = out_user; c.B = B; c.N = N; c.H = H;
-    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.st = (hipStream_t)stream;
-    return encoder_fwd_impl(c);
-}
-
-size_t digat_encoder_grouped_workspace_bytes(int B, int N, int H, int C, int d, int depth) { (void)depth; return encoder_ws_bytes(B, N, H, C, d, ENC_GROUPED); }
-
-int digat_encoder_fwd_grouped(const digat_params* p, const float* Xn_in, const uint8_t* An, const uint8_t* Mn,
-                              const float* ue_g, const uint8_t* Au_g, const uint8_t* cat_mask_g, const int64_t* cat_idx_g,
-                              const int32_t* row_group, const float* c_n0, float* out_news, float* out_user,
-                              int B, int G, int N, int H, void* workspace, size_t workspace_bytes, void* stream) {
-    return digat_encoder_fwd_grouped_cached(p, Xn_in, An, Mn, ue_g, Au_g, cat_mask_g, cat_idx_g, row_group, c_n0, nullptr, nullptr, nullptr,
-                                            nullptr, nullptr, 0, out_news, out_user, B, G, N, H, workspace, workspace_bytes, stream);
-}
-
-int digat_encoder_fwd_grouped_cached(const digat_params* p, const float* Xn_in, const uint8_t* An, const uint8_t* Mn,
-                                     const float* ue_g, const uint8_t* Au_g, const uint8_t* cat_mask_g, const int64_t* cat_idx_g,
-                                     const int32_t* row_group, const float* c_n0, const float* news_hpq0,
-                                     const float* hist_hpq0, const float* topic_hpq0, const float* ctxq0,
-                                     const int64_t* news_index, int64_t news_rows, float* out_news,
-                                     float* out_user, int B, int G, int N, int H, void* workspace, size_t workspace_bytes,
-                                     void* stream) {
-    if ((hist_hpq0 == nullptr) != (topic_hpq0 == nullptr)) return DIGAT_ERR_ARG;
-    if (ctxq0 && !c_n0) return DIGAT_ERR_ARG;           // the queries belong to a given news context
-    EncoderCall c{};
-    c.variant = ENC_GROUPED; c.p = p; c.Xn_in = Xn_in; c.An = An; c.Mn = Mn; c.ue = ue_g; c.Au_g = Au_g; c.cm_g = cat_mask_g; c.ci_g = cat_idx_g;
-    c.row_group = row_group; c.G = G; c.c_n0 = c_n0; c.out_news = out_news; c.out_user = out_user; c.B = B; c.N = N; c.H = H;
-    c.news_hpq0 = news_hpq0; c.hist_hpq0 = hist_hpq0; c.topic_hpq0 = topic_hpq0; c.ctxq0 = ctxq0; c.news_index = news_index; c.news_rows = news_rows;
-    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.st = (hipStream_t)stream;
-    return encoder_fwd_impl(c);
-}
-
-// ---- shared-user runs: the per-row signature of digat_encoder_fwd, the grouped arithmetic of layer 0 --------------------------
-size_t digat_encoder_shared_workspace_bytes(int B, int N, int H, int C, int d, int depth) { (void)depth; return encoder_ws_bytes(B, N, H, C, d, ENC_SHARED); }
-
-int digat_encoder_fwd_shared(const digat_params* p, const float* Xn_in, const uint8_t* An, const uint8_t* Mn, const float* ue,
-                             const uint8_t* Au, const uint8_t* cat_mask, const int64_t* cat_idx, const float* c_n0, float* out_news,
-                             float* out_user, int B, int N, int H, void* workspace, size_t workspace_bytes, void* stream) {
-    EncoderCall c{};
-    c.variant = ENC_SHARED; c.p = p; c.Xn_in = Xn_in; c.An = An; c.Mn = Mn; c.ue = ue; c.Au = Au; c.cat_mask = cat_mask; c.cat_idx = cat_idx;
-    c.c_n0 = c_n0; c.out_news = out_news; c.out_user = out_user; c.B = B; c.N = N; c.H = H;
-    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.st = (hipStream_t)stream;
-    return encoder_fwd_impl(c);
-}
-
-int digat_news_context_queries(const digat_params* p, const float* c_n, float* out, int M, void* stream) {
-    if (!p || !c_n || !out || M < 0) return DIGAT_ERR_ARG;
-    if (!p->user_news_fold_W || !p->userAtt_fold_W) return DIGAT_ERR_ARG;          // folded inference path only
-    const int d = p->d, L = p->depth;
-    if (d <= 0 || d % 4) return DIGAT_ERR_SHAPE;
-    if (M == 0) return DIGAT_OK;
-    const size_t md = (size_t)M * d;
-    // exactly the launch the encoder makes from the batch's c_n0 before layer 0 (rows are independent of the batch they sit in)
-    GemmArgs g = gemm_plain(c_n, d, p->user_news_fold_W, p->user_news_fold_b, out, d, M, d, d, 0);
-    g.w[1] = p->userAtt_fold_W; g.bias[1] = p->userAtt_fold_b; g.y[1] = out + md;
-    g.nsegs = 2;
-    if (L > 0) { g.w[2] = p->user[0].F3; g.bias[2] = p->user[0].b3; g.y[2] = out + 2 * md; g.nsegs = 3; }
-    g.wsplit = (const unsigned short*)p->ctx_wsplit[0];
-    g.format = (p->flags & DIGAT_PARAMS_GEMM_F16X3) ? 1 : 0; g.range_flag = g.format ? (unsigned*)p->range_flag : nullptr;
-    g.m_dispatch = (p->flags & DIGAT_PARAMS_BD_TILED) ? (1 << 30) : 1;      // the kernel the encoder uses for this linear inside a batch: same bits
-    return launch_gemm(g, (hipStream_t)stream);
-}
-
-int digat_user_project0(const digat_params* p, const float* X, float* hpq, int M, void* stream) {
-    if (!p || !X || !hpq || M < 0 || p->depth <= 0) return DIGAT_ERR_ARG;
-    const int d = p->d;
-    if (d <= 0 || d % 4) return DIGAT_ERR_SHAPE;
-    if (M == 0) return DIGAT_OK;
-    const digat_layer_params& lu = p->user[0];
-    const size_t nd = (size_t)M * d;
-    GemmArgs gg = gemm_plain(X, d, lu.W, lu.bW, hpq, d, M, d, d, 0);       // the groups' projection launch of layer 0, row by row
-    gg.w[1] = lu.F1; gg.bias[1] = nullptr; gg.y[1] = hpq + nd;
-    gg.w[2] = lu.F2; gg.bias[2] = nullptr; gg.y[2] = hpq + 2 * nd;
-    gg.nsegs = 3;
-    gg.x3_segs = (p->flags & DIGAT_PROJ_PQ_X3) ? 6 : 0;
-    gg.wsplit = (const unsigned short*)lu.wsplit;
-    gg.format = (p->flags & DIGAT_PARAMS_GEMM_F16X3) ? 1 : 0; gg.range_flag = gg.format ? (unsigned*)p->range_flag : nullptr;
-    if (p->flags & DIGAT_PARAMS_PROJ_F16F8C) gg.format = DIGAT_GEMM_F16F8C;
-    gg.m_dispatch = 1 << 30;                                               // the large-M kernel whatever M is (C topic rows)
-    return launch_gemm(gg, (hipStream_t)stream, DIGAT_KERNEL_PROJ);
-}
-
-int digat_news_project0(const digat_params* p, const float* Xn, float* hpq, int M, int N, void* stream) {
-    if (!p || !Xn || !hpq || M < 0 || N <= 0 || p->depth <= 0) return DIGAT_ERR_ARG;
-    const int d = p->d;
-    if (d <= 0 || d % 4 || (long)M * N > 0x7fffffffL / 4) return DIGAT_ERR_SHAPE;
-    if (M == 0) return DIGAT_OK;
-    const digat_layer_params& ln = p->news[0];
-    const size_t ndn = (size_t)M * N * d;
-    // exactly the launch the encoder makes for layer 0 of the news graph (rows are independent of the batch they sit in)
-    GemmArgs gp = gemm_plain(Xn, d, ln.W, ln.bW, hpq, d, M * N, d, d, 0);
-    gp.w[1] = ln.F1; gp.bias[1] = nullptr; gp.y[1] = hpq + ndn;
-    gp.w[2] = ln.F2; gp.bias[2] = nullptr; gp.y[2] = hpq + 2 * ndn;
-    gp.nsegs = 3;
-    gp.x3_segs = (p->flags & DIGAT_PROJ_PQ_X3) ? 6 : 0;
-    gp.wsplit = (const unsigned short*)ln.wsplit;
-    gp.format = (p->flags & DIGAT_PARAMS_GEMM_F16X3) ? 1 : 0; gp.range_flag = gp.format ? (unsigned*)p->range_flag : nullptr;
-    if (p->flags & DIGAT_PARAMS_PROJ_F16F8C) gp.format = DIGAT_GEMM_F16F8C;
-    gp.m_dispatch = 1 << 30;
-    return launch_gemm(gp, (hipStream_t)stream, DIGAT_KERNEL_PROJ);
-}
+#include "digat_encoder.inc"
 
 static double g_prof_last_live_fraction = -1.0;
 double digat_profile_live_row_fraction(void) { return g_prof_last_live_fraction; }

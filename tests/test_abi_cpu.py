@@ -165,7 +165,7 @@ def test_no_environment_switch_and_no_mutable_mode_in_the_product_library():
     L = _lib.lib()
     for setter in ("digat_set_side_stream", "digat_set_live_row_skipping", "digat_set_staged_xattn", "digat_set_gemm_format"):
         assert not hasattr(L, setter), setter
-    text = open(os.path.join(REPO, "digat_amd", "csrc", "digat_kernels.hip")).read()
+    text = "".join(open(os.path.join(REPO, "digat_amd", "csrc", f)).read() for f in ("digat_kernels.hip", "digat_encoder.inc"))
     assert "g_live_rows_on" not in text and "g_side_stream_on" not in text
     for d in (os.path.join(REPO, "digat_amd", "csrc"), os.path.join(REPO, "include")):
         for f in os.listdir(d):
