@@ -40,6 +40,16 @@ class MsaParams(C.Structure):
                                              "qkv_wsplit", "a1_wsplit")])
 
 
+class MhsaParams(C.Structure):
+    """digat_mhsa_params (include/digat_hip.h)."""
+    _fields_ = ([(k, C.c_int32) for k in ("in_dim", "head_num", "head_dim", "attention_dim")]
+                + [(k, C.c_void_p) for k in ("table", "W_Q", "b_Q", "W_K", "W_V", "b_V", "A1", "b1", "a2", "qkv_wsplit", "a1_wsplit")]
+                + [("flags", C.c_int32), ("reserved", C.c_int32)])
+
+
+MHSA_POOL_UNMASKED = 1                  # digat_mhsa_params.flags: the pooling softmax is unmasked (the NRMS user encoder)
+
+
 class CnnParams(C.Structure):
     """digat_cnn_params (include/digat_hip.h)."""
     _fields_ = ([(k, C.c_int32) for k in ("word_embedding_dim", "kernel_num", "taps", "attention_dim")]
@@ -119,6 +129,16 @@ _SIGNATURES = {
     "digat_msa_bwd": (C.c_int, [C.POINTER(MsaParams), _f, _f, _f, C.c_float, _f, C.c_size_t, _f, C.c_int64] + [_f] * 8
                       + [C.c_int, C.c_int, _f, C.c_size_t, _f]),
     "digat_msa_row_grad_ld": (C.c_int64, [C.c_int] * 3),
+    "digat_mhsa_workspace_bytes": (C.c_size_t, [C.c_int] * 6),
+    "digat_mhsa_fwd": (C.c_int, [C.POINTER(MhsaParams), _f, _f, _f, C.c_int, C.c_int, _f, C.c_size_t, _f]),
+    "digat_mhsa_train_save_bytes": (C.c_size_t, [C.c_int] * 6),
+    "digat_mhsa_train_workspace_bytes": (C.c_size_t, [C.c_int] * 6),
+    "digat_mhsa_fwd_train": (C.c_int, [C.POINTER(MhsaParams), _f, _f, _f, C.c_float, C.c_float, C.c_uint32, C.c_int, C.c_int, _f, C.c_size_t, _f,
+                                       C.c_size_t, _f]),
+    "digat_mhsa_bwd": (C.c_int, [C.POINTER(MhsaParams), _f, _f, _f, C.c_float, C.c_float, C.c_uint32, _f, C.c_size_t, _f, C.c_int64] + [_f] * 8
+                       + [C.c_int, C.c_int, _f, C.c_size_t, _f]),
+    "digat_mhsa_attention_fwd": (C.c_int, [_f, _f, _f, C.c_float, C.c_uint32] + [C.c_int] * 4 + [_f]),
+    "digat_mhsa_attention_bwd": (C.c_int, [_f, _f, _f, _f, C.c_float, C.c_uint32] + [C.c_int] * 4 + [_f]),
     "digat_cnn_split_bytes": (C.c_size_t, [C.c_int] * 3),
     "digat_split_cnn_weights": (C.c_int, [_f] + [C.c_int] * 3 + [_f, _f]),
     "digat_cnn_merge_group3": (C.c_int, [_f] * 6 + [C.c_int] * 2 + [_f] * 3),

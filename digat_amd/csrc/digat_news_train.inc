@@ -563,6 +563,55 @@ static size_t msa_train_carve(Arena& w, int T, int Lw, int dm, int hd, int att, 
     o->db3g = w.take<float>(3 * (size_t)hd);
     return w.used;
 }
+// ---- the projections' backward, shared by digat_msa_bwd and digat_mhsa_bwd (digat_mhsa.inc) --------------------------------------
+// row_grad = (dQ W_Q + dK W_K + dV W_V) under the input dropout's keep bytes: w.dqkv [M, 3 hd] -> row_grad [M, dm], rows ld_row_grad apart
+static int qkv_input_grad(const float* W_Q, const float* W_K, const float* W_V, const MsaTrainWs& w, const uint8_t* dmask, float p_drop,
+                          float* row_grad, int64_t ld_row_grad, long M, int dm, int hd, hipStream_t st) {
+    const int dmp = (int)msa_attp(dm);
+    // projections: dEd = dQ W_Q + dK W_K + dV W_V; dW_* = d*^T Ed; db_Q, db_V = column sums
+    if (M >= 2048 && (3 * hd) % 8 == 0 && ld_row_grad == dmp) {
+        // one bf16x6 product over the stacked weights [W_Q; W_K; W_V] ([3 hd, dm], used as its transpose), split from their three
+        // homes; the output's 80-column strips run over dm rounded up (zero weight rows): row_grad's rows are ld_row_grad = dmp
+        // floats apart
+        T_TRY(launch_split(W_Q, W_K, W_V, dm, 1, 3 * hd, w.wcat_img, st, 2));
+        GemmArgs gx = gemm_plain(w.dqkv, 3 * hd, W_Q, nullptr, row_grad, ld_row_grad, (int)M, dm, 3 * hd, 0);
+        gx.nseg = dmp; gx.wsplit = (const unsigned short*)w.wcat_img;
+        if (g_train_bf16) gx.x1_segs = 7;
+        if (!gemm_takes_row_list(gx)) return DIGAT_ERR_SHAPE;
+        const bool mask_here = p_drop > 0.f && dm % 4 == 0;          // the embedding dropout's backward in this product's epilogue
+        if (mask_here) { gx.dmask = dmask; gx.lddm = dm; gx.dscale = 1.f / (1.f - p_drop); gx.dmask_cols = dm; }
+        T_TRY(launch_gemm(gx, st, DIGAT_KERNEL_LINEAR));
+        if (mask_here) p_drop = 0.f;                                  // (the launch below is not needed)
+    } else {
+        T_TRY(digat_linear_bwd_input(w.dqkv, 3 * hd, W_Q, row_grad, ld_row_grad, (int)M, hd, dm, 0, st));
+        T_TRY(digat_linear_bwd_input(w.dqkv + hd, 3 * hd, W_K, row_grad, ld_row_grad, (int)M, hd, dm, 1, st));
+        T_TRY(digat_linear_bwd_input(w.dqkv + 2 * hd, 3 * hd, W_V, row_grad, ld_row_grad, (int)M, hd, dm, 1, st));
+    }
+    if (p_drop > 0.f) {
+        MsaRowDropArgs a{row_grad, ld_row_grad, dmask, M, dm, 1.f / (1.f - p_drop)};
+        hipLaunchKernelGGL(msa_row_dropout_bwd_kernel, dim3(grid_for(M * dm)), dim3(256), 0, st, a);
+        DIGAT_CHECK_LAUNCH();
+    }
+    return DIGAT_OK;
+}
+// dW_Q, dW_K, dW_V [hd, dm] and db_Q, db_V [hd] from w.dqkv and the projections' input rows Xd [M, dm]
+static int qkv_weight_grad(const MsaTrainWs& w, const float* Xd, float* dW_Q, float* db_Q, float* dW_K, float* dW_V, float* db_V, long M, int dm,
+                           int hd, hipStream_t st) {
+    const size_t wn = (size_t)hd * dm, hn = hd;
+    {   // the three weight gradients as one product dQKV^T Ed ([3 hd, dm]); db_Q / db_V are the column sums of its outer blocks
+        // a caller that hands over dW_Q, dW_K, dW_V as the three blocks of ONE [3 hd, dm] buffer (newsEncoders.MsaFused does) gets the
+        // product written in place
+        const bool stacked = dW_K == dW_Q + wn && dW_V == dW_Q + 2 * wn;
+        T_TRY(digat_linear_bwd_weight(w.dqkv, 3 * hd, Xd, dm, stacked ? dW_Q : w.wg3, w.db3g, (int)M, 3 * hd, dm, 0, w.wg, w.wgb, st));
+        if (!stacked && (hipMemcpyAsync(dW_Q, w.wg3, wn * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+                         hipMemcpyAsync(dW_K, w.wg3 + wn, wn * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+                         hipMemcpyAsync(dW_V, w.wg3 + 2 * wn, wn * 4, hipMemcpyDeviceToDevice, st) != hipSuccess)) return DIGAT_ERR_LAUNCH;
+        if (hipMemcpyAsync(db_Q, w.db3g, hn * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+            hipMemcpyAsync(db_V, w.db3g + 2 * hd, hn * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return DIGAT_ERR_LAUNCH;
+    }
+    return DIGAT_OK;
+}
+
 static int msa_shape_ok(const digat_msa_params* p, int Lw) {
     const int dm = p->word_embedding_dim, heads = p->head_num, dk = p->head_dim, att = p->attention_dim;
     return dm > 0 && dm % 4 == 0 && heads > 0 && dk > 0 && dk <= MSA_MAX_DK && att > 0 && att % 4 == 0 && (heads * dk) % 4 == 0 && Lw <= 32;
@@ -656,42 +705,8 @@ int digat_msa_bwd(const digat_msa_params* p, const int32_t* title_text, const ui
         hipLaunchKernelGGL(msa_attention_bwd_kernel, dim3(T), dim3(128), lds, st, a);
         DIGAT_CHECK_LAUNCH();
     }
-    // projections: dEd = dQ W_Q + dK W_K + dV W_V; dW_* = d*^T Ed; db_Q, db_V = column sums
-    if (M >= 2048 && (3 * hd) % 8 == 0 && ld_row_grad == dmp) {
-        // one bf16x6 product over the stacked weights [W_Q; W_K; W_V] ([3 hd, dm], used as its transpose), split from their three
-        // homes; the output's 80-column strips run over dm rounded up (zero weight rows): row_grad's rows are ld_row_grad = dmp
-        // floats apart
-        T_TRY(launch_split(p->W_Q, p->W_K, p->W_V, dm, 1, 3 * hd, o.wcat_img, st, 2));
-        GemmArgs gx = gemm_plain(o.dqkv, 3 * hd, p->W_Q, nullptr, row_grad, ld_row_grad, (int)M, dm, 3 * hd, 0);
-        gx.nseg = dmp; gx.wsplit = (const unsigned short*)o.wcat_img;
-        if (g_train_bf16) gx.x1_segs = 7;
-        if (!gemm_takes_row_list(gx)) return DIGAT_ERR_SHAPE;
-        const bool mask_here = p_drop > 0.f && dm % 4 == 0;          // the embedding dropout's backward in this product's epilogue
-        if (mask_here) { gx.dmask = s.dmask; gx.lddm = dm; gx.dscale = 1.f / (1.f - p_drop); gx.dmask_cols = dm; }
-        T_TRY(launch_gemm(gx, st, DIGAT_KERNEL_LINEAR));
-        if (mask_here) p_drop = 0.f;                                  // (the launch below is not needed)
-    } else {
-        T_TRY(digat_linear_bwd_input(o.dqkv, 3 * hd, p->W_Q, row_grad, ld_row_grad, (int)M, hd, dm, 0, st));
-        T_TRY(digat_linear_bwd_input(o.dqkv + hd, 3 * hd, p->W_K, row_grad, ld_row_grad, (int)M, hd, dm, 1, st));
-        T_TRY(digat_linear_bwd_input(o.dqkv + 2 * hd, 3 * hd, p->W_V, row_grad, ld_row_grad, (int)M, hd, dm, 1, st));
-    }
-    {   // the three weight gradients as one product dQKV^T Ed ([3 hd, dm]); db_Q / db_V are the column sums of its outer blocks
-        // a caller that hands over dW_Q, dW_K, dW_V as the three blocks of ONE [3 hd, dm] buffer (newsEncoders.MsaFused does) gets the
-        // product written in place
-        const bool stacked = dW_K == dW_Q + wn && dW_V == dW_Q + 2 * wn;
-        T_TRY(digat_linear_bwd_weight(o.dqkv, 3 * hd, s.Ed, dm, stacked ? dW_Q : o.wg3, o.db3g, (int)M, 3 * hd, dm, 0, o.wg, o.wgb, st));
-        if (!stacked && (hipMemcpyAsync(dW_Q, o.wg3, wn * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-                         hipMemcpyAsync(dW_K, o.wg3 + wn, wn * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-                         hipMemcpyAsync(dW_V, o.wg3 + 2 * wn, wn * 4, hipMemcpyDeviceToDevice, st) != hipSuccess)) return DIGAT_ERR_LAUNCH;
-        if (hipMemcpyAsync(db_Q, o.db3g, hn * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-            hipMemcpyAsync(db_V, o.db3g + 2 * hd, hn * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return DIGAT_ERR_LAUNCH;
-    }
-    if (p_drop > 0.f) {
-        MsaRowDropArgs a{row_grad, ld_row_grad, s.dmask, M, dm, 1.f / (1.f - p_drop)};
-        hipLaunchKernelGGL(msa_row_dropout_bwd_kernel, dim3(grid_for(M * dm)), dim3(256), 0, st, a);
-        DIGAT_CHECK_LAUNCH();
-    }
-    return DIGAT_OK;
+    T_TRY(qkv_input_grad(p->W_Q, p->W_K, p->W_V, o, s.dmask, p_drop, row_grad, ld_row_grad, M, dm, hd, st));
+    return qkv_weight_grad(o, s.Ed, dW_Q, db_Q, dW_K, dW_V, db_V, M, dm, hd, st);
 }
 
 }  // extern "C"

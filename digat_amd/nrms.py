@@ -1,0 +1,486 @@
+"""The NRMS and NRMS-SA baselines of the reference's second experiment (``Appendix-B/``) on the HIP kernels.
+
+``NRMS_NewsEncoder``, ``SA_NRMS_NewsEncoder``, ``NRMS_UserEncoder`` and ``Model`` keep the reference's constructor arguments, method
+signatures and ``state_dict`` keys (Appendix-B newsEncoders.py, userEncoders.py, model.py).  The word-embedding pickle is not
+required: the table keeps its init, as in ``newsEncoders.py`` here.
+
+On the GPU an encoder is one library call: ``digat_mhsa_fwd`` in inference, ``digat_mhsa_fwd_train`` / ``digat_mhsa_bwd`` under
+autograd (``MhsaFused``) — the stacked Q|K|V projection, the key-masked attention (csrc/digat_mhsa.inc), the additive pooling.  The
+news encoder hands over token ids and the word embedding, the user encoder dense rows (training) or news ids and the cached news
+representations (dev scoring).  The SA gate is the news-graph context call ``digat_news_ctx_*`` on ``[orig ; aug]`` with node 0
+masked out: it takes its query from node 0, attends over the unmasked nodes, gates and mixes (Appendix-B newsEncoders.py:100-102).
+Every class has a ``forward_stock`` on stock PyTorch: the CPU path and the yardstick.  There is no fall-back on the GPU: a shape the
+library refuses raises.
+"""
+from __future__ import annotations
+
+import math
+from types import SimpleNamespace
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _lib
+from .layers import ScaledDotProductAttention
+from .newsEncoders import Attention, _embedding_grad
+from .training import NewsCtxFused, RowLogits, _seed
+
+
+class MultiHeadAttention(nn.Module):
+    """Appendix-B layers.py:50-95: no output projection, K without bias, -1e9 over masked keys after the scale."""
+
+    def __init__(self, h: int, d_model: int, len_q: int, len_k: int, d_k: int, d_v: int):
+        super().__init__()
+        self.h, self.d_model, self.len_q, self.len_k, self.d_k, self.d_v = h, d_model, len_q, len_k, d_k, d_v
+        self.out_dim = h * d_v
+        self.attention_scalar = math.sqrt(float(d_k))
+        self.W_K = nn.Linear(d_model, h * d_k, bias=False)
+        self.W_Q = nn.Linear(d_model, h * d_k, bias=True)
+        self.W_V = nn.Linear(d_model, h * d_v, bias=True)
+
+    def initialize(self):
+        nn.init.xavier_uniform_(self.W_K.weight)
+        nn.init.xavier_uniform_(self.W_Q.weight)
+        nn.init.zeros_(self.W_Q.bias)
+        nn.init.xavier_uniform_(self.W_V.weight)
+        nn.init.zeros_(self.W_V.bias)
+
+    def forward(self, Q, K, V, mask=None):
+        B, Lq, Lk = Q.shape[0], Q.shape[1], K.shape[1]
+        q = self.W_Q(Q).view(B, Lq, self.h, self.d_k).transpose(1, 2)
+        k = self.W_K(K).view(B, Lk, self.h, self.d_k).transpose(1, 2)
+        v = self.W_V(V).view(B, Lk, self.h, self.d_v).transpose(1, 2)
+        a = q @ k.transpose(2, 3) / self.attention_scalar
+        if mask is not None:
+            a = a.masked_fill(mask.view(B, 1, 1, Lk) == 0, -1e9)
+        return (F.softmax(a, dim=3) @ v).transpose(1, 2).reshape(B, Lq, self.out_dim)
+
+
+def _stock_sdpa(att: ScaledDotProductAttention, feature, query):
+    """Appendix-B layers.py:206-213 without a mask (the parameter container's own forward raises: the product path is the kernels')."""
+    a = (att.K(feature) @ att.Q(query).unsqueeze(2)).squeeze(2) / att.attention_scalar
+    return (F.softmax(a, dim=1).unsqueeze(1) @ feature).squeeze(1)
+
+
+# ---- the library calls -------------------------------------------------------------------------------------------------------
+def _mhsa_params(table, WQ, bQ, WK, WV, bV, A1, b1, a2, heads, dk, flags):
+    P = _lib.MhsaParams(in_dim=WQ.shape[1], head_num=heads, head_dim=dk, attention_dim=A1.shape[0], flags=flags)
+    for name, w in zip(("table", "W_Q", "b_Q", "W_K", "W_V", "b_V", "A1", "b1", "a2"), (table, WQ, bQ, WK, WV, bV, A1, b1, a2)):
+        setattr(P, name, w.data_ptr())
+    return P
+
+
+def _weights(mha: MultiHeadAttention, att: Attention):
+    return [mha.W_Q.weight, mha.W_Q.bias, mha.W_K.weight, mha.W_V.weight, mha.W_V.bias, att.affine1.weight, att.affine1.bias,
+            att.affine2.weight]
+
+
+class _InferenceBlock:
+    """The parameter block of one encoder for inference, with the split images of the bf16x6 matrix-core GEMM path when
+    ``hd % 80 == 0`` (else the fp32 path, as ``MSA._build_hip_params`` decides); rebuilt when a parameter has moved or been written."""
+
+    def __init__(self, mha, att, flags):
+        self.mha, self.att, self.flags, self.key, self.P, self.keep = mha, att, flags, None, None, None
+
+    def params(self, table):
+        ws = _weights(self.mha, self.att)
+        key = tuple((w.data_ptr(), w._version) for w in ws)
+        if key != self.key:
+            L = _lib.lib()
+            keep = [w.detach().float().contiguous() for w in ws]
+            mha = self.mha
+            dm, hd, natt, dev = mha.d_model, mha.h * mha.d_k, keep[5].shape[0], keep[0].device
+            P = _mhsa_params(keep[0], *keep, mha.h, mha.d_k, self.flags)
+            if hd % 80 == 0 and dm % 4 == 0 and dm >= 32:
+                qkv = _lib.split_buffer(L.digat_msa_split_bytes(dm, mha.h, mha.d_k), dev)
+                _lib.check(L.digat_split_msa_weights(keep[0].data_ptr(), keep[2].data_ptr(), keep[3].data_ptr(), dm, hd, qkv.data_ptr(),
+                                                     _lib.stream_ptr()), "digat_split_msa_weights")
+                a1 = _lib.split_buffer(L.digat_split_weights_bytes(natt, hd), dev)
+                _lib.check(L.digat_split_weights(keep[5].data_ptr(), natt, hd, a1.data_ptr(), _lib.GEMM_BF16X6, _lib.stream_ptr()),
+                           "digat_split_weights")
+                P.qkv_wsplit, P.a1_wsplit = qkv.data_ptr(), a1.data_ptr()
+                keep += [qkv, a1]
+            self.key, self.P, self.keep = key, P, keep
+        self.P.table = table.data_ptr()
+        return self.P
+
+
+def mhsa_infer(block: _InferenceBlock, table, ids, mask):
+    """``digat_mhsa_fwd``: table [V, in_dim] with ids [T, L] (any integer dtype), or ids None and table = dense rows [T L, in_dim];
+    mask [T, L] -> [T, hd]."""
+    L = _lib.lib()
+    table = table.detach().float().contiguous()
+    msk = (mask != 0).to(torch.uint8).contiguous()
+    T, Ls = msk.shape
+    idx = ids.reshape(T, Ls).to(torch.int32).contiguous() if ids is not None else None
+    dev = _lib.require_device(table, msk)
+    P = block.params(table)
+    out = torch.empty((T, P.head_num * P.head_dim), dtype=torch.float32, device=dev)
+    if T:
+        dims = (T, Ls, P.in_dim, P.head_num, P.head_dim, P.attention_dim)
+        nb = L.digat_mhsa_workspace_bytes(*dims)
+        ws = _lib.workspace(nb, dev, "mhsa")
+        _lib.check(L.digat_mhsa_fwd(P, _lib.ptr(idx), msk.data_ptr(), out.data_ptr(), T, Ls, ws.data_ptr(), nb, _lib.stream_ptr()),
+                   "digat_mhsa_fwd")
+    return out
+
+
+class MhsaFused(torch.autograd.Function):
+    """One encoder as one library call per direction (``digat_mhsa_fwd_train`` / ``digat_mhsa_bwd``).  ``ids`` int32 [T, L] with
+    ``table`` [V, in_dim] (its gradient: ``digat_embedding_bwd``), or ``ids`` None with ``table`` = dense rows [T L, in_dim] (its
+    gradient: the rows the library writes)."""
+
+    @staticmethod
+    def forward(ctx, ids, mask, table, WQ, bQ, WK, WV, bV, A1, b1, a2, heads, dk, p_in, p_ctx, flags):
+        L = _lib.lib()
+        ws_ = [w.detach().float().contiguous() for w in (table, WQ, bQ, WK, WV, bV, A1, b1, a2)]
+        dev = _lib.require_device(mask, *ws_)
+        T, Ls = mask.shape
+        dims = (T, Ls, ws_[1].shape[1], heads, dk, ws_[6].shape[0])
+        P = _mhsa_params(*ws_, heads, dk, flags)
+        out = torch.empty((T, heads * dk), dtype=torch.float32, device=dev)
+        nsave, nws = L.digat_mhsa_train_save_bytes(*dims), L.digat_mhsa_train_workspace_bytes(*dims)
+        save, ws = _lib.save_buffer(nsave, dev), _lib.workspace(nws, dev, "mhsa_train")
+        p_in, p_ctx = float(p_in), float(p_ctx)
+        seed = _seed() if (p_in > 0 or p_ctx > 0) else 0
+        if T:
+            _lib.check(L.digat_mhsa_fwd_train(P, _lib.ptr(ids), mask.data_ptr(), out.data_ptr(), p_in, p_ctx, seed, T, Ls, save.data_ptr(),
+                                              nsave, ws.data_ptr(), nws, _lib.stream_ptr()), "digat_mhsa_fwd_train")
+        ctx.save_for_backward(mask, save, *ws_)
+        ctx.ids, ctx.dims, ctx.p, ctx.seed, ctx.sizes, ctx.flags = ids, (heads, dk), (p_in, p_ctx), seed, (nsave, nws), flags
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        L = _lib.lib()
+        mask, save, *ws_ = ctx.saved_tensors
+        table, WQ, bQ, WK, WV, bV, A1, b1, a2 = ws_
+        ids = ctx.ids
+        heads, dk = ctx.dims
+        T, Ls = mask.shape
+        dm, hd, att = WQ.shape[1], heads * dk, A1.shape[0]
+        dev = mask.device
+        if T == 0:                                # no sequence: every gradient is zero
+            z = [torch.zeros_like(w) for w in ws_]
+            return (None, None, z[0] if ctx.needs_input_grad[2] else None, *z[1:], None, None, None, None, None)
+        dout = dout.float().contiguous()
+        P = _mhsa_params(*ws_, heads, dk, ctx.flags)
+        nsave, nws = ctx.sizes
+        ws = _lib.workspace(nws, dev, "mhsa_train")
+        f = dict(dtype=torch.float32, device=dev)
+        ld = int(L.digat_msa_row_grad_ld(T, Ls, dm))
+        row_grad = torch.empty((T * Ls, ld), **f)
+        dW3 = torch.empty((3, hd, dm), **f)       # one buffer: the library writes its single [3 hd, dm] weight-gradient product in place
+        dWQ, dWK, dWV = dW3[0], dW3[1], dW3[2]
+        dbQ, dbV = torch.empty(hd, **f), torch.empty(hd, **f)
+        dA1, db1, da2 = torch.empty((att, hd), **f), torch.empty(att, **f), torch.empty(att, **f)
+        _lib.check(L.digat_mhsa_bwd(P, _lib.ptr(ids), mask.data_ptr(), dout.data_ptr(), ctx.p[0], ctx.p[1], ctx.seed, save.data_ptr(), nsave,
+                                    row_grad.data_ptr(), ld, dWQ.data_ptr(), dbQ.data_ptr(), dWK.data_ptr(), dWV.data_ptr(), dbV.data_ptr(),
+                                    dA1.data_ptr(), db1.data_ptr(), da2.data_ptr(), T, Ls, ws.data_ptr(), nws, _lib.stream_ptr()),
+                   "digat_mhsa_bwd")
+        dtable = None
+        if ctx.needs_input_grad[2]:
+            dtable = _embedding_grad(ids, row_grad, ld, table) if ids is not None else row_grad[:, :dm].reshape(table.shape)
+        return None, None, dtable, dWQ, dbQ, dWK, dWV, dbV, dA1, db1, da2.view_as(a2), None, None, None, None, None
+
+
+def _sa_gate_hip(orig, aug, sa_attention, sa_transformation, p_gate):
+    """Appendix-B newsEncoders.py:100-102 as the news-graph context call: nodes [orig ; aug] with node 0 masked out of the attention."""
+    T, A, hd = aug.shape
+    X = torch.cat([orig.unsqueeze(1), aug], dim=1).contiguous()
+    mask = torch.ones((T, 1 + A), dtype=torch.uint8, device=X.device)
+    mask[:, 0] = 0
+    Kc, Qc, bQc = sa_attention.K.weight, sa_attention.Q.weight, sa_attention.Q.bias
+    Wg, bg = sa_transformation.weight, sa_transformation.bias
+    if torch.is_grad_enabled():
+        return NewsCtxFused.apply(X, mask, Kc, Qc, bQc, Wg, bg, p_gate)
+    L = _lib.lib()
+    ws_ = [w.detach().float().contiguous() for w in (Kc, Qc, bQc, Wg, bg)]
+    out = torch.empty((T, hd), dtype=torch.float32, device=X.device)
+    nb = L.digat_news_ctx_workspace_bytes(T, 1 + A, hd)
+    ws = _lib.workspace(nb, X.device, "nrms_sa")
+    _lib.check(L.digat_news_ctx_fwd(X.data_ptr(), mask.data_ptr(), *(w.data_ptr() for w in ws_), None, out.data_ptr(), T, 1 + A, hd,
+                                    ws.data_ptr(), nb, _lib.stream_ptr()), "digat_news_ctx_fwd")
+    return out
+
+
+# ---- the reference's classes ---------------------------------------------------------------------------------------------------
+class NewsEncoder(nn.Module):
+    """Appendix-B newsEncoders.py:8-31 without the pickle."""
+
+    def __init__(self, config):
+        super().__init__()
+        self.max_sentence_length = config.max_title_length
+        self.word_embedding_dim = config.word_embedding_dim
+        self.word_embedding = nn.Embedding(config.vocabulary_size, self.word_embedding_dim)
+        self.dropout = nn.Dropout(p=config.dropout_rate)
+        self.dropout_ = nn.Dropout(p=config.dropout_rate / 2)
+        self.augmented_news_num = config.augmented_news_num
+
+    def initialize(self):
+        pass
+
+
+class NRMS_NewsEncoder(NewsEncoder):
+    """Appendix-B newsEncoders.py:34-58."""
+
+    def __init__(self, config):
+        super().__init__(config)
+        self.news_embedding_dim = config.head_num * config.head_dim
+        self.multiheadAttention = MultiHeadAttention(config.head_num, config.word_embedding_dim, config.max_title_length,
+                                                     config.max_title_length, config.head_dim, config.head_dim)
+        self.attention = Attention(self.news_embedding_dim, config.attention_dim)
+
+    def initialize(self):
+        super().initialize()
+        self.multiheadAttention.initialize()
+        self.attention.initialize()
+
+    def _block(self):
+        if getattr(self, "_hip_block", None) is None:
+            self._hip_block = _InferenceBlock(self.multiheadAttention, self.attention, 0)
+        return self._hip_block
+
+    def encode_titles(self, text, mask):
+        """text / mask [T, Lw] -> [T, news_embedding_dim]: the HIP encoder on the GPU, the stock modules on the CPU."""
+        if not text.is_cuda:
+            return self._titles_stock(text, mask)
+        if not torch.is_grad_enabled() and (not self.training or self.dropout.p == 0):
+            return mhsa_infer(self._block(), self.word_embedding.weight, text, mask)
+        mha = self.multiheadAttention
+        p = float(self.dropout.p) if self.training else 0.0
+        return MhsaFused.apply(text.to(torch.int32).contiguous(), (mask != 0).to(torch.uint8).contiguous(), self.word_embedding.weight,
+                               *_weights(mha, self.attention), mha.h, mha.d_k, p, p, 0)
+
+    def _titles_stock(self, text, mask):
+        w = self.dropout(self.word_embedding(text.long()))
+        c = self.dropout(self.multiheadAttention(w, w, w, mask))
+        return self.attention(c, mask=mask)
+
+    def forward(self, title_text, title_mask, augmented_news_title_text=None, augmented_news_title_mask=None):
+        B, n = title_text.shape[:2]
+        L = self.max_sentence_length
+        return self.encode_titles(title_text.reshape(B * n, L), title_mask.reshape(B * n, L)).view(B, n, self.news_embedding_dim)
+
+    def forward_stock(self, title_text, title_mask, augmented_news_title_text=None, augmented_news_title_mask=None):
+        B, n = title_text.shape[:2]
+        L = self.max_sentence_length
+        return self._titles_stock(title_text.reshape(B * n, L), title_mask.reshape(B * n, L)).view(B, n, self.news_embedding_dim)
+
+
+class SA_NRMS_NewsEncoder(NRMS_NewsEncoder):
+    """Appendix-B newsEncoders.py:61-103: the same encoder over the augmented titles, attention of the original over them, a gate."""
+
+    def __init__(self, config):
+        super().__init__(config)
+        d = self.news_embedding_dim
+        self.SA_attention = ScaledDotProductAttention(d, d, d)
+        self.SA_transformation = nn.Linear(2 * d, d, bias=True)
+
+    def initialize(self):
+        super().initialize()
+        self.SA_attention.initialize()
+        nn.init.xavier_uniform_(self.SA_transformation.weight)
+        nn.init.zeros_(self.SA_transformation.bias)
+
+    def sa_gate(self, orig, aug):
+        """orig [T, hd], aug [T, A, hd] -> [T, hd] (newsEncoders.py:100-102)."""
+        if orig.is_cuda:
+            return _sa_gate_hip(orig, aug, self.SA_attention, self.SA_transformation, float(self.dropout_.p) if self.training else 0.0)
+        return self.sa_gate_stock(orig, aug)
+
+    def sa_gate_stock(self, orig, aug):
+        g = _stock_sdpa(self.SA_attention, aug, orig)
+        gate = torch.sigmoid(self.dropout_(self.SA_transformation(torch.cat([orig, g], dim=1))))
+        return gate * orig + (1 - gate) * g
+
+    def _forward(self, titles, gate, title_text, title_mask, aug_text, aug_mask):
+        B, n = title_text.shape[:2]
+        L, A, d = self.max_sentence_length, self.augmented_news_num, self.news_embedding_dim
+        orig = titles(title_text.reshape(B * n, L), title_mask.reshape(B * n, L))
+        if aug_text is not None:
+            aug = titles(aug_text.reshape(B * n * A, L), aug_mask.reshape(B * n * A, L)).view(B * n, A, d)
+            orig = gate(orig, aug)
+        return orig.view(B, n, d)
+
+    def forward(self, title_text, title_mask, augmented_news_title_text=None, augmented_news_title_mask=None):
+        return self._forward(self.encode_titles, self.sa_gate, title_text, title_mask, augmented_news_title_text, augmented_news_title_mask)
+
+    def forward_stock(self, title_text, title_mask, augmented_news_title_text=None, augmented_news_title_mask=None):
+        return self._forward(self._titles_stock, self.sa_gate_stock, title_text, title_mask, augmented_news_title_text,
+                             augmented_news_title_mask)
+
+
+class UserEncoder(nn.Module):
+    """Appendix-B userEncoders.py:8-31."""
+
+    def __init__(self, news_encoder, config):
+        super().__init__()
+        self.news_embedding_dim = news_encoder.news_embedding_dim
+        self.news_encoder = news_encoder
+        self.max_history_num = config.max_history_num
+
+
+class NRMS_UserEncoder(UserEncoder):
+    """Appendix-B userEncoders.py:34-52: the history mask is the key mask, the pooling is unmasked."""
+
+    def __init__(self, news_encoder, config):
+        super().__init__(news_encoder, config)
+        self.multiheadAttention = MultiHeadAttention(config.head_num, self.news_embedding_dim, config.max_history_num,
+                                                     config.max_history_num, config.head_dim, config.head_dim)
+        self.attention = Attention(self.news_embedding_dim, config.attention_dim)
+
+    def initialize(self):
+        self.multiheadAttention.initialize()
+        self.attention.initialize()
+
+    def _block(self):
+        if getattr(self, "_hip_block", None) is None:
+            self._hip_block = _InferenceBlock(self.multiheadAttention, self.attention, _lib.MHSA_POOL_UNMASKED)
+        return self._hip_block
+
+    def encode(self, history_embedding, user_history_mask):
+        if not history_embedding.is_cuda:
+            return self.encode_stock(history_embedding, user_history_mask)
+        B, H, d = history_embedding.shape
+        if not torch.is_grad_enabled():
+            return mhsa_infer(self._block(), history_embedding.reshape(B * H, d), None, user_history_mask)
+        mha = self.multiheadAttention
+        return MhsaFused.apply(None, (user_history_mask != 0).to(torch.uint8).contiguous(), history_embedding.reshape(B * H, d),
+                               *_weights(mha, self.attention), mha.h, mha.d_k, 0.0, 0.0, _lib.MHSA_POOL_UNMASKED)
+
+    def encode_cached(self, news_embeddings, history_ids, user_history_mask):
+        """Dev scoring: the histories are rows of the cached news representations, looked up by id inside the library."""
+        if not news_embeddings.is_cuda:
+            return self.encode_stock(news_embeddings[history_ids.long()], user_history_mask)
+        return mhsa_infer(self._block(), news_embeddings, history_ids, user_history_mask)
+
+    def encode_stock(self, history_embedding, user_history_mask):
+        h = self.multiheadAttention(history_embedding, history_embedding, history_embedding, user_history_mask)
+        return self.attention(h)
+
+    def forward(self, user_title_text, user_title_mask, user_history_mask):
+        return self.encode(self.news_encoder(user_title_text, user_title_mask), user_history_mask)
+
+    def forward_stock(self, user_title_text, user_title_mask, user_history_mask):
+        return self.encode_stock(self.news_encoder.forward_stock(user_title_text, user_title_mask), user_history_mask)
+
+
+class Model(nn.Module):
+    """Appendix-B model.py: the logit is <user, news>."""
+
+    def __init__(self, config):
+        super().__init__()
+        if config.model == 'NRMS':
+            self.news_encoder = NRMS_NewsEncoder(config)
+        elif config.model == 'NRMS-SA':
+            self.news_encoder = SA_NRMS_NewsEncoder(config)
+        else:
+            raise Exception(config.model + ' is not implemented')
+        self.user_encoder = NRMS_UserEncoder(self.news_encoder, config)
+        self.model_name = config.model
+        self.news_embedding_dim = self.news_encoder.news_embedding_dim
+
+    def initialize(self):
+        self.news_encoder.initialize()
+        self.user_encoder.initialize()
+
+    def forward(self, user_title_text, user_title_mask, user_history_mask, news_title_text, news_title_mask,
+                augmented_news_title_text=None, augmented_news_title_mask=None):
+        if not news_title_text.is_cuda:
+            return self.forward_stock(user_title_text, user_title_mask, user_history_mask, news_title_text, news_title_mask,
+                                      augmented_news_title_text, augmented_news_title_mask)
+        B, K = news_title_text.shape[:2]
+        news = self.news_encoder(news_title_text, news_title_mask, augmented_news_title_text, augmented_news_title_mask)
+        user = self.user_encoder(user_title_text, user_title_mask, user_history_mask)
+        return row_logits(news.reshape(B * K, -1), user.unsqueeze(1).expand(B, K, -1).reshape(B * K, -1)).view(B, K)
+
+    def forward_stock(self, user_title_text, user_title_mask, user_history_mask, news_title_text, news_title_mask,
+                      augmented_news_title_text=None, augmented_news_title_mask=None):
+        news = self.news_encoder.forward_stock(news_title_text, news_title_mask, augmented_news_title_text, augmented_news_title_mask)
+        user = self.user_encoder.forward_stock(user_title_text, user_title_mask, user_history_mask)
+        return (user.unsqueeze(1) * news).sum(dim=2)
+
+
+def row_logits(news, user):
+    """<news[r], user[r]> per row on the device (``digat_row_logits``), with autograd when gradients are enabled."""
+    news, user = news.float().contiguous(), user.float().contiguous()
+    if torch.is_grad_enabled() and (news.requires_grad or user.requires_grad):
+        return RowLogits.apply(news, user)
+    out = torch.empty(news.shape[0], dtype=torch.float32, device=news.device)
+    if news.shape[0]:
+        _lib.binding().row_logits(news, user, out)
+    return out
+
+
+def make_config(model='NRMS', vocabulary_size=1000, word_embedding_dim=300, head_num=20, head_dim=20, attention_dim=200, max_title_length=32,
+                max_history_num=50, augmented_news_num=10, dropout_rate=0.2):
+    """The fields of the reference's Config that these classes read, at the Appendix-B defaults."""
+    return SimpleNamespace(**locals())
+
+
+# ---- the dev run (Appendix-B util.py:10-72) ------------------------------------------------------------------------------------
+def news_caches(model, title_text, title_mask, augmented_title_text, augmented_title_mask, batch_size=1024):
+    """(plain, augmented) news representations [N, hd], built in batches.  NRMS ignores the augmented titles: one cache serves both.
+    NRMS-SA encodes a batch's original titles once and gates them with their augmented titles (the reference encodes them twice,
+    util.py:37-38: the same values)."""
+    enc = model.news_encoder
+    plain, aug = [], []
+    sa = isinstance(enc, SA_NRMS_NewsEncoder)
+    with torch.no_grad():
+        for lo in range(0, title_text.shape[0], batch_size):
+            sl = slice(lo, lo + batch_size)
+            orig = enc.encode_titles(title_text[sl], title_mask[sl])
+            plain.append(orig)
+            if sa:
+                at, am = augmented_title_text[sl], augmented_title_mask[sl]
+                n, A, L = at.shape
+                aug.append(enc.sa_gate(orig, enc.encode_titles(at.reshape(n * A, L), am.reshape(n * A, L)).view(n, A, -1)))
+    plain = torch.cat(plain) if plain else title_text.new_zeros((0, enc.news_embedding_dim), dtype=torch.float32)
+    return plain, (torch.cat(aug) if sa and aug else plain)
+
+
+def compute_scores(model, dev, batch_size=1024, grouped=True, result_file=None, news_batch_size=None):
+    """The dev run on a corpus-like object with ``title_text / title_mask`` [N, Lw], ``augmented_title_text / augmented_title_mask``
+    [N, A, Lw], ``history_ids / history_mask`` [I, H] (one row per impression), ``row_candidate / row_impression`` [R]
+    (impression-major) and optionally ``row_label`` [R]; tensors on the model's device, the row arrays on the host.
+    Candidates are read from the augmented cache, histories from the plain one.  ``grouped``: each impression's user is encoded
+    once and its representation gathered per row; else once per row, as the reference does — the same scores.
+    ``news_batch_size``: titles per batch of the news caches, by default 4 x batch_size as in the reference (util.py:16).
+    -> (scores [R] tensor, ranks int64 numpy [R], (auc, mrr, ndcg5, ndcg10) or None); ``result_file`` gets the rank file."""
+    from . import evaluate
+    model.eval()
+    plain, aug = news_caches(model, dev.title_text, dev.title_mask, dev.augmented_title_text, dev.augmented_title_mask,
+                             news_batch_size or 4 * batch_size)
+    device = plain.device
+    row_imp = np.asarray(dev.row_impression, dtype=np.int64)
+    cand = torch.from_numpy(np.asarray(dev.row_candidate, dtype=np.int64)).to(device)
+    imp = torch.from_numpy(row_imp).to(device)
+    R = len(row_imp)
+    ue = model.user_encoder
+    scores = torch.empty(R, dtype=torch.float32, device=device)
+    with torch.no_grad():
+        if grouped:
+            users = [ue.encode_cached(plain, dev.history_ids[lo:lo + batch_size], dev.history_mask[lo:lo + batch_size])
+                     for lo in range(0, dev.history_ids.shape[0], batch_size)]
+            users = torch.cat(users) if users else plain.new_zeros((0, plain.shape[1]))
+        for lo in range(0, R, batch_size):
+            sl = slice(lo, lo + batch_size)
+            if grouped:
+                u = users.index_select(0, imp[sl])
+            else:
+                u = ue.encode_cached(plain, dev.history_ids.index_select(0, imp[sl]), dev.history_mask.index_select(0, imp[sl]))
+            c = aug.index_select(0, cand[sl])
+            scores[sl] = row_logits(c, u) if device.type == "cuda" else (c * u).sum(dim=1)
+    labels = getattr(dev, "row_label", None)
+    if device.type == "cuda":
+        ranks, metrics = evaluate.device_ranks_and_metrics(scores, row_imp, labels)
+    else:
+        ranks = evaluate.impression_ranks(scores.numpy(), row_imp)
+        metrics = evaluate.scoring(np.asarray(labels), ranks, row_imp) if labels is not None else None
+    if result_file is not None:
+        with open(result_file, "wb") as f:
+            f.write(evaluate.rank_file_bytes(ranks, row_imp))
+    return scores, ranks, metrics

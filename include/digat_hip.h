@@ -629,6 +629,50 @@ int digat_embedding_bwd_unsorted(const int64_t* ids0, const float* g0, int64_t l
                                  int64_t ld1, int64_t M1, int dm, int64_t V, float* table_grad, void* workspace, size_t workspace_bytes,
                                  void* stream);
 
+/* ---- key-masked multi-head self-attention encoder: the NRMS / NRMS-SA baselines (the reference's Appendix-B) --------------------
+ * Appendix-B/layers.py:79-95 MultiHeadAttention.forward WITH its key mask and without a ReLU, then layers.Attention: the news encoder
+ * (newsEncoders.py:46-58: rows of the word embedding, title mask = key mask = pooling mask) and the user encoder (userEncoders.py:44-47:
+ * rows of the news representations, history mask = key mask, pooling unmasked) are one entry.
+ * `table` [V, in_dim] with ids [T, L] int32 (the lookup rides on the projection's row list where its kernel takes one), or ids == NULL
+ * and `table` = dense rows [T*L, in_dim].  mask [T, L] bytes, 0 = masked key: its score reads -1e9 for every query row, after the
+ * scale; a sequence without a live key therefore attends uniformly over all L positions and passes no gradient to its scores.
+ * out [T, head_num * head_dim].  L <= 64, head_dim <= 128 (fp32 matrix cores up to 32, a plain fp32 kernel above), in_dim % 4 == 0,
+ * head_num * head_dim % 4 == 0.  The split images are digat_split_msa_weights / digat_split_weights outputs, as in digat_msa_params. */
+#define DIGAT_MHSA_POOL_UNMASKED 1               /* flags: the pooling softmax runs over all L positions (the user encoder) */
+typedef struct digat_mhsa_params {
+    int32_t in_dim, head_num, head_dim, attention_dim;
+    const float *table;                          /* [V, in_dim] looked up by ids, or the dense input rows       */
+    const float *W_Q, *b_Q, *W_K, *W_V, *b_V;    /* multiheadAttention.W_{Q,K,V}.{weight,bias}                  */
+    const float *A1, *b1, *a2;                   /* attention.affine1.{weight,bias}, attention.affine2.weight   */
+    const void  *qkv_wsplit;                     /* digat_split_msa_weights output, or NULL                     */
+    const void  *a1_wsplit;                      /* digat_split_weights(affine1.weight, attention_dim, hd) output, or NULL */
+    int32_t flags, reserved;
+} digat_mhsa_params;
+size_t digat_mhsa_workspace_bytes(int T, int L, int in_dim, int head_num, int head_dim, int attention_dim);
+int digat_mhsa_fwd(const digat_mhsa_params* params, const int32_t* ids, const uint8_t* mask, float* out, int T, int L,
+                   void* workspace, size_t workspace_bytes, void* stream);
+/* Training, one call per direction.  p_in: dropout on the input rows (site 1: the counter hash of `seed` over the [T*L, in_dim]
+ * elements), p_ctx: on the attention's output (site 2: `seed + 1` over the [T*L, hd] elements, applied in the attention kernel; the
+ * backward regenerates its keep bits).  `save` carries the dropped input rows, Q|K|V, the attention output, the affine1 product and
+ * the pooling weights; scores and attention weights are recomputed in the backward.  attention_dim % 4 == 0.  The *_wsplit fields
+ * are ignored.  digat_mhsa_bwd writes (does not accumulate) row_grad [T*L, in_dim], rows ld_row_grad floats apart (in_dim, or
+ * digat_msa_row_grad_ld(T, L, in_dim)) — feed it to digat_embedding_bwd; for dense input it is dX — and the weight gradients as
+ * digat_msa_bwd does. */
+size_t digat_mhsa_train_save_bytes(int T, int L, int in_dim, int head_num, int head_dim, int attention_dim);
+size_t digat_mhsa_train_workspace_bytes(int T, int L, int in_dim, int head_num, int head_dim, int attention_dim);
+int digat_mhsa_fwd_train(const digat_mhsa_params* params, const int32_t* ids, const uint8_t* mask, float* out, float p_in, float p_ctx,
+                         uint32_t seed, int T, int L, void* save, size_t save_bytes, void* workspace, size_t workspace_bytes, void* stream);
+int digat_mhsa_bwd(const digat_mhsa_params* params, const int32_t* ids, const uint8_t* mask, const float* dout, float p_in, float p_ctx,
+                   uint32_t seed, const void* save, size_t save_bytes, float* row_grad, int64_t ld_row_grad, float* dW_Q, float* db_Q,
+                   float* dW_K, float* dW_V, float* db_V, float* dA1, float* db1, float* da2, int T, int L, void* workspace,
+                   size_t workspace_bytes, void* stream);
+/* The middle stage alone.  qkv [T*L, 3*hd] (Q | K | V per row), h [T*L, hd] = dropout_{p_ctx}(softmax(mask(Q K^T / sqrt(d_k))) V), keep
+ * bits of `seed` over the [T*L, hd] elements (p_ctx = 0: none); the backward takes dh (the gradient at h) and writes dqkv [T*L, 3*hd]. */
+int digat_mhsa_attention_fwd(const float* qkv, const uint8_t* mask, float* h, float p_ctx, uint32_t seed, int T, int L, int head_num,
+                             int head_dim, void* stream);
+int digat_mhsa_attention_bwd(const float* qkv, const uint8_t* mask, const float* dh, float* dqkv, float p_ctx, uint32_t seed, int T, int L,
+                             int head_num, int head_dim, void* stream);
+
 /* ---- CNN news encoder (newsEncoders.py:29-54, layers.Conv1D :7-47, layers.Attention :91-115) ---------------------------------
  * out[t] = attention_pool(dropout_2(relu(conv1d(dropout_1(word_embedding[title_text[t]])) + b))): the convolution zero-pads
  * (taps - 1) / 2 positions at both ends of each title; padding tokens are looked up like any other.  taps odd, 1..7; `group3`

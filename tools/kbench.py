@@ -350,6 +350,87 @@ def bench_cnn_train(T=6400, Lw=32, V=30000, dm=300, Kc=400, att=256, window=3):
           f"   stock torch {m2:.2f} ms [{lo2:.2f}, {hi2:.2f}]")
 
 
+def _nrms_model(model, V=30000, dm=300, h=20, dk=20, att=200, Lw=32, H=50, A=10, dropout=0.2):
+    from digat_amd import nrms, synthetic
+    cfg = nrms.make_config(model=model, vocabulary_size=V, word_embedding_dim=dm, head_num=h, head_dim=dk, attention_dim=att,
+                           max_title_length=Lw, max_history_num=H, augmented_news_num=A, dropout_rate=dropout)
+    m = nrms.Model(cfg)
+    m.load_state_dict({k_: torch.from_numpy(v) for k_, v in synthetic.make_nrms_state(V, dm, h, dk, att, sa=(model == "NRMS-SA"), seed=1).items()})
+    return m.to(torch.device("cuda:0"))
+
+
+def bench_nrms_news(T=65238, Lw=32, V=30000):
+    """NRMS news encoder, inference (digat_mhsa_fwd: key-masked attention) against forward_stock, alternated in one process.
+    T = 65 238 is MIND-small's news count: the plain news cache of a dev run."""
+    from digat_amd import synthetic
+    m = _nrms_model("NRMS", V=V, Lw=Lw).eval()
+    enc = m.news_encoder
+    text, mask = synthetic.make_titles(T, Lw, V, seed=2)
+    tt, tm = torch.from_numpy(text).cuda().unsqueeze(0), torch.from_numpy(mask).cuda().unsqueeze(0)
+
+    def hip():
+        with torch.no_grad():
+            return enc(tt, tm)
+
+    def stock():
+        with torch.no_grad():
+            return enc.forward_stock(tt, tm)
+    diff = float((hip() - stock()).abs().max())
+    (m1, lo1, hi1), (m2, lo2, hi2) = alternate(hip, stock)
+    print(f"NRMS news encoder T={T} titles x {Lw} tokens: HIP {m1:.2f} ms [{lo1:.2f}, {hi1:.2f}] ({T/m1/1e3:.2f} M titles/s)"
+          f"   stock torch {m2:.2f} ms [{lo2:.2f}, {hi2:.2f}]   max|diff| {diff:.2e}")
+
+
+def bench_nrms_user(B=4096, H=50, N=65238):
+    """NRMS user encoder, inference: B users x H history items looked up in the cached news representations by id (digat_mhsa_fwd with
+    the cache as its table) against index_select + encode_stock, alternated."""
+    m = _nrms_model("NRMS", H=H).eval()
+    ue = m.user_encoder
+    g = torch.Generator().manual_seed(3)
+    cache = torch.randn(N, m.news_embedding_dim, generator=g).cuda()
+    ids = torch.randint(0, N, (B, H), generator=g).cuda()
+    length = torch.randint(0, H + 1, (B, 1), generator=g)
+    mask = (torch.arange(H)[None, :] < length).cuda()
+
+    def hip():
+        with torch.no_grad():
+            return ue.encode_cached(cache, ids, mask)
+
+    def stock():
+        with torch.no_grad():
+            return ue.encode_stock(cache.index_select(0, ids.flatten()).view(B, H, -1), mask)
+    diff = float((hip() - stock()).abs().max())
+    (m1, lo1, hi1), (m2, lo2, hi2) = alternate(hip, stock)
+    print(f"NRMS user encoder B={B} users x {H} history items: HIP {m1:.2f} ms [{lo1:.2f}, {hi1:.2f}] ({B/m1/1e3:.2f} M users/s)"
+          f"   stock torch {m2:.2f} ms [{lo2:.2f}, {hi2:.2f}]   max|diff| {diff:.2e}")
+
+
+def bench_nrms_train(B=64, K=5, A=10, H=50, Lw=32, V=30000, sa=1):
+    """One training step of the whole model (forward + backward, dropout 0.2): B impressions x (K candidates x (1 + A) titles + H history
+    titles) through the HIP pairs against forward_stock, alternated."""
+    from digat_amd import synthetic
+    m = _nrms_model("NRMS-SA" if sa else "NRMS", V=V, Lw=Lw, H=H, A=A).train()
+    dev = torch.device("cuda:0")
+
+    def titles(n, seed):
+        t, k = synthetic.make_titles(n, Lw, V, seed=seed)
+        return torch.from_numpy(t).to(dev), torch.from_numpy(k).to(dev)
+    ut, um = (x.view(B, H, Lw) for x in titles(B * H, 4))
+    nt, nm = (x.view(B, K, Lw) for x in titles(B * K, 5))
+    at, am = (x.view(B, K, A, Lw) for x in titles(B * K * A, 6))
+    hm = (torch.arange(H)[None, :] < torch.randint(0, H + 1, (B, 1), generator=torch.Generator().manual_seed(7))).to(dev)
+    label = torch.zeros(B, dtype=torch.long, device=dev)
+
+    def step(fn):
+        def run():
+            m.zero_grad(set_to_none=True)
+            torch.nn.functional.cross_entropy(fn(ut, um, hm, nt, nm, at, am), label).backward()
+        return run
+    (m1, lo1, hi1), (m2, lo2, hi2) = alternate(step(m), step(m.forward_stock))
+    print(f"{m.model_name} training step {B} x ({K} x {1 + A if sa else 1} + {H}) titles x {Lw} tokens: HIP {m1:.2f} ms [{lo1:.2f}, {hi1:.2f}]"
+          f"   stock torch {m2:.2f} ms [{lo2:.2f}, {hi2:.2f}]")
+
+
 def bench_sag(n=30000, m=30000, dim=768, top_M=5, news_num=65238, hop=2, cpu_rows=32):
     """SAG construction: cosine top-k of one category of n news against an m-news corpus, and the walk over
     news_num similarity lists; the reference's per-news loop (oracle restatement) timed on cpu_rows rows beside it."""
@@ -397,6 +478,12 @@ if __name__ == "__main__":
         bench_cnn(*nums)
     elif what == "cnn-train":
         bench_cnn_train(*nums)
+    elif what == "nrms-news":
+        bench_nrms_news(*nums)
+    elif what == "nrms-user":
+        bench_nrms_user(*nums)
+    elif what == "nrms-train":
+        bench_nrms_train(*nums)
     elif what == "sag":
         bench_sag(*nums)
     elif what == "topic":
