@@ -57,6 +57,8 @@ class Config:
         p.add_argument('--inference_projection', default='auto',
                        choices=['auto', 'bf16x6', 'bf16x6-pq3', 'fp32', 'fp16x3', 'fp16-fp8c', 'pq-bf16', 'pq-bf16-x1', 'pq-fp8'],
                        help="the graph encoder's projection_mode for dev / test scoring (fp16-fp8c: fp16 + fp8 matrix-core corrections)")
+        p.add_argument('--user_graphs', default='table', choices=['table', 'derived'],
+                       help='table: user graphs uploaded with the corpus; derived: built on the device per batch from the category indices')
         a = p.parse_args(argv)
         self.attribute_dict = dict(vars(a))
         for k, v in self.attribute_dict.items():

@@ -13,6 +13,7 @@
 //   digat_glue.inc     user-node build, group expansion, live-row lists, row logits
 //   digat_train.inc    backward / training kernels;  digat_eval.inc  per-impression ranking + metrics
 //   digat_news.inc     MSA news encoder (inference);  digat_gat.inc  vanilla-GAT layer of the ablation encoders
+//   digat_user_graph.inc  user graphs and category masks from category indices
 // This file: shared helpers, the per-kernel profiler, and the C ABI.  The encoder's orchestration is digat_encoder.inc (host
 // code only), and every decision of an encoder call is made in digat_encoder_plan.h (plain C++).
 //
@@ -819,3 +820,4 @@ int digat_row_logits(const float* news_ctx, const float* user_ctx, float* logits
 #include "digat_cnn.inc"
 #include "digat_gat.inc"
 #include "digat_sag.inc"
+#include "digat_user_graph.inc"

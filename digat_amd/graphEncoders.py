@@ -26,6 +26,18 @@ from .layers import ScaledDotProductAttention
 _TLS = threading.local()          # per-thread launch-option overrides, keyed by encoder (DIGAT.launch_options)
 
 
+def derive_user_graph(user_graph, user_category_mask, user_category_indices, category_num: int):
+    """``user_graph=None`` (and then ``user_category_mask=None``) means "derive both from ``user_category_indices``": they are a
+    pure function of the indices (``util.user_graphs_from_indices``, one launch into Python-allocated buffers).  A given graph
+    passes through untouched.  ``category_num``: C, without the padding bucket."""
+    if user_graph is not None:
+        return user_graph, user_category_mask
+    if user_category_mask is not None:
+        raise ValueError("user_graph=None derives the category mask too: pass user_category_mask=None")
+    from .util import user_graphs_from_indices
+    return user_graphs_from_indices(user_category_indices, category_num)
+
+
 class GraphEncoder(nn.Module):
     def __init__(self, config, news_embedding_dim: int):
         super().__init__()
@@ -548,6 +560,7 @@ class DIGAT(GraphEncoder):
         each row to its group; results are bit-identical to ``inference`` on the expanded tensors.
         ``news_index`` [B] int64: ``news_graph_embeddings`` and ``news_hpq0`` are then the per-news TABLES ([news_num, N, d],
         [3, news_num, N, d]) and row b reads their row ``news_index[b]`` in place (no gathered copies)."""
+        user_graph, user_category_mask = derive_user_graph(user_graph, user_category_mask, user_category_indices, self.category_num - 1)
         Xn, ue = _lib.f32(news_graph_embeddings), _lib.f32(user_news_embedding)
         dev = _lib.require_device(Xn, news_graph, news_graph_mask, ue, user_graph, user_category_mask,
                                   user_category_indices, row_group)
@@ -601,6 +614,7 @@ class DIGAT(GraphEncoder):
 
     def forward(self, news_graph_embeddings, news_graph, news_graph_mask, user_news_embedding, user_graph,
                 user_category_mask, user_category_indices):
+        user_graph, user_category_mask = derive_user_graph(user_graph, user_category_mask, user_category_indices, self.category_num - 1)
         if self.training and torch.is_grad_enabled():
             from .training import digat_forward_train
             return digat_forward_train(self, news_graph_embeddings, news_graph, news_graph_mask,
@@ -615,6 +629,7 @@ class DIGAT(GraphEncoder):
         call goes to ``digat_encoder_fwd_shared`` — the runs are found on the device (every byte of the four user tensors compared
         with the previous row's), nothing is read back by the host, and layer 0 of the user graph is computed once per run.
         Bit-identical to the per-row entry; rows that share nothing cost the comparison pass on top of it."""
+        user_graph, user_category_mask = derive_user_graph(user_graph, user_category_mask, user_category_indices, self.category_num - 1)
         want = bool(self._launch_option("detect_shared_users") and not self.training and self.graph_depth > 0
                     and news_graph_embeddings.shape[0] >= self.SHARED_USERS_MIN_ROWS)
         if (want and self.user_xattn_mode == "auto" and "user" not in self.corpus_xattn_hint and user_graph.is_cuda
@@ -776,6 +791,7 @@ class _Ablation(GraphEncoder):
 
     def forward(self, news_graph_embeddings, news_graph, news_graph_mask, user_news_embedding, user_graph,
                 user_category_mask, user_category_indices):
+        user_graph, user_category_mask = derive_user_graph(user_graph, user_category_mask, user_category_indices, self.category_num - 1)
         if self.training and torch.is_grad_enabled():
             from .training import ablation_forward_train
             return ablation_forward_train(self, news_graph_embeddings, news_graph, news_graph_mask, user_news_embedding,
@@ -786,6 +802,7 @@ class _Ablation(GraphEncoder):
 
     def inference(self, news_graph_embeddings, news_graph, news_graph_mask, user_news_embedding, user_graph,
                   user_category_mask, user_category_indices, news_graph_context):
+        user_graph, user_category_mask = derive_user_graph(user_graph, user_category_mask, user_category_indices, self.category_num - 1)
         return self._encode(_lib.f32(news_graph_embeddings), news_graph, news_graph_mask, user_news_embedding, user_graph,
                             user_category_mask, user_category_indices, _lib.f32(news_graph_context))
 
@@ -806,6 +823,7 @@ class wo_SA(_Ablation):
 
     def forward(self, news_graph_embeddings, news_graph, news_graph_mask, user_news_embedding, user_graph,
                 user_category_mask, user_category_indices):
+        user_graph, user_category_mask = derive_user_graph(user_graph, user_category_mask, user_category_indices, self.category_num - 1)
         if self.training and torch.is_grad_enabled():
             from .training import ablation_forward_train
             return ablation_forward_train(self, news_graph_embeddings, news_graph, news_graph_mask, user_news_embedding,
@@ -814,6 +832,7 @@ class wo_SA(_Ablation):
 
     def inference(self, news_graph_embeddings, news_graph, news_graph_mask, user_news_embedding, user_graph,
                   user_category_mask, user_category_indices, news_graph_context):
+        user_graph, user_category_mask = derive_user_graph(user_graph, user_category_mask, user_category_indices, self.category_num - 1)
         return self._run(news_graph_embeddings, user_news_embedding, user_graph, user_category_mask, user_category_indices)
 
 

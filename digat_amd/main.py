@@ -29,7 +29,7 @@ def main(argv=None):
                                                               trainable=config.mode == 'train'))
     model.initialize()
     model = model.to(dev)
-    dc = util.DeviceCorpus.from_numpy(corpus, dev)
+    dc = util.DeviceCorpus.from_numpy(corpus, dev, user_graphs=config.user_graphs)
     if config.mode == 'train':
         trainer = Trainer(model, config, dc, SyntheticTrainSet(corpus, config.negative_sample_num, config.seed),
                           local_rank=config.local_rank, dev_labels=corpus.row_label)

@@ -63,6 +63,9 @@ class Model(nn.Module):
         def per_candidate(t):
             return t.unsqueeze(1).expand(-1, news_num, *t.shape[1:]).contiguous().view([bn, *t.shape[1:]])
 
+        # user_graph=None: built once per behaviour from its category indices, then expanded like a given one
+        user_graph, user_category_mask = graphEncoders.derive_user_graph(user_graph, user_category_mask, user_category_indices,
+                                                                         self.category_num - 1)
         user_graph = per_candidate(user_graph)
         user_category_mask = per_candidate(user_category_mask)
         user_category_indices = per_candidate(user_category_indices)

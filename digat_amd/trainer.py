@@ -126,9 +126,10 @@ class Trainer:
         # is made once, on the host, as util.prepare_news_side does for scoring; an explicit encoder.user_xattn_mode wins
         enc = getattr(model, "graph_encoder", None)
         if enc is not None and hasattr(enc, "corpus_xattn_hint") and "user" not in enc.corpus_xattn_hint and dc is not None \
-                and getattr(dc, "user_graph", None) is not None and dc.user_graph.numel() > 0:
-            per_node = float(dc.user_graph.sum(dtype=torch.float64) / (dc.user_graph.shape[0] * dc.user_graph.shape[1]))
-            enc.corpus_xattn_hint = dict(enc.corpus_xattn_hint, user="sparse" if per_node <= util.SPARSE_ENTRIES_PER_NODE else "dense")
+                and (getattr(dc, "user_graph", None) is not None or getattr(dc, "category_num", 0) > 0):
+            per_node = util.user_graph_entries_per_node(dc)          # from the table, or from one build over the corpus's indices
+            if per_node is not None:
+                enc.corpus_xattn_hint = dict(enc.corpus_xattn_hint, user="sparse" if per_node <= util.SPARSE_ENTRIES_PER_NODE else "dense")
         util.freeze_host_heap()           # the corpus's host-side structures: out of the garbage collector's walks (util.freeze_host_heap)
 
     def lr_decay(self):
@@ -168,12 +169,12 @@ class Trainer:
                         dc.title_mask.index_select(0, flat).view(*ids.shape[:-1], Lw))
             ht, hm = titles(hist)
             nt, nm = titles(node_ids)
-            return (ht, hm, dc.user_graph.index_select(0, imp), dc.user_category_mask.index_select(0, imp),
+            return (ht, hm, *util.user_side_rows(dc, imp),
                     dc.user_category_indices.index_select(0, imp), nt, nm,
                     dc.news_graph.index_select(0, news.flatten()).view(B, K, *dc.news_graph.shape[1:]),
                     dc.news_graph_mask.index_select(0, news.flatten()).view(B, K, -1))
-        return (hist, torch.ones_like(hist, dtype=torch.bool), dc.user_graph.index_select(0, imp),
-                dc.user_category_mask.index_select(0, imp), dc.user_category_indices.index_select(0, imp),
+        return (hist, torch.ones_like(hist, dtype=torch.bool), *util.user_side_rows(dc, imp),
+                dc.user_category_indices.index_select(0, imp),
                 node_ids, torch.ones_like(node_ids, dtype=torch.bool),
                 dc.news_graph.index_select(0, news.flatten()).view(B, K, *dc.news_graph.shape[1:]),
                 dc.news_graph_mask.index_select(0, news.flatten()).view(B, K, -1))

@@ -38,8 +38,8 @@ class DeviceCorpus:
     news_graph: torch.Tensor             # [news_num, N, N] bool
     news_graph_mask: torch.Tensor        # [news_num, N]   bool
     history: torch.Tensor                # [I, H] int64
-    user_graph: torch.Tensor             # [I, U, U] bool
-    user_category_mask: torch.Tensor     # [I, C+1] bool
+    user_graph: Optional[torch.Tensor]          # [I, U, U] bool, or None: built per batch from user_category_indices ("derived")
+    user_category_mask: Optional[torch.Tensor]  # [I, C+1] bool, or None likewise
     user_category_indices: torch.Tensor  # [I, H] int64
     row_impression: torch.Tensor         # [R] int64
     row_candidate: torch.Tensor          # [R] int64
@@ -56,20 +56,113 @@ class DeviceCorpus:
     xattn_hint: Optional[dict] = None                        # THIS corpus's sparse / dense choice per graph (prepare_news_side); applied to the
                                                              # encoder whenever this corpus is scored (two corpora may share one encoder)
     range_overflow_at_prepare: bool = False                  # an fp16x3 GEMM left the format's range while the per-news tables were built
+    category_num: int = 0                                    # C (without the padding bucket); 0: read off user_category_mask
+
+    def __post_init__(self):
+        if not self.category_num and self.user_category_mask is not None:
+            self.category_num = int(self.user_category_mask.shape[1]) - 1
 
     @classmethod
-    def from_numpy(cls, corpus, device) -> "DeviceCorpus":
+    def from_numpy(cls, corpus, device, user_graphs: str = "table", category_num: Optional[int] = None) -> "DeviceCorpus":
+        """``user_graphs="table"``: the corpus's ``user_graph`` / ``user_category_mask`` are uploaded and batches gather rows from
+        them.  ``"derived"``: neither is uploaded (nor read: the corpus need not have them) — both are a pure function of
+        ``user_category_indices`` and are built on the device per batch (``user_graphs_from_indices``); ``category_num`` then
+        comes from the argument, the corpus's mask shape or its spec."""
+        if user_graphs not in ("table", "derived"):
+            raise ValueError("user_graphs must be 'table' or 'derived'")
+
         def t(a, dtype=None):
             x = torch.from_numpy(np.ascontiguousarray(a))
             return (x.to(dtype) if dtype is not None else x).to(device)
+        table = user_graphs == "table"
+        if category_num is None:
+            mask = getattr(corpus, "user_category_mask", None)
+            category_num = int(mask.shape[1]) - 1 if mask is not None else int(corpus.spec.category_num)
         return cls(t(corpus.news_embedding), t(corpus.news_node_ID, torch.int64), t(corpus.news_graph),
-                   t(corpus.news_graph_mask), t(corpus.history, torch.int64), t(corpus.user_graph),
-                   t(corpus.user_category_mask), t(corpus.user_category_indices, torch.int64),
-                   t(corpus.row_impression, torch.int64), t(corpus.row_candidate, torch.int64))
+                   t(corpus.news_graph_mask), t(corpus.history, torch.int64), t(corpus.user_graph) if table else None,
+                   t(corpus.user_category_mask) if table else None, t(corpus.user_category_indices, torch.int64),
+                   t(corpus.row_impression, torch.int64), t(corpus.row_candidate, torch.int64), category_num=int(category_num))
 
     @property
     def rows(self) -> int:
         return int(self.row_impression.shape[0])
+
+    @property
+    def user_graph_size(self) -> int:
+        """U = H + C: nodes of a user graph."""
+        return int(self.user_category_indices.shape[1]) + self.category_num
+
+
+USER_GRAPH_CHUNK_BYTES = 256 << 20      # a corpus-wide build (entries per node) keeps its transient graph buffer below this
+USER_GRAPH_CHUNK_ROWS = 4096            # ... and at this many graphs (20 MB at U = 67: enough to fill the chip, never a corpus-sized table)
+
+
+def user_graphs_from_indices(cat_idx: torch.Tensor, category_num: int, rows: Optional[torch.Tensor] = None, out=None,
+                             want_entries: bool = False):
+    """User graphs and category masks from category indices, on the device (``digat_user_graph_build``: MIND_corpus.py:145-176 as
+    one launch on the current stream).  ``cat_idx`` [I, H] int64; graph g is built from row ``rows[g]`` (``rows`` [G] int64, any
+    order, repeats allowed) or from row g.  Returns ``(user_graph [G,U,U] bool, user_category_mask [G,C+1] bool)`` and, with
+    ``want_entries``, ``entries`` [G] int32 (set bytes per graph).  ``out``: preallocated contiguous buffers in that order (bool or
+    uint8; the third is optional).  GPU tensors only."""
+    from . import _lib
+    dev = _lib.require_device(*((cat_idx,) if rows is None else (cat_idx, rows)))
+    if cat_idx.dim() != 2:
+        raise _lib.DigatHipError("user_category_indices must be [rows, max_history_num]")
+    ci = cat_idx.to(torch.int64).contiguous()
+    H, C = int(ci.shape[1]), int(category_num)
+    U = H + C
+    if rows is not None:
+        rows = rows.to(torch.int64).contiguous()
+    G = int(ci.shape[0] if rows is None else rows.shape[0])
+    if out is None:
+        graph = torch.empty((G, U, U), dtype=torch.bool, device=dev)
+        mask = torch.empty((G, C + 1), dtype=torch.bool, device=dev)
+        entries = None
+    else:
+        graph, mask = out[0], out[1]
+        entries = out[2] if len(out) > 2 else None
+        _lib.require_device(cat_idx, graph, mask)
+        for t, shape in ((graph, (G, U, U)), (mask, (G, C + 1))):
+            if tuple(t.shape) != shape or t.dtype not in (torch.bool, torch.uint8) or not t.is_contiguous():
+                raise _lib.DigatHipError(f"out buffer must be contiguous bool / uint8 {shape}, got {t.dtype} {tuple(t.shape)}")
+    if want_entries and entries is None:
+        entries = torch.empty((G,), dtype=torch.int32, device=dev)
+    if entries is not None and (tuple(entries.shape) != (G,) or entries.dtype != torch.int32 or not entries.is_contiguous()
+                                or entries.device != dev):
+        raise _lib.DigatHipError("entries must be a contiguous int32 [G] tensor on the same device")
+    if G:                                # empty tensors have no storage to point at
+        _lib.check(_lib.lib().digat_user_graph_build(ci.data_ptr(), _lib.ptr(rows), G, H, C, graph.data_ptr(), mask.data_ptr(),
+                                                     _lib.ptr(entries), _lib.stream_ptr()), "digat_user_graph_build")
+    graph, mask = graph.view(torch.bool), mask.view(torch.bool)
+    return (graph, mask, entries) if want_entries else (graph, mask)
+
+
+def user_side_rows(dc: DeviceCorpus, imp: torch.Tensor):
+    """``(user_graph, user_category_mask)`` of the impressions ``imp``: rows of the corpus tables, or — a corpus without them —
+    built in place from the impressions' category indices."""
+    if dc.user_graph is not None:
+        return dc.user_graph.index_select(0, imp), dc.user_category_mask.index_select(0, imp)
+    return user_graphs_from_indices(dc.user_category_indices, dc.category_num, rows=imp)
+
+
+def user_graph_entries_per_node(dc: DeviceCorpus) -> Optional[float]:
+    """Mean number of adjacency entries per node over the corpus's user graphs (the sparse / dense choice of Eq. 8), or None for a
+    corpus without impressions.  Without a table: from ``entries`` of one build over the corpus, in chunks of at most
+    ``USER_GRAPH_CHUNK_ROWS`` graphs whose transient buffer stays below ``USER_GRAPH_CHUNK_BYTES``."""
+    I, U = int(dc.user_category_indices.shape[0]), dc.user_graph_size
+    if I == 0:
+        return None
+    if dc.user_graph is not None:
+        return float(dc.user_graph.sum(dtype=torch.float64) / (I * U))
+    dev = dc.user_category_indices.device
+    chunk = max(1, min(I, USER_GRAPH_CHUNK_ROWS, (USER_GRAPH_CHUNK_BYTES - 1) // (U * U)))
+    graph = torch.empty((chunk, U, U), dtype=torch.bool, device=dev)
+    mask = torch.empty((chunk, dc.category_num + 1), dtype=torch.bool, device=dev)
+    entries = torch.empty((I,), dtype=torch.int32, device=dev)
+    for s in range(0, I, chunk):
+        n = min(chunk, I - s)
+        user_graphs_from_indices(dc.user_category_indices[s:s + n], dc.category_num, out=(graph[:n], mask[:n], entries[s:s + n]))
+    return float(entries.sum(dtype=torch.float64) / (I * U))
 
 
 def shard_rows(row_impression: np.ndarray, world_size: int, rank: int) -> Tuple[int, int]:
@@ -118,9 +211,8 @@ def prepare_news_side(encoder, dc: DeviceCorpus, batch_size: int) -> None:
     # number of adjacency entries per node (MIND user graphs: ~4 of 67).  An explicit "dense" / "sparse" setting wins.
     if hasattr(encoder, "resolved_xattn_mode"):
         hint = {}
-        if dc.user_graph.numel() > 0:
-            U = dc.user_graph.shape[1]
-            per_node = float(dc.user_graph.sum(dtype=torch.float64) / (dc.user_graph.shape[0] * U))
+        per_node = user_graph_entries_per_node(dc)
+        if per_node is not None:
             hint["user"] = "sparse" if per_node <= SPARSE_ENTRIES_PER_NODE else "dense"
         if N > 16 and dc.news_graph.numel() > 0:
             per_node = float(dc.news_graph.sum(dtype=torch.float64) / (news_num * N))
@@ -214,7 +306,7 @@ def gather_batch(dc: DeviceCorpus, start: int, end: int):
     d = dc.news_embedding.shape[1]
     hist = dc.history.index_select(0, imp)
     user_rep = dc.news_embedding.index_select(0, hist.flatten()).view(end - start, H, d)
-    return (user_rep, dc.user_graph.index_select(0, imp), dc.user_category_mask.index_select(0, imp),
+    return (user_rep, *user_side_rows(dc, imp),
             dc.user_category_indices.index_select(0, imp), dc.SA_news_representations.index_select(0, cand),
             dc.news_graph.index_select(0, cand), dc.news_graph_mask.index_select(0, cand),
             dc.c_n0.index_select(0, cand))
@@ -233,7 +325,7 @@ def gather_batch_grouped(dc: DeviceCorpus, start: int, end: int, row_impression_
     H, d = dc.history.shape[1], dc.news_embedding.shape[1]
     hist = dc.history.index_select(0, uniq)
     user_rep = dc.news_embedding.index_select(0, hist.flatten()).view(uniq.shape[0], H, d)
-    return (user_rep, dc.user_graph.index_select(0, uniq), dc.user_category_mask.index_select(0, uniq),
+    return (user_rep, *user_side_rows(dc, uniq),
             dc.user_category_indices.index_select(0, uniq), row_group, dc.SA_news_representations.index_select(0, cand),
             dc.news_graph.index_select(0, cand), dc.news_graph_mask.index_select(0, cand), dc.c_n0.index_select(0, cand))
 
@@ -261,8 +353,10 @@ class GroupedBatchPipeline:
         B = max(e - s for s, e in self.batches)
         Gmax = max(1, B // 4)
         H, d = dc.history.shape[1], dc.news_embedding.shape[1]
-        U, C1 = dc.user_graph.shape[1], dc.user_category_mask.shape[1]
+        U, C1 = dc.user_graph_size, dc.category_num + 1
         N = dc.news_graph.shape[1]
+        ug_dtype = dc.user_graph.dtype if dc.user_graph is not None else torch.bool
+        cm_dtype = dc.user_category_mask.dtype if dc.user_category_mask is not None else torch.bool
 
         import os
         in_place_tables = in_place_tables and os.environ.get("DIGAT_IN_PLACE", "1") != "0"          # A/B switch for measurements
@@ -272,8 +366,8 @@ class GroupedBatchPipeline:
         def bufs():
             return dict(hist=torch.empty((Gmax, H), dtype=torch.int64, device=dev),
                         user_rep=torch.empty((Gmax, H, d), dtype=torch.float32, device=dev),
-                        user_graph=torch.empty((Gmax, U, U), dtype=dc.user_graph.dtype, device=dev),
-                        cat_mask=torch.empty((Gmax, C1), dtype=dc.user_category_mask.dtype, device=dev),
+                        user_graph=torch.empty((Gmax, U, U), dtype=ug_dtype, device=dev),
+                        cat_mask=torch.empty((Gmax, C1), dtype=cm_dtype, device=dev),
                         cat_idx=torch.empty((Gmax, H), dtype=torch.int64, device=dev),
                         sa=(torch.empty((B, N, d), dtype=torch.float32, device=dev) if not in_place else None),
                         news_graph=torch.empty((B, N, N), dtype=dc.news_graph.dtype, device=dev),
@@ -334,8 +428,9 @@ class GroupedBatchPipeline:
                 return t[0].numel() * t.element_size()
             job(hist_tab, b["hist"].data_ptr(), rowb(dc.history), G, uniq_ptr)
             job(dc.news_embedding.data_ptr(), b["user_rep"].data_ptr(), d * 4, G * H, uniq_ptr, hist_tab, H)
-            job(dc.user_graph.data_ptr(), b["user_graph"].data_ptr(), rowb(dc.user_graph), G, uniq_ptr)
-            job(dc.user_category_mask.data_ptr(), b["cat_mask"].data_ptr(), rowb(dc.user_category_mask), G, uniq_ptr)
+            if dc.user_graph is not None:
+                job(dc.user_graph.data_ptr(), b["user_graph"].data_ptr(), rowb(dc.user_graph), G, uniq_ptr)
+                job(dc.user_category_mask.data_ptr(), b["cat_mask"].data_ptr(), rowb(dc.user_category_mask), G, uniq_ptr)
             job(dc.user_category_indices.data_ptr(), b["cat_idx"].data_ptr(), rowb(dc.user_category_indices), G, uniq_ptr)
             if b["sa"] is not None:
                 job(dc.SA_news_representations.data_ptr(), b["sa"].data_ptr(), rowb(dc.SA_news_representations), n, cand_ptr)
@@ -353,6 +448,8 @@ class GroupedBatchPipeline:
                     job(dc.news_hpq0[t].data_ptr(), b["hpq"].data_ptr() + 4 * t * n * N * d, N * d * 4, n, cand_ptr)
             arr = (_lib.GatherJob * len(jobs))(*[_lib.GatherJob(*j) for j in jobs])
             _lib.check(_lib.lib().digat_gather_tables(arr, len(jobs), _lib.stream_ptr()), "digat_gather_tables")
+            if dc.user_graph is None:          # no table to gather from: the groups' graphs and masks are built in the set's buffers
+                user_graphs_from_indices(dc.user_category_indices, dc.category_num, rows=uniq, out=(b["user_graph"][:G], b["cat_mask"][:G]))
             self.ready[par].record(self.stream)
         self.meta[par] = (k, (G, n, self.row_group_all[self.ro[k]:self.ro[k + 1]]))
 

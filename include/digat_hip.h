@@ -747,6 +747,19 @@ typedef struct digat_gather_job {
 } digat_gather_job;
 int digat_gather_tables(const digat_gather_job* jobs, int njobs, void* stream);
 
+/* ---- user graphs from category indices (the device-side counterpart of MIND_corpus.py:145-176) --------------------------------
+ * The user graph [U, U] (U = H + C) and the category mask [C + 1] of an impression are a pure function of its H category
+ * indices: slot t is valid iff 0 <= idx[t] < C (the padding bucket C, negatives and larger values are padding; valid slots need
+ * not form a prefix), present[c] iff some valid slot has idx[t] == c, and
+ *   A[i][j] (i, j < H) = i == j, or both valid and idx[i] == idx[j];   A[i][H+c] = A[H+c][i] = slot i valid and idx[i] == c;
+ *   A[H+a][H+b] = a == b, or present[a] and present[b];   mask[c] = present[c] for c < C, mask[C] = 0.
+ * Graph g is built from row rows[g] of the [I, H] table cat_idx (any order, repeats allowed; the caller keeps rows[g] in [0, I)),
+ * or from row g of a [G, H] cat_idx when rows == NULL.  graph [G, U, U] and cat_mask [G, C + 1]: every byte is written, 0 or 1.
+ * entries (optional) [G]: the number of set bytes of graph g.  One launch on `stream`; no allocation, no synchronisation (safe
+ * under stream capture).  DIGAT_ERR_SHAPE unless 1 <= H, 1 <= C, H + C <= DIGAT_MAX_NODES; G == 0 returns without a launch. */
+int digat_user_graph_build(const int64_t* cat_idx, const int64_t* rows, long G, int H, int C, uint8_t* graph, uint8_t* cat_mask,
+                           int32_t* entries, void* stream);
+
 /* ---- measurement aid (not on the reference's surface): per-kernel HIP-event timing ---------------
  * Between start and stop every kernel launch of this library is bracketed by two events recorded
  * on the stream it is launched on.  stop() synchronises and returns, per kernel kind, the summed

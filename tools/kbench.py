@@ -9,6 +9,8 @@
   python tools/kbench.py cnn [T Lw V dm Kc att window]        CNN news encoder, inference: HIP vs forward_stock on the same device,
                                              alternated, the spread of the rounds' medians reported (default T = 8 192 and 65 238)
   python tools/kbench.py cnn-train [T ...]   one CNN training step (forward + backward, dropout 0.2), the same way (T = 6 400)
+  python tools/kbench.py user-graph [G H C I]   a batch's user graphs: gathered from the [I,U,U] table (digat_gather_tables) vs built
+                                             from category indices (digat_user_graph_build), and one build over all I impressions
 Timing with torch events on the current stream, median of --iters launches.
 """
 import os
@@ -461,6 +463,81 @@ def bench_sag(n=30000, m=30000, dim=768, top_M=5, news_num=65238, hop=2, cpu_row
           f"   CPU walk {cpu2 * news_num:.0f} ms ({1 / cpu2:.1f} k news/s, 1 thread, {sub} rows)")
 
 
+def bench_user_graph(G=1024, H=50, C=17, I=73152, rounds=5):
+    """A scoring batch's user graphs and category masks, three ways in one process, alternated, median [min, max] of ``rounds``
+    rounds: (a) the table path's two gathers (digat_gather_tables) of G consecutive impressions, (b) digat_user_graph_build with
+    ``rows`` for the same impressions, (c) one build over all I impressions (MIND-small dev: 73 152).  Every call of (a) and (b)
+    takes the next block of G impressions, so the table rows (a) reads come from HBM as in a scoring run, not from a warm cache.
+    A launch is a few microseconds, less than its enqueue from Python: each timing replays a captured hipGraph of many launches
+    (no host work between them) between two events and divides by their number."""
+    from digat_amd import util
+    dev = torch.device("cuda:0")
+    rng = np.random.default_rng(7)
+    U, C1 = H + C, C + 1
+    w = 1.0 / np.arange(1, C + 1) ** 1.2
+    cats = rng.choice(C, size=(I, H), p=w / w.sum())
+    hist_len = np.clip(np.round(rng.lognormal(3.0, 0.8, size=I)), 0, H).astype(np.int64)       # synthetic.make_corpus's histories
+    ci = torch.from_numpy(np.where(np.arange(H)[None, :] < hist_len[:, None], cats, C).astype(np.int64)).to(dev)
+    table, mask_table, entries = util.user_graphs_from_indices(ci, C, want_entries=True)
+    per_node = float(entries.sum(dtype=torch.float64)) / (I * U)
+    all_rows = torch.arange(I, dtype=torch.int64, device=dev)
+    blocks = max(1, I // G)
+    out_a = (torch.empty((G, U, U), dtype=torch.bool, device=dev), torch.empty((G, C1), dtype=torch.bool, device=dev))
+    out_b = (torch.empty((G, U, U), dtype=torch.bool, device=dev), torch.empty((G, C1), dtype=torch.bool, device=dev))
+    L, turn = _lib.lib(), [0, 0]
+
+    def gather():
+        rows = all_rows[(turn[0] % blocks) * G:].data_ptr()
+        turn[0] += 1
+        jobs = [(table.data_ptr(), out_a[0].data_ptr(), U * U, G, rows, 0, 1), (mask_table.data_ptr(), out_a[1].data_ptr(), C1, G, rows, 0, 1)]
+        arr = (_lib.GatherJob * 2)(*[_lib.GatherJob(*j) for j in jobs])
+        _lib.check(L.digat_gather_tables(arr, 2, _lib.stream_ptr()), "digat_gather_tables")
+
+    def build():
+        rows = all_rows[(turn[1] % blocks) * G:].data_ptr()
+        turn[1] += 1
+        _lib.check(L.digat_user_graph_build(ci.data_ptr(), rows, G, H, C, out_b[0].data_ptr(), out_b[1].data_ptr(), None, _lib.stream_ptr()),
+                   "digat_user_graph_build")
+
+    def build_all():
+        _lib.check(L.digat_user_graph_build(ci.data_ptr(), None, I, H, C, table.data_ptr(), mask_table.data_ptr(), None, _lib.stream_ptr()),
+                   "digat_user_graph_build")
+
+    gather(); build()
+    torch.cuda.synchronize()
+    same = torch.equal(out_a[0], out_b[0]) and torch.equal(out_a[1], out_b[1])
+
+    def captured(fn, reps):
+        """``reps`` launches of fn as one hipGraph: a replay runs them back to back with no host enqueue between them."""
+        turn[0] = turn[1] = 0
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            for _ in range(reps):
+                fn()
+        graph.replay()
+        torch.cuda.synchronize()
+        return graph, reps
+
+    def replay_us(item):
+        graph, reps = item
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(); graph.replay(); b.record(); b.synchronize()
+        return a.elapsed_time(b) / reps * 1e3          # us per launch
+
+    ga, gb, gc = captured(gather, 4 * blocks), captured(build, 4 * blocks), captured(build_all, 4)
+    ta, tb, tc = [], [], []
+    for _ in range(rounds):
+        ta.append(replay_us(ga)); tb.append(replay_us(gb)); tc.append(replay_us(gc))
+    stat = lambda v: (sorted(v)[len(v) // 2], min(v), max(v))
+    (ma, la, ha), (mb, lb, hb), (mc, lc, hc) = stat(ta), stat(tb), stat(tc)
+    wb, wc = G * (U * U + C1), I * (U * U + C1)
+    print(f"user graphs, H={H} C={C} U={U}, {per_node:.2f} entries per node, gathered == built: {same}")
+    print(f"  (a) table gathers, G={G}: {ma:.1f} us [{la:.1f}, {ha:.1f}]  ({2 * wb / ma / 1e6:.2f} TB/s read + written)")
+    print(f"  (b) build with rows, G={G}: {mb:.1f} us [{lb:.1f}, {hb:.1f}]  ({wb / mb / 1e6:.2f} TB/s written)")
+    print(f"  (c) build over I={I}: {mc:.1f} us [{lc:.1f}, {hc:.1f}]  ({wc / mc / 1e6:.2f} TB/s written, {wc / 1e6:.0f} MB)")
+    print(f"  device memory of the table path: {I * (U * U + C1) / 1e6:.0f} MB; derived: 0 (the indices, {I * H * 8 / 1e6:.0f} MB, are needed either way)")
+
+
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "xattn"
     nums = [int(v) for v in sys.argv[2:]]
@@ -488,6 +565,8 @@ if __name__ == "__main__":
         bench_sag(*nums)
     elif what == "topic":
         bench_topic(*nums)
+    elif what == "user-graph":
+        bench_user_graph(*nums)
     elif what == "linear":
         bench_linear(*nums)
     elif what == "gemm":
