@@ -53,37 +53,34 @@ __global__ void __launch_bounds__(256) gat_alpha_kernel(const float* s1, const f
     if (lane + 64 < n) alpha[rho * n + lane + 64] = e1 / inv;
 }
 
+// inference workspace: h [B,n,d], the two node scores [B,n] each, alpha [B,n,n]
+struct GatWs { float *h, *s1, *s2, *alpha; };
+static GatWs gat_carve(Arena& w, int B, int n, int d) {
+    const size_t bn = (size_t)B * n;
+    return GatWs{w.take<float>(bn * d), w.take<float>(bn), w.take<float>(bn), w.take<float>(bn * n)};      // braces: taken left to right
+}
+
 extern "C" {
 
-size_t digat_gat_workspace_bytes(int B, int n, int d) {
-    return align_up((size_t)B * n * d * 4, 256) + 2 * align_up((size_t)B * n * 4, 256) + align_up((size_t)B * n * n * 4, 256);
-}
+size_t digat_gat_workspace_bytes(int B, int n, int d) { Arena a; gat_carve(a, B, n, d); return a.used; }
 
 int digat_gat_fwd(const float* X, const uint8_t* A, const float* W, const float* bW, const float* a1, const float* a2,
                   float* out, int B, int n, int d, void* workspace, size_t workspace_bytes, void* stream) {
     if (!X || !A || !W || !a1 || !a2 || !out || !workspace || B < 0 || n <= 0 || d <= 0) return DIGAT_ERR_ARG;
     if (d % 4 || n > DIGAT_MAX_NODES) return DIGAT_ERR_SHAPE;
-    if (workspace_bytes < digat_gat_workspace_bytes(B, n, d)) return DIGAT_ERR_WORKSPACE;
+    Arena w(workspace, workspace_bytes);
+    const GatWs o = gat_carve(w, B, n, d);
+    if (!w.ok) return DIGAT_ERR_WORKSPACE;
     if (B == 0) return DIGAT_OK;
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    float* h = (float*)ws;   ws += align_up((size_t)B * n * d * 4, 256);
-    float* s1 = (float*)ws;  ws += align_up((size_t)B * n * 4, 256);
-    float* s2 = (float*)ws;  ws += align_up((size_t)B * n * 4, 256);
-    float* alpha = (float*)ws;
-    int rc = launch_gemm(gemm_plain(X, d, W, bW, h, d, B * n, d, d, 0), st, DIGAT_KERNEL_PROJ);
+    int rc = launch_gemm(gemm_plain(X, d, W, bW, o.h, d, B * n, d, d, 0), st, DIGAT_KERNEL_PROJ);
     if (rc) return rc;
     const long nodes = (long)B * n;
-    hipLaunchKernelGGL(gat_node_scores_kernel, dim3((unsigned)((nodes + 3) / 4)), dim3(256), 0, st, (const float*)h, a1, a2, s1, s2, nodes, d / 4);
+    hipLaunchKernelGGL(gat_node_scores_kernel, dim3((unsigned)((nodes + 3) / 4)), dim3(256), 0, st, (const float*)o.h, a1, a2, o.s1, o.s2, nodes, d / 4);
     DIGAT_CHECK_LAUNCH();
-    hipLaunchKernelGGL(gat_alpha_kernel, dim3((unsigned)((nodes + 3) / 4)), dim3(256), 0, st, (const float*)s1, (const float*)s2, A, alpha, (float*)nullptr, nodes, n);
+    hipLaunchKernelGGL(gat_alpha_kernel, dim3((unsigned)((nodes + 3) / 4)), dim3(256), 0, st, (const float*)o.s1, (const float*)o.s2, A, o.alpha, (float*)nullptr, nodes, n);
     DIGAT_CHECK_LAUNCH();
-    AggArgs ag{alpha, h, X, out, B, n, d, (d + 63) / 64, n | 1, nullptr, nullptr, nullptr};
-    if (ag.groups > 16) return DIGAT_ERR_SHAPE;
-    if (ag.groups <= 8) hipLaunchKernelGGL(xattn_agg_kernel<512>, dim3(B), dim3(64 * ag.groups), (size_t)n * ag.sa * 4 + n, st, ag);
-        else hipLaunchKernelGGL(xattn_agg_kernel<1024>, dim3(B), dim3(64 * ag.groups), (size_t)n * ag.sa * 4 + n, st, ag);
-    DIGAT_CHECK_LAUNCH();
-    return DIGAT_OK;
+    return launch_agg(AggArgs{o.alpha, o.h, X, out, B, n, d, (d + 63) / 64, n | 1, nullptr, nullptr, nullptr}, st);
 }
 
 }  // extern "C"
@@ -119,25 +116,37 @@ __global__ void __launch_bounds__(256) gat_score_bwd_kernel(const GatScoreBwdArg
     }
 }
 
+// save: h, alpha (before dropout), the scores before leaky_relu / the mask, the attention dropout's keep bytes
+struct GatSave { float *h, *alpha, *s_pre; uint8_t* amask; };
+static GatSave gat_save_carve(Arena& a, int B, int n, int d) {
+    const size_t nn = (size_t)B * n * n;
+    return GatSave{a.take<float>((size_t)B * n * d), a.take<float>(nn), a.take<float>(nn), a.take<uint8_t>(nn)};
+}
+// forward workspace: the two node scores [B,n] each, alpha after dropout, split scratch
+struct GatFwdWs { float *s1, *s2, *adrop; void* wsplit; };
+static GatFwdWs gat_fwd_carve(Arena& w, int B, int n, int d) {
+    const size_t bn = (size_t)B * n;
+    return GatFwdWs{w.take<float>(bn), w.take<float>(bn), w.take<float>(bn * n), w.take<char>(wsplit_scratch(d))};
+}
+// backward workspace: dZ, dh [B,n,d], ds [B,n,n], the rows' [da1 | da2] partials [B,2d], dW scratch, split scratch
+struct GatBwdWs { float *dZ, *dh, *ds, *dap; void* wws; size_t wb; void* wsplit; };
+static GatBwdWs gat_bwd_carve(Arena& w, int B, int n, int d) {
+    const size_t nd = (size_t)B * n * d;
+    GatBwdWs o;
+    o.dZ = w.take<float>(nd); o.dh = w.take<float>(nd); o.ds = w.take<float>((size_t)B * n * n);
+    o.dap = w.take<float>((size_t)B * 2 * d);
+    o.wb = digat_linear_bwd_weight_workspace(B * n, d, d);
+    o.wws = w.take<char>(o.wb); o.wsplit = w.take<char>(wsplit_scratch(d));
+    return o;
+}
+
 extern "C" {
 
-size_t digat_gat_train_save_bytes(int B, int n, int d) {
-    return align_up((size_t)B * n * d * 4, 256) + 2 * align_up((size_t)B * n * n * 4, 256) + align_up((size_t)B * n * n, 256);
-}
-size_t digat_gat_train_workspace_bytes(int B, int n, int d) {
-    const size_t nd = align_up((size_t)B * n * d * 4, 256), nn = align_up((size_t)B * n * n * 4, 256);
-    const size_t fwd = 2 * align_up((size_t)B * n * 4, 256) + nn + align_up(wsplit_scratch(d), 256);
-    const size_t bwd = 2 * nd + nn + align_up((size_t)B * 2 * d * 4, 256) + align_up(digat_linear_bwd_weight_workspace(B * n, d, d), 256)
-                       + align_up(wsplit_scratch(d), 256);
-    return fwd > bwd ? fwd : bwd;
-}
-
-struct GatSave { float *h, *alpha, *s_pre; uint8_t* amask; };
-static bool gat_save_carve(void* save, size_t bytes, int B, int n, int d, GatSave* s) {
-    Arena a(save, bytes);
-    const size_t nn = (size_t)B * n * n;
-    s->h = a.take<float>((size_t)B * n * d); s->alpha = a.take<float>(nn); s->s_pre = a.take<float>(nn); s->amask = a.take<uint8_t>(nn);
-    return a.ok;
+size_t digat_gat_train_save_bytes(int B, int n, int d) { Arena a; gat_save_carve(a, B, n, d); return a.used; }
+size_t digat_gat_train_workspace_bytes(int B, int n, int d) {          // one buffer serves both directions
+    Arena fwd, bwd;
+    gat_fwd_carve(fwd, B, n, d); gat_bwd_carve(bwd, B, n, d);
+    return larger(fwd, bwd);
 }
 
 // X: the layer's input AFTER its input dropout (:495; the residual uses the dropped input, :501); out = relu(drop_p(alpha) h) + X
@@ -148,33 +157,24 @@ int digat_gat_fwd_train(const float* X, const uint8_t* A, const float* W, const 
     if (B < 0 || n <= 0 || d <= 0 || p_alpha < 0.f || p_alpha >= 1.f) return DIGAT_ERR_ARG;
     if (d % 4 || n > DIGAT_MAX_NODES) return DIGAT_ERR_SHAPE;
     if (B == 0) return DIGAT_OK;
-    GatSave s;
-    if (save_bytes < digat_gat_train_save_bytes(B, n, d) || !gat_save_carve(save, save_bytes, B, n, d, &s)) return DIGAT_ERR_WORKSPACE;
-    if (workspace_bytes < digat_gat_train_workspace_bytes(B, n, d)) return DIGAT_ERR_WORKSPACE;
-    Arena w(workspace, workspace_bytes);
-    float* s1 = w.take<float>((size_t)B * n); float* s2 = w.take<float>((size_t)B * n);
-    float* adrop = w.take<float>((size_t)B * n * n);
-    void* wsplit = w.take<char>(wsplit_scratch(d));
-    if (!w.ok) return DIGAT_ERR_WORKSPACE;
+    Arena sa(save, save_bytes), w(workspace, workspace_bytes);
+    const GatSave s = gat_save_carve(sa, B, n, d);
+    if (!sa.ok || workspace_bytes < digat_gat_train_workspace_bytes(B, n, d)) return DIGAT_ERR_WORKSPACE;
+    const GatFwdWs o = gat_fwd_carve(w, B, n, d);
     hipStream_t st = (hipStream_t)stream;
     const long nodes = (long)B * n;
-    T_TRY(t_linear_fwd(X, d, W, bW, s.h, (int)nodes, d, d, wsplit, st));
-    hipLaunchKernelGGL(gat_node_scores_kernel, dim3((unsigned)((nodes + 3) / 4)), dim3(256), 0, st, (const float*)s.h, a1, a2, s1, s2, nodes, d / 4);
+    T_TRY(t_linear_fwd(X, d, W, bW, s.h, (int)nodes, d, d, o.wsplit, st));
+    hipLaunchKernelGGL(gat_node_scores_kernel, dim3((unsigned)((nodes + 3) / 4)), dim3(256), 0, st, (const float*)s.h, a1, a2, o.s1, o.s2, nodes, d / 4);
     DIGAT_CHECK_LAUNCH();
-    hipLaunchKernelGGL(gat_alpha_kernel, dim3((unsigned)((nodes + 3) / 4)), dim3(256), 0, st, (const float*)s1, (const float*)s2, A, s.alpha,
+    hipLaunchKernelGGL(gat_alpha_kernel, dim3((unsigned)((nodes + 3) / 4)), dim3(256), 0, st, (const float*)o.s1, (const float*)o.s2, A, s.alpha,
                        s.s_pre, nodes, n);
     DIGAT_CHECK_LAUNCH();
     const float* aggalpha = s.alpha;
     if (p_alpha > 0.f) {
-        T_TRY(digat_dropout_fwd(s.alpha, adrop, s.amask, (int64_t)B * n * n, p_alpha, seed, stream));
-        aggalpha = adrop;
+        T_TRY(digat_dropout_fwd(s.alpha, o.adrop, s.amask, (int64_t)B * n * n, p_alpha, seed, stream));
+        aggalpha = o.adrop;
     }
-    AggArgs ag{aggalpha, s.h, X, out, B, n, d, (d + 63) / 64, n | 1, nullptr, nullptr, nullptr};
-    if (ag.groups > 16) return DIGAT_ERR_SHAPE;
-    if (ag.groups <= 8) hipLaunchKernelGGL(xattn_agg_kernel<512>, dim3(B), dim3(64 * ag.groups), (size_t)n * ag.sa * 4 + n, st, ag);
-        else hipLaunchKernelGGL(xattn_agg_kernel<1024>, dim3(B), dim3(64 * ag.groups), (size_t)n * ag.sa * 4 + n, st, ag);
-    DIGAT_CHECK_LAUNCH();
-    return DIGAT_OK;
+    return launch_agg(AggArgs{aggalpha, s.h, X, out, B, n, d, (d + 63) / 64, n | 1, nullptr, nullptr, nullptr}, st);
 }
 
 // dX [B,n,d], dW [d,d], dbW [d], da1 da2 [d]: all written (not accumulated)
@@ -185,46 +185,22 @@ int digat_gat_bwd(const float* dOut, const float* out, const float* X, const uin
     if (B < 0 || n <= 0 || d <= 0) return DIGAT_ERR_ARG;
     if (d % 4 || n > DIGAT_MAX_NODES) return DIGAT_ERR_SHAPE;
     hipStream_t st = (hipStream_t)stream;
-    if (B == 0) {
-        if (hipMemsetAsync(dW, 0, (size_t)d * d * 4, st) != hipSuccess || hipMemsetAsync(dbW, 0, (size_t)d * 4, st) != hipSuccess ||
-            hipMemsetAsync(da1, 0, (size_t)d * 4, st) != hipSuccess || hipMemsetAsync(da2, 0, (size_t)d * 4, st) != hipSuccess)
-            return DIGAT_ERR_LAUNCH;
-        return DIGAT_OK;
-    }
-    GatSave s;
-    if (save_bytes < digat_gat_train_save_bytes(B, n, d) || !gat_save_carve(const_cast<void*>(save), save_bytes, B, n, d, &s))
-        return DIGAT_ERR_WORKSPACE;
-    if (workspace_bytes < digat_gat_train_workspace_bytes(B, n, d)) return DIGAT_ERR_WORKSPACE;
-    Arena w(workspace, workspace_bytes);
+    if (B == 0) return zero_floats(st, {{dW, (size_t)d * d}, {dbW, (size_t)d}, {da1, (size_t)d}, {da2, (size_t)d}});
+    Arena sa(const_cast<void*>(save), save_bytes), w(workspace, workspace_bytes);
+    const GatSave s = gat_save_carve(sa, B, n, d);
+    if (!sa.ok || workspace_bytes < digat_gat_train_workspace_bytes(B, n, d)) return DIGAT_ERR_WORKSPACE;
+    const GatBwdWs o = gat_bwd_carve(w, B, n, d);
+    float *dZ = o.dZ, *dh = o.dh, *dap = o.dap;
     const size_t nd = (size_t)B * n * d;
-    float* dZ = w.take<float>(nd); float* dh = w.take<float>(nd); float* ds = w.take<float>((size_t)B * n * n);
-    float* dap = w.take<float>((size_t)B * 2 * d);
-    const size_t wb = digat_linear_bwd_weight_workspace(B * n, d, d);
-    void* wws = w.take<char>(wb); void* wsplit = w.take<char>(wsplit_scratch(d));
-    if (!w.ok) return DIGAT_ERR_WORKSPACE;
     hipLaunchKernelGGL(relu_res_mask_kernel, dim3(grid_for((long)nd)), dim3(256), 0, st, dOut, out, X, dZ, (long)nd);
     DIGAT_CHECK_LAUNCH();
     const float ascale = p_alpha > 0.f ? 1.f / (1.f - p_alpha) : 1.f;
     const uint8_t* am = p_alpha > 0.f ? s.amask : nullptr;
-    {   // dh = alpha'^T dZ
-        AggTArgs t{s.alpha, am, ascale, dZ, dh, B, n, d, (long)d};
-        const size_t lds = (size_t)n * n * 4 + (((size_t)n * n + 3) & ~(size_t)3) + (size_t)n * 4;
-        if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)xattn_aggT_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   160 * 1024) != hipSuccess) return DIGAT_ERR_LAUNCH;
-        hipLaunchKernelGGL(xattn_aggT_kernel, dim3(B), dim3(256), lds, st, t);
-        DIGAT_CHECK_LAUNCH();
-    }
-    {   // ds: dalpha' = dZ h^T through (dropout,) softmax, mask, leaky_relu'
-        DsArgs t{dZ, s.h, s.alpha, s.s_pre, A, am, ascale, ds, B, n, d};
-        const int n16 = (n + 15) / 16 * 16;
-        const size_t lds = ((size_t)2 * n16 * (DS_CH + 1) + (size_t)n * n) * 4;
-        if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)xattn_ds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   160 * 1024) != hipSuccess) return DIGAT_ERR_LAUNCH;
-        hipLaunchKernelGGL(xattn_ds_kernel, dim3(B), dim3(256), lds, st, t);
-        DIGAT_CHECK_LAUNCH();
-    }
+    T_TRY(launch_aggT(AggTArgs{s.alpha, am, ascale, dZ, dh, B, n, d, (long)d}, st));                 // dh = alpha'^T dZ
+    // ds: dalpha' = dZ h^T through (dropout,) softmax, mask, leaky_relu'
+    T_TRY(launch_ds(DsArgs{dZ, s.h, s.alpha, s.s_pre, A, am, ascale, o.ds, B, n, d}, st));
     {   // the separable score: dh += du a1 + dv a2; da1, da2 partials
-        GatScoreBwdArgs t{ds, s.h, a1, a2, dh, dap, B, n, d};
+        GatScoreBwdArgs t{o.ds, s.h, a1, a2, dh, dap, B, n, d};
         hipLaunchKernelGGL(gat_score_bwd_kernel, dim3(B), dim3(256), 0, st, t);
         DIGAT_CHECK_LAUNCH();
     }
@@ -234,8 +210,8 @@ int digat_gat_bwd(const float* dOut, const float* out, const float* X, const uin
     DIGAT_CHECK_LAUNCH();
     const int M = B * n;
     if (hipMemcpyAsync(dX, dOut, nd * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return DIGAT_ERR_LAUNCH;      // the residual
-    T_TRY(t_linear_bwd_input(dh, W, dX, M, d, d, 1, wsplit, st));
-    return t_linear_bwd_weight(dh, X, d, dW, dbW, M, d, d, wws, wb, st);
+    T_TRY(t_linear_bwd_input(dh, W, dX, M, d, d, 1, o.wsplit, st));
+    return t_linear_bwd_weight(dh, X, d, dW, dbW, M, d, d, o.wws, o.wb, st);
 }
 
 }  // extern "C"

@@ -59,6 +59,15 @@ struct Arena {
         return r;
     }
 };
+// the size of a buffer that two carves share (a training pair's workspace: the forward's layout or the backward's); an entry that
+// has held its buffer to that size carves either layout without a further check
+static inline size_t larger(const Arena& a, const Arena& b) { return a.used > b.used ? a.used : b.used; }
+// {pointer, floats} pairs zero-filled on the stream: the gradients of a backward call over an empty batch
+static int zero_floats(hipStream_t st, std::initializer_list<std::pair<float*, size_t>> bufs) {
+    for (const auto& b : bufs)
+        if (hipMemsetAsync(b.first, 0, b.second * 4, st) != hipSuccess) return DIGAT_ERR_LAUNCH;
+    return DIGAT_OK;
+}
 
 // ---- optional per-kernel event timing (bench.py's roofline leg) ---------------------------------
 // Between digat_profile_start and digat_profile_stop every launch is bracketed by two hipEvents

@@ -427,13 +427,6 @@ __global__ void __launch_bounds__(256) msa_row_dropout_bwd_kernel(const MsaRowDr
     }
 }
 
-// {pointer, floats} pairs zero-filled on the stream: the gradients of a call without titles
-static int zero_floats(hipStream_t st, std::initializer_list<std::pair<float*, size_t>> bufs) {
-    for (const auto& b : bufs)
-        if (hipMemsetAsync(b.first, 0, b.second * 4, st) != hipSuccess) return DIGAT_ERR_LAUNCH;
-    return DIGAT_OK;
-}
-
 extern "C" {
 
 // table_grad [V, dm] must be zero-filled by the caller (rows of tokens that do not occur stay zero).

@@ -329,13 +329,8 @@ __global__ void __launch_bounds__(256) colsum_groups_kernel(const float* x, long
 
 // out[c] = sum_m x[m][c] in two ordered stages (groups of 32 rows, then the groups): ~8x the workgroups of colsum_kernel alone,
 // whose four waves per 64 columns walk all M rows (21 us at M = 320)
-static size_t colsum2_scratch(int M, int N) { return (size_t)((M + 31) / 32) * N * 4; }
-// the same, run only when (*flag != 0) == (want != 0) (the device chose between two producers of the partial rows)
-static int launch_colsum2_if(const float* x, long ldx, float* out, int M, int N, int accumulate, float* scratch, hipStream_t st,
-                             const int* flag, int want);
-static int launch_colsum2(const float* x, long ldx, float* out, int M, int N, int accumulate, float* scratch, hipStream_t st) {
-    return launch_colsum2_if(x, ldx, out, M, N, accumulate, scratch, st, nullptr, 0);
-}
+static size_t colsum2_scratch(int M, int N) { return (size_t)((M + 31) / 32) * N; }      // floats
+// flag != NULL: run only when (*flag != 0) == (want != 0) (the device chose between two producers of the partial rows)
 static int launch_colsum2_if(const float* x, long ldx, float* out, int M, int N, int accumulate, float* scratch, hipStream_t st,
                              const int* flag, int want) {
     const int per = 32, G = (M + per - 1) / per;
@@ -348,6 +343,9 @@ static int launch_colsum2_if(const float* x, long ldx, float* out, int M, int N,
         hipLaunchKernelGGL(colsum_kernel, dim3((N + 63) / 64), dim3(256), 0, st, (const float*)scratch, (long)N, out, G, N, accumulate, flag, want);
     }
     return hipGetLastError() == hipSuccess ? DIGAT_OK : DIGAT_ERR_LAUNCH;
+}
+static int launch_colsum2(const float* x, long ldx, float* out, int M, int N, int accumulate, float* scratch, hipStream_t st) {
+    return launch_colsum2_if(x, ldx, out, M, N, accumulate, scratch, st, nullptr, 0);
 }
 
 // =================================================================================================
@@ -751,6 +749,16 @@ __global__ void __launch_bounds__(256) xattn_ds_kernel(const DsArgs g) {
         g.ds[(long)b * n * n + e] = de * (sp > 0.f ? 1.f : 0.2f);
     }
 }
+// every launch of it: the two [n16][33] chunk images and the row's n x n block in dynamic LDS, opted in above 64 KB
+static int launch_ds(const DsArgs& t, hipStream_t st) {
+    const int n16 = (t.n + 15) / 16 * 16;
+    const size_t lds = ((size_t)2 * n16 * (DS_CH + 1) + (size_t)t.n * t.n) * 4;
+    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)xattn_ds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               160 * 1024) != hipSuccess) return DIGAT_ERR_LAUNCH;
+    hipLaunchKernelGGL(xattn_ds_kernel, dim3(t.B), dim3(256), lds, st, t);
+    DIGAT_CHECK_LAUNCH();
+    return DIGAT_OK;
+}
 
 // (b) pairwise backward: with x_ijc = P'_jc + Q_ic (recomputed), g_ijc = ds_ij a_c [x_ijc > 0]:
 //     dQ_ic = sum_j g_ijc ; dP'_jc = sum_i g_ijc ; da_c += sum_ij ds_ij relu(x_ijc)
@@ -908,6 +916,15 @@ __global__ void __launch_bounds__(256) xattn_aggT_kernel(const AggTArgs g) {
         }
         reinterpret_cast<float4*>(g.dh + ((long)b * n + j) * g.ldh)[c4] = acc;
     }
+}
+// every launch of it: alpha' [n][n], the column lists [n][n] bytes and their counts [n] in dynamic LDS, opted in above 64 KB
+static int launch_aggT(const AggTArgs& t, hipStream_t st) {
+    const size_t lds = (size_t)t.n * t.n * 4 + (((size_t)t.n * t.n + 3) & ~(size_t)3) + (size_t)t.n * 4;
+    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)xattn_aggT_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               160 * 1024) != hipSuccess) return DIGAT_ERR_LAUNCH;
+    hipLaunchKernelGGL(xattn_aggT_kernel, dim3(t.B), dim3(256), lds, st, t);
+    DIGAT_CHECK_LAUNCH();
+    return DIGAT_OK;
 }
 
 // (d) the same backward OVER THE ADJACENCY'S ENTRIES (round 6): the three launches above visit all n^2 pairs of a row (dalpha' on the
@@ -1346,9 +1363,6 @@ static int tn_slices(int M, int No, int Ni) {
 }
 // The same on the bf16 matrix cores (bf16x6, fp32-grade): W^T is split into `wsplit` (digat_split_weights_bytes(K, N)
 // bytes, rewritten by every call: the weights change every optimiser step).  M >= 2048, K % 80 == 0, N % 8 == 0, N >= 32.
-static int linear_bwd_input_x3_add(const float* dy, int64_t lddy, const float* w, float* dx, int64_t lddx, const float* addend,
-                                   int M, int N, int K, void* wsplit, void* stream, const float* w1, const float* w2, const uint8_t* dmask,
-                                   float dscale);
 int digat_linear_bwd_input_x3(const float* dy, int64_t lddy, const float* w, float* dx, int64_t lddx,
                               int M, int N, int K, int accumulate, void* wsplit, void* stream) {
     if (!dy || !w || !dx || !wsplit || M < 0 || N <= 0 || K <= 0) return DIGAT_ERR_ARG;
@@ -1383,43 +1397,45 @@ static int linear_bwd_input_x3_add(const float* dy, int64_t lddy, const float* w
 size_t digat_linear_bwd_weight_workspace(int M, int No, int Ni) {
     return (size_t)tn_slices(M, No, Ni) * ((size_t)No * Ni + No) * 4;
 }
-// dW[No,Ni] (+)= dy[M,No]^T @ x[M,Ni] ;  db[No] (+)= colsum(dy)  (db may be NULL)
-static int linear_bwd_weight_dbn(const float* dy, int64_t lddy, const float* x, int64_t ldx, float* dW, float* db, int db_cols,
-                                 int M, int No, int Ni, int accumulate, void* workspace, size_t workspace_bytes, void* stream);
-int digat_linear_bwd_weight(const float* dy, int64_t lddy, const float* x, int64_t ldx, float* dW, float* db,
-                            int M, int No, int Ni, int accumulate, void* workspace, size_t workspace_bytes, void* stream) {
-    return linear_bwd_weight_dbn(dy, lddy, x, ldx, dW, db, No, M, No, Ni, accumulate, workspace, workspace_bytes, stream);
+// the product's launch arguments over `workspace`: M in tn_slices slices of whole 32-row steps, the slices' partial dW [slices][No, Ni]
+// and, when the column sums are wanted, their partial db [slices][No] behind them; 16-byte loads where strides and addresses allow
+static TnArgs tn_args(const float* dy, int64_t lddy, const float* x, int64_t ldx, bool want_db, int M, int No, int Ni, void* workspace) {
+    const int slices = tn_slices(M, No, Ni);
+    const int mper = ((M + slices - 1) / slices + 31) / 32 * 32;
+    float* part = (float*)workspace;
+    float* part_db = want_db ? part + (size_t)slices * No * Ni : nullptr;
+    const int vec = (lddy % 4 == 0 && ldx % 4 == 0 && No % 4 == 0 && Ni % 4 == 0 &&
+                     ((uintptr_t)dy & 15) == 0 && ((uintptr_t)x & 15) == 0) ? 1 : 0;
+    return TnArgs{dy, lddy, x, ldx, part, part_db, M, No, Ni, slices, mper > 0 ? mper : 32, vec};
 }
-// db_cols <= No: only the leading db_cols column sums are wanted (db [db_cols])
+// dW[No,Ni] (+)= dy[M,No]^T @ x[M,Ni] ;  db (+)= the leading db_cols <= No column sums of dy (db [db_cols], may be NULL)
 static int linear_bwd_weight_dbn(const float* dy, int64_t lddy, const float* x, int64_t ldx, float* dW, float* db, int db_cols,
                                  int M, int No, int Ni, int accumulate, void* workspace, size_t workspace_bytes, void* stream) {
     if (!dy || !x || !dW || !workspace || M < 0 || No <= 0 || Ni <= 0 || db_cols < 0 || db_cols > No) return DIGAT_ERR_ARG;
     if (workspace_bytes < digat_linear_bwd_weight_workspace(M, No, Ni)) return DIGAT_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    const int slices = tn_slices(M, No, Ni);
-    const int mper = ((M + slices - 1) / slices + 31) / 32 * 32;
-    float* part = (float*)workspace;
-    float* part_db = db ? part + (size_t)slices * No * Ni : nullptr;
-    const int vec = (lddy % 4 == 0 && ldx % 4 == 0 && No % 4 == 0 && Ni % 4 == 0 &&
-                     ((uintptr_t)dy & 15) == 0 && ((uintptr_t)x & 15) == 0) ? 1 : 0;
-    TnArgs t{dy, lddy, x, ldx, part, part_db, M, No, Ni, slices, mper > 0 ? mper : 32, vec};
+    const TnArgs t = tn_args(dy, lddy, x, ldx, db != nullptr, M, No, Ni, workspace);
     // the weight-gradient product as an MFMA launch of the step (bench.py's train-step roofline): 2 M No Ni flops, both operands in, dW out
     ProfScope prof(DIGAT_KERNEL_LINEAR, 2.0 * M * (double)No * Ni, st, 4.0 * ((double)M * (No + Ni) + (double)No * Ni));
-    if (tn_bf16x6_ok(M, vec)) {
+    if (tn_bf16x6_ok(M, t.vec)) {
         const int tiles = ((No + TNB - 1) / TNB) * ((Ni + TNB - 1) / TNB);
-        if (g_train_bf16) hipLaunchKernelGGL(gemm_tn_bf16x6_kernel<true>, dim3(tiles, slices), dim3(256), 0, st, t);
-        else hipLaunchKernelGGL(gemm_tn_bf16x6_kernel<false>, dim3(tiles, slices), dim3(256), 0, st, t);
+        if (g_train_bf16) hipLaunchKernelGGL(gemm_tn_bf16x6_kernel<true>, dim3(tiles, t.slices), dim3(256), 0, st, t);
+        else hipLaunchKernelGGL(gemm_tn_bf16x6_kernel<false>, dim3(tiles, t.slices), dim3(256), 0, st, t);
     } else {
         const int tiles = ((No + 79) / 80) * ((Ni + 79) / 80);
-        hipLaunchKernelGGL(gemm_tn_kernel, dim3(tiles, slices), dim3(256), 0, st, t);
+        hipLaunchKernelGGL(gemm_tn_kernel, dim3(tiles, t.slices), dim3(256), 0, st, t);
     }
     DIGAT_CHECK_LAUNCH();
     const long nel = (long)No * Ni;
-    if (db) hipLaunchKernelGGL(slice_reduce2_kernel, dim3(grid_for(nel + db_cols)), dim3(256), 0, st, (const float*)part, dW, nel,
-                               (const float*)part_db, db, (long)db_cols, (long)No, slices, accumulate);
-    else hipLaunchKernelGGL(slice_reduce_kernel, dim3(grid_for(nel)), dim3(256), 0, st, (const float*)part, dW, nel, slices, accumulate);
+    if (db) hipLaunchKernelGGL(slice_reduce2_kernel, dim3(grid_for(nel + db_cols)), dim3(256), 0, st, (const float*)t.part, dW, nel,
+                               (const float*)t.part_db, db, (long)db_cols, (long)No, t.slices, accumulate);
+    else hipLaunchKernelGGL(slice_reduce_kernel, dim3(grid_for(nel)), dim3(256), 0, st, (const float*)t.part, dW, nel, t.slices, accumulate);
     DIGAT_CHECK_LAUNCH();
     return DIGAT_OK;
+}
+int digat_linear_bwd_weight(const float* dy, int64_t lddy, const float* x, int64_t ldx, float* dW, float* db,
+                            int M, int No, int Ni, int accumulate, void* workspace, size_t workspace_bytes, void* stream) {
+    return linear_bwd_weight_dbn(dy, lddy, x, ldx, dW, db, No, M, No, Ni, accumulate, workspace, workspace_bytes, stream);
 }
 
 // collects the short products of one backward entry; flush() issues them as one product launch + one reduction launch.  A product
@@ -1433,18 +1449,14 @@ struct TnGroup {
         if (!dy || !x || !dW || M < 0 || No <= 0 || Ni <= 0) return DIGAT_ERR_ARG;
         const size_t need = align_up(digat_linear_bwd_weight_workspace(M, No, Ni), 256);
         if (need > left) return DIGAT_ERR_WORKSPACE;
-        const int vec = (lddy % 4 == 0 && ldx % 4 == 0 && No % 4 == 0 && Ni % 4 == 0 && ((uintptr_t)dy & 15) == 0 && ((uintptr_t)x & 15) == 0) ? 1 : 0;
-        if (tn_bf16x6_ok(M, vec)) return digat_linear_bwd_weight(dy, lddy, x, ldx, dW, db, M, No, Ni, accumulate, ws, left, st);
+        const TnArgs t = tn_args(dy, lddy, x, ldx, db != nullptr, M, No, Ni, ws);
+        if (tn_bf16x6_ok(M, t.vec)) return digat_linear_bwd_weight(dy, lddy, x, ldx, dW, db, M, No, Ni, accumulate, ws, left, st);
         if (n == TN_GROUP_MAX) { const int rc = flush(); if (rc) return rc; }
-        const int slices = tn_slices(M, No, Ni);
-        const int mper = ((M + slices - 1) / slices + 31) / 32 * 32;
-        float* part = (float*)ws;
-        float* part_db = db ? part + (size_t)slices * No * Ni : nullptr;
         ws += need; left -= need;
-        a.p[n] = TnArgs{dy, lddy, x, ldx, part, part_db, M, No, Ni, slices, mper > 0 ? mper : 32, vec};
+        a.p[n] = t;
         a.tiles[n] = ((No + 79) / 80) * ((Ni + 79) / 80);
-        r.part[n] = part; r.out[n] = dW; r.n[n] = (long)No * Ni; r.part_b[n] = part_db; r.out_b[n] = db; r.nb[n] = db ? No : 0;
-        r.slices[n] = slices; r.accumulate[n] = accumulate;
+        r.part[n] = t.part; r.out[n] = dW; r.n[n] = (long)No * Ni; r.part_b[n] = t.part_db; r.out_b[n] = db; r.nb[n] = db ? No : 0;
+        r.slices[n] = t.slices; r.accumulate[n] = accumulate;
         flops += 2.0 * M * (double)No * Ni; bytes += 4.0 * ((double)M * (No + Ni) + (double)No * Ni);
         ++n;
         return DIGAT_OK;
@@ -1525,16 +1537,10 @@ int digat_relu_mask(const float* dout, const float* y, float* dy, int64_t n, voi
 
 // ---- pooling ------------------------------------------------------------------------------------------
 // forward that also returns the attention weights (needed by the backward)
-static int attn_pool_fwd_ld(const float* feat, int64_t ld_b, const float* kq, const uint8_t* mask, float* out, long ld_out, float* node0,
-                            long ld_node0, float* alpha_out, int B, int n, int d, void* stream, const float* addend = nullptr);
-int digat_attn_pool_fwd(const float* feat, int64_t ld_b, const float* kq, const uint8_t* mask, float* out, float* alpha_out,
-                        int B, int n, int d, void* stream) {
-    return attn_pool_fwd_ld(feat, ld_b, kq, mask, out, 0, nullptr, 0, alpha_out, B, n, d, stream);
-}
 // out rows of stride ld_out (0: d); node0 != NULL: node 0 of every row is copied there too (rows of stride ld_node0) — the news
 // context's [l ; g] rows are written by the pooling launch itself
 static int attn_pool_fwd_ld(const float* feat, int64_t ld_b, const float* kq, const uint8_t* mask, float* out, long ld_out, float* node0,
-                            long ld_node0, float* alpha_out, int B, int n, int d, void* stream, const float* addend) {
+                            long ld_node0, float* alpha_out, int B, int n, int d, void* stream, const float* addend = nullptr) {
     if (!feat || !kq || !mask || !out) return DIGAT_ERR_ARG;
     if (n > DIGAT_MAX_NODES || d % 4 || ld_out % 4 || ld_node0 % 4) return DIGAT_ERR_SHAPE;
     if (B == 0) return DIGAT_OK;
@@ -1543,13 +1549,9 @@ static int attn_pool_fwd_ld(const float* feat, int64_t ld_b, const float* kq, co
     DIGAT_CHECK_LAUNCH();
     return DIGAT_OK;
 }
-static int attn_pool_bwd_ld(const float* feat, int64_t ld_b, const float* kq, const uint8_t* mask, const float* alpha,
-                            const float* dout, long ld_dout, float* dfeat, int64_t ldd_b, float* dkq, int B, int n, int d,
-                            int accumulate_dfeat, void* stream);
-int digat_attn_pool_bwd(const float* feat, int64_t ld_b, const float* kq, const uint8_t* mask, const float* alpha,
-                        const float* dout, float* dfeat, int64_t ldd_b, float* dkq, int B, int n, int d,
-                        int accumulate_dfeat, void* stream) {
-    return attn_pool_bwd_ld(feat, ld_b, kq, mask, alpha, dout, 0, dfeat, ldd_b, dkq, B, n, d, accumulate_dfeat, stream);
+int digat_attn_pool_fwd(const float* feat, int64_t ld_b, const float* kq, const uint8_t* mask, float* out, float* alpha_out,
+                        int B, int n, int d, void* stream) {
+    return attn_pool_fwd_ld(feat, ld_b, kq, mask, out, 0, nullptr, 0, alpha_out, B, n, d, stream);
 }
 static int attn_pool_bwd_ld(const float* feat, int64_t ld_b, const float* kq, const uint8_t* mask, const float* alpha,
                             const float* dout, long ld_dout, float* dfeat, int64_t ldd_b, float* dkq, int B, int n, int d,
@@ -1561,6 +1563,11 @@ static int attn_pool_bwd_ld(const float* feat, int64_t ld_b, const float* kq, co
     hipLaunchKernelGGL(attn_pool_bwd_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, g);
     DIGAT_CHECK_LAUNCH();
     return DIGAT_OK;
+}
+int digat_attn_pool_bwd(const float* feat, int64_t ld_b, const float* kq, const uint8_t* mask, const float* alpha,
+                        const float* dout, float* dfeat, int64_t ldd_b, float* dkq, int B, int n, int d,
+                        int accumulate_dfeat, void* stream) {
+    return attn_pool_bwd_ld(feat, ld_b, kq, mask, alpha, dout, 0, dfeat, ldd_b, dkq, B, n, d, accumulate_dfeat, stream);
 }
 int digat_topic_pool_fwd_train(const float* Xu, const float* kq, const int64_t* cat_idx, float* out, float* alpha_out,
                                int B, int U, int H, int C1, int d, void* stream) {
@@ -1595,15 +1602,6 @@ int digat_topic_pool_bwd(const float* Xu, const float* kq, const int64_t* cat_id
 // training forward of the pairwise part: like digat_xattn_pairwise_fwd but keeps what the backward needs:
 // alpha [B,n,n] (before dropout), s_pre [B,n,n] (scores before leaky_relu/mask), and applies the attention
 // dropout (amask [B,n,n] written; p = 0 -> no dropout, amask may be NULL).
-static int xattn_pairwise_fwd_train_flag(const float* Pr, const float* Q, const float* h, const float* X, const float* a,
-                                        const uint8_t* A, float* out, float* alpha, float* s_pre, float* alpha_drop,
-                                        uint8_t* amask, float p, uint32_t seed, int B, int n, int d, int* sparse_flag, void* stream,
-                                        int mode = 0);
-int digat_xattn_pairwise_fwd_train(const float* Pr, const float* Q, const float* h, const float* X, const float* a,
-                                   const uint8_t* A, float* out, float* alpha, float* s_pre, float* alpha_drop,
-                                   uint8_t* amask, float p, uint32_t seed, int B, int n, int d, void* stream) {
-    return xattn_pairwise_fwd_train_flag(Pr, Q, h, X, a, A, out, alpha, s_pre, alpha_drop, amask, p, seed, B, n, d, nullptr, stream);
-}
 // sparse_flag != NULL (a device int of the caller's scratch): graphs of more than 16 nodes take the wave-per-centre kernel when a
 // sample of the batch's adjacency is sparse (decided on the device: the dense pair then returns at once, and vice versa).
 // mode (DIGAT_TRAIN_XATTN_*): 0 = that device-side choice; 1 = the entry-wise kernel, 2 = the all-pairs pair, unguarded — a caller
@@ -1611,7 +1609,8 @@ int digat_xattn_pairwise_fwd_train(const float* Pr, const float* Q, const float*
 // The choice is one of speed only: both sides compute the same function.
 static int xattn_pairwise_fwd_train_flag(const float* Pr, const float* Q, const float* h, const float* X, const float* a,
                                         const uint8_t* A, float* out, float* alpha, float* s_pre, float* alpha_drop,
-                                        uint8_t* amask, float p, uint32_t seed, int B, int n, int d, int* sparse_flag, void* stream, int mode) {
+                                        uint8_t* amask, float p, uint32_t seed, int B, int n, int d, int* sparse_flag, void* stream,
+                                        int mode = 0) {
     if (!Pr || !Q || !h || !X || !a || !A || !out || !alpha || !s_pre) return DIGAT_ERR_ARG;
     if (p > 0.f && (!alpha_drop || !amask)) return DIGAT_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -1641,52 +1640,44 @@ static int xattn_pairwise_fwd_train_flag(const float* Pr, const float* Q, const 
     rc = launch_score(pl, st);
     if (rc || small) return rc;
     const float* aggalpha = p > 0.f ? alpha_drop : alpha;
-    AggArgs ag{aggalpha, h, X, out, B, n, d, (d + 63) / 64, n | 1, nullptr, nullptr, guarded ? sparse_flag : nullptr};
-    if (ag.groups > 16) return DIGAT_ERR_SHAPE;
-    if (ag.groups <= 8) hipLaunchKernelGGL(xattn_agg_kernel<512>, dim3(B), dim3(64 * ag.groups), (size_t)n * ag.sa * 4 + n, st, ag);
-        else hipLaunchKernelGGL(xattn_agg_kernel<1024>, dim3(B), dim3(64 * ag.groups), (size_t)n * ag.sa * 4 + n, st, ag);
-    DIGAT_CHECK_LAUNCH();
-    return DIGAT_OK;
+    return launch_agg(AggArgs{aggalpha, h, X, out, B, n, d, (d + 63) / 64, n | 1, nullptr, nullptr, guarded ? sparse_flag : nullptr}, st);
+}
+int digat_xattn_pairwise_fwd_train(const float* Pr, const float* Q, const float* h, const float* X, const float* a,
+                                   const uint8_t* A, float* out, float* alpha, float* s_pre, float* alpha_drop,
+                                   uint8_t* amask, float p, uint32_t seed, int B, int n, int d, void* stream) {
+    return xattn_pairwise_fwd_train_flag(Pr, Q, h, X, a, A, out, alpha, s_pre, alpha_drop, amask, p, seed, B, n, d, nullptr, stream);
 }
 
+// the pairwise backward's scratch.  All-pairs launches: dZ [B,n,d], ds [B,n,n], the rows' da partials [B,d] and their group sums;
+// entry-wise kernels: the (alpha', ds) pairs [B,n,n], a row of da per workgroup and the group sums of those rows
 static long spb_blocks(int B, int n) { return ((long)B * n + 3) / 4; }
-size_t digat_xattn_pairwise_bwd_workspace(int B, int n, int d) {
-    // dZ [B,n,d] + ds [B,n,n] + da partials [B,d] + their group sums; the entry-wise kernels: the (alpha', ds) pairs [B,n,n], a row
-    // of da per workgroup and the group sums of those rows
-    return align_up((size_t)B * n * d * 4, 256) + align_up((size_t)B * n * n * 4, 256) + align_up((size_t)B * d * 4, 256)
-           + align_up(colsum2_scratch(B, d), 256) + align_up((size_t)B * n * n * 8, 256) + align_up((size_t)spb_blocks(B, n) * d * 4, 256)
-           + align_up(colsum2_scratch((int)spb_blocks(B, n), d), 256);
+struct PairBwdWs { float *dZ, *ds, *dap, *dag; float2* wds; float *dap2, *dag2; };
+static PairBwdWs pair_bwd_carve(Arena& w, int B, int n, int d) {
+    const size_t nn = (size_t)B * n * n;
+    const long nblk = spb_blocks(B, n);
+    PairBwdWs o;
+    o.dZ = w.take<float>((size_t)B * n * d); o.ds = w.take<float>(nn);
+    o.dap = w.take<float>((size_t)B * d); o.dag = w.take<float>(colsum2_scratch(B, d));
+    o.wds = w.take<float2>(nn);
+    o.dap2 = w.take<float>((size_t)nblk * d); o.dag2 = w.take<float>(colsum2_scratch((int)nblk, d));
+    return o;
 }
+size_t digat_xattn_pairwise_bwd_workspace(int B, int n, int d) { Arena a; pair_bwd_carve(a, B, n, d); return a.used; }
 // given dOut [B,n,d]: dPr, dQ, dh [B,n,d], da [d] (accumulated if accumulate_da), dXres [B,n,d] = dOut (caller adds)
-static int xattn_pairwise_bwd_ld(const float* dOut, const float* out, const float* Xres, const float* Pr, const float* Q,
-                                 const float* h, const float* a, const uint8_t* A, const float* alpha, const float* s_pre,
-                                 const uint8_t* amask, float p, float* dPr, float* dQ, float* dh, long ldg, float* da, int accumulate_da,
-                                 int B, int n, int d, void* workspace, size_t workspace_bytes, void* stream, float* dr = nullptr,
-                                 const int* sparse_flag = nullptr, int mode = 0);
-int digat_xattn_pairwise_bwd(const float* dOut, const float* out, const float* Xres, const float* Pr, const float* Q,
-                             const float* h, const float* a, const uint8_t* A, const float* alpha, const float* s_pre,
-                             const uint8_t* amask, float p, float* dPr, float* dQ, float* dh, float* da, int accumulate_da,
-                             int B, int n, int d, void* workspace, size_t workspace_bytes, void* stream) {
-    return xattn_pairwise_bwd_ld(dOut, out, Xres, Pr, Q, h, a, A, alpha, s_pre, amask, p, dPr, dQ, dh, (long)d, da, accumulate_da, B, n, d,
-                                 workspace, workspace_bytes, stream);
-}
 // ldg: row stride of the three gradient outputs (d, or 3 d when they are the column blocks of one [dh | dP' | dQ] matrix)
 static int xattn_pairwise_bwd_ld(const float* dOut, const float* out, const float* Xres, const float* Pr, const float* Q,
                                  const float* h, const float* a, const uint8_t* A, const float* alpha, const float* s_pre,
                                  const uint8_t* amask, float p, float* dPr, float* dQ, float* dh, long ldg, float* da, int accumulate_da,
-                                 int B, int n, int d, void* workspace, size_t workspace_bytes, void* stream, float* dr, const int* sparse_flag,
-                                 int mode) {
+                                 int B, int n, int d, void* workspace, size_t workspace_bytes, void* stream, float* dr = nullptr,
+                                 const int* sparse_flag = nullptr, int mode = 0) {
     if (!dOut || !out || !Xres || !Pr || !Q || !h || !a || !A || !alpha || !s_pre || !dPr || !dQ || !dh || !da || !workspace)
         return DIGAT_ERR_ARG;
     if (d % 4 || n > DIGAT_MAX_NODES) return DIGAT_ERR_SHAPE;
-    if (workspace_bytes < digat_xattn_pairwise_bwd_workspace(B, n, d)) return DIGAT_ERR_WORKSPACE;
+    Arena w(workspace, workspace_bytes);
+    const PairBwdWs o = pair_bwd_carve(w, B, n, d);
+    if (!w.ok) return DIGAT_ERR_WORKSPACE;
     if (B == 0) return DIGAT_OK;
     hipStream_t st = (hipStream_t)stream;
-    float* dZ = (float*)workspace;
-    float* ds = (float*)((char*)workspace + align_up((size_t)B * n * d * 4, 256));
-    float* dap = (float*)((char*)ds + align_up((size_t)B * n * n * 4, 256));
-    float* dag = (float*)((char*)dap + align_up((size_t)B * d * 4, 256));
-    float2* wds = (float2*)((char*)dag + align_up(colsum2_scratch(B, d), 256));
     const float ascale = p > 0.f ? 1.f / (1.f - p) : 1.f;
     const uint8_t* am = p > 0.f ? amask : nullptr;
     // the forward's choice (a device int in its save buffer): the entry-wise pair below when the batch's adjacency is sparse, the three
@@ -1697,10 +1688,8 @@ static int xattn_pairwise_bwd_ld(const float* dOut, const float* out, const floa
     const bool only_sparse = eligible && (mode == 1 || n <= 16) && mode != 2;   // else the caller's choice (xattn_pairwise_fwd_train_flag): no guards
     const int* guard = (eligible && !only_sparse && sparse_flag && mode == 0) ? sparse_flag : nullptr;
     const int nblk = (int)spb_blocks(B, n);
-    float* dap2 = (float*)((char*)wds + align_up((size_t)B * n * n * 8, 256));
-    float* dag2 = (float*)((char*)dap2 + align_up((size_t)nblk * d * 4, 256));
     if (guard || only_sparse) {
-        SpBwdArgs t{dOut, out, Xres, h, Pr, Q, a, A, alpha, s_pre, am, ascale, dZ, wds, dQ, dh, dPr, ldg, dap2, B, n, d / 4, guard};
+        SpBwdArgs t{dOut, out, Xres, h, Pr, Q, a, A, alpha, s_pre, am, ascale, o.dZ, o.wds, dQ, dh, dPr, ldg, o.dap2, B, n, d / 4, guard};
         if (d / 4 <= 64) {
             hipLaunchKernelGGL(xattn_sparse_bwd_centre_kernel<1>, dim3(nblk), dim3(256), 0, st, t);
             hipLaunchKernelGGL(xattn_sparse_bwd_node_kernel<1>, dim3(nblk), dim3(256), 0, st, t);
@@ -1713,27 +1702,15 @@ static int xattn_pairwise_bwd_ld(const float* dOut, const float* out, const floa
     if (only_sparse) {
         hipLaunchKernelGGL(sum_nodes_kernel, dim3(grid_for((long)B * d)), dim3(256), 0, st, (const float*)dPr, dr, B, n, d, ldg);
         DIGAT_CHECK_LAUNCH();
-        return launch_colsum2(dap2, d, da, nblk, d, accumulate_da, dag2, st);
+        return launch_colsum2(o.dap2, d, da, nblk, d, accumulate_da, o.dag2, st);
     }
-    {   // ds — and dZ = dOut [out - Xres > 0] on its way in (written for the two launches below)
-        DsArgs t{dZ, h, alpha, s_pre, A, am, ascale, ds, B, n, d, dOut, out, Xres, dZ, guard};
-        const int n16 = (n + 15) / 16 * 16;
-        const size_t lds = ((size_t)2 * n16 * (DS_CH + 1) + (size_t)n * n) * 4;
-        if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)xattn_ds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   160 * 1024) != hipSuccess) return DIGAT_ERR_LAUNCH;
-        hipLaunchKernelGGL(xattn_ds_kernel, dim3(B), dim3(256), lds, st, t);
-        DIGAT_CHECK_LAUNCH();
-    }
-    {   // dh = alpha'^T dZ
-        AggTArgs t{alpha, am, ascale, dZ, dh, B, n, d, ldg, guard};
-        const size_t lds = (size_t)n * n * 4 + (((size_t)n * n + 3) & ~(size_t)3) + (size_t)n * 4;
-        if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)xattn_aggT_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   160 * 1024) != hipSuccess) return DIGAT_ERR_LAUNCH;
-        hipLaunchKernelGGL(xattn_aggT_kernel, dim3(B), dim3(256), lds, st, t);
-        DIGAT_CHECK_LAUNCH();
-    }
+    // ds — and dZ = dOut [out - Xres > 0] on its way in (written for the two launches below)
+    int rc = launch_ds(DsArgs{o.dZ, h, alpha, s_pre, A, am, ascale, o.ds, B, n, d, dOut, out, Xres, o.dZ, guard}, st);
+    if (rc) return rc;
+    rc = launch_aggT(AggTArgs{alpha, am, ascale, o.dZ, dh, B, n, d, ldg, guard}, st);                // dh = alpha'^T dZ
+    if (rc) return rc;
     {   // dP', dQ, da partials
-        PairBwdArgs t{Pr, Q, a, ds, dPr, dQ, dap, B, n, d, ldg, dr, guard};
+        PairBwdArgs t{Pr, Q, a, o.ds, dPr, dQ, o.dap, B, n, d, ldg, dr, guard};
         auto lds_of = [&](int ch) { return ((size_t)3 * n * ch + (size_t)n * n) * 4 + 2 * (((size_t)n * n + 3) & ~(size_t)3) + 2 * (size_t)n * 4; };
         const int ch = lds_of(64) <= 160 * 1024 ? 64 : 32;
         const size_t lds = lds_of(ch);
@@ -1748,11 +1725,18 @@ static int xattn_pairwise_bwd_ld(const float* dOut, const float* out, const floa
         // over the nodes of dP' (valid on both sides; the all-pairs kernel wrote the same sums already)
         hipLaunchKernelGGL(sum_nodes_kernel, dim3(grid_for((long)B * d)), dim3(256), 0, st, (const float*)dPr, dr, B, n, d, ldg);
         DIGAT_CHECK_LAUNCH();
-        const int rc2 = launch_colsum2_if(dap2, d, da, nblk, d, accumulate_da, dag2, st, guard, 1);
-        if (rc2) return rc2;
-        return launch_colsum2_if(dap, d, da, B, d, accumulate_da, dag, st, guard, 0);
+        rc = launch_colsum2_if(o.dap2, d, da, nblk, d, accumulate_da, o.dag2, st, guard, 1);
+        if (rc) return rc;
+        return launch_colsum2_if(o.dap, d, da, B, d, accumulate_da, o.dag, st, guard, 0);
     }
-    return launch_colsum2(dap, d, da, B, d, accumulate_da, dag, st);
+    return launch_colsum2(o.dap, d, da, B, d, accumulate_da, o.dag, st);
+}
+int digat_xattn_pairwise_bwd(const float* dOut, const float* out, const float* Xres, const float* Pr, const float* Q,
+                             const float* h, const float* a, const uint8_t* A, const float* alpha, const float* s_pre,
+                             const uint8_t* amask, float p, float* dPr, float* dQ, float* dh, float* da, int accumulate_da,
+                             int B, int n, int d, void* workspace, size_t workspace_bytes, void* stream) {
+    return xattn_pairwise_bwd_ld(dOut, out, Xres, Pr, Q, h, a, A, alpha, s_pre, amask, p, dPr, dQ, dh, (long)d, da, accumulate_da, B, n, d,
+                                 workspace, workspace_bytes, stream);
 }
 
 int digat_sum_nodes(const float* dP, float* dr, int B, int n, int d, void* stream) {
@@ -1769,10 +1753,7 @@ int digat_xattn_project(const float* X, const float* r, const float* W, const fl
     if (!X || !r || !W || !F1 || !F2 || !h || !Pr || !Q) return DIGAT_ERR_ARG;
     if (d % 4) return DIGAT_ERR_SHAPE;
     if (B == 0) return DIGAT_OK;
-    GemmArgs g = gemm_plain(X, d, W, bW, h, d, B * n, d, d, 0);
-    g.w[1] = F1; g.bias[1] = nullptr; g.y[1] = Pr;
-    g.w[2] = F2; g.bias[2] = nullptr; g.y[2] = Q;
-    g.nsegs = 3;
+    GemmArgs g = proj3_args(X, B * n, d, W, bW, F1, F2, h, Pr, Q, nullptr, 0, 0, nullptr);
     g.radd = r; g.radd_seg = 1; g.rows_per_b = n;
     return launch_gemm(g, (hipStream_t)stream, DIGAT_KERNEL_PROJ);
 }
@@ -1783,11 +1764,7 @@ int digat_xattn_project_x3(const float* X, const float* r, const float* W, const
     if (d % 80 || (long)B * n < 2048) return DIGAT_ERR_SHAPE;
     int rc = launch_split(W, F1, F2, d, 3, d, wsplit, (hipStream_t)stream, 0, 0);
     if (rc) return rc;
-    GemmArgs g = gemm_plain(X, d, W, bW, h, d, B * n, d, d, 0);
-    g.w[1] = F1; g.bias[1] = nullptr; g.y[1] = Pr;
-    g.w[2] = F2; g.bias[2] = nullptr; g.y[2] = Q;
-    g.nsegs = 3;
-    g.wsplit = (const unsigned short*)wsplit;
+    GemmArgs g = proj3_args(X, B * n, d, W, bW, F1, F2, h, Pr, Q, wsplit, 0, DIGAT_GEMM_BF16X6, nullptr);
     if (g_train_bf16) g.x1_segs = 7;           // digat_set_train_precision(1): one bf16 product
     g.radd = r; g.radd_seg = 1; g.rows_per_b = n;
     return launch_gemm(g, (hipStream_t)stream, DIGAT_KERNEL_PROJ);

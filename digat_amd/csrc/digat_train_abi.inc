@@ -38,31 +38,41 @@ extern "C" {
 //   X: the layer's input AFTER its input dropout (the caller applies drop_{p/2}; the residual uses the dropped input, :145,153)
 //   out = relu(drop_p(alpha) h) + X, alpha from the masked softmax of leaky_relu(a . relu(K3 + K1 + K2))
 // ============================================================================================================
-size_t digat_xattn_train_save_bytes(int B, int n, int d) {
-    // h, P', Q, r, alpha, s_pre, the attention dropout's keep bytes; the dropped input and the input dropout's keep bytes (p_in > 0)
-    return 3 * align_up((size_t)B * n * d * 4, 256) + align_up((size_t)B * d * 4, 256) + 2 * align_up((size_t)B * n * n * 4, 256)
-           + align_up((size_t)B * n * n, 256) + align_up((size_t)B * n * d * 4, 256) + align_up((size_t)B * n * d, 256) + 256;
-}
-size_t digat_xattn_train_workspace_bytes(int B, int n, int d) {
-    // forward: alpha after dropout + split scratch; backward: dPr, dQ, dh, dr, the pairwise backward's own scratch, dW scratch
-    const size_t fwd = align_up((size_t)B * n * n * 4, 256) + align_up(wsplit_scratch(d), 256) + 256;
-    const size_t bwd = align_up(3 * (size_t)B * n * d * 4, 256) + align_up((size_t)B * d * 4, 256)
-                       + align_up(digat_xattn_pairwise_bwd_workspace(B, n, d), 256)
-                       + align_up(digat_linear_bwd_weight_workspace(B * n, 3 * d, d), 256) + align_up(wsplit_scratch(d), 256)
-                       + 2 * align_up(3 * (size_t)d * d * 4, 256) + align_up(3 * (size_t)d * 4, 256)
-                       + align_up(digat_split_weights_bytes(d, 3 * d), 256);
-    return fwd > bwd ? fwd : bwd;
-}
-
+// save: h, P', Q, r, alpha, s_pre, the attention dropout's keep bytes; the dropped input and the input dropout's keep bytes (p_in > 0)
 struct XattnSave { float *h, *Pr, *Q, *r, *alpha, *s_pre; uint8_t* amask; float* Xd; uint8_t* xmask; int* sflag; };
-static bool xattn_save_carve(void* save, size_t bytes, int B, int n, int d, XattnSave* s) {
-    Arena a(save, bytes);
+static XattnSave xattn_save_carve(Arena& a, int B, int n, int d) {
     const size_t nd = (size_t)B * n * d, nn = (size_t)B * n * n;
-    s->h = a.take<float>(nd); s->Pr = a.take<float>(nd); s->Q = a.take<float>(nd); s->r = a.take<float>((size_t)B * d);
-    s->alpha = a.take<float>(nn); s->s_pre = a.take<float>(nn); s->amask = a.take<uint8_t>(nn);
-    s->Xd = a.take<float>(nd); s->xmask = a.take<uint8_t>(nd);
-    s->sflag = a.take<int>(1);                     // sparse or dense Eq. 8 for this batch: decided on the device by the forward, read by the backward
-    return a.ok;
+    XattnSave s;
+    s.h = a.take<float>(nd); s.Pr = a.take<float>(nd); s.Q = a.take<float>(nd); s.r = a.take<float>((size_t)B * d);
+    s.alpha = a.take<float>(nn); s.s_pre = a.take<float>(nn); s.amask = a.take<uint8_t>(nn);
+    s.Xd = a.take<float>(nd); s.xmask = a.take<uint8_t>(nd);
+    s.sflag = a.take<int>(1);                      // sparse or dense Eq. 8 for this batch: decided on the device by the forward, read by the backward
+    return s;
+}
+// forward workspace: alpha after dropout + split scratch
+struct XattnFwdWs { float* adrop; void* wsplit; };
+static XattnFwdWs xattn_fwd_carve(Arena& w, int B, int n, int d) {
+    return XattnFwdWs{w.take<float>((size_t)B * n * n), w.take<char>(wsplit_scratch(d))};      // braces: taken left to right
+}
+// backward workspace: G = [dh | dP' | dQ] ([B n, 3 d]), dr, the pairwise backward's own scratch, dW scratch, split scratch, the
+// stacked [dW; dF1; dF2] for callers whose three buffers are not one, the image of the stacked weights' transpose
+struct XattnBwdWs { float *G, *dr; void* pws; size_t pb; void* wws; size_t wb; void* wsplit; float* wg3; void* wcat_split; };
+static XattnBwdWs xattn_bwd_carve(Arena& w, int B, int n, int d) {
+    XattnBwdWs o;
+    o.G = w.take<float>(3 * (size_t)B * n * d);
+    o.dr = w.take<float>((size_t)B * d);
+    o.pb = digat_xattn_pairwise_bwd_workspace(B, n, d);
+    o.wb = digat_linear_bwd_weight_workspace(B * n, 3 * d, d);
+    o.pws = w.take<char>(o.pb); o.wws = w.take<char>(o.wb); o.wsplit = w.take<char>(wsplit_scratch(d));
+    o.wg3 = w.take<float>(3 * (size_t)d * d);
+    o.wcat_split = w.take<char>(digat_split_weights_bytes(d, 3 * d));
+    return o;
+}
+size_t digat_xattn_train_save_bytes(int B, int n, int d) { Arena a; xattn_save_carve(a, B, n, d); return a.used; }
+size_t digat_xattn_train_workspace_bytes(int B, int n, int d) {        // one buffer serves both directions
+    Arena fwd, bwd;
+    xattn_fwd_carve(fwd, B, n, d); xattn_bwd_carve(bwd, B, n, d);
+    return larger(fwd, bwd);
 }
 
 int digat_xattn_fwd_train(const float* X, const uint8_t* A, const float* ctx, const float* W, const float* bW, const float* F1,
@@ -73,14 +83,11 @@ int digat_xattn_fwd_train(const float* X, const uint8_t* A, const float* ctx, co
     if (B < 0 || n <= 0 || d <= 0 || p_alpha < 0.f || p_alpha >= 1.f || p_in < 0.f || p_in >= 1.f || xattn_mode < 0 || xattn_mode > 2) return DIGAT_ERR_ARG;
     if (d % 4 || n > DIGAT_MAX_NODES) return DIGAT_ERR_SHAPE;
     if (B == 0) return DIGAT_OK;
-    XattnSave s;
-    if (save_bytes < digat_xattn_train_save_bytes(B, n, d) || !xattn_save_carve(save, save_bytes, B, n, d, &s)) return DIGAT_ERR_WORKSPACE;
-    if (workspace_bytes < digat_xattn_train_workspace_bytes(B, n, d)) return DIGAT_ERR_WORKSPACE;
-    Arena w(workspace, workspace_bytes);
-    float* adrop = w.take<float>((size_t)B * n * n);
-    void* wsplit = w.take<char>(wsplit_scratch(d));
-    int* sflag = s.sflag;
-    if (!w.ok) return DIGAT_ERR_WORKSPACE;
+    Arena sa(save, save_bytes), w(workspace, workspace_bytes);
+    const XattnSave s = xattn_save_carve(sa, B, n, d);
+    if (!sa.ok || workspace_bytes < digat_xattn_train_workspace_bytes(B, n, d)) return DIGAT_ERR_WORKSPACE;
+    const XattnFwdWs o = xattn_fwd_carve(w, B, n, d);
+    void* wsplit = o.wsplit;
     hipStream_t st = (hipStream_t)stream;
     if (p_in > 0.f) {        // the layer's input dropout (:145 / :165), kept with its keep bytes: the projections, the residual and the backward read Xd
         T_TRY(digat_dropout_fwd(X, s.Xd, s.xmask, (int64_t)B * n * d, p_in, seed_in, st));
@@ -94,8 +101,8 @@ int digat_xattn_fwd_train(const float* X, const uint8_t* A, const float* ctx, co
     else T_TRY(digat_xattn_project(X, s.r, W, bW, F1, F2, s.h, s.Pr, s.Q, B, n, d, st));
     // (s_pre is written on the adjacency's entries only and read, by xattn_ds_kernel, behind the adjacency test only: de = 0 off the
     // entries whatever the slot holds — 0 x (sp > 0 ? 1 : 0.2) — so the rest of the buffer needs no zero-fill: six memsets per step less)
-    return xattn_pairwise_fwd_train_flag(s.Pr, s.Q, s.h, X, a, A, out, s.alpha, s.s_pre, p_alpha > 0.f ? adrop : nullptr,
-                                         p_alpha > 0.f ? s.amask : nullptr, p_alpha, seed, B, n, d, sflag, st, xattn_mode);
+    return xattn_pairwise_fwd_train_flag(s.Pr, s.Q, s.h, X, a, A, out, s.alpha, s.s_pre, p_alpha > 0.f ? o.adrop : nullptr,
+                                         p_alpha > 0.f ? s.amask : nullptr, p_alpha, seed, B, n, d, s.sflag, st, xattn_mode);
 }
 
 // dX [B,n,d], dctx [B,d], dW dF1 dF2 dF3 [d,d], dbW db3 [d], da [d]: all written (not accumulated)
@@ -109,33 +116,19 @@ int digat_xattn_bwd(const float* dOut, const float* out, const float* X, const u
     if (B < 0 || n <= 0 || d <= 0 || xattn_mode < 0 || xattn_mode > 2) return DIGAT_ERR_ARG;
     if (d % 4 || n > DIGAT_MAX_NODES) return DIGAT_ERR_SHAPE;
     hipStream_t st = (hipStream_t)stream;
-    if (B == 0) {
-        const size_t dd = (size_t)d * d * 4;
-        if (hipMemsetAsync(dW, 0, dd, st) != hipSuccess || hipMemsetAsync(dF1, 0, dd, st) != hipSuccess ||
-            hipMemsetAsync(dF2, 0, dd, st) != hipSuccess || hipMemsetAsync(dF3, 0, dd, st) != hipSuccess ||
-            hipMemsetAsync(dbW, 0, (size_t)d * 4, st) != hipSuccess || hipMemsetAsync(db3, 0, (size_t)d * 4, st) != hipSuccess ||
-            hipMemsetAsync(da, 0, (size_t)d * 4, st) != hipSuccess) return DIGAT_ERR_LAUNCH;
-        return DIGAT_OK;
-    }
-    XattnSave s;
-    if (save_bytes < digat_xattn_train_save_bytes(B, n, d) || !xattn_save_carve(const_cast<void*>(save), save_bytes, B, n, d, &s))
-        return DIGAT_ERR_WORKSPACE;
-    if (workspace_bytes < digat_xattn_train_workspace_bytes(B, n, d)) return DIGAT_ERR_WORKSPACE;
-    Arena w(workspace, workspace_bytes);
+    const size_t dd = (size_t)d * d;
+    if (B == 0) return zero_floats(st, {{dW, dd}, {dF1, dd}, {dF2, dd}, {dF3, dd}, {dbW, (size_t)d}, {db3, (size_t)d}, {da, (size_t)d}});
+    Arena sa(const_cast<void*>(save), save_bytes), w(workspace, workspace_bytes);
+    const XattnSave s = xattn_save_carve(sa, B, n, d);
+    if (!sa.ok || workspace_bytes < digat_xattn_train_workspace_bytes(B, n, d)) return DIGAT_ERR_WORKSPACE;
+    const XattnBwdWs o = xattn_bwd_carve(w, B, n, d);
     const size_t nd = (size_t)B * n * d;
     // the three gradients are the column blocks of ONE matrix G = [dh | dP' | dQ] ([B n, 3 d]): their input-gradient products are
     // then a single product with the stacked weights [W; F1; F2] (one pass over dX instead of three read-modify-writes)
-    float* G = w.take<float>(3 * nd);
+    float* G = o.G;
     const long ldg = 3L * d;
     float* dh = G; float* dPr = G + d; float* dQ = G + 2 * d;
-    float* dr = w.take<float>((size_t)B * d);
-    const size_t pb = digat_xattn_pairwise_bwd_workspace(B, n, d), wb = digat_linear_bwd_weight_workspace(B * n, 3 * d, d);
-    void* pws = w.take<char>(pb); void* wws = w.take<char>(wb); void* wsplit = w.take<char>(wsplit_scratch(d));
-    float* wcat = w.take<float>(3 * (size_t)d * d);
-    float* wg3 = w.take<float>(3 * (size_t)d * d);      // [dW; dF1; dF2] as one [3 d, d] product G^T X
-    float* db3g = w.take<float>(3 * (size_t)d);
-    void* wcat_split = w.take<char>(digat_split_weights_bytes(d, 3 * d));
-    if (!w.ok) return DIGAT_ERR_WORKSPACE;
+    void* wcat_split = o.wcat_split;
     const int M = B * n;
     const uint8_t* xmask = nullptr;
     const float xscale = p_in > 0.f ? 1.f / (1.f - p_in) : 1.f;
@@ -145,11 +138,10 @@ int digat_xattn_bwd(const float* dOut, const float* out, const float* X, const u
     if (bwd_image) wcat_split = const_cast<void*>(bwd_image);
     // (dr[b] = sum_j dP'[b,j] — K3 = ctx F3^T + b3 was added to every neighbour-side row — leaves the pairwise backward's launch)
     T_TRY(xattn_pairwise_bwd_ld(dOut, out, X, s.Pr, s.Q, s.h, a, A, s.alpha, s.s_pre, p_alpha > 0.f ? s.amask : nullptr, p_alpha,
-                                dPr, dQ, dh, ldg, da, 0, B, n, d, pws, pb, st, dr, s.sflag, xattn_mode));
+                                dPr, dQ, dh, ldg, da, 0, B, n, d, o.pws, o.pb, st, o.dr, s.sflag, xattn_mode));
     // projections: dX = dOut (residual) + dh W + dP' F1 + dQ F2 = dOut + G [W; F1; F2]
     if (x3_ok(M, d, 3 * d)) {
-        // the stacked weights [W; F1; F2] are split from their three homes (round 5: three device copies per call before)
-        (void)wcat;
+        // the stacked weights [W; F1; F2] are split from their three homes
         T_TRY(linear_bwd_input_x3_add(G, ldg, W, dX, d, dOut, M, 3 * d, d, wcat_split, st, F1, F2, xmask, xscale));   // dOut joins in the epilogue, and the input dropout's backward
     } else {
         if (hipMemcpyAsync(dX, dOut, nd * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return DIGAT_ERR_LAUNCH;
@@ -160,43 +152,47 @@ int digat_xattn_bwd(const float* dOut, const float* out, const float* X, const u
     }
     // ... and the three weight gradients one product G^T X ([3 d, d]; the column sums of G's first block are dbW)
     // a caller that hands over dW, dF1, dF2 as the three blocks of ONE [3 d, d] buffer (training.XattnFused does) gets the product
-    // written in place: no copies (round 5: four device copies per call before, three now only for separate buffers)
-    const bool stacked = dF1 == dW + (size_t)d * d && dF2 == dW + 2 * (size_t)d * d;
-    // (the reduction writes the d leading column sums — dbW — where they belong: one device copy per call less)
-    (void)db3g;
-    T_TRY(linear_bwd_weight_dbn(G, ldg, X, d, stacked ? dW : wg3, dbW, d, M, 3 * d, d, 0, wws, wb, st));
-    {
-        const size_t wbytes = (size_t)d * d * 4;
-        if (!stacked && (hipMemcpyAsync(dW, wg3, wbytes, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-                         hipMemcpyAsync(dF1, wg3 + (size_t)d * d, wbytes, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-                         hipMemcpyAsync(dF2, wg3 + 2 * (size_t)d * d, wbytes, hipMemcpyDeviceToDevice, st) != hipSuccess)) return DIGAT_ERR_LAUNCH;
-    }
-    T_TRY(t_linear_bwd_input(dr, F3, dctx, B, d, d, 0, wsplit, st));
-    return t_linear_bwd_weight(dr, ctx, d, dF3, db3, B, d, d, wws, wb, st);
+    // written in place: no copies; separate buffers get theirs from o.wg3 by three device copies
+    const bool stacked = dF1 == dW + dd && dF2 == dW + 2 * dd;
+    // (the reduction writes the d leading column sums — dbW — where they belong)
+    T_TRY(linear_bwd_weight_dbn(G, ldg, X, d, stacked ? dW : o.wg3, dbW, d, M, 3 * d, d, 0, o.wws, o.wb, st));
+    if (!stacked && (hipMemcpyAsync(dW, o.wg3, dd * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+                     hipMemcpyAsync(dF1, o.wg3 + dd, dd * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+                     hipMemcpyAsync(dF2, o.wg3 + 2 * dd, dd * 4, hipMemcpyDeviceToDevice, st) != hipSuccess)) return DIGAT_ERR_LAUNCH;
+    T_TRY(t_linear_bwd_input(o.dr, F3, dctx, B, d, d, 0, o.wsplit, st));
+    return t_linear_bwd_weight(o.dr, ctx, d, dF3, db3, B, d, d, o.wws, o.wb, st);
 }
 
 // ============================================================================================================
 // a3: news-graph context, training (graphEncoders.py:109-114):  l = X[:,0]; g = SDPA(X, l, mask);
 //     out = gate(drop_{p/2}(W_g [l;g] + b_g), l, g)
 // ============================================================================================================
-size_t digat_news_ctx_train_save_bytes(int B, int N, int d) {
-    return 3 * align_up((size_t)B * d * 4, 256) + align_up((size_t)B * N * 4, 256) + align_up((size_t)B * 2 * d * 4, 256)
-           + align_up((size_t)B * d, 256);
+struct NewsCtxSave { float *qv, *kq, *zd, *alpha, *cat; uint8_t* zmask; };
+static NewsCtxSave news_save_carve(Arena& a, int B, int N, int d) {
+    NewsCtxSave s;
+    s.qv = a.take<float>((size_t)B * d); s.kq = a.take<float>((size_t)B * d); s.zd = a.take<float>((size_t)B * d);
+    s.alpha = a.take<float>((size_t)B * N); s.cat = a.take<float>((size_t)B * 2 * d); s.zmask = a.take<uint8_t>((size_t)B * d);
+    return s;
 }
+// forward workspace: the gate's pre-activation z [B,d]
+static float* news_fwd_carve(Arena& w, int B, int d) { return w.take<float>((size_t)B * d); }
+// backward workspace: dz, dkq, dqv [B,d]; [dl | dg] [B,2d]; the scratch of the three weight-gradient products (collected and issued
+// together: each has its own slices)
+struct NewsCtxBwdWs { float *dz, *dkq, *dqv, *dlg; void* wws; size_t wb; };
+static NewsCtxBwdWs news_bwd_carve(Arena& w, int B, int d) {
+    const size_t bd = (size_t)B * d;
+    NewsCtxBwdWs o;
+    o.dz = w.take<float>(bd); o.dkq = w.take<float>(bd); o.dqv = w.take<float>(bd); o.dlg = w.take<float>(2 * bd);
+    o.wb = align_up(digat_linear_bwd_weight_workspace(B, d, 2 * d), 256) + 2 * align_up(digat_linear_bwd_weight_workspace(B, d, d), 256);
+    o.wws = w.take<char>(o.wb);
+    return o;
+}
+size_t digat_news_ctx_train_save_bytes(int B, int N, int d) { Arena a; news_save_carve(a, B, N, d); return a.used; }
 size_t digat_news_ctx_train_workspace_bytes(int B, int N, int d) {
     (void)N;
-    // backward: dz, dkq, dqv [B,d]; [dl | dg] [B,2d]; dW scratch for the widest weight ([d, 2d])
-    // (three weight-gradient products, collected and issued together: each has its own slices)
-    return 3 * align_up((size_t)B * d * 4, 256) + align_up((size_t)B * 2 * d * 4, 256)
-           + align_up(digat_linear_bwd_weight_workspace(B, d, 2 * d), 256) + 2 * align_up(digat_linear_bwd_weight_workspace(B, d, d), 256)
-           + align_up(wsplit_scratch(d), 256);
-}
-struct NewsCtxSave { float *qv, *kq, *zd, *alpha, *cat; uint8_t* zmask; };
-static bool news_save_carve(void* save, size_t bytes, int B, int N, int d, NewsCtxSave* s) {
-    Arena a(save, bytes);
-    s->qv = a.take<float>((size_t)B * d); s->kq = a.take<float>((size_t)B * d); s->zd = a.take<float>((size_t)B * d);
-    s->alpha = a.take<float>((size_t)B * N); s->cat = a.take<float>((size_t)B * 2 * d); s->zmask = a.take<uint8_t>((size_t)B * d);
-    return a.ok;
+    Arena fwd, bwd;
+    news_fwd_carve(fwd, B, d); news_bwd_carve(bwd, B, d);
+    return larger(fwd, bwd);
 }
 // dX[b,0,:] += dl[b] (the local context is node 0 of every row)
 __global__ void __launch_bounds__(256) add_node0_kernel(float4* dX, long ldx4, const float4* dl, long ldl4, long B, int d4) {
@@ -214,12 +210,10 @@ int digat_news_ctx_fwd_train(const float* X, const uint8_t* mask, const float* K
     if (B < 0 || N <= 0 || d <= 0 || p_gate < 0.f || p_gate >= 1.f) return DIGAT_ERR_ARG;
     if (d % 4 || N > DIGAT_MAX_NODES) return DIGAT_ERR_SHAPE;
     if (B == 0) return DIGAT_OK;
-    NewsCtxSave s;
-    if (save_bytes < digat_news_ctx_train_save_bytes(B, N, d) || !news_save_carve(save, save_bytes, B, N, d, &s)) return DIGAT_ERR_WORKSPACE;
-    if (workspace_bytes < digat_news_ctx_train_workspace_bytes(B, N, d)) return DIGAT_ERR_WORKSPACE;
-    Arena w(workspace, workspace_bytes);
-    float* z = w.take<float>((size_t)B * d);
-    if (!w.ok) return DIGAT_ERR_WORKSPACE;
+    Arena sa(save, save_bytes), w(workspace, workspace_bytes);
+    const NewsCtxSave s = news_save_carve(sa, B, N, d);
+    if (!sa.ok || workspace_bytes < digat_news_ctx_train_workspace_bytes(B, N, d)) return DIGAT_ERR_WORKSPACE;
+    float* z = news_fwd_carve(w, B, d);
     hipStream_t st = (hipStream_t)stream;
     const long ldx = (long)N * d;
     T_TRY(digat_linear_f32(X, ldx, Qc, bQc, s.qv, d, B, d, d, st));                                 // Q l + b
@@ -243,20 +237,15 @@ int digat_news_ctx_bwd(const float* dout, const float* X, const uint8_t* mask, c
         return DIGAT_ERR_ARG;
     if (B <= 0 || N <= 0 || d <= 0) return DIGAT_ERR_ARG;
     if (d % 4 || N > DIGAT_MAX_NODES) return DIGAT_ERR_SHAPE;
-    NewsCtxSave s;
-    if (save_bytes < digat_news_ctx_train_save_bytes(B, N, d) || !news_save_carve(const_cast<void*>(save), save_bytes, B, N, d, &s))
-        return DIGAT_ERR_WORKSPACE;
-    if (workspace_bytes < digat_news_ctx_train_workspace_bytes(B, N, d)) return DIGAT_ERR_WORKSPACE;
-    Arena w(workspace, workspace_bytes);
+    Arena sa(const_cast<void*>(save), save_bytes), w(workspace, workspace_bytes);
+    const NewsCtxSave s = news_save_carve(sa, B, N, d);
+    if (!sa.ok || workspace_bytes < digat_news_ctx_train_workspace_bytes(B, N, d)) return DIGAT_ERR_WORKSPACE;
+    const NewsCtxBwdWs o = news_bwd_carve(w, B, d);
+    float *dz = o.dz, *dkq = o.dkq, *dqv = o.dqv, *dlg = o.dlg;
     const size_t bd = (size_t)B * d;
-    float* dz = w.take<float>(bd); float* dkq = w.take<float>(bd); float* dqv = w.take<float>(bd); float* dlg = w.take<float>(2 * bd);
-    const size_t wb = align_up(digat_linear_bwd_weight_workspace(B, d, 2 * d), 256) + 2 * align_up(digat_linear_bwd_weight_workspace(B, d, d), 256);
-    void* wws = w.take<char>(wb); void* wsplit = w.take<char>(wsplit_scratch(d));
-    (void)wsplit;
-    if (!w.ok) return DIGAT_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const int acc = accumulate_params ? 1 : 0;
-    TnGroup dws(wws, wb, st);                      // the entry's three weight gradients: one product launch + one reduction at the end
+    TnGroup dws(o.wws, o.wb, st);                      // the entry's three weight gradients: one product launch + one reduction at the end
     const long ldx = (long)N * d;
     // gate: out = sig(zd) l + (1 - sig(zd)) g, zd = dropout(z).  Round 6: one launch gives dz (through the dropout's keep bytes) and
     // the gate's dl, dg as the two halves of ONE [B, 2 d] matrix [dl | dg] — the matrix z's other path adds to: [dl | dg] += dz Wg —
@@ -286,27 +275,36 @@ int digat_news_ctx_bwd(const float* dout, const float* X, const uint8_t* mask, c
 // ============================================================================================================
 // a4 (+a6, a7): user-graph context, training (graphEncoders.py:123-134)
 // ============================================================================================================
-size_t digat_user_ctx_train_save_bytes(int B, int U, int H, int C1, int d) {
-    (void)U;
-    return 4 * align_up((size_t)B * d * 4, 256) + align_up((size_t)B * H * 4, 256) + 3 * align_up((size_t)B * C1 * d * 4, 256)
-           + align_up((size_t)B * C1 * d, 256) + align_up((size_t)B * C1 * 4, 256);
+struct UserCtxSave { float *qv, *kq, *qv2, *kq2, *alpha_t, *T, *y, *T2d, *alpha_u; uint8_t* tmask; };
+static UserCtxSave user_save_carve(Arena& a, int B, int H, int C1, int d) {
+    const size_t bd = (size_t)B * d, t = (size_t)B * C1 * d;
+    UserCtxSave s;
+    s.qv = a.take<float>(bd); s.kq = a.take<float>(bd); s.qv2 = a.take<float>(bd); s.kq2 = a.take<float>(bd);
+    s.alpha_t = a.take<float>((size_t)B * H);
+    s.T = a.take<float>(t); s.y = a.take<float>(t); s.T2d = a.take<float>(t);
+    s.tmask = a.take<uint8_t>(t); s.alpha_u = a.take<float>((size_t)B * C1);
+    return s;
 }
+// forward workspace: split scratch
+static void* user_fwd_carve(Arena& w, int d) { return w.take<char>(wsplit_scratch(d)); }
+// backward workspace: dT2d, dT2, dy [B,C1,d]; dkq2, dqv2, dkq, dqv [B,d]; the scratch of dFa's product and of the four short ones of
+// the query chains (collected and issued together); split scratch
+struct UserCtxBwdWs { float *dT2d, *dT2, *dy, *dkq2, *dqv2, *dkq, *dqv; void* wws; size_t wb; void* wsplit; };
+static UserCtxBwdWs user_bwd_carve(Arena& w, int B, int C1, int d) {
+    const size_t bd = (size_t)B * d, t = (size_t)B * C1 * d;
+    UserCtxBwdWs o;
+    o.dT2d = w.take<float>(t); o.dT2 = w.take<float>(t); o.dy = w.take<float>(t);
+    o.dkq2 = w.take<float>(bd); o.dqv2 = w.take<float>(bd); o.dkq = w.take<float>(bd); o.dqv = w.take<float>(bd);
+    o.wb = align_up(digat_linear_bwd_weight_workspace(B * C1, d, d), 256) + 4 * align_up(digat_linear_bwd_weight_workspace(B, d, d), 256);
+    o.wws = w.take<char>(o.wb); o.wsplit = w.take<char>(wsplit_scratch(d));
+    return o;
+}
+size_t digat_user_ctx_train_save_bytes(int B, int U, int H, int C1, int d) { (void)U; Arena a; user_save_carve(a, B, H, C1, d); return a.used; }
 size_t digat_user_ctx_train_workspace_bytes(int B, int U, int H, int C1, int d) {
     (void)U; (void)H;
-    const size_t t = align_up((size_t)B * C1 * d * 4, 256), v = align_up((size_t)B * d * 4, 256);
-    // (dFa's product + the four short ones of the query chains, collected and issued together)
-    return 3 * t + 4 * v + align_up(digat_linear_bwd_weight_workspace(B * C1, d, d), 256)
-           + 4 * align_up(digat_linear_bwd_weight_workspace(B, d, d), 256) + align_up(wsplit_scratch(d), 256);
-}
-struct UserCtxSave { float *qv, *kq, *qv2, *kq2, *alpha_t, *T, *y, *T2d, *alpha_u; uint8_t* tmask; };
-static bool user_save_carve(void* save, size_t bytes, int B, int H, int C1, int d, UserCtxSave* s) {
-    Arena a(save, bytes);
-    const size_t bd = (size_t)B * d, t = (size_t)B * C1 * d;
-    s->qv = a.take<float>(bd); s->kq = a.take<float>(bd); s->qv2 = a.take<float>(bd); s->kq2 = a.take<float>(bd);
-    s->alpha_t = a.take<float>((size_t)B * H);
-    s->T = a.take<float>(t); s->y = a.take<float>(t); s->T2d = a.take<float>(t);
-    s->tmask = a.take<uint8_t>(t); s->alpha_u = a.take<float>((size_t)B * C1);
-    return a.ok;
+    Arena fwd, bwd;
+    user_fwd_carve(fwd, d); user_bwd_carve(bwd, B, C1, d);
+    return larger(fwd, bwd);
 }
 
 int digat_user_ctx_fwd_train(const float* Xu, const uint8_t* cat_mask, const int64_t* cat_idx, const float* c_n, const float* Ku,
@@ -319,14 +317,10 @@ int digat_user_ctx_fwd_train(const float* Xu, const uint8_t* cat_mask, const int
     if (B < 0 || H < 0 || U < H || C1 <= 0 || d <= 0 || p_topic < 0.f || p_topic >= 1.f) return DIGAT_ERR_ARG;
     if (d % 4 || C1 > DIGAT_MAX_NODES || H > TOPIC_MAX_H) return DIGAT_ERR_SHAPE;
     if (B == 0) return DIGAT_OK;
-    UserCtxSave s;
-    if (save_bytes < digat_user_ctx_train_save_bytes(B, U, H, C1, d) || !user_save_carve(save, save_bytes, B, H, C1, d, &s))
-        return DIGAT_ERR_WORKSPACE;
-    if (workspace_bytes < digat_user_ctx_train_workspace_bytes(B, U, H, C1, d)) return DIGAT_ERR_WORKSPACE;
-    Arena w(workspace, workspace_bytes);
-    float* T2 = w.take<float>((size_t)B * C1 * d);
-    void* wsplit = w.take<char>(wsplit_scratch(d));
-    if (!w.ok) return DIGAT_ERR_WORKSPACE;
+    Arena sa(save, save_bytes), w(workspace, workspace_bytes);
+    const UserCtxSave s = user_save_carve(sa, B, H, C1, d);
+    if (!sa.ok || workspace_bytes < digat_user_ctx_train_workspace_bytes(B, U, H, C1, d)) return DIGAT_ERR_WORKSPACE;
+    void* wsplit = user_fwd_carve(w, d);
     hipStream_t st = (hipStream_t)stream;
     const int M = B * C1;
     const PremadeImage premade(fa_image);          // featureAffine.weight already split (digat_split_jobs, layout 0)
@@ -339,7 +333,7 @@ int digat_user_ctx_fwd_train(const float* Xu, const uint8_t* cat_mask, const int
     T_TRY(digat_linear_bwd_input(s.qv, d, Ku, s.kq, d, B, d, d, 0, st));
     T_TRY(digat_topic_pool_fwd_train(Xu, s.kq, cat_idx, s.T, s.alpha_t, B, U, H, C1, d, st));       // scatter_softmax + scatter_sum (:129-130)
     T_TRY(t_linear_fwd(s.T, d, Fa, bFa, s.y, M, d, d, wsplit, st));                                 // featureAffine (:131)
-    (void)T2;                                                                                       // relu + residual + dropout: one launch (round 6)
+    // relu + residual + dropout: one launch
     hipLaunchKernelGGL(relu_res_drop_fwd_kernel, dim3(grid_for((long)M * d)), dim3(256), 0, st, (const float*)s.y, (const float*)s.T, s.T2d,
                        p_topic > 0.f ? s.tmask : (uint8_t*)nullptr, (long)M * d, p_topic, seed);
     DIGAT_CHECK_LAUNCH();
@@ -357,23 +351,19 @@ int digat_user_ctx_bwd(const float* dout, const float* Xu, const uint8_t* cat_ma
         !dbQu || !dFa || !dbFa || !dKua || !dQua || !dbQua || !workspace) return DIGAT_ERR_ARG;
     if (B <= 0 || H < 0 || U < H || C1 <= 0 || d <= 0) return DIGAT_ERR_ARG;
     if (d % 4 || C1 > DIGAT_MAX_NODES || H > TOPIC_MAX_H) return DIGAT_ERR_SHAPE;
-    UserCtxSave s;
-    if (save_bytes < digat_user_ctx_train_save_bytes(B, U, H, C1, d) ||
-        !user_save_carve(const_cast<void*>(save), save_bytes, B, H, C1, d, &s)) return DIGAT_ERR_WORKSPACE;
-    if (workspace_bytes < digat_user_ctx_train_workspace_bytes(B, U, H, C1, d)) return DIGAT_ERR_WORKSPACE;
-    Arena w(workspace, workspace_bytes);
-    const size_t bd = (size_t)B * d, t = (size_t)B * C1 * d;
-    float* dT2d = w.take<float>(t); float* dT2 = w.take<float>(t); float* dy = w.take<float>(t);
-    float* dkq2 = w.take<float>(bd); float* dqv2 = w.take<float>(bd); float* dkq = w.take<float>(bd); float* dqv = w.take<float>(bd);
+    Arena sa(const_cast<void*>(save), save_bytes), w(workspace, workspace_bytes);
+    const UserCtxSave s = user_save_carve(sa, B, H, C1, d);
+    if (!sa.ok || workspace_bytes < digat_user_ctx_train_workspace_bytes(B, U, H, C1, d)) return DIGAT_ERR_WORKSPACE;
+    const UserCtxBwdWs o = user_bwd_carve(w, B, C1, d);
+    float *dT2d = o.dT2d, *dT2 = o.dT2, *dy = o.dy, *dkq2 = o.dkq2, *dqv2 = o.dqv2, *dkq = o.dkq, *dqv = o.dqv;
+    const size_t t = (size_t)B * C1 * d;
+    void* wsplit = o.wsplit;
     const int M = B * C1;
-    const size_t wb = align_up(digat_linear_bwd_weight_workspace(M, d, d), 256) + 4 * align_up(digat_linear_bwd_weight_workspace(B, d, d), 256);
-    void* wws = w.take<char>(wb); void* wsplit = w.take<char>(wsplit_scratch(d));
-    if (!w.ok) return DIGAT_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const int acc = accumulate_params ? 1 : 0;
     const PremadeImage premade(fa_bwd_image);      // featureAffine.weight already split for the input gradient (digat_split_jobs, layout 1)
     if (fa_bwd_image) wsplit = const_cast<void*>(fa_bwd_image);
-    TnGroup dws(wws, wb, st);                      // dFa's long product goes out at once; the four short ones together at the end
+    TnGroup dws(o.wws, o.wb, st);                  // dFa's long product goes out at once; the four short ones together at the end
     // user-level attention over the (dropped) topic representations
     T_TRY(digat_attn_pool_bwd(s.T2d, (long)C1 * d, s.kq2, cat_mask, s.alpha_u, dout, dT2d, (long)C1 * d, dkq2, B, C1, d, 0, st));
     // T2 = relu(y) + T,  y = T Fa^T + bFa:  dT = dT2 + dy Fa; dT2 = dropout'(dT2d) and dy = dT2 [y > 0] in one launch (round 6)

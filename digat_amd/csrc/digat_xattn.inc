@@ -1675,6 +1675,15 @@ __global__ void __launch_bounds__(MAXT) xattn_agg_kernel(const AggArgs g) {
         }
     }
 }
+// every launch of it: a workgroup per row, a wave per 64 channels (d <= 1024); alpha[b] and the live flags in LDS
+static int launch_agg(const AggArgs& ag, hipStream_t st) {
+    if (ag.groups > 16) return DIGAT_ERR_SHAPE;
+    const size_t lds = (size_t)ag.n * ag.sa * 4 + ag.n;
+    if (ag.groups <= 8) hipLaunchKernelGGL(xattn_agg_kernel<512>, dim3(ag.B), dim3(64 * ag.groups), lds, st, ag);
+    else hipLaunchKernelGGL(xattn_agg_kernel<1024>, dim3(ag.B), dim3(64 * ag.groups), lds, st, ag);
+    DIGAT_CHECK_LAUNCH();
+    return DIGAT_OK;
+}
 
 struct XattnPlan { ScoreArgs g; int threads; size_t lds; int blocks; };
 
@@ -1805,13 +1814,10 @@ static int launch_xattn_pairwise(const float* Pr, const float* Q, const float* h
     }
     if (!fused) {
         AggArgs ag{alpha, h, X, out, B, n, d, (d + 63) / 64, n | 1, live, group, skip_if};
-        if (ag.groups > 16) return DIGAT_ERR_SHAPE;        // d <= 1024
         // algorithmic bytes of the aggregation launch: h, X in + out (3 n d floats), alpha in;
         // flops 2 n^2 d per row run on the MFMA pipe
         ProfScope prof(DIGAT_KERNEL_AGG, skip_if ? 0.0 : (double)B * (3.0 * n * d * 4 + (double)n * n * 4.0), st);
-        if (ag.groups <= 8) hipLaunchKernelGGL(xattn_agg_kernel<512>, dim3(B), dim3(64 * ag.groups), (size_t)n * ag.sa * 4 + n, st, ag);
-        else hipLaunchKernelGGL(xattn_agg_kernel<1024>, dim3(B), dim3(64 * ag.groups), (size_t)n * ag.sa * 4 + n, st, ag);
-        DIGAT_CHECK_LAUNCH();
+        return launch_agg(ag, st);
     }
     return DIGAT_OK;
 }

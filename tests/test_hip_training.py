@@ -417,6 +417,47 @@ def test_eq8_layer_with_attention_dropout_live(n, d, B, p_in, per_node, mode, mo
         close(got[k], want[k].numpy(), f"Eq. 8 n={n} dropout grad {k}")
 
 
+@pytest.mark.parametrize("B,n,d", [(3, 10, 80), (32, 67, 80)])
+def test_eq8_backward_into_three_separate_weight_gradients_equals_the_stacked_call(B, n, d):
+    """digat_xattn_bwd with dW, dF1, dF2 as three separate allocations: the [3 d, d] product lands in the workspace's `wg3` and
+    three device copies hand it out.  Every output must equal, bit for bit, the call that both bindings make (one [3, d, d] buffer,
+    written in place: _ctypes_binding.xattn_bwd).  30 rows take the fp32 products, 32 x 67 = 2 144 rows the bf16x6 ones; attention
+    dropout 0.2 and input dropout 0.25 are live."""
+    from digat_amd import _ctypes_binding as cb, _lib, training
+    L = _lib.lib()
+    g = torch.Generator().manual_seed(B * 1000 + n)
+    p_alpha, p_in, seed, seed_in = 0.2, 0.25, 1234, 4321
+    if B * n >= 2048:
+        assert training._x3_ok(B * n, d, 3 * d)
+    X = torch.randn(B, n, d, generator=g).to(DEV)
+    A = (torch.rand(B, n, n, generator=g) < min(1.0, 6.0 / n)) | torch.eye(n, dtype=torch.bool).unsqueeze(0)
+    A = A.to(torch.uint8).to(DEV).contiguous()
+    ctx, dOut = torch.randn(B, d, generator=g).to(DEV), torch.randn(B, n, d, generator=g).to(DEV)
+    W, F1, F2, F3 = (((torch.randn(d, d, generator=g) * d ** -0.5)).to(DEV) for _ in range(4))
+    bW, b3, a = ((torch.randn(d, generator=g) * 0.1).to(DEV) for _ in range(3))
+    out, save = cb.xattn_fwd_train(X, A, ctx, W, bW, F1, F2, F3, b3, a, p_alpha, seed, p_in, seed_in, None, 0)
+    want = cb.xattn_bwd(dOut, out, X, A, ctx, W, F1, F2, F3, a, p_alpha, p_in, save, None, 0)
+    torch.cuda.synchronize()
+    want = [t.clone() for t in want]
+
+    dd = d * d * 4
+    dF2, dF1, dW = (torch.full((d, d), float("nan"), device=DEV) for _ in range(3))
+    assert not (dF1.data_ptr() == dW.data_ptr() + dd and dF2.data_ptr() == dW.data_ptr() + 2 * dd)     # not the stacked layout
+    dX, dc, dF3 = torch.empty_like(X), torch.empty_like(ctx), torch.empty_like(W)
+    dbW, db3, da = (torch.empty(d, device=DEV) for _ in range(3))
+    nsave, nws = L.digat_xattn_train_save_bytes(B, n, d), L.digat_xattn_train_workspace_bytes(B, n, d)
+    ws = _lib.workspace(nws, X.device, "train")
+    _lib.check(L.digat_xattn_bwd(dOut.data_ptr(), out.data_ptr(), X.data_ptr(), A.data_ptr(), ctx.data_ptr(), W.data_ptr(), F1.data_ptr(),
+                                 F2.data_ptr(), F3.data_ptr(), a.data_ptr(), p_alpha, p_in, save.data_ptr(), nsave, dX.data_ptr(), dc.data_ptr(),
+                                 dW.data_ptr(), dbW.data_ptr(), dF1.data_ptr(), dF2.data_ptr(), dF3.data_ptr(), db3.data_ptr(), da.data_ptr(),
+                                 B, n, d, ws.data_ptr(), nws, None, 0, _lib.stream_ptr()), "digat_xattn_bwd")
+    torch.cuda.synchronize()
+    got = [dX, dc, torch.stack([dW, dF1, dF2]), dbW, dF3, db3, da]
+    for name, x, y in zip(("dX", "dctx", "dW3", "dbW", "dF3", "db3", "da"), got, want):
+        assert torch.isfinite(y).all(), name
+        assert torch.equal(x, y), (name, float((x - y).abs().max()))
+
+
 def test_table_lookup_of_two_id_lists_has_one_dense_gradient_equal_to_two_embedding_backwards():
     """training.TableLookup2 (the table-backed news encoder's two lookups of a training batch, one launch for the table gradient)
     against torch's own embedding backward: many repeated ids (a history repeats news, candidates share neighbours), ids only one
