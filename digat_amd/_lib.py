@@ -107,6 +107,8 @@ _SIGNATURES = {
     "digat_set_train_precision": (C.c_int, [C.c_int]),
     "digat_gather_tables": (C.c_int, [C.POINTER(GatherJob), C.c_int, _f]),
     "digat_user_graph_build": (C.c_int, [_f, _f, C.c_long, C.c_int, C.c_int, _f, _f, _f, _f]),
+    "digat_negative_sample": (C.c_int, [_f, _f, _f, C.c_long, C.c_int, C.c_uint32, C.c_uint32, _f, _f]),
+    "digat_train_batch_ids": (C.c_int, [_f, C.c_long, _f, _f, C.c_long, C.c_int, _f, C.c_long, C.c_int, _f, C.c_long, C.c_int, _f, _f, _f, _f, _f]),
     "digat_profile_live_row_fraction": (C.c_double, []),
     "digat_rank_metrics": (C.c_int, [_f] * 3 + [C.c_int] + [_f] * 4),
     "digat_format_rank_file": (C.c_int64, [_f, _f, C.c_int64, _f, C.c_int64]),

@@ -59,6 +59,8 @@ class Config:
                        help="the graph encoder's projection_mode for dev / test scoring (fp16-fp8c: fp16 + fp8 matrix-core corrections)")
         p.add_argument('--user_graphs', default='table', choices=['table', 'derived'],
                        help='table: user graphs uploaded with the corpus; derived: built on the device per batch from the category indices')
+        p.add_argument('--train_input', default='host', choices=['host', 'device'],
+                       help='host: negative sampling and batch indices in numpy; device: sampled per epoch and assembled per step by HIP kernels')
         a = p.parse_args(argv)
         self.attribute_dict = dict(vars(a))
         for k, v in self.attribute_dict.items():

@@ -14,6 +14,7 @@
 //   digat_train.inc    backward / training kernels;  digat_eval.inc  per-impression ranking + metrics
 //   digat_news.inc     MSA news encoder (inference);  digat_gat.inc  vanilla-GAT layer of the ablation encoders
 //   digat_user_graph.inc  user graphs and category masks from category indices
+//   digat_train_input.inc  the training input: an epoch's negative samples, the index lists of a step
 // This file: shared helpers, the per-kernel profiler, and the C ABI.  The encoder's orchestration is digat_encoder.inc (host
 // code only), and every decision of an encoder call is made in digat_encoder_plan.h (plain C++).
 //
@@ -212,7 +213,7 @@ __device__ __forceinline__ float leaky02_uniform(float e) {
 // Dropout of the training path: a counter-based hash of (seed, flat element index) against floor(p 2^32) — every kernel that applies a
 // dropout (dropout_fwd_kernel and the fused sites: the Eq. 8 scores, the gate, the pooled topics) draws element e's bit from here,
 // so a fused site lands on the elements the stand-alone launch would have (oracle/digat_oracle.py restates it for the tests)
-__device__ __forceinline__ unsigned hash32(unsigned x) {
+__host__ __device__ __forceinline__ unsigned hash32(unsigned x) {
     x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
     return x;
 }
@@ -830,3 +831,4 @@ int digat_row_logits(const float* news_ctx, const float* user_ctx, float* logits
 #include "digat_gat.inc"
 #include "digat_sag.inc"
 #include "digat_user_graph.inc"
+#include "digat_train_input.inc"

@@ -31,8 +31,12 @@ def main(argv=None):
     model = model.to(dev)
     dc = util.DeviceCorpus.from_numpy(corpus, dev, user_graphs=config.user_graphs)
     if config.mode == 'train':
-        trainer = Trainer(model, config, dc, SyntheticTrainSet(corpus, config.negative_sample_num, config.seed),
-                          local_rank=config.local_rank, dev_labels=corpus.row_label)
+        if config.train_input == 'device':
+            from .train_input import DeviceTrainSet
+            train_set = DeviceTrainSet(corpus, config.negative_sample_num, config.seed, dev)
+        else:
+            train_set = SyntheticTrainSet(corpus, config.negative_sample_num, config.seed)
+        trainer = Trainer(model, config, dc, train_set, local_rank=config.local_rank, dev_labels=corpus.row_label)
         trainer.train(max_steps=config.max_steps or None, log_every=50)
         if config.local_rank != -1:
             import torch.distributed as dist

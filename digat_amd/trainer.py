@@ -9,6 +9,8 @@ launched with one process per GPU (:19, :78-80; backend "nccl" is RCCL on ROCm) 
 Real MIND is not reachable from this environment, so the data side is ``SyntheticTrainSet``: behaviours
 with one clicked and ``negative_sample_num`` sampled non-clicked candidates (MIND_dataset.py:26-47),
 indexed into the device-resident synthetic corpus (no DataLoader workers: a batch is a few index_selects).
+``train_input.DeviceTrainSet`` is the same set with its arrays on the device (``--train_input device``): sampling is one
+launch per epoch and a batch two launches per step.
 """
 from __future__ import annotations
 
@@ -51,17 +53,11 @@ class SyntheticTrainSet:
     def __init__(self, corpus, negative_sample_num: int = 4, seed: int = 0):
         self.neg = negative_sample_num
         self.rng = np.random.default_rng(seed)
-        imp, cand, lab = corpus.row_impression, corpus.row_candidate, corpus.row_label
-        bounds = np.r_[0, np.flatnonzero(np.diff(imp)) + 1, len(imp)]
-        self.behaviors = []                                              # (impression, clicked, [non-clicked])
-        for s, e in zip(bounds[:-1], bounds[1:]):
-            pos, negs = cand[s:e][lab[s:e] == 1], cand[s:e][lab[s:e] == 0]
-            if len(negs) == 0:
-                continue
-            for c in pos:
-                self.behaviors.append((int(imp[s]), int(c), negs))
+        from .train_input import behavior_arrays
+        self.impression, click, offsets, pool = behavior_arrays(corpus)
+        self.behaviors = [(int(i), int(c), pool[s:e])                    # (impression, clicked, [non-clicked])
+                          for i, c, s, e in zip(self.impression, click, offsets[:-1], offsets[1:])]
         self.samples = np.zeros((len(self.behaviors), 1 + self.neg), dtype=np.int64)
-        self.impression = np.array([b[0] for b in self.behaviors], dtype=np.int64)
 
     def negative_sampling(self):
         """MIND_dataset.py:26-47: without replacement when the pool is large enough, cyclic otherwise."""
@@ -77,7 +73,7 @@ class SyntheticTrainSet:
 
 
 class Trainer:
-    def __init__(self, model: nn.Module, config, dc: "util.DeviceCorpus", train_set: SyntheticTrainSet,
+    def __init__(self, model: nn.Module, config, dc: "util.DeviceCorpus", train_set,
                  local_rank: int = -1, dev_labels: Optional[np.ndarray] = None, model_dir: Optional[str] = None):
         self.local_rank = local_rank
         self.is_main_rank = local_rank in (-1, 0)
@@ -137,19 +133,30 @@ class Trainer:
             group['lr'] = group['lr'] / 10
 
     def batches(self, epoch: int):
-        n = len(self.train_set)
-        order = np.random.default_rng(1000 + epoch).permutation(n)
+        """The epoch's batches: arrays of behaviour indices, or — a ``train_input.DeviceTrainSet`` — ``(offset, length)`` views
+        into the same order, uploaded once here (both input paths visit identical batches)."""
+        from .train_input import epoch_order
+        world, rank = 1, 0
         if self.local_rank != -1:                                        # DistributedSampler: strided shards
             import torch.distributed as dist
             world, rank = dist.get_world_size(), dist.get_rank()
-            total = (n + world - 1) // world * world
-            order = np.r_[order, order[: total - n]][rank::world]
+        order = epoch_order(len(self.train_set), epoch, world, rank)
+        if getattr(self.train_set, "on_device", False):
+            self.order_dev = torch.from_numpy(np.ascontiguousarray(order, dtype=np.int64)).to(self.dc.news_embedding.device)
+            for s in range(0, len(order), self.batch_size):
+                yield (s, min(self.batch_size, len(order) - s))
+            return
         for s in range(0, len(order), self.batch_size):
             yield order[s:s + self.batch_size]
 
-    def gather(self, idx: np.ndarray):
+    def gather(self, idx):
         """The 9 inputs of Model.forward (trainer.py:88-96) for the behaviours ``idx`` — news ids stand in for
-        title text (the synthetic news 'encoder' is an embedding table)."""
+        title text (the synthetic news 'encoder' is an embedding table).  ``idx``: behaviour indices on the host, or an
+        ``(offset, length)`` view into the order ``batches`` uploaded (a device train set: train_input.device_batch, no host
+        work beyond two launches)."""
+        if getattr(self.train_set, "on_device", False):
+            from .train_input import device_batch
+            return device_batch(self.dc, self.train_set, self.order_dev, int(idx[0]), int(idx[1]))
         dc, dev = self.dc, self.dc.news_embedding.device
         # the step's indices travel as ONE pinned, asynchronous copy: a pageable .to(device) is a blocking copy — the host waits there
         # until the device has drained the previous step, every step (round 5: 1.5 ms of host time per 7 ms step)
@@ -179,7 +186,7 @@ class Trainer:
                 dc.news_graph.index_select(0, news.flatten()).view(B, K, *dc.news_graph.shape[1:]),
                 dc.news_graph_mask.index_select(0, news.flatten()).view(B, K, -1))
 
-    def train_step(self, idx: np.ndarray, read_loss: bool = True):
+    def train_step(self, idx, read_loss: bool = True):
         """One optimisation step (trainer.py:98-105).  ``read_loss`` (default): return the loss as a Python float, as the reference's
         loop reads it every step (``loss.item()``: a host synchronisation per step, which serialises the host's enqueue of the next
         step with the device's work on this one); False: return the loss TENSOR (detached, on the device) and read nothing — the

@@ -760,6 +760,32 @@ int digat_gather_tables(const digat_gather_job* jobs, int njobs, void* stream);
 int digat_user_graph_build(const int64_t* cat_idx, const int64_t* rows, long G, int H, int C, uint8_t* graph, uint8_t* cat_mask,
                            int32_t* entries, void* stream);
 
+/* ---- training input on the device (the counterpart of MIND_dataset.py:26-47 and of its __getitem__ + collate in training) ------
+ * digat_negative_sample: an epoch's samples.  Behaviour i has the clicked news click[i] and the non-clicked pool
+ * pool[pool_offsets[i] .. pool_offsets[i+1]) (CSR, pool_offsets [n+1] non-decreasing) of size m; samples [n, 1+K]:
+ *   samples[i][0] = click[i];   1 <= m <= K: samples[i][1+j] = pool_i[j % m] (the reference's cyclic rule);
+ *   m > K: K distinct members of the pool in draw order, every ordered K-subset equally likely (a partial Fisher-Yates shuffle
+ *   with exactly K draws; the multiply-shift map of a 32-bit word onto the remaining positions is biased by at most m / 2^32);
+ *   m == 0: every column is click[i] (defined; the reference drops such behaviours before it samples).
+ * A draw is a pure function of (seed, epoch, i, draw number) through the dropout path's counter hash, so the result does not
+ * depend on the launch shape (digat_amd/train_input.py: negative_samples_host restates it bit for bit).  One launch on `stream`,
+ * no allocation, no synchronisation.  DIGAT_ERR_ARG: a null pointer, n < 0, K < 1; DIGAT_ERR_SHAPE: K > 16; n == 0 returns
+ * without a launch.
+ * digat_train_batch_ids: the index lists of a step.  Batch row b is behaviour order[b] (order: a device pointer into the
+ * epoch's permutation, B entries read) of the n behaviours impression [n], samples [n, 1+K]:
+ *   imp [B] = impression[order[b]];   news [B (1+K)] = samples[order[b]][k];
+ *   node_ids [B (1+K) N] = news_node_ID[news][t]  (news_node_ID [news_num, N]);   hist [B H] = history[imp][t]  (history
+ *   [impressions, H]).
+ * All int64.  The step's large rows are then gathered by ONE digat_gather_tables call whose jobs index with these lists.  An
+ * index outside its table is clamped into it (no read leaves a table); the caller keeps them inside.  One launch; B == 0
+ * returns without one.  DIGAT_ERR_ARG: a null pointer, a negative size, K < 1, an empty table with B > 0; DIGAT_ERR_SHAPE:
+ * K > 16, N < 1, H < 1. */
+int digat_negative_sample(const int64_t* click, const int64_t* pool_offsets, const int64_t* pool, long n, int K, uint32_t seed,
+                          uint32_t epoch, int64_t* samples, void* stream);
+int digat_train_batch_ids(const int64_t* order, long B, const int64_t* impression, const int64_t* samples, long n, int K,
+                          const int64_t* news_node_ID, long news_num, int N, const int64_t* history, long impressions, int H,
+                          int64_t* imp, int64_t* news, int64_t* node_ids, int64_t* hist, void* stream);
+
 /* ---- measurement aid (not on the reference's surface): per-kernel HIP-event timing ---------------
  * Between start and stop every kernel launch of this library is bracketed by two events recorded
  * on the stream it is launched on.  stop() synchronises and returns, per kernel kind, the summed

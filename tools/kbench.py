@@ -11,6 +11,9 @@
   python tools/kbench.py cnn-train [T ...]   one CNN training step (forward + backward, dropout 0.2), the same way (T = 6 400)
   python tools/kbench.py user-graph [G H C I]   a batch's user graphs: gathered from the [I,U,U] table (digat_gather_tables) vs built
                                              from category indices (digat_user_graph_build), and one build over all I impressions
+  python tools/kbench.py train-input [n_behaviours]   the training input, host path vs device path (train_input.py), alternated,
+                                             median [min, max] of five rounds: one epoch's negative sampling, the enqueue of 200
+                                             steps' inputs, and 60 training steps (B = 64, K = 4; table and derived user graphs)
 Timing with torch events on the current stream, median of --iters launches.
 """
 import os
@@ -538,6 +541,100 @@ def bench_user_graph(G=1024, H=50, C=17, I=73152, rounds=5):
     print(f"  device memory of the table path: {I * (U * U + C1) / 1e6:.0f} MB; derived: 0 (the indices, {I * H * 8 / 1e6:.0f} MB, are needed either way)")
 
 
+def bench_train_input(n_behaviours=20000, rounds=5):
+    """The training input through the host path (trainer.SyntheticTrainSet + Trainer.gather) and the device path
+    (train_input.DeviceTrainSet), in one process, alternated, median [min, max] of ``rounds`` rounds:
+    (a) one epoch's negative sampling over ``n_behaviours`` synthetic behaviours with pools of 4-58 candidates, K = 4: the host
+        loop against one launch (wall time to completion, and the kernel alone between two events);
+    (b) the inputs of 200 consecutive steps, B = 64, K = 4, N = 10, H = 50, C = 17: host time until the last step is enqueued,
+        one synchronisation after it (the time including the drain is printed next to it);
+    (c) 60 training steps (d = 400, three layers) with either input, wall time per step including the drain at the end.
+    (b) and (c) run with the user graphs as a table and derived from the category indices."""
+    import time
+    import types
+    from digat_amd import synthetic, util
+    from digat_amd.model import Model, PrecomputedNewsEncoder
+    from digat_amd.train_input import DeviceTrainSet, negative_samples_host
+    from digat_amd.trainer import SyntheticTrainSet, Trainer
+    dev = torch.device("cuda:0")
+    stat = lambda v: (sorted(v)[len(v) // 2], min(v), max(v))
+    fmt = lambda v, unit: "%.3f %s [%.3f, %.3f]" % (*stat(v)[:1], unit, *stat(v)[1:])
+
+    # (a) sampling
+    rng = np.random.default_rng(11)
+    m = rng.integers(4, 59, size=n_behaviours)
+    rows = int(m.sum()) + n_behaviours
+    lab = np.zeros(rows, dtype=np.int8)
+    starts = np.r_[0, np.cumsum(m + 1)[:-1]]
+    lab[starts] = 1
+    fake = types.SimpleNamespace(row_impression=np.repeat(np.arange(n_behaviours, dtype=np.int64), m + 1),
+                                 row_candidate=rng.integers(1, 65000, size=rows).astype(np.int32), row_label=lab,
+                                 news_node_ID=np.zeros((65000, 1), dtype=np.int64), history=np.zeros((n_behaviours, 1), dtype=np.int32))
+    host_set, dev_set = SyntheticTrainSet(fake, 4, seed=0), DeviceTrainSet(fake, 4, seed=0, device=dev)
+    dev_set.negative_sampling(0)
+    torch.cuda.synchronize()
+    same = np.array_equal(dev_set.samples_host(), negative_samples_host(dev_set.click.cpu().numpy(), dev_set.pool_offsets.cpu().numpy(),
+                                                                        dev_set.pool.cpu().numpy(), 4, 0, 0))
+    th, td, tk = [], [], []
+    for r in range(rounds):
+        t0 = time.perf_counter(); host_set.negative_sampling(); th.append((time.perf_counter() - t0) * 1e3)
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0 = time.perf_counter()
+        a.record(); dev_set.negative_sampling(); b.record()
+        torch.cuda.synchronize()
+        td.append((time.perf_counter() - t0) * 1e3); tk.append(a.elapsed_time(b))
+    print(f"(a) negative sampling, {len(host_set)} behaviours, pools 4-58, K=4 (kernel == numpy restatement: {same})")
+    print(f"    host loop   {fmt(th, 'ms')}  ({stat(th)[0] / len(host_set) * 1e3:.2f} us per behaviour)")
+    print(f"    device call {fmt(td, 'ms')} to completion; the launch between two events {fmt(tk, 'ms')}")
+
+    # (b), (c)
+    spec = synthetic.SynthSpec(news_num=8192, impressions=2048, seed=3)
+    corpus = synthetic.make_corpus(spec)
+    cfg = types.SimpleNamespace(news_encoder="MSA", graph_encoder="DIGAT", news_graph_size=spec.news_graph_size,
+                                max_history_num=spec.max_history_num, category_num=spec.category_num, graph_depth=3, dropout_rate=0.2,
+                                epoch=1, batch_size=64, lr=1e-4, weight_decay=0.0, gradient_clip_norm=1.0)
+    torch.manual_seed(0)
+    model = Model(cfg, news_encoder=PrecomputedNewsEncoder(torch.from_numpy(corpus.news_embedding), trainable=True))
+    model.initialize()
+    model = model.to(dev).train()
+    for user_graphs in ("table", "derived"):
+        dc = util.DeviceCorpus.from_numpy(corpus, dev, user_graphs=user_graphs)
+        dev_set = DeviceTrainSet(corpus, 4, seed=0, device=dev)
+        dev_set.negative_sampling(0)
+        host_set = SyntheticTrainSet(corpus, 4, seed=0)
+        host_set.samples[:] = dev_set.samples_host()
+        trainers = {"host": Trainer(model, cfg, dc, host_set), "device": Trainer(model, cfg, dc, dev_set)}
+        batches = {k: [b for b in t.batches(1) if (b[1] if k == "device" else len(b)) == 64] for k, t in trainers.items()}
+        print(f"user graphs: {user_graphs}; {len(host_set)} behaviours, {len(batches['host'])} full batches of 64, N={spec.news_graph_size} "
+              f"H={spec.max_history_num} C={spec.category_num} d={spec.embedding_dim}")
+        enq, tot = {k: [] for k in trainers}, {k: [] for k in trainers}
+        for r in range(rounds + 1):                                  # round 0 warms both paths
+            for k, t in trainers.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for s in range(200):
+                    out = t.gather(batches[k][s % len(batches[k])])
+                t1 = time.perf_counter()
+                torch.cuda.synchronize()
+                t2 = time.perf_counter()
+                if r:
+                    enq[k].append((t1 - t0) * 1e6 / 200); tot[k].append((t2 - t0) * 1e6 / 200)
+        for k in trainers:
+            print(f"(b) step inputs, {k:6s}: enqueue {fmt(enq[k], 'us')} per step; with the drain {fmt(tot[k], 'us')}")
+        step = {k: [] for k in trainers}
+        for r in range(rounds + 1):
+            for k, t in trainers.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for s in range(60):
+                    t.train_step(batches[k][s % len(batches[k])], read_loss=False)
+                torch.cuda.synchronize()
+                if r:
+                    step[k].append((time.perf_counter() - t0) * 1e3 / 60)
+        for k in trainers:
+            print(f"(c) training step, {k:6s} input: {fmt(step[k], 'ms')} per step (60 steps, one drain)")
+
+
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "xattn"
     nums = [int(v) for v in sys.argv[2:]]
@@ -567,6 +664,8 @@ if __name__ == "__main__":
         bench_topic(*nums)
     elif what == "user-graph":
         bench_user_graph(*nums)
+    elif what == "train-input":
+        bench_train_input(*nums)
     elif what == "linear":
         bench_linear(*nums)
     elif what == "gemm":
