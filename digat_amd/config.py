@@ -24,6 +24,9 @@ class Config:
         p.add_argument('--news_encoder', default='MSA', choices=['MSA', 'CNN'])
         p.add_argument('--graph_encoder', default='DIGAT',
                        choices=['DIGAT', 'wo_SA', 'Seq_SA', 'wo_interaction', 'news_graph_wo_inter', 'user_graph_wo_inter'])
+        p.add_argument('--dev_model_path', type=str, default='best_model/MIND-small/MSA-DIGAT/#1/MSA-DIGAT', help='Dev model path')
+        p.add_argument('--test_model_path', type=str, default='best_model/MIND-small/MSA-DIGAT/#1/MSA-DIGAT', help='Test model path')
+        p.add_argument('--test_output_file', type=str, default='', help='Test output file (the rank file of --mode test)')
         p.add_argument('--seed', type=int, default=0)
         p.add_argument('--local_rank', '--local-rank', type=int, default=int(os.environ.get('LOCAL_RANK', -1)))
         p.add_argument('--dataset', default='MIND-small', choices=['MIND-small', 'MIND-large'])

@@ -621,19 +621,12 @@ int digat_topic_pool_fwd(const float* Xu, const float* kq, const int64_t* cat_id
     return launch_topic(Xu, (long)U * d, kq, cat_idx, out, B, H, C1, d, (hipStream_t)stream);
 }
 
-int digat_user_ctx_fwd(const float* Xu, const uint8_t* cat_mask, const int64_t* cat_idx, const float* c_n,
-                       const float* Ku, const float* Qu, const float* bQu, const float* Fa, const float* bFa,
-                       const float* Kua, const float* Qua, const float* bQua, const float* addend, float* out,
-                       int B, int U, int H, int C1, int d, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!Xu || !cat_mask || !cat_idx || !c_n || !Ku || !Qu || !Fa || !Kua || !Qua || !out || !workspace)
-        return DIGAT_ERR_ARG;
-    if (B < 0 || H < 0 || U < H || C1 <= 0 || d <= 0) return DIGAT_ERR_ARG;
-    if (d % 4 || C1 > DIGAT_MAX_NODES || H > TOPIC_MAX_H) return DIGAT_ERR_SHAPE;
-    Arena ar(workspace, workspace_bytes);
-    const UserCtxWs w = user_ctx_carve(ar, B, C1, d);
-    if (!ar.ok) return DIGAT_ERR_WORKSPACE;
-    if (B == 0) return DIGAT_OK;
-    hipStream_t st = (hipStream_t)stream;
+// the launches of compute_user_graph_context on a carved workspace.  group (optional, [B]): row b's nodes live at
+// Xu + group[b] * U * d (rows of one impression share them: digat_user_ctx_fwd_grouped); everything else is per row
+static int user_ctx_run(const float* Xu, const uint8_t* cat_mask, const int64_t* cat_idx, const int* group, const float* c_n,
+                        const float* Ku, const float* Qu, const float* bQu, const float* Fa, const float* bFa,
+                        const float* Kua, const float* Qua, const float* bQua, const float* addend, float* out,
+                        int B, int U, int H, int C1, int d, const UserCtxWs& w, hipStream_t st) {
     float *qv = w.qv, *kq = w.kq, *T = w.T, *T2 = w.T2;
     int rc;
     // topic-level attention (:126-130)
@@ -641,7 +634,7 @@ int digat_user_ctx_fwd(const float* Xu, const uint8_t* cat_mask, const int64_t* 
     if (rc) return rc;
     rc = launch_gemm(gemm_plain(qv, d, Ku, nullptr, kq, d, B, d, d, 1), st);
     if (rc) return rc;
-    rc = launch_topic(Xu, (long)U * d, kq, cat_idx, T, B, H, C1, d, st);
+    rc = launch_topic(Xu, (long)U * d, kq, cat_idx, T, B, H, C1, d, st, group);
     if (rc) return rc;
     // featureAffine + relu + residual (:131)
     GemmArgs g = gemm_plain(T, d, Fa, bFa, T2, d, B * C1, d, d, 0);
@@ -654,6 +647,22 @@ int digat_user_ctx_fwd(const float* Xu, const uint8_t* cat_mask, const int64_t* 
     rc = launch_gemm(gemm_plain(qv, d, Kua, nullptr, kq, d, B, d, d, 1), st);
     if (rc) return rc;
     return launch_pool(T2, (long)C1 * d, kq, cat_mask, addend, out, B, C1, d, st);
+}
+
+int digat_user_ctx_fwd(const float* Xu, const uint8_t* cat_mask, const int64_t* cat_idx, const float* c_n,
+                       const float* Ku, const float* Qu, const float* bQu, const float* Fa, const float* bFa,
+                       const float* Kua, const float* Qua, const float* bQua, const float* addend, float* out,
+                       int B, int U, int H, int C1, int d, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!Xu || !cat_mask || !cat_idx || !c_n || !Ku || !Qu || !Fa || !Kua || !Qua || !out || !workspace)
+        return DIGAT_ERR_ARG;
+    if (B < 0 || H < 0 || U < H || C1 <= 0 || d <= 0) return DIGAT_ERR_ARG;
+    if (d % 4 || C1 > DIGAT_MAX_NODES || H > TOPIC_MAX_H) return DIGAT_ERR_SHAPE;
+    Arena ar(workspace, workspace_bytes);
+    const UserCtxWs w = user_ctx_carve(ar, B, C1, d);
+    if (!ar.ok) return DIGAT_ERR_WORKSPACE;
+    if (B == 0) return DIGAT_OK;
+    return user_ctx_run(Xu, cat_mask, cat_idx, nullptr, c_n, Ku, Qu, bQu, Fa, bFa, Kua, Qua, bQua, addend, out, B, U, H, C1, d, w,
+                        (hipStream_t)stream);
 }
 
 // ---- folded attention queries (inference): (K x).(Q c + b) = x.(K^T Q c + K^T b) ------------------
@@ -832,3 +841,4 @@ int digat_row_logits(const float* news_ctx, const float* user_ctx, float* logits
 #include "digat_sag.inc"
 #include "digat_user_graph.inc"
 #include "digat_train_input.inc"
+#include "digat_ablation.inc"

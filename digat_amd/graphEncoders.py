@@ -682,7 +682,8 @@ class _Ablation(GraphEncoder):
     and whether the news context exists (``NEWS_CONTEXT``); parameter names are the reference's, so its checkpoints
     load.  Inference / eval-mode forward run on the HIP kernels (``digat_xattn_fwd``, ``digat_gat_fwd``,
     ``digat_news_ctx_fwd``, ``digat_user_ctx_fwd``); training-mode forward (with autograd) goes through
-    ``training.ablation_forward_train`` on the ``digat_*_fwd_train`` / ``digat_*_bwd`` pairs."""
+    ``training.ablation_forward_train`` on the ``digat_*_fwd_train`` / ``digat_*_bwd`` pairs.  ``inference_grouped`` is the
+    scoring pass's entry (util.score_rows): user tensors once per impression, the candidate-independent halves computed once."""
     EQ8: tuple = ()
     GAT: tuple = ()
     NEWS_CONTEXT = True
@@ -806,10 +807,185 @@ class _Ablation(GraphEncoder):
         return self._encode(_lib.f32(news_graph_embeddings), news_graph, news_graph_mask, user_news_embedding, user_graph,
                             user_category_mask, user_category_indices, _lib.f32(news_graph_context))
 
+    # ------------------------------------------------------------------ the scoring pass: what an impression's rows share
+    # What util.GroupedBatchPipeline gathers per ROW for this class: "news_graphs" (neighbourhood embeddings, adjacency, mask),
+    # "c_n0", "ctx_layers" (the candidates' rows of DeviceCorpus.news_ctx_layers).  The user side is always gathered per group.
+    PIPELINE_READS: tuple = ("news_graphs", "c_n0")
+
+    def _user_nodes_dev(self, user_news_embedding, row_group=None):
+        """Xu^(0) in one launch (``digat_user_nodes_build``): [G,U,d] from ``user_news_embedding`` [G,H,d] and the topic
+        embeddings, or — ``row_group`` [B] int32 — the expanded [B,U,d] written directly (no ``cat``, no ``index_select``)."""
+        ue = _lib.f32(user_news_embedding)
+        topic = _lib.f32(self.topic_node_embedding.detach())
+        dev = _lib.require_device(ue, topic) if row_group is None else _lib.require_device(ue, topic, row_group)
+        if ue.data_ptr() % 16:
+            ue = ue.clone()
+        G, H, d = ue.shape
+        C = self.category_num - 1
+        rows = G if row_group is None else int(row_group.shape[0])
+        out = torch.empty((rows, H + C, d), dtype=torch.float32, device=dev)
+        if rows:
+            _lib.check(_lib.lib().digat_user_nodes_build(ue.data_ptr(), topic.data_ptr(), _lib.ptr(row_group), out.data_ptr(), rows, G,
+                                                         H, C, d, _lib.stream_ptr()), "digat_user_nodes_build")
+        return out
+
+    def _user_ctx(self, Xu, user_category_mask, user_category_indices, c_n, acc=None, row_group=None):
+        """``compute_user_graph_context`` added to ``acc`` in place (``addend == out``; ``acc=None``: a new tensor).  With ``row_group``
+        [B] int32 the three user tensors are per GROUP and row b reads the nodes of group ``row_group[b]`` in place
+        (``digat_user_ctx_fwd_grouped``: the bits of the per-row entry on the expanded tensors)."""
+        Xu, c_n = _lib.f32(Xu), _lib.f32(c_n)
+        dev = _lib.require_device(Xu, user_category_mask, user_category_indices, c_n)
+        B, d = c_n.shape
+        U, H, C1 = Xu.shape[1], self.max_history_num, self.category_num
+        mask = _lib.as_bytes(user_category_mask)
+        idx = user_category_indices.to(torch.int64).contiguous()
+        out = acc if acc is not None else torch.empty((B, d), dtype=torch.float32, device=dev)
+        if B == 0:
+            return out
+        L = _lib.lib()
+        ua = self.userAttention
+        weights = (self.user_news_K.weight.data_ptr(), self.user_news_Q.weight.data_ptr(), self.user_news_Q.bias.data_ptr(),
+                   self.featureAffine.weight.data_ptr(), self.featureAffine.bias.data_ptr(), ua.K.weight.data_ptr(),
+                   ua.Q.weight.data_ptr(), ua.Q.bias.data_ptr())
+        if row_group is None:
+            nbytes = L.digat_user_ctx_workspace_bytes(B, U, H, C1, d)
+            ws = _lib.workspace(nbytes, dev, "ctx")
+            _lib.check(L.digat_user_ctx_fwd(Xu.data_ptr(), mask.data_ptr(), idx.data_ptr(), c_n.data_ptr(), *weights, _lib.ptr(acc),
+                                            out.data_ptr(), B, U, H, C1, d, ws.data_ptr(), nbytes, _lib.stream_ptr()),
+                       "digat_user_ctx_fwd")
+            return out
+        G = Xu.shape[0]
+        nbytes = L.digat_user_ctx_grouped_workspace_bytes(B, G, U, H, C1, d)
+        ws = _lib.workspace(nbytes, dev, "ctx")
+        _lib.check(L.digat_user_ctx_fwd_grouped(Xu.data_ptr(), mask.data_ptr(), idx.data_ptr(), row_group.data_ptr(), c_n.data_ptr(),
+                                                *weights, _lib.ptr(acc), out.data_ptr(), B, G, U, H, C1, d, ws.data_ptr(), nbytes,
+                                                _lib.stream_ptr()), "digat_user_ctx_fwd_grouped")
+        return out
+
+    @staticmethod
+    def _expand_rows(table, rows64):
+        """``table.index_select(0, rows64)`` of a bool / byte table through ``digat_gather_tables`` (the groups' adjacency, per row)."""
+        t = _lib.as_bytes(table)
+        out = torch.empty((rows64.shape[0],) + tuple(t.shape[1:]), dtype=torch.uint8, device=t.device)
+        if out.numel():
+            job = (_lib.GatherJob * 1)(_lib.GatherJob(t.data_ptr(), out.data_ptr(), t[0].numel(), rows64.shape[0], rows64.data_ptr(), None, 1))
+            _lib.check(_lib.lib().digat_gather_tables(job, 1, _lib.stream_ptr()), "digat_gather_tables")
+        return out
+
+    def news_context_layers(self, news_graph_embeddings, news_graph, news_graph_mask, news_graph_context=None):
+        """c_n^(0..L) of M news as one [L+1, M, d] tensor, for the classes whose news graph runs the vanilla GAT layer: the chain
+        depends on the news alone (``util.prepare_news_side`` keeps it per news).  Prefix sums in ``inference``'s order."""
+        if "news" not in self.GAT:
+            raise _lib.DigatHipError(type(self).__name__ + ": the news context depends on the user side")
+        X = _lib.f32(news_graph_embeddings)
+        c = (self.compute_news_graph_context(X, news_graph_mask) if news_graph_context is None else _lib.f32(news_graph_context))
+        out = torch.empty((self.graph_depth + 1,) + tuple(c.shape), dtype=torch.float32, device=c.device)
+        out[0] = c
+        for i in range(self.graph_depth):
+            X = self._gat("news", i, X, news_graph)
+            c = c + self.compute_news_graph_context(X, news_graph_mask)
+            out[i + 1] = c
+        return out
+
+    def news_side_tables(self, SA_news_representations, news_graph, news_graph_mask, batch_size: int):
+        """``(c_n0 [news_num, d], news_ctx_layers [K, news_num, d] or None)`` for ``util.prepare_news_side``: whatever of this
+        class's news side is a function of the news id alone, computed in chunks."""
+        SA = SA_news_representations
+        news_num, _, d = SA.shape
+        c_n0 = torch.empty((news_num, d), dtype=torch.float32, device=SA.device)
+        layers = None
+        if "news" in self.GAT:
+            layers = torch.empty((self.graph_depth + 1, news_num, d), dtype=torch.float32, device=SA.device)
+        chunk = max(1, int(batch_size))
+        for s in range(0, news_num, chunk):
+            e = min(s + chunk, news_num)
+            c_n0[s:e] = self.compute_news_graph_context(SA[s:e], news_graph_mask[s:e])
+        if layers is not None:
+            chunk = max(chunk, 4096)
+            for s in range(0, news_num, chunk):
+                e = min(s + chunk, news_num)
+                layers[:, s:e] = self.news_context_layers(SA[s:e], news_graph[s:e], news_graph_mask[s:e], c_n0[s:e])
+        return c_n0, layers
+
+    def _grouped(self, Xn, An, Mn, ue, Xu0, Au, cm, ci, rg, rg64, c_n, layers):
+        """The class's pass over B rows of G groups (``inference_grouped``): ``ue`` [G,H,d] and ``Xu0`` [G,U,d] built from it, the
+        user tensors per group, ``rg`` / ``rg64`` the row -> group map as int32 / int64."""
+        raise NotImplementedError
+
+    def inference_grouped(self, news_graph_embeddings, news_graph, news_graph_mask, user_news_embedding, user_graph,
+                          user_category_mask, user_category_indices, row_group, news_graph_context, *, news_ctx_layers=None,
+                          news_index=None):
+        """``inference`` for rows that share users: the four user tensors once per GROUP ([G,...]), ``row_group`` [B] mapping each
+        row to its group (any mapping).  What does not depend on the candidate is computed once per group — the vanilla GAT layers
+        of the user graph, Xu^(0) — and the user contexts on such features read them in place (``digat_user_ctx_fwd_grouped``).
+        ``news_ctx_layers`` [K, B, d]: the rows' c_n^(0..L) (``news_context_layers``; wo_SA: K = 1, the candidate's own
+        representation) — the news-side tensors may then be None for the classes that read nothing else of them.
+        ``news_index`` [B] int64: ``news_graph_embeddings`` / ``news_ctx_layers`` are the per-news tables and row b is their row
+        ``news_index[b]``.  Too few rows per group (4 G > B), an empty batch or training mode: expands and calls ``inference``."""
+        user_graph, user_category_mask = derive_user_graph(user_graph, user_category_mask, user_category_indices, self.category_num - 1)
+        ue = _lib.f32(user_news_embedding)
+        dev = _lib.require_device(ue, user_graph, user_category_mask, user_category_indices, row_group)
+        B, G = int(row_group.shape[0]), int(ue.shape[0])
+        Xn, layers = news_graph_embeddings, news_ctx_layers
+        if news_index is not None:
+            ni = news_index.long()
+            Xn = None if Xn is None else Xn.index_select(0, ni)
+            layers = None if layers is None else layers.index_select(1, ni)
+        if B == 0 or 4 * G > B or self.training:
+            if Xn is None or news_graph is None or news_graph_mask is None or news_graph_context is None:
+                raise ValueError("inference_grouped: the per-row path needs the news-side tensors")
+            rg = row_group.long()
+            return self.inference(Xn, news_graph, news_graph_mask, ue.index_select(0, rg), user_graph.index_select(0, rg),
+                                  user_category_mask.index_select(0, rg), user_category_indices.index_select(0, rg),
+                                  news_graph_context)
+        rg64 = row_group.to(torch.int64).clamp(0, G - 1)          # the gathers below index with it: no read leaves the groups' buffers
+        rg = rg64.to(torch.int32)
+        if layers is not None:
+            layers = _lib.f32(layers)
+            if layers.dim() != 3 or layers.shape[1] != B:
+                raise ValueError("news_ctx_layers must be [K, B, d] (or the [K, news_num, d] table with news_index)")
+        c_n = None if news_graph_context is None else _lib.f32(news_graph_context)
+        reads = self.PIPELINE_READS
+        if ("news_graphs" in reads or ("ctx_layers" in reads and layers is None)) and (
+                Xn is None or news_graph is None or news_graph_mask is None):
+            raise ValueError(type(self).__name__ + ".inference_grouped: the news-graph tensors may only be None with news_ctx_layers")
+        if "c_n0" in reads and c_n is None:
+            raise ValueError(type(self).__name__ + ".inference_grouped needs news_graph_context")
+        return self._grouped(None if Xn is None else _lib.f32(Xn), news_graph, news_graph_mask, ue, self._user_nodes_dev(ue), user_graph,
+                             user_category_mask, user_category_indices, rg, rg64, c_n, layers)
+
+    def _eq8_user_rows(self, ue, rg, Au, cm, ci, rg64):
+        """The per-row inputs of the user graph's Eq. 8 layers: expanded Xu^(0) (written directly), adjacency, mask, indices."""
+        return (self._user_nodes_dev(ue, rg), self._expand_rows(Au, rg64), _lib.as_bytes(cm).index_select(0, rg64),
+                ci.index_select(0, rg64))
+
+    def _gat_user_layers(self, Xu0, Au):
+        """Xu^(0..L) of the G groups: the vanilla GAT layers of the user graph see nothing of the candidate."""
+        Xs = [Xu0]
+        for i in range(self.graph_depth):
+            Xs.append(self._gat("user", i, Xs[-1], Au))
+        return Xs
+
 
 class wo_SA(_Ablation):
     """graphEncoders.py:201-293 — no semantic-augmentation graph: the candidate's own representation is the context."""
     EQ8, GAT, NEWS_CONTEXT = ("user",), (), False
+    PIPELINE_READS = ("ctx_layers",)
+
+    def news_side_tables(self, SA_news_representations, news_graph, news_graph_mask, batch_size: int):
+        """No news context exists: c_n0 is a zero table that is never read, and the one "layer" is the candidate's own
+        representation (node 0 of its neighbourhood), so that a pass gathers d floats per row instead of N d."""
+        SA = SA_news_representations
+        return torch.zeros((SA.shape[0], SA.shape[2]), dtype=torch.float32, device=SA.device), SA[:, 0].contiguous().unsqueeze(0)
+
+    def _grouped(self, Xn, An, Mn, ue, Xu0, Au, cm, ci, rg, rg64, c_n, layers):
+        c = layers[0] if layers is not None else Xn[:, 0].contiguous()
+        if self.graph_depth == 0:
+            return c, self._user_ctx(Xu0, cm, ci, c, row_group=rg)
+        Xu, Au_r, cm_r, ci_r = self._eq8_user_rows(ue, rg, Au, cm, ci, rg64)
+        for i in range(self.graph_depth):
+            Xu = self._layer("user", i, Xu, Au_r, c)
+        return c, self._user_ctx(Xu, cm_r, ci_r, c)
 
     def compute_user_graph_embeddings(self, index, user_graph_embeddings, user_graph, news_graph_context):
         return self._layer("user", index, user_graph_embeddings, user_graph, news_graph_context)
@@ -839,6 +1015,16 @@ class wo_SA(_Ablation):
 class Seq_SA(_Ablation):
     """graphEncoders.py:295-408 — the neighbourhood as a sequence: pooled once into the news context, never updated."""
     EQ8, GAT = ("user",), ()
+    PIPELINE_READS = ("c_n0",)
+
+    def _grouped(self, Xn, An, Mn, ue, Xu0, Au, cm, ci, rg, rg64, c_n, layers):
+        c_u = self._user_ctx(Xu0, cm, ci, c_n, row_group=rg)
+        if self.graph_depth:
+            Xu, Au_r, cm_r, ci_r = self._eq8_user_rows(ue, rg, Au, cm, ci, rg64)
+            for i in range(self.graph_depth):
+                Xu = self._layer("user", i, Xu, Au_r, c_n)
+                self._user_ctx(Xu, cm_r, ci_r, c_n, acc=c_u)
+        return c_n, c_u
 
     def compute_news_sequence_context(self, news_graph_embeddings, news_graph_mask):
         return self.compute_news_graph_context(news_graph_embeddings, news_graph_mask)
@@ -858,6 +1044,15 @@ class Seq_SA(_Ablation):
 class wo_interaction(_Ablation):
     """graphEncoders.py:410-549 — vanilla GAT layers on both graphs."""
     EQ8, GAT = (), ("news", "user")
+    PIPELINE_READS = ("ctx_layers",)
+
+    def _grouped(self, Xn, An, Mn, ue, Xu0, Au, cm, ci, rg, rg64, c_n, layers):
+        if layers is None:
+            layers = self.news_context_layers(Xn, An, Mn, c_n)
+        c_u = None
+        for i, Xu in enumerate(self._gat_user_layers(Xu0, Au)):          # c_u = sum_i ctx(Xu^(i)[g], c_n^(i)[cand]), left to right
+            c_u = self._user_ctx(Xu, cm, ci, layers[i], acc=c_u, row_group=rg)
+        return layers[self.graph_depth], c_u
 
     def compute_news_graph_embeddings(self, index, news_graph_embeddings, news_graph):
         return self._gat("news", index, news_graph_embeddings, news_graph)
@@ -869,6 +1064,18 @@ class wo_interaction(_Ablation):
 class News_graph_wo_inter(_Ablation):
     """graphEncoders.py:551-696 — vanilla GAT on the news graph, Eq. 8 on the user graph."""
     EQ8, GAT = ("user",), ("news",)
+    PIPELINE_READS = ("ctx_layers",)
+
+    def _grouped(self, Xn, An, Mn, ue, Xu0, Au, cm, ci, rg, rg64, c_n, layers):
+        if layers is None:
+            layers = self.news_context_layers(Xn, An, Mn, c_n)
+        c_u = self._user_ctx(Xu0, cm, ci, layers[0], row_group=rg)
+        if self.graph_depth:
+            Xu, Au_r, cm_r, ci_r = self._eq8_user_rows(ue, rg, Au, cm, ci, rg64)
+            for i in range(self.graph_depth):
+                Xu = self._layer("user", i, Xu, Au_r, layers[i])
+                self._user_ctx(Xu, cm_r, ci_r, layers[i + 1], acc=c_u)
+        return layers[self.graph_depth], c_u
 
     def compute_news_graph_embeddings(self, index, news_graph_embeddings, news_graph):
         return self._gat("news", index, news_graph_embeddings, news_graph)
@@ -880,6 +1087,16 @@ class News_graph_wo_inter(_Ablation):
 class User_graph_wo_inter(_Ablation):
     """graphEncoders.py:698-842 — Eq. 8 on the news graph, vanilla GAT on the user graph."""
     EQ8, GAT = ("news",), ("user",)
+    PIPELINE_READS = ("news_graphs", "c_n0")
+
+    def _grouped(self, Xn, An, Mn, ue, Xu0, Au, cm, ci, rg, rg64, c_n, layers):
+        Xs = self._gat_user_layers(Xu0, Au)
+        c_u = self._user_ctx(Xs[0], cm, ci, c_n, row_group=rg)
+        for i in range(self.graph_depth):
+            Xn = self._layer("news", i, Xn, An, c_u)
+            c_n = c_n + self.compute_news_graph_context(Xn, Mn)
+            self._user_ctx(Xs[i + 1], cm, ci, c_n, acc=c_u, row_group=rg)
+        return c_n, c_u
 
     def compute_news_graph_embeddings(self, index, news_graph_embeddings, news_graph, user_graph_context):
         return self._layer("news", index, news_graph_embeddings, news_graph, user_graph_context)

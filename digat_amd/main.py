@@ -1,8 +1,10 @@
 """Entry point: ``python -m digat_amd.main --mode={train,dev,test} --graph_encoder=DIGAT ...``
 
 The counterpart of the reference's ``main.py`` on a synthetic MIND-shaped corpus: ``train`` runs the
-``Trainer`` (DDP when launched with one process per GPU) and then scores the dev rows; ``dev`` / ``test``
-score them and print AUC / MRR / nDCG@5 / nDCG@10 and the inference time (main.py:66-72).
+``Trainer`` (DDP when launched with one process per GPU) and then scores the dev rows; ``dev`` / ``test`` load
+``--dev_model_path`` / ``--test_model_path`` (the ``{model_name: state_dict}`` file the ``Trainer`` writes, main.py:23,36),
+score the rows and print AUC / MRR / nDCG@5 / nDCG@10 and the inference time (main.py:66-72); ``test`` writes the rank file
+to ``--test_output_file`` when one is named.
 """
 from __future__ import annotations
 
@@ -14,6 +16,16 @@ from . import synthetic, util
 from .config import Config
 from .model import Model, PrecomputedNewsEncoder
 from .trainer import SyntheticTrainSet, Trainer
+
+
+def load_checkpoint(model, path: str) -> None:
+    """Load the ``{model_name: state_dict}`` file ``Trainer`` writes (trainer.py:169-170, :188) into ``model``, as the
+    reference's dev / test modes do (main.py:23,36).  A file that does not hold this model's name is an error."""
+    saved = torch.load(path, map_location=torch.device('cpu'))
+    if not isinstance(saved, dict) or model.model_name not in saved:
+        have = sorted(map(str, saved)) if isinstance(saved, dict) else type(saved).__name__
+        raise KeyError(f"{path} holds no state dict for '{model.model_name}' (found: {have})")
+    model.load_state_dict(saved[model.model_name])
 
 
 def main(argv=None):
@@ -28,6 +40,8 @@ def main(argv=None):
     model = Model(config, news_encoder=PrecomputedNewsEncoder(torch.from_numpy(corpus.news_embedding),
                                                               trainable=config.mode == 'train'))
     model.initialize()
+    if config.mode in ('dev', 'test'):
+        load_checkpoint(model, config.dev_model_path if config.mode == 'dev' else config.test_model_path)
     model = model.to(dev)
     dc = util.DeviceCorpus.from_numpy(corpus, dev, user_graphs=config.user_graphs)
     if config.mode == 'train':
@@ -49,7 +63,8 @@ def main(argv=None):
         dc.news_embedding = model.news_encoder.table.detach()
         if hasattr(model.graph_encoder, 'projection_mode'):      # the public switch of the scoring run's projection format
             model.graph_encoder.projection_mode = config.inference_projection
-        scores, metrics = util.compute_scores(model, dc, config.batch_size * 16, labels=corpus.row_label)
+        result_file = config.test_output_file if config.mode == 'test' and config.test_output_file else None
+        scores, metrics = util.compute_scores(model, dc, config.batch_size * 16, labels=corpus.row_label, result_file=result_file)
         print('AUC : %.4f\nMRR : %.4f\nnDCG@5 : %.4f\nnDCG@10 : %.4f' % metrics)
         print('Inference time : %.1fs' % (time.time() - start))
 

@@ -49,7 +49,9 @@ class DeviceCorpus:
     user_hpq0: Optional[torch.Tensor] = None                 # [3, news_num, d]: layer 0's user-graph [h|P|Q] of every news as a history node
     topic_hpq0: Optional[torch.Tensor] = None                # [3, C, d]: ... of the topic nodes
     ctxq0: Optional[torch.Tensor] = None                     # [3, news_num, d]: topic query | user query | layer-0 user K3 of every c_n0
-    weights_key: Optional[tuple] = None                      # the weight version the five caches above were computed from
+    news_ctx_layers: Optional[torch.Tensor] = None           # [K, news_num, d]: an ablation encoder's per-news contexts c_n^(0..L)
+                                                             # (graphEncoders._Ablation.news_side_tables)
+    weights_key: Optional[tuple] = None                      # the weight version the six caches above were computed from
     title_text: Optional[torch.Tensor] = None                # [news_num, Lw] int32 token ids (MIND_corpus.py: news_title_text)
     title_mask: Optional[torch.Tensor] = None                # [news_num, Lw] bool                       (news_title_mask)
     news_key: Optional[tuple] = None                         # the news-encoder weight version news_embedding was computed from
@@ -223,12 +225,20 @@ def prepare_news_side(encoder, dc: DeviceCorpus, batch_size: int) -> None:
         # the range of the node features the projections will see ("auto" projection format: graphEncoders.resolved_projection_mode)
         encoder.corpus_activation_max = float(dc.news_embedding.abs().max())
     dc.SA_news_representations = dc.news_embedding.index_select(0, dc.news_node_ID.flatten()).view(news_num, N, d)
-    c_n0 = torch.empty((news_num, d), dtype=torch.float32, device=dc.news_embedding.device)
-    with torch.no_grad():
-        for s in range(0, news_num, batch_size):
-            e = min(s + batch_size, news_num)
-            c_n0[s:e] = encoder.compute_news_graph_context(dc.SA_news_representations[s:e], dc.news_graph_mask[s:e])
-    dc.c_n0 = c_n0
+    dc.news_ctx_layers = None
+    if hasattr(encoder, "news_side_tables"):
+        # an ablation encoder names what of its news side depends on the news alone: c_n0 (a zero table where no news context
+        # exists) and, where the news graph never sees the user, the whole chain c_n^(0..L) — 417 MB at MIND-small, depth 3; built
+        # here once per dev run, in chunks, never on the pass
+        with torch.no_grad():
+            dc.c_n0, dc.news_ctx_layers = encoder.news_side_tables(dc.SA_news_representations, dc.news_graph, dc.news_graph_mask, batch_size)
+    else:
+        c_n0 = torch.empty((news_num, d), dtype=torch.float32, device=dc.news_embedding.device)
+        with torch.no_grad():
+            for s in range(0, news_num, batch_size):
+                e = min(s + batch_size, news_num)
+                c_n0[s:e] = encoder.compute_news_graph_context(dc.SA_news_representations[s:e], dc.news_graph_mask[s:e])
+        dc.c_n0 = c_n0
     # ... and, in the same spirit, layer 0's projections of the news graph, which depend on the news alone (small news graphs:
     # the kernel that consumes them adds K3 itself).  [3, news_num, N, d] fp32: 3.1 GB for MIND-small at N = 10.
     # Larger news graphs (N = 26, 65) keep the table too when their Eq. 8 runs on the sparse kernel, which reads the candidates' rows
@@ -342,8 +352,11 @@ class GroupedBatchPipeline:
     (``score_rows`` passes its lane count; with two sets a third lane only overlapped its prologue)."""
 
     def __init__(self, dc: DeviceCorpus, batches, row_impression_host: np.ndarray, nsets: int = 2, in_place_tables: bool = True,
-                 news_sparse: Optional[bool] = None):
-        """``news_sparse``: whether the encoder's Eq. 8 of the NEWS graph resolves to the sparse kernel at call time — the only
+                 news_sparse: Optional[bool] = None, reads: Optional[tuple] = None):
+        """``reads``: what the encoder reads per row, of "news_graphs" (neighbourhood embeddings, adjacency, mask), "c_n0" and
+        "ctx_layers" (the candidates' rows of ``dc.news_ctx_layers``) — an ablation encoder's ``PIPELINE_READS``; what is not named
+        is not gathered and ``take`` hands out None in its place.  None (DIGAT): the news graphs and c_n0.
+        ``news_sparse``: whether the encoder's Eq. 8 of the NEWS graph resolves to the sparse kernel at call time — the only
         reader that can take layer 0 of news graphs of more than 16 nodes from the per-news table; False leaves the table unused
         (in-batch projection).  None: trust the table's presence (prepare_news_side built it under the sparse mode)."""
         self.dc, self.batches = dc, list(batches)
@@ -362,6 +375,12 @@ class GroupedBatchPipeline:
         in_place_tables = in_place_tables and os.environ.get("DIGAT_IN_PLACE", "1") != "0"          # A/B switch for measurements
         in_place = dc.news_hpq0 is not None and d % 4 == 0 and d <= 1024 and in_place_tables and not (N > 16 and news_sparse is False)
         gathered_tables = dc.news_hpq0 is not None and not in_place and N <= 16        # larger news graphs: in place or not at all
+        if reads is not None and "ctx_layers" in reads and dc.news_ctx_layers is None:
+            reads = None                          # no per-news context table (prepare_news_side has not run): the encoder computes the chain in-batch
+        want_graphs = reads is None or "news_graphs" in reads
+        want_c0 = reads is None or "c_n0" in reads
+        self.ctx_layers = dc.news_ctx_layers if (reads is not None and "ctx_layers" in reads) else None
+        K = 0 if self.ctx_layers is None else int(self.ctx_layers.shape[0])
 
         def bufs():
             return dict(hist=torch.empty((Gmax, H), dtype=torch.int64, device=dev),
@@ -369,10 +388,11 @@ class GroupedBatchPipeline:
                         user_graph=torch.empty((Gmax, U, U), dtype=ug_dtype, device=dev),
                         cat_mask=torch.empty((Gmax, C1), dtype=cm_dtype, device=dev),
                         cat_idx=torch.empty((Gmax, H), dtype=torch.int64, device=dev),
-                        sa=(torch.empty((B, N, d), dtype=torch.float32, device=dev) if not in_place else None),
-                        news_graph=torch.empty((B, N, N), dtype=dc.news_graph.dtype, device=dev),
-                        news_mask=torch.empty((B, N), dtype=dc.news_graph_mask.dtype, device=dev),
-                        c_n0=torch.empty((B, d), dtype=torch.float32, device=dev),
+                        sa=(torch.empty((B, N, d), dtype=torch.float32, device=dev) if not in_place and want_graphs else None),
+                        news_graph=(torch.empty((B, N, N), dtype=dc.news_graph.dtype, device=dev) if want_graphs else None),
+                        news_mask=(torch.empty((B, N), dtype=dc.news_graph_mask.dtype, device=dev) if want_graphs else None),
+                        c_n0=(torch.empty((B, d), dtype=torch.float32, device=dev) if want_c0 else None),
+                        ctx_layers=(torch.empty((K * B * d,), dtype=torch.float32, device=dev) if K else None),
                         hpq=(torch.empty((3 * B * N * d,), dtype=torch.float32, device=dev) if gathered_tables else None),
                         hist_hpq=(torch.empty((3 * Gmax * H * d,), dtype=torch.float32, device=dev) if dc.user_hpq0 is not None else None),
                         ctxq=(torch.empty((3 * B * d,), dtype=torch.float32, device=dev) if dc.ctxq0 is not None else None))
@@ -434,9 +454,14 @@ class GroupedBatchPipeline:
             job(dc.user_category_indices.data_ptr(), b["cat_idx"].data_ptr(), rowb(dc.user_category_indices), G, uniq_ptr)
             if b["sa"] is not None:
                 job(dc.SA_news_representations.data_ptr(), b["sa"].data_ptr(), rowb(dc.SA_news_representations), n, cand_ptr)
-            job(dc.news_graph.data_ptr(), b["news_graph"].data_ptr(), rowb(dc.news_graph), n, cand_ptr)
-            job(dc.news_graph_mask.data_ptr(), b["news_mask"].data_ptr(), rowb(dc.news_graph_mask), n, cand_ptr)
-            job(dc.c_n0.data_ptr(), b["c_n0"].data_ptr(), d * 4, n, cand_ptr)
+            if b["news_graph"] is not None:
+                job(dc.news_graph.data_ptr(), b["news_graph"].data_ptr(), rowb(dc.news_graph), n, cand_ptr)
+                job(dc.news_graph_mask.data_ptr(), b["news_mask"].data_ptr(), rowb(dc.news_graph_mask), n, cand_ptr)
+            if b["c_n0"] is not None:
+                job(dc.c_n0.data_ptr(), b["c_n0"].data_ptr(), d * 4, n, cand_ptr)
+            if b["ctx_layers"] is not None:
+                for t in range(self.ctx_layers.shape[0]):      # [K, n, d] <- news_ctx_layers[t][candidate]
+                    job(self.ctx_layers[t].data_ptr(), b["ctx_layers"].data_ptr() + 4 * t * n * d, d * 4, n, cand_ptr)
             if b["hist_hpq"] is not None:
                 for t in range(3):             # [3, G*H, d] <- user_hpq0[t][history of the impression]
                     job(dc.user_hpq0[t].data_ptr(), b["hist_hpq"].data_ptr() + 4 * t * G * H * d, d * 4, G * H, uniq_ptr, hist_tab, H)
@@ -464,9 +489,15 @@ class GroupedBatchPipeline:
         b = self.sets[par]
         torch.cuda.current_stream(self.dev).wait_event(self.ready[par])
         s0, e0 = self.batches[k]
-        sa = b["sa"][:n] if b["sa"] is not None else self.dc.SA_news_representations
+
+        def rows(t):
+            return t[:n] if t is not None else None
+        sa = b["sa"][:n] if b["sa"] is not None else (self.dc.SA_news_representations if self.in_place else None)
         out = (b["user_rep"][:G], b["user_graph"][:G], b["cat_mask"][:G], b["cat_idx"][:G], row_group,
-               sa, b["news_graph"][:n], b["news_mask"][:n], b["c_n0"][:n])
+               sa, rows(b["news_graph"]), rows(b["news_mask"]), rows(b["c_n0"]))
+        if b["ctx_layers"] is not None:          # an ablation encoder: no layer-0 tables, the candidates' context rows instead
+            K_ = self.ctx_layers.shape[0]
+            return out + (None, None, None, None, None, b["ctx_layers"][:K_ * n * self.dc.news_embedding.shape[1]].view(K_, n, -1))
         N_, d_ = self.dc.news_graph.shape[1], self.dc.news_embedding.shape[1]
         H_ = b["hist"].shape[1]
         news_hpq = b["hpq"][:3 * n * N_ * d_].view(3, n, N_, d_) if b["hpq"] is not None else (self.dc.news_hpq0 if self.in_place else None)
@@ -559,7 +590,9 @@ def score_rows(model, dc: DeviceCorpus, start: int, end: int, batch_size: int, g
                streams: int = 3, in_place_tables: bool = True, launch_rows: Optional[int] = None,
                check_range: bool = True) -> torch.Tensor:
     """Scores of rows [start, end): the hot loop of util.py:51-69.  ``grouped`` passes each impression's user
-    tensors once (bit-identical scores, less work in layer 0); it needs ``model.inference_grouped``.  ``streams``:
+    tensors once (DIGAT: bit-identical scores, less work in layer 0; the ablation encoders: what does not depend on the
+    candidate once per impression or per news); it needs the graph encoder's ``inference_grouped``.  ``grouped=False`` is the
+    per-row entry, for every encoder.  ``streams``:
     consecutive launch sets alternate over this many HIP streams (same kernels, same bits: see ``batch_streams``).
     ``batch_size`` is the reference's dev batch; ``launch_rows`` (default ``LAUNCH_ROWS``) how many rows — whole batches — one
     pass through the encoder takes (``launch_rows=batch_size``: the reference's own chunking).
@@ -601,9 +634,11 @@ def _range_fallback(enc, dc, batch_size):
 def _score_rows_once(model, dc, start, end, batch_size, grouped, streams, in_place_tables, launch_rows):
     dev = dc.news_embedding.device
     scores = torch.empty(end - start, dtype=torch.float32, device=dev)
-    grouped = grouped and hasattr(model, "inference_grouped")
     batches = launch_batches(start, end, batch_size, launch_rows)
     enc = getattr(model, "graph_encoder", None)
+    # the grouped route needs the GRAPH ENCODER's grouped entry (Model.inference_grouped only forwards to it); a model without a
+    # graph encoder is taken at its word
+    grouped = grouped and hasattr(model, "inference_grouped") and (enc is None or hasattr(enc, "inference_grouped"))
     if enc is not None:
         apply_corpus_hint(enc, dc)
     if hasattr(enc, "pass_rows") and batches:
@@ -632,7 +667,7 @@ def _score_sets(model, dc, start, batches, scores, lanes, grouped, in_place_tabl
     with torch.no_grad():
         news_sparse = (enc.resolved_xattn_mode("news") == "sparse") if hasattr(enc, "resolved_xattn_mode") else None
         pipe = (GroupedBatchPipeline(dc, batches, dc.row_impression.cpu().numpy(), nsets=len(lanes), in_place_tables=in_place_tables,
-                                     news_sparse=news_sparse)
+                                     news_sparse=news_sparse, reads=getattr(enc, "PIPELINE_READS", None))
                 if grouped and batches else None)
         # the parameter block (split weights, folded queries) is (re)built on the first lane BEFORE the other lanes are
         # ordered after it: a rebuild inside the loop would run on one lane while the next batch reads it on the other

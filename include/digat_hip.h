@@ -140,6 +140,31 @@ int digat_user_ctx_fwd(const float* Xu, const uint8_t* cat_mask, const int64_t* 
                        const float* addend, float* out, int B, int U, int H, int C1, int d,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* digat_user_ctx_fwd for rows that SHARE node features (the ablation encoders' scoring pass: the user graph of an impression does
+ * not depend on the candidate there, graphEncoders._Ablation.inference_grouped).  Xu [G,U,d], cat_mask [G,C1] and cat_idx [G,H]
+ * are given per GROUP; row_group [B] int32 maps each row to its group (any mapping with values in [0, G): not only ascending
+ * runs; a value outside is held inside, so that no read leaves the groups' buffers); c_n, addend and out are [B,d] per row.
+ * Bit-identical to digat_user_ctx_fwd on the expanded tensors: the [B,d] query chain, the featureAffine GEMM and the SDPA pooling
+ * are the same launches on the same rows, the topic pooling reads row b's nodes at Xu + row_group[b] U d.  No [B,U,d] copy of the
+ * node features is made (the workspace holds per-row copies of the category indices and mask bytes: B (8 H + C1 + 4) bytes).
+ * addend may be NULL or == out.  B == 0 returns without a launch.  Errors as digat_user_ctx_fwd, and DIGAT_ERR_ARG for a null
+ * row_group or G <= 0 with B > 0.  No allocation, no host synchronisation. */
+size_t digat_user_ctx_grouped_workspace_bytes(int B, int G, int U, int H, int C1, int d);
+int digat_user_ctx_fwd_grouped(const float* Xu, const uint8_t* cat_mask, const int64_t* cat_idx, const int32_t* row_group,
+                               const float* c_n,
+                               const float* Ku, const float* Qu, const float* bQu,
+                               const float* Fa, const float* bFa,
+                               const float* Kua, const float* Qua, const float* bQua,
+                               const float* addend, float* out, int B, int G, int U, int H, int C1, int d,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
+/* The user graph's node features Xu = [user_news_embedding (H rows) | topic_node_embedding (C rows)] (graphEncoders.py:191) in one
+ * launch: ue [G,H,d], topic [C,d].  row_group == NULL: Xu [G,U,d], one graph per group (rows must equal G).  row_group [rows]
+ * int32: Xu [rows,U,d], graph r built from group row_group[r] (held inside [0, G)) — the expanded tensor written directly.
+ * d % 4 == 0 and 16-byte-aligned pointers (DIGAT_ERR_SHAPE / DIGAT_ERR_ARG otherwise); rows == 0 returns without a launch. */
+int digat_user_nodes_build(const float* ue, const float* topic, const int32_t* row_group, float* Xu, long rows, long G, int H,
+                           int C, int d, void* stream);
+
 /* topic pooling alone: out [B,C1,d] = scatter_sum(scatter_softmax(a) * hist) with
  * a_t = hist_t . kq / sqrt(d); kq [B,d] = (c_n Qu^T + bQu) Ku.  (graphEncoders.py:126-130) */
 int digat_topic_pool_fwd(const float* Xu, const float* kq, const int64_t* cat_idx, float* out,

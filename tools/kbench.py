@@ -14,6 +14,10 @@
   python tools/kbench.py train-input [n_behaviours]   the training input, host path vs device path (train_input.py), alternated,
                                              median [min, max] of five rounds: one epoch's negative sampling, the enqueue of 200
                                              steps' inputs, and 60 training steps (B = 64, K = 4; table and derived user graphs)
+  python tools/kbench.py ablation-score [passes news_num]   the five ablation encoders over a MIND-small-shaped dev corpus
+                                             (65 238 news, N = 10, H = 50, C = 17, d = 400, depth 3; 50 passes of 4 096 rows): the
+                                             per-row path (util.gather_batch + graph_encoder.inference) against
+                                             util.score_rows(grouped=True), alternated, median [min, max] of five rounds
 Timing with torch events on the current stream, median of --iters launches.
 """
 import os
@@ -635,6 +639,65 @@ def bench_train_input(n_behaviours=20000, rounds=5):
             print(f"(c) training step, {k:6s} input: {fmt(step[k], 'ms')} per step (60 steps, one drain)")
 
 
+def bench_ablation_score(passes=50, news_num=65238, rounds=5):
+    """Scoring throughput of the ablation encoders, two legs per encoder in one process, alternated (``alternate``):
+    (a) the per-row path, written with the gathers of ``util.gather_batch`` and ``graph_encoder.inference`` alone — every row
+        carries its own copy of the impression's user tensors and every layer runs per row;
+    (b) ``util.score_rows(grouped=True)``: the pipeline, per-news context tables and per-impression user layers.
+    One timed run is all ``passes`` passes of 4 096 rows.  The per-news tables (``prepare_news_side``) are built before, untimed."""
+    import types
+    from digat_amd import synthetic, util
+    from digat_amd.model import Model, PrecomputedNewsEncoder
+    dev = torch.device("cuda:0")
+    rows_per_pass, depth = 4096, 3
+    impressions = int(passes * rows_per_pass / 37.0 * 1.03) + 8
+    spec = synthetic.SynthSpec(news_num=news_num, sag_neighbors=3, sag_hops=2, impressions=impressions, seed=61)
+    corpus = synthetic.make_corpus(spec)
+    assert corpus.rows >= passes * rows_per_pass, (corpus.rows, passes * rows_per_pass)
+    end = passes * rows_per_pass
+    n_imp = int(corpus.row_impression[end - 1]) + 1
+    dc = util.DeviceCorpus.from_numpy(corpus, dev)
+    batches = util.launch_batches(0, end, 1024)
+    print(f"ablation-score: {news_num} news, N = {spec.news_graph_size}, H = {spec.max_history_num}, C = {spec.category_num}, "
+          f"d = {spec.embedding_dim}, depth {depth}; {end} rows of {n_imp} impressions in {len(batches)} passes", flush=True)
+    choices = (("wo_SA", "wo_SA"), ("Seq_SA", "Seq_SA"), ("wo_interaction", "wo_interaction"),
+               ("News_graph_wo_inter", "news_graph_wo_inter"), ("User_graph_wo_inter", "user_graph_wo_inter"))
+    for name, choice in choices:
+        cfg = types.SimpleNamespace(news_encoder="MSA", graph_encoder=choice, news_graph_size=spec.news_graph_size,
+                                    max_history_num=spec.max_history_num, category_num=spec.category_num, graph_depth=depth,
+                                    dropout_rate=0.2)
+        state = synthetic.make_ablation_state_dict(name, spec.embedding_dim, spec.category_num, depth, seed=62, bias_std=0.05)
+        model = Model(cfg, news_encoder=PrecomputedNewsEncoder(torch.from_numpy(corpus.news_embedding)))
+        model.graph_encoder.load_state_dict({k: torch.from_numpy(v) for k, v in state.items()})
+        model = model.to(dev).eval()
+        enc = model.graph_encoder
+        util.prepare_news_side(enc, dc, 1024)
+        out = torch.empty(end, dtype=torch.float32, device=dev)
+
+        def per_row():
+            with torch.no_grad():
+                for s, e in batches:
+                    ue, Au, cm, ci, Xn, An, Mn, c0 = util.gather_batch(dc, s, e)
+                    n, u = enc.inference(Xn, An, Mn, ue, Au, cm, ci, c0)
+                    _lib.binding().row_logits(n, u, out[s:e])
+
+        def grouped():
+            out.copy_(util.score_rows(model, dc, 0, end, 1024, grouped=True))
+        per_row()
+        a = out.clone()
+        grouped()
+        rms = float(a.double().pow(2).mean().sqrt())
+        diff = float((out - a).abs().max())
+        (ma, lo_a, hi_a), (mb, lo_b, hi_b) = alternate(per_row, grouped, rounds=rounds, iters=1)
+        per = lambda ms: ms / len(batches)
+        print(f"  {name:20s} per-row {per(ma):7.3f} ms / 4096 rows [{per(lo_a):.3f}, {per(hi_a):.3f}]  {n_imp / ma * 1e3:9.0f} impressions/s | "
+              f"grouped {per(mb):7.3f} ms [{per(lo_b):.3f}, {per(hi_b):.3f}]  {n_imp / mb * 1e3:9.0f} impressions/s | "
+              f"x{ma / mb:.2f}  max|d| {diff:.2e} (rms {rms:.2e})", flush=True)
+        del model, enc
+        dc.news_ctx_layers = dc.c_n0 = None
+        torch.cuda.empty_cache()
+
+
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "xattn"
     nums = [int(v) for v in sys.argv[2:]]
@@ -666,6 +729,8 @@ if __name__ == "__main__":
         bench_user_graph(*nums)
     elif what == "train-input":
         bench_train_input(*nums)
+    elif what == "ablation-score":
+        bench_ablation_score(*nums)
     elif what == "linear":
         bench_linear(*nums)
     elif what == "gemm":
