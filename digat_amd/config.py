@@ -20,13 +20,15 @@ from .synthetic import news_graph_size
 class Config:
     def __init__(self, argv=None):
         p = argparse.ArgumentParser(description='DIGAT (MI355X HIP path) experiments')
-        p.add_argument('--mode', default='train', choices=['train', 'dev', 'test'])
+        p.add_argument('--mode', default='train', choices=['train', 'dev', 'test', 'recommend'])
         p.add_argument('--news_encoder', default='MSA', choices=['MSA', 'CNN'])
         p.add_argument('--graph_encoder', default='DIGAT',
                        choices=['DIGAT', 'wo_SA', 'Seq_SA', 'wo_interaction', 'news_graph_wo_inter', 'user_graph_wo_inter'])
         p.add_argument('--dev_model_path', type=str, default='best_model/MIND-small/MSA-DIGAT/#1/MSA-DIGAT', help='Dev model path')
         p.add_argument('--test_model_path', type=str, default='best_model/MIND-small/MSA-DIGAT/#1/MSA-DIGAT', help='Test model path')
         p.add_argument('--test_output_file', type=str, default='', help='Test output file (the rank file of --mode test)')
+        p.add_argument('--recommend_k', type=int, default=10, help='news recommended per impression (--mode recommend; 1..128)')
+        p.add_argument('--recommend_output', type=str, default='', help='Recommendation file of --mode recommend: "<impression id> [id1,id2,...]" per line')
         p.add_argument('--seed', type=int, default=0)
         p.add_argument('--local_rank', '--local-rank', type=int, default=int(os.environ.get('LOCAL_RANK', -1)))
         p.add_argument('--dataset', default='MIND-small', choices=['MIND-small', 'MIND-large'])

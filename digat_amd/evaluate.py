@@ -118,6 +118,101 @@ def device_ranks_and_metrics(scores, row_impression: np.ndarray, labels: np.ndar
     return ranks.cpu().numpy().astype(np.int64), metrics
 
 
+TOPK_CHUNK = 16384       # include/digat_hip.h: DIGAT_TOPK_CHUNK, the elements one level-1 workgroup of digat_topk_segments selects from
+TOPK_MAX_K = 128
+TOPK_MAX_SKIP = 256
+
+
+def topk_keys(scores: np.ndarray) -> np.ndarray:
+    """The kernel's monotone 32-bit key of every score (csrc/digat_topk.inc): a larger key orders first.  ``-0.0`` and ``+0.0``
+    share a key, every NaN has key 1 — below ``-inf``'s 0x007fffff."""
+    b = np.ascontiguousarray(scores, dtype=np.float32).view(np.uint32).copy()
+    nan = (b & np.uint32(0x7fffffff)) > np.uint32(0x7f800000)
+    b[b == np.uint32(0x80000000)] = 0
+    neg = (b & np.uint32(0x80000000)) != 0
+    key = np.where(neg, ~b, b | np.uint32(0x80000000)).astype(np.uint32)
+    key[nan] = 1
+    return key
+
+
+def topk_segments_host(scores, seg_start, k: int, ids=None, skip=None):
+    """The contract of ``digat_topk_segments`` in numpy — the yardstick of the kernel.  Per segment: the elements whose id is not
+    in the segment's ``skip`` row, in a stable descending sort of their keys (``topk_keys``: ties keep position order, NaNs last),
+    the first k of them.  Returns ``(scores [S,k] float32, ids [S,k] int64, count [S] int32)``; slots at or beyond ``count`` hold
+    ``-inf`` / ``-1``; without ``ids`` the position inside the segment is returned."""
+    sc = np.ascontiguousarray(scores, dtype=np.float32)
+    st = np.asarray(seg_start, dtype=np.int64)
+    _check_topk_args(len(sc), st.shape, k, None if ids is None else np.shape(ids), None if skip is None else np.shape(skip))
+    S = len(st) - 1
+    out_s = np.full((S, k), -np.inf, dtype=np.float32)
+    out_i = np.full((S, k), -1, dtype=np.int64)
+    count = np.zeros(S, dtype=np.int32)
+    keys = topk_keys(sc).astype(np.int64)
+    idv = None if ids is None else np.asarray(ids, dtype=np.int64)
+    skv = None if skip is None else np.asarray(skip, dtype=np.int64).reshape(S, -1)
+    for s in range(S):
+        a, b = int(st[s]), int(st[s + 1])
+        pos = np.arange(b - a, dtype=np.int64)
+        if skv is not None and skv.shape[1]:
+            pos = pos[~np.isin(idv[a:b], skv[s])]
+        order = pos[np.argsort(-keys[a:b][pos], kind="stable")][:k]
+        m = len(order)
+        count[s] = m
+        out_s[s, :m] = sc[a:b][order]
+        out_i[s, :m] = order if idv is None else idv[a:b][order]
+    return out_s, out_i, count
+
+
+def _check_topk_args(rows, start_shape, k, ids_shape, skip_shape):
+    if not 1 <= int(k) <= TOPK_MAX_K:
+        raise ValueError(f"k must be in [1, {TOPK_MAX_K}], got {k}")
+    if len(start_shape) != 1 or start_shape[0] < 1:
+        raise ValueError("seg_start must be a 1-D array of segments + 1 row offsets")
+    if ids_shape is not None and tuple(ids_shape) != (rows,):
+        raise ValueError(f"ids must have one entry per score ({rows}), got shape {tuple(ids_shape)}")
+    if skip_shape is not None:
+        if ids_shape is None:
+            raise ValueError("skip needs ids")
+        if len(skip_shape) != 2 or skip_shape[0] != start_shape[0] - 1 or skip_shape[1] > TOPK_MAX_SKIP:
+            raise ValueError(f"skip must be [segments, at most {TOPK_MAX_SKIP}], got shape {tuple(skip_shape)}")
+
+
+def topk_segments(scores, seg_start, k: int, ids=None, skip=None):
+    """Per segment of a ragged score array, the k best elements in order, on the GPU (``digat_topk_segments``).
+
+    ``scores`` [R] float32 and ``seg_start`` [S+1] int64 (non-decreasing row offsets) are device tensors; ``ids`` [R] int64
+    (returned in place of positions) and ``skip`` [S, L <= 256] int64 (ids a segment must not return) are optional.  Order: score
+    descending, ties by position — the rank file's; NaNs last.  Returns ``(scores [S,k] float32, ids [S,k] int64, count [S] int32)``
+    on the device; slots at or beyond ``count`` hold ``-inf`` / ``-1``.  Stream-ordered: nothing is read back."""
+    import torch
+    from . import _lib
+    given = [t for t in (scores, seg_start, ids, skip) if t is not None]
+    dev = _lib.require_device(*given)
+    _check_topk_args(int(scores.shape[0]) if scores.dim() == 1 else -1, tuple(seg_start.shape), k,
+                     None if ids is None else tuple(ids.shape), None if skip is None else tuple(skip.shape))
+    if scores.dim() != 1:
+        raise ValueError("scores must be 1-D")
+    sc = _lib.f32(scores.detach())
+    st = seg_start.to(torch.int64).contiguous()
+    idt = None if ids is None else ids.to(torch.int64).contiguous()
+    sk = None if skip is None or skip.shape[1] == 0 else skip.to(torch.int64).contiguous()
+    R, S, k = int(sc.shape[0]), int(st.shape[0]) - 1, int(k)
+    out_s = torch.empty((S, k), dtype=torch.float32, device=dev)
+    out_i = torch.empty((S, k), dtype=torch.int64, device=dev)
+    count = torch.empty((S,), dtype=torch.int32, device=dev)
+    if S == 0:
+        return out_s, out_i, count
+    L = _lib.lib()
+    need = int(L.digat_topk_segments_workspace_bytes(R, S, k))
+    ws = _lib.workspace(need, dev, "topk")
+    dummy = ws if R == 0 else sc                        # an empty tensor has no storage to point at
+    _lib.check(L.digat_topk_segments(dummy.data_ptr(), st.data_ptr(), R, S, _lib.ptr(idt) if R else None,
+                                     _lib.ptr(sk) if R else None, 0 if sk is None or not R else int(sk.shape[1]), k,
+                                     out_s.data_ptr(), out_i.data_ptr(), count.data_ptr(), ws.data_ptr(), need, _lib.stream_ptr()),
+               "digat_topk_segments")
+    return out_s, out_i, count
+
+
 class AvgMetric:
     """util.py:100-121: the model-selection average."""
 

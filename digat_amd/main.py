@@ -4,7 +4,9 @@ The counterpart of the reference's ``main.py`` on a synthetic MIND-shaped corpus
 ``Trainer`` (DDP when launched with one process per GPU) and then scores the dev rows; ``dev`` / ``test`` load
 ``--dev_model_path`` / ``--test_model_path`` (the ``{model_name: state_dict}`` file the ``Trainer`` writes, main.py:23,36),
 score the rows and print AUC / MRR / nDCG@5 / nDCG@10 and the inference time (main.py:66-72); ``test`` writes the rank file
-to ``--test_output_file`` when one is named.
+to ``--test_output_file`` when one is named.  ``recommend`` loads ``--test_model_path`` as ``test`` does and, for every impression of the
+corpus, picks the ``--recommend_k`` best of ALL non-PAD news the impression's user has not read (``util.recommend``); it writes
+``"<impression id> [id1,id2,...]"`` per line — the rank file's framing — to ``--recommend_output`` when one is named.
 """
 from __future__ import annotations
 
@@ -28,6 +30,16 @@ def load_checkpoint(model, path: str) -> None:
     model.load_state_dict(saved[model.model_name])
 
 
+def recommend_lines(model, dc, k: int, batch_size: int):
+    """``"<impression id> [id1,id2,...]"`` (1-based impression ids, best news first) for every impression of ``dc`` against the
+    pool of all non-PAD news, the user's own history excluded."""
+    pool = torch.arange(1, dc.news_embedding.shape[0], dtype=torch.int64, device=dc.news_embedding.device)
+    users = torch.arange(dc.history.shape[0], dtype=torch.int64)
+    ids, _, count = util.recommend(model, dc, users, pool, k, batch_size=batch_size)
+    ids, count = ids.cpu().numpy(), count.cpu().numpy()
+    return ['%d [%s]' % (i + 1, ','.join(str(int(v)) for v in ids[i, :count[i]])) for i in range(len(count))]
+
+
 def main(argv=None):
     config = Config(argv)
     config.set_device()
@@ -40,7 +52,7 @@ def main(argv=None):
     model = Model(config, news_encoder=PrecomputedNewsEncoder(torch.from_numpy(corpus.news_embedding),
                                                               trainable=config.mode == 'train'))
     model.initialize()
-    if config.mode in ('dev', 'test'):
+    if config.mode in ('dev', 'test', 'recommend'):
         load_checkpoint(model, config.dev_model_path if config.mode == 'dev' else config.test_model_path)
     model = model.to(dev)
     dc = util.DeviceCorpus.from_numpy(corpus, dev, user_graphs=config.user_graphs)
@@ -63,6 +75,14 @@ def main(argv=None):
         dc.news_embedding = model.news_encoder.table.detach()
         if hasattr(model.graph_encoder, 'projection_mode'):      # the public switch of the scoring run's projection format
             model.graph_encoder.projection_mode = config.inference_projection
+        if config.mode == 'recommend':
+            lines = recommend_lines(model, dc, config.recommend_k, config.batch_size * 16)
+            if config.recommend_output:
+                with open(config.recommend_output, 'w') as f:
+                    f.write('\n'.join(lines))
+            print('Recommended %d news for each of %d impressions' % (config.recommend_k, len(lines)))
+            print('Inference time : %.1fs' % (time.time() - start))
+            return
         result_file = config.test_output_file if config.mode == 'test' and config.test_output_file else None
         scores, metrics = util.compute_scores(model, dc, config.batch_size * 16, labels=corpus.row_label, result_file=result_file)
         print('AUC : %.4f\nMRR : %.4f\nnDCG@5 : %.4f\nnDCG@10 : %.4f' % metrics)

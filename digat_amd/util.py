@@ -14,6 +14,7 @@ The graph encoder is the HIP plugin (``digat_amd.graphEncoders.DIGAT``); nothing
 """
 from __future__ import annotations
 
+import dataclasses
 import os
 from dataclasses import dataclass
 from typing import Callable, List, Optional, Tuple
@@ -691,6 +692,158 @@ def _score_sets(model, dc, start, batches, scores, lanes, grouped, in_place_tabl
         with torch.cuda.stream(lanes[0]):
             pipe.drain()                  # its buffers go back to the allocator when this function returns
     return scores
+
+
+# ---- top-k recommendation ---------------------------------------------------------------------------------------------------------
+# Pairs (user, candidate) that exist at once in ``recommend``: each costs 20 bytes outside the scoring pass (its two int64 row ids
+# and its fp32 score), so 4 Mi pairs bound those arrays at 80 MiB; the pass's own buffers are sized by LAUNCH_ROWS, not by this.
+RECOMMEND_MAX_ROWS = 4 << 20
+
+
+def _ndim(x) -> int:
+    return x.dim() if torch.is_tensor(x) else np.ndim(x)
+
+
+def recommend_users(dc: DeviceCorpus, users):
+    """The user side of ``recommend``: ``(history [G,H], user_category_indices [G,H], user_graph, user_category_mask)`` on the
+    corpus's device.  ``users``: a 1-D integer array of impression indices of ``dc`` (the corpus's graph and mask tables are
+    gathered when it has them), or a pair ``(history [G,H], user_category_indices [G,H])`` of users that are no rows of the
+    corpus — padded as the corpus is (history id 0, category index C) — whose graphs are then derived on the device."""
+    dev = dc.history.device
+    H = int(dc.history.shape[1])
+    if isinstance(users, (tuple, list)) and len(users) == 2 and _ndim(users[0]) == 2:
+        hist, cat = (torch.as_tensor(np.asarray(u) if not torch.is_tensor(u) else u).to(torch.int64) for u in users)
+        if hist.dim() != 2 or tuple(cat.shape) != tuple(hist.shape):
+            raise ValueError(f"users must be (history [G,H], user_category_indices [G,H]), got {tuple(hist.shape)} and {tuple(cat.shape)}")
+        if int(hist.shape[1]) != H:
+            raise ValueError(f"users' history length {int(hist.shape[1])} is not the corpus's max_history_num {H}")
+        if hist.numel() and (int(hist.min()) < 0 or int(hist.max()) >= int(dc.news_embedding.shape[0])):
+            raise ValueError("history ids must lie in [0, news_num)")
+        return hist.to(dev).contiguous(), cat.to(dev).contiguous(), None, None
+    idx = torch.as_tensor(np.asarray(users) if not torch.is_tensor(users) else users)
+    if idx.dim() != 1 or idx.dtype in (torch.float16, torch.float32, torch.float64, torch.bool):
+        raise ValueError("users must be a 1-D integer array of impression indices or a (history, user_category_indices) pair")
+    idx = idx.to(torch.int64)
+    I = int(dc.history.shape[0])
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= I):
+        raise ValueError(f"impression indices must lie in [0, {I})")
+    idx = idx.to(dev)
+    graph = dc.user_graph.index_select(0, idx) if dc.user_graph is not None else None
+    mask = dc.user_category_mask.index_select(0, idx) if dc.user_graph is not None else None
+    return dc.history.index_select(0, idx), dc.user_category_indices.index_select(0, idx), graph, mask
+
+
+def recommend_candidates(candidates, users: int, news_num: int):
+    """``candidates`` of ``recommend`` as ``(ids int64 tensor, start int64 numpy [users + 1] or None)``: a 1-D pool shared by all
+    users (``start`` None) or a pair ``(ids [R], start [users + 1])`` of per-user lists (CSR).  The ids stay where they are."""
+    if isinstance(candidates, (tuple, list)) and len(candidates) == 2 and _ndim(candidates[0]) == 1 and _ndim(candidates[1]) == 1:
+        ids, start = candidates
+        start = np.asarray(start.cpu() if torch.is_tensor(start) else start).astype(np.int64)
+        ids = torch.as_tensor(np.asarray(ids) if not torch.is_tensor(ids) else ids).to(torch.int64)
+        if start.shape != (users + 1,):
+            raise ValueError(f"candidate starts must have users + 1 = {users + 1} entries, got {start.shape}")
+        if start[0] != 0 or np.any(np.diff(start) < 0):
+            raise ValueError("candidate starts must begin at 0 and never decrease")
+        if int(start[-1]) != int(ids.shape[0]):
+            raise ValueError(f"the last candidate start ({int(start[-1])}) is not the number of candidate ids ({int(ids.shape[0])})")
+    else:
+        ids = torch.as_tensor(np.asarray(candidates) if not torch.is_tensor(candidates) else candidates)
+        if ids.dim() != 1:
+            raise ValueError("candidates must be a 1-D pool of news ids or a pair (ids [R], start [users + 1])")
+        ids, start = ids.to(torch.int64), None
+    if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= news_num):
+        raise ValueError(f"candidate ids must lie in [0, {news_num})")
+    return ids.contiguous(), start
+
+
+def recommend_rows(g0: int, g1: int, ids: torch.Tensor, start: Optional[np.ndarray]):
+    """The user-major (user, candidate) pairs of users [g0, g1): ``(row_impression [r], row_candidate [r], seg_start [g1-g0+1])``,
+    int64 tensors on the device of ``ids``.  ``start`` None: every user meets the whole pool ``ids``; else user g meets
+    ``ids[start[g]:start[g+1]]``."""
+    dev, g = ids.device, g1 - g0
+    users = torch.arange(g0, g1, dtype=torch.int64, device=dev)
+    if start is None:
+        P = int(ids.shape[0])
+        return users.repeat_interleave(P), ids.repeat(g), torch.arange(g + 1, dtype=torch.int64, device=dev) * P
+    seg = torch.from_numpy(start[g0:g1 + 1] - start[g0]).to(dev)
+    rows = int(start[g1] - start[g0])
+    return users.repeat_interleave(seg[1:] - seg[:-1], output_size=rows), ids[int(start[g0]):int(start[g1])], seg
+
+
+def recommend_user_chunks(users: int, ids_len: int, start: Optional[np.ndarray], max_rows: int) -> List[Tuple[int, int]]:
+    """Ranges [g0, g1) of consecutive users whose pairs number at most ``max_rows`` (a single user's own list may exceed it)."""
+    if max_rows < 1:
+        raise ValueError("max_rows must be positive")
+    if start is None:
+        step = max(1, max_rows // max(1, ids_len))
+        return [(g, min(g + step, users)) for g in range(0, users, step)]
+    out, g0 = [], 0
+    while g0 < users:
+        g1 = int(np.searchsorted(start, start[g0] + max_rows, side="right")) - 1
+        g1 = min(users, max(g1, g0 + 1))
+        out.append((g0, g1))
+        g0 = g1
+    return out
+
+
+def recommend(model, dc: DeviceCorpus, users, candidates, k: int, exclude_history: bool = True, batch_size: int = 1024,
+              max_rows: int = RECOMMEND_MAX_ROWS):
+    """For every user, which k news of its candidates, in order: ``(news_ids [G,k] int64, scores [G,k] float32, count [G] int32)``
+    on the device.  Order: score descending, equal scores in candidate order (the rank file's order); ``count[g]`` is the number of
+    valid slots of row g, the slots behind it hold id -1 and score -inf.
+
+    ``users``: impression indices of ``dc``, or ``(history, user_category_indices)`` arrays of users that are no rows of the corpus
+    (``recommend_users``).  ``candidates``: one pool of news ids for all users, or ``(ids, start)`` per user
+    (``recommend_candidates``).  ``exclude_history``: a news of the user's history is never returned — histories are padded with
+    id 0, so the PAD news is then never returned either; False takes the candidates at their word.
+
+    Scoring is ``score_rows`` on a view of ``dc`` (same per-news tables and caches; the users' tensors and the user-major pairs in
+    place of the corpus's impressions and rows), so the grouped route and the fp16x3 range check apply; selection is
+    ``evaluate.topk_segments``.  Users are processed in chunks of at most ``max_rows`` pairs (``RECOMMEND_MAX_ROWS``: 20 bytes per
+    pair, 80 MiB).  Like ``compute_scores`` this puts the model in eval mode and refreshes the per-news tables when the weights
+    have moved on.  The chunking may move fp32 bits of a score (pass composition), as the launch-set size does."""
+    if not 1 <= int(k) <= evaluate.TOPK_MAX_K:
+        raise ValueError(f"k must be in [1, {evaluate.TOPK_MAX_K}], got {k}")
+    k = int(k)
+    hist, cat, graph, mask = recommend_users(dc, users)
+    G, H = int(hist.shape[0]), int(hist.shape[1])
+    if exclude_history and H > evaluate.TOPK_MAX_SKIP:
+        raise ValueError(f"exclude_history takes histories of at most {evaluate.TOPK_MAX_SKIP} news, this corpus has {H}")
+    dev = dc.news_embedding.device
+    ids, start = recommend_candidates(candidates, G, int(dc.news_embedding.shape[0]))
+    ids = ids.to(dev)
+    chunks = recommend_user_chunks(G, int(ids.shape[0]), start, int(max_rows))
+    if hasattr(model, "eval"):
+        model.eval()
+    enc = model.graph_encoder
+    ne = getattr(model, "news_encoder", None)
+    if dc.title_text is not None and ne is not None and not hasattr(ne, "table"):
+        nk = tuple((p.data_ptr(), p._version) for p in ne.parameters())
+        if dc.news_key != nk:
+            dc.news_embedding = cache_news_representations(ne, dc.title_text, dc.title_mask, max(batch_size, 4096))
+            dc.news_key = nk
+    if hasattr(enc, "pass_rows"):
+        enc.pass_rows = _pass_rows(batch_size)
+    apply_corpus_hint(enc, dc)
+    if dc.c_n0 is None or dc.weights_key != weights_key(enc, dc):
+        prepare_news_side(enc, dc, batch_size)
+    out_ids = torch.full((G, k), -1, dtype=torch.int64, device=dev)
+    out_scores = torch.full((G, k), float("-inf"), dtype=torch.float32, device=dev)
+    out_count = torch.zeros((G,), dtype=torch.int32, device=dev)
+    for g0, g1 in chunks:
+        row_user, row_cand, seg = recommend_rows(g0, g1, ids, start)
+        if int(row_user.shape[0]) == 0:
+            continue
+        view = dataclasses.replace(dc, history=hist, user_category_indices=cat, user_graph=graph, user_category_mask=mask,
+                                   row_impression=row_user, row_candidate=row_cand)
+        scores = score_rows(model, view, 0, view.rows, batch_size)
+        if view.weights_key != dc.weights_key:        # the range fallback rebuilt the per-news tables: on the view — keep them
+            for f in ("SA_news_representations", "c_n0", "news_hpq0", "user_hpq0", "topic_hpq0", "ctxq0", "news_ctx_layers",
+                      "weights_key", "xattn_hint", "range_overflow_at_prepare"):
+                setattr(dc, f, getattr(view, f))
+        s, i, c = evaluate.topk_segments(scores, seg, k, ids=row_cand, skip=hist[g0:g1] if exclude_history else None)
+        out_scores[g0:g1], out_ids[g0:g1], out_count[g0:g1] = s, i, c
+    return out_ids, out_scores, out_count
 
 
 def all_gather_scores(local: torch.Tensor, counts: List[int], group=None) -> torch.Tensor:

@@ -561,6 +561,26 @@ int digat_rank_metrics(const float* scores, const uint8_t* labels, const int64_t
  * small — the capacity needed. */
 int64_t digat_format_rank_file(const int64_t* ranks, const int64_t* starts, int64_t impressions, char* out, int64_t cap);
 
+/* ---- segmented top-k: which k elements of every segment, in order (digat_amd.util.recommend) ----------------------
+ * scores [rows] f32; seg_start [segments + 1] int64, non-decreasing, on the DEVICE (segment s owns rows [start[s], start[s+1]);
+ * values outside [0, rows] are held inside it).  Within a segment elements are ordered by score descending, ties by position
+ * ascending (the order of digat_rank_metrics and of list.sort(reverse=True)); -0.0 == +0.0; a NaN orders after every number,
+ * -inf included, NaNs among themselves by position.  ids [rows] int64 or NULL (NULL: the position inside the segment is
+ * returned).  skip [segments, skip_len] int64 or NULL / 0: an element whose id occurs in its segment's skip row is left out
+ * (skip without ids: DIGAT_ERR_ARG); repeated ids inside a segment are distinct elements.
+ * out_count [segments] = min(k, elements left); slots j < count of out_scores / out_ids [segments, k] hold the j-th element's
+ * original score bits and its id (or position), slots j >= count hold -inf and -1: every output byte is written, for empty
+ * segments too.  1 <= k <= 128, 0 <= skip_len <= 256 and non-null required pointers (DIGAT_ERR_ARG otherwise, before any
+ * launch); rows / DIGAT_TOPK_CHUNK + segments < 2^31 (DIGAT_ERR_SHAPE); a short workspace is DIGAT_ERR_WORKSPACE (it may hold
+ * anything on entry); segments == 0 returns DIGAT_OK.  Stream-ordered: two launches on `stream`, sized by rows and segments
+ * alone (one workgroup per chunk of DIGAT_TOPK_CHUNK elements, then one per segment); no allocation, no host synchronisation,
+ * no read of seg_start on the host. */
+#define DIGAT_TOPK_CHUNK 16384
+size_t digat_topk_segments_workspace_bytes(int64_t rows, int64_t segments, int k);
+int digat_topk_segments(const float* scores, const int64_t* seg_start, int64_t rows, int64_t segments, const int64_t* ids,
+                        const int64_t* skip, int skip_len, int k, float* out_scores, int64_t* out_ids, int32_t* out_count,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- vanilla-GAT update layer of the ablation encoders -----------------------------------------
  * graphEncoders.py:493-519 (wo_interaction), :641-651 (News_graph_wo_inter), :788-798 (User_graph_wo_inter), eval mode:
  * h = X W^T + bW; e_ij = leaky_relu_0.2(a1.h_j + a2.h_i); -1e9 where A_ij = 0; alpha = softmax_j; out = relu(alpha h) + X.

@@ -18,6 +18,12 @@
                                              (65 238 news, N = 10, H = 50, C = 17, d = 400, depth 3; 50 passes of 4 096 rows): the
                                              per-row path (util.gather_batch + graph_encoder.inference) against
                                              util.score_rows(grouped=True), alternated, median [min, max] of five rounds
+  python tools/kbench.py topk                segmented top-k (digat_topk_segments) against torch.topk — (a) one segment of 65 238,
+                                             k = 10; (b) 256 segments of 65 238, k = 10 and 100 — and against digat_rank_metrics —
+                                             (c) 73 152 segments of the dev length distribution, k = 10; alternated in one process,
+                                             median [min, max] of five rounds, bytes/s against the one-pass floor rows x 4 B
+  python tools/kbench.py recommend [users news_num]   util.recommend: 64 users against the pool of all news at MIND-small shapes
+                                             (65 238 news, N = 10, H = 50, C = 17, d = 400, depth 3), users per second
 Timing with torch events on the current stream, median of --iters launches.
 """
 import os
@@ -698,6 +704,113 @@ def bench_ablation_score(passes=50, news_num=65238, rounds=5):
         torch.cuda.empty_cache()
 
 
+def bench_topk(rounds=5):
+    """``digat_topk_segments`` (the C entry, buffers allocated once) against what the tree had before for the same question, in one
+    process, alternated (``alternate``): ``torch.topk`` where the segments are equally long — its tie order is unspecified, so it is
+    a yardstick for speed only — and ``digat_rank_metrics`` (ranks of every element, one wave per segment) on the ragged dev
+    shape.  GB/s = rows x 4 B / time: the floor is one pass over the scores."""
+    from digat_amd import evaluate
+    dev = torch.device("cuda:0")
+    L = _lib.lib()
+    g = torch.Generator(device="cpu").manual_seed(0)
+
+    def ours(scores, start, k):
+        R, S = int(scores.shape[0]), int(start.shape[0]) - 1
+        need = int(L.digat_topk_segments_workspace_bytes(R, S, k))
+        ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        out_s = torch.empty((S, k), dtype=torch.float32, device=dev)
+        out_i = torch.empty((S, k), dtype=torch.int64, device=dev)
+        out_c = torch.empty((S,), dtype=torch.int32, device=dev)
+
+        def run():
+            _lib.check(L.digat_topk_segments(scores.data_ptr(), start.data_ptr(), R, S, None, None, 0, k, out_s.data_ptr(), out_i.data_ptr(),
+                                             out_c.data_ptr(), ws.data_ptr(), need, _lib.stream_ptr()), "digat_topk_segments")
+        return run, (out_s, out_i, out_c)
+
+    def line(tag, rows, a, b, other):
+        (ma, lo_a, hi_a), (mb, lo_b, hi_b) = a, b
+        gbs = lambda ms: rows * 4 / ms / 1e6
+        print(f"  {tag:42s} digat_topk_segments {ma * 1e3:9.1f} us [{lo_a * 1e3:.1f}, {hi_a * 1e3:.1f}]  {gbs(ma):7.1f} GB/s | "
+              f"{other} {mb * 1e3:9.1f} us [{lo_b * 1e3:.1f}, {hi_b * 1e3:.1f}]  {gbs(mb):7.1f} GB/s | x{mb / ma:.2f}", flush=True)
+
+    P = 65238
+    for S, ks in ((1, (10,)), (256, (10, 100))):
+        scores = torch.randn(S * P, generator=g).to(dev)
+        start = (torch.arange(S + 1, dtype=torch.int64) * P).to(dev)
+        for k in ks:
+            run, outs = ours(scores, start, k)
+            run()
+            want = torch.topk(scores.view(S, P), k, dim=1)
+            torch.cuda.synchronize()
+            assert torch.equal(outs[0], want.values), "scores differ from torch.topk's"       # distinct values: no tie to order
+            a, b = alternate(run, lambda: torch.topk(scores.view(S, P), k, dim=1), rounds=rounds, iters=10)
+            line(f"{S} segment(s) of {P}, k = {k}", S * P, a, b, "torch.topk")
+    rng = np.random.default_rng(0)
+    lengths = np.clip(rng.poisson(37.0, size=73152), 2, 300)
+    start_np = np.r_[0, np.cumsum(lengths)].astype(np.int64)
+    R = int(start_np[-1])
+    scores = torch.randn(R, generator=g).to(dev)
+    start = torch.from_numpy(start_np).to(dev)
+    run, outs = ours(scores, start, 10)
+    ranks = torch.empty(R, dtype=torch.int32, device=dev)
+
+    def rank_all():
+        _lib.check(L.digat_rank_metrics(scores.data_ptr(), None, start.data_ptr(), len(lengths), ranks.data_ptr(), None, None, _lib.stream_ptr()),
+                   "digat_rank_metrics")
+    run()
+    rank_all()
+    torch.cuda.synchronize()
+    pos, cnt, rk = outs[1].cpu().numpy(), outs[2].cpu().numpy(), ranks.cpu().numpy()
+    for s in range(0, len(lengths), 997):
+        assert np.array_equal(rk[start_np[s] + pos[s, :cnt[s]]], np.arange(1, cnt[s] + 1)), s
+    a, b = alternate(run, rank_all, rounds=rounds, iters=10)
+    line(f"{len(lengths)} ragged segments ({R} rows), k = 10", R, a, b, "digat_rank_metrics")
+
+
+def bench_recommend(users=64, news_num=65238, rounds=5):
+    """``util.recommend`` for ``users`` impressions of a MIND-small-shaped corpus against the pool of all non-PAD news, k = 10, the
+    history excluded: users per second, median [min, max] of ``rounds`` runs; and the selection's share (``evaluate.topk_segments``
+    on scores of the same shape with the same skip rows).  The per-news tables are built before, untimed."""
+    import types
+    from digat_amd import evaluate, synthetic, util
+    from digat_amd.model import Model, PrecomputedNewsEncoder
+    dev = torch.device("cuda:0")
+    depth = 3
+    spec = synthetic.SynthSpec(news_num=news_num, sag_neighbors=3, sag_hops=2, impressions=max(users, 256), seed=61)
+    corpus = synthetic.make_corpus(spec)
+    cfg = types.SimpleNamespace(news_encoder="MSA", graph_encoder="DIGAT", news_graph_size=spec.news_graph_size,
+                                max_history_num=spec.max_history_num, category_num=spec.category_num, graph_depth=depth, dropout_rate=0.2)
+    state = synthetic.make_state_dict(spec.embedding_dim, spec.category_num, depth, seed=62, bias_std=0.05)
+    model = Model(cfg, news_encoder=PrecomputedNewsEncoder(torch.from_numpy(corpus.news_embedding)))
+    model.graph_encoder.load_state_dict({k: torch.from_numpy(v) for k, v in state.items()})
+    model = model.to(dev).eval()
+    dc = util.DeviceCorpus.from_numpy(corpus, dev)
+    pool = torch.arange(1, news_num, dtype=torch.int64, device=dev)
+    who = np.arange(users)
+    rows = users * (news_num - 1)
+    print(f"recommend: {users} users x {news_num - 1} news = {rows} pairs, N = {spec.news_graph_size}, H = {spec.max_history_num}, "
+          f"C = {spec.category_num}, d = {spec.embedding_dim}, depth {depth}, k = 10", flush=True)
+    util.recommend(model, dc, who, pool, 10)                         # builds the per-news tables, warms every path
+    torch.cuda.synchronize()
+    import time
+    secs = []
+    for _ in range(rounds):
+        t0 = time.perf_counter()
+        util.recommend(model, dc, who, pool, 10)
+        torch.cuda.synchronize()
+        secs.append(time.perf_counter() - t0)
+    secs.sort()
+    med = secs[len(secs) // 2]
+    print(f"  util.recommend {med:.3f} s [{secs[0]:.3f}, {secs[-1]:.3f}]: {users / med:.1f} users/s, "
+          f"{med / (rows / 4096) * 1e3:.3f} ms per 4096 pairs", flush=True)
+    scores = torch.randn(rows, device=dev)
+    _, cand, seg = util.recommend_rows(0, users, pool, None)
+    skip = dc.history[:users].contiguous()
+    med_ms, best_ms = timeit(lambda: evaluate.topk_segments(scores, seg, 10, ids=cand, skip=skip), iters=10)
+    print(f"  of which selection (topk_segments, ids + {skip.shape[1]}-entry skip rows): median {med_ms:.3f} ms, best {best_ms:.3f} ms "
+          f"({rows * 12 / med_ms / 1e6:.1f} GB/s of scores + ids)", flush=True)
+
+
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "xattn"
     nums = [int(v) for v in sys.argv[2:]]
@@ -731,6 +844,10 @@ if __name__ == "__main__":
         bench_train_input(*nums)
     elif what == "ablation-score":
         bench_ablation_score(*nums)
+    elif what == "topk":
+        bench_topk(*nums)
+    elif what == "recommend":
+        bench_recommend(*nums)
     elif what == "linear":
         bench_linear(*nums)
     elif what == "gemm":
