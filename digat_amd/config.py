@@ -2,7 +2,10 @@
 
 Same flag names, defaults and dataset overrides (config.py:14-75): MIND-small forces dropout 0.2 / 16 epochs,
 MIND-large 0.1 / 7; ``news_graph_size = 1 + M + M(M-1) + ...``.  Differences, all forced by the environment:
-real MIND cannot be downloaded, so the corpus is synthetic (``--synthetic_news``, ``--synthetic_impressions``);
+real MIND cannot be downloaded, so the default corpus is synthetic (``--synthetic_news``, ``--synthetic_impressions``);
+``--data_root`` names MIND files on disk instead (``mind.load``: ``--artefact_root``, ``--similarity_file``,
+``--word_embedding_file``, ``--data_cache``, ``--word_threshold``, ``--max_title_length``), and only then are those flags attributes
+(``--model_dir`` also when it is given: the Trainer saves there on either corpus);
 ``--local_rank`` also accepts torch >= 2.0's ``--local-rank`` spelling and the ``LOCAL_RANK`` variable.
 """
 from __future__ import annotations
@@ -66,8 +69,21 @@ class Config:
                        help='table: user graphs uploaded with the corpus; derived: built on the device per batch from the category indices')
         p.add_argument('--train_input', default='host', choices=['host', 'device'],
                        help='host: negative sampling and batch indices in numpy; device: sampled per epoch and assembled per step by HIP kernels')
+        # a MIND corpus on disk (mind.load): without --data_root none of these is an attribute and every path is the synthetic one
+        p.add_argument('--data_root', type=str, default='', help='MIND files: train/, dev/ and test/, each with news.tsv and behaviors.tsv')
+        p.add_argument('--artefact_root', type=str, default='',
+                       help="directory of the reference's artefacts (news_ID-*.json ... news_graph-*.pkl): used where present")
+        p.add_argument('--similarity_file', type=str, default='', help="the reference's similarity-M.json: news graphs by the device walk")
+        p.add_argument('--word_embedding_file', type=str, default='', help="the reference's word_embedding-*.pkl or an .npy [V, dim]")
+        p.add_argument('--data_cache', type=str, default='', help='directory the parsed corpus is cached in (rebuilt when stale)')
+        p.add_argument('--word_threshold', type=int, default=3)
+        p.add_argument('--max_title_length', type=int, default=32)
+        p.add_argument('--model_dir', type=str, default='', help='directory the trained models are saved in')
         a = p.parse_args(argv)
-        self.attribute_dict = dict(vars(a))
+        mind_flags = ('data_root', 'artefact_root', 'similarity_file', 'word_embedding_file', 'data_cache', 'word_threshold',
+                      'max_title_length', 'model_dir')
+        self.attribute_dict = {k: v for k, v in vars(a).items()
+                               if a.data_root or k not in mind_flags or (k == 'model_dir' and a.model_dir)}
         for k, v in self.attribute_dict.items():
             setattr(self, k, v)
         if self.dataset == 'MIND-small':
@@ -75,7 +91,13 @@ class Config:
         else:
             self.dropout_rate, self.epoch, self.category_num = 0.1, 7, 18
         self.news_graph_size = news_graph_size(self.SAG_neighbors, self.SAG_hops)
-        self.max_title_length = 1                                   # synthetic "titles" are news ids
+        if not a.data_root:
+            self.max_title_length = 1                               # synthetic "titles" are news ids
+
+    def set_corpus(self, corpus):
+        """The sizes a MIND corpus decides (MIND_corpus.py:192-204)."""
+        self.user_num, self.category_num = corpus.user_num, corpus.category_num
+        self.subCategory_num, self.vocabulary_size = corpus.subCategory_num, corpus.vocabulary_size
 
     def set_device(self):
         assert torch.cuda.is_available(), 'GPU is not available'

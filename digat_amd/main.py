@@ -1,6 +1,8 @@
 """Entry point: ``python -m digat_amd.main --mode={train,dev,test} --graph_encoder=DIGAT ...``
 
-The counterpart of the reference's ``main.py`` on a synthetic MIND-shaped corpus: ``train`` runs the
+The counterpart of the reference's ``main.py``, on a synthetic MIND-shaped corpus or — ``--data_root`` — on MIND files read by
+``mind.load`` (the model then has its text encoder, ``--news_encoder MSA|CNN``; trained on the train split, selected on dev, saved
+under ``--model_dir``; ``test`` / ``recommend`` run on the test split, an unlabelled one gives the rank file and no metrics): ``train`` runs the
 ``Trainer`` (DDP when launched with one process per GPU) and then scores the dev rows; ``dev`` / ``test`` load
 ``--dev_model_path`` / ``--test_model_path`` (the ``{model_name: state_dict}`` file the ``Trainer`` writes, main.py:23,36),
 score the rows and print AUC / MRR / nDCG@5 / nDCG@10 and the inference time (main.py:66-72); ``test`` writes the rank file
@@ -40,10 +42,8 @@ def recommend_lines(model, dc, k: int, batch_size: int):
     return ['%d [%s]' % (i + 1, ','.join(str(int(v)) for v in ids[i, :count[i]])) for i in range(len(count))]
 
 
-def main(argv=None):
-    config = Config(argv)
-    config.set_device()
-    dev = torch.device('cuda', torch.cuda.current_device())
+def synthetic_setup(config, dev):
+    """The synthetic corpus and a table-backed model: ``(model, dc, train corpus, labels of dc, dev_dc or None)``."""
     spec = synthetic.SynthSpec(news_num=config.synthetic_news, sag_neighbors=config.SAG_neighbors, sag_hops=config.SAG_hops,
                                max_history_num=config.max_history_num, category_num=config.category_num,
                                embedding_dim=config.news_embedding_dim, impressions=config.synthetic_impressions,
@@ -56,13 +56,53 @@ def main(argv=None):
         load_checkpoint(model, config.dev_model_path if config.mode == 'dev' else config.test_model_path)
     model = model.to(dev)
     dc = util.DeviceCorpus.from_numpy(corpus, dev, user_graphs=config.user_graphs)
+    return model, dc, corpus, corpus.row_label, None
+
+
+def mind_setup(config, dev):
+    """``--data_root``: the MIND files (``mind.load``) and the model with its text encoder.  ``train`` trains on the train split and
+    selects on dev (one set of news tables for both: ``news_from``); ``dev`` scores the dev split, ``test`` and ``recommend`` the
+    test split.  Returns what ``synthetic_setup`` returns; the labels are None for an unlabelled test file."""
+    from . import mind
+    corpus = mind.load(config.data_root, max_history_num=config.max_history_num, max_title_length=config.max_title_length,
+                       word_threshold=config.word_threshold, sag_neighbors=config.SAG_neighbors, sag_hops=config.SAG_hops,
+                       dataset=config.dataset, artefact_root=config.artefact_root or None, similarity_file=config.similarity_file or None,
+                       word_embedding_file=config.word_embedding_file or None, word_embedding_dim=config.word_embedding_dim,
+                       data_cache=config.data_cache or None, verbose=config.local_rank in (-1, 0))
+    config.set_corpus(corpus)
+    model = Model(config)
+    model.initialize()
+    if corpus.word_embedding is not None:
+        weight = model.news_encoder.word_embedding.weight
+        if tuple(corpus.word_embedding.shape) != tuple(weight.shape):
+            raise ValueError(f"word embedding file holds {corpus.word_embedding.shape}, the model takes {tuple(weight.shape)}")
+        with torch.no_grad():
+            weight.copy_(torch.from_numpy(corpus.word_embedding))
+    if config.mode in ('dev', 'test', 'recommend'):
+        load_checkpoint(model, config.dev_model_path if config.mode == 'dev' else config.test_model_path)
+    model = model.to(dev)
+    if config.mode == 'train':
+        dc = util.DeviceCorpus.from_numpy(corpus.train, dev, user_graphs=config.user_graphs)
+        dev_dc = util.DeviceCorpus.from_numpy(corpus.dev, dev, user_graphs=config.user_graphs, news_from=dc)
+        return model, dc, corpus.train, corpus.dev.row_label, dev_dc
+    split = corpus.dev if config.mode == 'dev' else corpus.test
+    return model, util.DeviceCorpus.from_numpy(split, dev, user_graphs=config.user_graphs), None, split.row_label, None
+
+
+def main(argv=None):
+    config = Config(argv)
+    config.set_device()
+    dev = torch.device('cuda', torch.cuda.current_device())
+    on_mind = bool(getattr(config, 'data_root', ''))
+    model, dc, corpus, labels, dev_dc = (mind_setup if on_mind else synthetic_setup)(config, dev)
     if config.mode == 'train':
         if config.train_input == 'device':
             from .train_input import DeviceTrainSet
             train_set = DeviceTrainSet(corpus, config.negative_sample_num, config.seed, dev)
         else:
             train_set = SyntheticTrainSet(corpus, config.negative_sample_num, config.seed)
-        trainer = Trainer(model, config, dc, train_set, local_rank=config.local_rank, dev_labels=corpus.row_label)
+        trainer = Trainer(model, config, dc, train_set, local_rank=config.local_rank, dev_labels=labels,
+                          model_dir=getattr(config, 'model_dir', '') or None, dev_dc=dev_dc)
         trainer.train(max_steps=config.max_steps or None, log_every=50)
         if config.local_rank != -1:
             import torch.distributed as dist
@@ -70,9 +110,12 @@ def main(argv=None):
             dist.destroy_process_group()
         if not trainer.is_main_rank:
             return
+        if dev_dc is not None:
+            dc = dev_dc                                              # the split the model was selected on
     if config.local_rank in (-1, 0):
         start = time.time()
-        dc.news_embedding = model.news_encoder.table.detach()
+        if hasattr(model.news_encoder, 'table'):                 # a text encoder's representations: compute_scores / recommend encode them
+            dc.news_embedding = model.news_encoder.table.detach()
         if hasattr(model.graph_encoder, 'projection_mode'):      # the public switch of the scoring run's projection format
             model.graph_encoder.projection_mode = config.inference_projection
         if config.mode == 'recommend':
@@ -84,8 +127,9 @@ def main(argv=None):
             print('Inference time : %.1fs' % (time.time() - start))
             return
         result_file = config.test_output_file if config.mode == 'test' and config.test_output_file else None
-        scores, metrics = util.compute_scores(model, dc, config.batch_size * 16, labels=corpus.row_label, result_file=result_file)
-        print('AUC : %.4f\nMRR : %.4f\nnDCG@5 : %.4f\nnDCG@10 : %.4f' % metrics)
+        scores, metrics = util.compute_scores(model, dc, config.batch_size * 16, labels=labels, result_file=result_file)
+        if metrics is not None:                                  # an unlabelled test file: the rank file is the result
+            print('AUC : %.4f\nMRR : %.4f\nnDCG@5 : %.4f\nnDCG@10 : %.4f' % metrics)
         print('Inference time : %.1fs' % (time.time() - start))
 
 

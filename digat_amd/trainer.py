@@ -8,7 +8,9 @@ launched with one process per GPU (:19, :78-80; backend "nccl" is RCCL on ROCm) 
 
 Real MIND is not reachable from this environment, so the data side is ``SyntheticTrainSet``: behaviours
 with one clicked and ``negative_sample_num`` sampled non-clicked candidates (MIND_dataset.py:26-47),
-indexed into the device-resident synthetic corpus (no DataLoader workers: a batch is a few index_selects).
+indexed into the device-resident synthetic corpus (no DataLoader workers: a batch is a few index_selects).  A split of MIND files
+read by ``mind.load`` has the synthetic corpus's attribute names and goes through the same two sets; ``Trainer(..., dev_dc=)`` then
+selects on the dev split while training on the train split.
 ``train_input.DeviceTrainSet`` is the same set with its arrays on the device (``--train_input device``): sampling is one
 launch per epoch and a batch two launches per step.
 """
@@ -74,7 +76,10 @@ class SyntheticTrainSet:
 
 class Trainer:
     def __init__(self, model: nn.Module, config, dc: "util.DeviceCorpus", train_set,
-                 local_rank: int = -1, dev_labels: Optional[np.ndarray] = None, model_dir: Optional[str] = None):
+                 local_rank: int = -1, dev_labels: Optional[np.ndarray] = None, model_dir: Optional[str] = None,
+                 dev_dc: Optional["util.DeviceCorpus"] = None):
+        """``dev_dc``: the corpus ``dev_epoch`` scores against ``dev_labels`` — another split than the one trained on (a real
+        corpus trains on one split and selects on another); None: ``dc`` itself."""
         self.local_rank = local_rank
         self.is_main_rank = local_rank in (-1, 0)
         if local_rank == -1:
@@ -106,6 +111,7 @@ class Trainer:
         self.gradient_clip_norm = getattr(config, "gradient_clip_norm", 1.0)
         self.decay_epoch = lr_decay_epoch(self.epochs)
         self.dc, self.train_set = dc, train_set
+        self.dev_dc = dc if dev_dc is None else dev_dc
         self.losses = []
         # per-epoch dev evaluation and model selection on the main rank (trainer.py:52-69, :109-172)
         self.dev_labels = dev_labels
@@ -214,7 +220,7 @@ class Trainer:
         epoch, keep / save its state dict.  Returns True when early stopping says stop."""
         net = self.model.module if hasattr(self.model, "module") else self.model
         was_training = net.training
-        metrics = evaluate_dev(net, self.dc, self.dev_labels, self.batch_size * 16, as_tuple=True)
+        metrics = evaluate_dev(net, self.dev_dc, self.dev_labels, self.batch_size * 16, as_tuple=True)
         net.train(was_training)
         for acc, v in zip((self.auc, self.mrr, self.ndcg5, self.ndcg10), metrics):
             acc.append(v)

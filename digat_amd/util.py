@@ -60,17 +60,29 @@ class DeviceCorpus:
                                                              # encoder whenever this corpus is scored (two corpora may share one encoder)
     range_overflow_at_prepare: bool = False                  # an fp16x3 GEMM left the format's range while the per-news tables were built
     category_num: int = 0                                    # C (without the padding bucket); 0: read off user_category_mask
+    news_source: Optional["DeviceCorpus"] = None             # the corpus this one shares its news side with (from_numpy's news_from)
 
     def __post_init__(self):
         if not self.category_num and self.user_category_mask is not None:
             self.category_num = int(self.user_category_mask.shape[1]) - 1
 
     @classmethod
-    def from_numpy(cls, corpus, device, user_graphs: str = "table", category_num: Optional[int] = None) -> "DeviceCorpus":
+    def from_numpy(cls, corpus, device, user_graphs: str = "table", category_num: Optional[int] = None,
+                   news_from: Optional["DeviceCorpus"] = None) -> "DeviceCorpus":
         """``user_graphs="table"``: the corpus's ``user_graph`` / ``user_category_mask`` are uploaded and batches gather rows from
-        them.  ``"derived"``: neither is uploaded (nor read: the corpus need not have them) — both are a pure function of
-        ``user_category_indices`` and are built on the device per batch (``user_graphs_from_indices``); ``category_num`` then
-        comes from the argument, the corpus's mask shape or its spec."""
+        them; a corpus that holds no ``user_graph`` (``mind.MindSplit``: the ``[I, U, U]`` table is never built on the host) gets
+        both built on the device from its category indices, in chunks (``user_graph_tables``).  ``"derived"``: neither is uploaded
+        (nor read: the corpus need not have them) — both are a pure function of ``user_category_indices`` and are built on the
+        device per batch (``user_graphs_from_indices``); ``category_num`` then comes from the argument, the corpus's mask shape or
+        its spec.  A corpus with ``news_title_text`` / ``news_title_mask`` has them uploaded as ``title_text`` / ``title_mask``; one
+        without ``news_embedding`` (a text encoder produces it) starts with an empty ``[news_num, 0]`` table, which
+        ``compute_scores`` / ``recommend`` fill before anything reads it.
+
+        ``news_from``: another corpus of the same news (a second split).  Nothing of the news side is uploaded: its tensors
+        (``news_node_ID``, ``news_graph``, ``news_graph_mask``, ``title_text``, ``title_mask``, ``news_embedding``) and the per-news
+        caches of ``prepare_news_side`` are the other corpus's own, and later — the weights have moved on and the other corpus has
+        been scored since — this one takes the other's newer ones over while ``weights_key`` matches (``adopt_news_side``);
+        otherwise it rebuilds its own, as any corpus does."""
         if user_graphs not in ("table", "derived"):
             raise ValueError("user_graphs must be 'table' or 'derived'")
 
@@ -81,10 +93,30 @@ class DeviceCorpus:
         if category_num is None:
             mask = getattr(corpus, "user_category_mask", None)
             category_num = int(mask.shape[1]) - 1 if mask is not None else int(corpus.spec.category_num)
-        return cls(t(corpus.news_embedding), t(corpus.news_node_ID, torch.int64), t(corpus.news_graph),
-                   t(corpus.news_graph_mask), t(corpus.history, torch.int64), t(corpus.user_graph) if table else None,
-                   t(corpus.user_category_mask) if table else None, t(corpus.user_category_indices, torch.int64),
-                   t(corpus.row_impression, torch.int64), t(corpus.row_candidate, torch.int64), category_num=int(category_num))
+        cat_idx = t(corpus.user_category_indices, torch.int64)
+        host_graph = getattr(corpus, "user_graph", None) if table else None
+        if table and host_graph is None:
+            user_graph, cat_mask = user_graph_tables(cat_idx, int(category_num))
+        else:
+            user_graph, cat_mask = (t(host_graph), t(corpus.user_category_mask)) if table else (None, None)
+        if news_from is not None:
+            if int(news_from.news_node_ID.shape[0]) != int(np.asarray(corpus.news_node_ID).shape[0]):
+                raise ValueError("news_from holds another number of news than the corpus")
+            news = (news_from.news_embedding, news_from.news_node_ID, news_from.news_graph, news_from.news_graph_mask)
+        else:
+            emb = getattr(corpus, "news_embedding", None)
+            news_num = int(np.asarray(corpus.news_node_ID).shape[0])
+            news = (t(emb) if emb is not None else torch.empty((news_num, 0), dtype=torch.float32, device=device),
+                    t(corpus.news_node_ID, torch.int64), t(corpus.news_graph), t(corpus.news_graph_mask))
+        dc = cls(*news, t(corpus.history, torch.int64), user_graph, cat_mask, cat_idx,
+                 t(corpus.row_impression, torch.int64), t(corpus.row_candidate, torch.int64), category_num=int(category_num))
+        if news_from is not None:
+            dc.news_source = news_from
+            dc.title_text, dc.title_mask, dc.news_key = news_from.title_text, news_from.title_mask, news_from.news_key
+            adopt_news_side(None, dc, force=True)
+        elif getattr(corpus, "news_title_text", None) is not None:
+            dc.title_text, dc.title_mask = t(corpus.news_title_text, torch.int32), t(corpus.news_title_mask, torch.bool)
+        return dc
 
     @property
     def rows(self) -> int:
@@ -166,6 +198,59 @@ def user_graph_entries_per_node(dc: DeviceCorpus) -> Optional[float]:
         n = min(chunk, I - s)
         user_graphs_from_indices(dc.user_category_indices[s:s + n], dc.category_num, out=(graph[:n], mask[:n], entries[s:s + n]))
     return float(entries.sum(dtype=torch.float64) / (I * U))
+
+
+def user_graph_tables(cat_idx: torch.Tensor, category_num: int):
+    """The whole corpus's ``(user_graph [I,U,U], user_category_mask [I,C+1])`` from its category indices on the device, written
+    chunk by chunk into the two tables (chunks as ``user_graph_entries_per_node`` cuts them)."""
+    I, U = int(cat_idx.shape[0]), int(cat_idx.shape[1]) + int(category_num)
+    graph = torch.empty((I, U, U), dtype=torch.bool, device=cat_idx.device)
+    mask = torch.empty((I, category_num + 1), dtype=torch.bool, device=cat_idx.device)
+    chunk = max(1, min(I, USER_GRAPH_CHUNK_ROWS, (USER_GRAPH_CHUNK_BYTES - 1) // (U * U)))
+    for s in range(0, I, chunk):
+        n = min(chunk, I - s)
+        user_graphs_from_indices(cat_idx[s:s + n], category_num, out=(graph[s:s + n], mask[s:s + n]))
+    return graph, mask
+
+
+NEWS_SIDE_CACHES = ("SA_news_representations", "c_n0", "news_hpq0", "user_hpq0", "topic_hpq0", "ctxq0", "news_ctx_layers", "weights_key",
+                    "range_overflow_at_prepare")
+
+
+def adopt_news_side(model, dc: DeviceCorpus, force: bool = False) -> bool:
+    """A corpus built with ``news_from`` takes over its source's news representations and per-news caches when the source holds
+    newer ones for the current weights, so that one process keeps ONE set of news tables however many splits it scores.  The
+    sparse / dense hint of the user graph stays this corpus's own (its users differ); the news part is the source's (same news
+    graphs).  ``force``: at construction, whatever the source holds.  Returns whether the caches were taken."""
+    src = dc.news_source
+    if src is None:
+        return False
+    enc = getattr(model, "graph_encoder", None)
+    ne = getattr(model, "news_encoder", None)
+    if not force:
+        if src.news_key is None or ne is None or src.news_key != tuple((p.data_ptr(), p._version) for p in ne.parameters()):
+            return False                                  # the source's news representations are stale too: score_* re-encodes here
+    if dc.news_embedding is not src.news_embedding:
+        dc.news_embedding, dc.news_key = src.news_embedding, src.news_key
+    if src.c_n0 is None or src.weights_key is None or (dc.c_n0 is src.c_n0 and dc.weights_key == src.weights_key):
+        return False
+    if src.xattn_hint is not None:
+        hint = dict(src.xattn_hint)
+        hint.pop("user", None)
+        user = (dc.xattn_hint or {}).get("user")          # this corpus's users do not change: decided once
+        if user is None:
+            per_node = user_graph_entries_per_node(dc)
+            user = None if per_node is None else "sparse" if per_node <= SPARSE_ENTRIES_PER_NODE else "dense"
+        if user is not None:
+            hint["user"] = user
+        dc.xattn_hint = hint
+    if not force:
+        apply_corpus_hint(enc, dc)
+        if src.weights_key != weights_key(enc, dc):
+            return False
+    for f in NEWS_SIDE_CACHES:
+        setattr(dc, f, getattr(src, f))
+    return True
 
 
 def shard_rows(row_impression: np.ndarray, world_size: int, rank: int) -> Tuple[int, int]:
@@ -817,13 +902,14 @@ def recommend(model, dc: DeviceCorpus, users, candidates, k: int, exclude_histor
         model.eval()
     enc = model.graph_encoder
     ne = getattr(model, "news_encoder", None)
+    if hasattr(enc, "pass_rows"):
+        enc.pass_rows = _pass_rows(batch_size)
+    adopt_news_side(model, dc)
     if dc.title_text is not None and ne is not None and not hasattr(ne, "table"):
         nk = tuple((p.data_ptr(), p._version) for p in ne.parameters())
         if dc.news_key != nk:
             dc.news_embedding = cache_news_representations(ne, dc.title_text, dc.title_mask, max(batch_size, 4096))
             dc.news_key = nk
-    if hasattr(enc, "pass_rows"):
-        enc.pass_rows = _pass_rows(batch_size)
     apply_corpus_hint(enc, dc)
     if dc.c_n0 is None or dc.weights_key != weights_key(enc, dc):
         prepare_news_side(enc, dc, batch_size)
@@ -897,6 +983,10 @@ def compute_scores(model, dc: DeviceCorpus, batch_size: int, labels: Optional[np
         model.eval()
     freeze_host_heap()
     ne = getattr(model, "news_encoder", None)
+    if score_fn is None and dc.news_source is not None:
+        if hasattr(model.graph_encoder, "pass_rows"):
+            model.graph_encoder.pass_rows = _pass_rows(batch_size)      # weights_key names it: set before the keys are compared
+        adopt_news_side(model, dc)
     if score_fn is None and dc.title_text is not None and ne is not None and not hasattr(ne, "table"):
         # a text news encoder (MSA): util.py:24-33 re-encodes every news at the start of each dev / test run — here whenever the
         # encoder's weights have moved on since news_embedding was computed (training epochs), not otherwise
