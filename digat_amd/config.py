@@ -3,7 +3,7 @@
 Same flag names, defaults and dataset overrides (config.py:14-75): MIND-small forces dropout 0.2 / 16 epochs,
 MIND-large 0.1 / 7; ``news_graph_size = 1 + M + M(M-1) + ...``.  Differences, all forced by the environment:
 real MIND cannot be downloaded, so the default corpus is synthetic (``--synthetic_news``, ``--synthetic_impressions``);
-``--data_root`` names MIND files on disk instead (``mind.load``: ``--artefact_root``, ``--similarity_file``,
+``--data_root`` names MIND files on disk instead (``mind.load``: ``--artefact_root``, ``--similarity_file``, ``--semantic_embedding_root``,
 ``--word_embedding_file``, ``--data_cache``, ``--word_threshold``, ``--max_title_length``), and only then are those flags attributes
 (``--model_dir`` also when it is given: the Trainer saves there on either corpus);
 ``--local_rank`` also accepts torch >= 2.0's ``--local-rank`` spelling and the ``LOCAL_RANK`` variable.
@@ -74,13 +74,15 @@ class Config:
         p.add_argument('--artefact_root', type=str, default='',
                        help="directory of the reference's artefacts (news_ID-*.json ... news_graph-*.pkl): used where present")
         p.add_argument('--similarity_file', type=str, default='', help="the reference's similarity-M.json: news graphs by the device walk")
+        p.add_argument('--semantic_embedding_root', type=str, default='',
+                       help="the reference's <dataset>-SAG directory of sentence embeddings: similar-news lists and news graphs built on the device")
         p.add_argument('--word_embedding_file', type=str, default='', help="the reference's word_embedding-*.pkl or an .npy [V, dim]")
         p.add_argument('--data_cache', type=str, default='', help='directory the parsed corpus is cached in (rebuilt when stale)')
         p.add_argument('--word_threshold', type=int, default=3)
         p.add_argument('--max_title_length', type=int, default=32)
         p.add_argument('--model_dir', type=str, default='', help='directory the trained models are saved in')
         a = p.parse_args(argv)
-        mind_flags = ('data_root', 'artefact_root', 'similarity_file', 'word_embedding_file', 'data_cache', 'word_threshold',
+        mind_flags = ('data_root', 'artefact_root', 'similarity_file', 'semantic_embedding_root', 'word_embedding_file', 'data_cache', 'word_threshold',
                       'max_title_length', 'model_dir')
         self.attribute_dict = {k: v for k, v in vars(a).items()
                                if a.data_root or k not in mind_flags or (k == 'model_dir' and a.model_dir)}

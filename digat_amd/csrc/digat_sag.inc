@@ -1,9 +1,12 @@
-// digat_sag.inc — semantic-augmented-graph construction (SURVEY §8f-4), the two device-shaped steps of construct_SAG.py:
+// digat_sag.inc — semantic-augmented-graph construction (SURVEY §8f-4), construct_SAG.py from embeddings to news graphs:
 //   * generate_cos_similarities (:112-162): for every news of a category, the cosine of its title / content embedding with
 //     every corpus title / content embedding (four [n, m] matrices), their mean, and torch.topk(k = top_M + 1) of each.
 //     The reference loops over the n news, five topk calls each; here the embeddings are row-normalised once, the four
 //     matrices are ONE GEMM  [title ; content] x [corpus_title ; corpus_content]^T  on the matrix cores (the bf16x6 kernel
 //     above 2048 rows: fp32-grade products), and a selection kernel keeps the k largest of every row.
+//   * generate_similariy_info + generate_similar_news_list + aggregate (:217-446) for the kind aggregate reads, the average:
+//     behind the same GEMM, sag_lists_kernel selects a title group's k best corpus groups and walks them for every news of
+//     the group (skip its own group, keep M' = k - 1), writing the [news_num, top_M] lists the walk below reads.
 //   * generate_news_graph (:449-485): breadth-first expansion of every news over its similar-news list; integer work,
 //     one thread per news (the walk itself is sequential: <= news_node_num nodes, <= top_M edges each).
 // Included at the end of digat_kernels.hip.
@@ -36,6 +39,48 @@ struct SagTopkArgs {
 
 __device__ __forceinline__ bool sag_better(float v, int j, float w, int i) { return v > w || (v == w && j < i); }
 
+// The K best of a thread's column slice, sorted descending in registers: (v, j) enters when it beats the last one kept.
+template <int K>
+__device__ __forceinline__ void sag_keep(float (&val)[K], int (&idx)[K], float v, int j) {
+    if (v > val[K - 1]) {
+        val[K - 1] = v; idx[K - 1] = j;
+#pragma unroll
+        for (int t = K - 1; t > 0; --t)
+            if (val[t] > val[t - 1]) {
+                const float fv = val[t]; val[t] = val[t - 1]; val[t - 1] = fv;
+                const int fj = idx[t]; idx[t] = idx[t - 1]; idx[t - 1] = fj;
+            }
+    }
+}
+
+// One round of the workgroup arg-max over every thread's best entry (ties: lower column first).  Returns the thread that
+// held the winner, which drops it from its list; (v, j) is the winner in every thread.  Two barriers; red_* are [4].
+template <int K>
+__device__ __forceinline__ int sag_pop_best(float (&val)[K], int (&idx)[K], float* red_v, int* red_j, int* red_t, float& v, int& j) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int t = tid;
+    v = val[0]; j = idx[0];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float w = __shfl_xor(v, off);
+        const int wj = __shfl_xor(j, off), wt = __shfl_xor(t, off);
+        if (sag_better(w, wj, v, j)) { v = w; j = wj; t = wt; }
+    }
+    if (lane == 0) { red_v[wave] = v; red_j[wave] = j; red_t[wave] = t; }
+    __syncthreads();
+    v = red_v[0]; j = red_j[0]; t = red_t[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w)
+        if (sag_better(red_v[w], red_j[w], v, j)) { v = red_v[w]; j = red_j[w]; t = red_t[w]; }
+    __syncthreads();
+    if (tid == t) {
+#pragma unroll
+        for (int s = 0; s < K - 1; ++s) { val[s] = val[s + 1]; idx[s] = idx[s + 1]; }
+        val[K - 1] = -INFINITY; idx[K - 1] = 0x7fffffff;
+    }
+    return t;
+}
+
 // One workgroup per (news, kind); kind 0..4 = title-title, content-content, title-content, content-title, mean of the four
 // (the order construct_SAG.py:117-162 returns them in).  Every thread keeps the K best of its column slice sorted in
 // registers; k rounds of a workgroup arg-max then emit the row's k best in descending order (ties: lower column first).
@@ -43,7 +88,7 @@ template <int K>
 __global__ void __launch_bounds__(256) sag_topk_kernel(const SagTopkArgs a) {
     __shared__ float red_v[4];
     __shared__ int red_j[4], red_t[4];
-    const int i = blockIdx.x, kind = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int i = blockIdx.x, kind = blockIdx.y, tid = threadIdx.x;
     const float* tt = a.S + (long)i * a.ld;
     const float* tc = tt + a.mp;
     const float* ct = a.S + (long)(a.nc + i) * a.ld;
@@ -57,40 +102,72 @@ __global__ void __launch_bounds__(256) sag_topk_kernel(const SagTopkArgs a) {
         float v;
         if (kind < 4) v = single[j];
         else v = (((tt[j] + cc[j]) + tc[j]) + ct[j]) * 0.25f;            // :159, (tt + cc + tc + ct) / 4
-        if (v > val[K - 1]) {
-            val[K - 1] = v; idx[K - 1] = j;
-#pragma unroll
-            for (int t = K - 1; t > 0; --t)
-                if (val[t] > val[t - 1]) {
-                    const float fv = val[t]; val[t] = val[t - 1]; val[t - 1] = fv;
-                    const int fj = idx[t]; idx[t] = idx[t - 1]; idx[t - 1] = fj;
-                }
-        }
+        sag_keep<K>(val, idx, v, j);
     }
     float* ov = a.values + ((long)kind * a.n + a.row0 + i) * a.k;
     int* oj = a.indices + ((long)kind * a.n + a.row0 + i) * a.k;
     for (int round = 0; round < a.k; ++round) {
-        float v = val[0];
-        int j = idx[0], t = tid;
+        float v;
+        int j;
+        if (sag_pop_best<K>(val, idx, red_v, red_j, red_t, v, j) == tid) { ov[round] = v; oj[round] = j; }
+    }
+}
+
+// generate_similar_news_list (:303-320), the average kind, fused behind the selection: one workgroup per query group of the
+// chunk.  The k best corpus groups by the mean of the four cosines (sag_topk_kernel's kind 4, same arithmetic and order) stay
+// in LDS; thread t then serves members t, t + 256, ... of the group: walk the k entries in order, skip a corpus group that
+// holds the news itself, write (first member of the corpus group, cosine) and stop at M' = k - 1 entries (with M' = 0 the stop
+// test never fires, as in the reference, and the one entry is written unless skipped).  Every news row has one writer.
+struct SagListsArgs {
+    const float* S; long ld;        // as SagTopkArgs
+    int nc, m, mp, k, top_M;        // top_M: row stride of sim_index / sim_cos
+    long row0;                      // query group of chunk row 0
+    const int* group_start; const int* group_member;        // CSR over the query groups: news rows
+    const int* corpus_start; const int* corpus_member;      // CSR over the corpus groups: news rows, first = representative
+    int* sim_index; float* sim_cos; int* sim_len;
+};
+
+template <int K>
+__global__ void __launch_bounds__(256) sag_lists_kernel(const SagListsArgs a) {
+    __shared__ float red_v[4];
+    __shared__ int red_j[4], red_t[4];
+    __shared__ float win_v[32];
+    __shared__ int win_j[32];
+    const int i = blockIdx.x, tid = threadIdx.x;
+    const float* tt = a.S + (long)i * a.ld;
+    const float* tc = tt + a.mp;
+    const float* ct = a.S + (long)(a.nc + i) * a.ld;
+    const float* cc = ct + a.mp;
+    float val[K];
+    int idx[K];
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const float w = __shfl_xor(v, off);
-            const int wj = __shfl_xor(j, off), wt = __shfl_xor(t, off);
-            if (sag_better(w, wj, v, j)) { v = w; j = wj; t = wt; }
+    for (int t = 0; t < K; ++t) { val[t] = -INFINITY; idx[t] = 0x7fffffff; }
+    for (int j = tid; j < a.m; j += 256)
+        sag_keep<K>(val, idx, (((tt[j] + cc[j]) + tc[j]) + ct[j]) * 0.25f, j);
+    for (int round = 0; round < a.k; ++round) {
+        float v;
+        int j;
+        if (sag_pop_best<K>(val, idx, red_v, red_j, red_t, v, j) == tid) { win_v[round] = v; win_j[round] = j; }
+    }
+    __syncthreads();
+    const int stop = a.k - 1;                                                // M' = min(top_M, m - 1)
+    const long g = a.row0 + i;
+    for (int p = a.group_start[g] + tid; p < a.group_start[g + 1]; p += 256) {
+        const int x = a.group_member[p];
+        int* oi = a.sim_index + (long)x * a.top_M;
+        float* oc = a.sim_cos + (long)x * a.top_M;
+        int cnt = 0;
+        for (int e = 0; e < a.k; ++e) {
+            if ((unsigned)win_j[e] >= (unsigned)a.m) break;                  // fewer than k comparable cosines (NaN embeddings): no such group
+            const int cs = a.corpus_start[win_j[e]], ce = a.corpus_start[win_j[e] + 1];
+            bool self = false;
+            for (int q = cs; q < ce; ++q) self |= a.corpus_member[q] == x;   // :312, news_ID not in corpus_news_IDs
+            if (self) continue;
+            oi[cnt] = a.corpus_member[cs];
+            oc[cnt] = win_v[e];
+            if (++cnt == stop) break;                                        // :318
         }
-        if (lane == 0) { red_v[wave] = v; red_j[wave] = j; red_t[wave] = t; }
-        __syncthreads();
-        v = red_v[0]; j = red_j[0]; t = red_t[0];
-#pragma unroll
-        for (int w = 1; w < 4; ++w)
-            if (sag_better(red_v[w], red_j[w], v, j)) { v = red_v[w]; j = red_j[w]; t = red_t[w]; }
-        __syncthreads();
-        if (tid == t) {
-            ov[round] = v; oj[round] = j;
-#pragma unroll
-            for (int s = 0; s < K - 1; ++s) { val[s] = val[s + 1]; idx[s] = idx[s + 1]; }
-            val[K - 1] = -INFINITY; idx[K - 1] = 0x7fffffff;
-        }
+        a.sim_len[x] = cnt;
     }
 }
 
@@ -139,23 +216,13 @@ __global__ void __launch_bounds__(64) sag_news_graph_kernel(const int* sim_index
 static long sag_pad_corpus(long m) { return (m + 119) / 120 * 120; }       // 2*mp is a multiple of 240: three-strip GEMM tiles
 static long sag_chunk_rows(long n) { return n < 4096 ? n : 4096; }
 
-extern "C" {
-
-size_t digat_sag_cos_topk_workspace_bytes(int64_t n, int64_t m, int dim) {
-    const long mp = sag_pad_corpus(m), nc = sag_chunk_rows(n);
-    return align_up((size_t)2 * mp * dim * 4, 256) + align_up((size_t)2 * (nc > 0 ? nc : 1) * dim * 4, 256)
-           + align_up(digat_split_weights_bytes((int)(2 * mp), dim), 256) + align_up((size_t)2 * (nc > 0 ? nc : 1) * 2 * mp * 4, 256);
-}
-
-int digat_sag_cos_topk(const float* title, const float* content, int64_t n, const float* corpus_title, const float* corpus_content,
-                       int64_t m, int dim, int k, float* values, int32_t* indices, void* workspace, size_t workspace_bytes,
-                       void* stream) {
-    if (!title || !content || !corpus_title || !corpus_content || !values || !indices || !workspace || n < 0 || m <= 0 || dim <= 0 || k <= 0)
-        return DIGAT_ERR_ARG;
-    if (k > m || k > 32 || dim % 16 || 2 * sag_pad_corpus(m) > 0x7fffffffL / dim) return DIGAT_ERR_SHAPE;
-    if (workspace_bytes < digat_sag_cos_topk_workspace_bytes(n, m, dim)) return DIGAT_ERR_WORKSPACE;
-    if (n == 0) return DIGAT_OK;
-    hipStream_t st = (hipStream_t)stream;
+// The cosine matrices of one category, chunk by chunk: normalise the corpus once and split it for the GEMM, then for every
+// chunk of <= 4096 query rows normalise [title ; content], run the one GEMM into S [2*nc, 2*mp] and hand S to ``select``
+// (S, mp, nc, first row of the chunk), which launches the selection kernel that consumes it.  Workspace as
+// digat_sag_cos_topk_workspace_bytes lays it out.
+template <class Select>
+static int sag_cos_chunks(const float* title, const float* content, long n, const float* corpus_title, const float* corpus_content,
+                          long m, int dim, void* workspace, hipStream_t st, Select select) {
     const long mp = sag_pad_corpus(m), nc_max = sag_chunk_rows(n);
     char* ws = (char*)workspace;
     float* Cn = (float*)ws;            ws += align_up((size_t)2 * mp * dim * 4, 256);
@@ -179,15 +246,64 @@ int digat_sag_cos_topk(const float* title, const float* content, int64_t n, cons
         g.wsplit = (const unsigned short*)wsplit;
         rc = launch_gemm(g, st, DIGAT_KERNEL_LINEAR);
         if (rc) return rc;
+        select(S, mp, nc, r0);
+        DIGAT_CHECK_LAUNCH();
+    }
+    return DIGAT_OK;
+}
+
+extern "C" {
+
+size_t digat_sag_cos_topk_workspace_bytes(int64_t n, int64_t m, int dim) {
+    const long mp = sag_pad_corpus(m), nc = sag_chunk_rows(n);
+    return align_up((size_t)2 * mp * dim * 4, 256) + align_up((size_t)2 * (nc > 0 ? nc : 1) * dim * 4, 256)
+           + align_up(digat_split_weights_bytes((int)(2 * mp), dim), 256) + align_up((size_t)2 * (nc > 0 ? nc : 1) * 2 * mp * 4, 256);
+}
+
+int digat_sag_cos_topk(const float* title, const float* content, int64_t n, const float* corpus_title, const float* corpus_content,
+                       int64_t m, int dim, int k, float* values, int32_t* indices, void* workspace, size_t workspace_bytes,
+                       void* stream) {
+    if (!title || !content || !corpus_title || !corpus_content || !values || !indices || !workspace || n < 0 || m <= 0 || dim <= 0 || k <= 0)
+        return DIGAT_ERR_ARG;
+    if (k > m || k > 32 || dim % 16 || 2 * sag_pad_corpus(m) > 0x7fffffffL / dim) return DIGAT_ERR_SHAPE;
+    if (workspace_bytes < digat_sag_cos_topk_workspace_bytes(n, m, dim)) return DIGAT_ERR_WORKSPACE;
+    if (n == 0) return DIGAT_OK;
+    hipStream_t st = (hipStream_t)stream;
+    return sag_cos_chunks(title, content, n, corpus_title, corpus_content, m, dim, workspace, st,
+                          [&](const float* S, long mp, long nc, long r0) {
         SagTopkArgs a{S, 2 * mp, (int)nc, (int)m, (int)mp, k, r0, (long)n, values, indices};
         const dim3 grid((unsigned)nc, 5);
         if (k <= 4) hipLaunchKernelGGL(sag_topk_kernel<4>, grid, dim3(256), 0, st, a);
         else if (k <= 8) hipLaunchKernelGGL(sag_topk_kernel<8>, grid, dim3(256), 0, st, a);
         else if (k <= 16) hipLaunchKernelGGL(sag_topk_kernel<16>, grid, dim3(256), 0, st, a);
         else hipLaunchKernelGGL(sag_topk_kernel<32>, grid, dim3(256), 0, st, a);
-        DIGAT_CHECK_LAUNCH();
-    }
-    return DIGAT_OK;
+    });
+}
+
+size_t digat_sag_similar_lists_workspace_bytes(int64_t n, int64_t m, int dim) { return digat_sag_cos_topk_workspace_bytes(n, m, dim); }
+
+int digat_sag_similar_lists(const float* title, const float* content, int64_t n, const float* corpus_title, const float* corpus_content,
+                            int64_t m, int dim, int top_M, const int32_t* group_start, const int32_t* group_member,
+                            const int32_t* corpus_start, const int32_t* corpus_member, int32_t* sim_index, float* sim_cos,
+                            int32_t* sim_len, int64_t news_num, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!title || !content || !corpus_title || !corpus_content || !group_start || !group_member || !corpus_start || !corpus_member
+        || !sim_index || !sim_cos || !sim_len || !workspace || n < 0 || m <= 0 || dim <= 0 || top_M <= 0 || news_num <= 0)
+        return DIGAT_ERR_ARG;
+    const int k = (int)(top_M < m - 1 ? top_M : m - 1) + 1;                       // :292, M' + 1
+    if (k > 32 || dim % 16 || 2 * sag_pad_corpus(m) > 0x7fffffffL / dim) return DIGAT_ERR_SHAPE;
+    if (workspace_bytes < digat_sag_similar_lists_workspace_bytes(n, m, dim)) return DIGAT_ERR_WORKSPACE;
+    if (n == 0) return DIGAT_OK;
+    hipStream_t st = (hipStream_t)stream;
+    return sag_cos_chunks(title, content, n, corpus_title, corpus_content, m, dim, workspace, st,
+                          [&](const float* S, long mp, long nc, long r0) {
+        SagListsArgs a{S, 2 * mp, (int)nc, (int)m, (int)mp, k, top_M, r0, group_start, group_member, corpus_start, corpus_member,
+                       sim_index, sim_cos, sim_len};
+        const dim3 grid((unsigned)nc);
+        if (k <= 4) hipLaunchKernelGGL(sag_lists_kernel<4>, grid, dim3(256), 0, st, a);
+        else if (k <= 8) hipLaunchKernelGGL(sag_lists_kernel<8>, grid, dim3(256), 0, st, a);
+        else if (k <= 16) hipLaunchKernelGGL(sag_lists_kernel<16>, grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(sag_lists_kernel<32>, grid, dim3(256), 0, st, a);
+    });
 }
 
 int digat_sag_news_graph(const int32_t* sim_index, const float* sim_cos, const int32_t* sim_len, int64_t news_num, int top_M, int hop,

@@ -68,7 +68,7 @@ def mind_setup(config, dev):
                        word_threshold=config.word_threshold, sag_neighbors=config.SAG_neighbors, sag_hops=config.SAG_hops,
                        dataset=config.dataset, artefact_root=config.artefact_root or None, similarity_file=config.similarity_file or None,
                        word_embedding_file=config.word_embedding_file or None, word_embedding_dim=config.word_embedding_dim,
-                       data_cache=config.data_cache or None, verbose=config.local_rank in (-1, 0))
+                       data_cache=config.data_cache or None, semantic_embedding_root=config.semantic_embedding_root or None, verbose=config.local_rank in (-1, 0))
     config.set_corpus(corpus)
     model = Model(config)
     model.initialize()

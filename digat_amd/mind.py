@@ -17,7 +17,9 @@ library: no torchtext, no sentence-transformers, no import of the reference.  Wh
   (``digat_user_graph_build``), as a table or per batch.
 * news graphs, first source that exists: the reference's ``news_graph-<hops>-<M>-<dataset>.pkl`` (``mask[:, 0] = 0``, :210); a
   similarity file ``{news_ID: [[news_ID, cos], ...]}`` walked on the device (``construct_SAG.generate_news_graph`` ->
-  ``digat_sag_news_graph``), then ``+ I`` and the cleared mask column (:118, :210); else singleton graphs (node 0 only) with a notice.
+  ``digat_sag_news_graph``), then ``+ I`` and the cleared mask column (:118, :210); a directory of sentence embeddings in the
+  reference's layout (``semantic_embedding_root``: ``construct_SAG.build_similarity`` makes the similar-news lists on the device, the
+  same walk follows); else singleton graphs (node 0 only) with a notice.
 
 Departures from the reference, all documented here:
 * a title number (``<NUM>``) that falls under ``word_threshold`` is absent from ``word_dict``; the reference raises ``KeyError`` at
@@ -44,7 +46,7 @@ from .synthetic import news_graph_size
 
 _PAT = re.compile(r"[\w]+|[.,!?;|]")
 SPLITS = ("train", "dev", "test")
-CACHE_VERSION = 1
+CACHE_VERSION = 2
 
 
 def is_number(s: str) -> bool:
@@ -75,6 +77,22 @@ def read_news(roots):
                 if news_ID not in seen:
                     seen.add(news_ID)
                     out.append((news_ID, category, subCategory, title, i))
+    return out
+
+
+def read_news_text(roots):
+    """``read_news`` with the abstract, which the SAG's sentence embeddings are made of too:
+    ``(news_ID, category, subCategory, title, abstract, file index)``."""
+    seen, out = set(), []
+    for i, root in enumerate(roots):
+        with open(os.path.join(root, 'news.tsv'), 'r', encoding='utf-8') as f:
+            for line in f:
+                if not line.strip():
+                    continue
+                news_ID, category, subCategory, title, abstract = line.split('\t')[:5]
+                if news_ID not in seen:
+                    seen.add(news_ID)
+                    out.append((news_ID, category, subCategory, title, abstract, i))
     return out
 
 
@@ -202,8 +220,9 @@ class MindCorpus:
     news_node_ID: Optional[np.ndarray] = None        # [news_num, N] int32
     news_graph: Optional[np.ndarray] = None          # [news_num, N, N] bool
     news_graph_mask: Optional[np.ndarray] = None     # [news_num, N] bool, column 0 cleared
-    news_graph_source: str = ""                      # "artefact", "similarity" or "singleton"
+    news_graph_source: str = ""                      # "artefact", "similarity", "embeddings" or "singleton"
     similarity: Optional[dict] = None                # a similarity file read but not walked yet
+    embedding_news: Optional[list] = None            # read_news_text's list: the SAG is built from params['semantic_embedding_root'] on first use
     word_embedding: Optional[np.ndarray] = None      # [V, dim] float32, or None: the module's own initialisation
     tsv_sizes: dict = field(default_factory=dict)
 
@@ -218,13 +237,19 @@ class MindCorpus:
     test = property(lambda self: self.splits['test'])
 
     def graphs(self):
-        """(news_node_ID, news_graph, news_graph_mask); a similarity file is walked here, on the device, on first use."""
+        """(news_node_ID, news_graph, news_graph_mask); a similarity file is walked here, on the device, on first use, and so are
+        the lists built from sentence embeddings."""
         if self.news_graph is None:
-            if self.similarity is None:
+            if self.similarity is not None:
+                self.set_news_graphs(*walk_similarity(self.similarity, self.dictionaries['news_ID'], self.params['sag_neighbors'],
+                                                      self.params['sag_hops'], self.news_graph_size), source="similarity")
+            elif self.embedding_news is not None:
+                self.set_news_graphs(*walk_embeddings(self.embedding_news, self.dictionaries, self.params['semantic_embedding_root'],
+                                                      self.params['sag_neighbors'], self.params['sag_hops'], self.news_graph_size,
+                                                      self.params['dataset']), source="embeddings")
+            else:
                 raise ValueError("this corpus has no news graphs")
-            self.set_news_graphs(*walk_similarity(self.similarity, self.dictionaries['news_ID'], self.params['sag_neighbors'],
-                                                  self.params['sag_hops'], self.news_graph_size), source="similarity")
-            self.similarity = None
+            self.similarity = self.embedding_news = None
         return self.news_node_ID, self.news_graph, self.news_graph_mask
 
     def set_news_graphs(self, node_ID, graph, mask, source: str):
@@ -295,6 +320,16 @@ def walk_similarity(similarity: dict, news_ID: dict, top_M: int, hops: int, node
     return node_ID, graph, mask
 
 
+def walk_embeddings(news, dictionaries: dict, embedding_root: str, top_M: int, hops: int, node_num: int, dataset: str):
+    """Sentence embeddings -> similar-news lists -> (news_node_ID, news_graph + I, news_graph_mask), all on the device."""
+    import torch
+    from . import construct_SAG
+    lists = construct_SAG.build_similarity(news, dictionaries, embedding_root, top_M, dataset)
+    node_ID, graph, mask = construct_SAG.news_graph_device(*lists, top_M=top_M, hop=hops, news_node_num=node_num)
+    graph = graph | torch.eye(node_num, dtype=torch.bool, device=graph.device)[None]          # MIND_corpus.py:118
+    return node_ID.cpu().numpy(), graph.cpu().numpy(), mask.cpu().numpy()
+
+
 def singleton_graphs(news_num: int, node_num: int):
     """Every news alone in its graph: node 0 is the news, identity adjacency, empty mask — what an isolated news gets from the walk."""
     node_ID = np.zeros((news_num, node_num), dtype=np.int32)
@@ -342,6 +377,13 @@ def parse_behaviors(path: str, news_ID: dict, news_category: np.ndarray, categor
                      np.asarray(cand, dtype=np.int32), np.asarray(label, dtype=np.int8) if labelled else None)
 
 
+def _embedding_files(root: Optional[str]):
+    if not root:
+        return ()
+    return tuple(sorted(p for sub in ('semantic_embeddings', 'corpus_semantic_embeddings') for ext in ('pkl', 'npy')
+                        for p in glob.glob(os.path.join(glob.escape(root), sub, '*_semantic_embeddings-*.' + ext))))
+
+
 def _tsv_sizes(roots, extra=()):
     files = [os.path.join(r, n) for r in roots for n in ('news.tsv', 'behaviors.tsv')] + [p for p in extra if p]
     return {p: os.path.getsize(p) for p in files}
@@ -350,20 +392,23 @@ def _tsv_sizes(roots, extra=()):
 def load(data_root: str, max_history_num: int = 50, max_title_length: int = 32, word_threshold: int = 3, sag_neighbors: int = 5,
          sag_hops: int = 2, dataset: str = 'MIND-small', artefact_root: Optional[str] = None, similarity_file: Optional[str] = None,
          word_embedding_file: Optional[str] = None, word_embedding_dim: int = 300, data_cache: Optional[str] = None,
-         defer_news_graphs: bool = False, verbose: bool = True) -> MindCorpus:
+         defer_news_graphs: bool = False, verbose: bool = True, semantic_embedding_root: Optional[str] = None) -> MindCorpus:
     """The corpus under ``data_root`` (``train/``, ``dev/``, ``test/``, each with ``news.tsv`` and ``behaviors.tsv``).
 
     ``artefact_root``: a directory of the reference's artefacts; its five dictionaries are used instead of being rebuilt when all
     are there (the news count is checked against the files, :251), its ``news_graph`` / ``word_embedding`` pkl are taken, and the
     category indices of its ``user_history_graph`` pkl are checked against the loader's.  ``similarity_file``: walked on the device
     unless the artefacts hold the news graphs — at once, or with ``defer_news_graphs`` on first use (nothing is cached then: the
-    cache holds the graphs).  ``data_cache``: a directory
+    cache holds the graphs).  ``semantic_embedding_root``: the reference's ``<dataset>-SAG`` directory of sentence embeddings
+    (``construct_SAG.read_embeddings``); with neither graphs nor a similarity file the similar-news lists are built from it on the
+    device and walked, at once or deferred as a similarity file is.  ``data_cache``: a directory
     ``MindCorpus.save`` wrote is loaded when its header names these parameters and these files' sizes, and (re)written otherwise."""
     roots = [os.path.join(data_root, s) for s in SPLITS]
     params = dict(max_history_num=int(max_history_num), max_title_length=int(max_title_length), word_threshold=int(word_threshold),
                   sag_neighbors=int(sag_neighbors), sag_hops=int(sag_hops), dataset=dataset, artefact_root=artefact_root,
-                  similarity_file=similarity_file, word_embedding_file=word_embedding_file, word_embedding_dim=int(word_embedding_dim))
-    sizes = _tsv_sizes(roots, (similarity_file, word_embedding_file))
+                  similarity_file=similarity_file, word_embedding_file=word_embedding_file, word_embedding_dim=int(word_embedding_dim),
+                  semantic_embedding_root=semantic_embedding_root)
+    sizes = _tsv_sizes(roots, (similarity_file, word_embedding_file) + _embedding_files(semantic_embedding_root))
     if data_cache and os.path.exists(os.path.join(data_cache, 'header.json')):
         with open(os.path.join(data_cache, 'header.json'), 'r', encoding='utf-8') as f:
             header = json.load(f)
@@ -409,9 +454,13 @@ def load(data_root: str, max_history_num: int = 50, max_title_length: int = 32, 
             corpus.similarity = json.load(f)
         if not defer_news_graphs:
             corpus.graphs()
+    elif semantic_embedding_root:
+        corpus.embedding_news = read_news_text(roots)
+        if not defer_news_graphs:
+            corpus.graphs()
     else:
         if verbose:
-            print("mind: no news_graph artefact and no similarity file: every news graph is the news alone", flush=True)
+            print("mind: no news_graph artefact, no similarity file and no sentence embeddings: every news graph is the news alone", flush=True)
         corpus.set_news_graphs(*singleton_graphs(news_num, corpus.news_graph_size), source="singleton")
     if artefact_root:
         user_file = _artefact(artefact_root, 'user_history_graph-%d-' % max_history_num, '.pkl', dataset)
@@ -430,7 +479,9 @@ def load(data_root: str, max_history_num: int = 50, max_title_length: int = 32, 
             raise ValueError(f"{word_embedding_file}: {corpus.word_embedding.shape[0]} rows for a vocabulary of {len(word_dict)}")
     elif verbose:
         print("mind: no word embedding file: the word embedding keeps the module's own initialisation", flush=True)
-    if data_cache and (corpus.news_graph is not None or corpus.similarity is not None):
+    if verbose:
+        print(f"mind: news graphs from {corpus.news_graph_source or 'a source walked on first use'}", flush=True)
+    if data_cache and (corpus.news_graph is not None or corpus.similarity is not None or corpus.embedding_news is not None):
         if not (defer_news_graphs and corpus.news_graph is None):
             corpus.save(data_cache)
     return corpus

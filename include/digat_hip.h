@@ -611,6 +611,20 @@ size_t digat_sag_cos_topk_workspace_bytes(int64_t n, int64_t m, int dim);
 int digat_sag_cos_topk(const float* title, const float* content, int64_t n, const float* corpus_title, const float* corpus_content,
                        int64_t m, int dim, int k, float* values, int32_t* indices, void* workspace, size_t workspace_bytes,
                        void* stream);
+/* generate_similar_news_list (construct_SAG.py:303-320), the average kind, for one category, fused behind the same cosine
+ * GEMM: the n query rows and m corpus rows are GROUPS of news with one title (news_dict_inv); group_start [n + 1] /
+ * group_member and corpus_start [m + 1] / corpus_member are CSR tables of their news rows (corpus: first member = the
+ * group's representative, every group non-empty).  M' = min(top_M, m - 1), k = M' + 1 <= 32.  For every member news x of
+ * query group g, the k best corpus groups by the mean of the four cosines (digat_sag_cos_topk's kind 4, bit for bit) are
+ * walked in order; one that holds x itself is skipped, the others append (representative, cosine) to row x of sim_index /
+ * sim_cos [news_num, top_M] until M' are written (M' = 0: the stop test never fires, as in the reference, and the one entry
+ * is written unless skipped); sim_len[x] = the count.  Rows of news in no group of the call are not touched.  The tables
+ * are not validated here: every member row must lie in [0, news_num).  Workspace: that of digat_sag_cos_topk. */
+size_t digat_sag_similar_lists_workspace_bytes(int64_t n, int64_t m, int dim);
+int digat_sag_similar_lists(const float* title, const float* content, int64_t n, const float* corpus_title, const float* corpus_content,
+                            int64_t m, int dim, int top_M, const int32_t* group_start, const int32_t* group_member,
+                            const int32_t* corpus_start, const int32_t* corpus_member, int32_t* sim_index, float* sim_cos,
+                            int32_t* sim_len, int64_t news_num, void* workspace, size_t workspace_bytes, void* stream);
 /* generate_news_graph (construct_SAG.py:449-485): sim_index / sim_cos [news_num, top_M] = every news's similar-news list
  * (news indices, cosines; sim_len [news_num] entries are valid), hop, news_node_num <= 256, threshold = the reference's
  * similarity_threshold (0.5, :10).  Outputs (all rewritten): news_node_ID [news_num, nn] int32, news_graph

@@ -24,6 +24,12 @@
                                              median [min, max] of five rounds, bytes/s against the one-pass floor rows x 4 B
   python tools/kbench.py recommend [users news_num]   util.recommend: 64 users against the pool of all news at MIND-small shapes
                                              (65 238 news, N = 10, H = 50, C = 17, d = 400, depth 3), users per second
+  python tools/kbench.py sag-lists [news categories dim top_M]   the SAG's similar-news lists of a MIND-small-shaped corpus
+                                             (65 238 news over 17 categories of skewed sizes, the largest ~30 %, dim 768, top_M 5):
+                                             construct_SAG.similar_news_lists_device per category against cos_topk_device + all five
+                                             kinds copied to the host + similar_news_lists_host, alternated, median [min, max] of five
+                                             rounds (wall clock around a device synchronise); then the walk, and build_similarity
+                                             with the embeddings read from .npy files
 Timing with torch events on the current stream, median of --iters launches.
 """
 import os
@@ -476,6 +482,90 @@ def bench_sag(n=30000, m=30000, dim=768, top_M=5, news_num=65238, hop=2, cpu_row
           f"   CPU walk {cpu2 * news_num:.0f} ms ({1 / cpu2:.1f} k news/s, 1 thread, {sub} rows)")
 
 
+def bench_sag_lists(news_num=65238, categories=17, dim=768, top_M=5, rounds=5):
+    """Embeddings -> similar-news lists for a whole corpus, two ways in one process, alternated, median [min, max] of ``rounds``
+    rounds of wall clock (device synchronised): (a) one ``similar_news_lists_device`` call per category (CSR validation and upload
+    included), (b) the route without the fused entry: ``cos_topk_device`` per category, its [5, n, k] tables copied to the host,
+    ``similar_news_lists_host``.  Embeddings are on the device for both.  Then the news-graph walk over (a)'s lists, and
+    ``build_similarity`` end to end (news bookkeeping + .npy files read from a temporary directory + upload + (a))."""
+    import shutil
+    import tempfile
+    import time
+    from digat_amd import construct_SAG, synthetic
+    dev = torch.device("cuda:0")
+    rng = np.random.default_rng(0)
+    share = 0.7 ** np.arange(categories)
+    sizes = np.maximum((share / share.sum() * news_num).astype(np.int64), 8)
+    sizes[0] += news_num - sizes.sum()
+    news, serial = [], 0
+    for c, size in enumerate(sizes):                                   # ~2 % of the news repeat a title; a quarter are test news
+        for i in range(int(size)):
+            serial += 1
+            group = i if rng.random() > 0.02 or i == 0 else int(rng.integers(0, i))
+            news.append(("N%d" % serial, "c%d" % c, "s", "title %d of %d" % (group, c), "abstract %d" % serial, int(rng.integers(0, 4)) % 3))
+    news_ID = {"<PAD>": 0, **{n[0]: i + 1 for i, n in enumerate(news)}}
+    dictionaries = {"news_ID": news_ID, "category": {"c%d" % c: c for c in range(categories)}}
+    rows, _ = construct_SAG.category_rows(news)
+    root = tempfile.mkdtemp(prefix="kbench_sag_")
+    try:
+        work, embeddings = [], {}
+        for c in range(categories):
+            name = "c%d" % c
+            full, corpus, gs, gm, cs, cm = construct_SAG.category_tables(rows[name], news_ID, "small")
+            title, content = synthetic.make_semantic_embeddings(len(full[2]), dim, seed=c)
+            at = {t: i for i, t in enumerate(full[2])}
+            pick = np.array([at[t] for t in corpus[2]])
+            tables = (title, content, title[pick], content[pick])
+            for (mode, sub), pair in zip(construct_SAG.EMBEDDING_DIRS.items(), (tables[:2], tables[2:])):
+                os.makedirs(os.path.join(root, sub), exist_ok=True)
+                for kind, x in zip(("title", "content"), pair):
+                    np.save(os.path.join(root, sub, "%s_semantic_embeddings-%s.npy" % (kind, name)), x)
+            embeddings[name] = tuple(torch.from_numpy(x).to(dev) for x in tables)
+            work.append((embeddings[name], gs, gm, cs, cm))
+        N = len(news_ID)
+        print(f"sag-lists: {N - 1} news, {categories} categories of {int(sizes.max())} .. {int(sizes.min())} news, dim {dim}, top_M {top_M}; "
+              f"{sum(len(w[1]) - 1 for w in work)} query groups, {sum(len(w[3]) - 1 for w in work)} corpus groups")
+        out = tuple(torch.zeros(shape, dtype=dt, device=dev) for shape, dt in (((N, top_M), torch.int32), ((N, top_M), torch.float32), ((N,), torch.int32)))
+
+        def fused():
+            for emb, gs, gm, cs, cm in work:
+                construct_SAG.similar_news_lists_device(*emb, top_M, gs, gm, cs, cm, N, out=out)
+
+        host_out = [None]
+
+        def unfused():
+            res = (np.zeros((N, top_M), dtype=np.int32), np.zeros((N, top_M), dtype=np.float32), np.zeros(N, dtype=np.int32))
+            for emb, gs, gm, cs, cm in work:
+                values, indices = construct_SAG.cos_topk_device(*emb, top_M=top_M)
+                values, indices = values.cpu().numpy(), indices.cpu().numpy()
+                construct_SAG.similar_news_lists_host(values[4], indices[4], values.shape[2], gs, gm, cs, cm, top_M, N, out=res)
+            host_out[0] = res
+
+        def wall(fn):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3
+
+        fused()
+        ta, tb = [], []
+        for _ in range(rounds):
+            ta.append(wall(fused))
+            tb.append(wall(unfused))
+        same = all(np.array_equal(o.cpu().numpy(), h) for o, h in zip(out, host_out[0]))
+        stat = lambda v: "%.1f ms [%.1f, %.1f]" % (sorted(v)[len(v) // 2], min(v), max(v))
+        print(f"  similar_news_lists_device per category : {stat(ta)}")
+        print(f"  cos_topk_device + 5 kinds to host + host walk : {stat(tb)}   ({sorted(tb)[len(tb) // 2] / sorted(ta)[len(ta) // 2]:.1f}x; same lists: {same})")
+        nn = synthetic.news_graph_size(top_M, 2)
+        tw = [wall(lambda: construct_SAG.news_graph_device(*out, top_M=top_M, hop=2, news_node_num=nn)) for _ in range(rounds)]
+        print(f"  news_graph_device (2 hops, {nn} nodes) over those lists : {stat(tw)}")
+        td = [wall(lambda: construct_SAG.build_similarity(news, dictionaries, root, top_M, "small")) for _ in range(3)]
+        print(f"  build_similarity end to end (news_meta, .npy files read, upload, lists) : {stat(td)}  (3 runs)")
+    finally:
+        shutil.rmtree(root, ignore_errors=True)
+
+
 def bench_user_graph(G=1024, H=50, C=17, I=73152, rounds=5):
     """A scoring batch's user graphs and category masks, three ways in one process, alternated, median [min, max] of ``rounds``
     rounds: (a) the table path's two gathers (digat_gather_tables) of G consecutive impressions, (b) digat_user_graph_build with
@@ -836,6 +926,8 @@ if __name__ == "__main__":
         bench_nrms_train(*nums)
     elif what == "sag":
         bench_sag(*nums)
+    elif what == "sag-lists":
+        bench_sag_lists(*nums)
     elif what == "topic":
         bench_topic(*nums)
     elif what == "user-graph":
