@@ -213,6 +213,88 @@ def topk_segments(scores, seg_start, k: int, ids=None, skip=None):
     return out_s, out_i, count
 
 
+DOT_TOPK_CHUNK = 2048    # include/digat_hip.h: DIGAT_DOT_TOPK_CHUNK, the pool positions one level-1 workgroup of digat_dot_topk walks
+DOT_TOPK_USERS = 64      # ... DIGAT_DOT_TOPK_USERS, the users of that workgroup's tile
+DOT_TOPK_SUB = 64        # ... DIGAT_DOT_TOPK_SUB, the pool positions of one product sub-tile
+
+
+def dot_topk_host(scores, k: int, pool=None, skip=None):
+    """The contract of ``digat_dot_topk`` on a given score matrix ``scores`` [G, P], in numpy: ``topk_segments_host`` over G
+    segments of length P whose ids are ``pool`` (the positions when None).  Returns ``(scores [G,k], ids [G,k], count [G])``."""
+    S = np.ascontiguousarray(scores, dtype=np.float32)
+    if S.ndim != 2:
+        raise ValueError("scores must be [G, P]")
+    G, P = S.shape
+    ids = np.arange(P, dtype=np.int64) if pool is None else np.asarray(pool, dtype=np.int64)
+    if ids.shape != (P,):
+        raise ValueError(f"pool must have one id per column ({P}), got shape {ids.shape}")
+    return topk_segments_host(S.ravel(), np.arange(G + 1, dtype=np.int64) * P, k, ids=np.tile(ids, G), skip=skip)
+
+
+def _check_dot_args(users, news, pool, skip=None, k=None):
+    import torch
+    if users.dim() != 2 or news.dim() != 2 or users.shape[1] != news.shape[1] or users.shape[1] < 1:
+        raise ValueError(f"users [G, d] and news [N, d] must share d >= 1, got {tuple(users.shape)} and {tuple(news.shape)}")
+    G, N = int(users.shape[0]), int(news.shape[0])
+    if k is not None and not 1 <= int(k) <= TOPK_MAX_K:
+        raise ValueError(f"k must be in [1, {TOPK_MAX_K}], got {k}")
+    if pool is not None:
+        if pool.dim() != 1 or pool.dtype in (torch.float16, torch.float32, torch.float64, torch.bool):
+            raise ValueError("pool must be a 1-D integer tensor of news rows")
+        if pool.numel() and (int(pool.min()) < 0 or int(pool.max()) >= N):
+            raise ValueError(f"pool ids must lie in [0, {N})")
+    if skip is not None and (skip.dim() != 2 or skip.shape[0] != G or skip.shape[1] > TOPK_MAX_SKIP):
+        raise ValueError(f"skip must be [users, at most {TOPK_MAX_SKIP}], got shape {tuple(skip.shape)}")
+    return G, N, N if pool is None else int(pool.shape[0]), int(users.shape[1])
+
+
+def dot_topk(users, news, k: int, pool=None, skip=None):
+    """For every row of ``users`` [G, d] the k best rows of ``news`` [N, d] by inner product, on the GPU without the [G, P] score
+    matrix (``digat_dot_topk``).  ``pool`` [P] int64: the news rows to choose from, in this order (None: all N); ``skip``
+    [G, L <= 256] int64: ids a user must not get.  Order: score descending, ties by pool position, NaNs last.  Returns
+    ``(scores [G,k] float32, ids [G,k] int64, count [G] int32)`` on the device; slots at or beyond ``count`` hold ``-inf`` / ``-1``.
+    A score is the fp32 fmaf chain over the d channels: the bits ``dot_scores`` gives.  Stream-ordered; only the pool's id range is
+    read back, for the check."""
+    import torch
+    from . import _lib
+    given = [t for t in (users, news, pool, skip) if t is not None]
+    dev = _lib.require_device(*given)
+    G, N, P, d = _check_dot_args(users, news, pool, skip, k)
+    u, v = _lib.f32(users.detach()), _lib.f32(news.detach())
+    pl = None if pool is None else pool.to(torch.int64).contiguous()
+    sk = None if skip is None or skip.shape[1] == 0 else skip.to(torch.int64).contiguous()
+    k = int(k)
+    out_s = torch.full((G, k), float("-inf"), dtype=torch.float32, device=dev)
+    out_i = torch.full((G, k), -1, dtype=torch.int64, device=dev)
+    count = torch.zeros((G,), dtype=torch.int32, device=dev)
+    if G == 0 or P == 0:
+        return out_s, out_i, count
+    L = _lib.lib()
+    need = int(L.digat_dot_topk_workspace_bytes(G, P, k))
+    ws = _lib.workspace(need, dev, "dot_topk")
+    _lib.check(L.digat_dot_topk(u.data_ptr(), v.data_ptr(), _lib.ptr(pl), G, N, P, d, _lib.ptr(sk), 0 if sk is None else int(sk.shape[1]),
+                                k, out_s.data_ptr(), out_i.data_ptr(), count.data_ptr(), ws.data_ptr(), need, _lib.stream_ptr()),
+               "digat_dot_topk")
+    return out_s, out_i, count
+
+
+def dot_scores(users, news, pool=None):
+    """``users`` [G, d] x ``news[pool]`` [P, d] -> [G, P] float32 on the GPU (``digat_dot_scores``): the product ``dot_topk`` selects
+    from, bit for bit — its yardstick, and the way to the matrix for a caller who wants it."""
+    import torch
+    from . import _lib
+    given = [t for t in (users, news, pool) if t is not None]
+    dev = _lib.require_device(*given)
+    G, N, P, d = _check_dot_args(users, news, pool)
+    u, v = _lib.f32(users.detach()), _lib.f32(news.detach())
+    pl = None if pool is None else pool.to(torch.int64).contiguous()
+    out = torch.empty((G, P), dtype=torch.float32, device=dev)
+    if G and P:
+        _lib.check(_lib.lib().digat_dot_scores(u.data_ptr(), v.data_ptr(), _lib.ptr(pl), G, N, P, d, out.data_ptr(), _lib.stream_ptr()),
+                   "digat_dot_scores")
+    return out
+
+
 class AvgMetric:
     """util.py:100-121: the model-selection average."""
 

@@ -9,6 +9,9 @@ autograd (``MhsaFused``) — the stacked Q|K|V projection, the key-masked attent
 news encoder hands over token ids and the word embedding, the user encoder dense rows (training) or news ids and the cached news
 representations (dev scoring).  The SA gate is the news-graph context call ``digat_news_ctx_*`` on ``[orig ; aug]`` with node 0
 masked out: it takes its query from node 0, attends over the unmasked nodes, gates and mixes (Appendix-B newsEncoders.py:100-102).
+``recommend`` answers "which k news for this user": the logit is a plain inner product, so a shared candidate pool runs on the fused
+inner-product + top-k kernel (``evaluate.dot_topk``: no [users, news] score matrix), and ``candidates_csr`` hands the lists to
+``util.recommend`` for a DIGAT re-ranking.
 Every class has a ``forward_stock`` on stock PyTorch: the CPU path and the yardstick.  There is no fall-back on the GPU: a shape the
 library refuses raises.
 """
@@ -484,3 +487,108 @@ def compute_scores(model, dev, batch_size=1024, grouped=True, result_file=None, 
         with open(result_file, "wb") as f:
             f.write(evaluate.rank_file_bytes(ranks, row_imp))
     return scores, ranks, metrics
+
+
+# ---- retrieval: which k news of the corpus for this user -----------------------------------------------------------------------
+def _histories(dev, users):
+    """``users`` of ``recommend`` as ``(history_ids [G,H] int64, history_mask [G,H])`` on the device of ``dev.history_ids``: a 1-D
+    integer array of impression indices of ``dev``, or a pair ``(history_ids, history_mask)`` of people who are no rows of it."""
+    device = dev.history_ids.device
+    H, I, N = int(dev.history_ids.shape[1]), int(dev.history_ids.shape[0]), int(dev.title_text.shape[0])
+    as_t = lambda x: torch.as_tensor(np.asarray(x) if not torch.is_tensor(x) else x)
+    if isinstance(users, (tuple, list)) and len(users) == 2 and as_t(users[0]).dim() == 2:
+        hist, mask = as_t(users[0]).to(torch.int64), as_t(users[1])
+        if tuple(mask.shape) != tuple(hist.shape):
+            raise ValueError(f"users must be (history_ids [G,H], history_mask [G,H]), got {tuple(hist.shape)} and {tuple(mask.shape)}")
+        if int(hist.shape[1]) != H:
+            raise ValueError(f"users' history length {int(hist.shape[1])} is not the corpus's max_history_num {H}")
+        if hist.numel() and (int(hist.min()) < 0 or int(hist.max()) >= N):
+            raise ValueError(f"history ids must lie in [0, {N})")
+        return hist.to(device).contiguous(), mask.to(device).contiguous()
+    idx = as_t(users)
+    if idx.dim() != 1 or idx.dtype in (torch.float16, torch.float32, torch.float64, torch.bool):
+        raise ValueError("users must be a 1-D integer array of impression indices or a (history_ids, history_mask) pair")
+    idx = idx.to(torch.int64)
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= I):
+        raise ValueError(f"impression indices must lie in [0, {I})")
+    idx = idx.to(device)
+    return dev.history_ids.index_select(0, idx).to(torch.int64), dev.history_mask.index_select(0, idx)
+
+
+def _encode_users(model, plain, hist, mask, batch_size):
+    ue = model.user_encoder
+    with torch.no_grad():
+        out = [ue.encode_cached(plain, hist[lo:lo + batch_size], mask[lo:lo + batch_size]) for lo in range(0, hist.shape[0], batch_size)]
+    return torch.cat(out) if out else plain.new_zeros((0, plain.shape[1]))
+
+
+def user_vectors(model, dev, users, batch_size=1024):
+    """The user representations [G, hd] of ``users`` (``_histories``: impression indices of ``dev`` or a ``(history_ids,
+    history_mask)`` pair), encoded through ``encode_cached`` on the plain news cache in batches, in eval mode."""
+    hist, mask = _histories(dev, users)
+    model.eval()
+    plain, _ = news_caches(model, dev.title_text, dev.title_mask, dev.augmented_title_text, dev.augmented_title_mask, 4 * batch_size)
+    return _encode_users(model, plain, hist, mask, batch_size)
+
+
+def recommend(model, dev, users, candidates=None, k=10, exclude_history=True, batch_size=1024):
+    """For every user, which k news, in order: ``(news_ids [G,k] int64, scores [G,k] float32, count [G] int32)`` on the model's
+    device.  Order: score descending, equal scores in candidate order; slots at or beyond ``count[g]`` hold id -1 and score -inf.
+
+    ``dev`` is the corpus-like object of ``compute_scores``; candidates are read from the augmented cache, histories from the plain
+    one, as there.  ``users``: impression indices of ``dev`` or ``(history_ids [G,H], history_mask [G,H])``.  ``candidates``: None =
+    every news but row 0 (<PAD>); a 1-D id array = one pool for all users — ``evaluate.dot_topk``, the fused inner-product + top-k
+    kernel, which never writes the [G, P] scores; ``(ids [R], start [G+1])`` = per-user lists (``util.recommend_candidates``) —
+    gather, ``row_logits``, ``evaluate.topk_segments``.  ``exclude_history``: a news of the user's history (mask non-zero) is never
+    returned, nor is row 0; False takes the candidates at their word.  On CPU tensors: stock PyTorch and ``topk_segments_host``."""
+    from . import evaluate, util
+    if not 1 <= int(k) <= evaluate.TOPK_MAX_K:
+        raise ValueError(f"k must be in [1, {evaluate.TOPK_MAX_K}], got {k}")
+    k = int(k)
+    hist, mask = _histories(dev, users)
+    G, H, N = int(hist.shape[0]), int(hist.shape[1]), int(dev.title_text.shape[0])
+    if exclude_history and H > evaluate.TOPK_MAX_SKIP:
+        raise ValueError(f"exclude_history takes histories of at most {evaluate.TOPK_MAX_SKIP} news, this corpus has {H}")
+    if candidates is None:
+        candidates = np.arange(1, N, dtype=np.int64)
+    ids, start = util.recommend_candidates(candidates, G, N)
+    model.eval()
+    plain, aug = news_caches(model, dev.title_text, dev.title_mask, dev.augmented_title_text, dev.augmented_title_mask, 4 * batch_size)
+    device = plain.device
+    ids = ids.to(device)
+    user = _encode_users(model, plain, hist, mask, batch_size)
+    skip = torch.where(mask != 0, hist, torch.zeros_like(hist)) if exclude_history else None
+    if device.type != "cuda":
+        row_user, row_cand, seg = util.recommend_rows(0, G, ids, start)
+        scores = (aug[row_cand] * user[row_user]).sum(dim=1)
+        s, i, c = evaluate.topk_segments_host(scores.numpy(), seg.numpy(), k, ids=row_cand.numpy(), skip=skip.numpy() if skip is not None and G else None)
+        return torch.from_numpy(i), torch.from_numpy(s), torch.from_numpy(c)
+    if start is None:
+        s, i, c = evaluate.dot_topk(user, aug, k, pool=ids, skip=skip)
+        return i, s, c
+    out_ids = torch.full((G, k), -1, dtype=torch.int64, device=device)
+    out_scores = torch.full((G, k), float("-inf"), dtype=torch.float32, device=device)
+    out_count = torch.zeros((G,), dtype=torch.int32, device=device)
+    for g0, g1 in util.recommend_user_chunks(G, int(ids.shape[0]), start, util.RECOMMEND_MAX_ROWS):
+        row_user, row_cand, seg = util.recommend_rows(g0, g1, ids, start)
+        if int(row_user.shape[0]) == 0:
+            continue
+        scores = row_logits(aug.index_select(0, row_cand), user.index_select(0, row_user))
+        s, i, c = evaluate.topk_segments(scores, seg, k, ids=row_cand, skip=None if skip is None else skip[g0:g1])
+        out_scores[g0:g1], out_ids[g0:g1], out_count[g0:g1] = s, i, c
+    return out_ids, out_scores, out_count
+
+
+def candidates_csr(news_ids, count):
+    """The valid slots of a ``[G,k]`` result (``recommend``'s ``news_ids`` and ``count``) as the per-user lists
+    ``util.recommend(candidates=...)`` takes: ``(ids [R] int64 tensor, start [G+1] int64 numpy)`` — NRMS retrieves, DIGAT re-ranks."""
+    news_ids = torch.as_tensor(news_ids)
+    cnt = torch.as_tensor(count).to(torch.int64).cpu()
+    if news_ids.dim() != 2 or tuple(cnt.shape) != (news_ids.shape[0],):
+        raise ValueError(f"news_ids must be [G,k] and count [G], got {tuple(news_ids.shape)} and {tuple(cnt.shape)}")
+    if cnt.numel() and (int(cnt.min()) < 0 or int(cnt.max()) > news_ids.shape[1]):
+        raise ValueError(f"count must lie in [0, {int(news_ids.shape[1])}]")
+    keep = torch.arange(news_ids.shape[1])[None, :] < cnt[:, None]
+    start = np.zeros(news_ids.shape[0] + 1, dtype=np.int64)
+    np.cumsum(cnt.numpy(), out=start[1:])
+    return news_ids[keep.to(news_ids.device)].to(torch.int64).contiguous(), start

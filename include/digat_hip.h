@@ -581,6 +581,34 @@ int digat_topk_segments(const float* scores, const int64_t* seg_start, int64_t r
                         const int64_t* skip, int skip_len, int k, float* out_scores, int64_t* out_ids, int32_t* out_count,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- inner-product retrieval: the k best rows of a table per user vector, without the score matrix (digat_amd.nrms.recommend) ---
+ * users [G, d] f32, news [N, d] f32; pool [P] int64 row ids of news, or NULL = rows 0 .. N-1 in order (then P must equal N).
+ * score(g, p) = the fp32 fmaf chain over c = 0 .. d-1 from 0 of users[g][c] * news[pool[p]][c], on the fp32 matrix cores: its bits
+ * depend on the two vectors and d alone — not on G, N, P, the pool order, the tile, or which of the two entries computed it.
+ * digat_dot_topk is digat_topk_segments over G segments of equal length P without the scores in memory: for user g the elements
+ * are the pool positions whose id is not in skip[g] ([G, skip_len] int64, or NULL / 0) and lies in [0, N) (any other id is no
+ * element, and no read leaves the arrays); order: topk_key of the score descending, ties by pool position, NaNs last,
+ * -0.0 == +0.0; repeated ids are distinct elements.  out_count [G] = min(k, elements); slots j < count of out_scores / out_ids
+ * [G, k] hold the j-th element's score bits and pool id (the row number when pool is NULL), slots j >= count hold -inf and -1:
+ * every output byte is written.  1 <= k <= 128, 0 <= skip_len <= 256, d > 0, non-null required pointers, sizes >= 0, an
+ * 8-byte-aligned workspace (DIGAT_ERR_ARG otherwise); ceil(G / DIGAT_DOT_TOPK_USERS) * ceil(P / DIGAT_DOT_TOPK_CHUNK) < 2^31
+ * (DIGAT_ERR_SHAPE); a short workspace is DIGAT_ERR_WORKSPACE (it may hold anything on entry) — all before any launch.  G == 0
+ * returns DIGAT_OK without a launch; P == 0 sets every count to 0.  Workspace: 8 k bytes per (user, chunk of
+ * DIGAT_DOT_TOPK_CHUNK pool positions).  Stream-ordered: two launches on `stream` (one workgroup per tile of
+ * DIGAT_DOT_TOPK_USERS users and chunk, walking sub-tiles of DIGAT_DOT_TOPK_SUB positions; then one per user); no allocation,
+ * no host synchronisation, no read of device memory on the host.
+ * digat_dot_scores: the same product stored as out [G, P] — the yardstick of the fused entry, and the way to the matrix for
+ * callers who want it (a position whose id is outside [0, N) reads a zero row). */
+#define DIGAT_DOT_TOPK_CHUNK 2048
+#define DIGAT_DOT_TOPK_USERS 64
+#define DIGAT_DOT_TOPK_SUB 64
+size_t digat_dot_topk_workspace_bytes(int64_t users, int64_t pool, int k);
+int digat_dot_topk(const float* users, const float* news, const int64_t* pool, int64_t G, int64_t N, int64_t P, int d, const int64_t* skip,
+                   int skip_len, int k, float* out_scores, int64_t* out_ids, int32_t* out_count, void* workspace, size_t workspace_bytes,
+                   void* stream);
+int digat_dot_scores(const float* users, const float* news, const int64_t* pool, int64_t G, int64_t N, int64_t P, int d, float* out,
+                     void* stream);
+
 /* ---- vanilla-GAT update layer of the ablation encoders -----------------------------------------
  * graphEncoders.py:493-519 (wo_interaction), :641-651 (News_graph_wo_inter), :788-798 (User_graph_wo_inter), eval mode:
  * h = X W^T + bW; e_ij = leaky_relu_0.2(a1.h_j + a2.h_i); -1e9 where A_ij = 0; alpha = softmax_j; out = relu(alpha h) + X.

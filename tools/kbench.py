@@ -24,7 +24,11 @@
                                              median [min, max] of five rounds, bytes/s against the one-pass floor rows x 4 B
   python tools/kbench.py recommend [users news_num]   util.recommend: 64 users against the pool of all news at MIND-small shapes
                                              (65 238 news, N = 10, H = 50, C = 17, d = 400, depth 3), users per second
-  python tools/kbench.py sag-lists [news categories dim top_M]   the SAG's similar-news lists of a MIND-small-shaped corpus
+  python tools/kbench.py dot-topk [news_num d]   NRMS retrieval: evaluate.dot_topk (fused inner product + top-k, no score matrix)
+                                             against torch.matmul + evaluate.topk_segments and torch.matmul + torch.topk, G = 64 and
+                                             4 096 users x 65 237 news, d = 400, k = 10 and 100, the three legs in turn, median
+                                             [min, max] of five rounds; then nrms.recommend for 4 096 users end to end
+  python tools/kbench.py sag-lists [news categories dim top_M]  the SAG's similar-news lists of a MIND-small-shaped corpus
                                              (65 238 news over 17 categories of skewed sizes, the largest ~30 %, dim 768, top_M 5):
                                              construct_SAG.similar_news_lists_device per category against cos_topk_device + all five
                                              kinds copied to the host + similar_news_lists_host, alternated, median [min, max] of five
@@ -901,6 +905,73 @@ def bench_recommend(users=64, news_num=65238, rounds=5):
           f"({rows * 12 / med_ms / 1e6:.1f} GB/s of scores + ids)", flush=True)
 
 
+def bench_dot_topk(news_num=65238, d=400, rounds=5):
+    """``evaluate.dot_topk`` (the fused inner-product + top-k kernel: no score matrix) against the two ways to the same lists that
+    write the [G, P] matrix first — (a) ``torch.matmul`` + ``evaluate.topk_segments``, built only from what the tree had before,
+    and (b) ``torch.matmul`` + ``torch.topk`` (tie order unspecified: a yardstick for speed only) — in one process, the three legs
+    taken in turn, median [min, max] of ``rounds`` rounds; G in {64, 4 096} users against all but the PAD row of a MIND-small-sized
+    table, k in {10, 100}.  Then ``nrms.recommend`` for 4 096 users end to end (news caches, user vectors, selection)."""
+    import time
+    import types
+    from digat_amd import evaluate, nrms, synthetic
+    dev = torch.device("cuda:0")
+    L = _lib.lib()
+    g = torch.Generator(device="cpu").manual_seed(0)
+    news = torch.randn(news_num, d, generator=g).to(dev)
+    P = news_num - 1
+    table = news[1:]                                                # the pool "every news but row 0" as a table of its own
+    stat = lambda v: (sorted(v)[len(v) // 2], min(v), max(v))
+    for G in (64, 4096):
+        users = torch.randn(G, d, generator=g).to(dev)
+        seg = (torch.arange(G + 1, dtype=torch.int64) * P).to(dev)
+        for k in (10, 100):
+            fused = lambda: evaluate.dot_topk(users, table, k)
+            via_segments = lambda: evaluate.topk_segments(torch.matmul(users, table.t()).view(-1), seg, k)
+            via_torch = lambda: torch.topk(torch.matmul(users, table.t()), k, dim=1)
+            got, want = fused(), via_torch()
+            torch.cuda.synchronize()
+            same = float((got[1] == want.indices).float().mean())    # the products round differently: near-ties may swap
+            times = ([], [], [])
+            for _ in range(rounds):
+                for leg, fn in zip(times, (fused, via_segments, via_torch)):
+                    leg.append(timeit(fn, iters=5, warm=1)[0])
+            (a, alo, ahi), (b, blo, bhi), (c, clo, chi) = (stat(t) for t in times)
+            product = timeit(lambda: evaluate.dot_scores(users, table), iters=5, warm=1)[0] if k == 10 else None
+            ws = int(L.digat_dot_topk_workspace_bytes(G, P, k))
+            print(f"  G = {G:5d}, P = {P}, d = {d}, k = {k:3d}: dot_topk {a:8.3f} ms [{alo:.3f}, {ahi:.3f}] ({2.0 * G * P * d / a / 1e9:6.1f} TFLOP/s, "
+                  f"workspace {ws / 2**20:.1f} MiB) | matmul + topk_segments {b:8.3f} ms [{blo:.3f}, {bhi:.3f}] (x{b / a:.2f}) | "
+                  f"matmul + torch.topk {c:8.3f} ms [{clo:.3f}, {chi:.3f}] (x{c / a:.2f}) | score matrix {4.0 * G * P / 2**20:.1f} MiB | "
+                  f"ids equal to torch.topk's: {same:.4f}" + (f" | dot_scores alone {product:.3f} ms" if product else ""), flush=True)
+            del got, want
+        del users, seg
+        torch.cuda.empty_cache()
+    G, H, Lw, V = 4096, 50, 32, 30000
+    m = _nrms_model("NRMS", V=V, Lw=Lw, H=H).eval()
+    text, mask = synthetic.make_titles(news_num, Lw, V, seed=2)
+    length = torch.randint(0, H + 1, (G, 1), generator=g)
+    hist_mask = torch.arange(H)[None, :] < length
+    hist = torch.randint(1, news_num, (G, H), generator=g) * hist_mask
+    corpus = types.SimpleNamespace(title_text=torch.from_numpy(text).to(dev), title_mask=torch.from_numpy(mask).to(dev),
+                                   augmented_title_text=None, augmented_title_mask=None, history_ids=hist.to(dev), history_mask=hist_mask.to(dev))
+    who = np.arange(G)
+    nrms.recommend(m, corpus, who, k=10)
+    torch.cuda.synchronize()
+    secs = []
+    for _ in range(rounds):
+        t0 = time.perf_counter()
+        nrms.recommend(m, corpus, who, k=10)
+        torch.cuda.synchronize()
+        secs.append(time.perf_counter() - t0)
+    med, lo, hi = stat(secs)
+    vec = nrms.user_vectors(m, corpus, who)
+    _, aug = nrms.news_caches(m, corpus.title_text, corpus.title_mask, None, None, 4096)
+    pool = torch.arange(1, news_num, dtype=torch.int64, device=dev)
+    skip = corpus.history_ids
+    sel, _ = timeit(lambda: evaluate.dot_topk(vec, aug, 10, pool=pool, skip=skip), iters=5, warm=1)
+    print(f"  nrms.recommend, {G} users x {P} news, k = 10, history excluded: {med:.3f} s [{lo:.3f}, {hi:.3f}] ({G / med:.0f} users/s), "
+          f"of which dot_topk with the pool and {H}-entry skip rows {sel:.3f} ms", flush=True)
+
+
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "xattn"
     nums = [int(v) for v in sys.argv[2:]]
@@ -940,6 +1011,8 @@ if __name__ == "__main__":
         bench_topk(*nums)
     elif what == "recommend":
         bench_recommend(*nums)
+    elif what == "dot-topk":
+        bench_dot_topk(*nums)
     elif what == "linear":
         bench_linear(*nums)
     elif what == "gemm":
