@@ -21,8 +21,8 @@
 //   kept — a later key has to beat it, an equal one loses the position tie.  Cutting early keeps the cuts short and the
 //   threshold fresh.  At the end of the chunk lists longer than k are cut, and the <= k entries go to workspace slot
 //   [user][chunk][k]; unused entries carry position DOT_NOPOS.
-// Level 2, dot_topk_user_kernel, one workgroup per user: topk_select over the user's chunks * k slots (position order), the winners
-//   ordered by counting, score bits from the slots, ids from the pool.
+// Level 2, dot_topk_user_kernel, one workgroup per user: topk_select over the user's chunks * k slots (position order), then
+//   topk_finish (digat_topk.inc: order by counting, fill, count) with score bits from the slots and ids from the pool.
 // The cut is a wave's own count and not topk_select: measured on an MI355X at G = 4 096, P = 65 237, d = 400, topk_select over a
 // list (the whole workgroup behind barriers, one user at a time) made the call 7.7 ms at k = 10 and 42.8 ms at k = 100; the
 // wave-local cut with the early limit 4.4 and 13.1 ms (DESIGN section 8).
@@ -326,29 +326,17 @@ __global__ void __launch_bounds__(256) dot_chunk_kernel(const DotArgs a) {
 
 __global__ void __launch_bounds__(256) dot_topk_user_kernel(const DotArgs a) {
     __shared__ TopkShared sh;
-    const int tid = threadIdx.x;
     const long g = blockIdx.x;
     const uint2* slots = a.ws + g * a.chunks * a.k;
     const DotSlotLoad ld{slots};
     topk_select(ld, a.chunks * a.k, a.k, sh);
-    const int m = (int)sh.nwin;
-    if (tid == 0) a.out_count[g] = m;
-    if (tid < a.k) {
-        if (tid < m) {
-            const unsigned key = sh.win_key[tid];
-            const long long mine = sh.win_idx[tid];               // slot index: slots lie in position order
-            int r = 0;
-            for (int q = 0; q < m; ++q) r += sh.win_key[q] > key || (sh.win_key[q] == key && sh.win_idx[q] < mine);
-            const uint2 e = slots[mine];
-            long pos = (mine / a.k) * DIGAT_DOT_TOPK_CHUNK + (long)e.y;
-            if (pos >= a.P) pos = a.P - 1;                        // cannot happen with level 1's slots: stay inside the pool
-            a.out_scores[g * a.k + r] = __uint_as_float(e.x);
-            a.out_ids[g * a.k + r] = a.pool ? a.pool[pos] : (int64_t)pos;
-        } else {
-            a.out_scores[g * a.k + tid] = -INFINITY;
-            a.out_ids[g * a.k + tid] = -1;
-        }
-    }
+    topk_finish(sh, a.k, a.out_scores + g * a.k, a.out_ids + g * a.k, a.out_count + g, [&](long long slot, float& score, int64_t& id) {
+        const uint2 e = slots[slot];                              // slots lie in position order
+        long pos = (slot / a.k) * DIGAT_DOT_TOPK_CHUNK + (long)e.y;
+        if (pos >= a.P) pos = a.P - 1;                            // cannot happen with level 1's slots: stay inside the pool
+        score = __uint_as_float(e.x);
+        id = a.pool ? a.pool[pos] : (int64_t)pos;
+    });
 }
 
 static long dot_chunks(long pool) { return (pool + DIGAT_DOT_TOPK_CHUNK - 1) / DIGAT_DOT_TOPK_CHUNK; }
@@ -372,12 +360,9 @@ int digat_dot_topk(const float* users, const float* news, const int64_t* pool, i
                    int skip_len, int k, float* out_scores, int64_t* out_ids, int32_t* out_count, void* workspace, size_t workspace_bytes,
                    void* stream) {
     if (!out_scores || !out_ids || !out_count) return DIGAT_ERR_ARG;
-    if (k < 1 || k > TOPK_MAX_K || skip_len < 0 || skip_len > TOPK_MAX_SKIP) return DIGAT_ERR_ARG;
-    const int rc = dot_check(users, news, pool, G, N, P, d);
-    if (rc != DIGAT_OK) return rc;
-    if (!skip || skip_len == 0) { skip = nullptr; skip_len = 0; }
     const size_t need = digat_dot_topk_workspace_bytes(G, P, k);
-    if (need > 0 && (!workspace || ((uintptr_t)workspace & 7))) return DIGAT_ERR_ARG;
+    const int rc = topk_check_args(k, skip, skip_len, dot_check(users, news, pool, G, N, P, d), need > 0, workspace);
+    if (rc != DIGAT_OK) return rc;
     if (workspace_bytes < need) return DIGAT_ERR_WORKSPACE;
     if (G == 0) return DIGAT_OK;
     hipStream_t st = (hipStream_t)stream;

@@ -13,7 +13,7 @@
 //       a workgroup finds its segment by bisection over seg_start and leaves if its id is nobody's.  It writes the chunk's <= k
 //       winners as (key, position in the segment), in POSITION order, into workspace slot [chunk id]; unused slots get key 0.
 //   level 2, one workgroup per segment: the same selection over the segment's candidate slots (contiguous, in position order),
-//       then the <= k winners are ordered by counting and written with their original score bits and ids.
+//       then topk_finish (as in digat_dot_topk.inc): the <= k winners ordered by counting, their score bits and ids, the fill.
 //       A segment of at most TOPK_SMALL = 256 elements (a dev impression has ~37) is level 2's alone: one element per thread, keys
 //       in LDS, every thread counts the elements that order before its own — level 1's workgroups for it leave at once.
 // The selection (topk_select): four rounds of radix select on 256-bin LDS histograms find the k-th key T; every key above T wins,
@@ -23,7 +23,7 @@
 //
 // Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage), 256 threads per workgroup:
 //   topk_chunk_kernel     VGPRs 31   SGPRs 65   LDS 4688 B   scratch 0   occupancy 8 waves / SIMD
-//   topk_segment_kernel   VGPRs 26   SGPRs 80   LDS 4688 B   scratch 0   occupancy 8 waves / SIMD
+//   topk_segment_kernel   VGPRs 26   SGPRs 79   LDS 4688 B   scratch 0   occupancy 8 waves / SIMD   (80 SGPRs before topk_finish)
 
 #define TOPK_MAX_K 128
 #define TOPK_MAX_SKIP 256
@@ -150,6 +150,22 @@ __device__ void topk_select(const Load& ld, long n, int k, TopkShared& sh) {
     __syncthreads();
     if (tid == 0 && sh.nwin > TOPK_MAX_K) sh.nwin = TOPK_MAX_K;
     __syncthreads();
+}
+
+// The end of level 2, called by the whole workgroup after topk_select: the m <= k winners, ranked by counting (key descending,
+// index ascending), go to one output row — winner(index, score, id) hands over each one's original score and id —, fill, count.
+template <class Winner>
+__device__ __forceinline__ void topk_finish(const TopkShared& sh, int k, float* out_scores, int64_t* out_ids, int32_t* out_count,
+                                            const Winner& winner) {
+    const int tid = threadIdx.x, m = (int)sh.nwin;
+    if (tid == 0) *out_count = m;
+    if (tid < k && tid < m) {
+        const unsigned key = sh.win_key[tid];
+        const long long mine = sh.win_idx[tid];
+        int r = 0;
+        for (int q = 0; q < m; ++q) r += sh.win_key[q] > key || (sh.win_key[q] == key && sh.win_idx[q] < mine);
+        winner(mine, out_scores[r], out_ids[r]);
+    } else if (tid < k) { out_scores[tid] = -INFINITY; out_ids[tid] = -1; }
 }
 
 struct TopkArgs {
@@ -287,26 +303,23 @@ __global__ void __launch_bounds__(256) topk_segment_kernel(const TopkArgs a) {
     const long o = topk_first_slot(a, s) * a.k;
     const TopkSlotLoad ld{a.ws_key + o};
     topk_select(ld, chunks * a.k, a.k, sh);
-    const int m = (int)sh.nwin;
-    if (tid == 0) a.out_count[s] = m;
-    if (tid < a.k) {
-        if (tid < m) {
-            const unsigned key = sh.win_key[tid];
-            const long long mine = sh.win_idx[tid];           // candidate index: candidates lie in position order
-            int r = 0;
-            for (int q = 0; q < m; ++q) r += sh.win_key[q] > key || (sh.win_key[q] == key && sh.win_idx[q] < mine);
-            long pos = a.ws_pos[o + mine];
-            if (pos < 0 || pos >= en - st) pos = 0;              // a seg_start that is not non-decreasing: stay inside the segment
-            a.out_scores[s * a.k + r] = a.scores[st + pos];
-            a.out_ids[s * a.k + r] = a.ids ? a.ids[st + pos] : pos;
-        } else {
-            a.out_scores[s * a.k + tid] = -INFINITY;
-            a.out_ids[s * a.k + tid] = -1;
-        }
-    }
+    topk_finish(sh, a.k, a.out_scores + s * a.k, a.out_ids + s * a.k, a.out_count + s, [&](long long c, float& score, int64_t& id) {
+        long pos = a.ws_pos[o + c];                              // candidates lie in position order
+        if (pos < 0 || pos >= en - st) pos = 0;                  // a seg_start that is not non-decreasing: stay inside the segment
+        score = a.scores[st + pos];
+        id = a.ids ? a.ids[st + pos] : pos;
+    });
 }
 
 static long topk_slots(long rows, long segments) { return rows / DIGAT_TOPK_CHUNK + segments; }
+
+// What both selection entries ask of k, the skip rows and the workspace; the entry's verdict `rc` on the rest ranks in between.
+static int topk_check_args(int k, const int64_t*& skip, int& skip_len, int rc, bool need_workspace, const void* workspace) {
+    if (k < 1 || k > TOPK_MAX_K || skip_len < 0 || skip_len > TOPK_MAX_SKIP) return DIGAT_ERR_ARG;
+    if (rc != DIGAT_OK) return rc;
+    if (!skip || skip_len == 0) { skip = nullptr; skip_len = 0; }
+    return need_workspace && (!workspace || ((uintptr_t)workspace & 7)) ? DIGAT_ERR_ARG : DIGAT_OK;
+}
 
 extern "C" {
 
@@ -320,10 +333,8 @@ int digat_topk_segments(const float* scores, const int64_t* seg_start, int64_t r
                         const int64_t* skip, int skip_len, int k, float* out_scores, int64_t* out_ids, int32_t* out_count,
                         void* workspace, size_t workspace_bytes, void* stream) {
     if (!scores || !seg_start || !out_scores || !out_ids || !out_count || rows < 0 || segments < 0) return DIGAT_ERR_ARG;
-    if (k < 1 || k > TOPK_MAX_K || skip_len < 0 || skip_len > TOPK_MAX_SKIP) return DIGAT_ERR_ARG;
     if (skip && !ids) return DIGAT_ERR_ARG;
-    if (!skip || skip_len == 0) { skip = nullptr; skip_len = 0; }
-    if (segments > 0 && (!workspace || ((uintptr_t)workspace & 7))) return DIGAT_ERR_ARG;
+    if (topk_check_args(k, skip, skip_len, DIGAT_OK, segments > 0, workspace) != DIGAT_OK) return DIGAT_ERR_ARG;
     if (topk_slots(rows, segments) > 0x7fffffffL) return DIGAT_ERR_SHAPE;
     if (workspace_bytes < digat_topk_segments_workspace_bytes(rows, segments, k)) return DIGAT_ERR_WORKSPACE;
     if (segments == 0) return DIGAT_OK;

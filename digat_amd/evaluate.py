@@ -118,6 +118,21 @@ def device_ranks_and_metrics(scores, row_impression: np.ndarray, labels: np.ndar
     return ranks.cpu().numpy().astype(np.int64), metrics
 
 
+def ranks_metrics_file(scores, row_impression: np.ndarray, labels=None, result_file=None):
+    """The end of a dev run: ``(ranks int64 numpy [R], (auc, mrr, ndcg5, ndcg10) or None)`` of a score tensor [R] — on the device
+    for CUDA scores (``device_ranks_and_metrics``), ``impression_ranks`` + ``scoring`` for host ones — and the rank file written
+    to ``result_file`` when one is named."""
+    if scores.is_cuda:
+        ranks, metrics = device_ranks_and_metrics(scores, row_impression, labels)
+    else:
+        ranks = impression_ranks(scores.detach().numpy(), row_impression)
+        metrics = scoring(np.asarray(labels), ranks, row_impression) if labels is not None else None
+    if result_file is not None:
+        with open(result_file, "wb") as f:
+            f.write(rank_file_bytes(ranks, row_impression))
+    return ranks, metrics
+
+
 TOPK_CHUNK = 16384       # include/digat_hip.h: DIGAT_TOPK_CHUNK, the elements one level-1 workgroup of digat_topk_segments selects from
 TOPK_MAX_K = 128
 TOPK_MAX_SKIP = 256

@@ -477,15 +477,7 @@ def compute_scores(model, dev, batch_size=1024, grouped=True, result_file=None, 
                 u = ue.encode_cached(plain, dev.history_ids.index_select(0, imp[sl]), dev.history_mask.index_select(0, imp[sl]))
             c = aug.index_select(0, cand[sl])
             scores[sl] = row_logits(c, u) if device.type == "cuda" else (c * u).sum(dim=1)
-    labels = getattr(dev, "row_label", None)
-    if device.type == "cuda":
-        ranks, metrics = evaluate.device_ranks_and_metrics(scores, row_imp, labels)
-    else:
-        ranks = evaluate.impression_ranks(scores.numpy(), row_imp)
-        metrics = evaluate.scoring(np.asarray(labels), ranks, row_imp) if labels is not None else None
-    if result_file is not None:
-        with open(result_file, "wb") as f:
-            f.write(evaluate.rank_file_bytes(ranks, row_imp))
+    ranks, metrics = evaluate.ranks_metrics_file(scores, row_imp, getattr(dev, "row_label", None), result_file)
     return scores, ranks, metrics
 
 
@@ -493,25 +485,11 @@ def compute_scores(model, dev, batch_size=1024, grouped=True, result_file=None, 
 def _histories(dev, users):
     """``users`` of ``recommend`` as ``(history_ids [G,H] int64, history_mask [G,H])`` on the device of ``dev.history_ids``: a 1-D
     integer array of impression indices of ``dev``, or a pair ``(history_ids, history_mask)`` of people who are no rows of it."""
-    device = dev.history_ids.device
-    H, I, N = int(dev.history_ids.shape[1]), int(dev.history_ids.shape[0]), int(dev.title_text.shape[0])
-    as_t = lambda x: torch.as_tensor(np.asarray(x) if not torch.is_tensor(x) else x)
-    if isinstance(users, (tuple, list)) and len(users) == 2 and as_t(users[0]).dim() == 2:
-        hist, mask = as_t(users[0]).to(torch.int64), as_t(users[1])
-        if tuple(mask.shape) != tuple(hist.shape):
-            raise ValueError(f"users must be (history_ids [G,H], history_mask [G,H]), got {tuple(hist.shape)} and {tuple(mask.shape)}")
-        if int(hist.shape[1]) != H:
-            raise ValueError(f"users' history length {int(hist.shape[1])} is not the corpus's max_history_num {H}")
-        if hist.numel() and (int(hist.min()) < 0 or int(hist.max()) >= N):
-            raise ValueError(f"history ids must lie in [0, {N})")
-        return hist.to(device).contiguous(), mask.to(device).contiguous()
-    idx = as_t(users)
-    if idx.dim() != 1 or idx.dtype in (torch.float16, torch.float32, torch.float64, torch.bool):
-        raise ValueError("users must be a 1-D integer array of impression indices or a (history_ids, history_mask) pair")
-    idx = idx.to(torch.int64)
-    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= I):
-        raise ValueError(f"impression indices must lie in [0, {I})")
-    idx = idx.to(device)
+    from . import util
+    idx, hist, mask = util.recommend_user_arrays(users, int(dev.history_ids.shape[0]), int(dev.history_ids.shape[1]),
+                                                 int(dev.title_text.shape[0]), dev.history_ids.device, ("history_ids", "history_mask"))
+    if idx is None:
+        return hist, mask
     return dev.history_ids.index_select(0, idx).to(torch.int64), dev.history_mask.index_select(0, idx)
 
 
@@ -542,41 +520,27 @@ def recommend(model, dev, users, candidates=None, k=10, exclude_history=True, ba
     gather, ``row_logits``, ``evaluate.topk_segments``.  ``exclude_history``: a news of the user's history (mask non-zero) is never
     returned, nor is row 0; False takes the candidates at their word.  On CPU tensors: stock PyTorch and ``topk_segments_host``."""
     from . import evaluate, util
-    if not 1 <= int(k) <= evaluate.TOPK_MAX_K:
-        raise ValueError(f"k must be in [1, {evaluate.TOPK_MAX_K}], got {k}")
-    k = int(k)
     hist, mask = _histories(dev, users)
-    G, H, N = int(hist.shape[0]), int(hist.shape[1]), int(dev.title_text.shape[0])
-    if exclude_history and H > evaluate.TOPK_MAX_SKIP:
-        raise ValueError(f"exclude_history takes histories of at most {evaluate.TOPK_MAX_SKIP} news, this corpus has {H}")
+    G, N = int(hist.shape[0]), int(dev.title_text.shape[0])
+    k = util.recommend_limits(k, int(hist.shape[1]) if exclude_history else 0)
     if candidates is None:
         candidates = np.arange(1, N, dtype=np.int64)
     ids, start = util.recommend_candidates(candidates, G, N)
     model.eval()
     plain, aug = news_caches(model, dev.title_text, dev.title_mask, dev.augmented_title_text, dev.augmented_title_mask, 4 * batch_size)
-    device = plain.device
-    ids = ids.to(device)
+    cuda = plain.device.type == "cuda"
+    ids = ids.to(plain.device)
     user = _encode_users(model, plain, hist, mask, batch_size)
     skip = torch.where(mask != 0, hist, torch.zeros_like(hist)) if exclude_history else None
-    if device.type != "cuda":
-        row_user, row_cand, seg = util.recommend_rows(0, G, ids, start)
-        scores = (aug[row_cand] * user[row_user]).sum(dim=1)
-        s, i, c = evaluate.topk_segments_host(scores.numpy(), seg.numpy(), k, ids=row_cand.numpy(), skip=skip.numpy() if skip is not None and G else None)
-        return torch.from_numpy(i), torch.from_numpy(s), torch.from_numpy(c)
-    if start is None:
+    if cuda and start is None:
         s, i, c = evaluate.dot_topk(user, aug, k, pool=ids, skip=skip)
         return i, s, c
-    out_ids = torch.full((G, k), -1, dtype=torch.int64, device=device)
-    out_scores = torch.full((G, k), float("-inf"), dtype=torch.float32, device=device)
-    out_count = torch.zeros((G,), dtype=torch.int32, device=device)
-    for g0, g1 in util.recommend_user_chunks(G, int(ids.shape[0]), start, util.RECOMMEND_MAX_ROWS):
-        row_user, row_cand, seg = util.recommend_rows(g0, g1, ids, start)
-        if int(row_user.shape[0]) == 0:
-            continue
-        scores = row_logits(aug.index_select(0, row_cand), user.index_select(0, row_user))
-        s, i, c = evaluate.topk_segments(scores, seg, k, ids=row_cand, skip=None if skip is None else skip[g0:g1])
-        out_scores[g0:g1], out_ids[g0:g1], out_count[g0:g1] = s, i, c
-    return out_ids, out_scores, out_count
+
+    def score(g0, g1, row_user, row_cand):
+        c, u = aug.index_select(0, row_cand), user.index_select(0, row_user)
+        return row_logits(c, u) if cuda else (c * u).sum(dim=1)
+    # on the CPU one chunk holds all pairs
+    return util.recommend_select(G, k, ids, start, skip, util.RECOMMEND_MAX_ROWS if cuda else max(1, G * int(ids.shape[0])), score)
 
 
 def candidates_csr(news_ids, count):

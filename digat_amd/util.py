@@ -789,30 +789,38 @@ def _ndim(x) -> int:
     return x.dim() if torch.is_tensor(x) else np.ndim(x)
 
 
+def recommend_user_arrays(users, I: int, H: int, news_num: int, dev, names=("history", "user_category_indices")):
+    """``users`` of a ``recommend`` in either form, checked and moved to ``dev``: ``(idx [G] int64, None, None)`` for a 1-D integer
+    array of impression indices in [0, I), or ``(None, a [G,H] int64, b [G,H])`` for a pair of arrays called ``names`` that
+    describes people who are no rows of the corpus (``a``: history ids in [0, news_num))."""
+    as_t = lambda x: torch.as_tensor(np.asarray(x) if not torch.is_tensor(x) else x)
+    if isinstance(users, (tuple, list)) and len(users) == 2 and _ndim(users[0]) == 2:
+        a, b = as_t(users[0]).to(torch.int64), as_t(users[1])
+        if tuple(b.shape) != tuple(a.shape):
+            raise ValueError(f"users must be ({names[0]} [G,H], {names[1]} [G,H]), got {tuple(a.shape)} and {tuple(b.shape)}")
+        if int(a.shape[1]) != H:
+            raise ValueError(f"users' history length {int(a.shape[1])} is not the corpus's max_history_num {H}")
+        if a.numel() and (int(a.min()) < 0 or int(a.max()) >= news_num):
+            raise ValueError(f"history ids must lie in [0, {news_num})")
+        return None, a.to(dev).contiguous(), b.to(dev).contiguous()
+    idx = as_t(users)
+    if idx.dim() != 1 or idx.dtype in (torch.float16, torch.float32, torch.float64, torch.bool):
+        raise ValueError(f"users must be a 1-D integer array of impression indices or a ({names[0]}, {names[1]}) pair")
+    idx = idx.to(torch.int64)
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= I):
+        raise ValueError(f"impression indices must lie in [0, {I})")
+    return idx.to(dev), None, None
+
+
 def recommend_users(dc: DeviceCorpus, users):
     """The user side of ``recommend``: ``(history [G,H], user_category_indices [G,H], user_graph, user_category_mask)`` on the
     corpus's device.  ``users``: a 1-D integer array of impression indices of ``dc`` (the corpus's graph and mask tables are
     gathered when it has them), or a pair ``(history [G,H], user_category_indices [G,H])`` of users that are no rows of the
     corpus — padded as the corpus is (history id 0, category index C) — whose graphs are then derived on the device."""
-    dev = dc.history.device
-    H = int(dc.history.shape[1])
-    if isinstance(users, (tuple, list)) and len(users) == 2 and _ndim(users[0]) == 2:
-        hist, cat = (torch.as_tensor(np.asarray(u) if not torch.is_tensor(u) else u).to(torch.int64) for u in users)
-        if hist.dim() != 2 or tuple(cat.shape) != tuple(hist.shape):
-            raise ValueError(f"users must be (history [G,H], user_category_indices [G,H]), got {tuple(hist.shape)} and {tuple(cat.shape)}")
-        if int(hist.shape[1]) != H:
-            raise ValueError(f"users' history length {int(hist.shape[1])} is not the corpus's max_history_num {H}")
-        if hist.numel() and (int(hist.min()) < 0 or int(hist.max()) >= int(dc.news_embedding.shape[0])):
-            raise ValueError("history ids must lie in [0, news_num)")
-        return hist.to(dev).contiguous(), cat.to(dev).contiguous(), None, None
-    idx = torch.as_tensor(np.asarray(users) if not torch.is_tensor(users) else users)
-    if idx.dim() != 1 or idx.dtype in (torch.float16, torch.float32, torch.float64, torch.bool):
-        raise ValueError("users must be a 1-D integer array of impression indices or a (history, user_category_indices) pair")
-    idx = idx.to(torch.int64)
-    I = int(dc.history.shape[0])
-    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= I):
-        raise ValueError(f"impression indices must lie in [0, {I})")
-    idx = idx.to(dev)
+    idx, hist, cat = recommend_user_arrays(users, int(dc.history.shape[0]), int(dc.history.shape[1]), int(dc.news_embedding.shape[0]),
+                                           dc.history.device)
+    if idx is None:
+        return hist, cat.to(torch.int64), None, None
     graph = dc.user_graph.index_select(0, idx) if dc.user_graph is not None else None
     mask = dc.user_category_mask.index_select(0, idx) if dc.user_graph is not None else None
     return dc.history.index_select(0, idx), dc.user_category_indices.index_select(0, idx), graph, mask
@@ -871,6 +879,63 @@ def recommend_user_chunks(users: int, ids_len: int, start: Optional[np.ndarray],
     return out
 
 
+def recommend_limits(k, skip_len: int) -> int:
+    """``k`` as an int, once it and the length of the skip rows (histories) are what ``evaluate.topk_segments`` takes."""
+    if not 1 <= int(k) <= evaluate.TOPK_MAX_K:
+        raise ValueError(f"k must be in [1, {evaluate.TOPK_MAX_K}], got {k}")
+    if skip_len > evaluate.TOPK_MAX_SKIP:
+        raise ValueError(f"exclude_history takes histories of at most {evaluate.TOPK_MAX_SKIP} news, this corpus has {skip_len}")
+    return int(k)
+
+
+def recommend_select(G: int, k: int, ids: torch.Tensor, start: Optional[np.ndarray], skip: Optional[torch.Tensor], max_rows: int,
+                     score: Callable, prepare: Optional[Callable] = None):
+    """Select k per user over chunked (user, candidate) pairs: ``(news_ids [G,k] int64, scores [G,k] float32, count [G] int32)`` on
+    the device of ``ids``, rows without pairs and slots at or beyond ``count`` holding id -1 and score -inf.  ``ids`` / ``start``
+    as ``recommend_candidates`` returns them; ``skip`` [G, L] holds ids user g must not get, or None.  Users are taken in chunks
+    of at most ``max_rows`` pairs (``recommend_user_chunks``); ``score(g0, g1, row_user, row_cand)`` returns the scores [r] of a
+    chunk's pairs (``recommend_rows``), which ``evaluate.topk_segments`` selects from — ``topk_segments_host`` for host scores.
+    ``prepare()`` runs once, behind the argument checks and before the first ``score``."""
+    k = recommend_limits(k, 0 if skip is None else int(skip.shape[1]))
+    chunks = recommend_user_chunks(G, int(ids.shape[0]), start, int(max_rows))
+    if prepare is not None:
+        prepare()
+    out_ids = torch.full((G, k), -1, dtype=torch.int64, device=ids.device)
+    out_scores = torch.full((G, k), float("-inf"), dtype=torch.float32, device=ids.device)
+    out_count = torch.zeros((G,), dtype=torch.int32, device=ids.device)
+    for g0, g1 in chunks:
+        row_user, row_cand, seg = recommend_rows(g0, g1, ids, start)
+        if int(row_user.shape[0]) == 0:
+            continue
+        scores, sk = score(g0, g1, row_user, row_cand), None if skip is None else skip[g0:g1]
+        if scores.is_cuda:
+            s, i, c = evaluate.topk_segments(scores, seg, k, ids=row_cand, skip=sk)
+        else:
+            s, i, c = map(torch.from_numpy, evaluate.topk_segments_host(scores.numpy(), seg.numpy(), k, ids=row_cand.numpy(),
+                                                                        skip=None if sk is None else sk.numpy()))
+        out_scores[g0:g1], out_ids[g0:g1], out_count[g0:g1] = s, i, c
+    return out_ids, out_scores, out_count
+
+
+def refresh_news_side(model, dc: DeviceCorpus, batch_size: int) -> None:
+    """What a run over ``dc`` needs of its news side, brought up to the model's weights: the news tables of the corpus it shares
+    them with (``adopt_news_side``), the text news table, this corpus's sparse / dense hint, the per-news caches."""
+    enc, ne = model.graph_encoder, getattr(model, "news_encoder", None)
+    if hasattr(enc, "pass_rows"):
+        enc.pass_rows = _pass_rows(batch_size)      # what score_rows will pass per call; weights_key names it: set before the keys are compared
+    adopt_news_side(model, dc)
+    if dc.title_text is not None and ne is not None and not hasattr(ne, "table"):
+        # a text news encoder (MSA): util.py:24-33 re-encodes every news at the start of each dev / test run — here whenever the
+        # encoder's weights have moved on since news_embedding was computed (training epochs), not otherwise
+        nk = tuple((p.data_ptr(), p._version) for p in ne.parameters())
+        if dc.news_key != nk:
+            dc.news_embedding = cache_news_representations(ne, dc.title_text, dc.title_mask, max(batch_size, 4096))
+            dc.news_key = nk               # a new tensor: weights_key below changes and the per-news caches follow
+    apply_corpus_hint(enc, dc)
+    if dc.c_n0 is None or dc.weights_key != weights_key(enc, dc):
+        prepare_news_side(enc, dc, batch_size)      # first use, or the weights moved on since (an optimizer step, load_state_dict)
+
+
 def recommend(model, dc: DeviceCorpus, users, candidates, k: int, exclude_history: bool = True, batch_size: int = 1024,
               max_rows: int = RECOMMEND_MAX_ROWS):
     """For every user, which k news of its candidates, in order: ``(news_ids [G,k] int64, scores [G,k] float32, count [G] int32)``
@@ -883,43 +948,19 @@ def recommend(model, dc: DeviceCorpus, users, candidates, k: int, exclude_histor
     id 0, so the PAD news is then never returned either; False takes the candidates at their word.
 
     Scoring is ``score_rows`` on a view of ``dc`` (same per-news tables and caches; the users' tensors and the user-major pairs in
-    place of the corpus's impressions and rows), so the grouped route and the fp16x3 range check apply; selection is
-    ``evaluate.topk_segments``.  Users are processed in chunks of at most ``max_rows`` pairs (``RECOMMEND_MAX_ROWS``: 20 bytes per
-    pair, 80 MiB).  Like ``compute_scores`` this puts the model in eval mode and refreshes the per-news tables when the weights
-    have moved on.  The chunking may move fp32 bits of a score (pass composition), as the launch-set size does."""
-    if not 1 <= int(k) <= evaluate.TOPK_MAX_K:
-        raise ValueError(f"k must be in [1, {evaluate.TOPK_MAX_K}], got {k}")
-    k = int(k)
+    place of the corpus's impressions and rows), so the grouped route and the fp16x3 range check apply; selection and the chunks of
+    at most ``max_rows`` pairs (``RECOMMEND_MAX_ROWS``: 20 bytes per pair, 80 MiB) are ``recommend_select``'s.  Like
+    ``compute_scores`` this puts the model in eval mode and refreshes the per-news tables when the weights have moved on
+    (``refresh_news_side``).  The chunking may move fp32 bits of a score (pass composition), as the launch-set size does."""
     hist, cat, graph, mask = recommend_users(dc, users)
-    G, H = int(hist.shape[0]), int(hist.shape[1])
-    if exclude_history and H > evaluate.TOPK_MAX_SKIP:
-        raise ValueError(f"exclude_history takes histories of at most {evaluate.TOPK_MAX_SKIP} news, this corpus has {H}")
-    dev = dc.news_embedding.device
-    ids, start = recommend_candidates(candidates, G, int(dc.news_embedding.shape[0]))
-    ids = ids.to(dev)
-    chunks = recommend_user_chunks(G, int(ids.shape[0]), start, int(max_rows))
-    if hasattr(model, "eval"):
-        model.eval()
-    enc = model.graph_encoder
-    ne = getattr(model, "news_encoder", None)
-    if hasattr(enc, "pass_rows"):
-        enc.pass_rows = _pass_rows(batch_size)
-    adopt_news_side(model, dc)
-    if dc.title_text is not None and ne is not None and not hasattr(ne, "table"):
-        nk = tuple((p.data_ptr(), p._version) for p in ne.parameters())
-        if dc.news_key != nk:
-            dc.news_embedding = cache_news_representations(ne, dc.title_text, dc.title_mask, max(batch_size, 4096))
-            dc.news_key = nk
-    apply_corpus_hint(enc, dc)
-    if dc.c_n0 is None or dc.weights_key != weights_key(enc, dc):
-        prepare_news_side(enc, dc, batch_size)
-    out_ids = torch.full((G, k), -1, dtype=torch.int64, device=dev)
-    out_scores = torch.full((G, k), float("-inf"), dtype=torch.float32, device=dev)
-    out_count = torch.zeros((G,), dtype=torch.int32, device=dev)
-    for g0, g1 in chunks:
-        row_user, row_cand, seg = recommend_rows(g0, g1, ids, start)
-        if int(row_user.shape[0]) == 0:
-            continue
+    ids, start = recommend_candidates(candidates, int(hist.shape[0]), int(dc.news_embedding.shape[0]))
+
+    def prepare():
+        if hasattr(model, "eval"):
+            model.eval()
+        refresh_news_side(model, dc, batch_size)
+
+    def score(g0, g1, row_user, row_cand):
         view = dataclasses.replace(dc, history=hist, user_category_indices=cat, user_graph=graph, user_category_mask=mask,
                                    row_impression=row_user, row_candidate=row_cand)
         scores = score_rows(model, view, 0, view.rows, batch_size)
@@ -927,9 +968,9 @@ def recommend(model, dc: DeviceCorpus, users, candidates, k: int, exclude_histor
             for f in ("SA_news_representations", "c_n0", "news_hpq0", "user_hpq0", "topic_hpq0", "ctxq0", "news_ctx_layers",
                       "weights_key", "xattn_hint", "range_overflow_at_prepare"):
                 setattr(dc, f, getattr(view, f))
-        s, i, c = evaluate.topk_segments(scores, seg, k, ids=row_cand, skip=hist[g0:g1] if exclude_history else None)
-        out_scores[g0:g1], out_ids[g0:g1], out_count[g0:g1] = s, i, c
-    return out_ids, out_scores, out_count
+        return scores
+    return recommend_select(int(hist.shape[0]), k, ids.to(dc.news_embedding.device), start, hist if exclude_history else None,
+                            max_rows, score, prepare)
 
 
 def all_gather_scores(local: torch.Tensor, counts: List[int], group=None) -> torch.Tensor:
@@ -982,27 +1023,10 @@ def compute_scores(model, dc: DeviceCorpus, batch_size: int, labels: Optional[np
     if hasattr(model, "eval"):
         model.eval()
     freeze_host_heap()
-    ne = getattr(model, "news_encoder", None)
-    if score_fn is None and dc.news_source is not None:
-        if hasattr(model.graph_encoder, "pass_rows"):
-            model.graph_encoder.pass_rows = _pass_rows(batch_size)      # weights_key names it: set before the keys are compared
-        adopt_news_side(model, dc)
-    if score_fn is None and dc.title_text is not None and ne is not None and not hasattr(ne, "table"):
-        # a text news encoder (MSA): util.py:24-33 re-encodes every news at the start of each dev / test run — here whenever the
-        # encoder's weights have moved on since news_embedding was computed (training epochs), not otherwise
-        nk = tuple((p.data_ptr(), p._version) for p in ne.parameters())
-        if dc.news_key != nk:
-            dc.news_embedding = cache_news_representations(ne, dc.title_text, dc.title_mask, max(batch_size, 4096))
-            dc.news_key = nk               # a new tensor: weights_key below changes and the per-news caches follow
-    if score_fn is None and hasattr(model.graph_encoder, "range_overflowed"):
-        model.graph_encoder.range_overflowed()                      # clear what earlier calls may have left in the flag
-    if score_fn is None and hasattr(model.graph_encoder, "pass_rows"):
-        model.graph_encoder.pass_rows = _pass_rows(batch_size)      # what score_rows will pass per call: names the [B,d] kernel
     if score_fn is None:
-        apply_corpus_hint(model.graph_encoder, dc)
-    if score_fn is None and (dc.c_n0 is None or dc.weights_key != weights_key(model.graph_encoder, dc)):
-        prepare_news_side(model.graph_encoder, dc, batch_size)      # first use, or the weights moved on since (an optimizer
-                                                                    # step, load_state_dict): the per-news caches are stale
+        if hasattr(model.graph_encoder, "range_overflowed"):
+            model.graph_encoder.range_overflowed()                  # clear what earlier calls may have left in the flag
+        refresh_news_side(model, dc, batch_size)
     row_imp = dc.row_impression.cpu().numpy()
     start, end = shard_rows(row_imp, world_size, rank)
     enc = getattr(model, "graph_encoder", None)
@@ -1020,12 +1044,5 @@ def compute_scores(model, dc: DeviceCorpus, batch_size: int, labels: Optional[np
     scores_np = scores.detach().cpu().numpy()
     if rank != 0:
         return scores_np, None
-    if scores.is_cuda:          # ranking + metrics on the device (digat_rank_metrics); one wave per impression
-        ranks, metrics = evaluate.device_ranks_and_metrics(scores, row_imp, labels)
-    else:                       # host tensors only occur in the CPU harness tests (score_fn)
-        ranks = evaluate.impression_ranks(scores_np, row_imp)
-        metrics = evaluate.scoring(labels, ranks, row_imp) if labels is not None else None
-    if result_file is not None:
-        with open(result_file, "wb") as f:
-            f.write(evaluate.rank_file_bytes(ranks, row_imp))
-    return scores_np, metrics
+    # ranking + metrics on the device (digat_rank_metrics); host tensors only occur in the CPU harness tests (score_fn)
+    return scores_np, evaluate.ranks_metrics_file(scores, row_imp, labels, result_file)[1]

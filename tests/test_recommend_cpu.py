@@ -274,6 +274,38 @@ def test_user_chunks_respect_max_rows():
     assert util.RECOMMEND_MAX_ROWS * 20 == 80 << 20                                             # the bytes the docstring states
 
 
+@pytest.mark.parametrize("with_skip", [False, True])
+def test_select_driver_is_chunk_invariant_and_matches_the_host_selection(with_skip):
+    """``util.recommend_select`` over host scores (routed to ``topk_segments_host``): whatever ``max_rows`` cuts the users into, the
+    ids, score bits, counts and fills are those of one selection over all pairs at once."""
+    from digat_amd import evaluate, util
+    lens = [0, 1, 5, 0, 12, 3, 9]
+    G, k = len(lens), 4
+    rng = np.random.default_rng(5)
+    ids = torch.from_numpy(rng.integers(0, 40, size=sum(lens)))
+    start = np.r_[0, np.cumsum(lens)].astype(np.int64)
+    skip = torch.from_numpy(rng.integers(0, 40, size=(G, 6))) if with_skip else None
+    seen = []
+
+    def score(g0, g1, row_user, row_cand):                      # a fixed function of (user, candidate), three values: many ties
+        seen.append((g0, g1, int(row_user.shape[0])))
+        return ((row_user * 7 + row_cand) % 3).to(torch.float32) * 0.5 - 0.5
+    row_user, row_cand, seg = util.recommend_rows(0, G, ids, start)
+    want_s, want_i, want_c = evaluate.topk_segments_host(score(0, G, row_user, row_cand).numpy(), seg.numpy(), k, ids=row_cand.numpy(),
+                                                         skip=None if skip is None else skip.numpy())
+    assert want_c.tolist()[0] == 0 and want_c.tolist()[3] == 0 and (want_c < k).any() and (want_c == k).any()
+    if with_skip:
+        assert want_c.sum() < evaluate.topk_segments_host(np.zeros(sum(lens), dtype=np.float32), start, k)[2].sum()   # the rows bite
+    for max_rows in (1, 4, 1000):
+        del seen[:]
+        got_i, got_s, got_c = util.recommend_select(G, k, ids, start, skip, max_rows, score)
+        assert got_i.dtype == torch.int64 and got_s.dtype == torch.float32 and got_c.dtype == torch.int32
+        assert np.array_equal(got_i.numpy(), want_i) and np.array_equal(got_c.numpy(), want_c), max_rows
+        assert np.array_equal(got_s.numpy().view(np.uint32), want_s.view(np.uint32)), max_rows          # fills included
+        assert all(r > 0 for _, _, r in seen), "an empty chunk was scored"
+        assert all(r <= max_rows or g1 - g0 == 1 for g0, g1, r in seen) and (len(seen) == 1) == (max_rows == 1000)
+
+
 def test_config_parses_the_recommend_mode():
     from digat_amd.config import Config
     c = Config(["--mode", "recommend", "--recommend_k", "5"])
