@@ -6,6 +6,7 @@ real MIND cannot be downloaded, so the default corpus is synthetic (``--syntheti
 ``--data_root`` names MIND files on disk instead (``mind.load``: ``--artefact_root``, ``--similarity_file``, ``--semantic_embedding_root``,
 ``--word_embedding_file``, ``--data_cache``, ``--word_threshold``, ``--max_title_length``), and only then are those flags attributes
 (``--model_dir`` also when it is given: the Trainer saves there on either corpus);
+``--recommend_diversity`` (with ``--recommend_shortlist``, ``--recommend_max_per_category``) likewise: attributes only when it is given;
 ``--local_rank`` also accepts torch >= 2.0's ``--local-rank`` spelling and the ``LOCAL_RANK`` variable.
 """
 from __future__ import annotations
@@ -32,6 +33,12 @@ class Config:
         p.add_argument('--test_output_file', type=str, default='', help='Test output file (the rank file of --mode test)')
         p.add_argument('--recommend_k', type=int, default=10, help='news recommended per impression (--mode recommend; 1..128)')
         p.add_argument('--recommend_output', type=str, default='', help='Recommendation file of --mode recommend: "<impression id> [id1,id2,...]" per line')
+        p.add_argument('--recommend_diversity', type=float, default=None,
+                       help='--mode recommend: pick the k by maximal-marginal relevance from a shortlist, lam = 1 - this value (0..1; default: off)')
+        p.add_argument('--recommend_shortlist', type=int, default=0,
+                       help='the shortlist --recommend_diversity picks from (recommend_k..128; 0: min(128, 4 * recommend_k))')
+        p.add_argument('--recommend_max_per_category', type=int, default=0,
+                       help='with --recommend_diversity: at most this many news of one category per list (0: no cap; needs a corpus with categories)')
         p.add_argument('--seed', type=int, default=0)
         p.add_argument('--local_rank', '--local-rank', type=int, default=int(os.environ.get('LOCAL_RANK', -1)))
         p.add_argument('--dataset', default='MIND-small', choices=['MIND-small', 'MIND-large'])
@@ -82,10 +89,18 @@ class Config:
         p.add_argument('--max_title_length', type=int, default=32)
         p.add_argument('--model_dir', type=str, default='', help='directory the trained models are saved in')
         a = p.parse_args(argv)
+        if a.recommend_diversity is None and (a.recommend_shortlist or a.recommend_max_per_category):
+            p.error('--recommend_shortlist and --recommend_max_per_category need --recommend_diversity (0 for the cap alone)')
+        if a.recommend_diversity is not None and not 0.0 <= a.recommend_diversity <= 1.0:
+            p.error('--recommend_diversity must lie in [0, 1]')
+        if a.recommend_shortlist < 0 or a.recommend_max_per_category < 0:
+            p.error('--recommend_shortlist and --recommend_max_per_category must not be negative')
         mind_flags = ('data_root', 'artefact_root', 'similarity_file', 'semantic_embedding_root', 'word_embedding_file', 'data_cache', 'word_threshold',
                       'max_title_length', 'model_dir')
+        diversity_flags = ('recommend_diversity', 'recommend_shortlist', 'recommend_max_per_category')    # attributes only when asked for
         self.attribute_dict = {k: v for k, v in vars(a).items()
-                               if a.data_root or k not in mind_flags or (k == 'model_dir' and a.model_dir)}
+                               if (a.data_root or k not in mind_flags or (k == 'model_dir' and a.model_dir))
+                               and (a.recommend_diversity is not None or k not in diversity_flags)}
         for k, v in self.attribute_dict.items():
             setattr(self, k, v)
         if self.dataset == 'MIND-small':

@@ -310,6 +310,137 @@ def dot_scores(users, news, pool=None):
     return out
 
 
+MMR_MAX_LIST = TOPK_MAX_K      # include/digat_hip.h: digat_mmr_select takes lists of at most this many entries
+
+
+def mmr_weights(lam):
+    """``(lam, mu)`` as float32 — what ``digat_mmr_select`` is handed: ``mu = float32(1) - float32(lam)``, computed once."""
+    if not 0.0 <= float(lam) <= 1.0:                                # a NaN fails both comparisons
+        raise ValueError(f"lam must lie in [0, 1], got {lam}")
+    lam32 = np.float32(lam)
+    return lam32, np.float32(1) - lam32
+
+
+def _check_mmr_args(ids_shape, scores_shape, count_shape, k, category_shape, max_per_category):
+    if len(ids_shape) != 2 or tuple(scores_shape) != tuple(ids_shape) or not 1 <= ids_shape[1] <= MMR_MAX_LIST:
+        raise ValueError(f"ids and scores must both be [G, M] with 1 <= M <= {MMR_MAX_LIST}, got {tuple(ids_shape)} and {tuple(scores_shape)}")
+    if count_shape is not None and tuple(count_shape) != (ids_shape[0],):
+        raise ValueError(f"count must have one entry per list ({ids_shape[0]}), got shape {tuple(count_shape)}")
+    if not 1 <= int(k) <= TOPK_MAX_K:
+        raise ValueError(f"k must be in [1, {TOPK_MAX_K}], got {k}")
+    if int(max_per_category) < 0:
+        raise ValueError(f"max_per_category must be >= 0 (0: no cap), got {max_per_category}")
+    if int(max_per_category) > 0 and category_shape is None:
+        raise ValueError("max_per_category needs category")
+    if category_shape is not None and len(category_shape) != 1:
+        raise ValueError(f"category must be [N], got shape {tuple(category_shape)}")
+
+
+def mmr_select_host(ids, scores, count, sim, k: int, lam, category=None, max_per_category: int = 0, news_num=None):
+    """The contract of ``digat_mmr_select`` in numpy — the yardstick of the kernel — on given similarities ``sim`` [G, M, M]
+    float32 (``sim[g, i, j]``: list positions i and j of user g).  ``ids`` / ``scores`` [G, M], ``count`` [G] or None (M): position p
+    is an element when ``p < count[g]`` and ``0 <= id < N`` (``news_num``; None: ``len(category)``, or no upper bound).  Greedy,
+    k steps: ``value = float32(lam) * s - float32(mu) * pen`` with every operation rounded, the winner is the eligible element with
+    the largest ``topk_keys(value)``, ties to the lowest position; then ``pen = np.fmax(pen, sim[winner])``.  Eligible: not selected,
+    and with ``max_per_category`` q > 0 fewer than q selected elements of its ``category[id]``.  Returns ``(scores [G,k] float32 —
+    the INPUT score bits —, ids [G,k] int64, count [G] int32)``; slots at or beyond ``count`` hold ``-inf`` / ``-1``."""
+    idv = np.asarray(ids, dtype=np.int64)
+    sc = np.ascontiguousarray(scores, dtype=np.float32)
+    cat = None if category is None else np.asarray(category, dtype=np.int64)
+    _check_mmr_args(idv.shape, sc.shape, None if count is None else np.shape(count), k, None if cat is None else cat.shape,
+                    max_per_category)
+    G, M = idv.shape
+    S = np.asarray(sim, dtype=np.float32)
+    if S.shape != (G, M, M):
+        raise ValueError(f"sim must be [G, M, M] = {(G, M, M)}, got {S.shape}")
+    lam32, mu32 = mmr_weights(lam)
+    k, q = int(k), int(max_per_category)
+    N = news_num if news_num is not None else (len(cat) if cat is not None else None)
+    cnt = np.full(G, M, dtype=np.int64) if count is None else np.clip(np.asarray(count, dtype=np.int64), 0, M)
+    out_s = np.full((G, k), -np.inf, dtype=np.float32)
+    out_i = np.full((G, k), -1, dtype=np.int64)
+    out_c = np.zeros(G, dtype=np.int32)
+    pos = np.arange(M)
+    for g in range(G):
+        elem = (pos < cnt[g]) & (idv[g] >= 0)
+        if N is not None:
+            elem &= idv[g] < N
+        cg = cat[np.where(elem, idv[g], 0)] if q > 0 and elem.any() else np.zeros(M, dtype=np.int64)
+        pen = np.zeros(M, dtype=np.float32)
+        chosen = np.zeros(M, dtype=bool)
+        same = np.zeros(M, dtype=np.int64)
+        for t in range(k):
+            ok = elem & ~chosen
+            if q > 0:
+                ok &= same < q
+            if not ok.any():
+                break
+            with np.errstate(invalid="ignore", over="ignore"):
+                value = (lam32 * sc[g]).astype(np.float32) - (mu32 * pen).astype(np.float32)
+            keys = np.where(ok, topk_keys(value).astype(np.int64), -1)
+            j = int(np.argmax(keys))                                # the first (lowest position) of the largest key
+            chosen[j] = True
+            out_s[g, t], out_i[g, t] = sc[g, j], idv[g, j]
+            out_c[g] = t + 1
+            pen = np.fmax(pen, S[g, j])
+            if q > 0:
+                same += elem & (cg == cg[j])
+    return out_s, out_i, out_c
+
+
+def mmr_select(ids, scores, count, vectors, k: int, lam, category=None, max_per_category: int = 0):
+    """Diversified top-k on the GPU (``digat_mmr_select``): per user, k greedy maximal-marginal-relevance picks from a short list.
+
+    ``ids`` [G, M <= 128] int64, ``scores`` [G, M] float32 and ``count`` [G] int32 (None: M) are device tensors — what
+    ``topk_segments``, ``dot_topk`` and both ``recommend``s return; ``vectors`` [N, d] float32 holds the rows the similarity is the
+    inner product of (pass unit rows: ``util.unit_rows``); ``lam`` in [0, 1] weighs the score against the largest similarity to
+    what is already picked (1: the plain order by score); ``category`` [N] and ``max_per_category`` q >= 1 cap the picks per
+    category (0: no cap).  The contract is ``mmr_select_host``'s, exactly.  Returns ``(scores [G,k] float32, ids [G,k] int64, count
+    [G] int32)`` on the device — the picked entries' input scores; slots at or beyond ``count`` hold ``-inf`` / ``-1``.
+    Stream-ordered: one launch, nothing is read back."""
+    import torch
+    from . import _lib
+    given = [t for t in (ids, scores, count, vectors, category) if t is not None]
+    dev = _lib.require_device(*given)
+    _check_mmr_args(tuple(ids.shape), tuple(scores.shape), None if count is None else tuple(count.shape), k,
+                    None if category is None else tuple(category.shape), max_per_category)
+    if vectors.dim() != 2 or vectors.shape[1] < 1:
+        raise ValueError(f"vectors must be [N, d] with d >= 1, got {tuple(vectors.shape)}")
+    if category is not None and int(category.shape[0]) != int(vectors.shape[0]):
+        raise ValueError(f"category must have one entry per row of vectors ({int(vectors.shape[0])}), got {int(category.shape[0])}")
+    lam32, mu32 = mmr_weights(lam)
+    idt = ids.to(torch.int64).contiguous()
+    sc = _lib.f32(scores.detach())
+    ct = None if count is None else count.to(torch.int32).contiguous()
+    v = _lib.f32(vectors.detach())
+    q = int(max_per_category)
+    cat = None if category is None or q == 0 else category.to(torch.int32).contiguous()
+    G, M, k = int(idt.shape[0]), int(idt.shape[1]), int(k)
+    out_s = torch.empty((G, k), dtype=torch.float32, device=dev)
+    out_i = torch.empty((G, k), dtype=torch.int64, device=dev)
+    out_c = torch.empty((G,), dtype=torch.int32, device=dev)
+    if G == 0:
+        return out_s, out_i, out_c
+    L = _lib.lib()
+    need = int(L.digat_mmr_select_workspace_bytes(G, M, k))
+    ws = _lib.workspace(need, dev, "mmr")
+    _lib.check(L.digat_mmr_select(idt.data_ptr(), sc.data_ptr(), _lib.ptr(ct), G, M, v.data_ptr(), int(v.shape[0]), int(v.shape[1]),
+                                  _lib.ptr(cat), q, float(lam32), float(mu32), k, out_i.data_ptr(), out_s.data_ptr(), out_c.data_ptr(),
+                                  ws.data_ptr(), need, _lib.stream_ptr()),
+               "digat_mmr_select")
+    return out_s, out_i, out_c
+
+
+def mmr_gram_stock(ids, vectors):
+    """``sim`` [G, M, M] of ``mmr_select_host`` on stock PyTorch, for lists and vectors on any device: the Gram of the gathered rows
+    (an id outside [0, N) gathers row 0: no element, its similarities are never used)."""
+    import torch
+    N = int(vectors.shape[0])
+    safe = torch.where((ids >= 0) & (ids < N), ids, torch.zeros_like(ids))
+    rows = vectors[safe] if N else vectors.new_zeros(tuple(ids.shape) + (int(vectors.shape[1]),))
+    return torch.bmm(rows, rows.transpose(1, 2))
+
+
 class AvgMetric:
     """util.py:100-121: the model-selection average."""
 

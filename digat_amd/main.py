@@ -9,6 +9,8 @@ score the rows and print AUC / MRR / nDCG@5 / nDCG@10 and the inference time (ma
 to ``--test_output_file`` when one is named.  ``recommend`` loads ``--test_model_path`` as ``test`` does and, for every impression of the
 corpus, picks the ``--recommend_k`` best of ALL non-PAD news the impression's user has not read (``util.recommend``); it writes
 ``"<impression id> [id1,id2,...]"`` per line — the rank file's framing — to ``--recommend_output`` when one is named.
+``--recommend_diversity F`` makes those the k maximal-marginal-relevance picks of a shortlist (``--recommend_shortlist``), with
+``--recommend_max_per_category Q`` at most Q of one category — on a corpus that carries the news' categories (MIND does).
 """
 from __future__ import annotations
 
@@ -32,12 +34,28 @@ def load_checkpoint(model, path: str) -> None:
     model.load_state_dict(saved[model.model_name])
 
 
-def recommend_lines(model, dc, k: int, batch_size: int):
+def recommend_category(dc, max_per_category: int):
+    """The per-news category array ``--recommend_max_per_category`` caps by, or None without a cap; a corpus that carries none
+    cannot be capped."""
+    if not max_per_category:
+        return None
+    category = getattr(dc, 'news_category', None)
+    if category is None:
+        raise ValueError('--recommend_max_per_category needs the category of every news, and this corpus carries none '
+                         '(mind.load and synthetic.make_corpus give one: news_category)')
+    return category
+
+
+def recommend_lines(model, dc, k: int, batch_size: int, diversity=None, shortlist: int = 0, max_per_category: int = 0):
     """``"<impression id> [id1,id2,...]"`` (1-based impression ids, best news first) for every impression of ``dc`` against the
-    pool of all non-PAD news, the user's own history excluded."""
+    pool of all non-PAD news, the user's own history excluded; with ``diversity`` the diversified lists of ``util.recommend``."""
     pool = torch.arange(1, dc.news_embedding.shape[0], dtype=torch.int64, device=dc.news_embedding.device)
     users = torch.arange(dc.history.shape[0], dtype=torch.int64)
-    ids, _, count = util.recommend(model, dc, users, pool, k, batch_size=batch_size)
+    if diversity is None:
+        ids, _, count = util.recommend(model, dc, users, pool, k, batch_size=batch_size)
+    else:
+        ids, _, count = util.recommend(model, dc, users, pool, k, batch_size=batch_size, diversity=diversity, shortlist=shortlist or None,
+                                       category=recommend_category(dc, max_per_category), max_per_category=max_per_category)
     ids, count = ids.cpu().numpy(), count.cpu().numpy()
     return ['%d [%s]' % (i + 1, ','.join(str(int(v)) for v in ids[i, :count[i]])) for i in range(len(count))]
 
@@ -119,7 +137,10 @@ def main(argv=None):
         if hasattr(model.graph_encoder, 'projection_mode'):      # the public switch of the scoring run's projection format
             model.graph_encoder.projection_mode = config.inference_projection
         if config.mode == 'recommend':
-            lines = recommend_lines(model, dc, config.recommend_k, config.batch_size * 16)
+            diversity, cap = getattr(config, 'recommend_diversity', None), getattr(config, 'recommend_max_per_category', 0)
+            recommend_category(dc, cap)                                     # refuse before the model runs
+            lines = recommend_lines(model, dc, config.recommend_k, config.batch_size * 16, diversity,
+                                    getattr(config, 'recommend_shortlist', 0), cap)
             if config.recommend_output:
                 with open(config.recommend_output, 'w') as f:
                     f.write('\n'.join(lines))

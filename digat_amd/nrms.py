@@ -509,7 +509,8 @@ def user_vectors(model, dev, users, batch_size=1024):
     return _encode_users(model, plain, hist, mask, batch_size)
 
 
-def recommend(model, dev, users, candidates=None, k=10, exclude_history=True, batch_size=1024):
+def recommend(model, dev, users, candidates=None, k=10, exclude_history=True, batch_size=1024, diversity=None, shortlist=None, category=None,
+              max_per_category=0):
     """For every user, which k news, in order: ``(news_ids [G,k] int64, scores [G,k] float32, count [G] int32)`` on the model's
     device.  Order: score descending, equal scores in candidate order; slots at or beyond ``count[g]`` hold id -1 and score -inf.
 
@@ -518,8 +519,23 @@ def recommend(model, dev, users, candidates=None, k=10, exclude_history=True, ba
     every news but row 0 (<PAD>); a 1-D id array = one pool for all users — ``evaluate.dot_topk``, the fused inner-product + top-k
     kernel, which never writes the [G, P] scores; ``(ids [R], start [G+1])`` = per-user lists (``util.recommend_candidates``) —
     gather, ``row_logits``, ``evaluate.topk_segments``.  ``exclude_history``: a news of the user's history (mask non-zero) is never
-    returned, nor is row 0; False takes the candidates at their word.  On CPU tensors: stock PyTorch and ``topk_segments_host``."""
+    returned, nor is row 0; False takes the candidates at their word.  On CPU tensors: stock PyTorch and ``topk_segments_host``.
+
+    ``diversity`` in [0, 1] (None: off, the call above and nothing else): retrieval runs at ``k' = shortlist or min(128, 4 k)`` and
+    ``util.diversify`` cuts every list to k by greedy maximal-marginal relevance with ``lam = 1 - diversity`` over the plain news
+    cache; ``max_per_category`` q >= 1 lets at most q news of one ``category`` [N] (None: ``dev.news_category``) into a list."""
     from . import evaluate, util
+    if diversity is not None:
+        k, wide, lam = util.diversify_limits(k, diversity, shortlist, max_per_category)
+        if int(max_per_category) > 0 and category is None:
+            category = getattr(dev, "news_category", None)
+        if int(max_per_category) > 0 and category is None:
+            raise ValueError("max_per_category needs category: this corpus carries no news_category")
+        i, s, c = recommend(model, dev, users, candidates, wide, exclude_history, batch_size)
+        plain, _ = news_caches(model, dev.title_text, dev.title_mask, dev.augmented_title_text, dev.augmented_title_mask, 4 * batch_size)
+        return util.diversify(i, s, c, plain, k, lam, category, max_per_category)
+    if shortlist is not None or category is not None or max_per_category:
+        raise ValueError("shortlist, category and max_per_category belong to a diversified call: name diversity (0.0: the cap alone)")
     hist, mask = _histories(dev, users)
     G, N = int(hist.shape[0]), int(dev.title_text.shape[0])
     k = util.recommend_limits(k, int(hist.shape[1]) if exclude_history else 0)

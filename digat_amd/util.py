@@ -61,6 +61,8 @@ class DeviceCorpus:
     range_overflow_at_prepare: bool = False                  # an fp16x3 GEMM left the format's range while the per-news tables were built
     category_num: int = 0                                    # C (without the padding bucket); 0: read off user_category_mask
     news_source: Optional["DeviceCorpus"] = None             # the corpus this one shares its news side with (from_numpy's news_from)
+    news_category: Optional[torch.Tensor] = None             # [news_num] int32 category of every news, where the corpus carries one
+                                                             # (mind.MindSplit does): recommend's max_per_category reads it
 
     def __post_init__(self):
         if not self.category_num and self.user_category_mask is not None:
@@ -116,6 +118,10 @@ class DeviceCorpus:
             adopt_news_side(None, dc, force=True)
         elif getattr(corpus, "news_title_text", None) is not None:
             dc.title_text, dc.title_mask = t(corpus.news_title_text, torch.int32), t(corpus.news_title_mask, torch.bool)
+        if news_from is not None:
+            dc.news_category = news_from.news_category
+        elif getattr(corpus, "news_category", None) is not None:
+            dc.news_category = t(corpus.news_category, torch.int32)
         return dc
 
     @property
@@ -936,8 +942,56 @@ def refresh_news_side(model, dc: DeviceCorpus, batch_size: int) -> None:
         prepare_news_side(enc, dc, batch_size)      # first use, or the weights moved on since (an optimizer step, load_state_dict)
 
 
+def unit_rows(table: torch.Tensor) -> torch.Tensor:
+    """The rows of ``table`` [N, d] scaled to L2 norm 1 (float32, contiguous); a zero row stays zero.  What ``diversify`` measures
+    DIGAT's news by: the inner product of two unit rows is their cosine."""
+    t = table.detach().to(torch.float32)
+    norm = t.norm(dim=1, keepdim=True)
+    return (t / torch.where(norm > 0, norm, torch.ones_like(norm))).contiguous()
+
+
+def diversify_limits(k, diversity, shortlist, max_per_category) -> Tuple[int, int, float]:
+    """``(k, k', lam)`` of a diversified ``recommend``: the plain selection runs at ``k' = shortlist or min(128, 4 k)``, and
+    ``evaluate.mmr_select`` cuts its lists to k with ``lam = 1 - diversity``."""
+    if not 1 <= int(k) <= evaluate.TOPK_MAX_K:
+        raise ValueError(f"k must be in [1, {evaluate.TOPK_MAX_K}], got {k}")
+    if not 0.0 <= float(diversity) <= 1.0:
+        raise ValueError(f"diversity must lie in [0, 1], got {diversity}")
+    if int(max_per_category) < 0:
+        raise ValueError(f"max_per_category must be >= 0 (0: no cap), got {max_per_category}")
+    k = int(k)
+    wide = min(evaluate.MMR_MAX_LIST, 4 * k) if not shortlist else int(shortlist)
+    if not k <= wide <= evaluate.MMR_MAX_LIST:
+        raise ValueError(f"shortlist must lie in [k, {evaluate.MMR_MAX_LIST}] = [{k}, {evaluate.MMR_MAX_LIST}], got {shortlist}")
+    return k, wide, 1.0 - float(diversity)
+
+
+def diversify(ids: torch.Tensor, scores: torch.Tensor, count: torch.Tensor, vectors: torch.Tensor, k: int, lam: float, category=None,
+              max_per_category: int = 0):
+    """The last stage of a diversified ``recommend``: the lists ``(ids [G,M], scores [G,M], count [G])`` of the plain selection cut
+    to k by greedy maximal-marginal relevance over ``vectors`` [N, d] — ``evaluate.mmr_select`` on the device; on CPU tensors the
+    Gram of stock PyTorch (``evaluate.mmr_gram_stock``) and ``evaluate.mmr_select_host``.  Returns ``recommend``'s triple
+    ``(news_ids [G,k], scores [G,k], count [G])``."""
+    cat = None
+    if int(max_per_category) > 0:
+        if category is None:
+            raise ValueError("max_per_category needs category, one entry per news")
+        cat = torch.as_tensor(np.asarray(category) if not torch.is_tensor(category) else category).to(ids.device)
+        if cat.dim() != 1 or int(cat.shape[0]) != int(vectors.shape[0]):
+            raise ValueError(f"category must be [{int(vectors.shape[0])}], one entry per news, got shape {tuple(cat.shape)}")
+    if ids.is_cuda:
+        s, i, c = evaluate.mmr_select(ids, scores, count, vectors, k, lam, category=cat, max_per_category=max_per_category)
+        return i, s, c
+    sim = evaluate.mmr_gram_stock(ids, vectors.detach().to(torch.float32))
+    s, i, c = evaluate.mmr_select_host(ids.numpy(), scores.numpy(), count.numpy(), sim.numpy(), k, lam,
+                                       category=None if cat is None else cat.numpy(), max_per_category=max_per_category,
+                                       news_num=int(vectors.shape[0]))
+    return torch.from_numpy(i), torch.from_numpy(s), torch.from_numpy(c)
+
+
 def recommend(model, dc: DeviceCorpus, users, candidates, k: int, exclude_history: bool = True, batch_size: int = 1024,
-              max_rows: int = RECOMMEND_MAX_ROWS):
+              max_rows: int = RECOMMEND_MAX_ROWS, diversity: Optional[float] = None, shortlist: Optional[int] = None, category=None,
+              max_per_category: int = 0):
     """For every user, which k news of its candidates, in order: ``(news_ids [G,k] int64, scores [G,k] float32, count [G] int32)``
     on the device.  Order: score descending, equal scores in candidate order (the rank file's order); ``count[g]`` is the number of
     valid slots of row g, the slots behind it hold id -1 and score -inf.
@@ -951,7 +1005,23 @@ def recommend(model, dc: DeviceCorpus, users, candidates, k: int, exclude_histor
     place of the corpus's impressions and rows), so the grouped route and the fp16x3 range check apply; selection and the chunks of
     at most ``max_rows`` pairs (``RECOMMEND_MAX_ROWS``: 20 bytes per pair, 80 MiB) are ``recommend_select``'s.  Like
     ``compute_scores`` this puts the model in eval mode and refreshes the per-news tables when the weights have moved on
-    (``refresh_news_side``).  The chunking may move fp32 bits of a score (pass composition), as the launch-set size does."""
+    (``refresh_news_side``).  The chunking may move fp32 bits of a score (pass composition), as the launch-set size does.
+
+    ``diversity`` in [0, 1] (None: off, the call above and nothing else): the selection above runs at ``k' = shortlist or
+    min(128, 4 k)`` and ``diversify`` cuts every list to k by greedy maximal-marginal relevance with ``lam = 1 - diversity`` over
+    ``unit_rows(dc.news_embedding)``: a pick's score is weighed against its largest cosine to what the user already got.
+    ``max_per_category`` q >= 1 lets at most q news of one ``category`` [news_num] (None: ``dc.news_category``) into a list.  The
+    scores returned are still the model's."""
+    if diversity is not None:
+        k, wide, lam = diversify_limits(k, diversity, shortlist, max_per_category)
+        if int(max_per_category) > 0 and category is None:
+            category = dc.news_category
+        if int(max_per_category) > 0 and category is None:
+            raise ValueError("max_per_category needs category: this corpus carries no news_category")
+        i, s, c = recommend(model, dc, users, candidates, wide, exclude_history, batch_size, max_rows)
+        return diversify(i, s, c, unit_rows(dc.news_embedding), k, lam, category, max_per_category)
+    if shortlist is not None or category is not None or max_per_category:
+        raise ValueError("shortlist, category and max_per_category belong to a diversified call: name diversity (0.0: the cap alone)")
     hist, cat, graph, mask = recommend_users(dc, users)
     ids, start = recommend_candidates(candidates, int(hist.shape[0]), int(dc.news_embedding.shape[0]))
 

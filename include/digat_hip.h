@@ -609,6 +609,30 @@ int digat_dot_topk(const float* users, const float* news, const int64_t* pool, i
 int digat_dot_scores(const float* users, const float* news, const int64_t* pool, int64_t G, int64_t N, int64_t P, int d, float* out,
                      void* stream);
 
+/* ---- diversified top-k: greedy maximal-marginal-relevance selection over a short list (digat_amd.evaluate.mmr_select) ---------
+ * Per user g a list: ids [G, M] int64, scores [G, M] f32, count [G] int32 (the entries in use, held inside [0, M]; NULL: M) — the
+ * triple digat_topk_segments and digat_dot_topk write.  vectors [N, d] f32, rows taken as they are (callers pass unit rows).
+ * Position p of list g is an ELEMENT when p < count[g] and 0 <= ids[g][p] < N; anything else is no element and no read leaves the
+ * arrays.  Repeated ids are distinct elements.  sim(i, j) = the fp32 fmaf chain over c = 0 .. d-1 from 0 of the two elements'
+ * rows: the bits digat_dot_scores gives for them, symmetric.
+ * Selection, t = 0 .. k-1, every element starting with pen = 0: an element is eligible when it is not selected yet and — with
+ * max_per_category = q > 0 — fewer than q selected elements share its category[id] (category [N] int32; q == 0: no cap, category
+ * is not read and may be NULL).  value = lam * score - mu * pen in fp32, both products and the difference rounded (never an fma);
+ * mu is the caller's (float)1 - lam.  The winner is the eligible element with the largest topk_key(value) (digat_topk_segments'
+ * order: NaNs last, -0.0 == +0.0), ties to the lowest list position; then pen = fmax(pen, sim(i, winner)) for every element (a NaN
+ * similarity leaves pen as it is, a negative one earns nothing).  Selection stops when nothing is eligible.
+ * out_count [G] = the elements selected; slots t < count of out_ids / out_scores [G, k] hold the t-th winner's id and its INPUT
+ * score bits, slots t >= count hold -1 and -inf: every output byte is written.
+ * DIGAT_ERR_ARG: a null ids / scores / vectors / out pointer, G < 0, N < 0, q < 0, q > 0 without category, lam outside [0, 1] (a
+ * NaN included); DIGAT_ERR_SHAPE: k outside [1, 128], M outside [1, 128], d outside [1, 2^24], G >= 2^31 — all before any launch.
+ * G == 0 returns DIGAT_OK without a launch.  Stream-ordered: one launch on `stream`, one workgroup per user, the Gram of a list
+ * never leaves LDS; no allocation, no host synchronisation, no read of device memory on the host.  The workspace is not used
+ * (digat_mmr_select_workspace_bytes returns 0; workspace may be NULL). */
+size_t digat_mmr_select_workspace_bytes(int64_t users, int m, int k);
+int digat_mmr_select(const int64_t* ids, const float* scores, const int32_t* count, int64_t G, int M, const float* vectors, int64_t N, int d,
+                     const int32_t* category, int max_per_category, float lam, float mu, int k, int64_t* out_ids, float* out_scores,
+                     int32_t* out_count, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- vanilla-GAT update layer of the ablation encoders -----------------------------------------
  * graphEncoders.py:493-519 (wo_interaction), :641-651 (News_graph_wo_inter), :788-798 (User_graph_wo_inter), eval mode:
  * h = X W^T + bW; e_ij = leaky_relu_0.2(a1.h_j + a2.h_i); -1e9 where A_ij = 0; alpha = softmax_j; out = relu(alpha h) + X.

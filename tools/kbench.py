@@ -28,6 +28,11 @@
                                              against torch.matmul + evaluate.topk_segments and torch.matmul + torch.topk, G = 64 and
                                              4 096 users x 65 237 news, d = 400, k = 10 and 100, the three legs in turn, median
                                              [min, max] of five rounds; then nrms.recommend for 4 096 users end to end
+  python tools/kbench.py diversify [news_num d]   diversified top-k: evaluate.mmr_select (one launch, the Gram in LDS) against gather +
+                                             torch.bmm + k rounds of torch element-wise ops and arg-max, G = 64 and 4 096 lists of
+                                             M = 128, d = 400, k = 10 and 100, with and without a cap of 2 per category, the legs in
+                                             turn, median [min, max] of five rounds; then util.recommend for 64 users at k = 10 with
+                                             and without diversity=0.3
   python tools/kbench.py sag-lists [news categories dim top_M]  the SAG's similar-news lists of a MIND-small-shaped corpus
                                              (65 238 news over 17 categories of skewed sizes, the largest ~30 %, dim 768, top_M 5):
                                              construct_SAG.similar_news_lists_device per category against cos_topk_device + all five
@@ -861,15 +866,12 @@ def bench_topk(rounds=5):
     line(f"{len(lengths)} ragged segments ({R} rows), k = 10", R, a, b, "digat_rank_metrics")
 
 
-def bench_recommend(users=64, news_num=65238, rounds=5):
-    """``util.recommend`` for ``users`` impressions of a MIND-small-shaped corpus against the pool of all non-PAD news, k = 10, the
-    history excluded: users per second, median [min, max] of ``rounds`` runs; and the selection's share (``evaluate.topk_segments``
-    on scores of the same shape with the same skip rows).  The per-news tables are built before, untimed."""
+def _recommend_setup(users, news_num, depth=3):
+    """A MIND-small-shaped synthetic corpus on the device and a DIGAT model with random weights: ``(spec, model, dc)``."""
     import types
-    from digat_amd import evaluate, synthetic, util
+    from digat_amd import synthetic, util
     from digat_amd.model import Model, PrecomputedNewsEncoder
     dev = torch.device("cuda:0")
-    depth = 3
     spec = synthetic.SynthSpec(news_num=news_num, sag_neighbors=3, sag_hops=2, impressions=max(users, 256), seed=61)
     corpus = synthetic.make_corpus(spec)
     cfg = types.SimpleNamespace(news_encoder="MSA", graph_encoder="DIGAT", news_graph_size=spec.news_graph_size,
@@ -877,8 +879,17 @@ def bench_recommend(users=64, news_num=65238, rounds=5):
     state = synthetic.make_state_dict(spec.embedding_dim, spec.category_num, depth, seed=62, bias_std=0.05)
     model = Model(cfg, news_encoder=PrecomputedNewsEncoder(torch.from_numpy(corpus.news_embedding)))
     model.graph_encoder.load_state_dict({k: torch.from_numpy(v) for k, v in state.items()})
-    model = model.to(dev).eval()
-    dc = util.DeviceCorpus.from_numpy(corpus, dev)
+    return spec, model.to(dev).eval(), util.DeviceCorpus.from_numpy(corpus, dev)
+
+
+def bench_recommend(users=64, news_num=65238, rounds=5):
+    """``util.recommend`` for ``users`` impressions of a MIND-small-shaped corpus against the pool of all non-PAD news, k = 10, the
+    history excluded: users per second, median [min, max] of ``rounds`` runs; and the selection's share (``evaluate.topk_segments``
+    on scores of the same shape with the same skip rows).  The per-news tables are built before, untimed."""
+    from digat_amd import evaluate, util
+    dev = torch.device("cuda:0")
+    depth = 3
+    spec, model, dc = _recommend_setup(users, news_num, depth)
     pool = torch.arange(1, news_num, dtype=torch.int64, device=dev)
     who = np.arange(users)
     rows = users * (news_num - 1)
@@ -972,6 +983,104 @@ def bench_dot_topk(news_num=65238, d=400, rounds=5):
           f"of which dot_topk with the pool and {H}-entry skip rows {sel:.3f} ms", flush=True)
 
 
+def torch_mmr(ids, scores, count, vectors, k, lam, category=None, q=0):
+    """Greedy maximal-marginal relevance built only from stock PyTorch: gather, ``torch.bmm``, then k rounds of element-wise ops and
+    arg-max over all lists at once.  Every id is taken to lie in the table; NaN scores and the order among tied values are not the
+    contract's (a yardstick for speed)."""
+    G, M = ids.shape
+    dev = ids.device
+    rows = vectors[ids]
+    sim = torch.bmm(rows, rows.transpose(1, 2))
+    elem = torch.arange(M, device=dev)[None, :] < count[:, None]
+    pen = torch.zeros((G, M), device=dev)
+    chosen = torch.zeros((G, M), dtype=torch.bool, device=dev)
+    same = torch.zeros((G, M), dtype=torch.int32, device=dev)
+    cat = category[ids] if q else None
+    out_i = torch.full((G, k), -1, dtype=torch.int64, device=dev)
+    out_s = torch.full((G, k), float("-inf"), device=dev)
+    cnt = torch.zeros(G, dtype=torch.int32, device=dev)
+    ar = torch.arange(G, device=dev)
+    neg = torch.full((), float("-inf"), device=dev)
+    for t in range(k):
+        ok = elem & ~chosen
+        if q:
+            ok &= same < q
+        value = torch.where(ok, lam * scores - (1.0 - lam) * pen, neg)
+        j = value.argmax(dim=1)
+        live = ok[ar, j]
+        out_i[:, t] = torch.where(live, ids[ar, j], out_i[:, t])
+        out_s[:, t] = torch.where(live, scores[ar, j], out_s[:, t])
+        chosen[ar, j] |= live
+        pen = torch.maximum(pen, sim[ar, j])
+        if q:
+            same += ((cat == cat[ar, j][:, None]) & live[:, None]).to(torch.int32)
+        cnt += live.to(torch.int32)
+    return out_s, out_i, cnt
+
+
+def bench_diversify(news_num=65238, d=400, rounds=5):
+    """``evaluate.mmr_select`` against ``torch_mmr`` (what the tree had: gather + ``torch.bmm`` + k rounds of tiny launches), the two
+    legs in turn in one process, median [min, max] of ``rounds`` rounds: G in {64, 4 096} lists of M = 128 ids of a table of
+    ``news_num`` unit rows, k in {10, 100}, without and with a cap of 2 per category (17 categories).  Then ``util.recommend`` for
+    64 users at k = 10 without and with ``diversity=0.3``, and ``mmr_select`` on lists of that shape, for the stage's share."""
+    import time
+    from digat_amd import evaluate, util
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device="cpu").manual_seed(0)
+    M = 128
+    table = util.unit_rows(torch.randn(news_num, d, generator=g).to(dev))
+    table[1::2] = table[0:news_num - 1:2][:table[1::2].shape[0]]   # every other row a copy of its neighbour: the penalty bites
+    category = torch.randint(0, 17, (news_num,), generator=g, dtype=torch.int32).to(dev)
+    print(f"diversify: lists of M = {M} ids of {news_num} unit rows, d = {d}; ms per call, median [min, max] of {rounds} rounds", flush=True)
+    for G in (64, 4096):
+        ids = torch.randint(0, news_num, (G, M), generator=g).to(dev)
+        scores = torch.randn(G, M, generator=g).to(dev)
+        count = torch.full((G,), M, dtype=torch.int32, device=dev)
+        for k in (10, 100):
+            for q in (0, 2):
+                cat = category if q else None
+                ours = lambda: evaluate.mmr_select(ids, scores, count, table, k, 0.7, category=cat, max_per_category=q)
+                stock = lambda: torch_mmr(ids, scores, count, table, k, 0.7, category, q)
+                got, want = ours(), stock()
+                torch.cuda.synchronize()
+                same = float((got[1] == want[1]).float().mean())     # bmm rounds otherwise than the fmaf chain: near-ties may swap
+                (a, alo, ahi), (b, blo, bhi) = alternate(ours, stock, rounds=rounds, iters=5)
+                print(f"  G = {G:5d}, k = {k:3d}, cap {q}: mmr_select {a:8.3f} ms [{alo:.3f}, {ahi:.3f}] ({2.0 * G * M * M * d / a / 1e9:6.2f} TFLOP/s "
+                      f"of Gram) | gather + bmm + {k} torch rounds {b:8.3f} ms [{blo:.3f}, {bhi:.3f}] (x{b / a:.2f}) | ids equal: {same:.4f}",
+                      flush=True)
+        del ids, scores, count
+    del table
+    torch.cuda.empty_cache()
+    users = 64
+    spec, model, dc = _recommend_setup(users, news_num)
+    pool = torch.arange(1, news_num, dtype=torch.int64, device=dev)
+    who = np.arange(users)
+    stat = lambda v: (sorted(v)[len(v) // 2], min(v), max(v))
+    legs = {"plain k = 10": dict(), "plain k' = 40": dict(k=40), "diversity=0.3": dict(diversity=0.3),
+            "diversity=0.3, 2 per category": dict(diversity=0.3, max_per_category=2)}
+    for kw in legs.values():
+        util.recommend(model, dc, who, pool, kw.pop("k", 10), **kw)  # the per-news tables, every path warm
+    legs["plain k' = 40"]["k"] = 40
+    torch.cuda.synchronize()
+    secs = {name: [] for name in legs}
+    for _ in range(rounds):
+        for name, kw in legs.items():
+            kw = dict(kw)
+            t0 = time.perf_counter()
+            util.recommend(model, dc, who, pool, kw.pop("k", 10), **kw)
+            torch.cuda.synchronize()
+            secs[name].append(time.perf_counter() - t0)
+    for name, v in secs.items():
+        med, lo, hi = stat(v)
+        print(f"  util.recommend, {users} users x {news_num - 1} news, {name}: {med:.3f} s [{lo:.3f}, {hi:.3f}]", flush=True)
+    i, s, c = util.recommend(model, dc, who, pool, 40)
+    unit = util.unit_rows(dc.news_embedding)
+    sel, _ = timeit(lambda: evaluate.mmr_select(i, s, c, unit, 10, 0.7), iters=10)
+    norm, _ = timeit(lambda: util.unit_rows(dc.news_embedding), iters=10)
+    print(f"  of which mmr_select on the {users} lists of 40: {sel:.3f} ms, unit_rows of the {news_num} x {spec.embedding_dim} table: {norm:.3f} ms",
+          flush=True)
+
+
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "xattn"
     nums = [int(v) for v in sys.argv[2:]]
@@ -1013,6 +1122,8 @@ if __name__ == "__main__":
         bench_recommend(*nums)
     elif what == "dot-topk":
         bench_dot_topk(*nums)
+    elif what == "diversify":
+        bench_diversify(*nums)
     elif what == "linear":
         bench_linear(*nums)
     elif what == "gemm":
