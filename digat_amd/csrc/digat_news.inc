@@ -277,7 +277,10 @@ static int launch_msa_attention(const float* qkv, float* h, int T, int Lw, int h
             default: hipLaunchKernelGGL(msa_attention_mfma_kernel<8>, dim3(T), dim3(256), lds, st, a); break;
         }
     } else {
+        // up to 132 096 B (Lw = 64, d_k = 32) of the CU's 160 KiB: above 64 KiB a launch has to opt in (as cnn_launch_conv does)
         const size_t lds = (size_t)4 * (2 * Lw * dk + Lw * (Lw + 1)) * 4;
+        if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)msa_attention_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                   (int)lds) != hipSuccess) return DIGAT_ERR_LAUNCH;
         hipLaunchKernelGGL(msa_attention_kernel, dim3(T), dim3(256), lds, st, a);
     }
     DIGAT_CHECK_LAUNCH();

@@ -689,7 +689,9 @@ int digat_sag_news_graph(const int32_t* sim_index, const float* sim_cos, const i
 /* ---- news encoder (upstream of the path): newsEncoders.MSA.forward in eval mode ------------------
  * newsEncoders.py:70-82 with layers.MultiHeadAttention (layers.py:50-88) and layers.Attention (:91-115).
  * title_text [T, Lw] int32 token ids (rows of word_embedding), title_mask [T, Lw] bytes (0 = padding: masked only in
- * the pooling, as in the reference), out [T, head_num * head_dim].  Lw <= 64, head_dim <= 32.
+ * the pooling, as in the reference), out [T, head_num * head_dim].  Lw <= 64, head_dim <= 32.  Titles of 33..64 words take up
+ * to 132 096 bytes of dynamic LDS per workgroup (every shape of the contract fits the CU's 160 KiB); DIGAT_ERR_LAUNCH if the
+ * runtime does not grant the size.
  * qkv_wsplit: [W_Q|W_K|W_V] split by digat_split_proj_weights-style call digat_split_msa_weights (optional: NULL =
  * fp32 MFMA path with a materialised embedding gather). */
 typedef struct digat_msa_params {
