@@ -25,6 +25,7 @@ PARAMS_PQ_FP8 = 256                     # digat_params.flags: P', Q of Eq. 8 sto
 PARAMS_SIDE_STREAM_OFF, PARAMS_SIDE_STREAM_ON = 512, 1024      # digat_params.flags: never / always (neither: by pass size)
 PARAMS_NO_LIVE_ROWS = 2048              # digat_params.flags: project every user-graph node in every layer
 PARAMS_PROJ_F16F8C = 4096               # digat_params.flags: the layers' [W|ffn1|ffn2] images are GEMM_F16F8C
+PARAMS_RAGGED_OFF, PARAMS_RAGGED_ROWMAJOR = 8192, 16384      # digat_params.flags: featureAffine on one-strip tiles / ragged tiles row-tile-major
 
 _f = C.c_void_p  # every device pointer crosses as void*
 
@@ -183,6 +184,8 @@ _SIGNATURES = {
     "digat_split_proj_weights": (C.c_int, [_f, _f, _f, C.c_int, _f, C.c_int, _f]),
     "digat_split_weights": (C.c_int, [_f, C.c_int, C.c_int, _f, C.c_int, _f]),
     "digat_linear_f32x3": (C.c_int, [_f, C.c_int64, _f, _f, _f, C.c_int64, C.c_int, C.c_int, C.c_int, _f, C.c_int, _f]),
+    "digat_linear_rows_f32x3": (C.c_int, [_f, C.c_int64] + [_f] * 6 + [C.c_int64] + [C.c_int] * 3 + [_f, C.c_int, _f, _f, _f, C.c_int64, _f]
+                                + [C.c_int] * 3 + [_f]),
     "digat_fold_workspace_bytes": (C.c_size_t, [C.c_int]),
     "digat_fold_attention": (C.c_int, [_f] * 5 + [C.c_int, _f, C.c_size_t, _f]),
     "digat_linear_bwd_input": (C.c_int, [_f, C.c_int64, _f, _f, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _f]),

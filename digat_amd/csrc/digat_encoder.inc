@@ -196,6 +196,7 @@ struct FoldedPass {
     const digat_params* const p; const EncoderWs& w; const hipStream_t st;
     const int B, N, H, G, d, C, L, U, C1;
     const GemmFormats f;
+    const int ragged;                      // encoder_ragged (digat_encoder_plan.h): GemmArgs::ragged of the launches that ask
     // c_n_src: where the news context stands BEFORE layer 0 — c_n itself, or (depth >= 1, context given) the caller's c_n0, read
     // in place by the two consumers that precede the first update instead of being copied into c_n first
     float *const c_n, *const c_u; const float* const c_n_src;
@@ -206,7 +207,7 @@ struct FoldedPass {
     FoldedPass(const EncoderCall& call, const float* Xg0_, SideStream* side_)
         : c(call), pl(call.plan), Xg0(Xg0_), side(side_), p(call.p), w(call.ws), st(call.st), B(call.B), N(call.N), H(call.H), G(call.G),
           d(call.p->d), C(call.p->category_num), L(call.p->depth), U(call.H + call.p->category_num), C1(call.p->category_num + 1),
-          f(gemm_formats(call.p)), c_n(call.out_news), c_u(call.out_user), c_n_src(call.plan.c_n0_in_place ? call.c_n0 : call.out_news) {}
+          f(gemm_formats(call.p)), ragged(encoder_ragged(call.p->flags)), c_n(call.out_news), c_u(call.out_user), c_n_src(call.plan.c_n0_in_place ? call.c_n0 : call.out_news) {}
 
     // the user-side queries + (optionally) the next user-graph K3, all from c_n
     int context_queries(int next_layer, hipStream_t sq) const {
@@ -234,6 +235,7 @@ struct FoldedPass {
         g.epi = EPI_RELU_RES; g.e0 = T; g.lde0 = d;
         g.wsplit = (const unsigned short*)p->featureAffine_wsplit;       // non-NULL: split operands on the matrix cores
         g.format = f.fmt; g.range_flag = f.range_flag;
+        g.ragged = ragged;        // d = 400: 3 + 2 strips instead of five one-strip tiles that each fetch and split the A tile
         if (live.bucket_idx && gemm_takes_row_list(g)) { g.rowidx = live.bucket_idx; g.nrows_dev = live.nbuckets; }   // unmasked buckets only
         e = launch_gemm(g, sq);
         if (e) return e;

@@ -131,3 +131,8 @@ static inline EncoderPlan encoder_plan(const EncoderPlanIn& in) {
     pl.side_wanted = folded && !(pl.side_mode == 0 || (pl.side_mode == 2 && B >= 2048));
     return pl;
 }
+
+// ---- how the strip-mined GEMM's launches are tiled (flags bits 13-14: A/B switches, no result depends on them) -------------------
+// GemmArgs::ragged of the launches that ask for ragged 240-column tiles (featureAffine):
+// DIGAT_GEMM_RAGGED (1), DIGAT_GEMM_RAGGED_ROWMAJOR (2), or 0 = nobody asks
+static inline int encoder_ragged(int flags) { return (flags & DIGAT_PARAMS_RAGGED_OFF) ? 0 : ((flags & DIGAT_PARAMS_RAGGED_ROWMAJOR) ? 2 : 1); }

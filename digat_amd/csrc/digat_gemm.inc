@@ -421,9 +421,14 @@ __device__ unsigned long long g_gemm_timers[8];
 // selector becomes a compile-time constant, the wave-uniform branch around each 16-column block's extra products (five per strip)
 // goes, and a strip's 30 MFMAs + 10 fragment reads are ONE basic block for the scheduler.  The variants measured and rejected
 // (pre-split A rows, the spread DMA issue, 64-row "fat" wave tiles) are in docs/REJECTED.md.
-template <int NSUB, bool F16, int MT, bool FULL>      // MT: 16-row blocks per wave (wave tile 16 MT x 80 NSUB)
+// RAG (ragged 240-column tiles, GemmPlan::ragged): the last column tile of a launch whose N is no multiple of 240 has ns = 1 or 2
+// strips; ns is wave-uniform and drives the step count, the ring indices and where the A tile is issued and split.  The steps
+// themselves (DMA pieces, MFMA order, split) are those of the full-width tile, so every output element keeps its product chain
+// — and the launches without ragged tiles keep their code: RAG = false folds every ns to NSUB.
+template <int NSUB, bool F16, int MT, bool FULL, bool RAG = false>      // MT: 16-row blocks per wave (wave tile 16 MT x 80 NSUB)
 __global__ void __launch_bounds__(256, MT == 1 ? 3 : 2) gemm_bf16x6s_kernel(const GemmArgs g) {
     static_assert(MT == 1 || MT == 2, "wave tiles of 16 or 32 rows");
+    static_assert(!RAG || (NSUB == 3 && MT == 2), "ragged tiles: 128 rows x up to three strips");
     constexpr int NT = 5;
     constexpr int WROWS = 16 * MT, TROWS = 4 * WROWS;      // rows of a wave tile / of the workgroup's tile (four waves stacked along M)
     constexpr int APW = 2 * MT;                             // 1 KB DMA pieces (8 rows x 32 k fp32) of the A tile per wave
@@ -432,8 +437,8 @@ __global__ void __launch_bounds__(256, MT == 1 ? 3 : 2) gemm_bf16x6s_kernel(cons
     // 16.0 -> 14.7 us on 7 000 x 400 x 400).  Deeper rings measured no better (3 / 3: 16.2 us; 5 / 4 at one workgroup per CU:
     // 24.8 us): the phase timers show these launches waiting 7 % of a step — what is left is launch, prologue and epilogue.
     constexpr int RING = 3;                   // strip images in LDS: RING - 1 in flight behind the one being read
-    constexpr int ABUF = NSUB == 1 ? 2 : 1;   // fp32 A tiles (128 rows x 32 k) in LDS (three 15 KB bf16 planes per image leave
-                                              // room for two: 77 KB, two workgroups per CU)
+    constexpr int ABUF = NSUB == 1 || RAG ? 2 : 1;   // fp32 A tiles (128 rows x 32 k) in LDS (three 15 KB bf16 planes per image leave
+                                              // room for two: 77 KB, two workgroups per CU); ragged: a one-strip tile needs the second
     constexpr int PL = F16 ? 2 : 3;          // operand pieces
     constexpr int WS_SLOTS = PL * 320;       // 16-byte slots of one strip image (shadows the bf16 constant)
     constexpr int PIECES = WS_SLOTS / 64;    // 1 KB DMA pieces of an image: 15 / 10
@@ -445,12 +450,32 @@ __global__ void __launch_bounds__(256, MT == 1 ? 3 : 2) gemm_bf16x6s_kernel(cons
     // count comes from the live row count, so the live tiles still spread over the 8 XCDs evenly.
     const int Mv = g.nrows_dev ? __builtin_amdgcn_readfirstlane(*g.nrows_dev) : g.M;      // scalar: the tile index and every base address that follows from it stay in SGPRs
     if (g.exec_rows && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(g.exec_rows, (unsigned long long)Mv);
-    const int total = ((Mv + TROWS - 1) / TROWS) * g.ntiles;
-    const int chunk = (total + 7) >> 3;
-    if ((int)(blockIdx.x >> 3) >= chunk) return;
-    const int tile = (int)(blockIdx.x & 7) * chunk + (int)(blockIdx.x >> 3);
-    if (tile >= total) return;
-    const int mtile = tile / g.ntiles, ntile = tile - mtile * g.ntiles;
+    int mtile, ntile;
+    if (!RAG || g.ragged == DIGAT_GEMM_RAGGED_ROWMAJOR) {
+        const int total = ((Mv + TROWS - 1) / TROWS) * g.ntiles;
+        const int chunk = (total + 7) >> 3;
+        if ((int)(blockIdx.x >> 3) >= chunk) return;
+        const int tile = (int)(blockIdx.x & 7) * chunk + (int)(blockIdx.x >> 3);
+        if (tile >= total) return;
+        mtile = tile / g.ntiles; ntile = tile - mtile * g.ntiles;
+    } else {
+        // Long tiles first: an XCD's chunk is its share of the full-width tiles (row-tile-major) followed by its share of the short
+        // last-column tiles, so the workgroups that start late — behind the first wave of two per CU — are the short ones.
+        const int mlive = (Mv + TROWS - 1) / TROWS, nfw = g.ntiles - 1;
+        const int nfull = mlive * nfw, cf = (nfull + 7) >> 3, cs = (mlive + 7) >> 3;
+        const int xcd = (int)(blockIdx.x & 7), j = (int)(blockIdx.x >> 3);
+        if (j < cf) {
+            const int t = xcd * cf + j;
+            if (t >= nfull) return;
+            mtile = t / nfw; ntile = t - mtile * nfw;
+        } else {
+            const int t = xcd * cs + (j - cf);
+            if (j - cf >= cs || t >= mlive) return;
+            mtile = t; ntile = nfw;
+        }
+    }
+    // strips of this column tile: wave-uniform (SGPR); without ragged tiles the constant NSUB
+    const int ns = RAG ? __builtin_amdgcn_readfirstlane(g.strips - NSUB * ntile < NSUB ? g.strips - NSUB * ntile : NSUB) : NSUB;
 
     const int tid = threadIdx.x, lane = tid & 63, wm = tid >> 6;
     const int kg = lane >> 4, lr = lane & 15;
@@ -461,7 +486,7 @@ __global__ void __launch_bounds__(256, MT == 1 ? 3 : 2) gemm_bf16x6s_kernel(cons
     unsigned long long gt_wait = 0, gt_bar = 0, gt_body = 0, gt_steps = 0, gt_last = 0;
 #endif
     const int KT = (g.K + 31) >> 5;
-    const int nsteps = KT * NSUB;
+    const int nsteps = KT * ns;
     const unsigned ldsB = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)&Bs[0][0];
     const unsigned ldsA = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)&As[0][0];
     const char* const wimg = reinterpret_cast<const char*>(g.wsplit);      // wave-uniform: the pieces' sources are (scalar base) + lane x 16
@@ -470,9 +495,7 @@ __global__ void __launch_bounds__(256, MT == 1 ? 3 : 2) gemm_bf16x6s_kernel(cons
 
     // Every global read of the loop is an LDS-DMA, four wave-instructions per wave and image, so the vector-memory
     // queue holds whole images in issue order and "s_waitcnt vmcnt(4)" means "all but the youngest image".
-    auto issue_b = [&](int step) {           // strip image of step (kt, s) -> Bs[step % RING]; 15 instructions + 1 repeat
-        const int kt = step / NSUB, s = step - kt * NSUB;
-        const int buf = step % RING;
+    auto issue_b_at = [&](int kt, int s, int buf) {      // strip image of step (kt, s) -> Bs[buf]; 15 instructions + 1 repeat
         const char* src = wimg + ((long)(strip0 + s) * KT + kt) * (WS_SLOTS * 16);
 #pragma unroll
         for (int k = 0; k < IMG_I; ++k) {
@@ -480,6 +503,18 @@ __global__ void __launch_bounds__(256, MT == 1 ? 3 : 2) gemm_bf16x6s_kernel(cons
             q = q < PIECES ? q : PIECES - 1;                     // the last piece is copied more than once: IMG_I per wave, always
             lds_dma16_s(src + q * 1024, wlane, ldsB + (unsigned)((buf * WS_SLOTS + q * 64) * 16));
         }
+    };
+    auto issue_b = [&](int step) {           // full-width tiles: step = kt * NSUB + s, ring slot step % RING
+        const int kt = step / NSUB;
+        issue_b_at(kt, step - kt * NSUB, step % RING);
+    };
+    // ragged tiles: the image that goes out next — two steps ahead of the one being read — as (K tile, strip, ring slot),
+    // carried along in SGPRs instead of divided out of the step at every issue
+    int nb_kt = 0, nb_s = 0, nb_buf = 0;
+    auto issue_b_next = [&]() {
+        issue_b_at(nb_kt, nb_s, nb_buf);
+        if (++nb_s == ns) { nb_s = 0; ++nb_kt; }
+        nb_buf = nb_buf == RING - 1 ? 0 : nb_buf + 1;
     };
     // this lane's source of A-tile piece q = wu + 4k at K tile 0, as a 32-bit byte offset from a scalar base: the tile's first row
     // (contiguous rows: the offsets stay below 128 rows), or the operand's start for a row-list launch, whose rows then have to span
@@ -581,6 +616,11 @@ __global__ void __launch_bounds__(256, MT == 1 ? 3 : 2) gemm_bf16x6s_kernel(cons
         for (int j = 0; j < ABUF; ++j) if (j < KT) issue_a(j, j);
 #pragma unroll
         for (int j = 0; j < RING - 1; ++j) if (j < nsteps) issue_b(j);
+    } else if constexpr (RAG) {
+        issue_a(0, 0);
+        if (ns == 1 && KT > 1) issue_a(1, 1);      // a one-strip tile keeps its A tiles two steps ahead (as the NSUB == 1 kernel does)
+        issue_b_next();
+        if (nsteps > 1) issue_b_next();
     } else {
         issue_a(0, 0);
         issue_b(0);
@@ -591,106 +631,127 @@ __global__ void __launch_bounds__(256, MT == 1 ? 3 : 2) gemm_bf16x6s_kernel(cons
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) split_mt(mt, 0, af);
 
-    for (int kt = 0; kt < KT; ++kt) {
-        const bool more = kt + 1 < KT;
+    // The K loop.  ONE (ragged launches only, a compile-time flag so that a strip stays one basic block): this is a one-strip
+    // tile — A(kt + 2) is issued at step kt into the buffer A(kt) was split from a step ago, and A(kt + 1) is split during step
+    // kt.  Ragged tiles of two or three strips issue A(kt + 1) at strip 0 and split it at strip 1 like the full-width kernel,
+    // into the other A buffer; their ring slot and step number are counted along, since kt * ns + s is no constant modulo RING.
+    auto k_loop = [&](auto one_strip) __attribute__((always_inline)) {
+        constexpr bool ONE = decltype(one_strip)::value;
+        constexpr int SMAX = ONE ? 1 : NSUB;
+        int step_r = 0, buf_r = 0;
+        for (int kt = 0; kt < KT; ++kt) {
+            const bool more = kt + 1 < KT;
+            const int sbuf = RAG ? ((more ? kt + 1 : kt) & 1) : 0;      // the A tile the step splits (after the last K tile: the stale one)
 #pragma unroll
-        for (int s = 0; s < NSUB; ++s) {
-            const int step = kt * NSUB + s;
-            const int buf = step % RING;
-            // queue, oldest first: image(step) | A tile requested a step ago | image(step+1): only the last may stay in flight
+            for (int s = 0; s < SMAX; ++s) {
+                if constexpr (RAG && !ONE) { if (s == 2 && ns == 2) break; }
+                const bool split_here = ONE ? s == 0 : s == 1;
+                const int step = RAG ? step_r : kt * NSUB + s;
+                const int buf = RAG ? buf_r : step % RING;
+                // queue, oldest first: image(step) | A tile requested a step ago | image(step+1): only the last may stay in flight
 #ifdef DIGAT_GEMM_TIMERS
-            const unsigned long long gt0 = GT_NOW();
-            if (step > 0) gt_body += gt0 - gt_last;
+                const unsigned long long gt0 = GT_NOW();
+                if (step > 0) gt_body += gt0 - gt_last;
 #endif
-            if constexpr (NSUB == 1) {
-                // needed now: image(kt) (issued RING - 1 steps ago) and A(kt + 1) (issued ABUF - 1 steps ago); a step issues
-                // [A, image].  With L = min(RING - 1, ABUF - 1) whole steps younger than both — plus, when the A tile is the
-                // younger of the two, the image issued right behind it — (4 + IMG_I) L (+ IMG_I) requests may stay in flight.
-                // The last steps issue less than that: they drain the queue.
-                constexpr int L = (RING - 1 < ABUF - 1 ? RING - 1 : ABUF - 1) - 1;
-                constexpr int KEEP = (APW + IMG_I) * (L < 0 ? 0 : L) + ((ABUF - 1 < RING - 1) ? IMG_I : 0);
-                static_assert(KEEP <= 63, "vmcnt is six bits");
-                if (kt + (RING - 1 > ABUF ? RING - 1 : ABUF) < KT) wait_vmcnt_imm<KEEP>();
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            } else if (step + 1 < nsteps) {
-                if constexpr (IMG_I == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-            } else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                if constexpr (NSUB == 1) {
+                    // needed now: image(kt) (issued RING - 1 steps ago) and A(kt + 1) (issued ABUF - 1 steps ago); a step issues
+                    // [A, image].  With L = min(RING - 1, ABUF - 1) whole steps younger than both — plus, when the A tile is the
+                    // younger of the two, the image issued right behind it — (4 + IMG_I) L (+ IMG_I) requests may stay in flight.
+                    // The last steps issue less than that: they drain the queue.
+                    constexpr int L = (RING - 1 < ABUF - 1 ? RING - 1 : ABUF - 1) - 1;
+                    constexpr int KEEP = (APW + IMG_I) * (L < 0 ? 0 : L) + ((ABUF - 1 < RING - 1) ? IMG_I : 0);
+                    static_assert(KEEP <= 63, "vmcnt is six bits");
+                    if (kt + (RING - 1 > ABUF ? RING - 1 : ABUF) < KT) wait_vmcnt_imm<KEEP>();
+                    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                } else if (step + 1 < nsteps) {
+                    if constexpr (IMG_I == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+                    else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+                } else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #ifdef DIGAT_GEMM_TIMERS
-            const unsigned long long gt1 = GT_NOW();
+                const unsigned long long gt1 = GT_NOW();
 #endif
-            __builtin_amdgcn_s_barrier();                          // landed for every wave; image(step-1) and the old A tile are free
+                __builtin_amdgcn_s_barrier();                          // landed for every wave; image(step-1) and the old A tile are free
 #ifdef DIGAT_GEMM_TIMERS
-            gt_last = GT_NOW();
-            gt_wait += gt1 - gt0; gt_bar += gt_last - gt1; ++gt_steps;
+                gt_last = GT_NOW();
+                gt_wait += gt1 - gt0; gt_bar += gt_last - gt1; ++gt_steps;
 #endif
-            if (NSUB == 1) {
-                if (kt + ABUF < KT) issue_a(kt + ABUF, kt % ABUF);  // the buffer of A(kt): split during step kt - 1
-                if (step + RING - 1 < nsteps) issue_b(step + RING - 1);
-            } else {
-                if (s == 0 && more) issue_a(kt + 1, 0);   // read at strip 1, after the next barrier
-                if (step + 2 < nsteps) issue_b(step + 2);
+                if (NSUB == 1) {
+                    if (kt + ABUF < KT) issue_a(kt + ABUF, kt % ABUF);  // the buffer of A(kt): split during step kt - 1
+                    if (step + RING - 1 < nsteps) issue_b(step + RING - 1);
+                } else if constexpr (RAG) {
+                    if constexpr (ONE) { if (kt + 2 < KT) issue_a(kt + 2, kt & 1); }
+                    else if (s == 0 && more) issue_a(kt + 1, (kt + 1) & 1);
+                    if (step + 2 < nsteps) issue_b_next();
+                } else {
+                    if (s == 0 && more) issue_a(kt + 1, 0);   // read at strip 1, after the next barrier
+                    if (step + 2 < nsteps) issue_b(step + 2);
+                }
+                const uint4* Bi = Bs[buf];
+                const int lslot = kg * 80 + lr;
+                bf16x8 bq[2][3];
+#pragma unroll
+                for (int p = 0; p < PL; ++p) bq[0][p] = __builtin_bit_cast(bf16x8, Bi[p * 320 + lslot]);
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) {
+                    if (nt + 1 < NT) {
+#pragma unroll
+                        for (int p = 0; p < PL; ++p) bq[(nt + 1) & 1][p] = __builtin_bit_cast(bf16x8, Bi[p * 320 + lslot + (nt + 1) * 16]);
+                    }
+                    const bf16x8 b1 = bq[nt & 1][0], b2 = bq[nt & 1][1], b3 = bq[nt & 1][PL - 1];
+                    v4f c[MT];
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt) c[mt] = acc[s][mt][nt];
+                    // the MT accumulators of a column block are independent chains: the products go round them (mt innermost)
+                    if (!F16 && (FULL || !lite[s])) {
+#pragma unroll
+                        for (int mt = 0; mt < MT; ++mt) c[mt] = mma(b1, af[2][mt], c[mt]);   // x3 w1
+#pragma unroll
+                        for (int mt = 0; mt < MT; ++mt) c[mt] = mma(b2, af[1][mt], c[mt]);   // x2 w2
+#pragma unroll
+                        for (int mt = 0; mt < MT; ++mt) c[mt] = mma(b3, af[0][mt], c[mt]);   // x1 w3
+                    }
+                    if (FULL || lite[s] < 2) {        // fp16x3: lo.hi and hi.lo
+#pragma unroll
+                        for (int mt = 0; mt < MT; ++mt) c[mt] = mma(b1, af[1][mt], c[mt]);   // x2 w1
+#pragma unroll
+                        for (int mt = 0; mt < MT; ++mt) c[mt] = mma(b2, af[0][mt], c[mt]);   // x1 w2
+                    }
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt) c[mt] = mma(b1, af[0][mt], c[mt]);       // x1 w1
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt) acc[s][mt][nt] = c[mt];
+                    if (NSUB > 1) {      // the next K tile's rows landed at this step's wait (requested at strip 0); after the last
+                                         // K tile the split runs on the stale tile (unused) so that the strip stays one basic block
+                        if (split_here && nt == 0) split_mt(0, sbuf, afn);
+                        if constexpr (MT > 1) { if (split_here && nt == 2) split_mt(1, sbuf, afn); }
+                    } else {             // one-strip tiles: A(kt + 1) landed at this step's wait (after the last K tile: a stale buffer, unused)
+                        if (nt == 0) split_mt(0, (kt + 1) % ABUF, afn);
+                        if constexpr (MT > 1) { if (nt == 2) split_mt(1, (kt + 1) % ABUF, afn); }
+                    }
+                }
+                if (NSUB == 1 || split_here) {
+                    // the ~100 vector instructions of the operand split go two per MFMA (an MFMA holds the SIMD's vector issue for
+                    // 8 of its 16 cycles: two 4-cycle instructions fit in the gap) instead of two bursts that stall the matrix pipe
+#pragma unroll
+                    for (int i = 0; i < 56; ++i) {
+                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                        __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+                    }
+                }
+                if constexpr (RAG) { ++step_r; buf_r = buf_r == RING - 1 ? 0 : buf_r + 1; }
             }
-            const uint4* Bi = Bs[buf];
-            const int lslot = kg * 80 + lr;
-            bf16x8 bq[2][3];
+            if (more) {
 #pragma unroll
-            for (int p = 0; p < PL; ++p) bq[0][p] = __builtin_bit_cast(bf16x8, Bi[p * 320 + lslot]);
+                for (int p = 0; p < 3; ++p)
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                if (nt + 1 < NT) {
-#pragma unroll
-                    for (int p = 0; p < PL; ++p) bq[(nt + 1) & 1][p] = __builtin_bit_cast(bf16x8, Bi[p * 320 + lslot + (nt + 1) * 16]);
-                }
-                const bf16x8 b1 = bq[nt & 1][0], b2 = bq[nt & 1][1], b3 = bq[nt & 1][PL - 1];
-                v4f c[MT];
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) c[mt] = acc[s][mt][nt];
-                // the MT accumulators of a column block are independent chains: the products go round them (mt innermost)
-                if (!F16 && (FULL || !lite[s])) {
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) c[mt] = mma(b1, af[2][mt], c[mt]);   // x3 w1
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) c[mt] = mma(b2, af[1][mt], c[mt]);   // x2 w2
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) c[mt] = mma(b3, af[0][mt], c[mt]);   // x1 w3
-                }
-                if (FULL || lite[s] < 2) {        // fp16x3: lo.hi and hi.lo
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) c[mt] = mma(b1, af[1][mt], c[mt]);   // x2 w1
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) c[mt] = mma(b2, af[0][mt], c[mt]);   // x1 w2
-                }
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) c[mt] = mma(b1, af[0][mt], c[mt]);       // x1 w1
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) acc[s][mt][nt] = c[mt];
-                if (NSUB > 1) {      // the next K tile's rows landed at this step's wait (requested at strip 0); after the last
-                                     // K tile the split runs on the stale tile (unused) so that the strip stays one basic block
-                    if (s == 1 && nt == 0) split_mt(0, 0, afn);
-                    if constexpr (MT > 1) { if (s == 1 && nt == 2) split_mt(1, 0, afn); }
-                } else {             // one-strip tiles: A(kt + 1) landed at this step's wait (after the last K tile: a stale buffer, unused)
-                    if (nt == 0) split_mt(0, (kt + 1) % ABUF, afn);
-                    if constexpr (MT > 1) { if (nt == 2) split_mt(1, (kt + 1) % ABUF, afn); }
-                }
-            }
-            if (NSUB == 1 || s == 1) {
-                // the ~100 vector instructions of the operand split go two per MFMA (an MFMA holds the SIMD's vector issue for
-                // 8 of its 16 cycles: two 4-cycle instructions fit in the gap) instead of two bursts that stall the matrix pipe
-#pragma unroll
-                for (int i = 0; i < 56; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-                }
+                    for (int mt = 0; mt < MT; ++mt) af[p][mt] = afn[p][mt];
             }
         }
-        if (more) {
-#pragma unroll
-            for (int p = 0; p < 3; ++p)
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) af[p][mt] = afn[p][mt];
-        }
-    }
+    };
+    if constexpr (RAG) {
+        if (ns == 1) k_loop(std::true_type{});
+        else k_loop(std::false_type{});
+    } else k_loop(std::false_type{});
 
 #ifdef DIGAT_GEMM_TIMERS
     const unsigned long long gt_loop_end = GT_NOW();
@@ -724,6 +785,7 @@ __global__ void __launch_bounds__(256, MT == 1 ? 3 : 2) gemm_bf16x6s_kernel(cons
     const bool has_e0 = g.epi == EPI_RELU_RES || g.epi == EPI_ADD_E0;
 #pragma unroll
     for (int s = 0; s < NSUB; ++s) {
+        if constexpr (RAG) { if (s >= ns) break; }       // a short tile's missing strips lie past N (or in nobody's segment)
         const int ncol0 = (strip0 + s) * 80;             // first column of this strip in the stacked output
         const int seg = ncol0 / g.nseg;
         const int nbase = ncol0 - seg * g.nseg + kg * 4;
@@ -1548,6 +1610,17 @@ static int launch_gemm(GemmArgs g, hipStream_t st, int kind = DIGAT_KERNEL_LINEA
     }
     ProfScope prof(kind, listed ? 0.0 : 2.0 * g.M * (double)Ntot * g.K, st, listed ? 0.0 : (double)g.M * gemm_row_bytes(g));
     g.mtiles = p.mtiles; g.ntiles = p.ntiles;
+    g.ragged = p.ragged; g.strips = p.ragged ? Ntot / 80 : 0;
+    if (p.ragged) {          // the chosen kernel's ragged instantiation (the same symbol with RAG = true)
+        void (*ragged)(const GemmArgs) = nullptr;
+        if (p.kernel == GEMM_STRIP_3_F16_FULL) ragged = gemm_bf16x6s_kernel<3, true, 2, true, true>;
+        else if (p.kernel == GEMM_STRIP_3_F16) ragged = gemm_bf16x6s_kernel<3, true, 2, false, true>;
+        else if (p.kernel == GEMM_STRIP_3_BF16) ragged = gemm_bf16x6s_kernel<3, false, 2, false, true>;
+        else return DIGAT_ERR_ARG;
+        hipLaunchKernelGGL(ragged, dim3(p.grid), dim3(p.block), 0, st, g);
+        DIGAT_CHECK_LAUNCH();
+        return DIGAT_OK;
+    }
     switch (p.kernel) {
 #define DIGAT_GEMM_LAUNCH(id, ...) case GEMM_##id: hipLaunchKernelGGL((__VA_ARGS__), dim3(p.grid), dim3(p.block), 0, st, g); break;
         DIGAT_GEMM_KERNELS(DIGAT_GEMM_LAUNCH)

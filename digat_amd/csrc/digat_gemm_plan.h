@@ -35,7 +35,11 @@ struct GemmArgs {
     const uint8_t* dmask; long lddm; float dscale; // bf16x6 kernel, optional: y = (result [+ e0]) x (dmask[row][col] ? dscale : 0) — the backward
     int dmask_cols;                                // of the dropout in front of the layer (training: dX through the keep bytes [M, lddm]);
                                                    // dmask_cols > 0: the mask has that many columns, output columns beyond them are left as computed
+    int ragged;                                    // != 0 ASKS for ragged 240-column tiles where N is no multiple of 240 (gemm_plan decides: see
+                                                   // GemmPlan::ragged); DIGAT_GEMM_RAGGED: full-width tiles dispatched first, _ROWMAJOR: row-tile-major
+    int strips;                                    // set by launch_gemm for a ragged launch: the 80-column strips of N (the last tile has strips % 3)
 };
+enum { DIGAT_GEMM_RAGGED = 1, DIGAT_GEMM_RAGGED_ROWMAJOR = 2 };
 
 // Every GEMM kernel instantiation the library launches, X(id, kernel): the GemmKernel values, their names and launch_gemm's
 // switch are all made from this one list.
@@ -87,6 +91,8 @@ struct GemmPlan {
     int mtiles, ntiles;    // the kernel's tile counts (GemmArgs::mtiles / ntiles)
     unsigned grid, block;
     int image_format;      // the format the kernel reads GemmArgs::wsplit in (the image must have been split in it); -1: no image
+    int ragged;            // != 0: the kernel's ragged instantiation (the same symbol with RAG = true): ntiles = ceil(strips / 3), the
+                           // last column tile has strips % 3 strips; the value is GemmArgs::ragged (the tile order)
 };
 
 static inline bool gemm_kernel_takes_row_list(int kernel) {
@@ -96,7 +102,7 @@ static inline bool gemm_kernel_takes_row_list(int kernel) {
 // The whole dispatch of launch_gemm, in its order of decisions.  `kind` (DIGAT_KERNEL_*) only names the large fp32 kernel's
 // instantiation, so that profiles list the Eq. 8 projections under their own symbol.
 static inline GemmPlan gemm_plan(const GemmArgs& g, int kind = DIGAT_KERNEL_LINEAR) {
-    GemmPlan p = {DIGAT_OK, GEMM_NONE, 0, 0, 0, 256, -1};
+    GemmPlan p = {DIGAT_OK, GEMM_NONE, 0, 0, 0, 256, -1, 0};
     const int Ntot = g.nseg * g.nsegs;
     const int Md = g.m_dispatch > 0 ? g.m_dispatch : g.M;
     const auto tiles = [&](int kernel, int mtiles, int ntiles, bool round8) {
@@ -176,13 +182,25 @@ static inline GemmPlan gemm_plan(const GemmArgs& g, int kind = DIGAT_KERNEL_LINE
         // Launches that leave the chip under-filled at 128-row tiles (a 4 096-row pass's [B,d] linears and news-side projections:
         // 160 workgroups for 256 CUs, each a 13-step latency chain) take 64-row tiles: twice the workgroups, the same chain; the
         // same for the bf16x6 launches of a training step's news graph (3 200 rows: 125 workgroups at 128-row tiles) without a row list
-        if (((g.M + 127) / 128) * ntiles < 400 && (f16 || !g.rowidx)) {
+        // (a launch that asks for ragged tiles counts its workgroups at m_dispatch, like the choice of this kernel: the same bits at every batching)
+        const int Mfill = g.ragged ? Md : g.M;
+        if (((Mfill + 127) / 128) * ntiles < 400 && (f16 || !g.rowidx)) {
             const int k = f16 ? (three ? GEMM_STRIP_3_F16_64 : GEMM_STRIP_1_F16_64) : (three ? GEMM_STRIP_3_BF16_64 : GEMM_STRIP_1_BF16_64);
             return tiles(k, (g.M + 63) / 64, ntiles, true);
         }
         // FULL: every segment takes all its products (what inference launches ask for)
         const int k = three ? (f16 ? (!g.x1_segs && !g.x3_segs ? GEMM_STRIP_3_F16_FULL : GEMM_STRIP_3_F16) : GEMM_STRIP_3_BF16)
                             : (f16 ? GEMM_STRIP_1_F16 : GEMM_STRIP_1_BF16);
+        // Ragged 240-column tiles, for launches that ask (GemmArgs::ragged) and whose N is no multiple of 240: ceil(strips / 3) column
+        // tiles, the last with strips % 3 strips, instead of one-strip tiles that fetch and split the A tile once per strip.  The
+        // grid holds, per XCD, the XCD's share of the full-width tiles and then its share of the short ones (long tiles first).
+        if (g.ragged && !three && strips > 3) {
+            const int mt = (g.M + 127) / 128, nt = (strips + 2) / 3;
+            tiles(f16 ? (!g.x1_segs && !g.x3_segs ? GEMM_STRIP_3_F16_FULL : GEMM_STRIP_3_F16) : GEMM_STRIP_3_BF16, mt, nt, true);
+            p.grid = (unsigned)(8 * ((mt * (nt - 1) + 7) / 8 + (mt + 7) / 8));
+            p.ragged = g.ragged;
+            return p;
+        }
         return tiles(k, (g.M + 127) / 128, ntiles, true);
     }
     // 7. the fp32 MFMA kernel

@@ -573,6 +573,32 @@ int digat_linear_f32x3(const float* x, int64_t ldx, const float* w, const float*
     return launch_gemm(g, (hipStream_t)stream, DIGAT_KERNEL_PROJ);
 }
 
+// digat_linear_f32x3 with what the encoder's row-list launches add: one or two weight segments (w1 non-NULL: y1 = x w1^T + b1,
+// columns [nseg, 2 nseg) of the image), a row list, relu + residual (e0 non-NULL), the K3 addend on segment 1 (radd, one row per
+// rows_per_b rows), m_dispatch and the request for ragged 240-column tiles (GemmArgs::ragged).  The tests' way to those launches.
+int digat_linear_rows_f32x3(const float* x, int64_t ldx, const float* w0, const float* w1, const float* b0, const float* b1,
+                            float* y0, float* y1, int64_t ldy, int M, int nseg, int K, void* wsplit, int format,
+                            const int* rowidx, const int* nrows_dev, const float* e0, int64_t lde0,
+                            const float* radd, int rows_per_b, int m_dispatch, int ragged, void* stream) {
+    if (!x || !w0 || !y0 || !wsplit || M < 0 || nseg <= 0 || K <= 0 || (w1 && !y1) || (radd && (!w1 || rows_per_b <= 0))) return DIGAT_ERR_ARG;
+    if (ragged < 0 || ragged > DIGAT_GEMM_RAGGED_ROWMAJOR || (rowidx && !nrows_dev)) return DIGAT_ERR_ARG;
+    if (K % 8 || ldx % 4 || nseg % 80) return DIGAT_ERR_SHAPE;
+    const int nsegs = w1 ? 2 : 1;
+    const int rcs = launch_split(w0, w1 ? w1 : w0, w0, nseg, nsegs, K, wsplit, (hipStream_t)stream, 0, format);
+    if (rcs) return rcs;
+    GemmArgs g = gemm_plain(x, ldx, w0, b0, y0, ldy, M, nseg, K, 0);
+    g.w[1] = w1; g.bias[1] = b1; g.y[1] = y1; g.nsegs = nsegs;
+    g.wsplit = (const unsigned short*)wsplit; g.format = format;
+    if (e0) { g.epi = EPI_RELU_RES; g.e0 = e0; g.lde0 = lde0; }
+    g.radd = radd; g.radd_seg = 1; g.rows_per_b = rows_per_b;
+    g.m_dispatch = m_dispatch; g.ragged = ragged;
+    if (rowidx) {
+        if (!gemm_takes_row_list(g)) return DIGAT_ERR_ARG;
+        g.rowidx = rowidx; g.nrows_dev = nrows_dev;
+    }
+    return launch_gemm(g, (hipStream_t)stream, DIGAT_KERNEL_PROJ);
+}
+
 // ---- a3 -----------------------------------------------------------------------------------------
 // query, K^T query and the global context, [B,d] each
 struct NewsCtxWs { float *qv, *kq, *glob; };

@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import contextlib
 import math
+import os
 import threading
 
 import torch
@@ -122,6 +123,11 @@ class DIGAT(GraphEncoder):
         # ``launch_options(...)`` overrides them for the calling THREAD only — nothing here is process-wide.
         self.side_stream = "auto"
         self.live_rows = True
+        # A/B switch of featureAffine's GEMM launch (digat_params.flags bits 13-14; results do not depend on it, bit for bit):
+        # "long-first" = ragged 240-column tiles (3 + 2 strips at d = 400), the full-width tiles dispatched first, "row-major" = the
+        # same tiles in row-tile-major order, "off" = one-strip tiles.  The environment sets the default so that a benchmark run
+        # can be A/B'd (2.80 against 2.85 ms per step).
+        self.ragged_tiles = os.environ.get("DIGAT_RAGGED_TILES", "long-first")
         # compute_user_graph_context of the folded inference path as ONE launch (csrc/digat_ctxfused.inc: topic pooling, featureAffine
         # and the SDPA pooling without T / T' leaving the CU; fp16x3 format, H <= 52, 192 < d <= 448, C + 1 <= 20).  OFF by default:
         # measured at parity with the three launches it replaces (round 6: 0.73 against 0.78 ms of kernel time per 4 096-row pass alone,
@@ -362,7 +368,8 @@ class DIGAT(GraphEncoder):
                 | (_lib.PARAMS_PROJ_F16F8C if pm == "fp16-fp8c" else 0)  # ... except the layers' images: fp16 + MX-e4m3 corrections
                 | (_lib.PARAMS_BD_TILED if self.pass_rows >= 2048 else 0)
                 | {"auto": 0, "off": _lib.PARAMS_SIDE_STREAM_OFF, "on": _lib.PARAMS_SIDE_STREAM_ON}[self._launch_option("side_stream")]
-                | (0 if self._launch_option("live_rows") else _lib.PARAMS_NO_LIVE_ROWS))
+                | (0 if self._launch_option("live_rows") else _lib.PARAMS_NO_LIVE_ROWS)
+                | {"long-first": 0, "row-major": _lib.PARAMS_RAGGED_ROWMAJOR, "off": _lib.PARAMS_RAGGED_OFF}[self.ragged_tiles])
 
     def _fold_sources(self):
         ca, ua = self.candidate_attention, self.userAttention

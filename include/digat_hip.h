@@ -77,6 +77,15 @@ int digat_split_proj_weights(const float* W, const float* F1, const float* F2, i
 int digat_split_weights(const float* W, int N, int K, void* wsplit, int format, void* stream);    /* one [N,K] matrix */
 int digat_linear_f32x3(const float* x, int64_t ldx, const float* w, const float* b, float* y, int64_t ldy,
                        int M, int N, int K, void* wsplit, int format, void* stream);
+/* The same with what the encoder's row-list launches add (M >= 2048 or m_dispatch >= 2048: the strip-mined kernel).  w1 non-NULL:
+ * a second segment y1 = x w1^T + b1 (wsplit holds both: digat_split_weights_bytes(2 nseg, K)); rowidx / nrows_dev (device): only
+ * rows rowidx[0 .. *nrows_dev) of x / y are processed; e0 non-NULL: y = relu(.) + e0; radd non-NULL (needs w1): y1 += radd[row /
+ * rows_per_b]; m_dispatch != 0: choose the kernel as if M were this; ragged: 0, or 1 / 2 to ask for ragged 240-column tiles where
+ * N is no multiple of 240 (1: full-width tiles dispatched first, 2: row-tile-major) — the results do not depend on it, bit for bit. */
+int digat_linear_rows_f32x3(const float* x, int64_t ldx, const float* w0, const float* w1, const float* b0, const float* b1,
+                            float* y0, float* y1, int64_t ldy, int M, int nseg, int K, void* wsplit, int format,
+                            const int* rowidx, const int* nrows_dev, const float* e0, int64_t lde0,
+                            const float* radd, int rows_per_b, int m_dispatch, int ragged, void* stream);
 
 /* ---- a1 / a2: DIGAT.compute_news_graph_embeddings / compute_user_graph_embeddings -------------
  * graphEncoders.py:143-154 / :163-174 (Eq. 8).  X [B,n,d], A [B,n,n] bytes, ctx [B,d] (the OTHER
@@ -304,6 +313,12 @@ enum { DIGAT_PARAMS_SIDE_STREAM_OFF = 512, DIGAT_PARAMS_SIDE_STREAM_ON = 1024, D
  * and per-row layer-0 projections, every layer's projection GEMM, digat_news_project0 / digat_user_project0 — runs the fp8-
  * correction kernel at any row count.  Not combined with DIGAT_PROJ_PQ_X3, DIGAT_PQ_BF16 or DIGAT_PQ_FP8 (DIGAT_ERR_ARG). */
 enum { DIGAT_PARAMS_PROJ_F16F8C = 4096 };
+/* Bits 13-14: how the strip-mined GEMM tiles featureAffine (N = d; d = 400 is five 80-column strips, no multiple of the three a
+ * 240-column tile holds).  Results do not depend on them, bit for bit (no output element's product chain changes); they exist for A/B runs.
+ * Default (both clear): ragged 240-column tiles, 3 + 2 strips, the full-width tiles dispatched first.
+ * DIGAT_PARAMS_RAGGED_OFF: one-strip tiles (each fetches and splits its A tile again).
+ * DIGAT_PARAMS_RAGGED_ROWMAJOR: ragged tiles in row-tile-major order (long and short tiles alternate). */
+enum { DIGAT_PARAMS_RAGGED_OFF = 8192, DIGAT_PARAMS_RAGGED_ROWMAJOR = 16384 };
 
 /* The same inference for rows that SHARE users: in dev/test scoring the ~37 candidate rows of one
  * impression carry identical user tensors (util.py:57-67 expands them per row).  Here the user side is
