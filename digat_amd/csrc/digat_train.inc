@@ -1640,7 +1640,7 @@ static int xattn_pairwise_fwd_train_flag(const float* Pr, const float* Q, const 
     rc = launch_score(pl, st);
     if (rc || small) return rc;
     const float* aggalpha = p > 0.f ? alpha_drop : alpha;
-    return launch_agg(AggArgs{aggalpha, h, X, out, B, n, d, (d + 63) / 64, n | 1, nullptr, nullptr, guarded ? sparse_flag : nullptr}, st);
+    return launch_agg_1024(AggArgs{aggalpha, h, X, out, B, n, d, (d + 63) / 64, n | 1, nullptr, nullptr, guarded ? sparse_flag : nullptr}, st);
 }
 int digat_xattn_pairwise_fwd_train(const float* Pr, const float* Q, const float* h, const float* X, const float* a,
                                    const uint8_t* A, float* out, float* alpha, float* s_pre, float* alpha_drop,

@@ -1611,79 +1611,83 @@ __global__ void __launch_bounds__(MAXT) xattn_agg_kernel(const AggArgs g) {
         }
     }
     __syncthreads();
-    if (wave >= g.groups) return;
     const int lr = lane & 15, lq = lane >> 4;
-    const int ch = wave * 64 + 4 * lr;
-    const bool ch_ok = ch < d;
-    const float* Hb = g.Hh + (long)(g.hgroup ? g.hgroup[b] : b) * n * d;
-    const float* Xb = g.X + (long)b * n * d;
-    float* Ob = g.out + (long)b * n * d;
-    const int nit = (n + 15) >> 4;
-    const int nsteps = (n + 3) >> 2;
+    // a wave per 64 channels; beyond 1024 channels (more groups than the 16 waves of the largest workgroup) a wave takes several in turn
+    for (int cg = wave; cg < g.groups; cg += (int)(blockDim.x >> 6)) {
+        const int ch = cg * 64 + 4 * lr;
+        const bool ch_ok = ch < d;
+        const float* Hb = g.Hh + (long)(g.hgroup ? g.hgroup[b] : b) * n * d;
+        const float* Xb = g.X + (long)b * n * d;
+        float* Ob = g.out + (long)b * n * d;
+        const int nit = (n + 15) >> 4;
+        const int nsteps = (n + 3) >> 2;
 
-    auto load_h = [&](int step) -> float4 {
-        const int j = step * 4 + lq;
-        return (j < n && ch_ok && lv[j]) ? *reinterpret_cast<const float4*>(Hb + (long)j * d + ch) : f4_zero();
-    };
+        auto load_h = [&](int step) -> float4 {
+            const int j = step * 4 + lq;
+            return (j < n && ch_ok && lv[j]) ? *reinterpret_cast<const float4*>(Hb + (long)j * d + ch) : f4_zero();
+        };
 
-    for (int it0 = 0; it0 < nit; it0 += AG_IT) {
-        v4f acc[AG_IT][4];
-#pragma unroll
-        for (int it = 0; it < AG_IT; ++it)
-#pragma unroll
-            for (int s = 0; s < 4; ++s) acc[it][s] = (v4f){0.f, 0.f, 0.f, 0.f};
+        for (int it0 = 0; it0 < nit; it0 += AG_IT) {
+            v4f acc[AG_IT][4];
+    #pragma unroll
+            for (int it = 0; it < AG_IT; ++it)
+    #pragma unroll
+                for (int s = 0; s < 4; ++s) acc[it][s] = (v4f){0.f, 0.f, 0.f, 0.f};
 
-        float4 hq[AG_PF];
-#pragma unroll
-        for (int u = 0; u < AG_PF; ++u) hq[u] = load_h(u);
-        for (int step = 0; step < nsteps; step += AG_PF) {
-#pragma unroll
-            for (int u = 0; u < AG_PF; ++u) {
-                const int st = step + u;
-                if (st < nsteps) {
-                    const float4 hc = hq[u];
-                    hq[u] = load_h(st + AG_PF);
-                    const int j = st * 4 + lq;
-#pragma unroll
-                    for (int it = 0; it < AG_IT; ++it) {
-                        const int i = (it0 + it) * 16 + lr;
-                        const float av = (i < n && j < n) ? As[i * sa + j] : 0.f;
-                        if (it0 + it < nit && __any(av != 0.f)) {
-                            acc[it][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, hc.x, acc[it][0], 0, 0, 0);
-                            acc[it][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, hc.y, acc[it][1], 0, 0, 0);
-                            acc[it][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, hc.z, acc[it][2], 0, 0, 0);
-                            acc[it][3] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, hc.w, acc[it][3], 0, 0, 0);
+            float4 hq[AG_PF];
+    #pragma unroll
+            for (int u = 0; u < AG_PF; ++u) hq[u] = load_h(u);
+            for (int step = 0; step < nsteps; step += AG_PF) {
+    #pragma unroll
+                for (int u = 0; u < AG_PF; ++u) {
+                    const int st = step + u;
+                    if (st < nsteps) {
+                        const float4 hc = hq[u];
+                        hq[u] = load_h(st + AG_PF);
+                        const int j = st * 4 + lq;
+    #pragma unroll
+                        for (int it = 0; it < AG_IT; ++it) {
+                            const int i = (it0 + it) * 16 + lr;
+                            const float av = (i < n && j < n) ? As[i * sa + j] : 0.f;
+                            if (it0 + it < nit && __any(av != 0.f)) {
+                                acc[it][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, hc.x, acc[it][0], 0, 0, 0);
+                                acc[it][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, hc.y, acc[it][1], 0, 0, 0);
+                                acc[it][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, hc.z, acc[it][2], 0, 0, 0);
+                                acc[it][3] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, hc.w, acc[it][3], 0, 0, 0);
+                            }
                         }
                     }
                 }
             }
-        }
-        if (ch_ok) {
-#pragma unroll
-            for (int it = 0; it < AG_IT; ++it) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int i = (it0 + it) * 16 + 4 * lq + r;
-                    if (i < n && lv[i]) {
-                        const float4 x = *reinterpret_cast<const float4*>(Xb + (long)i * d + ch);
-                        *reinterpret_cast<float4*>(Ob + (long)i * d + ch) =
-                            make_float4(fmaxf(acc[it][0][r], 0.f) + x.x, fmaxf(acc[it][1][r], 0.f) + x.y,
-                                        fmaxf(acc[it][2][r], 0.f) + x.z, fmaxf(acc[it][3][r], 0.f) + x.w);
+            if (ch_ok) {
+    #pragma unroll
+                for (int it = 0; it < AG_IT; ++it) {
+    #pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int i = (it0 + it) * 16 + 4 * lq + r;
+                        if (i < n && lv[i]) {
+                            const float4 x = *reinterpret_cast<const float4*>(Xb + (long)i * d + ch);
+                            *reinterpret_cast<float4*>(Ob + (long)i * d + ch) =
+                                make_float4(fmaxf(acc[it][0][r], 0.f) + x.x, fmaxf(acc[it][1][r], 0.f) + x.y,
+                                            fmaxf(acc[it][2][r], 0.f) + x.z, fmaxf(acc[it][3][r], 0.f) + x.w);
+                        }
                     }
                 }
             }
         }
     }
 }
-// every launch of it: a workgroup per row, a wave per 64 channels (d <= 1024); alpha[b] and the live flags in LDS
+// every launch of it: a workgroup per row, a wave per 64 channels (up to 16 waves: from d = 1028 a wave takes several groups);
+// alpha[b] and the live flags in LDS
 static int launch_agg(const AggArgs& ag, hipStream_t st) {
-    if (ag.groups > 16) return DIGAT_ERR_SHAPE;
     const size_t lds = (size_t)ag.n * ag.sa * 4 + ag.n;
     if (ag.groups <= 8) hipLaunchKernelGGL(xattn_agg_kernel<512>, dim3(ag.B), dim3(64 * ag.groups), lds, st, ag);
-    else hipLaunchKernelGGL(xattn_agg_kernel<1024>, dim3(ag.B), dim3(64 * ag.groups), lds, st, ag);
+    else hipLaunchKernelGGL(xattn_agg_kernel<1024>, dim3(ag.B), dim3(64 * (ag.groups < 16 ? ag.groups : 16)), lds, st, ag);
     DIGAT_CHECK_LAUNCH();
     return DIGAT_OK;
 }
+// the GAT layer and the training forward keep the limit their other kernels were written and tested for: d <= 1024
+static int launch_agg_1024(const AggArgs& ag, hipStream_t st) { return ag.groups > 16 ? DIGAT_ERR_SHAPE : launch_agg(ag, st); }
 
 struct XattnPlan { ScoreArgs g; int threads; size_t lds; int blocks; };
 
@@ -1704,8 +1708,14 @@ static int plan_xattn(int B, int n, int d, XattnPlan* pl) {
     int bestRB = 0, bestCC = 0;
     // <= 40 KiB keeps 4 workgroups per CU (1024 rows = one round on 256 CUs); graphs too large for
     // that may take up to 150 KiB.  The DMA ring must sit in the first 64 KiB of LDS (M0 addressing).
-    for (int pass = 0; pass < 3 && !bestRB; ++pass) {
-        const size_t lds_budget = pass == 0 ? 40 * 1024 : (pass == 1 ? 64 * 1024 : 150 * 1024);
+    // Phase 0 stages the adjacency bytes at the start of LDS, below the bit rows at am_off = max(ring, scores).  The three budgets
+    // are first tried with the bytes inside the ring alone; wide graphs of few channels (n >= 111 at d = 4: a 12 KiB ring, 12 - 16 KiB
+    // of bytes) find no plan that way, and a second round (`relaxed`) lets the bytes reach into the score area, which is idle until
+    // the chunk loop has ended.  Plans of the first round are never replaced.
+    for (int pass = 0; pass < 6 && !bestRB; ++pass) {
+        const bool relaxed = pass >= 3;
+        const int budget = pass % 3;
+        const size_t lds_budget = budget == 0 ? 40 * 1024 : (budget == 1 ? 64 * 1024 : 150 * 1024);
         for (int rb = rbmax; rb >= 1 && !bestRB; --rb) {
             int cc_ok = 0;
             // odd chunk widths first (conflict-free LDS reads), widest first
@@ -1718,7 +1728,8 @@ static int plan_xattn(int B, int n, int d, XattnPlan* pl) {
                     if ((size_t)XA_RING * ring_slots * 16 > 60 * 1024) continue;
                     const size_t sc = (size_t)rb * n * g.SN * 4;
                     const size_t ringb = (size_t)XA_RING * ring_slots * 16;
-                    if ((size_t)rb * n * n + 32 > ringb) continue;          // the byte image passes through the ring area
+                    const size_t stage = (relaxed && sc > ringb) ? sc : ringb;     // where the byte image of phase 0 may lie
+                    if ((size_t)rb * n * n + 32 > stage) continue;
                     const size_t tot = align_up(ringb > sc ? ringb : sc, 16) + (size_t)rb * n * ((n + 31) / 32) * 4
                                        + (size_t)d * 4 + ((size_t)rb * tiles + 16) * 4 + (size_t)rb * 8 * g.NT * 4
                                        + (size_t)2 * rb * n * 4;
