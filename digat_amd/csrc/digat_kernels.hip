@@ -16,6 +16,7 @@
 //   digat_user_graph.inc  user graphs and category masks from category indices
 //   digat_train_input.inc  the training input: an epoch's negative samples, the index lists of a step
 //   digat_dot_topk.inc  inner-product retrieval: fp32 matrix-core product fused with the top-k selection of digat_topk.inc
+//   digat_dot_rank.inc  retrieval evaluation: the same product fused with the rank of given targets in the whole pool
 // This file: shared helpers, the per-kernel profiler, and the C ABI.  The encoder's orchestration is digat_encoder.inc (host
 // code only), and every decision of an encoder call is made in digat_encoder_plan.h (plain C++).
 //
@@ -871,4 +872,5 @@ int digat_row_logits(const float* news_ctx, const float* user_ctx, float* logits
 #include "digat_train_input.inc"
 #include "digat_ablation.inc"
 #include "digat_dot_topk.inc"
+#include "digat_dot_rank.inc"
 #include "digat_mmr.inc"

@@ -310,6 +310,186 @@ def dot_scores(users, news, pool=None):
     return out
 
 
+def _check_target_start(target_start, users: int, targets: int) -> np.ndarray:
+    """``target_start`` of the rank entries as a host int64 array: [users + 1] row offsets from 0 to ``targets`` that never decrease."""
+    import torch
+    st = np.asarray(target_start.cpu() if torch.is_tensor(target_start) else target_start)
+    if st.ndim != 1 or st.shape[0] != users + 1 or st.dtype.kind not in "iu":
+        raise ValueError(f"target_start must be a 1-D integer array of users + 1 = {users + 1} offsets, got shape {st.shape} {st.dtype}")
+    st = st.astype(np.int64)
+    if st[0] != 0 or np.any(np.diff(st) < 0) or int(st[-1]) != targets:
+        raise ValueError(f"target_start must begin at 0, never decrease and end at the number of targets ({targets})")
+    return st
+
+
+def dot_rank_host(scores, target_pos, target_start, pool=None, skip=None, news_num=None):
+    """The contract of ``digat_dot_rank`` on a given score matrix ``scores`` [G, P], in numpy — the yardstick of the kernel.  The
+    elements of user g are ``dot_topk_host``'s: the pool positions whose id (``pool``; the position when None) is not in ``skip[g]``
+    and lies in [0, ``news_num``) (None: no upper bound).  ``target_pos`` [T] holds pool positions, ``target_start`` [G + 1] gives
+    every user its slice.  Returns ``rank`` [T] int32: the elements of the target's user that order before it — a larger key
+    (``topk_keys``: NaNs last, ``-0.0 == +0.0``), or the same key at a smaller position — or -1 where the target is no element of
+    its user."""
+    S = np.ascontiguousarray(scores, dtype=np.float32)
+    if S.ndim != 2:
+        raise ValueError("scores must be [G, P]")
+    G, P = S.shape
+    pos = np.asarray(target_pos, dtype=np.int64)
+    if pos.ndim != 1:
+        raise ValueError("target_pos must be 1-D")
+    st = _check_target_start(target_start, G, len(pos))
+    ids = np.arange(P, dtype=np.int64) if pool is None else np.asarray(pool, dtype=np.int64)
+    if ids.shape != (P,):
+        raise ValueError(f"pool must have one id per column ({P}), got shape {ids.shape}")
+    skv = None if skip is None else np.asarray(skip, dtype=np.int64).reshape(G, -1)
+    if skv is not None and skv.shape[1] > TOPK_MAX_SKIP:
+        raise ValueError(f"skip must be [users, at most {TOPK_MAX_SKIP}], got shape {skv.shape}")
+    base = ids >= 0
+    if news_num is not None:
+        base &= ids < int(news_num)
+    where = np.arange(P, dtype=np.int64)
+    rank = np.full(len(pos), -1, dtype=np.int32)
+    for g in range(G):
+        a, b = int(st[g]), int(st[g + 1])
+        if a == b:
+            continue
+        elem = base if skv is None or not skv.shape[1] else base & ~np.isin(ids, skv[g])
+        keys = topk_keys(S[g]).astype(np.int64)
+        q = pos[a:b]
+        ok = (q >= 0) & (q < P)
+        ok[ok] = elem[q[ok]]
+        qs = q[ok]
+        before = (keys[None, :] > keys[qs][:, None]) | ((keys[None, :] == keys[qs][:, None]) & (where[None, :] < qs[:, None]))
+        out = rank[a:b]
+        out[ok] = (before & elem[None, :]).sum(axis=1)
+    return rank
+
+
+def dot_rank(users, news, target_pos, target_start, pool=None, skip=None):
+    """For every target — a pool position of one user — its rank in that user's whole ordered pool, on the GPU without the [G, P]
+    score matrix (``digat_dot_rank``).  ``users`` [G, d], ``news`` [N, d], ``pool`` [P] and ``skip`` [G, L <= 256] are ``dot_topk``'s,
+    and so are a user's elements and their order; ``target_pos`` [T] int64 (a device tensor or a host array) holds pool positions,
+    ``target_start`` [G + 1] is a HOST array — checked here, then uploaded — that gives user g the targets
+    ``[start[g], start[g+1])``: none, one or many, repeats allowed.  Returns ``(rank [T] int32, scores [T] float32)`` on the device:
+    the number of the user's elements that order before the target, and the target's score with the bits ``dot_scores`` gives; -1
+    and NaN where the target is no element of its user (a position outside [0, P), a skipped id).  The contract is
+    ``dot_rank_host``'s on ``dot_scores``, exactly; ``rank < k`` holds exactly when ``dot_topk``'s list carries the element at slot
+    ``rank``.  Stream-ordered; only the pool's id range is read back, for the check."""
+    import torch
+    from . import _lib
+    given = [t for t in (users, news, pool, skip) if t is not None]
+    dev = _lib.require_device(*given)
+    G, N, P, d = _check_dot_args(users, news, pool, skip)
+    tp = torch.as_tensor(np.asarray(target_pos) if not torch.is_tensor(target_pos) else target_pos)
+    if tp.dim() != 1 or tp.dtype in (torch.float16, torch.float32, torch.float64, torch.bool):
+        raise ValueError("target_pos must be a 1-D integer array of pool positions")
+    T = int(tp.shape[0])
+    st = _check_target_start(target_start, G, T)
+    u, v = _lib.f32(users.detach()), _lib.f32(news.detach())
+    pl = None if pool is None else pool.to(torch.int64).contiguous()
+    sk = None if skip is None or skip.shape[1] == 0 else skip.to(torch.int64).contiguous()
+    rank = torch.full((T,), -1, dtype=torch.int32, device=dev)
+    scores = torch.full((T,), float("nan"), dtype=torch.float32, device=dev)
+    if G == 0 or T == 0 or P == 0:                                  # an empty pool: nothing is an element
+        return rank, scores
+    tp = tp.to(dev, torch.int64).contiguous()
+    std = torch.from_numpy(st).to(dev)
+    L = _lib.lib()
+    need = int(L.digat_dot_rank_workspace_bytes(G, P, T))
+    ws = _lib.workspace(need, dev, "dot_rank")
+    _lib.check(L.digat_dot_rank(u.data_ptr(), v.data_ptr(), _lib.ptr(pl), G, N, P, d, _lib.ptr(sk), 0 if sk is None else int(sk.shape[1]),
+                                tp.data_ptr(), std.data_ptr(), T, rank.data_ptr(), scores.data_ptr(), ws.data_ptr(), need,
+                                _lib.stream_ptr()),
+               "digat_dot_rank")
+    return rank, scores
+
+
+def list_ranks(ids, count, target_ids, target_start):
+    """The slot of every target id in its user's list: ``rank`` [T] int32, -1 where the list does not hold it (its first occurrence
+    where it holds it twice).  ``ids`` [G, k] and ``count`` [G] (None: k) are what ``util.recommend`` / ``nrms.recommend`` return —
+    slots at or beyond ``count`` are fill —, ``target_ids`` [T] news ids, ``target_start`` [G + 1] the users' slices.  Torch
+    operations only, on the device of ``ids``: the way to hold a second stage (a re-rank, a diversified list) to ``rank_metrics``."""
+    import torch
+    ids = torch.as_tensor(ids)
+    if ids.dim() != 2:
+        raise ValueError(f"ids must be [G, k], got {tuple(ids.shape)}")
+    G, k = int(ids.shape[0]), int(ids.shape[1])
+    dev = ids.device
+    tg = torch.as_tensor(np.asarray(target_ids) if not torch.is_tensor(target_ids) else target_ids).to(dev, torch.int64)
+    if tg.dim() != 1:
+        raise ValueError("target_ids must be 1-D")
+    T = int(tg.shape[0])
+    st = torch.from_numpy(_check_target_start(target_start, G, T)).to(dev)
+    cnt = torch.full((G,), k, dtype=torch.int64, device=dev) if count is None else torch.as_tensor(count).to(dev, torch.int64)
+    if tuple(cnt.shape) != (G,):
+        raise ValueError(f"count must have one entry per list ({G}), got shape {tuple(cnt.shape)}")
+    owner = torch.repeat_interleave(torch.arange(G, device=dev), st[1:] - st[:-1], output_size=T)
+    slot = torch.arange(k, device=dev)
+    hit = (ids.to(torch.int64).index_select(0, owner) == tg[:, None]) & (slot[None, :] < cnt.index_select(0, owner)[:, None])
+    first = torch.where(hit, slot[None, :], torch.full_like(slot, k)[None, :]).amin(dim=1) if k else tg.new_zeros(T)
+    return torch.where(first < k, first, torch.full_like(first, -1)).to(torch.int32)
+
+
+def rank_metrics(rank, target_start, ks=(10, 50, 100, 128)):
+    """Full-catalogue retrieval metrics of a rank array (``dot_rank``, ``dot_rank_host``, ``list_ranks``: 0-based, -1 = not ranked),
+    in float64 on the host.  A dict with, for every k of ``ks`` (any positive k): ``recall@k`` — the targets with
+    ``0 <= rank < k`` over ALL targets, an unranked one is a miss — and ``user_recall@k`` — the mean over the users with at least
+    one target of their share of targets inside k —; ``mrr`` — the mean over those users of ``1 / (1 + their best rank)``, 0 for a
+    user none of whose targets is ranked —; ``median_rank`` over the ranked targets; the counts ``not_ranked``, ``targets`` and
+    ``users`` (those with a target).  What has nothing to average over is NaN."""
+    import torch
+    r = np.asarray(rank.cpu() if torch.is_tensor(rank) else rank).astype(np.int64)
+    if r.ndim != 1:
+        raise ValueError("rank must be 1-D")
+    T = len(r)
+    st = np.asarray(target_start.cpu() if torch.is_tensor(target_start) else target_start)
+    if st.size == 0:
+        st = np.zeros(1, dtype=np.int64)                            # nobody
+    st = _check_target_start(st, len(st) - 1 if st.ndim == 1 else 0, T)
+    per_user = np.diff(st)
+    have = per_user > 0
+    users = int(have.sum())
+    ranked = r >= 0
+    owner = np.repeat(np.arange(len(per_user)), per_user)
+    nan = float("nan")
+    out = {}
+    for k in ks:
+        if int(k) != k or k < 1:
+            raise ValueError(f"every k must be a positive integer, got {k}")
+        inside = ranked & (r < int(k))
+        out[f"recall@{int(k)}"] = float(inside.sum()) / T if T else nan
+        share = np.bincount(owner, weights=inside.astype(np.float64), minlength=len(per_user))[have] / per_user[have]
+        out[f"user_recall@{int(k)}"] = float(share.mean()) if users else nan
+    best = np.full(len(per_user), np.iinfo(np.int64).max, dtype=np.int64)
+    np.minimum.at(best, owner[ranked], r[ranked])
+    best = best[have]
+    found = best != np.iinfo(np.int64).max
+    out["mrr"] = float(np.where(found, 1.0 / (1.0 + np.where(found, best, 0).astype(np.float64)), 0.0).mean()) if users else nan
+    out["median_rank"] = float(np.median(r[ranked])) if ranked.any() else nan
+    out["not_ranked"], out["targets"], out["users"] = int(T - ranked.sum()), T, users
+    return out
+
+
+def shortlist_for(rank, share: float):
+    """The smallest shortlist length k with ``recall@k >= share`` for a rank array (``rank_metrics``' recall: over all targets, an
+    unranked one is a miss), or None when no k reaches it — too many targets are unranked, or there is no target."""
+    import torch
+    r = np.asarray(rank.cpu() if torch.is_tensor(rank) else rank).astype(np.int64)
+    T = len(r)
+    if not 0.0 <= float(share) <= 1.0:
+        raise ValueError(f"share must lie in [0, 1], got {share}")
+    if T == 0:
+        return None
+    m = int(np.ceil(float(share) * T))                              # the targets that must be inside: the smallest m with m / T >= share
+    while m > 0 and (m - 1) / T >= share:
+        m -= 1
+    while m / T < share:
+        m += 1
+    got = np.sort(r[r >= 0])
+    if m > len(got):
+        return None
+    return 1 if m == 0 else int(got[m - 1]) + 1
+
+
 MMR_MAX_LIST = TOPK_MAX_K      # include/digat_hip.h: digat_mmr_select takes lists of at most this many entries
 
 

@@ -559,6 +559,109 @@ def recommend(model, dev, users, candidates=None, k=10, exclude_history=True, ba
     return util.recommend_select(G, k, ids, start, skip, util.RECOMMEND_MAX_ROWS if cuda else max(1, G * int(ids.shape[0])), score)
 
 
+def _clicked_targets(dev, users):
+    """``(impression indices [G], target_ids [T], target_start [G+1])`` from the rows of ``dev`` with ``row_label == 1``: every
+    user's clicked candidates in row order.  ``users`` None: every impression that has a clicked row, ascending."""
+    for name in ("row_candidate", "row_impression", "row_label"):
+        if getattr(dev, name, None) is None:
+            raise ValueError(f"the clicked targets come from dev.{name}, which this corpus does not carry: pass targets=(target_ids, target_start)")
+    cand = np.asarray(dev.row_candidate, dtype=np.int64)
+    imp = np.asarray(dev.row_impression, dtype=np.int64)
+    label = np.asarray(dev.row_label)
+    if not (cand.shape == imp.shape == label.shape and cand.ndim == 1):
+        raise ValueError("row_candidate, row_impression and row_label must be 1-D arrays of one length")
+    I = int(dev.history_ids.shape[0])
+    if imp.size and (int(imp.min()) < 0 or int(imp.max()) >= I):
+        raise ValueError(f"row_impression must lie in [0, {I})")
+    rows = np.flatnonzero(label == 1)
+    rows = rows[np.argsort(imp[rows], kind="stable")]               # impression-major already; any other order keeps rows in order per user
+    per = np.bincount(imp[rows], minlength=I)
+    first = np.r_[0, np.cumsum(per)]
+    idx = np.flatnonzero(per > 0) if users is None else np.asarray(users.cpu() if torch.is_tensor(users) else users)
+    if idx.ndim != 1 or idx.dtype.kind not in "iu":
+        raise ValueError("the clicked targets belong to impressions: users must be a 1-D integer array of impression indices (or pass targets)")
+    if idx.size and (int(idx.min()) < 0 or int(idx.max()) >= I):
+        raise ValueError(f"impression indices must lie in [0, {I})")
+    idx = idx.astype(np.int64)
+    n = per[idx]
+    start = np.r_[0, np.cumsum(n)].astype(np.int64)
+    take = np.repeat(first[idx] - start[:-1], n) + np.arange(int(start[-1]), dtype=np.int64)
+    return idx, cand[rows[take]], start
+
+
+def retrieval_metrics(model, dev, users=None, targets=None, candidates=None, ks=(10, 50, 100, 128), exclude_history=True, batch_size=1024):
+    """Full-catalogue retrieval metrics of the first stage: where in a user's whole ordered pool the target news stand — how long
+    ``recommend``'s shortlist must be for a clicked news to survive into a re-rank (``evaluate.shortlist_for`` on the returned
+    ranks).  Returns ``evaluate.rank_metrics``' dict plus ``rank`` [T] int32 (0-based, -1: not ranked), ``target_start`` [G+1] and
+    ``target_ids`` [T], numpy arrays.
+
+    ``dev``, ``exclude_history`` and ``batch_size`` are ``recommend``'s: candidates are read from the augmented cache, histories
+    from the plain one, a news of the user's history (mask non-zero) is no element, nor is row 0.  ``users``: impression indices of
+    ``dev`` (or a ``(history_ids, history_mask)`` pair together with explicit targets); None = every impression with a clicked row.
+    ``targets``: None = every user's clicked candidates — ``dev.row_candidate`` where ``dev.row_label == 1`` —, else ``(target_ids
+    [T], target_start [G+1])``.  ``candidates``: None = every news but row 0, or one 1-D pool shared by all users; per-user lists
+    have no whole-pool rank — score such lists with ``evaluate.list_ranks``.  A target takes the first pool position of its id; a
+    target that is not in the pool, is row 0, or — under ``exclude_history`` — is in its user's history is NOT RANKED (-1): it
+    counts as a miss in every recall, and ``not_ranked`` says how many there are.
+
+    On CUDA tensors the ranks come from ``evaluate.dot_rank`` (``digat_dot_rank``: no [users, news] score matrix); on CPU tensors
+    from the stock product and ``evaluate.dot_rank_host``."""
+    from . import evaluate, util
+    N = int(dev.title_text.shape[0])
+    if targets is None:
+        users, target_ids, target_start = _clicked_targets(dev, users)
+    else:
+        if users is None:
+            raise ValueError("explicit targets need users: the impressions (or histories) target_start refers to")
+        if not (isinstance(targets, (tuple, list)) and len(targets) == 2):
+            raise ValueError("targets must be None or a pair (target_ids [T], target_start [G+1])")
+        target_ids = np.asarray(targets[0].cpu() if torch.is_tensor(targets[0]) else targets[0])
+        if target_ids.ndim != 1 or (target_ids.size and target_ids.dtype.kind not in "iu"):
+            raise ValueError("target_ids must be a 1-D integer array of news ids")
+        target_ids, target_start = target_ids.astype(np.int64), targets[1]
+    hist, mask = _histories(dev, users)
+    G = int(hist.shape[0])
+    target_start = evaluate._check_target_start(target_start, G, len(target_ids))
+    if target_ids.size and (int(target_ids.min()) < 0 or int(target_ids.max()) >= N):
+        raise ValueError(f"target ids must lie in [0, {N})")
+    util.recommend_limits(1, int(hist.shape[1]) if exclude_history else 0)
+    if candidates is None:
+        candidates = np.arange(1, N, dtype=np.int64)
+    ids, start = util.recommend_candidates(candidates, G, N)
+    if start is not None:
+        raise ValueError("retrieval_metrics ranks targets in one pool shared by all users; per-user candidate lists have no such rank: "
+                         "score them with evaluate.list_ranks on the lists recommend returns")
+    # every target's first position in the pool, on the host; -1: not in it
+    pool = ids.cpu().numpy()
+    order = np.argsort(pool, kind="stable")
+    at = np.searchsorted(pool[order], target_ids, side="left")
+    inside = at < len(pool)
+    inside[inside] = pool[order[at[inside]]] == target_ids[inside]
+    target_pos = np.where(inside, order[np.minimum(at, max(len(pool) - 1, 0))] if len(pool) else -1, -1).astype(np.int64)
+    model.eval()
+    plain, aug = news_caches(model, dev.title_text, dev.title_mask, dev.augmented_title_text, dev.augmented_title_mask, 4 * batch_size)
+    ids = ids.to(plain.device)
+    user = _encode_users(model, plain, hist, mask, batch_size)
+    skip = torch.where(mask != 0, hist, torch.zeros_like(hist)) if exclude_history else None
+    if plain.device.type == "cuda":
+        rank = evaluate.dot_rank(user, aug, target_pos, target_start, pool=ids, skip=skip)[0].cpu().numpy()
+    else:
+        rank = np.full(len(target_ids), -1, dtype=np.int32)
+        rows = aug.index_select(0, ids)
+        P = int(ids.shape[0])
+        for g0 in range(0, G, max(1, int(batch_size))):
+            g1 = min(G, g0 + max(1, int(batch_size)))
+            t0, t1 = int(target_start[g0]), int(target_start[g1])
+            if t0 == t1:
+                continue
+            S = (rows.repeat(g1 - g0, 1) * user[g0:g1].repeat_interleave(P, dim=0)).sum(dim=1).view(g1 - g0, P)
+            rank[t0:t1] = evaluate.dot_rank_host(S.numpy(), target_pos[t0:t1], target_start[g0:g1 + 1] - t0, pool=pool,
+                                                 skip=None if skip is None else skip[g0:g1].numpy(), news_num=N)
+    out = evaluate.rank_metrics(rank, target_start, ks)
+    out.update(rank=rank, target_start=target_start, target_ids=target_ids)
+    return out
+
+
 def candidates_csr(news_ids, count):
     """The valid slots of a ``[G,k]`` result (``recommend``'s ``news_ids`` and ``count``) as the per-user lists
     ``util.recommend(candidates=...)`` takes: ``(ids [R] int64 tensor, start [G+1] int64 numpy)`` — NRMS retrieves, DIGAT re-ranks."""

@@ -624,6 +624,30 @@ int digat_dot_topk(const float* users, const float* news, const int64_t* pool, i
 int digat_dot_scores(const float* users, const float* news, const int64_t* pool, int64_t G, int64_t N, int64_t P, int d, float* out,
                      void* stream);
 
+/* ---- retrieval evaluation: the rank of given targets in a user's whole ordered pool (digat_amd.nrms.retrieval_metrics) ---------
+ * users, news, pool, G, N, P, d, skip, skip_len: digat_dot_topk's, and so are the elements of user g (the pool positions whose id
+ * lies in [0, N) and is not in skip[g]; repeated ids are distinct elements, skip rows may repeat ids), their scores (the bits
+ * digat_dot_scores stores) and their order (topk_key descending, ties by pool position, NaNs last, -0.0 == +0.0).
+ * target_pos [T] int64: pool positions; target_start [G + 1] int64, non-decreasing from 0 to T, on the DEVICE: user g owns targets
+ * [start[g], start[g+1]) — none, one or many, repeated positions allowed (values are held inside [0, T] and made non-decreasing
+ * before use: a malformed array gives wrong numbers, no access outside the arrays).
+ * out_rank [T] int32 = the number of elements of the target's user that order before the target, or -1 when the target is no
+ * element of its user (position outside [0, P), id outside [0, N), id skipped); out_scores [T] f32 = the target's score bits, or a
+ * NaN where the rank is -1: every output byte is written.  For any k <= 128, 0 <= rank < k exactly when digat_dot_topk's list of
+ * that user holds the element at slot rank; the ranks of all elements of a user are a permutation of 0 .. elements - 1.
+ * DIGAT_ERR_ARG: a null required pointer (pool, skip and — for T == 0 — workspace may be NULL), a negative size, d <= 0, skip_len
+ * outside [0, 256], pool == NULL with P != N, a workspace that is not 8-byte aligned; DIGAT_ERR_SHAPE:
+ * ceil(G / DIGAT_DOT_TOPK_USERS) * ceil(P / DIGAT_DOT_TOPK_CHUNK) or T at or beyond 2^31; DIGAT_ERR_WORKSPACE: a short workspace
+ * (it may hold anything on entry) — all before any launch.  T == 0 or G == 0 returns DIGAT_OK without a launch (nobody owns a
+ * target when G == 0: nothing is written); P == 0 makes every rank -1.  Workspace: 4 bytes per target.  Stream-ordered: three
+ * launches on `stream` (one thread per target; one workgroup per tile of DIGAT_DOT_TOPK_USERS users for the targets' own scores; one
+ * per tile and chunk of DIGAT_DOT_TOPK_CHUNK positions, which returns at once for a tile without targets); no allocation, no host
+ * synchronisation, no read of device memory on the host. */
+size_t digat_dot_rank_workspace_bytes(int64_t users, int64_t pool, int64_t targets);
+int digat_dot_rank(const float* users, const float* news, const int64_t* pool, int64_t G, int64_t N, int64_t P, int d, const int64_t* skip,
+                   int skip_len, const int64_t* target_pos, const int64_t* target_start, int64_t T, int32_t* out_rank, float* out_scores,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- diversified top-k: greedy maximal-marginal-relevance selection over a short list (digat_amd.evaluate.mmr_select) ---------
  * Per user g a list: ids [G, M] int64, scores [G, M] f32, count [G] int32 (the entries in use, held inside [0, M]; NULL: M) — the
  * triple digat_topk_segments and digat_dot_topk write.  vectors [N, d] f32, rows taken as they are (callers pass unit rows).

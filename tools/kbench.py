@@ -28,6 +28,12 @@
                                              against torch.matmul + evaluate.topk_segments and torch.matmul + torch.topk, G = 64 and
                                              4 096 users x 65 237 news, d = 400, k = 10 and 100, the three legs in turn, median
                                              [min, max] of five rounds; then nrms.recommend for 4 096 users end to end
+  python tools/kbench.py dot-rank [news_num d]   retrieval evaluation: evaluate.dot_rank (fused inner product + rank of given targets,
+                                             no score matrix) against the same ranks from evaluate.dot_scores or torch.matmul over
+                                             chunks of 1 024 users + torch compares and sums with the skip mask, G = 64 and 4 096
+                                             users x 65 237 news, d = 400, one and five targets per user, the legs in turn, median
+                                             [min, max] of five rounds, time and peak device bytes; then nrms.retrieval_metrics for
+                                             4 096 users end to end
   python tools/kbench.py diversify [news_num d]   diversified top-k: evaluate.mmr_select (one launch, the Gram in LDS) against gather +
                                              torch.bmm + k rounds of torch element-wise ops and arg-max, G = 64 and 4 096 lists of
                                              M = 128, d = 400, k = 10 and 100, with and without a cap of 2 per category, the legs in
@@ -983,6 +989,109 @@ def bench_dot_topk(news_num=65238, d=400, rounds=5):
           f"of which dot_topk with the pool and {H}-entry skip rows {sel:.3f} ms", flush=True)
 
 
+def matrix_ranks(users, table, pos, skip_pos, product, chunk=1024):
+    """The ranks of ``evaluate.dot_rank`` built from what the tree had before it: per chunk of users the [chunk, P] score matrix
+    (``product(users, table)``), then torch compares and sums against every target's own score with the skip mask.  ``pos`` [G, t]
+    target positions, ``skip_pos`` [G, L] skipped positions.  Plain float compares: NaNs and signed zeros are not the
+    contract's (there are none in the benchmark's data)."""
+    G, P = users.shape[0], table.shape[0]
+    where = torch.arange(P, device=users.device)[None, :]
+    out = torch.empty(pos.shape, dtype=torch.int32, device=users.device)
+    for g0 in range(0, G, chunk):
+        S = product(users[g0:g0 + chunk], table)
+        sp = skip_pos[g0:g0 + chunk]
+        elem = torch.ones(S.shape, dtype=torch.bool, device=S.device)
+        elem.scatter_(1, sp, False)
+        for j in range(pos.shape[1]):
+            q = pos[g0:g0 + chunk, j:j + 1]
+            own = S.gather(1, q)
+            before = ((S > own) | ((S == own) & (where < q))) & elem
+            out[g0:g0 + chunk, j] = torch.where(elem.gather(1, q)[:, 0], before.sum(dim=1), torch.full_like(q[:, 0], -1)).to(torch.int32)
+    return out
+
+
+def bench_dot_rank(news_num=65238, d=400, rounds=5):
+    """``evaluate.dot_rank`` (the fused inner-product + rank-of-target kernel: no score matrix) against the same ranks built from
+    what the tree had before it — the [1 024, P] score matrix per chunk of users from ``evaluate.dot_scores`` (same bits: the ranks
+    must be equal) or ``torch.matmul`` (near-ties may differ), then torch compares and sums with the skip mask (``matrix_ranks``) —
+    in one process, the three legs taken in turn, median [min, max] of ``rounds`` rounds, and each leg's peak of device bytes
+    beyond its inputs; G in {64, 4 096} users against all but the PAD row of a MIND-small-sized table, one and five targets per
+    user, 50-entry skip rows.  Then ``nrms.retrieval_metrics`` for 4 096 users end to end."""
+    import time
+    import types
+    from digat_amd import evaluate, nrms, synthetic
+    dev = torch.device("cuda:0")
+    L = _lib.lib()
+    g = torch.Generator(device="cpu").manual_seed(0)
+    news = torch.randn(news_num, d, generator=g).to(dev)
+    P = news_num - 1
+    table = news[1:].contiguous()
+    stat = lambda v: (sorted(v)[len(v) // 2], min(v), max(v))
+
+    def peak(fn):
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        out = fn()
+        torch.cuda.synchronize()
+        return out, torch.cuda.max_memory_allocated() - base
+    print(f"dot-rank: P = {P} news, d = {d}, 50-entry skip rows; ms per call, median [min, max] of {rounds} rounds", flush=True)
+    for G in (64, 4096):
+        users = torch.randn(G, d, generator=g).to(dev)
+        skip_pos = torch.randint(1, P, (G, 50), generator=g).to(dev)
+        for per in (1, 5):
+            pos = torch.randint(0, P, (G, per), generator=g).to(dev)
+            start = np.arange(G + 1, dtype=np.int64) * per
+            flat = pos.reshape(-1).contiguous()
+            fused = lambda: evaluate.dot_rank(users, table, flat, start, skip=skip_pos)[0]      # no pool: the id is the position
+            via_scores = lambda: matrix_ranks(users, table, pos, skip_pos, evaluate.dot_scores)
+            via_matmul = lambda: matrix_ranks(users, table, pos, skip_pos, lambda u, t: torch.matmul(u, t.t()))
+            (got, pa), (want, pb), (near, pc) = peak(fused), peak(via_scores), peak(via_matmul)
+            exact = bool(torch.equal(got.view(G, per), want))
+            close = float((got.view(G, per) == near).float().mean())
+            times = ([], [], [])
+            for _ in range(rounds):
+                for leg, fn in zip(times, (fused, via_scores, via_matmul)):
+                    leg.append(timeit(fn, iters=3, warm=1)[0])
+            (a, alo, ahi), (b, blo, bhi), (c, clo, chi) = (stat(t) for t in times)
+            ws = int(L.digat_dot_rank_workspace_bytes(G, P, G * per))
+            print(f"  G = {G:5d}, {per} target(s) per user: dot_rank {a:8.3f} ms [{alo:.3f}, {ahi:.3f}] ({2.0 * G * P * d / a / 1e9:6.1f} TFLOP/s, "
+                  f"workspace {ws} B, peak {pa / 2**20:.2f} MiB) | dot_scores + torch {b:8.3f} ms [{blo:.3f}, {bhi:.3f}] (x{b / a:.2f}, peak "
+                  f"{pb / 2**20:.1f} MiB) | matmul + torch {c:8.3f} ms [{clo:.3f}, {chi:.3f}] (x{c / a:.2f}, peak {pc / 2**20:.1f} MiB) | "
+                  f"ranks equal to the dot_scores leg's: {exact}, share equal to the matmul leg's: {close:.4f}", flush=True)
+            del got, want, near
+        del users, skip_pos
+        torch.cuda.empty_cache()
+    G, H, Lw, V = 4096, 50, 32, 30000
+    m = _nrms_model("NRMS", V=V, Lw=Lw, H=H).eval()
+    text, mask = synthetic.make_titles(news_num, Lw, V, seed=2)
+    length = torch.randint(0, H + 1, (G, 1), generator=g)
+    hist_mask = torch.arange(H)[None, :] < length
+    hist = torch.randint(1, news_num, (G, H), generator=g) * hist_mask
+    corpus = types.SimpleNamespace(title_text=torch.from_numpy(text).to(dev), title_mask=torch.from_numpy(mask).to(dev),
+                                   augmented_title_text=None, augmented_title_mask=None, history_ids=hist.to(dev), history_mask=hist_mask.to(dev))
+    who = np.arange(G)
+    targets = (torch.randint(1, news_num, (G,), generator=g).numpy(), np.arange(G + 1, dtype=np.int64))
+    res = nrms.retrieval_metrics(m, corpus, who, targets=targets)
+    torch.cuda.synchronize()
+    secs = []
+    for _ in range(rounds):
+        t0 = time.perf_counter()
+        nrms.retrieval_metrics(m, corpus, who, targets=targets)
+        torch.cuda.synchronize()
+        secs.append(time.perf_counter() - t0)
+    med, lo, hi = stat(secs)
+    vec = nrms.user_vectors(m, corpus, who)
+    _, aug = nrms.news_caches(m, corpus.title_text, corpus.title_mask, None, None, 4096)
+    pool = torch.arange(1, news_num, dtype=torch.int64, device=dev)
+    tpos = torch.from_numpy(targets[0] - 1).to(dev)
+    sel, _ = timeit(lambda: evaluate.dot_rank(vec, aug, tpos, targets[1], pool=pool, skip=corpus.history_ids), iters=5, warm=1)
+    print(f"  nrms.retrieval_metrics, {G} users x {P} news, one target each, history excluded: {med:.3f} s [{lo:.3f}, {hi:.3f}] "
+          f"({G / med:.0f} users/s), of which dot_rank with the pool and {H}-entry skip rows {sel:.3f} ms; recall@128 {res['recall@128']:.4f}, "
+          f"median rank {res['median_rank']:.0f}, not ranked {res['not_ranked']}", flush=True)
+
+
 def torch_mmr(ids, scores, count, vectors, k, lam, category=None, q=0):
     """Greedy maximal-marginal relevance built only from stock PyTorch: gather, ``torch.bmm``, then k rounds of element-wise ops and
     arg-max over all lists at once.  Every id is taken to lie in the table; NaN scores and the order among tied values are not the
@@ -1122,6 +1231,8 @@ if __name__ == "__main__":
         bench_recommend(*nums)
     elif what == "dot-topk":
         bench_dot_topk(*nums)
+    elif what == "dot-rank":
+        bench_dot_rank(*nums)
     elif what == "diversify":
         bench_diversify(*nums)
     elif what == "linear":
