@@ -417,16 +417,18 @@ struct FoldedPass {
             // P' = K1 (the groups' P0) + K3 (this layer's r_user) is formed inside the kernel: nothing is expanded
             // live centres only (the list of the adjacency pass), P / Q / h / X read through the group index
             const bool l0_live = pl.want_live && live.flags;
-            SparseArgs sg{P0, Q0, h0, pl.xu0_grouped ? Xg0 : w.Xu[0], lu.a, c.Au, w.Xu[1], r_user, c.row_group, l0_live ? live.flags : nullptr,
-                          pl.sparse_mode == DIGAT_XATTN_AUTO ? sparse_flag : nullptr, B, U, d / 4, (pl.xu0_grouped || pl.xu0_shared) ? 1 : 0,
-                          (!l0_live && pl.xu0_grouped && pl.want_live) ? (const uint8_t*)pend.flags : nullptr, w.Xu[0],
-                          l0_live ? live.rowidx : nullptr, l0_live ? live.nrows : nullptr, G, nullptr, 0, 0};
-            if (pl.l0_chunked && l0_live && sparse_l0_ok(sg)) {
-                // R rows of an impression per wave: every neighbour row fetched serves R rows (xattn_sparse_l0_kernel; same bits)
-                rc = launch_sparse_l0(sg, pl.shared ? c.run_lead : w.l0_lead, w.l0_idx, w.l0_off + B,
-                                      pl.shared ? (B + SPARSE_L0_ROWS - 1) / SPARSE_L0_ROWS : G, st);
-            } else
-                rc = launch_sparse(sg, st);
+            SparseArgs sg = sparse_args(P0, Q0, h0, pl.xu0_grouped ? Xg0 : w.Xu[0], lu.a, c.Au, w.Xu[1], B, U, d / 4);
+            sg.radd = r_user; sg.group = c.row_group; sg.G = G;
+            sg.xgroup = (pl.xu0_grouped || pl.xu0_shared) ? 1 : 0;
+            if (l0_live) { sg.live = live.flags; sg.rowidx = live.rowidx; sg.nrows_dev = live.nrows; }
+            if (pl.sparse_mode == DIGAT_XATTN_AUTO) sg.run_if = sparse_flag;
+            if (!l0_live && pl.xu0_grouped && pl.want_live) sg.fill_flags = (const uint8_t*)pend.flags;
+            sg.fill_out = w.Xu[0];
+            // R rows of an impression per wave: every neighbour row fetched serves R rows (xattn_sparse_l0_kernel; same bits)
+            const Eq8L0Route l0 = (pl.l0_chunked && l0_live) ? eq8_l0_route(sparse_in(sg), pl.shared ? (B + SPARSE_L0_ROWS - 1) / SPARSE_L0_ROWS : G)
+                                                             : Eq8L0Route();
+            if (l0.eligible) rc = launch_sparse_l0(sg, l0.launch, pl.shared ? c.run_lead : w.l0_lead, w.l0_idx, w.l0_off + B, st);
+            else rc = launch_sparse(sg, st);
         }
         if (rc || !pl.l0_dense) return rc;
         const int* skip_if = pl.l0_sparse ? sparse_flag : nullptr;      // both arms: the device's decision picks one
@@ -438,7 +440,9 @@ struct FoldedPass {
                                c.row_group, (float4*)P, (long)B, U, d / 4, skip_if);
             DIGAT_CHECK_LAUNCH();
         }
-        return launch_xattn_pairwise(P, Q0, h0, w.Xu[0], lu.a, c.Au, w.Xu[1], w.xu.alpha, B, U, d, st, nullptr, c.row_group, nullptr, true, skip_if);
+        PairOpts po;
+        po.group = c.row_group; po.skip_if = skip_if;
+        return launch_xattn_pairwise(P, Q0, h0, w.Xu[0], lu.a, c.Au, w.Xu[1], w.xu.alpha, B, U, d, st, po);
     }
 
     // A per-row layer of the user graph: every layer projects, scores and writes the live nodes only (layer 0 too: see publish)
@@ -487,8 +491,10 @@ struct FoldedPass {
         if (pl.news_early) {     // small graphs, projections already done (news_projection): K3 joins in the score kernel
             // layer 0 with news_index: h | P | Q and the nodes themselves are the per-news TABLES, read in place through the index
             const float* hn = cached ? c.news_hpq0 : w.xn.h;
-            return launch_xattn_pairwise(hn + plane, hn + 2 * plane, hn, Xn_in, ln.a, c.An, Xn_out, w.xn.alpha, B, N, d, sn, nullptr, nullptr,
-                                         w.r_news, false, nullptr, indexed ? c.news_index : nullptr);
+            PairOpts po;
+            po.radd = w.r_news; po.alpha_wanted = false;
+            if (indexed) po.bindex = c.news_index;
+            return launch_xattn_pairwise(hn + plane, hn + 2 * plane, hn, Xn_in, ln.a, c.An, Xn_out, w.xn.alpha, B, N, d, sn, po);
         }
         if (indexed) {
             // Larger news graphs, layer 0 from the per-news TABLES: [h | P | Q] of a news graph depend on the news alone, so
@@ -497,8 +503,10 @@ struct FoldedPass {
             // and adding K3 in the kernel, in the GEMM epilogue's order (K3 + K1): the bits of the in-batch launch.
             hipLaunchKernelGGL(index_to_i32_kernel, dim3((B + 255) / 256), dim3(256), 0, sn, c.news_index, w.idx32, B);
             DIGAT_CHECK_LAUNCH();
-            SparseArgs sgn{c.news_hpq0 + plane, c.news_hpq0 + 2 * plane, c.news_hpq0, Xn_in, ln.a, c.An, Xn_out, w.r_news, w.idx32, news_flags,
-                           nullptr, B, N, d / 4, 1, nullptr, nullptr, news_rowidx, news_nrows, B, nullptr, 0, 0};      // G (profiling: distinct rows behind the index): at most B candidates
+            SparseArgs sgn = sparse_args(c.news_hpq0 + plane, c.news_hpq0 + 2 * plane, c.news_hpq0, Xn_in, ln.a, c.An, Xn_out, B, N, d / 4);
+            sgn.radd = w.r_news; sgn.group = w.idx32; sgn.xgroup = 1;
+            sgn.G = B;                      // profiling, the distinct rows behind the index: at most B candidates
+            sgn.live = news_flags; sgn.rowidx = news_rowidx; sgn.nrows_dev = news_nrows;
             if (news_rowidx) sgn.prof_part = XPART_NEWS + 1;
             return launch_sparse(sgn, sn);
         }

@@ -5,17 +5,9 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "../../include/digat_hip.h"
+#include "digat_xattn_plan.h"      // the Eq. 8 kernel eligibilities (eq8_*): the plan and the launch routes ask the same questions
 
 enum { ENC_PLAIN, ENC_GROUPED, ENC_SHARED };      // the public entry: per-row users, users per group, per-row users with runs found
-
-// ---- Eq. 8 kernel eligibilities (the plan and xattn_core ask the same questions) ------------------------------------------------
-// the wave-per-centre sparse kernel and the small-graph kernels hold a row as at most four float4 pieces per lane
-static inline bool eq8_row_fits_wave(int d) { return d / 4 <= 256; }
-// the layer-0 chunk kernel and the twin kernel keep several centres per wave: two float4 pieces per lane, one adjacency word pair
-static inline bool eq8_multi_centre_fits(int d, int n) { return d / 4 <= 128 && n <= 128; }
-// graphs the sparse kernel serves: up to 16 nodes belong to the small-graph kernels (the graph in LDS, a workgroup per graph)
-static inline bool eq8_sparse_graph(int n) { return n > 16; }
-static inline bool eq8_small_graph(int n) { return n <= 16; }
 
 // ---- the operand formats of a weight version ------------------------------------------------------------------------------------
 // fmt: the format every wsplit image of the parameters was split in; lfmt: the layers' [W|ffn1|ffn2] images (fp16-fp8c under

@@ -80,7 +80,7 @@ int digat_gat_fwd(const float* X, const uint8_t* A, const float* W, const float*
     DIGAT_CHECK_LAUNCH();
     hipLaunchKernelGGL(gat_alpha_kernel, dim3((unsigned)((nodes + 3) / 4)), dim3(256), 0, st, (const float*)o.s1, (const float*)o.s2, A, o.alpha, (float*)nullptr, nodes, n);
     DIGAT_CHECK_LAUNCH();
-    return launch_agg_1024(AggArgs{o.alpha, o.h, X, out, B, n, d, (d + 63) / 64, n | 1, nullptr, nullptr, nullptr}, st);
+    return launch_agg(agg_args(o.alpha, o.h, X, out, B, n, d), eq8_agg_route(B, n, d, true, EQ8_UNGUARDED), st);
 }
 
 }  // extern "C"
@@ -174,7 +174,7 @@ int digat_gat_fwd_train(const float* X, const uint8_t* A, const float* W, const 
         T_TRY(digat_dropout_fwd(s.alpha, o.adrop, s.amask, (int64_t)B * n * n, p_alpha, seed, stream));
         aggalpha = o.adrop;
     }
-    return launch_agg_1024(AggArgs{aggalpha, s.h, X, out, B, n, d, (d + 63) / 64, n | 1, nullptr, nullptr, nullptr}, st);
+    return launch_agg(agg_args(aggalpha, s.h, X, out, B, n, d), eq8_agg_route(B, n, d, true, EQ8_UNGUARDED), st);
 }
 
 // dX [B,n,d], dW [d,d], dbW [d], da1 da2 [d]: all written (not accumulated)

@@ -18,7 +18,8 @@
 //   digat_dot_topk.inc  inner-product retrieval: fp32 matrix-core product fused with the top-k selection of digat_topk.inc
 //   digat_dot_rank.inc  retrieval evaluation: the same product fused with the rank of given targets in the whole pool
 // This file: shared helpers, the per-kernel profiler, and the C ABI.  The encoder's orchestration is digat_encoder.inc (host
-// code only), and every decision of an encoder call is made in digat_encoder_plan.h (plain C++).
+// code only), and every decision of an encoder call is made in digat_encoder_plan.h, every launch decision of Eq. 8 in
+// digat_xattn_plan.h, every one of the GEMM in digat_gemm_plan.h (plain C++, pinned by CPU tests).
 //
 // gfx950 only: 64-wide wavefronts, 160 KiB LDS per CU, MFMA f32 16x16x4.  No CUDA shims.
 #include <hip/hip_runtime.h>
@@ -28,11 +29,13 @@
 #include <atomic>
 #include <initializer_list>
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 #include <utility>
 
 #include "../../include/digat_hip.h"
 #include "digat_encoder_plan.h"
+#include "digat_xattn_plan.h"
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 
@@ -200,10 +203,8 @@ __device__ __forceinline__ void wait_vmcnt(int n) {      // n is wave-uniform
 }
 
 // Round 5: TWO twins per wave at five waves per SIMD (94 registers) instead of four at four (114): 280 against 305 us per 4 096-row
-// launch alone, 460-510 against 535-570 inside the overlapped region (tools/exp/ab.py, alternating runs; three at five waves spill)
-#ifndef DIGAT_TWIN_R
-#define DIGAT_TWIN_R 2
-#endif
+// launch alone, 460-510 against 535-570 inside the overlapped region (tools/exp/ab.py, alternating runs; three at five waves spill):
+// DIGAT_TWIN_R = 2 (digat_xattn_plan.h, with the twin kernel's grid)
 // leaky_relu(0.2) of a WAVE-UNIFORM score (a wave_sum result): e > 0 ? e : 0.2 e = max(e, 0.2 e), bit for bit (also for -0, inf, NaN),
 // as one multiply and one v_max_f32 with the score as the scalar operand (fmaxf costs a third instruction that canonicalises e)
 __device__ __forceinline__ float leaky02_uniform(float e) {
@@ -333,18 +334,23 @@ static int xattn_core(const float* X, const uint8_t* A, const float* r_given,
     if (rc) return rc;
     const int* skip_if = nullptr;
     if (sparse_mode != DIGAT_XATTN_DENSE && sparse_fits) {
-        SparseArgs sg{P, Q, h, X, a, A, out, nullptr, nullptr, listed ? live : nullptr,
-                      sparse_mode == DIGAT_XATTN_AUTO ? o.sparse_flag : nullptr, B, n, d / 4, 0, nullptr, nullptr,
-                      listed && live ? rowidx : nullptr, listed && live ? nrows_dev : nullptr, 0, nullptr, pq8 ? 2 : (pq16 ? 1 : 0), o.centre_limit};
+        SparseArgs sg = sparse_args(P, Q, h, X, a, A, out, B, n, d / 4);
+        if (listed) sg.live = live;
+        if (listed && live) { sg.rowidx = rowidx; sg.nrows_dev = nrows_dev; }
+        if (sparse_mode == DIGAT_XATTN_AUTO) sg.run_if = o.sparse_flag;
+        sg.pq16 = pq8 ? 2 : (pq16 ? 1 : 0);
         sg.ld8 = pq8 ? ld8 : 0;
+        sg.centre_limit = o.centre_limit;
         sg.prof_part = o.prof_part;
         if (o.tw && listed && live) { sg.twin = o.tw->word; sg.twlist = o.tw->list; sg.twcount = o.tw->count; }
         const int rcs = launch_sparse(sg, st);
         if (rcs || sparse_mode == DIGAT_XATTN_SPARSE) return rcs;
         skip_if = o.sparse_flag;
     }
-    return launch_xattn_pairwise(P, Q, h, X, a, A, out, alpha, B, n, d, st, listed ? live : nullptr, nullptr, nullptr,
-                                 alpha_out != nullptr, skip_if);
+    PairOpts po;
+    if (listed) po.live = live;
+    po.alpha_wanted = alpha_out != nullptr; po.skip_if = skip_if;
+    return launch_xattn_pairwise(P, Q, h, X, a, A, out, alpha, B, n, d, st, po);
 }
 
 // the xattn entries: r = ctx F3^T + b3 (K3) into the workspace's r, then the layer
@@ -395,7 +401,8 @@ int digat_xattn_fwd_lowprec(const float* X, const uint8_t* A, const float* ctx,
         return DIGAT_ERR_ARG;
     if (!X || !A || !ctx || !W || !F1 || !F2 || !F3 || !a || !wsplit || !out || !workspace) return DIGAT_ERR_ARG;
     if (B < 0 || n <= 0 || d <= 0) return DIGAT_ERR_ARG;
-    if (d % 80 || d > 1024 || n <= 16 || n > DIGAT_MAX_NODES || (long)B * n < 2048) return DIGAT_ERR_SHAPE;
+    // the low-precision rows are the sparse kernel's alone, written by the strip-mined projection (whole 80-column strips, from 2 048 rows)
+    if (d % 80 || !eq8_row_fits_wave(d) || !eq8_sparse_graph(n) || n > DIGAT_MAX_NODES || (long)B * n < 2048) return DIGAT_ERR_SHAPE;
     XattnOpts o;
     o.wsplit = wsplit; o.sparse_mode = DIGAT_XATTN_SPARSE; o.pq_mode = pq == 1 ? 1 : (pq == 2 ? 4 : 0); o.gemm_format = format;
     return xattn_fwd_k3(X, A, ctx, W, bW, F1, F2, F3, b3, a, out, nullptr, B, n, d, workspace, workspace_bytes, stream, o);

@@ -1602,50 +1602,61 @@ int digat_topic_pool_bwd(const float* Xu, const float* kq, const int64_t* cat_id
 // training forward of the pairwise part: like digat_xattn_pairwise_fwd but keeps what the backward needs:
 // alpha [B,n,n] (before dropout), s_pre [B,n,n] (scores before leaky_relu/mask), and applies the attention
 // dropout (amask [B,n,n] written; p = 0 -> no dropout, amask may be NULL).
-// sparse_flag != NULL (a device int of the caller's scratch): graphs of more than 16 nodes take the wave-per-centre kernel when a
-// sample of the batch's adjacency is sparse (decided on the device: the dense pair then returns at once, and vice versa).
-// mode (DIGAT_TRAIN_XATTN_*): 0 = that device-side choice; 1 = the entry-wise kernel, 2 = the all-pairs pair, unguarded — a caller
-// that knows its corpus (digat_amd: the encoder's corpus hint) saves the decision launch and the launches that return at once.
-// The choice is one of speed only: both sides compute the same function.
+// Which kernels run is eq8_train_fwd_route's decision (digat_xattn_plan.h), from the sizes and the caller's TrainEq8Opts; the choice
+// is one of speed only: both sides compute the same function.
+struct TrainEq8Opts {
+    int* sparse_flag = nullptr;             // a device int of the caller's scratch.  Forward: with mode AUTO, graphs of more than 16 nodes take the
+                                            // wave-per-centre kernel when a sample of the batch's adjacency is sparse (decided on the device: the
+                                            // dense pair then returns at once, and vice versa).  Backward: the forward's choice, read there.
+    int mode = DIGAT_TRAIN_XATTN_AUTO;      // _AUTO = that device-side choice; _SPARSE = the entry-wise kernels, _DENSE = the all-pairs kernels,
+                                            // unguarded — a caller that knows its corpus (digat_amd: the encoder's corpus hint) saves the decision
+                                            // launch and the launches that return at once.  A hint: see eq8_train_bwd_route
+    float* dr = nullptr;                    // backward only: [B,d], the gradient of K3 (the node sums of dP')
+};
 static int xattn_pairwise_fwd_train_flag(const float* Pr, const float* Q, const float* h, const float* X, const float* a,
                                         const uint8_t* A, float* out, float* alpha, float* s_pre, float* alpha_drop,
-                                        uint8_t* amask, float p, uint32_t seed, int B, int n, int d, int* sparse_flag, void* stream,
-                                        int mode = 0) {
+                                        uint8_t* amask, float p, uint32_t seed, int B, int n, int d, void* stream,
+                                        const TrainEq8Opts& o = TrainEq8Opts()) {
     if (!Pr || !Q || !h || !X || !a || !A || !out || !alpha || !s_pre) return DIGAT_ERR_ARG;
     if (p > 0.f && (!alpha_drop || !amask)) return DIGAT_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    XattnPlan pl;
-    int rc = plan_xattn(B, n, d, &pl);
-    if (rc) return rc;
-    if (B == 0) return DIGAT_OK;
-    pl.g.P = Pr; pl.g.Q = Q; pl.g.a = a; pl.g.A = A; pl.g.alpha = alpha; pl.g.s_out = s_pre;
-    // the attention dropout happens where alpha is produced (round 6: one dropout launch per layer and graph less); graphs of at
-    // most 16 nodes (the news graph) are also aggregated there, from registers (no aggregation launch, no dropped copy of alpha)
-    const bool small = n <= 16 && d / 4 <= 256;
-    if (p > 0.f) { pl.g.amask = amask; pl.g.adrop = small ? nullptr : alpha_drop; pl.g.drop_p = p; pl.g.drop_seed = seed; }
-    if (small) { pl.g.agg_h = h; pl.g.agg_x = X; pl.g.agg_out = out; }
-    const bool eligible = !small && d / 4 <= 256;
-    if (eligible && mode == 1)          // the caller knows the corpus is sparse: the entry-wise kernel alone
-        return launch_sparse_train(Pr, Q, h, X, a, A, out, alpha, s_pre, amask, p, seed, B, n, d, nullptr, st);
-    const bool guarded = eligible && sparse_flag && mode == 0;
+    Eq8TrainIn in = {};
+    in.B = B; in.n = n; in.d = d; in.mode = o.mode; in.flag = o.sparse_flag != nullptr;
+    const Eq8TrainFwdRoute r = eq8_train_fwd_route(in);
+    if (r.status || r.path == EQ8_TRAIN_NOTHING) return r.status;
+    const bool small = r.path == EQ8_TRAIN_SMALL, guarded = r.path == EQ8_TRAIN_GUARDED;
     if (guarded) {
+        hipLaunchKernelGGL(train_sparse_decide_kernel, dim3(1), dim3(1024), 0, st, A, B, n, SPARSE_PER_NODE, o.sparse_flag);
+        DIGAT_CHECK_LAUNCH();
+    }
+    if (r.sparse.kernel != EQ8_NONE) {
         // round 6: the user graph's forward on the sparse kernel (a wave per centre walks its ~9 adjacency entries: score, softmax,
         // dropout and aggregation from registers; the tile kernel + aggregation pair visits all n^2 pairs)
-        hipLaunchKernelGGL(train_sparse_decide_kernel, dim3(1), dim3(1024), 0, st, A, B, n, SPARSE_PER_NODE, sparse_flag);
+        SparseArgs g = sparse_args(Pr, Q, h, X, a, A, out, B, n, d / 4);
+        if (guarded) g.run_if = o.sparse_flag;
+        g.xcd_group = r.sparse.xcd_group;
+        g.t_alpha = alpha; g.t_spre = s_pre; g.t_amask = p > 0.f ? amask : nullptr; g.t_p = p; g.t_seed = seed;
+        launch_sparse_kernel(r.sparse, g, st);
         DIGAT_CHECK_LAUNCH();
-        rc = launch_sparse_train(Pr, Q, h, X, a, A, out, alpha, s_pre, amask, p, seed, B, n, d, sparse_flag, st);
-        if (rc) return rc;
-        pl.g.skip_if = sparse_flag;
+        if (!guarded) return DIGAT_OK;      // the caller knows the corpus is sparse: the entry-wise kernel alone
     }
-    rc = launch_score(pl, st);
+    ScoreArgs g = score_args(r.tile);
+    g.P = Pr; g.Q = Q; g.a = a; g.A = A; g.alpha = alpha; g.s_out = s_pre;
+    // the attention dropout happens where alpha is produced (round 6: one dropout launch per layer and graph less); graphs of at
+    // most 16 nodes (the news graph) are also aggregated there, from registers (no aggregation launch, no dropped copy of alpha)
+    if (p > 0.f) { g.amask = amask; g.adrop = small ? nullptr : alpha_drop; g.drop_p = p; g.drop_seed = seed; }
+    if (small) { g.agg_h = h; g.agg_x = X; g.agg_out = out; }
+    if (guarded) g.skip_if = o.sparse_flag;
+    const int rc = launch_score(r.score, g, st);
     if (rc || small) return rc;
-    const float* aggalpha = p > 0.f ? alpha_drop : alpha;
-    return launch_agg_1024(AggArgs{aggalpha, h, X, out, B, n, d, (d + 63) / 64, n | 1, nullptr, nullptr, guarded ? sparse_flag : nullptr}, st);
+    AggArgs ag = agg_args(p > 0.f ? alpha_drop : alpha, h, X, out, B, n, d);
+    if (guarded) ag.skip_if = o.sparse_flag;
+    return launch_agg(ag, r.agg, st);
 }
 int digat_xattn_pairwise_fwd_train(const float* Pr, const float* Q, const float* h, const float* X, const float* a,
                                    const uint8_t* A, float* out, float* alpha, float* s_pre, float* alpha_drop,
                                    uint8_t* amask, float p, uint32_t seed, int B, int n, int d, void* stream) {
-    return xattn_pairwise_fwd_train_flag(Pr, Q, h, X, a, A, out, alpha, s_pre, alpha_drop, amask, p, seed, B, n, d, nullptr, stream);
+    return xattn_pairwise_fwd_train_flag(Pr, Q, h, X, a, A, out, alpha, s_pre, alpha_drop, amask, p, seed, B, n, d, stream);
 }
 
 // the pairwise backward's scratch.  All-pairs launches: dZ [B,n,d], ds [B,n,n], the rows' da partials [B,d] and their group sums;
@@ -1668,8 +1679,8 @@ size_t digat_xattn_pairwise_bwd_workspace(int B, int n, int d) { Arena a; pair_b
 static int xattn_pairwise_bwd_ld(const float* dOut, const float* out, const float* Xres, const float* Pr, const float* Q,
                                  const float* h, const float* a, const uint8_t* A, const float* alpha, const float* s_pre,
                                  const uint8_t* amask, float p, float* dPr, float* dQ, float* dh, long ldg, float* da, int accumulate_da,
-                                 int B, int n, int d, void* workspace, size_t workspace_bytes, void* stream, float* dr = nullptr,
-                                 const int* sparse_flag = nullptr, int mode = 0) {
+                                 int B, int n, int d, void* workspace, size_t workspace_bytes, void* stream,
+                                 const TrainEq8Opts& opts = TrainEq8Opts()) {
     if (!dOut || !out || !Xres || !Pr || !Q || !h || !a || !A || !alpha || !s_pre || !dPr || !dQ || !dh || !da || !workspace)
         return DIGAT_ERR_ARG;
     if (d % 4 || n > DIGAT_MAX_NODES) return DIGAT_ERR_SHAPE;
@@ -1681,22 +1692,21 @@ static int xattn_pairwise_bwd_ld(const float* dOut, const float* out, const floa
     const float ascale = p > 0.f ? 1.f / (1.f - p) : 1.f;
     const uint8_t* am = p > 0.f ? amask : nullptr;
     // the forward's choice (a device int in its save buffer): the entry-wise pair below when the batch's adjacency is sparse, the three
-    // all-pairs launches otherwise — the launches of the other side return at once
-    const bool eligible = d / 4 <= 128 && dr;
-    // graphs of at most 16 nodes (the news graph): a centre has at most 16 entries whatever the adjacency — always the entry-wise pair
-    // (the all-pairs launches walk 13 channel chunks per row for a 10 x 10 product: 65 us per layer against 20)
-    const bool only_sparse = eligible && (mode == 1 || n <= 16) && mode != 2;   // else the caller's choice (xattn_pairwise_fwd_train_flag): no guards
-    const int* guard = (eligible && !only_sparse && sparse_flag && mode == 0) ? sparse_flag : nullptr;
+    // all-pairs launches otherwise — the launches of the other side return at once (eq8_train_bwd_route: which sides are launched)
+    float* const dr = opts.dr;
+    Eq8TrainIn in = {};
+    in.B = B; in.n = n; in.d = d; in.mode = opts.mode; in.flag = opts.sparse_flag != nullptr; in.dr = dr != nullptr;
+    const Eq8TrainBwdRoute r = eq8_train_bwd_route(in);
+    const bool only_sparse = r.only_sparse;
+    const int* guard = r.guard ? opts.sparse_flag : nullptr;
     const int nblk = (int)spb_blocks(B, n);
-    if (guard || only_sparse) {
+    if (r.sparse.kernel != EQ8_NONE) {
         SpBwdArgs t{dOut, out, Xres, h, Pr, Q, a, A, alpha, s_pre, am, ascale, o.dZ, o.wds, dQ, dh, dPr, ldg, o.dap2, B, n, d / 4, guard};
-        if (d / 4 <= 64) {
-            hipLaunchKernelGGL(xattn_sparse_bwd_centre_kernel<1>, dim3(nblk), dim3(256), 0, st, t);
-            hipLaunchKernelGGL(xattn_sparse_bwd_node_kernel<1>, dim3(nblk), dim3(256), 0, st, t);
-        } else {
-            hipLaunchKernelGGL(xattn_sparse_bwd_centre_kernel<2>, dim3(nblk), dim3(256), 0, st, t);
-            hipLaunchKernelGGL(xattn_sparse_bwd_node_kernel<2>, dim3(nblk), dim3(256), 0, st, t);
-        }
+        eq8_by_width<2>(r.sparse.U, [&](auto u) {
+            constexpr int U = decltype(u)::value;
+            hipLaunchKernelGGL(xattn_sparse_bwd_centre_kernel<U>, dim3(r.sparse.grid), dim3(r.sparse.block), 0, st, t);
+            hipLaunchKernelGGL(xattn_sparse_bwd_node_kernel<U>, dim3(r.sparse.grid), dim3(r.sparse.block), 0, st, t);
+        });
         DIGAT_CHECK_LAUNCH();
     }
     if (only_sparse) {
@@ -1711,13 +1721,11 @@ static int xattn_pairwise_bwd_ld(const float* dOut, const float* out, const floa
     if (rc) return rc;
     {   // dP', dQ, da partials
         PairBwdArgs t{Pr, Q, a, o.ds, dPr, dQ, o.dap, B, n, d, ldg, dr, guard};
-        auto lds_of = [&](int ch) { return ((size_t)3 * n * ch + (size_t)n * n) * 4 + 2 * (((size_t)n * n + 3) & ~(size_t)3) + 2 * (size_t)n * 4; };
-        const int ch = lds_of(64) <= 160 * 1024 ? 64 : 32;
-        const size_t lds = lds_of(ch);
-        auto kern = ch == 64 ? xattn_pair_bwd_kernel<64> : xattn_pair_bwd_kernel<32>;
-        if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   160 * 1024) != hipSuccess) return DIGAT_ERR_LAUNCH;
-        hipLaunchKernelGGL(kern, dim3(B, (d + ch - 1) / ch), dim3(1024), lds, st, t);
+        const Eq8Launch& l = r.pair;
+        auto kern = l.ch == 64 ? xattn_pair_bwd_kernel<64> : xattn_pair_bwd_kernel<32>;
+        if (l.raise_lds && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               160 * 1024) != hipSuccess) return DIGAT_ERR_LAUNCH;
+        hipLaunchKernelGGL(kern, dim3(l.grid, l.grid_y), dim3(l.block), l.lds, st, t);
         DIGAT_CHECK_LAUNCH();
     }
     if (guard) {

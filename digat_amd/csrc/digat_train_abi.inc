@@ -101,8 +101,10 @@ int digat_xattn_fwd_train(const float* X, const uint8_t* A, const float* ctx, co
     else T_TRY(digat_xattn_project(X, s.r, W, bW, F1, F2, s.h, s.Pr, s.Q, B, n, d, st));
     // (s_pre is written on the adjacency's entries only and read, by xattn_ds_kernel, behind the adjacency test only: de = 0 off the
     // entries whatever the slot holds — 0 x (sp > 0 ? 1 : 0.2) — so the rest of the buffer needs no zero-fill: six memsets per step less)
+    TrainEq8Opts eo;
+    eo.sparse_flag = s.sflag; eo.mode = xattn_mode;
     return xattn_pairwise_fwd_train_flag(s.Pr, s.Q, s.h, X, a, A, out, s.alpha, s.s_pre, p_alpha > 0.f ? o.adrop : nullptr,
-                                         p_alpha > 0.f ? s.amask : nullptr, p_alpha, seed, B, n, d, s.sflag, st, xattn_mode);
+                                         p_alpha > 0.f ? s.amask : nullptr, p_alpha, seed, B, n, d, st, eo);
 }
 
 // dX [B,n,d], dctx [B,d], dW dF1 dF2 dF3 [d,d], dbW db3 [d], da [d]: all written (not accumulated)
@@ -137,8 +139,10 @@ int digat_xattn_bwd(const float* dOut, const float* out, const float* X, const u
     const PremadeImage premade(bwd_image);
     if (bwd_image) wcat_split = const_cast<void*>(bwd_image);
     // (dr[b] = sum_j dP'[b,j] — K3 = ctx F3^T + b3 was added to every neighbour-side row — leaves the pairwise backward's launch)
+    TrainEq8Opts eo;
+    eo.sparse_flag = s.sflag; eo.mode = xattn_mode; eo.dr = o.dr;
     T_TRY(xattn_pairwise_bwd_ld(dOut, out, X, s.Pr, s.Q, s.h, a, A, s.alpha, s.s_pre, p_alpha > 0.f ? s.amask : nullptr, p_alpha,
-                                dPr, dQ, dh, ldg, da, 0, B, n, d, o.pws, o.pb, st, o.dr, s.sflag, xattn_mode));
+                                dPr, dQ, dh, ldg, da, 0, B, n, d, o.pws, o.pb, st, eo));
     // projections: dX = dOut (residual) + dh W + dP' F1 + dQ F2 = dOut + G [W; F1; F2]
     if (x3_ok(M, d, 3 * d)) {
         // the stacked weights [W; F1; F2] are split from their three homes

@@ -54,8 +54,27 @@ struct ScoreArgs {
     // kernel aggregates from registers) receives drop_p(alpha)
     uint8_t* amask; float* adrop; float drop_p; unsigned drop_seed;
 };
-constexpr int XA_RING = 3;   // chunk images in the LDS ring
-constexpr int XA_KMAX = 4;   // DMA wave-instructions one wave issues per chunk (upper bound)
+// XA_RING (chunk images in the LDS ring), XA_KMAX (DMA wave-instructions a wave issues per chunk): digat_xattn_plan.h
+
+// the geometry of a tile plan as kernel arguments; the caller adds its pointers by name
+static ScoreArgs score_args(const XattnTile& t) {
+    ScoreArgs g = {};
+    g.B = t.B; g.n = t.n; g.d = t.d; g.d4 = t.d4;
+    g.NT = t.NT; g.SN = t.SN; g.CC4 = t.CC4; g.nchunks = t.nchunks; g.RB = t.RB;
+    g.img_slots = t.img_slots; g.ring_slots = t.ring_slots; g.ninstr = t.ninstr;
+    g.am_off = t.am_off; g.a_off = t.a_off; g.tl_off = t.tl_off; g.ld_off = t.ld_off; g.pm_off = t.pm_off;
+    return g;
+}
+// A route's width class as a template parameter: f(std::integral_constant<int, U>) for U = 1, 2, and 4 where MAXU = 4 (the kernels
+// that keep several centres per wave, and the entry-wise backward, have no instantiation at four pieces per lane)
+template <int MAXU, class F>
+static inline void eq8_by_width(int U, F&& f) {
+    switch (U) {
+        case 1: f(std::integral_constant<int, 1>()); break;
+        case 2: f(std::integral_constant<int, 2>()); break;
+        case 4: if constexpr (MAXU >= 4) f(std::integral_constant<int, 4>()); break;
+    }
+}
 
 
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(5, 8))) xattn_score_kernel(const ScoreArgs g) {
@@ -939,26 +958,6 @@ __global__ void __launch_bounds__(1024) train_sparse_decide_kernel(const uint8_t
         *flag = tot <= per_node * rows * n ? 1 : 0;
     }
 }
-// the training forward of Eq. 8 on the wave-per-centre kernel, guarded by *run_if
-static int launch_sparse_train(const float* Pr, const float* Q, const float* h, const float* X, const float* a, const uint8_t* A, float* out,
-                               float* alpha, float* s_pre, uint8_t* amask, float p, unsigned seed, int B, int n, int d, const int* run_if,
-                               hipStream_t st) {
-    SparseArgs g;
-    memset(&g, 0, sizeof(g));
-    g.P = Pr; g.Q = Q; g.h = h; g.X = X; g.a = a; g.A = A; g.out = out; g.B = B; g.n = n; g.d4 = d / 4; g.run_if = run_if;
-    g.t_alpha = alpha; g.t_spre = s_pre; g.t_amask = p > 0.f ? amask : nullptr; g.t_p = p; g.t_seed = seed;
-    if (g.n > 128 || g.d4 > 256) return DIGAT_ERR_SHAPE;
-    unsigned blocks = (unsigned)(((long)B * n + 3) / 4);
-    if (run_if && blocks > 8192u) blocks = 8192u;
-    g.xcd_group = 16;
-    blocks = (blocks + 127u) / 128u * 128u;        // whole windows of 8 x 16 workgroups
-    if (g.d4 <= 64) hipLaunchKernelGGL((xattn_sparse_kernel<1, 0, false, true>), dim3(blocks), dim3(256), 0, st, g);
-    else if (g.d4 <= 128) hipLaunchKernelGGL((xattn_sparse_kernel<2, 0, false, true>), dim3(blocks), dim3(256), 0, st, g);
-    else hipLaunchKernelGGL((xattn_sparse_kernel<4, 0, false, true>), dim3(blocks), dim3(256), 0, st, g);
-    DIGAT_CHECK_LAUNCH();
-    return DIGAT_OK;
-}
-
 // ---- layer 0 of grouped rows: R rows of one impression per wave ------------------------------------------------------------------
 // At layer 0 the rows of an impression share everything but K3: P, Q, h and the nodes X exist once per GROUP, the adjacency and
 // the live centres are the group's.  The wave-per-centre kernel above still fetched the ~9 neighbour rows of P and of h once per
@@ -1368,9 +1367,7 @@ __device__ __forceinline__ void xattn_sparse_twin_chunk(const SparseArgs& g, con
 #ifndef DIGAT_TWIN_WAVES
 #define DIGAT_TWIN_WAVES (DIGAT_TWIN_R <= 2 ? 5 : 4)   // TWIN_R = 2: 94 registers, five waves per SIMD; 4: 114 registers, four (five would spill 10)
 #endif
-#ifndef DIGAT_TWIN_WPG
-#define DIGAT_TWIN_WPG 4                               // waves per workgroup
-#endif
+// DIGAT_TWIN_WPG (waves per workgroup): digat_xattn_plan.h, with the grid
 template <int U, int R>
 __global__ void __launch_bounds__(64 * DIGAT_TWIN_WPG, U <= 2 ? DIGAT_TWIN_WAVES : 1) xattn_sparse_twin_kernel(const SparseArgs g) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1499,77 +1496,69 @@ extern "C" int digat_debug_sparse_timers(double* out9) {
     return DIGAT_OK;
 }
 #endif
+// SparseArgs with its mandatory fields; everything optional is off until the caller sets it by name
+static SparseArgs sparse_args(const float* P, const float* Q, const float* h, const float* X, const float* a, const uint8_t* A, float* out,
+                              int B, int n, int d4) {
+    SparseArgs g = {};
+    g.P = P; g.Q = Q; g.h = h; g.X = X; g.a = a; g.A = A; g.out = out; g.B = B; g.n = n; g.d4 = d4;
+    return g;
+}
+// what the routes of digat_xattn_plan.h ask about a launch: its sizes, and which optional fields were passed
+static Eq8SparseIn sparse_in(const SparseArgs& g) {
+    Eq8SparseIn in = {};
+    in.B = g.B; in.n = g.n; in.d4 = g.d4;
+    in.radd = g.radd != nullptr; in.group = g.group != nullptr; in.xgroup = g.xgroup != 0; in.live = g.live != nullptr;
+    in.run_if = g.run_if != nullptr; in.fill_flags = g.fill_flags != nullptr; in.rowidx = g.rowidx != nullptr; in.nrows_dev = g.nrows_dev != nullptr;
+    in.twin = g.twin && g.twlist && g.twcount;
+    in.pq16 = g.pq16; in.centre_limit = g.centre_limit; in.ld8 = g.ld8;
+    return in;
+}
+// every launch of xattn_sparse_kernel: the route's instantiation on the route's grid
+static void launch_sparse_kernel(const Eq8Launch& l, const SparseArgs& g, hipStream_t st) {
+    eq8_by_width<4>(l.U, [&](auto u) {
+        constexpr int U = decltype(u)::value;
+        const dim3 grid(l.grid), block(l.block);
+        if (l.train) hipLaunchKernelGGL((xattn_sparse_kernel<U, 0, false, true>), grid, block, 0, st, g);
+        else if (l.pq16 == 2) hipLaunchKernelGGL((xattn_sparse_kernel<U, 2, false>), grid, block, 0, st, g);
+        else if (l.pq16 == 1) hipLaunchKernelGGL((xattn_sparse_kernel<U, 1, false>), grid, block, 0, st, g);
+        else if (l.radd) hipLaunchKernelGGL((xattn_sparse_kernel<U, 0, true>), grid, block, 0, st, g);
+        else hipLaunchKernelGGL((xattn_sparse_kernel<U, 0, false>), grid, block, 0, st, g);
+    });
+}
+// the sparse arm of an inference layer: the twin kernel or the wave-per-centre kernel (eq8_sparse_route)
 static int launch_sparse(const SparseArgs& g_in, hipStream_t st) {
+    const Eq8SparseRoute r = eq8_sparse_route(sparse_in(g_in));
+    if (r.status) return r.status;
+    const Eq8Launch& l = r.launch;
     SparseArgs g = g_in;
-    if (g.n > 128 || g.d4 > 256) return DIGAT_ERR_SHAPE;
     { const int rcp = sparse_prof_bytes(g, st); if (rcp) return rcp; }
     ProfScope prof(DIGAT_KERNEL_XATTN, sparse_bytes(g), st, 0.0, sparse_part(g));
-    unsigned blocks = (unsigned)(((long)g.B * g.n + 3) / 4);
-    if (g.run_if && blocks > 2048u) blocks = 2048u;        // guarded: a fixed grid striding over the centres (see the kernel)
-    // 16: runs of 64 consecutive centres (about two user graphs) per XCD; measured 1.431 vs 1.442 ms per step against the
-    // dispatcher's plain round-robin (0), 8: 1.434, 4: 1.436, 2: 1.443 (tools/exp/ab.sh, two alternating runs each)
-    constexpr int SPARSE_XCD_GROUP = 16;
-    g.xcd_group = SPARSE_XCD_GROUP;
+    g.xcd_group = l.xcd_group;
 #ifdef DIGAT_SPARSE_TIMERS
     if (!g_sparse_timers && hipMalloc((void**)&g_sparse_timers, 16 * 8) == hipSuccess) (void)hipMemset(g_sparse_timers, 0, 16 * 8);
     g.timers = g.rowidx ? g_sparse_timers : nullptr;          // the user graph's row-list launches
 #endif
-    blocks = (blocks + 8u * g.xcd_group - 1) / (8u * g.xcd_group) * (8u * g.xcd_group);   // whole windows
-    if (g.twin && g.twlist && g.twcount && g.rowidx && !g.pq16 && !g.radd && !g.group && !g.run_if && !g.fill_flags && g.d4 <= 128) {
-        // centres with equal adjacency rows together (xattn_sparse_twin_kernel); how many lead is known on the device only: a capped
-        // grid whose waves stride over the list
-        constexpr unsigned TWIN_GRID_CAP = 8192;
-        if (blocks > TWIN_GRID_CAP) blocks = TWIN_GRID_CAP;
-        blocks = (blocks * 4 + DIGAT_TWIN_WPG - 1) / DIGAT_TWIN_WPG;
-        if (g.d4 <= 64) hipLaunchKernelGGL((xattn_sparse_twin_kernel<1, TWIN_R>), dim3(blocks), dim3(64 * DIGAT_TWIN_WPG), 0, st, g);
-        else hipLaunchKernelGGL((xattn_sparse_twin_kernel<2, TWIN_R>), dim3(blocks), dim3(64 * DIGAT_TWIN_WPG), 0, st, g);
-        DIGAT_CHECK_LAUNCH();
-        return DIGAT_OK;
-    }
-    if (g.pq16 == 2) {  // P' and Q as block-scaled e4m3 rows (projection GEMM with fp8 segments: 80-channel strips, d = 4 d4)
-        if (g.radd || g.d4 % 20 || g.ld8 < 4 * g.d4 + 4 * (g.d4 / 20) || (g.ld8 & 7)) return DIGAT_ERR_SHAPE;
-        if (g.d4 <= 64) hipLaunchKernelGGL((xattn_sparse_kernel<1, 2, false>), dim3(blocks), dim3(256), 0, st, g);
-        else if (g.d4 <= 128) hipLaunchKernelGGL((xattn_sparse_kernel<2, 2, false>), dim3(blocks), dim3(256), 0, st, g);
-        else hipLaunchKernelGGL((xattn_sparse_kernel<4, 2, false>), dim3(blocks), dim3(256), 0, st, g);
-    } else if (g.pq16) {       // P' and Q in bf16 (projection GEMM with bf16 segments); K3 is in P' already: no radd here
-        if (g.radd || (g.d4 & 1)) return DIGAT_ERR_SHAPE;
-        if (g.d4 <= 64) hipLaunchKernelGGL((xattn_sparse_kernel<1, 1, false>), dim3(blocks), dim3(256), 0, st, g);
-        else if (g.d4 <= 128) hipLaunchKernelGGL((xattn_sparse_kernel<2, 1, false>), dim3(blocks), dim3(256), 0, st, g);
-        else hipLaunchKernelGGL((xattn_sparse_kernel<4, 1, false>), dim3(blocks), dim3(256), 0, st, g);
-    } else if (g.radd) {
-        if (g.d4 <= 64) hipLaunchKernelGGL((xattn_sparse_kernel<1, 0, true>), dim3(blocks), dim3(256), 0, st, g);
-        else if (g.d4 <= 128) hipLaunchKernelGGL((xattn_sparse_kernel<2, 0, true>), dim3(blocks), dim3(256), 0, st, g);
-        else hipLaunchKernelGGL((xattn_sparse_kernel<4, 0, true>), dim3(blocks), dim3(256), 0, st, g);
-    } else {
-        if (g.d4 <= 64) hipLaunchKernelGGL((xattn_sparse_kernel<1, 0, false>), dim3(blocks), dim3(256), 0, st, g);
-        else if (g.d4 <= 128) hipLaunchKernelGGL((xattn_sparse_kernel<2, 0, false>), dim3(blocks), dim3(256), 0, st, g);
-        else hipLaunchKernelGGL((xattn_sparse_kernel<4, 0, false>), dim3(blocks), dim3(256), 0, st, g);
-    }
+    if (l.kernel == EQ8_TWIN)
+        eq8_by_width<2>(l.U, [&](auto u) {
+            hipLaunchKernelGGL((xattn_sparse_twin_kernel<decltype(u)::value, TWIN_R>), dim3(l.grid), dim3(l.block), 0, st, g);
+        });
+    else launch_sparse_kernel(l, g, st);
     DIGAT_CHECK_LAUNCH();
     return DIGAT_OK;
 }
 
-// layer 0 of grouped rows on the chunk kernel (see xattn_sparse_l0_kernel); `lead` from sparse_l0_chunks_kernel
-#ifndef DIGAT_L0_ROWS
-#define DIGAT_L0_ROWS 4
-#endif
+// layer 0 of grouped rows on the chunk kernel (see xattn_sparse_l0_kernel; `l` from eq8_l0_route, where the launch is eligible);
+// `lead` from sparse_l0_chunks_kernel
 constexpr int SPARSE_L0_ROWS = DIGAT_L0_ROWS;
-static bool sparse_l0_ok(const SparseArgs& g) {
-    return g.group && g.xgroup && g.radd && g.rowidx && g.nrows_dev && g.live && !g.run_if && !g.pq16 && !g.fill_flags && !g.centre_limit &&
-           g.n <= 128 && g.d4 <= 128;
-}
-static int launch_sparse_l0(const SparseArgs& g_in, const uint8_t* lead, const int* list, const int* count, int G, hipStream_t st) {
+static int launch_sparse_l0(const SparseArgs& g_in, const Eq8Launch& l, const uint8_t* lead, const int* list, const int* count, hipStream_t st) {
     SparseL0Args a{g_in, lead, list, count};
     SparseArgs& g = a.g;
     { const int rcp = sparse_prof_bytes(g, st); if (rcp) return rcp; }
     ProfScope prof(DIGAT_KERNEL_XATTN, sparse_bytes(g), st, 0.0, XPART_L0);
-    constexpr int L0_XCD_GROUP = 16;       // runs of workgroups per XCD, as in launch_sparse
-    g.xcd_group = L0_XCD_GROUP;
-    // at most ceil(rows of a group / R) chunks per group: B / R + G chunks, n centres each
-    unsigned blocks = (unsigned)((((long)g.B / SPARSE_L0_ROWS + G) * g.n + 3) / 4);
-    blocks = (blocks + 8u * g.xcd_group - 1) / (8u * g.xcd_group) * (8u * g.xcd_group);
-    if (g.d4 <= 64) hipLaunchKernelGGL((xattn_sparse_l0_kernel<1, SPARSE_L0_ROWS>), dim3(blocks), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((xattn_sparse_l0_kernel<2, SPARSE_L0_ROWS>), dim3(blocks), dim3(256), 0, st, a);
+    g.xcd_group = l.xcd_group;
+    eq8_by_width<2>(l.U, [&](auto u) {
+        hipLaunchKernelGGL((xattn_sparse_l0_kernel<decltype(u)::value, SPARSE_L0_ROWS>), dim3(l.grid), dim3(l.block), 0, st, a);
+    });
     DIGAT_CHECK_LAUNCH();
     return DIGAT_OK;
 }
@@ -1677,159 +1666,83 @@ __global__ void __launch_bounds__(MAXT) xattn_agg_kernel(const AggArgs g) {
         }
     }
 }
-// every launch of it: a workgroup per row, a wave per 64 channels (up to 16 waves: from d = 1028 a wave takes several groups);
-// alpha[b] and the live flags in LDS
-static int launch_agg(const AggArgs& ag, hipStream_t st) {
-    const size_t lds = (size_t)ag.n * ag.sa * 4 + ag.n;
-    if (ag.groups <= 8) hipLaunchKernelGGL(xattn_agg_kernel<512>, dim3(ag.B), dim3(64 * ag.groups), lds, st, ag);
-    else hipLaunchKernelGGL(xattn_agg_kernel<1024>, dim3(ag.B), dim3(64 * (ag.groups < 16 ? ag.groups : 16)), lds, st, ag);
+// AggArgs with its mandatory fields (groups and sa come from the route: launch_agg)
+static AggArgs agg_args(const float* alpha, const float* h, const float* X, float* out, int B, int n, int d) {
+    AggArgs ag = {};
+    ag.alpha = alpha; ag.Hh = h; ag.X = X; ag.out = out; ag.B = B; ag.n = n; ag.d = d;
+    return ag;
+}
+// every launch of it (eq8_agg_route)
+static int launch_agg(AggArgs ag, const Eq8AggRoute& r, hipStream_t st) {
+    if (r.status) return r.status;
+    const Eq8Launch& l = r.launch;
+    ag.groups = r.groups; ag.sa = r.sa;
+    if (l.maxt == 512) hipLaunchKernelGGL(xattn_agg_kernel<512>, dim3(l.grid), dim3(l.block), l.lds, st, ag);
+    else hipLaunchKernelGGL(xattn_agg_kernel<1024>, dim3(l.grid), dim3(l.block), l.lds, st, ag);
     DIGAT_CHECK_LAUNCH();
     return DIGAT_OK;
 }
-// the GAT layer and the training forward keep the limit their other kernels were written and tested for: d <= 1024
-static int launch_agg_1024(const AggArgs& ag, hipStream_t st) { return ag.groups > 16 ? DIGAT_ERR_SHAPE : launch_agg(ag, st); }
 
-struct XattnPlan { ScoreArgs g; int threads; size_t lds; int blocks; };
-
-static int plan_xattn(int B, int n, int d, XattnPlan* pl) {
-    if (B < 0 || n <= 0 || d <= 0) return DIGAT_ERR_ARG;
-    if (d % 4 != 0 || n > DIGAT_MAX_NODES) return DIGAT_ERR_SHAPE;
-    ScoreArgs& g = pl->g;
-    memset(&g, 0, sizeof(g));
-    g.B = B; g.n = n; g.d = d; g.d4 = d / 4;
-    g.NT = (n + 3) / 4;
-    g.SN = (n + 3) / 4 * 4;
-    const int tiles = g.NT * g.NT;
-    int threads, rbmax;
-    if (tiles >= 128) { threads = (tiles + 63) / 64 * 64; rbmax = 1; }
-    else { threads = 256; rbmax = 256 / tiles; }
-    if (rbmax > B && B > 0) rbmax = B;
-    const int nwaves = threads / 64;
-    int bestRB = 0, bestCC = 0;
-    // <= 40 KiB keeps 4 workgroups per CU (1024 rows = one round on 256 CUs); graphs too large for
-    // that may take up to 150 KiB.  The DMA ring must sit in the first 64 KiB of LDS (M0 addressing).
-    // Phase 0 stages the adjacency bytes at the start of LDS, below the bit rows at am_off = max(ring, scores).  The three budgets
-    // are first tried with the bytes inside the ring alone; wide graphs of few channels (n >= 111 at d = 4: a 12 KiB ring, 12 - 16 KiB
-    // of bytes) find no plan that way, and a second round (`relaxed`) lets the bytes reach into the score area, which is idle until
-    // the chunk loop has ended.  Plans of the first round are never replaced.
-    for (int pass = 0; pass < 6 && !bestRB; ++pass) {
-        const bool relaxed = pass >= 3;
-        const int budget = pass % 3;
-        const size_t lds_budget = budget == 0 ? 40 * 1024 : (budget == 1 ? 64 * 1024 : 150 * 1024);
-        for (int rb = rbmax; rb >= 1 && !bestRB; --rb) {
-            int cc_ok = 0;
-            // odd chunk widths first (conflict-free LDS reads), widest first
-            for (int odd = 1; odd >= 0 && !cc_ok; --odd) {
-                for (int cc = g.d4; cc >= 1; --cc) {
-                    if (g.d4 % cc || (cc & 1) != odd) continue;
-                    const long img = (long)rb * 4 * g.NT * cc;
-                    const long ring_slots = (2 * img + 63) / 64 * 64;
-                    if (ring_slots / 64 > (long)XA_KMAX * nwaves) continue;
-                    if ((size_t)XA_RING * ring_slots * 16 > 60 * 1024) continue;
-                    const size_t sc = (size_t)rb * n * g.SN * 4;
-                    const size_t ringb = (size_t)XA_RING * ring_slots * 16;
-                    const size_t stage = (relaxed && sc > ringb) ? sc : ringb;     // where the byte image of phase 0 may lie
-                    if ((size_t)rb * n * n + 32 > stage) continue;
-                    const size_t tot = align_up(ringb > sc ? ringb : sc, 16) + (size_t)rb * n * ((n + 31) / 32) * 4
-                                       + (size_t)d * 4 + ((size_t)rb * tiles + 16) * 4 + (size_t)rb * 8 * g.NT * 4
-                                       + (size_t)2 * rb * n * 4;
-                    if (2 * rb * 4 * g.NT > threads) continue;           // one thread per image row for the linear terms
-                    if (tot > lds_budget) continue;
-                    cc_ok = cc;
-                    break;
-                }
+// the score launch of a route (eq8_score_launch): a small-graph kernel, or the tile kernel on the plan `g` was made from
+static int launch_score(const Eq8Launch& l, const ScoreArgs& g, hipStream_t st) {
+    const dim3 grid(l.grid), block(l.block);
+    if (l.kernel == EQ8_SMALL_LDS)
+        eq8_by_width<4>(l.U, [&](auto u) { hipLaunchKernelGGL(xattn_small_lds_kernel<decltype(u)::value>, grid, block, l.lds, st, g); });
+    else if (l.kernel == EQ8_SMALL)
+        eq8_by_width<4>(l.U, [&](auto u) { hipLaunchKernelGGL(xattn_score_small_kernel<decltype(u)::value>, grid, block, 0, st, g); });
+    else {
+        if (l.raise_lds) {
+            static int raised = 0;     // benign race: the attribute is idempotent
+            if (!raised) {
+                if (hipFuncSetAttribute((const void*)xattn_score_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        160 * 1024) != hipSuccess) return DIGAT_ERR_LAUNCH;
+                raised = 1;
             }
-            const int want = g.d4 < 5 ? 1 : 5;
-            if (cc_ok >= want || (rb == 1 && cc_ok >= 1)) { bestRB = rb; bestCC = cc_ok; }
         }
+        hipLaunchKernelGGL(xattn_score_kernel, grid, block, l.lds, st, g);
     }
-    if (!bestRB) return DIGAT_ERR_SHAPE;
-    g.RB = bestRB; g.CC4 = bestCC; g.nchunks = g.d4 / g.CC4;
-    g.img_slots = g.RB * 4 * g.NT * g.CC4;
-    g.ring_slots = (2 * g.img_slots + 63) / 64 * 64;
-    g.ninstr = g.ring_slots / 64;
-    const size_t ringb = (size_t)XA_RING * g.ring_slots * 16;
-    const size_t sc = (size_t)g.RB * n * g.SN * 4;
-    g.am_off = (int)align_up(ringb > sc ? ringb : sc, 16);
-    g.a_off = g.am_off + (int)align_up((size_t)g.RB * n * ((n + 31) / 32) * 4, 16);
-    g.tl_off = g.a_off + d * 4;
-    g.ld_off = g.tl_off + (g.RB * tiles + 16) * 4;
-    g.pm_off = g.ld_off + g.RB * 8 * g.NT * 4;
-    pl->lds = g.pm_off + (size_t)2 * g.RB * n * 4;
-    pl->threads = threads;
-    pl->blocks = (B + g.RB - 1) / g.RB;
-    return DIGAT_OK;
-}
-
-// the score launch of a filled-in plan: the wave-per-centre kernel for small graphs, the tile kernel otherwise
-static int launch_score(const XattnPlan& pl, hipStream_t st) {
-    const ScoreArgs& g = pl.g;
-    // small graphs in the fused form: the graph-in-LDS kernel when P' and h of a graph fit 64 KB (LDS-DMA addresses go through M0)
-    if (g.n <= 16 && g.d4 <= 256 && g.agg_out && !g.qgroup && !g.s_out) {
-        const size_t lds = (size_t)2 * (((size_t)g.n * g.d4 + 63) / 64) * 1024;
-        if (lds <= 64 * 1024) {
-            if (g.d4 <= 64) hipLaunchKernelGGL(xattn_small_lds_kernel<1>, dim3(g.B), dim3(256), lds, st, g);
-            else if (g.d4 <= 128) hipLaunchKernelGGL(xattn_small_lds_kernel<2>, dim3(g.B), dim3(256), lds, st, g);
-            else hipLaunchKernelGGL(xattn_small_lds_kernel<4>, dim3(g.B), dim3(256), lds, st, g);
-            DIGAT_CHECK_LAUNCH();
-            return DIGAT_OK;
-        }
-    }
-    if (g.n <= 16 && g.d4 <= 256) {
-        const unsigned blocks = (unsigned)(((long)g.B * g.n + 3) / 4);
-        if (g.d4 <= 64) hipLaunchKernelGGL(xattn_score_small_kernel<1>, dim3(blocks), dim3(256), 0, st, g);
-        else if (g.d4 <= 128) hipLaunchKernelGGL(xattn_score_small_kernel<2>, dim3(blocks), dim3(256), 0, st, g);
-        else hipLaunchKernelGGL(xattn_score_small_kernel<4>, dim3(blocks), dim3(256), 0, st, g);
-        DIGAT_CHECK_LAUNCH();
-        return DIGAT_OK;
-    }
-    if (pl.lds > 64 * 1024) {
-        static int raised = 0;     // benign race: the attribute is idempotent
-        if (!raised) {
-            if (hipFuncSetAttribute((const void*)xattn_score_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    160 * 1024) != hipSuccess) return DIGAT_ERR_LAUNCH;
-            raised = 1;
-        }
-    }
-    hipLaunchKernelGGL(xattn_score_kernel, dim3(pl.blocks), dim3(pl.threads), pl.lds, st, pl.g);
     DIGAT_CHECK_LAUNCH();
     return DIGAT_OK;
 }
 
+// launch_xattn_pairwise's optional inputs; what a caller does not set stays off
+struct PairOpts {
+    const uint8_t* live = nullptr;         // [B,n]: dead nodes are neither scored nor aggregated
+    const int* group = nullptr;            // [B]: Q and h of row b live at row group[b]
+    const float* radd = nullptr;           // [B,d] (small graphs): Pr holds K1 alone, K3 is added in the kernel
+    bool alpha_wanted = true;              // false: small graphs are scored and aggregated in one launch, alpha is not written
+    const int* skip_if = nullptr;          // device int: both launches return at once when it is != 0 (the sparse kernel does this batch)
+    const int64_t* bindex = nullptr;       // [B] (fused small-graph form): Pr, Q, h, X are tables, row b's graph is their row bindex[b]
+};
 // Pr = K3 + K1 (r already added to the neighbour-side projection), see xattn_core
 static int launch_xattn_pairwise(const float* Pr, const float* Q, const float* h, const float* X,
                                  const float* a, const uint8_t* A, float* out, float* alpha,
-                                 int B, int n, int d, hipStream_t st, const uint8_t* live = nullptr, const int* group = nullptr,
-                                 const float* radd = nullptr, bool alpha_wanted = true, const int* skip_if = nullptr,
-                                 const int64_t* bindex = nullptr) {
-    XattnPlan pl;
-    const int rc = plan_xattn(B, n, d, &pl);
-    if (rc) return rc;
-    if (B == 0) return DIGAT_OK;
-    pl.g.P = Pr; pl.g.Q = Q; pl.g.a = a; pl.g.A = A; pl.g.alpha = alpha; pl.g.live = live; pl.g.qgroup = group; pl.g.radd = radd;
-    pl.g.bindex = bindex;
-    if (bindex && (alpha_wanted || live || group || !(n <= 16 && pl.g.d4 <= 256))) return DIGAT_ERR_SHAPE;   // fused small-graph form only
-    pl.g.skip_if = skip_if;            // guarded launches (the device decides between them and the sparse kernel) carry no nominal work
-    if (radd && !(n <= 16 && pl.g.d4 <= 256)) return DIGAT_ERR_SHAPE;        // only the small-graph kernel adds K3 itself
-    // small graphs whose alpha nobody asked for: score, softmax and aggregation in one launch
-    const bool fused = !alpha_wanted && n <= 16 && pl.g.d4 <= 256 && !live && !group;
-    if (fused) { pl.g.agg_h = h; pl.g.agg_x = X; pl.g.agg_out = out; }
+                                 int B, int n, int d, hipStream_t st, const PairOpts& o = PairOpts()) {
+    Eq8PairIn in = {};
+    in.B = B; in.n = n; in.d = d; in.alpha_wanted = o.alpha_wanted; in.live = o.live != nullptr; in.group = o.group != nullptr;
+    in.radd = o.radd != nullptr; in.bindex = o.bindex != nullptr; in.guarded = o.skip_if != nullptr;
+    const Eq8PairRoute r = eq8_pair_route(in);
+    if (r.status || r.score.kernel == EQ8_NONE) return r.status;
+    ScoreArgs g = score_args(r.tile);
+    g.P = Pr; g.Q = Q; g.a = a; g.A = A; g.alpha = alpha; g.live = o.live; g.qgroup = o.group; g.radd = o.radd; g.bindex = o.bindex;
+    g.skip_if = o.skip_if;            // guarded launches (the device decides between them and the sparse kernel) carry no nominal work
+    if (r.fused) { g.agg_h = h; g.agg_x = X; g.agg_out = out; }
     {
         // algorithmic bytes of the score launch: P', Q in (2 n d floats), adjacency, alpha out, a (SURVEY 8d bytes_A);
         // the fused small-graph launch also aggregates: P', Q, h, X in, the nodes out, K3, adjacency (bytes_B)
-        const double bytes = fused ? (double)B * (5.0 * n * d * 4 + (radd ? 4.0 * d : 0.0) + (double)n * n) + 4.0 * d
-                                   : (double)B * (2.0 * n * d * 4 + (double)n * n * 5.0) + 4.0 * d;
-        ProfScope prof(DIGAT_KERNEL_XATTN, skip_if ? 0.0 : bytes, st, 0.0, fused ? XPART_NEWS : XPART_OTHER);
-        const int rc2 = launch_score(pl, st);
+        const double bytes = r.fused ? (double)B * (5.0 * n * d * 4 + (o.radd ? 4.0 * d : 0.0) + (double)n * n) + 4.0 * d
+                                     : (double)B * (2.0 * n * d * 4 + (double)n * n * 5.0) + 4.0 * d;
+        ProfScope prof(DIGAT_KERNEL_XATTN, o.skip_if ? 0.0 : bytes, st, 0.0, r.fused ? XPART_NEWS : XPART_OTHER);
+        const int rc2 = launch_score(r.score, g, st);
         if (rc2) return rc2;
     }
-    if (!fused) {
-        AggArgs ag{alpha, h, X, out, B, n, d, (d + 63) / 64, n | 1, live, group, skip_if};
+    if (!r.fused) {
+        AggArgs ag = agg_args(alpha, h, X, out, B, n, d);
+        ag.live = o.live; ag.hgroup = o.group; ag.skip_if = o.skip_if;
         // algorithmic bytes of the aggregation launch: h, X in + out (3 n d floats), alpha in;
         // flops 2 n^2 d per row run on the MFMA pipe
-        ProfScope prof(DIGAT_KERNEL_AGG, skip_if ? 0.0 : (double)B * (3.0 * n * d * 4 + (double)n * n * 4.0), st);
-        return launch_agg(ag, st);
+        ProfScope prof(DIGAT_KERNEL_AGG, o.skip_if ? 0.0 : (double)B * (3.0 * n * d * 4 + (double)n * n * 4.0), st);
+        return launch_agg(ag, r.agg, st);
     }
     return DIGAT_OK;
 }
-

@@ -516,7 +516,12 @@ size_t digat_xattn_train_workspace_bytes(int B, int n, int d);
  * only, the function is the same.  DIGAT_TRAIN_XATTN_AUTO: decided on the device per batch from a sample of the adjacency (the
  * entry-wise kernels when it holds at most ~20 entries per node, the all-pairs kernels otherwise; the launches of the side not
  * taken return at once); _SPARSE: the entry-wise kernels (a wave per centre / per node over the adjacency's entries), _DENSE: the
- * all-pairs kernels — unguarded: a caller that knows its corpus saves the decision and the empty launches. */
+ * all-pairs kernels — unguarded: a caller that knows its corpus saves the decision and the empty launches.
+ * xattn_mode is a HINT: each direction follows it where its own kernels fit (csrc/digat_xattn_plan.h: eq8_train_fwd_route,
+ * eq8_train_bwd_route).  Graphs of at most 16 nodes ignore it (one fused forward launch; the entry-wise backward).  The entry-wise
+ * forward takes d <= 1024, the entry-wise backward d <= 512: for 512 < d <= 1024 a forward that ran entry-wise is followed by the
+ * all-pairs backward whatever the mode, and beyond d = 1024 the entry refuses the shape.  Every combination computes the same
+ * function from the same saved tensors, so the two directions need not agree. */
 enum { DIGAT_TRAIN_XATTN_AUTO = 0, DIGAT_TRAIN_XATTN_SPARSE = 1, DIGAT_TRAIN_XATTN_DENSE = 2 };
 int digat_xattn_fwd_train(const float* X, const uint8_t* A, const float* ctx, const float* W, const float* bW, const float* F1,
                           const float* F2, const float* F3, const float* b3, const float* a, float* out, float p_alpha,

@@ -64,7 +64,7 @@ D_DENSE_ONLY = (1028,)
 N_ALL_D = (10, 16, 17, 44, 67, 128)
 D_ALL_N = (36, 400)
 CORNERS = ((8, 1024), (9, 1024), (15, 516), (16, 516), (16, 512), (128, 1024), (128, 4), (1, 4),
-           (112, 4))       # with (128, 4): n n + 32 adjacency bytes beyond the 12 KiB ring of d = 4, staged in the score area (plan_xattn)
+           (112, 4))       # with (128, 4): n n + 32 adjacency bytes beyond the 12 KiB ring of d = 4, staged in the score area (xattn_tile_plan)
 
 
 def _shapes(with_dense_only):

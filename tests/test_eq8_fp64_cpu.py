@@ -6,12 +6,14 @@
     within a QUARTER of the tolerance of the fp64 reference for the inference cases and within HALF of it for the training cases
     (there also with the scores summed as one fp32 chain over the channels, the order a kernel takes): a condition on the inputs
     of a case, so that the tolerance the kernels are held to is not already spent by the number format;
-  * the case lists name at least one case of every kernel class of the Eq. 8 dispatch (a membership check on (n, d, B))."""
+  * the case lists name at least one case of every kernel class of the Eq. 8 dispatch (a membership check on (n, d, B)), and the
+    launch plan (digat_amd/csrc/digat_xattn_plan.h) sends them to every kernel family at every width class."""
 import numpy as np
 import pytest
 import torch
 
 import eq8_fp64_common as C
+import xattn_plan_common as XP
 from conftest import load_golden, split_fixture
 from oracle import digat_oracle as O
 
@@ -85,7 +87,7 @@ def test_adjacency_kinds_are_what_they_are_named_for():
 
 
 def test_case_lists_name_every_kernel_class():
-    """At least one case of each class of the Eq. 8 dispatch: membership on (n, d, B), not a restatement of plan_xattn."""
+    """At least one case of each class of the Eq. 8 dispatch: membership on (n, d, B), not a restatement of the launch plan; then the plan's own answer."""
     pair = {(c.n, c.d, c.B) for c in C.PAIR_CASES}
     layer = {(c.n, c.d) for c in C.LAYER_CASES}
     has = lambda s, f: any(f(*c) for c in s)
@@ -113,6 +115,36 @@ def test_case_lists_name_every_kernel_class():
     assert has(train, lambda n, d: n > 16 and d <= 256) and has(train, lambda n, d: n > 16 and 256 < d <= 512) and has(train, lambda n, d: d > 512)
     assert {(112, 36), (113, 36), (128, 256), (1, 36), (16, 36), (17, 36)} <= train
     assert all(c.B <= 3 for c in C.PAIR_CASES if (c.n, c.d, c.B) not in C.RB_EXTRA) and all(c.B <= 3 for c in C.TRAIN_CASES)
+
+    # ... and what the launch plan itself says (digat_amd/csrc/digat_xattn_plan.h, asked through its test harness): the kernel
+    # instantiations the cases of each list take, as the GPU file calls the entries
+    def kernels(requests, *fields):
+        return {XP.kernel_name(w[f]) for w in map(XP.parse, XP.run(requests)) for f in fields} - {"NONE"}
+    shapes = lambda cases: sorted({(c.B, c.n, c.d) for c in cases})
+    widths = lambda fmt: {fmt.format(U) for U in (1, 2, 4)}
+    # block A: digat_xattn_pairwise_fwd, alpha wanted
+    pair_k = kernels([("pair", dict(B=B, n=n, d=d, alpha_wanted=1)) for B, n, d in shapes(C.PAIR_CASES)], "score", "agg")
+    assert pair_k == widths("SMALL<{}>") | {"TILE", "AGG<512>", "AGG<1024>"}, pair_k
+    # block B, dense: the layer without alpha; sparse (n > 16, d <= 1024): the wave-per-centre kernel
+    dense_k = kernels([("pair", dict(B=B, n=n, d=d, alpha_wanted=0)) for B, n, d in shapes(C.LAYER_CASES)], "score", "agg")
+    # (16 nodes of up to two pieces per lane always fit the graph-in-LDS kernel: the fused form reaches the other one at four only)
+    assert dense_k == widths("SMALL_LDS<{}>") | {"SMALL<4>", "TILE", "AGG<512>", "AGG<1024>"}, dense_k
+    sparse_k = kernels([("sparse", dict(B=B, n=n, d4=d // 4)) for B, n, d in shapes(C.LAYER_CASES) if n > 16 and d <= 1024], "launch")
+    assert sparse_k == widths("SPARSE<{},0,0,0>"), sparse_k
+    # block C: layer 0 of grouped rows (the chunk kernel, or the sparse kernel adding K3 beyond two pieces per lane), then the
+    # layers on the live lists with their twins
+    B = C.ENC_G * C.ENC_ROWS
+    l0_on = dict(group=1, xgroup=1, radd=1, rowidx=1, nrows_dev=1, live=1)
+    enc_k = kernels([("l0", dict(B=B, n=U, d4=d // 4, G=C.ENC_G, **l0_on)) for U, d in C.ENC_CASES], "launch")
+    enc_k |= kernels([("sparse", dict(B=B, n=U, d4=d // 4, **l0_on)) for U, d in C.ENC_CASES if d > 512], "launch")
+    enc_k |= kernels([("sparse", dict(B=B, n=U, d4=d // 4, twin=1, rowidx=1, nrows_dev=1, live=1)) for U, d in C.ENC_CASES], "launch")
+    assert enc_k == {"L0<1,4>", "L0<2,4>", "TWIN<1,2>", "TWIN<2,2>", "SPARSE<4,0,1,0>", "SPARSE<4,0,0,0>"}, enc_k
+    # block D: the layer's training entries always pass the device flag and ask for K3's gradient; modes 1 and 2
+    tr = [(r, dict(B=B, n=n, d=d, mode=m, flag=1, dr=1)) for B, n, d in shapes(C.TRAIN_CASES) for m in (1, 2) for r in ("train_fwd", "train_bwd")]
+    fwd_k = kernels([q for q in tr if q[0] == "train_fwd"], "sparse", "score", "agg")
+    bwd_k = kernels([q for q in tr if q[0] == "train_bwd"], "sparse", "pair")
+    assert fwd_k == widths("SPARSE<{},0,0,1>") | widths("SMALL<{}>") | {"TILE", "AGG<512>", "AGG<1024>"}, fwd_k
+    assert bwd_k == {"SPARSE_BWD<1>", "SPARSE_BWD<2>", "PAIR_BWD<64>", "PAIR_BWD<32>"}, bwd_k
 
 
 # ---- headroom: fp32 against fp64 ---------------------------------------------------------------------------------------------
