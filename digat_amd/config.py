@@ -7,6 +7,7 @@ real MIND cannot be downloaded, so the default corpus is synthetic (``--syntheti
 ``--word_embedding_file``, ``--data_cache``, ``--word_threshold``, ``--max_title_length``), and only then are those flags attributes
 (``--model_dir`` also when it is given: the Trainer saves there on either corpus);
 ``--recommend_diversity`` (with ``--recommend_shortlist``, ``--recommend_max_per_category``) likewise: attributes only when it is given;
+``--recommend_report`` (a tuple of diversities; it brings the other two with it as well) likewise;
 ``--local_rank`` also accepts torch >= 2.0's ``--local-rank`` spelling and the ``LOCAL_RANK`` variable.
 """
 from __future__ import annotations
@@ -39,6 +40,9 @@ class Config:
                        help='the shortlist --recommend_diversity picks from (recommend_k..128; 0: min(128, 4 * recommend_k))')
         p.add_argument('--recommend_max_per_category', type=int, default=0,
                        help='with --recommend_diversity: at most this many news of one category per list (0: no cap; needs a corpus with categories)')
+        p.add_argument('--recommend_report', type=str, default=None,
+                       help='--mode recommend: diversities "0,0.1,0.3" to report list quality for (one scoring pass; honours --recommend_k, '
+                            '--recommend_shortlist, --recommend_max_per_category)')
         p.add_argument('--seed', type=int, default=0)
         p.add_argument('--local_rank', '--local-rank', type=int, default=int(os.environ.get('LOCAL_RANK', -1)))
         p.add_argument('--dataset', default='MIND-small', choices=['MIND-small', 'MIND-large'])
@@ -89,8 +93,15 @@ class Config:
         p.add_argument('--max_title_length', type=int, default=32)
         p.add_argument('--model_dir', type=str, default='', help='directory the trained models are saved in')
         a = p.parse_args(argv)
-        if a.recommend_diversity is None and (a.recommend_shortlist or a.recommend_max_per_category):
-            p.error('--recommend_shortlist and --recommend_max_per_category need --recommend_diversity (0 for the cap alone)')
+        if a.recommend_report is not None:
+            try:
+                a.recommend_report = tuple(float(f) for f in a.recommend_report.split(',') if f.strip())
+            except ValueError:
+                p.error('--recommend_report takes diversities separated by commas, such as 0,0.1,0.3')
+            if not a.recommend_report or not all(0.0 <= f <= 1.0 for f in a.recommend_report):
+                p.error('--recommend_report needs at least one diversity, each in [0, 1]')
+        if a.recommend_diversity is None and a.recommend_report is None and (a.recommend_shortlist or a.recommend_max_per_category):
+            p.error('--recommend_shortlist and --recommend_max_per_category need --recommend_diversity (0 for the cap alone) or --recommend_report')
         if a.recommend_diversity is not None and not 0.0 <= a.recommend_diversity <= 1.0:
             p.error('--recommend_diversity must lie in [0, 1]')
         if a.recommend_shortlist < 0 or a.recommend_max_per_category < 0:
@@ -98,9 +109,11 @@ class Config:
         mind_flags = ('data_root', 'artefact_root', 'similarity_file', 'semantic_embedding_root', 'word_embedding_file', 'data_cache', 'word_threshold',
                       'max_title_length', 'model_dir')
         diversity_flags = ('recommend_diversity', 'recommend_shortlist', 'recommend_max_per_category')    # attributes only when asked for
+        report_flags = ('recommend_report', 'recommend_shortlist', 'recommend_max_per_category')
+        asked = lambda k: ((a.recommend_diversity is not None and k in diversity_flags) or (a.recommend_report is not None and k in report_flags)
+                           or k not in diversity_flags + report_flags)
         self.attribute_dict = {k: v for k, v in vars(a).items()
-                               if (a.data_root or k not in mind_flags or (k == 'model_dir' and a.model_dir))
-                               and (a.recommend_diversity is not None or k not in diversity_flags)}
+                               if (a.data_root or k not in mind_flags or (k == 'model_dir' and a.model_dir)) and asked(k)}
         for k, v in self.attribute_dict.items():
             setattr(self, k, v)
         if self.dataset == 'MIND-small':

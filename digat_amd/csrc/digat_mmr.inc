@@ -4,8 +4,8 @@
 // DOT_KB, DOT_LD, dot_wave_sync: the product below is dot_tile's loop, so sim(i, j) has the bits of digat_dot_scores).
 //
 // mmr_kernel, one workgroup (4 waves) per user:
-//   the list's ids (-1: beyond count[g] or outside [0, N): a zero row, no element), then the [Mu, Mu] Gram of the gathered rows,
-//   Mu = count rounded up to 16 — wave w owns the 16-row tile rows w and w + 4 and every tile column as 2 x 8 MFMA tiles, the rows
+//   the list's ids (-1: beyond count[g] or outside [0, N): a zero row, no element), then the [Mu, Mu] Gram of the gathered rows
+//   (mmr_gram), Mu = count rounded up to 16 — wave w owns the 16-row tile rows w and w + 4 and every tile column as 2 x 8 MFMA tiles, the rows
 //   staged through LDS in K blocks of DOT_KB channels (tail padded with zeros, k-steps wholly beyond d not issued), the next block's
 //   global loads in flight under the MFMAs.  The Gram lands in LDS over the staging area (the accumulators are in registers by
 //   then), row stride Mp + 4 with Mp = M rounded up to 16: 128 * 132 * 4 = 67 584 B at M = 128, two workgroups per CU.
@@ -18,8 +18,11 @@
 //
 // Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage), 256 threads per workgroup; dynamic LDS
 // 4 Mp max(Mp + 4, DOT_LD) bytes (2 304 B at M <= 16, 67 584 B at M = 128):
-//   mmr_kernel   VGPRs 44 + AGPRs 64 (the 2 x 8 accumulator tiles)   SGPRs 87   LDS 1536 B static   scratch 0   occupancy 4 waves / SIMD
+//   mmr_kernel   VGPRs 46 + AGPRs 64 (the 2 x 8 accumulator tiles)   SGPRs 87   LDS 1536 B static   scratch 0   occupancy 4 waves / SIMD
 //   (by registers; at M = 128 the 69 120 B of LDS allow two workgroups = 2 waves / SIMD)
+// The Gram is mmr_gram, a __device__ function that digat_listq.inc calls too: one product in the sources.  With the loop written out
+// inside mmr_kernel the compiler reported 44 VGPRs; 44 + 64 and 46 + 64 both allocate 112 registers a lane (granule 8), scratch is 0
+// either way and the selection's bits are the same (tests/test_hip_diversify.py), so the function is shared and not copied.
 
 #define MMR_MAX_M TOPK_MAX_K
 
@@ -53,34 +56,18 @@ __device__ __forceinline__ float mmr_value(float lam, float s, float mu, float p
     return rel - red;
 }
 
-__global__ void __launch_bounds__(256) mmr_kernel(const MmrArgs a) {
-    extern __shared__ float4 mmr_lds[];              // the staged rows [Mu][DOT_LD], then the Gram [Mu][ld]
-    __shared__ long long lid[MMR_MAX_M];             // vectors row of every list position, -1: not an element
-    __shared__ int lcat[MMR_MAX_M];
-    float* const L = (float*)mmr_lds;
+// The [16 T, 16 T] Gram of the rows lid[] names (-1: a zero row) into L as S[col][row], row stride ld — the one product of this file and
+// of digat_listq.inc.  Called by all 256 threads of the workgroup, lid[] written and a barrier passed; returns behind the barrier
+// that makes the Gram visible.  L holds max(16 T * DOT_LD, 16 T * ld) floats.
+__device__ __forceinline__ void mmr_gram(float* const L, const long long* lid, const float* vectors, const int d, const int T, const int ld) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 15, lq = lane >> 4;
-    const long g = blockIdx.x;
-    int cnt = a.count ? a.count[g] : a.M;
-    cnt = cnt < 0 ? 0 : (cnt > a.M ? a.M : cnt);
-    const int T = (cnt + 15) >> 4;                   // 16-row tiles of this user's Gram: <= 8, and 16 T <= ld - 4
-    if (tid < MMR_MAX_M) {
-        long long id = -1;
-        if (tid < cnt) {
-            id = (long long)a.ids[g * a.M + tid];
-            if (id < 0 || id >= a.N) id = -1;
-        }
-        lid[tid] = id;
-    }
-    __syncthreads();
-
-    // ---- the Gram: dot_tile's loop over 16 T rows on both sides
     const int c4 = (tid & 7) * 4, r0 = tid >> 3;     // this thread stages rows r0 + 32 h, channels c4 .. c4 + 3
-    const bool vec = (a.d & 3) == 0 && (((uintptr_t)a.vectors) & 15) == 0;
+    const bool vec = (d & 3) == 0 && (((uintptr_t)vectors) & 15) == 0;
     const float* row[4];
 #pragma unroll
     for (int h = 0; h < 4; ++h) {
         const long long id = lid[r0 + 32 * h];
-        row[h] = id >= 0 ? a.vectors + id * a.d : nullptr;
+        row[h] = id >= 0 ? vectors + id * d : nullptr;
     }
     v4f acc[2][8];
 #pragma unroll
@@ -89,20 +76,20 @@ __global__ void __launch_bounds__(256) mmr_kernel(const MmrArgs a) {
         for (int tc = 0; tc < 8; ++tc) acc[i][tc] = (v4f){0.f, 0.f, 0.f, 0.f};
     float4 rv[4];
 #pragma unroll
-    for (int h = 0; h < 4; ++h) rv[h] = dot_load4(row[h], c4, a.d, vec);
-    for (int kb = 0; kb < a.d; kb += DOT_KB) {
+    for (int h = 0; h < 4; ++h) rv[h] = dot_load4(row[h], c4, d, vec);
+    for (int kb = 0; kb < d; kb += DOT_KB) {
 #pragma unroll
         for (int h = 0; h < 4; ++h)
             if (r0 + 32 * h < 16 * T) *(float4*)&L[(r0 + 32 * h) * DOT_LD + c4] = rv[h];
         __syncthreads();
-        if (kb + DOT_KB < a.d) {
+        if (kb + DOT_KB < d) {
 #pragma unroll
-            for (int h = 0; h < 4; ++h) rv[h] = dot_load4(row[h], kb + DOT_KB + c4, a.d, vec);
+            for (int h = 0; h < 4; ++h) rv[h] = dot_load4(row[h], kb + DOT_KB + c4, d, vec);
         }
         if (wave < T) {                               // wave-uniform: this wave owns a tile row of the user's Gram
 #pragma unroll
             for (int ks = 0; ks < DOT_KB / 4; ++ks) {
-                if (kb + ks * 4 < a.d) {              // workgroup-uniform: no k-step wholly beyond d
+                if (kb + ks * 4 < d) {                // workgroup-uniform: no k-step wholly beyond d
                     const int k = ks * 4 + lq;
                     const float a0 = L[(16 * wave + lr) * DOT_LD + k];
                     const float a1 = wave + 4 < T ? L[(16 * (wave + 4) + lr) * DOT_LD + k] : 0.f;
@@ -127,10 +114,34 @@ __global__ void __launch_bounds__(256) mmr_kernel(const MmrArgs a) {
 #pragma unroll
             for (int tc = 0; tc < 8; ++tc)
                 if (tc < T)
-                    *(float4*)&L[(16 * tc + lr) * a.ld + 16 * tr + 4 * lq] = make_float4(acc[i][tc][0], acc[i][tc][1], acc[i][tc][2], acc[i][tc][3]);
+                    *(float4*)&L[(16 * tc + lr) * ld + 16 * tr + 4 * lq] = make_float4(acc[i][tc][0], acc[i][tc][1], acc[i][tc][2], acc[i][tc][3]);
         }
     }
     __syncthreads();
+}
+
+__global__ void __launch_bounds__(256) mmr_kernel(const MmrArgs a) {
+    extern __shared__ float4 mmr_lds[];              // the staged rows [Mu][DOT_LD], then the Gram [Mu][ld]
+    __shared__ long long lid[MMR_MAX_M];             // vectors row of every list position, -1: not an element
+    __shared__ int lcat[MMR_MAX_M];
+    float* const L = (float*)mmr_lds;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long g = blockIdx.x;
+    int cnt = a.count ? a.count[g] : a.M;
+    cnt = cnt < 0 ? 0 : (cnt > a.M ? a.M : cnt);
+    const int T = (cnt + 15) >> 4;                   // 16-row tiles of this user's Gram: <= 8, and 16 T <= ld - 4
+    if (tid < MMR_MAX_M) {
+        long long id = -1;
+        if (tid < cnt) {
+            id = (long long)a.ids[g * a.M + tid];
+            if (id < 0 || id >= a.N) id = -1;
+        }
+        lid[tid] = id;
+    }
+    __syncthreads();
+
+    // ---- the Gram: dot_tile's loop over 16 T rows on both sides
+    mmr_gram(L, lid, a.vectors, a.d, T, a.ld);
     if (wave != 0) return;
 
     // ---- the greedy steps: one wave, positions lane and lane + 64

@@ -8,7 +8,7 @@ identical to ``sklearn.metrics.roc_auc_score`` on these inputs).
 """
 from __future__ import annotations
 
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 import numpy as np
 
@@ -619,6 +619,184 @@ def mmr_gram_stock(ids, vectors):
     safe = torch.where((ids >= 0) & (ids < N), ids, torch.zeros_like(ids))
     rows = vectors[safe] if N else vectors.new_zeros(tuple(ids.shape) + (int(vectors.shape[1]),))
     return torch.bmm(rows, rows.transpose(1, 2))
+
+
+# ---- list quality: what finished lists look like ----------------------------------------------------------------------------------
+def _check_list_quality_args(ids_shape, count_shape, category_shape, base_shape, base_count_shape):
+    if len(ids_shape) != 2 or not 1 <= ids_shape[1] <= MMR_MAX_LIST:
+        raise ValueError(f"ids must be [G, k] with 1 <= k <= {MMR_MAX_LIST}, got {tuple(ids_shape)}")
+    if count_shape is not None and tuple(count_shape) != (ids_shape[0],):
+        raise ValueError(f"count must have one entry per list ({ids_shape[0]}), got shape {tuple(count_shape)}")
+    if category_shape is not None and len(category_shape) != 1:
+        raise ValueError(f"category must be [N], got shape {tuple(category_shape)}")
+    if base_shape is None and base_count_shape is not None:
+        raise ValueError("base_count needs base_ids")
+    if base_shape is not None:
+        if len(base_shape) != 2 or base_shape[0] != ids_shape[0] or not 1 <= base_shape[1] <= MMR_MAX_LIST:
+            raise ValueError(f"base_ids must be [G, kb] = [{ids_shape[0]}, 1 .. {MMR_MAX_LIST}], got {tuple(base_shape)}")
+        if base_count_shape is not None and tuple(base_count_shape) != (ids_shape[0],):
+            raise ValueError(f"base_count must have one entry per list ({ids_shape[0]}), got shape {tuple(base_count_shape)}")
+
+
+def _news_num(named) -> Optional[int]:
+    """The one N that the per-news arrays ``[(name, length or None)]`` agree on, or None when none is given."""
+    given = [(name, int(n)) for name, n in named if n is not None]
+    if len({n for _, n in given}) > 1:
+        raise ValueError("the per-news arrays must have one entry per news, all of one N: got " + ", ".join(f"{name} {n}" for name, n in given))
+    return given[0][1] if given else None
+
+
+def list_quality_host(ids, count=None, sim=None, category=None, base_ids=None, base_count=None, news_num=None, exposure=None):
+    """The contract of ``digat_list_quality`` in numpy — the yardstick of the kernel — on given similarities ``sim`` [G, k, k]
+    float32 (as for ``mmr_select_host``).  ``ids`` [G, k], ``count`` [G] or None (k): position p is an element when
+    ``p < clip(count[g], 0, k)`` and ``0 <= id < N`` (``news_num``; None: the length of ``category`` / ``exposure``, or no upper
+    bound) — ``mmr_select_host``'s rule; a repeated id is one element per position it holds.  Returns a dict of numpy arrays, [G]
+    each: ``elements`` int32; with ``sim``: ``sim_sum`` float64 — ``math.fsum`` of ``sim[g, p, q]`` over the element pairs p < q,
+    the exactly rounded sum, 0.0 without a pair — and ``sim_max`` float32 — ``np.fmax`` over the same pairs from ``-inf`` (NaNs are
+    passed over; a maximum of zero is ``+0.0``) —; with ``category`` [N] (any integers): ``categories`` and ``category_max`` int32,
+    the distinct ``category[id]`` over the elements and the count of the most frequent one; with ``base_ids`` [G, kb] and
+    ``base_count`` (elements by the same rule): ``overlap`` int32, the element positions whose id some element position of the
+    user's base list holds; with ``exposure`` [N]: ``exposure``, a NEW int64 array — the input plus one per element position."""
+    import math
+    idv = np.asarray(ids, dtype=np.int64)
+    cat = None if category is None else np.asarray(category, dtype=np.int64)
+    base = None if base_ids is None else np.asarray(base_ids, dtype=np.int64)
+    _check_list_quality_args(idv.shape, None if count is None else np.shape(count), None if cat is None else cat.shape,
+                             None if base is None else base.shape, None if base_count is None else np.shape(base_count))
+    G, k = idv.shape
+    S = None if sim is None else np.asarray(sim, dtype=np.float32)
+    if S is not None and S.shape != (G, k, k):
+        raise ValueError(f"sim must be [G, k, k] = {(G, k, k)}, got {S.shape}")
+    expo = None if exposure is None else np.array(exposure, dtype=np.int64)
+    if expo is not None and expo.ndim != 1:
+        raise ValueError(f"exposure must be [N], got shape {expo.shape}")
+    N = _news_num([("news_num", news_num), ("category", None if cat is None else len(cat)), ("exposure", None if expo is None else len(expo))])
+
+    def elements(v, c):
+        n = v.shape[1]
+        cnt = np.full(len(v), n, dtype=np.int64) if c is None else np.clip(np.asarray(c, dtype=np.int64), 0, n)
+        el = (np.arange(n)[None, :] < cnt[:, None]) & (v >= 0)
+        return el & (v < N) if N is not None else el
+    el = elements(idv, count)
+    out = {"elements": el.sum(axis=1).astype(np.int32)}
+    if S is not None:
+        out["sim_sum"], out["sim_max"] = np.zeros(G, dtype=np.float64), np.full(G, -np.inf, dtype=np.float32)
+        for g in range(G):
+            pair = np.triu(el[g][:, None] & el[g][None, :], 1)
+            vals = S[g][pair]
+            out["sim_sum"][g] = math.fsum(float(x) for x in vals)
+            out["sim_max"][g] = np.fmax.reduce(vals, initial=np.float32(-np.inf)) + np.float32(0)
+    if cat is not None:
+        out["categories"], out["category_max"] = np.zeros(G, dtype=np.int32), np.zeros(G, dtype=np.int32)
+        for g in range(G):
+            if el[g].any():
+                n = np.unique(cat[idv[g][el[g]]], return_counts=True)[1]
+                out["categories"][g], out["category_max"][g] = len(n), n.max()
+    if base is not None:
+        bel = elements(base, base_count)
+        out["overlap"] = np.array([int(np.isin(idv[g][el[g]], base[g][bel[g]]).sum()) for g in range(G)], dtype=np.int32).reshape(G)
+    if expo is not None:
+        np.add.at(expo, idv[el], 1)
+        out["exposure"] = expo
+    return out
+
+
+def list_quality(ids, count=None, vectors=None, category=None, base_ids=None, base_count=None, exposure=None):
+    """What finished lists look like, on the GPU (``digat_list_quality``): per list its cosine diversity, category spread and
+    overlap with the list before a second stage, and over all lists the catalogue's exposure.
+
+    ``ids`` [G, k <= 128] int64 and ``count`` [G] int32 (None: k) are device tensors — what ``mmr_select``, ``topk_segments``,
+    ``dot_topk`` and both ``recommend``s return.  Every part is optional and goes by its input: ``vectors`` [N, d] float32 (pass
+    unit rows: ``util.unit_rows``) gives ``sim_sum`` float64 and ``sim_max`` float32 over the element pairs of the Gram
+    ``mmr_select`` picks on; ``category`` [N] gives ``categories`` and ``category_max``; ``base_ids`` [G, kb <= 128] with
+    ``base_count`` gives ``overlap``; ``exposure`` [N] int32 (contiguous, on the device) gets one more per element position, IN
+    PLACE — it accumulates across calls, the caller zeroes it and keeps the counts inside int32 — and is returned too.  At least
+    one of ``vectors`` / ``category`` / ``exposure`` is needed: they say how many news there are.  The contract is
+    ``list_quality_host``'s: the integers exactly, ``sim_max`` by bits, ``sim_sum`` a double sum of the same float32 entries in a
+    fixed order (bit-identical from run to run and in any batch).  Returns a dict of device tensors [G] (``elements`` always; a
+    part that was not asked for has no key).  Stream-ordered: one launch, nothing is read back."""
+    import torch
+    from . import _lib
+    given = [t for t in (ids, count, vectors, category, base_ids, base_count, exposure) if t is not None]
+    dev = _lib.require_device(*given)
+    _check_list_quality_args(tuple(ids.shape), None if count is None else tuple(count.shape), None if category is None else tuple(category.shape),
+                             None if base_ids is None else tuple(base_ids.shape), None if base_count is None else tuple(base_count.shape))
+    if vectors is not None and (vectors.dim() != 2 or vectors.shape[1] < 1):
+        raise ValueError(f"vectors must be [N, d] with d >= 1, got {tuple(vectors.shape)}")
+    if exposure is not None and (exposure.dim() != 1 or exposure.dtype != torch.int32 or not exposure.is_contiguous()):
+        raise ValueError(f"exposure must be a contiguous [N] int32 tensor (it is updated in place), got {tuple(exposure.shape)} {exposure.dtype}")
+    N = _news_num([("vectors", None if vectors is None else vectors.shape[0]), ("category", None if category is None else category.shape[0]),
+                   ("exposure", None if exposure is None else exposure.shape[0])])
+    if N is None:
+        raise ValueError("list_quality needs vectors, category or exposure: one of them says how many news there are")
+    idt = ids.to(torch.int64).contiguous()
+    ct = None if count is None else count.to(torch.int32).contiguous()
+    v = None if vectors is None else _lib.f32(vectors.detach())
+    cat = None if category is None else category.to(torch.int32).contiguous()
+    bt = None if base_ids is None else base_ids.to(torch.int64).contiguous()
+    bc = None if base_count is None else base_count.to(torch.int32).contiguous()
+    G, k, kb = int(idt.shape[0]), int(idt.shape[1]), 0 if bt is None else int(bt.shape[1])
+    new = lambda dtype: torch.empty((G,), dtype=dtype, device=dev)
+    out = {"elements": new(torch.int32)}
+    if v is not None:
+        out["sim_sum"], out["sim_max"] = new(torch.float64), new(torch.float32)
+    if cat is not None:
+        out["categories"], out["category_max"] = new(torch.int32), new(torch.int32)
+    if bt is not None:
+        out["overlap"] = new(torch.int32)
+    if exposure is not None:
+        out["exposure"] = exposure
+    if G == 0:
+        return out
+    L = _lib.lib()
+    need = int(L.digat_list_quality_workspace_bytes(G, k, kb))
+    ws = _lib.workspace(need, dev, "list_quality")
+    _lib.check(L.digat_list_quality(idt.data_ptr(), _lib.ptr(ct), G, k, N, _lib.ptr(v), 0 if v is None else int(v.shape[1]), _lib.ptr(cat),
+                                    _lib.ptr(bt), _lib.ptr(bc), kb, _lib.ptr(exposure), out["elements"].data_ptr(), _lib.ptr(out.get("sim_sum")),
+                                    _lib.ptr(out.get("sim_max")), _lib.ptr(out.get("categories")), _lib.ptr(out.get("category_max")),
+                                    _lib.ptr(out.get("overlap")), ws.data_ptr(), need, _lib.stream_ptr()),
+               "digat_list_quality")
+    return out
+
+
+def quality_summary(q, exposure=None, pool=None):
+    """The figures of a ``list_quality`` / ``list_quality_host`` dict ``q`` over all its lists, in float64 on the host: ``ild`` —
+    intra-list diversity, the mean over the lists with at least two elements of ``1 - sim_sum / (n (n - 1) / 2)`` —, ``max_sim`` —
+    the mean of ``sim_max`` over the same lists —, ``categories`` — the mean distinct-category count —, ``category_max_share`` —
+    the mean of ``category_max / elements`` over the non-empty lists —, ``overlap`` — the mean of ``overlap / elements`` over the
+    non-empty lists —, and ``lists``, their number.  From ``exposure`` [N] (None: ``q["exposure"]`` where it has one) over ``pool``
+    (ids; None: all N): ``coverage`` — the share of pool ids with exposure > 0 — and ``gini`` — on the ascending counts
+    ``x_1 .. x_n``, ``2 sum(i x_i) / (n sum(x)) - (n + 1) / n``: 0 for equal exposure, ``(n - 1) / n`` when one id has it all.  A
+    part ``q`` does not carry, and anything with nothing to average over, is NaN — as in ``rank_metrics``."""
+    import torch
+    host = lambda x: None if x is None else np.asarray(x.cpu() if torch.is_tensor(x) else x)
+    nan = float("nan")
+    mean = lambda x: float(np.mean(x)) if len(x) else nan
+    el = host(q["elements"]).astype(np.float64)
+    some, two = el > 0, el > 1
+    out = {"lists": int(len(el)), "ild": nan, "max_sim": nan, "categories": nan, "category_max_share": nan, "overlap": nan,
+           "coverage": nan, "gini": nan}
+    if q.get("sim_sum") is not None:
+        n = el[two]
+        out["ild"] = mean(1.0 - host(q["sim_sum"]).astype(np.float64)[two] / (n * (n - 1.0) / 2.0))
+        out["max_sim"] = mean(host(q["sim_max"]).astype(np.float64)[two])
+    if q.get("categories") is not None:
+        out["categories"] = mean(host(q["categories"]).astype(np.float64))
+        out["category_max_share"] = mean(host(q["category_max"]).astype(np.float64)[some] / el[some])
+    if q.get("overlap") is not None:
+        out["overlap"] = mean(host(q["overlap"]).astype(np.float64)[some] / el[some])
+    x = host(exposure if exposure is not None else q.get("exposure"))
+    if x is not None:
+        x = x.astype(np.float64)
+        if pool is not None:
+            x = x[np.unique(host(pool).astype(np.int64))]
+        x = np.sort(x)
+        n = len(x)
+        if n:
+            out["coverage"] = float((x > 0).sum()) / n
+            if x.sum() > 0:
+                out["gini"] = float(2.0 * (np.arange(1, n + 1) * x).sum() / (n * x.sum()) - (n + 1.0) / n)
+    return out
 
 
 class AvgMetric:

@@ -11,11 +11,14 @@ corpus, picks the ``--recommend_k`` best of ALL non-PAD news the impression's us
 ``"<impression id> [id1,id2,...]"`` per line — the rank file's framing — to ``--recommend_output`` when one is named.
 ``--recommend_diversity F`` makes those the k maximal-marginal-relevance picks of a shortlist (``--recommend_shortlist``), with
 ``--recommend_max_per_category Q`` at most Q of one category — on a corpus that carries the news' categories (MIND does).
+``--recommend_report 0,0.1,0.3`` then prints one line per diversity with what the knob buys and costs (``util.recommend_report``: one
+scoring pass for all of them; on a labelled split the accuracy of the lists against each impression's clicked candidates as well).
 """
 from __future__ import annotations
 
 import time
 
+import numpy as np
 import torch
 
 from . import synthetic, util
@@ -58,6 +61,29 @@ def recommend_lines(model, dc, k: int, batch_size: int, diversity=None, shortlis
                                        category=recommend_category(dc, max_per_category), max_per_category=max_per_category)
     ids, count = ids.cpu().numpy(), count.cpu().numpy()
     return ['%d [%s]' % (i + 1, ','.join(str(int(v)) for v in ids[i, :count[i]])) for i in range(len(count))]
+
+
+def clicked_targets(dc, labels):
+    """``(target_ids [T], target_start [I + 1])`` for all impressions of ``dc``: each impression's clicked candidates — the rows
+    with label 1 — in row order (``nrms._clicked_targets`` reads the same for its corpus)."""
+    imp, cand = dc.row_impression.cpu().numpy(), dc.row_candidate.cpu().numpy()
+    rows = np.flatnonzero(np.asarray(labels) == 1)
+    rows = rows[np.argsort(imp[rows], kind='stable')]
+    start = np.r_[0, np.cumsum(np.bincount(imp[rows], minlength=int(dc.history.shape[0])))].astype(np.int64)
+    return cand[rows].astype(np.int64), start
+
+
+def report_lines(model, dc, k: int, batch_size: int, diversities, shortlist: int = 0, max_per_category: int = 0, labels=None):
+    """One line per diversity of ``--recommend_report``: ``util.recommend_report`` for every impression of ``dc`` against the pool
+    ``recommend_lines`` uses, ``evaluate.quality_summary``'s fields in its order; with ``labels`` (a labelled split) the accuracy
+    fields against each impression's clicked candidates behind them."""
+    pool = torch.arange(1, dc.news_embedding.shape[0], dtype=torch.int64, device=dc.news_embedding.device)
+    users = torch.arange(dc.history.shape[0], dtype=torch.int64)
+    rows = util.recommend_report(model, dc, users, pool, k, diversities, shortlist=shortlist or None,
+                                 category=recommend_category(dc, max_per_category), max_per_category=max_per_category,
+                                 targets=None if labels is None else clicked_targets(dc, labels), batch_size=batch_size)
+    fmt = lambda v: '%d' % v if isinstance(v, int) else '%.4f' % v
+    return ['diversity %.3f : ' % r['diversity'] + '  '.join('%s %s' % (f, fmt(v)) for f, v in r.items() if f != 'diversity') for r in rows]
 
 
 def synthetic_setup(config, dev):
@@ -145,6 +171,10 @@ def main(argv=None):
                 with open(config.recommend_output, 'w') as f:
                     f.write('\n'.join(lines))
             print('Recommended %d news for each of %d impressions' % (config.recommend_k, len(lines)))
+            if getattr(config, 'recommend_report', None):
+                for line in report_lines(model, dc, config.recommend_k, config.batch_size * 16, config.recommend_report,
+                                         getattr(config, 'recommend_shortlist', 0), cap, labels):
+                    print(line)
             print('Inference time : %.1fs' % (time.time() - start))
             return
         result_file = config.test_output_file if config.mode == 'test' and config.test_output_file else None

@@ -17,6 +17,7 @@ library refuses raises.
 """
 from __future__ import annotations
 
+import functools
 import math
 from types import SimpleNamespace
 
@@ -526,14 +527,10 @@ def recommend(model, dev, users, candidates=None, k=10, exclude_history=True, ba
     cache; ``max_per_category`` q >= 1 lets at most q news of one ``category`` [N] (None: ``dev.news_category``) into a list."""
     from . import evaluate, util
     if diversity is not None:
-        k, wide, lam = util.diversify_limits(k, diversity, shortlist, max_per_category)
-        if int(max_per_category) > 0 and category is None:
-            category = getattr(dev, "news_category", None)
-        if int(max_per_category) > 0 and category is None:
-            raise ValueError("max_per_category needs category: this corpus carries no news_category")
-        i, s, c = recommend(model, dev, users, candidates, wide, exclude_history, batch_size)
-        plain, _ = news_caches(model, dev.title_text, dev.title_mask, dev.augmented_title_text, dev.augmented_title_mask, 4 * batch_size)
-        return util.diversify(i, s, c, plain, k, lam, category, max_per_category)
+        select = lambda wide: recommend(model, dev, users, candidates, wide, exclude_history, batch_size)
+        plain = lambda: news_caches(model, dev.title_text, dev.title_mask, dev.augmented_title_text, dev.augmented_title_mask, 4 * batch_size)[0]
+        return util.shortlist_then_diversify(select, plain, k, (diversity,), shortlist, category, max_per_category,
+                                             getattr(dev, "news_category", None))[1][0]
     if shortlist is not None or category is not None or max_per_category:
         raise ValueError("shortlist, category and max_per_category belong to a diversified call: name diversity (0.0: the cap alone)")
     hist, mask = _histories(dev, users)
@@ -557,6 +554,25 @@ def recommend(model, dev, users, candidates=None, k=10, exclude_history=True, ba
         return row_logits(c, u) if cuda else (c * u).sum(dim=1)
     # on the CPU one chunk holds all pairs
     return util.recommend_select(G, k, ids, start, skip, util.RECOMMEND_MAX_ROWS if cuda else max(1, G * int(ids.shape[0])), score)
+
+
+def recommend_report(model, dev, users, candidates=None, k=10, diversities=(0.0, 0.1, 0.3, 0.5), shortlist=None, category=None,
+                     max_per_category=0, targets=None, exclude_history=True, batch_size=1024, return_lists=False):
+    """``util.recommend_report`` on NRMS's own retrieval: one ``recommend`` at the shortlist's width, then every diversity's lists
+    from it — bit for bit the lists ``recommend(..., diversity=f)`` returns — and their quality, one dict per diversity
+    (``util.quality_report``).  The maximal-marginal-relevance stage keeps the vectors it uses in ``recommend``, the plain news
+    cache; the QUALITY is always measured on ``util.unit_rows`` of those vectors, so ``ild`` and ``max_sim`` are cosine figures
+    for both models whatever the cache's norms.  ``candidates`` None: every news but row 0, which is then the coverage pool too.
+    ``targets = (target_ids [T], target_start [G+1])`` (``_clicked_targets`` reads a labelled corpus's) adds ``recall@k``,
+    ``user_recall@k`` and ``mrr``.  The category figures go by ``category``, else ``dev.news_category`` where there is one."""
+    from . import util
+    N = int(dev.title_text.shape[0])
+    select = lambda wide: recommend(model, dev, users, candidates, wide, exclude_history, batch_size)
+    plain = functools.lru_cache(maxsize=None)(
+        lambda: news_caches(model, dev.title_text, dev.title_mask, dev.augmented_title_text, dev.augmented_title_mask, 4 * batch_size)[0])
+    pool = np.arange(1, N, dtype=np.int64) if candidates is None else util.candidate_pool(candidates)
+    return util.quality_report(select, plain, lambda: util.unit_rows(plain()), k, diversities, shortlist, category, max_per_category,
+                               getattr(dev, "news_category", None), pool, targets, return_lists)
 
 
 def _clicked_targets(dev, users):

@@ -15,6 +15,7 @@ The graph encoder is the HIP plugin (``digat_amd.graphEncoders.DIGAT``); nothing
 from __future__ import annotations
 
 import dataclasses
+import functools
 import os
 from dataclasses import dataclass
 from typing import Callable, List, Optional, Tuple
@@ -989,6 +990,104 @@ def diversify(ids: torch.Tensor, scores: torch.Tensor, count: torch.Tensor, vect
     return torch.from_numpy(i), torch.from_numpy(s), torch.from_numpy(c)
 
 
+def cap_category(category, max_per_category, corpus_category):
+    """The category array a cap of ``max_per_category`` goes by: ``category``, else the corpus's own; a cap without either is
+    refused.  Without a cap: ``category`` as given."""
+    if int(max_per_category) > 0 and category is None:
+        category = corpus_category
+    if int(max_per_category) > 0 and category is None:
+        raise ValueError("max_per_category needs category: this corpus carries no news_category")
+    return category
+
+
+def shortlist_then_diversify(select: Callable, vectors: Callable, k, diversities, shortlist=None, category=None, max_per_category: int = 0,
+                             corpus_category=None):
+    """The step behind ``recommend(diversity=)`` of either model, and behind ``recommend_report``: ``select(k')`` — the plain
+    selection, once, at ``diversify_limits``' width — then ``diversify`` over ``vectors()`` for every value of ``diversities`` on
+    that one shortlist, a cap going by ``cap_category(category, max_per_category, corpus_category)``.  Returns ``(shortlist triple,
+    [recommend's triple per diversity])``."""
+    limits = [diversify_limits(k, f, shortlist, max_per_category) for f in diversities]
+    if not limits:
+        raise ValueError("diversities must name at least one value")
+    category = cap_category(category, max_per_category, corpus_category)
+    short = select(limits[0][1])
+    vec = vectors()
+    return short, [diversify(*short, vec, kk, lam, category, max_per_category) for kk, _, lam in limits]
+
+
+def measure_lists(ids, count, vectors, category=None, base_ids=None, base_count=None, exposure=None):
+    """``evaluate.list_quality`` on device lists; on CPU tensors the Gram of stock PyTorch (``evaluate.mmr_gram_stock``) and
+    ``evaluate.list_quality_host``, as ``diversify`` does.  ``exposure`` [N] int32 is updated in place either way.  Returns the
+    dict with the exposure in it."""
+    if ids.is_cuda:
+        return evaluate.list_quality(ids, count, vectors, category, base_ids, base_count, exposure)
+    host = lambda t: None if t is None else t.numpy()
+    q = evaluate.list_quality_host(ids.numpy(), host(count), evaluate.mmr_gram_stock(ids, vectors).numpy(), host(category), host(base_ids),
+                                   host(base_count), int(vectors.shape[0]), host(exposure))
+    if exposure is not None:
+        exposure.copy_(torch.from_numpy(q["exposure"]).to(torch.int32))
+    return q
+
+
+def candidate_pool(candidates):
+    """The ids of ``recommend``'s ``candidates`` in either form (``recommend_candidates``): the shared pool, or all ids of the
+    per-user lists."""
+    if isinstance(candidates, (tuple, list)) and len(candidates) == 2 and _ndim(candidates[0]) == 1 and _ndim(candidates[1]) == 1:
+        return candidates[0]
+    return candidates
+
+
+def quality_report(select: Callable, mmr_vectors: Callable, quality_vectors: Callable, k, diversities, shortlist, category,
+                   max_per_category, corpus_category, pool, targets=None, return_lists: bool = False):
+    """The sweep behind ``recommend_report`` of either model: ``shortlist_then_diversify`` — one ``select``, every diversity's
+    lists from that shortlist, the lists ``recommend(diversity=f)`` returns bit for bit — and after each ``diversify`` one
+    ``measure_lists`` over ``quality_vectors()`` (unit rows: the similarities are cosines) with ``category``, else
+    ``corpus_category``, else no category figures, the first k slots of the shortlist (the plain top-k) as the base list and an
+    exposure histogram that starts from zero for every diversity.  Returns one dict per diversity: ``{"diversity": f,
+    **evaluate.quality_summary(...)}`` with the coverage over ``pool`` (ids), and with ``targets = (target_ids [T], target_start
+    [G+1])`` also ``recall@k``, ``user_recall@k`` and ``mrr`` of the lists (``evaluate.list_ranks``, ``evaluate.rank_metrics``).
+    ``return_lists``: ``(rows, [triple per diversity])``."""
+    if targets is not None and not (isinstance(targets, (tuple, list)) and len(targets) == 2):
+        raise ValueError("targets must be None or a pair (target_ids [T], target_start [G+1])")
+    diversities = [float(f) for f in diversities]
+    short, lists = shortlist_then_diversify(select, mmr_vectors, k, diversities, shortlist, category, max_per_category, corpus_category)
+    k = int(k)
+    unit = quality_vectors()
+    dev = short[0].device
+    cat = category if category is not None else corpus_category
+    if cat is not None:
+        cat = torch.as_tensor(np.asarray(cat) if not torch.is_tensor(cat) else cat).to(dev, torch.int32)
+    base_ids, base_count = short[0][:, :k].contiguous(), torch.clamp(short[2], max=k)
+    rows = []
+    for f, (ids, _, count) in zip(diversities, lists):
+        exposure = torch.zeros((int(unit.shape[0]),), dtype=torch.int32, device=dev)
+        q = measure_lists(ids, count, unit, cat, base_ids, base_count, exposure)
+        row = {"diversity": f, **evaluate.quality_summary(q, exposure, pool)}
+        if targets is not None:
+            m = evaluate.rank_metrics(evaluate.list_ranks(ids, count, targets[0], targets[1]), targets[1], ks=(k,))
+            row.update({name: m[name] for name in (f"recall@{k}", f"user_recall@{k}", "mrr")})
+        rows.append(row)
+    return (rows, lists) if return_lists else rows
+
+
+def recommend_report(model, dc: DeviceCorpus, users, candidates, k: int, diversities=(0.0, 0.1, 0.3, 0.5), shortlist: Optional[int] = None,
+                     category=None, max_per_category: int = 0, targets=None, exclude_history: bool = True, batch_size: int = 1024,
+                     max_rows: int = RECOMMEND_MAX_ROWS, return_lists: bool = False):
+    """What the ``diversity`` knob of ``recommend`` buys and costs, for every value of ``diversities``, at the price of ONE scoring
+    pass: the plain selection runs once at ``k' = shortlist or min(128, 4 k)``, then every diversity's lists are cut from that
+    shortlist (``diversify``) and measured (``evaluate.list_quality``).  The lists are the ones ``recommend(..., diversity=f,
+    shortlist=, category=, max_per_category=)`` returns, bit for bit.  Returns one dict per diversity (``quality_report``):
+    ``diversity``, then ``evaluate.quality_summary``'s ``ild`` / ``max_sim`` (cosines: ``unit_rows(dc.news_embedding)``),
+    ``categories`` / ``category_max_share`` (``category``, else ``dc.news_category`` where the corpus has one; NaN without),
+    ``overlap`` with the plain top-k, ``coverage`` / ``gini`` of the exposure over the candidate pool (the shared pool, or the
+    distinct ids of per-user lists) and ``lists``; with ``targets = (target_ids, target_start)`` also ``recall@k``,
+    ``user_recall@k`` and ``mrr``.  ``return_lists``: ``(rows, [(news_ids, scores, count) per diversity])``."""
+    select = lambda wide: recommend(model, dc, users, candidates, wide, exclude_history, batch_size, max_rows)
+    unit = functools.lru_cache(maxsize=None)(lambda: unit_rows(dc.news_embedding))     # behind select: a text encoder's table is fresh then
+    return quality_report(select, unit, unit, k, diversities, shortlist, category, max_per_category, dc.news_category,
+                          candidate_pool(candidates), targets, return_lists)
+
+
 def recommend(model, dc: DeviceCorpus, users, candidates, k: int, exclude_history: bool = True, batch_size: int = 1024,
               max_rows: int = RECOMMEND_MAX_ROWS, diversity: Optional[float] = None, shortlist: Optional[int] = None, category=None,
               max_per_category: int = 0):
@@ -1013,13 +1112,9 @@ def recommend(model, dc: DeviceCorpus, users, candidates, k: int, exclude_histor
     ``max_per_category`` q >= 1 lets at most q news of one ``category`` [news_num] (None: ``dc.news_category``) into a list.  The
     scores returned are still the model's."""
     if diversity is not None:
-        k, wide, lam = diversify_limits(k, diversity, shortlist, max_per_category)
-        if int(max_per_category) > 0 and category is None:
-            category = dc.news_category
-        if int(max_per_category) > 0 and category is None:
-            raise ValueError("max_per_category needs category: this corpus carries no news_category")
-        i, s, c = recommend(model, dc, users, candidates, wide, exclude_history, batch_size, max_rows)
-        return diversify(i, s, c, unit_rows(dc.news_embedding), k, lam, category, max_per_category)
+        select = lambda wide: recommend(model, dc, users, candidates, wide, exclude_history, batch_size, max_rows)
+        return shortlist_then_diversify(select, lambda: unit_rows(dc.news_embedding), k, (diversity,), shortlist, category, max_per_category,
+                                        dc.news_category)[1][0]
     if shortlist is not None or category is not None or max_per_category:
         raise ValueError("shortlist, category and max_per_category belong to a diversified call: name diversity (0.0: the cap alone)")
     hist, cat, graph, mask = recommend_users(dc, users)

@@ -677,6 +677,36 @@ int digat_mmr_select(const int64_t* ids, const float* scores, const int32_t* cou
                      const int32_t* category, int max_per_category, float lam, float mu, int k, int64_t* out_ids, float* out_scores,
                      int32_t* out_count, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- list quality: what finished lists look like (digat_amd.evaluate.list_quality) -------------------------------------------
+ * Per list g: ids [G, k] int64 and count [G] int32 (NULL: k) — what digat_mmr_select, digat_topk_segments and digat_dot_topk write;
+ * N news rows.  Position p is an ELEMENT when p < clamp(count[g], 0, k) and 0 <= ids[g][p] < N (digat_mmr_select's rule); a repeated
+ * id is one element per position it holds; no read leaves the arrays.  Every output is [G]; the optional parts go by their input:
+ *   out_elements (always): the number of elements.
+ *   vectors [N, d] f32 -> out_sim_sum (f64) and out_sim_max (f32), over the element pairs p < q of sim(p, q), digat_mmr_select's
+ *     Gram (the bits of digat_dot_scores, symmetric): the sum of the entries widened to double — 0.0 with fewer than two elements;
+ *     the order of the additions is fixed by the list alone, so a list's value is the same bits from run to run and in any batch;
+ *     no float atomics — and their fmax (NaNs are passed over; -inf with fewer than two elements or NaNs alone; a maximum of zero is
+ *     +0.0): exact bits.
+ *   category [N] int32, any values -> out_categories and out_category_max: the distinct category[id] over the elements, and the
+ *     elements of the most frequent one; both 0 without elements.
+ *   base_ids [G, kb] int64 with base_count [G] (NULL: kb; elements by the same rule) -> out_overlap: the element positions whose
+ *     id is the id of some element position of base list g.
+ *   exposure [N] int32, read and written: exposure[id] += 1 per element position, integer atomics (order-free, exact).  The counts
+ *     ACCUMULATE across calls: the caller zeroes the array, and keeping the counts inside int32 (fewer than 2^31 element positions
+ *     per id between two zeroings) is the caller's concern — nothing here checks it.
+ * A part whose input is NULL is not computed and its outputs must be NULL; with the input, its outputs are required.
+ * DIGAT_ERR_ARG: a null ids / out_elements, an input without its outputs or outputs without their input, base_count without
+ * base_ids, vectors with d < 1, G < 0, N < 0; DIGAT_ERR_SHAPE: k outside [1, 128], kb outside [1, 128] (with base_ids), d > 2^24,
+ * G >= 2^31 — all before any launch.  G == 0 returns DIGAT_OK without a launch.  Stream-ordered: one launch on `stream`, one
+ * workgroup per list, the Gram never leaves LDS (without vectors none is formed and no dynamic LDS is asked for); no allocation,
+ * no host synchronisation, no read of device memory on the host.  The workspace is not used
+ * (digat_list_quality_workspace_bytes returns 0; workspace may be NULL). */
+size_t digat_list_quality_workspace_bytes(int64_t lists, int k, int kb);
+int digat_list_quality(const int64_t* ids, const int32_t* count, int64_t G, int k, int64_t N, const float* vectors, int d,
+                       const int32_t* category, const int64_t* base_ids, const int32_t* base_count, int kb, int32_t* exposure,
+                       int32_t* out_elements, double* out_sim_sum, float* out_sim_max, int32_t* out_categories, int32_t* out_category_max,
+                       int32_t* out_overlap, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- vanilla-GAT update layer of the ablation encoders -----------------------------------------
  * graphEncoders.py:493-519 (wo_interaction), :641-651 (News_graph_wo_inter), :788-798 (User_graph_wo_inter), eval mode:
  * h = X W^T + bW; e_ij = leaky_relu_0.2(a1.h_j + a2.h_i); -1e9 where A_ij = 0; alpha = softmax_j; out = relu(alpha h) + X.

@@ -23,7 +23,8 @@
                                              (c) 73 152 segments of the dev length distribution, k = 10; alternated in one process,
                                              median [min, max] of five rounds, bytes/s against the one-pass floor rows x 4 B
   python tools/kbench.py recommend [users news_num]   util.recommend: 64 users against the pool of all news at MIND-small shapes
-                                             (65 238 news, N = 10, H = 50, C = 17, d = 400, depth 3), users per second
+                                             (65 238 news, N = 10, H = 50, C = 17, d = 400, depth 3), users per second;
+                                             then util.recommend_report for four diversities beside four recommend(diversity=) calls
   python tools/kbench.py dot-topk [news_num d]   NRMS retrieval: evaluate.dot_topk (fused inner product + top-k, no score matrix)
                                              against torch.matmul + evaluate.topk_segments and torch.matmul + torch.topk, G = 64 and
                                              4 096 users x 65 237 news, d = 400, k = 10 and 100, the three legs in turn, median
@@ -39,6 +40,11 @@
                                              M = 128, d = 400, k = 10 and 100, with and without a cap of 2 per category, the legs in
                                              turn, median [min, max] of five rounds; then util.recommend for 64 users at k = 10 with
                                              and without diversity=0.3
+  python tools/kbench.py list-quality [news_num d]   list quality: evaluate.list_quality (one launch, the Gram in LDS) against the same
+                                             figures from gather + torch.bmm, the upper triangle's sum and max, a sort for the
+                                             categories, a broadcast compare for the overlap and torch.bincount for the exposure,
+                                             G = 64 and 4 096 lists of k = 10 and 100, d = 400, with and without category and base
+                                             list, the legs in turn, median [min, max] of five rounds
   python tools/kbench.py sag-lists [news categories dim top_M]  the SAG's similar-news lists of a MIND-small-shaped corpus
                                              (65 238 news over 17 categories of skewed sizes, the largest ~30 %, dim 768, top_M 5):
                                              construct_SAG.similar_news_lists_device per category against cos_topk_device + all five
@@ -920,6 +926,23 @@ def bench_recommend(users=64, news_num=65238, rounds=5):
     med_ms, best_ms = timeit(lambda: evaluate.topk_segments(scores, seg, 10, ids=cand, skip=skip), iters=10)
     print(f"  of which selection (topk_segments, ids + {skip.shape[1]}-entry skip rows): median {med_ms:.3f} ms, best {best_ms:.3f} ms "
           f"({rows * 12 / med_ms / 1e6:.1f} GB/s of scores + ids)", flush=True)
+    del scores
+    # the diversity sweep: one scoring pass for four diversities, beside four separate recommend(diversity=) calls
+    fs = (0.0, 0.1, 0.3, 0.5)
+    report = lambda: util.recommend_report(model, dc, who, pool, 10, fs)
+    separate = lambda: [util.recommend(model, dc, who, pool, 10, diversity=f) for f in fs]
+    report(), separate()
+    torch.cuda.synchronize()
+    secs = {"report": [], "separate": []}
+    for _ in range(rounds):
+        for name, fn in (("report", report), ("separate", separate)):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            secs[name].append(time.perf_counter() - t0)
+    (ra, rlo, rhi), (sa, slo, shi) = ((sorted(v)[len(v) // 2], min(v), max(v)) for v in (secs["report"], secs["separate"]))
+    print(f"  util.recommend_report, {len(fs)} diversities (lists and their quality): {ra:.3f} s [{rlo:.3f}, {rhi:.3f}] | {len(fs)} x "
+          f"util.recommend(diversity=) (lists alone): {sa:.3f} s [{slo:.3f}, {shi:.3f}] (x{sa / ra:.2f})", flush=True)
 
 
 def bench_dot_topk(news_num=65238, d=400, rounds=5):
@@ -1190,6 +1213,68 @@ def bench_diversify(news_num=65238, d=400, rounds=5):
           flush=True)
 
 
+def torch_list_quality(ids, count, vectors, category=None, base_ids=None, base_count=None, exposure=None):
+    """``evaluate.list_quality``'s figures built only from stock PyTorch: gather + ``torch.bmm``, the upper triangle's sum (in double)
+    and max, a sort per list for the categories, a broadcast compare for the overlap, ``torch.bincount`` for the exposure."""
+    G, k = ids.shape
+    N = int(vectors.shape[0])
+    slot = torch.arange(k, device=ids.device)
+    el = (slot[None, :] < count[:, None]) & (ids >= 0) & (ids < N)
+    safe = torch.where(el, ids, torch.zeros_like(ids))
+    out = {"elements": el.sum(dim=1, dtype=torch.int32)}
+    rows = vectors[safe]
+    gram = torch.bmm(rows, rows.transpose(1, 2))
+    pair = (el[:, :, None] & el[:, None, :]).triu(1)
+    out["sim_sum"] = torch.where(pair, gram, torch.zeros_like(gram)).sum(dim=(1, 2), dtype=torch.float64)
+    out["sim_max"] = torch.where(pair, gram, torch.full_like(gram, float("-inf"))).amax(dim=(1, 2))
+    if category is not None:
+        big = torch.iinfo(torch.int64).max
+        c = torch.where(el, category[safe].to(torch.int64), torch.full_like(safe, big)).sort(dim=1).values
+        new = torch.ones_like(c, dtype=torch.bool)
+        new[:, 1:] = c[:, 1:] != c[:, :-1]
+        out["categories"] = (new & (c != big)).sum(dim=1, dtype=torch.int32)
+        run = slot[None, :] - torch.where(new, slot[None, :], torch.zeros_like(c)).cummax(dim=1).values + 1
+        out["category_max"] = torch.where(c != big, run, torch.zeros_like(run)).amax(dim=1).to(torch.int32)
+    if base_ids is not None:
+        bel = (torch.arange(base_ids.shape[1], device=ids.device)[None, :] < base_count[:, None]) & (base_ids >= 0) & (base_ids < N)
+        hit = ((ids[:, :, None] == base_ids[:, None, :]) & bel[:, None, :]).any(dim=2)
+        out["overlap"] = (hit & el).sum(dim=1, dtype=torch.int32)
+    if exposure is not None:
+        exposure += torch.bincount(ids[el], minlength=N).to(torch.int32)
+        out["exposure"] = exposure
+    return out
+
+
+def bench_list_quality(news_num=65238, d=400, rounds=5):
+    """``evaluate.list_quality`` against ``torch_list_quality`` (what the tree had), the two legs in turn in one process, median
+    [min, max] of ``rounds`` rounds: G in {64, 4 096} lists of k in {10, 100} ids of a table of ``news_num`` unit rows, the
+    exposure histogram always, without and with category (17 values) and base list (the list rolled by k // 2)."""
+    from digat_amd import evaluate, util
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device="cpu").manual_seed(0)
+    table = util.unit_rows(torch.randn(news_num, d, generator=g).to(dev))
+    category = torch.randint(0, 17, (news_num,), generator=g, dtype=torch.int32).to(dev)
+    print(f"list-quality: lists of k ids of {news_num} unit rows, d = {d}; ms per call, median [min, max] of {rounds} rounds", flush=True)
+    for G in (64, 4096):
+        for k in (10, 100):
+            ids = torch.randint(0, news_num, (G, k), generator=g).to(dev)
+            count = torch.full((G,), k, dtype=torch.int32, device=dev)
+            base = torch.cat([ids[:, k // 2:], torch.randint(0, news_num, (G, k // 2), generator=g).to(dev)], dim=1).contiguous()
+            for extras in (False, True):
+                cat, b, bc = (category, base, count) if extras else (None, None, None)
+                ea, eb = (torch.zeros(news_num, dtype=torch.int32, device=dev) for _ in range(2))
+                ours = lambda: evaluate.list_quality(ids, count, table, cat, b, bc, ea)
+                stock = lambda: torch_list_quality(ids, count, table, cat, b, bc, eb)
+                got, want = ours(), stock()
+                torch.cuda.synchronize()
+                ints = all(torch.equal(got[key], want[key]) for key in got if key not in ("sim_sum", "sim_max"))
+                off = float((got["sim_sum"] - want["sim_sum"]).abs().max())
+                (a, alo, ahi), (bb, blo, bhi) = alternate(ours, stock, rounds=rounds, iters=5)
+                print(f"  G = {G:5d}, k = {k:3d}, category and base list {'yes' if extras else 'no '}: list_quality {a:8.3f} ms [{alo:.3f}, {ahi:.3f}] | "
+                      f"gather + bmm + torch reductions {bb:8.3f} ms [{blo:.3f}, {bhi:.3f}] (x{bb / a:.2f}) | integers equal: {ints}, "
+                      f"largest |sim_sum difference| {off:.2e}", flush=True)
+
+
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "xattn"
     nums = [int(v) for v in sys.argv[2:]]
@@ -1235,6 +1320,8 @@ if __name__ == "__main__":
         bench_dot_rank(*nums)
     elif what == "diversify":
         bench_diversify(*nums)
+    elif what == "list-quality":
+        bench_list_quality(*nums)
     elif what == "linear":
         bench_linear(*nums)
     elif what == "gemm":
