@@ -121,6 +121,11 @@ _SIGNATURES = {
     "digat_dot_topk_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
     "digat_dot_topk": (C.c_int, [_f, _f, _f, C.c_int64, C.c_int64, C.c_int64, C.c_int, _f, C.c_int, C.c_int, _f, _f, _f, _f, C.c_size_t, _f]),
     "digat_dot_scores": (C.c_int, [_f, _f, _f, C.c_int64, C.c_int64, C.c_int64, C.c_int, _f, _f]),
+    "digat_shortlist_segments_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
+    "digat_shortlist_segments": (C.c_int, [_f, _f, C.c_int64, C.c_int64, _f, _f, C.c_int, C.c_int, _f, _f, _f, _f, C.c_size_t, _f]),
+    "digat_dot_shortlist_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int, C.c_int64]),
+    "digat_dot_shortlist": (C.c_int, [_f, _f, _f, C.c_int64, C.c_int64, C.c_int64, C.c_int, _f, C.c_int, C.c_int, C.c_int64, _f, _f, _f, _f,
+                                      C.c_size_t, _f]),
     "digat_dot_rank_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
     "digat_dot_rank": (C.c_int, [_f, _f, _f, C.c_int64, C.c_int64, C.c_int64, C.c_int, _f, C.c_int, _f, _f, C.c_int64, _f, _f, _f, C.c_size_t, _f]),
     "digat_mmr_select_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),

@@ -32,6 +32,7 @@
 //   dot_chunk_kernel<true>    VGPRs 118   SGPRs 106   LDS 43008 B static   scratch 0   occupancy 3 waves / SIMD (by static LDS)
 //   dot_chunk_kernel<false>   VGPRs 74    SGPRs 69    LDS 43008 B static   scratch 0   occupancy 3 waves / SIMD (by static LDS)
 //   dot_topk_user_kernel      VGPRs 26    SGPRs 68    LDS 2632 B           scratch 0   occupancy 8 waves / SIMD
+// (unchanged by dot_chunk_kernel's CHUNK parameter, whose default instantiations these are; digat_shortlist.inc adds <false, 256>.)
 
 #define DOT_USERS DIGAT_DOT_TOPK_USERS
 #define DOT_SUB DIGAT_DOT_TOPK_SUB
@@ -257,14 +258,17 @@ __device__ __forceinline__ void dot_cut(DotShared& s, uint2* list, int u, int k,
     dot_wave_sync();
 }
 
-template <bool FUSED>
+// CHUNK: the pool positions one workgroup walks — DIGAT_DOT_TOPK_CHUNK for the entries of this file; digat_shortlist.inc stores a slab's
+// scores in shorter chunks (more workgroups for few users), the same sub-tiles through the same dot_tile: the same bits.
+template <bool FUSED, int CHUNK = DIGAT_DOT_TOPK_CHUNK>
 __global__ void __launch_bounds__(256) dot_chunk_kernel(const DotArgs a) {
     __shared__ DotShared s;
     extern __shared__ uint2 dot_lists[];            // [DOT_USERS][k + DOT_SUB]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long tile = blockIdx.x % a.tiles, chunk = blockIdx.x / a.tiles;
-    const long u0 = tile * DOT_USERS, p0 = chunk * DIGAT_DOT_TOPK_CHUNK;
-    const long pend = p0 + DIGAT_DOT_TOPK_CHUNK < a.P ? p0 + DIGAT_DOT_TOPK_CHUNK : a.P;
+    static_assert(CHUNK % DOT_SUB == 0, "a chunk is a whole number of sub-tiles");
+    const long u0 = tile * DOT_USERS, p0 = chunk * CHUNK;
+    const long pend = p0 + CHUNK < a.P ? p0 + CHUNK : a.P;
     const int cap = a.k + DOT_SUB;
     const int soft = 2 * a.k > 32 ? (2 * a.k < cap ? 2 * a.k : cap) : 32;      // cut early while that is cheap: a tighter threshold sooner
     if (FUSED) {

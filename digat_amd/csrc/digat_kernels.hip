@@ -881,6 +881,7 @@ int digat_row_logits(const float* news_ctx, const float* user_ctx, float* logits
 #include "digat_train_input.inc"
 #include "digat_ablation.inc"
 #include "digat_dot_topk.inc"
+#include "digat_shortlist.inc"
 #include "digat_dot_rank.inc"
 #include "digat_mmr.inc"
 #include "digat_listq.inc"

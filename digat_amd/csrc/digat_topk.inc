@@ -67,16 +67,18 @@ __device__ __forceinline__ void topk_win(TopkShared& sh, unsigned key, long i) {
     if (slot < TOPK_MAX_K) { sh.win_key[slot] = key; sh.win_idx[slot] = i; }       // never more than k: the list cannot be overrun
 }
 
-// The k best of the n elements ld.key(0 .. n-1) (key 0: not an element): sh.nwin <= k winners in sh.win_key / sh.win_idx, in no
-// particular order.  Called by the whole workgroup (256 threads); ends behind a barrier.
-template <class Load>
-__device__ void topk_select(const Load& ld, long n, int k, TopkShared& sh) {
+// The k-th largest key T of ld.key(0 .. n-1) (key 0: not an element) and the number `need` of elements equal to T that win beside
+// every key above T; T = 0, need = 0 when at most k elements exist: all of them win.  Four rounds of radix select on sh.hist.
+// `Shared`: TopkShared here, ShortShared in digat_shortlist.inc.  Called by the whole workgroup (256 threads); every thread gets the
+// same T and need.
+template <class Load, class Shared>
+__device__ __forceinline__ void topk_threshold(const Load& ld, long n, int k, Shared& sh, unsigned& T, unsigned& need) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     sh.hist[tid] = 0;
-    if (tid == 0) { sh.nvalid = 0; sh.nwin = 0; }
+    if (tid == 0) sh.nvalid = 0;
     __syncthreads();
     unsigned prefix = 0, mask = 0, krem = 0;
-    unsigned T = 0, need = 0;                      // winners: key > T, and the first `need` with key == T
+    T = 0; need = 0;                               // winners: key > T, and the first `need` with key == T
     for (int round = 0; round < 4; ++round) {
         const int shift = 24 - 8 * round;
         unsigned mine = 0;
@@ -119,6 +121,16 @@ __device__ void topk_select(const Load& ld, long n, int k, TopkShared& sh) {
             if (sh.bin_count == need) { T -= 1; need = 0; }      // every element equal to T wins: key >= T, nothing to order
         }
     }
+}
+
+// The k best of the n elements ld.key(0 .. n-1) (key 0: not an element): sh.nwin <= k winners in sh.win_key / sh.win_idx, in no
+// particular order.  Called by the whole workgroup (256 threads); ends behind a barrier.
+template <class Load>
+__device__ void topk_select(const Load& ld, long n, int k, TopkShared& sh) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) sh.nwin = 0;
+    unsigned T, need;
+    topk_threshold(ld, n, k, sh, T, need);
     unsigned run = 0;                               // elements equal to T met so far (the same in every thread)
     int buf = 0;
     for (long base = 0; base < n; base += 256) {
@@ -313,9 +325,11 @@ __global__ void __launch_bounds__(256) topk_segment_kernel(const TopkArgs a) {
 
 static long topk_slots(long rows, long segments) { return rows / DIGAT_TOPK_CHUNK + segments; }
 
-// What both selection entries ask of k, the skip rows and the workspace; the entry's verdict `rc` on the rest ranks in between.
-static int topk_check_args(int k, const int64_t*& skip, int& skip_len, int rc, bool need_workspace, const void* workspace) {
-    if (k < 1 || k > TOPK_MAX_K || skip_len < 0 || skip_len > TOPK_MAX_SKIP) return DIGAT_ERR_ARG;
+// What the selection entries ask of k (at most `max_k`: digat_shortlist.inc takes longer lists), the skip rows and the workspace; the
+// entry's verdict `rc` on the rest ranks in between.
+static int topk_check_args(int k, const int64_t*& skip, int& skip_len, int rc, bool need_workspace, const void* workspace,
+                           int max_k = TOPK_MAX_K) {
+    if (k < 1 || k > max_k || skip_len < 0 || skip_len > TOPK_MAX_SKIP) return DIGAT_ERR_ARG;
     if (rc != DIGAT_OK) return rc;
     if (!skip || skip_len == 0) { skip = nullptr; skip_len = 0; }
     return need_workspace && (!workspace || ((uintptr_t)workspace & 7)) ? DIGAT_ERR_ARG : DIGAT_OK;

@@ -136,6 +136,10 @@ def ranks_metrics_file(scores, row_impression: np.ndarray, labels=None, result_f
 TOPK_CHUNK = 16384       # include/digat_hip.h: DIGAT_TOPK_CHUNK, the elements one level-1 workgroup of digat_topk_segments selects from
 TOPK_MAX_K = 128
 TOPK_MAX_SKIP = 256
+SHORTLIST_MAX_K = 1024   # include/digat_hip.h: DIGAT_SHORTLIST_MAX_K, the longest list of digat_shortlist_segments / digat_dot_shortlist
+SHORTLIST_SLAB_USERS = 256      # the users digat_dot_shortlist scores at a time when the caller names no slab
+_TOPK_LIMIT = ("k", "%d" % TOPK_MAX_K, TOPK_MAX_K)      # what a selection calls its list length, how it words the bound, the bound
+_SHORTLIST_LIMIT = ("m", "SHORTLIST_MAX_K = %d" % SHORTLIST_MAX_K, SHORTLIST_MAX_K)
 
 
 def topk_keys(scores: np.ndarray) -> np.ndarray:
@@ -155,9 +159,13 @@ def topk_segments_host(scores, seg_start, k: int, ids=None, skip=None):
     in the segment's ``skip`` row, in a stable descending sort of their keys (``topk_keys``: ties keep position order, NaNs last),
     the first k of them.  Returns ``(scores [S,k] float32, ids [S,k] int64, count [S] int32)``; slots at or beyond ``count`` hold
     ``-inf`` / ``-1``; without ``ids`` the position inside the segment is returned."""
+    return _select_segments_host(scores, seg_start, k, ids, skip, _TOPK_LIMIT)
+
+
+def _select_segments_host(scores, seg_start, k, ids, skip, limit):
     sc = np.ascontiguousarray(scores, dtype=np.float32)
     st = np.asarray(seg_start, dtype=np.int64)
-    _check_topk_args(len(sc), st.shape, k, None if ids is None else np.shape(ids), None if skip is None else np.shape(skip))
+    _check_topk_args(len(sc), st.shape, k, None if ids is None else np.shape(ids), None if skip is None else np.shape(skip), limit)
     S = len(st) - 1
     out_s = np.full((S, k), -np.inf, dtype=np.float32)
     out_i = np.full((S, k), -1, dtype=np.int64)
@@ -178,9 +186,15 @@ def topk_segments_host(scores, seg_start, k: int, ids=None, skip=None):
     return out_s, out_i, count
 
 
-def _check_topk_args(rows, start_shape, k, ids_shape, skip_shape):
-    if not 1 <= int(k) <= TOPK_MAX_K:
-        raise ValueError(f"k must be in [1, {TOPK_MAX_K}], got {k}")
+def _check_limit(k, limit=_TOPK_LIMIT) -> int:
+    name, words, bound = limit
+    if not 1 <= int(k) <= bound:
+        raise ValueError(f"{name} must be in [1, {words}], got {k}")
+    return int(k)
+
+
+def _check_topk_args(rows, start_shape, k, ids_shape, skip_shape, limit=_TOPK_LIMIT):
+    _check_limit(k, limit)
     if len(start_shape) != 1 or start_shape[0] < 1:
         raise ValueError("seg_start must be a 1-D array of segments + 1 row offsets")
     if ids_shape is not None and tuple(ids_shape) != (rows,):
@@ -199,12 +213,16 @@ def topk_segments(scores, seg_start, k: int, ids=None, skip=None):
     (returned in place of positions) and ``skip`` [S, L <= 256] int64 (ids a segment must not return) are optional.  Order: score
     descending, ties by position — the rank file's; NaNs last.  Returns ``(scores [S,k] float32, ids [S,k] int64, count [S] int32)``
     on the device; slots at or beyond ``count`` hold ``-inf`` / ``-1``.  Stream-ordered: nothing is read back."""
+    return _select_segments(scores, seg_start, k, ids, skip, _TOPK_LIMIT, "digat_topk_segments", "topk")
+
+
+def _select_segments(scores, seg_start, k, ids, skip, limit, entry, tag):
     import torch
     from . import _lib
     given = [t for t in (scores, seg_start, ids, skip) if t is not None]
     dev = _lib.require_device(*given)
     _check_topk_args(int(scores.shape[0]) if scores.dim() == 1 else -1, tuple(seg_start.shape), k,
-                     None if ids is None else tuple(ids.shape), None if skip is None else tuple(skip.shape))
+                     None if ids is None else tuple(ids.shape), None if skip is None else tuple(skip.shape), limit)
     if scores.dim() != 1:
         raise ValueError("scores must be 1-D")
     sc = _lib.f32(scores.detach())
@@ -218,14 +236,26 @@ def topk_segments(scores, seg_start, k: int, ids=None, skip=None):
     if S == 0:
         return out_s, out_i, count
     L = _lib.lib()
-    need = int(L.digat_topk_segments_workspace_bytes(R, S, k))
-    ws = _lib.workspace(need, dev, "topk")
+    need = int(getattr(L, entry + "_workspace_bytes")(R, S, k))
+    ws = _lib.workspace(need, dev, tag)
     dummy = ws if R == 0 else sc                        # an empty tensor has no storage to point at
-    _lib.check(L.digat_topk_segments(dummy.data_ptr(), st.data_ptr(), R, S, _lib.ptr(idt) if R else None,
-                                     _lib.ptr(sk) if R else None, 0 if sk is None or not R else int(sk.shape[1]), k,
-                                     out_s.data_ptr(), out_i.data_ptr(), count.data_ptr(), ws.data_ptr(), need, _lib.stream_ptr()),
-               "digat_topk_segments")
+    _lib.check(getattr(L, entry)(dummy.data_ptr(), st.data_ptr(), R, S, _lib.ptr(idt) if R else None,
+                                 _lib.ptr(sk) if R else None, 0 if sk is None or not R else int(sk.shape[1]), k,
+                                 out_s.data_ptr(), out_i.data_ptr(), count.data_ptr(), ws.data_ptr(), need, _lib.stream_ptr()),
+               entry)
     return out_s, out_i, count
+
+
+def shortlist_segments_host(scores, seg_start, m: int, ids=None, skip=None):
+    """The contract of ``digat_shortlist_segments`` in numpy: ``topk_segments_host`` with lists of up to ``SHORTLIST_MAX_K``."""
+    return _select_segments_host(scores, seg_start, m, ids, skip, _SHORTLIST_LIMIT)
+
+
+def shortlist_segments(scores, seg_start, m: int, ids=None, skip=None):
+    """``topk_segments`` for lists of up to ``SHORTLIST_MAX_K`` = 1024 entries, on the GPU (``digat_shortlist_segments``): the same
+    arguments, order and returns — ``(scores [S,m] float32, ids [S,m] int64, count [S] int32)`` — and for ``m <= 128`` the same bits.
+    The winners of a long list are ordered by a sort in LDS where ``topk_segments`` counts ranks."""
+    return _select_segments(scores, seg_start, m, ids, skip, _SHORTLIST_LIMIT, "digat_shortlist_segments", "shortlist")
 
 
 DOT_TOPK_CHUNK = 2048    # include/digat_hip.h: DIGAT_DOT_TOPK_CHUNK, the pool positions one level-1 workgroup of digat_dot_topk walks
@@ -233,7 +263,7 @@ DOT_TOPK_USERS = 64      # ... DIGAT_DOT_TOPK_USERS, the users of that workgroup
 DOT_TOPK_SUB = 64        # ... DIGAT_DOT_TOPK_SUB, the pool positions of one product sub-tile
 
 
-def dot_topk_host(scores, k: int, pool=None, skip=None):
+def dot_topk_host(scores, k: int, pool=None, skip=None, limit=_TOPK_LIMIT):
     """The contract of ``digat_dot_topk`` on a given score matrix ``scores`` [G, P], in numpy: ``topk_segments_host`` over G
     segments of length P whose ids are ``pool`` (the positions when None).  Returns ``(scores [G,k], ids [G,k], count [G])``."""
     S = np.ascontiguousarray(scores, dtype=np.float32)
@@ -243,16 +273,21 @@ def dot_topk_host(scores, k: int, pool=None, skip=None):
     ids = np.arange(P, dtype=np.int64) if pool is None else np.asarray(pool, dtype=np.int64)
     if ids.shape != (P,):
         raise ValueError(f"pool must have one id per column ({P}), got shape {ids.shape}")
-    return topk_segments_host(S.ravel(), np.arange(G + 1, dtype=np.int64) * P, k, ids=np.tile(ids, G), skip=skip)
+    return _select_segments_host(S.ravel(), np.arange(G + 1, dtype=np.int64) * P, k, np.tile(ids, G), skip, limit)
 
 
-def _check_dot_args(users, news, pool, skip=None, k=None):
+def dot_shortlist_host(scores, m: int, pool=None, skip=None):
+    """The contract of ``digat_dot_shortlist`` on a given score matrix: ``dot_topk_host`` with lists of up to ``SHORTLIST_MAX_K``."""
+    return dot_topk_host(scores, m, pool=pool, skip=skip, limit=_SHORTLIST_LIMIT)
+
+
+def _check_dot_args(users, news, pool, skip=None, k=None, limit=_TOPK_LIMIT):
     import torch
     if users.dim() != 2 or news.dim() != 2 or users.shape[1] != news.shape[1] or users.shape[1] < 1:
         raise ValueError(f"users [G, d] and news [N, d] must share d >= 1, got {tuple(users.shape)} and {tuple(news.shape)}")
     G, N = int(users.shape[0]), int(news.shape[0])
-    if k is not None and not 1 <= int(k) <= TOPK_MAX_K:
-        raise ValueError(f"k must be in [1, {TOPK_MAX_K}], got {k}")
+    if k is not None:
+        _check_limit(k, limit)
     if pool is not None:
         if pool.dim() != 1 or pool.dtype in (torch.float16, torch.float32, torch.float64, torch.bool):
             raise ValueError("pool must be a 1-D integer tensor of news rows")
@@ -270,11 +305,16 @@ def dot_topk(users, news, k: int, pool=None, skip=None):
     ``(scores [G,k] float32, ids [G,k] int64, count [G] int32)`` on the device; slots at or beyond ``count`` hold ``-inf`` / ``-1``.
     A score is the fp32 fmaf chain over the d channels: the bits ``dot_scores`` gives.  Stream-ordered; only the pool's id range is
     read back, for the check."""
+    return _dot_select(users, news, k, pool, skip, _TOPK_LIMIT, None)
+
+
+def _dot_select(users, news, k, pool, skip, limit, slab_users):
+    """``dot_topk`` (``slab_users`` None) or ``dot_shortlist``: the checks, the outputs, the workspace and the call."""
     import torch
     from . import _lib
     given = [t for t in (users, news, pool, skip) if t is not None]
     dev = _lib.require_device(*given)
-    G, N, P, d = _check_dot_args(users, news, pool, skip, k)
+    G, N, P, d = _check_dot_args(users, news, pool, skip, k, limit)
     u, v = _lib.f32(users.detach()), _lib.f32(news.detach())
     pl = None if pool is None else pool.to(torch.int64).contiguous()
     sk = None if skip is None or skip.shape[1] == 0 else skip.to(torch.int64).contiguous()
@@ -285,12 +325,29 @@ def dot_topk(users, news, k: int, pool=None, skip=None):
     if G == 0 or P == 0:
         return out_s, out_i, count
     L = _lib.lib()
-    need = int(L.digat_dot_topk_workspace_bytes(G, P, k))
-    ws = _lib.workspace(need, dev, "dot_topk")
-    _lib.check(L.digat_dot_topk(u.data_ptr(), v.data_ptr(), _lib.ptr(pl), G, N, P, d, _lib.ptr(sk), 0 if sk is None else int(sk.shape[1]),
-                                k, out_s.data_ptr(), out_i.data_ptr(), count.data_ptr(), ws.data_ptr(), need, _lib.stream_ptr()),
-               "digat_dot_topk")
+    head = (u.data_ptr(), v.data_ptr(), _lib.ptr(pl), G, N, P, d, _lib.ptr(sk), 0 if sk is None else int(sk.shape[1]), k)
+    outs = (out_s.data_ptr(), out_i.data_ptr(), count.data_ptr())
+    if slab_users is None:
+        need = int(L.digat_dot_topk_workspace_bytes(G, P, k))
+        ws = _lib.workspace(need, dev, "dot_topk")
+        _lib.check(L.digat_dot_topk(*head, *outs, ws.data_ptr(), need, _lib.stream_ptr()), "digat_dot_topk")
+    else:
+        need = int(L.digat_dot_shortlist_workspace_bytes(G, P, k, slab_users))
+        ws = _lib.workspace(need, dev, "dot_shortlist")
+        _lib.check(L.digat_dot_shortlist(*head, slab_users, *outs, ws.data_ptr(), need, _lib.stream_ptr()), "digat_dot_shortlist")
     return out_s, out_i, count
+
+
+def dot_shortlist(users, news, m: int, pool=None, skip=None, slab_users=None):
+    """``dot_topk`` for lists of up to ``SHORTLIST_MAX_K`` = 1024 entries (``digat_dot_shortlist``): the same arguments, elements,
+    score bits, order and returns — ``(scores [G,m] float32, ids [G,m] int64, count [G] int32)``.  Lists this long do not fit the
+    fused kernel's LDS, so the users are walked in slabs of ``slab_users`` (None: ``SHORTLIST_SLAB_USERS`` = 256; never more than
+    G): per slab the [slab, P] scores are stored — ``dot_scores``' kernel — and selected from.  The workspace, slab x P x 4 bytes
+    plus the selection's, does not grow with G; the results do not depend on the slab."""
+    slab = SHORTLIST_SLAB_USERS if slab_users is None else int(slab_users)
+    if slab < 1:
+        raise ValueError(f"slab_users must be positive, got {slab_users}")
+    return _dot_select(users, news, m, pool, skip, _SHORTLIST_LIMIT, max(1, min(slab, int(users.shape[0]))))
 
 
 def dot_scores(users, news, pool=None):

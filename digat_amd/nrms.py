@@ -533,9 +533,16 @@ def recommend(model, dev, users, candidates=None, k=10, exclude_history=True, ba
                                              getattr(dev, "news_category", None))[1][0]
     if shortlist is not None or category is not None or max_per_category:
         raise ValueError("shortlist, category and max_per_category belong to a diversified call: name diversity (0.0: the cap alone)")
+    return _retrieve(model, dev, users, candidates, k, exclude_history, batch_size, False)
+
+
+def _retrieve(model, dev, users, candidates, k, exclude_history, batch_size, long_lists):
+    """``recommend`` without diversity (k <= 128: ``dot_topk`` / ``topk_segments``) or, with ``long_lists``, ``shortlist`` (k <= 1024:
+    ``dot_shortlist`` / ``shortlist_segments``): the same caches, user vectors, skip rows and chunk loop."""
+    from . import evaluate, util
     hist, mask = _histories(dev, users)
     G, N = int(hist.shape[0]), int(dev.title_text.shape[0])
-    k = util.recommend_limits(k, int(hist.shape[1]) if exclude_history else 0)
+    k = util.recommend_limits(k, int(hist.shape[1]) if exclude_history else 0, long_lists)
     if candidates is None:
         candidates = np.arange(1, N, dtype=np.int64)
     ids, start = util.recommend_candidates(candidates, G, N)
@@ -546,14 +553,27 @@ def recommend(model, dev, users, candidates=None, k=10, exclude_history=True, ba
     user = _encode_users(model, plain, hist, mask, batch_size)
     skip = torch.where(mask != 0, hist, torch.zeros_like(hist)) if exclude_history else None
     if cuda and start is None:
-        s, i, c = evaluate.dot_topk(user, aug, k, pool=ids, skip=skip)
+        s, i, c = (evaluate.dot_shortlist if long_lists else evaluate.dot_topk)(user, aug, k, pool=ids, skip=skip)
         return i, s, c
 
     def score(g0, g1, row_user, row_cand):
         c, u = aug.index_select(0, row_cand), user.index_select(0, row_user)
         return row_logits(c, u) if cuda else (c * u).sum(dim=1)
     # on the CPU one chunk holds all pairs
-    return util.recommend_select(G, k, ids, start, skip, util.RECOMMEND_MAX_ROWS if cuda else max(1, G * int(ids.shape[0])), score)
+    return util.recommend_select(G, k, ids, start, skip, util.RECOMMEND_MAX_ROWS if cuda else max(1, G * int(ids.shape[0])), score,
+                                 long_lists=long_lists)
+
+
+def shortlist(model, dev, users, candidates=None, m=512, exclude_history=True, batch_size=1024):
+    """``recommend`` for the retrieval stage in front of a re-rank: for every user the m <= ``evaluate.SHORTLIST_MAX_K`` = 1024 best
+    news, in order — ``(news_ids [G,m] int64, scores [G,m] float32, count [G] int32)`` — where ``recommend`` stops at 128.  ``dev``,
+    ``users``, ``candidates``, ``exclude_history`` and ``batch_size`` are ``recommend``'s, and so are the caches, the user vectors,
+    the skip rows, the order and the fill; for ``m <= 128`` the lists are ``recommend``'s, bit for bit.  A shared pool goes through
+    ``evaluate.dot_shortlist`` (scores stored a slab of users at a time, then selected), per-user lists through gather,
+    ``row_logits`` and ``evaluate.shortlist_segments``; on CPU tensors: stock PyTorch and ``shortlist_segments_host``.  How long the
+    list must be: ``retrieval_metrics`` and ``evaluate.shortlist_for``; ``candidates_csr`` turns the result into the per-user
+    lists ``util.recommend`` re-ranks."""
+    return _retrieve(model, dev, users, candidates, m, exclude_history, batch_size, True)
 
 
 def recommend_report(model, dev, users, candidates=None, k=10, diversities=(0.0, 0.1, 0.3, 0.5), shortlist=None, category=None,

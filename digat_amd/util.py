@@ -886,24 +886,27 @@ def recommend_user_chunks(users: int, ids_len: int, start: Optional[np.ndarray],
     return out
 
 
-def recommend_limits(k, skip_len: int) -> int:
-    """``k`` as an int, once it and the length of the skip rows (histories) are what ``evaluate.topk_segments`` takes."""
-    if not 1 <= int(k) <= evaluate.TOPK_MAX_K:
-        raise ValueError(f"k must be in [1, {evaluate.TOPK_MAX_K}], got {k}")
+def recommend_limits(k, skip_len: int, long_lists: bool = False) -> int:
+    """``k`` as an int, once it and the length of the skip rows (histories) are what ``evaluate.topk_segments`` takes — or, with
+    ``long_lists``, what ``evaluate.shortlist_segments`` takes."""
+    evaluate._check_limit(k, evaluate._SHORTLIST_LIMIT if long_lists else evaluate._TOPK_LIMIT)
     if skip_len > evaluate.TOPK_MAX_SKIP:
         raise ValueError(f"exclude_history takes histories of at most {evaluate.TOPK_MAX_SKIP} news, this corpus has {skip_len}")
     return int(k)
 
 
 def recommend_select(G: int, k: int, ids: torch.Tensor, start: Optional[np.ndarray], skip: Optional[torch.Tensor], max_rows: int,
-                     score: Callable, prepare: Optional[Callable] = None):
+                     score: Callable, prepare: Optional[Callable] = None, long_lists: bool = False):
     """Select k per user over chunked (user, candidate) pairs: ``(news_ids [G,k] int64, scores [G,k] float32, count [G] int32)`` on
     the device of ``ids``, rows without pairs and slots at or beyond ``count`` holding id -1 and score -inf.  ``ids`` / ``start``
     as ``recommend_candidates`` returns them; ``skip`` [G, L] holds ids user g must not get, or None.  Users are taken in chunks
     of at most ``max_rows`` pairs (``recommend_user_chunks``); ``score(g0, g1, row_user, row_cand)`` returns the scores [r] of a
     chunk's pairs (``recommend_rows``), which ``evaluate.topk_segments`` selects from — ``topk_segments_host`` for host scores.
-    ``prepare()`` runs once, behind the argument checks and before the first ``score``."""
-    k = recommend_limits(k, 0 if skip is None else int(skip.shape[1]))
+    ``prepare()`` runs once, behind the argument checks and before the first ``score``.  ``long_lists``: k up to
+    ``evaluate.SHORTLIST_MAX_K``, selected by ``evaluate.shortlist_segments`` / ``shortlist_segments_host``."""
+    k = recommend_limits(k, 0 if skip is None else int(skip.shape[1]), long_lists)
+    on_device, on_host = ((evaluate.shortlist_segments, evaluate.shortlist_segments_host) if long_lists else
+                          (evaluate.topk_segments, evaluate.topk_segments_host))
     chunks = recommend_user_chunks(G, int(ids.shape[0]), start, int(max_rows))
     if prepare is not None:
         prepare()
@@ -916,10 +919,10 @@ def recommend_select(G: int, k: int, ids: torch.Tensor, start: Optional[np.ndarr
             continue
         scores, sk = score(g0, g1, row_user, row_cand), None if skip is None else skip[g0:g1]
         if scores.is_cuda:
-            s, i, c = evaluate.topk_segments(scores, seg, k, ids=row_cand, skip=sk)
+            s, i, c = on_device(scores, seg, k, ids=row_cand, skip=sk)
         else:
-            s, i, c = map(torch.from_numpy, evaluate.topk_segments_host(scores.numpy(), seg.numpy(), k, ids=row_cand.numpy(),
-                                                                        skip=None if sk is None else sk.numpy()))
+            s, i, c = map(torch.from_numpy, on_host(scores.numpy(), seg.numpy(), k, ids=row_cand.numpy(),
+                                                    skip=None if sk is None else sk.numpy()))
         out_scores[g0:g1], out_ids[g0:g1], out_count[g0:g1] = s, i, c
     return out_ids, out_scores, out_count
 

@@ -629,6 +629,33 @@ int digat_dot_topk(const float* users, const float* news, const int64_t* pool, i
 int digat_dot_scores(const float* users, const float* news, const int64_t* pool, int64_t G, int64_t N, int64_t P, int d, float* out,
                      void* stream);
 
+/* ---- long shortlists: the two selections above for lists of up to 1024 entries (digat_amd.nrms.shortlist) ------------------------
+ * digat_shortlist_segments is digat_topk_segments' contract to the letter with 1 <= m <= DIGAT_SHORTLIST_MAX_K in place of
+ * 1 <= k <= 128: elements, order (topk_key descending, ties by position, NaNs last, -0.0 == +0.0), ids, skip rows (skip_len <= 256,
+ * skip needs ids), the seg_start held inside [0, rows] and made non-decreasing (a malformed array gives wrong numbers, no access
+ * outside the arrays), outputs [segments, m] with -inf / -1 at and beyond out_count, every output byte written, the refusals and
+ * their order, segments == 0 returning DIGAT_OK.  For m <= 128 its outputs are digat_topk_segments', bit for bit.  Workspace: 8 m
+ * bytes per chunk slot (rows / DIGAT_TOPK_CHUNK + segments of them; it may hold anything on entry).  Stream-ordered: two launches
+ * sized by rows and segments alone (one workgroup per chunk of DIGAT_TOPK_CHUNK elements — none when rows <= 1024 —, then one per
+ * segment, which orders its winners by a sort in LDS); no allocation, no host synchronisation, no read of seg_start on the host.
+ * digat_dot_shortlist is digat_dot_topk's contract with that bound: elements (pool ids in [0, N), not in skip[g]), scores (the bits
+ * digat_dot_scores stores), order, outputs and refusals are its.  The users are walked in slabs of slab_users (<= 0: 256; any
+ * positive value is legal and the results do not depend on it): per slab digat_dot_scores' kernel stores [slab, P] scores in the
+ * workspace and the selection runs over them as slab segments of length P, so the workspace — slab * P * 4 bytes, rounded up to
+ * 256, plus 8 m bytes per (slab user, chunk of DIGAT_TOPK_CHUNK pool positions) — depends on slab_users and not on G.  The shape
+ * limits (DIGAT_ERR_SHAPE) hold per slab.  G == 0 returns DIGAT_OK without a launch; P == 0 sets every count to 0; neither needs a
+ * workspace.  Stream-ordered: up to three launches per slab, their number and sizes given by G, P and slab_users alone; no
+ * allocation, no host synchronisation, no read of device memory on the host. */
+#define DIGAT_SHORTLIST_MAX_K 1024
+size_t digat_shortlist_segments_workspace_bytes(int64_t rows, int64_t segments, int m);
+int digat_shortlist_segments(const float* scores, const int64_t* seg_start, int64_t rows, int64_t segments, const int64_t* ids,
+                             const int64_t* skip, int skip_len, int m, float* out_scores, int64_t* out_ids, int32_t* out_count,
+                             void* workspace, size_t workspace_bytes, void* stream);
+size_t digat_dot_shortlist_workspace_bytes(int64_t G, int64_t P, int m, int64_t slab_users);
+int digat_dot_shortlist(const float* users, const float* news, const int64_t* pool, int64_t G, int64_t N, int64_t P, int d,
+                        const int64_t* skip, int skip_len, int m, int64_t slab_users, float* out_scores, int64_t* out_ids,
+                        int32_t* out_count, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- retrieval evaluation: the rank of given targets in a user's whole ordered pool (digat_amd.nrms.retrieval_metrics) ---------
  * users, news, pool, G, N, P, d, skip, skip_len: digat_dot_topk's, and so are the elements of user g (the pool positions whose id
  * lies in [0, N) and is not in skip[g]; repeated ids are distinct elements, skip rows may repeat ids), their scores (the bits

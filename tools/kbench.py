@@ -29,6 +29,13 @@
                                              against torch.matmul + evaluate.topk_segments and torch.matmul + torch.topk, G = 64 and
                                              4 096 users x 65 237 news, d = 400, k = 10 and 100, the three legs in turn, median
                                              [min, max] of five rounds; then nrms.recommend for 4 096 users end to end
+  python tools/kbench.py shortlist           long segmented selection (digat_shortlist_segments): 256 segments of 65 238 scores at
+                                             m = 128, 256 and 1 024 against torch.topk and, at 128, against digat_topk_segments; the
+                                             legs in turn in one process, median [min, max] of five rounds
+  python tools/kbench.py dot-shortlist [news_num d]   NRMS retrieval of long lists: evaluate.dot_shortlist (scores a slab of 256 users
+                                             at a time, then the selection) against torch.matmul per 1 024 users + torch.topk, G = 64
+                                             and 4 096 users x 65 237 news, d = 400, m = 256 and 1 024, 50-entry skip rows, the legs in
+                                             turn, median [min, max] of five rounds, time and peak device bytes
   python tools/kbench.py dot-rank [news_num d]   retrieval evaluation: evaluate.dot_rank (fused inner product + rank of given targets,
                                              no score matrix) against the same ranks from evaluate.dot_scores or torch.matmul over
                                              chunks of 1 024 users + torch compares and sums with the skip mask, G = 64 and 4 096
@@ -1012,6 +1019,106 @@ def bench_dot_topk(news_num=65238, d=400, rounds=5):
           f"of which dot_topk with the pool and {H}-entry skip rows {sel:.3f} ms", flush=True)
 
 
+def bench_shortlist(rounds=5):
+    """``digat_shortlist_segments`` (the C entry, buffers allocated once) on 256 segments of 65 238 scores at m in {128, 256, 1024},
+    against ``torch.topk`` (tie order unspecified: a yardstick for speed only) and, at 128, against ``digat_topk_segments``; the legs
+    taken in turn in one process, median [min, max] of ``rounds`` rounds.  GB/s = rows x 4 B / time: the floor is one pass."""
+    dev = torch.device("cuda:0")
+    L = _lib.lib()
+    g = torch.Generator(device="cpu").manual_seed(0)
+    S, P = 256, 65238
+    R = S * P
+    scores = torch.randn(R, generator=g).to(dev)
+    start = (torch.arange(S + 1, dtype=torch.int64) * P).to(dev)
+    stat = lambda v: (sorted(v)[len(v) // 2], min(v), max(v))
+
+    def entry(name, m):
+        need = int(getattr(L, name + "_workspace_bytes")(R, S, m))
+        ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        outs = (torch.empty((S, m), dtype=torch.float32, device=dev), torch.empty((S, m), dtype=torch.int64, device=dev),
+                torch.empty((S,), dtype=torch.int32, device=dev))
+
+        def run():
+            _lib.check(getattr(L, name)(scores.data_ptr(), start.data_ptr(), R, S, None, None, 0, m, outs[0].data_ptr(), outs[1].data_ptr(),
+                                        outs[2].data_ptr(), ws.data_ptr(), need, _lib.stream_ptr()), name)
+        return run, outs, need
+    print(f"shortlist: {S} segments of {P} scores; us per call, median [min, max] of {rounds} rounds", flush=True)
+    for m in (128, 256, 1024):
+        run, outs, need = entry("digat_shortlist_segments", m)
+        stock = lambda: torch.topk(scores.view(S, P), m, dim=1)
+        legs = [("digat_shortlist_segments", run), ("torch.topk", stock)]
+        run()
+        want = stock()
+        torch.cuda.synchronize()
+        assert torch.equal(outs[0], want.values), "scores differ from torch.topk's"         # equal scores may swap their indices there
+        assert torch.equal(scores.view(S, P).gather(1, outs[1]), outs[0]) and bool((outs[2] == m).all())
+        if m <= 128:
+            old, old_outs, _ = entry("digat_topk_segments", m)
+            old()
+            torch.cuda.synchronize()
+            assert all(torch.equal(a, b) for a, b in zip(outs, old_outs)), "lists differ from digat_topk_segments'"
+            legs.append(("digat_topk_segments", old))
+        times = [[] for _ in legs]
+        for _ in range(rounds):
+            for leg, (_, fn) in zip(times, legs):
+                leg.append(timeit(fn, iters=10, warm=1)[0])
+        base = stat(times[0])[0]
+        print(f"  m = {m:4d} (workspace {need / 2**20:.1f} MiB): " + " | ".join(
+            f"{name} {a * 1e3:9.1f} us [{lo * 1e3:.1f}, {hi * 1e3:.1f}] {R * 4 / a / 1e6:7.1f} GB/s" + ("" if n == 0 else f" (x{a / base:.2f})")
+            for n, ((name, _), (a, lo, hi)) in enumerate(zip(legs, map(stat, times)))), flush=True)
+
+
+def bench_dot_shortlist(news_num=65238, d=400, rounds=5):
+    """``evaluate.dot_shortlist`` (scores stored a slab of 256 users at a time, then the long selection) against ``torch.matmul`` per
+    1 024 users + the skip positions set to -inf + ``torch.topk`` (tie order unspecified and another rounding of the products: a
+    yardstick for speed and memory only), G in {64, 4 096} users x all but the PAD row of a MIND-small-sized table, m in {256, 1024},
+    50-entry skip rows; the two legs in turn in one process, median [min, max] of ``rounds`` rounds, and the peak device bytes of a
+    first call (workspace included)."""
+    from digat_amd import evaluate
+    dev = torch.device("cuda:0")
+    L = _lib.lib()
+    g = torch.Generator(device="cpu").manual_seed(0)
+    table = torch.randn(news_num, d, generator=g).to(dev)[1:].contiguous()
+    P = news_num - 1
+
+    def peak(fn):
+        _lib._workspaces.clear()                                      # a first call: the workspace is part of the peak
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        out = fn()
+        torch.cuda.synchronize()
+        return out, torch.cuda.max_memory_allocated() - base
+    print(f"dot-shortlist: P = {P} news, d = {d}, 50-entry skip rows; ms per call, median [min, max] of {rounds} rounds", flush=True)
+    for G in (4096, 64):
+        users = torch.randn(G, d, generator=g).to(dev)
+        skip_pos = torch.randint(1, P, (G, 50), generator=g).to(dev)
+        for m in (256, 1024):
+            ours = lambda: evaluate.dot_shortlist(users, table, m, skip=skip_pos)                # no pool: the id is the position
+
+            def stock():
+                vals, idx = [], []
+                for g0 in range(0, G, 1024):
+                    sc = torch.matmul(users[g0:g0 + 1024], table.t())
+                    sc.scatter_(1, skip_pos[g0:g0 + 1024], float("-inf"))
+                    top = torch.topk(sc, m, dim=1)
+                    vals.append(top.values)
+                    idx.append(top.indices)
+                return torch.cat(vals), torch.cat(idx)
+            (got, pa), (want, pb) = peak(ours), peak(stock)
+            same = float((got[1] == want[1]).float().mean())          # the products round differently: near-ties may swap
+            (a, alo, ahi), (b, blo, bhi) = alternate(ours, stock, rounds=rounds, iters=3)
+            product = timeit(lambda: evaluate.dot_scores(users, table), iters=3, warm=1)[0]
+            ws = int(L.digat_dot_shortlist_workspace_bytes(G, P, m, min(G, evaluate.SHORTLIST_SLAB_USERS)))
+            print(f"  G = {G:5d}, m = {m:4d}: dot_shortlist {a:8.3f} ms [{alo:.3f}, {ahi:.3f}] (workspace {ws / 2**20:.1f} MiB, peak {pa / 2**20:.1f} "
+                  f"MiB) | matmul + torch.topk {b:8.3f} ms [{blo:.3f}, {bhi:.3f}] (x{b / a:.2f}, peak {pb / 2**20:.1f} MiB) | score matrix "
+                  f"{4.0 * G * P / 2**20:.1f} MiB | ids equal to torch.topk's: {same:.4f} | dot_scores alone {product:.3f} ms", flush=True)
+            del got, want
+        del users, skip_pos
+        torch.cuda.empty_cache()
+
+
 def matrix_ranks(users, table, pos, skip_pos, product, chunk=1024):
     """The ranks of ``evaluate.dot_rank`` built from what the tree had before it: per chunk of users the [chunk, P] score matrix
     (``product(users, table)``), then torch compares and sums against every target's own score with the skip mask.  ``pos`` [G, t]
@@ -1316,6 +1423,10 @@ if __name__ == "__main__":
         bench_recommend(*nums)
     elif what == "dot-topk":
         bench_dot_topk(*nums)
+    elif what == "shortlist":
+        bench_shortlist(*nums)
+    elif what == "dot-shortlist":
+        bench_dot_shortlist(*nums)
     elif what == "dot-rank":
         bench_dot_rank(*nums)
     elif what == "diversify":
