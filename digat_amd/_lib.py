@@ -128,6 +128,11 @@ _SIGNATURES = {
                                       C.c_size_t, _f]),
     "digat_dot_rank_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
     "digat_dot_rank": (C.c_int, [_f, _f, _f, C.c_int64, C.c_int64, C.c_int64, C.c_int, _f, C.c_int, _f, _f, C.c_int64, _f, _f, _f, C.c_size_t, _f]),
+    "digat_pool_softmax_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int]),
+    "digat_pool_softmax_fwd": (C.c_int, [_f, _f, _f, C.c_int64, C.c_int64, C.c_int64, C.c_int, _f, C.c_int, _f, _f, C.c_int64, C.c_float, _f, _f, _f,
+                                         _f, C.c_size_t, _f]),
+    "digat_pool_softmax_bwd": (C.c_int, [_f, _f, _f, C.c_int64, C.c_int64, C.c_int64, C.c_int, _f, C.c_int, _f, _f, C.c_int64, C.c_float, _f, _f, _f,
+                                         _f, _f, C.c_size_t, _f]),
     "digat_mmr_select_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
     "digat_mmr_select": (C.c_int, [_f, _f, _f, C.c_int64, C.c_int, _f, C.c_int64, C.c_int, _f, C.c_int, C.c_float, C.c_float, C.c_int, _f, _f, _f,
                                    _f, C.c_size_t, _f]),

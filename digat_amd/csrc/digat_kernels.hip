@@ -17,6 +17,7 @@
 //   digat_train_input.inc  the training input: an epoch's negative samples, the index lists of a step
 //   digat_dot_topk.inc  inner-product retrieval: fp32 matrix-core product fused with the top-k selection of digat_topk.inc
 //   digat_dot_rank.inc  retrieval evaluation: the same product fused with the rank of given targets in the whole pool
+//   digat_pool_softmax.inc  retrieval training: the same product fused with the softmax loss over the whole pool and its gradients
 //   digat_mmr.inc  diversified top-k: a short list's Gram in LDS and the greedy maximal-marginal-relevance picks on it
 //   digat_listq.inc  list quality: the same Gram reduced to a list's diversity, with category spread, overlap and exposure
 // This file: shared helpers, the per-kernel profiler, and the C ABI.  The encoder's orchestration is digat_encoder.inc (host
@@ -883,5 +884,6 @@ int digat_row_logits(const float* news_ctx, const float* user_ctx, float* logits
 #include "digat_dot_topk.inc"
 #include "digat_shortlist.inc"
 #include "digat_dot_rank.inc"
+#include "digat_pool_softmax.inc"
 #include "digat_mmr.inc"
 #include "digat_listq.inc"

@@ -547,6 +547,215 @@ def shortlist_for(rank, share: float):
     return 1 if m == 0 else int(got[m - 1]) + 1
 
 
+POOL_SOFTMAX_MAX_D = 512      # csrc/digat_pool_softmax.inc: PSM_MAX_D, the widest vectors digat_pool_softmax_bwd takes
+
+
+def _pool_softmax_host_args(scores, target_pos, target_start, pool, skip, news_num):
+    """The checks of ``dot_rank_host`` and its element rule: ``(S float64 [G,P], pos, start, elements bool [G,P], ranked bool [T],
+    owner [T])``."""
+    S = np.ascontiguousarray(scores, dtype=np.float64)
+    if S.ndim != 2:
+        raise ValueError("scores must be [G, P]")
+    G, P = S.shape
+    pos = np.asarray(target_pos, dtype=np.int64)
+    if pos.ndim != 1:
+        raise ValueError("target_pos must be 1-D")
+    st = _check_target_start(target_start, G, len(pos))
+    ids = np.arange(P, dtype=np.int64) if pool is None else np.asarray(pool, dtype=np.int64)
+    if ids.shape != (P,):
+        raise ValueError(f"pool must have one id per column ({P}), got shape {ids.shape}")
+    skv = None if skip is None else np.asarray(skip, dtype=np.int64).reshape(G, -1)
+    if skv is not None and skv.shape[1] > TOPK_MAX_SKIP:
+        raise ValueError(f"skip must be [users, at most {TOPK_MAX_SKIP}], got shape {skv.shape}")
+    base = ids >= 0
+    if news_num is not None:
+        base &= ids < int(news_num)
+    elem = np.repeat(base[None, :], G, axis=0)
+    if skv is not None and skv.shape[1]:
+        for g in range(G):
+            elem[g] &= ~np.isin(ids, skv[g])
+    owner = np.repeat(np.arange(G), np.diff(st))
+    ranked = (pos >= 0) & (pos < P)
+    ranked[ranked] = elem[owner[ranked], pos[ranked]]
+    return S, pos, st, elem, ranked, owner
+
+
+def pool_softmax_host(scores, target_pos, target_start, pool=None, skip=None, news_num=None, scale=1.0):
+    """The contract of ``digat_pool_softmax_fwd`` on a given score matrix ``scores`` [G, P], in numpy float64 — the yardstick of the
+    kernel.  The elements of user g are ``dot_rank_host``'s.  With ``x = scale * scores``: ``lse`` [G] = log of the sum of ``exp(x)``
+    over the user's elements (-inf without one); ``loss`` [T] = ``lse[user] - x[user, target]`` where the target is an element of its
+    user, 0 elsewhere; ``ranked`` [T] bool says where.  Returns ``(loss, lse, ranked)``."""
+    S, pos, st, elem, ranked, owner = _pool_softmax_host_args(scores, target_pos, target_start, pool, skip, news_num)
+    G = S.shape[0]
+    x = np.where(elem, float(scale) * S, -np.inf)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        m = x.max(axis=1) if x.shape[1] else np.full(G, -np.inf)
+        safe = np.where(np.isfinite(m), m, 0.0)
+        lse = safe + np.log(np.exp(x - safe[:, None]).sum(axis=1))
+    loss = np.zeros(len(pos), dtype=np.float64)
+    loss[ranked] = lse[owner[ranked]] - x[owner[ranked], pos[ranked]]
+    return loss, lse, ranked
+
+
+def pool_softmax_grad_host(users, rows, scores, target_pos, target_start, pool=None, skip=None, news_num=None, scale=1.0, grad_loss=None):
+    """The contract of ``digat_pool_softmax_bwd`` in numpy float64: ``users`` [G, d], ``rows`` [P, d] — the news row of every pool
+    POSITION (zeros where the id is no row) —, ``scores`` [G, P] the matrix the loss was taken on, ``grad_loss`` [T] (None: ones;
+    ignored where the target is not ranked).  Returns ``(d_users [G, d], d_rows [P, d])``, the gradients of ``sum(grad_loss * loss)``
+    with the scores' dependence on ``users`` and ``rows`` being the inner product."""
+    S, pos, st, elem, ranked, owner = _pool_softmax_host_args(scores, target_pos, target_start, pool, skip, news_num)
+    _, lse, _ = pool_softmax_host(scores, target_pos, target_start, pool, skip, news_num, scale)
+    U, R = np.asarray(users, dtype=np.float64), np.asarray(rows, dtype=np.float64)
+    G, P = S.shape
+    if U.ndim != 2 or R.ndim != 2 or U.shape[0] != G or R.shape[0] != P or U.shape[1] != R.shape[1]:
+        raise ValueError(f"users must be [{G}, d] and rows [{P}, d], got {U.shape} and {R.shape}")
+    gl = np.ones(len(pos)) if grad_loss is None else np.asarray(grad_loss, dtype=np.float64)
+    if gl.shape != pos.shape:
+        raise ValueError("grad_loss must have one entry per target")
+    gl = np.where(ranked, gl, 0.0)
+    c = np.bincount(owner, weights=gl, minlength=G) if len(pos) else np.zeros(G)
+    C = np.zeros((G, P), dtype=np.float64)
+    live = c != 0
+    with np.errstate(invalid="ignore", over="ignore"):
+        C[live] = np.where(elem[live], c[live, None] * np.exp(float(scale) * S[live] - lse[live, None]), 0.0)
+    np.subtract.at(C, (owner[ranked], pos[ranked]), gl[ranked])
+    return float(scale) * (C @ R), float(scale) * (C.T @ U)
+
+
+def pool_softmax_bound(P, lse, x_max, x_target=None, loss=None):
+    """The error bound csrc/digat_pool_softmax.inc derives for ``lse`` (and, with ``x_target`` and ``loss``, for ``loss``) against an
+    exact evaluation on the same fp32 scores: ``u (15 + ceil(C / 64) + log n + 4 |lse| + 2 max|x|)`` with u = 2^-24, n <= P elements
+    and C chunks, plus ``u (|x_target| + |loss|)`` for a loss."""
+    u = 2.0 ** -24
+    chunks = -(-int(P) // DOT_TOPK_CHUNK)
+    b = u * (15.0 + -(-chunks // 64) + np.log(max(int(P), 1)) + 4.0 * np.abs(lse) + 2.0 * np.abs(x_max))
+    if x_target is not None:
+        b = b + u * (np.abs(x_target) + np.abs(loss))
+    return b
+
+
+def _pool_softmax_args(users, news, target_pos, target_start, pool, skip):
+    """``dot_rank``'s checks: ``(G, N, P, d, target_pos as a tensor, target_start as a host array)``."""
+    import torch
+    G, N, P, d = _check_dot_args(users, news, pool, skip)
+    tp = torch.as_tensor(np.asarray(target_pos) if not torch.is_tensor(target_pos) else target_pos)
+    if tp.dim() != 1 or tp.dtype in (torch.float16, torch.float32, torch.float64, torch.bool):
+        raise ValueError("target_pos must be a 1-D integer array of pool positions")
+    st = _check_target_start(target_start, G, int(tp.shape[0]))
+    return G, N, P, d, tp, st
+
+
+def _pool_softmax_call(entry, u, v, pl, sk, tp, std, scale, tail):
+    """One of the two entries: the shared head of the argument list, the workspace and the call."""
+    from . import _lib
+    L = _lib.lib()
+    G, d = int(u.shape[0]), int(u.shape[1])
+    N, P, T = int(v.shape[0]), int(v.shape[0] if pl is None else pl.shape[0]), int(tp.shape[0])
+    need = int(L.digat_pool_softmax_workspace_bytes(G, P, T, d))
+    ws = _lib.workspace(need, u.device, "pool_softmax")
+    _lib.check(getattr(L, entry)(u.data_ptr(), v.data_ptr(), _lib.ptr(pl), G, N, P, d, _lib.ptr(sk), 0 if sk is None else int(sk.shape[1]),
+                                 tp.data_ptr() if T else ws.data_ptr(), std.data_ptr(), T, float(scale), *tail, ws.data_ptr(), need,
+                                 _lib.stream_ptr()), entry)
+
+
+def _pool_softmax_function():
+    import torch
+
+    class PoolSoftmax(torch.autograd.Function):
+        """``digat_pool_softmax_fwd`` / ``digat_pool_softmax_bwd``: the gradient of ``news`` [N, d] is the ``index_add_`` of the
+        per-position rows the library writes."""
+
+        @staticmethod
+        def forward(ctx, users, news, pl, sk, tp, std, scale):
+            u, v = users.detach().float().contiguous(), news.detach().float().contiguous()
+            G, T = int(u.shape[0]), int(tp.shape[0])
+            f = dict(dtype=torch.float32, device=u.device)
+            per_target, lse = torch.empty((2, max(T, 1)), **f), torch.empty(G, **f)          # no target: still two pointers to hand over
+            loss, score = per_target[0, :T], per_target[1, :T]
+            _pool_softmax_call("digat_pool_softmax_fwd", u, v, pl, sk, tp, std, scale,
+                               (per_target[0].data_ptr(), lse.data_ptr(), per_target[1].data_ptr()))
+            ctx.save_for_backward(u, v, lse, tp, std)
+            ctx.pl, ctx.sk, ctx.scale, ctx.dtypes = pl, sk, scale, (users.dtype, news.dtype)
+            ctx.mark_non_differentiable(lse, score)
+            return loss, lse, score
+
+        @staticmethod
+        def backward(ctx, grad_loss, _lse, _score):
+            u, v, lse, tp, std = ctx.saved_tensors
+            pl, sk = ctx.pl, ctx.sk
+            G, d, N = int(u.shape[0]), int(u.shape[1]), int(v.shape[0])
+            P = N if pl is None else int(pl.shape[0])
+            if d > POOL_SOFTMAX_MAX_D:
+                raise ValueError(f"the backward of pool_softmax takes vectors of at most {POOL_SOFTMAX_MAX_D} channels, got {d}")
+            f = dict(dtype=torch.float32, device=u.device)
+            d_users, d_rows = torch.empty((G, d), **f), torch.empty((P, d), **f)
+            gl = grad_loss.float().contiguous()
+            _pool_softmax_call("digat_pool_softmax_bwd", u, v, pl, sk, tp, std, ctx.scale,
+                               (lse.data_ptr(), gl.data_ptr() if gl.numel() else lse.data_ptr(), d_users.data_ptr(), d_rows.data_ptr()))
+            d_news = None
+            if ctx.needs_input_grad[1]:
+                d_news = d_rows if pl is None else torch.zeros((N, d), **f).index_add_(0, pl, d_rows)
+            return (d_users.to(ctx.dtypes[0]) if ctx.needs_input_grad[0] else None), (None if d_news is None else d_news.to(ctx.dtypes[1])), \
+                None, None, None, None, None
+
+    return PoolSoftmax
+
+
+_PoolSoftmax = None
+
+
+def pool_softmax(users, news, target_pos, target_start, pool=None, skip=None, scale=1.0):
+    """The softmax loss of every target — a pool position of one user — over that user's WHOLE pool: ``(loss [T], lse [G],
+    target_score [T])`` float32.  ``users`` [G, d], ``news`` [N, d], ``pool`` [P], ``skip`` [G, L <= 256], ``target_pos`` [T] and the
+    HOST array ``target_start`` [G + 1] are ``dot_rank``'s, and so are a user's elements.  With ``x = scale * <user, news>``:
+    ``lse`` = log-sum-exp of x over the user's elements (-inf without one), ``loss = lse - x[target]``; a target that is no element of
+    its user (``dot_rank``'s -1) has loss 0 and a NaN ``target_score``.  ``loss`` is differentiable in ``users`` and ``news``; ``lse``
+    and ``target_score`` are not.
+
+    On CUDA tensors: ``digat_pool_softmax_fwd`` / ``_bwd`` under autograd — no [G, P] scores, softmax or score gradient in memory;
+    the backward takes ``d <= POOL_SOFTMAX_MAX_D`` = 512 and raises ``ValueError`` beyond.  Two calls give the same bits, the gradient of
+    ``news`` included as long as ``pool`` repeats no id (repeated ids are summed by ``index_add_``, whose order torch does not fix).
+    On CPU tensors: the stock composition —
+    product, masked ``logsumexp``, gather — differentiable by autograd."""
+    import torch
+    global _PoolSoftmax
+    G, N, P, d, tp, st = _pool_softmax_args(users, news, target_pos, target_start, pool, skip)
+    dev = users.device
+    given = [t for t in (news, pool, skip) if t is not None]
+    if any(t.device != dev for t in given):
+        raise ValueError("users, news, pool and skip must live on one device")
+    pl = None if pool is None else pool.to(torch.int64).contiguous()
+    sk = None if skip is None or skip.shape[1] == 0 else skip.to(torch.int64).contiguous()
+    tp = tp.to(dev, torch.int64).contiguous()
+    T = int(tp.shape[0])
+    if dev.type == "cuda":
+        if _PoolSoftmax is None:
+            _PoolSoftmax = _pool_softmax_function()
+        if G == 0 or P == 0:                                          # nothing is an element: no launch, a zero gradient
+            z = users.new_zeros(T, dtype=torch.float32) + 0.0 * (users.float().sum() + news.float().sum())
+            return z, users.new_full((G,), float("-inf"), dtype=torch.float32), users.new_full((T,), float("nan"), dtype=torch.float32)
+        return _PoolSoftmax.apply(users, news, pl, sk, tp, torch.from_numpy(st).to(dev), float(scale))
+    ids = torch.arange(P) if pl is None else pl
+    S = users @ news.index_select(0, ids).t()                                        # [G, P]
+    x = float(scale) * S
+    elem = torch.ones((G, P), dtype=torch.bool)
+    if sk is not None:
+        elem &= ~(ids[None, :, None] == sk[:, None, :]).any(dim=2)
+    has = elem.any(dim=1)                                                            # a row without an element never meets logsumexp
+    masked = torch.where(has[:, None], x.masked_fill(~elem, float("-inf")), torch.zeros_like(x))
+    lse = torch.where(has, torch.logsumexp(masked, dim=1), x.new_full((G,), float("-inf"))) if P else x.new_full((G,), float("-inf"))
+    owner = torch.from_numpy(np.repeat(np.arange(G), np.diff(st)))
+    inside = (tp >= 0) & (tp < P)
+    at = torch.where(inside, tp, torch.zeros_like(tp))
+    if P and T:
+        ranked = inside & elem[owner, at]
+        loss = torch.where(ranked, torch.where(ranked, lse[owner], torch.zeros_like(lse[owner])) - x[owner, at], x.new_zeros(T))
+        score = torch.where(ranked, S.detach()[owner, at], S.new_full((T,), float("nan")))
+    else:
+        loss = x.new_zeros(T) + 0.0 * x.sum()
+        score = S.new_full((T,), float("nan"))
+    return loss, lse.detach(), score
+
+
 MMR_MAX_LIST = TOPK_MAX_K      # include/digat_hip.h: digat_mmr_select takes lists of at most this many entries
 
 

@@ -698,6 +698,153 @@ def retrieval_metrics(model, dev, users=None, targets=None, candidates=None, ks=
     return out
 
 
+def _first_positions(pool, N):
+    """[N] int64: the first position of every news id in ``pool``, -1 for an id that is not in it."""
+    where = np.full(N, -1, dtype=np.int64)
+    where[pool[::-1]] = np.arange(len(pool) - 1, -1, -1, dtype=np.int64)
+    return where
+
+
+def retrieval_loss(model, dev, users=None, targets=None, candidates=None, exclude_history=True, batch_size=1024, scale=1.0):
+    """The quantity ``fit_retriever`` minimises, measured as ``retrieval_metrics`` measures ranks: for every target its full-pool
+    softmax loss ``logsumexp(scale * <user, news>) - scale * <user, target>`` over the user's elements, in eval mode under
+    ``no_grad``.  ``dev``, ``users``, ``targets``, ``candidates`` (None or ONE shared 1-D pool), ``exclude_history`` and
+    ``batch_size`` are ``retrieval_metrics``'; a target that has no rank there has no loss here.  Returns ``{"nll": the mean loss
+    over the ranked targets (NaN without one), "not_ranked", "targets", "users": those with a target, "loss" [T], "lse" [G]}`` —
+    numpy float64 arrays, ``loss`` 0 where the target is not ranked.
+
+    On CUDA tensors ``evaluate.pool_softmax`` (``digat_pool_softmax_fwd``: no [users, news] score matrix); on CPU tensors the stock
+    product per batch of users and ``evaluate.pool_softmax_host``."""
+    from . import evaluate, util
+    N = int(dev.title_text.shape[0])
+    if targets is None:
+        users, target_ids, target_start = _clicked_targets(dev, users)
+    else:
+        if users is None:
+            raise ValueError("explicit targets need users: the impressions (or histories) target_start refers to")
+        if not (isinstance(targets, (tuple, list)) and len(targets) == 2):
+            raise ValueError("targets must be None or a pair (target_ids [T], target_start [G+1])")
+        target_ids = np.asarray(targets[0].cpu() if torch.is_tensor(targets[0]) else targets[0])
+        if target_ids.ndim != 1 or (target_ids.size and target_ids.dtype.kind not in "iu"):
+            raise ValueError("target_ids must be a 1-D integer array of news ids")
+        target_ids, target_start = target_ids.astype(np.int64), targets[1]
+    hist, mask = _histories(dev, users)
+    G = int(hist.shape[0])
+    target_start = evaluate._check_target_start(target_start, G, len(target_ids))
+    if target_ids.size and (int(target_ids.min()) < 0 or int(target_ids.max()) >= N):
+        raise ValueError(f"target ids must lie in [0, {N})")
+    util.recommend_limits(1, int(hist.shape[1]) if exclude_history else 0)
+    ids, start = util.recommend_candidates(np.arange(1, N, dtype=np.int64) if candidates is None else candidates, G, N)
+    if start is not None:
+        raise ValueError("retrieval_loss takes the softmax over one pool shared by all users, not over per-user candidate lists")
+    pool = ids.cpu().numpy()
+    target_pos = _first_positions(pool, N)[target_ids]
+    model.eval()
+    plain, aug = news_caches(model, dev.title_text, dev.title_mask, dev.augmented_title_text, dev.augmented_title_mask, 4 * batch_size)
+    ids = ids.to(plain.device)
+    user = _encode_users(model, plain, hist, mask, batch_size)
+    skip = torch.where(mask != 0, hist, torch.zeros_like(hist)) if exclude_history else None
+    if plain.device.type == "cuda":
+        with torch.no_grad():
+            loss, lse, score = evaluate.pool_softmax(user, aug, target_pos, target_start, pool=ids, skip=skip, scale=scale)
+        loss, lse, ranked = loss.double().cpu().numpy(), lse.double().cpu().numpy(), ~torch.isnan(score).cpu().numpy()
+    else:
+        loss, lse, ranked = np.zeros(len(target_ids)), np.zeros(G), np.zeros(len(target_ids), dtype=bool)
+        rows = aug.index_select(0, ids)
+        P = int(ids.shape[0])
+        step = max(1, int(batch_size))
+        for g0 in range(0, G, step):
+            g1 = min(G, g0 + step)
+            t0, t1 = int(target_start[g0]), int(target_start[g1])
+            S = (rows.repeat(g1 - g0, 1) * user[g0:g1].repeat_interleave(P, dim=0)).sum(dim=1).view(g1 - g0, P)
+            loss[t0:t1], lse[g0:g1], ranked[t0:t1] = evaluate.pool_softmax_host(
+                S.numpy(), target_pos[t0:t1], target_start[g0:g1 + 1] - t0, pool=pool, skip=None if skip is None else skip[g0:g1].numpy(),
+                news_num=N, scale=scale)
+    return {"nll": float(loss[ranked].mean()) if ranked.any() else float("nan"), "not_ranked": int((~ranked).sum()),
+            "targets": len(target_ids), "users": int((np.diff(target_start) > 0).sum()), "loss": loss, "lse": lse}
+
+
+def retrieval_step(model, train, users, pool=None, exclude_history=True, scale=1.0):
+    """One training step's loss for the first stage, with its graph: the full-pool softmax loss of the clicked candidates of
+    ``users`` (impression indices of ``train``; ``_clicked_targets``), summed over the ranked targets and divided by their number
+    (by 1 when there is none).  ``pool``: a 1-D array of news ids (None: every news but row 0).  The pool's titles go through
+    ``model.news_encoder`` WITH gradients — the augmented titles too for NRMS-SA, as in ``Model.forward`` — into a compact [P, d]
+    table, the users' histories through ``model.user_encoder`` on their title texts; history ids and targets are mapped to pool
+    POSITIONS (-1: not in the pool), so the skip rows and the targets speak in positions and no [N, d] table is built.  A target
+    outside the pool or — under ``exclude_history`` — inside its user's history is not ranked and carries no loss.  The model's
+    mode (dropout) is the caller's.  On CUDA tensors the loss is ``evaluate.pool_softmax`` on the HIP encoders; on CPU tensors
+    ``forward_stock`` and the stock composition."""
+    from . import evaluate
+    N, H = int(train.title_text.shape[0]), int(train.history_ids.shape[1])
+    device = train.title_text.device
+    idx, target_ids, target_start = _clicked_targets(train, users)
+    pl = np.arange(1, N, dtype=np.int64) if pool is None else np.asarray(pool.cpu() if torch.is_tensor(pool) else pool)
+    if pl.ndim != 1 or (pl.size and pl.dtype.kind not in "iu"):
+        raise ValueError("pool must be a 1-D integer array of news ids")
+    pl = pl.astype(np.int64)
+    if pl.size and (int(pl.min()) < 0 or int(pl.max()) >= N):
+        raise ValueError(f"pool ids must lie in [0, {N})")
+    if exclude_history and H > evaluate.TOPK_MAX_SKIP:
+        raise ValueError(f"exclude_history takes histories of at most {evaluate.TOPK_MAX_SKIP} news, got {H}")
+    where = _first_positions(pl, N)
+    ids = torch.from_numpy(pl).to(device)
+    enc, ue = model.news_encoder, model.user_encoder
+    cuda = device.type == "cuda"
+    sa = isinstance(enc, SA_NRMS_NewsEncoder)
+    table = (enc if cuda else enc.forward_stock)(
+        train.title_text.index_select(0, ids)[None], train.title_mask.index_select(0, ids)[None],
+        train.augmented_title_text.index_select(0, ids)[None] if sa else None,
+        train.augmented_title_mask.index_select(0, ids)[None] if sa else None)[0]                       # [P, d]
+    at = torch.from_numpy(idx).to(device)
+    hist, mask = train.history_ids.index_select(0, at).to(torch.int64), train.history_mask.index_select(0, at)
+    user = (ue if cuda else ue.forward_stock)(train.title_text[hist], train.title_mask[hist], mask)    # [G, d]
+    skip = None
+    if exclude_history:
+        skip = torch.where(mask != 0, torch.from_numpy(where).to(device)[hist], torch.full_like(hist, -1))
+    loss, _, score = evaluate.pool_softmax(user, table, where[target_ids], target_start, skip=skip, scale=scale)
+    return loss.sum() / (~torch.isnan(score)).sum().clamp(min=1)
+
+
+def fit_retriever(model, train, steps, batch_users=64, pool_size=None, lr=1e-4, seed=0, exclude_history=True, scale=1.0, optimizer=None):
+    """Train ``model`` for retrieval: ``steps`` times one ``retrieval_step`` on a seeded draw of ``batch_users`` impressions of
+    ``train`` that have a click (without replacement inside a step; all of them when there are fewer), one backward and one
+    optimizer step, in train mode.  The pool is every news but row 0 (``pool_size`` None), or the sorted union of the batch's targets
+    and ``pool_size`` uniformly drawn ids — never row 0.  ``optimizer``: None = the one ``Trainer`` builds — Adam(``lr``) over
+    ``trainer.parameter_groups``, ``optim.ClipAdam`` on the GPU — and its state lives for this call only.  Returns the per-step
+    losses as Python floats.  The draws depend on ``seed`` and the corpus alone, so CPU tensors see the same steps — through
+    ``forward_stock`` and the stock composition."""
+    from .trainer import parameter_groups
+    N = int(train.title_text.shape[0])
+    clicked, _, _ = _clicked_targets(train, None)
+    if len(clicked) == 0:
+        raise ValueError("no impression of this corpus has a clicked row: nothing to train on")
+    if N < 2:
+        raise ValueError("the corpus holds no news but row 0")
+    if optimizer is None:
+        groups = parameter_groups(model, 0.0)
+        if all(p.is_cuda and p.dtype == torch.float32 for g in groups for p in g["params"]):
+            from .optim import ClipAdam
+            optimizer = ClipAdam(groups, lr=lr)
+        else:
+            optimizer = torch.optim.Adam(groups, lr=lr)
+    rng = np.random.default_rng(seed)
+    model.train()
+    losses = []
+    for _ in range(int(steps)):
+        batch = np.sort(rng.choice(clicked, size=min(int(batch_users), len(clicked)), replace=False))
+        pool = None
+        if pool_size is not None:
+            _, target_ids, _ = _clicked_targets(train, batch)
+            drawn = rng.integers(1, N, size=int(pool_size), dtype=np.int64)
+            pool = np.union1d(target_ids[target_ids > 0], drawn)
+        optimizer.zero_grad()
+        loss = retrieval_step(model, train, batch, pool=pool, exclude_history=exclude_history, scale=scale)
+        loss.backward()
+        optimizer.step()
+        losses.append(float(loss.detach()))
+    return losses
+
+
 def candidates_csr(news_ids, count):
     """The valid slots of a ``[G,k]`` result (``recommend``'s ``news_ids`` and ``count``) as the per-user lists
     ``util.recommend(candidates=...)`` takes: ``(ids [R] int64 tensor, start [G+1] int64 numpy)`` — NRMS retrieves, DIGAT re-ranks."""

@@ -680,6 +680,37 @@ int digat_dot_rank(const float* users, const float* news, const int64_t* pool, i
                    int skip_len, const int64_t* target_pos, const int64_t* target_start, int64_t T, int32_t* out_rank, float* out_scores,
                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- retrieval training: softmax loss of given targets over a user's whole pool, and its gradients (digat_amd.nrms.retrieval_step) ---
+ * users, news, pool, G, N, P, d, skip, skip_len, target_pos, target_start, T: digat_dot_rank's, and so are the elements of user g, their
+ * scores (the bits digat_dot_scores stores), the clamping of target_start and the meaning of "ranked": the target is an element of its
+ * user.  x(g, p) = scale * score(g, p).
+ * Forward: out_lse [G] = log of the sum of exp(x(g, p)) over g's elements (-inf when g has none; the maximum is always subtracted);
+ * out_loss [T] = lse[g(t)] - x(g(t), pos[t]) for a ranked target, 0 otherwise; out_target_score [T] = digat_dot_rank's out_scores (score
+ * bits, a NaN where not ranked).  Every output byte is written whatever target_start holds (G == 0: out_loss and out_target_score).
+ * Backward, given lse [G] (the forward's) and grad_loss [T] (ignored where the target is not ranked): with c[g] = the sum of grad_loss
+ * over g's ranked targets in ascending t and C(g, p) = c[g] exp(x(g, p) - lse[g]) - (the grad_loss of g's ranked targets at p, subtracted
+ * in ascending t) on elements, 0 elsewhere,
+ *   d_users [G, d] = scale * sum_p C(g, p) news[id(p), :]          d_rows [P, d] = scale * sum_g C(g, p) users[g, :]
+ * — d_rows has one row per POOL POSITION: scattering it over repeated ids is the caller's.  A user with c[g] == 0 never meets its lse
+ * (no NaN from lse = -inf).  Every byte of d_users and d_rows is written.  No floating-point atomics: every sum's order is fixed by the
+ * shapes and the targets, two calls give the same bits.
+ * DIGAT_ERR_ARG, DIGAT_ERR_SHAPE and DIGAT_ERR_WORKSPACE as digat_dot_rank, before any launch; the backward takes d <= 512
+ * (DIGAT_ERR_SHAPE beyond: its 64 x d block of accumulators lives in registers), the forward any d.
+ * Workspace (one query for both; it may hold anything on entry), every region rounded up to 256 bytes:
+ *   20 T  +  8 G ceil(P / DIGAT_DOT_TOPK_CHUNK)  +  4 G  +  4 tiles  +  256 d min(tiles ceil(P / DIGAT_DOT_TOPK_CHUNK), 256 + tiles),
+ * tiles = ceil(G / DIGAT_DOT_TOPK_USERS): nothing the size of the [G, P] matrix — of it there is one (reference, sum) pair per user and
+ * chunk —; 0 for a negative argument or d <= 0.
+ * Stream-ordered: four launches forward, six backward, sized by G, P, T and d alone; no allocation, no host synchronisation, no read of
+ * device memory on the host. */
+size_t digat_pool_softmax_workspace_bytes(int64_t users, int64_t pool, int64_t targets, int d);
+int digat_pool_softmax_fwd(const float* users, const float* news, const int64_t* pool, int64_t G, int64_t N, int64_t P, int d,
+                           const int64_t* skip, int skip_len, const int64_t* target_pos, const int64_t* target_start, int64_t T, float scale,
+                           float* out_loss, float* out_lse, float* out_target_score, void* workspace, size_t workspace_bytes, void* stream);
+int digat_pool_softmax_bwd(const float* users, const float* news, const int64_t* pool, int64_t G, int64_t N, int64_t P, int d,
+                           const int64_t* skip, int skip_len, const int64_t* target_pos, const int64_t* target_start, int64_t T, float scale,
+                           const float* lse, const float* grad_loss, float* d_users, float* d_rows, void* workspace, size_t workspace_bytes,
+                           void* stream);
+
 /* ---- diversified top-k: greedy maximal-marginal-relevance selection over a short list (digat_amd.evaluate.mmr_select) ---------
  * Per user g a list: ids [G, M] int64, scores [G, M] f32, count [G] int32 (the entries in use, held inside [0, M]; NULL: M) — the
  * triple digat_topk_segments and digat_dot_topk write.  vectors [N, d] f32, rows taken as they are (callers pass unit rows).

@@ -42,6 +42,12 @@
                                              users x 65 237 news, d = 400, one and five targets per user, the legs in turn, median
                                              [min, max] of five rounds, time and peak device bytes; then nrms.retrieval_metrics for
                                              4 096 users end to end
+  python tools/kbench.py pool-softmax [news_num d]   retrieval training: evaluate.pool_softmax (fused full-pool softmax loss, no score
+                                             matrix) against the stock composition — torch.matmul per 1 024 users, masked logsumexp,
+                                             gather, autograd backward —, G = 64 and 4 096 users x 65 237 news, d = 400, 50-entry skip
+                                             rows, one and five targets per user, forward and forward + backward, the legs in turn,
+                                             median [min, max] of five rounds, time and peak device bytes; then nrms.fit_retriever on
+                                             the planted-signal corpus: nrms.retrieval_metrics before and after
   python tools/kbench.py diversify [news_num d]   diversified top-k: evaluate.mmr_select (one launch, the Gram in LDS) against gather +
                                              torch.bmm + k rounds of torch element-wise ops and arg-max, G = 64 and 4 096 lists of
                                              M = 128, d = 400, k = 10 and 100, with and without a cap of 2 per category, the legs in
@@ -1222,6 +1228,112 @@ def bench_dot_rank(news_num=65238, d=400, rounds=5):
           f"median rank {res['median_rank']:.0f}, not ranked {res['not_ranked']}", flush=True)
 
 
+def stock_pool_softmax(users, table, pos, skip_pos, scale=1.0, chunk=1024):
+    """The loss of ``evaluate.pool_softmax`` from stock PyTorch: per chunk of users the [chunk, P] scores (``torch.matmul``), the
+    skip positions masked out, ``logsumexp``, the targets gathered.  ``pos`` [G, t] target positions, ``skip_pos`` [G, L].  A target
+    inside its user's skip row is not treated (there is none in the benchmark's data).  Returns the summed loss."""
+    total = users.new_zeros(())
+    for g0 in range(0, users.shape[0], chunk):
+        x = scale * torch.matmul(users[g0:g0 + chunk], table.t())
+        masked = x.scatter(1, skip_pos[g0:g0 + chunk], float("-inf"))
+        total = total + (torch.logsumexp(masked, dim=1, keepdim=True) - x.gather(1, pos[g0:g0 + chunk])).sum()
+    return total
+
+
+def bench_pool_softmax(news_num=65238, d=400, rounds=5):
+    """``evaluate.pool_softmax`` (the fused full-pool softmax loss and its gradients: no score matrix) against ``stock_pool_softmax``
+    under autograd, in one process, the legs taken in turn, median [min, max] of ``rounds`` rounds of three calls, and each leg's
+    peak of device bytes beyond its inputs; forward alone (``no_grad``) and forward + backward.  Then ``nrms.fit_retriever`` on the
+    planted-signal corpus (``synthetic.PLANTED_SPEC`` with random titles): ``nrms.retrieval_metrics`` of the held-out impressions
+    before and after."""
+    import time
+    import types
+    from digat_amd import evaluate, nrms, synthetic
+    dev = torch.device("cuda:0")
+    L = _lib.lib()
+    g = torch.Generator(device="cpu").manual_seed(0)
+    P = news_num - 1
+    table = (torch.randn(P, d, generator=g) / d ** 0.5).to(dev)
+    stat = lambda v: (sorted(v)[len(v) // 2], min(v), max(v))
+
+    def peak(fn):
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        out = fn()
+        torch.cuda.synchronize()
+        out = float(out)
+        return out, torch.cuda.max_memory_allocated() - base
+    print(f"pool-softmax: P = {P} news, d = {d}, 50-entry skip rows; ms per call, median [min, max] of {rounds} rounds", flush=True)
+    for G in (64, 4096):
+        users = (3.0 * torch.randn(G, d, generator=g)).to(dev)
+        skip_pos = torch.randint(1, P, (G, 50), generator=g).to(dev)
+        for per in (1, 5):
+            pos = torch.randint(0, P, (G, per), generator=g).to(dev)
+            pos = torch.where((pos[:, :, None] == skip_pos[:, None, :]).any(dim=2), torch.zeros_like(pos), pos)   # position 0 is never skipped
+            start = np.arange(G + 1, dtype=np.int64) * per
+            flat = pos.reshape(-1).contiguous()
+
+            def fused_fwd():
+                with torch.no_grad():
+                    return evaluate.pool_softmax(users, table, flat, start, skip=skip_pos)[0].sum()
+
+            def stock_fwd():
+                with torch.no_grad():
+                    return stock_pool_softmax(users, table, pos, skip_pos)
+
+            def both(fn):
+                def run():
+                    u, t = users.detach().requires_grad_(True), table.detach().requires_grad_(True)
+                    loss = fn(u, t)
+                    loss.backward()
+                    return loss.detach() + 0.0 * (u.grad[0, 0] + t.grad[0, 0])
+                return run
+            fused_both = both(lambda u, t: evaluate.pool_softmax(u, t, flat, start, skip=skip_pos)[0].sum())
+            stock_both = both(lambda u, t: stock_pool_softmax(u, t, pos, skip_pos))
+            legs = (fused_fwd, stock_fwd, fused_both, stock_both)
+            peaks = [peak(fn) for fn in legs]
+            times = [[] for _ in legs]
+            for _ in range(rounds):
+                for leg, fn in zip(times, legs):
+                    leg.append(timeit(fn, iters=3, warm=1)[0])
+            (a, alo, ahi), (b, blo, bhi), (c, clo, chi), (e, elo, ehi) = (stat(t) for t in times)
+            ws = int(L.digat_pool_softmax_workspace_bytes(G, P, G * per, d))
+            print(f"  G = {G:5d}, {per} target(s) per user: forward: pool_softmax {a:8.3f} ms [{alo:.3f}, {ahi:.3f}] (peak {peaks[0][1] / 2**20:.2f} "
+                  f"MiB) | stock {b:8.3f} ms [{blo:.3f}, {bhi:.3f}] (x{b / a:.2f}, peak {peaks[1][1] / 2**20:.1f} MiB) || forward + backward: "
+                  f"pool_softmax {c:8.3f} ms [{clo:.3f}, {chi:.3f}] ({6.0 * G * P * d / c / 1e9:5.1f} TFLOP/s, workspace {ws / 2**20:.1f} MiB, peak "
+                  f"{peaks[2][1] / 2**20:.1f} MiB) | stock {e:8.3f} ms [{elo:.3f}, {ehi:.3f}] (x{e / c:.2f}, peak {peaks[3][1] / 2**20:.1f} MiB) | "
+                  f"summed loss {peaks[0][0]:.3f} vs stock {peaks[1][0]:.3f}", flush=True)
+        del users, skip_pos
+        torch.cuda.empty_cache()
+    # the first stage trained for retrieval on the planted-signal corpus
+    corpus = synthetic.make_corpus(synthetic.SynthSpec(**synthetic.PLANTED_SPEC))
+    N, H, Lw, V = corpus.spec.news_num, corpus.spec.max_history_num, 16, 4000
+    text, mask = synthetic.make_titles(N, Lw, V, seed=2)
+
+    def part(lo, hi):
+        c = synthetic.slice_impressions(corpus, lo, hi)
+        hist = torch.from_numpy(c.history.astype(np.int64)).to(dev)
+        return types.SimpleNamespace(title_text=torch.from_numpy(text).to(dev), title_mask=torch.from_numpy(mask).to(dev),
+                                     augmented_title_text=None, augmented_title_mask=None, history_ids=hist, history_mask=hist != 0,
+                                     row_candidate=c.row_candidate.astype(np.int64), row_impression=c.row_impression, row_label=c.row_label)
+    held, train = part(0, synthetic.PLANTED_DEV_IMPRESSIONS), part(synthetic.PLANTED_DEV_IMPRESSIONS, corpus.spec.impressions)
+    m = _nrms_model("NRMS", V=V, dm=64, h=8, dk=8, att=32, Lw=Lw, H=H, dropout=0.2)
+    report = lambda r, l: (f"recall@10 {r['recall@10']:.4f}, recall@100 {r['recall@100']:.4f}, median rank {r['median_rank']:.0f}, "
+                           f"targets {r['targets']}, not ranked {r['not_ranked']}, retrieval loss {l['nll']:.4f}")
+    print(f"  planted-signal corpus, {N - 1} news, held-out impressions [0, {synthetic.PLANTED_DEV_IMPRESSIONS}): before: "
+          + report(nrms.retrieval_metrics(m, held), nrms.retrieval_loss(m, held)), flush=True)
+    steps = 400
+    t0 = time.perf_counter()
+    losses = nrms.fit_retriever(m, train, steps, batch_users=256, lr=1e-3, seed=0)
+    torch.cuda.synchronize()
+    secs = time.perf_counter() - t0
+    print(f"  nrms.fit_retriever: {steps} steps of 256 users against the full pool, lr 1e-3: {secs:.1f} s ({1e3 * secs / steps:.1f} ms per step), "
+          f"loss {np.mean(losses[:10]):.4f} (first ten steps) -> {np.mean(losses[-10:]):.4f} (last ten); after: "
+          + report(nrms.retrieval_metrics(m, held), nrms.retrieval_loss(m, held)), flush=True)
+
+
 def torch_mmr(ids, scores, count, vectors, k, lam, category=None, q=0):
     """Greedy maximal-marginal relevance built only from stock PyTorch: gather, ``torch.bmm``, then k rounds of element-wise ops and
     arg-max over all lists at once.  Every id is taken to lie in the table; NaN scores and the order among tied values are not the
@@ -1429,6 +1541,8 @@ if __name__ == "__main__":
         bench_dot_shortlist(*nums)
     elif what == "dot-rank":
         bench_dot_rank(*nums)
+    elif what == "pool-softmax":
+        bench_pool_softmax(*nums)
     elif what == "diversify":
         bench_diversify(*nums)
     elif what == "list-quality":
