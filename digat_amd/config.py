@@ -8,6 +8,7 @@ real MIND cannot be downloaded, so the default corpus is synthetic (``--syntheti
 (``--model_dir`` also when it is given: the Trainer saves there on either corpus);
 ``--recommend_diversity`` (with ``--recommend_shortlist``, ``--recommend_max_per_category``) likewise: attributes only when it is given;
 ``--recommend_report`` (a tuple of diversities; it brings the other two with it as well) likewise;
+``--bootstrap`` (with ``--bootstrap_level``, ``--compare_model_path``) likewise;
 ``--local_rank`` also accepts torch >= 2.0's ``--local-rank`` spelling and the ``LOCAL_RANK`` variable.
 """
 from __future__ import annotations
@@ -43,6 +44,12 @@ class Config:
         p.add_argument('--recommend_report', type=str, default=None,
                        help='--mode recommend: diversities "0,0.1,0.3" to report list quality for (one scoring pass; honours --recommend_k, '
                             '--recommend_shortlist, --recommend_max_per_category)')
+        p.add_argument('--bootstrap', type=int, default=0,
+                       help='--mode dev|test on a labelled split: percentile intervals of the four metrics from this many bootstrap replicates '
+                            'over impressions (0: none)')
+        p.add_argument('--bootstrap_level', type=float, default=0.95, help='the level of the --bootstrap intervals')
+        p.add_argument('--compare_model_path', type=str, default='',
+                       help='with --bootstrap: a second checkpoint of the same architecture, compared with the first by a paired bootstrap')
         p.add_argument('--seed', type=int, default=0)
         p.add_argument('--local_rank', '--local-rank', type=int, default=int(os.environ.get('LOCAL_RANK', -1)))
         p.add_argument('--dataset', default='MIND-small', choices=['MIND-small', 'MIND-large'])
@@ -106,12 +113,17 @@ class Config:
             p.error('--recommend_diversity must lie in [0, 1]')
         if a.recommend_shortlist < 0 or a.recommend_max_per_category < 0:
             p.error('--recommend_shortlist and --recommend_max_per_category must not be negative')
+        if a.bootstrap < 0 or not 0.0 < a.bootstrap_level < 1.0:
+            p.error('--bootstrap must not be negative and --bootstrap_level must lie inside (0, 1)')
+        if a.compare_model_path and not a.bootstrap:
+            p.error('--compare_model_path needs --bootstrap B: the replicates of the paired bootstrap')
         mind_flags = ('data_root', 'artefact_root', 'similarity_file', 'semantic_embedding_root', 'word_embedding_file', 'data_cache', 'word_threshold',
                       'max_title_length', 'model_dir')
         diversity_flags = ('recommend_diversity', 'recommend_shortlist', 'recommend_max_per_category')    # attributes only when asked for
         report_flags = ('recommend_report', 'recommend_shortlist', 'recommend_max_per_category')
+        bootstrap_flags = ('bootstrap', 'bootstrap_level', 'compare_model_path')
         asked = lambda k: ((a.recommend_diversity is not None and k in diversity_flags) or (a.recommend_report is not None and k in report_flags)
-                           or k not in diversity_flags + report_flags)
+                           or (a.bootstrap and k in bootstrap_flags) or k not in diversity_flags + report_flags + bootstrap_flags)
         self.attribute_dict = {k: v for k, v in vars(a).items()
                                if (a.data_root or k not in mind_flags or (k == 'model_dir' and a.model_dir)) and asked(k)}
         for k, v in self.attribute_dict.items():

@@ -887,3 +887,4 @@ int digat_row_logits(const float* news_ctx, const float* user_ctx, float* logits
 #include "digat_pool_softmax.inc"
 #include "digat_mmr.inc"
 #include "digat_listq.inc"
+#include "digat_bootstrap.inc"

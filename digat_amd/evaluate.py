@@ -45,25 +45,33 @@ def _dcg(labels_sorted: np.ndarray, k: int) -> float:
     return float(np.sum((2.0 ** g - 1.0) / np.log2(np.arange(len(g)) + 2.0)))
 
 
-def scoring(labels: np.ndarray, ranks: np.ndarray, row_impression: np.ndarray) -> Tuple[float, float, float, float]:
-    """(AUC, MRR, nDCG@5, nDCG@10), mean over impressions that have at least one row."""
+def impression_metric_rows(labels: np.ndarray, ranks: np.ndarray, row_impression: np.ndarray) -> np.ndarray:
+    """[I, 4] float64: (AUC, MRR, nDCG@5, nDCG@10) of every impression that has at least one row — the values ``scoring`` averages.
+    An impression without a positive or without a negative divides by zero: its row is not finite."""
     labels = np.asarray(labels, dtype=np.float64)
     imp = np.asarray(row_impression, dtype=np.int64)
-    bounds = np.r_[0, np.flatnonzero(np.diff(imp)) + 1, len(imp)]
-    aucs, mrrs, n5, n10 = [], [], [], []
-    for s, e in zip(bounds[:-1], bounds[1:]):
-        y, r = labels[s:e], ranks[s:e].astype(np.float64)
-        n_pos = float(y.sum())
-        n_neg = float(len(y) - n_pos)
-        # score = 1/rank is strictly decreasing in rank, so ascending-score rank = len - rank + 1
-        asc = len(y) - r + 1.0
-        aucs.append((asc[y > 0].sum() - n_pos * (n_pos + 1) / 2.0) / (n_pos * n_neg))
-        by_rank = y[np.argsort(r, kind="stable")]
-        mrrs.append(float(np.sum(by_rank / (np.arange(len(y)) + 1.0)) / n_pos))
-        ideal = np.sort(y)[::-1]
-        n5.append(_dcg(by_rank, 5) / _dcg(ideal, 5))
-        n10.append(_dcg(by_rank, 10) / _dcg(ideal, 10))
-    return float(np.mean(aucs)), float(np.mean(mrrs)), float(np.mean(n5)), float(np.mean(n10))
+    bounds = np.r_[0, np.flatnonzero(np.diff(imp)) + 1, len(imp)] if len(imp) else np.zeros(1, dtype=np.int64)
+    out = np.empty((len(bounds) - 1, 4), dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for i, (s, e) in enumerate(zip(bounds[:-1], bounds[1:])):
+            y, r = labels[s:e], ranks[s:e].astype(np.float64)
+            n_pos = float(y.sum())
+            n_neg = float(len(y) - n_pos)
+            # score = 1/rank is strictly decreasing in rank, so ascending-score rank = len - rank + 1
+            asc = len(y) - r + 1.0
+            out[i, 0] = (asc[y > 0].sum() - n_pos * (n_pos + 1) / 2.0) / np.float64(n_pos * n_neg)
+            by_rank = y[np.argsort(r, kind="stable")]
+            out[i, 1] = np.sum(by_rank / (np.arange(len(y)) + 1.0)) / np.float64(n_pos)
+            ideal = np.sort(y)[::-1]
+            out[i, 2] = np.float64(_dcg(by_rank, 5)) / np.float64(_dcg(ideal, 5))
+            out[i, 3] = np.float64(_dcg(by_rank, 10)) / np.float64(_dcg(ideal, 10))
+    return out
+
+
+def scoring(labels: np.ndarray, ranks: np.ndarray, row_impression: np.ndarray) -> Tuple[float, float, float, float]:
+    """(AUC, MRR, nDCG@5, nDCG@10), mean over impressions that have at least one row."""
+    per = impression_metric_rows(labels, ranks, row_impression)
+    return tuple(float(np.mean(np.ascontiguousarray(per[:, k]))) for k in range(4))
 
 
 def rank_file_bytes(ranks: np.ndarray, row_impression: np.ndarray) -> bytes:
@@ -1062,6 +1070,438 @@ def quality_summary(q, exposure=None, pool=None):
             out["coverage"] = float((x > 0).sum()) / n
             if x.sum() > 0:
                 out["gini"] = float(2.0 * (np.arange(1, n + 1) * x).sum() / (n * x.sum()) - (n + 1.0) / n)
+    return out
+
+
+BOOTSTRAP_MAX_COLUMNS = 16     # include/digat_hip.h: DIGAT_BOOTSTRAP_MAX_COLUMNS
+BOOTSTRAP_SLICE = 8192         # ... DIGAT_BOOTSTRAP_SLICE, the draws one workgroup of digat_bootstrap_sums adds
+BOOTSTRAP_MAX_REPLICATE = 1 << 31      # first_replicate + replicates may reach this
+_BOOTSTRAP_WORKSPACE = 1 << 28         # bootstrap_sums splits a call whose slice partials would need more bytes than this
+_M32 = np.uint64(0xFFFFFFFF)
+METRIC_NAMES = ("auc", "mrr", "ndcg5", "ndcg10")      # the columns of impression_metrics
+
+
+def _hash32(x: np.ndarray) -> np.ndarray:
+    """csrc/digat_kernels.hip: hash32, on the low 32 bits of a uint64 array."""
+    x = x & _M32
+    x = x ^ (x >> np.uint64(16))
+    x = (x * np.uint64(0x7feb352d)) & _M32
+    x = x ^ (x >> np.uint64(15))
+    x = (x * np.uint64(0x846ca68b)) & _M32
+    return x ^ (x >> np.uint64(16))
+
+
+def _is_tensor(x) -> bool:
+    return hasattr(x, "detach") and hasattr(x, "is_cuda")         # a torch tensor, without importing torch
+
+
+def _on_device(x) -> bool:
+    return _is_tensor(x) and bool(x.is_cuda)
+
+
+def _host(x) -> np.ndarray:
+    return np.asarray(x.detach().cpu() if _is_tensor(x) else x)
+
+
+def _check_bootstrap_args(n, c, replicates, first_replicate):
+    if int(n) < 1:
+        raise ValueError(f"values must have at least one row (a resampling unit), got n = {n}")
+    if int(n) > (1 << 31) - 1:
+        raise ValueError(f"values must have at most 2^31 - 1 rows, got n = {n}")
+    if c is not None and not 1 <= int(c) <= BOOTSTRAP_MAX_COLUMNS:
+        raise ValueError(f"values must have between 1 and BOOTSTRAP_MAX_COLUMNS = {BOOTSTRAP_MAX_COLUMNS} columns, got {c}")
+    if int(replicates) != replicates or int(replicates) < 1:
+        raise ValueError(f"replicates must be a positive integer, got {replicates}")
+    if int(first_replicate) != first_replicate or int(first_replicate) < 0:
+        raise ValueError(f"first_replicate must be a non-negative integer, got {first_replicate}")
+    if int(first_replicate) + int(replicates) > BOOTSTRAP_MAX_REPLICATE:
+        raise ValueError(f"first_replicate + replicates must not exceed 2^31, got {first_replicate} + {replicates}")
+
+
+def bootstrap_draws_host(n: int, replicates: int, seed: int = 0, first_replicate: int = 0) -> np.ndarray:
+    """The draws of ``digat_bootstrap_sums`` in numpy, bit for bit: ``idx`` [replicates, n] int64.  Replicate ``r = first_replicate
+    + b`` draws n units with replacement; draw j has the 64-bit counter ``e = r n + j``, the word ``w = hash32((uint32)e *
+    0x9E3779B9 + hash32(seed + (uint32)(e >> 32)))`` (``drop_keep``'s construction, the low 32 bits of ``seed`` used as given) and
+    the unit ``(w n) >> 32``: uniform on [0, n) up to a bias of at most ``n / 2^32``."""
+    _check_bootstrap_args(n, None, replicates, first_replicate)
+    n64 = np.uint64(int(n))
+    r = np.arange(int(first_replicate), int(first_replicate) + int(replicates), dtype=np.uint64)
+    e = r[:, None] * n64 + np.arange(int(n), dtype=np.uint64)[None, :]
+    inner = _hash32(np.uint64(int(seed) & 0xFFFFFFFF) + (e >> np.uint64(32)))
+    w = _hash32((((e & _M32) * np.uint64(0x9E3779B9)) & _M32) + inner)
+    return ((w * n64) >> np.uint64(32)).astype(np.int64)
+
+
+def _value_matrix(values, name="values"):
+    """``values`` as float64 [n, c] (a 1-D input is one column): a CUDA tensor stays one, everything else becomes numpy."""
+    if _on_device(values):
+        import torch
+        v = values.detach()
+        v = v.reshape(-1, 1) if v.dim() == 1 else v
+        if v.dim() != 2 or not (v.is_floating_point() or v.dtype in (torch.int32, torch.int64, torch.uint8, torch.bool)):
+            raise ValueError(f"{name} must be a real [n, c] array, got {tuple(values.shape)} {values.dtype}")
+        return v if v.dtype == torch.float64 else v.to(torch.float64)
+    v = _host(values)
+    if v.dtype.kind not in "fiub":
+        raise ValueError(f"{name} must be a real [n, c] array, got dtype {v.dtype}")
+    v = v.astype(np.float64, copy=False)
+    v = v.reshape(-1, 1) if v.ndim == 1 else v
+    if v.ndim != 2:
+        raise ValueError(f"{name} must be [n, c], got shape {v.shape}")
+    return v
+
+
+def bootstrap_sums_host(values, replicates: int, seed: int = 0, first_replicate: int = 0) -> np.ndarray:
+    """The yardstick of ``bootstrap_sums``: ``sums`` [replicates, c] float64, ``sums[b, k]`` the CORRECTLY ROUNDED sum
+    (``math.fsum``) of ``values[idx, k]`` over replicate b's draws ``bootstrap_draws_host`` gives.  ``values``: [n, c] (or [n])."""
+    import math
+    v = np.ascontiguousarray(_value_matrix(_host(values)))
+    n, c = v.shape
+    _check_bootstrap_args(n, c, replicates, first_replicate)
+    B = int(replicates)
+    out = np.empty((B, c), dtype=np.float64)
+    per = max(1, (1 << 22) // n)
+    for b0 in range(0, B, per):
+        idx = bootstrap_draws_host(n, min(per, B - b0), seed, int(first_replicate) + b0)
+        for b in range(idx.shape[0]):
+            rows = v[idx[b]]
+            for k in range(c):
+                out[b0 + b, k] = math.fsum(rows[:, k].tolist())
+    return out
+
+
+def bootstrap_sums(values, replicates: int, seed: int = 0, first_replicate: int = 0):
+    """Bootstrap sums on the GPU (``digat_bootstrap_sums``): ``sums`` [replicates, c] float64 on the device of ``values`` [n, c]
+    (or [n]: one column), ``sums[b, :]`` the sum of the n rows replicate ``first_replicate + b`` draws with replacement —
+    ``bootstrap_draws_host``'s draws, one index per draw for every column.  ``values``: a device tensor of any real dtype and any
+    strides, converted to contiguous float64 once (exactly, from float32 and the integers).  1 <= c <= 16, ``first_replicate +
+    replicates <= 2^31``.  A column's sums depend on that column, n, ``seed`` and the replicate alone: the same bits from run to
+    run, from a call split by ``first_replicate`` and from the columns split over two calls; against ``bootstrap_sums_host`` an
+    entry is off by at most ``n 2^-53 sum |terms|`` and exact on integer-valued data below 2^53.  Stream-ordered: nothing is read
+    back (a call whose slice partials would pass 256 MiB is split by replicates)."""
+    import torch
+    from . import _lib
+    dev = _lib.require_device(values)
+    v = _value_matrix(values).contiguous()
+    n, c = int(v.shape[0]), int(v.shape[1])
+    _check_bootstrap_args(n, c, replicates, first_replicate)
+    B, r0 = int(replicates), int(first_replicate)
+    sums = torch.empty((B, c), dtype=torch.float64, device=dev)
+    L = _lib.lib()
+    per_replicate = int(L.digat_bootstrap_workspace_bytes(n, c, 1))
+    per = B if per_replicate == 0 else max(1, min(B, _BOOTSTRAP_WORKSPACE // per_replicate))
+    need = per * per_replicate
+    ws = _lib.workspace(need, dev, "bootstrap")
+    for b0 in range(0, B, per):
+        nb = min(per, B - b0)
+        _lib.check(L.digat_bootstrap_sums(v.data_ptr(), n, c, nb, r0 + b0, int(seed) & 0xFFFFFFFF, sums.data_ptr() + b0 * c * 8,
+                                          ws.data_ptr(), need, _lib.stream_ptr()),
+                   "digat_bootstrap_sums")
+    return sums
+
+
+def _check_units(units, rows: int) -> np.ndarray:
+    """``units`` — a CSR ``start`` over contiguous rows — as a host int64 array: [U + 1] offsets from 0 to ``rows`` that never decrease."""
+    st = _host(units)
+    if st.ndim != 1 or st.shape[0] < 1 or st.dtype.kind not in "iu":
+        raise ValueError(f"start must be a 1-D integer array of units + 1 row offsets, got shape {st.shape} {st.dtype}")
+    st = st.astype(np.int64)
+    if st[0] != 0 or np.any(np.diff(st) < 0) or int(st[-1]) != rows:
+        raise ValueError(f"start must begin at 0, never decrease and end at the number of rows ({rows})")
+    return st
+
+
+def segment_sums_host(values, start) -> np.ndarray:
+    """``out`` [U, c] float64: ``out[u, :]`` the sum of the rows ``start[u] .. start[u+1] - 1`` of ``values`` [rows, c] (or [rows]),
+    added left to right from 0.0 — the order of ``segment_sums``, so the same bits.  An empty unit gives 0."""
+    v = _value_matrix(_host(values))
+    st = _check_units(start, v.shape[0])
+    length = np.diff(st)
+    out = np.zeros((len(length), v.shape[1]), dtype=np.float64)
+    for p in range(int(length.max()) if len(length) else 0):
+        live = np.flatnonzero(length > p)
+        out[live] += v[st[live] + p]
+    return out
+
+
+def segment_sums(values, start):
+    """Row-level values turned into resampling units on the GPU (``digat_segment_sums_f64``): ``out`` [U, c] float64 on the device
+    of ``values`` [rows, c] (or [rows]; any real dtype), ``out[u, :]`` the sum of the rows ``start[u] .. start[u+1] - 1`` added left
+    to right (bit-identical to ``segment_sums_host``), 0 for an empty unit.  ``start`` [U + 1] is checked on the host (an array, or
+    a tensor that is read back), then uploaded.  Stream-ordered otherwise: one launch."""
+    import torch
+    from . import _lib
+    dev = _lib.require_device(values)
+    v = _value_matrix(values).contiguous()
+    rows, c = int(v.shape[0]), int(v.shape[1])
+    if c < 1:
+        raise ValueError("values must have at least one column")
+    st = _check_units(start, rows)
+    U = len(st) - 1
+    out = torch.empty((U, c), dtype=torch.float64, device=dev)
+    if U == 0:
+        return out
+    std = torch.from_numpy(st).to(dev)
+    _lib.check(_lib.lib().digat_segment_sums_f64(v.data_ptr() if rows else None, rows, c, std.data_ptr(), U, out.data_ptr(), _lib.stream_ptr()),
+               "digat_segment_sums_f64")
+    return out
+
+
+def impression_metrics(scores, row_impression, labels):
+    """``[I, 4]`` float64: AUC, MRR, nDCG@5 and nDCG@10 of every impression (``METRIC_NAMES``) — the resampling units of a dev run.
+    For CUDA ``scores`` [R] this is ``digat_rank_metrics``' own per-impression output, the array whose mean
+    ``device_ranks_and_metrics`` reports, and it stays on the device; for host scores (an array or a CPU tensor) it is
+    ``impression_metric_rows``, the values ``scoring`` averages.  Rows are impression-major; an impression without a positive or
+    without a negative has a row that is not finite (``metric_intervals`` refuses it by its index)."""
+    imp = np.asarray(row_impression, dtype=np.int64)
+    if not _on_device(scores):
+        return impression_metric_rows(labels, impression_ranks(_host(scores), imp), imp)
+    import torch
+    from . import _lib
+    dev = _lib.require_device(scores)
+    R = len(imp)
+    if int(scores.shape[0]) != R or len(labels) != R:
+        raise ValueError(f"scores, row_impression and labels must have one entry per row, got {int(scores.shape[0])}, {R} and {len(labels)}")
+    if np.any(np.diff(imp) < 0):
+        raise ValueError("rows must be impression-major")
+    per = torch.empty((0, 4), dtype=torch.float64, device=dev)
+    if R == 0:
+        return per
+    starts = np.r_[0, np.flatnonzero(np.diff(imp)) + 1, R].astype(np.int64)
+    I = len(starts) - 1
+    sc = scores.detach().to(torch.float32).contiguous()
+    st = torch.from_numpy(starts).to(dev)
+    lab = torch.from_numpy(np.ascontiguousarray(np.asarray(labels) > 0).view(np.uint8)).to(dev)
+    ranks = torch.empty(R, dtype=torch.int32, device=dev)
+    per = torch.empty((I, 4), dtype=torch.float64, device=dev)
+    _lib.check(_lib.lib().digat_rank_metrics(sc.data_ptr(), lab.data_ptr(), st.data_ptr(), I, ranks.data_ptr(), per.data_ptr(), None,
+                                             _lib.stream_ptr()),
+               "digat_rank_metrics")
+    return per
+
+
+def _check_level(level) -> float:
+    if not 0.0 < float(level) < 1.0:
+        raise ValueError(f"level must lie inside (0, 1), got {level}")
+    return float(level)
+
+
+def _check_finite(m, name):
+    if _on_device(m):
+        import torch
+        bad = torch.nonzero(~torch.isfinite(m).all(dim=1))
+        first = int(bad[0, 0]) if bad.numel() else None
+    else:
+        bad = np.flatnonzero(~np.isfinite(m).all(axis=1))
+        first = int(bad[0]) if len(bad) else None
+    if first is not None:
+        raise ValueError(f"{name} must be finite: row {first} is not (an impression without a positive or without a negative has no "
+                         "AUC / MRR / nDCG; leave such rows out)")
+
+
+def _statistic_columns(values, denominators, units, name="values"):
+    """What one set of columns hands the resampling: ``(matrix [n, cv + cd], cv, cd)`` — the value columns, then cd = 0 (the
+    statistic divides by n), 1 (one denominator for every column) or cv denominator columns —, rows summed into ``units`` first;
+    under ``units`` without ``denominators`` the unit's row count is the denominator."""
+    v = _value_matrix(values, name)
+    _check_finite(v, name)
+    rows, cv = int(v.shape[0]), int(v.shape[1])
+    dev = _on_device(v)
+    parts, cd = [v], 0
+    if denominators is not None:
+        dname = "denominators" + name[len("values"):]
+        d = _value_matrix(denominators, dname)
+        if dev != _on_device(d):
+            import torch
+            d = torch.from_numpy(np.ascontiguousarray(d)).to(v.device) if dev else _host(d)
+        cd = int(d.shape[1])
+        if int(d.shape[0]) != rows or cd not in (1, cv):
+            raise ValueError(f"{dname} must be [n] or [n, c] for {name} [{rows}, {cv}], got shape {tuple(d.shape)}")
+        _check_finite(d, dname)
+        parts.append(d)
+    if dev:
+        import torch
+        m = torch.cat(parts, dim=1) if len(parts) > 1 else v
+    else:
+        m = np.concatenate(parts, axis=1) if len(parts) > 1 else v
+    if units is not None:
+        st = _check_units(units, rows)
+        m = segment_sums(m, st) if dev else segment_sums_host(m, st)
+        if denominators is None:
+            count = np.diff(st).astype(np.float64)[:, None]
+            if dev:
+                import torch
+                m = torch.cat([m, torch.from_numpy(count).to(m.device)], dim=1)
+            else:
+                m = np.concatenate([m, count], axis=1)
+            cd = 1
+    return m, cv, cd
+
+
+def _resample(m, replicates, seed):
+    """``(totals [c], sums [B, c])`` of a matrix, as host float64 arrays: device tensors through the kernel, numpy through its host twin."""
+    if _on_device(m):
+        total = m.sum(dim=0).cpu().numpy()
+        return total, bootstrap_sums(m, replicates, seed).cpu().numpy()
+    return np.array([np.sum(np.ascontiguousarray(m[:, k])) for k in range(m.shape[1])], dtype=np.float64), bootstrap_sums_host(m, replicates, seed)
+
+
+def _statistics(total, sums, n, cv, cd):
+    """The statistic of the data ([cv]) and of every replicate ([B, cv]) from the column totals and the replicate sums of one set."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if cd == 0:
+            return total[:cv] / np.float64(n), sums[:, :cv] / np.float64(n)
+        den, dens = (total[cv:cv + 1], sums[:, cv:cv + 1]) if cd == 1 else (total[cv:2 * cv], sums[:, cv:2 * cv])
+        return total[:cv] / den, sums[:, :cv] / dens
+
+
+def interval_fields(value, stats, level):
+    """One column's entry of ``metric_intervals`` from its replicate statistics ``stats`` [B]: the percentile interval —
+    ``numpy.quantile(stats, q, method="linear")`` at ``(1 - level) / 2`` and ``1 - (1 - level) / 2`` — and ``se``, their
+    ``std(ddof=1)`` (NaN for one replicate)."""
+    stats = np.asarray(stats, dtype=np.float64)
+    alpha = (1.0 - _check_level(level)) / 2.0
+    lo, hi = np.quantile(stats, [alpha, 1.0 - alpha], method="linear")
+    se = float(np.std(stats, ddof=1)) if len(stats) > 1 else float("nan")
+    return {"value": float(value), "lo": float(lo), "hi": float(hi), "se": se, "replicates": int(len(stats)), "level": float(level)}
+
+
+def paired_fields(a, b, diffs, level):
+    """One column's entry of ``compare_metrics`` from the replicate differences ``diffs`` [B] = ``stat_a* - stat_b*``: the
+    percentile interval and ``se`` of ``interval_fields``, ``p = min(1, 2 min((#{d* <= 0} + 1) / (B + 1), (#{d* >= 0} + 1) /
+    (B + 1)))`` — two-sided, never 0 — and ``wins``, the share of replicates with ``d* > 0``."""
+    diffs = np.asarray(diffs, dtype=np.float64)
+    B = len(diffs)
+    f = interval_fields(float(a) - float(b), diffs, level)
+    p = min(1.0, 2.0 * min((int((diffs <= 0).sum()) + 1) / (B + 1), (int((diffs >= 0).sum()) + 1) / (B + 1)))
+    return {"a": float(a), "b": float(b), "diff": f["value"], "lo": f["lo"], "hi": f["hi"], "se": f["se"], "p": float(p),
+            "wins": float((diffs > 0).sum()) / B}
+
+
+def _column_names(names, c):
+    names = tuple("column%d" % k for k in range(c)) if names is None else tuple(names)
+    if len(names) != c or len(set(names)) != c:
+        raise ValueError(f"names must give {c} different names, one per column, got {names}")
+    return names
+
+
+def metric_intervals(values, names=None, replicates: int = 2000, level: float = 0.95, seed: int = 0, denominators=None, units=None):
+    """Bootstrap PERCENTILE intervals of the means this library reports: ``name -> {value, lo, hi, se, replicates, level}``.
+
+    ``values`` [n, c] (or [n]) holds one row per resampling unit — ``impression_metrics``' rows, ``rank_metric_columns``' users —
+    and the statistic of column k is ``sum(values[:, k]) / n``; with ``denominators`` ([n], shared, or [n, c]) it is
+    ``sum(values[:, k]) / sum(denominators)``, a ratio of sums (recall over all targets).  ``units`` — a CSR ``start`` [U + 1] over
+    contiguous rows — resamples whole units (a reader's impressions) instead of rows: the rows are summed per unit first
+    (``segment_sums``), and without ``denominators`` a unit's row count is its denominator, so the statistic stays the mean over
+    rows.  The unit is what the caller hands in: rows that belong to one reader are only kept together by ``units``.
+    Each of the ``replicates`` draws n units with replacement (``bootstrap_draws_host``, ``seed``) and gives one replicate
+    statistic; ``lo`` / ``hi`` are ``numpy.quantile(..., method="linear")`` of them at ``(1 - level) / 2`` and ``1 - (1 - level) /
+    2``, ``se`` their ``std(ddof=1)``, ``value`` the statistic of the data itself.  CUDA tensors go through the kernel
+    (``bootstrap_sums``), numpy arrays and CPU tensors through its host twin (``bootstrap_sums_host``) — the same draws, so the same
+    result to the rounding of the sums.  Value and denominator columns together are at most 16.  Non-finite input is a
+    ``ValueError`` that names the first bad row."""
+    _check_level(level)
+    m, cv, cd = _statistic_columns(values, denominators, units)
+    names = _column_names(names, cv)
+    n, c = int(m.shape[0]), int(m.shape[1])
+    _check_bootstrap_args(n, c, replicates, 0)
+    total, sums = _resample(m, int(replicates), seed)
+    value, stats = _statistics(total, sums, n, cv, cd)
+    return {name: interval_fields(value[k], stats[:, k], level) for k, name in enumerate(names)}
+
+
+def compare_metrics(values_a, values_b, names=None, replicates: int = 2000, level: float = 0.95, seed: int = 0,
+                    denominators_a=None, denominators_b=None, units=None):
+    """Is the difference real?  The PAIRED bootstrap of two models scored on the same units: ``name -> {a, b, diff, lo, hi, se, p,
+    wins}``.  ``values_a`` and ``values_b`` [n, c] hold the same units in the same order (``impression_metrics`` of two models on
+    one dev set); both go through ONE resampling as ``[a | b]`` — one index per draw serves every column, so each replicate
+    compares the two models on the same resampled units — and the replicate statistic is ``stat_a* - stat_b*``, the statistics
+    being ``metric_intervals``' (``denominators_a`` / ``denominators_b`` and ``units`` as there).  ``a``, ``b``: the statistics of
+    the data; ``diff = a - b``; ``lo`` / ``hi`` / ``se``: the percentile interval and standard error of the replicate differences;
+    ``p``: the two-sided bootstrap p-value ``min(1, 2 min((#{d* <= 0} + 1) / (B + 1), (#{d* >= 0} + 1) / (B + 1)))``; ``wins``: the
+    share of replicates with ``d* > 0``.  All columns of both sets together are at most 16 (c <= 8 each without denominators)."""
+    _check_level(level)
+    sa, sb = tuple(np.shape(values_a)), tuple(np.shape(values_b))
+    if sa != sb:
+        raise ValueError(f"values_a and values_b must have the same shape (the same units in the same order), got {sa} and {sb}")
+    ma, cva, cda = _statistic_columns(values_a, denominators_a, units, "values_a")
+    mb, cvb, cdb = _statistic_columns(values_b, denominators_b, units, "values_b")
+    names = _column_names(names, cva)
+    if _on_device(ma) != _on_device(mb):
+        raise ValueError("values_a and values_b must both be device tensors or both be host arrays")
+    if _on_device(ma):
+        import torch
+        m = torch.cat([ma, mb.to(ma.device)], dim=1)
+    else:
+        m = np.concatenate([ma, mb], axis=1)
+    n, ca = int(m.shape[0]), int(ma.shape[1])
+    if int(m.shape[1]) > BOOTSTRAP_MAX_COLUMNS:
+        raise ValueError(f"values_a and values_b with their denominators have {int(m.shape[1])} columns together, at most "
+                         f"BOOTSTRAP_MAX_COLUMNS = {BOOTSTRAP_MAX_COLUMNS} go through one resampling")
+    _check_bootstrap_args(n, int(m.shape[1]), replicates, 0)
+    total, sums = _resample(m, int(replicates), seed)
+    a, stat_a = _statistics(total[:ca], sums[:, :ca], n, cva, cda)
+    b, stat_b = _statistics(total[ca:], sums[:, ca:], n, cvb, cdb)
+    return {name: paired_fields(a[k], b[k], stat_a[:, k] - stat_b[:, k], level) for k, name in enumerate(names)}
+
+
+def rank_metric_columns(rank, target_start, ks=(10, 50, 100, 128)):
+    """The per-user numerators and denominators ``rank_metrics``' averages are made of — what a bootstrap over users resamples.
+    A dict of float64 arrays [U], one entry per user of ``target_start`` (a user without targets holds zeros): ``hits@k`` — the
+    user's targets with ``0 <= rank < k`` —, ``targets`` — the user's target count —, ``share@k`` — ``hits@k / targets`` (0 without
+    targets) —, ``rr`` — ``1 / (1 + best rank)``, 0 when none of the user's targets is ranked — and ``has`` — 1 for a user with a
+    target.  ``recall@k = sum(hits@k) / sum(targets)``, ``user_recall@k = sum(share@k) / sum(has)`` and ``mrr = sum(rr) / sum(has)``
+    reproduce ``rank_metrics`` to float64 rounding."""
+    r = _host(rank).astype(np.int64)
+    if r.ndim != 1:
+        raise ValueError("rank must be 1-D")
+    st = _host(target_start)
+    if st.size == 0:
+        st = np.zeros(1, dtype=np.int64)
+    st = _check_target_start(st, len(st) - 1 if st.ndim == 1 else 0, len(r))
+    per_user = np.diff(st)
+    U = len(per_user)
+    owner = np.repeat(np.arange(U), per_user)
+    ranked = r >= 0
+    have = per_user > 0
+    out = {"targets": per_user.astype(np.float64), "has": have.astype(np.float64)}
+    for k in ks:
+        if int(k) != k or k < 1:
+            raise ValueError(f"every k must be a positive integer, got {k}")
+        hits = np.bincount(owner, weights=(ranked & (r < int(k))).astype(np.float64), minlength=U)
+        out[f"hits@{int(k)}"] = hits
+        out[f"share@{int(k)}"] = np.where(have, hits / np.maximum(per_user, 1), 0.0)
+    best = np.full(U, np.iinfo(np.int64).max, dtype=np.int64)
+    np.minimum.at(best, owner[ranked], r[ranked])
+    found = best != np.iinfo(np.int64).max
+    out["rr"] = np.where(found, 1.0 / (1.0 + np.where(found, best, 0).astype(np.float64)), 0.0)
+    return out
+
+
+def rank_metrics_intervals(rank, target_start, ks=(10, 50, 100, 128), replicates: int = 2000, level: float = 0.95, seed: int = 0, device=None):
+    """Percentile intervals of ``rank_metrics``' averages by a bootstrap over USERS (those with at least one target):
+    ``{"recall@k", "user_recall@k", "mrr"} -> {value, lo, hi, se, replicates, level}`` — ``metric_intervals``' fields, every metric
+    from the same draws (one resampling of ``rank_metric_columns``: ``recall@k`` as the ratio of summed hits to summed targets,
+    the other two as means over users).  ``median_rank`` is not a sum over users and gets NO interval, nor do the counts.  At most 7
+    values of k (2 k + 2 columns).  ``device``: a CUDA device runs the resampling on the GPU, None the host twin."""
+    _check_level(level)
+    ks = tuple(int(k) for k in ks)
+    col = rank_metric_columns(rank, target_start, ks)
+    keep = col["has"] > 0
+    if 2 * len(ks) + 2 > BOOTSTRAP_MAX_COLUMNS:
+        raise ValueError(f"ks: at most {(BOOTSTRAP_MAX_COLUMNS - 2) // 2} values of k go through one resampling, got {len(ks)}")
+    m = np.stack([col[f"hits@{k}"][keep] for k in ks] + [col[f"share@{k}"][keep] for k in ks] + [col["rr"][keep], col["targets"][keep]], axis=1)
+    n, K = int(m.shape[0]), len(ks)
+    _check_bootstrap_args(n, int(m.shape[1]), replicates, 0)
+    if device is not None:
+        import torch
+        m = torch.from_numpy(np.ascontiguousarray(m)).to(device)
+    total, sums = _resample(m, int(replicates), seed)
+    out = {}
+    for i, k in enumerate(ks):
+        out[f"recall@{k}"] = interval_fields(total[i] / total[-1], sums[:, i] / sums[:, -1], level)
+        out[f"user_recall@{k}"] = interval_fields(total[K + i] / n, sums[:, K + i] / n, level)
+    out["mrr"] = interval_fields(total[2 * K] / n, sums[:, 2 * K] / n, level)
     return out
 
 

@@ -13,6 +13,9 @@ corpus, picks the ``--recommend_k`` best of ALL non-PAD news the impression's us
 ``--recommend_max_per_category Q`` at most Q of one category — on a corpus that carries the news' categories (MIND does).
 ``--recommend_report 0,0.1,0.3`` then prints one line per diversity with what the knob buys and costs (``util.recommend_report``: one
 scoring pass for all of them; on a labelled split the accuracy of the lists against each impression's clicked candidates as well).
+``--bootstrap B`` (``dev`` / ``test`` on a labelled split) prints, below the four metrics, one line per metric with its percentile
+interval from B bootstrap replicates over impressions (``--bootstrap_level``, ``--seed``); ``--compare_model_path PATH`` loads a
+second checkpoint of the same architecture and prints the paired bootstrap of the differences (``evaluate.compare_metrics``).
 """
 from __future__ import annotations
 
@@ -84,6 +87,37 @@ def report_lines(model, dc, k: int, batch_size: int, diversities, shortlist: int
                                  targets=None if labels is None else clicked_targets(dc, labels), batch_size=batch_size)
     fmt = lambda v: '%d' % v if isinstance(v, int) else '%.4f' % v
     return ['diversity %.3f : ' % r['diversity'] + '  '.join('%s %s' % (f, fmt(v)) for f, v in r.items() if f != 'diversity') for r in rows]
+
+
+def interval_lines(per_impression, replicates: int, level: float, seed: int):
+    """One line per metric below the four of a labelled dev / test run: its bootstrap percentile interval over impressions
+    (``evaluate.metric_intervals`` of the ``evaluate.impression_metrics`` rows), with the replicates, the level and the seed."""
+    from . import evaluate
+    got = evaluate.metric_intervals(per_impression, names=evaluate.METRIC_NAMES, replicates=replicates, level=level, seed=seed)
+    label = dict(zip(evaluate.METRIC_NAMES, ('AUC', 'MRR', 'nDCG@5', 'nDCG@10')))
+    return ['%s interval : [%.4f, %.4f]  se %.4f  (%d bootstrap replicates over %d impressions, level %g, seed %d)'
+            % (label[k], v['lo'], v['hi'], v['se'], v['replicates'], int(per_impression.shape[0]), v['level'], seed) for k, v in got.items()]
+
+
+def compare_lines(per_a, per_b, replicates: int, level: float, seed: int):
+    """One line per metric of ``--compare_model_path``: the paired bootstrap of the two checkpoints' per-impression metrics
+    (``evaluate.compare_metrics``; a is the scored model, b the compared one)."""
+    from . import evaluate
+    got = evaluate.compare_metrics(per_a, per_b, names=evaluate.METRIC_NAMES, replicates=replicates, level=level, seed=seed)
+    label = dict(zip(evaluate.METRIC_NAMES, ('AUC', 'MRR', 'nDCG@5', 'nDCG@10')))
+    return ['%s difference : %.4f - %.4f = %+.4f  [%+.4f, %+.4f]  se %.4f  p %.4f  wins %.3f  (%d paired replicates, level %g, seed %d)'
+            % (label[k], v['a'], v['b'], v['diff'], v['lo'], v['hi'], v['se'], v['p'], v['wins'], replicates, level, seed)
+            for k, v in got.items()]
+
+
+def second_model(config, model, path: str, dev):
+    """``--compare_model_path``: a model of the architecture of ``model`` (a table-backed news encoder shares the table's values)
+    with the checkpoint at ``path`` loaded."""
+    table = getattr(model.news_encoder, 'table', None)
+    other = Model(config) if table is None else Model(config, news_encoder=PrecomputedNewsEncoder(table.detach().cpu().clone(), trainable=False))
+    other.initialize()
+    load_checkpoint(other, path)
+    return other.to(dev)
 
 
 def synthetic_setup(config, dev):
@@ -182,6 +216,23 @@ def main(argv=None):
         if metrics is not None:                                  # an unlabelled test file: the rank file is the result
             print('AUC : %.4f\nMRR : %.4f\nnDCG@5 : %.4f\nnDCG@10 : %.4f' % metrics)
         print('Inference time : %.1fs' % (time.time() - start))
+        replicates = getattr(config, 'bootstrap', 0)
+        if metrics is not None and replicates:                   # the instrument beside the means: percentile intervals over impressions
+            from . import evaluate
+            row_imp = dc.row_impression.cpu().numpy()
+            per = evaluate.impression_metrics(torch.from_numpy(np.ascontiguousarray(scores)).to(dev), row_imp, labels)
+            for line in interval_lines(per, replicates, config.bootstrap_level, config.seed):
+                print(line)
+            if config.compare_model_path:
+                other = second_model(config, model, config.compare_model_path, dev)
+                if hasattr(other.news_encoder, 'table'):
+                    dc.news_embedding = other.news_encoder.table.detach()
+                if hasattr(other.graph_encoder, 'projection_mode'):
+                    other.graph_encoder.projection_mode = config.inference_projection
+                scores_b, _ = util.compute_scores(other, dc, config.batch_size * 16)
+                per_b = evaluate.impression_metrics(torch.from_numpy(np.ascontiguousarray(scores_b)).to(dev), row_imp, labels)
+                for line in compare_lines(per, per_b, replicates, config.bootstrap_level, config.seed):
+                    print(line)
 
 
 if __name__ == '__main__':

@@ -625,7 +625,8 @@ def _clicked_targets(dev, users):
     return idx, cand[rows[take]], start
 
 
-def retrieval_metrics(model, dev, users=None, targets=None, candidates=None, ks=(10, 50, 100, 128), exclude_history=True, batch_size=1024):
+def retrieval_metrics(model, dev, users=None, targets=None, candidates=None, ks=(10, 50, 100, 128), exclude_history=True, batch_size=1024,
+                      intervals=None, level=0.95, seed=0):
     """Full-catalogue retrieval metrics of the first stage: where in a user's whole ordered pool the target news stand — how long
     ``recommend``'s shortlist must be for a clicked news to survive into a re-rank (``evaluate.shortlist_for`` on the returned
     ranks).  Returns ``evaluate.rank_metrics``' dict plus ``rank`` [T] int32 (0-based, -1: not ranked), ``target_start`` [G+1] and
@@ -641,7 +642,11 @@ def retrieval_metrics(model, dev, users=None, targets=None, candidates=None, ks=
     counts as a miss in every recall, and ``not_ranked`` says how many there are.
 
     On CUDA tensors the ranks come from ``evaluate.dot_rank`` (``digat_dot_rank``: no [users, news] score matrix); on CPU tensors
-    from the stock product and ``evaluate.dot_rank_host``."""
+    from the stock product and ``evaluate.dot_rank_host``.
+
+    ``intervals``: None returns exactly the dict above; an integer B adds ``"intervals"`` — ``evaluate.rank_metrics_intervals``'
+    percentile intervals (``level``, ``seed``) of every ``recall@k``, ``user_recall@k`` and ``mrr`` from B bootstrap replicates over
+    the users with a target, resampled on the GPU for CUDA tensors; ``median_rank`` has none."""
     from . import evaluate, util
     N = int(dev.title_text.shape[0])
     if targets is None:
@@ -695,6 +700,9 @@ def retrieval_metrics(model, dev, users=None, targets=None, candidates=None, ks=
                                                  skip=None if skip is None else skip[g0:g1].numpy(), news_num=N)
     out = evaluate.rank_metrics(rank, target_start, ks)
     out.update(rank=rank, target_start=target_start, target_ids=target_ids)
+    if intervals is not None:
+        out["intervals"] = evaluate.rank_metrics_intervals(rank, target_start, ks, replicates=intervals, level=level, seed=seed,
+                                                           device=plain.device if plain.device.type == "cuda" else None)
     return out
 
 

@@ -1214,3 +1214,25 @@ def compute_scores(model, dc: DeviceCorpus, batch_size: int, labels: Optional[np
         return scores_np, None
     # ranking + metrics on the device (digat_rank_metrics); host tensors only occur in the CPU harness tests (score_fn)
     return scores_np, evaluate.ranks_metrics_file(scores, row_imp, labels, result_file)[1]
+
+
+def compare_models(model_a, model_b, dc: DeviceCorpus, labels: np.ndarray, replicates: int = 2000, level: float = 0.95, seed: int = 0,
+                   batch_size: int = 1024, score_fn: Optional[Callable] = None):
+    """Is model_a better than model_b on this corpus?  Two ``compute_scores`` passes over ``dc``, the per-impression AUC / MRR /
+    nDCG@5 / nDCG@10 of each (``evaluate.impression_metrics``: on the device for a CUDA corpus) and their PAIRED bootstrap over
+    impressions (``evaluate.compare_metrics``: every replicate resamples the same impressions for both models).  Returns
+    ``{"auc", "mrr", "ndcg5", "ndcg10"} -> {a, b, diff, lo, hi, se, p, wins}``; ``a`` and ``b`` are the metrics ``compute_scores``
+    reports, to float64 rounding.  Any two models that score the same corpus will do — ``DIGAT`` against an ablation encoder, two
+    checkpoints of one architecture.  The resampling unit is the impression; ``score_fn`` is ``compute_scores``'.  A model whose news encoder is a table scores
+    with its own table (``dc.news_embedding`` is set to it, as the dev driver does)."""
+    if labels is None:
+        raise ValueError("labels are needed: a comparison of metrics has nothing to compare on an unlabelled split")
+    row_imp = dc.row_impression.cpu().numpy()
+    dev = dc.row_impression.device
+    per = []
+    for model in (model_a, model_b):
+        if hasattr(getattr(model, "news_encoder", None), "table"):
+            dc.news_embedding = model.news_encoder.table.detach()
+        scores, _ = compute_scores(model, dc, batch_size, labels=None, score_fn=score_fn)
+        per.append(evaluate.impression_metrics(torch.from_numpy(np.ascontiguousarray(scores)).to(dev), row_imp, labels))
+    return evaluate.compare_metrics(per[0], per[1], names=evaluate.METRIC_NAMES, replicates=replicates, level=level, seed=seed)

@@ -765,6 +765,42 @@ int digat_list_quality(const int64_t* ids, const int32_t* count, int64_t G, int 
                        int32_t* out_elements, double* out_sim_sum, float* out_sim_max, int32_t* out_categories, int32_t* out_category_max,
                        int32_t* out_overlap, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- bootstrap resampling of per-unit metric rows (digat_amd.evaluate.bootstrap_sums / metric_intervals / compare_metrics) -----
+ * values [n, c] float64 row-major: one row per resampling unit (an impression, a user), one column per summed quantity;
+ * sums [B, c] float64.  Replicate r = first_replicate + b makes n draws with replacement; draw j has the 64-bit counter
+ * e = r n + j, the word w = hash32((uint32)e * 0x9E3779B9 + hash32(seed + (uint32)(e >> 32))) — the dropout hash's construction, the
+ * seed used as given — and the unit idx = (w n) >> 32 (64-bit product; idx < n always; idx is uniform up to a bias of at most
+ * n / 2^32); sums[b, :] = sum over j of values[idx_j, :].  ONE index per draw serves every column: the columns of two models side by
+ * side are resampled as pairs.  evaluate.bootstrap_draws_host restates the draws bit for bit.
+ * Determinism: the order in which a replicate's n terms are added is fixed by n alone — not by B, first_replicate, c, the grid or
+ * the other columns — and no floating-point atomics are used, so sums[b, k] depends on column k, n, seed and r only: the same bits
+ * from run to run, from a call split by first_replicate, and from the columns split over two calls.  Against the correctly rounded
+ * sum of the same draws an entry is off by at most n 2^-53 sum_j |values[idx_j, k]|; integer-valued data below 2^53 is exact.
+ * Limits: 1 <= n <= 2^31 - 1, 1 <= c <= DIGAT_BOOTSTRAP_MAX_COLUMNS, B >= 0, first_replicate >= 0, first_replicate + B <= 2^31
+ * (every counter stays below 2^62).  DIGAT_ERR_ARG: a null or not 8-byte-aligned values / sums (an odd workspace address too),
+ * n < 1, c < 1, B < 0, first_replicate < 0; DIGAT_ERR_SHAPE: n, c or first_replicate + B beyond the limits; DIGAT_ERR_WORKSPACE:
+ * fewer than digat_bootstrap_workspace_bytes(n, c, B) bytes — all before any HIP call.  B == 0 returns DIGAT_OK without a launch.
+ * The draws are cut into slices of DIGAT_BOOTSTRAP_SLICE; one workgroup per (slice, replicate) sums its slice in registers; with
+ * more than one slice the partial sums [B, slices, c] go through the workspace (8 B ceil(n / DIGAT_BOOTSTRAP_SLICE) c bytes, it may
+ * hold anything on entry; 0 bytes and workspace may be NULL for n <= DIGAT_BOOTSTRAP_SLICE) and a second launch adds a replicate's
+ * slices in ascending order.  Stream-ordered: one or two launches per 65 535 replicates on `stream`; no allocation, no host
+ * synchronisation, no read of device memory on the host.  digat_bootstrap_workspace_bytes returns 0 for arguments outside the limits. */
+#define DIGAT_BOOTSTRAP_MAX_COLUMNS 16
+#define DIGAT_BOOTSTRAP_SLICE 8192
+size_t digat_bootstrap_workspace_bytes(int64_t n, int c, int64_t B);
+int digat_bootstrap_sums(const double* values, int64_t n, int c, int64_t B, int64_t first_replicate, uint32_t seed, double* sums,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* out[u, :] = the sum of the rows start[u] .. start[u + 1] - 1 of values [rows, columns] float64, added left to right by one thread
+ * per (unit, column): row-level values turned into resampling units (a user's impressions, a user's targets).  start [units + 1]
+ * int64 on the device, non-decreasing from 0 to rows (the caller's concern; the kernel clamps what it reads to [0, rows], so no read
+ * leaves the table); an empty unit gives 0.0.  evaluate.segment_sums_host adds in the same order: the same bits.
+ * DIGAT_ERR_ARG: a null start / out (values too unless rows == 0), a pointer that is not 8-byte aligned, rows < 0, columns < 1,
+ * units < 0; DIGAT_ERR_SHAPE: columns > 2^20 or units x columns > 2^38 — before any HIP call.  units == 0 returns without a launch.
+ * Stream-ordered: one launch, no workspace. */
+int digat_segment_sums_f64(const double* values, int64_t rows, int columns, const int64_t* start, int64_t units, double* out,
+                           void* stream);
+
 /* ---- vanilla-GAT update layer of the ablation encoders -----------------------------------------
  * graphEncoders.py:493-519 (wo_interaction), :641-651 (News_graph_wo_inter), :788-798 (User_graph_wo_inter), eval mode:
  * h = X W^T + bW; e_ij = leaky_relu_0.2(a1.h_j + a2.h_i); -1e9 where A_ij = 0; alpha = softmax_j; out = relu(alpha h) + X.

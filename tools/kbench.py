@@ -58,6 +58,12 @@
                                              categories, a broadcast compare for the overlap and torch.bincount for the exposure,
                                              G = 64 and 4 096 lists of k = 10 and 100, d = 400, with and without category and base
                                              list, the legs in turn, median [min, max] of five rounds
+  python tools/kbench.py bootstrap [units columns replicates]   metric intervals: evaluate.bootstrap_sums (one kernel: hash a draw,
+                                             gather the row, add in registers) against torch.randint + gather + sum with the
+                                             replicates chunked to about 1 GiB of intermediates, and against the numpy twin at 20
+                                             replicates (as measured, not extrapolated); 73 152 units x 4 and 8 columns x 1 000 and
+                                             10 000 replicates, and 4 096 units x 8 columns; the legs in turn, median [min, max] of
+                                             five rounds, time and peak device bytes
   python tools/kbench.py sag-lists [news categories dim top_M]  the SAG's similar-news lists of a MIND-small-shaped corpus
                                              (65 238 news over 17 categories of skewed sizes, the largest ~30 %, dim 768, top_M 5):
                                              construct_SAG.similar_news_lists_device per category against cos_topk_device + all five
@@ -1494,6 +1500,78 @@ def bench_list_quality(news_num=65238, d=400, rounds=5):
                       f"largest |sim_sum difference| {off:.2e}", flush=True)
 
 
+def stock_bootstrap_sums(values, replicates, generator, budget=1 << 30):
+    """Bootstrap sums built only from stock PyTorch: ``torch.randint`` indices, a row gather and ``sum`` over the draws, the
+    replicates in chunks whose [chunk, n] int64 indices and [chunk, n, c] float64 rows together stay near ``budget`` bytes.  Its own
+    draws (torch's generator), so its sums are another sample of the same distribution, not the kernel's numbers."""
+    n, c = values.shape
+    per = max(1, budget // (n * (8 + 8 * c)))
+    out = torch.empty((replicates, c), dtype=torch.float64, device=values.device)
+    for b0 in range(0, replicates, per):
+        nb = min(per, replicates - b0)
+        idx = torch.randint(0, n, (nb, n), device=values.device, generator=generator)
+        out[b0:b0 + nb] = values[idx].sum(dim=1)
+    return out
+
+
+def bench_bootstrap(units=0, columns=0, replicates=0, rounds=5, host_replicates=20):
+    """``evaluate.bootstrap_sums`` (one kernel: hash, gather, add in registers) against ``stock_bootstrap_sums`` (what stock torch can
+    do) and ``evaluate.bootstrap_sums_host`` (the numpy twin, at ``host_replicates`` replicates: reported as measured, never
+    extrapolated), the legs in turn in one process, median [min, max] of ``rounds`` rounds, time and peak device bytes.  Default
+    shapes: MIND-small dev's 73 152 impressions x 4 and 8 columns x 1 000 and 10 000 replicates, and 4 096 units x 8 columns."""
+    import time
+    from digat_amd import evaluate
+    dev = torch.device("cuda:0")
+    shapes = [(units, columns, replicates)] if units else [(73152, 4, 1000), (73152, 4, 10000), (73152, 8, 1000), (73152, 8, 10000),
+                                                            (4096, 8, 1000), (4096, 8, 10000)]
+    stat = lambda v: (sorted(v)[len(v) // 2], min(v), max(v))
+
+    def peak(fn):
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        out = fn()
+        torch.cuda.synchronize()
+        return out, torch.cuda.max_memory_allocated() - base
+    print(f"bootstrap: sums [B, c] of B replicates of n draws from values [n, c] float64; ms per call, median [min, max] of {rounds} rounds", flush=True)
+    for n, c, B in shapes:
+        g = torch.Generator(device="cpu").manual_seed(0)
+        host = torch.rand(n, c, generator=g, dtype=torch.float64)
+        values = host.to(dev)
+        gd = torch.Generator(device=dev).manual_seed(0)
+        ours = lambda: evaluate.bootstrap_sums(values, B, seed=1)
+        stock = lambda: stock_bootstrap_sums(values, B, gd)
+        _lib._workspaces.clear()                        # the cached workspace of the shape before is no part of this call's peak
+        (got, pa), (other, pb) = peak(ours), peak(stock)
+        # the two legs draw differently: their replicate means agree as two samples of one distribution do
+        gm, om = got.mean(dim=0) / n, other.mean(dim=0) / n
+        gs = got.std(dim=0) / n
+        apart = float(((gm - om).abs() / (gs * (2.0 / B) ** 0.5)).max())
+        times = ([], [])
+        for _ in range(rounds):
+            for leg, fn in zip(times, (ours, stock)):
+                leg.append(timeit(fn, iters=3, warm=1)[0])
+        (a, alo, ahi), (b, blo, bhi) = (stat(t) for t in times)
+        hb = min(B, host_replicates)
+        secs = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            want = evaluate.bootstrap_sums_host(host.numpy(), hb, seed=1)
+            secs.append(time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        evaluate.bootstrap_draws_host(n, hb, seed=1)
+        draws_s = time.perf_counter() - t0
+        err = float((got[:hb].cpu() - torch.from_numpy(want)).abs().max())
+        ws = int(_lib.lib().digat_bootstrap_workspace_bytes(n, c, B))
+        print(f"  n = {n:6d}, c = {c:2d}, B = {B:6d}: bootstrap_sums {a:9.3f} ms [{alo:.3f}, {ahi:.3f}] ({n * B / a / 1e6:7.2f} G draws/s, workspace "
+              f"{ws / 2**20:.2f} MiB, peak {pa / 2**20:.2f} MiB) | randint + gather + sum {b:9.3f} ms [{blo:.3f}, {bhi:.3f}] (x{b / a:.2f}, peak "
+              f"{pb / 2**20:.1f} MiB) | numpy twin at B = {hb}: {1e3 * sorted(secs)[1]:9.1f} ms ({n * hb / sorted(secs)[1] / 1e6:.2f} M draws/s; the draws "
+              f"alone {1e3 * draws_s:.1f} ms) | largest |kernel - twin| {err:.2e}, legs' means apart by {apart:.2f} standard errors", flush=True)
+        del got, other, values
+        torch.cuda.empty_cache()
+
+
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "xattn"
     nums = [int(v) for v in sys.argv[2:]]
@@ -1547,6 +1625,8 @@ if __name__ == "__main__":
         bench_diversify(*nums)
     elif what == "list-quality":
         bench_list_quality(*nums)
+    elif what == "bootstrap":
+        bench_bootstrap(*nums)
     elif what == "linear":
         bench_linear(*nums)
     elif what == "gemm":
