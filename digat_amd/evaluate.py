@@ -764,7 +764,260 @@ def pool_softmax(users, news, target_pos, target_start, pool=None, skip=None, sc
     return loss, lse.detach(), score
 
 
-MMR_MAX_LIST = TOPK_MAX_K      # include/digat_hip.h: digat_mmr_select takes lists of at most this many entries
+LIST_SOFTMAX_MAX_D = 512      # include/digat_hip.h: DIGAT_LIST_SOFTMAX_MAX_D, the widest vectors digat_list_softmax_fwd / _bwd take
+
+
+def _list_softmax_host_args(scores, ids, count, teacher, rows_num):
+    """The element rule of ``digat_list_softmax_fwd`` in numpy: ``(S float64 [G,M], ids int64 [G,M], teacher float64 [G,M], elements
+    bool [G,M], mass bool [G,M])``."""
+    S = np.ascontiguousarray(scores, dtype=np.float64)
+    if S.ndim != 2:
+        raise ValueError("scores must be [G, M]")
+    G, M = S.shape
+    I = np.asarray(ids)
+    if I.shape != (G, M) or I.dtype.kind not in "iu":
+        raise ValueError(f"ids must be an integer array of shape {(G, M)}, got {I.shape} {I.dtype}")
+    I = I.astype(np.int64)
+    Tt = np.asarray(teacher, dtype=np.float64)
+    if Tt.shape != (G, M):
+        raise ValueError(f"teacher must have one value per slot {(G, M)}, got shape {Tt.shape}")
+    cnt = np.full(G, M, dtype=np.int64) if count is None else np.asarray(count).astype(np.int64)
+    if cnt.shape != (G,):
+        raise ValueError(f"count must have one entry per list ({G}), got shape {cnt.shape}")
+    elem = (np.arange(M)[None, :] < np.clip(cnt, 0, M)[:, None]) & (I >= 0) & (I < int(rows_num))
+    return S, I, Tt, elem, elem & np.isfinite(Tt)
+
+
+def _masked_lse_host(v, mask):
+    """log of the sum of exp(v) over ``mask`` per row, the maximum subtracted; -inf for a row without a True."""
+    w = np.where(mask, v, -np.inf)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        m = w.max(axis=1) if w.shape[1] else np.full(w.shape[0], -np.inf)
+        safe = np.where(np.isfinite(m), m, 0.0)
+        return safe + np.log(np.exp(w - safe[:, None]).sum(axis=1))
+
+
+def _list_softmax_host_parts(scores, ids, count, teacher, rows_num, scale, temperature):
+    if not float(temperature) > 0.0:
+        raise ValueError(f"temperature must be positive, got {temperature}")
+    S, I, Tt, elem, mass = _list_softmax_host_args(scores, ids, count, teacher, rows_num)
+    x = float(scale) * S
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        tau = np.where(mass, Tt, 0.0) / float(temperature)
+    lse_x, lse_t = _masked_lse_host(x, elem), _masked_lse_host(tau, mass)
+    valid = elem.any(axis=1) & mass.any(axis=1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        q = np.where(mass & valid[:, None], np.exp(np.where(mass, tau, 0.0) - np.where(valid, lse_t, 0.0)[:, None]), 0.0)
+        p = np.where(elem & valid[:, None], np.exp(np.where(elem, x, 0.0) - np.where(valid, lse_x, 0.0)[:, None]), 0.0)
+    return S, I, elem, mass, x, tau, lse_x, lse_t, valid, p, q
+
+
+def list_softmax_host(scores, ids, count, teacher, rows_num, scale=1.0, temperature=1.0):
+    """The contract of ``digat_list_softmax_fwd`` on given scores ``scores`` [G, M] (slot (g, j) holds the inner product of user g
+    with row ``ids[g, j]``), in numpy float64 — the yardstick of the kernel.  Slot (g, j) is an element when
+    ``j < clip(count[g], 0, M)`` (``count`` None: M) and ``0 <= ids[g, j] < rows_num``; a repeated id is two elements.  With
+    ``x = scale * scores`` and ``tau = teacher / temperature`` where the element's teacher value is finite (any other element has no
+    target mass): ``lse`` [G] = log-sum-exp of x over the elements (-inf without one), ``loss`` [G] = KL(softmax(tau) over the elements
+    with mass || softmax(x) over the elements) = ``lse_x - lse_tau + sum_j q_j (tau_j - x_j)``; ``valid`` [G] bool says where the list
+    has an element and an element with mass — loss is 0 elsewhere.  Returns ``(loss, lse, valid)``."""
+    S, I, elem, mass, x, tau, lse_x, lse_t, valid, p, q = _list_softmax_host_parts(scores, ids, count, teacher, rows_num, scale, temperature)
+    with np.errstate(invalid="ignore"):
+        cross = np.where(q > 0, q * (np.where(mass, tau, 0.0) - np.where(mass, x, 0.0)), 0.0).sum(axis=1)
+        loss = np.where(valid, np.where(valid, lse_x, 0.0) - np.where(valid, lse_t, 0.0) + cross, 0.0)
+    return loss, lse_x, valid
+
+
+def list_softmax_grad_host(users, rows, scores, ids, count, teacher, scale=1.0, temperature=1.0, grad_loss=None):
+    """The contract of ``digat_list_softmax_bwd`` in numpy float64: ``users`` [G, d], ``rows`` [P, d], ``scores`` [G, M] the scores the
+    loss was taken on, ``grad_loss`` [G] (None: ones).  With ``coef = grad_loss scale (p - q)`` on the elements of valid lists and 0
+    elsewhere: ``d_users[g] = sum_j coef[g, j] rows[ids[g, j]]`` and ``d_rows[p]`` = the sum of ``coef[g, j] users[g]`` over the
+    elements with ``ids[g, j] == p``.  Returns ``(d_users [G, d], d_rows [P, d])``."""
+    U, R = np.asarray(users, dtype=np.float64), np.asarray(rows, dtype=np.float64)
+    if U.ndim != 2 or R.ndim != 2 or U.shape[1] != R.shape[1]:
+        raise ValueError(f"users [G, d] and rows [P, d] must share d, got {U.shape} and {R.shape}")
+    S, I, elem, mass, x, tau, lse_x, lse_t, valid, p, q = _list_softmax_host_parts(scores, ids, count, teacher, R.shape[0], scale,
+                                                                                    temperature)
+    G = S.shape[0]
+    if U.shape[0] != G:
+        raise ValueError(f"users must have one row per list ({G}), got {U.shape}")
+    gl = np.ones(G) if grad_loss is None else np.asarray(grad_loss, dtype=np.float64)
+    if gl.shape != (G,):
+        raise ValueError("grad_loss must have one entry per list")
+    coef = np.where(elem & valid[:, None], gl[:, None] * float(scale) * (p - q), 0.0)
+    g_of, j_of = np.nonzero(elem)
+    d_users, d_rows = np.zeros_like(U), np.zeros_like(R)
+    np.add.at(d_users, g_of, coef[g_of, j_of][:, None] * R[I[g_of, j_of]])
+    np.add.at(d_rows, I[g_of, j_of], coef[g_of, j_of][:, None] * U[g_of])
+    return d_users, d_rows
+
+
+def list_softmax_keys_host(ids, count, rows_num):
+    """``entry_keys`` of ``digat_list_softmax_bwd`` in numpy: the sorted int64 values ``ids[g, j] * (G M) + (g M + j)`` of all elements."""
+    I = np.asarray(ids)
+    if I.ndim != 2:
+        raise ValueError("ids must be [G, M]")
+    G, M = I.shape
+    _, I, _, elem, _ = _list_softmax_host_args(np.zeros((G, M)), I, count, np.zeros((G, M)), rows_num)
+    flat = np.arange(G * M, dtype=np.int64).reshape(G, M)
+    return np.sort(I[elem] * np.int64(G * M) + flat[elem])
+
+
+def list_softmax_bound(lse, x_max, tau_max=0.0, loss=None):
+    """The error bound csrc/digat_list_softmax.inc derives against an exact evaluation on the same fp32 scores, with ``scale`` and
+    ``temperature`` the float32 numbers the entry receives: for ``lse`` (``loss`` None) ``u (max|x| + |lse|) + e64``, for ``loss``
+    ``u (max|x| min(2, sqrt(2 loss)) + |loss|) + 2 e64``, with u = 2^-24 and ``e64 = 2^-40 (1 + max|x| + max|tau|)``."""
+    u = 2.0 ** -24
+    e64 = 2.0 ** -40 * (1.0 + np.abs(x_max) + np.abs(tau_max))
+    if loss is None:
+        return u * (np.abs(x_max) + np.abs(lse)) + e64
+    return u * (np.abs(x_max) * np.minimum(2.0, np.sqrt(2.0 * np.abs(loss))) + np.abs(loss)) + 2.0 * e64
+
+
+def _check_list_softmax_args(users, rows, ids, count, teacher, temperature):
+    import torch
+    if users.dim() != 2 or rows.dim() != 2 or users.shape[1] != rows.shape[1] or users.shape[1] < 1:
+        raise ValueError(f"users [G, d] and rows [P, d] must share d >= 1, got {tuple(users.shape)} and {tuple(rows.shape)}")
+    G, d, P = int(users.shape[0]), int(users.shape[1]), int(rows.shape[0])
+    if d > LIST_SOFTMAX_MAX_D:
+        raise ValueError(f"list_softmax takes vectors of at most LIST_SOFTMAX_MAX_D = {LIST_SOFTMAX_MAX_D} channels, got {d}")
+    if ids.dim() != 2 or ids.shape[0] != G or ids.dtype in (torch.float16, torch.float32, torch.float64, torch.bool):
+        raise ValueError(f"ids must be an integer tensor [G = {G}, M], got {tuple(ids.shape)} {ids.dtype}")
+    M = int(ids.shape[1])
+    if not 1 <= M <= SHORTLIST_MAX_K:
+        raise ValueError(f"a list holds between 1 and SHORTLIST_MAX_K = {SHORTLIST_MAX_K} slots, got M = {M}")
+    if G * M >= 1 << 31:
+        raise ValueError(f"G x M must stay below 2^31, got {G} x {M}")
+    if tuple(teacher.shape) != (G, M) or not teacher.is_floating_point():
+        raise ValueError(f"teacher must be a floating-point tensor with one value per slot {(G, M)}, got {tuple(teacher.shape)} {teacher.dtype}")
+    if count is not None and (tuple(count.shape) != (G,) or count.dtype in (torch.float16, torch.float32, torch.float64, torch.bool)):
+        raise ValueError(f"count must be an integer tensor with one entry per list ({G}), got {tuple(count.shape)} {count.dtype}")
+    if not float(temperature) > 0.0 or float(temperature) == float("inf"):
+        raise ValueError(f"temperature must be a positive finite number, got {temperature}")
+    return G, P, M, d
+
+
+def list_elements(ids, count, rows_num: int):
+    """bool [G, M]: the slots of ``ids`` that are elements — ``j < clip(count[g], 0, M)`` and ``0 <= ids[g, j] < rows_num``."""
+    import torch
+    G, M = int(ids.shape[0]), int(ids.shape[1])
+    slot = torch.arange(M, device=ids.device)
+    inside = (ids >= 0) & (ids < int(rows_num))
+    if count is None:
+        return inside
+    return inside & (slot[None, :] < count.to(ids.device, torch.int64).clamp(0, M)[:, None])
+
+
+def _list_softmax_function():
+    import torch
+    from . import _lib
+
+    def head(u, v, ids, cnt, teacher, scale, temperature):
+        G, d = int(u.shape[0]), int(u.shape[1])
+        return (u.data_ptr(), v.data_ptr(), ids.data_ptr(), _lib.ptr(cnt), teacher.data_ptr(), G, int(v.shape[0]), int(ids.shape[1]), d,
+                float(scale), float(temperature))
+
+    class ListSoftmax(torch.autograd.Function):
+        """``digat_list_softmax_fwd`` / ``digat_list_softmax_bwd``; the sorted entry keys of the rows kernel are built here, in the
+        forward: the ids carry no gradient."""
+
+        @staticmethod
+        def forward(ctx, users, rows, ids, cnt, teacher, scale, temperature):
+            u, v = users.detach().float().contiguous(), rows.detach().float().contiguous()
+            G, M, P = int(u.shape[0]), int(ids.shape[1]), int(v.shape[0])
+            f = dict(dtype=torch.float32, device=u.device)
+            per_list, scores = torch.empty((2, G), **f), torch.empty((G, M), **f)
+            valid = torch.empty(G, dtype=torch.int32, device=u.device)
+            _lib.check(_lib.lib().digat_list_softmax_fwd(*head(u, v, ids, cnt, teacher, scale, temperature), per_list[0].data_ptr(),
+                                                         per_list[1].data_ptr(), valid.data_ptr(), scores.data_ptr(), _lib.stream_ptr()),
+                       "digat_list_softmax_fwd")
+            keys = None
+            if ctx.needs_input_grad[1]:
+                elem = list_elements(ids, cnt, P).view(-1)
+                flat = torch.arange(G * M, device=u.device)
+                keys = torch.sort(ids.view(-1)[elem] * (G * M) + flat[elem]).values.contiguous()
+            loss, lse = per_list[0], per_list[1]
+            ctx.save_for_backward(u, v, ids, teacher, lse, scores)
+            ctx.cnt, ctx.keys, ctx.scale, ctx.temperature, ctx.dtypes = cnt, keys, scale, temperature, (users.dtype, rows.dtype)
+            ctx.mark_non_differentiable(lse, scores)
+            return loss, lse, scores
+
+        @staticmethod
+        def backward(ctx, grad_loss, _lse, _scores):
+            u, v, ids, teacher, lse, scores = ctx.saved_tensors
+            G, d, P, M = int(u.shape[0]), int(u.shape[1]), int(v.shape[0]), int(ids.shape[1])
+            f = dict(dtype=torch.float32, device=u.device)
+            want_rows = ctx.needs_input_grad[1] and ctx.keys is not None
+            d_users = torch.empty((G, d), **f)
+            d_rows = torch.empty((P, d), **f) if want_rows else None
+            gl = grad_loss.float().contiguous()
+            L = _lib.lib()
+            need = int(L.digat_list_softmax_workspace_bytes(G, M))
+            ws = _lib.workspace(need, u.device, "list_softmax")
+            keys = ctx.keys if want_rows else None
+            _lib.check(L.digat_list_softmax_bwd(*head(u, v, ids, ctx.cnt, teacher, ctx.scale, ctx.temperature), lse.data_ptr(),
+                                                scores.data_ptr(), gl.data_ptr(), _lib.ptr(keys) if keys is not None and keys.numel() else None,
+                                                0 if keys is None else int(keys.numel()), d_users.data_ptr(), _lib.ptr(d_rows), ws.data_ptr(),
+                                                need, _lib.stream_ptr()), "digat_list_softmax_bwd")
+            return (d_users.to(ctx.dtypes[0]) if ctx.needs_input_grad[0] else None), (None if d_rows is None else d_rows.to(ctx.dtypes[1])), \
+                None, None, None, None, None
+
+    return ListSoftmax
+
+
+_ListSoftmax = None
+
+
+def list_softmax(users, rows, ids, count, teacher, scale=1.0, temperature=1.0):
+    """The softmax of every user's OWN list held against a target distribution given as scores: ``(loss [G], lse [G], scores [G, M])``.
+    ``users`` [G, d], ``rows`` [P, d], ``ids`` [G, M] integer rows of ``rows`` and ``count`` [G] (None: M) — what ``util.recommend`` /
+    ``nrms.shortlist`` return —, ``teacher`` [G, M].  Slot (g, j) is an element when ``j < clip(count[g], 0, M)`` and
+    ``0 <= ids[g, j] < P``; a repeated id is two elements.  With ``x = scale * <users[g], rows[ids[g, j]]>`` and
+    ``tau = teacher / temperature`` where the element's teacher value is finite (``-inf``, ``+inf`` and NaN mean "no target mass": the
+    ``-inf`` fill of ``recommend`` and a one-hot click target go through unchanged): ``lse`` = log-sum-exp of x over the elements (-inf
+    without one), ``loss`` = KL(softmax(tau) over the elements with mass || softmax(x) over the elements) — 0 for a list without an
+    element or without mass —, ``scores`` = the inner products at elements, NaN elsewhere.  ``loss`` is differentiable in ``users`` and
+    ``rows``; ``lse`` and ``scores`` are not, and ``teacher`` gets no gradient.  M <= ``SHORTLIST_MAX_K`` = 1024,
+    d <= ``LIST_SOFTMAX_MAX_D`` = 512, G M < 2^31.
+
+    On CUDA tensors: ``digat_list_softmax_fwd`` / ``_bwd`` under autograd — no [G, M, d] gather in memory, no float atomics: two calls
+    give the same bits in every output and gradient; float32 outputs, the score bits are ``dot_scores``'.  On CPU tensors: the stock
+    composition — ``index_select``, ``bmm``, ``log_softmax``, KL — in the dtype of ``users``, differentiable by autograd."""
+    import torch
+    global _ListSoftmax
+    cnt = None if count is None else torch.as_tensor(count)
+    G, P, M, d = _check_list_softmax_args(users, rows, ids, cnt, teacher, temperature)
+    dev = users.device
+    if any(t.device != dev for t in (rows, ids, teacher) + (() if cnt is None else (cnt,))):
+        raise ValueError("users, rows, ids, count and teacher must live on one device")
+    ids = ids.to(torch.int64).contiguous()
+    teacher = teacher.detach()
+    if dev.type == "cuda":
+        if _ListSoftmax is None:
+            _ListSoftmax = _list_softmax_function()
+        if G == 0 or P == 0:                                          # nothing is an element: no launch, a zero gradient
+            z = users.new_zeros(G, dtype=torch.float32) + 0.0 * (users.float().sum() + rows.float().sum())
+            return z, users.new_full((G,), float("-inf"), dtype=torch.float32), users.new_full((G, M), float("nan"), dtype=torch.float32)
+        return _ListSoftmax.apply(users, rows, ids, None if cnt is None else cnt.to(torch.int32).contiguous(),
+                                  teacher.float().contiguous(), float(scale), float(temperature))
+    elem = list_elements(ids, cnt, P)
+    mass = elem & torch.isfinite(teacher)
+    gathered = rows.index_select(0, torch.where(elem, ids, torch.zeros_like(ids)).view(-1)).view(G, M, d)        # [G, M, d]
+    S = torch.bmm(gathered, users.unsqueeze(2)).squeeze(2)
+    x = float(scale) * S
+    neg = float("-inf")
+    has, hm = elem.any(dim=1), mass.any(dim=1)
+    xm = torch.where(has[:, None], x.masked_fill(~elem, neg), torch.zeros_like(x))          # a row without an element never meets the softmax
+    tau = (torch.where(mass, teacher, torch.zeros_like(teacher)).to(x.dtype) / float(temperature)).masked_fill(~mass, neg)
+    tm = torch.where(hm[:, None], tau, torch.zeros_like(tau))
+    logp, logq = torch.log_softmax(xm, dim=1), torch.log_softmax(tm, dim=1)
+    keep = mass & (has & hm)[:, None]
+    zero = torch.zeros_like(x)
+    loss = (torch.where(keep, logq.exp(), zero) * (torch.where(keep, logq, zero) - torch.where(keep, logp, zero))).sum(dim=1)
+    lse = torch.where(has, torch.logsumexp(xm, dim=1), x.new_full((G,), neg)).detach()
+    return loss, lse, torch.where(elem, S.detach(), S.new_full((G, M), float("nan")))
+
+
+MMR_MAX_LIST = TOPK_MAX_K     # include/digat_hip.h: digat_mmr_select takes lists of at most this many entries
 
 
 def mmr_weights(lam):

@@ -813,6 +813,18 @@ def retrieval_step(model, train, users, pool=None, exclude_history=True, scale=1
     return loss.sum() / (~torch.isnan(score)).sum().clamp(min=1)
 
 
+def _retriever_optimizer(model, lr, optimizer=None):
+    """``optimizer``, or the one ``Trainer`` builds: Adam(``lr``) over ``trainer.parameter_groups``, ``optim.ClipAdam`` on the GPU."""
+    if optimizer is not None:
+        return optimizer
+    from .trainer import parameter_groups
+    groups = parameter_groups(model, 0.0)
+    if all(p.is_cuda and p.dtype == torch.float32 for g in groups for p in g["params"]):
+        from .optim import ClipAdam
+        return ClipAdam(groups, lr=lr)
+    return torch.optim.Adam(groups, lr=lr)
+
+
 def fit_retriever(model, train, steps, batch_users=64, pool_size=None, lr=1e-4, seed=0, exclude_history=True, scale=1.0, optimizer=None):
     """Train ``model`` for retrieval: ``steps`` times one ``retrieval_step`` on a seeded draw of ``batch_users`` impressions of
     ``train`` that have a click (without replacement inside a step; all of them when there are fewer), one backward and one
@@ -821,20 +833,13 @@ def fit_retriever(model, train, steps, batch_users=64, pool_size=None, lr=1e-4, 
     ``trainer.parameter_groups``, ``optim.ClipAdam`` on the GPU — and its state lives for this call only.  Returns the per-step
     losses as Python floats.  The draws depend on ``seed`` and the corpus alone, so CPU tensors see the same steps — through
     ``forward_stock`` and the stock composition."""
-    from .trainer import parameter_groups
     N = int(train.title_text.shape[0])
     clicked, _, _ = _clicked_targets(train, None)
     if len(clicked) == 0:
         raise ValueError("no impression of this corpus has a clicked row: nothing to train on")
     if N < 2:
         raise ValueError("the corpus holds no news but row 0")
-    if optimizer is None:
-        groups = parameter_groups(model, 0.0)
-        if all(p.is_cuda and p.dtype == torch.float32 for g in groups for p in g["params"]):
-            from .optim import ClipAdam
-            optimizer = ClipAdam(groups, lr=lr)
-        else:
-            optimizer = torch.optim.Adam(groups, lr=lr)
+    optimizer = _retriever_optimizer(model, lr, optimizer)
     rng = np.random.default_rng(seed)
     model.train()
     losses = []
@@ -851,6 +856,165 @@ def fit_retriever(model, train, steps, batch_users=64, pool_size=None, lr=1e-4, 
         optimizer.step()
         losses.append(float(loss.detach()))
     return losses
+
+
+# ---- listwise distillation: teach the first stage what the second stage ranks high ----------------------------------------------
+def _host_array(x):
+    return np.asarray(x.cpu() if torch.is_tensor(x) else x)
+
+
+def _check_lists(users, ids, teacher, count, rows):
+    """``(users [U] int64, ids [U,M] int64, teacher [U,M] float32, count [U] int64)`` as host arrays, checked."""
+    from . import evaluate
+    users, ids, teacher = _host_array(users), _host_array(ids), _host_array(teacher)
+    if users.ndim != 1 or users.dtype.kind not in "iu":
+        raise ValueError("users must be a 1-D integer array of impression indices")
+    if users.size and (int(users.min()) < 0 or int(users.max()) >= rows):
+        raise ValueError(f"impression indices must lie in [0, {rows})")
+    U = len(users)
+    if ids.ndim != 2 or ids.shape[0] != U or ids.dtype.kind not in "iu":
+        raise ValueError(f"ids must be an integer array [users = {U}, M], got {ids.shape} {ids.dtype}")
+    M = ids.shape[1]
+    if not 1 <= M <= evaluate.SHORTLIST_MAX_K:
+        raise ValueError(f"a list holds between 1 and SHORTLIST_MAX_K = {evaluate.SHORTLIST_MAX_K} slots, got M = {M}")
+    if teacher.shape != ids.shape or teacher.dtype.kind != "f":
+        raise ValueError(f"teacher must be a floating-point array with one value per slot {ids.shape}, got {teacher.shape} {teacher.dtype}")
+    count = np.full(U, M, dtype=np.int64) if count is None else _host_array(count)
+    if count.shape != (U,) or count.dtype.kind not in "iu":
+        raise ValueError(f"count must be an integer array with one entry per list ({U}), got {count.shape} {count.dtype}")
+    return users.astype(np.int64), ids.astype(np.int64), teacher.astype(np.float32), count.astype(np.int64)
+
+
+def distil_step(model, train, users, ids, teacher, count=None, scale=1.0, temperature=1.0):
+    """One listwise step's loss for the first stage, with its graph — ``retrieval_step``'s twin over per-user lists: for every user of
+    ``users`` (impression indices of ``train``) the KL divergence of ``softmax(teacher / temperature)`` from the model's
+    ``softmax(scale * <user, news>)`` over the user's OWN list ``ids[g, :count[g]]`` (``evaluate.list_softmax``), summed over the valid
+    lists — those with an element and an element whose teacher value is finite — and divided by their number (by 1 when there is
+    none).  ``ids`` [G, M], ``count`` [G] (None: M) and ``teacher`` [G, M] are what ``shortlist`` and ``util.score_lists`` return; an
+    id outside the corpus is no element, ``-inf`` (and ``+inf``, NaN) in ``teacher`` means no target mass.  The distinct ids of the
+    batch's lists form a compact pool whose titles go through ``model.news_encoder`` WITH gradients — the augmented titles too for
+    NRMS-SA — into a [P, d] table; histories go through ``model.user_encoder`` on their title texts; list ids are mapped to pool
+    positions.  The model's mode (dropout) is the caller's.  On CUDA tensors ``digat_list_softmax_fwd`` / ``_bwd`` on the HIP encoders;
+    on CPU tensors ``forward_stock`` and the stock composition."""
+    from . import evaluate
+    N = int(train.title_text.shape[0])
+    device = train.title_text.device
+    idx, ids, teacher, count = _check_lists(users, ids, teacher, count, int(train.history_ids.shape[0]))
+    M = ids.shape[1]
+    elem = (np.arange(M)[None, :] < np.clip(count, 0, M)[:, None]) & (ids >= 0) & (ids < N)
+    pl = np.unique(ids[elem])
+    where = np.full(N, -1, dtype=np.int64)
+    where[pl] = np.arange(len(pl), dtype=np.int64)
+    pos = np.where(elem, where[np.where(elem, ids, 0)], -1)
+    if len(pl) == 0:
+        pl = np.zeros(1, dtype=np.int64)                             # no list names a news: one row nobody points at keeps the graph
+    pool = torch.from_numpy(pl).to(device)
+    enc, ue = model.news_encoder, model.user_encoder
+    cuda = device.type == "cuda"
+    sa = isinstance(enc, SA_NRMS_NewsEncoder)
+    table = (enc if cuda else enc.forward_stock)(
+        train.title_text.index_select(0, pool)[None], train.title_mask.index_select(0, pool)[None],
+        train.augmented_title_text.index_select(0, pool)[None] if sa else None,
+        train.augmented_title_mask.index_select(0, pool)[None] if sa else None)[0]                      # [P, d]
+    at = torch.from_numpy(idx).to(device)
+    hist, mask = train.history_ids.index_select(0, at).to(torch.int64), train.history_mask.index_select(0, at)
+    user = (ue if cuda else ue.forward_stock)(train.title_text[hist], train.title_mask[hist], mask)    # [G, d]
+    tch = torch.from_numpy(teacher).to(device)
+    loss, _, _ = evaluate.list_softmax(user, table, torch.from_numpy(pos).to(device), torch.from_numpy(count.clip(0, M).astype(np.int32)).to(device),
+                                       tch if cuda else tch.to(user.dtype), scale=scale, temperature=temperature)
+    valid = int((elem & np.isfinite(teacher)).any(axis=1).sum())
+    return loss.sum() / max(valid, 1)
+
+
+def distil_retriever(model, train, lists, steps, batch_users=64, lr=1e-4, seed=0, scale=1.0, temperature=1.0, optimizer=None):
+    """Train ``model`` to keep in its shortlist what a teacher ranks high: ``steps`` times one ``distil_step`` on a seeded draw of
+    ``batch_users`` of the given lists (without replacement inside a step; all of them when there are fewer), one backward and one
+    optimizer step, in train mode.  ``lists = (users [U], ids [U, M], teacher [U, M], count [U] or None)`` is computed ONCE by the
+    caller — ``shortlist`` + ``util.score_lists`` for a DIGAT teacher, ``impression_lists`` for the listwise click loss — and not
+    refreshed here: recompute it between calls to follow the student's shortlist.  ``optimizer``: ``fit_retriever``'s choice.  Returns
+    the per-step losses as Python floats.  The draws depend on ``seed`` and the number of lists alone, so CPU tensors see the same
+    steps."""
+    if not (isinstance(lists, (tuple, list)) and len(lists) == 4):
+        raise ValueError("lists must be (users [U], ids [U, M], teacher [U, M], count [U] or None)")
+    users, ids, teacher, count = _check_lists(*lists[:3], lists[3], int(train.history_ids.shape[0]))
+    if len(users) == 0:
+        raise ValueError("no list to train on")
+    optimizer = _retriever_optimizer(model, lr, optimizer)
+    rng = np.random.default_rng(seed)
+    model.train()
+    losses = []
+    for _ in range(int(steps)):
+        b = np.sort(rng.choice(len(users), size=min(int(batch_users), len(users)), replace=False))
+        optimizer.zero_grad()
+        loss = distil_step(model, train, users[b], ids[b], teacher[b], count[b], scale=scale, temperature=temperature)
+        loss.backward()
+        optimizer.step()
+        losses.append(float(loss.detach()))
+    return losses
+
+
+def impression_lists(train, users=None):
+    """Every impression's own candidates as a training list: ``(users [U] int64, ids [U, M] int64, teacher [U, M] float32, count [U]
+    int32)``, numpy arrays — the rows of ``train`` (``row_impression``, ``row_candidate``, ``row_label``) in row order, M the longest
+    impression (at most ``evaluate.SHORTLIST_MAX_K``), slots beyond ``count`` holding id -1.  ``teacher`` is 0 at clicked rows and
+    ``-inf`` elsewhere: through ``distil_retriever`` this is the listwise click loss over whole impressions — with one click,
+    ``-log softmax`` of the clicked row over the impression's candidates.  ``users`` None: every impression with a clicked row."""
+    from . import evaluate
+    idx, _, _ = _clicked_targets(train, users)
+    cand = np.asarray(train.row_candidate, dtype=np.int64)
+    imp = np.asarray(train.row_impression, dtype=np.int64)
+    label = np.asarray(train.row_label)
+    I = int(train.history_ids.shape[0])
+    order = np.argsort(imp, kind="stable")
+    per = np.bincount(imp, minlength=I)
+    first = np.r_[0, np.cumsum(per)]
+    n = per[idx]
+    M = int(n.max()) if len(idx) else 1
+    if M > evaluate.SHORTLIST_MAX_K:
+        raise ValueError(f"an impression of this corpus has {M} candidates, a list holds at most SHORTLIST_MAX_K = {evaluate.SHORTLIST_MAX_K}")
+    M = max(M, 1)
+    ids = np.full((len(idx), M), -1, dtype=np.int64)
+    teacher = np.full((len(idx), M), -np.inf, dtype=np.float32)
+    slot = np.arange(M)[None, :] < n[:, None]
+    rows = order[(first[idx][:, None] + np.arange(M)[None, :])[slot]]
+    ids[slot] = cand[rows]
+    teacher[slot] = np.where(label[rows] == 1, 0.0, -np.inf).astype(np.float32)
+    return idx, ids, teacher, n.astype(np.int32)
+
+
+def teacher_agreement(student_ids, student_count, teacher_ids, teacher_count, ks=(10,)):
+    """How much of the teacher's top-k the student's list holds: per user the share of the first ``min(k, teacher_count[g])`` slots of
+    ``teacher_ids`` [G, kt] — a list ordered best first, as ``util.recommend`` returns it — whose id stands anywhere in
+    ``student_ids[g, :student_count[g]]`` (``evaluate.list_ranks``); 0 for a user whose teacher list is empty.  Returns
+    ``{"agreement@k": the mean over all users, ..., "per_user": [G, len(ks)] float64, "names": [...]}``; the ``per_user`` matrix goes
+    into ``evaluate.metric_intervals(per_user, names=names)`` unchanged for intervals over users."""
+    from . import evaluate
+    t_ids = torch.as_tensor(teacher_ids)
+    if t_ids.dim() != 2:
+        raise ValueError(f"teacher_ids must be [G, k], got {tuple(t_ids.shape)}")
+    G, kt = int(t_ids.shape[0]), int(t_ids.shape[1])
+    t_cnt = np.full(G, kt, dtype=np.int64) if teacher_count is None else _host_array(teacher_count).astype(np.int64)
+    if t_cnt.shape != (G,):
+        raise ValueError(f"teacher_count must have one entry per list ({G}), got shape {t_cnt.shape}")
+    s_ids = torch.as_tensor(student_ids)
+    if s_ids.dim() != 2 or int(s_ids.shape[0]) != G:
+        raise ValueError(f"student_ids must be [G = {G}, m], got {tuple(s_ids.shape)}")
+    t_host = t_ids.cpu().numpy().astype(np.int64)
+    per_user, names = np.zeros((G, len(ks)), dtype=np.float64), []
+    for c, k in enumerate(ks):
+        if int(k) != k or k < 1:
+            raise ValueError(f"every k must be a positive integer, got {k}")
+        n = np.clip(t_cnt, 0, min(int(k), kt))
+        start = np.r_[0, np.cumsum(n)].astype(np.int64)
+        take = np.arange(kt)[None, :] < n[:, None]
+        rank = evaluate.list_ranks(s_ids, student_count, t_host[take], start).cpu().numpy()
+        held = np.add.reduceat(np.r_[(rank >= 0).astype(np.float64), 0.0], start[:-1])[:G] if G else np.zeros(0)
+        held = np.where(n > 0, held, 0.0)                             # reduceat of an empty slice takes the next entry
+        per_user[:, c] = held / np.maximum(n, 1)
+        names.append(f"agreement@{int(k)}")
+    out = {name: float(per_user[:, c].mean()) if G else float("nan") for c, name in enumerate(names)}
+    out.update(per_user=per_user, names=names)
+    return out
 
 
 def candidates_csr(news_ids, count):

@@ -1122,7 +1122,52 @@ def recommend(model, dc: DeviceCorpus, users, candidates, k: int, exclude_histor
         raise ValueError("shortlist, category and max_per_category belong to a diversified call: name diversity (0.0: the cap alone)")
     hist, cat, graph, mask = recommend_users(dc, users)
     ids, start = recommend_candidates(candidates, int(hist.shape[0]), int(dc.news_embedding.shape[0]))
+    prepare, score = recommend_scoring(model, dc, hist, cat, graph, mask, batch_size)
+    return recommend_select(int(hist.shape[0]), k, ids.to(dc.news_embedding.device), start, hist if exclude_history else None,
+                            max_rows, score, prepare)
 
+
+def score_lists(model, dc: DeviceCorpus, users, ids, count=None, batch_size: int = 1024, max_rows: int = RECOMMEND_MAX_ROWS):
+    """The model's scores of given per-user lists IN PLACE: ``scores`` [G, M] float32 on the device, slot ``j`` of row g belonging to
+    ``ids[g, j]`` — ``-inf`` at or beyond ``count[g]`` (None: M) and for an id outside the corpus.  ``users`` as ``recommend`` takes
+    them; ``ids`` [G, M] and ``count`` [G] are what ``recommend`` / ``nrms.shortlist`` return.  Nothing is selected, so M goes up to
+    ``evaluate.SHORTLIST_MAX_K`` = 1024 where ``recommend`` stops at 128: a DIGAT (or ablation) teacher for an NRMS shortlist
+    (``nrms.distil_retriever``).  The scoring closure and the chunks of at most ``max_rows`` pairs are ``recommend``'s: a slot holds the
+    bits ``recommend`` returns for that id on the same per-user lists and ``max_rows``."""
+    hist, cat, graph, mask = recommend_users(dc, users)
+    G, N, dev = int(hist.shape[0]), int(dc.news_embedding.shape[0]), dc.news_embedding.device
+    ids = torch.as_tensor(np.asarray(ids) if not torch.is_tensor(ids) else ids)
+    if ids.dim() != 2 or int(ids.shape[0]) != G or ids.dtype in (torch.float16, torch.float32, torch.float64, torch.bool):
+        raise ValueError(f"ids must be an integer array [users = {G}, M], got {tuple(ids.shape)} {ids.dtype}")
+    M = int(ids.shape[1])
+    if not 1 <= M <= evaluate.SHORTLIST_MAX_K:
+        raise ValueError(f"a list holds between 1 and SHORTLIST_MAX_K = {evaluate.SHORTLIST_MAX_K} slots, got M = {M}")
+    ids = ids.to(dev, torch.int64)
+    if count is not None:
+        count = torch.as_tensor(np.asarray(count) if not torch.is_tensor(count) else count).to(dev)
+        if tuple(count.shape) != (G,):
+            raise ValueError(f"count must have one entry per list ({G}), got shape {tuple(count.shape)}")
+    elem = evaluate.list_elements(ids, count, N)
+    start = np.concatenate([[0], np.cumsum(elem.sum(dim=1).cpu().numpy())]).astype(np.int64)
+    flat = torch.nonzero(elem.view(-1)).view(-1)                     # row-major: user-major, slots ascending
+    pairs = ids.view(-1).index_select(0, flat)
+    out = torch.full((G * M,), float("-inf"), dtype=torch.float32, device=dev)
+    prepare, score = recommend_scoring(model, dc, hist, cat, graph, mask, batch_size)
+    chunks = recommend_user_chunks(G, int(pairs.shape[0]), start, int(max_rows))
+    prepare()
+    for g0, g1 in chunks:
+        row_user, row_cand, _ = recommend_rows(g0, g1, pairs, start)
+        if int(row_user.shape[0]) == 0:
+            continue
+        out[flat[int(start[g0]):int(start[g1])]] = score(g0, g1, row_user, row_cand).to(dev, torch.float32)
+    return out.view(G, M)
+
+
+def recommend_scoring(model, dc: DeviceCorpus, hist, cat, graph, mask, batch_size: int):
+    """``(prepare, score)`` of ``recommend_select`` for the model's own scores of the users ``recommend_users`` returned: ``prepare()``
+    puts the model in eval mode and refreshes the per-news tables; ``score(g0, g1, row_user, row_cand)`` is ``score_rows`` on a view
+    of ``dc`` with the users' tensors and the user-major pairs in place of the corpus's impressions and rows.  ``recommend`` and
+    ``score_lists`` both run on it."""
     def prepare():
         if hasattr(model, "eval"):
             model.eval()
@@ -1137,8 +1182,7 @@ def recommend(model, dc: DeviceCorpus, users, candidates, k: int, exclude_histor
                       "weights_key", "xattn_hint", "range_overflow_at_prepare"):
                 setattr(dc, f, getattr(view, f))
         return scores
-    return recommend_select(int(hist.shape[0]), k, ids.to(dc.news_embedding.device), start, hist if exclude_history else None,
-                            max_rows, score, prepare)
+    return prepare, score
 
 
 def all_gather_scores(local: torch.Tensor, counts: List[int], group=None) -> torch.Tensor:

@@ -711,6 +711,40 @@ int digat_pool_softmax_bwd(const float* users, const float* news, const int64_t*
                            const float* lse, const float* grad_loss, float* d_users, float* d_rows, void* workspace, size_t workspace_bytes,
                            void* stream);
 
+/* ---- listwise distillation: softmax over a user's own list held against a target distribution (digat_amd.evaluate.list_softmax) ---
+ * users [G, d] f32, rows [P, d] f32, ids [G, M] int64, count [G] int32 (NULL: M), teacher [G, M] f32, scale, temperature > 0.  Slot
+ * (g, j) is an element when j < clamp(count[g], 0, M) and 0 <= ids[g, j] < P; a repeated id in one list is two elements.  score(g, j) is
+ * the fp32 fmaf chain over the d channels (the bits digat_dot_scores stores), x = scale * score.  tau = teacher / temperature where the
+ * slot is an element and teacher is finite; an element whose teacher is -inf, +inf or NaN has target mass 0.  q = softmax(tau) over the
+ * elements with mass, p = softmax(x) over all elements.
+ * Forward: out_lse [G] = log of the sum of exp(x) over g's elements (-inf without one; the maximum is always subtracted); out_loss [G] =
+ * KL(q || p) = lse_x - lse_tau + sum_j q_j (tau_j - x_j), and out_valid [G] = 1 — loss 0 and valid 0 for a list without an element or
+ * without an element with mass; out_scores [G, M] = the score bits at elements, a NaN elsewhere.  Every output byte is written whatever
+ * count holds.  The reductions run in fp64 and are rounded once; a list's outputs depend on that list alone.
+ * Backward, given the forward's lse [G] and scores [G, M] and grad_loss [G]: coef(g, j) = grad_loss[g] scale (p_j - q_j) on elements of
+ * valid lists, exactly 0 elsewhere (written to the workspace),
+ *   d_users [G, d] = sum_j coef(g, j) rows[ids[g, j], :]      d_rows [P, d] = sum over the elements with ids[g, j] == p of coef(g, j) users[g, :]
+ * in ascending (g, j).  entry_keys [E] int64 is the CALLER's: the values ids[g, j] (G M) + (g M + j) of all E elements, sorted ascending
+ * (they are distinct: any correct sort gives the same array) — the rows kernel looks its row's entries up in it and never follows a key
+ * outside that row's range.  d_rows == NULL skips that launch and needs no keys.  Every byte of d_users and of a given d_rows is written,
+ * zeros included.  No floating-point atomics: two calls give the same bits.
+ * DIGAT_ERR_ARG: a null required pointer (count; d_rows; entry_keys without d_rows or with E == 0 may be NULL), G < 0, P < 0,
+ * temperature not a positive finite number, E outside [0, G M], a workspace that is not 4-byte aligned; DIGAT_ERR_SHAPE: M outside
+ * [1, DIGAT_SHORTLIST_MAX_K], d outside [1, DIGAT_LIST_SOFTMAX_MAX_D], G M >= 2^31, P > 2^31; DIGAT_ERR_WORKSPACE: a short workspace —
+ * all before any launch.  G == 0 launches nothing forward.  Workspace (backward only; it may hold anything on entry): 4 G M bytes
+ * rounded up to 256; 0 for a negative argument.
+ * Stream-ordered: one launch forward (one workgroup per list), two backward; no allocation, no host synchronisation, no read of device
+ * memory on the host. */
+#define DIGAT_LIST_SOFTMAX_MAX_D 512
+size_t digat_list_softmax_workspace_bytes(int64_t lists, int m);
+int digat_list_softmax_fwd(const float* users, const float* rows, const int64_t* ids, const int32_t* count, const float* teacher, int64_t G,
+                           int64_t P, int M, int d, float scale, float temperature, float* out_loss, float* out_lse, int32_t* out_valid,
+                           float* out_scores, void* stream);
+int digat_list_softmax_bwd(const float* users, const float* rows, const int64_t* ids, const int32_t* count, const float* teacher, int64_t G,
+                           int64_t P, int M, int d, float scale, float temperature, const float* lse, const float* scores,
+                           const float* grad_loss, const int64_t* entry_keys, int64_t E, float* d_users, float* d_rows, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
 /* ---- diversified top-k: greedy maximal-marginal-relevance selection over a short list (digat_amd.evaluate.mmr_select) ---------
  * Per user g a list: ids [G, M] int64, scores [G, M] f32, count [G] int32 (the entries in use, held inside [0, M]; NULL: M) — the
  * triple digat_topk_segments and digat_dot_topk write.  vectors [N, d] f32, rows taken as they are (callers pass unit rows).

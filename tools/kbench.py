@@ -48,6 +48,13 @@
                                              rows, one and five targets per user, forward and forward + backward, the legs in turn,
                                              median [min, max] of five rounds, time and peak device bytes; then nrms.fit_retriever on
                                              the planted-signal corpus: nrms.retrieval_metrics before and after
+  python tools/kbench.py list-softmax [d]    listwise distillation: evaluate.list_softmax (fused per-user list softmax, no [G, M, d] gather)
+                                             against the stock composition — index_select, torch.bmm, log_softmax, KL, autograd —,
+                                             G = 64 and 4 096 lists of M = 128 and 1 024 over a compact pool, d = 400, forward and
+                                             forward + backward, the legs in turn, median [min, max] of five rounds, time and peak
+                                             device bytes; then nrms.distil_retriever on the planted-signal corpus with the trained
+                                             DIGAT as the teacher: teacher_agreement@10 and recall@k of the held-out clicks before
+                                             and after, with intervals
   python tools/kbench.py diversify [news_num d]   diversified top-k: evaluate.mmr_select (one launch, the Gram in LDS) against gather +
                                              torch.bmm + k rounds of torch element-wise ops and arg-max, G = 64 and 4 096 lists of
                                              M = 128, d = 400, k = 10 and 100, with and without a cap of 2 per category, the legs in
@@ -1340,6 +1347,150 @@ def bench_pool_softmax(news_num=65238, d=400, rounds=5):
           + report(nrms.retrieval_metrics(m, held), nrms.retrieval_loss(m, held)), flush=True)
 
 
+def stock_list_softmax(users, rows, ids, count, teacher, scale=1.0, temperature=1.0):
+    """The summed loss of ``evaluate.list_softmax`` from stock PyTorch: ``index_select`` into [G, M, d], ``torch.bmm``, ``log_softmax``
+    over the slots below ``count``, ``F.kl_div`` against ``softmax(teacher / temperature)``.  Every id is a row and every teacher value
+    finite in the benchmark's data."""
+    G, M = ids.shape
+    x = scale * torch.bmm(rows.index_select(0, ids.reshape(-1)).view(G, M, -1), users.unsqueeze(2)).squeeze(2)
+    out = torch.arange(M, device=ids.device)[None, :] >= count[:, None]
+    logp = torch.log_softmax(x.masked_fill(out, float("-inf")), dim=1)
+    logq = torch.log_softmax((teacher / temperature).masked_fill(out, float("-inf")), dim=1)
+    return torch.nn.functional.kl_div(logp.masked_fill(out, 0.0), logq.masked_fill(out, 0.0), reduction="sum", log_target=True)
+
+
+def bench_list_softmax(d=400, rounds=5, demo=1):
+    """``evaluate.list_softmax`` (the fused per-user list softmax and its gradients: no [G, M, d] gather, no float atomics) against
+    ``stock_list_softmax`` under autograd, in one process, the legs taken in turn, median [min, max] of ``rounds`` rounds of three
+    calls, and each leg's peak of device bytes beyond its inputs; forward alone (``no_grad``) and forward + backward.  The pool is
+    compact: the distinct ids of the batch's lists, drawn from min(65 237, G M / 4) rows.  Then (``demo``) the demonstration run:
+    ``nrms.distil_retriever`` on the planted-signal corpus, the trained DIGAT (tests/golden/trained_planted_state.npz) teaching an
+    NRMS at d = 64 on its own shortlists of 256."""
+    from digat_amd import evaluate
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device="cpu").manual_seed(0)
+    stat = lambda v: (sorted(v)[len(v) // 2], min(v), max(v))
+
+    def peak(fn):
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        out = fn()
+        torch.cuda.synchronize()
+        out = float(out)
+        return out, torch.cuda.max_memory_allocated() - base
+    print(f"list-softmax: d = {d}, compact pool, temperature 2; ms per call, median [min, max] of {rounds} rounds", flush=True)
+    for G in (64, 4096):
+        for M in (128, 1024):
+            P = max(M, min(65237, G * M // 4))
+            rows = (torch.randn(P, d, generator=g) / d ** 0.5).to(dev)
+            users = (3.0 * torch.randn(G, d, generator=g)).to(dev)
+            ids = torch.stack([torch.randperm(P, generator=g)[:M] for _ in range(G)]).to(dev)       # no id twice in a list, many times across lists
+            count = torch.randint(M // 2, M + 1, (G,), generator=g).to(torch.int32).to(dev)
+            teacher = (3.0 * torch.randn(G, M, generator=g)).to(dev)
+
+            def fused_fwd():
+                with torch.no_grad():
+                    return evaluate.list_softmax(users, rows, ids, count, teacher, temperature=2.0)[0].sum()
+
+            def stock_fwd():
+                with torch.no_grad():
+                    return stock_list_softmax(users, rows, ids, count, teacher, temperature=2.0)
+
+            def both(fn):
+                def run():
+                    u, t = users.detach().requires_grad_(True), rows.detach().requires_grad_(True)
+                    loss = fn(u, t)
+                    loss.backward()
+                    return loss.detach() + 0.0 * (u.grad[0, 0] + t.grad[0, 0])
+                return run
+            fused_both = both(lambda u, t: evaluate.list_softmax(u, t, ids, count, teacher, temperature=2.0)[0].sum())
+            stock_both = both(lambda u, t: stock_list_softmax(u, t, ids, count, teacher, temperature=2.0))
+            legs = (fused_fwd, stock_fwd, fused_both, stock_both)
+            peaks = [peak(fn) for fn in legs]
+            times = [[] for _ in legs]
+            for _ in range(rounds):
+                for leg, fn in zip(times, legs):
+                    leg.append(timeit(fn, iters=3, warm=1)[0])
+            (a, alo, ahi), (b, blo, bhi), (c, clo, chi), (e, elo, ehi) = (stat(t) for t in times)
+            print(f"  G = {G:5d}, M = {M:4d}, P = {P:5d}: forward: list_softmax {a:8.3f} ms [{alo:.3f}, {ahi:.3f}] (peak {peaks[0][1] / 2**20:.2f} "
+                  f"MiB) | stock {b:8.3f} ms [{blo:.3f}, {bhi:.3f}] (x{b / a:.2f}, peak {peaks[1][1] / 2**20:.1f} MiB) || forward + backward: "
+                  f"list_softmax {c:8.3f} ms [{clo:.3f}, {chi:.3f}] (gather {8.0 * G * M * d / c / 1e6:6.1f} GB/s, peak {peaks[2][1] / 2**20:.1f} "
+                  f"MiB) | stock {e:8.3f} ms [{elo:.3f}, {ehi:.3f}] (x{e / c:.2f}, peak {peaks[3][1] / 2**20:.1f} MiB) | "
+                  f"summed loss {peaks[0][0]:.3f} vs stock {peaks[1][0]:.3f}", flush=True)
+            del rows, users, ids, count, teacher
+            torch.cuda.empty_cache()
+    if demo:
+        demo_distil()
+
+
+def demo_distil(train_users=2048, held_users=1024, m=256, steps=300, temperature=2.0, replicates=2000):
+    """The demonstration run of listwise distillation: on the planted-signal corpus the trained DIGAT
+    (tests/golden/trained_planted_state.npz) teaches an NRMS at d = 64 with random titles.  The lists are the student's own
+    ``nrms.shortlist`` (m = 256) of ``train_users`` training impressions, scored once by ``util.score_lists``.  Reported, before and
+    after ``nrms.distil_retriever``, on ``held_users`` held-out impressions: ``nrms.teacher_agreement`` @10 of the student's shortlist
+    with the teacher's top 10 over the whole catalogue (``util.recommend``), and ``nrms.retrieval_metrics``' recall@k of the held-out
+    clicks, each with ``evaluate.metric_intervals`` / ``rank_metrics_intervals``."""
+    import time
+    import types
+    from digat_amd import evaluate, nrms, synthetic, util
+    from digat_amd.model import Model, PrecomputedNewsEncoder
+    dev = torch.device("cuda:0")
+    golden = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
+    state = {k: v for k, v in np.load(os.path.join(golden, "trained_planted_state.npz")).items()}
+    depth = int(np.load(os.path.join(golden, "devset_trained_2k.npz"))["depth"])
+    corpus = synthetic.make_corpus(synthetic.SynthSpec(**synthetic.PLANTED_SPEC))
+    spec = corpus.spec
+    N, H, Lw, V = spec.news_num, spec.max_history_num, 16, 4000
+    text, mask = synthetic.make_titles(N, Lw, V, seed=2)
+    cfg = types.SimpleNamespace(news_encoder="MSA", graph_encoder="DIGAT", news_graph_size=spec.news_graph_size, max_history_num=H,
+                                category_num=spec.category_num, graph_depth=depth, dropout_rate=0.2)
+    digat = Model(cfg, news_encoder=PrecomputedNewsEncoder(torch.from_numpy(corpus.news_embedding)))
+    digat.graph_encoder.load_state_dict({k: torch.from_numpy(v) for k, v in state.items()})
+    digat = digat.to(dev).eval()
+
+    def part(lo, hi):
+        c = synthetic.slice_impressions(corpus, lo, hi)
+        hist = torch.from_numpy(c.history.astype(np.int64)).to(dev)
+        ns = types.SimpleNamespace(title_text=torch.from_numpy(text).to(dev), title_mask=torch.from_numpy(mask).to(dev),
+                                   augmented_title_text=None, augmented_title_mask=None, history_ids=hist, history_mask=hist != 0,
+                                   row_candidate=c.row_candidate.astype(np.int64), row_impression=c.row_impression, row_label=c.row_label)
+        return ns, util.DeviceCorpus.from_numpy(c, dev)
+    (held, dc_held), (train, dc_train) = part(0, synthetic.PLANTED_DEV_IMPRESSIONS), part(synthetic.PLANTED_DEV_IMPRESSIONS, spec.impressions)
+    student = _nrms_model("NRMS", V=V, dm=64, h=8, dk=8, att=32, Lw=Lw, H=H, dropout=0.2)
+    hu = np.arange(held_users, dtype=np.int64)
+    pool = np.arange(1, N, dtype=np.int64)
+    t_ids, _, t_count = util.recommend(digat, dc_held, hu, pool, 10)
+
+    def report(tag):
+        s_ids, _, s_count = nrms.shortlist(student, held, hu, m=m)
+        agree = nrms.teacher_agreement(s_ids, s_count, t_ids, t_count, ks=(10,))
+        iv = evaluate.metric_intervals(agree["per_user"], names=agree["names"], replicates=replicates)
+        r = nrms.retrieval_metrics(student, held, users=hu, ks=(10, 100, m), intervals=replicates)
+        fmt = lambda f: f"{f['value']:.4f} [{f['lo']:.4f}, {f['hi']:.4f}]" if isinstance(f, dict) and "lo" in f else str(f)
+        print(f"  {tag}: teacher_agreement@10 of the shortlist of {m}: {fmt(iv['agreement@10'])}; held-out clicks: "
+              + ", ".join(f"recall@{k} {fmt(r['intervals'][f'recall@{k}'])}" for k in (10, 100, m))
+              + f", median rank {r['median_rank']:.0f} ({r['targets']} targets)", flush=True)
+        return agree["agreement@10"]
+    print(f"distillation demo: planted-signal corpus, {N - 1} news; teacher: the trained DIGAT; student: NRMS at d = 64, random titles; "
+          f"{held_users} held-out users, 95 % intervals from {replicates} replicates over users", flush=True)
+    report("before")
+    tu = np.arange(train_users, dtype=np.int64)
+    t0 = time.perf_counter()
+    ids, _, count = nrms.shortlist(student, train, tu, m=m)
+    teacher = util.score_lists(digat, dc_train, tu, ids, count)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    losses = nrms.distil_retriever(student, train, (tu, ids, teacher, count), steps, batch_users=64, lr=1e-3, seed=0, temperature=temperature)
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    print(f"  lists: nrms.shortlist + util.score_lists for {train_users} users x {m}: {t1 - t0:.1f} s; nrms.distil_retriever: {steps} steps of "
+          f"64 lists, lr 1e-3, temperature {temperature}: {t2 - t1:.1f} s ({1e3 * (t2 - t1) / steps:.1f} ms per step), mean KL "
+          f"{np.mean(losses[:10]):.4f} (first ten steps) -> {np.mean(losses[-10:]):.4f} (last ten)", flush=True)
+    report("after")
+
+
 def torch_mmr(ids, scores, count, vectors, k, lam, category=None, q=0):
     """Greedy maximal-marginal relevance built only from stock PyTorch: gather, ``torch.bmm``, then k rounds of element-wise ops and
     arg-max over all lists at once.  Every id is taken to lie in the table; NaN scores and the order among tied values are not the
@@ -1621,6 +1772,8 @@ if __name__ == "__main__":
         bench_dot_rank(*nums)
     elif what == "pool-softmax":
         bench_pool_softmax(*nums)
+    elif what == "list-softmax":
+        bench_list_softmax(*nums)
     elif what == "diversify":
         bench_diversify(*nums)
     elif what == "list-quality":
