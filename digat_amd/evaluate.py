@@ -1148,6 +1148,210 @@ def mmr_gram_stock(ids, vectors):
     return torch.bmm(rows, rows.transpose(1, 2))
 
 
+# ---- calibrated top-k: lists that keep the reader's own category mix ----------------------------------------------------------------
+CAL_MAX_LIST = SHORTLIST_MAX_K     # include/digat_hip.h: DIGAT_CALIBRATE_MAX_LIST, the longest list digat_calibrated_select takes
+CAL_MAX_CATEGORIES = 64            # ... DIGAT_CALIBRATE_MAX_CATEGORIES, the widest target
+CAL_ROBUST_ULPS = 8                # a robust step's winner leads by this many float32 ulps (calibrated_select_host)
+
+
+def _check_alpha(alpha) -> float:
+    if not 0.0 < float(alpha) < 1.0:                                # a NaN fails both comparisons
+        raise ValueError(f"alpha must lie in (0, 1), got {alpha}")
+    return float(alpha)
+
+
+def _check_calibrate_args(ids_shape, scores_shape, count_shape, category_shape, target_shape, k):
+    if len(ids_shape) != 2 or tuple(scores_shape) != tuple(ids_shape) or not 1 <= ids_shape[1] <= CAL_MAX_LIST:
+        raise ValueError(f"ids and scores must both be [G, M] with 1 <= M <= {CAL_MAX_LIST}, got {tuple(ids_shape)} and {tuple(scores_shape)}")
+    if count_shape is not None and tuple(count_shape) != (ids_shape[0],):
+        raise ValueError(f"count must have one entry per list ({ids_shape[0]}), got shape {tuple(count_shape)}")
+    if not 1 <= int(k) <= TOPK_MAX_K:
+        raise ValueError(f"k must be in [1, {TOPK_MAX_K}], got {k}")
+    if category_shape is None or len(category_shape) != 1:
+        raise ValueError(f"category must be [N], one entry per news, got {None if category_shape is None else tuple(category_shape)}")
+    if len(target_shape) != 2 or target_shape[0] != ids_shape[0] or not 1 <= target_shape[1] <= CAL_MAX_CATEGORIES:
+        raise ValueError(f"target must be [G, C] = [{ids_shape[0]}, 1 <= C <= {CAL_MAX_CATEGORIES}], got {tuple(target_shape)}")
+
+
+def calibrated_select_host(ids, scores, count, category, target, k: int, lam, alpha=0.01, return_robust: bool = False):
+    """The contract of ``digat_calibrated_select`` in numpy — the yardstick of the kernel.  ``ids`` / ``scores`` [G, M <= 1024],
+    ``count`` [G] or None (M): position p is an element when ``p < clip(count[g], 0, M)`` and ``0 <= id < N = len(category)``
+    (``mmr_select_host``'s rule; a repeated id is one element per position).  ``target`` [G, C <= 64] float32: ``p_c =
+    float64(target[g, c])`` where that is finite and > 0, else 0 — nothing is normalised.  An element whose ``category[id]`` lies
+    outside [0, C) is uncategorised: its gain is 0 and it is never counted.
+
+    Greedy, steps t = 0 .. k-1 with T = t + 1 and ``n_c`` the picked elements of category c: in float64, every operation rounded,
+    ``q_c(n) = ((1 - alpha) n) / T + alpha p_c`` and ``gain64_c = p_c (log q_c(n_c + 1) - log q_c(n_c))`` (0 where ``p_c = 0``);
+    ``gain32_c = float32(gain64_c)``; ``value = float32(lam) * s + float32(mu) * gain32[cat]`` with both products and the sum
+    rounded (``mmr_weights``); the winner is the unpicked element with the largest ``topk_keys(value)``, ties to the lowest
+    position; selection stops when no element is left.  That is the greedy step of ``lam sum(s) - mu KL(p || q)`` with the term all
+    candidates share dropped.  Returns ``(scores [G,k] float32 — the INPUT score bits —, ids [G,k] int64, count [G] int32, kl [G]
+    float32)``: slots at or beyond ``count`` hold ``-inf`` / ``-1``; ``kl = float32(sum over p_c > 0 of p_c (log p_c - log
+    q_c(n_c)))`` at ``T = max(count, 1)``, summed in float64.  ``lam = 1`` and an all-zero target row give the plain top-k.
+
+    ``return_robust``: a fifth array [G] bool.  A list is robust when at every step the winner's value leads every other unpicked
+    element's by at least ``CAL_ROBUST_ULPS`` = 8 float32 ulps of the largest of ``|value|``, ``|lam s|`` and ``|mu gain|`` of the
+    two — or the two are a true tie: equal scores and the same gain inputs (the same ``p_c`` bits and ``n_c``, or both
+    gain-free), or one of the two scores is not finite (then neither value depends on a gain).  Two correct float64 logarithms
+    may differ by one float32 step in ``gain32``, about 2 ulps of a value: on a robust list every such implementation picks
+    the same elements."""
+    idv = np.asarray(ids, dtype=np.int64)
+    sc = np.ascontiguousarray(scores, dtype=np.float32)
+    cat = None if category is None else np.asarray(category, dtype=np.int64)
+    tgt = np.asarray(target, dtype=np.float32)
+    _check_calibrate_args(idv.shape, sc.shape, None if count is None else np.shape(count), None if cat is None else cat.shape, tgt.shape, k)
+    lam32, mu32 = mmr_weights(lam)
+    alpha = np.float64(_check_alpha(alpha))
+    oma = np.float64(1.0) - alpha
+    (G, M), C, N, k = idv.shape, tgt.shape[1], len(cat), int(k)
+    cnt = np.full(G, M, dtype=np.int64) if count is None else np.clip(np.asarray(count, dtype=np.int64), 0, M)
+    out_s = np.full((G, k), -np.inf, dtype=np.float32)
+    out_i = np.full((G, k), -1, dtype=np.int64)
+    out_c = np.zeros(G, dtype=np.int32)
+    out_kl = np.zeros(G, dtype=np.float32)
+    robust = np.ones(G, dtype=bool)
+    pos = np.arange(M)
+    zero = np.float32(0)
+    for g in range(G):
+        elem = (pos < cnt[g]) & (idv[g] >= 0) & (idv[g] < N)
+        cg = cat[np.where(elem, idv[g], 0)] if elem.any() else np.zeros(M, dtype=np.int64)
+        cated = elem & (cg >= 0) & (cg < C)
+        ci = np.where(cated, cg, 0)
+        pbits = np.where(np.isfinite(tgt[g]) & (tgt[g] > 0), tgt[g], zero).astype(np.float32)
+        p = pbits.astype(np.float64)
+        live = p > 0
+        pl, apl = p[live], alpha * p[live]
+        free = ~(cated & live[ci])                                  # elements no gain reaches
+        n = np.zeros(C, dtype=np.int64)
+        chosen = np.zeros(M, dtype=bool)
+        with np.errstate(invalid="ignore", over="ignore"):
+            rel = (lam32 * sc[g]).astype(np.float32)
+        t_end = 0
+        for t in range(k):
+            ok = elem & ~chosen
+            if not ok.any():
+                break
+            T = np.float64(t + 1)
+            gain64 = np.zeros(C, dtype=np.float64)
+            nl = n[live].astype(np.float64)
+            gain64[live] = pl * (np.log((oma * (nl + 1.0)) / T + apl) - np.log((oma * nl) / T + apl))
+            with np.errstate(invalid="ignore", over="ignore"):
+                mg = (mu32 * gain64.astype(np.float32)).astype(np.float32)
+                red = np.where(cated, mg[ci], zero)
+                value = (rel + red).astype(np.float32)
+            keys = np.where(ok, topk_keys(value).astype(np.int64), -1)
+            j = int(np.argmax(keys))                                # the first (lowest position) of the largest key
+            if return_robust and robust[g]:
+                others = ok.copy()
+                others[j] = False
+                with np.errstate(invalid="ignore", over="ignore"):
+                    mag = np.maximum(np.maximum(np.abs(value), np.abs(rel)), np.abs(red))
+                    ulp = np.spacing(np.maximum(mag, mag[j]).astype(np.float32)).astype(np.float64)
+                    lead = np.float64(value[j]) - value.astype(np.float64)
+                    fixed = ~np.isfinite(rel) | ~np.isfinite(rel[j])
+                    same_gain = (free & free[j]) | (~free & ~free[j] & (pbits[ci].view(np.uint32) == pbits[ci[j]].view(np.uint32))
+                                                    & (n[ci] == n[ci[j]]))
+                    tie = (sc[g] == sc[g, j]) & same_gain
+                    if np.any(others & ~fixed & ~tie & ~(lead >= CAL_ROBUST_ULPS * ulp)):
+                        robust[g] = False
+            chosen[j] = True
+            out_s[g, t], out_i[g, t] = sc[g, j], idv[g, j]
+            t_end = t + 1
+            if cated[j]:
+                n[cg[j]] += 1
+        out_c[g] = t_end
+        if live.any():
+            q = (oma * n[live].astype(np.float64)) / np.float64(max(t_end, 1)) + apl
+            out_kl[g] = np.float32(np.sum(pl * (np.log(pl) - np.log(q))))
+    return (out_s, out_i, out_c, out_kl, robust) if return_robust else (out_s, out_i, out_c, out_kl)
+
+
+def calibrated_select(ids, scores, count, category, target, k: int, lam, alpha=0.01):
+    """Calibrated top-k on the GPU (``digat_calibrated_select``): per user, k greedy picks from a shortlist that weigh an entry's
+    score against what it does for the KL divergence between ``target`` — the category mix the list should have, e.g.
+    ``category_share`` of the user's history — and the list's own mix.
+
+    ``ids`` [G, M <= 1024] int64, ``scores`` [G, M] float32 and ``count`` [G] int32 (None: M) are device tensors — what
+    ``shortlist_segments``, ``dot_shortlist``, ``topk_segments`` and both ``recommend``s return; ``category`` [N] int, ``target``
+    [G, C <= 64] float32; ``lam`` in [0, 1] (1: the plain order by score), ``alpha`` in (0, 1) smooths the list's mix towards the
+    target.  The contract is ``calibrated_select_host``'s, exactly.  Returns ``(scores [G,k] float32, ids [G,k] int64, count [G]
+    int32, kl [G] float32)`` on the device — the picked entries' input scores and the divergence of the finished list; slots at
+    or beyond ``count`` hold ``-inf`` / ``-1``.  Stream-ordered: one launch, nothing is read back."""
+    import torch
+    from . import _lib
+    given = [t for t in (ids, scores, count, category, target) if t is not None]
+    dev = _lib.require_device(*given)
+    _check_calibrate_args(tuple(ids.shape), tuple(scores.shape), None if count is None else tuple(count.shape),
+                          None if category is None else tuple(category.shape), tuple(target.shape), k)
+    lam32, mu32 = mmr_weights(lam)
+    alpha = _check_alpha(alpha)
+    idt = ids.to(torch.int64).contiguous()
+    sc = _lib.f32(scores.detach())
+    ct = None if count is None else count.to(torch.int32).contiguous()
+    cat = category.to(torch.int32).contiguous()
+    tg = _lib.f32(target.detach())
+    G, M, C, k = int(idt.shape[0]), int(idt.shape[1]), int(tg.shape[1]), int(k)
+    out_s = torch.empty((G, k), dtype=torch.float32, device=dev)
+    out_i = torch.empty((G, k), dtype=torch.int64, device=dev)
+    out_c = torch.empty((G,), dtype=torch.int32, device=dev)
+    out_kl = torch.empty((G,), dtype=torch.float32, device=dev)
+    if G == 0:
+        return out_s, out_i, out_c, out_kl
+    L = _lib.lib()
+    need = int(L.digat_calibrated_select_workspace_bytes(G, M, C, k))
+    ws = _lib.workspace(need, dev, "calibrate")
+    dummy = ws if int(cat.shape[0]) == 0 else cat                    # an empty tensor has no storage to point at
+    _lib.check(L.digat_calibrated_select(idt.data_ptr(), sc.data_ptr(), _lib.ptr(ct), G, M, dummy.data_ptr(), int(cat.shape[0]),
+                                         tg.data_ptr(), C, float(lam32), float(mu32), alpha, k, out_i.data_ptr(), out_s.data_ptr(),
+                                         out_c.data_ptr(), out_kl.data_ptr(), ws.data_ptr(), need, _lib.stream_ptr()),
+               "digat_calibrated_select")
+    return out_s, out_i, out_c, out_kl
+
+
+def _check_share_args(history_shape, category_shape, C):
+    if len(history_shape) != 2:
+        raise ValueError(f"history must be [G, H], got shape {tuple(history_shape)}")
+    if len(category_shape) != 1:
+        raise ValueError(f"category must be [N], got shape {tuple(category_shape)}")
+    if not 1 <= int(C) <= CAL_MAX_CATEGORIES:
+        raise ValueError(f"C must be in [1, {CAL_MAX_CATEGORIES}], got {C}")
+
+
+def category_share_host(history, category, C: int, pad_id: int = 0) -> np.ndarray:
+    """``category_share`` in numpy: [G, C] float32."""
+    hist = np.asarray(history, dtype=np.int64)
+    cat = np.asarray(category, dtype=np.int64)
+    _check_share_args(hist.shape, cat.shape, C)
+    G, C = hist.shape[0], int(C)
+    inside = (hist != pad_id) & (hist >= 0) & (hist < len(cat))
+    c = cat[np.where(inside, hist, 0)] if inside.any() else np.zeros_like(hist)
+    ok = inside & (c >= 0) & (c < C)
+    counts = np.zeros((G, C), dtype=np.int64)
+    np.add.at(counts, (np.nonzero(ok)[0], c[ok]), 1)
+    total = counts.sum(axis=1, keepdims=True)
+    return np.where(total > 0, counts.astype(np.float32) / np.maximum(total, 1).astype(np.float32), np.float32(0)).astype(np.float32)
+
+
+def category_share(history, category, C: int, pad_id: int = 0):
+    """The category mix of every user's history, the usual ``target`` of ``calibrated_select``: row g of the result [G, C] float32
+    is the share of each category among the slots of ``history`` [G, H] (news ids) whose id is not ``pad_id``, lies in [0, N) and
+    whose ``category`` [N] lies in [0, C).  Integer counts (``scatter_add``: exact), then one float32 division; a history without
+    such a slot gives a zero row — the plain top-k for that user.  Stock PyTorch on the tensors' device: not a hot path."""
+    import torch
+    _check_share_args(tuple(history.shape), tuple(category.shape), C)
+    hist = history.to(torch.int64)
+    cat = category.to(hist.device, torch.int64)
+    G, C, N = int(hist.shape[0]), int(C), int(cat.shape[0])
+    inside = (hist != pad_id) & (hist >= 0) & (hist < N)
+    c = cat[torch.where(inside, hist, torch.zeros_like(hist))] if N else torch.zeros_like(hist)
+    ok = inside & (c >= 0) & (c < C)
+    counts = torch.zeros((G, C), dtype=torch.int64, device=hist.device)
+    counts.scatter_add_(1, torch.where(ok, c, torch.zeros_like(c)), ok.to(torch.int64))
+    total = counts.sum(dim=1, keepdim=True)
+    share = counts.to(torch.float32) / torch.clamp(total, min=1).to(torch.float32)
+    return torch.where(total > 0, share, torch.zeros_like(share))
+
+
 # ---- list quality: what finished lists look like ----------------------------------------------------------------------------------
 def _check_list_quality_args(ids_shape, count_shape, category_shape, base_shape, base_count_shape):
     if len(ids_shape) != 2 or not 1 <= ids_shape[1] <= MMR_MAX_LIST:

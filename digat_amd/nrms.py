@@ -511,7 +511,7 @@ def user_vectors(model, dev, users, batch_size=1024):
 
 
 def recommend(model, dev, users, candidates=None, k=10, exclude_history=True, batch_size=1024, diversity=None, shortlist=None, category=None,
-              max_per_category=0):
+              max_per_category=0, calibration=None, calibration_target=None, alpha=0.01):
     """For every user, which k news, in order: ``(news_ids [G,k] int64, scores [G,k] float32, count [G] int32)`` on the model's
     device.  Order: score descending, equal scores in candidate order; slots at or beyond ``count[g]`` hold id -1 and score -inf.
 
@@ -524,8 +524,26 @@ def recommend(model, dev, users, candidates=None, k=10, exclude_history=True, ba
 
     ``diversity`` in [0, 1] (None: off, the call above and nothing else): retrieval runs at ``k' = shortlist or min(128, 4 k)`` and
     ``util.diversify`` cuts every list to k by greedy maximal-marginal relevance with ``lam = 1 - diversity`` over the plain news
-    cache; ``max_per_category`` q >= 1 lets at most q news of one ``category`` [N] (None: ``dev.news_category``) into a list."""
+    cache; ``max_per_category`` q >= 1 lets at most q news of one ``category`` [N] (None: ``dev.news_category``) into a list.
+
+    ``calibration`` in [0, 1] (None: off): retrieval runs at ``k' = shortlist or min(1024, 8 k)`` (``shortlist``'s kernels beyond
+    128) and ``util.calibrate`` cuts every list to k with ``lam = 1 - calibration`` towards the category mix of the user's history
+    (``evaluate.category_share`` under ``category``, None: ``dev.news_category``; at most 64 categories) or towards
+    ``calibration_target`` [G, C]; ``alpha`` smooths the list's mix.  ``util.recommend`` has the details; ``calibration`` and
+    ``diversity`` do not combine."""
     from . import evaluate, util
+    if calibration is not None:
+        if diversity is not None or max_per_category:
+            raise ValueError("calibration does not combine with diversity or max_per_category: name one of them")
+        select = lambda wide, long_lists: _retrieve(model, dev, users, candidates, wide, exclude_history, batch_size, long_lists)
+
+        def history():
+            hist, mask = _histories(dev, users)
+            return torch.where(mask != 0, hist, torch.zeros_like(hist))
+        return util.shortlist_then_calibrate(select, history, k, calibration, shortlist, category, getattr(dev, "news_category", None),
+                                             calibration_target, alpha)[1][:3]
+    if calibration_target is not None:
+        raise ValueError("calibration_target belongs to a calibrated call: name calibration")
     if diversity is not None:
         select = lambda wide: recommend(model, dev, users, candidates, wide, exclude_history, batch_size)
         plain = lambda: news_caches(model, dev.title_text, dev.title_mask, dev.augmented_title_text, dev.augmented_title_mask, 4 * batch_size)[0]

@@ -1018,6 +1018,87 @@ def shortlist_then_diversify(select: Callable, vectors: Callable, k, diversities
     return short, [diversify(*short, vec, kk, lam, category, max_per_category) for kk, _, lam in limits]
 
 
+def calibrate_limits(k, calibration, shortlist) -> Tuple[int, int, float]:
+    """``(k, k', lam)`` of a calibrated ``recommend``: the plain selection runs at ``k' = shortlist or min(1024, 8 k)``, and
+    ``calibrate`` cuts its lists to k with ``lam = 1 - calibration``."""
+    if not 1 <= int(k) <= evaluate.TOPK_MAX_K:
+        raise ValueError(f"k must be in [1, {evaluate.TOPK_MAX_K}], got {k}")
+    if not 0.0 <= float(calibration) <= 1.0:
+        raise ValueError(f"calibration must lie in [0, 1], got {calibration}")
+    k = int(k)
+    wide = min(evaluate.CAL_MAX_LIST, 8 * k) if not shortlist else int(shortlist)
+    if not k <= wide <= evaluate.CAL_MAX_LIST:
+        raise ValueError(f"shortlist must lie in [k, {evaluate.CAL_MAX_LIST}] = [{k}, {evaluate.CAL_MAX_LIST}], got {shortlist}")
+    return k, wide, 1.0 - float(calibration)
+
+
+def _tensor_on(x, dev) -> torch.Tensor:
+    t = torch.as_tensor(np.asarray(x) if not torch.is_tensor(x) else x)
+    return t if dev is None else t.to(dev)
+
+
+def calibrate(ids: torch.Tensor, scores: torch.Tensor, count: torch.Tensor, category, target, k: int, lam: float, alpha: float = 0.01):
+    """The last stage of a calibrated ``recommend``: the lists ``(ids [G,M <= 1024], scores [G,M], count [G])`` of the plain selection
+    cut to k by the greedy calibrated re-rank towards ``target`` [G, C <= 64] under ``category`` [N] —
+    ``evaluate.calibrated_select`` on device tensors, ``evaluate.calibrated_select_host`` on CPU tensors, as ``diversify`` does.
+    Returns ``recommend``'s triple and the divergence of every finished list: ``(news_ids [G,k], scores [G,k], count [G], kl [G])``."""
+    if category is None:
+        raise ValueError("calibrate needs category, one entry per news")
+    cat = _tensor_on(category, ids.device)
+    tgt = _tensor_on(target, ids.device).to(torch.float32)
+    if ids.is_cuda:
+        s, i, c, kl = evaluate.calibrated_select(ids, scores, count, cat, tgt, k, lam, alpha)
+        return i, s, c, kl
+    s, i, c, kl = evaluate.calibrated_select_host(ids.numpy(), scores.numpy(), None if count is None else count.numpy(), cat.numpy(),
+                                                  tgt.numpy(), k, lam, alpha)
+    return torch.from_numpy(i), torch.from_numpy(s), torch.from_numpy(c), torch.from_numpy(kl)
+
+
+def calibration_kl(ids: torch.Tensor, count, category, target, alpha: float = 0.01) -> torch.Tensor:
+    """``kl`` [G] float32 of given lists ``ids`` [G, M <= 128] (``count`` [G] or None: M) against ``target`` [G, C]: the smoothed KL
+    divergence ``calibrate`` reports, for any list — a plain top-k, a diversified one.  It is ``calibrate`` at ``lam = 1`` and
+    ``k = M``, which picks every element."""
+    M = int(ids.shape[1]) if ids.dim() == 2 else 0
+    if not 1 <= M <= evaluate.TOPK_MAX_K:
+        raise ValueError(f"ids must be [G, M] with 1 <= M <= {evaluate.TOPK_MAX_K}, got {tuple(ids.shape)}")
+    return calibrate(ids, torch.zeros(tuple(ids.shape), dtype=torch.float32, device=ids.device), count, category, target, M, 1.0, alpha)[3]
+
+
+def calibration_category(category, corpus_category) -> Tuple[torch.Tensor, int]:
+    """``(category [N] int32, C)`` of a calibrated ``recommend``: ``category``, else the corpus's own, where it is; ``C = max + 1``."""
+    if category is None:
+        category = corpus_category
+    if category is None:
+        raise ValueError("calibration needs category: this corpus carries no news_category")
+    cat = _tensor_on(category, None).to(torch.int32)
+    if cat.dim() != 1:
+        raise ValueError(f"category must be [N], one entry per news, got shape {tuple(cat.shape)}")
+    C = max(1, int(cat.max()) + 1) if cat.numel() else 1
+    if C > evaluate.CAL_MAX_CATEGORIES:
+        raise ValueError(f"calibration takes at most {evaluate.CAL_MAX_CATEGORIES} categories, category names {C}")
+    return cat, C
+
+
+def shortlist_then_calibrate(select: Callable, history: Callable, k, calibration, shortlist=None, category=None, corpus_category=None,
+                             calibration_target=None, alpha: float = 0.01):
+    """The step behind ``recommend(calibration=)`` of either model: ``select(k', long_lists)`` — the plain selection at
+    ``calibrate_limits``' width, ``long_lists`` when ``k' > 128`` — then ``calibrate`` towards ``calibration_target`` or, without
+    one, ``evaluate.category_share`` of ``history()`` [G, H] (news ids, padded with 0) under ``calibration_category``.  Returns
+    ``(shortlist triple, (news_ids, scores, count, kl))``."""
+    k, wide, lam = calibrate_limits(k, calibration, shortlist)
+    evaluate._check_alpha(alpha)
+    cat, C = calibration_category(category, corpus_category)        # refused before anything is scored
+    short = select(wide, wide > evaluate.TOPK_MAX_K)
+    cat = cat.to(short[0].device)
+    if calibration_target is None:
+        target = evaluate.category_share(history().to(short[0].device), cat, C)
+    else:
+        target = _tensor_on(calibration_target, short[0].device).to(torch.float32)
+        if target.dim() != 2 or int(target.shape[0]) != int(short[0].shape[0]):
+            raise ValueError(f"calibration_target must be [users = {int(short[0].shape[0])}, C], got {tuple(target.shape)}")
+    return short, calibrate(*short, cat, target, k, lam, alpha)
+
+
 def measure_lists(ids, count, vectors, category=None, base_ids=None, base_count=None, exposure=None):
     """``evaluate.list_quality`` on device lists; on CPU tensors the Gram of stock PyTorch (``evaluate.mmr_gram_stock``) and
     ``evaluate.list_quality_host``, as ``diversify`` does.  ``exposure`` [N] int32 is updated in place either way.  Returns the
@@ -1093,7 +1174,7 @@ def recommend_report(model, dc: DeviceCorpus, users, candidates, k: int, diversi
 
 def recommend(model, dc: DeviceCorpus, users, candidates, k: int, exclude_history: bool = True, batch_size: int = 1024,
               max_rows: int = RECOMMEND_MAX_ROWS, diversity: Optional[float] = None, shortlist: Optional[int] = None, category=None,
-              max_per_category: int = 0):
+              max_per_category: int = 0, calibration: Optional[float] = None, calibration_target=None, alpha: float = 0.01):
     """For every user, which k news of its candidates, in order: ``(news_ids [G,k] int64, scores [G,k] float32, count [G] int32)``
     on the device.  Order: score descending, equal scores in candidate order (the rank file's order); ``count[g]`` is the number of
     valid slots of row g, the slots behind it hold id -1 and score -inf.
@@ -1113,18 +1194,43 @@ def recommend(model, dc: DeviceCorpus, users, candidates, k: int, exclude_histor
     min(128, 4 k)`` and ``diversify`` cuts every list to k by greedy maximal-marginal relevance with ``lam = 1 - diversity`` over
     ``unit_rows(dc.news_embedding)``: a pick's score is weighed against its largest cosine to what the user already got.
     ``max_per_category`` q >= 1 lets at most q news of one ``category`` [news_num] (None: ``dc.news_category``) into a list.  The
-    scores returned are still the model's."""
+    scores returned are still the model's.
+
+    ``calibration`` in [0, 1] (None: off) makes the list keep the reader's own category mix: the selection above runs at ``k' =
+    shortlist or min(1024, 8 k)`` — calibration needs a deep pool, a user's rarer categories sit far down the list — and
+    ``calibrate`` cuts every list to k with ``lam = 1 - calibration``, each pick weighing its score against what it does for the KL
+    divergence between the target mix and the list's.  The target is ``evaluate.category_share`` of the users' histories under
+    ``category`` (None: ``dc.news_category``; at most 64 categories), or ``calibration_target`` [G, C] as given; ``alpha`` smooths
+    the list's mix.  A user with an empty history gets the plain top-k.  As for ``diversity``, ``lam`` weighs raw model scores
+    against a gain of order 1: the useful range of the knob depends on the scale of the scores.  ``calibration`` and ``diversity``
+    do not combine."""
+    if calibration is not None:
+        if diversity is not None or max_per_category:
+            raise ValueError("calibration does not combine with diversity or max_per_category: name one of them")
+        plain = lambda wide, long_lists: recommend_lists(model, dc, users, candidates, wide, exclude_history, batch_size, max_rows, long_lists)
+        return shortlist_then_calibrate(plain, lambda: recommend_users(dc, users)[0], k, calibration, shortlist, category, dc.news_category,
+                                        calibration_target, alpha)[1][:3]
+    if calibration_target is not None:
+        raise ValueError("calibration_target belongs to a calibrated call: name calibration")
     if diversity is not None:
         select = lambda wide: recommend(model, dc, users, candidates, wide, exclude_history, batch_size, max_rows)
         return shortlist_then_diversify(select, lambda: unit_rows(dc.news_embedding), k, (diversity,), shortlist, category, max_per_category,
                                         dc.news_category)[1][0]
     if shortlist is not None or category is not None or max_per_category:
         raise ValueError("shortlist, category and max_per_category belong to a diversified call: name diversity (0.0: the cap alone)")
+    return recommend_lists(model, dc, users, candidates, k, exclude_history, batch_size, max_rows, False)
+
+
+def recommend_lists(model, dc: DeviceCorpus, users, candidates, k: int, exclude_history: bool = True, batch_size: int = 1024,
+                    max_rows: int = RECOMMEND_MAX_ROWS, long_lists: bool = True):
+    """``recommend`` without a re-rank — the same triple, order and fill; with ``long_lists`` for k up to
+    ``evaluate.SHORTLIST_MAX_K`` = 1024 (``recommend_select``: ``evaluate.shortlist_segments``), the deep shortlist a calibrated
+    re-rank picks from; for ``k <= 128`` the lists are ``recommend``'s, bit for bit."""
     hist, cat, graph, mask = recommend_users(dc, users)
     ids, start = recommend_candidates(candidates, int(hist.shape[0]), int(dc.news_embedding.shape[0]))
     prepare, score = recommend_scoring(model, dc, hist, cat, graph, mask, batch_size)
     return recommend_select(int(hist.shape[0]), k, ids.to(dc.news_embedding.device), start, hist if exclude_history else None,
-                            max_rows, score, prepare)
+                            max_rows, score, prepare, long_lists=long_lists)
 
 
 def score_lists(model, dc: DeviceCorpus, users, ids, count=None, batch_size: int = 1024, max_rows: int = RECOMMEND_MAX_ROWS):

@@ -799,6 +799,36 @@ int digat_list_quality(const int64_t* ids, const int32_t* count, int64_t G, int 
                        int32_t* out_elements, double* out_sim_sum, float* out_sim_max, int32_t* out_categories, int32_t* out_category_max,
                        int32_t* out_overlap, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- calibrated top-k: greedy history-proportional category re-rank of a shortlist (digat_amd.evaluate.calibrated_select) ------
+ * Per list g: ids [G, M] int64, scores [G, M] f32, count [G] int32 (NULL: M) — what digat_shortlist_segments / digat_dot_shortlist
+ * write, 1 <= M <= DIGAT_CALIBRATE_MAX_LIST; category [N] int32; target [G, C] f32, 1 <= C <= DIGAT_CALIBRATE_MAX_CATEGORIES.
+ * Position p is an ELEMENT when p < clamp(count[g], 0, M) and 0 <= ids[g][p] < N (digat_mmr_select's rule; a repeated id is one
+ * element per position; no read leaves the arrays).  An element whose category[id] lies outside [0, C) is uncategorised: its gain
+ * is 0 and it is never counted.  p_c = (double)target[g][c] where that is finite and > 0, else 0; nothing is normalised.
+ * Selection, t = 0 .. k-1, T = t + 1, n_c = the picked elements of category c: in float64, every operation rounded,
+ *   q~_c(n) = ((1 - alpha) n) / T + alpha p_c,   gain64_c = p_c (log q~_c(n_c + 1) - log q~_c(n_c))   (0 where p_c = 0),
+ * gain32_c = (float)gain64_c; an element's value = lam * score + mu * gain32[category] in fp32, both products and the sum rounded
+ * (never an fma); the winner is the unpicked element with the largest value in digat_topk_segments' order (NaNs last,
+ * -0.0 == +0.0), ties to the lowest position.  Selection stops when no element is left.  This is the greedy step of
+ * lam sum(score) - mu KL(p || q~) with the term common to all candidates dropped.
+ * out_count [G] = the elements picked; slots t < count of out_ids / out_scores [G, k] hold the t-th winner's id and its INPUT score
+ * bits, slots t >= count hold -1 and -inf; out_kl [G] = (float) sum over c with p_c > 0 of p_c (log p_c - log q~_c(n_c)) at
+ * T = max(count, 1), summed in float64 in an order fixed by C alone.  Every output byte is written.  The logarithm is the device
+ * library's float64 log: against another correctly implemented log a gain32 may differ by one fp32 step.
+ * lam = 1 (mu = 0) and an all-zero target row give the plain top-k of the list, bit for bit.
+ * DIGAT_ERR_ARG: a null ids / scores / category / target / out pointer, G < 0, N < 0, lam outside [0, 1], alpha outside (0, 1)
+ * (NaNs included); DIGAT_ERR_SHAPE: k outside [1, 128], M outside [1, 1024], C outside [1, 64], G >= 2^31 — all before any launch.
+ * G == 0 returns DIGAT_OK without a launch.  Stream-ordered: one launch on `stream`, one workgroup per list (one wave for
+ * M <= 128, four beyond), the list in registers; no atomics: the same bits from run to run and in any batch; no allocation, no host synchronisation, no
+ * read of device memory on the host.  The workspace is not used (digat_calibrated_select_workspace_bytes returns 0; workspace may
+ * be NULL). */
+#define DIGAT_CALIBRATE_MAX_LIST 1024
+#define DIGAT_CALIBRATE_MAX_CATEGORIES 64
+size_t digat_calibrated_select_workspace_bytes(int64_t lists, int m, int c, int k);
+int digat_calibrated_select(const int64_t* ids, const float* scores, const int32_t* count, int64_t G, int M, const int32_t* category,
+                            int64_t N, const float* target, int C, float lam, float mu, double alpha, int k, int64_t* out_ids,
+                            float* out_scores, int32_t* out_count, float* out_kl, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- bootstrap resampling of per-unit metric rows (digat_amd.evaluate.bootstrap_sums / metric_intervals / compare_metrics) -----
  * values [n, c] float64 row-major: one row per resampling unit (an impression, a user), one column per summed quantity;
  * sums [B, c] float64.  Replicate r = first_replicate + b makes n draws with replacement; draw j has the 64-bit counter

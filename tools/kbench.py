@@ -60,6 +60,12 @@
                                              M = 128, d = 400, k = 10 and 100, with and without a cap of 2 per category, the legs in
                                              turn, median [min, max] of five rounds; then util.recommend for 64 users at k = 10 with
                                              and without diversity=0.3
+  python tools/kbench.py calibrate [rounds demo]   calibrated top-k: evaluate.calibrated_select (one launch, a list in registers) against a
+                                             gather of the categories + k rounds of torch element-wise ops with torch.log in float64 and
+                                             arg-max, G = 64 and 4 096 lists of M = 128 and 1 024, k = 10 and 100, C = 17, the legs in
+                                             turn, median [min, max] of five rounds, time and peak device bytes; then recommend(calibration=)
+                                             in {0, 0.3, 0.5, 0.8} on 512 held-out impressions of the planted-signal corpus: kl,
+                                             category_max_share, recall@10 and MRR with intervals, paired against calibration 0
   python tools/kbench.py list-quality [news_num d]   list quality: evaluate.list_quality (one launch, the Gram in LDS) against the same
                                              figures from gather + torch.bmm, the upper triangle's sum and max, a sort for the
                                              categories, a broadcast compare for the overlap and torch.bincount for the exposure,
@@ -1589,6 +1595,149 @@ def bench_diversify(news_num=65238, d=400, rounds=5):
           flush=True)
 
 
+def torch_calibrate(ids, scores, count, category, target, k, lam, alpha=0.01):
+    """The calibrated re-rank built only from stock PyTorch — what the tree offered before ``digat_calibrated_select``: a gather of
+    the categories, then k rounds of element-wise operations with ``torch.log`` in float64, a gather of the gains and arg-max over
+    all lists at once.  Every id is taken to lie in the table and every category in [0, C); NaN scores and the order among tied
+    values are not the contract's (a yardstick for speed)."""
+    G, M = ids.shape
+    dev = ids.device
+    cat = category[ids].to(torch.int64)
+    p = target.to(torch.float64)
+    live = p > 0
+    one = torch.ones((), dtype=torch.float64, device=dev)
+    elem = torch.arange(M, device=dev)[None, :] < count[:, None]
+    chosen = torch.zeros((G, M), dtype=torch.bool, device=dev)
+    n = torch.zeros_like(p)
+    out_i = torch.full((G, k), -1, dtype=torch.int64, device=dev)
+    out_s = torch.full((G, k), float("-inf"), device=dev)
+    cnt = torch.zeros(G, dtype=torch.int32, device=dev)
+    ar = torch.arange(G, device=dev)
+    neg = torch.full((), float("-inf"), device=dev)
+    rel = lam * scores
+    for t in range(k):
+        q0 = torch.where(live, (1.0 - alpha) * n / (t + 1.0) + alpha * p, one)
+        q1 = torch.where(live, (1.0 - alpha) * (n + 1.0) / (t + 1.0) + alpha * p, one)
+        gain = ((1.0 - lam) * (p * (torch.log(q1) - torch.log(q0))).to(torch.float32))
+        ok = elem & ~chosen
+        value = torch.where(ok, rel + gain.gather(1, cat), neg)
+        j = value.argmax(dim=1)
+        hit = ok[ar, j]
+        out_i[:, t] = torch.where(hit, ids[ar, j], out_i[:, t])
+        out_s[:, t] = torch.where(hit, scores[ar, j], out_s[:, t])
+        chosen[ar, j] |= hit
+        n[ar, cat[ar, j]] += hit.to(torch.float64)
+        cnt += hit.to(torch.int32)
+    q = torch.where(live, (1.0 - alpha) * n / torch.clamp(cnt, min=1).to(torch.float64)[:, None] + alpha * p, one)
+    kl = torch.where(live, p * (torch.log(torch.where(live, p, one)) - torch.log(q)), torch.zeros_like(p)).sum(dim=1).to(torch.float32)
+    return out_s, out_i, cnt, kl
+
+
+def bench_calibrate(rounds=5, demo=1):
+    """``evaluate.calibrated_select`` against ``torch_calibrate``, the two legs in turn in one process, median [min, max] of
+    ``rounds`` rounds and each leg's peak of device bytes beyond its inputs: G in {64, 4 096} lists of M in {128, 1 024} ids,
+    k in {10, 100}, C = 17 categories, targets from a Dirichlet draw, lam = 0.5.  Then (``demo``) the effect on the planted-signal
+    corpus (``demo_calibrate``)."""
+    from digat_amd import evaluate
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device="cpu").manual_seed(0)
+    news_num, C = 65238, 17
+    category = torch.randint(0, C, (news_num,), generator=g, dtype=torch.int32).to(dev)
+    conc = torch.distributions.Dirichlet(torch.full((C,), 0.7))
+
+    def peak(fn):
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        out = fn()
+        torch.cuda.synchronize()
+        return out, torch.cuda.max_memory_allocated() - base
+    print(f"calibrate: lists of ids of {news_num} news in C = {C} categories, lam = 0.5, alpha = 0.01; ms per call, median [min, max] of "
+          f"{rounds} rounds", flush=True)
+    for G in (64, 4096):
+        torch.manual_seed(G)
+        target = conc.sample((G,)).to(torch.float32).to(dev)
+        for M in (128, 1024):
+            ids = torch.randint(0, news_num, (G, M), generator=g).to(dev)
+            scores = torch.randn(G, M, generator=g).sort(dim=1, descending=True).values.to(dev)      # a shortlist comes sorted
+            count = torch.full((G,), M, dtype=torch.int32, device=dev)
+            for k in (10, 100):
+                ours = lambda: evaluate.calibrated_select(ids, scores, count, category, target, k, 0.5)
+                stock = lambda: torch_calibrate(ids, scores, count, category, target, k, 0.5)
+                (got, pa), (want, pb) = peak(ours), peak(stock)
+                same = float((got[1] == want[1]).float().mean())         # torch.log is another logarithm: near-ties may swap
+                dkl = float((got[3] - want[3]).abs().max())
+                (a, alo, ahi), (b, blo, bhi) = alternate(ours, stock, rounds=rounds, iters=5)
+                print(f"  G = {G:5d}, M = {M:4d}, k = {k:3d}: calibrated_select {a:8.3f} ms [{alo:.3f}, {ahi:.3f}] ({1e3 * a / k:.2f} us per step, "
+                      f"peak {pa / 2**20:.2f} MiB) | gather + {k} torch rounds {b:8.3f} ms [{blo:.3f}, {bhi:.3f}] (x{b / a:.2f}, peak "
+                      f"{pb / 2**20:.1f} MiB) | ids equal: {same:.4f}, max |kl - kl| {dkl:.2e}", flush=True)
+            del ids, scores, count
+        del target
+    torch.cuda.empty_cache()
+    if demo:
+        demo_calibrate()
+
+
+def demo_calibrate(users=512, k=10, calibrations=(0.0, 0.3, 0.5, 0.8), replicates=2000):
+    """What ``recommend(calibration=)`` does on the planted-signal corpus: the trained DIGAT (tests/golden/trained_planted_state.npz),
+    ``users`` held-out impressions against the pool of all news, k = 10, one ``util.recommend`` per value of ``calibrations``.
+    Reported per value, as means over the users with 95 % intervals (``evaluate.metric_intervals``, users resampled) and, against
+    calibration 0, the paired difference (``evaluate.compare_metrics``): ``kl`` (``util.calibration_kl`` of the list against the
+    history's category mix), ``category_max_share`` (``evaluate.list_quality``), recall@k of the impression's clicked candidates
+    (summed hits over summed clicks) and MRR."""
+    import types
+    from digat_amd import evaluate, synthetic, util
+    from digat_amd.main import clicked_targets
+    from digat_amd.model import Model, PrecomputedNewsEncoder
+    dev = torch.device("cuda:0")
+    golden = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
+    state = {name: v for name, v in np.load(os.path.join(golden, "trained_planted_state.npz")).items()}
+    depth = int(np.load(os.path.join(golden, "devset_trained_2k.npz"))["depth"])
+    full = synthetic.make_corpus(synthetic.SynthSpec(**synthetic.PLANTED_SPEC))
+    corpus = synthetic.slice_impressions(full, 0, users)
+    spec = full.spec
+    cfg = types.SimpleNamespace(news_encoder="MSA", graph_encoder="DIGAT", news_graph_size=spec.news_graph_size,
+                                max_history_num=spec.max_history_num, category_num=spec.category_num, graph_depth=depth, dropout_rate=0.2)
+    model = Model(cfg, news_encoder=PrecomputedNewsEncoder(torch.from_numpy(corpus.news_embedding)))
+    model.graph_encoder.load_state_dict({name: torch.from_numpy(v) for name, v in state.items()})
+    model = model.to(dev).eval()
+    dc = util.DeviceCorpus.from_numpy(corpus, dev)
+    who = np.arange(users, dtype=np.int64)
+    pool = np.arange(1, spec.news_num, dtype=np.int64)
+    C = int(dc.news_category.max()) + 1
+    target = evaluate.category_share(dc.history, dc.news_category, C)
+    tg_ids, tg_start = clicked_targets(dc, corpus.row_label)
+    names = ("kl", "category_max_share", f"recall@{k}", "mrr")
+
+    def columns(f):
+        ids, scores, count = util.recommend(model, dc, who, pool, k, calibration=f)
+        kl = util.calibration_kl(ids, count, dc.news_category, target).cpu().numpy().astype(np.float64)
+        q = evaluate.list_quality(ids, count, category=dc.news_category)
+        el = q["elements"].cpu().numpy().astype(np.float64)
+        share = q["category_max"].cpu().numpy().astype(np.float64) / np.maximum(el, 1.0)
+        col = evaluate.rank_metric_columns(evaluate.list_ranks(ids, count, tg_ids, tg_start), tg_start, ks=(k,))
+        ones = np.ones(users)
+        spread = float(scores[:, 0].mean() - scores[:, k - 1].mean())
+        return (np.stack([kl, share, col[f"hits@{k}"], col["rr"]], axis=1), np.stack([ones, ones, col["targets"], col["has"]], axis=1), spread)
+    base = None
+    print(f"calibration demo: planted-signal corpus, {spec.news_num - 1} news in {C} categories, the trained DIGAT, {users} held-out "
+          f"impressions, k = {k}, shortlist min(1024, 8 k) = {min(1024, 8 * k)}; means with 95 % intervals from {replicates} replicates over "
+          f"users; 'vs 0': paired difference to calibration 0", flush=True)
+    for f in calibrations:
+        values, den, spread = columns(f)
+        iv = evaluate.metric_intervals(values, names=names, replicates=replicates, denominators=den)
+        line = f"  calibration {f:.1f}: " + "  ".join(f"{name} {iv[name]['value']:.4f} [{iv[name]['lo']:.4f}, {iv[name]['hi']:.4f}]" for name in names)
+        if base is None:
+            base = (values, den)
+            line += f"  (score of slot 1 minus slot {k}, mean: {spread:.3f})"
+        else:
+            cmp = evaluate.compare_metrics(values, base[0], names=names, replicates=replicates, denominators_a=den, denominators_b=base[1])
+            line += " | vs 0: " + "  ".join(f"{name} {cmp[name]['diff']:+.4f} [{cmp[name]['lo']:+.4f}, {cmp[name]['hi']:+.4f}] p {cmp[name]['p']:.3f}"
+                                            for name in names)
+        print(line, flush=True)
+
+
 def torch_list_quality(ids, count, vectors, category=None, base_ids=None, base_count=None, exposure=None):
     """``evaluate.list_quality``'s figures built only from stock PyTorch: gather + ``torch.bmm``, the upper triangle's sum (in double)
     and max, a sort per list for the categories, a broadcast compare for the overlap, ``torch.bincount`` for the exposure."""
@@ -1778,6 +1927,8 @@ if __name__ == "__main__":
         bench_diversify(*nums)
     elif what == "list-quality":
         bench_list_quality(*nums)
+    elif what == "calibrate":
+        bench_calibrate(*nums)
     elif what == "bootstrap":
         bench_bootstrap(*nums)
     elif what == "linear":
