@@ -126,7 +126,14 @@ _SIGNATURES = {
     "digat_dot_shortlist_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int, C.c_int64]),
     "digat_dot_shortlist": (C.c_int, [_f, _f, _f, C.c_int64, C.c_int64, C.c_int64, C.c_int, _f, C.c_int, C.c_int, C.c_int64, _f, _f, _f, _f,
                                       C.c_size_t, _f]),
-    "digat_dot_rank_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
+    "digat_quantize_rows_i8": (C.c_int, [_f, C.c_int64, C.c_int, C.c_int, _f, _f, _f]),
+    "digat_qdot_scores": (C.c_int, [_f] * 5 + [C.c_int64] * 3 + [C.c_int, C.c_int, _f, _f]),
+    "digat_qdot_topk_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
+    "digat_qdot_topk": (C.c_int, [_f] * 5 + [C.c_int64] * 3 + [C.c_int, C.c_int, _f, C.c_int, C.c_int, _f, _f, _f, _f, C.c_size_t, _f]),
+    "digat_qdot_shortlist_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int, C.c_int64]),
+    "digat_qdot_shortlist": (C.c_int, [_f] * 5 + [C.c_int64] * 3 + [C.c_int, C.c_int, _f, C.c_int, C.c_int, C.c_int64, _f, _f, _f, _f,
+                                       C.c_size_t, _f]),
+    "digat_dot_rank_workspace_bytes":(C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
     "digat_dot_rank": (C.c_int, [_f, _f, _f, C.c_int64, C.c_int64, C.c_int64, C.c_int, _f, C.c_int, _f, _f, C.c_int64, _f, _f, _f, C.c_size_t, _f]),
     "digat_pool_softmax_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int]),
     "digat_pool_softmax_fwd": (C.c_int, [_f, _f, _f, C.c_int64, C.c_int64, C.c_int64, C.c_int, _f, C.c_int, _f, _f, C.c_int64, C.c_float, _f, _f, _f,

@@ -260,10 +260,9 @@ __device__ __forceinline__ void dot_cut(DotShared& s, uint2* list, int u, int k,
 
 // CHUNK: the pool positions one workgroup walks — DIGAT_DOT_TOPK_CHUNK for the entries of this file; digat_shortlist.inc stores a slab's
 // scores in shorter chunks (more workgroups for few users), the same sub-tiles through the same dot_tile: the same bits.
-template <bool FUSED, int CHUNK = DIGAT_DOT_TOPK_CHUNK>
-__global__ void __launch_bounds__(256) dot_chunk_kernel(const DotArgs a) {
-    __shared__ DotShared s;
-    extern __shared__ uint2 dot_lists[];            // [DOT_USERS][k + DOT_SUB]
+// The walk itself, shared with digat_qdot.inc's kernel: `product(u0)` leaves the sub-tile's scores in s.Ss behind a barrier (dot_tile here).
+template <bool FUSED, int CHUNK, class Tile>
+__device__ __forceinline__ void dot_chunk_walk(const DotArgs& a, DotShared& s, uint2* dot_lists, const Tile& product) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long tile = blockIdx.x % a.tiles, chunk = blockIdx.x / a.tiles;
     static_assert(CHUNK % DOT_SUB == 0, "a chunk is a whole number of sub-tiles");
@@ -285,7 +284,7 @@ __global__ void __launch_bounds__(256) dot_chunk_kernel(const DotArgs a) {
             s.id[tid] = id;
         }
         __syncthreads();
-        dot_tile(a, s, u0);
+        product(u0);
         if (!FUSED) {
             for (int i = wave; i < DOT_USERS; i += 4) {
                 const long g = u0 + i, p = q0 + lane;
@@ -326,6 +325,13 @@ __global__ void __launch_bounds__(256) dot_chunk_kernel(const DotArgs a) {
                 a.ws[(g * a.chunks + chunk) * a.k + i] = (unsigned)i < s.cnt[u] ? dot_lists[(size_t)u * cap + i] : make_uint2(0u, DOT_NOPOS);
         }
     }
+}
+
+template <bool FUSED, int CHUNK = DIGAT_DOT_TOPK_CHUNK>
+__global__ void __launch_bounds__(256) dot_chunk_kernel(const DotArgs a) {
+    __shared__ DotShared s;
+    extern __shared__ uint2 dot_lists[];            // [DOT_USERS][k + DOT_SUB]
+    dot_chunk_walk<FUSED, CHUNK>(a, s, dot_lists, [&](long u0) { dot_tile(a, s, u0); });
 }
 
 __global__ void __launch_bounds__(256) dot_topk_user_kernel(const DotArgs a) {

@@ -884,6 +884,7 @@ int digat_row_logits(const float* news_ctx, const float* user_ctx, float* logits
 #include "digat_ablation.inc"
 #include "digat_dot_topk.inc"
 #include "digat_shortlist.inc"
+#include "digat_qdot.inc"
 #include "digat_dot_rank.inc"
 #include "digat_pool_softmax.inc"
 #include "digat_list_softmax.inc"

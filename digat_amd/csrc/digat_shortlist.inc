@@ -262,6 +262,42 @@ static int short_launch(const ShortArgs& a, long slots, hipStream_t st) {
 static long short_dot_chunks(long pool) { return (pool + SHORT_DOT_CHUNK - 1) / SHORT_DOT_CHUNK; }
 static long short_slab(int64_t slab_users) { return slab_users > 0 ? (long)slab_users : SHORT_SLAB_USERS; }
 
+static size_t short_dot_workspace_bytes(int64_t G, int64_t P, int m, int64_t slab_users) {
+    if (G < 0 || P < 0 || m < 1 || m > SHORT_MAX_K) return 0;
+    const size_t slab = (size_t)short_slab(slab_users);
+    return align_up(slab * (size_t)P * sizeof(float), 256) + slab * (size_t)short_chunks((long)P) * (size_t)m * sizeof(uint2);
+}
+
+// digat_dot_shortlist behind its product, shared with digat_qdot_shortlist: `check(slab)` is the entry's verdict on its operands for
+// launches of `slab` users, `scores(g0, gs, out, st)` launches the [gs, P] scores of users g0 .. g0 + gs into `out` on `st`.
+template <class Check, class Scores>
+static int short_dot_slabs(const int64_t* pool, int64_t G, int64_t N, int64_t P, const int64_t* skip, int skip_len, int m, int64_t slab_users,
+                           float* out_scores, int64_t* out_ids, int32_t* out_count, void* workspace, size_t workspace_bytes, hipStream_t st,
+                           const Check& check, const Scores& scores) {
+    if (!out_scores || !out_ids || !out_count) return DIGAT_ERR_ARG;
+    const long slab = G > 0 && G < short_slab(slab_users) ? (long)G : short_slab(slab_users);      // users per launch
+    int rc = check(slab);
+    if (rc == DIGAT_OK && ((double)slab * (double)short_chunks((long)P) > 2147483647.0 ||
+                           (double)dot_tiles(slab) * (double)short_dot_chunks((long)P) > 2147483647.0)) rc = DIGAT_ERR_SHAPE;
+    rc = topk_check_args(m, skip, skip_len, rc, G > 0 && P > 0, workspace, SHORT_MAX_K);
+    if (rc != DIGAT_OK) return rc;
+    if (G > 0 && P > 0 && workspace_bytes < short_dot_workspace_bytes(G, P, m, slab_users)) return DIGAT_ERR_WORKSPACE;
+    float* slab_scores = (float*)workspace;
+    uint2* ws = (uint2*)((char*)workspace + align_up((size_t)short_slab(slab_users) * (size_t)P * sizeof(float), 256));
+    for (long g0 = 0; g0 < (long)G; g0 += slab) {
+        const long gs = (long)G - g0 < slab ? (long)G - g0 : slab;
+        if (P > 0) {
+            scores(g0, gs, slab_scores, st);
+            DIGAT_CHECK_LAUNCH();
+        }
+        const ShortArgs a{slab_scores, nullptr, gs * (long)P, gs, (long)P, short_chunks((long)P), pool, pool ? (long)N : 0,
+                          skip ? skip + g0 * skip_len : nullptr, skip_len, m, out_scores + g0 * m, out_ids + g0 * m, out_count + g0, ws};
+        rc = short_launch(a, P > SHORT_SMALL ? gs * a.seg_chunks : 0, st);
+        if (rc != DIGAT_OK) return rc;
+    }
+    return DIGAT_OK;
+}
+
 extern "C" {
 
 size_t digat_shortlist_segments_workspace_bytes(int64_t rows, int64_t segments, int m) {
@@ -284,39 +320,20 @@ int digat_shortlist_segments(const float* scores, const int64_t* seg_start, int6
 }
 
 size_t digat_dot_shortlist_workspace_bytes(int64_t G, int64_t P, int m, int64_t slab_users) {
-    if (G < 0 || P < 0 || m < 1 || m > SHORT_MAX_K) return 0;
-    const size_t slab = (size_t)short_slab(slab_users);
-    return align_up(slab * (size_t)P * sizeof(float), 256) + slab * (size_t)short_chunks((long)P) * (size_t)m * sizeof(uint2);
+    return short_dot_workspace_bytes(G, P, m, slab_users);
 }
 
 int digat_dot_shortlist(const float* users, const float* news, const int64_t* pool, int64_t G, int64_t N, int64_t P, int d,
                         const int64_t* skip, int skip_len, int m, int64_t slab_users, float* out_scores, int64_t* out_ids,
                         int32_t* out_count, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!out_scores || !out_ids || !out_count) return DIGAT_ERR_ARG;
-    const long slab = G > 0 && G < short_slab(slab_users) ? (long)G : short_slab(slab_users);      // users per launch
-    int rc = dot_check(users, news, pool, G < 0 ? G : slab, N, P, d);
-    if (rc == DIGAT_OK && ((double)slab * (double)short_chunks((long)P) > 2147483647.0 ||
-                           (double)dot_tiles(slab) * (double)short_dot_chunks((long)P) > 2147483647.0)) rc = DIGAT_ERR_SHAPE;
-    rc = topk_check_args(m, skip, skip_len, rc, G > 0 && P > 0, workspace, SHORT_MAX_K);
-    if (rc != DIGAT_OK) return rc;
-    if (G > 0 && P > 0 && workspace_bytes < digat_dot_shortlist_workspace_bytes(G, P, m, slab_users)) return DIGAT_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    float* slab_scores = (float*)workspace;
-    uint2* ws = (uint2*)((char*)workspace + align_up((size_t)short_slab(slab_users) * (size_t)P * sizeof(float), 256));
-    for (long g0 = 0; g0 < (long)G; g0 += slab) {
-        const long gs = (long)G - g0 < slab ? (long)G - g0 : slab;
-        if (P > 0) {
+    return short_dot_slabs(
+        pool, G, N, P, skip, skip_len, m, slab_users, out_scores, out_ids, out_count, workspace, workspace_bytes, (hipStream_t)stream,
+        [&](long slab) { return dot_check(users, news, pool, G < 0 ? G : slab, N, P, d); },
+        [&](long g0, long gs, float* slab_scores, hipStream_t st) {
             DotArgs da{users + g0 * d, news, pool, gs, (long)N, (long)P, d, nullptr, 0, 0, dot_tiles(gs), short_dot_chunks((long)P), slab_scores,
                        nullptr, nullptr, nullptr, nullptr};
             hipLaunchKernelGGL((dot_chunk_kernel<false, SHORT_DOT_CHUNK>), dim3((unsigned)(da.tiles * da.chunks)), dim3(256), 0, st, da);
-            DIGAT_CHECK_LAUNCH();
-        }
-        const ShortArgs a{slab_scores, nullptr, gs * (long)P, gs, (long)P, short_chunks((long)P), pool, pool ? (long)N : 0,
-                          skip ? skip + g0 * skip_len : nullptr, skip_len, m, out_scores + g0 * m, out_ids + g0 * m, out_count + g0, ws};
-        rc = short_launch(a, P > SHORT_SMALL ? gs * a.seg_chunks : 0, st);
-        if (rc != DIGAT_OK) return rc;
-    }
-    return DIGAT_OK;
+        });
 }
 
 }  // extern "C"

@@ -375,6 +375,234 @@ def dot_scores(users, news, pool=None):
     return out
 
 
+QDOT_MAX_D = 1024        # include/digat_hip.h: DIGAT_QDOT_MAX_D, the widest vectors the quantised entries take
+
+
+def _qdot_width(d: int) -> int:
+    if not 1 <= int(d) <= QDOT_MAX_D:
+        raise ValueError(f"the quantised entries take vectors of 1 to QDOT_MAX_D = {QDOT_MAX_D} channels, got {d}")
+    return (int(d) + 15) // 16 * 16
+
+
+def quantize_rows_host(x):
+    """The contract of ``digat_quantize_rows_i8`` in numpy float32 — the yardstick of the kernel, byte for byte.  ``x`` [R, d] ->
+    ``(q int8 [R, dq], scale float32 [R])`` with dq = d rounded up to 16 and zeros from d on: per row ``amax = max |x|``,
+    ``scale = amax / 127`` and ``q = clip(rint(x / scale), -127, 127)`` — float32 divisions, rint to nearest even.  ``scale == 0``
+    (a zero row, an amax that underflows): codes 0.  A row with a NaN or an infinity: codes 0 and scale NaN."""
+    X = np.ascontiguousarray(x, dtype=np.float32)
+    if X.ndim != 2:
+        raise ValueError("x must be [R, d]")
+    R, d = X.shape
+    dq = _qdot_width(d)
+    q = np.zeros((R, dq), dtype=np.int8)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        bad = ~np.isfinite(X).all(axis=1)
+        amax = np.abs(np.where(bad[:, None], np.float32(0), X)).max(axis=1).astype(np.float32)
+        scale = (amax / np.float32(127.0)).astype(np.float32)
+        live = ~bad & (scale > 0)
+        codes = np.clip(np.rint((X[live] / scale[live, None]).astype(np.float32)), -127, 127)
+    q[live, :d] = codes.astype(np.int8)
+    scale[bad] = np.float32("nan")
+    return q, scale
+
+
+def _check_qdot_host(qu, su, qn, sn):
+    QU, QN = np.asarray(qu), np.asarray(qn)
+    if QU.ndim != 2 or QN.ndim != 2 or QU.shape[1] != QN.shape[1] or QU.dtype != np.int8 or QN.dtype != np.int8:
+        raise ValueError(f"qu [G, dq] and qn [N, dq] must be int8 codes of one width, got {QU.shape} {QU.dtype} and {QN.shape} {QN.dtype}")
+    if QU.shape[1] != _qdot_width(QU.shape[1]):
+        raise ValueError(f"rows of codes are padded to a multiple of 16, got dq = {QU.shape[1]}")
+    SU, SN = np.ascontiguousarray(su, dtype=np.float32), np.ascontiguousarray(sn, dtype=np.float32)
+    if SU.shape != (QU.shape[0],) or SN.shape != (QN.shape[0],):
+        raise ValueError(f"one scale per row: su {SU.shape} for {QU.shape[0]} users, sn {SN.shape} for {QN.shape[0]} news")
+    return QU, SU, QN, SN
+
+
+def qdot_scores_host(qu, su, qn, sn, pool=None):
+    """The contract of ``digat_qdot_scores`` in numpy — its bits: ``score(g, p) = (float32(acc) * su[g]) * sn[id]`` with ``acc`` the
+    exact integer product of the code rows, ``id = pool[p]`` (None: p); a position whose id lies outside [0, N) holds +0.0."""
+    QU, SU, QN, SN = _check_qdot_host(qu, su, qn, sn)
+    N = QN.shape[0]
+    ids = np.arange(N, dtype=np.int64) if pool is None else np.asarray(pool, dtype=np.int64)
+    if ids.ndim != 1:
+        raise ValueError("pool must be 1-D")
+    ok = (ids >= 0) & (ids < N)
+    safe = np.where(ok, ids, 0)
+    acc = QU.astype(np.float64) @ QN[safe].astype(np.float64).T if N else np.zeros((QU.shape[0], len(ids)))     # exact: |acc| < 2^24
+    with np.errstate(invalid="ignore", over="ignore"):
+        S = ((acc.astype(np.float32) * SU[:, None]).astype(np.float32) * (SN[safe][None, :] if N else np.float32(0))).astype(np.float32)
+    S[:, ~ok] = np.float32(0)
+    return S
+
+
+def qdot_bound(users, news, su, sn):
+    """The derived error of a quantised score against the real product (csrc/digat_qdot.inc), float64 [G, N]:
+    ``(sn/2 |u|_1 + su/2 |v|_1 + d su sn / 4) (1 + 2^-15)`` for the codes, plus ``2^-23 (|u|_2 |v|_2 + that)`` for the two fp32
+    multiplications.  Rows with a NaN scale have no bound (NaN)."""
+    U, V = np.asarray(users, dtype=np.float64), np.asarray(news, dtype=np.float64)
+    SU, SN = np.asarray(su, dtype=np.float64), np.asarray(sn, dtype=np.float64)
+    d = U.shape[1]
+    u1, v1 = np.abs(U).sum(axis=1), np.abs(V).sum(axis=1)
+    u2, v2 = np.sqrt((U * U).sum(axis=1)), np.sqrt((V * V).sum(axis=1))
+    code = (0.5 * SN[None, :] * u1[:, None] + 0.5 * SU[:, None] * v1[None, :] + 0.25 * d * SU[:, None] * SN[None, :]) * (1.0 + 2.0 ** -15)
+    return code + 2.0 ** -23 * (u2[:, None] * v2[None, :] + code)
+
+
+def quantize_rows(x):
+    """``x`` [R, d] float32 -> ``(q int8 [R, dq], scale float32 [R])``: per-row symmetric int8 codes, dq = d rounded up to 16 with a
+    zero tail (``digat_quantize_rows_i8``; on CPU tensors ``quantize_rows_host``, the same bytes).  d <= ``QDOT_MAX_D`` = 1024."""
+    import torch
+    from . import _lib
+    if x.dim() != 2:
+        raise ValueError("x must be [R, d]")
+    R, d = int(x.shape[0]), int(x.shape[1])
+    dq = _qdot_width(d)
+    if x.device.type != "cuda":
+        return tuple(map(torch.from_numpy, quantize_rows_host(x.detach().float().numpy())))
+    xs = _lib.f32(x.detach())
+    q = torch.empty((R, dq), dtype=torch.int8, device=x.device)
+    scale = torch.empty((R,), dtype=torch.float32, device=x.device)
+    if R:
+        _lib.check(_lib.lib().digat_quantize_rows_i8(xs.data_ptr(), R, d, dq, q.data_ptr(), scale.data_ptr(), _lib.stream_ptr()),
+                   "digat_quantize_rows_i8")
+    return q, scale
+
+
+def _check_qdot_args(qu, su, qn, sn, pool, skip=None, k=None, limit=_TOPK_LIMIT):
+    import torch
+    if qu.dim() != 2 or qn.dim() != 2 or qu.shape[1] != qn.shape[1] or qu.dtype != torch.int8 or qn.dtype != torch.int8:
+        raise ValueError(f"qu [G, dq] and qn [N, dq] must be int8 codes of one width, got {tuple(qu.shape)} {qu.dtype} and "
+                         f"{tuple(qn.shape)} {qn.dtype}")
+    dq = int(qu.shape[1])
+    if dq != _qdot_width(dq):
+        raise ValueError(f"rows of codes are padded to a multiple of 16, got dq = {dq}")
+    if tuple(su.shape) != (qu.shape[0],) or tuple(sn.shape) != (qn.shape[0],) or su.dtype != torch.float32 or sn.dtype != torch.float32:
+        raise ValueError("su [G] and sn [N] must hold one float32 scale per row of codes")
+    G, N = int(qu.shape[0]), int(qn.shape[0])
+    if k is not None:
+        _check_limit(k, limit)
+    if pool is not None:
+        if pool.dim() != 1 or pool.dtype in (torch.float16, torch.float32, torch.float64, torch.bool):
+            raise ValueError("pool must be a 1-D integer tensor of news rows")
+        if pool.numel() and (int(pool.min()) < 0 or int(pool.max()) >= N):
+            raise ValueError(f"pool ids must lie in [0, {N})")
+    if skip is not None and (skip.dim() != 2 or skip.shape[0] != G or skip.shape[1] > TOPK_MAX_SKIP):
+        raise ValueError(f"skip must be [users, at most {TOPK_MAX_SKIP}], got shape {tuple(skip.shape)}")
+    return G, N, N if pool is None else int(pool.shape[0]), dq
+
+
+def _qdot_head(qu, su, qn, sn, pl, G, N, P, dq):
+    # the codes' tail is zero, so the padded width is the d the entry is told
+    return (qu.data_ptr(), su.data_ptr(), qn.data_ptr(), sn.data_ptr(), None if pl is None else pl.data_ptr(), G, N, P, dq, dq)
+
+
+def qdot_scores(qu, su, qn, sn, pool=None):
+    """Quantised scores [G, P] float32 of code rows ``qu`` [G, dq] / ``qn`` [N, dq] (int8, ``quantize_rows``) with scales ``su`` [G] /
+    ``sn`` [N]: ``(float32(acc) * su[g]) * sn[pool[p]]`` with ``acc`` the int32 product on the int8 matrix cores
+    (``digat_qdot_scores``) — the bits ``qdot_topk`` and ``qdot_shortlist`` select from, and ``qdot_scores_host``'s, which CPU tensors
+    go through.  ``qdot_bound`` holds them to the real product."""
+    import torch
+    from . import _lib
+    G, N, P, dq = _check_qdot_args(qu, su, qn, sn, pool)
+    if qu.device.type != "cuda":
+        return torch.from_numpy(qdot_scores_host(qu.numpy(), su.numpy(), qn.numpy(), sn.numpy(), None if pool is None else pool.numpy()))
+    dev = _lib.require_device(*[t for t in (qu, su, qn, sn, pool) if t is not None])
+    qu, su, qn, sn = qu.contiguous(), su.contiguous(), qn.contiguous(), sn.contiguous()
+    pl = None if pool is None else pool.to(torch.int64).contiguous()
+    out = torch.empty((G, P), dtype=torch.float32, device=dev)
+    if G and P:
+        _lib.check(_lib.lib().digat_qdot_scores(*_qdot_head(qu, su, qn, sn, pl, G, N, P, dq), out.data_ptr(), _lib.stream_ptr()),
+                   "digat_qdot_scores")
+    return out
+
+
+def _qdot_select(qu, su, qn, sn, k, pool, skip, limit, slab_users):
+    """``qdot_topk`` (``slab_users`` None) or ``qdot_shortlist``: ``_dot_select`` on codes."""
+    import torch
+    from . import _lib
+    G, N, P, dq = _check_qdot_args(qu, su, qn, sn, pool, skip, k, limit)
+    k = int(k)
+    if qu.device.type != "cuda":
+        host = lambda t: None if t is None else t.numpy()
+        S = qdot_scores_host(qu.numpy(), su.numpy(), qn.numpy(), sn.numpy(), host(pool))
+        sk = None if skip is None or skip.shape[1] == 0 else host(skip)
+        return tuple(map(torch.from_numpy, dot_topk_host(S, k, pool=host(pool), skip=sk, limit=limit)))
+    dev = _lib.require_device(*[t for t in (qu, su, qn, sn, pool, skip) if t is not None])
+    qu, su, qn, sn = qu.contiguous(), su.contiguous(), qn.contiguous(), sn.contiguous()
+    pl = None if pool is None else pool.to(torch.int64).contiguous()
+    sk = None if skip is None or skip.shape[1] == 0 else skip.to(torch.int64).contiguous()
+    out_s = torch.full((G, k), float("-inf"), dtype=torch.float32, device=dev)
+    out_i = torch.full((G, k), -1, dtype=torch.int64, device=dev)
+    count = torch.zeros((G,), dtype=torch.int32, device=dev)
+    if G == 0 or P == 0:
+        return out_s, out_i, count
+    L = _lib.lib()
+    head = _qdot_head(qu, su, qn, sn, pl, G, N, P, dq) + (_lib.ptr(sk), 0 if sk is None else int(sk.shape[1]), k)
+    outs = (out_s.data_ptr(), out_i.data_ptr(), count.data_ptr())
+    if slab_users is None:
+        need = int(L.digat_qdot_topk_workspace_bytes(G, P, k))
+        ws = _lib.workspace(need, dev, "dot_topk")
+        _lib.check(L.digat_qdot_topk(*head, *outs, ws.data_ptr(), need, _lib.stream_ptr()), "digat_qdot_topk")
+    else:
+        need = int(L.digat_qdot_shortlist_workspace_bytes(G, P, k, slab_users))
+        ws = _lib.workspace(need, dev, "dot_shortlist")
+        _lib.check(L.digat_qdot_shortlist(*head, slab_users, *outs, ws.data_ptr(), need, _lib.stream_ptr()), "digat_qdot_shortlist")
+    return out_s, out_i, count
+
+
+def qdot_topk(qu, su, qn, sn, k: int, pool=None, skip=None):
+    """``dot_topk`` on quantised scores (``digat_qdot_topk``): for every row of codes ``qu`` the k <= 128 best rows of ``qn`` by
+    ``qdot_scores``' bits, in ``dot_topk``'s order, with its ``pool``, ``skip``, fill and returns ``(scores [G,k], ids [G,k],
+    count [G])``; the [G, P] scores never reach memory.  On CPU tensors: ``dot_topk_host`` over ``qdot_scores_host``."""
+    return _qdot_select(qu, su, qn, sn, k, pool, skip, _TOPK_LIMIT, None)
+
+
+def qdot_shortlist(qu, su, qn, sn, m: int, pool=None, skip=None, slab_users=None):
+    """``dot_shortlist`` on quantised scores (``digat_qdot_shortlist``): lists of up to ``SHORTLIST_MAX_K`` = 1024, the users walked
+    in slabs of ``slab_users`` (None: 256) whose scores ``qdot_scores``' kernel stores; the results do not depend on the slab.  On
+    CPU tensors: ``dot_shortlist_host`` over ``qdot_scores_host``."""
+    slab = SHORTLIST_SLAB_USERS if slab_users is None else int(slab_users)
+    if slab < 1:
+        raise ValueError(f"slab_users must be positive, got {slab_users}")
+    return _qdot_select(qu, su, qn, sn, m, pool, skip, _SHORTLIST_LIMIT, max(1, min(slab, int(qu.shape[0]))))
+
+
+def refine_lists(users, rows, ids, count, k: int):
+    """The second stage behind a quantised shortlist: the exact fp32 scores of given lists and their k <= 128 best —
+    ``(scores [G,k] float32, ids [G,k] int64, count [G] int32)`` in selection order (score descending, ties by position IN THE LIST,
+    NaNs last; ``-inf`` / ``-1`` at and beyond ``count``).  ``users`` [G, d], ``rows`` [N, d], ``ids`` [G, M] rows of ``rows`` and
+    ``count`` [G] (None: M) — what ``qdot_shortlist`` returns; slot (g, j) is an element when ``j < count[g]`` and
+    ``0 <= ids[g, j] < N``.  A caller who wants ties in pool order hands the lists over in pool order (``nrms.recommend`` does).
+
+    On the device no new kernel: ``list_softmax``'s forward stores the lists' scores — ``dot_scores``' bits, M <= 1024 and d <= 512 —
+    and ``topk_segments`` selects from them, the non-elements skipped as id -1.  On CPU tensors: a gather, ``(c * u).sum(1)`` as
+    ``recommend``'s brute force scores its pairs, and ``topk_segments_host``."""
+    import torch
+    if ids.dim() != 2 or ids.shape[0] != users.shape[0]:
+        raise ValueError(f"ids must be [G = {int(users.shape[0])}, M], got {tuple(ids.shape)}")
+    k = _check_limit(k)
+    G, M, N = int(ids.shape[0]), int(ids.shape[1]), int(rows.shape[0])
+    dev = users.device
+    ids = ids.to(torch.int64)
+    cnt = None if count is None else torch.as_tensor(count).to(dev)
+    elem = list_elements(ids, cnt, N)
+    flat_ids = torch.where(elem, ids, torch.full_like(ids, -1)).reshape(-1).contiguous()
+    seg = torch.arange(G + 1, dtype=torch.int64, device=dev) * M
+    skip = torch.full((G, 1), -1, dtype=torch.int64, device=dev)
+    if G == 0 or M == 0:
+        return (torch.full((G, k), float("-inf"), dtype=torch.float32, device=dev), torch.full((G, k), -1, dtype=torch.int64, device=dev),
+                torch.zeros((G,), dtype=torch.int32, device=dev))
+    if dev.type == "cuda":
+        with torch.no_grad():
+            S = list_softmax(users.detach(), rows.detach(), ids, cnt, torch.zeros((G, M), dtype=torch.float32, device=dev))[2]
+        return topk_segments(S.reshape(-1), seg, k, ids=flat_ids, skip=skip)
+    safe = torch.where(elem, ids, torch.zeros_like(ids)).reshape(-1)
+    owner = torch.arange(G, dtype=torch.int64).repeat_interleave(M)
+    with torch.no_grad():
+        S = (rows.index_select(0, safe) * users.index_select(0, owner)).sum(dim=1).float()
+    return tuple(map(torch.from_numpy, topk_segments_host(S.numpy(), seg.numpy(), k, ids=flat_ids.numpy(), skip=skip.numpy())))
+
+
 def _check_target_start(target_start, users: int, targets: int) -> np.ndarray:
     """``target_start`` of the rank entries as a host int64 array: [users + 1] row offsets from 0 to ``targets`` that never decrease."""
     import torch

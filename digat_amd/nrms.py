@@ -511,7 +511,7 @@ def user_vectors(model, dev, users, batch_size=1024):
 
 
 def recommend(model, dev, users, candidates=None, k=10, exclude_history=True, batch_size=1024, diversity=None, shortlist=None, category=None,
-              max_per_category=0, calibration=None, calibration_target=None, alpha=0.01):
+              max_per_category=0, calibration=None, calibration_target=None, alpha=0.01, index=None, refine=None):
     """For every user, which k news, in order: ``(news_ids [G,k] int64, scores [G,k] float32, count [G] int32)`` on the model's
     device.  Order: score descending, equal scores in candidate order; slots at or beyond ``count[g]`` hold id -1 and score -inf.
 
@@ -530,8 +530,20 @@ def recommend(model, dev, users, candidates=None, k=10, exclude_history=True, ba
     128) and ``util.calibrate`` cuts every list to k with ``lam = 1 - calibration`` towards the category mix of the user's history
     (``evaluate.category_share`` under ``category``, None: ``dev.news_category``; at most 64 categories) or towards
     ``calibration_target`` [G, C]; ``alpha`` smooths the list's mix.  ``util.recommend`` has the details; ``calibration`` and
-    ``diversity`` do not combine."""
+    ``diversity`` do not combine.
+
+    ``index`` (``build_index``; None: the call above, bit for bit): a quantised first stage.  The users are encoded as always and
+    quantised on the device, ``evaluate.qdot_shortlist`` (``qdot_topk`` up to 128) retrieves ``M = refine or min(1024, max(8 k, 64))``
+    news per user on the int8 matrix cores from the shared pool, and ``evaluate.refine_lists`` re-scores those M in fp32 and cuts
+    them to k: the scores returned are exact (``dot_scores``' bits), and wherever the exact top-k lies inside the quantised
+    shortlist the result is the plain call's, bit for bit (``index_report`` measures how often that is).  Per-user candidate lists
+    are refused.  ``diversity`` composes — its shortlist of k' comes from the indexed call —; ``calibration`` does not: its
+    shortlist may be longer than the 128 entries ``refine_lists`` returns."""
     from . import evaluate, util
+    if index is None and refine is not None:
+        raise ValueError("refine belongs to an indexed call: name index (build_index)")
+    if calibration is not None and index is not None:
+        raise ValueError("calibration does not combine with index: its shortlist may exceed the 128 entries the re-score returns")
     if calibration is not None:
         if diversity is not None or max_per_category:
             raise ValueError("calibration does not combine with diversity or max_per_category: name one of them")
@@ -545,12 +557,14 @@ def recommend(model, dev, users, candidates=None, k=10, exclude_history=True, ba
     if calibration_target is not None:
         raise ValueError("calibration_target belongs to a calibrated call: name calibration")
     if diversity is not None:
-        select = lambda wide: recommend(model, dev, users, candidates, wide, exclude_history, batch_size)
+        select = lambda wide: recommend(model, dev, users, candidates, wide, exclude_history, batch_size, index=index, refine=refine)
         plain = lambda: news_caches(model, dev.title_text, dev.title_mask, dev.augmented_title_text, dev.augmented_title_mask, 4 * batch_size)[0]
         return util.shortlist_then_diversify(select, plain, k, (diversity,), shortlist, category, max_per_category,
                                              getattr(dev, "news_category", None))[1][0]
     if shortlist is not None or category is not None or max_per_category:
         raise ValueError("shortlist, category and max_per_category belong to a diversified call: name diversity (0.0: the cap alone)")
+    if index is not None:
+        return _retrieve_indexed(model, dev, users, candidates, k, exclude_history, batch_size, index, refine, True)
     return _retrieve(model, dev, users, candidates, k, exclude_history, batch_size, False)
 
 
@@ -582,7 +596,93 @@ def _retrieve(model, dev, users, candidates, k, exclude_history, batch_size, lon
                                  long_lists=long_lists)
 
 
-def shortlist(model, dev, users, candidates=None, m=512, exclude_history=True, batch_size=1024):
+class RetrievalIndex:
+    """What ``build_index`` returns: ``codes`` [N, dq] int8 and ``scales`` [N] float32 of the augmented news cache
+    (``evaluate.quantize_rows``), ``vectors`` [N, hd] — that cache in fp32, for the re-score —, ``plain`` [N, hd] — the plain cache
+    the user encoder reads (the same tensor for NRMS) — and ``news_num`` = N.  It is a snapshot of the model's weights."""
+
+    def __init__(self, codes, scales, vectors, plain):
+        self.codes, self.scales, self.vectors, self.plain, self.news_num = codes, scales, vectors, plain, int(vectors.shape[0])
+
+
+def build_index(model, dev, batch_size=1024):
+    """The quantised index of ``dev``'s news for ``recommend(index=)`` / ``shortlist(index=)``: the news caches, encoded once, and
+    the augmented cache's per-row int8 codes and scales — 1 byte per channel beside the 4 of the fp32 cache.  Rebuild it when the
+    model's weights change."""
+    from . import evaluate
+    model.eval()
+    plain, aug = news_caches(model, dev.title_text, dev.title_mask, dev.augmented_title_text, dev.augmented_title_mask, 4 * batch_size)
+    codes, scales = evaluate.quantize_rows(aug)
+    return RetrievalIndex(codes, scales, aug, plain)
+
+
+def _retrieve_indexed(model, dev, users, candidates, k, exclude_history, batch_size, index, refine, rescore):
+    """``recommend(index=)`` (``rescore``: M quantised candidates, then the exact k) or ``shortlist(index=)`` (the k quantised lists
+    themselves): ``_retrieve``'s users, pool and skip rows on ``index``'s caches and codes."""
+    from . import evaluate, util
+    if not isinstance(index, RetrievalIndex):
+        raise ValueError("index must come from build_index")
+    hist, mask = _histories(dev, users)
+    G, N = int(hist.shape[0]), int(dev.title_text.shape[0])
+    if index.news_num != N:
+        raise ValueError(f"the index holds {index.news_num} news, this corpus {N}: rebuild it (build_index)")
+    k = util.recommend_limits(k, int(hist.shape[1]) if exclude_history else 0, not rescore)
+    if rescore:
+        M = int(refine) if refine else min(evaluate.SHORTLIST_MAX_K, max(8 * k, 64))
+        if not k <= M <= evaluate.SHORTLIST_MAX_K:
+            raise ValueError(f"refine must lie in [k, {evaluate.SHORTLIST_MAX_K}] = [{k}, {evaluate.SHORTLIST_MAX_K}], got {refine}")
+    elif refine is not None:
+        raise ValueError("refine belongs to recommend: shortlist returns the quantised lists themselves")
+    else:
+        M = k
+    if candidates is None:
+        candidates = np.arange(1, N, dtype=np.int64)
+    ids, start = util.recommend_candidates(candidates, G, N)
+    if start is not None:
+        raise ValueError("an index retrieves from one pool shared by all users: per-user candidate lists go through the call without index=")
+    model.eval()
+    device = index.vectors.device
+    pool = ids.to(device)
+    user = _encode_users(model, index.plain, hist, mask, batch_size)
+    skip = torch.where(mask != 0, hist, torch.zeros_like(hist)) if exclude_history else None
+    qu, su = evaluate.quantize_rows(user)
+    if M <= evaluate.TOPK_MAX_K:
+        s, i, c = evaluate.qdot_topk(qu, su, index.codes, index.scales, M, pool=pool, skip=skip)
+    else:
+        s, i, c = evaluate.qdot_shortlist(qu, su, index.codes, index.scales, M, pool=pool, skip=skip)
+    if not rescore:
+        return i, s, c
+    # exact ties go by pool position, as in the plain call: hand the lists to the re-score in pool order
+    where = torch.full((N + 1,), int(pool.shape[0]), dtype=torch.int64, device=device)
+    where[pool.flip(0)] = torch.arange(int(pool.shape[0]) - 1, -1, -1, dtype=torch.int64, device=device)
+    order = torch.argsort(where[torch.where(i >= 0, i, torch.full_like(i, N))], dim=1, stable=True)
+    s, i, c = evaluate.refine_lists(user, index.vectors, torch.gather(i, 1, order), c, k)
+    return i, s, c
+
+
+def index_report(model, dev, users, k=10, ms=(32, 64, 128, 256), batch_size=1024, index=None, replicates=2000, seed=0):
+    """What a quantised first stage of length M loses, per M of ``ms``: ``containment`` — the share of users whose exact top-k
+    (``recommend``) lies wholly inside the quantised shortlist (``shortlist(index=)``), where ``recommend(index=, refine=M)`` returns
+    the exact lists bit for bit — and ``agreement`` — ``teacher_agreement@k`` of the shortlist with the exact top-k as the teacher,
+    the mean share of the exact top-k that the shortlist holds.  Both come with ``evaluate.metric_intervals`` over users.  Returns
+    one dict per M: ``{"m": M, "containment": .., "agreement": .., "intervals": {...}}``.  ``index`` None: ``build_index`` here."""
+    from . import evaluate
+    index = build_index(model, dev, batch_size) if index is None else index
+    t_ids, _, t_cnt = recommend(model, dev, users, k=k, batch_size=batch_size)
+    rows = []
+    for M in ms:
+        s_ids, _, s_cnt = shortlist(model, dev, users, m=max(int(M), 1), batch_size=batch_size, index=index)
+        agree = teacher_agreement(s_ids, s_cnt, t_ids, t_cnt, ks=(int(k),))["per_user"][:, 0]
+        # the teacher's list is never longer than its user's elements, so a full share is containment (an empty list is contained)
+        inside = np.where(_host_array(t_cnt) > 0, agree >= 1.0, True).astype(np.float64)
+        per_user = np.stack([inside, agree], axis=1)
+        iv = evaluate.metric_intervals(per_user, names=["containment", "agreement"], replicates=replicates, seed=seed)
+        rows.append({"m": int(M), "containment": float(inside.mean()) if len(inside) else float("nan"),
+                     "agreement": float(agree.mean()) if len(agree) else float("nan"), "intervals": iv})
+    return rows
+
+
+def shortlist(model, dev, users, candidates=None, m=512, exclude_history=True, batch_size=1024, index=None):
     """``recommend`` for the retrieval stage in front of a re-rank: for every user the m <= ``evaluate.SHORTLIST_MAX_K`` = 1024 best
     news, in order — ``(news_ids [G,m] int64, scores [G,m] float32, count [G] int32)`` — where ``recommend`` stops at 128.  ``dev``,
     ``users``, ``candidates``, ``exclude_history`` and ``batch_size`` are ``recommend``'s, and so are the caches, the user vectors,
@@ -590,7 +690,13 @@ def shortlist(model, dev, users, candidates=None, m=512, exclude_history=True, b
     ``evaluate.dot_shortlist`` (scores stored a slab of users at a time, then selected), per-user lists through gather,
     ``row_logits`` and ``evaluate.shortlist_segments``; on CPU tensors: stock PyTorch and ``shortlist_segments_host``.  How long the
     list must be: ``retrieval_metrics`` and ``evaluate.shortlist_for``; ``candidates_csr`` turns the result into the per-user
-    lists ``util.recommend`` re-ranks."""
+    lists ``util.recommend`` re-ranks.
+
+    ``index`` (``build_index``; None: the call above, bit for bit): the lists come from ``evaluate.qdot_shortlist`` (``qdot_topk`` up
+    to 128) on the int8 codes, and both their order and their SCORES are the quantised ones — ``evaluate.qdot_scores``' bits, within
+    ``evaluate.qdot_bound`` of the real products —, not ``dot_scores``'.  A shared pool only."""
+    if index is not None:
+        return _retrieve_indexed(model, dev, users, candidates, m, exclude_history, batch_size, index, None, False)
     return _retrieve(model, dev, users, candidates, m, exclude_history, batch_size, True)
 
 

@@ -656,6 +656,36 @@ int digat_dot_shortlist(const float* users, const float* news, const int64_t* po
                         const int64_t* skip, int skip_len, int m, int64_t slab_users, float* out_scores, int64_t* out_ids,
                         int32_t* out_count, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- quantised first stage: the three inner-product entries above on int8 codes (digat_amd.nrms.build_index, recommend(index=)) ----
+ * digat_quantize_rows_i8: x [R, d] f32 -> q [R, dq] int8 and scale [R] f32, per row and symmetric: amax = max |x|,
+ * scale = amax / 127.0f, q[c] = clamp(rint(x[c] / scale), -127, 127) — fp32 divisions correctly rounded, rint to nearest even, so numpy
+ * float32 gives the same bytes —, q[d .. dq) = 0.  dq must be d rounded up to 16 (DIGAT_ERR_ARG otherwise); 0 < d <=
+ * DIGAT_QDOT_MAX_D (beyond: DIGAT_ERR_SHAPE).  scale == 0 (a zero row, an amax that underflows): codes 0.  A row with a NaN or an
+ * infinity: codes 0 and scale NaN — its scores are NaN and order last.  R == 0 returns DIGAT_OK without a launch.
+ * qu [G, dq], qn [N, dq] int8 (16-byte aligned; rows of dq bytes with zeros from d on), su [G], sn [N] f32; pool, G, N, P, skip,
+ * skip_len, k / m, slab_users, the outputs and the workspace are those of digat_dot_scores, digat_dot_topk and digat_dot_shortlist.
+ * score(g, p) = ((float)acc * su[g]) * sn[id]: acc the int32 sum over the channels of qu[g][c] * qn[id][c] (v_mfma_i32_16x16x64_i8),
+ * converted exactly (|acc| <= 127^2 d < 2^24), then two fp32 multiplications from left to right.  Its bits depend on the two code rows
+ * and the two scales alone — not on G, N, P, the pool order, the tile, or which of the three entries computed it.
+ * digat_qdot_scores stores out [G, P] (+0.0 at a position whose id is outside [0, N)); digat_qdot_topk (1 <= k <= 128) and
+ * digat_qdot_shortlist (1 <= m <= DIGAT_SHORTLIST_MAX_K) are digat_dot_topk's and digat_dot_shortlist's contracts to the letter on
+ * these scores: elements, order (topk_key descending, ties by pool position, NaNs last), skip rows, fill, count, workspace sizes
+ * (the _workspace_bytes below return what their fp32 twins return), launches and the order of the refusals, where the operand test
+ * is: null qu / su / qn / sn, negative sizes, d <= 0, pool == NULL with P != N, dq != d rounded up to 16, or codes not 16-byte
+ * aligned: DIGAT_ERR_ARG; d > DIGAT_QDOT_MAX_D or too many workgroups: DIGAT_ERR_SHAPE. */
+#define DIGAT_QDOT_MAX_D 1024
+int digat_quantize_rows_i8(const float* x, int64_t R, int d, int dq, int8_t* q, float* scale, void* stream);
+int digat_qdot_scores(const int8_t* qu, const float* su, const int8_t* qn, const float* sn, const int64_t* pool, int64_t G, int64_t N, int64_t P,
+                      int d, int dq, float* out, void* stream);
+size_t digat_qdot_topk_workspace_bytes(int64_t users, int64_t pool, int k);
+int digat_qdot_topk(const int8_t* qu, const float* su, const int8_t* qn, const float* sn, const int64_t* pool, int64_t G, int64_t N, int64_t P,
+                    int d, int dq, const int64_t* skip, int skip_len, int k, float* out_scores, int64_t* out_ids, int32_t* out_count,
+                    void* workspace, size_t workspace_bytes, void* stream);
+size_t digat_qdot_shortlist_workspace_bytes(int64_t G, int64_t P, int m, int64_t slab_users);
+int digat_qdot_shortlist(const int8_t* qu, const float* su, const int8_t* qn, const float* sn, const int64_t* pool, int64_t G, int64_t N,
+                         int64_t P, int d, int dq, const int64_t* skip, int skip_len, int m, int64_t slab_users, float* out_scores,
+                         int64_t* out_ids, int32_t* out_count, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- retrieval evaluation: the rank of given targets in a user's whole ordered pool (digat_amd.nrms.retrieval_metrics) ---------
  * users, news, pool, G, N, P, d, skip, skip_len: digat_dot_topk's, and so are the elements of user g (the pool positions whose id
  * lies in [0, N) and is not in skip[g]; repeated ids are distinct elements, skip rows may repeat ids), their scores (the bits

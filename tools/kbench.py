@@ -36,6 +36,12 @@
                                              at a time, then the selection) against torch.matmul per 1 024 users + torch.topk, G = 64
                                              and 4 096 users x 65 237 news, d = 400, m = 256 and 1 024, 50-entry skip rows, the legs in
                                              turn, median [min, max] of five rounds, time and peak device bytes
+  python tools/kbench.py qdot [news_num d]   the quantised first stage: user quantisation + evaluate.qdot_topk / qdot_shortlist at
+                                             M = 128, 256 and 1 024 + evaluate.refine_lists to k = 10 and 100, against
+                                             evaluate.dot_topk and against torch.matmul per 1 024 users + evaluate.topk_segments, G = 64
+                                             and 4 096 users x 65 237 news, d = 400, 50-entry skip rows, the legs in turn, median
+                                             [min, max] of five rounds, the parts alone, peak device bytes, the index build; then
+                                             nrms.index_report on the planted-signal corpus with fit_retriever's retriever
   python tools/kbench.py dot-rank [news_num d]   retrieval evaluation: evaluate.dot_rank (fused inner product + rank of given targets,
                                              no score matrix) against the same ranks from evaluate.dot_scores or torch.matmul over
                                              chunks of 1 024 users + torch compares and sums with the skip mask, G = 64 and 4 096
@@ -1144,6 +1150,108 @@ def bench_dot_shortlist(news_num=65238, d=400, rounds=5):
         torch.cuda.empty_cache()
 
 
+def bench_qdot(news_num=65238, d=400, rounds=5, demo=1):
+    """The quantised first stage against the two fp32 ones: user quantisation + ``evaluate.qdot_topk`` (M = 128) / ``qdot_shortlist``
+    (M = 256, 1 024) + ``evaluate.refine_lists`` to k, against ``evaluate.dot_topk`` (k = 10, 100) and against ``torch.matmul`` per
+    1 024 users + the skip positions at -inf + ``evaluate.topk_segments``; G in {4 096, 64} users x all but the PAD row of a
+    MIND-small-sized table, d = 400, 50-entry skip rows.  The legs run in turn in one process: median [min, max] of ``rounds`` rounds,
+    the parts of the quantised leg timed alone, the peak device bytes of a first call of every leg, the index build.  Then (``demo``)
+    ``nrms.index_report`` on the planted-signal corpus with the retriever ``fit_retriever``'s demonstration trains."""
+    import types
+    from digat_amd import evaluate, nrms, synthetic
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device="cpu").manual_seed(0)
+    table = torch.randn(news_num, d, generator=g).to(dev)[1:].contiguous()
+    P = news_num - 1
+    stat = lambda v: (sorted(v)[len(v) // 2], min(v), max(v))
+    fmt = lambda s: f"{s[0]:8.3f} ms [{s[1]:.3f}, {s[2]:.3f}]"
+
+    def peak(fn):
+        _lib._workspaces.clear()
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        out = fn()
+        torch.cuda.synchronize()
+        return out, torch.cuda.max_memory_allocated() - base
+    build = timeit(lambda: evaluate.quantize_rows(table), iters=5, warm=2)[0]
+    qn, sn = evaluate.quantize_rows(table)
+    print(f"qdot: P = {P} news, d = {d}, 50-entry skip rows; ms per call, median [min, max] of {rounds} rounds; index build "
+          f"(quantize_rows of the table): {build:.3f} ms, codes {qn.numel() / 2**20:.1f} MiB beside {4.0 * table.numel() / 2**20:.1f} MiB", flush=True)
+    for G in (4096, 64):
+        users = torch.randn(G, d, generator=g).to(dev)
+        skip_pos = torch.randint(1, P, (G, 50), generator=g).to(dev)
+        seg = torch.arange(0, 1025, device=dev) * P
+        for k in (10, 100):
+            exact = lambda: evaluate.dot_topk(users, table, k, skip=skip_pos)
+
+            def stock():
+                out = []
+                for g0 in range(0, G, 1024):
+                    sc = torch.matmul(users[g0:g0 + 1024], table.t())
+                    sc.scatter_(1, skip_pos[g0:g0 + 1024], float("-inf"))
+                    out.append(evaluate.topk_segments(sc.view(-1), seg[:sc.shape[0] + 1], k))
+                return out
+            want, pe = peak(exact)
+            _, ps = peak(stock)
+            for M in (128, 256, 1024):
+                if M < k:
+                    continue
+
+                def first(M=M):
+                    qu, su = evaluate.quantize_rows(users)
+                    if M <= 128:
+                        return evaluate.qdot_topk(qu, su, qn, sn, M, skip=skip_pos)
+                    return evaluate.qdot_shortlist(qu, su, qn, sn, M, skip=skip_pos)
+
+                def ours(M=M):
+                    _, ids, cnt = first(M)
+                    return evaluate.refine_lists(users, table, ids, cnt, k)
+                got, pq = peak(ours)
+                inside = float(((got[1].unsqueeze(2) == want[1].unsqueeze(1)).any(dim=1) | (want[1] < 0)).all(dim=1).float().mean())
+                legs = [[], [], []]
+                for _ in range(rounds):
+                    for leg, fn in zip(legs, (ours, exact, stock)):
+                        leg.append(timeit(fn, iters=3, warm=1)[0])
+                t_first = timeit(first, iters=3, warm=1)[0]
+                _, ids, cnt = first()
+                t_refine = timeit(lambda: evaluate.refine_lists(users, table, ids, cnt, k), iters=3, warm=1)[0]
+                qu, su = evaluate.quantize_rows(users)
+                t_scores = timeit(lambda: evaluate.qdot_scores(qu, su, qn, sn), iters=3, warm=1)[0] if G <= 1024 else float("nan")
+                a, b, c = (stat(v) for v in legs)
+                print(f"  G = {G:5d}, k = {k:3d}, M = {M:4d}: quantised + refine {fmt(a)} (first stage {t_first:.3f}, refine_lists {t_refine:.3f}, "
+                      f"qdot_scores alone {t_scores:.3f}; peak {pq / 2**20:.1f} MiB) | dot_topk {fmt(b)} (x{b[0] / a[0]:.2f}, peak {pe / 2**20:.1f} MiB) | "
+                      f"matmul + topk_segments {fmt(c)} (x{c[0] / a[0]:.2f}, peak {ps / 2**20:.1f} MiB) | users whose dot_topk list is "
+                      f"returned whole: {inside:.4f}", flush=True)
+                del got, ids, cnt
+            del want
+        del users, skip_pos
+        torch.cuda.empty_cache()
+    if not demo:
+        return
+    corpus = synthetic.make_corpus(synthetic.SynthSpec(**synthetic.PLANTED_SPEC))
+    N, H, Lw, V = corpus.spec.news_num, corpus.spec.max_history_num, 16, 4000
+    text, mask = synthetic.make_titles(N, Lw, V, seed=2)
+
+    def part(lo, hi):
+        c = synthetic.slice_impressions(corpus, lo, hi)
+        hist = torch.from_numpy(c.history.astype(np.int64)).to(dev)
+        return types.SimpleNamespace(title_text=torch.from_numpy(text).to(dev), title_mask=torch.from_numpy(mask).to(dev),
+                                     augmented_title_text=None, augmented_title_mask=None, history_ids=hist, history_mask=hist != 0,
+                                     row_candidate=c.row_candidate.astype(np.int64), row_impression=c.row_impression, row_label=c.row_label)
+    held, train = part(0, synthetic.PLANTED_DEV_IMPRESSIONS), part(synthetic.PLANTED_DEV_IMPRESSIONS, corpus.spec.impressions)
+    m = _nrms_model("NRMS", V=V, dm=64, h=8, dk=8, att=32, Lw=Lw, H=H, dropout=0.2)
+    nrms.fit_retriever(m, train, 400, batch_users=256, lr=1e-3, seed=0)
+    users = np.arange(int(held.history_ids.shape[0]))
+    print(f"  index_report: planted-signal corpus, {N - 1} news, NRMS at d = 64 after fit_retriever's 400 steps, {len(users)} held-out "
+          f"impressions, k = 10; 95 % intervals over users", flush=True)
+    for r in nrms.index_report(m, held, users, k=10, ms=(32, 64, 128, 256)):
+        iv = r["intervals"]
+        cell = lambda name: f"{r[name]:.4f} [{iv[name]['lo']:.4f}, {iv[name]['hi']:.4f}]"
+        print(f"    M = {r['m']:4d}: containment {cell('containment')}, agreement@10 {cell('agreement')}", flush=True)
+
+
 def matrix_ranks(users, table, pos, skip_pos, product, chunk=1024):
     """The ranks of ``evaluate.dot_rank`` built from what the tree had before it: per chunk of users the [chunk, P] score matrix
     (``product(users, table)``), then torch compares and sums against every target's own score with the skip mask.  ``pos`` [G, t]
@@ -1917,6 +2025,8 @@ if __name__ == "__main__":
         bench_shortlist(*nums)
     elif what == "dot-shortlist":
         bench_dot_shortlist(*nums)
+    elif what == "qdot":
+        bench_qdot(*nums)
     elif what == "dot-rank":
         bench_dot_rank(*nums)
     elif what == "pool-softmax":
