@@ -144,6 +144,10 @@ _SIGNATURES = {
     "digat_list_softmax_fwd": (C.c_int, [_f] * 5 + [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_float] + [_f] * 5),
     "digat_list_softmax_bwd": (C.c_int, [_f] * 5 + [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_float] + [_f] * 4
                                + [C.c_int64, _f, _f, _f, C.c_size_t, _f]),
+    "digat_list_pairwise_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
+    "digat_list_pairwise_fwd": (C.c_int, [_f] * 6 + [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_float] + [_f] * 6),
+    "digat_list_pairwise_scores_fwd": (C.c_int, [_f] * 4 + [C.c_int64, C.c_int, C.c_float] + [_f] * 5),
+    "digat_list_pairwise_bwd": (C.c_int, [_f] * 4 + [C.c_int64, C.c_int64, C.c_int, C.c_int, _f, _f, _f, C.c_int64, _f, _f, _f, C.c_size_t, _f]),
     "digat_mmr_select_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
     "digat_mmr_select": (C.c_int, [_f, _f, _f, C.c_int64, C.c_int, _f, C.c_int64, C.c_int, _f, C.c_int, C.c_float, C.c_float, C.c_int, _f, _f, _f,
                                    _f, C.c_size_t, _f]),

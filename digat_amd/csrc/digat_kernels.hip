@@ -888,6 +888,7 @@ int digat_row_logits(const float* news_ctx, const float* user_ctx, float* logits
 #include "digat_dot_rank.inc"
 #include "digat_pool_softmax.inc"
 #include "digat_list_softmax.inc"
+#include "digat_list_pairwise.inc"
 #include "digat_mmr.inc"
 #include "digat_listq.inc"
 #include "digat_bootstrap.inc"

@@ -48,7 +48,7 @@
 // evaluate.list_softmax_bound is this formula; tests/test_hip_list_softmax.py holds the kernels to it.
 //
 // Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage), 256 threads per workgroup:
-//   lsm_fwd_kernel     VGPRs 78   SGPRs 82   LDS 41248 B   scratch 0   occupancy 3 waves / SIMD (by LDS: the staged tile)
+//   lsm_fwd_kernel     VGPRs 86   SGPRs 71   LDS 41248 B   scratch 0   occupancy 3 waves / SIMD (by LDS: the staged tile)
 //   lsm_users_kernel   VGPRs 52   SGPRs 58   LDS 20768 B   scratch 0   occupancy 7 waves / SIMD
 //   lsm_rows_kernel    VGPRs 43   SGPRs 75   LDS 0 B   scratch 0   occupancy 8 waves / SIMD
 //
@@ -142,22 +142,17 @@ __device__ __forceinline__ void lsm_slots(const LsmArgs& a, long g, const float 
     }
 }
 
-__global__ void __launch_bounds__(256) lsm_fwd_kernel(const LsmArgs a) {
-    __shared__ float4 su4[LSM_MAX_D / 4];
-    __shared__ float4 tile4[LSM_SLAB * LSM_LD / 4];
-    __shared__ long long sid[LSM_SLAB];
-    __shared__ double red[4];
+// The scoring stage of a forward kernel (lsm_fwd_kernel; digat_list_pairwise.inc's lpw_fwd_kernel): the whole workgroup scores list g —
+// sc[s] = the chain of slot s LSM_SLAB + tid, el[s] = whether that slot is an element — and writes a.scores.  su4, tile4 and sid are the
+// caller's LDS: the user row, the staged tile and a slab's rows; the tile is free again behind the caller's next barrier.
+__device__ __forceinline__ void lsm_score_stage(const LsmArgs& a, long g, int cnt, float4* su4, float4* tile4, long long* sid,
+                                                float (&sc)[LSM_SLABS], bool (&el)[LSM_SLABS]) {
     float* const su = (float*)su4;
     float* const T = (float*)tile4;
     const int tid = threadIdx.x;
-    const long g = blockIdx.x;
-    const int cnt = lsm_count(a, g);
     const int c4 = (tid & 7) * 4, r0 = tid >> 3;                  // this thread stages rows r0 + 32 h, channels c4 .. c4 + 3
     const bool vec = (a.d & 3) == 0 && (((uintptr_t)a.rows) & 15) == 0;
     for (int c = tid; c < LSM_MAX_D; c += 256) su[c] = c < a.d ? a.users[g * a.d + c] : 0.f;
-
-    float sc[LSM_SLABS];
-    bool el[LSM_SLABS];
 #pragma unroll
     for (int s = 0; s < LSM_SLABS; ++s) {
         const int j0 = s * LSM_SLAB, j = j0 + tid;
@@ -204,6 +199,19 @@ __global__ void __launch_bounds__(256) lsm_fwd_kernel(const LsmArgs a) {
         }
         if (j < a.M) a.scores[g * a.M + j] = el[s] ? sc[s] : __uint_as_float(0x7fc00000u);
     }
+}
+
+__global__ void __launch_bounds__(256) lsm_fwd_kernel(const LsmArgs a) {
+    __shared__ float4 su4[LSM_MAX_D / 4];
+    __shared__ float4 tile4[LSM_SLAB * LSM_LD / 4];
+    __shared__ long long sid[LSM_SLAB];
+    __shared__ double red[4];
+    const int tid = threadIdx.x;
+    const long g = blockIdx.x;
+    const int cnt = lsm_count(a, g);
+    float sc[LSM_SLABS];
+    bool el[LSM_SLABS];
+    lsm_score_stage(a, g, cnt, su4, tile4, sid, sc, el);
 
     double x[LSM_SLABS], tau[LSM_SLABS];
     bool ms[LSM_SLABS];
@@ -240,12 +248,51 @@ __global__ void __launch_bounds__(256) lsm_fwd_kernel(const LsmArgs a) {
     }
 }
 
+// The gather of a users kernel (lsm_users_kernel; digat_list_pairwise.inc's lpw_users_kernel): d_users[g, :] = sum_j scoef[j] rows[sid[j], :]
+// over the slots below cnt whose sid is a row, wave w taking j = w, w + 4, .. in ascending order, lane l the channels l, l + 64, ..; the four
+// waves' sums are added in wave order.  sid, scoef and part are the caller's LDS, written and behind a barrier; valid is workgroup-uniform.
+__device__ __forceinline__ void lsm_gather_users(const LsmArgs& a, long g, int cnt, bool valid, const long long* sid, const float* scoef,
+                                                 float (*part)[LSM_MAX_D]) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float acc[LSM_DREGS];
+#pragma unroll
+    for (int i = 0; i < LSM_DREGS; ++i) acc[i] = 0.f;
+    if (valid) {                                                  // workgroup-uniform
+        for (int j0 = wave; j0 < cnt; j0 += 16) {
+            const float* row[4];
+            float cf[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int j = j0 + 4 * u;
+                const long long id = j < cnt ? sid[j] : -1;
+                row[u] = id >= 0 ? a.rows + id * a.d : nullptr;
+                cf[u] = id >= 0 ? scoef[j] : 0.f;
+            }
+#pragma unroll
+            for (int i = 0; i < LSM_DREGS; ++i) {
+                if (64 * i < a.d) {                               // workgroup-uniform
+                    const int c = lane + 64 * i;
+                    float v[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) v[u] = row[u] && c < a.d ? row[u][c] : 0.f;
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) acc[i] = fmaf(cf[u], v[u], acc[i]);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < LSM_DREGS; ++i) part[wave][lane + 64 * i] = acc[i];
+    __syncthreads();
+    for (int c = tid; c < a.d; c += 256) a.d_users[g * a.d + c] = ((part[0][c] + part[1][c]) + part[2][c]) + part[3][c];
+}
+
 __global__ void __launch_bounds__(256) lsm_users_kernel(const LsmArgs a) {
     __shared__ long long sid[LSM_MAX_M];
     __shared__ float scoef[LSM_MAX_M];
     __shared__ float part[4][LSM_MAX_D];
     __shared__ double red[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const long g = blockIdx.x;
     const int cnt = lsm_count(a, g);
     float sc[LSM_SLABS];
@@ -288,37 +335,7 @@ __global__ void __launch_bounds__(256) lsm_users_kernel(const LsmArgs a) {
     }
     __syncthreads();
 
-    float acc[LSM_DREGS];
-#pragma unroll
-    for (int i = 0; i < LSM_DREGS; ++i) acc[i] = 0.f;
-    if (valid) {                                                  // workgroup-uniform
-        for (int j0 = wave; j0 < cnt; j0 += 16) {
-            const float* row[4];
-            float cf[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int j = j0 + 4 * u;
-                const long long id = j < cnt ? sid[j] : -1;
-                row[u] = id >= 0 ? a.rows + id * a.d : nullptr;
-                cf[u] = id >= 0 ? scoef[j] : 0.f;
-            }
-#pragma unroll
-            for (int i = 0; i < LSM_DREGS; ++i) {
-                if (64 * i < a.d) {                               // workgroup-uniform
-                    const int c = lane + 64 * i;
-                    float v[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) v[u] = row[u] && c < a.d ? row[u][c] : 0.f;
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) acc[i] = fmaf(cf[u], v[u], acc[i]);
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < LSM_DREGS; ++i) part[wave][lane + 64 * i] = acc[i];
-    __syncthreads();
-    for (int c = tid; c < a.d; c += 256) a.d_users[g * a.d + c] = ((part[0][c] + part[1][c]) + part[2][c]) + part[3][c];
+    lsm_gather_users(a, g, cnt, valid, sid, scoef, part);
 }
 
 __global__ void __launch_bounds__(256) lsm_rows_kernel(const LsmArgs a) {

@@ -1245,7 +1245,373 @@ def list_softmax(users, rows, ids, count, teacher, scale=1.0, temperature=1.0):
     return loss, lse, torch.where(elem, S.detach(), S.new_full((G, M), float("nan")))
 
 
-MMR_MAX_LIST = TOPK_MAX_K     # include/digat_hip.h: digat_mmr_select takes lists of at most this many entries
+# ---- pairwise nDCG loss (LambdaRank) over a user's own list: csrc/digat_list_pairwise.inc ---------------------------------------
+def ndcg_discount(M: int, k: int = 0) -> np.ndarray:
+    """The nDCG discount table ``D(r) = 1 / log2(2 + r)`` for the 0-based ranks ``r < M``, float64 numpy [M] — zero from rank ``k`` on
+    when ``k > 0`` (nDCG@k).  Built on the host, once: the kernels and the numpy twin read the same bits."""
+    M, k = int(M), int(k)
+    if M < 0 or k < 0:
+        raise ValueError(f"M and k must not be negative, got {M} and {k}")
+    D = 1.0 / np.log2(2.0 + np.arange(M, dtype=np.float64))
+    if k > 0:
+        D[k:] = 0.0
+    return D
+
+
+def _check_discount(discount, M: int) -> np.ndarray:
+    """``discount`` (None: ``ndcg_discount(M)``) as a contiguous float64 numpy [M] table: finite, non-negative, non-increasing."""
+    if discount is None:
+        return ndcg_discount(M)
+    D = discount.cpu().numpy() if _is_tensor(discount) else np.asarray(discount)
+    if D.dtype != np.float64:
+        raise ValueError(f"discount must be a float64 table (ndcg_discount builds one), got {D.dtype}")
+    if D.shape != (M,):
+        raise ValueError(f"discount must hold one value per rank ({M}), got shape {D.shape}")
+    if not np.isfinite(D).all() or (D < 0).any() or (np.diff(D) > 0).any():
+        raise ValueError("discount must be finite, non-negative and non-increasing")
+    return np.ascontiguousarray(D)
+
+
+def _list_pairwise_host_parts(scores, ids, count, gain, rows_num, scale, discount):
+    import math
+    S = np.asarray(scores)
+    if S.ndim != 2:
+        raise ValueError("scores must be [G, M]")
+    G, M = S.shape
+    S32 = np.ascontiguousarray(S, dtype=np.float32)
+    gn = np.asarray(gain)
+    if gn.shape != (G, M) or gn.dtype.kind != "f":
+        raise ValueError(f"gain must be a floating-point array with one value per slot {(G, M)}, got {gn.shape} {gn.dtype}")
+    gn = gn.astype(np.float32)
+    D = _check_discount(discount, M)
+    cnt = np.full(G, M, dtype=np.int64) if count is None else np.asarray(count).astype(np.int64)
+    if cnt.shape != (G,):
+        raise ValueError(f"count must have one entry per list ({G}), got shape {cnt.shape}")
+    elem = np.arange(M)[None, :] < np.clip(cnt, 0, M)[:, None]
+    if ids is None:
+        elem = elem & ~np.isnan(S32)
+    else:
+        I = np.asarray(ids)
+        if I.shape != (G, M) or I.dtype.kind not in "iu":
+            raise ValueError(f"ids must be an integer array of shape {(G, M)}, got {I.shape} {I.dtype}")
+        elem = elem & (I >= 0) & (I < int(rows_num))
+    with np.errstate(invalid="ignore", over="ignore"):
+        X = (np.float32(scale) * S32).astype(np.float64)              # fl32(scale * score), widened
+    lab = elem & np.isfinite(gn) & (gn >= 0) & ~np.isnan(X)
+    sc = float(np.float32(scale))
+    loss, ndcg, valid = np.zeros(G), np.zeros(G), np.zeros(G, dtype=bool)
+    lam, absum, num = np.zeros((G, M)), np.zeros((G, M)), lab.sum(axis=1)
+    for g in range(G):
+        at = np.flatnonzero(lab[g])
+        n = len(at)
+        if n == 0:
+            continue
+        x, gv = X[g, at], gn[g, at].astype(np.float64)
+        r, t = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int64)
+        r[np.lexsort((at, -x))] = np.arange(n)                        # x descending, then slot ascending
+        t[np.lexsort((at, -gv))] = np.arange(n)
+        Dr = D[r]
+        idcg = math.fsum(gv * D[t])
+        if not idcg > 0.0:
+            continue
+        valid[g] = True
+        ndcg[g] = math.fsum(gv * Dr) / idcg
+        dG = gv[:, None] - gv[None, :]
+        up = dG > 0
+        W = np.where(up, (dG * np.abs(Dr[:, None] - Dr[None, :])) / idcg, 0.0)
+        live = W != 0
+        with np.errstate(invalid="ignore", over="ignore"):
+            T = np.where(live, x[:, None] - x[None, :], 0.0)
+            sp = np.maximum(-T, 0.0) + np.log1p(np.exp(-np.abs(T)))
+            sg = 1.0 / (1.0 + np.exp(T))
+        loss[g] = math.fsum((W * sp)[live])
+        L = np.where(live, W * sg, 0.0)
+        for a in range(n):
+            lam[g, at[a]] = sc * math.fsum(np.concatenate((-L[a, :], L[:, a])))
+            absum[g, at[a]] = abs(sc) * math.fsum(np.concatenate((L[a, :], L[:, a])))
+    return loss, ndcg, valid, lam, num, absum
+
+
+def list_pairwise_host(scores, ids, count, gain, rows_num, scale=1.0, discount=None, parts: bool = False):
+    """The contract of ``digat_list_pairwise_fwd`` on given scores ``scores`` [G, M] (slot (g, j) holds the inner product of user g
+    with row ``ids[g, j]``), in numpy float64 with ``math.fsum`` sums — the yardstick of the kernels.  Slot (g, j) is an element when
+    ``j < clip(count[g], 0, M)`` (``count`` None: M) and ``0 <= ids[g, j] < rows_num`` — or, with ``ids`` None (the contract of
+    ``digat_list_pairwise_scores_fwd``), when its score is no NaN.  ``x = fl32(scale * scores)``.  An element is labelled when its
+    ``gain`` is finite and >= 0 and x is no NaN.  Among a list's labelled elements ``r`` ranks by (x descending, slot ascending), ``t``
+    by (gain descending, slot ascending), both 0-based; ``idcg = sum gain discount[t]``, ``dcg = sum gain discount[r]``, the list is
+    valid when ``idcg > 0``, ``ndcg = dcg / idcg``.  Over the ordered pairs with ``gain_i > gain_j``:
+    ``w = ((gain_i - gain_j) |discount[r_i] - discount[r_j]|) / idcg``, ``loss = sum w sp(x_i - x_j)`` with
+    ``sp(t) = max(-t, 0) + log1p(exp(-|t|))``, and ``lambda_i = scale (-sum_{gain_i > gain_j} w_ij sg(x_i - x_j) +
+    sum_{gain_j > gain_i} w_ji sg(x_j - x_i))`` with ``sg(t) = 1 / (1 + exp(t))``; all three are 0 for an invalid list, ``lambda`` is 0
+    at every slot that is no labelled element.  Returns ``(loss [G], ndcg [G], valid [G] bool, lambda [G, M])``; with ``parts`` also
+    ``n [G]``, the labelled elements of each list, and ``A [G, M]``, lambda's ABSOLUTE sum ``|scale| sum w sg`` —
+    ``list_pairwise_bound``'s arguments."""
+    out = _list_pairwise_host_parts(scores, ids, count, gain, rows_num, scale, discount)
+    return out if parts else out[:4]
+
+
+def list_pairwise_grad_host(users, rows, scores, ids, count, gain, scale=1.0, discount=None, grad_loss=None):
+    """The contract of ``digat_list_pairwise_bwd`` in numpy float64: with ``coef = grad_loss[:, None] * lambda`` (``lambda`` of
+    ``list_pairwise_host`` on ``scores``; ``grad_loss`` None: ones), ``d_users[g] = sum_j coef[g, j] rows[ids[g, j]]`` and ``d_rows[p]``
+    = the sum of ``coef[g, j] users[g]`` over the elements with ``ids[g, j] == p``.  Returns ``(d_users [G, d], d_rows [P, d])``."""
+    U, R = np.asarray(users, dtype=np.float64), np.asarray(rows, dtype=np.float64)
+    if U.ndim != 2 or R.ndim != 2 or U.shape[1] != R.shape[1]:
+        raise ValueError(f"users [G, d] and rows [P, d] must share d, got {U.shape} and {R.shape}")
+    lam = _list_pairwise_host_parts(scores, ids, count, gain, R.shape[0], scale, discount)[3]
+    G = lam.shape[0]
+    if U.shape[0] != G:
+        raise ValueError(f"users must have one row per list ({G}), got {U.shape}")
+    gl = np.ones(G) if grad_loss is None else np.asarray(grad_loss, dtype=np.float64)
+    if gl.shape != (G,):
+        raise ValueError("grad_loss must have one entry per list")
+    coef = gl[:, None] * lam
+    I = np.asarray(ids).astype(np.int64)
+    g_of, j_of = np.nonzero(lam != 0)
+    d_users, d_rows = np.zeros_like(U), np.zeros_like(R)
+    np.add.at(d_users, g_of, coef[g_of, j_of][:, None] * R[I[g_of, j_of]])
+    np.add.at(d_rows, I[g_of, j_of], coef[g_of, j_of][:, None] * U[g_of])
+    return d_users, d_rows
+
+
+def list_pairwise_bound(n, value, absolute=None):
+    """The error bound csrc/digat_list_pairwise.inc derives for ``loss``, ``ndcg`` and ``lambda`` against ``list_pairwise_host`` on the
+    same scores: ``u |value| + c(n) 2^-53 A (1 + u) + 2^-149`` with u = 2^-24, ``c(n) = 2 n + 32`` for a list of ``n`` labelled
+    elements, and ``A = |value|`` for ``loss`` and ``ndcg`` (sums of positive terms) or lambda's absolute sum ``absolute``."""
+    u = 2.0 ** -24
+    v = np.abs(np.asarray(value, dtype=np.float64))
+    A = v if absolute is None else np.abs(np.asarray(absolute, dtype=np.float64))
+    return u * v + (2.0 * np.asarray(n, dtype=np.float64) + 32.0) * 2.0 ** -53 * A * (1.0 + u) + 2.0 ** -149
+
+
+def _check_list_pairwise_args(scores_or_users, rows, ids, count, gain):
+    """Shapes of ``list_pairwise`` (``rows`` and ``ids`` given) and of ``pairwise_scores`` (both None): ``(G, P, M, d)``."""
+    import torch
+    no_index = (torch.float16, torch.bfloat16, torch.float32, torch.float64, torch.bool)
+    if rows is None:
+        S = scores_or_users
+        if S.dim() != 2 or not S.is_floating_point():
+            raise ValueError(f"scores must be a floating-point tensor [G, M], got {tuple(S.shape)} {S.dtype}")
+        G, M, P, d = int(S.shape[0]), int(S.shape[1]), 0, 0
+    else:
+        users = scores_or_users
+        if users.dim() != 2 or rows.dim() != 2 or users.shape[1] != rows.shape[1] or users.shape[1] < 1:
+            raise ValueError(f"users [G, d] and rows [P, d] must share d >= 1, got {tuple(users.shape)} and {tuple(rows.shape)}")
+        G, d, P = int(users.shape[0]), int(users.shape[1]), int(rows.shape[0])
+        if d > LIST_SOFTMAX_MAX_D:
+            raise ValueError(f"list_pairwise takes vectors of at most LIST_SOFTMAX_MAX_D = {LIST_SOFTMAX_MAX_D} channels, got {d}")
+        if ids.dim() != 2 or ids.shape[0] != G or ids.dtype in no_index:
+            raise ValueError(f"ids must be an integer tensor [G = {G}, M], got {tuple(ids.shape)} {ids.dtype}")
+        M = int(ids.shape[1])
+    if not 1 <= M <= SHORTLIST_MAX_K:
+        raise ValueError(f"a list holds between 1 and SHORTLIST_MAX_K = {SHORTLIST_MAX_K} slots, got M = {M}")
+    if G * M >= 1 << 31:
+        raise ValueError(f"G x M must stay below 2^31, got {G} x {M}")
+    if tuple(gain.shape) != (G, M) or not gain.is_floating_point():
+        raise ValueError(f"gain must be a floating-point tensor with one value per slot {(G, M)}, got {tuple(gain.shape)} {gain.dtype}")
+    if count is not None and (tuple(count.shape) != (G,) or count.dtype in no_index):
+        raise ValueError(f"count must be an integer tensor with one entry per list ({G}), got {tuple(count.shape)} {count.dtype}")
+    return G, P, M, d
+
+
+_DISCOUNT_TABLES = {}         # (device, the table's bytes) -> the uploaded float64 table
+
+
+def _device_discount(D: np.ndarray, device):
+    import torch
+    key = (str(device), D.tobytes())
+    t = _DISCOUNT_TABLES.get(key)
+    if t is None:
+        if len(_DISCOUNT_TABLES) >= 32:
+            _DISCOUNT_TABLES.clear()
+        t = _DISCOUNT_TABLES[key] = torch.from_numpy(D.copy()).to(device)
+    return t
+
+
+def _pairwise_stock(S, elem, gain, scale, disc):
+    """The stock [G, M, M] composition on scores ``S`` [G, M] (differentiable), in their dtype: ``(loss [G], ndcg [G])``."""
+    import torch
+    G, M = int(S.shape[0]), int(S.shape[1])
+    x = float(scale) * S
+    xd = x.detach()
+    gain = gain.detach()
+    lab = elem & torch.isfinite(gain) & (gain >= 0) & ~torch.isnan(xd)
+    gv = torch.where(lab, gain, torch.zeros_like(gain)).to(S.dtype)
+    xs = torch.where(lab, xd, torch.zeros_like(xd))
+    slot = torch.arange(M, device=S.device)
+    first = (slot[None, :] < slot[:, None])[None]                                                   # [1, i, j]: j < i
+    both = lab[:, :, None] & lab[:, None, :]
+    r = (both & ((xs[:, None, :] > xs[:, :, None]) | ((xs[:, None, :] == xs[:, :, None]) & first))).sum(dim=2)
+    t = (both & ((gv[:, None, :] > gv[:, :, None]) | ((gv[:, None, :] == gv[:, :, None]) & first))).sum(dim=2)
+    Dr, Dt = disc[r], disc[t]
+    idcg, dcg = (gv * Dt * lab).sum(dim=1), (gv * Dr * lab).sum(dim=1)
+    valid = idcg > 0
+    safe = torch.where(valid, idcg, torch.ones_like(idcg))
+    dG = gv[:, :, None] - gv[:, None, :]
+    W = torch.where(both & (dG > 0) & valid[:, None, None], (dG * (Dr[:, :, None] - Dr[:, None, :]).abs()) / safe[:, None, None],
+                    torch.zeros_like(dG))
+    live = W != 0
+    xm = torch.where(lab, x, torch.zeros_like(x))                     # no gradient reaches a slot without a label
+    T = torch.where(live, xm[:, :, None] - xm[:, None, :], torch.zeros_like(W))
+    sp = torch.logaddexp(torch.zeros_like(T), -T)                    # softplus(-T); its derivative at a tie, T = 0, is the right -1/2
+    loss = torch.where(live, W * sp, torch.zeros_like(W)).sum(dim=(1, 2))
+    return loss, torch.where(valid, dcg / safe, torch.zeros_like(dcg))
+
+
+def _list_pairwise_functions():
+    import torch
+    from . import _lib
+
+    class ListPairwise(torch.autograd.Function):
+        """``digat_list_pairwise_fwd`` / ``digat_list_pairwise_bwd``; lambda is saved, and the sorted entry keys of the rows kernel are
+        built here, in the forward: the ids carry no gradient."""
+
+        @staticmethod
+        def forward(ctx, users, rows, ids, cnt, gain, disc, scale):
+            u, v = users.detach().float().contiguous(), rows.detach().float().contiguous()
+            G, M, P, d = int(u.shape[0]), int(ids.shape[1]), int(v.shape[0]), int(u.shape[1])
+            f = dict(dtype=torch.float32, device=u.device)
+            per_list, per_slot = torch.empty((2, G), **f), torch.empty((2, G, M), **f)
+            valid = torch.empty(G, dtype=torch.int32, device=u.device)
+            _lib.check(_lib.lib().digat_list_pairwise_fwd(u.data_ptr(), v.data_ptr(), ids.data_ptr(), _lib.ptr(cnt), gain.data_ptr(),
+                                                          disc.data_ptr(), G, P, M, d, float(scale), per_list[0].data_ptr(),
+                                                          per_list[1].data_ptr(), valid.data_ptr(), per_slot[0].data_ptr(),
+                                                          per_slot[1].data_ptr(), _lib.stream_ptr()), "digat_list_pairwise_fwd")
+            keys = None
+            if ctx.needs_input_grad[1]:
+                elem = list_elements(ids, cnt, P).view(-1)
+                flat = torch.arange(G * M, device=u.device)
+                keys = torch.sort(ids.view(-1)[elem] * (G * M) + flat[elem]).values.contiguous()
+            loss, ndcg, scores, lam = per_list[0], per_list[1], per_slot[0], per_slot[1]
+            ctx.save_for_backward(u, v, ids, lam)
+            ctx.cnt, ctx.keys, ctx.dtypes = cnt, keys, (users.dtype, rows.dtype)
+            ctx.mark_non_differentiable(ndcg, scores)
+            return loss, ndcg, scores
+
+        @staticmethod
+        def backward(ctx, grad_loss, _ndcg, _scores):
+            u, v, ids, lam = ctx.saved_tensors
+            G, d, P, M = int(u.shape[0]), int(u.shape[1]), int(v.shape[0]), int(ids.shape[1])
+            f = dict(dtype=torch.float32, device=u.device)
+            want_rows = ctx.needs_input_grad[1] and ctx.keys is not None
+            d_users = torch.empty((G, d), **f)
+            d_rows = torch.empty((P, d), **f) if want_rows else None
+            gl = grad_loss.float().contiguous()
+            L = _lib.lib()
+            need = int(L.digat_list_pairwise_workspace_bytes(G, M))
+            ws = _lib.workspace(need, u.device, "list_pairwise")
+            keys = ctx.keys if want_rows else None
+            _lib.check(L.digat_list_pairwise_bwd(u.data_ptr(), v.data_ptr(), ids.data_ptr(), _lib.ptr(ctx.cnt), G, P, M, d, lam.data_ptr(),
+                                                 gl.data_ptr(), _lib.ptr(keys) if keys is not None and keys.numel() else None,
+                                                 0 if keys is None else int(keys.numel()), d_users.data_ptr(), _lib.ptr(d_rows),
+                                                 ws.data_ptr(), need, _lib.stream_ptr()), "digat_list_pairwise_bwd")
+            return (d_users.to(ctx.dtypes[0]) if ctx.needs_input_grad[0] else None), (None if d_rows is None else d_rows.to(ctx.dtypes[1])), \
+                None, None, None, None, None
+
+    class PairwiseScores(torch.autograd.Function):
+        """``digat_list_pairwise_scores_fwd``; the backward is ``grad_loss[:, None] * lambda``."""
+
+        @staticmethod
+        def forward(ctx, scores, cnt, gain, disc, scale):
+            s = scores.detach().float().contiguous()
+            G, M = int(s.shape[0]), int(s.shape[1])
+            f = dict(dtype=torch.float32, device=s.device)
+            per_list, lam = torch.empty((2, G), **f), torch.empty((G, M), **f)
+            valid = torch.empty(G, dtype=torch.int32, device=s.device)
+            _lib.check(_lib.lib().digat_list_pairwise_scores_fwd(s.data_ptr(), _lib.ptr(cnt), gain.data_ptr(), disc.data_ptr(), G, M,
+                                                                 float(scale), per_list[0].data_ptr(), per_list[1].data_ptr(),
+                                                                 valid.data_ptr(), lam.data_ptr(), _lib.stream_ptr()),
+                       "digat_list_pairwise_scores_fwd")
+            loss, ndcg = per_list[0], per_list[1]
+            ctx.save_for_backward(lam)
+            ctx.dtype = scores.dtype
+            ctx.mark_non_differentiable(ndcg)
+            return loss, ndcg
+
+        @staticmethod
+        def backward(ctx, grad_loss, _ndcg):
+            lam, = ctx.saved_tensors
+            return (grad_loss.float()[:, None] * lam).to(ctx.dtype), None, None, None, None
+
+    return ListPairwise, PairwiseScores
+
+
+_ListPairwise = None
+
+
+def list_pairwise(users, rows, ids, count, gain, scale=1.0, discount=None):
+    """The pairwise nDCG loss (LambdaRank) of every user's OWN list: ``(loss [G], ndcg [G], scores [G, M])``.  ``users`` [G, d],
+    ``rows`` [P, d], ``ids`` [G, M] integer rows of ``rows`` and ``count`` [G] (None: M) as in ``list_softmax``; ``gain`` [G, M], the
+    relevance of every slot — finite and >= 0; NaN, an infinity or a negative value means "no label", and such an element takes part
+    in nothing —; ``discount`` a float64 numpy table [M] of the 0-based rank, finite, non-negative and non-increasing (None:
+    ``ndcg_discount(M)``; ``ndcg_discount(M, k)`` trains for nDCG@k).  With ``x = scale * <users[g], rows[ids[g, j]]>``, ranks among
+    the labelled elements by (x descending, slot ascending), ``idcg`` the list's best possible ``sum gain discount[rank]``: for every
+    pair with ``gain_i > gain_j`` a logistic loss ``softplus(-(x_i - x_j))`` weighted by what swapping the two would do to nDCG,
+    ``(gain_i - gain_j) |discount[r_i] - discount[r_j]| / idcg`` — a constant: no gradient flows through the ranks.  ``ndcg`` is the
+    list's nDCG under the current scores; a list with ``idcg`` 0 (no positive gain) has loss 0 and ndcg 0.  ``scores`` = the inner
+    products at elements, NaN elsewhere.  ``loss`` is differentiable in ``users`` and ``rows``; ``ndcg`` and ``scores`` are not, and
+    ``gain`` gets no gradient.  M <= ``SHORTLIST_MAX_K`` = 1024, d <= ``LIST_SOFTMAX_MAX_D`` = 512, G M < 2^31.
+
+    On CUDA tensors: ``digat_list_pairwise_fwd`` / ``_bwd`` under autograd — no [G, M, M] tensor and no [G, M, d] gather in memory, fp64
+    pair arithmetic, no float atomics: two calls give the same bits in every output and gradient; float32 outputs.  On CPU tensors: the
+    stock [G, M, M] composition in the dtype of ``users``, differentiable by autograd."""
+    import torch
+    global _ListPairwise
+    cnt = None if count is None else torch.as_tensor(count)
+    G, P, M, d = _check_list_pairwise_args(users, rows, ids, cnt, gain)
+    D = _check_discount(discount, M)
+    dev = users.device
+    if any(t.device != dev for t in (rows, ids, gain) + (() if cnt is None else (cnt,))):
+        raise ValueError("users, rows, ids, count and gain must live on one device")
+    ids = ids.to(torch.int64).contiguous()
+    gain = gain.detach()
+    if dev.type == "cuda":
+        if _ListPairwise is None:
+            _ListPairwise = _list_pairwise_functions()
+        if G == 0 or P == 0:                                          # nothing is an element: no launch, a zero gradient
+            z = users.new_zeros(G, dtype=torch.float32) + 0.0 * (users.float().sum() + rows.float().sum())
+            return z, users.new_zeros(G, dtype=torch.float32), users.new_full((G, M), float("nan"), dtype=torch.float32)
+        return _ListPairwise[0].apply(users, rows, ids, None if cnt is None else cnt.to(torch.int32).contiguous(), gain.float().contiguous(),
+                                      _device_discount(D, dev), float(scale))
+    elem = list_elements(ids, cnt, P)
+    gathered = rows.index_select(0, torch.where(elem, ids, torch.zeros_like(ids)).view(-1)).view(G, M, d)        # [G, M, d]
+    S = torch.bmm(gathered, users.unsqueeze(2)).squeeze(2)
+    loss, ndcg = _pairwise_stock(S, elem, gain, scale, torch.from_numpy(D).to(S.dtype))
+    return loss, ndcg.detach(), torch.where(elem, S.detach(), S.new_full((G, M), float("nan")))
+
+
+def pairwise_scores(scores, count, gain, scale=1.0, discount=None):
+    """``list_pairwise``'s loss on GIVEN scores ``scores`` [G, M] — a model whose score is no inner product, through autograd on its own
+    logits: ``(loss [G], ndcg [G])``.  A slot is an element when ``j < clip(count[g], 0, M)`` (``count`` None: M) and its score is no
+    NaN; ``gain``, ``scale`` and ``discount`` as in ``list_pairwise``.  ``loss`` is differentiable in ``scores`` — its gradient is
+    ``grad_loss[:, None] * lambda``, exactly 0 at every slot that is no labelled element —; ``ndcg`` is not.  On CUDA tensors
+    ``digat_list_pairwise_scores_fwd`` (the pair stage of ``list_pairwise``: the same bits on the same scores); on CPU tensors the
+    stock [G, M, M] composition in the dtype of ``scores``."""
+    import torch
+    global _ListPairwise
+    cnt = None if count is None else torch.as_tensor(count)
+    G, _, M, _ = _check_list_pairwise_args(scores, None, None, cnt, gain)
+    D = _check_discount(discount, M)
+    dev = scores.device
+    if gain.device != dev or (cnt is not None and cnt.device != dev):
+        raise ValueError("scores, count and gain must live on one device")
+    gain = gain.detach()
+    if dev.type == "cuda":
+        if _ListPairwise is None:
+            _ListPairwise = _list_pairwise_functions()
+        if G == 0:
+            z = scores.new_zeros(0, dtype=torch.float32) + 0.0 * scores.float().sum()
+            return z, scores.new_zeros(0, dtype=torch.float32)
+        return _ListPairwise[1].apply(scores, None if cnt is None else cnt.to(torch.int32).contiguous(), gain.float().contiguous(),
+                                      _device_discount(D, dev), float(scale))
+    slot = torch.arange(M, device=dev)
+    elem = ~torch.isnan(scores.detach())
+    if cnt is not None:
+        elem = elem & (slot[None, :] < cnt.to(torch.int64).clamp(0, M)[:, None])
+    loss, ndcg = _pairwise_stock(torch.where(elem, scores, torch.zeros_like(scores)), elem, gain, scale, torch.from_numpy(D).to(scores.dtype))
+    return loss, ndcg.detach()
+
+
+MMR_MAX_LIST = TOPK_MAX_K    # include/digat_hip.h: digat_mmr_select takes lists of at most this many entries
 
 
 def mmr_weights(lam):

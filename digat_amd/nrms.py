@@ -1009,21 +1009,13 @@ def _check_lists(users, ids, teacher, count, rows):
     return users.astype(np.int64), ids.astype(np.int64), teacher.astype(np.float32), count.astype(np.int64)
 
 
-def distil_step(model, train, users, ids, teacher, count=None, scale=1.0, temperature=1.0):
-    """One listwise step's loss for the first stage, with its graph — ``retrieval_step``'s twin over per-user lists: for every user of
-    ``users`` (impression indices of ``train``) the KL divergence of ``softmax(teacher / temperature)`` from the model's
-    ``softmax(scale * <user, news>)`` over the user's OWN list ``ids[g, :count[g]]`` (``evaluate.list_softmax``), summed over the valid
-    lists — those with an element and an element whose teacher value is finite — and divided by their number (by 1 when there is
-    none).  ``ids`` [G, M], ``count`` [G] (None: M) and ``teacher`` [G, M] are what ``shortlist`` and ``util.score_lists`` return; an
-    id outside the corpus is no element, ``-inf`` (and ``+inf``, NaN) in ``teacher`` means no target mass.  The distinct ids of the
+def _list_front(model, train, idx, ids, count):
+    """The front half of a step over per-user lists (``distil_step``, ``rank_step``), on checked host arrays: the distinct ids of the
     batch's lists form a compact pool whose titles go through ``model.news_encoder`` WITH gradients — the augmented titles too for
     NRMS-SA — into a [P, d] table; histories go through ``model.user_encoder`` on their title texts; list ids are mapped to pool
-    positions.  The model's mode (dropout) is the caller's.  On CUDA tensors ``digat_list_softmax_fwd`` / ``_bwd`` on the HIP encoders;
-    on CPU tensors ``forward_stock`` and the stock composition."""
-    from . import evaluate
+    positions.  Returns ``(user [G, d], table [P, d], pos [G, M] int64 (-1: no element), count [G] int32, elem [G, M] numpy bool)``."""
     N = int(train.title_text.shape[0])
     device = train.title_text.device
-    idx, ids, teacher, count = _check_lists(users, ids, teacher, count, int(train.history_ids.shape[0]))
     M = ids.shape[1]
     elem = (np.arange(M)[None, :] < np.clip(count, 0, M)[:, None]) & (ids >= 0) & (ids < N)
     pl = np.unique(ids[elem])
@@ -1043,9 +1035,26 @@ def distil_step(model, train, users, ids, teacher, count=None, scale=1.0, temper
     at = torch.from_numpy(idx).to(device)
     hist, mask = train.history_ids.index_select(0, at).to(torch.int64), train.history_mask.index_select(0, at)
     user = (ue if cuda else ue.forward_stock)(train.title_text[hist], train.title_mask[hist], mask)    # [G, d]
-    tch = torch.from_numpy(teacher).to(device)
-    loss, _, _ = evaluate.list_softmax(user, table, torch.from_numpy(pos).to(device), torch.from_numpy(count.clip(0, M).astype(np.int32)).to(device),
-                                       tch if cuda else tch.to(user.dtype), scale=scale, temperature=temperature)
+    return user, table, torch.from_numpy(pos).to(device), torch.from_numpy(count.clip(0, M).astype(np.int32)).to(device), elem
+
+
+def distil_step(model, train, users, ids, teacher, count=None, scale=1.0, temperature=1.0):
+    """One listwise step's loss for the first stage, with its graph — ``retrieval_step``'s twin over per-user lists: for every user of
+    ``users`` (impression indices of ``train``) the KL divergence of ``softmax(teacher / temperature)`` from the model's
+    ``softmax(scale * <user, news>)`` over the user's OWN list ``ids[g, :count[g]]`` (``evaluate.list_softmax``), summed over the valid
+    lists — those with an element and an element whose teacher value is finite — and divided by their number (by 1 when there is
+    none).  ``ids`` [G, M], ``count`` [G] (None: M) and ``teacher`` [G, M] are what ``shortlist`` and ``util.score_lists`` return; an
+    id outside the corpus is no element, ``-inf`` (and ``+inf``, NaN) in ``teacher`` means no target mass.  The distinct ids of the
+    batch's lists form a compact pool whose titles go through ``model.news_encoder`` WITH gradients — the augmented titles too for
+    NRMS-SA — into a [P, d] table; histories go through ``model.user_encoder`` on their title texts; list ids are mapped to pool
+    positions.  The model's mode (dropout) is the caller's.  On CUDA tensors ``digat_list_softmax_fwd`` / ``_bwd`` on the HIP encoders;
+    on CPU tensors ``forward_stock`` and the stock composition."""
+    from . import evaluate
+    idx, ids, teacher, count = _check_lists(users, ids, teacher, count, int(train.history_ids.shape[0]))
+    user, table, pos, cnt, elem = _list_front(model, train, idx, ids, count)
+    cuda = user.device.type == "cuda"
+    tch = torch.from_numpy(teacher).to(user.device)
+    loss, _, _ = evaluate.list_softmax(user, table, pos, cnt, tch if cuda else tch.to(user.dtype), scale=scale, temperature=temperature)
     valid = int((elem & np.isfinite(teacher)).any(axis=1).sum())
     return loss.sum() / max(valid, 1)
 
@@ -1104,6 +1113,61 @@ def impression_lists(train, users=None):
     ids[slot] = cand[rows]
     teacher[slot] = np.where(label[rows] == 1, 0.0, -np.inf).astype(np.float32)
     return idx, ids, teacher, n.astype(np.int32)
+
+
+# ---- training for the metric the evaluation prints: the pairwise nDCG loss over per-user lists ----------------------------------
+def rank_step(model, train, users, ids, gain, count=None, scale=1.0, k=0):
+    """One pairwise-nDCG step's loss for the first stage, with its graph — ``distil_step``'s twin on ``evaluate.list_pairwise``: for
+    every user of ``users`` (impression indices of ``train``) the LambdaRank loss of the model's scores ``scale * <user, news>`` over
+    the user's OWN list ``ids[g, :count[g]]`` against the relevance ``gain`` [G, M] (finite and >= 0; NaN, an infinity or a negative
+    value: no label), with the discount ``evaluate.ndcg_discount(M, k)`` — ``k`` > 0 trains for nDCG@k —, summed over the valid lists —
+    those with a labelled element of positive gain — and divided by their number (by 1 when there is none).  The compact pool, the
+    encoders and the devices are ``distil_step``'s.  The model's mode (dropout) is the caller's."""
+    from . import evaluate
+    idx, ids, gain, count = _check_lists(users, ids, gain, count, int(train.history_ids.shape[0]))
+    user, table, pos, cnt, elem = _list_front(model, train, idx, ids, count)
+    cuda = user.device.type == "cuda"
+    gn = torch.from_numpy(gain).to(user.device)
+    D = evaluate.ndcg_discount(ids.shape[1], k)
+    loss, _, _ = evaluate.list_pairwise(user, table, pos, cnt, gn if cuda else gn.to(user.dtype), scale=scale, discount=D)
+    with np.errstate(invalid="ignore"):
+        valid = int((elem & np.isfinite(gain) & (gain > 0)).any(axis=1).sum()) if len(D) and D[0] > 0 else 0
+    return loss.sum() / max(valid, 1)
+
+
+def fit_ranker(model, train, lists, steps, batch_users=64, lr=1e-4, seed=0, scale=1.0, k=0, optimizer=None):
+    """Train ``model`` for the nDCG the evaluation prints: ``distil_retriever``'s loop on ``rank_step`` — ``steps`` times one step on a
+    seeded draw of ``batch_users`` of the given lists (the same draws as ``distil_retriever``'s for the same ``seed`` and number of
+    lists), one backward and one optimizer step, in train mode.  ``lists = (users [U], ids [U, M], gain [U, M], count [U] or None)``:
+    ``impression_gain_lists`` for click gains on whole impressions, or graded gains from a teacher's scores.  ``optimizer``:
+    ``fit_retriever``'s choice.  Returns the per-step losses as Python floats."""
+    if not (isinstance(lists, (tuple, list)) and len(lists) == 4):
+        raise ValueError("lists must be (users [U], ids [U, M], gain [U, M], count [U] or None)")
+    users, ids, gain, count = _check_lists(*lists[:3], lists[3], int(train.history_ids.shape[0]))
+    if len(users) == 0:
+        raise ValueError("no list to train on")
+    optimizer = _retriever_optimizer(model, lr, optimizer)
+    rng = np.random.default_rng(seed)
+    model.train()
+    losses = []
+    for _ in range(int(steps)):
+        b = np.sort(rng.choice(len(users), size=min(int(batch_users), len(users)), replace=False))
+        optimizer.zero_grad()
+        loss = rank_step(model, train, users[b], ids[b], gain[b], count[b], scale=scale, k=k)
+        loss.backward()
+        optimizer.step()
+        losses.append(float(loss.detach()))
+    return losses
+
+
+def impression_gain_lists(train, users=None):
+    """``impression_lists`` with relevance gains in place of the teacher: ``(users [U] int64, ids [U, M] int64, gain [U, M] float32,
+    count [U] int32)`` — ``gain`` 1.0 at clicked rows, 0.0 at the impression's other rows and NaN (no label) beyond ``count``: through
+    ``fit_ranker`` the pairwise nDCG loss over whole impressions."""
+    idx, ids, teacher, n = impression_lists(train, users)
+    slot = np.arange(ids.shape[1])[None, :] < n[:, None]
+    gain = np.where(slot, np.where(teacher == 0, 1.0, 0.0), np.nan).astype(np.float32)
+    return idx, ids, gain, n
 
 
 def teacher_agreement(student_ids, student_count, teacher_ids, teacher_count, ks=(10,)):

@@ -775,6 +775,42 @@ int digat_list_softmax_bwd(const float* users, const float* rows, const int64_t*
                            const float* grad_loss, const int64_t* entry_keys, int64_t E, float* d_users, float* d_rows, void* workspace,
                            size_t workspace_bytes, void* stream);
 
+/* ---- pairwise nDCG loss (LambdaRank) over a user's own list (digat_amd.evaluate.list_pairwise / pairwise_scores) ------------------
+ * users [G, d] f32, rows [P, d] f32, ids [G, M] int64, count [G] int32 (NULL: M), gain [G, M] f32, discount [M] f64 (the CALLER's table
+ * D(rank): evaluate.ndcg_discount — the kernels take no logarithm for it), scale.  Elements and score(g, j) are digat_list_softmax_fwd's;
+ * x = fl32(scale * score), widened to double.  digat_list_pairwise_scores_fwd takes scores [G, M] f32 as given, with no users, rows or
+ * ids: a slot is an element when j < clamp(count[g], 0, M) and its score is no NaN.  An element is LABELLED when its gain is finite
+ * and >= 0 and its x is no NaN; anything else takes part in nothing.  Among the labelled elements r_i = how many order before i under
+ * (x descending, slot ascending), t_i = the same under (gain descending, slot ascending).  idcg = sum gain_i discount[t_i],
+ * dcg = sum gain_i discount[r_i]; out_valid [G] = idcg > 0, out_ndcg [G] = dcg / idcg.  For every ordered pair of labelled elements
+ * with gain_i > gain_j: w_ij = ((gain_i - gain_j) |discount[r_i] - discount[r_j]|) / idcg — a constant — and, with t = x_i - x_j,
+ *   out_loss [G]      = sum_pairs w_ij (max(-t, 0) + log1p(exp(-|t|)))
+ *   out_lambda [G, M] = scale (- sum_{j: gain_i > gain_j} w_ij / (1 + exp(x_i - x_j)) + sum_{j: gain_j > gain_i} w_ji / (1 + exp(x_j - x_i)))
+ * = d loss[g] / d score(g, i).  loss, ndcg and lambda are 0 for an invalid list, lambda is exactly 0 at every slot that is no labelled
+ * element; out_scores [G, M] = the score bits at elements, a NaN elsewhere.  Every output byte is written whatever count holds.  All
+ * pair arithmetic and all sums run in fp64, in an order fixed by M, count, ids and gain, and are rounded to fp32 once; a list's outputs
+ * depend on that list alone; the two forward entries give the same bits when the second is fed the first's out_scores.
+ * Backward, given the forward's lambda [G, M] and grad_loss [G]: coef(g, j) = fl32(grad_loss[g] lambda[g, j]) at elements, 0 elsewhere
+ * (written to the workspace); d_users [G, d] and d_rows [P, d] are digat_list_softmax_bwd's two sums over coef, in its order, with its
+ * entry_keys [E] (the caller's sorted ids[g, j] (G M) + (g M + j) of all E elements); d_rows == NULL skips that launch and needs no
+ * keys.  Every byte of d_users and of a given d_rows is written.  No floating-point atomics: two calls give the same bits.
+ * DIGAT_ERR_ARG: a null required pointer (count; rows when P == 0; d_rows; entry_keys without d_rows or with E == 0 may be NULL), G < 0, P < 0, E outside
+ * [0, G M], a workspace that is not 4-byte aligned; DIGAT_ERR_SHAPE: M outside [1, DIGAT_SHORTLIST_MAX_K], d outside
+ * [1, DIGAT_LIST_SOFTMAX_MAX_D], G M >= 2^31, P > 2^31; DIGAT_ERR_WORKSPACE: a short workspace — all before any launch.  G == 0
+ * launches nothing forward; P == 0 leaves every slot without an element.  Workspace (backward only; it may hold anything on entry):
+ * 4 G M bytes rounded up to 256; 0 for a negative argument.
+ * Stream-ordered: one launch forward (one workgroup per list), two backward; no allocation, no host synchronisation, no read of device
+ * memory on the host. */
+size_t digat_list_pairwise_workspace_bytes(int64_t lists, int m);
+int digat_list_pairwise_fwd(const float* users, const float* rows, const int64_t* ids, const int32_t* count, const float* gain,
+                            const double* discount, int64_t G, int64_t P, int M, int d, float scale, float* out_loss, float* out_ndcg,
+                            int32_t* out_valid, float* out_scores, float* out_lambda, void* stream);
+int digat_list_pairwise_scores_fwd(const float* scores, const int32_t* count, const float* gain, const double* discount, int64_t G, int M,
+                                   float scale, float* out_loss, float* out_ndcg, int32_t* out_valid, float* out_lambda, void* stream);
+int digat_list_pairwise_bwd(const float* users, const float* rows, const int64_t* ids, const int32_t* count, int64_t G, int64_t P, int M, int d,
+                            const float* lambda, const float* grad_loss, const int64_t* entry_keys, int64_t E, float* d_users, float* d_rows,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- diversified top-k: greedy maximal-marginal-relevance selection over a short list (digat_amd.evaluate.mmr_select) ---------
  * Per user g a list: ids [G, M] int64, scores [G, M] f32, count [G] int32 (the entries in use, held inside [0, M]; NULL: M) — the
  * triple digat_topk_segments and digat_dot_topk write.  vectors [N, d] f32, rows taken as they are (callers pass unit rows).

@@ -55,6 +55,7 @@
                                              median [min, max] of five rounds, time and peak device bytes; then nrms.fit_retriever on
                                              the planted-signal corpus: nrms.retrieval_metrics before and after
   python tools/kbench.py list-softmax [d]    listwise distillation: evaluate.list_softmax (fused per-user list softmax, no [G, M, d] gather)
+  python tools/kbench.py list-pairwise [d]   pairwise nDCG loss: evaluate.list_pairwise (fused LambdaRank over per-user lists, no [G, M, M] tensor)
                                              against the stock composition — index_select, torch.bmm, log_softmax, KL, autograd —,
                                              G = 64 and 4 096 lists of M = 128 and 1 024 over a compact pool, d = 400, forward and
                                              forward + backward, the legs in turn, median [min, max] of five rounds, time and peak
@@ -1605,6 +1606,174 @@ def demo_distil(train_users=2048, held_users=1024, m=256, steps=300, temperature
     report("after")
 
 
+def stock_list_pairwise(users, rows, ids, count, gain, disc, backward=False, budget=1 << 30):
+    """The summed loss of ``evaluate.list_pairwise`` from stock PyTorch under autograd, the lists in chunks whose [g, M, M] float32
+    intermediates hold ``budget`` bytes each: ``index_select`` + ``torch.bmm``, ranks from a stable ``argsort``, the [g, M, M]
+    differences of scores, gains and discounts, ``softplus``.  ``backward``: every chunk's loss is differentiated as soon as it
+    stands, so that one chunk's graph lives at a time.  Every id is a row and every gain finite and >= 0 in the benchmark's data."""
+    G, M = ids.shape
+    step = max(1, budget // (4 * M * M))
+    slot = torch.arange(M, device=ids.device)
+    total = torch.zeros((), device=ids.device)
+    for lo in range(0, G, step):
+        sl = slice(lo, lo + step)
+        g = ids[sl].shape[0]
+        x = torch.bmm(rows.index_select(0, ids[sl].reshape(-1)).view(g, M, -1), users[sl].unsqueeze(2)).squeeze(2)
+        with torch.no_grad():
+            out = slot[None, :] >= count[sl][:, None]
+            order = torch.argsort(x.masked_fill(out, float("-inf")), dim=1, descending=True, stable=True)
+            r = torch.empty_like(order).scatter_(1, order, slot[None, :].expand(g, M))
+            gn = gain[sl].masked_fill(out, 0.0)
+            Dr = disc[r].masked_fill(out, 0.0)
+            idcg = (torch.sort(gn, dim=1, descending=True).values * disc[None, :]).sum(dim=1).clamp(min=1e-30)
+            W = torch.relu(gn[:, :, None] - gn[:, None, :]) * (Dr[:, :, None] - Dr[:, None, :]).abs() / idcg[:, None, None]
+            W = W.masked_fill(out[:, :, None] | out[:, None, :], 0.0)
+        loss = (W * torch.nn.functional.softplus(-(x[:, :, None] - x[:, None, :]))).sum()
+        if backward:
+            loss.backward()
+        total = total + loss.detach()
+    return total
+
+
+def bench_list_pairwise(d=400, rounds=5, demo=1):
+    """``evaluate.list_pairwise`` (the fused pairwise nDCG loss and its gradients: no [G, M, M] tensor, no [G, M, d] gather, fp64 pair
+    arithmetic, no float atomics) against ``stock_list_pairwise`` (float32, chunked to 1 GiB intermediates) under autograd, in one
+    process, the legs taken in turn, median [min, max] of ``rounds`` rounds of three calls, and each leg's peak of device bytes beyond
+    its inputs; forward alone (``no_grad``) and forward + backward; click gains (one to three ones a list) and all-distinct gains
+    (every pair live).  The pool is compact, as in ``bench_list_softmax``.  Then (``demo``) ``demo_rank``."""
+    from digat_amd import evaluate
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device="cpu").manual_seed(0)
+    stat = lambda v: (sorted(v)[len(v) // 2], min(v), max(v))
+
+    def peak(fn):
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        out = fn()
+        torch.cuda.synchronize()
+        out = float(out)
+        return out, torch.cuda.max_memory_allocated() - base
+    print(f"list-pairwise: d = {d}, compact pool, full discount; ms per call, median [min, max] of {rounds} rounds", flush=True)
+    for G in (64, 4096):
+        for M in (128, 1024):
+            P = max(M, min(65237, G * M // 4))
+            rows = (torch.randn(P, d, generator=g) / d ** 0.5).to(dev)
+            users = (3.0 * torch.randn(G, d, generator=g)).to(dev)
+            ids = torch.stack([torch.randperm(P, generator=g)[:M] for _ in range(G)]).to(dev)
+            count = torch.randint(M // 2, M + 1, (G,), generator=g).to(torch.int32).to(dev)
+            D = evaluate.ndcg_discount(M)
+            disc = torch.from_numpy(D).float().to(dev)
+            clicks = torch.zeros(G, M)
+            for row in clicks:
+                row[torch.randperm(M // 2, generator=g)[:int(torch.randint(1, 4, (1,), generator=g))]] = 1.0
+            distinct = torch.stack([torch.randperm(M, generator=g).float() for _ in range(G)]) * 0.25
+            for tag, gain in (("click gains", clicks.to(dev)), ("distinct gains", distinct.to(dev))):
+                def fused_fwd():
+                    with torch.no_grad():
+                        return evaluate.list_pairwise(users, rows, ids, count, gain, discount=D)[0].sum()
+
+                def stock_fwd():
+                    with torch.no_grad():
+                        return stock_list_pairwise(users, rows, ids, count, gain, disc)
+
+                def fused_both():
+                    u, t = users.detach().requires_grad_(True), rows.detach().requires_grad_(True)
+                    loss = evaluate.list_pairwise(u, t, ids, count, gain, discount=D)[0].sum()
+                    loss.backward()
+                    return loss.detach() + 0.0 * (u.grad[0, 0] + t.grad[0, 0])
+
+                def stock_both():
+                    u, t = users.detach().requires_grad_(True), rows.detach().requires_grad_(True)
+                    loss = stock_list_pairwise(u, t, ids, count, gain, disc, backward=True)
+                    return loss + 0.0 * (u.grad[0, 0] + t.grad[0, 0])
+                legs = (fused_fwd, stock_fwd, fused_both, stock_both)
+                peaks = [peak(fn) for fn in legs]
+                times = [[] for _ in legs]
+                for _ in range(rounds):
+                    for leg, fn in zip(times, legs):
+                        leg.append(timeit(fn, iters=3, warm=1)[0])
+                (a, alo, ahi), (b, blo, bhi), (c, clo, chi), (e, elo, ehi) = (stat(t) for t in times)
+                print(f"  G = {G:5d}, M = {M:4d}, P = {P:5d}, {tag}: forward: list_pairwise {a:8.3f} ms [{alo:.3f}, {ahi:.3f}] (peak "
+                      f"{peaks[0][1] / 2**20:.2f} MiB) | stock {b:8.3f} ms [{blo:.3f}, {bhi:.3f}] (x{b / a:.2f}, peak {peaks[1][1] / 2**20:.1f} MiB) || "
+                      f"forward + backward: list_pairwise {c:8.3f} ms [{clo:.3f}, {chi:.3f}] (peak {peaks[2][1] / 2**20:.1f} MiB) | stock {e:8.3f} ms "
+                      f"[{elo:.3f}, {ehi:.3f}] (x{e / c:.2f}, peak {peaks[3][1] / 2**20:.1f} MiB) | summed loss {peaks[0][0]:.3f} vs stock "
+                      f"{peaks[1][0]:.3f}", flush=True)
+            del rows, users, ids, count, clicks, distinct
+            torch.cuda.empty_cache()
+    if demo:
+        demo_rank()
+
+
+def demo_rank(train_users=2048, steps=300, k=10, replicates=2000):
+    """The demonstration run of the pairwise nDCG loss: on the planted-signal corpus two copies of one NRMS at d = 64 (random titles)
+    are trained on the whole impressions of ``train_users`` training users with the same seeded draws, steps and learning rate — one
+    by ``nrms.fit_ranker`` on ``impression_gain_lists`` (click gains, nDCG@``k`` weights), one by ``nrms.distil_retriever`` on
+    ``impression_lists`` (the listwise click softmax).  Both score the held-out impressions with ``nrms.compute_scores``;
+    ``evaluate.compare_metrics`` gives the paired intervals of the per-impression AUC, MRR, nDCG@5 and nDCG@10.  The mean nDCG@``k``
+    of the training lists themselves, before and after, says whether the steps fit what they were given."""
+    import copy
+    import time
+    import types
+    from digat_amd import evaluate, nrms, synthetic
+    dev = torch.device("cuda:0")
+    corpus = synthetic.make_corpus(synthetic.SynthSpec(**synthetic.PLANTED_SPEC))
+    spec = corpus.spec
+    N, H, Lw, V = spec.news_num, spec.max_history_num, 16, 4000
+    text, mask = synthetic.make_titles(N, Lw, V, seed=2)
+
+    def part(lo, hi):
+        c = synthetic.slice_impressions(corpus, lo, hi)
+        hist = torch.from_numpy(c.history.astype(np.int64)).to(dev)
+        return types.SimpleNamespace(title_text=torch.from_numpy(text).to(dev), title_mask=torch.from_numpy(mask).to(dev),
+                                     augmented_title_text=None, augmented_title_mask=None, history_ids=hist, history_mask=hist != 0,
+                                     row_candidate=c.row_candidate.astype(np.int64), row_impression=c.row_impression, row_label=c.row_label)
+    held, train = part(0, synthetic.PLANTED_DEV_IMPRESSIONS), part(synthetic.PLANTED_DEV_IMPRESSIONS, spec.impressions)
+    ranker = _nrms_model("NRMS", V=V, dm=64, h=8, dk=8, att=32, Lw=Lw, H=H, dropout=0.2)
+    softmax = copy.deepcopy(ranker)
+    tu = np.arange(train_users, dtype=np.int64)
+    gains, clicks = nrms.impression_gain_lists(train, tu), nrms.impression_lists(train, tu)
+    labels = np.asarray(held.row_label)
+
+    def rows_of(model):
+        scores, _, metrics = nrms.compute_scores(model, held)
+        return evaluate.impression_metrics(scores, held.row_impression, labels), metrics
+    print(f"ranking demo: planted-signal corpus, {N - 1} news; NRMS at d = 64, random titles; {len(gains[0])} training impressions of up to "
+          f"{gains[1].shape[1]} candidates; held-out: {int(held.history_ids.shape[0])} impressions", flush=True)
+    def train_ndcg(model):
+        """The mean nDCG@k of the TRAINING lists under the model's scores, in eval mode: ``list_pairwise``'s own second output."""
+        model.eval()
+        idx, ids, gain, count = nrms._check_lists(*gains[:3], gains[3], int(train.history_ids.shape[0]))
+        total = 0.0
+        with torch.no_grad():
+            for lo in range(0, len(idx), 256):
+                sl = slice(lo, lo + 256)
+                user, table, pos, cnt, _ = nrms._list_front(model, train, idx[sl], ids[sl], count[sl])
+                total += float(evaluate.list_pairwise(user, table, pos, cnt, torch.from_numpy(gain[sl]).to(dev),
+                                                      discount=evaluate.ndcg_discount(ids.shape[1], k))[1].sum())
+        return total / len(idx)
+    print("  before: AUC %.4f MRR %.4f nDCG@5 %.4f nDCG@10 %.4f" % rows_of(ranker)[1] + f"; training lists: nDCG@{k} {train_ndcg(ranker):.4f}", flush=True)
+    t0 = time.perf_counter()
+    l_rank = nrms.fit_ranker(ranker, train, gains, steps, batch_users=64, lr=1e-3, seed=0, k=k)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    l_soft = nrms.distil_retriever(softmax, train, clicks, steps, batch_users=64, lr=1e-3, seed=0)
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    print(f"  fit_ranker (k = {k}): {steps} steps of 64 lists, lr 1e-3: {1e3 * (t1 - t0) / steps:.1f} ms per step, loss {np.mean(l_rank[:10]):.4f} "
+          f"(first ten steps) -> {np.mean(l_rank[-10:]):.4f} (last ten); distil_retriever on impression_lists: {1e3 * (t2 - t1) / steps:.1f} ms "
+          f"per step, loss {np.mean(l_soft[:10]):.4f} -> {np.mean(l_soft[-10:]):.4f}", flush=True)
+    (ra, ma), (rb, mb) = rows_of(ranker), rows_of(softmax)
+    print("  after fit_ranker:        AUC %.4f MRR %.4f nDCG@5 %.4f nDCG@10 %.4f" % ma + f"; training lists: nDCG@{k} {train_ndcg(ranker):.4f}", flush=True)
+    print("  after the click softmax: AUC %.4f MRR %.4f nDCG@5 %.4f nDCG@10 %.4f" % mb + f"; training lists: nDCG@{k} {train_ndcg(softmax):.4f}", flush=True)
+    cmp_ = evaluate.compare_metrics(ra, rb, names=("AUC", "MRR", "nDCG@5", "nDCG@10"), replicates=replicates)
+    for name in ("MRR", "nDCG@10"):
+        f = cmp_[name]
+        print(f"  {name}: fit_ranker - click softmax = {f['diff']:+.4f} [{f['lo']:+.4f}, {f['hi']:+.4f}], p = {f['p']:.4f}, wins {f['wins']:.3f} "
+              f"({replicates} paired replicates over impressions)", flush=True)
+
+
 def torch_mmr(ids, scores, count, vectors, k, lam, category=None, q=0):
     """Greedy maximal-marginal relevance built only from stock PyTorch: gather, ``torch.bmm``, then k rounds of element-wise ops and
     arg-max over all lists at once.  Every id is taken to lie in the table; NaN scores and the order among tied values are not the
@@ -2033,6 +2202,8 @@ if __name__ == "__main__":
         bench_pool_softmax(*nums)
     elif what == "list-softmax":
         bench_list_softmax(*nums)
+    elif what == "list-pairwise":
+        bench_list_pairwise(*nums)
     elif what == "diversify":
         bench_diversify(*nums)
     elif what == "list-quality":
