@@ -9,6 +9,7 @@ real MIND cannot be downloaded, so the default corpus is synthetic (``--syntheti
 ``--recommend_diversity`` (with ``--recommend_shortlist``, ``--recommend_max_per_category``) likewise: attributes only when it is given;
 ``--recommend_report`` (a tuple of diversities; it brings the other two with it as well) likewise;
 ``--recommend_calibration`` (with ``--recommend_shortlist``, here up to 1024) likewise;
+``--recommend_sample`` (a temperature; with ``--recommend_seed`` and ``--recommend_shortlist``, here up to 1024) likewise;
 ``--bootstrap`` (with ``--bootstrap_level``, ``--compare_model_path``) likewise;
 ``--local_rank`` also accepts torch >= 2.0's ``--local-rank`` spelling and the ``LOCAL_RANK`` variable.
 """
@@ -46,6 +47,11 @@ class Config:
         p.add_argument('--recommend_calibration', type=float, default=None,
                        help="--mode recommend: pick the k from a shortlist so that the list keeps the category mix of the reader's history, "
                             'lam = 1 - this value (0..1; default: off; needs a corpus with categories; not with --recommend_diversity)')
+        p.add_argument('--recommend_sample', type=float, default=None,
+                       help='--mode recommend: DRAW the k from a shortlist (recommend_k..1024; 0: min(1024, 8 * recommend_k)) — one Plackett-Luce '
+                            'slate from softmax(score / this temperature) (> 0; default: off; not with --recommend_diversity, '
+                            '--recommend_calibration or --recommend_report)')
+        p.add_argument('--recommend_seed', type=int, default=0, help='with --recommend_sample: the seed of the draws')
         p.add_argument('--recommend_report', type=str, default=None,
                        help='--mode recommend: diversities "0,0.1,0.3" to report list quality for (one scoring pass; honours --recommend_k, '
                             '--recommend_shortlist, --recommend_max_per_category)')
@@ -116,8 +122,16 @@ class Config:
             p.error('--recommend_calibration must lie in [0, 1]')
         if a.recommend_calibration is not None and (a.recommend_diversity is not None or a.recommend_report is not None):
             p.error('--recommend_calibration does not combine with --recommend_diversity or --recommend_report')
+        if a.recommend_sample is not None and not 0.0 < a.recommend_sample < float('inf'):
+            p.error('--recommend_sample is a temperature: it must be positive and finite')
+        if a.recommend_sample is not None and (a.recommend_diversity is not None or a.recommend_report is not None
+                                               or a.recommend_calibration is not None or a.recommend_max_per_category):
+            p.error('--recommend_sample does not combine with --recommend_diversity, --recommend_calibration, --recommend_report or '
+                    '--recommend_max_per_category')
+        if a.recommend_seed and a.recommend_sample is None:
+            p.error('--recommend_seed needs --recommend_sample')
         if a.recommend_diversity is None and a.recommend_report is None and (
-                a.recommend_max_per_category or (a.recommend_shortlist and a.recommend_calibration is None)):
+                a.recommend_max_per_category or (a.recommend_shortlist and a.recommend_calibration is None and a.recommend_sample is None)):
             p.error('--recommend_shortlist and --recommend_max_per_category need --recommend_diversity (0 for the cap alone) or --recommend_report')
         if a.recommend_diversity is not None and not 0.0 <= a.recommend_diversity <= 1.0:
             p.error('--recommend_diversity must lie in [0, 1]')
@@ -132,10 +146,12 @@ class Config:
         diversity_flags = ('recommend_diversity', 'recommend_shortlist', 'recommend_max_per_category')    # attributes only when asked for
         report_flags = ('recommend_report', 'recommend_shortlist', 'recommend_max_per_category')
         calibration_flags = ('recommend_calibration', 'recommend_shortlist')
+        sample_flags = ('recommend_sample', 'recommend_seed', 'recommend_shortlist')
         bootstrap_flags = ('bootstrap', 'bootstrap_level', 'compare_model_path')
         asked = lambda k: ((a.recommend_diversity is not None and k in diversity_flags) or (a.recommend_report is not None and k in report_flags)
                            or (a.recommend_calibration is not None and k in calibration_flags) or (a.bootstrap and k in bootstrap_flags)
-                           or k not in diversity_flags + report_flags + calibration_flags + bootstrap_flags)
+                           or (a.recommend_sample is not None and k in sample_flags)
+                           or k not in diversity_flags + report_flags + calibration_flags + sample_flags + bootstrap_flags)
         self.attribute_dict = {k: v for k, v in vars(a).items()
                                if (a.data_root or k not in mind_flags or (k == 'model_dir' and a.model_dir)) and asked(k)}
         for k, v in self.attribute_dict.items():

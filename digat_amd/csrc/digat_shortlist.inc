@@ -15,7 +15,8 @@
 //       position order; unused slots get key 0.
 //   level 2, shortlist_segment_kernel, one workgroup per segment: the same two steps over the segment's chunks * m slots; the
 //       <= m winners land in LDS as unique 64-bit words (key, ~ordinal) — the ordinal grows with the position — beside their
-//       positions, a bitonic network over the next power of two (at most 1024 words, 8 KB, two pairs per thread and step) orders them,
+//       positions, a bitonic network over the next power of two (at most 1024 words, 8 KB, two pairs per thread and step;
+//       short_bitonic, which digat_pl_sample.inc runs over its own records) orders them,
 //       and the row is written: score bits and ids read back by position, then the fill, then the count.
 //       A segment of at most SHORT_SMALL = 1024 elements is level 2's alone: load, sort, write; level 1 leaves at once.
 // Uniform mode (seg_start == nullptr): `segments` segments of seg_len elements each, segment s at s * seg_len with the chunk slots
@@ -174,6 +175,23 @@ struct ShortSort {
     long long pos[SHORT_MAX_K];              // by ordinal: the winner's position inside the segment
 };
 
+// The bitonic network over w[0 .. n2) in LDS, n2 a power of two of at most SHORT_MAX_K records, two pairs per thread and step:
+// afterwards x stands in front of y wherever before(x, y) — a strict total order over the records (no two compare equal).  Called
+// by the whole workgroup of 256 threads behind a barrier; ends on one.  digat_pl_sample.inc orders its (key, position) records here.
+template <class T, class Before>
+__device__ __forceinline__ void short_bitonic(T* w, int n2, const Before& before) {
+    const int tid = threadIdx.x;
+    for (int k = 2; k <= n2; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < (n2 >> 1); t += 256) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), p = i | j;
+                const T x = w[i], y = w[p];
+                if ((i & k) == 0 ? before(y, x) : before(x, y)) { w[i] = y; w[p] = x; }
+            }
+            __syncthreads();
+        }
+}
+
 __global__ void __launch_bounds__(256) shortlist_segment_kernel(const ShortArgs a) {
     __shared__ ShortShared sh;
     __shared__ ShortSort so;
@@ -217,15 +235,7 @@ __global__ void __launch_bounds__(256) shortlist_segment_kernel(const ShortArgs 
     __syncthreads();
     int n2 = 2;
     while (n2 < held) n2 <<= 1;
-    for (int k = 2; k <= n2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < (n2 >> 1); t += 256) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), p = i | j;
-                const unsigned long long x = so.w[i], y = so.w[p];
-                if ((i & k) == 0 ? x < y : x > y) { so.w[i] = y; so.w[p] = x; }
-            }
-            __syncthreads();
-        }
+    short_bitonic(so.w, n2, [](unsigned long long x, unsigned long long y) { return x > y; });
     for (int j = tid; j < n2; j += 256)             // the winners stand in front: the last of them says how many they are
         if (so.w[j] != 0ull && (j + 1 == n2 || so.w[j + 1] == 0ull)) sh.count = (unsigned)(j + 1 < a.m ? j + 1 : a.m);
     __syncthreads();

@@ -2556,6 +2556,298 @@ def rank_metrics_intervals(rank, target_start, ks=(10, 50, 100, 128), replicates
     return out
 
 
+# ---- stochastic lists: Plackett-Luce slates with their propensities ------------------------------------------------------------------
+PL_MAX_LIST = SHORTLIST_MAX_K      # include/digat_hip.h: DIGAT_PL_MAX_LIST, the longest list digat_pl_sample / digat_pl_log_prob take
+PL_MAX_K = TOPK_MAX_K              # ... DIGAT_PL_MAX_K, the longest slate
+PL_MAX_SAMPLE = 1 << 22            # ... DIGAT_PL_MAX_SAMPLE: first_sample + samples may reach this (the sample shares a word with the position)
+PL_CLAMP = -700.0                  # ... DIGAT_PL_CLAMP: a weight is exp(max(a - a_max, PL_CLAMP)), never 0
+PL_ROBUST_GAP = 2.0 ** -40         # a robust slate's adjacent keys differ by this much of max(1, |key|) (pl_sample_host)
+_FLT_MAX = float(np.finfo(np.float32).max)
+
+
+def _check_pl_args(scores_shape, count_shape, k, temperature, samples=1, first_sample=0, streams_shape=None, picks_shape=None) -> float:
+    """The argument checks ``pl_sample``, ``pl_log_prob`` and their host twins share; returns ``inv_t = 1.0 / float64(temperature)``."""
+    if len(scores_shape) != 2 or not 1 <= scores_shape[1] <= PL_MAX_LIST:
+        raise ValueError(f"scores must be [G, M] with 1 <= M <= PL_MAX_LIST = {PL_MAX_LIST}, got {tuple(scores_shape)}")
+    G = int(scores_shape[0])
+    if count_shape is not None and tuple(count_shape) != (G,):
+        raise ValueError(f"count must have one entry per list ({G}), got shape {tuple(count_shape)}")
+    if int(k) != k or not 1 <= int(k) <= PL_MAX_K:
+        raise ValueError(f"k must be an integer in [1, {PL_MAX_K}], got {k}")
+    t = float(temperature)
+    if not 0.0 < t < float("inf"):                                  # a NaN fails both comparisons
+        raise ValueError(f"temperature must be positive and finite, got {temperature}")
+    inv_t = float(np.float64(1.0) / np.float64(t))
+    if not inv_t * _FLT_MAX < float("inf"):
+        raise ValueError(f"temperature {temperature} is too small: score / temperature must stay finite in float64")
+    if int(samples) != samples or int(samples) < 1:
+        raise ValueError(f"samples must be a positive integer, got {samples}")
+    if int(first_sample) != first_sample or int(first_sample) < 0:
+        raise ValueError(f"first_sample must be a non-negative integer, got {first_sample}")
+    if int(first_sample) + int(samples) > PL_MAX_SAMPLE:
+        raise ValueError(f"first_sample + samples must not exceed PL_MAX_SAMPLE = 2^22, got {first_sample} + {samples}")
+    if streams_shape is not None and tuple(streams_shape) != (G,):
+        raise ValueError(f"streams must have one entry per list ({G}), got shape {tuple(streams_shape)}")
+    if picks_shape is not None and (len(picks_shape) != 3 or picks_shape[0] != G or picks_shape[2] != int(k) or picks_shape[1] < 1):
+        raise ValueError(f"picks must be [G = {G}, S >= 1, k = {int(k)}], got {tuple(picks_shape)}")
+    return inv_t
+
+
+def _check_streams_host(streams, G: int) -> np.ndarray:
+    if streams is None:
+        return np.arange(G, dtype=np.uint64)
+    st = np.asarray(_host(streams))
+    if st.dtype.kind not in "iu" or st.ndim != 1:
+        raise ValueError(f"streams must be a 1-D integer array, got {st.dtype} {st.shape}")
+    if st.size and (int(st.min()) < 0 or int(st.max()) >= 1 << 32):
+        raise ValueError("every stream must lie in [0, 2^32)")
+    return st.astype(np.uint64)
+
+
+def pl_draws_host(streams, samples: int, M: int, seed: int = 0, first_sample: int = 0) -> np.ndarray:
+    """The uniform word behind every (list, sample, position) of ``digat_pl_sample``, bit for bit: ``w`` [G, S, M] uint32.  The 64-bit
+    counter is ``e = (streams[g] << 32) | ((first_sample + s) << 10 | p)`` and the word ``hash32((uint32)e * 0x9E3779B9 +
+    hash32(seed + (uint32)(e >> 32)))`` — ``bootstrap_draws_host``'s construction —: a pure function of (seed, stream, sample,
+    position), the same for a list alone or in a batch and in a call split by ``first_sample``.  ``streams`` [G]: 32-bit ids the
+    caller gives (an impression, a user); ``M <= 1024``, ``first_sample + samples <= 2^22``."""
+    st = np.asarray(_host(streams))
+    _check_pl_args((len(st), int(M)), None, 1, 1.0, samples, first_sample, st.shape)
+    st = _check_streams_host(st, len(st))
+    s = np.arange(int(first_sample), int(first_sample) + int(samples), dtype=np.uint64)
+    low = (s[:, None] << np.uint64(10)) | np.arange(int(M), dtype=np.uint64)[None, :]                 # [S, M] < 2^32
+    inner = _hash32(np.uint64(int(seed) & 0xFFFFFFFF) + st)                                         # [G]
+    w = _hash32((((low * np.uint64(0x9E3779B9)) & _M32)[None, :, :] + inner[:, None, None]))
+    return w.astype(np.uint32)
+
+
+def _pl_lists_host(scores, count, inv_t):
+    """``(scores float32 [G, M], live bool [G, M], a float64 [G, M])`` of the host twins: ``a = float64(x) * inv_t`` where live."""
+    sc = np.ascontiguousarray(_host(scores), dtype=np.float32)
+    G, M = sc.shape
+    cnt = np.full(G, M, dtype=np.int64) if count is None else np.clip(np.asarray(_host(count), dtype=np.int64), 0, M)
+    live = (np.arange(M)[None, :] < cnt[:, None]) & np.isfinite(sc)
+    a = np.where(live, sc, np.float32(0)).astype(np.float64) * np.float64(inv_t)
+    return sc, live, a
+
+
+def _pl_slate_host(a, live, picks, k):
+    """The probability stage of one list for one slate: ``(logp, step64 [k], logZ [k], length)`` — the slate is ``picks`` up to its
+    first entry that is negative, out of range, not live or repeated."""
+    import math
+    M = len(a)
+    step, logz = np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.float64)
+    if not live.any():
+        return 0.0, step, logz, 0
+    d = np.maximum(a - a[live].max(), PL_CLAMP)
+    w = np.exp(d)
+    left = live.copy()
+    n = 0
+    for p in picks[:k]:
+        p = int(p)
+        if p < 0 or p >= M or not left[p]:
+            break
+        logz[n] = np.log(np.float64(math.fsum(w[left].tolist())))
+        step[n] = d[p] - logz[n]
+        left[p] = False
+        n += 1
+    return math.fsum(step[:n].tolist()), step, logz, n
+
+
+def pl_sample_host(scores, count, k: int, temperature, seed: int = 0, samples: int = 1, first_sample: int = 0, streams=None,
+                   return_robust: bool = False, parts: bool = False):
+    """The contract of ``digat_pl_sample`` in numpy — the sampler's yardstick.  ``scores`` [G, M <= 1024] float32, ``count`` [G] or
+    None (M): position p of list g is LIVE when ``p < clip(count[g], 0, M)`` and ``scores[g, p]`` is finite; ``-inf``, ``+inf`` and
+    NaN carry no mass and are never drawn.  In float64, every operation rounded: ``inv_t = 1.0 / float64(temperature)``, ``a_p =
+    float64(x_p) * inv_t``, ``u = (w + 0.5) * 2^-32`` (exact) with ``w`` the word of ``pl_draws_host``, ``key_p = a_p +
+    (-log(-log(u)))`` — a Gumbel key: the live positions in descending key order are a draw without replacement from
+    ``softmax(score / temperature)``, a Plackett-Luce slate.  Ties go to the lowest position; the slate is cut to ``n_out = min(k,
+    live)``, ``1 <= k <= 128``.  Its probability: ``a_max`` the largest live ``a``, ``w_p = exp(max(a_p - a_max, -700))`` (the clamp
+    keeps every ``Z`` positive whatever the spread; while an unpicked entry lies within 700 of ``a_max`` its effect on a step is
+    below e^-700 — once the slate has used up all of those, the entries left sit on the clamp together and the step reported is
+    the uniform one over them: keep ``k`` gaps of ``score / temperature`` below 700 where the tail's propensity matters), ``Z_t`` the sum (``math.fsum``) of
+    ``w`` over the live positions not picked before step t, ``step[t] = max(a_pick(t) - a_max, -700) - log(Z_t)`` and ``logp`` the
+    ``fsum`` of the steps.
+
+    Returns ``(picks [G, S, k] int32 — positions, -1 beyond n_out —, n_out [G] int32, logp [G, S] float64, step_logp [G, S, k]
+    float32 — 0 beyond n_out)``; the ``logp`` of an empty slate is 0.  ``streams`` [G] (None: ``g``), ``seed``, ``samples`` and
+    ``first_sample`` are ``pl_draws_host``'s.
+
+    ``return_robust`` adds [G] bool: a list is robust when, in every sample, every adjacent pair among its top ``n_out + 1`` keys
+    is separated by at least ``2^-40 max(1, |key|)``.  Two float64 logarithms correct to 1 ulp move a key by at most a few
+    ``2^-52 max(1, |key|)``, so on a robust list every such implementation draws the same slate.  ``parts`` adds a dict with the
+    float64 ``step`` and ``logZ`` [G, S, k] and ``live`` [G] (what ``pl_bound`` takes)."""
+    inv_t = _check_pl_args(np.shape(scores), None if count is None else np.shape(count), k, temperature, samples, first_sample,
+                           None if streams is None else np.shape(streams))
+    sc, live, a = _pl_lists_host(scores, count, inv_t)
+    (G, M), k, S = sc.shape, int(k), int(samples)
+    words = pl_draws_host(_check_streams_host(streams, G), S, M, seed, first_sample)
+    with np.errstate(divide="ignore"):
+        gumbel = -np.log(-np.log((words.astype(np.float64) + 0.5) * 2.0 ** -32))
+    key = a[:, None, :] + gumbel
+    picks = np.full((G, S, k), -1, dtype=np.int32)
+    n_out = np.minimum(live.sum(axis=1), k).astype(np.int32)
+    logp = np.zeros((G, S), dtype=np.float64)
+    step = np.zeros((G, S, k), dtype=np.float64)
+    logz = np.zeros((G, S, k), dtype=np.float64)
+    robust = np.ones(G, dtype=bool)
+    for g in range(G):
+        pos = np.flatnonzero(live[g])
+        n = int(n_out[g])
+        for s in range(S):
+            kg = key[g, s, pos]
+            order = np.argsort(-kg, kind="stable")                  # descending key, equal keys by position
+            picks[g, s, :n] = pos[order[:n]]
+            top = kg[order[:n + 1]]
+            if len(top) > 1 and np.any(top[:-1] - top[1:] < PL_ROBUST_GAP * np.maximum(1.0, np.maximum(np.abs(top[:-1]), np.abs(top[1:])))):
+                robust[g] = False
+            logp[g, s], step[g, s], logz[g, s], _ = _pl_slate_host(a[g], live[g], picks[g, s], k)
+    out = (picks, n_out, logp, step.astype(np.float32))
+    if return_robust:
+        out += (robust,)
+    if parts:
+        out += ({"step": step, "logZ": logz, "live": live.sum(axis=1)},)
+    return out
+
+
+def pl_log_prob_host(scores, count, picks, temperature, parts: bool = False):
+    """``pl_sample_host``'s ``logp`` [G, S] float64 and ``step_logp`` [G, S, k] float32 for GIVEN slates — the probability of a logged
+    slate under another model's scores.  ``picks`` [G, S, k] holds positions; a slate ends at its first entry that is negative, out
+    of range, not live or repeated (``step_logp`` is 0 from there on).  ``parts`` adds the dict of ``pl_sample_host`` with the
+    slates' lengths ``length`` [G, S]."""
+    pk = np.asarray(_host(picks))
+    if pk.dtype.kind not in "iu":
+        raise ValueError(f"picks must hold integer positions, got {pk.dtype}")
+    k = int(pk.shape[2]) if pk.ndim == 3 else 0
+    inv_t = _check_pl_args(np.shape(scores), None if count is None else np.shape(count), k, temperature, picks_shape=pk.shape)
+    sc, live, a = _pl_lists_host(scores, count, inv_t)
+    G, S = sc.shape[0], int(pk.shape[1])
+    logp = np.zeros((G, S), dtype=np.float64)
+    step = np.zeros((G, S, k), dtype=np.float64)
+    logz = np.zeros((G, S, k), dtype=np.float64)
+    length = np.zeros((G, S), dtype=np.int32)
+    for g in range(G):
+        for s in range(S):
+            logp[g, s], step[g, s], logz[g, s], length[g, s] = _pl_slate_host(a[g], live[g], pk[g, s], k)
+    out = (logp, step.astype(np.float32))
+    return out + ({"step": step, "logZ": logz, "live": live.sum(axis=1), "length": length},) if parts else out
+
+
+def pl_bound(n, logZ, value=None, float32: bool = False, total: bool = False):
+    """The comparison bound of ``pl_sample`` / ``pl_log_prob`` against their host twins (derived in csrc/digat_pl_sample.inc).  Per
+    step: ``(n + 16) 2^-53 (1 + |log Z_t|)`` — n the live elements of the list: the order of the n positive terms of ``Z_t`` and the
+    few ulps of ``exp`` and ``log`` on either side — plus, with the step's ``value``, ``2^-52 |value|``: both sides round the final
+    difference, and two numbers that close may round to neighbours; ``float32`` adds ``2^-23 |value|`` for a ``step_logp`` compared
+    as float32 (one float32 rounding on either side).  ``total``: the bound of ``logp`` — the step bounds summed over the last axis
+    plus ``(k + 1) 2^-53 sum |value|``, the device adding the steps in slate order where the twin adds them exactly."""
+    n = np.asarray(n, dtype=np.float64)
+    lz = np.abs(np.asarray(logZ, dtype=np.float64))
+    b = (n + 16.0) * 2.0 ** -53 * (1.0 + lz)
+    if value is None:
+        return b
+    v = np.abs(np.asarray(value, dtype=np.float64))
+    b = b + 2.0 ** -52 * v + (2.0 ** -23 * v if float32 else 0.0)
+    if total:
+        return b.sum(axis=-1) + (b.shape[-1] + 1) * 2.0 ** -53 * v.sum(axis=-1)
+    return b
+
+
+def _pl_device_args(scores, count, streams=None):
+    import torch
+    from . import _lib
+    given = [t for t in (scores, count, streams) if t is not None]
+    dev = _lib.require_device(*given)
+    sc = _lib.f32(scores.detach())
+    ct = None if count is None else count.to(torch.int32).contiguous()
+    st = None if streams is None else streams.to(torch.int64).contiguous()
+    return dev, sc, ct, st
+
+
+def pl_sample(scores, count, k: int, temperature, seed: int = 0, samples: int = 1, first_sample: int = 0, streams=None):
+    """Plackett-Luce slates on the GPU (``digat_pl_sample``): per list and sample, k positions drawn without replacement from
+    ``softmax(scores / temperature)`` over the list's live positions, and the probability of what was drawn.  ``scores`` [G, M <=
+    1024] float32 and ``count`` [G] int32 (None: M) are device tensors — what ``shortlist_segments``, ``dot_shortlist``,
+    ``score_lists`` and both ``recommend``s return —, ``streams`` [G] an integer device tensor of 32-bit ids (its low 32 bits are
+    used; None: the list's index).  The contract is ``pl_sample_host``'s: the same picks on its robust lists, ``logp`` and
+    ``step_logp`` within ``pl_bound``.  Returns ``(picks [G, S, k] int32, n_out [G] int32, logp [G, S] float64, step_logp [G, S, k]
+    float32)`` on the device.  A draw is a pure function of (seed, stream, sample, position) and every order of addition is fixed by
+    the list and the slate: the same bits from run to run, for a list alone or in a batch, and from a call split by
+    ``first_sample``.  Stream-ordered: nothing is read back."""
+    import torch
+    from . import _lib
+    dev, sc, ct, st = _pl_device_args(scores, count, streams)
+    inv_t = _check_pl_args(tuple(sc.shape), None if ct is None else tuple(ct.shape), k, temperature, samples, first_sample,
+                           None if st is None else tuple(st.shape))
+    G, M, k, S = int(sc.shape[0]), int(sc.shape[1]), int(k), int(samples)
+    picks = torch.empty((G, S, k), dtype=torch.int32, device=dev)
+    n_out = torch.empty((G,), dtype=torch.int32, device=dev)
+    logp = torch.empty((G, S), dtype=torch.float64, device=dev)
+    step = torch.empty((G, S, k), dtype=torch.float32, device=dev)
+    if G == 0:
+        return picks, n_out, logp, step
+    L = _lib.lib()
+    need = int(L.digat_pl_sample_workspace_bytes(G, M, k, S))
+    ws = _lib.workspace(need, dev, "pl_sample")
+    _lib.check(L.digat_pl_sample(sc.data_ptr(), _lib.ptr(ct), G, M, k, inv_t, int(seed) & 0xFFFFFFFF, S, int(first_sample), _lib.ptr(st),
+                                 picks.data_ptr(), n_out.data_ptr(), logp.data_ptr(), step.data_ptr(), ws.data_ptr(), need,
+                                 _lib.stream_ptr()), "digat_pl_sample")
+    return picks, n_out, logp, step
+
+
+def pl_log_prob(scores, count, picks, temperature):
+    """The probability of GIVEN slates on the GPU (``digat_pl_log_prob``): ``(logp [G, S] float64, step_logp [G, S, k] float32)`` of
+    ``picks`` [G, S, k] (integer positions; a slate ends at its first entry that is negative, out of range, not live or repeated)
+    under ``softmax(scores / temperature)`` — ``pl_log_prob_host``'s contract within ``pl_bound``.  The kernel runs the sampler's own
+    probability stage: on ``pl_sample``'s picks, with its scores and temperature, both outputs are the sampler's bit for bit."""
+    import torch
+    from . import _lib
+    dev, sc, ct, _ = _pl_device_args(scores, count)
+    _lib.require_device(sc, picks)
+    if picks.is_floating_point() or picks.dtype == torch.bool:
+        raise ValueError(f"picks must hold integer positions, got {picks.dtype}")
+    k = int(picks.shape[2]) if picks.dim() == 3 else 0
+    inv_t = _check_pl_args(tuple(sc.shape), None if ct is None else tuple(ct.shape), k, temperature, picks_shape=tuple(picks.shape))
+    pk = torch.clamp(picks, min=-1, max=PL_MAX_LIST).to(torch.int32).contiguous()       # any position outside the list ends the slate
+    G, M, S = int(sc.shape[0]), int(sc.shape[1]), int(pk.shape[1])
+    logp = torch.empty((G, S), dtype=torch.float64, device=dev)
+    step = torch.empty((G, S, k), dtype=torch.float32, device=dev)
+    if G == 0:
+        return logp, step
+    L = _lib.lib()
+    need = int(L.digat_pl_sample_workspace_bytes(G, M, k, S))
+    ws = _lib.workspace(need, dev, "pl_sample")
+    _lib.check(L.digat_pl_log_prob(sc.data_ptr(), _lib.ptr(ct), G, M, k, inv_t, S, pk.data_ptr(), logp.data_ptr(), step.data_ptr(),
+                                   ws.data_ptr(), need, _lib.stream_ptr()), "digat_pl_log_prob")
+    return logp, step
+
+
+def off_policy_value(reward, logp_target, logp_logging, clip=None, units=None, replicates: int = 2000, level: float = 0.95, seed: int = 0):
+    """What a target policy would have earned on a log made by another: one row per logged slate, ``reward`` [n], ``logp_target`` /
+    ``logp_logging`` [n] the slate's log-probability under either policy (``pl_log_prob`` / ``pl_sample``), weights ``exp(logp_target
+    - logp_logging)`` capped at ``clip`` (None: no cap).  Returns ``{"ips", "snips"}`` — ``metric_intervals``' fields: ``ips`` the
+    mean of ``weight * reward``, ``snips`` the ratio of sums ``sum(weight * reward) / sum(weight)`` (its ``denominators=``), both
+    from the same draws — and ``ess`` (``sum(w)^2 / sum(w^2)``, the effective sample size), ``max_weight`` and ``n``.  ``units`` (a
+    CSR ``start`` over contiguous rows) keeps a user's slates together in the resampling.  Host arrays or tensors; the resampling
+    is ``metric_intervals``' own."""
+    r, lt, ll = (np.asarray(_host(x), dtype=np.float64).reshape(-1) for x in (reward, logp_target, logp_logging))
+    if not len(r) == len(lt) == len(ll) or len(r) < 1:
+        raise ValueError(f"reward, logp_target and logp_logging must hold one entry per logged slate, got {len(r)}, {len(lt)} and {len(ll)}")
+    if not (np.isfinite(lt).all() and np.isfinite(ll).all() and np.isfinite(r).all()):
+        raise ValueError("reward, logp_target and logp_logging must be finite (a slate the target cannot draw has no finite logp: cut it or leave it out)")
+    if clip is not None and not float(clip) > 0.0:
+        raise ValueError(f"clip must be positive, got {clip}")
+    with np.errstate(over="ignore"):
+        w = np.exp(lt - ll)
+    if clip is not None:
+        w = np.minimum(w, float(clip))
+    if not np.isfinite(w).all():
+        raise ValueError("a weight exp(logp_target - logp_logging) overflows: name clip")
+    wr = w * r
+    out = {"ips": metric_intervals(wr, ("ips",), replicates, level, seed, units=units)["ips"],
+           "snips": metric_intervals(wr, ("snips",), replicates, level, seed, denominators=w, units=units)["snips"]}
+    out.update({"ess": float(w.sum() ** 2 / np.sum(w * w)) if w.sum() > 0 else 0.0, "max_weight": float(w.max()), "n": int(len(w))})
+    return out
+
+
 class AvgMetric:
     """util.py:100-121: the model-selection average."""
 

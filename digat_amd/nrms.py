@@ -511,7 +511,8 @@ def user_vectors(model, dev, users, batch_size=1024):
 
 
 def recommend(model, dev, users, candidates=None, k=10, exclude_history=True, batch_size=1024, diversity=None, shortlist=None, category=None,
-              max_per_category=0, calibration=None, calibration_target=None, alpha=0.01, index=None, refine=None):
+              max_per_category=0, calibration=None, calibration_target=None, alpha=0.01, index=None, refine=None, sample=None, seed=0,
+              streams=None):
     """For every user, which k news, in order: ``(news_ids [G,k] int64, scores [G,k] float32, count [G] int32)`` on the model's
     device.  Order: score descending, equal scores in candidate order; slots at or beyond ``count[g]`` hold id -1 and score -inf.
 
@@ -538,8 +539,20 @@ def recommend(model, dev, users, candidates=None, k=10, exclude_history=True, ba
     them to k: the scores returned are exact (``dot_scores``' bits), and wherever the exact top-k lies inside the quantised
     shortlist the result is the plain call's, bit for bit (``index_report`` measures how often that is).  Per-user candidate lists
     are refused.  ``diversity`` composes — its shortlist of k' comes from the indexed call —; ``calibration`` does not: its
-    shortlist may be longer than the 128 entries ``refine_lists`` returns."""
+    shortlist may be longer than the 128 entries ``refine_lists`` returns.
+
+    ``sample`` — a temperature > 0 (None: off, the call as it was, bit for bit): retrieval runs at ``k' = shortlist or min(1024,
+    8 k)`` and ``util.sample_lists`` draws one Plackett-Luce slate of k from ``softmax(score / sample)`` over that shortlist;
+    ``seed`` and ``streams`` [G] name the draws (None: the impression indices where ``users`` are indices).  ``util.recommend`` has
+    the details; ``sample`` does not combine with ``diversity``, ``calibration`` or ``index``."""
     from . import evaluate, util
+    util.sample_refusals(sample, seed, streams, diversity=diversity, calibration=calibration, calibration_target=calibration_target,
+                         category=category, max_per_category=max_per_category, index=index, refine=refine)
+    if sample is not None:
+        select = lambda wide, long_lists: _retrieve(model, dev, users, candidates, wide, exclude_history, batch_size, long_lists)
+        ids, scores, n_out = util.shortlist_then_sample(select, k, sample, shortlist, seed,
+                                                        util.user_streams(users) if streams is None else streams)[1][:3]
+        return ids[:, 0].contiguous(), scores[:, 0].contiguous(), n_out
     if index is None and refine is not None:
         raise ValueError("refine belongs to an indexed call: name index (build_index)")
     if calibration is not None and index is not None:

@@ -1099,6 +1099,129 @@ def shortlist_then_calibrate(select: Callable, history: Callable, k, calibration
     return short, calibrate(*short, cat, target, k, lam, alpha)
 
 
+def sample_limits(k, sample, shortlist) -> Tuple[int, int, float]:
+    """``(k, k', temperature)`` of a sampled ``recommend``: the plain selection runs at ``k' = shortlist or min(1024, 8 k)``, and
+    ``sample_lists`` draws one slate of k from it at temperature ``sample`` > 0."""
+    if not 1 <= int(k) <= evaluate.PL_MAX_K:
+        raise ValueError(f"k must be in [1, {evaluate.PL_MAX_K}], got {k}")
+    if not 0.0 < float(sample) < float("inf"):                      # a NaN fails both comparisons
+        raise ValueError(f"sample is a temperature: positive and finite, got {sample}")
+    k = int(k)
+    wide = min(evaluate.PL_MAX_LIST, 8 * k) if not shortlist else int(shortlist)
+    if not k <= wide <= evaluate.PL_MAX_LIST:
+        raise ValueError(f"shortlist must lie in [k, {evaluate.PL_MAX_LIST}] = [{k}, {evaluate.PL_MAX_LIST}], got {shortlist}")
+    return k, wide, float(sample)
+
+
+def sample_refusals(sample, seed, streams, **others) -> None:
+    """What ``recommend(sample=)`` of either model refuses before anything is scored: ``sample`` beside a re-rank or an index
+    (``others``: the names and values of the arguments it does not combine with), ``seed`` / ``streams`` without ``sample``."""
+    if sample is None:
+        if seed or streams is not None:
+            raise ValueError("seed and streams belong to a sampled call: name sample (a temperature)")
+        return
+    named = [name for name, value in others.items() if value is not None and not (isinstance(value, int) and value == 0)]
+    if named:
+        raise ValueError(f"sample does not combine with {', '.join(named)}: the policy is Plackett-Luce over the plain shortlist")
+
+
+def sample_lists(ids: torch.Tensor, scores: torch.Tensor, count, k: int, temperature: float, seed: int = 0, samples: int = 1, streams=None,
+                 first_sample: int = 0):
+    """Plackett-Luce slates from given lists ``(ids [G,M <= 1024], scores [G,M], count [G])`` — what ``recommend``,
+    ``recommend_lists``, ``nrms.shortlist`` and ``score_lists`` return —: ``samples`` draws of k without replacement from
+    ``softmax(scores / temperature)`` over every list's own entries, each with its probability.  Returns ``(news_ids [G,S,k] int64,
+    scores [G,S,k] float32 — the input score bits —, n_out [G] int32, logp [G,S] float64, step_logp [G,S,k] float32)``: slots at or
+    beyond ``n_out`` hold -1 / -inf.  ``evaluate.pl_sample`` on device tensors, ``evaluate.pl_sample_host`` on CPU tensors, as
+    ``calibrate`` does; ``streams`` [G] (None: the list's index) and ``seed`` name the draws (``evaluate.pl_draws_host``)."""
+    if ids.dim() != 2 or tuple(scores.shape) != tuple(ids.shape):
+        raise ValueError(f"ids and scores must both be [G, M], got {tuple(ids.shape)} and {tuple(scores.shape)}")
+    st = None if streams is None else _tensor_on(streams, ids.device)
+    if ids.is_cuda:
+        picks, n_out, logp, step = evaluate.pl_sample(scores, count, k, temperature, seed, samples, first_sample, st)
+    else:
+        picks, n_out, logp, step = map(torch.from_numpy, evaluate.pl_sample_host(
+            scores.numpy(), None if count is None else count.numpy(), k, temperature, seed, samples, first_sample, None if st is None else st.numpy()))
+    G, S, k = (int(x) for x in picks.shape)
+    at = picks.to(torch.int64).clamp(min=0).view(G, S * k)
+    hit = picks >= 0
+    out_ids = torch.where(hit, ids.to(torch.int64).gather(1, at).view(G, S, k), torch.full_like(picks, -1, dtype=torch.int64))
+    out_scores = torch.where(hit, scores.gather(1, at).view(G, S, k), torch.full_like(step, float("-inf")))
+    return out_ids, out_scores, n_out, logp, step
+
+
+def slate_positions(ids: torch.Tensor, count, slates: torch.Tensor) -> torch.Tensor:
+    """``picks`` [G,S,k] int32: the position of every news of ``slates`` [G,S,k] in its user's list ``ids`` [G,M] (the first one
+    below ``count``), -1 for a news that is absent and for a negative id."""
+    G, M = int(ids.shape[0]), int(ids.shape[1])
+    live = torch.arange(M, device=ids.device)[None, :] < (count.to(torch.int64)[:, None] if count is not None else M)
+    picks = torch.empty(tuple(slates.shape), dtype=torch.int32, device=ids.device)
+    rows = max(1, (1 << 24) // max(1, M * int(slates.shape[1]) * int(slates.shape[2])))
+    for g0 in range(0, G, rows):                                    # [rows, S k, M] comparisons at a time
+        sl = slates[g0:g0 + rows].to(torch.int64)
+        eq = (sl.reshape(sl.shape[0], -1, 1) == ids[g0:g0 + rows, None, :].to(torch.int64)) & live[g0:g0 + rows, None, :]
+        first = torch.where(eq, torch.arange(M, device=ids.device), torch.full((), M, device=ids.device, dtype=torch.int64)).amin(dim=2)
+        found = (first < M) & (sl.reshape(sl.shape[0], -1) >= 0)
+        picks[g0:g0 + rows] = torch.where(found, first, torch.full_like(first, -1)).view(sl.shape).to(torch.int32)
+    return picks
+
+
+def slate_log_prob(ids: torch.Tensor, scores: torch.Tensor, count, slates, temperature: float):
+    """The probability of GIVEN slates under other scores — a logged slate under another model: ``slates`` [G,S,k] news ids are
+    matched to positions of ``ids`` [G,M] (``slate_positions``) and ``evaluate.pl_log_prob`` (CPU tensors:
+    ``evaluate.pl_log_prob_host``) gives ``logp`` [G,S] float64 and ``step_logp`` [G,S,k] float32 under ``softmax(scores /
+    temperature)``.  A news that is absent from the list — or whose score there is not finite — ends the slate at that slot.
+    Returns ``(logp, step_logp, covered [G,S] bool)``: ``covered`` says that every news of the slate (every slot with an id >= 0)
+    was found and counted."""
+    sl = _tensor_on(slates, ids.device)
+    if sl.dim() != 3 or int(sl.shape[0]) != int(ids.shape[0]) or sl.is_floating_point():
+        raise ValueError(f"slates must be integer news ids [G = {int(ids.shape[0])}, S, k], got {tuple(sl.shape)} {sl.dtype}")
+    if ids.dim() != 2 or tuple(scores.shape) != tuple(ids.shape):
+        raise ValueError(f"ids and scores must both be [G, M], got {tuple(ids.shape)} and {tuple(scores.shape)}")
+    picks = slate_positions(ids, count, sl)
+    if ids.is_cuda:
+        logp, step = evaluate.pl_log_prob(scores, count, picks, temperature)
+    else:
+        logp, step = map(torch.from_numpy, evaluate.pl_log_prob_host(scores.numpy(), None if count is None else count.numpy(), picks.numpy(),
+                                                                     temperature))
+    finite = torch.isfinite(scores.gather(1, picks.to(torch.int64).clamp(min=0).view(picks.shape[0], -1))).view(picks.shape)
+    covered = ((sl < 0) | ((picks >= 0) & finite)).all(dim=2)
+    return logp, step, covered
+
+
+def shortlist_then_sample(select: Callable, k, sample, shortlist=None, seed: int = 0, streams=None, samples: int = 1):
+    """The step behind ``recommend(sample=)`` of either model and ``recommend_slates``: ``select(k', long_lists)`` — the plain
+    selection at ``sample_limits``' width, ``long_lists`` when ``k' > 128`` — then ``sample_lists``.  Returns ``(shortlist triple,
+    (news_ids [G,S,k], scores [G,S,k], n_out [G], logp [G,S], step_logp [G,S,k]))``."""
+    k, wide, temperature = sample_limits(k, sample, shortlist)
+    evaluate._check_pl_args((1, wide), None, k, temperature, samples)               # refused before anything is scored
+    short = select(wide, wide > evaluate.TOPK_MAX_K)
+    return short, sample_lists(*short, k, temperature, seed, samples, streams)
+
+
+def user_streams(users):
+    """The default ``streams`` of a sampled ``recommend``: the impression indices where ``users`` are given as indices (a user's
+    draws do not depend on who else is in the call), None — the list's index — for users given as arrays."""
+    if isinstance(users, (tuple, list)) and len(users) == 2 and _ndim(users[0]) == 2:
+        return None
+    return users
+
+
+def recommend_slates(model, dc: DeviceCorpus, users, candidates, k: int, temperature: float, samples: int = 1, seed: int = 0,
+                     shortlist: Optional[int] = None, streams=None, exclude_history: bool = True, batch_size: int = 1024,
+                     max_rows: int = RECOMMEND_MAX_ROWS):
+    """The logging side of off-policy evaluation: the plain selection at ``k' = shortlist or min(1024, 8 k)`` and ``samples``
+    Plackett-Luce slates of k per user from it at ``temperature``, each with its propensity.  Returns a dict: ``ids`` / ``scores``
+    [G,k'] / ``count`` [G] — the shortlist, the support of the policy —, ``slates`` [G,S,k] int64, ``slate_scores`` [G,S,k],
+    ``n_out`` [G], ``logp`` [G,S] float64, ``step_logp`` [G,S,k] float32, and ``temperature`` / ``seed``.  Another model's
+    probability of the same slates: ``score_lists`` on ``ids`` / ``count``, then ``slate_log_prob``; ``evaluate.off_policy_value``
+    takes both ``logp``.  ``streams`` None: ``user_streams``."""
+    plain = lambda wide, long_lists: recommend_lists(model, dc, users, candidates, wide, exclude_history, batch_size, max_rows, long_lists)
+    short, (slates, slate_scores, n_out, logp, step) = shortlist_then_sample(
+        plain, k, temperature, shortlist, seed, user_streams(users) if streams is None else streams, samples)
+    return {"ids": short[0], "scores": short[1], "count": short[2], "slates": slates, "slate_scores": slate_scores, "n_out": n_out,
+            "logp": logp, "step_logp": step, "temperature": float(temperature), "seed": int(seed)}
+
+
 def measure_lists(ids, count, vectors, category=None, base_ids=None, base_count=None, exposure=None):
     """``evaluate.list_quality`` on device lists; on CPU tensors the Gram of stock PyTorch (``evaluate.mmr_gram_stock``) and
     ``evaluate.list_quality_host``, as ``diversify`` does.  ``exposure`` [N] int32 is updated in place either way.  Returns the
@@ -1174,7 +1297,8 @@ def recommend_report(model, dc: DeviceCorpus, users, candidates, k: int, diversi
 
 def recommend(model, dc: DeviceCorpus, users, candidates, k: int, exclude_history: bool = True, batch_size: int = 1024,
               max_rows: int = RECOMMEND_MAX_ROWS, diversity: Optional[float] = None, shortlist: Optional[int] = None, category=None,
-              max_per_category: int = 0, calibration: Optional[float] = None, calibration_target=None, alpha: float = 0.01):
+              max_per_category: int = 0, calibration: Optional[float] = None, calibration_target=None, alpha: float = 0.01,
+              sample: Optional[float] = None, seed: int = 0, streams=None):
     """For every user, which k news of its candidates, in order: ``(news_ids [G,k] int64, scores [G,k] float32, count [G] int32)``
     on the device.  Order: score descending, equal scores in candidate order (the rank file's order); ``count[g]`` is the number of
     valid slots of row g, the slots behind it hold id -1 and score -inf.
@@ -1203,7 +1327,20 @@ def recommend(model, dc: DeviceCorpus, users, candidates, k: int, exclude_histor
     ``category`` (None: ``dc.news_category``; at most 64 categories), or ``calibration_target`` [G, C] as given; ``alpha`` smooths
     the list's mix.  A user with an empty history gets the plain top-k.  As for ``diversity``, ``lam`` weighs raw model scores
     against a gain of order 1: the useful range of the knob depends on the scale of the scores.  ``calibration`` and ``diversity``
-    do not combine."""
+    do not combine.
+
+    ``sample`` — a temperature > 0 (None: off, the call as it was, bit for bit) — makes the list a DRAW: the selection above runs at
+    ``k' = shortlist or min(1024, 8 k)`` and ``sample_lists`` draws one Plackett-Luce slate of k from ``softmax(score / sample)``
+    over that shortlist; the triple returned is the slate in the order drawn, its scores the model's, ``count`` the slate's length.
+    ``seed`` and ``streams`` [G] name the draws (``streams`` None: the impression indices where ``users`` are indices, so a user's
+    slate does not depend on who else is in the call).  As ``sample`` goes to 0 the slate becomes the plain list.  ``sample`` does
+    not combine with ``diversity``, ``calibration`` or ``max_per_category``; ``recommend_slates`` also returns the propensities."""
+    sample_refusals(sample, seed, streams, diversity=diversity, calibration=calibration, calibration_target=calibration_target,
+                    category=category, max_per_category=max_per_category)
+    if sample is not None:
+        plain = lambda wide, long_lists: recommend_lists(model, dc, users, candidates, wide, exclude_history, batch_size, max_rows, long_lists)
+        ids, scores, n_out = shortlist_then_sample(plain, k, sample, shortlist, seed, user_streams(users) if streams is None else streams)[1][:3]
+        return ids[:, 0].contiguous(), scores[:, 0].contiguous(), n_out
     if calibration is not None:
         if diversity is not None or max_per_category:
             raise ValueError("calibration does not combine with diversity or max_per_category: name one of them")

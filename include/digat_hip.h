@@ -895,6 +895,46 @@ int digat_calibrated_select(const int64_t* ids, const float* scores, const int32
                             int64_t N, const float* target, int C, float lam, float mu, double alpha, int k, int64_t* out_ids,
                             float* out_scores, int32_t* out_count, float* out_kl, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- stochastic lists: Plackett-Luce slates with their propensities (digat_amd.evaluate.pl_sample / pl_log_prob) ----------------
+ * Per list g: scores [G, M] f32, count [G] int32 (NULL: M) — what digat_shortlist_segments / digat_dot_shortlist write,
+ * 1 <= M <= DIGAT_PL_MAX_LIST.  Position p is LIVE when p < clamp(count[g], 0, M) and scores[g][p] is finite (an infinity or a NaN
+ * carries no mass and is never drawn; no read leaves the arrays).  inv_t = 1.0 / (double)temperature, computed by the caller.
+ * digat_pl_sample draws, per list and sample s = 0 .. samples-1, a slate of n_out = min(k, live positions) positions without
+ * replacement from softmax(scores / temperature), 1 <= k <= DIGAT_PL_MAX_K.  In float64, every operation rounded (never an fma):
+ *   a_p = (double)x_p * inv_t;   the 64-bit counter e = (stream_g << 32) | ((first_sample + s) << 10 | p) and the word
+ *   w = hash32((uint32)e * 0x9E3779B9 + hash32(seed + (uint32)(e >> 32))) — digat_bootstrap_sums' construction —;
+ *   u = (w + 0.5) 2^-32 (exact);   key_p = a_p + (-log(-log(u))).
+ * stream_g = the low 32 bits of streams[g] (NULL: g).  The slate is the live positions in descending key order, equal keys by
+ * ascending position.  Its probability: a_max = the largest live a, w_p = exp(max(a_p - a_max, DIGAT_PL_CLAMP)),
+ * Z_t = the sum of w over the live positions not picked before step t, step[t] = max(a_pick(t) - a_max, DIGAT_PL_CLAMP) - log(Z_t),
+ * logp = the sum of the steps in slate order.  Z_t is a suffix sum: the unpicked positions reduced in an order fixed by M, then the
+ * picked weights added back from the end of the slate — no subtraction.
+ * out_picks [G, samples, k] int32: positions, -1 at or beyond n_out; out_n [G] = n_out; out_logp [G, samples] f64 (0 for an empty
+ * slate); out_step [G, samples, k] f32 (0 at or beyond n_out).  Every output byte is written.
+ * digat_pl_log_prob is the probability stage alone — the same device function — for GIVEN slates picks [G, samples, k]: a slate
+ * ends in front of its first entry that is negative, >= M, not live or a repeat of an earlier one.  On digat_pl_sample's picks,
+ * scores, count and inv_t it returns digat_pl_sample's out_logp and out_step bit for bit.
+ * A draw depends on (seed, stream, sample, position) alone and every order of addition on (M, count, the slate): the same bits from
+ * run to run, for a list alone or in a batch, and from a call split by first_sample.  The logarithms and exp are the device
+ * library's float64 ones: against another implementation correct to 1 ulp a key moves by a few 2^-52 max(1, |key|)
+ * (evaluate.pl_sample_host reports which lists have no nearer pair of keys) and the probabilities stay within evaluate.pl_bound.
+ * DIGAT_ERR_ARG: a null scores / picks / out pointer, a misaligned pointer (4 bytes; 8 for out_logp and streams), G < 0, inv_t not
+ * positive or inv_t * FLT_MAX not finite (NaNs included); DIGAT_ERR_SHAPE: k outside [1, 128], M outside [1, 1024], G >= 2^31,
+ * samples < 1, first_sample < 0, first_sample + samples > DIGAT_PL_MAX_SAMPLE — all before any launch.  G == 0 returns DIGAT_OK
+ * without a launch.  Stream-ordered: one workgroup per (list, sample), one launch per 2^23 lists x 65 535 samples; no atomics, no
+ * allocation, no host synchronisation, no read of device memory on the host.  The workspace is not used
+ * (digat_pl_sample_workspace_bytes returns 0; workspace may be NULL). */
+#define DIGAT_PL_MAX_LIST 1024
+#define DIGAT_PL_MAX_K 128
+#define DIGAT_PL_MAX_SAMPLE (1 << 22)
+#define DIGAT_PL_CLAMP (-700.0)
+size_t digat_pl_sample_workspace_bytes(int64_t lists, int m, int k, int64_t samples);
+int digat_pl_sample(const float* scores, const int32_t* count, int64_t G, int M, int k, double inv_t, uint32_t seed, int64_t samples,
+                    int64_t first_sample, const int64_t* streams, int32_t* out_picks, int32_t* out_n, double* out_logp, float* out_step,
+                    void* workspace, size_t workspace_bytes, void* stream);
+int digat_pl_log_prob(const float* scores, const int32_t* count, int64_t G, int M, int k, double inv_t, int64_t samples, const int32_t* picks,
+                      double* out_logp, float* out_step, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- bootstrap resampling of per-unit metric rows (digat_amd.evaluate.bootstrap_sums / metric_intervals / compare_metrics) -----
  * values [n, c] float64 row-major: one row per resampling unit (an impression, a user), one column per summed quantity;
  * sums [B, c] float64.  Replicate r = first_replicate + b makes n draws with replacement; draw j has the 64-bit counter

@@ -73,6 +73,15 @@
                                              turn, median [min, max] of five rounds, time and peak device bytes; then recommend(calibration=)
                                              in {0, 0.3, 0.5, 0.8} on 512 held-out impressions of the planted-signal corpus: kl,
                                              category_max_share, recall@10 and MRR with intervals, paired against calibration 0
+  python tools/kbench.py pl-sample [rounds demo]   stochastic lists: evaluate.pl_sample (one workgroup per slate: hash, two float64 logs, a
+                                             1024-record sort, the probability as a suffix sum) against rand + double log + topk + gather
+                                             + flipped logcumsumexp in stock PyTorch, chunked to 1 GiB, (G, M, k, S) in {64, 4 096} x
+                                             {128, 1 024} x {10, 100} x {1, 8}, the legs in turn, median [min, max] of five rounds, time
+                                             and peak device bytes
+  python tools/kbench.py off-policy [users k samples truth_samples replicates]   off-policy evaluation on the planted-signal corpus: the
+                                             trained DIGAT logs slates with propensities (util.recommend_slates), colder and hotter
+                                             target policies are valued on the log (score_lists, slate_log_prob, off_policy_value: IPS
+                                             and SNIPS with intervals, ess / n) beside their true on-policy value
   python tools/kbench.py list-quality [news_num d]   list quality: evaluate.list_quality (one launch, the Gram in LDS) against the same
                                              figures from gather + torch.bmm, the upper triangle's sum and max, a sort for the
                                              categories, a broadcast compare for the overlap and torch.bincount for the exposure,
@@ -2015,6 +2024,123 @@ def demo_calibrate(users=512, k=10, calibrations=(0.0, 0.3, 0.5, 0.8), replicate
         print(line, flush=True)
 
 
+def stock_pl_sample(scores, count, k, temperature, samples, budget=1 << 30):
+    """Plackett-Luce slates with their log-probabilities built only from stock PyTorch — what the tree offered before
+    ``digat_pl_sample``: ``torch.rand`` -> two float64 logarithms -> add -> ``torch.topk`` -> gather -> the unpicked tail's
+    ``logsumexp`` and a flipped ``logcumsumexp`` over the picks -> sum, over as many lists at a time as keep the [g, S, M] float64
+    intermediates (noise, keys, the masked copy, topk's workspace) inside ``budget`` bytes.  Its draws are ``torch.rand``'s: not
+    reproducible bit for bit across batch shapes, and not the contract's (a yardstick for speed and memory).  Every list is taken
+    to hold at least k live entries."""
+    G, M = scores.shape
+    dev = scores.device
+    a = scores.to(torch.float64) / temperature
+    a = torch.where(torch.arange(M, device=dev)[None, :] < count[:, None], a, torch.full((), float("-inf"), dtype=torch.float64, device=dev))
+    picks = torch.empty((G, samples, k), dtype=torch.int64, device=dev)
+    logp = torch.empty((G, samples), dtype=torch.float64, device=dev)
+    rows = max(1, budget // (samples * M * 8 * 4))
+    for g0 in range(0, G, rows):
+        ag = a[g0:g0 + rows, None, :].expand(-1, samples, -1)
+        key = ag - torch.log(-torch.log(torch.rand(ag.shape, dtype=torch.float64, device=dev)))
+        idx = key.topk(k, dim=2).indices
+        mine = ag.gather(2, idx)
+        tail = ag.scatter(2, idx, float("-inf")).logsumexp(dim=2, keepdim=True)
+        lse = torch.cat([mine, tail], dim=2).flip(2).logcumsumexp(dim=2).flip(2)[:, :, :k]
+        picks[g0:g0 + rows] = idx
+        logp[g0:g0 + rows] = (mine - lse).sum(dim=2)
+    return picks, logp
+
+
+def bench_pl_sample(rounds=5, demo=0):
+    """``evaluate.pl_sample`` against ``stock_pl_sample``, the two legs in turn in one process, median [min, max] of ``rounds``
+    rounds and each leg's peak of device bytes beyond its inputs: (G, M, k, S) in {64, 4 096} x {128, 1 024} x {10, 100} x {1, 8},
+    scores N(0, 1) sorted as a shortlist comes, T = 1.  The two legs draw different slates (another generator), so the check beside
+    the times is statistical: the mean ``logp`` of either leg's slates."""
+    from digat_amd import evaluate
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device="cpu").manual_seed(0)
+
+    def peak(fn):
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        out = fn()
+        torch.cuda.synchronize()
+        return out, torch.cuda.max_memory_allocated() - base
+    print(f"pl-sample: Plackett-Luce slates of k from lists of M scores, S samples per list, T = 1; ms per call, median [min, max] of "
+          f"{rounds} rounds", flush=True)
+    for G in (64, 4096):
+        for M in (128, 1024):
+            scores = torch.randn(G, M, generator=g).sort(dim=1, descending=True).values.to(dev)
+            count = torch.full((G,), M, dtype=torch.int32, device=dev)
+            for k in (10, 100):
+                for S in (1, 8):
+                    ours = lambda: evaluate.pl_sample(scores, count, k, 1.0, seed=1, samples=S)
+                    stock = lambda: stock_pl_sample(scores, count, k, 1.0, S)
+                    (got, pa), (want, pb) = peak(ours), peak(stock)
+                    ma, mb = float(got[2].mean()), float(want[1].mean())
+                    (a, alo, ahi), (b, blo, bhi) = alternate(ours, stock, rounds=rounds, iters=5)
+                    print(f"  G = {G:5d}, M = {M:4d}, k = {k:3d}, S = {S}: pl_sample {a:8.3f} ms [{alo:.3f}, {ahi:.3f}] ({1e3 * a / (G * S):.2f} us "
+                          f"per slate, peak {pa / 2**20:.2f} MiB) | stock composition {b:8.3f} ms [{blo:.3f}, {bhi:.3f}] (x{b / a:.2f}, peak "
+                          f"{pb / 2**20:.1f} MiB) | mean logp {ma:.3f} vs {mb:.3f}", flush=True)
+            del scores, count
+    torch.cuda.empty_cache()
+    if demo:
+        demo_off_policy()
+
+
+def demo_off_policy(users=2000, k=3, samples=4, truth_samples=64, replicates=2000):
+    """Off-policy evaluation end to end on the planted-signal corpus.  The LOGGING policy: the trained DIGAT
+    (tests/golden/trained_planted_state.npz), ``util.recommend_slates`` over ``users`` held-out impressions against the pool of all
+    news — a shortlist of 8 k, ``samples`` slates of k per user at temperature T_log (the mean spread — standard deviation — of a
+    user's shortlist scores, so that the policy is neither uniform nor the arg-max).  The TARGET policies: the same scores at other
+    temperatures (T_log / 2, colder: nearer the plain list; 2 T_log, hotter).  Reward of a slate: its mean planted match
+    (``synthetic.planted_reward``: 1 for a news of a preferred sub-topic, 1/2 for its category).  Per target: ``util.score_lists``
+    on the logged shortlists, ``util.slate_log_prob`` of the logged slates, ``evaluate.off_policy_value`` (users kept together);
+    beside it the target's TRUE value: ``truth_samples`` slates per user drawn from the target itself on the same shortlists."""
+    import types
+    from digat_amd import evaluate, synthetic, util
+    from digat_amd.model import Model, PrecomputedNewsEncoder
+    dev = torch.device("cuda:0")
+    golden = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
+    state = {name: v for name, v in np.load(os.path.join(golden, "trained_planted_state.npz")).items()}
+    depth = int(np.load(os.path.join(golden, "devset_trained_2k.npz"))["depth"])
+    full = synthetic.make_corpus(synthetic.SynthSpec(**synthetic.PLANTED_SPEC))
+    pref, news_sub = synthetic.planted_match(full)
+    corpus = synthetic.slice_impressions(full, 0, users)
+    spec = full.spec
+    cfg = types.SimpleNamespace(news_encoder="MSA", graph_encoder="DIGAT", news_graph_size=spec.news_graph_size,
+                                max_history_num=spec.max_history_num, category_num=spec.category_num, graph_depth=depth, dropout_rate=0.2)
+    model = Model(cfg, news_encoder=PrecomputedNewsEncoder(torch.from_numpy(corpus.news_embedding)))
+    model.graph_encoder.load_state_dict({name: torch.from_numpy(v) for name, v in state.items()})
+    model = model.to(dev).eval()
+    dc = util.DeviceCorpus.from_numpy(corpus, dev)
+    who = np.arange(users, dtype=np.int64)
+    pool = np.arange(1, spec.news_num, dtype=np.int64)
+    reward = lambda slates: synthetic.planted_reward(pref[:users], news_sub, slates.cpu().numpy(), spec.subtopics_per_category)
+    short = util.recommend(model, dc, who, pool, 8 * k)
+    t_log = float(short[1].to(torch.float64).std(dim=1).mean())
+    log = util.recommend_slates(model, dc, who, pool, k, t_log, samples=samples, seed=1)
+    r_log = reward(log["slates"]).reshape(-1)
+    plain = float(reward(short[0][:, None, :k]).mean())
+    units = np.arange(0, users * samples + 1, samples)
+    print(f"off-policy demo: planted-signal corpus, the trained DIGAT logs {samples} slates of k = {k} for each of {users} held-out "
+          f"impressions from a shortlist of {8 * k} at T_log = {t_log:.4f}; reward = mean planted match of the slate; logged mean reward "
+          f"{r_log.mean():.4f} (the plain top-{k}: {plain:.4f}); intervals: 95 %, {replicates} replicates over users", flush=True)
+    for name, t_target in (("colder", t_log / 2), ("hotter", 2 * t_log)):
+        scores = util.score_lists(model, dc, who, log["ids"], log["count"])
+        lt, _, covered = util.slate_log_prob(log["ids"], scores, log["count"], log["slates"], t_target)
+        out = evaluate.off_policy_value(r_log, lt.cpu().numpy().reshape(-1), log["logp"].cpu().numpy().reshape(-1), units=units,
+                                        replicates=replicates)
+        own = util.sample_lists(log["ids"], scores, log["count"], k, t_target, seed=2, samples=truth_samples, streams=torch.as_tensor(who))
+        truth = float(reward(own[0]).mean())
+        sn, ip = out["snips"], out["ips"]
+        print(f"  target {name} (T = {t_target:.4f}): SNIPS {sn['value']:.4f} [{sn['lo']:.4f}, {sn['hi']:.4f}]  IPS {ip['value']:.4f} "
+              f"[{ip['lo']:.4f}, {ip['hi']:.4f}]  truth (on-policy, {truth_samples} slates per user) {truth:.4f}  the SNIPS interval holds it: "
+              f"{sn['lo'] <= truth <= sn['hi']}  ess / n {out['ess'] / out['n']:.3f}  max weight {out['max_weight']:.1f}  covered "
+              f"{float(covered.float().mean()):.3f}", flush=True)
+
+
 def torch_list_quality(ids, count, vectors, category=None, base_ids=None, base_count=None, exposure=None):
     """``evaluate.list_quality``'s figures built only from stock PyTorch: gather + ``torch.bmm``, the upper triangle's sum (in double)
     and max, a sort per list for the categories, a broadcast compare for the overlap, ``torch.bincount`` for the exposure."""
@@ -2210,6 +2336,10 @@ if __name__ == "__main__":
         bench_list_quality(*nums)
     elif what == "calibrate":
         bench_calibrate(*nums)
+    elif what == "pl-sample":
+        bench_pl_sample(*nums)
+    elif what == "off-policy":
+        demo_off_policy(*nums)
     elif what == "bootstrap":
         bench_bootstrap(*nums)
     elif what == "linear":
