@@ -895,3 +895,4 @@ int digat_row_logits(const float* news_ctx, const float* user_ctx, float* logits
 #include "digat_bootstrap.inc"
 #include "digat_calibrate.inc"
 #include "digat_pl_sample.inc"
+#include "digat_list_pl.inc"

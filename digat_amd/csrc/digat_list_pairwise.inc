@@ -231,7 +231,7 @@ __global__ void __launch_bounds__(256) lpw_users_kernel(const LpwArgs a) {
     const int tid = threadIdx.x;
     const long g = blockIdx.x;
     const int cnt = lsm_count(a.l, g);
-    const float gl = a.l.grad_loss[g];
+    const float gl = a.l.grad_loss ? a.l.grad_loss[g] : 1.f;          // NULL: lambda is the coefficient itself (digat_list_pl.inc)
     bool live = false;
 #pragma unroll
     for (int s = 0; s < LSM_SLABS; ++s) {

@@ -118,9 +118,11 @@ __device__ __forceinline__ void pl_stage_list(const PlArgs& a, long g, PlShared&
     }
 }
 
-// The probability of the slate sh.pick[0 .. n_out) — live, distinct positions — under sh.a: out_step[0 .. k) and *out_logp.  Called
-// by the whole workgroup behind a barrier that made sh.a and sh.pick visible.
-__device__ __forceinline__ void pl_prob_stage(PlShared& sh, int k, int n_out, double* out_logp, float* out_step) {
+// The weights and the suffix sums of the slate sh.pick[0 .. n_out) — live, distinct positions — under sh.a: behind it sh.w holds the
+// weights with the picked slots at 0, sh.wpick / sh.d / sh.z [0 .. n_out) the picked weights, d_t and Z_t.  Called by the whole
+// workgroup behind a barrier that made sh.a and sh.pick visible; ends behind a barrier.  pl_prob_stage's first half, and all that
+// digat_list_pl.inc's lpl_coef_kernel needs of it.
+__device__ __forceinline__ void pl_z_stage(PlShared& sh, int n_out) {
 #pragma clang fp contract(off)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     double m = -INFINITY;
@@ -167,6 +169,13 @@ __device__ __forceinline__ void pl_prob_stage(PlShared& sh, int k, int n_out, do
         }
     }
     __syncthreads();
+}
+
+// The probability of the slate sh.pick[0 .. n_out) under sh.a: out_step[0 .. k) and *out_logp.  Called as pl_z_stage is.
+__device__ __forceinline__ void pl_prob_stage(PlShared& sh, int k, int n_out, double* out_logp, float* out_step) {
+#pragma clang fp contract(off)
+    const int tid = threadIdx.x;
+    pl_z_stage(sh, n_out);
     if (tid < k) {
         double v = 0.0;
         if (tid < n_out) v = sh.d[tid] - log(sh.z[tid]);
@@ -222,12 +231,11 @@ __global__ void __launch_bounds__(256) pl_sample_kernel(const PlArgs a) {
     pl_prob_stage(sh, a.k, n_out, a.out_logp + row, a.out_step + row * a.k);
 }
 
-__global__ void __launch_bounds__(256) pl_log_prob_kernel(const PlArgs a) {
-    __shared__ PlShared sh;
+// Row `row` of a.picks_in into sh.pick, cut in front of its first entry that is negative, out of range, not live or a repeat of an
+// earlier one: the slate's length.  The whole workgroup; its first barrier also makes sh.a visible.  pl_log_prob_kernel's rule, and
+// through this function digat_list_pl.inc's.
+__device__ __forceinline__ int pl_cut_slate(const PlArgs& a, size_t row, PlShared& sh) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long g = a.g0 + blockIdx.x, s = a.s0 + blockIdx.y;
-    const size_t row = (size_t)g * (size_t)a.S + (size_t)s;
-    pl_stage_list(a, g, sh);
     int p = -1;
     if (tid < a.k) {
         p = a.picks_in[row * a.k + tid];
@@ -243,6 +251,15 @@ __global__ void __launch_bounds__(256) pl_log_prob_kernel(const PlArgs a) {
     int n_out = a.k;                                 // the slate ends in front of the first bad entry
 #pragma unroll
     for (int w = 0; w < 4; ++w) n_out = sh.cut[w] < n_out ? sh.cut[w] : n_out;
+    return n_out;
+}
+
+__global__ void __launch_bounds__(256) pl_log_prob_kernel(const PlArgs a) {
+    __shared__ PlShared sh;
+    const long g = a.g0 + blockIdx.x, s = a.s0 + blockIdx.y;
+    const size_t row = (size_t)g * (size_t)a.S + (size_t)s;
+    pl_stage_list(a, g, sh);
+    const int n_out = pl_cut_slate(a, row, sh);
     pl_prob_stage(sh, a.k, n_out, a.out_logp + row, a.out_step + row * a.k);
 }
 

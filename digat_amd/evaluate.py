@@ -1101,13 +1101,14 @@ def list_softmax_bound(lse, x_max, tau_max=0.0, loss=None):
     return u * (np.abs(x_max) * np.minimum(2.0, np.sqrt(2.0 * np.abs(loss))) + np.abs(loss)) + 2.0 * e64
 
 
-def _check_list_softmax_args(users, rows, ids, count, teacher, temperature):
+def _check_list_args(users, rows, ids, count, name="list_softmax"):
+    """The list checks every per-list entry shares (``list_softmax``, ``list_pl``): ``(G, P, M, d)``."""
     import torch
     if users.dim() != 2 or rows.dim() != 2 or users.shape[1] != rows.shape[1] or users.shape[1] < 1:
         raise ValueError(f"users [G, d] and rows [P, d] must share d >= 1, got {tuple(users.shape)} and {tuple(rows.shape)}")
     G, d, P = int(users.shape[0]), int(users.shape[1]), int(rows.shape[0])
     if d > LIST_SOFTMAX_MAX_D:
-        raise ValueError(f"list_softmax takes vectors of at most LIST_SOFTMAX_MAX_D = {LIST_SOFTMAX_MAX_D} channels, got {d}")
+        raise ValueError(f"{name} takes vectors of at most LIST_SOFTMAX_MAX_D = {LIST_SOFTMAX_MAX_D} channels, got {d}")
     if ids.dim() != 2 or ids.shape[0] != G or ids.dtype in (torch.float16, torch.float32, torch.float64, torch.bool):
         raise ValueError(f"ids must be an integer tensor [G = {G}, M], got {tuple(ids.shape)} {ids.dtype}")
     M = int(ids.shape[1])
@@ -1115,10 +1116,15 @@ def _check_list_softmax_args(users, rows, ids, count, teacher, temperature):
         raise ValueError(f"a list holds between 1 and SHORTLIST_MAX_K = {SHORTLIST_MAX_K} slots, got M = {M}")
     if G * M >= 1 << 31:
         raise ValueError(f"G x M must stay below 2^31, got {G} x {M}")
-    if tuple(teacher.shape) != (G, M) or not teacher.is_floating_point():
-        raise ValueError(f"teacher must be a floating-point tensor with one value per slot {(G, M)}, got {tuple(teacher.shape)} {teacher.dtype}")
     if count is not None and (tuple(count.shape) != (G,) or count.dtype in (torch.float16, torch.float32, torch.float64, torch.bool)):
         raise ValueError(f"count must be an integer tensor with one entry per list ({G}), got {tuple(count.shape)} {count.dtype}")
+    return G, P, M, d
+
+
+def _check_list_softmax_args(users, rows, ids, count, teacher, temperature):
+    G, P, M, d = _check_list_args(users, rows, ids, count)
+    if tuple(teacher.shape) != (G, M) or not teacher.is_floating_point():
+        raise ValueError(f"teacher must be a floating-point tensor with one value per slot {(G, M)}, got {tuple(teacher.shape)} {teacher.dtype}")
     if not float(temperature) > 0.0 or float(temperature) == float("inf"):
         raise ValueError(f"temperature must be a positive finite number, got {temperature}")
     return G, P, M, d
@@ -2818,6 +2824,341 @@ def pl_log_prob(scores, count, picks, temperature):
     _lib.check(L.digat_pl_log_prob(sc.data_ptr(), _lib.ptr(ct), G, M, k, inv_t, S, pk.data_ptr(), logp.data_ptr(), step.data_ptr(),
                                    ws.data_ptr(), need, _lib.stream_ptr()), "digat_pl_log_prob")
     return logp, step
+
+
+# ---- the differentiable Plackett-Luce slate likelihood over a user's own list: csrc/digat_list_pl.inc -----------------------------
+def _pl_inv_t(scale, temperature) -> float:
+    """``inv_t = fl(float64(scale) * fl(1.0 / float64(temperature)))`` of ``list_pl``, checked: what the kernels multiply a score by."""
+    t, s = float(temperature), float(scale)
+    if not 0.0 < t < float("inf"):                                  # a NaN fails both comparisons
+        raise ValueError(f"temperature must be positive and finite, got {temperature}")
+    if not 0.0 < s < float("inf"):
+        raise ValueError(f"scale must be positive and finite, got {scale}")
+    with np.errstate(over="ignore"):
+        inv_t = float(np.float64(s) * (np.float64(1.0) / np.float64(t)))
+    if not (inv_t > 0.0 and inv_t * _FLT_MAX < float("inf")):
+        raise ValueError(f"scale / temperature = {scale} / {temperature} must stay positive and keep score * scale / temperature finite in float64")
+    return inv_t
+
+
+def _list_pl_host_parts(scores, ids, count, picks, rows_num, inv_t):
+    sc = np.array(_host(scores), dtype=np.float32)
+    if sc.ndim != 2:
+        raise ValueError("scores must be [G, M]")
+    G, M = sc.shape
+    pk = np.asarray(_host(picks))
+    if pk.dtype.kind not in "iu":
+        raise ValueError(f"picks must hold integer positions, got {pk.dtype}")
+    k = int(pk.shape[2]) if pk.ndim == 3 else 0
+    _check_pl_args(sc.shape, None if count is None else np.shape(count), k, 1.0, picks_shape=pk.shape)
+    if ids is not None:
+        I = np.asarray(_host(ids))
+        if I.shape != (G, M) or I.dtype.kind not in "iu":
+            raise ValueError(f"ids must be an integer array of shape {(G, M)}, got {I.shape} {I.dtype}")
+        sc[~((I >= 0) & (I < int(rows_num)))] = np.nan                # no element: no mass
+    sc, live, a = _pl_lists_host(sc, count, inv_t)
+    return sc, live, a, pk, k
+
+
+def _pl_slate_grad_host(a, live, picks, n):
+    """``(dlogp / da [M], 1[j in the slate] + w_j H_n [M])`` of one slate of length ``n`` (``_pl_slate_host``'s), float64."""
+    import math
+    M = len(a)
+    dl, ab = np.zeros(M), np.zeros(M)
+    if n == 0:
+        return dl, ab
+    w = np.where(live, np.exp(np.maximum(a - a[live].max(), PL_CLAMP)), 0.0)
+    left = live.copy()
+    recip = []
+    for t in range(n):
+        p = int(picks[t])
+        recip.append(1.0 / np.float64(math.fsum(w[left].tolist())))
+        dl[p] = 1.0 - w[p] * np.float64(math.fsum(recip))
+        ab[p] = 1.0
+        left[p] = False
+    Hn = np.float64(math.fsum(recip))
+    dl[left] = -(w[left] * Hn)
+    ab += w * Hn
+    return dl, ab
+
+
+def list_pl_host(scores, ids, count, picks, rows_num, scale=1.0, temperature=1.0, grad_logp=None, parts: bool = False):
+    """The contract of ``digat_list_pl_fwd`` and of the coefficient kernel on given scores ``scores`` [G, M] float32 (slot (g, j) holds
+    the inner product of user g with row ``ids[g, j]``), in numpy float64 with ``math.fsum`` — the yardstick of the kernels.  A slot
+    is an element when ``j < clip(count[g], 0, M)`` and ``0 <= ids[g, j] < rows_num`` (``ids`` None: the first condition alone —
+    ``pl_scores``' rule); a position is LIVE when it is an element and its score is finite.  ``a = float64(score) * inv_t`` with
+    ``inv_t = float64(scale) * (1.0 / float64(temperature))``; from there on ``logp`` [G, S] float64 and ``step_logp`` [G, S, k]
+    float32 are ``pl_log_prob_host``'s on ``a`` — the slates' cut rule, the clamp at -700, the ``fsum`` suffix sums, 0 for an empty
+    slate.  With ``grad_logp`` [G, S] the float64 ``coef`` [G, M] is returned too: ``w_j = exp(max(a_j - a_max, -700))``, ``Z_t`` the
+    ``fsum`` of ``w`` over the live positions not picked before step t, ``H_t = sum_{u < t} 1 / Z_u``, n the slate's length,
+    ``dlogp / da_j = -w_j H_n`` (live, not in the slate), ``1 - w_j H_{t+1}`` (``j = picks[t]``), 0 (not live) — ``a_max`` and the
+    clamp held constant — and ``coef[g, j] = inv_t * fsum_s(grad_logp[g, s] * dlogp_s / da_j)``; a slate that is empty or whose
+    ``grad_logp`` is 0 adds nothing.  ``parts`` adds a dict: ``logZ`` and ``step`` [G, S, k] float64, ``live`` [G], ``length`` [G, S]
+    and, with ``grad_logp``, ``absolute`` [G, M] = ``|inv_t| sum_s |grad_logp[g, s]| (1[j in slate s] + w_j H_n)``, what
+    ``list_pl_bound`` takes."""
+    import math
+    inv_t = _pl_inv_t(scale, temperature)
+    sc, live, a, pk, k = _list_pl_host_parts(scores, ids, count, picks, rows_num, inv_t)
+    G, M = sc.shape
+    S = int(pk.shape[1])
+    gl = None if grad_logp is None else np.asarray(_host(grad_logp), dtype=np.float64)
+    if gl is not None and gl.shape != (G, S):
+        raise ValueError(f"grad_logp must have one entry per slate {(G, S)}, got {gl.shape}")
+    logp, step, logz = np.zeros((G, S)), np.zeros((G, S, k)), np.zeros((G, S, k))
+    length = np.zeros((G, S), dtype=np.int32)
+    coef, absolute = np.zeros((G, M)), np.zeros((G, M))
+    for g in range(G):
+        terms, aterms = [], []
+        for s in range(S):
+            logp[g, s], step[g, s], logz[g, s], length[g, s] = _pl_slate_host(a[g], live[g], pk[g, s], k)
+            if gl is not None and length[g, s] > 0 and gl[g, s] != 0.0:
+                dl, ab = _pl_slate_grad_host(a[g], live[g], pk[g, s], int(length[g, s]))
+                terms.append(gl[g, s] * dl)
+                aterms.append(abs(gl[g, s]) * ab)
+        if terms:
+            coef[g] = [inv_t * math.fsum(col) for col in np.stack(terms, axis=1).tolist()]
+            absolute[g] = [abs(inv_t) * math.fsum(col) for col in np.stack(aterms, axis=1).tolist()]
+    out = (logp, step.astype(np.float32)) + (() if gl is None else (np.where(live, coef, 0.0),))
+    if parts:
+        d = {"step": step, "logZ": logz, "live": live.sum(axis=1), "length": length}
+        if gl is not None:
+            d["absolute"] = np.where(live, absolute, 0.0)
+        out += (d,)
+    return out
+
+
+def list_pl_grad_host(users, rows, scores, ids, count, picks, scale=1.0, temperature=1.0, grad_logp=None):
+    """The contract of ``digat_list_pl_bwd`` in numpy float64: with ``coef`` of ``list_pl_host`` on ``scores`` (``grad_logp`` None:
+    ones), ``d_users[g] = sum_j coef[g, j] rows[ids[g, j]]`` and ``d_rows[p]`` = the sum of ``coef[g, j] users[g]`` over the live slots
+    with ``ids[g, j] == p``.  Returns ``(d_users [G, d], d_rows [P, d])``."""
+    U, R = np.asarray(users, dtype=np.float64), np.asarray(rows, dtype=np.float64)
+    if U.ndim != 2 or R.ndim != 2 or U.shape[1] != R.shape[1]:
+        raise ValueError(f"users [G, d] and rows [P, d] must share d, got {U.shape} and {R.shape}")
+    pk = np.asarray(_host(picks))
+    gl = np.ones(pk.shape[:2]) if grad_logp is None else grad_logp
+    coef = list_pl_host(scores, ids, count, pk, R.shape[0], scale, temperature, grad_logp=gl)[2]
+    if U.shape[0] != coef.shape[0]:
+        raise ValueError(f"users must have one row per list ({coef.shape[0]}), got {U.shape}")
+    I = np.asarray(_host(ids)).astype(np.int64)
+    g_of, j_of = np.nonzero(coef != 0)
+    d_users, d_rows = np.zeros_like(U), np.zeros_like(R)
+    np.add.at(d_users, g_of, coef[g_of, j_of][:, None] * R[I[g_of, j_of]])
+    np.add.at(d_rows, I[g_of, j_of], coef[g_of, j_of][:, None] * U[g_of])
+    return d_users, d_rows
+
+
+def list_pl_bound(n, k, samples, coef, absolute):
+    """The error bound csrc/digat_list_pl.inc derives for the float32 ``coef`` of ``list_pl`` / ``pl_scores`` against ``list_pl_host``
+    on the same scores: ``2^-24 |coef| + (n + k + S + 20) 2^-53 A + 2^-149`` — ``n`` [G] the live positions of the list, ``k`` the
+    slate length, ``S`` the slates per list (their terms are added one after the other), ``A`` = ``absolute`` of ``list_pl_host``'s
+    parts, the sum the cancelling terms are measured against.  ``logp`` and ``step_logp`` carry ``pl_bound`` unchanged."""
+    c = np.abs(np.asarray(coef, dtype=np.float64))
+    A = np.abs(np.asarray(absolute, dtype=np.float64))
+    n = np.asarray(n, dtype=np.float64).reshape(-1, 1)
+    return 2.0 ** -24 * c + (n + float(k) + float(samples) + 20.0) * 2.0 ** -53 * A + 2.0 ** -149
+
+
+def _check_picks(picks, G: int):
+    import torch
+    if picks.is_floating_point() or picks.dtype == torch.bool:
+        raise ValueError(f"picks must hold integer positions, got {picks.dtype}")
+    if picks.dim() != 3 or int(picks.shape[0]) != G or int(picks.shape[1]) < 1 or not 1 <= int(picks.shape[2]) <= PL_MAX_K:
+        raise ValueError(f"picks must be [G = {G}, S >= 1, k] with 1 <= k <= PL_MAX_K = {PL_MAX_K}, got {tuple(picks.shape)}")
+    return int(picks.shape[1]), int(picks.shape[2])
+
+
+def _pl_stock(S, live, picks, inv_t):
+    """The stock composition on scores ``S`` [G, M] (differentiable), in their dtype: a gather of the picks, ``logsumexp`` of the
+    unpicked tail and a flipped ``logcumsumexp`` — ``(logp [G, S], step [G, S, k])`` with ``pl_log_prob``'s cut rule for the slates.
+    A position without mass holds a huge negative FINITE number in place of -inf: ``logcumsumexp``'s backward divides by its result."""
+    import torch
+    G, M = int(S.shape[0]), int(S.shape[1])
+    Sn, k = int(picks.shape[1]), int(picks.shape[2])
+    low = torch.finfo(S.dtype).min / 8
+    a = (torch.where(live, S, torch.zeros_like(S)) * inv_t).masked_fill(~live, low)
+    pk = picks.to(torch.int64)
+    pc = pk.clamp(0, M - 1)
+    flat = pc.view(G, Sn * k)
+    earlier = torch.ones(k, k, dtype=torch.bool, device=S.device).tril(-1)
+    bad = (pk < 0) | (pk >= M) | ~live.gather(1, flat).view(G, Sn, k) | ((pk[:, :, :, None] == pk[:, :, None, :]) & earlier).any(dim=3)
+    keep = bad.to(torch.int64).cumsum(dim=2) == 0
+    ap = torch.where(keep, a.gather(1, flat).view(G, Sn, k), a.new_full((), low))
+    picked = torch.zeros((G, Sn, M), dtype=torch.int32, device=S.device).scatter_add_(2, pc, keep.to(torch.int32)) > 0
+    tail = torch.logsumexp(a[:, None, :].expand(G, Sn, M).masked_fill(picked, low), dim=2)
+    logZ = torch.logcumsumexp(torch.cat([tail[:, :, None], ap.flip(2)], dim=2), dim=2)[:, :, 1:].flip(2)
+    step = torch.where(keep, ap - logZ, torch.zeros_like(ap))
+    return step.sum(dim=2), step
+
+
+def _list_pl_functions():
+    import torch
+    from . import _lib
+
+    class ListPL(torch.autograd.Function):
+        """``digat_list_pl_fwd`` / ``digat_list_pl_bwd``; the scores are saved, and the sorted entry keys of the rows kernel are built
+        here, in the forward: the ids carry no gradient."""
+
+        @staticmethod
+        def forward(ctx, users, rows, ids, cnt, picks, inv_t):
+            u, v = users.detach().float().contiguous(), rows.detach().float().contiguous()
+            G, M, P, d = int(u.shape[0]), int(ids.shape[1]), int(v.shape[0]), int(u.shape[1])
+            S, k = int(picks.shape[1]), int(picks.shape[2])
+            logp = torch.empty((G, S), dtype=torch.float64, device=u.device)
+            step = torch.empty((G, S, k), dtype=torch.float32, device=u.device)
+            scores = torch.empty((G, M), dtype=torch.float32, device=u.device)
+            _lib.check(_lib.lib().digat_list_pl_fwd(u.data_ptr(), v.data_ptr(), ids.data_ptr(), _lib.ptr(cnt), G, P, M, d, picks.data_ptr(),
+                                                    S, k, inv_t, logp.data_ptr(), step.data_ptr(), scores.data_ptr(), _lib.stream_ptr()),
+                       "digat_list_pl_fwd")
+            keys = None
+            if ctx.needs_input_grad[1]:
+                elem = list_elements(ids, cnt, P).view(-1)
+                flat = torch.arange(G * M, device=u.device)
+                keys = torch.sort(ids.view(-1)[elem] * (G * M) + flat[elem]).values.contiguous()
+            ctx.save_for_backward(u, v, ids, picks, scores)
+            ctx.cnt, ctx.keys, ctx.inv_t, ctx.dtypes = cnt, keys, inv_t, (users.dtype, rows.dtype)
+            ctx.mark_non_differentiable(step, scores)
+            return logp, step, scores
+
+        @staticmethod
+        def backward(ctx, grad_logp, _step, _scores):
+            u, v, ids, picks, scores = ctx.saved_tensors
+            G, d, P, M = int(u.shape[0]), int(u.shape[1]), int(v.shape[0]), int(ids.shape[1])
+            f = dict(dtype=torch.float32, device=u.device)
+            want_rows = ctx.needs_input_grad[1] and ctx.keys is not None
+            d_users = torch.empty((G, d), **f)
+            d_rows = torch.empty((P, d), **f) if want_rows else None
+            gl = grad_logp.to(torch.float64).contiguous()
+            L = _lib.lib()
+            need = int(L.digat_list_pl_workspace_bytes(G, M))
+            ws = _lib.workspace(need, u.device, "list_pl")
+            keys = ctx.keys if want_rows else None
+            _lib.check(L.digat_list_pl_bwd(u.data_ptr(), v.data_ptr(), ids.data_ptr(), _lib.ptr(ctx.cnt), G, P, M, d, scores.data_ptr(),
+                                           picks.data_ptr(), int(picks.shape[1]), int(picks.shape[2]), ctx.inv_t, gl.data_ptr(),
+                                           _lib.ptr(keys) if keys is not None and keys.numel() else None,
+                                           0 if keys is None else int(keys.numel()), d_users.data_ptr(), _lib.ptr(d_rows), ws.data_ptr(),
+                                           need, _lib.stream_ptr()), "digat_list_pl_bwd")
+            return (d_users.to(ctx.dtypes[0]) if ctx.needs_input_grad[0] else None), (None if d_rows is None else d_rows.to(ctx.dtypes[1])), \
+                None, None, None, None
+
+    class PLScores(torch.autograd.Function):
+        """``pl_log_prob``'s call as it is; the backward is the coefficient kernel alone (``digat_pl_scores_bwd``)."""
+
+        @staticmethod
+        def forward(ctx, scores, cnt, picks, temperature, inv_t):
+            sc = scores.detach().float().contiguous()                 # any floating dtype, as list_pl takes users and rows
+            logp, step = pl_log_prob(sc, cnt, picks, temperature)
+            ctx.save_for_backward(sc, picks)
+            ctx.cnt, ctx.inv_t, ctx.dtype = cnt, inv_t, scores.dtype
+            ctx.mark_non_differentiable(step)
+            return logp, step
+
+        @staticmethod
+        def backward(ctx, grad_logp, _step):
+            sc, picks = ctx.saved_tensors
+            G, M = int(sc.shape[0]), int(sc.shape[1])
+            grad = torch.empty((G, M), dtype=torch.float32, device=sc.device)
+            gl = grad_logp.to(torch.float64).contiguous()
+            _lib.check(_lib.lib().digat_pl_scores_bwd(sc.data_ptr(), _lib.ptr(ctx.cnt), G, M, int(picks.shape[2]), ctx.inv_t,
+                                                      int(picks.shape[1]), picks.data_ptr(), gl.data_ptr(), grad.data_ptr(),
+                                                      _lib.stream_ptr()), "digat_pl_scores_bwd")
+            return grad.to(ctx.dtype), None, None, None, None
+
+    return ListPL, PLScores
+
+
+_ListPL = None
+
+
+def list_pl(users, rows, ids, count, picks, scale=1.0, temperature=1.0):
+    """The log-probability of GIVEN slates under the Plackett-Luce model of every user's OWN list, differentiable: ``(logp [G, S]
+    float64, step_logp [G, S, k] float32, scores [G, M] float32)``.  ``users`` [G, d], ``rows`` [P, d], ``ids`` [G, M] integer rows
+    of ``rows`` and ``count`` [G] (None: M) as in ``list_softmax``: slot (g, j) is an element when ``j < clip(count[g], 0, M)`` and
+    ``0 <= ids[g, j] < P``; ``scores`` = the inner products at elements (``dot_scores``' bits), NaN elsewhere.  A position is LIVE
+    when it is an element and its score is finite.  ``picks`` [G, S, k] are integer positions into the list, ``1 <= k <= PL_MAX_K``;
+    a slate ends at its first entry that is negative, out of range, not live or repeated (``pl_log_prob``'s rule).  With ``a =
+    float64(score) * inv_t``, ``inv_t = float64(scale) * (1.0 / float64(temperature))``, ``logp`` and ``step_logp`` are
+    ``pl_log_prob_host``'s on ``a``: the probability of the slate under ``softmax(scale * <user, news> / temperature)`` drawn without
+    replacement — 0 for an empty slate.  At ``scale = 1`` they are ``pl_log_prob``'s bits on ``scores``.
+
+    ``logp`` is differentiable in ``users`` and ``rows``; ``step_logp`` and ``scores`` are not, and ``picks`` gets no gradient.  The
+    gradient is the closed form of ``list_pl_host`` — O(M + k) per slate, no [G, S, M] tensor — and treats ``a_max`` and the clamp at
+    -700 as constants: it is the exact gradient while no live entry sits on the clamp (keep ``score * scale / temperature`` spreads
+    below 700).  Uses: the likelihood of a logged slate (learning from a log), REINFORCE on sampled slates, and ListMLE with ``picks``
+    the ground-truth order.  M <= ``SHORTLIST_MAX_K`` = 1024, d <= ``LIST_SOFTMAX_MAX_D`` = 512, G M < 2^31.
+
+    On CUDA tensors: ``digat_list_pl_fwd`` / ``_bwd`` under autograd — no [G, M, d] gather in memory, no float atomics: two calls give
+    the same bits in every output and gradient.  On CPU tensors: the stock composition — ``index_select``, ``bmm``, a gather of the
+    picks, ``logsumexp`` of the unpicked tail, a flipped ``logcumsumexp`` — in the dtype of ``users``, differentiable by autograd."""
+    import torch
+    global _ListPL
+    cnt = None if count is None else torch.as_tensor(count)
+    if users.dim() != 2 or ids.dim() != 2 or not users.is_floating_point() or not rows.is_floating_point():
+        raise ValueError(f"users [G, d] and rows [P, d] must be floating-point matrices and ids [G, M], got {tuple(users.shape)} {users.dtype}, "
+                         f"{tuple(rows.shape)} {rows.dtype} and {tuple(ids.shape)}")
+    G, P, M, d = _check_list_args(users, rows, ids, cnt, "list_pl")
+    S, k = _check_picks(picks, G)
+    inv_t = _pl_inv_t(scale, temperature)
+    dev = users.device
+    if any(t.device != dev for t in (rows, ids, picks) + (() if cnt is None else (cnt,))):
+        raise ValueError("users, rows, ids, count and picks must live on one device")
+    ids = ids.to(torch.int64).contiguous()
+    if dev.type == "cuda":
+        if _ListPL is None:
+            _ListPL = _list_pl_functions()
+        if G == 0 or P == 0:                                          # nothing is live: every slate is empty, no launch, a zero gradient
+            z = torch.zeros((G, S), dtype=torch.float64, device=dev) + 0.0 * (users.double().sum() + rows.double().sum())
+            return z, users.new_zeros((G, S, k), dtype=torch.float32), users.new_full((G, M), float("nan"), dtype=torch.float32)
+        pk = torch.clamp(picks, min=-1, max=PL_MAX_LIST).to(torch.int32).contiguous()
+        return _ListPL[0].apply(users, rows, ids, None if cnt is None else cnt.to(torch.int32).contiguous(), pk, inv_t)
+    elem = list_elements(ids, cnt, P)
+    safe = torch.where(elem, ids, torch.zeros_like(ids)).view(-1)
+    if P == 0:
+        Sc = users.new_zeros((G, M)) + 0.0 * (users.sum() + rows.sum())
+    else:
+        gathered = rows.index_select(0, safe).view(G, M, d)                                              # [G, M, d]
+        Sc = torch.bmm(gathered, users.unsqueeze(2)).squeeze(2)
+    shown = torch.where(elem, Sc.detach(), Sc.new_full((G, M), float("nan")))
+    live = elem & torch.isfinite(Sc.detach())
+    if P > 0 and not bool(live[elem].all()):                          # a row without mass must not meet the backward: 0 * inf is a NaN
+        Sc = torch.bmm(torch.where(live[:, :, None], gathered, torch.zeros_like(gathered)), users.unsqueeze(2)).squeeze(2)
+    logp, step = _pl_stock(Sc, live, picks, inv_t)
+    return logp, step.detach(), shown
+
+
+def pl_scores(scores, count, picks, temperature):
+    """``list_pl``'s likelihood on GIVEN scores ``scores`` [G, M] — a model whose score is no inner product, through autograd on its
+    own logits: ``(logp [G, S] float64, step_logp [G, S, k] float32)``.  A position is live when ``j < clip(count[g], 0, M)``
+    (``count`` None: M) and its score is finite; ``picks`` as in ``list_pl``.  The forward is ``pl_log_prob``'s call unchanged — its
+    bits —; ``logp`` is differentiable in ``scores``: the gradient is ``list_pl_host``'s coefficient at ``scale = 1`` (``a_max`` and the
+    clamp held constant), exactly 0 at every position that is not live.  On CUDA tensors the kernels read float32: ``scores`` of
+    another floating dtype are converted first and the gradient comes back in their dtype; ``digat_pl_log_prob`` and
+    ``digat_pl_scores_bwd`` (the coefficient kernel of ``list_pl``: the same bits on the same scores); on CPU tensors the stock
+    composition in the dtype of ``scores``."""
+    import torch
+    global _ListPL
+    if scores.dim() != 2 or not scores.is_floating_point():
+        raise ValueError(f"scores must be a floating-point tensor [G, M], got {tuple(scores.shape)} {scores.dtype}")
+    cnt = None if count is None else torch.as_tensor(count)
+    G, M = int(scores.shape[0]), int(scores.shape[1])
+    k = int(picks.shape[2]) if picks.dim() == 3 else 0
+    inv_t = _check_pl_args((G, M), None if cnt is None else tuple(cnt.shape), k, temperature, picks_shape=tuple(picks.shape))
+    _check_picks(picks, G)
+    dev = scores.device
+    if picks.device != dev or (cnt is not None and cnt.device != dev):
+        raise ValueError("scores, count and picks must live on one device")
+    if dev.type == "cuda":
+        if _ListPL is None:
+            _ListPL = _list_pl_functions()
+        S = int(picks.shape[1])
+        if G == 0:
+            return torch.zeros((0, S), dtype=torch.float64, device=dev) + 0.0 * scores.double().sum(), scores.new_zeros((0, S, k), dtype=torch.float32)
+        pk = torch.clamp(picks, min=-1, max=PL_MAX_LIST).to(torch.int32).contiguous()
+        return _ListPL[1].apply(scores, None if cnt is None else cnt.to(torch.int32).contiguous(), pk, temperature, inv_t)
+    live = torch.isfinite(scores.detach())
+    if cnt is not None:
+        live = live & (torch.arange(M)[None, :] < cnt.to(torch.int64).clamp(0, M)[:, None])
+    logp, step = _pl_stock(torch.where(live, scores, torch.zeros_like(scores)), live, picks, inv_t)
+    return logp, step.detach()
 
 
 def off_policy_value(reward, logp_target, logp_logging, clip=None, units=None, replicates: int = 2000, level: float = 0.95, seed: int = 0):

@@ -1183,6 +1183,160 @@ def impression_gain_lists(train, users=None):
     return idx, ids, gain, n
 
 
+# ---- policy gradient: the Plackett-Luce likelihood of slates over per-user lists (evaluate.list_pl) -----------------------------
+def _slate_tensor(x, dims, G, name, device, floating):
+    """A per-slate argument of ``policy_step`` as a tensor on ``device`` (a tensor already there is not copied), checked."""
+    t = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
+    if t.dim() != dims or int(t.shape[0]) != G or t.is_floating_point() != floating or t.dtype == torch.bool:
+        raise ValueError(f"{name} must be {'a floating-point' if floating else 'an integer'} array with {dims} axes, the first of length "
+                         f"{G}, got {tuple(t.shape)} {t.dtype}")
+    return t.to(device)
+
+
+def policy_step(model, train, users, ids, slates, weight, count=None, scale=1.0, temperature=1.0):
+    """One policy-gradient step's loss for the first stage, with its graph — ``distil_step``'s twin on ``evaluate.list_pl``: for every
+    user of ``users`` (impression indices of ``train``) and every slate ``slates[g, s]`` (news ids [G, S, k], -1 ends a slate; matched
+    to positions of the user's OWN list ``ids[g, :count[g]]`` with ``util.slate_positions``) the log-probability ``logp[g, s]`` of the
+    slate under the Plackett-Luce policy ``softmax(scale * <user, news> / temperature)`` drawn without replacement.  ``weight`` [G, S]
+    is a constant per slate — an advantage, a clipped importance weight times a reward, or 1 for maximum likelihood (ListMLE when the
+    slate is the ground-truth order).  The loss is ``-sum(weight * logp)`` divided by the number of slates that have a non-zero
+    weight and a non-empty cut (by 1 when there is none).  Returns ``(loss, logp.detach() [G, S])`` — the second for importance
+    weights.  The compact pool, the encoders and the devices are ``distil_step``'s; the model's mode (dropout) is the caller's."""
+    from . import evaluate, util
+    ids_in = _host_array(ids)
+    idx, ids, _, count = _check_lists(users, ids_in, np.zeros(np.shape(ids_in), dtype=np.float32), count, int(train.history_ids.shape[0]))
+    user, table, pos, cnt, _ = _list_front(model, train, idx, ids, count)
+    dev = user.device
+    G = len(idx)
+    sl = _slate_tensor(slates, 3, G, "slates", dev, False)
+    wt = _slate_tensor(weight, 2, G, "weight", dev, True)
+    if tuple(wt.shape) != tuple(sl.shape[:2]):
+        raise ValueError(f"weight must have one entry per slate {tuple(sl.shape[:2])}, got {tuple(wt.shape)}")
+    picks = util.slate_positions(torch.from_numpy(ids).to(dev), cnt, sl)
+    logp, _, scores = evaluate.list_pl(user, table, pos, cnt, picks, scale=scale, temperature=temperature)
+    first = picks[:, :, 0].to(torch.int64)
+    begun = (first >= 0) & torch.isfinite(scores.gather(1, first.clamp(min=0)))       # the cut is not empty: its first entry is live
+    wt = wt.to(logp.dtype)
+    n = ((wt != 0) & begun).sum().clamp(min=1)
+    return -(wt * logp).sum() / n, logp.detach()
+
+
+def _list_scores(model, train, idx, ids, count):
+    """The batch's list scores without a graph — ``list_softmax``'s forward, as ``evaluate.refine_lists`` uses it: ``(scores [G, M]
+    float32-or-model dtype, NaN at slots that are no element, count [G] int32)``."""
+    from . import evaluate
+    with torch.no_grad():
+        user, table, pos, cnt, _ = _list_front(model, train, idx, ids, count)
+        _, _, scores = evaluate.list_softmax(user, table, pos, cnt, torch.zeros(pos.shape, dtype=user.dtype, device=user.device))
+    return scores, cnt
+
+
+def slate_ndcg(gain, picks, k: int):
+    """The nDCG@k of slates: ``gain`` [G, M] (NaN, an infinity or a negative value: 0), ``picks`` [G, S, k'] positions (-1: no
+    entry) -> [G, S] float64: the slate's DCG under ``evaluate.ndcg_discount(k', k)`` over the list's ideal DCG@k; 0 where that is 0."""
+    from . import evaluate
+    G, S, kk = (int(x) for x in picks.shape)
+    g = torch.where(torch.isfinite(gain) & (gain > 0), gain, torch.zeros_like(gain)).to(torch.float64)
+    disc = torch.from_numpy(evaluate.ndcg_discount(kk, k)).to(g.device)
+    at = picks.to(torch.int64)
+    got = torch.where(at >= 0, g.gather(1, at.clamp(min=0).view(G, S * kk)).view(G, S, kk), torch.zeros((), dtype=torch.float64, device=g.device))
+    dcg = (got * disc).sum(dim=2)
+    top = g.sort(dim=1, descending=True).values[:, :kk]
+    idcg = (top * disc[:top.shape[1]]).sum(dim=1)
+    return torch.where(idcg[:, None] > 0, dcg / idcg.clamp(min=1e-300)[:, None], torch.zeros_like(dcg))
+
+
+def fit_policy(model, train, lists, steps, k=10, samples=4, temperature=1.0, batch_users=64, lr=1e-4, seed=0, scale=1.0, optimizer=None):
+    """On-policy REINFORCE on the expected nDCG@k of a sampled slate: ``steps`` times, on the same seeded draw of ``batch_users``
+    lists as ``fit_ranker`` and ``distil_retriever`` make, (1) the batch's lists are scored without a graph (``list_softmax``'s
+    forward), (2) ``samples`` Plackett-Luce slates of ``k`` are drawn per list from ``softmax(scale * score / temperature)``
+    (``evaluate.pl_sample`` with the impression index as stream and ``first_sample = step * samples``; CPU tensors:
+    ``pl_sample_host``), (3) a slate's reward is its nDCG@k against ``gain`` (``slate_ndcg``), its weight the reward minus the mean
+    reward of the list's OTHER samples (leave-one-out; the reward itself when ``samples == 1``), (4) one ``policy_step``, one
+    backward, one optimizer step, in train mode.  The lists are therefore scored twice a step, and the two passes draw their own
+    dropout masks; the sampler also takes ``temperature / scale`` as its temperature, so its ``1 / (T / scale)`` and the gradient's
+    ``scale * (1 / T)`` may differ in the last bit — harmless for REINFORCE, whose weights do not use the sampler's ``logp``.
+    ``lists = (users [U], ids [U, M], gain [U, M], count [U] or None)`` is ``fit_ranker``'s format
+    (``impression_gain_lists``).  Returns ``(losses, mean rewards)`` per step as Python floats."""
+    from . import evaluate
+    if not (isinstance(lists, (tuple, list)) and len(lists) == 4):
+        raise ValueError("lists must be (users [U], ids [U, M], gain [U, M], count [U] or None)")
+    users, ids, gain, count = _check_lists(*lists[:3], lists[3], int(train.history_ids.shape[0]))
+    if len(users) == 0:
+        raise ValueError("no list to train on")
+    k, samples = int(k), int(samples)
+    evaluate._check_pl_args((1, ids.shape[1]), None, k, float(temperature) / float(scale), samples, max(int(steps) - 1, 0) * samples)
+    optimizer = _retriever_optimizer(model, lr, optimizer)
+    rng = np.random.default_rng(seed)
+    model.train()
+    losses, rewards = [], []
+    for step in range(int(steps)):
+        b = np.sort(rng.choice(len(users), size=min(int(batch_users), len(users)), replace=False))
+        scores, cnt = _list_scores(model, train, users[b], ids[b], count[b])
+        dev = scores.device
+        if dev.type == "cuda":
+            picks = evaluate.pl_sample(scores, cnt, k, float(temperature) / float(scale), seed, samples, step * samples,
+                                       torch.from_numpy(users[b]).to(dev))[0]
+        else:
+            picks = torch.from_numpy(evaluate.pl_sample_host(scores.float().numpy(), cnt.numpy(), k, float(temperature) / float(scale), seed,
+                                                             samples, step * samples, users[b])[0])
+        at = picks.to(torch.int64)
+        idt = torch.from_numpy(ids[b]).to(dev)
+        slates = torch.where(at >= 0, idt.gather(1, at.clamp(min=0).view(len(b), -1)).view(at.shape), torch.full_like(at, -1))
+        r = slate_ndcg(torch.from_numpy(gain[b]).to(dev), picks, k)
+        weight = r if samples == 1 else r - (r.sum(dim=1, keepdim=True) - r) / (samples - 1)
+        optimizer.zero_grad()
+        loss, _ = policy_step(model, train, users[b], ids[b], slates, weight, count[b], scale=scale, temperature=temperature)
+        loss.backward()
+        optimizer.step()
+        losses.append(float(loss.detach()))
+        rewards.append(float(r.mean()))
+    return losses, rewards
+
+
+def fit_from_logs(model, train, log, reward, steps, clip=10.0, users=None, batch_users=64, lr=1e-4, seed=0, scale=1.0, temperature=None,
+                  optimizer=None):
+    """Off-policy training on a log of slates with their propensities: maximise the clipped-IPS value ``evaluate.off_policy_value``
+    reports.  ``log`` is the dict ``util.recommend_slates`` returns — ``ids`` [U, M], ``count`` [U], ``slates`` [U, S, k] news ids,
+    ``logp`` [U, S] the logging policy's log-probabilities, ``temperature`` — for the impression indices ``users`` [U] (or
+    ``log["users"]``); ``reward`` [U, S]; ``temperature`` None: the log's.  Every step takes ``fit_ranker``'s seeded draw of
+    ``batch_users`` lists and scores them TWICE: a first ``policy_step`` without a graph gives ``logp_now`` and the importance
+    weights ``w = exp(logp_now - logp_logged)``; a slate's weight is ``w * reward`` where ``w < clip`` and 0 where it is clipped —
+    the gradient of ``mean(min(w, clip) * reward)`` in the model, ``w`` held as a number —; the second ``policy_step`` carries the
+    graph.  Both passes draw their own dropout masks in train mode.  Returns the per-step losses as Python floats."""
+    users = log.get("users") if users is None else users
+    if users is None:
+        raise ValueError("name the impression indices of the log's rows: users=, or log['users']")
+    idx = _host_array(users).astype(np.int64)
+    ids, count, slates = _host_array(log["ids"]).astype(np.int64), _host_array(log["count"]).astype(np.int64), _host_array(log["slates"]).astype(np.int64)
+    logged, rw = _host_array(log["logp"]).astype(np.float64), _host_array(reward).astype(np.float64)
+    U = len(idx)
+    if ids.ndim != 2 or slates.ndim != 3 or len(ids) != U or len(slates) != U or count.shape != (U,) or logged.shape != slates.shape[:2] \
+            or rw.shape != logged.shape:
+        raise ValueError("log must hold ids [U, M], count [U], slates [U, S, k] and logp [U, S] for the U users, and reward must be [U, S]")
+    if U == 0:
+        raise ValueError("no list to train on")
+    if not float(clip) > 0.0:
+        raise ValueError(f"clip must be positive, got {clip}")
+    temperature = float(log["temperature"]) if temperature is None else float(temperature)
+    optimizer = _retriever_optimizer(model, lr, optimizer)
+    rng = np.random.default_rng(seed)
+    model.train()
+    losses = []
+    for _ in range(int(steps)):
+        b = np.sort(rng.choice(U, size=min(int(batch_users), U), replace=False))
+        with torch.no_grad():
+            _, now = policy_step(model, train, idx[b], ids[b], slates[b], np.zeros(rw[b].shape), count[b], scale=scale, temperature=temperature)
+        w = torch.exp(now.to(torch.float64) - torch.from_numpy(logged[b]).to(now.device))
+        weight = torch.where(w < float(clip), w * torch.from_numpy(rw[b]).to(now.device), torch.zeros_like(w))
+        optimizer.zero_grad()
+        loss, _ = policy_step(model, train, idx[b], ids[b], slates[b], weight, count[b], scale=scale, temperature=temperature)
+        loss.backward()
+        optimizer.step()
+        losses.append(float(loss.detach()))
+    return losses
+
+
 def teacher_agreement(student_ids, student_count, teacher_ids, teacher_count, ks=(10,)):
     """How much of the teacher's top-k the student's list holds: per user the share of the first ``min(k, teacher_count[g])`` slots of
     ``teacher_ids`` [G, kt] — a list ordered best first, as ``util.recommend`` returns it — whose id stands anywhere in

@@ -1165,20 +1165,24 @@ def slate_positions(ids: torch.Tensor, count, slates: torch.Tensor) -> torch.Ten
     return picks
 
 
-def slate_log_prob(ids: torch.Tensor, scores: torch.Tensor, count, slates, temperature: float):
+def slate_log_prob(ids: torch.Tensor, scores: torch.Tensor, count, slates, temperature: float, differentiable: bool = False):
     """The probability of GIVEN slates under other scores — a logged slate under another model: ``slates`` [G,S,k] news ids are
     matched to positions of ``ids`` [G,M] (``slate_positions``) and ``evaluate.pl_log_prob`` (CPU tensors:
     ``evaluate.pl_log_prob_host``) gives ``logp`` [G,S] float64 and ``step_logp`` [G,S,k] float32 under ``softmax(scores /
     temperature)``.  A news that is absent from the list — or whose score there is not finite — ends the slate at that slot.
     Returns ``(logp, step_logp, covered [G,S] bool)``: ``covered`` says that every news of the slate (every slot with an id >= 0)
-    was found and counted."""
+    was found and counted.  ``differentiable=True`` routes through ``evaluate.pl_scores``: the same ``logp`` bits on the device,
+    with a gradient in ``scores`` — a DIGAT or ablation model whose list scores carry a graph can be trained on a log
+    (``-(weight * logp).sum()``); on CPU tensors the stock composition in the dtype of ``scores``."""
     sl = _tensor_on(slates, ids.device)
     if sl.dim() != 3 or int(sl.shape[0]) != int(ids.shape[0]) or sl.is_floating_point():
         raise ValueError(f"slates must be integer news ids [G = {int(ids.shape[0])}, S, k], got {tuple(sl.shape)} {sl.dtype}")
     if ids.dim() != 2 or tuple(scores.shape) != tuple(ids.shape):
         raise ValueError(f"ids and scores must both be [G, M], got {tuple(ids.shape)} and {tuple(scores.shape)}")
     picks = slate_positions(ids, count, sl)
-    if ids.is_cuda:
+    if differentiable:
+        logp, step = evaluate.pl_scores(scores, count, picks, temperature)
+    elif ids.is_cuda:
         logp, step = evaluate.pl_log_prob(scores, count, picks, temperature)
     else:
         logp, step = map(torch.from_numpy, evaluate.pl_log_prob_host(scores.numpy(), None if count is None else count.numpy(), picks.numpy(),

@@ -935,6 +935,46 @@ int digat_pl_sample(const float* scores, const int32_t* count, int64_t G, int M,
 int digat_pl_log_prob(const float* scores, const int32_t* count, int64_t G, int M, int k, double inv_t, int64_t samples, const int32_t* picks,
                       double* out_logp, float* out_step, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- differentiable Plackett-Luce slate likelihood over a user's own list (digat_amd.evaluate.list_pl / pl_scores) -------------
+ * users [G, d], rows [P, d], ids [G, M] int64, count [G] int32 (NULL: M) as in digat_list_softmax_fwd: slot (g, j) is an ELEMENT
+ * when j < clamp(count[g], 0, M) and 0 <= ids[g, j] < P; 1 <= M <= DIGAT_SHORTLIST_MAX_K, 1 <= d <= DIGAT_LIST_SOFTMAX_MAX_D,
+ * G M < 2^31.  picks [G, samples, k] int32: positions into the list, 1 <= k <= DIGAT_PL_MAX_K, samples >= 1.
+ * inv_t = fl(scale * fl(1.0 / temperature)) in float64, computed by the caller: scale and temperature enter nowhere else.
+ * digat_list_pl_fwd scores every list — out_scores [G, M] f32: digat_dot_scores' bits at elements, NaN elsewhere, as
+ * digat_list_softmax_fwd writes them — and runs digat_pl_log_prob's probability stage on them inside the same workgroup: a position is
+ * LIVE when it is an element and its score is finite, a_j = (double)score_j * inv_t, a slate ends in front of its first entry that is
+ * negative, >= M, not live or a repeat; out_logp [G, samples] f64 and out_step [G, samples, k] f32 are digat_pl_log_prob's bits on
+ * (out_scores, count, inv_t, picks).  Every output byte is written whatever count and picks hold.
+ * The gradient holds a_max and the clamp constant (exact while no live entry sits on the clamp).  With w_j and Z_t as above,
+ * H_t = sum_{u < t} 1 / Z_u and n the slate's length: dlogp/da_j = -w_j H_n (j live, not in the slate), 1 - w_j H_{t+1} (j = pick(t)),
+ * 0 (j not live);  coef(g, j) = fl32(inv_t * sum_s grad_logp[g, s] * dlogp_s/da_j), exactly 0 at every slot that is not live.  A slate
+ * that is empty or whose grad_logp is 0 contributes nothing.
+ * digat_pl_scores_bwd writes coef [G, M] for GIVEN scores [G, M] f32 (live: p < clamp(count[g], 0, M) and the score finite), the
+ * gradient of digat_pl_log_prob's out_logp in scores at inv_t = 1 / temperature.
+ * digat_list_pl_bwd takes digat_list_pl_fwd's out_scores as scores, writes coef into the workspace [G, M] f32
+ * (digat_list_pl_workspace_bytes) and forms digat_list_softmax_bwd's two sums from it, in its order and with its kernels:
+ * d_users [G, d] = sum_j coef(g, j) rows[ids[g, j]], d_rows [P, d] (may be NULL) = the sum of coef(g, j) users[g] over the elements
+ * with ids[g, j] == p; entry_keys [E] int64 as in digat_list_softmax_bwd.
+ * One workgroup per list runs its slates in ascending order: every order of addition is fixed by (M, d, count, ids, the slates), no
+ * floating-point atomics — the same bits from run to run and for a list alone or in a batch.  Against evaluate.list_pl_host, out_logp
+ * and out_step stay within evaluate.pl_bound and coef within evaluate.list_pl_bound (derived in csrc/digat_list_pl.inc).
+ * DIGAT_ERR_ARG: a null users / ids / picks / scores / grad_logp / out pointer (rows may be NULL when P == 0), a misaligned pointer
+ * (4 bytes; 8 for ids, out_logp, grad_logp and entry_keys), G < 0, P < 0, inv_t not positive or inv_t * FLT_MAX not finite, E outside
+ * [0, G M] or E > 0 without keys, a null workspace with G > 0; DIGAT_ERR_SHAPE: M, d, k outside their ranges, samples < 1,
+ * G M >= 2^31, P > 2^31; DIGAT_ERR_WORKSPACE: fewer bytes than digat_list_pl_workspace_bytes(G, M) — all before any launch.
+ * G == 0 returns DIGAT_OK without a list launch (digat_list_pl_bwd still zeroes d_rows).  Stream-ordered; no allocation, no host
+ * synchronisation. */
+size_t digat_list_pl_workspace_bytes(int64_t lists, int m);
+int digat_list_pl_fwd(const float* users, const float* rows, const int64_t* ids, const int32_t* count, int64_t G, int64_t P, int M, int d,
+                      const int32_t* picks, int64_t samples, int k, double inv_t, double* out_logp, float* out_step, float* out_scores,
+                      void* stream);
+int digat_pl_scores_bwd(const float* scores, const int32_t* count, int64_t G, int M, int k, double inv_t, int64_t samples,
+                        const int32_t* picks, const double* grad_logp, float* out_grad, void* stream);
+int digat_list_pl_bwd(const float* users, const float* rows, const int64_t* ids, const int32_t* count, int64_t G, int64_t P, int M, int d,
+                      const float* scores, const int32_t* picks, int64_t samples, int k, double inv_t, const double* grad_logp,
+                      const int64_t* entry_keys, int64_t E, float* d_users, float* d_rows, void* workspace, size_t workspace_bytes,
+                      void* stream);
+
 /* ---- bootstrap resampling of per-unit metric rows (digat_amd.evaluate.bootstrap_sums / metric_intervals / compare_metrics) -----
  * values [n, c] float64 row-major: one row per resampling unit (an impression, a user), one column per summed quantity;
  * sums [B, c] float64.  Replicate r = first_replicate + b makes n draws with replacement; draw j has the 64-bit counter

@@ -73,6 +73,12 @@
                                              turn, median [min, max] of five rounds, time and peak device bytes; then recommend(calibration=)
                                              in {0, 0.3, 0.5, 0.8} on 512 held-out impressions of the planted-signal corpus: kl,
                                              category_max_share, recall@10 and MRR with intervals, paired against calibration 0
+  python tools/kbench.py list-pl [d rounds demo]   policy gradient: evaluate.list_pl (fused Plackett-Luce slate likelihood over per-user lists and
+                                             its closed-form gradient) against index_select + bmm + gather + logsumexp + flipped logcumsumexp
+                                             under autograd, chunked to 1 GiB, (G, M, k, S) in {64, 4 096} x {128, 1 024} x {10, 100} x {1, 8},
+                                             forward and forward + backward, time and peak device bytes
+  python tools/kbench.py policy              nrms.fit_policy beside fit_ranker and the click softmax on the planted-signal corpus, and
+                                             nrms.fit_from_logs on a log the trained DIGAT makes, with intervals
   python tools/kbench.py pl-sample [rounds demo]   stochastic lists: evaluate.pl_sample (one workgroup per slate: hash, two float64 logs, a
                                              1024-record sort, the probability as a suffix sum) against rand + double log + topk + gather
                                              + flipped logcumsumexp in stock PyTorch, chunked to 1 GiB, (G, M, k, S) in {64, 4 096} x
@@ -2141,6 +2147,222 @@ def demo_off_policy(users=2000, k=3, samples=4, truth_samples=64, replicates=200
               f"{float(covered.float().mean()):.3f}", flush=True)
 
 
+def stock_list_pl(users, rows, ids, count, picks, inv_t, backward=False, budget=1 << 30):
+    """The summed ``logp`` of ``evaluate.list_pl`` from stock PyTorch under autograd in float32 — ``index_select`` + ``torch.bmm``, then
+    ``evaluate._pl_stock``: a gather of the picks, ``logsumexp`` of the unpicked tail, a flipped ``logcumsumexp`` — the lists in chunks
+    whose [g, M, d] gather and [g, S, M] intermediates (the expanded scores, the mask, the masked copy) hold ``budget`` bytes.
+    ``backward``: every chunk is differentiated as soon as it stands.  Every id is a row in the benchmark's data."""
+    from digat_amd import evaluate
+    G, M = ids.shape
+    S, d = int(picks.shape[1]), int(users.shape[1])
+    step = max(1, budget // (4 * (M * d + 4 * S * M)))
+    slot = torch.arange(M, device=ids.device)
+    total = torch.zeros((), dtype=torch.float32, device=ids.device)
+    for lo in range(0, G, step):
+        sl = slice(lo, lo + step)
+        g = ids[sl].shape[0]
+        x = torch.bmm(rows.index_select(0, ids[sl].reshape(-1)).view(g, M, -1), users[sl].unsqueeze(2)).squeeze(2)
+        logp = evaluate._pl_stock(x, slot[None, :] < count[sl][:, None], picks[sl], inv_t)[0].sum()
+        if backward:
+            logp.backward()
+        total = total + logp.detach()
+    return total
+
+
+def bench_list_pl(d=400, rounds=5, demo=0):
+    """``evaluate.list_pl`` (the fused Plackett-Luce slate likelihood and its gradients: no [G, M, d] gather, no [G, S, M] tensor, no
+    float atomics) against ``stock_list_pl`` (float32, chunked to 1 GiB) under autograd, in one process, the legs taken in turn,
+    median [min, max] of ``rounds`` rounds of three calls, and each leg's peak of device bytes beyond its inputs; forward alone
+    (``no_grad``) and forward + backward; (G, M, k, S) in {64, 4 096} x {128, 1 024} x {10, 100} x {1, 8}, a compact pool.  Then
+    (``demo``) ``demo_policy``."""
+    from digat_amd import evaluate
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device="cpu").manual_seed(0)
+    stat = lambda v: (sorted(v)[len(v) // 2], min(v), max(v))
+
+    def peak(fn):
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        out = fn()
+        torch.cuda.synchronize()
+        out = float(out)
+        return out, torch.cuda.max_memory_allocated() - base
+    print(f"list-pl: d = {d}, compact pool, scale = 1, T = 1; ms per call, median [min, max] of {rounds} rounds", flush=True)
+    for G in (64, 4096):
+        for M in (128, 1024):
+            P = max(M, min(65237, G * M // 4))
+            rows = (torch.randn(P, d, generator=g) / d ** 0.5).to(dev)
+            users = (3.0 * torch.randn(G, d, generator=g)).to(dev)
+            ids = torch.stack([torch.randperm(P, generator=g)[:M] for _ in range(G)]).to(dev)
+            count = torch.randint(M * 3 // 4, M + 1, (G,), generator=g).to(torch.int32).to(dev)
+            for k in (10, 100):
+                for S in (1, 8):
+                    noise = torch.rand(G, S, M, generator=g).to(dev)
+                    noise = noise.masked_fill(torch.arange(M, device=dev)[None, None, :] >= count[:, None, None], 2.0)
+                    order = noise.argsort(dim=2)[:, :, :k]
+                    picks = torch.where(order < count[:, None, None], order, torch.full_like(order, -1)).to(torch.int32).contiguous()
+                    del noise, order
+
+                    def fused_fwd():
+                        with torch.no_grad():
+                            return evaluate.list_pl(users, rows, ids, count, picks)[0].sum()
+
+                    def stock_fwd():
+                        with torch.no_grad():
+                            return stock_list_pl(users, rows, ids, count, picks, 1.0)
+
+                    def fused_both():
+                        u, t = users.detach().requires_grad_(True), rows.detach().requires_grad_(True)
+                        logp = evaluate.list_pl(u, t, ids, count, picks)[0].sum()
+                        logp.backward()
+                        return logp.detach() + 0.0 * (u.grad[0, 0] + t.grad[0, 0])
+
+                    def stock_both():
+                        u, t = users.detach().requires_grad_(True), rows.detach().requires_grad_(True)
+                        logp = stock_list_pl(u, t, ids, count, picks, 1.0, backward=True)
+                        return logp + 0.0 * (u.grad[0, 0] + t.grad[0, 0])
+                    legs = (fused_fwd, stock_fwd, fused_both, stock_both)
+                    peaks = [peak(fn) for fn in legs]
+                    times = [[] for _ in legs]
+                    for _ in range(rounds):
+                        for leg, fn in zip(times, legs):
+                            leg.append(timeit(fn, iters=3, warm=1)[0])
+                    (a, alo, ahi), (b, blo, bhi), (c, clo, chi), (e, elo, ehi) = (stat(t) for t in times)
+                    print(f"  G = {G:5d}, M = {M:4d}, k = {k:3d}, S = {S}: forward: list_pl {a:8.3f} ms [{alo:.3f}, {ahi:.3f}] (peak "
+                          f"{peaks[0][1] / 2**20:.2f} MiB) | stock {b:8.3f} ms [{blo:.3f}, {bhi:.3f}] (x{b / a:.2f}, peak {peaks[1][1] / 2**20:.1f} MiB) "
+                          f"|| forward + backward: list_pl {c:8.3f} ms [{clo:.3f}, {chi:.3f}] (peak {peaks[2][1] / 2**20:.1f} MiB) | stock {e:8.3f} ms "
+                          f"[{elo:.3f}, {ehi:.3f}] (x{e / c:.2f}, peak {peaks[3][1] / 2**20:.1f} MiB) | summed logp {peaks[0][0]:.1f} vs stock "
+                          f"{peaks[1][0]:.1f}", flush=True)
+                    del picks
+            del rows, users, ids, count
+            torch.cuda.empty_cache()
+    if demo:
+        demo_policy()
+
+
+def demo_policy(train_users=2048, steps=300, k=10, samples=4, log_users=2000, replicates=2000):
+    """The demonstration runs of the policy-gradient surface on the planted-signal corpus, in ``demo_rank``'s setting (NRMS at d = 64,
+    random titles, ``train_users`` training impressions, ``steps`` steps of 64 lists, lr 1e-3, the same seeded draws).  (1) Three copies
+    of one model: ``nrms.fit_policy`` (REINFORCE on the expected nDCG@``k`` of ``samples`` sampled slates), ``nrms.fit_ranker`` and the
+    listwise click softmax; held-out AUC / MRR / nDCG with ``evaluate.compare_metrics``.  (2) ``nrms.fit_from_logs``: the trained DIGAT
+    logs slates for ``log_users`` held-out impressions (``demo_off_policy``'s log and reward); a fresh NRMS is trained on the log; it
+    is judged by the mean reward of its OWN slates on the logged shortlists before and after, and by ``evaluate.off_policy_value`` of
+    its likelihoods on the log.  Beside it: what the graph-free first scoring pass of a ``fit_from_logs`` step costs."""
+    import copy
+    import time
+    import types
+    from digat_amd import evaluate, nrms, synthetic, util
+    from digat_amd.model import Model, PrecomputedNewsEncoder
+    dev = torch.device("cuda:0")
+    full = synthetic.make_corpus(synthetic.SynthSpec(**synthetic.PLANTED_SPEC))
+    spec = full.spec
+    N, H, Lw, V = spec.news_num, spec.max_history_num, 16, 4000
+    text, mask = synthetic.make_titles(N, Lw, V, seed=2)
+
+    def part(lo, hi):
+        c = synthetic.slice_impressions(full, lo, hi)
+        hist = torch.from_numpy(c.history.astype(np.int64)).to(dev)
+        return types.SimpleNamespace(title_text=torch.from_numpy(text).to(dev), title_mask=torch.from_numpy(mask).to(dev),
+                                     augmented_title_text=None, augmented_title_mask=None, history_ids=hist, history_mask=hist != 0,
+                                     row_candidate=c.row_candidate.astype(np.int64), row_impression=c.row_impression, row_label=c.row_label)
+    held, train = part(0, synthetic.PLANTED_DEV_IMPRESSIONS), part(synthetic.PLANTED_DEV_IMPRESSIONS, spec.impressions)
+    base = _nrms_model("NRMS", V=V, dm=64, h=8, dk=8, att=32, Lw=Lw, H=H, dropout=0.2)
+    policy, ranker, softmax, student = (copy.deepcopy(base) for _ in range(4))
+    tu = np.arange(train_users, dtype=np.int64)
+    gains, clicks = nrms.impression_gain_lists(train, tu), nrms.impression_lists(train, tu)
+    labels = np.asarray(held.row_label)
+
+    def rows_of(model):
+        scores, _, metrics = nrms.compute_scores(model, held)
+        return evaluate.impression_metrics(scores, held.row_impression, labels), metrics
+    print(f"policy demo (1): planted-signal corpus, NRMS at d = 64, random titles; {len(gains[0])} training impressions of up to "
+          f"{gains[1].shape[1]} candidates; held-out: {int(held.history_ids.shape[0])} impressions", flush=True)
+    print("  before: AUC %.4f MRR %.4f nDCG@5 %.4f nDCG@10 %.4f" % rows_of(base)[1], flush=True)
+    t0 = time.perf_counter()
+    l_pol, r_pol = nrms.fit_policy(policy, train, gains, steps, k=k, samples=samples, batch_users=64, lr=1e-3, seed=0)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    l_rank = nrms.fit_ranker(ranker, train, gains, steps, batch_users=64, lr=1e-3, seed=0, k=k)
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    nrms.distil_retriever(softmax, train, clicks, steps, batch_users=64, lr=1e-3, seed=0)
+    torch.cuda.synchronize()
+    t3 = time.perf_counter()
+    print(f"  fit_policy (k = {k}, {samples} samples): {1e3 * (t1 - t0) / steps:.1f} ms per step, mean reward (nDCG@{k} of a sampled slate) "
+          f"{np.mean(r_pol[:10]):.4f} (first ten steps) -> {np.mean(r_pol[-10:]):.4f} (last ten); fit_ranker {1e3 * (t2 - t1) / steps:.1f} ms per "
+          f"step; the click softmax {1e3 * (t3 - t2) / steps:.1f} ms per step", flush=True)
+    (rp, mp), (rr, mr), (rs, ms) = rows_of(policy), rows_of(ranker), rows_of(softmax)
+    for name, m in (("fit_policy", mp), ("fit_ranker", mr), ("the click softmax", ms)):
+        print(f"  after {name}: " + "AUC %.4f MRR %.4f nDCG@5 %.4f nDCG@10 %.4f" % m, flush=True)
+    for other, rows in (("fit_ranker", rr), ("click softmax", rs)):
+        cmp_ = evaluate.compare_metrics(rp, rows, names=("AUC", "MRR", "nDCG@5", "nDCG@10"), replicates=replicates)
+        for name in ("MRR", "nDCG@10"):
+            f = cmp_[name]
+            print(f"  {name}: fit_policy - {other} = {f['diff']:+.4f} [{f['lo']:+.4f}, {f['hi']:+.4f}], p = {f['p']:.4f} ({replicates} paired "
+                  f"replicates over impressions)", flush=True)
+    # (2) learning from a log the trained DIGAT makes
+    golden = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
+    state = {name: v for name, v in np.load(os.path.join(golden, "trained_planted_state.npz")).items()}
+    depth = int(np.load(os.path.join(golden, "devset_trained_2k.npz"))["depth"])
+    pref, news_sub = synthetic.planted_match(full)
+    corpus = synthetic.slice_impressions(full, 0, log_users)
+    cfg = types.SimpleNamespace(news_encoder="MSA", graph_encoder="DIGAT", news_graph_size=spec.news_graph_size,
+                                max_history_num=spec.max_history_num, category_num=spec.category_num, graph_depth=depth, dropout_rate=0.2)
+    teacher = Model(cfg, news_encoder=PrecomputedNewsEncoder(torch.from_numpy(corpus.news_embedding)))
+    teacher.graph_encoder.load_state_dict({name: torch.from_numpy(v) for name, v in state.items()})
+    teacher = teacher.to(dev).eval()
+    dc = util.DeviceCorpus.from_numpy(corpus, dev)
+    who = np.arange(log_users, dtype=np.int64)
+    pool = np.arange(1, spec.news_num, dtype=np.int64)
+    reward = lambda slates: synthetic.planted_reward(pref[:log_users], news_sub, slates.cpu().numpy(), spec.subtopics_per_category)
+    kk = 3
+    short = util.recommend(teacher, dc, who, pool, 8 * kk)
+    t_log = float(short[1].to(torch.float64).std(dim=1).mean())
+    log = util.recommend_slates(teacher, dc, who, pool, kk, t_log, samples=samples, seed=1)
+    r_log = reward(log["slates"])
+    logged = part(0, log_users)
+    ids_h, cnt_h = log["ids"].cpu().numpy().astype(np.int64), log["count"].cpu().numpy().astype(np.int64)
+
+    def judge(model):
+        """The student's own slates on the logged shortlists (eval mode, T = 1) and the clipped off-policy value of its likelihoods."""
+        model.eval()
+        own, lt = [], []
+        with torch.no_grad():
+            for lo in range(0, log_users, 256):
+                sl = slice(lo, lo + 256)
+                scores, cnt = nrms._list_scores(model, logged, who[sl], ids_h[sl], cnt_h[sl])
+                own.append(util.sample_lists(log["ids"][sl], scores, cnt, kk, 1.0, seed=2, samples=16, streams=torch.as_tensor(who[sl]))[0])
+                lt.append(nrms.policy_step(model, logged, who[sl], ids_h[sl], log["slates"][sl], np.zeros((len(who[sl]), samples)), cnt_h[sl])[1])
+        value = evaluate.off_policy_value(r_log.reshape(-1), torch.cat(lt).cpu().numpy().reshape(-1), log["logp"].cpu().numpy().reshape(-1),
+                                          clip=10.0, units=np.arange(0, log_users * samples + 1, samples), replicates=replicates)
+        return float(reward(torch.cat(own)).mean()), value
+    print(f"policy demo (2): the trained DIGAT logs {samples} slates of k = {kk} for each of {log_users} held-out impressions from a shortlist of "
+          f"{8 * kk} at T_log = {t_log:.4f}; reward = mean planted match; logged mean reward {r_log.mean():.4f}; the student: a fresh NRMS at "
+          f"d = 64 with random titles, policy softmax(<user, news>) over the logged shortlist", flush=True)
+    before = judge(student)
+    t0 = time.perf_counter()
+    l_log = nrms.fit_from_logs(student, logged, log, r_log, steps, clip=10.0, users=who, batch_users=64, lr=1e-3, seed=0, temperature=1.0)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    after = judge(student)
+    for tag, (own, v) in (("before", before), ("after fit_from_logs", after)):
+        sn, ip = v["snips"], v["ips"]
+        print(f"  {tag}: mean reward of the student's own slates (16 per user) {own:.4f}; on the log, clip 10: IPS {ip['value']:.4f} "
+              f"[{ip['lo']:.4f}, {ip['hi']:.4f}] SNIPS {sn['value']:.4f} [{sn['lo']:.4f}, {sn['hi']:.4f}] ess / n {v['ess'] / v['n']:.3f}", flush=True)
+    student.train()
+    b = np.arange(64)
+    zero = np.zeros((64, samples))
+
+    def first_pass():
+        with torch.no_grad():
+            return nrms.policy_step(student, logged, who[b], ids_h[b], log["slates"][b], zero, cnt_h[b])[0]
+    ms_first = timeit(first_pass, iters=10, warm=2)[0]
+    print(f"  fit_from_logs: {1e3 * (t1 - t0) / steps:.1f} ms per step of 64 lists, loss {np.mean(l_log[:10]):.4f} -> {np.mean(l_log[-10:]):.4f}; its "
+          f"graph-free first scoring pass alone: {ms_first:.1f} ms, {100 * ms_first / (1e3 * (t1 - t0) / steps):.0f} % of a step", flush=True)
+
+
 def torch_list_quality(ids, count, vectors, category=None, base_ids=None, base_count=None, exposure=None):
     """``evaluate.list_quality``'s figures built only from stock PyTorch: gather + ``torch.bmm``, the upper triangle's sum (in double)
     and max, a sort per list for the categories, a broadcast compare for the overlap, ``torch.bincount`` for the exposure."""
@@ -2340,6 +2562,10 @@ if __name__ == "__main__":
         bench_pl_sample(*nums)
     elif what == "off-policy":
         demo_off_policy(*nums)
+    elif what == "list-pl":
+        bench_list_pl(*nums)
+    elif what == "policy":
+        demo_policy(*nums)
     elif what == "bootstrap":
         bench_bootstrap(*nums)
     elif what == "linear":
