@@ -10,6 +10,7 @@ real MIND cannot be downloaded, so the default corpus is synthetic (``--syntheti
 ``--recommend_report`` (a tuple of diversities; it brings the other two with it as well) likewise;
 ``--recommend_calibration`` (with ``--recommend_shortlist``, here up to 1024) likewise;
 ``--recommend_sample`` (a temperature; with ``--recommend_seed`` and ``--recommend_shortlist``, here up to 1024) likewise;
+``--recommend_rerank`` (a pair ``D,C``; with ``--recommend_shortlist`` up to 1024 and ``--recommend_max_per_category``) likewise;
 ``--bootstrap`` (with ``--bootstrap_level``, ``--compare_model_path``) likewise;
 ``--local_rank`` also accepts torch >= 2.0's ``--local-rank`` spelling and the ``LOCAL_RANK`` variable.
 """
@@ -52,6 +53,11 @@ class Config:
                             'slate from softmax(score / this temperature) (> 0; default: off; not with --recommend_diversity, '
                             '--recommend_calibration or --recommend_report)')
         p.add_argument('--recommend_seed', type=int, default=0, help='with --recommend_sample: the seed of the draws')
+        p.add_argument('--recommend_rerank', type=str, default=None,
+                       help='--mode recommend: "D,C" — diversity and calibration at once, one greedy pass over a shortlist (recommend_k..1024; '
+                            '0: min(1024, 8 * recommend_k)) with the weights 1 - D - C, D and C (each 0..1, D + C <= 1; default: off; honours '
+                            '--recommend_max_per_category; not with --recommend_diversity, --recommend_calibration, --recommend_sample or '
+                            '--recommend_report)')
         p.add_argument('--recommend_report', type=str, default=None,
                        help='--mode recommend: diversities "0,0.1,0.3" to report list quality for (one scoring pass; honours --recommend_k, '
                             '--recommend_shortlist, --recommend_max_per_category)')
@@ -118,6 +124,17 @@ class Config:
                 p.error('--recommend_report takes diversities separated by commas, such as 0,0.1,0.3')
             if not a.recommend_report or not all(0.0 <= f <= 1.0 for f in a.recommend_report):
                 p.error('--recommend_report needs at least one diversity, each in [0, 1]')
+        if a.recommend_rerank is not None:
+            try:
+                a.recommend_rerank = tuple(float(f) for f in a.recommend_rerank.split(','))
+            except ValueError:
+                p.error('--recommend_rerank takes a diversity and a calibration separated by a comma, such as 0.2,0.4')
+            if len(a.recommend_rerank) != 2 or not all(0.0 <= f <= 1.0 for f in a.recommend_rerank) or not sum(a.recommend_rerank) <= 1.0:
+                p.error('--recommend_rerank needs two values D,C, each in [0, 1], with D + C <= 1')
+            if (a.recommend_diversity is not None or a.recommend_calibration is not None or a.recommend_sample is not None
+                    or a.recommend_report is not None):
+                p.error('--recommend_rerank does not combine with --recommend_diversity, --recommend_calibration, --recommend_sample or '
+                        '--recommend_report')
         if a.recommend_calibration is not None and not 0.0 <= a.recommend_calibration <= 1.0:
             p.error('--recommend_calibration must lie in [0, 1]')
         if a.recommend_calibration is not None and (a.recommend_diversity is not None or a.recommend_report is not None):
@@ -130,7 +147,7 @@ class Config:
                     '--recommend_max_per_category')
         if a.recommend_seed and a.recommend_sample is None:
             p.error('--recommend_seed needs --recommend_sample')
-        if a.recommend_diversity is None and a.recommend_report is None and (
+        if a.recommend_diversity is None and a.recommend_report is None and a.recommend_rerank is None and (
                 a.recommend_max_per_category or (a.recommend_shortlist and a.recommend_calibration is None and a.recommend_sample is None)):
             p.error('--recommend_shortlist and --recommend_max_per_category need --recommend_diversity (0 for the cap alone) or --recommend_report')
         if a.recommend_diversity is not None and not 0.0 <= a.recommend_diversity <= 1.0:
@@ -147,11 +164,13 @@ class Config:
         report_flags = ('recommend_report', 'recommend_shortlist', 'recommend_max_per_category')
         calibration_flags = ('recommend_calibration', 'recommend_shortlist')
         sample_flags = ('recommend_sample', 'recommend_seed', 'recommend_shortlist')
+        rerank_flags = ('recommend_rerank', 'recommend_shortlist', 'recommend_max_per_category')
         bootstrap_flags = ('bootstrap', 'bootstrap_level', 'compare_model_path')
         asked = lambda k: ((a.recommend_diversity is not None and k in diversity_flags) or (a.recommend_report is not None and k in report_flags)
                            or (a.recommend_calibration is not None and k in calibration_flags) or (a.bootstrap and k in bootstrap_flags)
                            or (a.recommend_sample is not None and k in sample_flags)
-                           or k not in diversity_flags + report_flags + calibration_flags + sample_flags + bootstrap_flags)
+                           or (a.recommend_rerank is not None and k in rerank_flags)
+                           or k not in diversity_flags + report_flags + calibration_flags + sample_flags + rerank_flags + bootstrap_flags)
         self.attribute_dict = {k: v for k, v in vars(a).items()
                                if (a.data_root or k not in mind_flags or (k == 'model_dir' and a.model_dir)) and asked(k)}
         for k, v in self.attribute_dict.items():

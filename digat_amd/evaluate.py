@@ -1908,6 +1908,231 @@ def calibrated_select(ids, scores, count, category, target, k: int, lam, alpha=0
     return out_s, out_i, out_c, out_kl
 
 
+# ---- joint re-rank: diversity, calibration and a cap per category in one greedy pass over up to 1024 entries -----------------------
+RERANK_MAX_LIST = SHORTLIST_MAX_K  # include/digat_hip.h: DIGAT_RERANK_MAX_LIST, the longest list digat_rerank_select takes
+RERANK_MAX_D = 512                 # ... DIGAT_LIST_SOFTMAX_MAX_D: the widest vectors a diversity term takes (w_div != 0)
+
+
+def rerank_weights(diversity, calibration):
+    """``(w_rel, w_div, w_cal)`` as float32 — what ``digat_rerank_select`` is handed — for the public knob ``rerank=(diversity,
+    calibration)``: both in [0, 1], their sum at most 1; ``w_rel = float32(1 - diversity - calibration)``."""
+    d, c = float(diversity), float(calibration)
+    if not (0.0 <= d <= 1.0 and 0.0 <= c <= 1.0):                    # a NaN fails the comparisons
+        raise ValueError(f"rerank's diversity and calibration must each lie in [0, 1], got {(diversity, calibration)}")
+    if not d + c <= 1.0:
+        raise ValueError(f"rerank's diversity and calibration must add up to at most 1, got {(diversity, calibration)}")
+    return np.float32(max(0.0, 1.0 - d - c)), np.float32(d), np.float32(c)
+
+
+def _check_rerank_weights(w_rel, w_div, w_cal):
+    w = tuple(np.float32(x) for x in (w_rel, w_div, w_cal))
+    if not all(np.isfinite(x) and x >= 0 for x in w):
+        raise ValueError(f"w_rel, w_div and w_cal must be finite and >= 0, got {(w_rel, w_div, w_cal)}")
+    return w
+
+
+def _check_rerank_args(ids_shape, scores_shape, count_shape, k, category_shape, target_shape, max_per_category, w_cal):
+    if len(ids_shape) != 2 or tuple(scores_shape) != tuple(ids_shape) or not 1 <= ids_shape[1] <= RERANK_MAX_LIST:
+        raise ValueError(f"ids and scores must both be [G, M] with 1 <= M <= {RERANK_MAX_LIST}, got {tuple(ids_shape)} and {tuple(scores_shape)}")
+    if count_shape is not None and tuple(count_shape) != (ids_shape[0],):
+        raise ValueError(f"count must have one entry per list ({ids_shape[0]}), got shape {tuple(count_shape)}")
+    if not 1 <= int(k) <= TOPK_MAX_K:
+        raise ValueError(f"k must be in [1, {TOPK_MAX_K}], got {k}")
+    if int(max_per_category) < 0:
+        raise ValueError(f"max_per_category must be >= 0 (0: no cap), got {max_per_category}")
+    if int(max_per_category) > 0 and category_shape is None:
+        raise ValueError("max_per_category needs category")
+    if category_shape is not None and len(category_shape) != 1:
+        raise ValueError(f"category must be [N], one entry per news, got shape {tuple(category_shape)}")
+    if w_cal != 0 and (category_shape is None or target_shape is None):
+        raise ValueError("a calibration weight needs category [N] and target [G, C]")
+    if target_shape is not None:
+        if category_shape is None:
+            raise ValueError("target needs category [N]")
+        if len(target_shape) != 2 or target_shape[0] != ids_shape[0] or not 1 <= target_shape[1] <= CAL_MAX_CATEGORIES:
+            raise ValueError(f"target must be [G, C] = [{ids_shape[0]}, 1 <= C <= {CAL_MAX_CATEGORIES}], got {tuple(target_shape)}")
+
+
+def rerank_select_host(ids, scores, count, sim, k: int, w_rel, w_div, w_cal, category=None, target=None, alpha=0.01,
+                       max_per_category: int = 0, news_num=None, return_robust: bool = False):
+    """The contract of ``digat_rerank_select`` in numpy — the yardstick of the kernel: ``mmr_select_host`` and
+    ``calibrated_select_host`` in one greedy pass.  ``ids`` / ``scores`` [G, M <= 1024], ``count`` [G] or None (M): position p is
+    an element when ``p < clip(count[g], 0, M)`` and ``0 <= id < N`` (``news_num``; None: ``len(category)``, or no upper bound);
+    ``sim`` [G, M, M] float32 as ``mmr_select_host`` takes it (None where ``w_div == 0``).  The weights are float32, finite and
+    >= 0, taken as given (``rerank_weights`` makes them from the public knob).
+
+    Step t, every operation a rounded float32 one: ``rel = w_rel * s`` (once); ``a = rel - (w_div * pen)`` if ``w_div != 0`` else
+    ``rel``; ``value = a + red`` if ``w_cal != 0`` else ``a`` with ``red = w_cal * gain32[c]`` for an element categorised in
+    [0, C) and 0 otherwise — ``calibrated_select_host``'s gains, float64 ``q_c`` and logarithms at the same ``alpha``.  The winner
+    is the eligible element with the largest ``topk_keys(value)``, ties to the lowest position; eligible: unpicked and, with
+    ``max_per_category`` q > 0, fewer than q picked elements of its raw ``category[id]``.  After a pick ``pen = fmax(pen,
+    sim[winner])`` (``w_div != 0``) and ``n_c += 1`` for a categorised winner.  Returns ``(scores [G,k] float32 — the INPUT score
+    bits —, ids [G,k] int64, count [G] int32, kl [G] float32)``; ``kl`` is ``calibrated_select_host``'s of the finished list, 0
+    without a target.
+
+    ``return_robust``: ``calibrated_select_host``'s certificate as a fifth array; the magnitude also takes ``|w_div * pen|`` and a
+    true tie also needs equal ``w_div * pen`` bits.  With ``w_cal == 0`` there is no logarithm and every list is robust."""
+    idv = np.asarray(ids, dtype=np.int64)
+    sc = np.ascontiguousarray(scores, dtype=np.float32)
+    cat = None if category is None else np.asarray(category, dtype=np.int64)
+    tgt = None if target is None else np.asarray(target, dtype=np.float32)
+    wr, wd, wc = _check_rerank_weights(w_rel, w_div, w_cal)
+    _check_rerank_args(idv.shape, sc.shape, None if count is None else np.shape(count), k, None if cat is None else cat.shape,
+                       None if tgt is None else tgt.shape, max_per_category, wc)
+    alpha = np.float64(_check_alpha(alpha))
+    oma = np.float64(1.0) - alpha
+    G, M = idv.shape
+    S = None
+    if wd != 0:
+        S = np.asarray(sim, dtype=np.float32)
+        if S.shape != (G, M, M):
+            raise ValueError(f"sim must be [G, M, M] = {(G, M, M)}, got {S.shape}")
+    k, q = int(k), int(max_per_category)
+    C = 0 if tgt is None else tgt.shape[1]
+    N = news_num if news_num is not None else (len(cat) if cat is not None else None)
+    cnt = np.full(G, M, dtype=np.int64) if count is None else np.clip(np.asarray(count, dtype=np.int64), 0, M)
+    out_s = np.full((G, k), -np.inf, dtype=np.float32)
+    out_i = np.full((G, k), -1, dtype=np.int64)
+    out_c = np.zeros(G, dtype=np.int32)
+    out_kl = np.zeros(G, dtype=np.float32)
+    robust = np.ones(G, dtype=bool)
+    pos = np.arange(M)
+    zero = np.float32(0)
+    for g in range(G):
+        elem = (pos < cnt[g]) & (idv[g] >= 0)
+        if N is not None:
+            elem &= idv[g] < N
+        cg = cat[np.where(elem, idv[g], 0)] if cat is not None and elem.any() else np.zeros(M, dtype=np.int64)
+        cated = elem & (cg >= 0) & (cg < C)
+        ci = np.where(cated, cg, 0)
+        if C:
+            pbits = np.where(np.isfinite(tgt[g]) & (tgt[g] > 0), tgt[g], zero).astype(np.float32)
+        else:
+            pbits = np.zeros(1, dtype=np.float32)
+        p = pbits.astype(np.float64)
+        live = p > 0
+        pl, apl = p[live], alpha * p[live]
+        free = ~(cated & live[ci])                                  # elements no gain reaches
+        n = np.zeros(max(C, 1), dtype=np.int64)
+        chosen = np.zeros(M, dtype=bool)
+        same = np.zeros(M, dtype=np.int64)
+        pen = np.zeros(M, dtype=np.float32)
+        with np.errstate(invalid="ignore", over="ignore"):
+            rel = (wr * sc[g]).astype(np.float32)
+        red = np.zeros(M, dtype=np.float32)
+        dp = np.zeros(M, dtype=np.float32)
+        t_end = 0
+        for t in range(k):
+            ok = elem & ~chosen
+            if q > 0:
+                ok &= same < q
+            if not ok.any():
+                break
+            with np.errstate(invalid="ignore", over="ignore"):
+                value = rel
+                if wd != 0:
+                    dp = (wd * pen).astype(np.float32)
+                    value = (rel - dp).astype(np.float32)
+                if wc != 0:
+                    T = np.float64(t + 1)
+                    gain64 = np.zeros(C, dtype=np.float64)
+                    nl = n[:C][live].astype(np.float64)
+                    gain64[live] = pl * (np.log((oma * (nl + 1.0)) / T + apl) - np.log((oma * nl) / T + apl))
+                    mg = (wc * gain64.astype(np.float32)).astype(np.float32)
+                    red = np.where(cated, mg[ci], zero)
+                    value = (value + red).astype(np.float32)
+            keys = np.where(ok, topk_keys(value).astype(np.int64), -1)
+            j = int(np.argmax(keys))                                # the first (lowest position) of the largest key
+            if return_robust and robust[g] and wc != 0:
+                others = ok.copy()
+                others[j] = False
+                with np.errstate(invalid="ignore", over="ignore"):
+                    mag = np.maximum(np.maximum(np.maximum(np.abs(value), np.abs(rel)), np.abs(red)), np.abs(dp))
+                    ulp = np.spacing(np.maximum(mag, mag[j]).astype(np.float32)).astype(np.float64)
+                    lead = np.float64(value[j]) - value.astype(np.float64)
+                    fixed = ~np.isfinite(rel) | ~np.isfinite(rel[j])
+                    same_gain = (free & free[j]) | (~free & ~free[j] & (pbits[ci].view(np.uint32) == pbits[ci[j]].view(np.uint32))
+                                                    & (n[ci] == n[ci[j]]))
+                    tie = (sc[g] == sc[g, j]) & same_gain & (dp.view(np.uint32) == dp[j].view(np.uint32))
+                    if np.any(others & ~fixed & ~tie & ~(lead >= CAL_ROBUST_ULPS * ulp)):
+                        robust[g] = False
+            chosen[j] = True
+            out_s[g, t], out_i[g, t] = sc[g, j], idv[g, j]
+            t_end = t + 1
+            if wd != 0:
+                pen = np.fmax(pen, S[g, j])
+            if cated[j]:
+                n[cg[j]] += 1
+            if q > 0:
+                same += elem & (cg == cg[j])
+        out_c[g] = t_end
+        if live.any():
+            qq = (oma * n[:C][live].astype(np.float64)) / np.float64(max(t_end, 1)) + apl
+            out_kl[g] = np.float32(np.sum(pl * (np.log(pl) - np.log(qq))))
+    return (out_s, out_i, out_c, out_kl, robust) if return_robust else (out_s, out_i, out_c, out_kl)
+
+
+def rerank_select(ids, scores, count, vectors, k: int, w_rel, w_div, w_cal, category=None, target=None, alpha=0.01,
+                  max_per_category: int = 0):
+    """The joint re-rank on the GPU (``digat_rerank_select``): per user, k greedy picks from a shortlist of up to 1024 that weigh
+    an entry's score against its largest similarity to what is already picked AND against what it does for the KL divergence
+    between ``target`` and the list's category mix, under a cap per category — ``mmr_select`` and ``calibrated_select`` in one
+    objective, and plain MMR beyond 128 entries (``w_cal = 0``).
+
+    ``ids`` [G, M <= 1024] int64, ``scores`` [G, M] float32 and ``count`` [G] int32 (None: M) are device tensors; ``vectors`` [N,
+    d <= 512] float32 holds the rows the similarity is the inner product of (``digat_dot_scores``' bits; None where ``w_div ==
+    0``); the weights are float32, finite and >= 0 (``rerank_weights``); ``category`` [N] int and ``target`` [G, C <= 64] as
+    ``calibrated_select`` takes them (None where ``w_cal == 0`` — ``category`` then only with a cap); ``max_per_category`` q >= 1
+    caps the picks per raw category.  The contract is ``rerank_select_host``'s, exactly.  Returns ``(scores [G,k] float32, ids
+    [G,k] int64, count [G] int32, kl [G] float32)`` on the device.  Stream-ordered: one launch, no Gram in memory, nothing is
+    read back."""
+    import torch
+    from . import _lib
+    given = [t for t in (ids, scores, count, vectors, category, target) if t is not None]
+    dev = _lib.require_device(*given)
+    wr, wd, wc = _check_rerank_weights(w_rel, w_div, w_cal)
+    _check_rerank_args(tuple(ids.shape), tuple(scores.shape), None if count is None else tuple(count.shape), k,
+                       None if category is None else tuple(category.shape), None if target is None else tuple(target.shape),
+                       max_per_category, wc)
+    alpha = _check_alpha(alpha)
+    if wd != 0:
+        if vectors is None or vectors.dim() != 2 or not 1 <= int(vectors.shape[1]) <= RERANK_MAX_D:
+            raise ValueError(f"a diversity weight needs vectors [N, d] with 1 <= d <= {RERANK_MAX_D}, got "
+                             f"{None if vectors is None else tuple(vectors.shape)}")
+    elif vectors is not None and vectors.dim() != 2:
+        raise ValueError(f"vectors must be [N, d], got {tuple(vectors.shape)}")
+    if vectors is not None and category is not None and int(category.shape[0]) != int(vectors.shape[0]):
+        raise ValueError(f"category must have one entry per row of vectors ({int(vectors.shape[0])}), got {int(category.shape[0])}")
+    if vectors is None and category is None:
+        raise ValueError("rerank_select needs vectors or category: the number of news N bounds the ids")
+    idt = ids.to(torch.int64).contiguous()
+    sc = _lib.f32(scores.detach())
+    ct = None if count is None else count.to(torch.int32).contiguous()
+    v = None if vectors is None or wd == 0 else _lib.f32(vectors.detach())
+    cat = None if category is None else category.to(torch.int32).contiguous()
+    tg = None if target is None else _lib.f32(target.detach())
+    N = int(vectors.shape[0]) if vectors is not None else int(category.shape[0])
+    G, M, k, q = int(idt.shape[0]), int(idt.shape[1]), int(k), int(max_per_category)
+    C = 0 if tg is None else int(tg.shape[1])
+    out_s = torch.empty((G, k), dtype=torch.float32, device=dev)
+    out_i = torch.empty((G, k), dtype=torch.int64, device=dev)
+    out_c = torch.empty((G,), dtype=torch.int32, device=dev)
+    out_kl = torch.empty((G,), dtype=torch.float32, device=dev)
+    if G == 0:
+        return out_s, out_i, out_c, out_kl
+    L = _lib.lib()
+    need = int(L.digat_rerank_select_workspace_bytes(G, M, k))
+    ws = _lib.workspace(need, dev, "rerank")
+    if N == 0:                                                      # empty tensors have no storage to point at; no id is an element
+        v = None if v is None else ws
+        cat = None if cat is None else ws
+    _lib.check(L.digat_rerank_select(idt.data_ptr(), sc.data_ptr(), _lib.ptr(ct), G, M, _lib.ptr(v), N, 0 if v is None else int(vectors.shape[1]),
+                                     _lib.ptr(cat), q, _lib.ptr(tg), C, float(wr), float(wd), float(wc), alpha, k, out_i.data_ptr(),
+                                     out_s.data_ptr(), out_c.data_ptr(), out_kl.data_ptr(), ws.data_ptr(), need, _lib.stream_ptr()),
+               "digat_rerank_select")
+    return out_s, out_i, out_c, out_kl
+
+
 def _check_share_args(history_shape, category_shape, C):
     if len(history_shape) != 2:
         raise ValueError(f"history must be [G, H], got shape {tuple(history_shape)}")

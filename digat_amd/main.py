@@ -15,6 +15,8 @@ corpus, picks the ``--recommend_k`` best of ALL non-PAD news the impression's us
 category mix of the reader's history (``util.recommend(calibration=)``) — on a corpus that carries the news' categories.
 ``--recommend_sample T`` instead DRAWS them: one Plackett-Luce slate per impression from ``softmax(score / T)`` over that shortlist
 (``util.recommend(sample=)``, ``--recommend_seed``).
+``--recommend_rerank D,C`` instead makes them diverse AND calibrated in one greedy pass over that shortlist (``util.recommend(rerank=)``;
+``--recommend_max_per_category`` composes).
 ``--recommend_report 0,0.1,0.3`` then prints one line per diversity with what the knob buys and costs (``util.recommend_report``: one
 scoring pass for all of them; on a labelled split the accuracy of the lists against each impression's clicked candidates as well).
 ``--bootstrap B`` (``dev`` / ``test`` on a labelled split) prints, below the four metrics, one line per metric with its percentile
@@ -57,13 +59,17 @@ def recommend_category(dc, max_per_category: int):
 
 
 def recommend_lines(model, dc, k: int, batch_size: int, diversity=None, shortlist: int = 0, max_per_category: int = 0, calibration=None,
-                    sample=None, seed: int = 0):
+                    sample=None, seed: int = 0, rerank=None):
     """``"<impression id> [id1,id2,...]"`` (1-based impression ids, best news first) for every impression of ``dc`` against the
     pool of all non-PAD news, the user's own history excluded; with ``diversity`` the diversified lists of ``util.recommend``, with
-    ``calibration`` its calibrated ones, with ``sample`` (a temperature) one drawn slate per impression (``seed``)."""
+    ``calibration`` its calibrated ones, with ``sample`` (a temperature) one drawn slate per impression (``seed``), with ``rerank``
+    (a pair) the jointly re-ranked ones."""
     pool = torch.arange(1, dc.news_embedding.shape[0], dtype=torch.int64, device=dc.news_embedding.device)
     users = torch.arange(dc.history.shape[0], dtype=torch.int64)
-    if sample is not None:
+    if rerank is not None:
+        ids, _, count = util.recommend(model, dc, users, pool, k, batch_size=batch_size, rerank=rerank, shortlist=shortlist or None,
+                                       category=recommend_category(dc, max_per_category), max_per_category=max_per_category)
+    elif sample is not None:
         ids, _, count = util.recommend(model, dc, users, pool, k, batch_size=batch_size, sample=sample, seed=seed, shortlist=shortlist or None)
     elif calibration is not None:
         ids, _, count = util.recommend(model, dc, users, pool, k, batch_size=batch_size, calibration=calibration, shortlist=shortlist or None)
@@ -210,11 +216,12 @@ def main(argv=None):
             diversity, cap = getattr(config, 'recommend_diversity', None), getattr(config, 'recommend_max_per_category', 0)
             calibration = getattr(config, 'recommend_calibration', None)
             recommend_category(dc, cap)                                     # refuse before the model runs
-            if calibration is not None:
+            rerank = getattr(config, 'recommend_rerank', None)
+            if calibration is not None or (rerank is not None and rerank[1] != 0.0):
                 util.calibration_category(None, getattr(dc, 'news_category', None))
             lines = recommend_lines(model, dc, config.recommend_k, config.batch_size * 16, diversity,
                                     getattr(config, 'recommend_shortlist', 0), cap, calibration,
-                                    getattr(config, 'recommend_sample', None), getattr(config, 'recommend_seed', 0))
+                                    getattr(config, 'recommend_sample', None), getattr(config, 'recommend_seed', 0), rerank)
             if config.recommend_output:
                 with open(config.recommend_output, 'w') as f:
                     f.write('\n'.join(lines))

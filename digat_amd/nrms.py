@@ -512,7 +512,7 @@ def user_vectors(model, dev, users, batch_size=1024):
 
 def recommend(model, dev, users, candidates=None, k=10, exclude_history=True, batch_size=1024, diversity=None, shortlist=None, category=None,
               max_per_category=0, calibration=None, calibration_target=None, alpha=0.01, index=None, refine=None, sample=None, seed=0,
-              streams=None):
+              streams=None, rerank=None):
     """For every user, which k news, in order: ``(news_ids [G,k] int64, scores [G,k] float32, count [G] int32)`` on the model's
     device.  Order: score descending, equal scores in candidate order; slots at or beyond ``count[g]`` hold id -1 and score -inf.
 
@@ -544,10 +544,26 @@ def recommend(model, dev, users, candidates=None, k=10, exclude_history=True, ba
     ``sample`` — a temperature > 0 (None: off, the call as it was, bit for bit): retrieval runs at ``k' = shortlist or min(1024,
     8 k)`` and ``util.sample_lists`` draws one Plackett-Luce slate of k from ``softmax(score / sample)`` over that shortlist;
     ``seed`` and ``streams`` [G] name the draws (None: the impression indices where ``users`` are indices).  ``util.recommend`` has
-    the details; ``sample`` does not combine with ``diversity``, ``calibration`` or ``index``."""
+    the details; ``sample`` does not combine with ``diversity``, ``calibration`` or ``index``.
+
+    ``rerank=(diversity, calibration)`` (None: off, the call as it was, bit for bit): both at once in one objective — retrieval runs
+    at ``k' = shortlist or min(1024, 8 k)`` and ``util.rerank`` cuts every list to k over the plain news cache (the vectors
+    ``diversity`` uses) towards the category mix of the history or ``calibration_target``; ``shortlist``, ``category``,
+    ``max_per_category`` and ``alpha`` compose.  ``util.recommend`` has the details; ``rerank`` does not combine with
+    ``diversity``, ``calibration``, ``sample`` or ``index``."""
     from . import evaluate, util
     util.sample_refusals(sample, seed, streams, diversity=diversity, calibration=calibration, calibration_target=calibration_target,
-                         category=category, max_per_category=max_per_category, index=index, refine=refine)
+                         category=category, max_per_category=max_per_category, index=index, refine=refine, rerank=rerank)
+    util.rerank_refusals(rerank, diversity=diversity, calibration=calibration, index=index, refine=refine)
+    if rerank is not None:
+        select = lambda wide, long_lists: _retrieve(model, dev, users, candidates, wide, exclude_history, batch_size, long_lists)
+        plain = lambda: news_caches(model, dev.title_text, dev.title_mask, dev.augmented_title_text, dev.augmented_title_mask, 4 * batch_size)[0]
+
+        def read():
+            hist, mask = _histories(dev, users)
+            return torch.where(mask != 0, hist, torch.zeros_like(hist))
+        return util.shortlist_then_rerank(select, plain, read, k, rerank, shortlist, category, max_per_category,
+                                          getattr(dev, "news_category", None), calibration_target, alpha)[1][:3]
     if sample is not None:
         select = lambda wide, long_lists: _retrieve(model, dev, users, candidates, wide, exclude_history, batch_size, long_lists)
         ids, scores, n_out = util.shortlist_then_sample(select, k, sample, shortlist, seed,

@@ -1099,6 +1099,89 @@ def shortlist_then_calibrate(select: Callable, history: Callable, k, calibration
     return short, calibrate(*short, cat, target, k, lam, alpha)
 
 
+def rerank_limits(k, rerank, shortlist, max_per_category) -> Tuple[int, int, Tuple[float, float]]:
+    """``(k, k', (diversity, calibration))`` of a jointly re-ranked ``recommend``: the plain selection runs at ``k' = shortlist or
+    min(1024, 8 k)`` and ``rerank`` cuts its lists to k with ``evaluate.rerank_weights(diversity, calibration)``."""
+    if not 1 <= int(k) <= evaluate.TOPK_MAX_K:
+        raise ValueError(f"k must be in [1, {evaluate.TOPK_MAX_K}], got {k}")
+    try:
+        diversity, calibration = rerank
+    except (TypeError, ValueError):
+        raise ValueError(f"rerank must be a pair (diversity, calibration), got {rerank!r}") from None
+    evaluate.rerank_weights(diversity, calibration)
+    if int(max_per_category) < 0:
+        raise ValueError(f"max_per_category must be >= 0 (0: no cap), got {max_per_category}")
+    k = int(k)
+    wide = min(evaluate.RERANK_MAX_LIST, 8 * k) if not shortlist else int(shortlist)
+    if not k <= wide <= evaluate.RERANK_MAX_LIST:
+        raise ValueError(f"shortlist must lie in [k, {evaluate.RERANK_MAX_LIST}] = [{k}, {evaluate.RERANK_MAX_LIST}], got {shortlist}")
+    return k, wide, (float(diversity), float(calibration))
+
+
+def rerank(ids: torch.Tensor, scores: torch.Tensor, count: torch.Tensor, vectors: torch.Tensor, k: int, diversity: float, calibration: float,
+           category=None, target=None, alpha: float = 0.01, max_per_category: int = 0):
+    """The last stage of a jointly re-ranked ``recommend``: the lists ``(ids [G,M <= 1024], scores [G,M], count [G])`` of the plain
+    selection cut to k by ONE greedy pass that weighs an entry's score (``1 - diversity - calibration``) against its largest
+    similarity over ``vectors`` [N, d <= 512] to what is already picked (``diversity``) and against what it does for the KL
+    divergence between ``target`` [G, C <= 64] and the list's mix under ``category`` [N] (``calibration``), with at most
+    ``max_per_category`` picks of one category — ``evaluate.rerank_select`` on device tensors; on CPU tensors the Gram of stock
+    PyTorch (``evaluate.mmr_gram_stock``) and ``evaluate.rerank_select_host``, as ``diversify`` / ``calibrate`` do.  ``category``
+    is needed by a calibration weight, a target or a cap; ``target`` by a calibration weight.  Returns ``recommend``'s triple and
+    the divergence of every finished list (0 without a target): ``(news_ids [G,k], scores [G,k], count [G], kl [G])``."""
+    wr, wd, wc = evaluate.rerank_weights(diversity, calibration)
+    cat = None if category is None else _tensor_on(category, ids.device)
+    tgt = None if target is None else _tensor_on(target, ids.device).to(torch.float32)
+    if cat is not None and (cat.dim() != 1 or int(cat.shape[0]) != int(vectors.shape[0])):
+        raise ValueError(f"category must be [{int(vectors.shape[0])}], one entry per news, got shape {tuple(cat.shape)}")
+    if ids.is_cuda:
+        s, i, c, kl = evaluate.rerank_select(ids, scores, count, vectors, k, wr, wd, wc, category=cat, target=tgt, alpha=alpha,
+                                             max_per_category=max_per_category)
+        return i, s, c, kl
+    sim = evaluate.mmr_gram_stock(ids, vectors.detach().to(torch.float32)).numpy() if wd != 0 else None
+    s, i, c, kl = evaluate.rerank_select_host(ids.numpy(), scores.numpy(), None if count is None else count.numpy(), sim, k, wr, wd, wc,
+                                              category=None if cat is None else cat.numpy(), target=None if tgt is None else tgt.numpy(),
+                                              alpha=alpha, max_per_category=max_per_category, news_num=int(vectors.shape[0]))
+    return torch.from_numpy(i), torch.from_numpy(s), torch.from_numpy(c), torch.from_numpy(kl)
+
+
+def rerank_refusals(rerank, **others) -> None:
+    """What ``recommend(rerank=)`` of either model refuses before anything is scored: ``rerank`` beside a re-rank of one kind or an
+    index (``others``: the names and values of the arguments it does not combine with)."""
+    if rerank is None:
+        return
+    named = [name for name, value in others.items() if value is not None]
+    if named:
+        raise ValueError(f"rerank does not combine with {', '.join(named)}: it names the diversity and the calibration weight itself")
+
+
+def shortlist_then_rerank(select: Callable, vectors: Callable, history: Callable, k, rerank_knob, shortlist=None, category=None,
+                          max_per_category: int = 0, corpus_category=None, calibration_target=None, alpha: float = 0.01):
+    """The step behind ``recommend(rerank=(diversity, calibration))`` of either model: ``select(k', long_lists)`` — the plain
+    selection at ``rerank_limits``' width, ``long_lists`` when ``k' > 128`` — then ``rerank`` over ``vectors()`` towards
+    ``calibration_target`` or, without one, ``evaluate.category_share`` of ``history()`` under ``calibration_category``; a cap goes
+    by the same category array.  With a calibration weight of 0 and no ``calibration_target`` there is no target and categories are
+    needed by a cap alone (``cap_category``).  Returns ``(shortlist triple, (news_ids, scores, count, kl))``."""
+    k, wide, (diversity, calibration) = rerank_limits(k, rerank_knob, shortlist, max_per_category)
+    evaluate._check_alpha(alpha)
+    wanted = calibration != 0.0 or calibration_target is not None
+    cat, C = None, 0
+    if wanted:
+        cat, C = calibration_category(category, corpus_category)   # refused before anything is scored
+    elif int(max_per_category) > 0:
+        cat = _tensor_on(cap_category(category, max_per_category, corpus_category), None).to(torch.int32)
+    short = select(wide, wide > evaluate.TOPK_MAX_K)
+    dev = short[0].device
+    cat = None if cat is None else cat.to(dev)
+    target = None
+    if wanted and calibration_target is None:
+        target = evaluate.category_share(history().to(dev), cat, C)
+    elif wanted:
+        target = _tensor_on(calibration_target, dev).to(torch.float32)
+        if target.dim() != 2 or int(target.shape[0]) != int(short[0].shape[0]):
+            raise ValueError(f"calibration_target must be [users = {int(short[0].shape[0])}, C], got {tuple(target.shape)}")
+    return short, rerank(*short, vectors(), k, diversity, calibration, cat, target, alpha, max_per_category)
+
+
 def sample_limits(k, sample, shortlist) -> Tuple[int, int, float]:
     """``(k, k', temperature)`` of a sampled ``recommend``: the plain selection runs at ``k' = shortlist or min(1024, 8 k)``, and
     ``sample_lists`` draws one slate of k from it at temperature ``sample`` > 0."""
@@ -1302,7 +1385,7 @@ def recommend_report(model, dc: DeviceCorpus, users, candidates, k: int, diversi
 def recommend(model, dc: DeviceCorpus, users, candidates, k: int, exclude_history: bool = True, batch_size: int = 1024,
               max_rows: int = RECOMMEND_MAX_ROWS, diversity: Optional[float] = None, shortlist: Optional[int] = None, category=None,
               max_per_category: int = 0, calibration: Optional[float] = None, calibration_target=None, alpha: float = 0.01,
-              sample: Optional[float] = None, seed: int = 0, streams=None):
+              sample: Optional[float] = None, seed: int = 0, streams=None, rerank=None):
     """For every user, which k news of its candidates, in order: ``(news_ids [G,k] int64, scores [G,k] float32, count [G] int32)``
     on the device.  Order: score descending, equal scores in candidate order (the rank file's order); ``count[g]`` is the number of
     valid slots of row g, the slots behind it hold id -1 and score -inf.
@@ -1338,9 +1421,22 @@ def recommend(model, dc: DeviceCorpus, users, candidates, k: int, exclude_histor
     over that shortlist; the triple returned is the slate in the order drawn, its scores the model's, ``count`` the slate's length.
     ``seed`` and ``streams`` [G] name the draws (``streams`` None: the impression indices where ``users`` are indices, so a user's
     slate does not depend on who else is in the call).  As ``sample`` goes to 0 the slate becomes the plain list.  ``sample`` does
-    not combine with ``diversity``, ``calibration`` or ``max_per_category``; ``recommend_slates`` also returns the propensities."""
+    not combine with ``diversity``, ``calibration`` or ``max_per_category``; ``recommend_slates`` also returns the propensities.
+
+    ``rerank=(diversity, calibration)`` (None: off, the call as it was, bit for bit) is both at once, in ONE objective: the
+    selection above runs at ``k' = shortlist or min(1024, 8 k)`` and ``rerank`` cuts every list to k, each pick weighing its score
+    (``1 - diversity - calibration``) against its largest cosine over ``unit_rows(dc.news_embedding)`` to what the user already got
+    and against what it does for the KL divergence towards the target mix — so the penalty sees every pick calibration makes, and
+    calibration picks from the deep pool.  Both weights lie in [0, 1], their sum at most 1.  ``shortlist``, ``category``,
+    ``max_per_category``, ``calibration_target`` and ``alpha`` mean what they mean above; ``rerank=(d, 0)`` is maximal marginal
+    relevance over up to 1024 entries.  ``rerank`` does not combine with ``diversity``, ``calibration`` or ``sample``."""
     sample_refusals(sample, seed, streams, diversity=diversity, calibration=calibration, calibration_target=calibration_target,
-                    category=category, max_per_category=max_per_category)
+                    category=category, max_per_category=max_per_category, rerank=rerank)
+    rerank_refusals(rerank, diversity=diversity, calibration=calibration)
+    if rerank is not None:
+        plain = lambda wide, long_lists: recommend_lists(model, dc, users, candidates, wide, exclude_history, batch_size, max_rows, long_lists)
+        return shortlist_then_rerank(plain, lambda: unit_rows(dc.news_embedding), lambda: recommend_users(dc, users)[0], k, rerank, shortlist,
+                                     category, max_per_category, dc.news_category, calibration_target, alpha)[1][:3]
     if sample is not None:
         plain = lambda wide, long_lists: recommend_lists(model, dc, users, candidates, wide, exclude_history, batch_size, max_rows, long_lists)
         ids, scores, n_out = shortlist_then_sample(plain, k, sample, shortlist, seed, user_streams(users) if streams is None else streams)[1][:3]

@@ -975,6 +975,34 @@ int digat_list_pl_bwd(const float* users, const float* rows, const int64_t* ids,
                       const int64_t* entry_keys, int64_t E, float* d_users, float* d_rows, void* workspace, size_t workspace_bytes,
                       void* stream);
 
+/* ---- joint re-rank: diversity, calibration and a cap per category in one greedy pass (digat_amd.evaluate.rerank_select) ---------
+ * Per list g: ids [G, M] int64, scores [G, M] f32, count [G] int32 (NULL: M), 1 <= M <= DIGAT_RERANK_MAX_LIST; vectors [N, d] f32,
+ * 1 <= d <= DIGAT_LIST_SOFTMAX_MAX_D (read only when w_div != 0; NULL allowed otherwise); category [N] int32 (NULL allowed when
+ * w_cal == 0, max_per_category == 0 and target is NULL); target [G, C] f32, 1 <= C <= DIGAT_CALIBRATE_MAX_CATEGORIES (NULL allowed
+ * when w_cal == 0: then no element is categorised and kl is 0).  Position p is an ELEMENT when p < clamp(count[g], 0, M) and
+ * 0 <= ids[g][p] < N (digat_mmr_select's rule; no read leaves the arrays).  The weights are finite and >= 0, taken as given.
+ * Greedy, steps t = 0 .. k-1, every operation a rounded float32 one, never an fma: rel = w_rel s (once); a = rel - (w_div pen) if
+ * w_div != 0, else rel; value = a + red if w_cal != 0, else a, where red = w_cal gain32_c is digat_calibrated_select's for an element
+ * categorised in [0, C) and 0 otherwise (the same float64 q_c and logarithms at the same alpha).  The winner is the eligible element
+ * with the largest digat_topk_segments key of value, ties to the lowest position; eligible: unpicked and, with max_per_category
+ * q > 0, fewer than q picked elements of its raw category[id] (digat_mmr_select's cap).  After a pick: pen = fmax(pen,
+ * sim(winner, .)) when w_div != 0, sim the fp32 fmaf chain over ascending channels (digat_dot_scores' bits); n_c += 1 for a
+ * categorised winner.  Selection stops when nothing is eligible.  out_scores / out_ids [G, k], 1 <= k <= 128: the picked entries'
+ * INPUT scores and ids, -inf / -1 from out_count[g] on; out_kl [G] as digat_calibrated_select writes it (0 without a target).
+ * DIGAT_ERR_ARG: a null required pointer, G < 0, N < 0, max_per_category < 0, a weight that is negative or not finite, alpha outside
+ * (0, 1); DIGAT_ERR_SHAPE: k outside [1, 128], M outside [1, DIGAT_RERANK_MAX_LIST], d outside [1, DIGAT_LIST_SOFTMAX_MAX_D] with
+ * w_div != 0, C outside [1, 64] with a target, G >= 2^31 — all before any launch.  G == 0 returns DIGAT_OK without a launch.
+ * Stream-ordered: one launch, one workgroup of 256 threads per list, the list in registers; M <= 128: the list's Gram in LDS
+ * (digat_mmr_select's), beyond: one row of it per step formed in LDS; no Gram in memory either way (the route goes by M alone and
+ * both give the same bits); no atomics: the same bits from run to run and in any batch; no allocation, no host synchronisation.  The
+ * workspace is not used (digat_rerank_select_workspace_bytes returns 0; workspace may be NULL). */
+#define DIGAT_RERANK_MAX_LIST 1024
+size_t digat_rerank_select_workspace_bytes(int64_t lists, int m, int k);
+int digat_rerank_select(const int64_t* ids, const float* scores, const int32_t* count, int64_t G, int M, const float* vectors, int64_t N, int d,
+                        const int32_t* category, int max_per_category, const float* target, int C, float w_rel, float w_div, float w_cal,
+                        double alpha, int k, int64_t* out_ids, float* out_scores, int32_t* out_count, float* out_kl, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 /* ---- bootstrap resampling of per-unit metric rows (digat_amd.evaluate.bootstrap_sums / metric_intervals / compare_metrics) -----
  * values [n, c] float64 row-major: one row per resampling unit (an impression, a user), one column per summed quantity;
  * sums [B, c] float64.  Replicate r = first_replicate + b makes n draws with replacement; draw j has the 64-bit counter

@@ -73,6 +73,14 @@
                                              turn, median [min, max] of five rounds, time and peak device bytes; then recommend(calibration=)
                                              in {0, 0.3, 0.5, 0.8} on 512 held-out impressions of the planted-signal corpus: kl,
                                              category_max_share, recall@10 and MRR with intervals, paired against calibration 0
+  python tools/kbench.py rerank [rounds demo d]    joint re-rank: evaluate.rerank_select (one launch, no Gram: one row of it per step) against
+                                             (a) gather + torch.bmm Gram + k rounds of torch ops with float64 logs and (b) rows gathered once + a
+                                             batched matrix-vector product per step, both chunked to 1 GiB; G = 64 and 4 096 lists of M = 128
+                                             and 1 024, k = 10 and 100, d = 400, C = 17, weights (0.5, 0.3, 0.2) and (0.7, 0.3, 0) (long MMR;
+                                             at M = 128 mmr_select too), the legs in turn, median [min, max] of five rounds, time and peak
+                                             device bytes; then plain, diversity=0.3, calibration=0.5 and rerank=(0.2, 0.4) on 512 held-out
+                                             impressions of the planted-signal corpus: ild, kl, recall@10 and MRR with intervals, paired
+                                             against plain
   python tools/kbench.py list-pl [d rounds demo]   policy gradient: evaluate.list_pl (fused Plackett-Luce slate likelihood over per-user lists and
                                              its closed-form gradient) against index_select + bmm + gather + logsumexp + flipped logcumsumexp
                                              under autograd, chunked to 1 GiB, (G, M, k, S) in {64, 4 096} x {128, 1 024} x {10, 100} x {1, 8},
@@ -2030,6 +2038,192 @@ def demo_calibrate(users=512, k=10, calibrations=(0.0, 0.3, 0.5, 0.8), replicate
         print(line, flush=True)
 
 
+def torch_rerank(ids, scores, count, vectors, category, target, k, w, alpha=0.01, lazy=False, budget=1 << 30):
+    """The joint re-rank built only from stock PyTorch, over chunks of lists that keep a leg's largest tensors within ``budget``
+    bytes.  ``lazy`` False: gather + ``torch.bmm`` Gram [g, M, M], then k rounds of element-wise operations with ``torch.log`` in
+    float64 and arg-max over the chunk's lists at once.  ``lazy`` True: the rows are gathered once per chunk and every step takes
+    one batched matrix-vector product with the picked rows — no Gram.  Every id is taken to lie in the table and every category in
+    [0, C); NaN scores and the order among tied values are not the contract's (a yardstick for speed)."""
+    G, M = ids.shape
+    d = int(vectors.shape[1])
+    dev = ids.device
+    wr, wd, wc = (float(x) for x in w)
+    per_list = 4 * M * d + (0 if lazy else 4 * M * M) + 64 * M
+    step = max(1, min(G, budget // per_list))
+    outs = []
+    one = torch.ones((), dtype=torch.float64, device=dev)
+    neg = torch.full((), float("-inf"), device=dev)
+    for g0 in range(0, G, step):
+        I, S, cn = ids[g0:g0 + step], scores[g0:g0 + step], count[g0:g0 + step]
+        g = int(I.shape[0])
+        rows = vectors[I]
+        sim = None if lazy or wd == 0 else torch.bmm(rows, rows.transpose(1, 2))
+        elem = torch.arange(M, device=dev)[None, :] < cn[:, None]
+        pen = torch.zeros((g, M), device=dev)
+        chosen = torch.zeros((g, M), dtype=torch.bool, device=dev)
+        ar = torch.arange(g, device=dev)
+        out_i = torch.full((g, k), -1, dtype=torch.int64, device=dev)
+        out_s = torch.full((g, k), float("-inf"), device=dev)
+        cnt = torch.zeros(g, dtype=torch.int32, device=dev)
+        rel = wr * S
+        if wc != 0:
+            cat = category[I].to(torch.int64)
+            p = target[g0:g0 + step].to(torch.float64)
+            live = p > 0
+            n = torch.zeros_like(p)
+        for t in range(k):
+            ok = elem & ~chosen
+            value = rel - wd * pen if wd != 0 else rel
+            if wc != 0:
+                q0 = torch.where(live, (1.0 - alpha) * n / (t + 1.0) + alpha * p, one)
+                q1 = torch.where(live, (1.0 - alpha) * (n + 1.0) / (t + 1.0) + alpha * p, one)
+                gain = wc * (p * (torch.log(q1) - torch.log(q0))).to(torch.float32)
+                value = value + gain.gather(1, cat)
+            j = torch.where(ok, value, neg).argmax(dim=1)
+            hit = ok[ar, j]
+            out_i[:, t] = torch.where(hit, I[ar, j], out_i[:, t])
+            out_s[:, t] = torch.where(hit, S[ar, j], out_s[:, t])
+            chosen[ar, j] |= hit
+            if wd != 0 and t + 1 < k:
+                row = torch.bmm(rows, rows[ar, j][:, :, None])[:, :, 0] if lazy else sim[ar, j]
+                pen = torch.maximum(pen, row)
+            if wc != 0:
+                n[ar, cat[ar, j]] += hit.to(torch.float64)
+            cnt += hit.to(torch.int32)
+        outs.append((out_s, out_i, cnt))
+    return tuple(torch.cat([o[x] for o in outs]) for x in range(3))
+
+
+def bench_rerank(rounds=5, demo=1, d=400):
+    """``evaluate.rerank_select`` against ``torch_rerank`` with a Gram (a) and lazy (b), the legs in turn in one process, median
+    [min, max] of ``rounds`` rounds and each leg's peak of device bytes beyond its inputs: G in {64, 4 096} lists of M in {128,
+    1 024} ids of unit rows, d = 400, k in {10, 100}, C = 17, weights (0.5, 0.3, 0.2) and — long MMR — (0.7, 0.3, 0); at M = 128
+    without a calibration weight also ``evaluate.mmr_select``.  Then (``demo``) the effect on the planted-signal corpus
+    (``demo_rerank``)."""
+    from digat_amd import evaluate, util
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device="cpu").manual_seed(0)
+    news_num, C = 65238, 17
+    table = util.unit_rows(torch.randn(news_num, d, generator=g).to(dev))
+    table[1::2] = table[0:news_num - 1:2][:table[1::2].shape[0]]   # every other row a copy of its neighbour: the penalty bites
+    category = torch.randint(0, C, (news_num,), generator=g, dtype=torch.int32).to(dev)
+    conc = torch.distributions.Dirichlet(torch.full((C,), 0.7))
+
+    def peak(fn):
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        out = fn()
+        torch.cuda.synchronize()
+        return out, torch.cuda.max_memory_allocated() - base
+    stat = lambda v: (sorted(v)[len(v) // 2], min(v), max(v))
+    print(f"rerank: lists of ids of {news_num} unit rows, d = {d}, C = {C} categories, alpha = 0.01; ms per call, median [min, max] of "
+          f"{rounds} rounds; (a) gather + bmm Gram + k torch rounds, (b) rows gathered once + one batched matrix-vector product per step, "
+          f"both chunked to 1 GiB", flush=True)
+    for G in (64, 4096):
+        torch.manual_seed(G)
+        target = conc.sample((G,)).to(torch.float32).to(dev)
+        for M in (128, 1024):
+            ids = torch.randint(0, news_num, (G, M), generator=g).to(dev)
+            scores = torch.randn(G, M, generator=g).sort(dim=1, descending=True).values.to(dev)      # a shortlist comes sorted
+            count = torch.full((G,), M, dtype=torch.int32, device=dev)
+            for k in (10, 100):
+                for w in ((0.5, 0.3, 0.2), (0.7, 0.3, 0.0)):
+                    w32 = tuple(np.float32(x) for x in w)
+                    cal = w[2] != 0
+                    legs = {"rerank_select": lambda: evaluate.rerank_select(ids, scores, count, table, k, *w32, category=category if cal else None,
+                                                                            target=target if cal else None),
+                            "(a)": lambda: torch_rerank(ids, scores, count, table, category, target, k, w32),
+                            "(b)": lambda: torch_rerank(ids, scores, count, table, category, target, k, w32, lazy=True)}
+                    if M == 128 and not cal:
+                        legs["mmr_select"] = lambda: evaluate.mmr_select(ids, scores, count, table, k, w32[0])
+                    outs = {name: peak(fn) for name, fn in legs.items()}
+                    got = outs["rerank_select"][0]
+                    same = {name: float((got[1] == o[0][1]).float().mean()) for name, o in outs.items() if name != "rerank_select"}
+                    iters = 5 if G * M * k <= 64 * 1024 * 100 else 2
+                    ms = {name: [] for name in legs}
+                    for _ in range(rounds):
+                        for name, fn in legs.items():
+                            ms[name].append(timeit(fn, iters=iters, warm=1)[0])
+                    a = stat(ms["rerank_select"])[0]
+                    line = f"  G = {G:5d}, M = {M:4d}, k = {k:3d}, w = {w}: "
+                    line += " | ".join(f"{name} {stat(v)[0]:9.3f} ms [{stat(v)[1]:.3f}, {stat(v)[2]:.3f}]"
+                                       + (f" (x{stat(v)[0] / a:.2f})" if name != "rerank_select" else f" ({1e3 * a / k:.1f} us per step)")
+                                       + f" peak {outs[name][1] / 2**20:.1f} MiB" for name, v in ms.items())
+                    line += " | ids equal: " + ", ".join(f"{name} {v:.4f}" for name, v in same.items())
+                    print(line, flush=True)
+            del ids, scores, count
+        del target
+    del table
+    torch.cuda.empty_cache()
+    if demo:
+        demo_rerank()
+
+
+def demo_rerank(users=512, k=10, shortlist=80, replicates=2000):
+    """What ``recommend(rerank=)`` does on the planted-signal corpus beside the re-rankers of one kind: the trained DIGAT
+    (tests/golden/trained_planted_state.npz), ``users`` held-out impressions against the pool of all news, k = 10, shortlist 80:
+    plain, ``diversity=0.3``, ``calibration=0.5`` and ``rerank=(0.2, 0.4)``.  Reported per setting, as means over the users with
+    95 % intervals (``evaluate.metric_intervals``) and, against plain, the paired difference (``evaluate.compare_metrics``): ``ild``
+    (``evaluate.list_quality`` over unit rows), ``kl`` (``util.calibration_kl`` against the history's category mix), recall@k of the
+    impression's clicked candidates (summed hits over summed clicks) and MRR."""
+    import types
+    from digat_amd import evaluate, synthetic, util
+    from digat_amd.main import clicked_targets
+    from digat_amd.model import Model, PrecomputedNewsEncoder
+    dev = torch.device("cuda:0")
+    golden = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
+    state = {name: v for name, v in np.load(os.path.join(golden, "trained_planted_state.npz")).items()}
+    depth = int(np.load(os.path.join(golden, "devset_trained_2k.npz"))["depth"])
+    full = synthetic.make_corpus(synthetic.SynthSpec(**synthetic.PLANTED_SPEC))
+    corpus = synthetic.slice_impressions(full, 0, users)
+    spec = full.spec
+    cfg = types.SimpleNamespace(news_encoder="MSA", graph_encoder="DIGAT", news_graph_size=spec.news_graph_size,
+                                max_history_num=spec.max_history_num, category_num=spec.category_num, graph_depth=depth, dropout_rate=0.2)
+    model = Model(cfg, news_encoder=PrecomputedNewsEncoder(torch.from_numpy(corpus.news_embedding)))
+    model.graph_encoder.load_state_dict({name: torch.from_numpy(v) for name, v in state.items()})
+    model = model.to(dev).eval()
+    dc = util.DeviceCorpus.from_numpy(corpus, dev)
+    who = np.arange(users, dtype=np.int64)
+    pool = np.arange(1, spec.news_num, dtype=np.int64)
+    C = int(dc.news_category.max()) + 1
+    target = evaluate.category_share(dc.history, dc.news_category, C)
+    unit = util.unit_rows(dc.news_embedding)
+    tg_ids, tg_start = clicked_targets(dc, corpus.row_label)
+    names = ("ild", "kl", f"recall@{k}", "mrr")
+    settings = (("plain", dict()), ("diversity=0.3", dict(diversity=0.3, shortlist=shortlist)),
+                ("calibration=0.5", dict(calibration=0.5, shortlist=shortlist)), ("rerank=(0.2, 0.4)", dict(rerank=(0.2, 0.4), shortlist=shortlist)))
+
+    def columns(kw):
+        ids, scores, count = util.recommend(model, dc, who, pool, k, **kw)
+        kl = util.calibration_kl(ids, count, dc.news_category, target).cpu().numpy().astype(np.float64)
+        q = evaluate.list_quality(ids, count, vectors=unit)
+        el = q["elements"].cpu().numpy().astype(np.float64)
+        two = (el > 1).astype(np.float64)                                 # quality_summary's ild: the mean over lists with a pair
+        ild = two * (1.0 - q["sim_sum"].cpu().numpy() / np.maximum(el * (el - 1.0) / 2.0, 1.0))
+        col = evaluate.rank_metric_columns(evaluate.list_ranks(ids, count, tg_ids, tg_start), tg_start, ks=(k,))
+        ones = np.ones(users)
+        return (np.stack([ild, kl, col[f"hits@{k}"], col["rr"]], axis=1), np.stack([two, ones, col["targets"], col["has"]], axis=1),
+                evaluate.quality_summary(q))
+    base = None
+    print(f"rerank demo: planted-signal corpus, {spec.news_num - 1} news in {C} categories, the trained DIGAT, {users} held-out impressions, "
+          f"k = {k}, shortlist {shortlist}; means with 95 % intervals from {replicates} replicates over users; 'vs plain': paired difference",
+          flush=True)
+    for name, kw in settings:
+        values, den, summary = columns(kw)
+        iv = evaluate.metric_intervals(values, names=names, replicates=replicates, denominators=den)
+        line = f"  {name}: " + "  ".join(f"{m} {iv[m]['value']:.4f} [{iv[m]['lo']:.4f}, {iv[m]['hi']:.4f}]" for m in names)
+        line += f"  (quality_summary ild {summary['ild']:.4f})"
+        if base is None:
+            base = (values, den)
+        else:
+            cmp = evaluate.compare_metrics(values, base[0], names=names, replicates=replicates, denominators_a=den, denominators_b=base[1])
+            line += " | vs plain: " + "  ".join(f"{m} {cmp[m]['diff']:+.4f} [{cmp[m]['lo']:+.4f}, {cmp[m]['hi']:+.4f}] p {cmp[m]['p']:.3f}"
+                                                for m in names)
+        print(line, flush=True)
+
+
 def stock_pl_sample(scores, count, k, temperature, samples, budget=1 << 30):
     """Plackett-Luce slates with their log-probabilities built only from stock PyTorch — what the tree offered before
     ``digat_pl_sample``: ``torch.rand`` -> two float64 logarithms -> add -> ``torch.topk`` -> gather -> the unpicked tail's
@@ -2558,6 +2752,8 @@ if __name__ == "__main__":
         bench_list_quality(*nums)
     elif what == "calibrate":
         bench_calibrate(*nums)
+    elif what == "rerank":
+        bench_rerank(*nums)
     elif what == "pl-sample":
         bench_pl_sample(*nums)
     elif what == "off-policy":
