@@ -102,6 +102,7 @@ _SIGNATURES = {
     "digat_user_ctx_fwd": (C.c_int, [_f] * 14 + [C.c_int] * 5 + [_f, C.c_size_t, _f]),
     "digat_user_ctx_grouped_workspace_bytes": (C.c_size_t, [C.c_int] * 6),
     "digat_user_ctx_fwd_grouped": (C.c_int, [_f] * 15 + [C.c_int] * 6 + [_f, C.c_size_t, _f]),
+    "digat_user_ctx0_fwd": (C.c_int, [_f, _f, C.c_int] + [_f] * 7 + [C.c_int, _f, _f] + [C.c_int] * 4 + [_f, C.c_size_t, _f]),
     "digat_user_nodes_build": (C.c_int, [_f] * 4 + [C.c_long, C.c_long] + [C.c_int] * 3 + [_f]),
     "digat_topic_pool_fwd": (C.c_int, [_f] * 4 + [C.c_int] * 5 + [_f]),
     "digat_encoder_workspace_bytes": (C.c_size_t, [C.c_int] * 6),

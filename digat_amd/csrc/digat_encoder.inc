@@ -89,6 +89,7 @@ struct EncoderCall {
     const float *news_hpq0, *hist_hpq0, *topic_hpq0, *ctxq0; const int64_t* news_index; int64_t news_rows;
     const uint8_t *run_leader, *run_lead;   // plan.shared: rows that lead a run, rows of the layer-0 chunk a row leads
     EncoderPlan plan;
+    bool ctx0;                              // encoder_plan_ctx0: the first user context of the folded pass is GEMM + user_ctx0_kernel
     EncoderWs ws;
 };
 struct SideStream { hipStream_t s; hipEvent_t fork, join, early; int ok; };
@@ -240,6 +241,22 @@ struct FoldedPass {
         e = launch_gemm(g, sq);
         if (e) return e;
         return launch_pool(T2, (long)C1 * d, kq_user, c.cat_mask, addend, c_u, B, C1, d, sq);
+    }
+
+    // The INITIAL c_u straight from the input rows (c.ctx0; digat_ctx0.inc): F x = ue W^T over the graphs ue holds (the groups of
+    // ENC_GROUPED, else every row: no list of the run leaders' history rows exists at this point of an ENC_SHARED pass), then one
+    // launch per row of the batch.  ue is read in place with stride H d: nothing here waits for build_user_nodes_kernel's output.
+    // F x lives in w.Xu[1], which nothing reads or writes before layer 0 of the user graph on the caller's stream — behind this
+    // call — with one exception: group_projection builds the groups' nodes at its start (G U d floats, possibly on the side
+    // stream, at once) when layer 0's nodes are not kept per group, so ENC_GROUPED puts F x behind them ((U + H) G d <= B U d
+    // floats: 4 G <= B).  The side stream's other early work (adjacency pass, news projection) has its own regions.
+    int user_context0(const float* kq_topic, const float* kq_user) const {
+        if (!kq_topic) { kq_topic = w.kq_t; kq_user = w.kq_u; }
+        const bool per_group = c.variant == ENC_GROUPED;
+        float* const fx = w.Xu[1] + (per_group ? (size_t)G * U * d : 0);
+        return launch_user_ctx0(c.ue, per_group ? G : B, (per_group || pl.shared) ? c.row_group : nullptr, kq_topic, kq_user, c.cat_idx,
+                                c.cat_mask, p->featureAffine_W, p->featureAffine_b, p->featureAffine_wsplit, f.fmt, f.range_flag, ragged,
+                                nullptr, c_u, fx, B, H, C1, d, st);
     }
 
     // c_n (+)= gate([local ; global context]) of the news nodes
@@ -558,8 +575,9 @@ struct FoldedPass {
             rc = context_queries(0, st);
             if (rc) return rc;
         }
-        rc = user_context(pl.xu0_grouped ? Xg0 : w.Xu[0], nullptr, st, (pl.xu0_grouped || pl.xu0_shared) ? c.row_group : nullptr, false,
-                          ctxq0, ctxq0 ? ctxq0 + bd : nullptr);        // c_u (:192)
+        rc = c.ctx0 ? user_context0(ctxq0, ctxq0 ? ctxq0 + bd : nullptr)
+                    : user_context(pl.xu0_grouped ? Xg0 : w.Xu[0], nullptr, st, (pl.xu0_grouped || pl.xu0_shared) ? c.row_group : nullptr, false,
+                                   ctxq0, ctxq0 ? ctxq0 + bd : nullptr);        // c_u (:192)
         if (rc) return rc;
         const float* xn_cur = c.Xn_in;
         int un = 0, nn = 0;
@@ -704,6 +722,7 @@ static int encoder_fwd_impl(EncoderCall& c) {
     in.news_index = c.news_index; in.news_rows = c.news_rows;
     in.fsplit = p->featureAffine_fsplit; in.ctx_fused_fits = ctxfused_ok(H, C + 1, d);
     const EncoderPlan& pl = c.plan = encoder_plan(in);
+    c.ctx0 = encoder_plan_ctx0(in);
     if (pl.status) return pl.status;
     Arena ar(c.workspace, c.workspace_bytes);
     if (!encoder_carve(ar, B, N, H, C, d, c.variant, c.ws)) return DIGAT_ERR_WORKSPACE;

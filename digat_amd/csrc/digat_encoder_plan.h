@@ -57,6 +57,25 @@ struct EncoderPlan {
     bool side_wanted;                // this pass wants a side stream (whether it gets one: side_stream())
 };
 
+// ---- the initial user context in one launch (user_ctx0_kernel, digat_ctx0.inc) ----------------------------------------------------
+// The kernel's LDS image: M [ceil(C1 / 16) * 16, H | 1], per-wave score scratch [waves, 64], four 64-entry tables (+ 4), 16 per-wave
+// floats, and the pooled topics [C1, d]
+static inline size_t ctx0_lds_bytes(int H, int C1, int d) {
+    const size_t ct = (size_t)(C1 + 15) / 16, waves = (size_t)(d + 63) / 64;
+    return (ct * 16 * (size_t)(H | 1) + waves * 64 + 3 * 64 + 68 + 16 + (size_t)C1 * d) * 4;
+}
+// Does (H, C + 1, d) fit the kernel?  The history rows of a wave's 64 channels live in registers (H <= 64: 16 four-row steps; the
+// 16-step instantiation is bounded to 512 threads like topic_pool_resident_kernel<16>, so H > 52 needs d <= 512), one wave per 64
+// channels (d <= 1024), one lane per bucket (C1 <= 64), and at least two workgroups' LDS images per CU (64 KB each at most).
+static inline bool ctx0_fits(int H, int C1, int d) {
+    return H >= 1 && H <= 64 && d > 0 && d % 4 == 0 && d <= 1024 && C1 >= 1 && C1 <= 64 && (H <= 52 || d <= 512) &&
+           ctx0_lds_bytes(H, C1, d) <= (size_t)64 * 1024;
+}
+// The plan bit: the folded pass's FIRST user context is the GEMM F x = ue W^T + user_ctx0_kernel, for every variant and operand
+// format, with and without the fused user context (which keeps governing calls 1..L).  A function of the plan's input beside
+// EncoderPlan rather than a member of it: it depends on the shape alone.
+static inline bool encoder_plan_ctx0(const EncoderPlanIn& in) { return in.folded && ctx0_fits(in.H, in.C + 1, in.d); }
+
 static inline EncoderPlan encoder_plan(const EncoderPlanIn& in) {
     EncoderPlan pl = {};
     const int flags = in.flags, B = in.B, N = in.N, H = in.H, C = in.C, d = in.d, L = in.L, U = H + C;

@@ -234,6 +234,7 @@ constexpr int TWIN_R = DIGAT_TWIN_R;   // centres with equal adjacency rows serv
 #include "digat_gemm.inc"
 #include "digat_xattn.inc"
 #include "digat_context.inc"
+#include "digat_ctx0.inc"
 #include "digat_ctxfused.inc"
 #include "digat_glue.inc"
 
@@ -704,6 +705,21 @@ int digat_user_ctx_fwd(const float* Xu, const uint8_t* cat_mask, const int64_t* 
     if (B == 0) return DIGAT_OK;
     return user_ctx_run(Xu, cat_mask, cat_idx, nullptr, c_n, Ku, Qu, bQu, Fa, bFa, Kua, Qua, bQua, addend, out, B, U, H, C1, d, w,
                         (hipStream_t)stream);
+}
+
+// the initial user context alone: F x = ue Fa^T + user_ctx0_kernel (digat_ctx0.inc), the encoder's first context launch for launch
+int digat_user_ctx0_fwd(const float* ue, const int32_t* row_group, int G, const float* kq_topic, const float* kq_user,
+                        const uint8_t* cat_mask, const int64_t* cat_idx, const float* Fa, const float* bFa,
+                        const void* fa_wsplit, int format, const float* addend, float* out, int B, int H, int C1, int d,
+                        void* scratch, size_t scratch_bytes, void* stream) {
+    if (!ue || !kq_topic || !kq_user || !cat_mask || !cat_idx || !Fa || !bFa || !out || !scratch) return DIGAT_ERR_ARG;
+    if (B < 0 || H < 0 || C1 <= 0 || d <= 0 || (row_group && G <= 0)) return DIGAT_ERR_ARG;
+    if (!ctx0_fits(H, C1, d)) return DIGAT_ERR_SHAPE;
+    const long rows = row_group ? G : B;
+    if (scratch_bytes < (size_t)rows * H * d * 4) return DIGAT_ERR_WORKSPACE;
+    if (B == 0) return DIGAT_OK;
+    return launch_user_ctx0(ue, rows, row_group, kq_topic, kq_user, cat_idx, cat_mask, Fa, bFa, fa_wsplit, format, nullptr, 0, addend, out,
+                            (float*)scratch, B, H, C1, d, (hipStream_t)stream);
 }
 
 // ---- folded attention queries (inference): (K x).(Q c + b) = x.(K^T Q c + K^T b) ------------------

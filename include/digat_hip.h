@@ -167,6 +167,22 @@ int digat_user_ctx_fwd_grouped(const float* Xu, const uint8_t* cat_mask, const i
                                const float* addend, float* out, int B, int G, int U, int H, int C1, int d,
                                void* workspace, size_t workspace_bytes, void* stream);
 
+/* The INITIAL user context of an encoder pass alone (round 8): c_u = compute_user_graph_context on the INPUT history rows, as the
+ * GEMM F x = ue Fa^T followed by one launch (user_ctx0_kernel) — featureAffine is linear and a present category's pooling weights
+ * sum to one, so it is applied to the few history rows in front of the pooling instead of to the B C1 pooled rows behind it; the
+ * pooled topics never reach memory.  ue [G,H,d] with row_group [B] int32 (row b reads group row_group[b]; values must lie in
+ * [0, G)), or [B,H,d] with row_group == NULL (G is ignored).  kq_topic, kq_user [B,d]: the two folded queries K^T (Q c_n + bQ);
+ * cat_mask [B,C1], cat_idx [B,H] per row; Fa [d,d], bFa [d]; fa_wsplit: digat_split_weights(Fa, d, d, ., format) output in
+ * `format` (DIGAT_GEMM_BF16X6 / _F16X3), or NULL for the exact fp32 product; addend NULL, [B,d] or == out; out [B,d].
+ * scratch: rows H d floats (rows = G or B), wholly written before it is read.  A row of the result has the same bits in a grouped
+ * and a per-row call and at every B and G.  Shapes: H in [1,64], d % 4 == 0, d <= 1024, C1 <= 64, H <= 52 or d <= 512, and
+ * (C1 d + ...) 4 bytes of LDS within 64 KB (DIGAT_ERR_SHAPE otherwise: digat_user_ctx_fwd serves those).  B == 0 returns
+ * without a launch.  No allocation, no host synchronisation. */
+int digat_user_ctx0_fwd(const float* ue, const int32_t* row_group, int G, const float* kq_topic, const float* kq_user,
+                        const uint8_t* cat_mask, const int64_t* cat_idx, const float* Fa, const float* bFa,
+                        const void* fa_wsplit, int format, const float* addend, float* out, int B, int H, int C1, int d,
+                        void* scratch, size_t scratch_bytes, void* stream);
+
 /* The user graph's node features Xu = [user_news_embedding (H rows) | topic_node_embedding (C rows)] (graphEncoders.py:191) in one
  * launch: ue [G,H,d], topic [C,d].  row_group == NULL: Xu [G,U,d], one graph per group (rows must equal G).  row_group [rows]
  * int32: Xu [rows,U,d], graph r built from group row_group[r] (held inside [0, G)) — the expanded tensor written directly.
