@@ -16,7 +16,8 @@
 // category.  value = fl(fl(lam * s) + fl(mu * gain32)) and q~ = fl(fl(fl((1 - alpha) n) / T) + fl(alpha p)) are written with
 // contraction switched off (cal_value, cal_q): never an fma.  The outputs are written once, behind the loop, and kl is one more
 // logarithm pair per category, summed over the wave by a butterfly (a fixed order: the same bits from run to run and in any batch).
-// No atomics, no workspace.
+// No atomics, no workspace.  The count clamp and the fill of unused slots are digat_mmr.inc's (sel_count, sel_fill); the target row,
+// a step's gains and the kl epilogue are __device__ functions below (cal_target, cal_gain, cal_finish) that digat_rerank.inc calls too.
 //
 // Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage):
 //   cal_kernel<1, 2>   64 threads   VGPRs 52   SGPRs 57   LDS 0 B    scratch 0   occupancy 8 waves / SIMD
@@ -67,14 +68,47 @@ __device__ __forceinline__ double cal_q(double oma, int n, double T, double ap) 
     return share + ap;
 }
 
+// The calibration pieces of a list, shared with rr_kernel and rr_gram_kernel (digat_rerank.inc).  Lane c of a wave owns category c.
+// p_c of list g: the target where it is finite and > 0, else 0 (lanes from C on: 0).
+__device__ __forceinline__ double cal_target(const float* target, const long g, const int C, const int lane) {
+    double p = 0.0;
+    if (lane < C) {
+        const float tv = target[g * C + lane];
+        if (tv > 0.f && tv < INFINITY) p = (double)tv;       // a NaN fails both comparisons
+    }
+    return p;
+}
+
+// fl(w * gain32_c) of step t with n_c = n picked: the two float64 logarithms of the lane's category; 0 where p_c = 0.
+__device__ __forceinline__ float cal_gain(const float w, const double p, const double oma, const double ap, const int n, const int t) {
+    if (!(p > 0.0)) return 0.f;
+    const double T = (double)(t + 1);
+    const double q0 = cal_q(oma, n, T, ap), q1 = cal_q(oma, n + 1, T, ap);
+    const double gain = p * (log(q1) - log(q0));
+    return cal_mul(w, (float)gain);
+}
+
+// Behind the loop, one whole wave: kl of the finished list of t picks — one more logarithm pair per category, summed by a butterfly
+// (a fixed order) — and lane 0 writes it with the count.
+__device__ __forceinline__ void cal_finish(const double p, const double oma, const double ap, const int n, const int t, const int lane,
+                                           const long g, int32_t* out_count, float* out_kl) {
+    double term = 0.0;
+    if (p > 0.0) term = p * (log(p) - log(cal_q(oma, n, (double)(t > 1 ? t : 1), ap)));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) term += __shfl_xor(term, o, 64);
+    if (lane == 0) {
+        out_count[g] = t;
+        out_kl[g] = (float)term;
+    }
+}
+
 template <int WAVES, int PPL>
 __global__ void __launch_bounds__(64 * WAVES) cal_kernel(const CalArgs a) {
     __shared__ unsigned xkey[2][WAVES];              // a wave's winner of the step, double-buffered: one barrier per step
     __shared__ int xpos[2][WAVES], xcat[2][WAVES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long g = blockIdx.x;
-    int cnt = a.count ? a.count[g] : a.M;
-    cnt = cnt < 0 ? 0 : (cnt > a.M ? a.M : cnt);
+    const int cnt = sel_count(a.count, g, a.M);
 
     float s[PPL];
     int cat[PPL], picked[PPL];
@@ -94,24 +128,14 @@ __global__ void __launch_bounds__(64 * WAVES) cal_kernel(const CalArgs a) {
         }
     }
     // lane c of every wave: category c of this list
-    double p = 0.0;
-    if (lane < a.C) {
-        const float tv = a.target[g * a.C + lane];
-        if (tv > 0.f && tv < INFINITY) p = (double)tv;       // a NaN fails both comparisons
-    }
+    const double p = cal_target(a.target, g, a.C, lane);
     const double oma = 1.0 - a.alpha;
     const double ap = a.alpha * p;
     int n = 0;
 
     int t = 0;
     for (; t < a.k; ++t) {
-        float mg = 0.f;
-        if (p > 0.0) {
-            const double T = (double)(t + 1);
-            const double q0 = cal_q(oma, n, T, ap), q1 = cal_q(oma, n + 1, T, ap);
-            const double gain = p * (log(q1) - log(q0));
-            mg = cal_mul(a.mu, (float)gain);
-        }
+        const float mg = cal_gain(a.mu, p, oma, ap, n, t);
         unsigned bkey = 0u;
         int bpos = 0, bcat = 0;
 #pragma unroll
@@ -169,20 +193,8 @@ __global__ void __launch_bounds__(64 * WAVES) cal_kernel(const CalArgs a) {
             a.out_ids[g * a.k + picked[h]] = a.ids[g * a.M + tid * PPL + h];
         }
     }
-    for (int x = t + tid; x < a.k; x += 64 * WAVES) {
-        a.out_scores[g * a.k + x] = -INFINITY;
-        a.out_ids[g * a.k + x] = -1;
-    }
-    if (wave == 0) {
-        double term = 0.0;
-        if (p > 0.0) term = p * (log(p) - log(cal_q(oma, n, (double)(t > 1 ? t : 1), ap)));
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) term += __shfl_xor(term, o, 64);
-        if (lane == 0) {
-            a.out_count[g] = t;
-            a.out_kl[g] = (float)term;
-        }
-    }
+    sel_fill(a.out_scores, a.out_ids, g, a.k, t, tid, 64 * WAVES);
+    if (wave == 0) cal_finish(p, oma, ap, n, t, lane, g, a.out_count, a.out_kl);
 }
 
 extern "C" {

@@ -23,6 +23,8 @@
 // The Gram is mmr_gram, a __device__ function that digat_listq.inc calls too: one product in the sources.  With the loop written out
 // inside mmr_kernel the compiler reported 44 VGPRs; 44 + 64 and 46 + 64 both allocate 112 registers a lane (granule 8), scratch is 0
 // either way and the selection's bits are the same (tests/test_hip_diversify.py), so the function is shared and not copied.
+// The count clamp and the fill of unused slots (sel_count, sel_fill) are __device__ functions too, called by digat_calibrate.inc and
+// digat_rerank.inc: the line above is what the compiler reports with them, as it was without.  The one-wave winner is not (below).
 
 #define MMR_MAX_M TOPK_MAX_K
 
@@ -55,6 +57,27 @@ __device__ __forceinline__ float mmr_value(float lam, float s, float mu, float p
     const float red = mu * pen;
     return rel - red;
 }
+
+// The pieces every greedy re-rank kernel shares (cal_kernel, rr_kernel and rr_gram_kernel call them too).
+// A list's count clamped to [0, M]; no count: M.
+__device__ __forceinline__ int sel_count(const int32_t* count, const long g, const int M) {
+    const int cnt = count ? count[g] : M;
+    return cnt < 0 ? 0 : (cnt > M ? M : cnt);
+}
+
+// Slots t .. k - 1 of list g hold no pick: -inf / -1.  Thread `tid` of `threads`.
+__device__ __forceinline__ void sel_fill(float* out_scores, int64_t* out_ids, const long g, const int k, const int t, const int tid,
+                                         const int threads) {
+    for (int x = t + tid; x < k; x += threads) {
+        out_scores[g * k + x] = -INFINITY;
+        out_ids[g * k + x] = -1;
+    }
+}
+
+// NOT shared: the one-wave winner (a wave max over the 32-bit keys, two ballots for the lowest position that holds it), which
+// mmr_kernel and rr_gram_kernel (digat_rerank.inc) each write out.  As a function — returning j, or j through a reference — the
+// "nothing eligible" exit merges with the found position and j becomes a per-lane value: a VGPR, the Gram's row address a vector
+// multiply, where the ballots give a scalar.  Registers, LDS and occupancy did not move, but both kernels measured about 1 % slower.
 
 // The [16 T, 16 T] Gram of the rows lid[] names (-1: a zero row) into L as S[col][row], row stride ld — the one product of this file and
 // of digat_listq.inc.  Called by all 256 threads of the workgroup, lid[] written and a barrier passed; returns behind the barrier
@@ -127,8 +150,7 @@ __global__ void __launch_bounds__(256) mmr_kernel(const MmrArgs a) {
     float* const L = (float*)mmr_lds;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long g = blockIdx.x;
-    int cnt = a.count ? a.count[g] : a.M;
-    cnt = cnt < 0 ? 0 : (cnt > a.M ? a.M : cnt);
+    const int cnt = sel_count(a.count, g, a.M);
     const int T = (cnt + 15) >> 4;                   // 16-row tiles of this user's Gram: <= 8, and 16 T <= ld - 4
     if (tid < MMR_MAX_M) {
         long long id = -1;
@@ -200,10 +222,7 @@ __global__ void __launch_bounds__(256) mmr_kernel(const MmrArgs a) {
             a.out_ids[g * a.k + picked[h]] = (int64_t)id[h];
         }
     }
-    for (int x = t + lane; x < a.k; x += 64) {
-        a.out_scores[g * a.k + x] = -INFINITY;
-        a.out_ids[g * a.k + x] = -1;
-    }
+    sel_fill(a.out_scores, a.out_ids, g, a.k, t, lane, 64);
     if (lane == 0) a.out_count[g] = t;
 }
 

@@ -2,8 +2,11 @@
 // and a cap per category in ONE greedy pass over a shortlist of up to DIGAT_RERANK_MAX_LIST = 1024 entries per user — the last stage
 // behind util.recommend(rerank=) / nrms.recommend(rerank=), and plain MMR beyond the 128 entries digat_mmr_select stops at.  Included at
 // the end of digat_kernels.hip, behind digat_topk.inc (topk_key), digat_dot_topk.inc (dot_load4), digat_list_softmax.inc (the LSM_*
-// tile sizes: the similarity below is lsm_score_stage's product, restated with the picked row where the user row stands) and
-// digat_calibrate.inc (cal_q, cal_mul: the gains are cal_kernel's).
+// tile sizes: the similarity below is lsm_score_stage's product, restated with the picked row where the user row stands),
+// digat_mmr.inc (sel_count, sel_fill, and for the short route mmr_gram) and digat_calibrate.inc (cal_target, cal_gain, cal_finish:
+// the target row, a step's gains and the kl epilogue are cal_kernel's own functions, called here, not copied — every kernel's
+// resource line is what it was with the code written out, down to the raw VGPR count).  One piece stays written out in
+// rr_gram_kernel, the one-wave winner: as a function it cost a scalar j and about 1 % (digat_mmr.inc has the details).
 //
 // rr_kernel, one workgroup of 256 threads per list, list position p = slab * 256 + tid held by thread tid as its slot `slab` (four slabs):
 // a thread keeps its slots' score, fl(w_rel s), gain category (-1: no element; 64: uncategorised), raw category, the step they were
@@ -95,8 +98,7 @@ __global__ void __launch_bounds__(256) rr_kernel(const RrArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c4 = (tid & 7) * 4, r0 = tid >> 3;                  // this thread stages rows r0 + 32 h, channels c4 .. c4 + 3
     const long g = blockIdx.x;
-    int cnt = a.count ? a.count[g] : a.M;
-    cnt = cnt < 0 ? 0 : (cnt > a.M ? a.M : cnt);
+    const int cnt = sel_count(a.count, g, a.M);
     const bool div = a.w_div != 0.f, cal = a.w_cal != 0.f;
     const bool vec = (a.d & 3) == 0 && (((uintptr_t)a.vectors) & 15) == 0;
 
@@ -129,12 +131,8 @@ __global__ void __launch_bounds__(256) rr_kernel(const RrArgs a) {
         lcat[pos] = (signed char)cat[b];
         lraw[pos] = raw[b];
     }
-    // lane c of every wave: category c of this list
-    double p = 0.0;
-    if (a.target && lane < a.C) {
-        const float tv = a.target[g * a.C + lane];
-        if (tv > 0.f && tv < INFINITY) p = (double)tv;            // a NaN fails both comparisons
-    }
+    // lane c of every wave: category c of this list (no target: C = 0, every p_c is 0)
+    const double p = cal_target(a.target, g, a.C, lane);
     const double oma = 1.0 - a.alpha;
     const double ap = a.alpha * p;
     int n = 0;
@@ -142,13 +140,7 @@ __global__ void __launch_bounds__(256) rr_kernel(const RrArgs a) {
 
     int t = 0;
     for (; t < a.k; ++t) {
-        float mg = 0.f;
-        if (cal && p > 0.0) {
-            const double Tn = (double)(t + 1);
-            const double q0 = cal_q(oma, n, Tn, ap), q1 = cal_q(oma, n + 1, Tn, ap);
-            const double gain = p * (log(q1) - log(q0));
-            mg = cal_mul(a.w_cal, (float)gain);
-        }
+        const float mg = cal ? cal_gain(a.w_cal, p, oma, ap, n, t) : 0.f;
         unsigned long long best = 0ull;
 #pragma unroll
         for (int b = 0; b < LSM_SLABS; ++b) {
@@ -233,20 +225,8 @@ __global__ void __launch_bounds__(256) rr_kernel(const RrArgs a) {
             a.out_ids[g * a.k + picked[b]] = (int64_t)lid[b * LSM_SLAB + tid];
         }
     }
-    for (int x = t + tid; x < a.k; x += 256) {
-        a.out_scores[g * a.k + x] = -INFINITY;
-        a.out_ids[g * a.k + x] = -1;
-    }
-    if (wave == 0) {
-        double term = 0.0;
-        if (p > 0.0) term = p * (log(p) - log(cal_q(oma, n, (double)(t > 1 ? t : 1), ap)));
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) term += __shfl_xor(term, o, 64);
-        if (lane == 0) {
-            a.out_count[g] = t;
-            a.out_kl[g] = (float)term;
-        }
-    }
+    sel_fill(a.out_scores, a.out_ids, g, a.k, t, tid, 256);
+    if (wave == 0) cal_finish(p, oma, ap, n, t, lane, g, a.out_count, a.out_kl);
 }
 
 // The route of short lists, M <= 128: mmr_kernel's layout.  All four waves form the list's Gram in LDS (mmr_gram — the product digat_mmr.inc
@@ -260,8 +240,7 @@ __global__ void __launch_bounds__(256) rr_gram_kernel(const RrArgs a, const int 
     float* const L = (float*)rr_lds;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long g = blockIdx.x;
-    int cnt = a.count ? a.count[g] : a.M;
-    cnt = cnt < 0 ? 0 : (cnt > a.M ? a.M : cnt);
+    const int cnt = sel_count(a.count, g, a.M);
     const bool div = a.w_div != 0.f, cal = a.w_cal != 0.f;
     const int T = (cnt + 15) >> 4;                   // 16-row tiles of this list's Gram: <= 8, and 16 T <= ld - 4
     if (tid < MMR_MAX_M) {
@@ -302,23 +281,13 @@ __global__ void __launch_bounds__(256) rr_gram_kernel(const RrArgs a, const int 
         lraw[pos] = raw[h];
     }
     dot_wave_sync();
-    double p = 0.0;
-    if (a.target && lane < a.C) {
-        const float tv = a.target[g * a.C + lane];
-        if (tv > 0.f && tv < INFINITY) p = (double)tv;
-    }
+    const double p = cal_target(a.target, g, a.C, lane);
     const double oma = 1.0 - a.alpha;
     const double ap = a.alpha * p;
     int n = 0;
     int t = 0;
     for (; t < a.k; ++t) {
-        float mg = 0.f;
-        if (cal && p > 0.0) {
-            const double Tn = (double)(t + 1);
-            const double q0 = cal_q(oma, n, Tn, ap), q1 = cal_q(oma, n + 1, Tn, ap);
-            const double gain = p * (log(q1) - log(q0));
-            mg = cal_mul(a.w_cal, (float)gain);
-        }
+        const float mg = cal ? cal_gain(a.w_cal, p, oma, ap, n, t) : 0.f;
         unsigned key[2];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -327,7 +296,7 @@ __global__ void __launch_bounds__(256) rr_gram_kernel(const RrArgs a, const int 
             const bool eligible = cat[h] >= 0 && picked[h] < 0 && (a.q == 0 || same[h] < a.q);
             key[h] = eligible ? topk_key(rr_value(rel[h], a.w_div, pen[h], red, div, cal)) : 0u;
         }
-        unsigned best = key[0] > key[1] ? key[0] : key[1];
+        unsigned best = key[0] > key[1] ? key[0] : key[1];         // the one-wave winner, written out as in mmr_kernel (digat_mmr.inc says why)
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             const unsigned other = (unsigned)__shfl_xor((int)best, o, 64);
@@ -353,18 +322,8 @@ __global__ void __launch_bounds__(256) rr_gram_kernel(const RrArgs a, const int 
             a.out_ids[g * a.k + picked[h]] = (int64_t)id[h];
         }
     }
-    for (int x = t + lane; x < a.k; x += 64) {
-        a.out_scores[g * a.k + x] = -INFINITY;
-        a.out_ids[g * a.k + x] = -1;
-    }
-    double term = 0.0;
-    if (p > 0.0) term = p * (log(p) - log(cal_q(oma, n, (double)(t > 1 ? t : 1), ap)));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) term += __shfl_xor(term, o, 64);
-    if (lane == 0) {
-        a.out_count[g] = t;
-        a.out_kl[g] = (float)term;
-    }
+    sel_fill(a.out_scores, a.out_ids, g, a.k, t, lane, 64);
+    cal_finish(p, oma, ap, n, t, lane, g, a.out_count, a.out_kl);
 }
 
 extern "C" {

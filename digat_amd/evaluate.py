@@ -1628,17 +1628,70 @@ def mmr_weights(lam):
     return lam32, np.float32(1) - lam32
 
 
-def _check_mmr_args(ids_shape, scores_shape, count_shape, k, category_shape, max_per_category):
-    if len(ids_shape) != 2 or tuple(scores_shape) != tuple(ids_shape) or not 1 <= ids_shape[1] <= MMR_MAX_LIST:
-        raise ValueError(f"ids and scores must both be [G, M] with 1 <= M <= {MMR_MAX_LIST}, got {tuple(ids_shape)} and {tuple(scores_shape)}")
+def _check_select_shapes(ids_shape, scores_shape, count_shape, k, max_list):
+    """What every greedy re-rank asks of its lists: ``ids`` / ``scores`` [G, 1 <= M <= max_list], ``count`` [G] or None, ``k``."""
+    if len(ids_shape) != 2 or tuple(scores_shape) != tuple(ids_shape) or not 1 <= ids_shape[1] <= max_list:
+        raise ValueError(f"ids and scores must both be [G, M] with 1 <= M <= {max_list}, got {tuple(ids_shape)} and {tuple(scores_shape)}")
     if count_shape is not None and tuple(count_shape) != (ids_shape[0],):
         raise ValueError(f"count must have one entry per list ({ids_shape[0]}), got shape {tuple(count_shape)}")
     if not 1 <= int(k) <= TOPK_MAX_K:
         raise ValueError(f"k must be in [1, {TOPK_MAX_K}], got {k}")
+
+
+def _check_cap(category_shape, max_per_category):
     if int(max_per_category) < 0:
         raise ValueError(f"max_per_category must be >= 0 (0: no cap), got {max_per_category}")
     if int(max_per_category) > 0 and category_shape is None:
         raise ValueError("max_per_category needs category")
+
+
+def _check_target_shape(target_shape, G):
+    if len(target_shape) != 2 or target_shape[0] != G or not 1 <= target_shape[1] <= CAL_MAX_CATEGORIES:
+        raise ValueError(f"target must be [G, C] = [{G}, 1 <= C <= {CAL_MAX_CATEGORIES}], got {tuple(target_shape)}")
+
+
+def _shape(x):
+    return None if x is None else tuple(x.shape if hasattr(x, "shape") else np.shape(x))
+
+
+def _host_lists(ids, scores, category):
+    """``(ids int64, scores float32, category int64 or None)``: the arrays a host contract works on."""
+    return (np.asarray(ids, dtype=np.int64), np.ascontiguousarray(scores, dtype=np.float32),
+            None if category is None else np.asarray(category, dtype=np.int64))
+
+
+def _host_sim(sim, G, M):
+    S = np.asarray(sim, dtype=np.float32)
+    if S.shape != (G, M, M):
+        raise ValueError(f"sim must be [G, M, M] = {(G, M, M)}, got {S.shape}")
+    return S
+
+
+def _select_on_device(ids, scores, count, k, others, with_kl, workspace_bytes, tag):
+    """What the device wrappers of the greedy re-ranks share, behind their argument checks: all tensors on one device, the lists
+    as int64 / float32 / int32, the outputs ``(scores [G,k], ids [G,k], count [G])`` and with ``with_kl`` ``kl [G]``, and the
+    workspace of ``workspace_bytes(lib, G, M, k)`` bytes.  Returns ``(ids, scores, count, outputs, workspace, bytes)``; the
+    workspace is None where G == 0: there is nothing to launch and the empty outputs are the answer."""
+    import torch
+    from . import _lib
+    dev = _lib.require_device(*[t for t in (ids, scores, count) + tuple(others) if t is not None])
+    idt = ids.to(torch.int64).contiguous()
+    sc = _lib.f32(scores.detach())
+    ct = None if count is None else count.to(torch.int32).contiguous()
+    G, M, k = int(idt.shape[0]), int(idt.shape[1]), int(k)
+    outs = (torch.empty((G, k), dtype=torch.float32, device=dev), torch.empty((G, k), dtype=torch.int64, device=dev),
+            torch.empty((G,), dtype=torch.int32, device=dev))
+    if with_kl:
+        outs += (torch.empty((G,), dtype=torch.float32, device=dev),)
+    if G == 0:
+        return idt, sc, ct, outs, None, 0
+    need = int(workspace_bytes(_lib.lib(), G, M, k))
+    return idt, sc, ct, outs, _lib.workspace(need, dev, tag), need
+
+
+def _check_mmr_args(ids_shape, scores_shape, count_shape, k, category_shape, max_per_category):
+    _check_select_shapes(ids_shape, scores_shape, count_shape, k, MMR_MAX_LIST)
+    _check_cap(category_shape, max_per_category)
     if category_shape is not None and len(category_shape) != 1:
         raise ValueError(f"category must be [N], got shape {tuple(category_shape)}")
 
@@ -1650,49 +1703,17 @@ def mmr_select_host(ids, scores, count, sim, k: int, lam, category=None, max_per
     k steps: ``value = float32(lam) * s - float32(mu) * pen`` with every operation rounded, the winner is the eligible element with
     the largest ``topk_keys(value)``, ties to the lowest position; then ``pen = np.fmax(pen, sim[winner])``.  Eligible: not selected,
     and with ``max_per_category`` q > 0 fewer than q selected elements of its ``category[id]``.  Returns ``(scores [G,k] float32 —
-    the INPUT score bits —, ids [G,k] int64, count [G] int32)``; slots at or beyond ``count`` hold ``-inf`` / ``-1``."""
-    idv = np.asarray(ids, dtype=np.int64)
-    sc = np.ascontiguousarray(scores, dtype=np.float32)
-    cat = None if category is None else np.asarray(category, dtype=np.int64)
-    _check_mmr_args(idv.shape, sc.shape, None if count is None else np.shape(count), k, None if cat is None else cat.shape,
-                    max_per_category)
-    G, M = idv.shape
-    S = np.asarray(sim, dtype=np.float32)
-    if S.shape != (G, M, M):
-        raise ValueError(f"sim must be [G, M, M] = {(G, M, M)}, got {S.shape}")
+    the INPUT score bits —, ids [G,k] int64, count [G] int32)``; slots at or beyond ``count`` hold ``-inf`` / ``-1``.
+
+    This is ``rerank_select_host``'s greedy pass (``_greedy_select_host``) with weights ``(lam, mu, 0)`` and the diversity term
+    ALWAYS formed: at ``lam = 1`` the value is still ``rel - fl(0 * pen)``, a NaN where a similarity is infinite — as the kernel's."""
+    idv, sc, cat = _host_lists(ids, scores, category)
+    _check_mmr_args(idv.shape, sc.shape, _shape(count), k, _shape(cat), max_per_category)
+    S = _host_sim(sim, *idv.shape)
     lam32, mu32 = mmr_weights(lam)
-    k, q = int(k), int(max_per_category)
+    q = int(max_per_category)
     N = news_num if news_num is not None else (len(cat) if cat is not None else None)
-    cnt = np.full(G, M, dtype=np.int64) if count is None else np.clip(np.asarray(count, dtype=np.int64), 0, M)
-    out_s = np.full((G, k), -np.inf, dtype=np.float32)
-    out_i = np.full((G, k), -1, dtype=np.int64)
-    out_c = np.zeros(G, dtype=np.int32)
-    pos = np.arange(M)
-    for g in range(G):
-        elem = (pos < cnt[g]) & (idv[g] >= 0)
-        if N is not None:
-            elem &= idv[g] < N
-        cg = cat[np.where(elem, idv[g], 0)] if q > 0 and elem.any() else np.zeros(M, dtype=np.int64)
-        pen = np.zeros(M, dtype=np.float32)
-        chosen = np.zeros(M, dtype=bool)
-        same = np.zeros(M, dtype=np.int64)
-        for t in range(k):
-            ok = elem & ~chosen
-            if q > 0:
-                ok &= same < q
-            if not ok.any():
-                break
-            with np.errstate(invalid="ignore", over="ignore"):
-                value = (lam32 * sc[g]).astype(np.float32) - (mu32 * pen).astype(np.float32)
-            keys = np.where(ok, topk_keys(value).astype(np.int64), -1)
-            j = int(np.argmax(keys))                                # the first (lowest position) of the largest key
-            chosen[j] = True
-            out_s[g, t], out_i[g, t] = sc[g, j], idv[g, j]
-            out_c[g] = t + 1
-            pen = np.fmax(pen, S[g, j])
-            if q > 0:
-                same += elem & (cg == cg[j])
-    return out_s, out_i, out_c
+    return _greedy_select_host(idv, sc, count, S, int(k), lam32, mu32, np.float32(0), True, False, cat=cat if q > 0 else None, q=q, N=N)[:3]
 
 
 def mmr_select(ids, scores, count, vectors, k: int, lam, category=None, max_per_category: int = 0):
@@ -1707,35 +1728,25 @@ def mmr_select(ids, scores, count, vectors, k: int, lam, category=None, max_per_
     Stream-ordered: one launch, nothing is read back."""
     import torch
     from . import _lib
-    given = [t for t in (ids, scores, count, vectors, category) if t is not None]
-    dev = _lib.require_device(*given)
-    _check_mmr_args(tuple(ids.shape), tuple(scores.shape), None if count is None else tuple(count.shape), k,
-                    None if category is None else tuple(category.shape), max_per_category)
+    _check_mmr_args(_shape(ids), _shape(scores), _shape(count), k, _shape(category), max_per_category)
     if vectors.dim() != 2 or vectors.shape[1] < 1:
         raise ValueError(f"vectors must be [N, d] with d >= 1, got {tuple(vectors.shape)}")
     if category is not None and int(category.shape[0]) != int(vectors.shape[0]):
         raise ValueError(f"category must have one entry per row of vectors ({int(vectors.shape[0])}), got {int(category.shape[0])}")
     lam32, mu32 = mmr_weights(lam)
-    idt = ids.to(torch.int64).contiguous()
-    sc = _lib.f32(scores.detach())
-    ct = None if count is None else count.to(torch.int32).contiguous()
+    idt, sc, ct, outs, ws, need = _select_on_device(ids, scores, count, k, (vectors, category), False,
+                                                    lambda L, G, M, k: L.digat_mmr_select_workspace_bytes(G, M, k), "mmr")
     v = _lib.f32(vectors.detach())
+    if ws is None:
+        return outs
     q = int(max_per_category)
     cat = None if category is None or q == 0 else category.to(torch.int32).contiguous()
-    G, M, k = int(idt.shape[0]), int(idt.shape[1]), int(k)
-    out_s = torch.empty((G, k), dtype=torch.float32, device=dev)
-    out_i = torch.empty((G, k), dtype=torch.int64, device=dev)
-    out_c = torch.empty((G,), dtype=torch.int32, device=dev)
-    if G == 0:
-        return out_s, out_i, out_c
-    L = _lib.lib()
-    need = int(L.digat_mmr_select_workspace_bytes(G, M, k))
-    ws = _lib.workspace(need, dev, "mmr")
-    _lib.check(L.digat_mmr_select(idt.data_ptr(), sc.data_ptr(), _lib.ptr(ct), G, M, v.data_ptr(), int(v.shape[0]), int(v.shape[1]),
-                                  _lib.ptr(cat), q, float(lam32), float(mu32), k, out_i.data_ptr(), out_s.data_ptr(), out_c.data_ptr(),
-                                  ws.data_ptr(), need, _lib.stream_ptr()),
+    out_s, out_i, out_c = outs
+    _lib.check(_lib.lib().digat_mmr_select(idt.data_ptr(), sc.data_ptr(), _lib.ptr(ct), *idt.shape, v.data_ptr(), int(v.shape[0]), int(v.shape[1]),
+                                           _lib.ptr(cat), q, float(lam32), float(mu32), int(k), out_i.data_ptr(), out_s.data_ptr(),
+                                           out_c.data_ptr(), ws.data_ptr(), need, _lib.stream_ptr()),
                "digat_mmr_select")
-    return out_s, out_i, out_c
+    return outs
 
 
 def mmr_gram_stock(ids, vectors):
@@ -1761,16 +1772,10 @@ def _check_alpha(alpha) -> float:
 
 
 def _check_calibrate_args(ids_shape, scores_shape, count_shape, category_shape, target_shape, k):
-    if len(ids_shape) != 2 or tuple(scores_shape) != tuple(ids_shape) or not 1 <= ids_shape[1] <= CAL_MAX_LIST:
-        raise ValueError(f"ids and scores must both be [G, M] with 1 <= M <= {CAL_MAX_LIST}, got {tuple(ids_shape)} and {tuple(scores_shape)}")
-    if count_shape is not None and tuple(count_shape) != (ids_shape[0],):
-        raise ValueError(f"count must have one entry per list ({ids_shape[0]}), got shape {tuple(count_shape)}")
-    if not 1 <= int(k) <= TOPK_MAX_K:
-        raise ValueError(f"k must be in [1, {TOPK_MAX_K}], got {k}")
+    _check_select_shapes(ids_shape, scores_shape, count_shape, k, CAL_MAX_LIST)
     if category_shape is None or len(category_shape) != 1:
         raise ValueError(f"category must be [N], one entry per news, got {None if category_shape is None else tuple(category_shape)}")
-    if len(target_shape) != 2 or target_shape[0] != ids_shape[0] or not 1 <= target_shape[1] <= CAL_MAX_CATEGORIES:
-        raise ValueError(f"target must be [G, C] = [{ids_shape[0]}, 1 <= C <= {CAL_MAX_CATEGORIES}], got {tuple(target_shape)}")
+    _check_target_shape(target_shape, ids_shape[0])
 
 
 def calibrated_select_host(ids, scores, count, category, target, k: int, lam, alpha=0.01, return_robust: bool = False):
@@ -1794,76 +1799,17 @@ def calibrated_select_host(ids, scores, count, category, target, k: int, lam, al
     two — or the two are a true tie: equal scores and the same gain inputs (the same ``p_c`` bits and ``n_c``, or both
     gain-free), or one of the two scores is not finite (then neither value depends on a gain).  Two correct float64 logarithms
     may differ by one float32 step in ``gain32``, about 2 ulps of a value: on a robust list every such implementation picks
-    the same elements."""
-    idv = np.asarray(ids, dtype=np.int64)
-    sc = np.ascontiguousarray(scores, dtype=np.float32)
-    cat = None if category is None else np.asarray(category, dtype=np.int64)
+    the same elements.
+
+    This is ``rerank_select_host``'s greedy pass (``_greedy_select_host``) with weights ``(lam, 0, mu)`` and the calibration term
+    ALWAYS formed, ``mu = 0`` included — so the certificate is computed at every ``lam``."""
+    idv, sc, cat = _host_lists(ids, scores, category)
     tgt = np.asarray(target, dtype=np.float32)
-    _check_calibrate_args(idv.shape, sc.shape, None if count is None else np.shape(count), None if cat is None else cat.shape, tgt.shape, k)
+    _check_calibrate_args(idv.shape, sc.shape, _shape(count), _shape(cat), tgt.shape, k)
     lam32, mu32 = mmr_weights(lam)
-    alpha = np.float64(_check_alpha(alpha))
-    oma = np.float64(1.0) - alpha
-    (G, M), C, N, k = idv.shape, tgt.shape[1], len(cat), int(k)
-    cnt = np.full(G, M, dtype=np.int64) if count is None else np.clip(np.asarray(count, dtype=np.int64), 0, M)
-    out_s = np.full((G, k), -np.inf, dtype=np.float32)
-    out_i = np.full((G, k), -1, dtype=np.int64)
-    out_c = np.zeros(G, dtype=np.int32)
-    out_kl = np.zeros(G, dtype=np.float32)
-    robust = np.ones(G, dtype=bool)
-    pos = np.arange(M)
-    zero = np.float32(0)
-    for g in range(G):
-        elem = (pos < cnt[g]) & (idv[g] >= 0) & (idv[g] < N)
-        cg = cat[np.where(elem, idv[g], 0)] if elem.any() else np.zeros(M, dtype=np.int64)
-        cated = elem & (cg >= 0) & (cg < C)
-        ci = np.where(cated, cg, 0)
-        pbits = np.where(np.isfinite(tgt[g]) & (tgt[g] > 0), tgt[g], zero).astype(np.float32)
-        p = pbits.astype(np.float64)
-        live = p > 0
-        pl, apl = p[live], alpha * p[live]
-        free = ~(cated & live[ci])                                  # elements no gain reaches
-        n = np.zeros(C, dtype=np.int64)
-        chosen = np.zeros(M, dtype=bool)
-        with np.errstate(invalid="ignore", over="ignore"):
-            rel = (lam32 * sc[g]).astype(np.float32)
-        t_end = 0
-        for t in range(k):
-            ok = elem & ~chosen
-            if not ok.any():
-                break
-            T = np.float64(t + 1)
-            gain64 = np.zeros(C, dtype=np.float64)
-            nl = n[live].astype(np.float64)
-            gain64[live] = pl * (np.log((oma * (nl + 1.0)) / T + apl) - np.log((oma * nl) / T + apl))
-            with np.errstate(invalid="ignore", over="ignore"):
-                mg = (mu32 * gain64.astype(np.float32)).astype(np.float32)
-                red = np.where(cated, mg[ci], zero)
-                value = (rel + red).astype(np.float32)
-            keys = np.where(ok, topk_keys(value).astype(np.int64), -1)
-            j = int(np.argmax(keys))                                # the first (lowest position) of the largest key
-            if return_robust and robust[g]:
-                others = ok.copy()
-                others[j] = False
-                with np.errstate(invalid="ignore", over="ignore"):
-                    mag = np.maximum(np.maximum(np.abs(value), np.abs(rel)), np.abs(red))
-                    ulp = np.spacing(np.maximum(mag, mag[j]).astype(np.float32)).astype(np.float64)
-                    lead = np.float64(value[j]) - value.astype(np.float64)
-                    fixed = ~np.isfinite(rel) | ~np.isfinite(rel[j])
-                    same_gain = (free & free[j]) | (~free & ~free[j] & (pbits[ci].view(np.uint32) == pbits[ci[j]].view(np.uint32))
-                                                    & (n[ci] == n[ci[j]]))
-                    tie = (sc[g] == sc[g, j]) & same_gain
-                    if np.any(others & ~fixed & ~tie & ~(lead >= CAL_ROBUST_ULPS * ulp)):
-                        robust[g] = False
-            chosen[j] = True
-            out_s[g, t], out_i[g, t] = sc[g, j], idv[g, j]
-            t_end = t + 1
-            if cated[j]:
-                n[cg[j]] += 1
-        out_c[g] = t_end
-        if live.any():
-            q = (oma * n[live].astype(np.float64)) / np.float64(max(t_end, 1)) + apl
-            out_kl[g] = np.float32(np.sum(pl * (np.log(pl) - np.log(q))))
-    return (out_s, out_i, out_c, out_kl, robust) if return_robust else (out_s, out_i, out_c, out_kl)
+    out = _greedy_select_host(idv, sc, count, None, int(k), lam32, np.float32(0), mu32, False, True, cat=cat, tgt=tgt,
+                              alpha=_check_alpha(alpha), N=len(cat), want_robust=return_robust)
+    return out if return_robust else out[:4]
 
 
 def calibrated_select(ids, scores, count, category, target, k: int, lam, alpha=0.01):
@@ -1879,33 +1825,24 @@ def calibrated_select(ids, scores, count, category, target, k: int, lam, alpha=0
     or beyond ``count`` hold ``-inf`` / ``-1``.  Stream-ordered: one launch, nothing is read back."""
     import torch
     from . import _lib
-    given = [t for t in (ids, scores, count, category, target) if t is not None]
-    dev = _lib.require_device(*given)
-    _check_calibrate_args(tuple(ids.shape), tuple(scores.shape), None if count is None else tuple(count.shape),
-                          None if category is None else tuple(category.shape), tuple(target.shape), k)
+    _check_calibrate_args(_shape(ids), _shape(scores), _shape(count), _shape(category), _shape(target), k)
     lam32, mu32 = mmr_weights(lam)
     alpha = _check_alpha(alpha)
-    idt = ids.to(torch.int64).contiguous()
-    sc = _lib.f32(scores.detach())
-    ct = None if count is None else count.to(torch.int32).contiguous()
+    C = int(target.shape[1])
+    idt, sc, ct, outs, ws, need = _select_on_device(ids, scores, count, k, (category, target), True,
+                                                    lambda L, G, M, k: L.digat_calibrated_select_workspace_bytes(G, M, C, k), "calibrate")
     cat = category.to(torch.int32).contiguous()
     tg = _lib.f32(target.detach())
-    G, M, C, k = int(idt.shape[0]), int(idt.shape[1]), int(tg.shape[1]), int(k)
-    out_s = torch.empty((G, k), dtype=torch.float32, device=dev)
-    out_i = torch.empty((G, k), dtype=torch.int64, device=dev)
-    out_c = torch.empty((G,), dtype=torch.int32, device=dev)
-    out_kl = torch.empty((G,), dtype=torch.float32, device=dev)
-    if G == 0:
-        return out_s, out_i, out_c, out_kl
-    L = _lib.lib()
-    need = int(L.digat_calibrated_select_workspace_bytes(G, M, C, k))
-    ws = _lib.workspace(need, dev, "calibrate")
+    if ws is None:
+        return outs
+    out_s, out_i, out_c, out_kl = outs
     dummy = ws if int(cat.shape[0]) == 0 else cat                    # an empty tensor has no storage to point at
-    _lib.check(L.digat_calibrated_select(idt.data_ptr(), sc.data_ptr(), _lib.ptr(ct), G, M, dummy.data_ptr(), int(cat.shape[0]),
-                                         tg.data_ptr(), C, float(lam32), float(mu32), alpha, k, out_i.data_ptr(), out_s.data_ptr(),
-                                         out_c.data_ptr(), out_kl.data_ptr(), ws.data_ptr(), need, _lib.stream_ptr()),
+    _lib.check(_lib.lib().digat_calibrated_select(idt.data_ptr(), sc.data_ptr(), _lib.ptr(ct), *idt.shape, dummy.data_ptr(), int(cat.shape[0]),
+                                                  tg.data_ptr(), C, float(lam32), float(mu32), alpha, int(k), out_i.data_ptr(),
+                                                  out_s.data_ptr(), out_c.data_ptr(), out_kl.data_ptr(), ws.data_ptr(), need,
+                                                  _lib.stream_ptr()),
                "digat_calibrated_select")
-    return out_s, out_i, out_c, out_kl
+    return outs
 
 
 # ---- joint re-rank: diversity, calibration and a cap per category in one greedy pass over up to 1024 entries -----------------------
@@ -1932,16 +1869,8 @@ def _check_rerank_weights(w_rel, w_div, w_cal):
 
 
 def _check_rerank_args(ids_shape, scores_shape, count_shape, k, category_shape, target_shape, max_per_category, w_cal):
-    if len(ids_shape) != 2 or tuple(scores_shape) != tuple(ids_shape) or not 1 <= ids_shape[1] <= RERANK_MAX_LIST:
-        raise ValueError(f"ids and scores must both be [G, M] with 1 <= M <= {RERANK_MAX_LIST}, got {tuple(ids_shape)} and {tuple(scores_shape)}")
-    if count_shape is not None and tuple(count_shape) != (ids_shape[0],):
-        raise ValueError(f"count must have one entry per list ({ids_shape[0]}), got shape {tuple(count_shape)}")
-    if not 1 <= int(k) <= TOPK_MAX_K:
-        raise ValueError(f"k must be in [1, {TOPK_MAX_K}], got {k}")
-    if int(max_per_category) < 0:
-        raise ValueError(f"max_per_category must be >= 0 (0: no cap), got {max_per_category}")
-    if int(max_per_category) > 0 and category_shape is None:
-        raise ValueError("max_per_category needs category")
+    _check_select_shapes(ids_shape, scores_shape, count_shape, k, RERANK_MAX_LIST)
+    _check_cap(category_shape, max_per_category)
     if category_shape is not None and len(category_shape) != 1:
         raise ValueError(f"category must be [N], one entry per news, got shape {tuple(category_shape)}")
     if w_cal != 0 and (category_shape is None or target_shape is None):
@@ -1949,47 +1878,21 @@ def _check_rerank_args(ids_shape, scores_shape, count_shape, k, category_shape, 
     if target_shape is not None:
         if category_shape is None:
             raise ValueError("target needs category [N]")
-        if len(target_shape) != 2 or target_shape[0] != ids_shape[0] or not 1 <= target_shape[1] <= CAL_MAX_CATEGORIES:
-            raise ValueError(f"target must be [G, C] = [{ids_shape[0]}, 1 <= C <= {CAL_MAX_CATEGORIES}], got {tuple(target_shape)}")
+        _check_target_shape(target_shape, ids_shape[0])
 
 
-def rerank_select_host(ids, scores, count, sim, k: int, w_rel, w_div, w_cal, category=None, target=None, alpha=0.01,
-                       max_per_category: int = 0, news_num=None, return_robust: bool = False):
-    """The contract of ``digat_rerank_select`` in numpy — the yardstick of the kernel: ``mmr_select_host`` and
-    ``calibrated_select_host`` in one greedy pass.  ``ids`` / ``scores`` [G, M <= 1024], ``count`` [G] or None (M): position p is
-    an element when ``p < clip(count[g], 0, M)`` and ``0 <= id < N`` (``news_num``; None: ``len(category)``, or no upper bound);
-    ``sim`` [G, M, M] float32 as ``mmr_select_host`` takes it (None where ``w_div == 0``).  The weights are float32, finite and
-    >= 0, taken as given (``rerank_weights`` makes them from the public knob).
-
-    Step t, every operation a rounded float32 one: ``rel = w_rel * s`` (once); ``a = rel - (w_div * pen)`` if ``w_div != 0`` else
-    ``rel``; ``value = a + red`` if ``w_cal != 0`` else ``a`` with ``red = w_cal * gain32[c]`` for an element categorised in
-    [0, C) and 0 otherwise — ``calibrated_select_host``'s gains, float64 ``q_c`` and logarithms at the same ``alpha``.  The winner
-    is the eligible element with the largest ``topk_keys(value)``, ties to the lowest position; eligible: unpicked and, with
-    ``max_per_category`` q > 0, fewer than q picked elements of its raw ``category[id]``.  After a pick ``pen = fmax(pen,
-    sim[winner])`` (``w_div != 0``) and ``n_c += 1`` for a categorised winner.  Returns ``(scores [G,k] float32 — the INPUT score
-    bits —, ids [G,k] int64, count [G] int32, kl [G] float32)``; ``kl`` is ``calibrated_select_host``'s of the finished list, 0
-    without a target.
-
-    ``return_robust``: ``calibrated_select_host``'s certificate as a fifth array; the magnitude also takes ``|w_div * pen|`` and a
-    true tie also needs equal ``w_div * pen`` bits.  With ``w_cal == 0`` there is no logarithm and every list is robust."""
-    idv = np.asarray(ids, dtype=np.int64)
-    sc = np.ascontiguousarray(scores, dtype=np.float32)
-    cat = None if category is None else np.asarray(category, dtype=np.int64)
-    tgt = None if target is None else np.asarray(target, dtype=np.float32)
-    wr, wd, wc = _check_rerank_weights(w_rel, w_div, w_cal)
-    _check_rerank_args(idv.shape, sc.shape, None if count is None else np.shape(count), k, None if cat is None else cat.shape,
-                       None if tgt is None else tgt.shape, max_per_category, wc)
-    alpha = np.float64(_check_alpha(alpha))
+def _greedy_select_host(idv, sc, count, S, k, wr, wd, wc, form_div, form_cal, cat=None, tgt=None, alpha=0.01, q=0, N=None,
+                        want_robust=False):
+    """The one greedy pass behind ``mmr_select_host``, ``calibrated_select_host`` and ``rerank_select_host``, on checked and
+    converted arrays (``_host_lists``; ``S`` [G, M, M] float32 where ``form_div``; ``tgt`` [G, C] float32 or None) and float32
+    weights.  ``form_div`` / ``form_cal`` say whether the diversity / calibration term is FORMED: ``rerank_select_host`` forms a
+    term where its weight is not zero, the two reductions form their own term at every weight.  A cap ``q`` > 0 needs ``cat``;
+    ``N`` bounds the ids (None: no upper bound).  Returns ``(scores, ids, count, kl, robust)``; ``robust`` is the certificate
+    where ``want_robust`` and the calibration term is formed, all True otherwise."""
+    alpha = np.float64(alpha)
     oma = np.float64(1.0) - alpha
     G, M = idv.shape
-    S = None
-    if wd != 0:
-        S = np.asarray(sim, dtype=np.float32)
-        if S.shape != (G, M, M):
-            raise ValueError(f"sim must be [G, M, M] = {(G, M, M)}, got {S.shape}")
-    k, q = int(k), int(max_per_category)
     C = 0 if tgt is None else tgt.shape[1]
-    N = news_num if news_num is not None else (len(cat) if cat is not None else None)
     cnt = np.full(G, M, dtype=np.int64) if count is None else np.clip(np.asarray(count, dtype=np.int64), 0, M)
     out_s = np.full((G, k), -np.inf, dtype=np.float32)
     out_i = np.full((G, k), -1, dtype=np.int64)
@@ -2030,10 +1933,10 @@ def rerank_select_host(ids, scores, count, sim, k: int, w_rel, w_div, w_cal, cat
                 break
             with np.errstate(invalid="ignore", over="ignore"):
                 value = rel
-                if wd != 0:
+                if form_div:
                     dp = (wd * pen).astype(np.float32)
                     value = (rel - dp).astype(np.float32)
-                if wc != 0:
+                if form_cal:
                     T = np.float64(t + 1)
                     gain64 = np.zeros(C, dtype=np.float64)
                     nl = n[:C][live].astype(np.float64)
@@ -2043,7 +1946,7 @@ def rerank_select_host(ids, scores, count, sim, k: int, w_rel, w_div, w_cal, cat
                     value = (value + red).astype(np.float32)
             keys = np.where(ok, topk_keys(value).astype(np.int64), -1)
             j = int(np.argmax(keys))                                # the first (lowest position) of the largest key
-            if return_robust and robust[g] and wc != 0:
+            if want_robust and robust[g] and form_cal:
                 others = ok.copy()
                 others[j] = False
                 with np.errstate(invalid="ignore", over="ignore"):
@@ -2059,7 +1962,7 @@ def rerank_select_host(ids, scores, count, sim, k: int, w_rel, w_div, w_cal, cat
             chosen[j] = True
             out_s[g, t], out_i[g, t] = sc[g, j], idv[g, j]
             t_end = t + 1
-            if wd != 0:
+            if form_div:
                 pen = np.fmax(pen, S[g, j])
             if cated[j]:
                 n[cg[j]] += 1
@@ -2069,7 +1972,38 @@ def rerank_select_host(ids, scores, count, sim, k: int, w_rel, w_div, w_cal, cat
         if live.any():
             qq = (oma * n[:C][live].astype(np.float64)) / np.float64(max(t_end, 1)) + apl
             out_kl[g] = np.float32(np.sum(pl * (np.log(pl) - np.log(qq))))
-    return (out_s, out_i, out_c, out_kl, robust) if return_robust else (out_s, out_i, out_c, out_kl)
+    return out_s, out_i, out_c, out_kl, robust
+
+
+def rerank_select_host(ids, scores, count, sim, k: int, w_rel, w_div, w_cal, category=None, target=None, alpha=0.01,
+                       max_per_category: int = 0, news_num=None, return_robust: bool = False):
+    """The contract of ``digat_rerank_select`` in numpy — the yardstick of the kernel: ``mmr_select_host`` and
+    ``calibrated_select_host`` in one greedy pass.  ``ids`` / ``scores`` [G, M <= 1024], ``count`` [G] or None (M): position p is
+    an element when ``p < clip(count[g], 0, M)`` and ``0 <= id < N`` (``news_num``; None: ``len(category)``, or no upper bound);
+    ``sim`` [G, M, M] float32 as ``mmr_select_host`` takes it (None where ``w_div == 0``).  The weights are float32, finite and
+    >= 0, taken as given (``rerank_weights`` makes them from the public knob).
+
+    Step t, every operation a rounded float32 one: ``rel = w_rel * s`` (once); ``a = rel - (w_div * pen)`` if ``w_div != 0`` else
+    ``rel``; ``value = a + red`` if ``w_cal != 0`` else ``a`` with ``red = w_cal * gain32[c]`` for an element categorised in
+    [0, C) and 0 otherwise — ``calibrated_select_host``'s gains, float64 ``q_c`` and logarithms at the same ``alpha``.  The winner
+    is the eligible element with the largest ``topk_keys(value)``, ties to the lowest position; eligible: unpicked and, with
+    ``max_per_category`` q > 0, fewer than q picked elements of its raw ``category[id]``.  After a pick ``pen = fmax(pen,
+    sim[winner])`` (``w_div != 0``) and ``n_c += 1`` for a categorised winner.  Returns ``(scores [G,k] float32 — the INPUT score
+    bits —, ids [G,k] int64, count [G] int32, kl [G] float32)``; ``kl`` is ``calibrated_select_host``'s of the finished list, 0
+    without a target.
+
+    ``return_robust``: ``calibrated_select_host``'s certificate as a fifth array; the magnitude also takes ``|w_div * pen|`` and a
+    true tie also needs equal ``w_div * pen`` bits.  With ``w_cal == 0`` there is no logarithm and every list is robust."""
+    idv, sc, cat = _host_lists(ids, scores, category)
+    tgt = None if target is None else np.asarray(target, dtype=np.float32)
+    wr, wd, wc = _check_rerank_weights(w_rel, w_div, w_cal)
+    _check_rerank_args(idv.shape, sc.shape, _shape(count), k, _shape(cat), _shape(tgt), max_per_category, wc)
+    alpha = _check_alpha(alpha)
+    S = _host_sim(sim, *idv.shape) if wd != 0 else None
+    N = news_num if news_num is not None else (len(cat) if cat is not None else None)
+    out = _greedy_select_host(idv, sc, count, S, int(k), wr, wd, wc, bool(wd != 0), bool(wc != 0), cat=cat, tgt=tgt, alpha=alpha,
+                              q=int(max_per_category), N=N, want_robust=return_robust)
+    return out if return_robust else out[:4]
 
 
 def rerank_select(ids, scores, count, vectors, k: int, w_rel, w_div, w_cal, category=None, target=None, alpha=0.01,
@@ -2088,12 +2022,8 @@ def rerank_select(ids, scores, count, vectors, k: int, w_rel, w_div, w_cal, cate
     read back."""
     import torch
     from . import _lib
-    given = [t for t in (ids, scores, count, vectors, category, target) if t is not None]
-    dev = _lib.require_device(*given)
     wr, wd, wc = _check_rerank_weights(w_rel, w_div, w_cal)
-    _check_rerank_args(tuple(ids.shape), tuple(scores.shape), None if count is None else tuple(count.shape), k,
-                       None if category is None else tuple(category.shape), None if target is None else tuple(target.shape),
-                       max_per_category, wc)
+    _check_rerank_args(_shape(ids), _shape(scores), _shape(count), k, _shape(category), _shape(target), max_per_category, wc)
     alpha = _check_alpha(alpha)
     if wd != 0:
         if vectors is None or vectors.dim() != 2 or not 1 <= int(vectors.shape[1]) <= RERANK_MAX_D:
@@ -2105,32 +2035,25 @@ def rerank_select(ids, scores, count, vectors, k: int, w_rel, w_div, w_cal, cate
         raise ValueError(f"category must have one entry per row of vectors ({int(vectors.shape[0])}), got {int(category.shape[0])}")
     if vectors is None and category is None:
         raise ValueError("rerank_select needs vectors or category: the number of news N bounds the ids")
-    idt = ids.to(torch.int64).contiguous()
-    sc = _lib.f32(scores.detach())
-    ct = None if count is None else count.to(torch.int32).contiguous()
+    idt, sc, ct, outs, ws, need = _select_on_device(ids, scores, count, k, (vectors, category, target), True,
+                                                    lambda L, G, M, k: L.digat_rerank_select_workspace_bytes(G, M, k), "rerank")
     v = None if vectors is None or wd == 0 else _lib.f32(vectors.detach())
     cat = None if category is None else category.to(torch.int32).contiguous()
     tg = None if target is None else _lib.f32(target.detach())
+    if ws is None:
+        return outs
     N = int(vectors.shape[0]) if vectors is not None else int(category.shape[0])
-    G, M, k, q = int(idt.shape[0]), int(idt.shape[1]), int(k), int(max_per_category)
     C = 0 if tg is None else int(tg.shape[1])
-    out_s = torch.empty((G, k), dtype=torch.float32, device=dev)
-    out_i = torch.empty((G, k), dtype=torch.int64, device=dev)
-    out_c = torch.empty((G,), dtype=torch.int32, device=dev)
-    out_kl = torch.empty((G,), dtype=torch.float32, device=dev)
-    if G == 0:
-        return out_s, out_i, out_c, out_kl
-    L = _lib.lib()
-    need = int(L.digat_rerank_select_workspace_bytes(G, M, k))
-    ws = _lib.workspace(need, dev, "rerank")
     if N == 0:                                                      # empty tensors have no storage to point at; no id is an element
         v = None if v is None else ws
         cat = None if cat is None else ws
-    _lib.check(L.digat_rerank_select(idt.data_ptr(), sc.data_ptr(), _lib.ptr(ct), G, M, _lib.ptr(v), N, 0 if v is None else int(vectors.shape[1]),
-                                     _lib.ptr(cat), q, _lib.ptr(tg), C, float(wr), float(wd), float(wc), alpha, k, out_i.data_ptr(),
-                                     out_s.data_ptr(), out_c.data_ptr(), out_kl.data_ptr(), ws.data_ptr(), need, _lib.stream_ptr()),
+    out_s, out_i, out_c, out_kl = outs
+    _lib.check(_lib.lib().digat_rerank_select(idt.data_ptr(), sc.data_ptr(), _lib.ptr(ct), *idt.shape, _lib.ptr(v), N,
+                                              0 if v is None else int(vectors.shape[1]), _lib.ptr(cat), int(max_per_category), _lib.ptr(tg), C,
+                                              float(wr), float(wd), float(wc), alpha, int(k), out_i.data_ptr(), out_s.data_ptr(),
+                                              out_c.data_ptr(), out_kl.data_ptr(), ws.data_ptr(), need, _lib.stream_ptr()),
                "digat_rerank_select")
-    return out_s, out_i, out_c, out_kl
+    return outs
 
 
 def _check_share_args(history_shape, category_shape, C):

@@ -551,50 +551,26 @@ def recommend(model, dev, users, candidates=None, k=10, exclude_history=True, ba
     ``diversity`` uses) towards the category mix of the history or ``calibration_target``; ``shortlist``, ``category``,
     ``max_per_category`` and ``alpha`` compose.  ``util.recommend`` has the details; ``rerank`` does not combine with
     ``diversity``, ``calibration``, ``sample`` or ``index``."""
-    from . import evaluate, util
-    util.sample_refusals(sample, seed, streams, diversity=diversity, calibration=calibration, calibration_target=calibration_target,
-                         category=category, max_per_category=max_per_category, index=index, refine=refine, rerank=rerank)
-    util.rerank_refusals(rerank, diversity=diversity, calibration=calibration, index=index, refine=refine)
-    if rerank is not None:
-        select = lambda wide, long_lists: _retrieve(model, dev, users, candidates, wide, exclude_history, batch_size, long_lists)
-        plain = lambda: news_caches(model, dev.title_text, dev.title_mask, dev.augmented_title_text, dev.augmented_title_mask, 4 * batch_size)[0]
+    from . import util
 
-        def read():
-            hist, mask = _histories(dev, users)
-            return torch.where(mask != 0, hist, torch.zeros_like(hist))
-        return util.shortlist_then_rerank(select, plain, read, k, rerank, shortlist, category, max_per_category,
-                                          getattr(dev, "news_category", None), calibration_target, alpha)[1][:3]
-    if sample is not None:
-        select = lambda wide, long_lists: _retrieve(model, dev, users, candidates, wide, exclude_history, batch_size, long_lists)
-        ids, scores, n_out = util.shortlist_then_sample(select, k, sample, shortlist, seed,
-                                                        util.user_streams(users) if streams is None else streams)[1][:3]
-        return ids[:, 0].contiguous(), scores[:, 0].contiguous(), n_out
-    if index is None and refine is not None:
-        raise ValueError("refine belongs to an indexed call: name index (build_index)")
-    if calibration is not None and index is not None:
-        raise ValueError("calibration does not combine with index: its shortlist may exceed the 128 entries the re-score returns")
-    if calibration is not None:
-        if diversity is not None or max_per_category:
-            raise ValueError("calibration does not combine with diversity or max_per_category: name one of them")
-        select = lambda wide, long_lists: _retrieve(model, dev, users, candidates, wide, exclude_history, batch_size, long_lists)
+    def select(wide, long_lists):
+        if index is not None:
+            return _retrieve_indexed(model, dev, users, candidates, wide, exclude_history, batch_size, index, refine, True)
+        return _retrieve(model, dev, users, candidates, wide, exclude_history, batch_size, long_lists)
 
-        def history():
-            hist, mask = _histories(dev, users)
-            return torch.where(mask != 0, hist, torch.zeros_like(hist))
-        return util.shortlist_then_calibrate(select, history, k, calibration, shortlist, category, getattr(dev, "news_category", None),
-                                             calibration_target, alpha)[1][:3]
-    if calibration_target is not None:
-        raise ValueError("calibration_target belongs to a calibrated call: name calibration")
-    if diversity is not None:
-        select = lambda wide: recommend(model, dev, users, candidates, wide, exclude_history, batch_size, index=index, refine=refine)
-        plain = lambda: news_caches(model, dev.title_text, dev.title_mask, dev.augmented_title_text, dev.augmented_title_mask, 4 * batch_size)[0]
-        return util.shortlist_then_diversify(select, plain, k, (diversity,), shortlist, category, max_per_category,
-                                             getattr(dev, "news_category", None))[1][0]
-    if shortlist is not None or category is not None or max_per_category:
-        raise ValueError("shortlist, category and max_per_category belong to a diversified call: name diversity (0.0: the cap alone)")
-    if index is not None:
-        return _retrieve_indexed(model, dev, users, candidates, k, exclude_history, batch_size, index, refine, True)
-    return _retrieve(model, dev, users, candidates, k, exclude_history, batch_size, False)
+    def history():
+        hist, mask = _histories(dev, users)
+        return torch.where(mask != 0, hist, torch.zeros_like(hist))
+
+    def own_refusals():
+        if index is None and refine is not None:
+            raise ValueError("refine belongs to an indexed call: name index (build_index)")
+        if calibration is not None and index is not None:
+            raise ValueError("calibration does not combine with index: its shortlist may exceed the 128 entries the re-score returns")
+    plain = lambda: news_caches(model, dev.title_text, dev.title_mask, dev.augmented_title_text, dev.augmented_title_mask, 4 * batch_size)[0]
+    return util.recommend_dispatch(select, plain, history, k, getattr(dev, "news_category", None), util.user_streams(users), diversity,
+                                   shortlist, category, max_per_category, calibration, calibration_target, alpha, sample, seed, streams, rerank,
+                                   {"index": index, "refine": refine}, own_refusals)
 
 
 def _retrieve(model, dev, users, candidates, k, exclude_history, batch_size, long_lists):
@@ -740,7 +716,7 @@ def recommend_report(model, dev, users, candidates=None, k=10, diversities=(0.0,
     ``user_recall@k`` and ``mrr``.  The category figures go by ``category``, else ``dev.news_category`` where there is one."""
     from . import util
     N = int(dev.title_text.shape[0])
-    select = lambda wide: recommend(model, dev, users, candidates, wide, exclude_history, batch_size)
+    select = lambda wide, long_lists: _retrieve(model, dev, users, candidates, wide, exclude_history, batch_size, long_lists)
     plain = functools.lru_cache(maxsize=None)(
         lambda: news_caches(model, dev.title_text, dev.title_mask, dev.augmented_title_text, dev.augmented_title_mask, 4 * batch_size)[0])
     pool = np.arange(1, N, dtype=np.int64) if candidates is None else util.candidate_pool(candidates)

@@ -954,20 +954,78 @@ def unit_rows(table: torch.Tensor) -> torch.Tensor:
     return (t / torch.where(norm > 0, norm, torch.ones_like(norm))).contiguous()
 
 
+# ---- the greedy re-rank behind recommend(diversity= / calibration= / rerank=): one contract (evaluate.rerank_select_host), of which
+# maximal marginal relevance and calibration are the two named reductions; one limits check, one stage and one driver serve all three
+def _rerank_limits(k, shortlist, default_width, max_list) -> Tuple[int, int]:
+    """``(k, k')`` of a re-ranked ``recommend``: the plain selection runs at ``k' = shortlist or min(max_list, default_width k)``."""
+    if not 1 <= int(k) <= evaluate.TOPK_MAX_K:
+        raise ValueError(f"k must be in [1, {evaluate.TOPK_MAX_K}], got {k}")
+    k = int(k)
+    wide = min(max_list, default_width * k) if not shortlist else int(shortlist)
+    if not k <= wide <= max_list:
+        raise ValueError(f"shortlist must lie in [k, {max_list}] = [{k}, {max_list}], got {shortlist}")
+    return k, wide
+
+
+def _check_cap(max_per_category) -> None:
+    if int(max_per_category) < 0:
+        raise ValueError(f"max_per_category must be >= 0 (0: no cap), got {max_per_category}")
+
+
 def diversify_limits(k, diversity, shortlist, max_per_category) -> Tuple[int, int, float]:
     """``(k, k', lam)`` of a diversified ``recommend``: the plain selection runs at ``k' = shortlist or min(128, 4 k)``, and
     ``evaluate.mmr_select`` cuts its lists to k with ``lam = 1 - diversity``."""
-    if not 1 <= int(k) <= evaluate.TOPK_MAX_K:
-        raise ValueError(f"k must be in [1, {evaluate.TOPK_MAX_K}], got {k}")
+    k, wide = _rerank_limits(k, shortlist, 4, evaluate.MMR_MAX_LIST)
     if not 0.0 <= float(diversity) <= 1.0:
         raise ValueError(f"diversity must lie in [0, 1], got {diversity}")
-    if int(max_per_category) < 0:
-        raise ValueError(f"max_per_category must be >= 0 (0: no cap), got {max_per_category}")
-    k = int(k)
-    wide = min(evaluate.MMR_MAX_LIST, 4 * k) if not shortlist else int(shortlist)
-    if not k <= wide <= evaluate.MMR_MAX_LIST:
-        raise ValueError(f"shortlist must lie in [k, {evaluate.MMR_MAX_LIST}] = [{k}, {evaluate.MMR_MAX_LIST}], got {shortlist}")
+    _check_cap(max_per_category)
     return k, wide, 1.0 - float(diversity)
+
+
+def calibrate_limits(k, calibration, shortlist) -> Tuple[int, int, float]:
+    """``(k, k', lam)`` of a calibrated ``recommend``: the plain selection runs at ``k' = shortlist or min(1024, 8 k)``, and
+    ``calibrate`` cuts its lists to k with ``lam = 1 - calibration``."""
+    k, wide = _rerank_limits(k, shortlist, 8, evaluate.CAL_MAX_LIST)
+    if not 0.0 <= float(calibration) <= 1.0:
+        raise ValueError(f"calibration must lie in [0, 1], got {calibration}")
+    return k, wide, 1.0 - float(calibration)
+
+
+def rerank_limits(k, rerank, shortlist, max_per_category) -> Tuple[int, int, Tuple[float, float]]:
+    """``(k, k', (diversity, calibration))`` of a jointly re-ranked ``recommend``: the plain selection runs at ``k' = shortlist or
+    min(1024, 8 k)`` and ``rerank`` cuts its lists to k with ``evaluate.rerank_weights(diversity, calibration)``."""
+    k, wide = _rerank_limits(k, shortlist, 8, evaluate.RERANK_MAX_LIST)
+    try:
+        diversity, calibration = rerank
+    except (TypeError, ValueError):
+        raise ValueError(f"rerank must be a pair (diversity, calibration), got {rerank!r}") from None
+    evaluate.rerank_weights(diversity, calibration)
+    _check_cap(max_per_category)
+    return k, wide, (float(diversity), float(calibration))
+
+
+def _tensor_on(x, dev) -> torch.Tensor:
+    t = torch.as_tensor(np.asarray(x) if not torch.is_tensor(x) else x)
+    return t if dev is None else t.to(dev)
+
+
+def _rerank_stage(ids, scores, count, vectors, need_sim, category, target, on_device: Callable, on_host: Callable):
+    """The fork ``diversify``, ``calibrate`` and ``rerank`` share.  ``category`` and ``target`` go onto the lists' device; with
+    ``vectors`` a category array has one entry per row of them.  Device lists: ``on_device(category, target)``, an ``evaluate``
+    wrapper.  CPU lists: ``on_host(ids, scores, count, sim, category, target)`` on numpy arrays, a host contract, ``sim`` the Gram
+    of stock PyTorch (``evaluate.mmr_gram_stock``) where ``need_sim``.  Both return ``(scores, ids, count[, kl])``; the stage
+    returns ``recommend``'s order ``(news_ids, scores, count[, kl])`` as tensors."""
+    cat = None if category is None else _tensor_on(category, ids.device)
+    tgt = None if target is None else _tensor_on(target, ids.device).to(torch.float32)
+    if cat is not None and vectors is not None and (cat.dim() != 1 or int(cat.shape[0]) != int(vectors.shape[0])):
+        raise ValueError(f"category must be [{int(vectors.shape[0])}], one entry per news, got shape {tuple(cat.shape)}")
+    if ids.is_cuda:
+        s, i, *rest = on_device(cat, tgt)
+        return (i, s, *rest)
+    host = lambda t: None if t is None else t.numpy()
+    sim = evaluate.mmr_gram_stock(ids, vectors.detach().to(torch.float32)).numpy() if need_sim else None
+    s, i, *rest = on_host(host(ids), host(scores), host(count), sim, host(cat), host(tgt))
+    return tuple(torch.from_numpy(x) for x in (i, s, *rest))
 
 
 def diversify(ids: torch.Tensor, scores: torch.Tensor, count: torch.Tensor, vectors: torch.Tensor, k: int, lam: float, category=None,
@@ -976,65 +1034,14 @@ def diversify(ids: torch.Tensor, scores: torch.Tensor, count: torch.Tensor, vect
     to k by greedy maximal-marginal relevance over ``vectors`` [N, d] — ``evaluate.mmr_select`` on the device; on CPU tensors the
     Gram of stock PyTorch (``evaluate.mmr_gram_stock``) and ``evaluate.mmr_select_host``.  Returns ``recommend``'s triple
     ``(news_ids [G,k], scores [G,k], count [G])``."""
-    cat = None
-    if int(max_per_category) > 0:
-        if category is None:
-            raise ValueError("max_per_category needs category, one entry per news")
-        cat = torch.as_tensor(np.asarray(category) if not torch.is_tensor(category) else category).to(ids.device)
-        if cat.dim() != 1 or int(cat.shape[0]) != int(vectors.shape[0]):
-            raise ValueError(f"category must be [{int(vectors.shape[0])}], one entry per news, got shape {tuple(cat.shape)}")
-    if ids.is_cuda:
-        s, i, c = evaluate.mmr_select(ids, scores, count, vectors, k, lam, category=cat, max_per_category=max_per_category)
-        return i, s, c
-    sim = evaluate.mmr_gram_stock(ids, vectors.detach().to(torch.float32))
-    s, i, c = evaluate.mmr_select_host(ids.numpy(), scores.numpy(), count.numpy(), sim.numpy(), k, lam,
-                                       category=None if cat is None else cat.numpy(), max_per_category=max_per_category,
-                                       news_num=int(vectors.shape[0]))
-    return torch.from_numpy(i), torch.from_numpy(s), torch.from_numpy(c)
-
-
-def cap_category(category, max_per_category, corpus_category):
-    """The category array a cap of ``max_per_category`` goes by: ``category``, else the corpus's own; a cap without either is
-    refused.  Without a cap: ``category`` as given."""
-    if int(max_per_category) > 0 and category is None:
-        category = corpus_category
-    if int(max_per_category) > 0 and category is None:
-        raise ValueError("max_per_category needs category: this corpus carries no news_category")
-    return category
-
-
-def shortlist_then_diversify(select: Callable, vectors: Callable, k, diversities, shortlist=None, category=None, max_per_category: int = 0,
-                             corpus_category=None):
-    """The step behind ``recommend(diversity=)`` of either model, and behind ``recommend_report``: ``select(k')`` — the plain
-    selection, once, at ``diversify_limits``' width — then ``diversify`` over ``vectors()`` for every value of ``diversities`` on
-    that one shortlist, a cap going by ``cap_category(category, max_per_category, corpus_category)``.  Returns ``(shortlist triple,
-    [recommend's triple per diversity])``."""
-    limits = [diversify_limits(k, f, shortlist, max_per_category) for f in diversities]
-    if not limits:
-        raise ValueError("diversities must name at least one value")
-    category = cap_category(category, max_per_category, corpus_category)
-    short = select(limits[0][1])
-    vec = vectors()
-    return short, [diversify(*short, vec, kk, lam, category, max_per_category) for kk, _, lam in limits]
-
-
-def calibrate_limits(k, calibration, shortlist) -> Tuple[int, int, float]:
-    """``(k, k', lam)`` of a calibrated ``recommend``: the plain selection runs at ``k' = shortlist or min(1024, 8 k)``, and
-    ``calibrate`` cuts its lists to k with ``lam = 1 - calibration``."""
-    if not 1 <= int(k) <= evaluate.TOPK_MAX_K:
-        raise ValueError(f"k must be in [1, {evaluate.TOPK_MAX_K}], got {k}")
-    if not 0.0 <= float(calibration) <= 1.0:
-        raise ValueError(f"calibration must lie in [0, 1], got {calibration}")
-    k = int(k)
-    wide = min(evaluate.CAL_MAX_LIST, 8 * k) if not shortlist else int(shortlist)
-    if not k <= wide <= evaluate.CAL_MAX_LIST:
-        raise ValueError(f"shortlist must lie in [k, {evaluate.CAL_MAX_LIST}] = [{k}, {evaluate.CAL_MAX_LIST}], got {shortlist}")
-    return k, wide, 1.0 - float(calibration)
-
-
-def _tensor_on(x, dev) -> torch.Tensor:
-    t = torch.as_tensor(np.asarray(x) if not torch.is_tensor(x) else x)
-    return t if dev is None else t.to(dev)
+    q = int(max_per_category)
+    if q > 0 and category is None:
+        raise ValueError("max_per_category needs category, one entry per news")
+    return _rerank_stage(
+        ids, scores, count, vectors, True, category if q > 0 else None, None,
+        lambda cat, _: evaluate.mmr_select(ids, scores, count, vectors, k, lam, category=cat, max_per_category=max_per_category),
+        lambda i, s, c, sim, cat, _: evaluate.mmr_select_host(i, s, c, sim, k, lam, category=cat, max_per_category=max_per_category,
+                                                              news_num=int(vectors.shape[0])))
 
 
 def calibrate(ids: torch.Tensor, scores: torch.Tensor, count: torch.Tensor, category, target, k: int, lam: float, alpha: float = 0.01):
@@ -1044,14 +1051,28 @@ def calibrate(ids: torch.Tensor, scores: torch.Tensor, count: torch.Tensor, cate
     Returns ``recommend``'s triple and the divergence of every finished list: ``(news_ids [G,k], scores [G,k], count [G], kl [G])``."""
     if category is None:
         raise ValueError("calibrate needs category, one entry per news")
-    cat = _tensor_on(category, ids.device)
-    tgt = _tensor_on(target, ids.device).to(torch.float32)
-    if ids.is_cuda:
-        s, i, c, kl = evaluate.calibrated_select(ids, scores, count, cat, tgt, k, lam, alpha)
-        return i, s, c, kl
-    s, i, c, kl = evaluate.calibrated_select_host(ids.numpy(), scores.numpy(), None if count is None else count.numpy(), cat.numpy(),
-                                                  tgt.numpy(), k, lam, alpha)
-    return torch.from_numpy(i), torch.from_numpy(s), torch.from_numpy(c), torch.from_numpy(kl)
+    return _rerank_stage(ids, scores, count, None, False, category, target,
+                         lambda cat, tgt: evaluate.calibrated_select(ids, scores, count, cat, tgt, k, lam, alpha),
+                         lambda i, s, c, _, cat, tgt: evaluate.calibrated_select_host(i, s, c, cat, tgt, k, lam, alpha))
+
+
+def rerank(ids: torch.Tensor, scores: torch.Tensor, count: torch.Tensor, vectors: torch.Tensor, k: int, diversity: float, calibration: float,
+           category=None, target=None, alpha: float = 0.01, max_per_category: int = 0):
+    """The last stage of a jointly re-ranked ``recommend``: the lists ``(ids [G,M <= 1024], scores [G,M], count [G])`` of the plain
+    selection cut to k by ONE greedy pass that weighs an entry's score (``1 - diversity - calibration``) against its largest
+    similarity over ``vectors`` [N, d <= 512] to what is already picked (``diversity``) and against what it does for the KL
+    divergence between ``target`` [G, C <= 64] and the list's mix under ``category`` [N] (``calibration``), with at most
+    ``max_per_category`` picks of one category — ``evaluate.rerank_select`` on device tensors; on CPU tensors the Gram of stock
+    PyTorch (``evaluate.mmr_gram_stock``) and ``evaluate.rerank_select_host``, as ``diversify`` / ``calibrate`` do.  ``category``
+    is needed by a calibration weight, a target or a cap; ``target`` by a calibration weight.  Returns ``recommend``'s triple and
+    the divergence of every finished list (0 without a target): ``(news_ids [G,k], scores [G,k], count [G], kl [G])``."""
+    w = evaluate.rerank_weights(diversity, calibration)
+    rest = dict(alpha=alpha, max_per_category=max_per_category)
+    return _rerank_stage(
+        ids, scores, count, vectors, w[1] != 0, category, target,
+        lambda cat, tgt: evaluate.rerank_select(ids, scores, count, vectors, k, *w, category=cat, target=tgt, **rest),
+        lambda i, s, c, sim, cat, tgt: evaluate.rerank_select_host(i, s, c, sim, k, *w, category=cat, target=tgt, news_num=int(vectors.shape[0]),
+                                                                   **rest))
 
 
 def calibration_kl(ids: torch.Tensor, count, category, target, alpha: float = 0.01) -> torch.Tensor:
@@ -1062,6 +1083,16 @@ def calibration_kl(ids: torch.Tensor, count, category, target, alpha: float = 0.
     if not 1 <= M <= evaluate.TOPK_MAX_K:
         raise ValueError(f"ids must be [G, M] with 1 <= M <= {evaluate.TOPK_MAX_K}, got {tuple(ids.shape)}")
     return calibrate(ids, torch.zeros(tuple(ids.shape), dtype=torch.float32, device=ids.device), count, category, target, M, 1.0, alpha)[3]
+
+
+def cap_category(category, max_per_category, corpus_category):
+    """The category array a cap of ``max_per_category`` goes by: ``category``, else the corpus's own; a cap without either is
+    refused.  Without a cap: ``category`` as given."""
+    if int(max_per_category) > 0 and category is None:
+        category = corpus_category
+    if int(max_per_category) > 0 and category is None:
+        raise ValueError("max_per_category needs category: this corpus carries no news_category")
+    return category
 
 
 def calibration_category(category, corpus_category) -> Tuple[torch.Tensor, int]:
@@ -1079,6 +1110,47 @@ def calibration_category(category, corpus_category) -> Tuple[torch.Tensor, int]:
     return cat, C
 
 
+def _shortlist_then(select: Callable, wide, cut: Callable, category, max_per_category, corpus_category, wants_target: bool = False,
+                    history: Optional[Callable] = None, calibration_target=None):
+    """The driver behind the three ``shortlist_then_*``, the limits checked by its caller.  The category array: with
+    ``wants_target`` ``calibration_category``'s, else with a cap ``cap_category``'s, else none — a refusal happens before anything is
+    scored.  Then ``select(wide, long_lists)``, ``long_lists`` when ``wide > 128`` (never for the diversity path: its lists stop at
+    128).  Then the target where one is wanted: ``calibration_target`` [G, C], or ``evaluate.category_share`` of ``history()``.
+    Returns ``(shortlist triple, cut(shortlist triple, category, target))``."""
+    cat, C = None, 0
+    if wants_target:
+        cat, C = calibration_category(category, corpus_category)
+    elif int(max_per_category) > 0:
+        cat = _tensor_on(cap_category(category, max_per_category, corpus_category), None).to(torch.int32)
+    short = select(wide, wide > evaluate.TOPK_MAX_K)
+    dev = short[0].device
+    cat = None if cat is None else cat.to(dev)
+    target = None
+    if wants_target and calibration_target is None:
+        target = evaluate.category_share(history().to(dev), cat, C)
+    elif wants_target:
+        target = _tensor_on(calibration_target, dev).to(torch.float32)
+        if target.dim() != 2 or int(target.shape[0]) != int(short[0].shape[0]):
+            raise ValueError(f"calibration_target must be [users = {int(short[0].shape[0])}, C], got {tuple(target.shape)}")
+    return short, cut(short, cat, target)
+
+
+def shortlist_then_diversify(select: Callable, vectors: Callable, k, diversities, shortlist=None, category=None, max_per_category: int = 0,
+                             corpus_category=None):
+    """The step behind ``recommend(diversity=)`` of either model, and behind ``recommend_report``: ``select(k', False)`` — the plain
+    selection, once, at ``diversify_limits``' width — then ``diversify`` over ``vectors()`` for every value of ``diversities`` on
+    that one shortlist, a cap going by ``cap_category(category, max_per_category, corpus_category)``.  Returns ``(shortlist triple,
+    [recommend's triple per diversity])``."""
+    limits = [diversify_limits(k, f, shortlist, max_per_category) for f in diversities]
+    if not limits:
+        raise ValueError("diversities must name at least one value")
+
+    def cut(short, cat, _):
+        vec = vectors()
+        return [diversify(*short, vec, kk, lam, cat, max_per_category) for kk, _, lam in limits]
+    return _shortlist_then(select, limits[0][1], cut, category, max_per_category, corpus_category)
+
+
 def shortlist_then_calibrate(select: Callable, history: Callable, k, calibration, shortlist=None, category=None, corpus_category=None,
                              calibration_target=None, alpha: float = 0.01):
     """The step behind ``recommend(calibration=)`` of either model: ``select(k', long_lists)`` — the plain selection at
@@ -1087,61 +1159,8 @@ def shortlist_then_calibrate(select: Callable, history: Callable, k, calibration
     ``(shortlist triple, (news_ids, scores, count, kl))``."""
     k, wide, lam = calibrate_limits(k, calibration, shortlist)
     evaluate._check_alpha(alpha)
-    cat, C = calibration_category(category, corpus_category)        # refused before anything is scored
-    short = select(wide, wide > evaluate.TOPK_MAX_K)
-    cat = cat.to(short[0].device)
-    if calibration_target is None:
-        target = evaluate.category_share(history().to(short[0].device), cat, C)
-    else:
-        target = _tensor_on(calibration_target, short[0].device).to(torch.float32)
-        if target.dim() != 2 or int(target.shape[0]) != int(short[0].shape[0]):
-            raise ValueError(f"calibration_target must be [users = {int(short[0].shape[0])}, C], got {tuple(target.shape)}")
-    return short, calibrate(*short, cat, target, k, lam, alpha)
-
-
-def rerank_limits(k, rerank, shortlist, max_per_category) -> Tuple[int, int, Tuple[float, float]]:
-    """``(k, k', (diversity, calibration))`` of a jointly re-ranked ``recommend``: the plain selection runs at ``k' = shortlist or
-    min(1024, 8 k)`` and ``rerank`` cuts its lists to k with ``evaluate.rerank_weights(diversity, calibration)``."""
-    if not 1 <= int(k) <= evaluate.TOPK_MAX_K:
-        raise ValueError(f"k must be in [1, {evaluate.TOPK_MAX_K}], got {k}")
-    try:
-        diversity, calibration = rerank
-    except (TypeError, ValueError):
-        raise ValueError(f"rerank must be a pair (diversity, calibration), got {rerank!r}") from None
-    evaluate.rerank_weights(diversity, calibration)
-    if int(max_per_category) < 0:
-        raise ValueError(f"max_per_category must be >= 0 (0: no cap), got {max_per_category}")
-    k = int(k)
-    wide = min(evaluate.RERANK_MAX_LIST, 8 * k) if not shortlist else int(shortlist)
-    if not k <= wide <= evaluate.RERANK_MAX_LIST:
-        raise ValueError(f"shortlist must lie in [k, {evaluate.RERANK_MAX_LIST}] = [{k}, {evaluate.RERANK_MAX_LIST}], got {shortlist}")
-    return k, wide, (float(diversity), float(calibration))
-
-
-def rerank(ids: torch.Tensor, scores: torch.Tensor, count: torch.Tensor, vectors: torch.Tensor, k: int, diversity: float, calibration: float,
-           category=None, target=None, alpha: float = 0.01, max_per_category: int = 0):
-    """The last stage of a jointly re-ranked ``recommend``: the lists ``(ids [G,M <= 1024], scores [G,M], count [G])`` of the plain
-    selection cut to k by ONE greedy pass that weighs an entry's score (``1 - diversity - calibration``) against its largest
-    similarity over ``vectors`` [N, d <= 512] to what is already picked (``diversity``) and against what it does for the KL
-    divergence between ``target`` [G, C <= 64] and the list's mix under ``category`` [N] (``calibration``), with at most
-    ``max_per_category`` picks of one category — ``evaluate.rerank_select`` on device tensors; on CPU tensors the Gram of stock
-    PyTorch (``evaluate.mmr_gram_stock``) and ``evaluate.rerank_select_host``, as ``diversify`` / ``calibrate`` do.  ``category``
-    is needed by a calibration weight, a target or a cap; ``target`` by a calibration weight.  Returns ``recommend``'s triple and
-    the divergence of every finished list (0 without a target): ``(news_ids [G,k], scores [G,k], count [G], kl [G])``."""
-    wr, wd, wc = evaluate.rerank_weights(diversity, calibration)
-    cat = None if category is None else _tensor_on(category, ids.device)
-    tgt = None if target is None else _tensor_on(target, ids.device).to(torch.float32)
-    if cat is not None and (cat.dim() != 1 or int(cat.shape[0]) != int(vectors.shape[0])):
-        raise ValueError(f"category must be [{int(vectors.shape[0])}], one entry per news, got shape {tuple(cat.shape)}")
-    if ids.is_cuda:
-        s, i, c, kl = evaluate.rerank_select(ids, scores, count, vectors, k, wr, wd, wc, category=cat, target=tgt, alpha=alpha,
-                                             max_per_category=max_per_category)
-        return i, s, c, kl
-    sim = evaluate.mmr_gram_stock(ids, vectors.detach().to(torch.float32)).numpy() if wd != 0 else None
-    s, i, c, kl = evaluate.rerank_select_host(ids.numpy(), scores.numpy(), None if count is None else count.numpy(), sim, k, wr, wd, wc,
-                                              category=None if cat is None else cat.numpy(), target=None if tgt is None else tgt.numpy(),
-                                              alpha=alpha, max_per_category=max_per_category, news_num=int(vectors.shape[0]))
-    return torch.from_numpy(i), torch.from_numpy(s), torch.from_numpy(c), torch.from_numpy(kl)
+    return _shortlist_then(select, wide, lambda short, cat, target: calibrate(*short, cat, target, k, lam, alpha), category, 0,
+                           corpus_category, True, history, calibration_target)
 
 
 def rerank_refusals(rerank, **others) -> None:
@@ -1163,23 +1182,11 @@ def shortlist_then_rerank(select: Callable, vectors: Callable, history: Callable
     needed by a cap alone (``cap_category``).  Returns ``(shortlist triple, (news_ids, scores, count, kl))``."""
     k, wide, (diversity, calibration) = rerank_limits(k, rerank_knob, shortlist, max_per_category)
     evaluate._check_alpha(alpha)
-    wanted = calibration != 0.0 or calibration_target is not None
-    cat, C = None, 0
-    if wanted:
-        cat, C = calibration_category(category, corpus_category)   # refused before anything is scored
-    elif int(max_per_category) > 0:
-        cat = _tensor_on(cap_category(category, max_per_category, corpus_category), None).to(torch.int32)
-    short = select(wide, wide > evaluate.TOPK_MAX_K)
-    dev = short[0].device
-    cat = None if cat is None else cat.to(dev)
-    target = None
-    if wanted and calibration_target is None:
-        target = evaluate.category_share(history().to(dev), cat, C)
-    elif wanted:
-        target = _tensor_on(calibration_target, dev).to(torch.float32)
-        if target.dim() != 2 or int(target.shape[0]) != int(short[0].shape[0]):
-            raise ValueError(f"calibration_target must be [users = {int(short[0].shape[0])}, C], got {tuple(target.shape)}")
-    return short, rerank(*short, vectors(), k, diversity, calibration, cat, target, alpha, max_per_category)
+    cut = lambda short, cat, target: rerank(*short, vectors(), k, diversity, calibration, cat, target, alpha, max_per_category)
+    return _shortlist_then(select, wide, cut, category, max_per_category, corpus_category,
+                           calibration != 0.0 or calibration_target is not None, history, calibration_target)
+
+
 
 
 def sample_limits(k, sample, shortlist) -> Tuple[int, int, float]:
@@ -1376,7 +1383,7 @@ def recommend_report(model, dc: DeviceCorpus, users, candidates, k: int, diversi
     ``overlap`` with the plain top-k, ``coverage`` / ``gini`` of the exposure over the candidate pool (the shared pool, or the
     distinct ids of per-user lists) and ``lists``; with ``targets = (target_ids, target_start)`` also ``recall@k``,
     ``user_recall@k`` and ``mrr``.  ``return_lists``: ``(rows, [(news_ids, scores, count) per diversity])``."""
-    select = lambda wide: recommend(model, dc, users, candidates, wide, exclude_history, batch_size, max_rows)
+    select = lambda wide, long_lists: recommend_lists(model, dc, users, candidates, wide, exclude_history, batch_size, max_rows, long_lists)
     unit = functools.lru_cache(maxsize=None)(lambda: unit_rows(dc.news_embedding))     # behind select: a text encoder's table is fresh then
     return quality_report(select, unit, unit, k, diversities, shortlist, category, max_per_category, dc.news_category,
                           candidate_pool(candidates), targets, return_lists)
@@ -1430,32 +1437,43 @@ def recommend(model, dc: DeviceCorpus, users, candidates, k: int, exclude_histor
     calibration picks from the deep pool.  Both weights lie in [0, 1], their sum at most 1.  ``shortlist``, ``category``,
     ``max_per_category``, ``calibration_target`` and ``alpha`` mean what they mean above; ``rerank=(d, 0)`` is maximal marginal
     relevance over up to 1024 entries.  ``rerank`` does not combine with ``diversity``, ``calibration`` or ``sample``."""
+    select = lambda wide, long_lists: recommend_lists(model, dc, users, candidates, wide, exclude_history, batch_size, max_rows, long_lists)
+    return recommend_dispatch(select, lambda: unit_rows(dc.news_embedding), lambda: recommend_users(dc, users)[0], k,
+                              getattr(dc, "news_category", None), user_streams(users), diversity, shortlist, category, max_per_category, calibration, calibration_target, alpha,
+                              sample, seed, streams, rerank)
+
+
+def recommend_dispatch(select: Callable, vectors: Callable, history: Callable, k, corpus_category, streams_default, diversity=None,
+                       shortlist=None, category=None, max_per_category=0, calibration=None, calibration_target=None, alpha=0.01, sample=None,
+                       seed=0, streams=None, rerank=None, own_knobs=None, own_refusals: Optional[Callable] = None):
+    """The ladder behind ``recommend`` of either model — which knob runs which step, and every refusal, before anything is scored.
+    ``select(k', long_lists)`` is the model's plain selection (the call without a knob is ``select(k, False)``), ``vectors()`` the
+    rows a diversity term measures, ``history()`` the users' histories [G, H] padded with 0; the knobs are ``recommend``'s.
+    ``own_knobs`` names the caller's further knobs that neither ``sample`` nor ``rerank`` combines with (``nrms``: index, refine),
+    ``own_refusals()`` raises what else the caller refuses, behind those two.  Returns ``recommend``'s triple."""
+    own_knobs = own_knobs or {}
     sample_refusals(sample, seed, streams, diversity=diversity, calibration=calibration, calibration_target=calibration_target,
-                    category=category, max_per_category=max_per_category, rerank=rerank)
-    rerank_refusals(rerank, diversity=diversity, calibration=calibration)
+                    category=category, max_per_category=max_per_category, **own_knobs, rerank=rerank)
+    rerank_refusals(rerank, diversity=diversity, calibration=calibration, **own_knobs)
+    if own_refusals is not None:
+        own_refusals()
     if rerank is not None:
-        plain = lambda wide, long_lists: recommend_lists(model, dc, users, candidates, wide, exclude_history, batch_size, max_rows, long_lists)
-        return shortlist_then_rerank(plain, lambda: unit_rows(dc.news_embedding), lambda: recommend_users(dc, users)[0], k, rerank, shortlist,
-                                     category, max_per_category, dc.news_category, calibration_target, alpha)[1][:3]
+        return shortlist_then_rerank(select, vectors, history, k, rerank, shortlist, category, max_per_category, corpus_category,
+                                     calibration_target, alpha)[1][:3]
     if sample is not None:
-        plain = lambda wide, long_lists: recommend_lists(model, dc, users, candidates, wide, exclude_history, batch_size, max_rows, long_lists)
-        ids, scores, n_out = shortlist_then_sample(plain, k, sample, shortlist, seed, user_streams(users) if streams is None else streams)[1][:3]
+        ids, scores, n_out = shortlist_then_sample(select, k, sample, shortlist, seed, streams_default if streams is None else streams)[1][:3]
         return ids[:, 0].contiguous(), scores[:, 0].contiguous(), n_out
     if calibration is not None:
         if diversity is not None or max_per_category:
             raise ValueError("calibration does not combine with diversity or max_per_category: name one of them")
-        plain = lambda wide, long_lists: recommend_lists(model, dc, users, candidates, wide, exclude_history, batch_size, max_rows, long_lists)
-        return shortlist_then_calibrate(plain, lambda: recommend_users(dc, users)[0], k, calibration, shortlist, category, dc.news_category,
-                                        calibration_target, alpha)[1][:3]
+        return shortlist_then_calibrate(select, history, k, calibration, shortlist, category, corpus_category, calibration_target, alpha)[1][:3]
     if calibration_target is not None:
         raise ValueError("calibration_target belongs to a calibrated call: name calibration")
     if diversity is not None:
-        select = lambda wide: recommend(model, dc, users, candidates, wide, exclude_history, batch_size, max_rows)
-        return shortlist_then_diversify(select, lambda: unit_rows(dc.news_embedding), k, (diversity,), shortlist, category, max_per_category,
-                                        dc.news_category)[1][0]
+        return shortlist_then_diversify(select, vectors, k, (diversity,), shortlist, category, max_per_category, corpus_category)[1][0]
     if shortlist is not None or category is not None or max_per_category:
         raise ValueError("shortlist, category and max_per_category belong to a diversified call: name diversity (0.0: the cap alone)")
-    return recommend_lists(model, dc, users, candidates, k, exclude_history, batch_size, max_rows, False)
+    return select(k, False)
 
 
 def recommend_lists(model, dc: DeviceCorpus, users, candidates, k: int, exclude_history: bool = True, batch_size: int = 1024,

@@ -285,3 +285,17 @@ def test_config_parses_the_diversity_flags():
         main.recommend_category(types.SimpleNamespace(news_category=None), 2)
     with pytest.raises(ValueError, match="carries none"):
         main.recommend_category(types.SimpleNamespace(), 1)
+
+
+def test_lam_one_still_forms_the_diversity_term_where_the_joint_contract_does_not():
+    """The two contracts are one greedy pass, but not the same call: ``mmr_select_host`` forms ``rel - fl(mu * pen)`` at every
+    ``lam`` (as ``digat_mmr_select`` does), ``rerank_select_host`` forms no term whose weight is zero.  After position 0 is
+    picked, position 1's MMR value is ``2 - 0 * inf`` = NaN (key 1), below position 2's."""
+    from digat_amd import evaluate
+    ids, scores = np.array([[0, 1, 2]]), np.array([[3.0, 2.0, 1.0]], dtype=np.float32)
+    sim = np.zeros((1, 3, 3), dtype=np.float32)
+    sim[0, 0, 1] = sim[0, 1, 0] = np.inf
+    _, got, count = evaluate.mmr_select_host(ids, scores, None, sim, 3, 1.0)
+    assert got.tolist() == [[0, 2, 1]] and count.tolist() == [3]
+    _, got, count, _ = evaluate.rerank_select_host(ids, scores, None, sim, 3, 1.0, 0.0, 0.0, news_num=3)
+    assert got.tolist() == [[0, 1, 2]] and count.tolist() == [3]

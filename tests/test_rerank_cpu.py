@@ -360,3 +360,74 @@ def test_recommend_lines_passes_the_pair_through(monkeypatch):
                                    max_per_category=2)
     assert lines == ['%d [%s]' % (g + 1, ','.join(str(int(v)) for v in ids[g, :count[g]])) for g in range(6)]
     assert lines != main.recommend_lines(model, dc, 5, 64)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# one contract, one ladder
+# ---------------------------------------------------------------------------------------------------------------------
+def test_the_three_host_contracts_reach_one_core(monkeypatch):
+    from digat_amd import evaluate
+    seen = []
+
+    def recorder(idv, sc, count, S, k, wr, wd, wc, form_div, form_cal, **rest):
+        seen.append((form_div, form_cal))
+        G = idv.shape[0]
+        return (np.zeros((G, k), np.float32), np.zeros((G, k), np.int64), np.zeros(G, np.int32), np.zeros(G, np.float32), np.ones(G, bool))
+    monkeypatch.setattr(evaluate, "_greedy_select_host", recorder)
+    ids, scores = np.arange(6).reshape(2, 3), np.ones((2, 3), dtype=np.float32)
+    sim, category, target = np.zeros((2, 3, 3), dtype=np.float32), np.arange(6) % 2, np.full((2, 2), 0.5, dtype=np.float32)
+    for lam in (0.3, 1.0):                                       # lam = 1: a zero weight, the term is formed all the same
+        assert len(evaluate.mmr_select_host(ids, scores, None, sim, 2, lam)) == 3
+        assert seen == [(True, False)]
+        seen.clear()
+        assert len(evaluate.calibrated_select_host(ids, scores, None, category, target, 2, lam)) == 4
+        assert len(evaluate.calibrated_select_host(ids, scores, None, category, target, 2, lam, return_robust=True)) == 5
+        assert seen == [(False, True)] * 2
+        seen.clear()
+    for w_div, w_cal in ((0.3, 0.2), (0.0, 0.2), (0.3, 0.0), (0.0, 0.0)):
+        evaluate.rerank_select_host(ids, scores, None, sim, 2, 0.5, w_div, w_cal, category=category, target=target)
+        assert seen == [(w_div != 0, w_cal != 0)]
+        seen.clear()
+
+
+RERANK_KNOBS = dict(diversity=0.3, calibration=0.3, sample=1.0, rerank=(0.2, 0.4))
+
+
+@pytest.mark.parametrize("which", ("util", "nrms"))
+def test_the_refusal_table_holds_before_anything_is_scored(which, monkeypatch):
+    """Every pair of knobs that does not combine, and every argument given without its knob, is refused — with the text the ladder
+    has always used — before the model's selection is called."""
+    import itertools
+    from digat_amd import nrms, util
+
+    def never(*args, **kwargs):
+        raise AssertionError("scored before the refusal")
+    if which == "util":
+        monkeypatch.setattr(util, "recommend_lists", never)
+        dc = host_corpus()
+        call = lambda **kw: util.recommend(types.SimpleNamespace(), dc, np.arange(5), np.arange(1, 300), 5, **kw)
+        knobs, users, news = dict(RERANK_KNOBS), 5, 300
+        alone = {}
+    else:
+        monkeypatch.setattr(nrms, "_retrieve", never)
+        monkeypatch.setattr(nrms, "_retrieve_indexed", never)
+        m, dev = D.model("nrms"), D.dev_set()
+        call = lambda **kw: nrms.recommend(m, dev, np.arange(D.USERS), k=4, **kw)
+        knobs, users, news = dict(RERANK_KNOBS, index=object()), D.USERS, D.NEWS
+        alone = {"refine": (64, "belongs to an indexed call")}
+    for a, b in itertools.combinations(knobs, 2):
+        if {a, b} == {"diversity", "index"}:
+            continue                                             # the one pair that composes: checked below
+        with pytest.raises(ValueError, match="does not combine"):
+            call(**{a: knobs[a], b: knobs[b]})
+    alone.update(calibration_target=(np.full((users, 4), 0.25, dtype=np.float32), "belongs to a calibrated call"),
+                 shortlist=(20, "belong to a diversified call"), category=(np.zeros(news, dtype=np.int64), "belong to a diversified call"),
+                 max_per_category=(1, "belong to a diversified call"))
+    for name, (value, text) in alone.items():
+        with pytest.raises(ValueError, match=text):
+            call(**{name: value})
+    with pytest.raises(AssertionError, match="scored"):          # the fake is live: a call that is not refused reaches it
+        call(diversity=0.3)
+    if which == "nrms":
+        with pytest.raises(AssertionError, match="scored"):      # diversity composes with index: its shortlist is the indexed call's
+            call(diversity=0.3, index=knobs["index"])
