@@ -290,6 +290,9 @@ _SIGNATURES = {
     "digat_profile_xattn_parts": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "digat_split_ctx_fused_bytes": (C.c_size_t, [C.c_int]),
     "digat_split_ctx_fused_weights": (C.c_int, [_f, C.c_int, _f, _f]),
+    "digat_pool_fwd": (C.c_int, [_f, C.c_int64] + [_f] * 4 + [C.c_int] * 3 + [_f]),
+    "digat_topic_pool_lists_fwd": (C.c_int, [_f, C.c_int64] + [_f] * 4 + [C.c_int, _f, _f] + [C.c_int] * 4 + [_f]),
+    "digat_user_ctx_fused_fwd": (C.c_int, [_f, C.c_int64, _f, _f, C.c_int] + [_f] * 10 + [C.c_int] * 4 + [_f]),
 }
 KERNEL_KINDS = ("proj", "linear", "xattn", "pool", "topic", "glue", "agg")
 XATTN_PARTS = ("twin", "l0", "news", "other")      # digat_profile_xattn_parts: the Eq. 8 launches by kernel

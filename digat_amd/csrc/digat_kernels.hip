@@ -707,6 +707,35 @@ int digat_user_ctx_fwd(const float* Xu, const uint8_t* cat_mask, const int64_t* 
                         (hipStream_t)stream);
 }
 
+// ---- the inference launchers of the context stage alone (tests/test_hip_ctx_fp64.py): arguments checked, then forwarded one for one ----
+int digat_pool_fwd(const float* feat, int64_t ld_b, const float* kq, const uint8_t* mask, const float* addend, float* out,
+                   int B, int n, int d, void* stream) {
+    if (!feat || !kq || !mask || !out || B < 0 || n <= 0 || d <= 0) return DIGAT_ERR_ARG;
+    if (ld_b % 4) return DIGAT_ERR_SHAPE;
+    return launch_pool(feat, (long)ld_b, kq, mask, addend, out, B, n, d, (hipStream_t)stream);
+}
+
+int digat_topic_pool_lists_fwd(const float* Xu, int64_t ld_b, const float* kq, const int64_t* cat_idx, const int32_t* row_group,
+                               const uint8_t* live, int live_ld, const int32_t* hlast, float* out,
+                               int B, int H, int C1, int d, void* stream) {
+    if (!Xu || !kq || !cat_idx || !out || B < 0 || H < 0 || C1 <= 0 || d <= 0) return DIGAT_ERR_ARG;
+    if ((hlast && !live) || (live && live_ld < H)) return DIGAT_ERR_ARG;       // the kernels ignore hlast without live
+    if (ld_b % 4) return DIGAT_ERR_SHAPE;
+    return launch_topic(Xu, (long)ld_b, kq, cat_idx, out, B, H, C1, d, (hipStream_t)stream, row_group, live, live_ld, hlast);
+}
+
+int digat_user_ctx_fused_fwd(const float* Xu, int64_t ld_b, const int32_t* row_group, const uint8_t* live, int live_ld,
+                             const int32_t* hlast, const float* kq_topic, const float* kq_user, const int64_t* cat_idx,
+                             const uint8_t* cat_mask, const float* addend, float* out, const void* image, const float* bFa,
+                             uint32_t* range_flag, int B, int H, int C1, int d, void* stream) {
+    if (!Xu || !kq_topic || !kq_user || !cat_idx || !cat_mask || !out || !image || !bFa) return DIGAT_ERR_ARG;
+    if (B < 0 || H < 0 || C1 <= 0 || d <= 0 || (hlast && !live) || (live && live_ld < H)) return DIGAT_ERR_ARG;
+    if (!ctxfused_ok(H, C1, d) || ld_b % 4) return DIGAT_ERR_SHAPE;
+    const CtxFusedArgs g{Xu, (long)ld_b, row_group, live, live_ld, hlast, kq_topic, kq_user, cat_idx, cat_mask, addend, out,
+                         (const uint4*)image, bFa, range_flag, B, H, C1, d, sqrtf((float)d)};
+    return launch_user_ctx_fused(g, (hipStream_t)stream);
+}
+
 // the initial user context alone: F x = ue Fa^T + user_ctx0_kernel (digat_ctx0.inc), the encoder's first context launch for launch
 int digat_user_ctx0_fwd(const float* ue, const int32_t* row_group, int G, const float* kq_topic, const float* kq_user,
                         const uint8_t* cat_mask, const int64_t* cat_idx, const float* Fa, const float* bFa,

@@ -195,6 +195,34 @@ int digat_user_nodes_build(const float* ue, const float* topic, const int32_t* r
 int digat_topic_pool_fwd(const float* Xu, const float* kq, const int64_t* cat_idx, float* out,
                          int B, int U, int H, int C1, int d, void* stream);
 
+/* The inference launchers of the context stage alone, for tests that hold one kernel at a time to a reference: arguments are
+ * checked and forwarded one for one.  No workspace, no allocation, no host synchronisation; B == 0 returns without a launch.
+ *
+ * digat_pool_fwd: ScaledDotProductAttention pooling on a folded query (layers.py:199-206 with (K x).q = x.(K^T q)) through the
+ * dispatch inference takes — the register-resident kernels up to n = 68, d = 512, the two-pass kernel beyond (digat_attn_pool_fwd
+ * always runs the latter).  feat: row b's n nodes at feat + b ld_b, d floats apart (ld_b % 4 == 0); kq [B,d]; mask [B,n] bytes;
+ * addend NULL or [B,d]; out [B,d].  A masked node weighs exactly 0 and its row is not read into any sum, unless every node of the
+ * row is masked (uniform weights).  n <= DIGAT_MAX_NODES, d % 4 == 0 (DIGAT_ERR_SHAPE).
+ *
+ * digat_topic_pool_lists_fwd: digat_topic_pool_fwd with what only the encoder passes.  Xu: row b's H history rows at
+ * Xu + (row_group ? row_group[b] : b) ld_b; row_group NULL or [B] int32; live NULL or [B, live_ld] bytes (live_ld >= H): history
+ * row t with live[b live_ld + t] == 0 is taken as a zero row, whatever bits it holds; hlast NULL or [B] int32, with live only
+ * (DIGAT_ERR_ARG otherwise): every history row t >= hlast[b] is dead and is not requested.  cat_idx [B,H] per row; out [B,C1,d].
+ *
+ * digat_user_ctx_fused_fwd: compute_user_graph_context as the one launch of the folded inference path (digat_params.
+ * featureAffine_fsplit), from the two folded queries kq_topic, kq_user [B,d].  image: digat_split_ctx_fused_weights(Fa, d, ...);
+ * bFa [d]; cat_mask [B,C1]; range_flag NULL or one device word (see digat_params.range_flag); the rest as above.
+ * DIGAT_ERR_SHAPE outside 1 <= H <= 52, C1 <= 20, 192 < d <= 448, d % 8 == 0. */
+int digat_pool_fwd(const float* feat, int64_t ld_b, const float* kq, const uint8_t* mask, const float* addend, float* out,
+                   int B, int n, int d, void* stream);
+int digat_topic_pool_lists_fwd(const float* Xu, int64_t ld_b, const float* kq, const int64_t* cat_idx, const int32_t* row_group,
+                               const uint8_t* live, int live_ld, const int32_t* hlast, float* out,
+                               int B, int H, int C1, int d, void* stream);
+int digat_user_ctx_fused_fwd(const float* Xu, int64_t ld_b, const int32_t* row_group, const uint8_t* live, int live_ld,
+                             const int32_t* hlast, const float* kq_topic, const float* kq_user, const int64_t* cat_idx,
+                             const uint8_t* cat_mask, const float* addend, float* out, const void* image, const float* bFa,
+                             uint32_t* range_flag, int B, int H, int C1, int d, void* stream);
+
 /* ---- a5: DIGAT.forward / DIGAT.inference  (graphEncoders.py:177-198) ---------------------------
  * Parameter block: the reference's state_dict tensors by name (prefix graph_encoder. in Model). */
 /* Eq. 8 of the USER graph inside the encoder entry points (digat_params.flags, bits 0-1).  MIND user graphs hold ~4 entries

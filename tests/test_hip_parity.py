@@ -1126,8 +1126,10 @@ def _folded_query(query, Kw, Qw, bQ):
 
 @pytest.mark.parametrize("name", ["tiny.npz", "edges.npz", "default_b8.npz", "stress_b2.npz"])
 def test_a6_scaled_dot_product_attention_standalone(name):
-    """digat_attn_pool_fwd against the reference-minted ``a6_sdpa_candidate`` (candidate_attention over the news graph's
-    nodes, query = node 0; edges.npz holds fully masked rows: uniform attention over every node, E1)."""
+    """digat_attn_pool_fwd — attn_pool_kernel, the two-pass kernel, at every size: the entry never takes the register-resident
+    kernels inference runs (those alone: digat_pool_fwd in tests/test_hip_ctx_fp64.py) — against the reference-minted
+    ``a6_sdpa_candidate`` (candidate_attention over the news graph's nodes, query = node 0; edges.npz holds fully masked rows:
+    uniform attention over every node, E1)."""
     from digat_amd import _lib
     fx = load_golden(name)
     if "in_news_graph_embeddings" in fx:

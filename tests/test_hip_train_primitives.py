@@ -458,8 +458,10 @@ def _pool_reference(feat, kq, dout, mask):
 
 @pytest.mark.parametrize("n,d", [(1, 4), (10, 400), (67, 64), (68, 512), (82, 800), (128, 32)])
 def test_attn_pool_backward_against_oracle_autograd(n, d):
-    """training.AttnPool (digat_attn_pool_fwd / digat_attn_pool_bwd) at the sizes around which the forward's register-resident kernel
-    hands over (68 nodes, 512 channels): out, dfeat and dkq against float64 autograd through the oracle's ScaledDotProductAttention.
+    """training.AttnPool (digat_attn_pool_fwd / digat_attn_pool_bwd): out, dfeat and dkq against float64 autograd through the oracle's
+    ScaledDotProductAttention.  digat_attn_pool_fwd always launches attn_pool_kernel, the two-pass kernel, at every size — also at
+    those below 68 nodes and 512 channels, where inference's launch_pool takes attn_pool_resident_kernel; the resident kernels are
+    held to fp64 alone through digat_pool_fwd in tests/test_hip_ctx_fp64.py.
     Rows: ordinary, fully masked (uniform weights, no gradient to the scores), only node 0 live, and a row whose masked nodes hold
     NaN on the device — a masked node's weight is exactly 0 and its row must not enter any sum (the forward's rule, round 6):
     dfeat there is exactly 0 and nothing turns NaN.  Then ``accumulate_dfeat`` = 1 through the raw entry."""
