@@ -165,6 +165,7 @@ _SIGNATURES = {
     "digat_pl_sample": (C.c_int, [_f, _f, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_uint32, C.c_int64, C.c_int64, _f, _f, _f, _f, _f, _f,
                                   C.c_size_t, _f]),
     "digat_pl_log_prob": (C.c_int, [_f, _f, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int64, _f, _f, _f, _f, C.c_size_t, _f]),
+    "digat_pl_expect": (C.c_int, [_f, _f, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int64] + [_f] * 8 + [C.c_size_t, _f]),
     "digat_list_pl_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "digat_list_pl_fwd": (C.c_int, [_f] * 4 + [C.c_int64, C.c_int64, C.c_int, C.c_int, _f, C.c_int64, C.c_int, C.c_double, _f, _f, _f, _f]),
     "digat_pl_scores_bwd": (C.c_int, [_f, _f, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int64, _f, _f, _f, _f]),

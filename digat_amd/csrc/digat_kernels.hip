@@ -22,6 +22,7 @@
 //   digat_listq.inc  list quality: the same Gram reduced to a list's diversity, with category spread, overlap and exposure
 //   digat_calibrate.inc  calibrated top-k: the greedy re-rank of a shortlist of up to 1024 towards the category mix of the history
 //   digat_pl_sample.inc  stochastic lists: Plackett-Luce slates drawn from a list of up to 1024, with the probability of the draw
+//   digat_pl_expect.inc  doubly robust off-policy value: a logged slate's per-step expectation of an item value under the target, beside Z_t
 //   digat_rerank.inc  joint re-rank: diversity, calibration and a cap per category in one greedy pass over up to 1024 entries, no Gram
 // This file: shared helpers, the per-kernel profiler, and the C ABI.  The encoder's orchestration is digat_encoder.inc (host
 // code only), and every decision of an encoder call is made in digat_encoder_plan.h, every launch decision of Eq. 8 in
@@ -941,5 +942,6 @@ int digat_row_logits(const float* news_ctx, const float* user_ctx, float* logits
 #include "digat_bootstrap.inc"
 #include "digat_calibrate.inc"
 #include "digat_pl_sample.inc"
+#include "digat_pl_expect.inc"
 #include "digat_list_pl.inc"
 #include "digat_rerank.inc"

@@ -273,15 +273,15 @@ static int pl_check(const float* scores, int64_t G, int M, int k, double inv_t, 
     return DIGAT_OK;
 }
 
-// One launch per (at most PL_GRID_X lists, at most PL_GRID_Y samples).
-template <class Kernel>
-static int pl_launch(Kernel kernel, PlArgs a, int64_t G, int64_t S, hipStream_t st) {
+// One launch per (at most PL_GRID_X lists, at most PL_GRID_Y samples); `more`: a kernel's arguments behind PlArgs (digat_pl_expect.inc).
+template <class Kernel, class... More>
+static int pl_launch(Kernel kernel, PlArgs a, int64_t G, int64_t S, hipStream_t st, More... more) {
     for (long g0 = 0; g0 < (long)G; g0 += PL_GRID_X)
         for (long s0 = 0; s0 < (long)S; s0 += PL_GRID_Y) {
             const long gs = (long)G - g0 < PL_GRID_X ? (long)G - g0 : PL_GRID_X, ss = (long)S - s0 < PL_GRID_Y ? (long)S - s0 : PL_GRID_Y;
             a.g0 = g0;
             a.s0 = s0;
-            hipLaunchKernelGGL(kernel, dim3((unsigned)gs, (unsigned)ss), dim3(256), 0, st, a);
+            hipLaunchKernelGGL(kernel, dim3((unsigned)gs, (unsigned)ss), dim3(256), 0, st, a, more...);
             DIGAT_CHECK_LAUNCH();
         }
     return DIGAT_OK;

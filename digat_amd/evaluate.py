@@ -2784,14 +2784,17 @@ def _pl_lists_host(scores, count, inv_t):
     return sc, live, a
 
 
-def _pl_slate_host(a, live, picks, k):
+def _pl_slate_host(a, live, picks, k, values=None):
     """The probability stage of one list for one slate: ``(logp, step64 [k], logZ [k], length)`` — the slate is ``picks`` up to its
-    first entry that is negative, out of range, not live or repeated."""
+    first entry that is negative, out of range, not live or repeated.  With ``values`` [M] float64 (``pl_expect_host``) three
+    arrays [k] follow: ``mean[t] = fsum(w v over what is left at t) / Z_t``, every product rounded once, ``absolute[t]`` the same
+    over ``|v|``, and ``used[t]`` the value of pick t."""
     import math
     M = len(a)
     step, logz = np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.float64)
+    extra = () if values is None else tuple(np.zeros(k, dtype=np.float64) for _ in range(3))
     if not live.any():
-        return 0.0, step, logz, 0
+        return (0.0, step, logz, 0) + extra
     d = np.maximum(a - a[live].max(), PL_CLAMP)
     w = np.exp(d)
     left = live.copy()
@@ -2800,11 +2803,17 @@ def _pl_slate_host(a, live, picks, k):
         p = int(p)
         if p < 0 or p >= M or not left[p]:
             break
-        logz[n] = np.log(np.float64(math.fsum(w[left].tolist())))
+        z = np.float64(math.fsum(w[left].tolist()))
+        logz[n] = np.log(z)
         step[n] = d[p] - logz[n]
+        if values is not None:
+            wv = w[left] * values[left]
+            extra[0][n] = np.float64(math.fsum(wv.tolist())) / z
+            extra[1][n] = np.float64(math.fsum(np.abs(wv).tolist())) / z
+            extra[2][n] = values[p]
         left[p] = False
         n += 1
-    return math.fsum(step[:n].tolist()), step, logz, n
+    return (math.fsum(step[:n].tolist()), step, logz, n) + extra
 
 
 def pl_sample_host(scores, count, k: int, temperature, seed: int = 0, samples: int = 1, first_sample: int = 0, streams=None,
@@ -2972,6 +2981,97 @@ def pl_log_prob(scores, count, picks, temperature):
     _lib.check(L.digat_pl_log_prob(sc.data_ptr(), _lib.ptr(ct), G, M, k, inv_t, S, pk.data_ptr(), logp.data_ptr(), step.data_ptr(),
                                    ws.data_ptr(), need, _lib.stream_ptr()), "digat_pl_log_prob")
     return logp, step
+
+
+# ---- the per-step expectation behind a doubly robust off-policy value: csrc/digat_pl_expect.inc ----------------------------------
+def _check_values_shape(values_shape, scores_shape) -> None:
+    if tuple(values_shape) != tuple(scores_shape):
+        raise ValueError(f"values must hold one value per item of every list, {tuple(scores_shape)}, got {tuple(values_shape)}")
+
+
+def pl_expect_host(scores, count, picks, values, temperature, parts: bool = False):
+    """The contract of ``digat_pl_expect`` in numpy float64 — ``pl_log_prob_host`` with, for every step t of a slate, the expectation
+    of a per-item value under the conditional distribution that step draws from.  ``values`` [G, M] float32: ``v_p =
+    float64(values[g, p])`` where that is finite, else 0.  With ``w`` and ``Z_t`` as in ``pl_sample_host`` and ``left`` the live
+    positions not picked before step t: ``step_mean[t] = fsum(w[left] * v[left]) / Z_t``, every product rounded once, and
+    ``step_value[t]`` the float32 value used at pick t.  Returns ``(logp [G, S] float64, step_logp [G, S, k] float32, step_mean
+    [G, S, k] float64, step_value [G, S, k] float32, length [G, S] int32)`` — the first two are ``pl_log_prob_host``'s, ``length``
+    is the slate's cut, and everything is 0 at and beyond it.  ``parts`` adds ``pl_log_prob_host``'s dict with ``absolute`` [G, S, k]:
+    ``A_t = fsum(w[left] * |v[left]|) / Z_t``, what ``pl_expect_bound`` takes."""
+    pk = np.asarray(_host(picks))
+    if pk.dtype.kind not in "iu":
+        raise ValueError(f"picks must hold integer positions, got {pk.dtype}")
+    k = int(pk.shape[2]) if pk.ndim == 3 else 0
+    inv_t = _check_pl_args(np.shape(scores), None if count is None else np.shape(count), k, temperature, picks_shape=pk.shape)
+    _check_values_shape(np.shape(values), np.shape(scores))
+    sc, live, a = _pl_lists_host(scores, count, inv_t)
+    v32 = np.ascontiguousarray(_host(values), dtype=np.float32)
+    v32 = np.where(np.isfinite(v32), v32, np.float32(0))
+    v = v32.astype(np.float64)
+    G, S = sc.shape[0], int(pk.shape[1])
+    logp = np.zeros((G, S), dtype=np.float64)
+    length = np.zeros((G, S), dtype=np.int32)
+    step, logz, mean, absolute, used = (np.zeros((G, S, k), dtype=np.float64) for _ in range(5))
+    for g in range(G):
+        for s in range(S):
+            logp[g, s], step[g, s], logz[g, s], length[g, s], mean[g, s], absolute[g, s], used[g, s] = _pl_slate_host(
+                a[g], live[g], pk[g, s], k, v[g])
+    out = (logp, step.astype(np.float32), mean, used.astype(np.float32), length)
+    if parts:
+        out += ({"step": step, "logZ": logz, "live": live.sum(axis=1), "length": length, "absolute": absolute},)
+    return out
+
+
+def pl_expect_bound(n, absolute, mean):
+    """The comparison bound of ``pl_expect``'s ``step_mean`` against ``pl_expect_host`` (derived in csrc/digat_pl_expect.inc): ``(2 n +
+    12) 2^-53 A_t + 2^-52 |mean|`` with n the live elements of the list and ``A_t = sum w |v| / Z_t`` (``absolute`` of the twin's
+    parts).  ``(n + 6) 2^-53 A_t`` is the numerator — the 1-ulp ``exp`` on either side, one rounding per product on either side,
+    the twin's ``fsum`` and the order of the device's at most n signed terms —, ``(n + 4) 2^-53 |mean| <= (n + 4) 2^-53 A_t`` the sum
+    in ``Z_t`` (``pl_bound``'s), 2 of the 12 cover every term of second order at n <= 1024, and ``2^-52 |mean|`` is the division
+    rounded on either side.  It holds while every non-zero product ``w |v|`` is a normal float64: ``|v| >= 2^-12`` or 0 is enough
+    whatever the spread of the scores (a weight is at least e^-700)."""
+    n = np.asarray(n, dtype=np.float64)
+    return (2.0 * n + 12.0) * 2.0 ** -53 * np.abs(np.asarray(absolute, dtype=np.float64)) + 2.0 ** -52 * np.abs(np.asarray(mean, dtype=np.float64))
+
+
+def pl_expect(scores, count, picks, values, temperature):
+    """The per-step expectation of a per-item value under the target policy on the GPU (``digat_pl_expect``) — the control variate
+    of a doubly robust off-policy value (``off_policy_steps``).  ``scores`` [G, M <= 1024], ``count`` and ``picks`` [G, S, k] as in
+    ``pl_log_prob``; ``values`` [G, M] a floating-point device tensor (read as float32; a non-finite value counts as 0).  Returns
+    ``(logp [G, S] float64, step_logp [G, S, k] float32, step_mean [G, S, k] float64, step_value [G, S, k] float32, length [G, S]
+    int32)`` on the device: ``logp`` and ``step_logp`` are ``pl_log_prob``'s bit for bit (the same device function on the same
+    image), ``length`` the slate's cut, ``step_value`` the value used at every pick and ``step_mean[t]`` the expectation of the
+    value over what is left of the list at step t — ``pl_expect_host``'s contract, within ``pl_expect_bound``; 0 at and beyond
+    ``length``.  One workgroup per (list, slate), one more suffix sum beside ``Z_t``: the same bits from run to run and for a list
+    alone or in a batch.  Stream-ordered: nothing is read back."""
+    import torch
+    from . import _lib
+    dev, sc, ct, _ = _pl_device_args(scores, count)
+    _lib.require_device(sc, picks, values)
+    if picks.is_floating_point() or picks.dtype == torch.bool:
+        raise ValueError(f"picks must hold integer positions, got {picks.dtype}")
+    if not values.is_floating_point():
+        raise ValueError(f"values must be a floating-point tensor, got {values.dtype}")
+    k = int(picks.shape[2]) if picks.dim() == 3 else 0
+    inv_t = _check_pl_args(tuple(sc.shape), None if ct is None else tuple(ct.shape), k, temperature, picks_shape=tuple(picks.shape))
+    _check_values_shape(tuple(values.shape), tuple(sc.shape))
+    pk = torch.clamp(picks, min=-1, max=PL_MAX_LIST).to(torch.int32).contiguous()       # any position outside the list ends the slate
+    vl = values.detach().to(torch.float32).contiguous()
+    G, M, S = int(sc.shape[0]), int(sc.shape[1]), int(pk.shape[1])
+    logp = torch.empty((G, S), dtype=torch.float64, device=dev)
+    step = torch.empty((G, S, k), dtype=torch.float32, device=dev)
+    mean = torch.empty((G, S, k), dtype=torch.float64, device=dev)
+    used = torch.empty((G, S, k), dtype=torch.float32, device=dev)
+    length = torch.empty((G, S), dtype=torch.int32, device=dev)
+    if G == 0:
+        return logp, step, mean, used, length
+    L = _lib.lib()
+    need = int(L.digat_pl_sample_workspace_bytes(G, M, k, S))
+    ws = _lib.workspace(need, dev, "pl_sample")
+    _lib.check(L.digat_pl_expect(sc.data_ptr(), _lib.ptr(ct), G, M, k, inv_t, S, pk.data_ptr(), vl.data_ptr(), logp.data_ptr(), step.data_ptr(),
+                                 mean.data_ptr(), used.data_ptr(), length.data_ptr(), ws.data_ptr(), need, _lib.stream_ptr()),
+               "digat_pl_expect")
+    return logp, step, mean, used, length
 
 
 # ---- the differentiable Plackett-Luce slate likelihood over a user's own list: csrc/digat_list_pl.inc -----------------------------
@@ -3334,6 +3434,73 @@ def off_policy_value(reward, logp_target, logp_logging, clip=None, units=None, r
     out = {"ips": metric_intervals(wr, ("ips",), replicates, level, seed, units=units)["ips"],
            "snips": metric_intervals(wr, ("snips",), replicates, level, seed, denominators=w, units=units)["snips"]}
     out.update({"ess": float(w.sum() ** 2 / np.sum(w * w)) if w.sum() > 0 else 0.0, "max_weight": float(w.max()), "n": int(len(w))})
+    return out
+
+
+def off_policy_steps(reward, step_logp_target, step_logp_logging, length, step_mean=None, step_value=None, position_weight=None,
+                     clip=None, units=None, replicates: int = 2000, level: float = 0.95, seed: int = 0, length_logging=None):
+    """Per-position and doubly robust off-policy values of a sequential slate policy: one row per logged slate, ``reward`` [n, k] the
+    reward earned at every position, ``step_logp_target`` / ``step_logp_logging`` [n, k] the step log-probabilities under either
+    policy (``pl_expect`` / ``pl_log_prob`` and ``pl_sample``), ``length`` [n] the slate's cut under the target (``pl_expect``'s).
+    ``rho_t = exp(sum_{u <= t} (lt_u - ll_u))`` capped at ``clip`` (None: no cap), ``rho_{-1} = 1``:
+
+    ``pdis = mean_i sum_{t < length} rho_t r_t`` — a position's reward is weighted by the ratio of the slate's prefix up to it alone;
+    ``dr = mean_i sum_{t < length} [rho_t (r_t - D_t step_value_t) + rho_{t-1} D_t step_mean_t]`` with a value model ``D_t v_item``
+    of the reward at position t: ``step_value`` [n, k] the model's value of the item shown, ``step_mean`` [n, k] its expectation
+    under the target over what was left of the list (both ``pl_expect``'s) and ``D = position_weight`` [k] (None: ones).  Each pair
+    of terms has mean zero under the logging policy whatever the model, so ``dr`` is unbiased where ``pdis`` is (``clip`` None) and
+    has less variance the better the model is.  Without ``step_mean`` / ``step_value`` the model is 0 and ``dr`` equals ``pdis``.
+
+    Returns ``{"pdis", "dr"}`` — ``metric_intervals``' fields, both from the same draws, ``units`` (a CSR ``start`` over contiguous
+    rows) keeping a user's slates together —, ``ess`` and ``max_weight`` [k] per position (``sum(rho_t)^2 / sum(rho_t^2)`` and the
+    largest ``rho_t`` over the slates that reach position t; 0 where none does) and ``n``.  ``length_logging`` [n]: the slate's cut
+    under the logging policy where it may differ; a slate whose two lengths differ cannot be drawn in full by the target (or was
+    not drawn in full by the logger) and is a ``ValueError``: cut it or leave it out.  Non-finite input is a ``ValueError``.  Host
+    arrays or tensors; the resampling is ``metric_intervals``' own."""
+    r, lt, ll = (np.asarray(_host(x), dtype=np.float64) for x in (reward, step_logp_target, step_logp_logging))
+    if r.ndim != 2 or r.shape[0] < 1 or r.shape[1] < 1 or lt.shape != r.shape or ll.shape != r.shape:
+        raise ValueError(f"reward, step_logp_target and step_logp_logging must all be [n >= 1, k >= 1], got {r.shape}, {lt.shape} and {ll.shape}")
+    n, k = r.shape
+    if (step_mean is None) != (step_value is None):
+        raise ValueError("step_mean and step_value come together (evaluate.pl_expect returns both)")
+    sm, sv = ((np.zeros_like(r), np.zeros_like(r)) if step_mean is None else
+              (np.asarray(_host(x), dtype=np.float64) for x in (step_mean, step_value)))
+    if sm.shape != r.shape or sv.shape != r.shape:
+        raise ValueError(f"step_mean and step_value must be [n, k] = {r.shape}, got {sm.shape} and {sv.shape}")
+    D = np.ones(k, dtype=np.float64) if position_weight is None else np.asarray(_host(position_weight), dtype=np.float64)
+    if D.shape != (k,):
+        raise ValueError(f"position_weight must be [k] = [{k}], got {D.shape}")
+    ln = np.asarray(_host(length))
+    if ln.shape != (n,) or ln.dtype.kind not in "iu" or (n and (int(ln.min()) < 0 or int(ln.max()) > k)):
+        raise ValueError(f"length must hold one integer in [0, k = {k}] per logged slate ({n}), got {ln.dtype} {ln.shape}")
+    if length_logging is not None:
+        lg = np.asarray(_host(length_logging))
+        if lg.shape != (n,) or lg.dtype.kind not in "iu":
+            raise ValueError(f"length_logging must hold one integer per logged slate ({n}), got {lg.dtype} {lg.shape}")
+        bad = np.flatnonzero(lg.astype(np.int64) != ln.astype(np.int64))
+        if len(bad):
+            raise ValueError(f"slate {int(bad[0])} has length {int(lg[bad[0]])} under the logging policy and {int(ln[bad[0]])} under the target "
+                             f"({len(bad)} such slates): the target cannot draw it in full — cut it or leave it out")
+    for name, x in (("reward", r), ("step_logp_target", lt), ("step_logp_logging", ll), ("step_mean", sm), ("step_value", sv),
+                    ("position_weight", D)):
+        if not np.isfinite(x).all():
+            raise ValueError(f"{name} must be finite (a step the target cannot draw has no finite log-probability: cut the slate or leave it out)")
+    if clip is not None and not float(clip) > 0.0:
+        raise ValueError(f"clip must be positive, got {clip}")
+    shown = np.arange(k)[None, :] < ln.astype(np.int64)[:, None]
+    with np.errstate(over="ignore"):
+        rho = np.exp(np.cumsum(np.where(shown, lt - ll, 0.0), axis=1))
+    if clip is not None:
+        rho = np.minimum(rho, float(clip))
+    rho = np.where(shown, rho, 0.0)
+    if not np.isfinite(rho).all():
+        raise ValueError("a weight exp(sum of step_logp_target - step_logp_logging) overflows: name clip")
+    before = np.concatenate([np.ones((n, 1), dtype=np.float64), rho[:, :-1]], axis=1)
+    pdis = np.where(shown, rho * r, 0.0).sum(axis=1)
+    dr = np.where(shown, rho * (r - D[None, :] * sv) + before * (D[None, :] * sm), 0.0).sum(axis=1)
+    out = metric_intervals(np.stack([pdis, dr], axis=1), ("pdis", "dr"), replicates, level, seed, units=units)
+    s1, s2 = rho.sum(axis=0), (rho * rho).sum(axis=0)
+    out.update({"ess": np.where(s2 > 0, s1 * s1 / np.where(s2 > 0, s2, 1.0), 0.0), "max_weight": rho.max(axis=0), "n": int(n)})
     return out
 
 

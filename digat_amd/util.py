@@ -1282,6 +1282,72 @@ def slate_log_prob(ids: torch.Tensor, scores: torch.Tensor, count, slates, tempe
     return logp, step, covered
 
 
+def slate_step_values(ids: torch.Tensor, scores: torch.Tensor, count, slates, temperature: float, values: torch.Tensor):
+    """``slate_log_prob`` with the control variate of a doubly robust value: ``slates`` [G,S,k] news ids are matched to positions of
+    ``ids`` [G,M] (``slate_positions``) and ``evaluate.pl_expect`` (CPU tensors: ``evaluate.pl_expect_host``) gives, under
+    ``softmax(scores / temperature)``, ``logp`` [G,S] float64, ``step_logp`` [G,S,k] float32, ``step_mean`` [G,S,k] float64 — the
+    expectation of ``values`` [G,M] (a value per item of every list) over what is left of the list at every step —, ``step_value``
+    [G,S,k] float32 — the value of the item shown — and ``length`` [G,S] int32, the slot at which the slate ended.  Returns those
+    five and ``covered`` [G,S] bool, ``slate_log_prob``'s."""
+    sl = _tensor_on(slates, ids.device)
+    if sl.dim() != 3 or int(sl.shape[0]) != int(ids.shape[0]) or sl.is_floating_point():
+        raise ValueError(f"slates must be integer news ids [G = {int(ids.shape[0])}, S, k], got {tuple(sl.shape)} {sl.dtype}")
+    if ids.dim() != 2 or tuple(scores.shape) != tuple(ids.shape) or tuple(values.shape) != tuple(ids.shape):
+        raise ValueError(f"ids, scores and values must all be [G, M], got {tuple(ids.shape)}, {tuple(scores.shape)} and {tuple(values.shape)}")
+    picks = slate_positions(ids, count, sl)
+    if ids.is_cuda:
+        out = evaluate.pl_expect(scores, count, picks, _tensor_on(values, ids.device), temperature)
+    else:
+        out = tuple(map(torch.from_numpy, evaluate.pl_expect_host(scores.numpy(), None if count is None else count.numpy(), picks.numpy(),
+                                                                  values.numpy(), temperature)))
+    finite = torch.isfinite(scores.gather(1, picks.to(torch.int64).clamp(min=0).view(picks.shape[0], -1))).view(picks.shape)
+    covered = ((sl < 0) | ((picks >= 0) & finite)).all(dim=2)
+    return out + (covered,)
+
+
+def off_policy_report(log: dict, target_scores: torch.Tensor, reward, values=None, position_weight=None, temperature=None, clip=None,
+                      units=None, replicates: int = 2000, level: float = 0.95, seed: int = 0):
+    """What a target policy would have earned on a ``recommend_slates`` log, by four estimators side by side.  ``log``: that dict;
+    ``target_scores`` [G,k']: the target's scores of the log's shortlist ``ids`` (``score_lists``); ``reward`` [G,S,k]: the reward at
+    every position of every logged slate; ``values`` [G,k'] (optional): a model of an item's reward, scaled per position by
+    ``position_weight`` [k] (None: ones); ``temperature`` None: the log's own.  The target's step probabilities and the model's
+    per-step expectation come from one ``slate_step_values`` call.  Returns ``ips`` / ``snips`` (``evaluate.off_policy_value`` on the
+    slate's summed reward and the slate-level weight, with its ``ess`` and ``max_weight``), ``pdis`` and — with ``values`` — ``dr``
+    (``evaluate.off_policy_steps``, with ``step_ess`` / ``step_max_weight`` [k]), every one with ``metric_intervals``' fields, and
+    ``n`` / ``dropped``: a slate that the target cannot draw in full (it ends earlier under the target than in the log) is left out
+    and counted — with ``units`` given such a slate is a ``ValueError``, because the rows of a unit must stay contiguous."""
+    ids, slates = log["ids"], log["slates"]
+    T = float(log["temperature"] if temperature is None else temperature)
+    tgt = _tensor_on(target_scores, ids.device)
+    vals = torch.zeros_like(tgt, dtype=torch.float32) if values is None else _tensor_on(values, ids.device)
+    logp, step, mean, used, length, _ = slate_step_values(ids, tgt, log["count"], slates, T, vals)
+    G, S, k = (int(x) for x in slates.shape)
+    r = np.asarray(evaluate._host(reward), dtype=np.float64)
+    if r.shape != (G, S, k):
+        raise ValueError(f"reward must be [G, S, k] = {(G, S, k)}, got {r.shape}")
+    ln = evaluate._host(length).reshape(-1).astype(np.int64)
+    ln_log = np.repeat(evaluate._host(log["n_out"]).astype(np.int64), S)
+    keep = ln == ln_log
+    dropped = int((~keep).sum())
+    if dropped and units is not None:
+        raise ValueError(f"{dropped} logged slates end earlier under the target than in the log: leave them out of the log and of units first")
+    if not keep.any():
+        raise ValueError("the target can draw none of the logged slates in full")
+    rows = lambda x: np.asarray(evaluate._host(x), dtype=np.float64).reshape(G * S, -1)[keep]
+    r2 = rows(r)
+    shown = np.arange(k)[None, :] < ln[keep][:, None]
+    slate = evaluate.off_policy_value(np.where(shown, r2, 0.0).sum(axis=1), rows(logp)[:, 0], rows(log["logp"])[:, 0], clip, units, replicates,
+                                      level, seed)
+    steps = evaluate.off_policy_steps(r2, rows(step), rows(log["step_logp"]), ln[keep], None if values is None else rows(mean),
+                                      None if values is None else rows(used), position_weight, clip, units, replicates, level, seed,
+                                      length_logging=ln_log[keep])
+    out = {"ips": slate["ips"], "snips": slate["snips"], "pdis": steps["pdis"], "ess": slate["ess"], "max_weight": slate["max_weight"],
+           "step_ess": steps["ess"], "step_max_weight": steps["max_weight"], "n": steps["n"], "dropped": dropped}
+    if values is not None:
+        out["dr"] = steps["dr"]
+    return out
+
+
 def shortlist_then_sample(select: Callable, k, sample, shortlist=None, seed: int = 0, streams=None, samples: int = 1):
     """The step behind ``recommend(sample=)`` of either model and ``recommend_slates``: ``select(k', long_lists)`` — the plain
     selection at ``sample_limits``' width, ``long_lists`` when ``k' > 128`` — then ``sample_lists``.  Returns ``(shortlist triple,

@@ -979,6 +979,24 @@ int digat_pl_sample(const float* scores, const int32_t* count, int64_t G, int M,
 int digat_pl_log_prob(const float* scores, const int32_t* count, int64_t G, int M, int k, double inv_t, int64_t samples, const int32_t* picks,
                       double* out_logp, float* out_step, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- doubly robust off-policy value: a logged slate's per-step expectation under the target (digat_amd.evaluate.pl_expect) -------
+ * scores, count, G, M, k, inv_t, samples and picks [G, samples, k] are digat_pl_log_prob's, under its rules and limits; out_logp
+ * [G, samples] f64 and out_step [G, samples, k] f32 are its outputs bit for bit (the same device function on the same image), and
+ * out_len [G, samples] int32 is the length at which the slate was cut.  values [G, M] f32 holds a value per item of the list:
+ * v_p = (double)values[g][p] where that float is finite, else 0.  For every step t below the length, with the weights w and Z_t of
+ * digat_pl_sample above: out_value [G, samples, k] f32 = the float32 value used at pick t (0 where it is not finite), and
+ *   out_mean [G, samples, k] f64 = fl(N_t / Z_t),   N_t = the sum of fl(w_j v_j) over the live positions not picked before step t
+ * — the expectation of v under the conditional distribution step t draws from.  N_t is the suffix sum beside Z_t: the unpicked
+ * positions reduced in Z_t's order, then fl(w_pick(t) v_pick(t)) added back from the end of the slate; every operation a rounded
+ * float64 one, never an fma.  At and beyond the length out_mean and out_value are 0.  Every output byte is written.
+ * The same bits from run to run and for a list alone or in a batch; against evaluate.pl_expect_host out_mean stays within
+ * evaluate.pl_expect_bound (derived in csrc/digat_pl_expect.inc).  Errors as digat_pl_log_prob, with values and the three further
+ * outputs among the pointers (8 bytes for out_mean).  Stream-ordered: one workgroup per (list, slate); no atomics, no allocation,
+ * no host synchronisation; the workspace is not used (digat_pl_sample_workspace_bytes). */
+int digat_pl_expect(const float* scores, const int32_t* count, int64_t G, int M, int k, double inv_t, int64_t samples, const int32_t* picks,
+                    const float* values, double* out_logp, float* out_step, double* out_mean, float* out_value, int32_t* out_len,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- differentiable Plackett-Luce slate likelihood over a user's own list (digat_amd.evaluate.list_pl / pl_scores) -------------
  * users [G, d], rows [P, d], ids [G, M] int64, count [G] int32 (NULL: M) as in digat_list_softmax_fwd: slot (g, j) is an ELEMENT
  * when j < clamp(count[g], 0, M) and 0 <= ids[g, j] < P; 1 <= M <= DIGAT_SHORTLIST_MAX_K, 1 <= d <= DIGAT_LIST_SOFTMAX_MAX_D,

@@ -96,6 +96,13 @@
                                              trained DIGAT logs slates with propensities (util.recommend_slates), colder and hotter
                                              target policies are valued on the log (score_lists, slate_log_prob, off_policy_value: IPS
                                              and SNIPS with intervals, ess / n) beside their true on-policy value
+  python tools/kbench.py pl-expect [rounds]  doubly robust control variate: evaluate.pl_expect (pl_log_prob's workgroup with one more suffix
+                                             sum beside Z_t) against gathers + the tail's logsumexp + a flipped logcumsumexp and the same
+                                             for the weighted sums in stock PyTorch, chunked to 1 GiB, pl-sample's shapes, the legs in turn,
+                                             median [min, max] of five rounds, time and peak device bytes
+  python tools/kbench.py off-policy-steps [users k shortlist samples truth_samples replicates]   the off-policy demonstration at k = 10 from a
+                                             shortlist of 80 with a reward per position: IPS, SNIPS, PDIS and DR (value model: the category
+                                             half of the planted match) with intervals (util.off_policy_report) beside the on-policy truth
   python tools/kbench.py list-quality [news_num d]   list quality: evaluate.list_quality (one launch, the Gram in LDS) against the same
                                              figures from gather + torch.bmm, the upper triangle's sum and max, a sort for the
                                              categories, a broadcast compare for the overlap and torch.bincount for the exposure,
@@ -2341,6 +2348,135 @@ def demo_off_policy(users=2000, k=3, samples=4, truth_samples=64, replicates=200
               f"{float(covered.float().mean()):.3f}", flush=True)
 
 
+def stock_pl_expect(scores, count, picks, values, temperature, budget=1 << 30):
+    """``evaluate.pl_expect``'s ``logp``, ``step_logp`` and ``step_mean`` built only from stock PyTorch in float64 — what the tree
+    offered before ``digat_pl_expect``: a gather of the picks, the unpicked tail's ``logsumexp`` and a flipped ``logcumsumexp`` for
+    ``log Z_t``; the same for the weighted sums in the linear domain — ``exp(a - a_max) v``, its gather, the tail's sum and a flipped
+    ``cumsum`` — and one division; over as many lists at a time as keep the [g, S, M] float64 intermediates (the expanded scores
+    and values, the masked copies, the weights and products) inside ``budget`` bytes.  Every slate is taken to be k live, distinct
+    positions."""
+    G, M = scores.shape
+    S, k = int(picks.shape[1]), int(picks.shape[2])
+    dev = scores.device
+    a = scores.to(torch.float64) / temperature
+    a = torch.where(torch.arange(M, device=dev)[None, :] < count[:, None], a, torch.full((), float("-inf"), dtype=torch.float64, device=dev))
+    v = torch.where(torch.isfinite(values), values, torch.zeros_like(values)).to(torch.float64)
+    logp = torch.empty((G, S), dtype=torch.float64, device=dev)
+    step = torch.empty((G, S, k), dtype=torch.float64, device=dev)
+    mean = torch.empty((G, S, k), dtype=torch.float64, device=dev)
+    rows = max(1, budget // (S * M * 8 * 6))
+    for g0 in range(0, G, rows):
+        ag = a[g0:g0 + rows, None, :].expand(-1, S, -1)
+        idx = picks[g0:g0 + rows].to(torch.int64)
+        mine = ag.gather(2, idx)
+        tail = ag.scatter(2, idx, float("-inf")).logsumexp(dim=2, keepdim=True)
+        lse = torch.cat([mine, tail], dim=2).flip(2).logcumsumexp(dim=2).flip(2)[:, :, :k]
+        top = a[g0:g0 + rows].amax(dim=1)[:, None, None]
+        wv = torch.exp(ag - top) * v[g0:g0 + rows, None, :]
+        num = torch.cat([wv.gather(2, idx), wv.scatter(2, idx, 0.0).sum(dim=2, keepdim=True)], dim=2).flip(2).cumsum(dim=2).flip(2)[:, :, :k]
+        step[g0:g0 + rows] = mine - lse
+        logp[g0:g0 + rows] = step[g0:g0 + rows].sum(dim=2)
+        mean[g0:g0 + rows] = num / torch.exp(lse - top)
+    return logp, step, mean
+
+
+def bench_pl_expect(rounds=5):
+    """``evaluate.pl_expect`` against ``stock_pl_expect``, the two legs in turn in one process, median [min, max] of ``rounds``
+    rounds and each leg's peak of device bytes beyond its inputs: ``pl-sample``'s shapes, (G, M, k, S) in {64, 4 096} x {128, 1 024}
+    x {10, 100} x {1, 8}, scores N(0, 1) sorted as a shortlist comes, values N(0, 1), T = 1, the slates ``pl_sample``'s own.  Beside
+    the times: the largest difference of the two legs' ``step_mean``."""
+    from digat_amd import evaluate
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device="cpu").manual_seed(0)
+
+    def peak(fn):
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        out = fn()
+        torch.cuda.synchronize()
+        return out, torch.cuda.max_memory_allocated() - base
+    print(f"pl-expect: logp, step_logp and the per-step expectation of a value for S logged slates of k per list of M, T = 1; ms per call, "
+          f"median [min, max] of {rounds} rounds", flush=True)
+    for G in (64, 4096):
+        for M in (128, 1024):
+            scores = torch.randn(G, M, generator=g).sort(dim=1, descending=True).values.to(dev)
+            values = torch.randn(G, M, generator=g).to(dev)
+            count = torch.full((G,), M, dtype=torch.int32, device=dev)
+            for k in (10, 100):
+                for S in (1, 8):
+                    picks = evaluate.pl_sample(scores, count, k, 1.0, seed=1, samples=S)[0]
+                    ours = lambda: evaluate.pl_expect(scores, count, picks, values, 1.0)
+                    stock = lambda: stock_pl_expect(scores, count, picks, values, 1.0)
+                    (got, pa), (want, pb) = peak(ours), peak(stock)
+                    diff = float((got[2] - want[2]).abs().max())
+                    (a, alo, ahi), (b, blo, bhi) = alternate(ours, stock, rounds=rounds, iters=5)
+                    print(f"  G = {G:5d}, M = {M:4d}, k = {k:3d}, S = {S}: pl_expect {a:8.3f} ms [{alo:.3f}, {ahi:.3f}] ({1e6 * a / (G * S):.1f} ns "
+                          f"per slate, peak {pa / 2**20:.2f} MiB) | stock composition {b:8.3f} ms [{blo:.3f}, {bhi:.3f}] (x{b / a:.2f}, peak "
+                          f"{pb / 2**20:.1f} MiB) | max |step_mean difference| {diff:.2e}", flush=True)
+                    del picks
+            del scores, values, count
+    torch.cuda.empty_cache()
+
+
+def demo_off_policy_steps(users=2000, k=10, shortlist=80, samples=4, truth_samples=64, replicates=2000):
+    """``demo_off_policy`` at a size the slate-level weight cannot carry — k = 10 from a shortlist of 80 — with a reward per POSITION
+    (the planted match of the item at t: 1 for a preferred sub-topic, 1/2 for its category) and all four estimators side by side
+    (``util.off_policy_report``): IPS and SNIPS on the slate's summed reward, PDIS, and DR with a deliberately imperfect value
+    model — the category half alone: 1/2 for a news of a preferred sub-topic's category, sub-topic or not.  Beside them the target's
+    TRUE value: the summed reward of ``truth_samples`` slates per user drawn from the target itself on the same shortlists."""
+    import types
+    from digat_amd import synthetic, util
+    from digat_amd.model import Model, PrecomputedNewsEncoder
+    dev = torch.device("cuda:0")
+    golden = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
+    state = {name: v for name, v in np.load(os.path.join(golden, "trained_planted_state.npz")).items()}
+    depth = int(np.load(os.path.join(golden, "devset_trained_2k.npz"))["depth"])
+    full = synthetic.make_corpus(synthetic.SynthSpec(**synthetic.PLANTED_SPEC))
+    pref, news_sub = synthetic.planted_match(full)
+    corpus = synthetic.slice_impressions(full, 0, users)
+    spec = full.spec
+    cfg = types.SimpleNamespace(news_encoder="MSA", graph_encoder="DIGAT", news_graph_size=spec.news_graph_size,
+                                max_history_num=spec.max_history_num, category_num=spec.category_num, graph_depth=depth, dropout_rate=0.2)
+    model = Model(cfg, news_encoder=PrecomputedNewsEncoder(torch.from_numpy(corpus.news_embedding)))
+    model.graph_encoder.load_state_dict({name: torch.from_numpy(v) for name, v in state.items()})
+    model = model.to(dev).eval()
+    dc = util.DeviceCorpus.from_numpy(corpus, dev)
+    who = np.arange(users, dtype=np.int64)
+    pool = np.arange(1, spec.news_num, dtype=np.int64)
+    spc = spec.subtopics_per_category
+
+    def item_reward(slates):                                            # [G, S, k] news ids -> the planted match of every item
+        sl = slates.cpu().numpy()
+        return synthetic.planted_reward(pref[:users], news_sub, sl.reshape(users, -1, 1), spc).reshape(sl.shape)
+    short = util.recommend(model, dc, who, pool, shortlist)
+    t_log = float(short[1].to(torch.float64).std(dim=1).mean())
+    log = util.recommend_slates(model, dc, who, pool, k, t_log, samples=samples, seed=1, shortlist=shortlist)
+    r_log = item_reward(log["slates"])
+    ids = log["ids"].cpu().numpy()
+    p = pref[:users][:, None, :]
+    same_cat = ((news_sub[np.maximum(ids, 0)][..., None] // spc == p // spc) & (p >= 0)).any(axis=-1)
+    values = torch.from_numpy(np.where(ids >= 0, 0.5 * same_cat, 0.0).astype(np.float32)).to(dev)
+    units = np.arange(0, users * samples + 1, samples)
+    print(f"off-policy-steps demo: planted-signal corpus, the trained DIGAT logs {samples} slates of k = {k} for each of {users} held-out "
+          f"impressions from a shortlist of {shortlist} at T_log = {t_log:.4f}; reward = the summed planted match of the slate's items, "
+          f"logged mean {r_log.sum(axis=2).mean():.4f}; value model: the category half alone; intervals: 95 %, {replicates} replicates over users",
+          flush=True)
+    scores = util.score_lists(model, dc, who, log["ids"], log["count"])
+    for name, t_target in (("colder", t_log / 2), ("hotter", 2 * t_log)):
+        rep = util.off_policy_report(log, scores, r_log, values=values, temperature=t_target, units=units, replicates=replicates)
+        own = util.sample_lists(log["ids"], scores, log["count"], k, t_target, seed=2, samples=truth_samples, streams=torch.as_tensor(who))
+        truth = float(item_reward(own[0]).sum(axis=2).mean())
+        print(f"  target {name} (T = {t_target:.4f}): truth (on-policy, {truth_samples} slates per user) {truth:.4f}; slate weight: ess / n "
+              f"{rep['ess'] / rep['n']:.4f}, max {rep['max_weight']:.1f}; per position ess / n {rep['step_ess'][0] / rep['n']:.3f} (t = 0) .. "
+              f"{rep['step_ess'][-1] / rep['n']:.4f} (t = {k - 1}), max {rep['step_max_weight'].max():.1f}; dropped {rep['dropped']}", flush=True)
+        for est in ("ips", "snips", "pdis", "dr"):
+            f = rep[est]
+            print(f"    {est.upper():5s} {f['value']:.4f} [{f['lo']:.4f}, {f['hi']:.4f}]  width {f['hi'] - f['lo']:.4f}  se {f['se']:.4f}  holds the truth: "
+                  f"{f['lo'] <= truth <= f['hi']}", flush=True)
+
+
 def stock_list_pl(users, rows, ids, count, picks, inv_t, backward=False, budget=1 << 30):
     """The summed ``logp`` of ``evaluate.list_pl`` from stock PyTorch under autograd in float32 — ``index_select`` + ``torch.bmm``, then
     ``evaluate._pl_stock``: a gather of the picks, ``logsumexp`` of the unpicked tail, a flipped ``logcumsumexp`` — the lists in chunks
@@ -2758,6 +2894,10 @@ if __name__ == "__main__":
         bench_pl_sample(*nums)
     elif what == "off-policy":
         demo_off_policy(*nums)
+    elif what == "pl-expect":
+        bench_pl_expect(*nums)
+    elif what == "off-policy-steps":
+        demo_off_policy_steps(*nums)
     elif what == "list-pl":
         bench_list_pl(*nums)
     elif what == "policy":
