@@ -236,6 +236,7 @@ _SIGNATURES = {
     "digat_linear_f32x3": (C.c_int, [_f, C.c_int64, _f, _f, _f, C.c_int64, C.c_int, C.c_int, C.c_int, _f, C.c_int, _f]),
     "digat_linear_rows_f32x3": (C.c_int, [_f, C.c_int64] + [_f] * 6 + [C.c_int64] + [C.c_int] * 3 + [_f, C.c_int, _f, _f, _f, C.c_int64, _f]
                                 + [C.c_int] * 3 + [_f]),
+    "digat_gemm_launch": (C.c_int, [_f, C.c_size_t, C.c_int, _f, C.POINTER(C.c_int), _f]),
     "digat_fold_workspace_bytes": (C.c_size_t, [C.c_int]),
     "digat_fold_attention": (C.c_int, [_f] * 5 + [C.c_int, _f, C.c_size_t, _f]),
     "digat_linear_bwd_input": (C.c_int, [_f, C.c_int64, _f, _f, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _f]),

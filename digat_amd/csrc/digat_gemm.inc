@@ -613,7 +613,10 @@ __global__ void __launch_bounds__(256, MT == 1 ? 3 : 2) gemm_bf16x6s_kernel(cons
     bf16x8 af[3][MT], afn[3][MT];
     if constexpr (NSUB == 1) {
 #pragma unroll
-        for (int j = 0; j < ABUF; ++j) if (j < KT) issue_a(j, j);
+        // every A buffer is filled before the loop: with a single K tile (K = 32) the second one takes a copy of it.  The last step
+        // splits the buffer after its own (unused products) — never written, its LDS garbage reached fp16x3's range check (amax)
+        // and raised range_flag on operands of ordinary size
+        for (int j = 0; j < ABUF; ++j) issue_a(j < KT ? j : KT - 1, j);
 #pragma unroll
         for (int j = 0; j < RING - 1; ++j) if (j < nsteps) issue_b(j);
     } else if constexpr (RAG) {

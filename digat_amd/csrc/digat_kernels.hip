@@ -615,6 +615,28 @@ int digat_linear_rows_f32x3(const float* x, int64_t ldx, const float* w0, const 
     return launch_gemm(g, (hipStream_t)stream, DIGAT_KERNEL_PROJ);
 }
 
+// Any launch launch_gemm takes, for the tests that hold every GEMM kernel alone to an fp64 product (tests/test_gemm_fp64_gpu.py):
+// `args` is a GemmArgs (args_bytes guards a mirror of the struct that has drifted); wsplit_scratch non-NULL: the weight segments
+// are split into it in args->format and the launch reads that image.  *kernel_out receives the GemmKernel gemm_plan chose, for
+// refused launches too.  exec_rows, mtiles, ntiles and strips are launch_gemm's own: whatever the caller put there is dropped.
+int digat_gemm_launch(const void* args, size_t args_bytes, int kind, void* wsplit_scratch, int* kernel_out, void* stream) {
+    if (!args || !kernel_out || args_bytes != sizeof(GemmArgs) || (kind != DIGAT_KERNEL_PROJ && kind != DIGAT_KERNEL_LINEAR)) return DIGAT_ERR_ARG;
+    GemmArgs g = *static_cast<const GemmArgs*>(args);
+    *kernel_out = GEMM_NONE;
+    if (g.nsegs < 1 || g.nsegs > 3 || g.M < 0 || g.nseg <= 0 || g.K <= 0 || g.k0 < 0 || g.k0 > g.K || !g.a0 || (g.k0 < g.K && !g.a1)) return DIGAT_ERR_ARG;
+    for (int s = 0; s < g.nsegs; ++s) if (!g.w[s] || !g.y[s]) return DIGAT_ERR_ARG;
+    if ((g.rowidx && !g.nrows_dev) || (g.radd && (g.rows_per_b <= 0 || g.radd_seg < 0 || g.radd_seg >= g.nsegs))) return DIGAT_ERR_ARG;
+    g.exec_rows = nullptr; g.mtiles = g.ntiles = g.strips = 0;
+    if (wsplit_scratch) g.wsplit = (const unsigned short*)wsplit_scratch;
+    *kernel_out = gemm_plan(g, kind).kernel;
+    if (wsplit_scratch) {
+        const int rcs = launch_split(g.w[0], g.w[g.nsegs > 1 ? 1 : 0], g.w[g.nsegs > 2 ? 2 : 0], g.nseg, g.nsegs, g.K, wsplit_scratch,
+                                     (hipStream_t)stream, 0, g.format);
+        if (rcs) return rcs;
+    }
+    return launch_gemm(g, (hipStream_t)stream, kind);
+}
+
 // ---- a3 -----------------------------------------------------------------------------------------
 // query, K^T query and the global context, [B,d] each
 struct NewsCtxWs { float *qv, *kq, *glob; };

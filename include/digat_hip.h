@@ -86,6 +86,12 @@ int digat_linear_rows_f32x3(const float* x, int64_t ldx, const float* w0, const 
                             float* y0, float* y1, int64_t ldy, int M, int nseg, int K, void* wsplit, int format,
                             const int* rowidx, const int* nrows_dev, const float* e0, int64_t lde0,
                             const float* radd, int rows_per_b, int m_dispatch, int ragged, void* stream);
+/* Any GEMM launch of the library, for the tests that hold each kernel alone to an fp64 product: `args` is a GemmArgs
+ * (digat_amd/csrc/digat_gemm_plan.h), args_bytes its size (anything else: DIGAT_ERR_ARG, a mirror of the struct has drifted); kind:
+ * DIGAT_KERNEL_PROJ or DIGAT_KERNEL_LINEAR.  wsplit_scratch non-NULL (digat_split_weights_bytes_format(nsegs nseg, K, format) bytes):
+ * the weight segments are split into it in args->format and the launch reads that image; NULL: args->wsplit as given.
+ * *kernel_out receives the GemmKernel the launch plan chose, for refused launches too.  Returns the launch's status. */
+int digat_gemm_launch(const void* args, size_t args_bytes, int kind, void* wsplit_scratch, int* kernel_out, void* stream);
 
 /* ---- a1 / a2: DIGAT.compute_news_graph_embeddings / compute_user_graph_embeddings -------------
  * graphEncoders.py:143-154 / :163-174 (Eq. 8).  X [B,n,d], A [B,n,n] bytes, ctx [B,d] (the OTHER
