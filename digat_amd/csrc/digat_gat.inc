@@ -60,6 +60,9 @@ static GatWs gat_carve(Arena& w, int B, int n, int d) {
     return GatWs{w.take<float>(bn * d), w.take<float>(bn), w.take<float>(bn), w.take<float>(bn * n)};      // braces: taken left to right
 }
 
+// the aggregation's route: d <= 1024 (eq8_agg_route's upto_1024), asked before the first launch of an entry
+static Eq8AggRoute gat_agg_route(int B, int n, int d) { return eq8_agg_route(B, n, d, true, EQ8_UNGUARDED); }
+
 extern "C" {
 
 size_t digat_gat_workspace_bytes(int B, int n, int d) { Arena a; gat_carve(a, B, n, d); return a.used; }
@@ -67,7 +70,7 @@ size_t digat_gat_workspace_bytes(int B, int n, int d) { Arena a; gat_carve(a, B,
 int digat_gat_fwd(const float* X, const uint8_t* A, const float* W, const float* bW, const float* a1, const float* a2,
                   float* out, int B, int n, int d, void* workspace, size_t workspace_bytes, void* stream) {
     if (!X || !A || !W || !a1 || !a2 || !out || !workspace || B < 0 || n <= 0 || d <= 0) return DIGAT_ERR_ARG;
-    if (d % 4 || n > DIGAT_MAX_NODES) return DIGAT_ERR_SHAPE;
+    if (d % 4 || n > DIGAT_MAX_NODES || gat_agg_route(B, n, d).status) return DIGAT_ERR_SHAPE;      // before any launch
     Arena w(workspace, workspace_bytes);
     const GatWs o = gat_carve(w, B, n, d);
     if (!w.ok) return DIGAT_ERR_WORKSPACE;
@@ -80,7 +83,7 @@ int digat_gat_fwd(const float* X, const uint8_t* A, const float* W, const float*
     DIGAT_CHECK_LAUNCH();
     hipLaunchKernelGGL(gat_alpha_kernel, dim3((unsigned)((nodes + 3) / 4)), dim3(256), 0, st, (const float*)o.s1, (const float*)o.s2, A, o.alpha, (float*)nullptr, nodes, n);
     DIGAT_CHECK_LAUNCH();
-    return launch_agg(agg_args(o.alpha, o.h, X, out, B, n, d), eq8_agg_route(B, n, d, true, EQ8_UNGUARDED), st);
+    return launch_agg(agg_args(o.alpha, o.h, X, out, B, n, d), gat_agg_route(B, n, d), st);
 }
 
 }  // extern "C"
@@ -155,7 +158,7 @@ int digat_gat_fwd_train(const float* X, const uint8_t* A, const float* W, const 
                         size_t workspace_bytes, void* stream) {
     if (!X || !A || !W || !bW || !a1 || !a2 || !out || !save || !workspace) return DIGAT_ERR_ARG;
     if (B < 0 || n <= 0 || d <= 0 || p_alpha < 0.f || p_alpha >= 1.f) return DIGAT_ERR_ARG;
-    if (d % 4 || n > DIGAT_MAX_NODES) return DIGAT_ERR_SHAPE;
+    if (d % 4 || n > DIGAT_MAX_NODES || gat_agg_route(B, n, d).status) return DIGAT_ERR_SHAPE;      // before any launch
     if (B == 0) return DIGAT_OK;
     Arena sa(save, save_bytes), w(workspace, workspace_bytes);
     const GatSave s = gat_save_carve(sa, B, n, d);
@@ -174,7 +177,7 @@ int digat_gat_fwd_train(const float* X, const uint8_t* A, const float* W, const 
         T_TRY(digat_dropout_fwd(s.alpha, o.adrop, s.amask, (int64_t)B * n * n, p_alpha, seed, stream));
         aggalpha = o.adrop;
     }
-    return launch_agg(agg_args(aggalpha, s.h, X, out, B, n, d), eq8_agg_route(B, n, d, true, EQ8_UNGUARDED), st);
+    return launch_agg(agg_args(aggalpha, s.h, X, out, B, n, d), gat_agg_route(B, n, d), st);
 }
 
 // dX [B,n,d], dW [d,d], dbW [d], da1 da2 [d]: all written (not accumulated)
@@ -183,7 +186,7 @@ int digat_gat_bwd(const float* dOut, const float* out, const float* X, const uin
                   int B, int n, int d, void* workspace, size_t workspace_bytes, void* stream) {
     if (!dOut || !out || !X || !A || !W || !a1 || !a2 || !save || !dX || !dW || !dbW || !da1 || !da2 || !workspace) return DIGAT_ERR_ARG;
     if (B < 0 || n <= 0 || d <= 0) return DIGAT_ERR_ARG;
-    if (d % 4 || n > DIGAT_MAX_NODES) return DIGAT_ERR_SHAPE;
+    if (d % 4 || n > DIGAT_MAX_NODES || gat_agg_route(B, n, d).status) return DIGAT_ERR_SHAPE;      // what the forward refuses
     hipStream_t st = (hipStream_t)stream;
     if (B == 0) return zero_floats(st, {{dW, (size_t)d * d}, {dbW, (size_t)d}, {da1, (size_t)d}, {da2, (size_t)d}});
     Arena sa(const_cast<void*>(save), save_bytes), w(workspace, workspace_bytes);

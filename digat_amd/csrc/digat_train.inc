@@ -1182,9 +1182,11 @@ __global__ void __launch_bounds__(256) click_loss_kernel(const float* logits, in
         for (int k = 1; k < K; ++k) m = fmaxf(m, row[k]);
         float z = 0.f;
         for (int k = 0; k < K; ++k) z += expf(row[k] - m);
-        const float lse = m + logf(z);
-        mine += lse - row[0];
-        for (int k = 0; k < K; ++k) dlogits[(long)b * K + k] = (expf(row[k] - lse) - (k == 0 ? 1.f : 0.f)) / (float)B;
+        // log_softmax as (x - m) - log z: m + log z would round at the size of the largest logit (half an ulp of 100 is 4e-6, of a
+        // loss of about 1), the differences from the maximum do not
+        const float lz = logf(z);
+        mine += lz - (row[0] - m);
+        for (int k = 0; k < K; ++k) dlogits[(long)b * K + k] = (expf((row[k] - m) - lz) - (k == 0 ? 1.f : 0.f)) / (float)B;
     }
     red[threadIdx.x] = mine;
     __syncthreads();

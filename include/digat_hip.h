@@ -1110,7 +1110,8 @@ int digat_segment_sums_f64(const double* values, int64_t rows, int columns, cons
 /* ---- vanilla-GAT update layer of the ablation encoders -----------------------------------------
  * graphEncoders.py:493-519 (wo_interaction), :641-651 (News_graph_wo_inter), :788-798 (User_graph_wo_inter), eval mode:
  * h = X W^T + bW; e_ij = leaky_relu_0.2(a1.h_j + a2.h_i); -1e9 where A_ij = 0; alpha = softmax_j; out = relu(alpha h) + X.
- * X, out [B,n,d]; A [B,n,n] bytes; W [d,d], bW [d] or NULL, a1, a2 [d]. */
+ * X, out [B,n,d]; A [B,n,n] bytes; W [d,d], bW [d] or NULL, a1, a2 [d].
+ * DIGAT_ERR_SHAPE, before any launch and from all three entries: d % 4 != 0, d > 1024 or n > DIGAT_MAX_NODES. */
 size_t digat_gat_workspace_bytes(int B, int n, int d);
 int digat_gat_fwd(const float* X, const uint8_t* A, const float* W, const float* bW, const float* a1, const float* a2,
                   float* out, int B, int n, int d, void* workspace, size_t workspace_bytes, void* stream);
