@@ -171,7 +171,14 @@ _SIGNATURES = {
     "digat_pl_scores_bwd": (C.c_int, [_f, _f, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int64, _f, _f, _f, _f]),
     "digat_list_pl_bwd": (C.c_int, [_f] * 4 + [C.c_int64, C.c_int64, C.c_int, C.c_int, _f, _f, C.c_int64, C.c_int, C.c_double, _f, _f,
                                     C.c_int64, _f, _f, _f, C.c_size_t, _f]),
-    "digat_bootstrap_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int64]),
+    "digat_list_plrank_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
+    "digat_list_plrank_fwd": (C.c_int, [_f] * 4 + [C.c_int64, C.c_int64, C.c_int, C.c_int] + [_f] * 4 + [C.c_int64, C.c_int, C.c_double, C.c_uint32,
+                                        C.c_int64] + [_f] * 6),
+    "digat_plrank_scores_fwd": (C.c_int, [_f, _f, C.c_int64, C.c_int] + [_f] * 4 + [C.c_int64, C.c_int, C.c_double, C.c_uint32, C.c_int64] + [_f] * 5),
+    "digat_plrank_scores_bwd": (C.c_int, [_f, _f, C.c_int64, C.c_int] + [_f] * 4 + [C.c_int64, C.c_int, C.c_double, _f, _f, _f]),
+    "digat_list_plrank_bwd": (C.c_int, [_f] * 4 + [C.c_int64, C.c_int64, C.c_int, C.c_int] + [_f] * 5 + [C.c_int64, C.c_int, C.c_double, _f, _f,
+                                        C.c_int64, _f, _f, _f, C.c_size_t, _f]),
+    "digat_bootstrap_workspace_bytes":(C.c_size_t, [C.c_int64, C.c_int, C.c_int64]),
     "digat_bootstrap_sums": (C.c_int, [_f, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_uint32, _f, _f, C.c_size_t, _f]),
     "digat_segment_sums_f64": (C.c_int, [_f, C.c_int64, C.c_int, _f, C.c_int64, _f, _f]),
     "digat_gat_workspace_bytes": (C.c_size_t, [C.c_int] * 3),

@@ -966,4 +966,5 @@ int digat_row_logits(const float* news_ctx, const float* user_ctx, float* logits
 #include "digat_pl_sample.inc"
 #include "digat_pl_expect.inc"
 #include "digat_list_pl.inc"
+#include "digat_list_plrank.inc"
 #include "digat_rerank.inc"

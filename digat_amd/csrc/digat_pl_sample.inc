@@ -10,7 +10,8 @@
 //           mapped to an unsigned word that orders as the doubles do (never 0 for a finite key) and stored beside the position.
 //   order   short_bitonic over the next power of two >= M of (key word, position) records, 16 bytes each: key descending, equal
 //           keys by ascending position (shortlist_segment_kernel's tie rule); records that are no live position carry key 0 and
-//           sink to the end.  The slate is the first n_out = min(k, live) records.
+//           sink to the end.  The slate is the first n_out = min(k, live) records.  Keys and order are pl_draw_slate, the ONE
+//           __device__ function this kernel and digat_list_plrank.inc's forward kernels call: the same draw from the same scores.
 //   pl_prob_stage, the probability of a slate in LDS — the ONE __device__ function pl_sample_kernel and pl_log_prob_kernel both
 //           call, on the same LDS image, so digat_pl_log_prob on the sampler's picks returns the sampler's bits:
 //           a_max by a max butterfly (exact in any order); w_p = exp(max(fl(a_p - a_max), -700)) for every position (0: not live);
@@ -190,17 +191,16 @@ __device__ __forceinline__ void pl_prob_stage(PlShared& sh, int k, int n_out, do
     }
 }
 
-__global__ void __launch_bounds__(256) pl_sample_kernel(const PlArgs a) {
-    __shared__ PlShared sh;
-    __shared__ PlRec rec[PL_MAX_M];
+// One Plackett-Luce draw under sh.a: the Gumbel keys of (seed, stream, sample, position) into rec, the live count, short_bitonic, and
+// the slate — the first n_out = min(k, live) records — into sh.pick[0 .. k), -1 from n_out on.  Returns n_out.  The ONE __device__
+// function pl_sample_kernel and digat_list_plrank.inc's forward kernels both call.  The whole workgroup; a thread reads the sh.a slots
+// it stored itself (p = tid + 256 h); ends with sh.pick[tid] written by thread tid alone: a barrier follows in the caller.
+__device__ __forceinline__ int pl_draw_slate(PlShared& sh, PlRec* rec, int M, int k, unsigned seed, unsigned stream, long sample) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long g = a.g0 + blockIdx.x, s = a.s0 + blockIdx.y;
-    pl_stage_list(a, g, sh);
     int n2 = 2;
-    while (n2 < a.M) n2 <<= 1;
-    const unsigned stream = a.streams ? (unsigned)a.streams[g] : (unsigned)g;
-    const unsigned inner = hash32(a.seed + stream);
-    const unsigned low0 = (unsigned)(a.first_sample + s) << 10;
+    while (n2 < M) n2 <<= 1;
+    const unsigned inner = hash32(seed + stream);
+    const unsigned low0 = (unsigned)sample << 10;
     int live = 0;
     for (int p = tid; p < n2; p += 256) {
         const double ap = sh.a[p];                  // this thread's own store
@@ -218,14 +218,22 @@ __global__ void __launch_bounds__(256) pl_sample_kernel(const PlArgs a) {
     if (lane == 0) sh.cut[wave] = live;
     __syncthreads();
     live = sh.cut[0] + sh.cut[1] + sh.cut[2] + sh.cut[3];
-    const int n_out = live < a.k ? live : a.k;
+    const int n_out = live < k ? live : k;
     short_bitonic(rec, n2, [](const PlRec& x, const PlRec& y) { return x.key > y.key || (x.key == y.key && x.pos < y.pos); });
+    if (tid < k) sh.pick[tid] = tid < n_out ? (int)rec[tid].pos : -1;
+    return n_out;
+}
+
+__global__ void __launch_bounds__(256) pl_sample_kernel(const PlArgs a) {
+    __shared__ PlShared sh;
+    __shared__ PlRec rec[PL_MAX_M];
+    const int tid = threadIdx.x;
+    const long g = a.g0 + blockIdx.x, s = a.s0 + blockIdx.y;
+    pl_stage_list(a, g, sh);
+    const unsigned stream = a.streams ? (unsigned)a.streams[g] : (unsigned)g;
+    const int n_out = pl_draw_slate(sh, rec, a.M, a.k, a.seed, stream, a.first_sample + s);
     const size_t row = (size_t)g * (size_t)a.S + (size_t)s;
-    if (tid < a.k) {
-        const int p = tid < n_out ? (int)rec[tid].pos : -1;
-        sh.pick[tid] = p;
-        a.out_picks[row * a.k + tid] = p;
-    }
+    if (tid < a.k) a.out_picks[row * a.k + tid] = sh.pick[tid];
     if (tid == 0 && s == 0) a.out_n[g] = n_out;
     __syncthreads();
     pl_prob_stage(sh, a.k, n_out, a.out_logp + row, a.out_step + row * a.k);

@@ -3409,6 +3409,386 @@ def pl_scores(scores, count, picks, temperature):
     return logp, step.detach()
 
 
+# ---- the PL-Rank policy gradient of a position-weighted metric over a user's own list: csrc/digat_list_plrank.inc ------------------
+def _plrank_discount(discount, k: int) -> np.ndarray:
+    """``discount`` (None: ``ndcg_discount(k)``) as a contiguous float64 numpy [k] table: finite and non-negative."""
+    if discount is None:
+        return ndcg_discount(int(k))
+    D = discount.cpu().numpy() if _is_tensor(discount) else np.asarray(discount)
+    if D.dtype != np.float64 or D.shape != (int(k),):
+        raise ValueError(f"discount must be a float64 table with one value per slate position ({int(k)}), got {D.dtype} {D.shape}")
+    if not np.isfinite(D).all() or (D < 0).any():
+        raise ValueError("discount must be finite and non-negative")
+    return np.ascontiguousarray(D)
+
+
+def _plrank_list_weight(list_weight, G: int) -> np.ndarray:
+    if list_weight is None:
+        return np.ones(G, dtype=np.float64)
+    w = np.ascontiguousarray(_host(list_weight), dtype=np.float64)
+    if w.shape != (G,) or not np.isfinite(w).all():
+        raise ValueError(f"list_weight must hold one finite value per list ({G}), got shape {w.shape}")
+    return w
+
+
+def _plrank_gain_host(gain, shape) -> np.ndarray:
+    """``gain`` as float64 [G, M] through float32: a NaN, an infinity or a negative value counts as 0 (``nrms.slate_ndcg``'s rule)."""
+    g = np.ascontiguousarray(_host(gain), dtype=np.float32)
+    if g.shape != tuple(shape):
+        raise ValueError(f"gain must hold one value per slot {tuple(shape)}, got {g.shape}")
+    with np.errstate(invalid="ignore"):
+        return np.where(np.isfinite(g) & (g > 0), g, np.float32(0)).astype(np.float64)
+
+
+def _plrank_slate_host(a, live, picks, n, rho, theta):
+    """``(c [M], absolute [M], PR_0)`` of one slate of length ``n`` (``_pl_slate_host``'s cut), float64 with ``math.fsum``."""
+    import math
+    M = len(a)
+    c, ab = np.zeros(M), np.zeros(M)
+    if n == 0:
+        return c, ab, 0.0
+    w = np.where(live, np.exp(np.maximum(a - a[live].max(), PL_CLAMP)), 0.0)
+    r = [np.float64(theta[t]) * rho[int(picks[t])] for t in range(n)]
+    PR = [np.float64(math.fsum(r[t:])) for t in range(n + 1)]
+    left = live.copy()
+    qa, qb = [], []
+    A = B = np.float64(0.0)
+    for t in range(n):
+        p = int(picks[t])
+        z = np.float64(math.fsum(w[left].tolist()))
+        qa.append(np.float64(theta[t]) / z)
+        qb.append(PR[t] / z)
+        A, B = np.float64(math.fsum(qa)), np.float64(math.fsum(qb))
+        c[p] = PR[t + 1] + w[p] * (rho[p] * A - B)
+        ab[p] = PR[t + 1] + w[p] * (rho[p] * A + B)
+        left[p] = False
+    c[left] = w[left] * (rho[left] * A - B)
+    ab[left] = w[left] * (rho[left] * A + B)
+    return c, ab, float(PR[0])
+
+
+def plrank_host(scores, ids, count, picks, gain, rows_num, discount=None, list_weight=None, scale=1.0, temperature=1.0, grad_value=None,
+                parts: bool = False):
+    """The contract of ``digat_list_plrank_fwd`` / ``digat_plrank_scores_fwd`` and of their coefficient kernel on given scores
+    ``scores`` [G, M] float32 and GIVEN slates ``picks`` [G, S, k], in numpy float64 with ``math.fsum`` — the yardstick of the kernels.
+    Lists, elements, live positions, ``a``, ``inv_t``, ``w`` and ``Z_t`` are ``list_pl_host``'s (``ids`` None: ``plrank_scores``' rule);
+    a slate is cut by ``pl_log_prob_host``'s rule, and one cut short is the metric truncated at its length.  ``gain`` [G, M] float32
+    (a NaN, an infinity or a negative value counts as 0) is ``rho``, ``discount`` [k] float64 (None: ``ndcg_discount(k)``) is
+    ``theta``, ``list_weight`` [G] float64 (None: 1).  For a slate of length n with picks ``p_0 .. p_{n-1}``: ``r_t = theta_t rho_{p_t}``,
+    ``PR_t = fsum(r[t:])``, ``A_t = fsum(theta_u / Z_u, u < t)``, ``B_t = fsum(PR_u / Z_u, u < t)`` and the PL-Rank-2 coefficient
+
+        ``c(j) = w_j (rho_j A_n - B_n)`` (live, not in the slate), ``c(p_t) = PR_{t+1} + w_{p_t} (rho_{p_t} A_{t+1} - B_{t+1})``, 0 (not live)
+
+    whose mean over the policy's slates is the exact gradient in ``a`` of the expected metric.  Returns ``(value [G], slate_value
+    [G, S])``: ``slate_value = PR_0`` and ``value = list_weight * (fsum_s slate_value / S)`` — the SAMPLE MEAN of the metric; with
+    ``grad_value`` [G] also ``coef`` [G, M] = ``((inv_t * list_weight) * grad_value) * (fsum_s c_s(j) / S)``, the ESTIMATOR of the
+    gradient of the expected metric, not the derivative of that sample mean; an empty slate adds nothing and counts in S.
+    ``parts`` adds a dict: ``live`` [G], ``length`` [G, S], ``terms`` [G, S, M] (``c_s(j)``) and, with ``grad_value``, ``absolute``
+    [G, M] = ``|f| fsum_s(PR_{t+1} + w_j (rho_j A + B)) / S``, what ``plrank_bound`` takes."""
+    import math
+    inv_t = _pl_inv_t(scale, temperature)
+    sc, live, a, pk, k = _list_pl_host_parts(scores, ids, count, picks, rows_num, inv_t)
+    G, M = sc.shape
+    S = int(pk.shape[1])
+    rho = _plrank_gain_host(gain, (G, M))
+    theta = _plrank_discount(discount, k)
+    lw = _plrank_list_weight(list_weight, G)
+    gv = None if grad_value is None else np.asarray(_host(grad_value), dtype=np.float64)
+    if gv is not None and gv.shape != (G,):
+        raise ValueError(f"grad_value must have one entry per list ({G}), got {gv.shape}")
+    length = np.zeros((G, S), dtype=np.int32)
+    slate_value, value = np.zeros((G, S)), np.zeros(G)
+    terms, aterms = np.zeros((G, S, M)), np.zeros((G, S, M))
+    coef, absolute = np.zeros((G, M)), np.zeros((G, M))
+    for g in range(G):
+        for s in range(S):
+            length[g, s] = _pl_slate_host(a[g], live[g], pk[g, s], k)[3]
+            terms[g, s], aterms[g, s], slate_value[g, s] = _plrank_slate_host(a[g], live[g], pk[g, s], int(length[g, s]), rho[g], theta)
+        value[g] = lw[g] * (np.float64(math.fsum(slate_value[g].tolist())) / np.float64(S))
+        if gv is not None and gv[g] != 0.0:
+            f = (np.float64(inv_t) * lw[g]) * gv[g]
+            coef[g] = [f * (np.float64(math.fsum(col)) / np.float64(S)) for col in terms[g].T.tolist()]
+            absolute[g] = [abs(f) * (np.float64(math.fsum(col)) / np.float64(S)) for col in aterms[g].T.tolist()]
+    out = (value, slate_value) + (() if gv is None else (np.where(live, coef, 0.0),))
+    if parts:
+        d = {"live": live.sum(axis=1), "length": length, "terms": terms}
+        if gv is not None:
+            d["absolute"] = np.where(live, absolute, 0.0)
+        out += (d,)
+    return out
+
+
+def plrank_grad_host(users, rows, scores, ids, count, picks, gain, discount=None, list_weight=None, scale=1.0, temperature=1.0,
+                     grad_value=None):
+    """The contract of ``digat_list_plrank_bwd`` in numpy float64: with ``coef`` of ``plrank_host`` on ``scores`` (``grad_value`` None:
+    ones), ``list_pl_grad_host``'s two sums: ``(d_users [G, d], d_rows [P, d])``."""
+    U, R = np.asarray(users, dtype=np.float64), np.asarray(rows, dtype=np.float64)
+    if U.ndim != 2 or R.ndim != 2 or U.shape[1] != R.shape[1]:
+        raise ValueError(f"users [G, d] and rows [P, d] must share d, got {U.shape} and {R.shape}")
+    gv = np.ones(U.shape[0]) if grad_value is None else grad_value
+    coef = plrank_host(scores, ids, count, picks, gain, R.shape[0], discount, list_weight, scale, temperature, grad_value=gv)[2]
+    I = np.asarray(_host(ids)).astype(np.int64)
+    g_of, j_of = np.nonzero(coef != 0)
+    d_users, d_rows = np.zeros_like(U), np.zeros_like(R)
+    np.add.at(d_users, g_of, coef[g_of, j_of][:, None] * R[I[g_of, j_of]])
+    np.add.at(d_rows, I[g_of, j_of], coef[g_of, j_of][:, None] * U[g_of])
+    return d_users, d_rows
+
+
+def plrank_bound(n, k, samples, coef=None, absolute=None, value=None):
+    """The error bounds csrc/digat_list_plrank.inc derives against ``plrank_host`` on the same scores and picks.  With ``coef`` and
+    ``absolute`` [G, M] (the twin's coefficient and the ``absolute`` of its parts), ``n`` [G] the live positions of the list, ``k``
+    the slate length and ``S`` the slates per list: ``2^-24 |coef| + (n + 2 k + S + 24) 2^-53 A + 2^-149`` — the float32 rounding
+    leads; ``rho_j A - B`` cancels, so the float64 terms are relative to the ABSOLUTE sum.  With ``value`` (``value`` [G] or
+    ``slate_value`` [G, S]): ``(k + S + 6) 2^-53 |value|``, the order of at most k + S positive additions."""
+    if value is not None:
+        return (float(k) + float(samples) + 6.0) * 2.0 ** -53 * np.abs(np.asarray(value, dtype=np.float64))
+    c = np.abs(np.asarray(coef, dtype=np.float64))
+    A = np.abs(np.asarray(absolute, dtype=np.float64))
+    n = np.asarray(n, dtype=np.float64).reshape(-1, 1)
+    return 2.0 ** -24 * c + (n + 2.0 * float(k) + float(samples) + 24.0) * 2.0 ** -53 * A + 2.0 ** -149
+
+
+def _pl_draw_host(sc, count, inv_t, k, seed, samples, first_sample, streams):
+    """``pl_sample_host``'s picks [G, S, k] int32 under a given ``inv_t`` (at ``inv_t = 1 / temperature`` they are its picks): the
+    draw ``list_plrank`` makes inside its kernel."""
+    sc, live, a = _pl_lists_host(sc, count, inv_t)
+    (G, M), k, S = sc.shape, int(k), int(samples)
+    words = pl_draws_host(_check_streams_host(streams, G), S, M, seed, first_sample)
+    with np.errstate(divide="ignore"):
+        key = a[:, None, :] + -np.log(-np.log((words.astype(np.float64) + 0.5) * 2.0 ** -32))
+    picks = np.full((G, S, k), -1, dtype=np.int32)
+    for g in range(G):
+        pos = np.flatnonzero(live[g])
+        n = min(len(pos), k)
+        for s in range(S):
+            picks[g, s, :n] = pos[np.argsort(-key[g, s, pos], kind="stable")[:n]]
+    return picks
+
+
+def _plrank_functions():
+    import torch
+    from . import _lib
+
+    class ListPLRank(torch.autograd.Function):
+        """``digat_list_plrank_fwd`` / ``_bwd``; the scores and the slates are saved, the sorted entry keys of the rows kernel are built
+        in the forward.  ``out_picks`` is filled in place when the slates are drawn (``picks`` None)."""
+
+        @staticmethod
+        def forward(ctx, users, rows, ids, cnt, gain, disc, lw, picks, out_picks, S, k, inv_t, seed, first_sample, streams):
+            u, v = users.detach().float().contiguous(), rows.detach().float().contiguous()
+            G, M, P, d = int(u.shape[0]), int(ids.shape[1]), int(v.shape[0]), int(u.shape[1])
+            value = torch.empty((G,), dtype=torch.float64, device=u.device)
+            slate_value = torch.empty((G, S), dtype=torch.float64, device=u.device)
+            scores = torch.empty((G, M), dtype=torch.float32, device=u.device)
+            _lib.check(_lib.lib().digat_list_plrank_fwd(u.data_ptr(), v.data_ptr(), ids.data_ptr(), _lib.ptr(cnt), G, P, M, d, gain.data_ptr(),
+                                                        disc.data_ptr(), _lib.ptr(lw), _lib.ptr(picks), S, k, inv_t, seed, first_sample,
+                                                        _lib.ptr(streams), _lib.ptr(out_picks), slate_value.data_ptr(), value.data_ptr(),
+                                                        scores.data_ptr(), _lib.stream_ptr()), "digat_list_plrank_fwd")
+            keys = None
+            if ctx.needs_input_grad[1]:
+                elem = list_elements(ids, cnt, P).view(-1)
+                flat = torch.arange(G * M, device=u.device)
+                keys = torch.sort(ids.view(-1)[elem] * (G * M) + flat[elem]).values.contiguous()
+            ctx.save_for_backward(u, v, ids, out_picks if picks is None else picks, scores, gain, disc)
+            ctx.cnt, ctx.lw, ctx.keys, ctx.inv_t, ctx.dtypes = cnt, lw, keys, inv_t, (users.dtype, rows.dtype)
+            ctx.mark_non_differentiable(slate_value, scores)
+            return value, slate_value, scores
+
+        @staticmethod
+        def backward(ctx, grad_value, _sv, _scores):
+            u, v, ids, picks, scores, gain, disc = ctx.saved_tensors
+            G, d, P, M = int(u.shape[0]), int(u.shape[1]), int(v.shape[0]), int(ids.shape[1])
+            f = dict(dtype=torch.float32, device=u.device)
+            want_rows = ctx.needs_input_grad[1] and ctx.keys is not None
+            d_users = torch.empty((G, d), **f)
+            d_rows = torch.empty((P, d), **f) if want_rows else None
+            gv = grad_value.to(torch.float64).contiguous()
+            L = _lib.lib()
+            need = int(L.digat_list_plrank_workspace_bytes(G, M))
+            ws = _lib.workspace(need, u.device, "list_pl")
+            keys = ctx.keys if want_rows else None
+            _lib.check(L.digat_list_plrank_bwd(u.data_ptr(), v.data_ptr(), ids.data_ptr(), _lib.ptr(ctx.cnt), G, P, M, d, scores.data_ptr(),
+                                               gain.data_ptr(), disc.data_ptr(), _lib.ptr(ctx.lw), picks.data_ptr(), int(picks.shape[1]),
+                                               int(picks.shape[2]), ctx.inv_t, gv.data_ptr(),
+                                               _lib.ptr(keys) if keys is not None and keys.numel() else None,
+                                               0 if keys is None else int(keys.numel()), d_users.data_ptr(), _lib.ptr(d_rows), ws.data_ptr(),
+                                               need, _lib.stream_ptr()), "digat_list_plrank_bwd")
+            return ((d_users.to(ctx.dtypes[0]) if ctx.needs_input_grad[0] else None), (None if d_rows is None else d_rows.to(ctx.dtypes[1]))) \
+                + (None,) * 13
+
+    class PLRankScores(torch.autograd.Function):
+        """``digat_plrank_scores_fwd``; the backward is the coefficient kernel alone (``digat_plrank_scores_bwd``)."""
+
+        @staticmethod
+        def forward(ctx, scores, cnt, gain, disc, lw, picks, out_picks, S, k, inv_t, seed, first_sample, streams):
+            sc = scores.detach().float().contiguous()
+            G, M = int(sc.shape[0]), int(sc.shape[1])
+            value = torch.empty((G,), dtype=torch.float64, device=sc.device)
+            slate_value = torch.empty((G, S), dtype=torch.float64, device=sc.device)
+            _lib.check(_lib.lib().digat_plrank_scores_fwd(sc.data_ptr(), _lib.ptr(cnt), G, M, gain.data_ptr(), disc.data_ptr(), _lib.ptr(lw),
+                                                          _lib.ptr(picks), S, k, inv_t, seed, first_sample, _lib.ptr(streams), _lib.ptr(out_picks),
+                                                          slate_value.data_ptr(), value.data_ptr(), _lib.stream_ptr()), "digat_plrank_scores_fwd")
+            ctx.save_for_backward(sc, out_picks if picks is None else picks, gain, disc)
+            ctx.cnt, ctx.lw, ctx.inv_t, ctx.dtype = cnt, lw, inv_t, scores.dtype
+            ctx.mark_non_differentiable(slate_value)
+            return value, slate_value
+
+        @staticmethod
+        def backward(ctx, grad_value, _sv):
+            sc, picks, gain, disc = ctx.saved_tensors
+            G, M = int(sc.shape[0]), int(sc.shape[1])
+            grad = torch.empty((G, M), dtype=torch.float32, device=sc.device)
+            gv = grad_value.to(torch.float64).contiguous()
+            _lib.check(_lib.lib().digat_plrank_scores_bwd(sc.data_ptr(), _lib.ptr(ctx.cnt), G, M, gain.data_ptr(), disc.data_ptr(), _lib.ptr(ctx.lw),
+                                                          picks.data_ptr(), int(picks.shape[1]), int(picks.shape[2]), ctx.inv_t, gv.data_ptr(),
+                                                          grad.data_ptr(), _lib.stream_ptr()), "digat_plrank_scores_bwd")
+            return (grad.to(ctx.dtype),) + (None,) * 12
+
+    return ListPLRank, PLRankScores
+
+
+_ListPLRank = None
+
+
+def _plrank_args(G, M, dev, gain, k, samples, discount, list_weight, scale, temperature, first_sample, streams, picks):
+    """The checks ``list_plrank`` and ``plrank_scores`` share: ``(k, S, inv_t, theta numpy [k], list_weight numpy [G] or None)``."""
+    import torch
+    inv_t = _pl_inv_t(scale, temperature)
+    if picks is not None:
+        S, kk = _check_picks(picks, G)
+        if int(k) != kk:
+            raise ValueError(f"picks must hold slates of k = {int(k)} positions, got {tuple(picks.shape)}")
+    else:
+        S = int(samples)
+    _check_pl_args((G, M), None, k, 1.0, S, first_sample, None if streams is None else tuple(streams.shape))
+    if not torch.is_tensor(gain) or not gain.is_floating_point() or tuple(gain.shape) != (G, M):
+        raise ValueError(f"gain must be a floating-point tensor with one value per slot {(G, M)}")
+    given = [t for t in (gain, streams, picks) if t is not None]
+    if any(t.device != dev for t in given):
+        raise ValueError("users, rows, ids, count, gain, streams and picks must live on one device")
+    return int(k), S, inv_t, _plrank_discount(discount, k), None if list_weight is None else _plrank_list_weight(list_weight, G)
+
+
+def _plrank_cpu(Sc, live, cnt, gain, k, S, theta, lw, scale, temperature, inv_t, seed, first_sample, streams, picks):
+    """The CPU branch on differentiable scores ``Sc`` [G, M] (0 where not live): the slates by ``_pl_draw_host``, the coefficient from
+    ``plrank_host`` on the detached scores, and ``value`` with the surrogate ``sum_j coef_j score_j`` attached so that autograd carries
+    the estimator."""
+    import torch
+    G, M = int(Sc.shape[0]), int(Sc.shape[1])
+    sc32 = np.where(live.numpy(), Sc.detach().to(torch.float32).numpy(), np.float32("nan"))
+    cn = None if cnt is None else cnt.numpy()
+    if picks is None:
+        pk = _pl_draw_host(sc32, cn, inv_t, k, seed, S, first_sample, None if streams is None else streams.numpy())
+    else:
+        pk = np.clip(picks.numpy(), -1, PL_MAX_LIST).astype(np.int32)
+    value, slate_value, coef = plrank_host(sc32, None, cn, pk, gain.detach().numpy(), 0, theta, lw, scale, temperature, grad_value=np.ones(G))
+    sur = (torch.from_numpy(coef).to(Sc.dtype) * Sc).sum(dim=1).to(torch.float64)
+    return torch.from_numpy(value) + (sur - sur.detach()), torch.from_numpy(slate_value), torch.from_numpy(pk)
+
+
+def list_plrank(users, rows, ids, count, gain, k, samples=1, discount=None, list_weight=None, scale=1.0, temperature=1.0, seed=0,
+                first_sample=0, streams=None, picks=None):
+    """The PL-Rank policy gradient of a position-weighted metric under the Plackett-Luce policy of every user's OWN list, in one pass:
+    ``(value [G] float64, slate_value [G, S] float64, picks [G, S, k] int32, scores [G, M] float32)``.  ``users``, ``rows``, ``ids``
+    and ``count`` are ``list_pl``'s, with its elements, live positions and ``inv_t``.  The metric of a slate is ``sum_t discount[t]
+    gain[g, picks[t]]``: ``gain`` [G, M] floating point (read as float32; a NaN, an infinity or a negative value counts as 0),
+    ``discount`` [k] float64 (None: ``ndcg_discount(k)``, DCG@k), ``list_weight`` [G] (None: 1; ``1 / IDCG@k`` makes it nDCG@k).
+    With ``picks`` None, ``samples`` slates of ``k`` are DRAWN per list from ``softmax(scale * <user, news> / temperature)`` without
+    replacement inside the kernel that scored the list — ``pl_sample``'s draw exactly (seed, ``streams`` [G], ``first_sample + s``,
+    the Gumbel key, the tie rule, ``min(k, live)`` entries, -1 behind them): at ``scale = 1`` they are ``pl_sample``'s picks on the
+    returned scores — and returned.  With ``picks`` [G, S, k] given, every slate is cut by ``pl_log_prob``'s rule; one cut short is the
+    metric truncated at its length; they come back as int32, a position outside the list held at -1 or ``PL_MAX_LIST`` (the same cut).  ``slate_value`` is the metric of every slate and ``value = list_weight * mean_s slate_value``.
+
+    Only ``value`` is differentiable, and only in ``users`` and ``rows``.  ``value`` is the SAMPLE MEAN of the metric; its backward is
+    the PL-Rank-2 ESTIMATOR of the gradient of the EXPECTED metric (``plrank_host``: every position is credited with the reward that
+    comes after it, an item's own reward enters through its conditional expectation; no baseline) — not the derivative of that sample
+    mean, which is zero.  O(M + k) per slate, no [G, S, M] tensor, ``a_max`` and the clamp at -700 held constant.
+
+    On CUDA tensors: ``digat_list_plrank_fwd`` / ``_bwd`` — one scoring pass, no float atomics: two calls give the same bits.  On CPU
+    tensors: ``index_select`` + ``bmm`` scores, the slates of ``pl_sample_host``'s draw, the coefficient from ``plrank_host`` on the
+    detached scores and ``value`` with the surrogate ``sum_j coef_j score_j`` attached, so that autograd carries the same gradient."""
+    import torch
+    global _ListPLRank
+    cnt = None if count is None else torch.as_tensor(count)
+    if users.dim() != 2 or ids.dim() != 2 or not users.is_floating_point() or not rows.is_floating_point():
+        raise ValueError(f"users [G, d] and rows [P, d] must be floating-point matrices and ids [G, M], got {tuple(users.shape)} {users.dtype}, "
+                         f"{tuple(rows.shape)} {rows.dtype} and {tuple(ids.shape)}")
+    G, P, M, d = _check_list_args(users, rows, ids, cnt, "list_plrank")
+    dev = users.device
+    if any(t.device != dev for t in (rows, ids) + (() if cnt is None else (cnt,))):
+        raise ValueError("users, rows, ids, count, gain, streams and picks must live on one device")
+    k, S, inv_t, theta, lw = _plrank_args(G, M, dev, gain, k, samples, discount, list_weight, scale, temperature, first_sample, streams, picks)
+    ids = ids.to(torch.int64).contiguous()
+    if dev.type == "cuda":
+        if _ListPLRank is None:
+            _ListPLRank = _plrank_functions()
+        pk = None if picks is None else torch.clamp(picks, min=-1, max=PL_MAX_LIST).to(torch.int32).contiguous()
+        if G == 0 or P == 0:                                          # nothing is live: every slate is empty, no launch, a zero gradient
+            z = torch.zeros((G,), dtype=torch.float64, device=dev) + 0.0 * (users.double().sum() + rows.double().sum())
+            return z, torch.zeros((G, S), dtype=torch.float64, device=dev), \
+                (torch.full((G, S, k), -1, dtype=torch.int32, device=dev) if pk is None else pk), \
+                users.new_full((G, M), float("nan"), dtype=torch.float32)
+        out = torch.empty((G, S, k), dtype=torch.int32, device=dev) if pk is None else None
+        value, slate_value, scores = _ListPLRank[0].apply(
+            users, rows, ids, None if cnt is None else cnt.to(torch.int32).contiguous(), gain.detach().to(torch.float32).contiguous(),
+            _device_discount(theta, dev), None if lw is None else torch.from_numpy(lw).to(dev), pk, out, S, k, inv_t, int(seed) & 0xFFFFFFFF,
+            int(first_sample), None if streams is None else streams.to(torch.int64).contiguous())
+        return value, slate_value, (out if pk is None else pk), scores
+    elem = list_elements(ids, cnt, P)
+    safe = torch.where(elem, ids, torch.zeros_like(ids)).view(-1)
+    if P == 0:
+        Sc = users.new_zeros((G, M)) + 0.0 * (users.sum() + rows.sum())
+    else:
+        gathered = rows.index_select(0, safe).view(G, M, d)                                              # [G, M, d]
+        Sc = torch.bmm(gathered, users.unsqueeze(2)).squeeze(2)
+    shown = torch.where(elem, Sc.detach(), Sc.new_full((G, M), float("nan")))
+    live = elem & torch.isfinite(Sc.detach()) & torch.isfinite(Sc.detach().to(torch.float32))
+    if P > 0 and not bool(live.all()):                                # a row without mass must not meet the backward: 0 * inf is a NaN
+        Sc = torch.bmm(torch.where(live[:, :, None], gathered, torch.zeros_like(gathered)), users.unsqueeze(2)).squeeze(2)
+    value, slate_value, pk = _plrank_cpu(Sc, live, cnt, gain, k, S, theta, lw, scale, temperature, inv_t, seed, first_sample, streams, picks)
+    return value, slate_value, pk, shown
+
+
+def plrank_scores(scores, count, gain, k, samples=1, discount=None, list_weight=None, temperature=1.0, seed=0, first_sample=0, streams=None,
+                  picks=None):
+    """``list_plrank`` on GIVEN scores ``scores`` [G, M] — a model whose score is no inner product, through autograd on its own logits,
+    and the use without a graph: ``(value [G] float64, slate_value [G, S] float64, picks [G, S, k] int32)``.  A position is live when
+    ``j < clip(count[g], 0, M)`` (``count`` None: M) and its score is finite; ``inv_t = 1 / temperature``.  ``value`` is differentiable
+    in ``scores``: the gradient is ``plrank_host``'s coefficient — the PL-Rank-2 estimator of the gradient of the EXPECTED metric, not
+    the derivative of the sample mean ``value`` holds —, exactly 0 at every position that is not live.  On CUDA tensors
+    ``digat_plrank_scores_fwd`` / ``_bwd`` read float32 (the coefficient kernel of ``list_plrank``: the same bits on the same scores and
+    slates); on CPU tensors the host twin with the surrogate attached."""
+    import torch
+    global _ListPLRank
+    if scores.dim() != 2 or not scores.is_floating_point():
+        raise ValueError(f"scores must be a floating-point tensor [G, M], got {tuple(scores.shape)} {scores.dtype}")
+    cnt = None if count is None else torch.as_tensor(count)
+    G, M = int(scores.shape[0]), int(scores.shape[1])
+    dev = scores.device
+    if cnt is not None and (cnt.device != dev or tuple(cnt.shape) != (G,)):
+        raise ValueError(f"count must hold one entry per list ({G}) on the scores' device")
+    k, S, inv_t, theta, lw = _plrank_args(G, M, dev, gain, k, samples, discount, list_weight, 1.0, temperature, first_sample, streams, picks)
+    if dev.type == "cuda":
+        if _ListPLRank is None:
+            _ListPLRank = _plrank_functions()
+        pk = None if picks is None else torch.clamp(picks, min=-1, max=PL_MAX_LIST).to(torch.int32).contiguous()
+        if G == 0:
+            return torch.zeros((0,), dtype=torch.float64, device=dev) + 0.0 * scores.double().sum(), \
+                torch.zeros((0, S), dtype=torch.float64, device=dev), torch.zeros((0, S, k), dtype=torch.int32, device=dev)
+        out = torch.empty((G, S, k), dtype=torch.int32, device=dev) if pk is None else None
+        value, slate_value = _ListPLRank[1].apply(
+            scores, None if cnt is None else cnt.to(torch.int32).contiguous(), gain.detach().to(torch.float32).contiguous(),
+            _device_discount(theta, dev), None if lw is None else torch.from_numpy(lw).to(dev), pk, out, S, k, inv_t, int(seed) & 0xFFFFFFFF,
+            int(first_sample), None if streams is None else streams.to(torch.int64).contiguous())
+        return value, slate_value, (out if pk is None else pk)
+    live = torch.isfinite(scores.detach()) & torch.isfinite(scores.detach().to(torch.float32))
+    if cnt is not None:
+        live = live & (torch.arange(M)[None, :] < cnt.to(torch.int64).clamp(0, M)[:, None])
+    return _plrank_cpu(torch.where(live, scores, torch.zeros_like(scores)), live, cnt, gain, k, S, theta, lw, 1.0, temperature, inv_t, seed,
+                       first_sample, streams, picks)
+
+
 def off_policy_value(reward, logp_target, logp_logging, clip=None, units=None, replicates: int = 2000, level: float = 0.95, seed: int = 0):
     """What a target policy would have earned on a log made by another: one row per logged slate, ``reward`` [n], ``logp_target`` /
     ``logp_logging`` [n] the slate's log-probability under either policy (``pl_log_prob`` / ``pl_sample``), weights ``exp(logp_target

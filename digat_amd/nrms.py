@@ -1238,8 +1238,43 @@ def slate_ndcg(gain, picks, k: int):
     return torch.where(idcg[:, None] > 0, dcg / idcg.clamp(min=1e-300)[:, None], torch.zeros_like(dcg))
 
 
-def fit_policy(model, train, lists, steps, k=10, samples=4, temperature=1.0, batch_users=64, lr=1e-4, seed=0, scale=1.0, optimizer=None):
-    """On-policy REINFORCE on the expected nDCG@k of a sampled slate: ``steps`` times, on the same seeded draw of ``batch_users``
+def plrank_step(model, train, users, ids, gain, count=None, k=10, samples=4, scale=1.0, temperature=1.0, seed=0, first_sample=0):
+    """One PL-Rank step's loss for the first stage, with its graph — ``rank_step``'s twin on ``evaluate.list_plrank``, in ONE scoring
+    pass: a single ``_list_front`` call with the graph scores the batch's lists; ``samples`` Plackett-Luce slates of ``k`` are drawn
+    per list from ``softmax(scale * <user, news> / temperature)`` inside the kernel that scored them (the impression indices
+    ``users`` are the streams, ``first_sample`` the first sample index: ``pl_sample``'s draw); a slate's value is its DCG@k against
+    ``gain`` [G, M] (``slate_ndcg``'s rule for NaN, infinite and negative gains) and ``list_weight = 1 / IDCG@k`` (0 where that is 0)
+    makes it nDCG@k.  The loss is minus the mean of ``value`` over the lists with a positive ideal DCG (divided by 1 when there is
+    none).  ``value`` is the sample mean of the slates' nDCG@k; its backward is the PL-Rank-2 estimator of the gradient of the
+    EXPECTED nDCG@k — no baseline, no second encoder pass, no second dropout mask, no id-to-position matching.  Returns ``(loss,
+    mean slate nDCG@k)``, the second a detached scalar over all lists and slates, as ``fit_policy`` reports its rewards.  The compact
+    pool, the encoders and the devices are ``distil_step``'s; the model's mode (dropout) is the caller's."""
+    from . import evaluate
+    idx, ids, gain, count = _check_lists(users, ids, gain, count, int(train.history_ids.shape[0]))
+    user, table, pos, cnt, _ = _list_front(model, train, idx, ids, count)
+    dev = user.device
+    k = int(k)
+    D = evaluate.ndcg_discount(k)
+    with np.errstate(invalid="ignore"):
+        clean = np.where(np.isfinite(gain) & (gain > 0), gain, np.float32(0)).astype(np.float64)
+    top = -np.sort(-clean, axis=1)[:, :k]
+    idcg = (top * D[:top.shape[1]]).sum(axis=1)
+    lw = np.where(idcg > 0, 1.0 / np.where(idcg > 0, idcg, 1.0), 0.0)
+    gn = torch.from_numpy(gain).to(dev)
+    value, slate_value, _, _ = evaluate.list_plrank(user, table, pos, cnt, gn if dev.type == "cuda" else gn.to(user.dtype), k, samples, D, lw,
+                                                    scale=scale, temperature=temperature, seed=seed, first_sample=first_sample,
+                                                    streams=torch.from_numpy(idx).to(dev))
+    reward = (slate_value * torch.from_numpy(lw).to(dev)[:, None]).mean()
+    return -value.sum() / max(int((idcg > 0).sum()), 1), reward.detach()
+
+
+def fit_policy(model, train, lists, steps, k=10, samples=4, temperature=1.0, batch_users=64, lr=1e-4, seed=0, scale=1.0, optimizer=None,
+               estimator="reinforce"):
+    """``estimator="plrank"``: the same seeded batches, one ``plrank_step`` a step with ``first_sample = step * samples`` — one scoring
+    pass, the PL-Rank-2 estimator in place of REINFORCE with a leave-one-out baseline; any other value but ``"reinforce"`` is a
+    ``ValueError``.  ``"reinforce"`` (the default), as it always was:
+
+    On-policy REINFORCE on the expected nDCG@k of a sampled slate: ``steps`` times, on the same seeded draw of ``batch_users``
     lists as ``fit_ranker`` and ``distil_retriever`` make, (1) the batch's lists are scored without a graph (``list_softmax``'s
     forward), (2) ``samples`` Plackett-Luce slates of ``k`` are drawn per list from ``softmax(scale * score / temperature)``
     (``evaluate.pl_sample`` with the impression index as stream and ``first_sample = step * samples``; CPU tensors:
@@ -1256,6 +1291,8 @@ def fit_policy(model, train, lists, steps, k=10, samples=4, temperature=1.0, bat
     users, ids, gain, count = _check_lists(*lists[:3], lists[3], int(train.history_ids.shape[0]))
     if len(users) == 0:
         raise ValueError("no list to train on")
+    if estimator not in ("reinforce", "plrank"):
+        raise ValueError(f"estimator must be 'reinforce' or 'plrank', got {estimator!r}")
     k, samples = int(k), int(samples)
     evaluate._check_pl_args((1, ids.shape[1]), None, k, float(temperature) / float(scale), samples, max(int(steps) - 1, 0) * samples)
     optimizer = _retriever_optimizer(model, lr, optimizer)
@@ -1264,6 +1301,15 @@ def fit_policy(model, train, lists, steps, k=10, samples=4, temperature=1.0, bat
     losses, rewards = [], []
     for step in range(int(steps)):
         b = np.sort(rng.choice(len(users), size=min(int(batch_users), len(users)), replace=False))
+        if estimator == "plrank":
+            optimizer.zero_grad()
+            loss, r = plrank_step(model, train, users[b], ids[b], gain[b], count[b], k=k, samples=samples, scale=scale, temperature=temperature,
+                                  seed=seed, first_sample=step * samples)
+            loss.backward()
+            optimizer.step()
+            losses.append(float(loss.detach()))
+            rewards.append(float(r))
+            continue
         scores, cnt = _list_scores(model, train, users[b], ids[b], count[b])
         dev = scores.device
         if dev.type == "cuda":

@@ -1043,6 +1043,50 @@ int digat_list_pl_bwd(const float* users, const float* rows, const int64_t* ids,
                       const int64_t* entry_keys, int64_t E, float* d_users, float* d_rows, void* workspace, size_t workspace_bytes,
                       void* stream);
 
+/* ---- PL-Rank policy gradient of a position-weighted metric over a user's own list (digat_amd.evaluate.list_plrank / plrank_scores) --
+ * Lists, elements, live positions, inv_t, a_j = (double)score_j * inv_t, w_j and Z_t are digat_list_pl_fwd's above, under its limits.
+ * gain [G, M] f32: rho_j, a NaN, an infinity or a negative value counting as 0; discount [k] f64: theta_t, finite and >= 0;
+ * list_weight [G] f64 (NULL: 1).  picks [G, samples, k] int32 GIVEN: every slate is cut by digat_pl_log_prob's rule (a slate cut short
+ * is the metric truncated at its length; out_picks is not written and may be NULL).  picks NULL (the two forwards only): slate s of
+ * list g is DRAWN as digat_pl_sample draws it — the same device function: the hash of (seed, stream, first_sample + s, position), the
+ * Gumbel key, the order, the tie rule, n_out = min(k, live) — from the scores inside the kernel that formed them, and written to
+ * out_picks [G, samples, k] (-1 from n_out on); streams [G] int64 (NULL: g), first_sample + samples <= DIGAT_PL_MAX_SAMPLE.
+ * For a slate of length n with picks p_0 .. p_{n-1}: r_t = theta_t rho_{p_t}, PR_t = sum_{x >= t} r_x (PR_n = 0),
+ * A_t = sum_{u < t} theta_u / Z_u, B_t = sum_{u < t} PR_u / Z_u, and, a_max and the clamp held constant,
+ *   c(j) = w_j (rho_j A_n - B_n) (j live, not in the slate);  c(p_t) = PR_{t+1} + w_{p_t} (rho_{p_t} A_{t+1} - B_{t+1});  0 (j not live):
+ * the PL-Rank-2 estimator — its mean over the policy's slates is the exact gradient in a of the EXPECTED metric sum_t theta_t rho_{y_t}.
+ *   out_slate_value [G, samples] f64 = PR_0;   out_value [G] f64 = list_weight[g] * (sum_s out_slate_value[g, s]) / samples;
+ *   coef [G, M] f32 = fl32(inv_t * list_weight[g] * grad_value[g] * (sum_s c_s(j)) / samples), exactly 0 at every slot that is not live.
+ * An empty slate adds nothing and still counts in samples; a list whose grad_value is 0 gets zeros.  out_value is the sample mean of
+ * the metric; coef is the ESTIMATOR of the gradient of its expectation, not the derivative of that sample mean.
+ * digat_list_plrank_fwd scores the lists (out_scores [G, M] f32 as digat_list_pl_fwd writes them) and runs the slates in the same
+ * workgroup; digat_plrank_scores_fwd is the same from GIVEN scores [G, M] f32; digat_plrank_scores_bwd writes coef [G, M] alone;
+ * digat_list_plrank_bwd writes coef into the workspace (digat_list_plrank_workspace_bytes) and forms digat_list_softmax_bwd's two sums
+ * d_users and d_rows (may be NULL) from it, with its kernels and entry_keys — digat_list_pl_bwd's chain.
+ * One workgroup per list runs its slates in ascending order: no floating-point atomics, the same bits from run to run and for a list
+ * alone or in a batch; out_picks and out_slate_value also from a call split by first_sample.  Against evaluate.plrank_host coef,
+ * out_slate_value and out_value stay within evaluate.plrank_bound (derived in csrc/digat_list_plrank.inc).
+ * Errors as digat_list_pl_fwd / _bwd, with gain, discount (8 bytes), list_weight (8), streams (8), out_slate_value (8), out_value (8)
+ * and grad_value (8) among the pointers; a forward with neither picks nor out_picks is DIGAT_ERR_ARG; first_sample < 0 or
+ * first_sample + samples > DIGAT_PL_MAX_SAMPLE is DIGAT_ERR_SHAPE — all before any launch.  G == 0 returns DIGAT_OK without a list
+ * launch.  Stream-ordered; no allocation, no host synchronisation. */
+size_t digat_list_plrank_workspace_bytes(int64_t lists, int m);
+int digat_list_plrank_fwd(const float* users, const float* rows, const int64_t* ids, const int32_t* count, int64_t G, int64_t P, int M, int d,
+                          const float* gain, const double* discount, const double* list_weight, const int32_t* picks, int64_t samples, int k,
+                          double inv_t, uint32_t seed, int64_t first_sample, const int64_t* streams, int32_t* out_picks,
+                          double* out_slate_value, double* out_value, float* out_scores, void* stream);
+int digat_plrank_scores_fwd(const float* scores, const int32_t* count, int64_t G, int M, const float* gain, const double* discount,
+                            const double* list_weight, const int32_t* picks, int64_t samples, int k, double inv_t, uint32_t seed,
+                            int64_t first_sample, const int64_t* streams, int32_t* out_picks, double* out_slate_value, double* out_value,
+                            void* stream);
+int digat_plrank_scores_bwd(const float* scores, const int32_t* count, int64_t G, int M, const float* gain, const double* discount,
+                            const double* list_weight, const int32_t* picks, int64_t samples, int k, double inv_t, const double* grad_value,
+                            float* out_grad, void* stream);
+int digat_list_plrank_bwd(const float* users, const float* rows, const int64_t* ids, const int32_t* count, int64_t G, int64_t P, int M, int d,
+                          const float* scores, const float* gain, const double* discount, const double* list_weight, const int32_t* picks,
+                          int64_t samples, int k, double inv_t, const double* grad_value, const int64_t* entry_keys, int64_t E,
+                          float* d_users, float* d_rows, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- joint re-rank: diversity, calibration and a cap per category in one greedy pass (digat_amd.evaluate.rerank_select) ---------
  * Per list g: ids [G, M] int64, scores [G, M] f32, count [G] int32 (NULL: M), 1 <= M <= DIGAT_RERANK_MAX_LIST; vectors [N, d] f32,
  * 1 <= d <= DIGAT_LIST_SOFTMAX_MAX_D (read only when w_div != 0; NULL allowed otherwise); category [N] int32 (NULL allowed when

@@ -85,8 +85,15 @@
                                              its closed-form gradient) against index_select + bmm + gather + logsumexp + flipped logcumsumexp
                                              under autograd, chunked to 1 GiB, (G, M, k, S) in {64, 4 096} x {128, 1 024} x {10, 100} x {1, 8},
                                              forward and forward + backward, time and peak device bytes
-  python tools/kbench.py policy              nrms.fit_policy beside fit_ranker and the click softmax on the planted-signal corpus, and
-                                             nrms.fit_from_logs on a log the trained DIGAT makes, with intervals
+  python tools/kbench.py policy [train_users steps k samples log_users replicates logs]   nrms.fit_policy (REINFORCE) beside fit_ranker, the
+                                             click softmax and fit_policy(estimator="plrank") on the planted-signal corpus — step times,
+                                             the nDCG@k of the steps' own slates, held-out metrics with paired intervals, and the variance
+                                             of d_users under both estimators — and (logs = 1) nrms.fit_from_logs on a log the trained
+                                             DIGAT makes, with intervals
+  python tools/kbench.py plrank [d rounds]   PL-Rank policy gradient: evaluate.list_plrank (score, draw and value in one kernel, the PL-Rank-2
+                                             coefficient behind it) against list_softmax forward + pl_sample + list_pl with leave-one-out
+                                             weights (what a step was made of) and against the stock torch composition, list-pl's sixteen
+                                             shapes, forward and forward + backward, the legs in turn, median [min, max] of five rounds
   python tools/kbench.py pl-sample [rounds demo]   stochastic lists: evaluate.pl_sample (one workgroup per slate: hash, two float64 logs, a
                                              1024-record sort, the probability as a suffix sum) against rand + double log + topk + gather
                                              + flipped logcumsumexp in stock PyTorch, chunked to 1 GiB, (G, M, k, S) in {64, 4 096} x
@@ -2572,11 +2579,165 @@ def bench_list_pl(d=400, rounds=5, demo=0):
         demo_policy()
 
 
-def demo_policy(train_users=2048, steps=300, k=10, samples=4, log_users=2000, replicates=2000):
+def _ideal_weight(gain, k):
+    """``1 / IDCG@k`` per list (0 where that is 0), float64 numpy [G], from a gain tensor [G, M]."""
+    from digat_amd import evaluate
+    g = gain.detach().cpu().numpy().astype(np.float64)
+    g = np.where(np.isfinite(g) & (g > 0), g, 0.0)
+    top = -np.sort(-g, axis=1)[:, :k]
+    idcg = (top * evaluate.ndcg_discount(k)[:top.shape[1]]).sum(axis=1)
+    return np.where(idcg > 0, 1.0 / np.where(idcg > 0, idcg, 1.0), 0.0)
+
+
+def _loo(r):
+    """Leave-one-out weights of rewards [G, S]: the reward minus the mean of the list's other samples (the reward itself at S = 1)."""
+    S = int(r.shape[1])
+    return r if S == 1 else r - (r.sum(dim=1, keepdim=True) - r) / (S - 1)
+
+
+def stock_reinforce(users, rows, ids, count, gain, lw, k, S, backward=False, budget=1 << 30):
+    """A sampled-slate policy-gradient step from stock PyTorch in float32: ``index_select`` + ``torch.bmm`` scores, Gumbel keys from
+    ``torch.rand`` and ``topk`` for the slates, a gather of the gains for the nDCG@k of every slate, leave-one-out weights, and
+    ``evaluate._pl_stock`` for the likelihood under autograd — the lists in chunks of ``budget`` bytes of intermediates, as
+    ``stock_list_pl``.  Returns the summed reward."""
+    from digat_amd import evaluate
+    G, M = ids.shape
+    d = int(users.shape[1])
+    step = max(1, budget // (4 * (M * d + 6 * S * M)))
+    slot = torch.arange(M, device=ids.device)
+    disc = torch.from_numpy(evaluate.ndcg_discount(k)).to(ids.device).float()
+    total = torch.zeros((), dtype=torch.float32, device=ids.device)
+    for lo in range(0, G, step):
+        sl = slice(lo, lo + step)
+        g = ids[sl].shape[0]
+        x = torch.bmm(rows.index_select(0, ids[sl].reshape(-1)).view(g, M, -1), users[sl].unsqueeze(2)).squeeze(2)
+        live = slot[None, :] < count[sl][:, None]
+        with torch.no_grad():
+            key = x.detach()[:, None, :] - torch.log(-torch.log(torch.rand((g, S, M), device=x.device).clamp_(1e-20, 1.0 - 1e-7)))
+            top = key.masked_fill(~live[:, None, :], float("-inf")).topk(min(k, M), dim=2)
+            picks = torch.where(torch.isfinite(top.values), top.indices, torch.full_like(top.indices, -1))
+            got = torch.where(picks >= 0, gain[sl].gather(1, picks.clamp(min=0).view(g, -1)).view(picks.shape), torch.zeros((), device=x.device))
+            r = (got * disc[:picks.shape[2]]).sum(dim=2) * lw[sl][:, None]
+            w = _loo(r)
+        if backward:
+            (-(w * evaluate._pl_stock(x, live, picks, 1.0)[0]).sum() / (g * S)).backward()
+        total = total + r.sum()
+    return total
+
+
+def bench_plrank(d=400, rounds=5):
+    """``evaluate.list_plrank`` (one pass: score, draw, value; the PL-Rank coefficient kernel behind it) against (1) what the tree had
+    for a sampled-slate policy-gradient step — ``list_softmax``'s forward for the scores, ``pl_sample``, the slates' nDCG@k by a gather
+    of the positions (no ``slate_positions``), leave-one-out weights, ``list_pl`` forward and backward — and (2) ``stock_reinforce``
+    (float32, chunked to 1 GiB), in one process, the legs taken in turn, median [min, max] of ``rounds`` rounds of three calls; forward
+    alone (``no_grad``) and forward + backward; ``list-pl``'s sixteen shapes, click-like gains (three positive per list)."""
+    from digat_amd import evaluate, nrms
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device="cpu").manual_seed(0)
+    stat = lambda v: (sorted(v)[len(v) // 2], min(v), max(v))
+    print(f"plrank: d = {d}, compact pool, scale = 1, T = 1, nDCG@k; ms per call, median [min, max] of {rounds} rounds", flush=True)
+    for G in (64, 4096):
+        for M in (128, 1024):
+            P = max(M, min(65237, G * M // 4))
+            rows = (torch.randn(P, d, generator=g) / d ** 0.5).to(dev)
+            users = (3.0 * torch.randn(G, d, generator=g)).to(dev)
+            ids = torch.stack([torch.randperm(P, generator=g)[:M] for _ in range(G)]).to(dev)
+            count = torch.randint(M * 3 // 4, M + 1, (G,), generator=g).to(torch.int32).to(dev)
+            gain = torch.zeros(G, M)
+            gain.scatter_(1, torch.stack([torch.randperm(M * 3 // 4, generator=g)[:3] for _ in range(G)]), 1.0)
+            gain = gain.to(dev)
+            zero = torch.zeros((G, M), device=dev)
+            for k in (10, 100):
+                lw = _ideal_weight(gain, k)
+                lw_t = torch.from_numpy(lw).to(dev)
+                for S in (1, 8):
+                    def fused(backward):
+                        u, t = users.detach().requires_grad_(backward), rows.detach().requires_grad_(backward)
+                        value = evaluate.list_plrank(u, t, ids, count, gain, k, S, None, lw, seed=1)[0]
+                        if not backward:
+                            return value.sum()
+                        (-value.sum() / G).backward()
+                        return value.detach().sum() + 0.0 * (u.grad[0, 0] + t.grad[0, 0])
+
+                    def parent(backward):
+                        with torch.no_grad():
+                            scores = evaluate.list_softmax(users, rows, ids, count, zero)[2]
+                            picks = evaluate.pl_sample(scores, count, k, 1.0, 1, S)[0]
+                            w = _loo(nrms.slate_ndcg(gain, picks, k))
+                        u, t = users.detach().requires_grad_(backward), rows.detach().requires_grad_(backward)
+                        logp = evaluate.list_pl(u, t, ids, count, picks)[0]
+                        if not backward:
+                            return logp.sum()
+                        (-(w * logp).sum() / (G * S)).backward()
+                        return logp.detach().sum() + 0.0 * (u.grad[0, 0] + t.grad[0, 0])
+
+                    def stock(backward):
+                        u, t = users.detach().requires_grad_(backward), rows.detach().requires_grad_(backward)
+                        if not backward:
+                            with torch.no_grad():
+                                return stock_reinforce(u, t, ids, count, gain, lw_t.float(), k, S)
+                        r = stock_reinforce(u, t, ids, count, gain, lw_t.float(), k, S, backward=True)
+                        return r + 0.0 * (u.grad[0, 0] + t.grad[0, 0])
+                    legs = [lambda f=f, b=b: f(b) for b in (False, True) for f in (fused, parent, stock)]
+                    times = [[] for _ in legs]
+                    for _ in range(rounds):
+                        for leg, fn in zip(times, legs):
+                            leg.append(timeit(fn, iters=3, warm=1)[0])
+                    st = [stat(t) for t in times]
+                    cell = lambda i: f"{st[i][0]:8.3f} ms [{st[i][1]:.3f}, {st[i][2]:.3f}]"
+                    print(f"  G = {G:5d}, M = {M:4d}, k = {k:3d}, S = {S}: forward: list_plrank {cell(0)} | softmax + sample + list_pl {cell(1)} "
+                          f"(x{st[1][0] / st[0][0]:.2f}) | stock {cell(2)} (x{st[2][0] / st[0][0]:.2f}) || forward + backward: list_plrank {cell(3)} | "
+                          f"softmax + sample + list_pl {cell(4)} (x{st[4][0] / st[3][0]:.2f}) | stock {cell(5)} (x{st[5][0] / st[3][0]:.2f})", flush=True)
+            del rows, users, ids, count, gain, zero
+            torch.cuda.empty_cache()
+
+
+def gradient_variance(model, train, lists, k=10, samples=4, draws=64, batch=64):
+    """The variance of one step's ``d_users`` under both estimators of the gradient of minus the mean expected nDCG@k of a batch: the
+    model in eval mode, the first ``batch`` lists, ``draws`` values of ``first_sample`` (``samples`` apart), the encoders run once.
+    PL-Rank: ``list_plrank``'s backward.  REINFORCE: ``pl_sample`` on the same scores, ``slate_ndcg``, leave-one-out weights, ``list_pl``'s
+    backward, divided by the valid lists times ``samples`` so that both estimate the same gradient (``policy_step`` divides by the number
+    of slates with a non-zero weight instead: another scale, not another direction).  Returns per estimator ``(total variance summed over the coordinates, squared norm of the mean)`` and the
+    distance between the two means."""
+    from digat_amd import evaluate, nrms
+    users, ids, gain, count = nrms._check_lists(*lists[:3], lists[3], int(train.history_ids.shape[0]))
+    b = np.arange(min(batch, len(users)))
+    model.eval()
+    with torch.no_grad():
+        user, table, pos, cnt, _ = nrms._list_front(model, train, users[b], ids[b], count[b])
+    dev = user.device
+    gn = torch.from_numpy(gain[b]).to(dev)
+    lw = _ideal_weight(gn, k)
+    valid = max(int((lw > 0).sum()), 1)
+    streams = torch.from_numpy(users[b]).to(dev)
+    got ={"plrank": [], "reinforce": []}
+    for f in range(draws):
+        u = user.detach().requires_grad_(True)
+        value, _, _, scores = evaluate.list_plrank(u, table, pos, cnt, gn, k, samples, None, lw, seed=0, first_sample=f * samples, streams=streams)
+        (-value.sum() / valid).backward()
+        got["plrank"].append(u.grad.double().cpu().numpy().copy())
+        picks = evaluate.pl_sample(scores, cnt, k, 1.0, 0, samples, f * samples, streams)[0]
+        w = _loo(nrms.slate_ndcg(gn, picks, k))
+        u = user.detach().requires_grad_(True)
+        logp = evaluate.list_pl(u, table, pos, cnt, picks)[0]
+        (-(w * logp).sum() / (valid * samples)).backward()
+        got["reinforce"].append(u.grad.double().cpu().numpy().copy())
+    out = {}
+    for name, v in got.items():
+        v = np.stack(v)
+        out[name] = (float(v.var(axis=0, ddof=1).sum()), float((v.mean(axis=0) ** 2).sum()))
+    out["distance"] = float(np.sqrt(((np.stack(got["plrank"]).mean(axis=0) - np.stack(got["reinforce"]).mean(axis=0)) ** 2).sum()))
+    return out
+
+
+def demo_policy(train_users=2048, steps=300, k=10, samples=4, log_users=2000, replicates=2000, logs=1):
     """The demonstration runs of the policy-gradient surface on the planted-signal corpus, in ``demo_rank``'s setting (NRMS at d = 64,
     random titles, ``train_users`` training impressions, ``steps`` steps of 64 lists, lr 1e-3, the same seeded draws).  (1) Three copies
     of one model: ``nrms.fit_policy`` (REINFORCE on the expected nDCG@``k`` of ``samples`` sampled slates), ``nrms.fit_ranker`` and the
-    listwise click softmax; held-out AUC / MRR / nDCG with ``evaluate.compare_metrics``.  (2) ``nrms.fit_from_logs``: the trained DIGAT
+    listwise click softmax; held-out AUC / MRR / nDCG with ``evaluate.compare_metrics``; then a fourth copy under
+    ``fit_policy(estimator="plrank")`` — its step time beside REINFORCE's from the same run (both warmed by three untimed steps on
+    further copies), the nDCG@``k`` of the steps' own slates, its held-out metrics paired against the REINFORCE leg — and
+    ``gradient_variance`` of both estimators on the untrained model.  ``logs`` = 0 stops here.  (2) ``nrms.fit_from_logs``: the trained DIGAT
     logs slates for ``log_users`` held-out impressions (``demo_off_policy``'s log and reward); a fresh NRMS is trained on the log; it
     is judged by the mean reward of its OWN slates on the logged shortlists before and after, and by ``evaluate.off_policy_value`` of
     its likelihoods on the log.  Beside it: what the graph-free first scoring pass of a ``fit_from_logs`` step costs."""
@@ -2599,7 +2760,7 @@ def demo_policy(train_users=2048, steps=300, k=10, samples=4, log_users=2000, re
                                      row_candidate=c.row_candidate.astype(np.int64), row_impression=c.row_impression, row_label=c.row_label)
     held, train = part(0, synthetic.PLANTED_DEV_IMPRESSIONS), part(synthetic.PLANTED_DEV_IMPRESSIONS, spec.impressions)
     base = _nrms_model("NRMS", V=V, dm=64, h=8, dk=8, att=32, Lw=Lw, H=H, dropout=0.2)
-    policy, ranker, softmax, student = (copy.deepcopy(base) for _ in range(4))
+    policy, ranker, softmax, student, plrank, fixed, *warm = (copy.deepcopy(base) for _ in range(8))      # before base runs: its caches do not copy
     tu = np.arange(train_users, dtype=np.int64)
     gains, clicks = nrms.impression_gain_lists(train, tu), nrms.impression_lists(train, tu)
     labels = np.asarray(held.row_label)
@@ -2610,6 +2771,9 @@ def demo_policy(train_users=2048, steps=300, k=10, samples=4, log_users=2000, re
     print(f"policy demo (1): planted-signal corpus, NRMS at d = 64, random titles; {len(gains[0])} training impressions of up to "
           f"{gains[1].shape[1]} candidates; held-out: {int(held.history_ids.shape[0])} impressions", flush=True)
     print("  before: AUC %.4f MRR %.4f nDCG@5 %.4f nDCG@10 %.4f" % rows_of(base)[1], flush=True)
+    for est, copy_ in zip(("reinforce", "plrank"), warm):              # three steps of either on a copy: the timed legs start warm
+        nrms.fit_policy(copy_, train, gains, 3, k=k, samples=samples, batch_users=64, lr=1e-3, seed=0, estimator=est)
+    torch.cuda.synchronize()
     t0 = time.perf_counter()
     l_pol, r_pol = nrms.fit_policy(policy, train, gains, steps, k=k, samples=samples, batch_users=64, lr=1e-3, seed=0)
     torch.cuda.synchronize()
@@ -2632,6 +2796,29 @@ def demo_policy(train_users=2048, steps=300, k=10, samples=4, log_users=2000, re
             f = cmp_[name]
             print(f"  {name}: fit_policy - {other} = {f['diff']:+.4f} [{f['lo']:+.4f}, {f['hi']:+.4f}], p = {f['p']:.4f} ({replicates} paired "
                   f"replicates over impressions)", flush=True)
+    # the third leg: the same trainer with the PL-Rank estimator, one scoring pass a step
+    torch.cuda.synchronize()
+    ta = time.perf_counter()
+    l_plr, r_plr = nrms.fit_policy(plrank, train, gains, steps, k=k, samples=samples, batch_users=64, lr=1e-3, seed=0, estimator="plrank")
+    torch.cuda.synchronize()
+    tb = time.perf_counter()
+    rq, mq = rows_of(plrank)
+    print(f"  fit_policy(estimator='plrank') (k = {k}, {samples} samples): {1e3 * (tb - ta) / steps:.1f} ms per step against REINFORCE's "
+          f"{1e3 * (t1 - t0) / steps:.1f} in this run; mean nDCG@{k} of the step's own sampled slates {np.mean(r_plr[:10]):.4f} (first ten steps) "
+          f"-> {np.mean(r_plr[-10:]):.4f} (last ten) against REINFORCE's {np.mean(r_pol[:10]):.4f} -> {np.mean(r_pol[-10:]):.4f}", flush=True)
+    print("  after fit_policy(estimator='plrank'): AUC %.4f MRR %.4f nDCG@5 %.4f nDCG@10 %.4f" % mq, flush=True)
+    cmp_ = evaluate.compare_metrics(rq, rp, names=("AUC", "MRR", "nDCG@5", "nDCG@10"), replicates=replicates)
+    for name in ("MRR", "nDCG@10"):
+        f = cmp_[name]
+        print(f"  {name}: plrank - REINFORCE = {f['diff']:+.4f} [{f['lo']:+.4f}, {f['hi']:+.4f}], p = {f['p']:.4f} ({replicates} paired replicates "
+              f"over impressions)", flush=True)
+    gvar = gradient_variance(fixed, train, gains, k=k, samples=samples)
+    print(f"  gradient variance (the untrained model in eval mode, the first 64 lists, 64 values of first_sample, {samples} samples; d_users, summed "
+          f"over coordinates): PL-Rank {gvar['plrank'][0]:.4e} (|mean|^2 {gvar['plrank'][1]:.4e}) | REINFORCE with leave-one-out "
+          f"{gvar['reinforce'][0]:.4e} (|mean|^2 {gvar['reinforce'][1]:.4e}) | ratio {gvar['plrank'][0] / gvar['reinforce'][0]:.3f}; the two means "
+          f"lie {gvar['distance']:.3e} apart", flush=True)
+    if not logs:
+        return
     # (2) learning from a log the trained DIGAT makes
     golden = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
     state = {name: v for name, v in np.load(os.path.join(golden, "trained_planted_state.npz")).items()}
@@ -2902,6 +3089,8 @@ if __name__ == "__main__":
         bench_list_pl(*nums)
     elif what == "policy":
         demo_policy(*nums)
+    elif what == "plrank":
+        bench_plrank(*nums)
     elif what == "bootstrap":
         bench_bootstrap(*nums)
     elif what == "linear":
