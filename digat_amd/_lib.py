@@ -161,6 +161,10 @@ _SIGNATURES = {
     "digat_rerank_select_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
     "digat_rerank_select": (C.c_int, [_f, _f, _f, C.c_int64, C.c_int, _f, C.c_int64, C.c_int, _f, C.c_int, _f, C.c_int, C.c_float, C.c_float,
                                       C.c_float, C.c_double, C.c_int, _f, _f, _f, _f, _f, C.c_size_t, _f]),
+    "digat_capped_select_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
+    "digat_capped_prepare": (C.c_int, [_f, _f, _f, _f, C.c_int64, C.c_int, C.c_int64, _f, C.c_size_t, _f]),
+    "digat_capped_rounds": (C.c_int, [C.c_int64, C.c_int, C.c_int, _f, _f, _f, _f, C.c_int64, _f, C.c_int, _f, C.c_size_t, _f]),
+    "digat_capped_emit": (C.c_int, [_f, _f, C.c_int64, C.c_int, C.c_int, _f, _f, _f, _f, _f, C.c_size_t, _f]),
     "digat_pl_sample_workspace_bytes":(C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int64]),
     "digat_pl_sample": (C.c_int, [_f, _f, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_uint32, C.c_int64, C.c_int64, _f, _f, _f, _f, _f, _f,
                                   C.c_size_t, _f]),

@@ -11,6 +11,7 @@ real MIND cannot be downloaded, so the default corpus is synthetic (``--syntheti
 ``--recommend_calibration`` (with ``--recommend_shortlist``, here up to 1024) likewise;
 ``--recommend_sample`` (a temperature; with ``--recommend_seed`` and ``--recommend_shortlist``, here up to 1024) likewise;
 ``--recommend_rerank`` (a pair ``D,C``; with ``--recommend_shortlist`` up to 1024 and ``--recommend_max_per_category``) likewise;
+``--recommend_exposure_cap`` (a capacity per news over the lists of the call; with ``--recommend_shortlist`` up to 1024) likewise;
 ``--bootstrap`` (with ``--bootstrap_level``, ``--compare_model_path``) likewise;
 ``--local_rank`` also accepts torch >= 2.0's ``--local-rank`` spelling and the ``LOCAL_RANK`` variable.
 """
@@ -58,6 +59,11 @@ class Config:
                             '0: min(1024, 8 * recommend_k)) with the weights 1 - D - C, D and C (each 0..1, D + C <= 1; default: off; honours '
                             '--recommend_max_per_category; not with --recommend_diversity, --recommend_calibration, --recommend_sample or '
                             '--recommend_report)')
+        p.add_argument('--recommend_exposure_cap', type=int, default=None,
+                       help='--mode recommend: no news in more than this many of the lists written (>= 0; default: off) — every list keeps its '
+                            'best k of a shortlist (recommend_k..1024; 0: min(1024, 8 * recommend_k)) among the news that still have room for '
+                            'it; not with --recommend_diversity, --recommend_calibration, --recommend_sample, --recommend_rerank, '
+                            '--recommend_report or --recommend_max_per_category')
         p.add_argument('--recommend_report', type=str, default=None,
                        help='--mode recommend: diversities "0,0.1,0.3" to report list quality for (one scoring pass; honours --recommend_k, '
                             '--recommend_shortlist, --recommend_max_per_category)')
@@ -135,6 +141,13 @@ class Config:
                     or a.recommend_report is not None):
                 p.error('--recommend_rerank does not combine with --recommend_diversity, --recommend_calibration, --recommend_sample or '
                         '--recommend_report')
+        if a.recommend_exposure_cap is not None:
+            if a.recommend_exposure_cap < 0:
+                p.error('--recommend_exposure_cap must not be negative')
+            if (a.recommend_diversity is not None or a.recommend_calibration is not None or a.recommend_sample is not None
+                    or a.recommend_rerank is not None or a.recommend_report is not None or a.recommend_max_per_category):
+                p.error('--recommend_exposure_cap does not combine with --recommend_diversity, --recommend_calibration, --recommend_sample, '
+                        '--recommend_rerank, --recommend_report or --recommend_max_per_category')
         if a.recommend_calibration is not None and not 0.0 <= a.recommend_calibration <= 1.0:
             p.error('--recommend_calibration must lie in [0, 1]')
         if a.recommend_calibration is not None and (a.recommend_diversity is not None or a.recommend_report is not None):
@@ -148,7 +161,8 @@ class Config:
         if a.recommend_seed and a.recommend_sample is None:
             p.error('--recommend_seed needs --recommend_sample')
         if a.recommend_diversity is None and a.recommend_report is None and a.recommend_rerank is None and (
-                a.recommend_max_per_category or (a.recommend_shortlist and a.recommend_calibration is None and a.recommend_sample is None)):
+                a.recommend_max_per_category or (a.recommend_shortlist and a.recommend_calibration is None and a.recommend_sample is None
+                                                 and a.recommend_exposure_cap is None)):
             p.error('--recommend_shortlist and --recommend_max_per_category need --recommend_diversity (0 for the cap alone) or --recommend_report')
         if a.recommend_diversity is not None and not 0.0 <= a.recommend_diversity <= 1.0:
             p.error('--recommend_diversity must lie in [0, 1]')
@@ -165,12 +179,15 @@ class Config:
         calibration_flags = ('recommend_calibration', 'recommend_shortlist')
         sample_flags = ('recommend_sample', 'recommend_seed', 'recommend_shortlist')
         rerank_flags = ('recommend_rerank', 'recommend_shortlist', 'recommend_max_per_category')
+        exposure_flags = ('recommend_exposure_cap', 'recommend_shortlist')
         bootstrap_flags = ('bootstrap', 'bootstrap_level', 'compare_model_path')
         asked = lambda k: ((a.recommend_diversity is not None and k in diversity_flags) or (a.recommend_report is not None and k in report_flags)
                            or (a.recommend_calibration is not None and k in calibration_flags) or (a.bootstrap and k in bootstrap_flags)
                            or (a.recommend_sample is not None and k in sample_flags)
                            or (a.recommend_rerank is not None and k in rerank_flags)
-                           or k not in diversity_flags + report_flags + calibration_flags + sample_flags + rerank_flags + bootstrap_flags)
+                           or (a.recommend_exposure_cap is not None and k in exposure_flags)
+                           or k not in diversity_flags + report_flags + calibration_flags + sample_flags + rerank_flags + exposure_flags
+                           + bootstrap_flags)
         self.attribute_dict = {k: v for k, v in vars(a).items()
                                if (a.data_root or k not in mind_flags or (k == 'model_dir' and a.model_dir)) and asked(k)}
         for k, v in self.attribute_dict.items():

@@ -968,3 +968,4 @@ int digat_row_logits(const float* news_ctx, const float* user_ctx, float* logits
 #include "digat_list_pl.inc"
 #include "digat_list_plrank.inc"
 #include "digat_rerank.inc"
+#include "digat_capped.inc"

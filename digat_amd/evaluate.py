@@ -2056,6 +2056,192 @@ def rerank_select(ids, scores, count, vectors, k: int, w_rel, w_div, w_cal, cate
     return outs
 
 
+# ---- exposure-capped top-k: the one stage over the BATCH of lists — no news in more than cap[id] of them (deferred acceptance) ------
+CAP_MAX_LIST = SHORTLIST_MAX_K     # include/digat_hip.h: DIGAT_CAPPED_MAX_LIST, the longest list the digat_capped_* entries take
+CAP_MAX_K = TOPK_MAX_K             # the most entries a list may hold
+CAP_ROUNDS_PER_SYNC = 4            # the rounds capped_select enqueues between two reads of the rejection counters
+CAP_MAX_ROUNDS = 1024              # the rounds after which capped_select / capped_select_host give up
+_CAP_NO_ELEMENT = 0x7fffffffffffffff       # the item word of a pair that is no element: behind every news in the sort
+_CAP_KEY_NEG_INF = 0x007fffff              # topk_keys(-inf); a NaN's key is 1: an element's score key lies above both
+
+
+def _check_capped_args(ids_shape, scores_shape, count_shape, priority_shape, k, pool, rounds_per_sync=1, max_rounds=1) -> int:
+    _check_select_shapes(ids_shape, scores_shape, count_shape, k, CAP_MAX_LIST)
+    if priority_shape is not None and tuple(priority_shape) != tuple(ids_shape):
+        raise ValueError(f"priority must be [G, M] = {tuple(ids_shape)}, got {tuple(priority_shape)}")
+    if not 0 <= int(pool) < 2 ** 31:
+        raise ValueError(f"pool must be the number of news, in [0, 2^31), got {pool}")
+    if ids_shape[0] * ids_shape[1] >= 2 ** 31:
+        raise ValueError(f"G M must stay below 2^31, got {tuple(ids_shape)}")
+    if int(rounds_per_sync) < 1 or int(max_rounds) < 1:
+        raise ValueError(f"rounds_per_sync and max_rounds must be >= 1, got {rounds_per_sync} and {max_rounds}")
+    return int(pool)
+
+
+def capped_caps_host(cap, pool: int) -> np.ndarray:
+    """``cap`` of ``capped_select_host`` as an int32 array [P]: an int >= 0 names every news' capacity, an integer array [P] is
+    taken as given (an entry <= 0 blocks its news)."""
+    P = int(pool)
+    if np.ndim(cap) == 0:
+        if isinstance(cap, (bool, np.bool_)) or int(cap) != cap or int(cap) < 0:
+            raise ValueError(f"cap must be an int >= 0 or an integer array [pool], got {cap!r}")
+        return np.full(P, min(int(cap), 2 ** 31 - 1), dtype=np.int32)
+    c = np.asarray(cap)
+    if c.shape != (P,) or c.dtype.kind not in "iu":
+        raise ValueError(f"cap must be an int >= 0 or an integer array [pool = {P}], got shape {c.shape} {c.dtype}")
+    return np.clip(c, -1, 2 ** 31 - 1).astype(np.int32)
+
+
+def capped_select_host(ids, scores, count, k: int, cap, pool: int, priority=None, max_rounds: int = CAP_MAX_ROUNDS):
+    """The contract of the ``digat_capped_*`` entries in numpy — the yardstick of ``capped_select``.  Exposure-capped top-k over a
+    BATCH of lists: every list keeps at most k of its entries and news ``id`` is kept by at most ``cap[id]`` lists of the call.
+
+    ``ids`` [G, M <= 1024] int64, ``scores`` [G, M] float32, ``count`` [G] or None (M), ``k`` in [1, 128], ``pool`` = P the number of
+    news, ``cap`` an int >= 0 for every news or an integer array [P] (``cap[id] <= 0`` blocks a news), ``priority`` [G, M] float32 or
+    None (the scores).  Pair (g, j) is an ELEMENT when ``j < clip(count[g], 0, M)``, ``0 <= ids[g, j] < P``, ``scores[g, j]`` is
+    neither NaN nor ``-inf`` and ``priority[g, j]`` is no NaN — ``recommend``'s fill (id -1, score ``-inf``) is no element.  A list
+    that names one id twice has TWO pairs; each is a pair in its own right, it may be held twice by that list and counts twice
+    against the news' capacity.
+
+    Orders, both strict: a list orders its elements by ``topk_keys(score)`` descending, then slot ascending (the rank file's order;
+    ``-0`` equals ``+0``); an item orders the pairs that name it by ``topk_keys(priority)`` descending, then g ascending, then slot
+    ascending.  The result is the unique set H of elements such that every list holds at most k, every item is held at most
+    ``cap[id]`` times, H is STABLE — no element outside H whose list holds fewer than k or prefers it to its worst held entry AND
+    whose item has capacity and either room or a worse holder — and among the stable sets H is the one every list likes best
+    (deferred acceptance with the lists proposing).  It is a stable assignment, NOT the assignment of largest total score.  No
+    floating-point arithmetic takes part, only comparisons of keys: any schedule of proposals gives the same H.
+
+    The round-wise definition the kernels follow: ``rejected`` starts as the non-elements; in a round every list demands its first k
+    non-rejected entries in list order, then every item walks its pairs in item order, counts the demanded ones, and from the pair
+    behind the ``cap[id]``-th demanded one on (from the start when the capacity is 0) every pair not yet rejected becomes rejected,
+    demanded or not — an item's held set only improves, so those can never be accepted.  The first round that rejects nothing ends
+    the loop; its demand sets are H and ``rounds`` counts the rounds up to and including it.  More than ``max_rounds``:
+    ``RuntimeError``.
+
+    Returns ``(ids [G,k] int64, scores [G,k] float32 — the INPUT bits —, count [G] int32, slots [G,k] int32, rounds)``: the held
+    entries in the list's order, behind ``count[g]`` id -1, score ``-inf``, slot -1.  A list comes back with fewer than k entries
+    when its shortlist runs out: hand in a deeper shortlist.  ``cap >= G`` everywhere gives the plain top-k of the elements."""
+    idv = np.asarray(ids, dtype=np.int64)
+    sc = np.ascontiguousarray(scores, dtype=np.float32)
+    pr = None if priority is None else np.ascontiguousarray(priority, dtype=np.float32)
+    P = _check_capped_args(idv.shape, sc.shape, _shape(count), _shape(pr), k, pool, 1, max_rounds)
+    caps = capped_caps_host(cap, P).astype(np.int64)
+    G, M = idv.shape
+    k = int(k)
+    cnt = np.full(G, M, dtype=np.int64) if count is None else np.clip(np.asarray(count, dtype=np.int64), 0, M)
+    ks = topk_keys(sc).reshape(G, M).astype(np.int64)
+    kp = ks if pr is None else topk_keys(pr).reshape(G, M).astype(np.int64)
+    elem = (np.arange(M)[None, :] < cnt[:, None]) & (idv >= 0) & (idv < P) & (ks > _CAP_KEY_NEG_INF) & (kp != 1)
+    # a list's order, rank -> slot: elements by key descending, slot ascending; the non-elements behind them
+    order = np.argsort(-np.where(elem, ks, -1), axis=1, kind="stable")
+    # the items' order: one stable sort of (id, ~priority key) words over the pairs in flat order — g ascending, then slot
+    words = np.where(elem, (np.where(elem, idv, 0) << 32) | (~kp & 0xffffffff), _CAP_NO_ELEMENT).reshape(-1)
+    perm = np.argsort(words, kind="stable")[:int(elem.sum())]
+    sid = idv.reshape(-1)[perm]
+    first = np.flatnonzero(np.r_[True, sid[1:] != sid[:-1]]) if len(sid) else np.zeros(0, dtype=np.int64)
+    seg = np.cumsum(np.r_[True, sid[1:] != sid[:-1]]) - 1 if len(sid) else np.zeros(0, dtype=np.int64)
+    cap_of = caps[sid]
+    rejected = ~elem.reshape(-1)
+    rounds = 0
+    while True:
+        if rounds == int(max_rounds):
+            raise RuntimeError(f"capped_select_host: no fixed point within max_rounds = {max_rounds} rounds")
+        rounds += 1
+        alive = ~np.take_along_axis(rejected.reshape(G, M), order, axis=1)                # rank space
+        ahead = np.cumsum(alive, axis=1)
+        wanted = alive & (ahead <= k)
+        demand = np.zeros((G, M), dtype=bool)
+        np.put_along_axis(demand, order, wanted, axis=1)
+        d = demand.reshape(-1)[perm].astype(np.int64)
+        before = np.cumsum(d) - d                                                       # demanded pairs in front, in the whole sort ...
+        before = before - before[first][seg] if len(d) else before                      # ... and in the pair's own segment
+        new = (before >= cap_of) & ~rejected[perm]
+        if not new.any():
+            break
+        rejected[perm[new]] = True
+    out_i = np.full((G, k), -1, dtype=np.int64)
+    out_s = np.full((G, k), -np.inf, dtype=np.float32)
+    out_p = np.full((G, k), -1, dtype=np.int32)
+    gi, ri = np.nonzero(wanted)
+    at, slot = ahead[gi, ri] - 1, order[gi, ri]
+    out_i[gi, at] = idv[gi, slot]
+    out_s[gi, at] = sc[gi, slot]
+    out_p[gi, at] = slot
+    return out_i, out_s, wanted.sum(axis=1).astype(np.int32), out_p, rounds
+
+
+def capped_select(ids, scores, count, k: int, cap, pool: int, priority=None, rounds_per_sync: int = CAP_ROUNDS_PER_SYNC,
+                  max_rounds: int = CAP_MAX_ROUNDS):
+    """Exposure-capped top-k on the GPU (``digat_capped_prepare`` / ``digat_capped_rounds`` / ``digat_capped_emit``): every list keeps
+    at most k of its entries, news ``id`` is kept by at most ``cap[id]`` lists of the call — the list-optimal stable assignment.
+
+    ``ids`` [G, M <= 1024] int64, ``scores`` [G, M] float32 and ``count`` [G] int32 (None: M) are device tensors — what
+    ``shortlist_segments``, ``dot_shortlist`` and both ``recommend``s return; ``pool`` the number of news, ``cap`` an int >= 0 or an
+    integer tensor [pool] (an entry <= 0 blocks its news), ``priority`` [G, M] float32 orders the lists that contend for a news
+    (None: by score).  The contract is ``capped_select_host``'s, exactly: ids, score bits, counts, slots, fill and ``rounds``; it is
+    a stable assignment, not the one of largest total score, and a list whose shortlist runs out comes back short — hand in a deeper
+    one.  Returns ``(ids [G,k] int64, scores [G,k] float32, count [G] int32, slots [G,k] int32, rounds)``, the tensors on the device.
+
+    Not stream-only: one stable ``torch.sort`` of the item words, one read of how many news can bind at all, and then blocks of
+    ``rounds_per_sync`` rounds, each followed by a read of its rejection counters — the loop stops at the first round that rejected
+    nothing.  Neither the result nor ``rounds`` depends on ``rounds_per_sync``.  More than ``max_rounds`` rounds: ``RuntimeError``,
+    nothing is returned."""
+    import torch
+    from . import _lib
+    P = _check_capped_args(_shape(ids), _shape(scores), _shape(count), _shape(priority), k, pool, rounds_per_sync, max_rounds)
+    cap_t = cap if torch.is_tensor(cap) else None
+    dev = _lib.require_device(*[t for t in (ids, scores, count, priority, cap_t) if t is not None])
+    if cap_t is None:
+        caps = torch.from_numpy(capped_caps_host(cap, P)).to(dev)
+    else:
+        if tuple(cap_t.shape) != (P,) or cap_t.is_floating_point() or cap_t.dtype == torch.bool:
+            raise ValueError(f"cap must be an int >= 0 or an integer tensor [pool = {P}], got {tuple(cap_t.shape)} {cap_t.dtype}")
+        caps = cap_t.clamp(-1, 2 ** 31 - 1).to(torch.int32).contiguous()
+    idt = ids.to(torch.int64).contiguous()
+    sc = _lib.f32(scores.detach())
+    pr = None if priority is None else _lib.f32(priority.detach())
+    ct = None if count is None else count.to(torch.int32).contiguous()
+    G, M, k = int(idt.shape[0]), int(idt.shape[1]), int(k)
+    out_i = torch.empty((G, k), dtype=torch.int64, device=dev)
+    out_s = torch.empty((G, k), dtype=torch.float32, device=dev)
+    out_c = torch.empty((G,), dtype=torch.int32, device=dev)
+    out_p = torch.empty((G, k), dtype=torch.int32, device=dev)
+    if G == 0:
+        return out_i, out_s, out_c, out_p, 1
+    L = _lib.lib()
+    need = int(L.digat_capped_select_workspace_bytes(G, M))
+    ws = _lib.workspace(need, dev, "capped")
+    tail = (ws.data_ptr(), need, _lib.stream_ptr())
+    _lib.check(L.digat_capped_prepare(idt.data_ptr(), sc.data_ptr(), _lib.ptr(pr), _lib.ptr(ct), G, M, P, *tail), "digat_capped_prepare")
+    # the inverted index in item order: one stable sort of the item words (ties keep flat order: g, then slot), then every news' run
+    # and the runs longer than their capacity — no other can ever reject
+    words, perm = torch.sort(ws[:G * M * 8].view(torch.int64), stable=True)
+    perm = perm.to(torch.int32)
+    bounds = torch.searchsorted(words >> 32, torch.arange(P + 1, dtype=torch.int64, device=dev))
+    length = bounds[1:] - bounds[:-1]
+    binding = torch.nonzero(length > caps).view(-1)                  # the one read-back before the rounds: it sizes the item grid
+    n_seg = int(binding.shape[0])
+    seg_begin = bounds[:-1][binding].to(torch.int32)
+    seg_cap = caps[binding].contiguous()
+    seg_live = length[binding].to(torch.int32)
+    segs = (seg_begin, seg_cap, seg_live) if n_seg else (None, None, None)
+    done, rounds = 0, 0
+    while not rounds:
+        if done >= int(max_rounds):
+            raise RuntimeError(f"capped_select: no fixed point within max_rounds = {max_rounds} rounds")
+        n = min(int(rounds_per_sync), int(max_rounds) - done)
+        counter = torch.zeros((n,), dtype=torch.int32, device=dev)
+        _lib.check(L.digat_capped_rounds(G, M, k, perm.data_ptr(), *(_lib.ptr(t) for t in segs), n_seg, counter.data_ptr(), n, *tail),
+                   "digat_capped_rounds")
+        still = np.flatnonzero(counter.cpu().numpy() == 0)
+        if len(still):
+            rounds = done + int(still[0]) + 1
+        done += n
+    _lib.check(L.digat_capped_emit(idt.data_ptr(), sc.data_ptr(), G, M, k, out_i.data_ptr(), out_s.data_ptr(), out_c.data_ptr(),
+                                   out_p.data_ptr(), *tail), "digat_capped_emit")
+    return out_i, out_s, out_c, out_p, rounds
+
+
 def _check_share_args(history_shape, category_shape, C):
     if len(history_shape) != 2:
         raise ValueError(f"history must be [G, H], got shape {tuple(history_shape)}")

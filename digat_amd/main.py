@@ -17,6 +17,8 @@ category mix of the reader's history (``util.recommend(calibration=)``) — on a
 (``util.recommend(sample=)``, ``--recommend_seed``).
 ``--recommend_rerank D,C`` instead makes them diverse AND calibrated in one greedy pass over that shortlist (``util.recommend(rerank=)``;
 ``--recommend_max_per_category`` composes).
+``--recommend_exposure_cap N`` instead bounds how often a news is shown: no news in more than N of the lists written, every list the
+best k of that shortlist among the news that still have room for it (``util.recommend(exposure_cap=)``; the cap holds over the run).
 ``--recommend_report 0,0.1,0.3`` then prints one line per diversity with what the knob buys and costs (``util.recommend_report``: one
 scoring pass for all of them; on a labelled split the accuracy of the lists against each impression's clicked candidates as well).
 ``--bootstrap B`` (``dev`` / ``test`` on a labelled split) prints, below the four metrics, one line per metric with its percentile
@@ -59,14 +61,16 @@ def recommend_category(dc, max_per_category: int):
 
 
 def recommend_lines(model, dc, k: int, batch_size: int, diversity=None, shortlist: int = 0, max_per_category: int = 0, calibration=None,
-                    sample=None, seed: int = 0, rerank=None):
+                    sample=None, seed: int = 0, rerank=None, exposure_cap=None):
     """``"<impression id> [id1,id2,...]"`` (1-based impression ids, best news first) for every impression of ``dc`` against the
     pool of all non-PAD news, the user's own history excluded; with ``diversity`` the diversified lists of ``util.recommend``, with
     ``calibration`` its calibrated ones, with ``sample`` (a temperature) one drawn slate per impression (``seed``), with ``rerank``
-    (a pair) the jointly re-ranked ones."""
+    (a pair) the jointly re-ranked ones, with ``exposure_cap`` the lists in which no news appears more often than that."""
     pool = torch.arange(1, dc.news_embedding.shape[0], dtype=torch.int64, device=dc.news_embedding.device)
     users = torch.arange(dc.history.shape[0], dtype=torch.int64)
-    if rerank is not None:
+    if exposure_cap is not None:
+        ids, _, count = util.recommend(model, dc, users, pool, k, batch_size=batch_size, exposure_cap=exposure_cap, shortlist=shortlist or None)
+    elif rerank is not None:
         ids, _, count = util.recommend(model, dc, users, pool, k, batch_size=batch_size, rerank=rerank, shortlist=shortlist or None,
                                        category=recommend_category(dc, max_per_category), max_per_category=max_per_category)
     elif sample is not None:
@@ -221,7 +225,8 @@ def main(argv=None):
                 util.calibration_category(None, getattr(dc, 'news_category', None))
             lines = recommend_lines(model, dc, config.recommend_k, config.batch_size * 16, diversity,
                                     getattr(config, 'recommend_shortlist', 0), cap, calibration,
-                                    getattr(config, 'recommend_sample', None), getattr(config, 'recommend_seed', 0), rerank)
+                                    getattr(config, 'recommend_sample', None), getattr(config, 'recommend_seed', 0), rerank,
+                                    getattr(config, 'recommend_exposure_cap', None))
             if config.recommend_output:
                 with open(config.recommend_output, 'w') as f:
                     f.write('\n'.join(lines))

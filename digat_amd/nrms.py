@@ -512,7 +512,7 @@ def user_vectors(model, dev, users, batch_size=1024):
 
 def recommend(model, dev, users, candidates=None, k=10, exclude_history=True, batch_size=1024, diversity=None, shortlist=None, category=None,
               max_per_category=0, calibration=None, calibration_target=None, alpha=0.01, index=None, refine=None, sample=None, seed=0,
-              streams=None, rerank=None):
+              streams=None, rerank=None, exposure_cap=None):
     """For every user, which k news, in order: ``(news_ids [G,k] int64, scores [G,k] float32, count [G] int32)`` on the model's
     device.  Order: score descending, equal scores in candidate order; slots at or beyond ``count[g]`` hold id -1 and score -inf.
 
@@ -550,7 +550,13 @@ def recommend(model, dev, users, candidates=None, k=10, exclude_history=True, ba
     at ``k' = shortlist or min(1024, 8 k)`` and ``util.rerank`` cuts every list to k over the plain news cache (the vectors
     ``diversity`` uses) towards the category mix of the history or ``calibration_target``; ``shortlist``, ``category``,
     ``max_per_category`` and ``alpha`` compose.  ``util.recommend`` has the details; ``rerank`` does not combine with
-    ``diversity``, ``calibration``, ``sample`` or ``index``."""
+    ``diversity``, ``calibration``, ``sample`` or ``index``.
+
+    ``exposure_cap`` (None: off, the call as it was, bit for bit): an int c >= 0 — no news in more than c lists of THIS call — or an
+    integer array [N] of capacities.  Retrieval runs once over all users at ``k' = shortlist or min(1024, 8 k)`` and
+    ``util.cap_exposure`` cuts the lists to k together (a stable assignment, not the one of largest total score; the cap holds per
+    call; a list whose shortlist runs out comes back short — name a deeper ``shortlist``).  ``util.recommend`` has the details;
+    ``exposure_cap`` does not combine with ``diversity``, ``calibration``, ``rerank``, ``sample``, ``max_per_category`` or ``index``."""
     from . import util
 
     def select(wide, long_lists):
@@ -570,7 +576,8 @@ def recommend(model, dev, users, candidates=None, k=10, exclude_history=True, ba
     plain = lambda: news_caches(model, dev.title_text, dev.title_mask, dev.augmented_title_text, dev.augmented_title_mask, 4 * batch_size)[0]
     return util.recommend_dispatch(select, plain, history, k, getattr(dev, "news_category", None), util.user_streams(users), diversity,
                                    shortlist, category, max_per_category, calibration, calibration_target, alpha, sample, seed, streams, rerank,
-                                   {"index": index, "refine": refine}, own_refusals)
+                                   {"index": index, "refine": refine}, own_refusals, exposure_cap=exposure_cap,
+                                   news_num=lambda: int(dev.title_text.shape[0]))
 
 
 def _retrieve(model, dev, users, candidates, k, exclude_history, batch_size, long_lists):

@@ -1187,6 +1187,58 @@ def shortlist_then_rerank(select: Callable, vectors: Callable, history: Callable
                            calibration != 0.0 or calibration_target is not None, history, calibration_target)
 
 
+# ---- the stage behind recommend(exposure_cap=): the one that works on the batch of lists (evaluate.capped_select_host) --------------
+def exposure_limits(k, exposure_cap, shortlist, pool) -> Tuple[int, int]:
+    """``(k, k')`` of an exposure-capped ``recommend``: the plain selection runs at ``k' = shortlist or min(1024, 8 k)`` and
+    ``cap_exposure`` cuts its lists to k.  ``exposure_cap``: an int >= 0 or an integer array / tensor [pool]."""
+    k, wide = _rerank_limits(k, shortlist, 8, evaluate.CAP_MAX_LIST)
+    if torch.is_tensor(exposure_cap):
+        if tuple(exposure_cap.shape) != (int(pool),) or exposure_cap.is_floating_point() or exposure_cap.dtype == torch.bool:
+            raise ValueError(f"exposure_cap must be an int >= 0 or an integer tensor [news = {int(pool)}], got {tuple(exposure_cap.shape)} "
+                             f"{exposure_cap.dtype}")
+    else:
+        evaluate.capped_caps_host(exposure_cap, pool)
+    return k, wide
+
+
+def exposure_refusals(exposure_cap, **others) -> None:
+    """What ``recommend(exposure_cap=)`` of either model refuses before anything is scored: ``exposure_cap`` beside a re-rank, a
+    draw, a cap per category or an index (``others``: the names and values of the arguments it does not combine with)."""
+    if exposure_cap is None:
+        return
+    named = [name for name, value in others.items() if value is not None and not (isinstance(value, int) and value == 0)]
+    if named:
+        raise ValueError(f"exposure_cap does not combine with {', '.join(named)}: it cuts the plain shortlists of the whole call")
+
+
+def cap_exposure(ids: torch.Tensor, scores: torch.Tensor, count, k: int, cap, pool: int, priority=None):
+    """The last stage of an exposure-capped ``recommend``: the lists ``(ids [G,M <= 1024], scores [G,M], count [G])`` of the plain
+    selection cut to k so that news ``id`` stays in at most ``cap[id]`` lists OF THIS CALL (``cap``: an int >= 0 for every news, or
+    an integer array [pool]; 0 blocks a news) — the list-optimal stable assignment of ``evaluate.capped_select_host``: a stable
+    assignment, not the one of largest total score.  ``priority`` [G,M] orders the lists that contend for a news (None: by score).
+    ``evaluate.capped_select`` on device tensors, ``evaluate.capped_select_host`` on CPU tensors, as ``diversify`` and ``calibrate``
+    do.  Returns ``(news_ids [G,k], scores [G,k], count [G], slots [G,k], rounds)``; a list whose shortlist runs out comes back with
+    fewer than k entries — the remedy is a deeper shortlist."""
+    if ids.dim() != 2 or tuple(scores.shape) != tuple(ids.shape):
+        raise ValueError(f"ids and scores must both be [G, M], got {tuple(ids.shape)} and {tuple(scores.shape)}")
+    pr = None if priority is None else _tensor_on(priority, ids.device).to(torch.float32)
+    if ids.is_cuda:
+        capv = cap.to(ids.device) if torch.is_tensor(cap) else cap
+        return evaluate.capped_select(ids, scores, count, k, capv, pool, pr)
+    host = lambda t: None if t is None else t.numpy()
+    capv = cap.numpy() if torch.is_tensor(cap) else cap
+    *arrays, rounds = evaluate.capped_select_host(host(ids), host(scores), host(count), k, capv, pool, host(pr))
+    return tuple(torch.from_numpy(x) for x in arrays) + (rounds,)
+
+
+def shortlist_then_cap(select: Callable, k, exposure_cap, pool, shortlist=None):
+    """The step behind ``recommend(exposure_cap=)`` of either model: ``select(k', long_lists)`` — the plain selection of ALL users
+    of the call at ``exposure_limits``' width, ``long_lists`` when ``k' > 128`` — then ``cap_exposure`` over those lists together.
+    Returns ``(shortlist triple, (news_ids, scores, count, slots, rounds))``."""
+    k, wide = exposure_limits(k, exposure_cap, shortlist, pool)
+    short = select(wide, wide > evaluate.TOPK_MAX_K)
+    return short, cap_exposure(*short, k, exposure_cap, pool)
+
 
 
 def sample_limits(k, sample, shortlist) -> Tuple[int, int, float]:
@@ -1458,7 +1510,7 @@ def recommend_report(model, dc: DeviceCorpus, users, candidates, k: int, diversi
 def recommend(model, dc: DeviceCorpus, users, candidates, k: int, exclude_history: bool = True, batch_size: int = 1024,
               max_rows: int = RECOMMEND_MAX_ROWS, diversity: Optional[float] = None, shortlist: Optional[int] = None, category=None,
               max_per_category: int = 0, calibration: Optional[float] = None, calibration_target=None, alpha: float = 0.01,
-              sample: Optional[float] = None, seed: int = 0, streams=None, rerank=None):
+              sample: Optional[float] = None, seed: int = 0, streams=None, rerank=None, exposure_cap=None):
     """For every user, which k news of its candidates, in order: ``(news_ids [G,k] int64, scores [G,k] float32, count [G] int32)``
     on the device.  Order: score descending, equal scores in candidate order (the rank file's order); ``count[g]`` is the number of
     valid slots of row g, the slots behind it hold id -1 and score -inf.
@@ -1502,27 +1554,43 @@ def recommend(model, dc: DeviceCorpus, users, candidates, k: int, exclude_histor
     and against what it does for the KL divergence towards the target mix — so the penalty sees every pick calibration makes, and
     calibration picks from the deep pool.  Both weights lie in [0, 1], their sum at most 1.  ``shortlist``, ``category``,
     ``max_per_category``, ``calibration_target`` and ``alpha`` mean what they mean above; ``rerank=(d, 0)`` is maximal marginal
-    relevance over up to 1024 entries.  ``rerank`` does not combine with ``diversity``, ``calibration`` or ``sample``."""
+    relevance over up to 1024 entries.  ``rerank`` does not combine with ``diversity``, ``calibration`` or ``sample``.
+
+    ``exposure_cap`` (None: off, the call as it was, bit for bit) bounds how often a news is shown ACROSS the lists of this call: an
+    int c >= 0 — no news in more than c lists — or an integer array [news_num] of capacities (0 blocks a news).  The selection above
+    runs ONCE over all users of the call at ``k' = shortlist or min(1024, 8 k)`` and ``cap_exposure`` sees every chunk's lists
+    together: each list keeps its best k entries among those whose news still has room for it, a contested news going to the lists
+    that score it highest, equal scores to the earlier user (``evaluate.capped_select_host``: the list-optimal stable assignment —
+    stable, not the assignment of largest total score).  The cap holds PER CALL: two calls know nothing of each other, so users
+    that should share one budget belong in one call.  A list whose shortlist runs out comes back with ``count < k``; the remedy is a
+    deeper ``shortlist``.  ``exposure_cap`` does not combine with ``diversity``, ``calibration``, ``rerank``, ``sample`` or
+    ``max_per_category``."""
     select = lambda wide, long_lists: recommend_lists(model, dc, users, candidates, wide, exclude_history, batch_size, max_rows, long_lists)
     return recommend_dispatch(select, lambda: unit_rows(dc.news_embedding), lambda: recommend_users(dc, users)[0], k,
                               getattr(dc, "news_category", None), user_streams(users), diversity, shortlist, category, max_per_category, calibration, calibration_target, alpha,
-                              sample, seed, streams, rerank)
+                              sample, seed, streams, rerank, exposure_cap=exposure_cap, news_num=lambda: int(dc.news_embedding.shape[0]))
 
 
 def recommend_dispatch(select: Callable, vectors: Callable, history: Callable, k, corpus_category, streams_default, diversity=None,
                        shortlist=None, category=None, max_per_category=0, calibration=None, calibration_target=None, alpha=0.01, sample=None,
-                       seed=0, streams=None, rerank=None, own_knobs=None, own_refusals: Optional[Callable] = None):
+                       seed=0, streams=None, rerank=None, own_knobs=None, own_refusals: Optional[Callable] = None, exposure_cap=None,
+                       news_num: Optional[Callable] = None):
     """The ladder behind ``recommend`` of either model — which knob runs which step, and every refusal, before anything is scored.
     ``select(k', long_lists)`` is the model's plain selection (the call without a knob is ``select(k, False)``), ``vectors()`` the
     rows a diversity term measures, ``history()`` the users' histories [G, H] padded with 0; the knobs are ``recommend``'s.
     ``own_knobs`` names the caller's further knobs that neither ``sample`` nor ``rerank`` combines with (``nrms``: index, refine),
-    ``own_refusals()`` raises what else the caller refuses, behind those two.  Returns ``recommend``'s triple."""
+    ``own_refusals()`` raises what else the caller refuses, behind those two.  ``exposure_cap`` (with ``news_num()``, the number of
+    news its capacities are counted over) combines with ``shortlist`` alone.  Returns ``recommend``'s triple."""
     own_knobs = own_knobs or {}
+    exposure_refusals(exposure_cap, diversity=diversity, calibration=calibration, calibration_target=calibration_target, rerank=rerank,
+                      sample=sample, category=category, max_per_category=max_per_category, **own_knobs)
     sample_refusals(sample, seed, streams, diversity=diversity, calibration=calibration, calibration_target=calibration_target,
                     category=category, max_per_category=max_per_category, **own_knobs, rerank=rerank)
     rerank_refusals(rerank, diversity=diversity, calibration=calibration, **own_knobs)
     if own_refusals is not None:
         own_refusals()
+    if exposure_cap is not None:
+        return shortlist_then_cap(select, k, exposure_cap, news_num(), shortlist)[1][:3]
     if rerank is not None:
         return shortlist_then_rerank(select, vectors, history, k, rerank, shortlist, category, max_per_category, corpus_category,
                                      calibration_target, alpha)[1][:3]

@@ -81,6 +81,13 @@
                                              device bytes; then plain, diversity=0.3, calibration=0.5 and rerank=(0.2, 0.4) on 512 held-out
                                              impressions of the planted-signal corpus: ild, kl, recall@10 and MRR with intervals, paired
                                              against plain
+  python tools/kbench.py exposure-cap [rounds demo]   exposure-capped top-k: evaluate.capped_select (prepare, one sort, blocks of rounds, emit)
+                                             against the same rounds in stock torch (argsort, sort, cumsum, gather, scatter), G = 64 and
+                                             4 096 lists of M = 128 and 1 024 of 65 237 news with a popularity head, k = 10 and 100, caps of
+                                             1.2 x and 2 x the mean exposure, the legs in turn, median [min, max] of five rounds, rounds and
+                                             peak device bytes; then plain and exposure_cap in {16, 4, 2} on 512 held-out impressions of the
+                                             planted-signal corpus: coverage, gini, largest exposure, short lists, recall@10 and MRR with
+                                             intervals, paired against plain
   python tools/kbench.py list-pl [d rounds demo]   policy gradient: evaluate.list_pl (fused Plackett-Luce slate likelihood over per-user lists and
                                              its closed-form gradient) against index_select + bmm + gather + logsumexp + flipped logcumsumexp
                                              under autograd, chunked to 1 GiB, (G, M, k, S) in {64, 4 096} x {128, 1 024} x {10, 100} x {1, 8},
@@ -2052,6 +2059,176 @@ def demo_calibrate(users=512, k=10, calibrations=(0.0, 0.3, 0.5, 0.8), replicate
         print(line, flush=True)
 
 
+def torch_topk_keys(x):
+    """``evaluate.topk_keys`` in stock PyTorch, int64."""
+    b = x.contiguous().view(torch.int32).to(torch.int64) & 0xffffffff
+    nan = (b & 0x7fffffff) > 0x7f800000
+    b = torch.where(b == 0x80000000, torch.zeros_like(b), b)
+    key = torch.where(b >= 0x80000000, 0xffffffff - b, b | 0x80000000)
+    return torch.where(nan, torch.ones_like(key), key)
+
+
+def torch_capped(ids, scores, count, k, caps, P, max_rounds=1024):
+    """Exposure-capped top-k built only from stock PyTorch — the rounds of ``evaluate.capped_select_host`` as they stand there: one
+    stable argsort per list, one stable sort of the item words, then per round a cumsum over the lists, a gather into item order, a
+    segmented cumsum, a scatter of the new rejections and one read of how many there were.  The same contract, bit for bit."""
+    G, M = ids.shape
+    dev = ids.device
+    ks = torch_topk_keys(scores)
+    elem = (torch.arange(M, device=dev)[None, :] < count.to(torch.int64).clamp(0, M)[:, None]) & (ids >= 0) & (ids < P) & (ks > 0x007fffff)
+    order = torch.argsort(-torch.where(elem, ks, -torch.ones_like(ks)), dim=1, stable=True)
+    words = torch.where(elem, (torch.where(elem, ids, torch.zeros_like(ids)) << 32) | (0xffffffff - ks),
+                        torch.full_like(ids, 0x7fffffffffffffff)).view(-1)
+    words, perm = torch.sort(words, stable=True)
+    sid = words >> 32
+    at = torch.arange(G * M, device=dev)
+    start = torch.cummax(torch.where(torch.cat([sid[:1] == sid[:1], sid[1:] != sid[:-1]]), at, torch.zeros_like(at)), dim=0).values
+    cap_of = caps.to(torch.int64)[sid.clamp(max=max(P - 1, 0))] if P else torch.zeros_like(sid)
+    rejected = ~elem.view(-1)
+    rounds = 0
+    while True:
+        if rounds == max_rounds:
+            raise RuntimeError("torch_capped: no fixed point")
+        rounds += 1
+        alive = ~rejected.view(G, M).gather(1, order)
+        ahead = alive.cumsum(dim=1)
+        wanted = alive & (ahead <= k)
+        demand = torch.zeros((G, M), dtype=torch.bool, device=dev).scatter_(1, order, wanted)
+        d = demand.view(-1)[perm].to(torch.int64)
+        before = d.cumsum(dim=0) - d
+        before = before - before[start]
+        gone = rejected[perm]
+        new = (before >= cap_of) & ~gone
+        if int(new.sum()) == 0:
+            break
+        rejected = rejected.scatter(0, perm, gone | new)
+    out_i = torch.full((G * k,), -1, dtype=torch.int64, device=dev)
+    out_s = torch.full((G * k,), float("-inf"), device=dev)
+    out_p = torch.full((G * k,), -1, dtype=torch.int32, device=dev)
+    to = (torch.arange(G, device=dev)[:, None] * k + ahead - 1)[wanted]
+    out_i[to] = ids.gather(1, order)[wanted]
+    out_s[to] = scores.gather(1, order)[wanted]
+    out_p[to] = order[wanted].to(torch.int32)
+    return out_i.view(G, k), out_s.view(G, k), wanted.sum(dim=1).to(torch.int32), out_p.view(G, k), rounds
+
+
+def popular_lists(G, M, P, generator, dev, slab=256):
+    """``(ids [G,M] int64, scores [G,M] float32)`` on ``dev``: per list M distinct news of P drawn with a strong popularity head
+    (Gumbel top-M over ``-1.2 log(rank)``), scored by that popularity plus unit noise, on a grid of 1/64 — exact ties are met —, each
+    list sorted by score as a shortlist comes."""
+    weight = -1.2 * torch.log(torch.arange(1, P + 1, dtype=torch.float32, device=dev))
+    ids, scores = [], []
+    for g0 in range(0, G, slab):
+        n = min(slab, G - g0)
+        u = torch.rand((n, P), generator=generator).to(dev).clamp_(1e-9, 1 - 1e-9)
+        pick = (weight[None, :] - torch.log(-torch.log(u))).topk(M, dim=1).indices
+        s = torch.round((0.7 * weight[pick] + torch.randn((n, M), generator=generator).to(dev)) * 64) / 64
+        s, o = s.sort(dim=1, descending=True, stable=True)
+        ids.append(pick.gather(1, o))
+        scores.append(s)
+    return torch.cat(ids), torch.cat(scores)
+
+
+def bench_exposure_cap(rounds=5, demo=1):
+    """``evaluate.capped_select`` against ``torch_capped`` — the same rounds in stock PyTorch —, the two legs in turn in one process,
+    median [min, max] of ``rounds`` rounds, each leg's peak of device bytes beyond its inputs and the rounds the call took: G in
+    {64, 4 096} lists of M in {128, 1 024} of 65 237 news with a popularity head (``popular_lists``), k in {10, 100}, a cap of 1.2 x
+    and 2 x the mean exposure G k / P (rounded up, at least 1).  Both legs read their counters back every block / round: the times
+    are whole calls.  Then (``demo``) the effect on the planted-signal corpus (``demo_exposure_cap``)."""
+    from digat_amd import evaluate
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device="cpu").manual_seed(0)
+    P = 65237
+
+    def peak(fn):
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        out = fn()
+        torch.cuda.synchronize()
+        return out, torch.cuda.max_memory_allocated() - base
+    print(f"exposure-cap: lists of distinct ids of {P} news with a popularity head; ms per call, median [min, max] of {rounds} rounds", flush=True)
+    for G in (64, 4096):
+        for M in (128, 1024):
+            ids, scores = popular_lists(G, M, P, g, dev)
+            count = torch.full((G,), M, dtype=torch.int32, device=dev)
+            for k in (10, 100):
+                for factor in (1.2, 2.0):
+                    cap = max(1, int(np.ceil(factor * G * k / P)))
+                    caps = torch.full((P,), cap, dtype=torch.int32, device=dev)
+                    ours = lambda: evaluate.capped_select(ids, scores, count, k, caps, P)
+                    stock = lambda: torch_capped(ids, scores, count, k, caps, P)
+                    (got, pa), (want, pb) = peak(ours), peak(stock)
+                    same = all(torch.equal(x, y) for x, y in zip(got[:4], want[:4])) and got[4] == want[4]
+                    short = float((got[2] < k).float().mean())
+                    top = int(torch.bincount(got[0][got[0] >= 0].view(-1), minlength=P).max())
+                    (a, alo, ahi), (b, blo, bhi) = alternate(ours, stock, rounds=rounds, iters=3)
+                    print(f"  G = {G:5d}, M = {M:4d}, k = {k:3d}, cap = {cap:3d} ({factor} x mean): capped_select {a:8.3f} ms [{alo:.3f}, {ahi:.3f}] "
+                          f"({got[4]} rounds, peak {pa / 2**20:.1f} MiB) | stock rounds {b:8.3f} ms [{blo:.3f}, {bhi:.3f}] (x{b / a:.2f}, peak "
+                          f"{pb / 2**20:.1f} MiB) | identical: {same} | largest exposure {top}, short lists {short:.3f}", flush=True)
+            del ids, scores, count
+    torch.cuda.empty_cache()
+    if demo:
+        demo_exposure_cap()
+
+
+def demo_exposure_cap(users=512, k=10, caps=(16, 4, 2), shortlist=128, replicates=2000):
+    """What ``recommend(exposure_cap=)`` does on the planted-signal corpus, in ``recommend_report``'s setting: the trained DIGAT
+    (tests/golden/trained_planted_state.npz), ``users`` held-out impressions against the pool of all news in ONE call, k = 10, the
+    plain call and one call per value of ``caps`` from a shortlist of ``shortlist``.  Per call: ``coverage`` and ``gini`` of the
+    exposure over the pool (``evaluate.quality_summary``; figures of the whole batch: no interval), the largest exposure, the share
+    of lists shorter than k, and recall@k of the impression's clicked candidates (summed hits over summed clicks) and MRR as means
+    with 95 % intervals (``evaluate.metric_intervals``, users resampled) and, against the plain call, the paired difference
+    (``evaluate.compare_metrics``)."""
+    import types
+    from digat_amd import evaluate, synthetic, util
+    from digat_amd.main import clicked_targets
+    from digat_amd.model import Model, PrecomputedNewsEncoder
+    dev = torch.device("cuda:0")
+    golden = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
+    state = {name: v for name, v in np.load(os.path.join(golden, "trained_planted_state.npz")).items()}
+    depth = int(np.load(os.path.join(golden, "devset_trained_2k.npz"))["depth"])
+    full = synthetic.make_corpus(synthetic.SynthSpec(**synthetic.PLANTED_SPEC))
+    corpus = synthetic.slice_impressions(full, 0, users)
+    spec = full.spec
+    cfg = types.SimpleNamespace(news_encoder="MSA", graph_encoder="DIGAT", news_graph_size=spec.news_graph_size,
+                                max_history_num=spec.max_history_num, category_num=spec.category_num, graph_depth=depth, dropout_rate=0.2)
+    model = Model(cfg, news_encoder=PrecomputedNewsEncoder(torch.from_numpy(corpus.news_embedding)))
+    model.graph_encoder.load_state_dict({name: torch.from_numpy(v) for name, v in state.items()})
+    model = model.to(dev).eval()
+    dc = util.DeviceCorpus.from_numpy(corpus, dev)
+    who = np.arange(users, dtype=np.int64)
+    pool = np.arange(1, spec.news_num, dtype=np.int64)
+    tg_ids, tg_start = clicked_targets(dc, corpus.row_label)
+    names = (f"recall@{k}", "mrr")
+
+    def columns(cap):
+        kw = {} if cap is None else dict(exposure_cap=cap, shortlist=shortlist)
+        ids, scores, count = util.recommend(model, dc, who, pool, k, **kw)
+        exposure = torch.zeros((spec.news_num,), dtype=torch.int32, device=dev)
+        q = evaluate.quality_summary(evaluate.list_quality(ids, count, exposure=exposure), exposure, pool)
+        col = evaluate.rank_metric_columns(evaluate.list_ranks(ids, count, tg_ids, tg_start), tg_start, ks=(k,))
+        batch = (q["coverage"], q["gini"], int(exposure.max()), float((count < k).float().mean()))
+        return np.stack([col[f"hits@{k}"], col["rr"]], axis=1), np.stack([col["targets"], col["has"]], axis=1), batch
+    print(f"exposure-cap demo: planted-signal corpus, {spec.news_num - 1} news, the trained DIGAT, {users} held-out impressions in one call, "
+          f"k = {k} (mean exposure {users * k / (spec.news_num - 1):.2f}), shortlist {shortlist}; recall and MRR: means with 95 % intervals "
+          f"from {replicates} replicates over users; 'vs plain': paired difference", flush=True)
+    base = None
+    for cap in (None,) + tuple(caps):
+        values, den, (coverage, gini, top, short) = columns(cap)
+        iv = evaluate.metric_intervals(values, names=names, replicates=replicates, denominators=den)
+        line = (f"  {'plain' if cap is None else 'cap %3d' % cap}: coverage {coverage:.4f}  gini {gini:.4f}  largest exposure {top}  short lists "
+                f"{short:.4f}  " + "  ".join(f"{name} {iv[name]['value']:.4f} [{iv[name]['lo']:.4f}, {iv[name]['hi']:.4f}]" for name in names))
+        if base is None:
+            base = (values, den)
+        else:
+            cmp = evaluate.compare_metrics(values, base[0], names=names, replicates=replicates, denominators_a=den, denominators_b=base[1])
+            line += " | vs plain: " + "  ".join(f"{name} {cmp[name]['diff']:+.4f} [{cmp[name]['lo']:+.4f}, {cmp[name]['hi']:+.4f}] p {cmp[name]['p']:.3f}"
+                                                for name in names)
+        print(line, flush=True)
+
+
 def torch_rerank(ids, scores, count, vectors, category, target, k, w, alpha=0.01, lazy=False, budget=1 << 30):
     """The joint re-rank built only from stock PyTorch, over chunks of lists that keep a leg's largest tensors within ``budget``
     bytes.  ``lazy`` False: gather + ``torch.bmm`` Gram [g, M, M], then k rounds of element-wise operations with ``torch.log`` in
@@ -3077,6 +3254,8 @@ if __name__ == "__main__":
         bench_calibrate(*nums)
     elif what == "rerank":
         bench_rerank(*nums)
+    elif what == "exposure-cap":
+        bench_exposure_cap(*nums)
     elif what == "pl-sample":
         bench_pl_sample(*nums)
     elif what == "off-policy":
